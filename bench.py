@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the RNA-MPNN forward hot path on MI355X (contract: see the task brief).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps, and prints one JSON line (``value``, ``ms_per_step`` = milliseconds
+of one timed step, ...).  ``--full`` adds every other measurement and check (the extra objects listed below).
+``--dump-outputs DIR`` writes what the timed path returned in its last step: the logits as ``DIR/logits.npy`` (float32,
+B x T x 4, zero on padded rows; ``DIR/logits_rank<r>.npy`` per rank at N > 1).  The inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.
 
 A "step" is one pass of ``RNAMPNN.forward`` over one batch of synthetic k-NN RNA graphs that is already
 resident in HBM.
@@ -26,7 +32,8 @@ Launch: with ``--gpus N > 1`` and no RANK in the environment this script spawns 
 the GPU); under an external ``torch.distributed.run`` it reads RANK / LOCAL_RANK / WORLD_SIZE and checks
 WORLD_SIZE == --gpus.  One process per GPU, RCCL ("nccl") for the collectives.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line of a ``--full`` run (the ``--cpu-sample``, ``--train-*`` and ``--recovery-steps`` options shape
+them; a plain run has none of them and leaves the timed launches unprofiled):
   roofline     - the dominant kernel (fused ResMPNN edge kernel): algorithmic HBM bytes per launch / its mean launch
                  duration, timed live with HIP events on the launch stream (rnampnn_profile_*), vs 8 TB/s.
   cpu_baseline - the CPU oracle (a port of the reference's PyTorch-CPU path, kind "port") timed on this box's host
@@ -36,8 +43,10 @@ Extra objects on the JSON line:
                  no host syncs) over seeded synthetic RNAs of exactly the 2,083 lengths of the reference's
                  data/train_data.csv (tests/data/c3_train_lengths.npy: 1 ... 4,417 nt, 1,205,038 nt, P = 4,500): epoch
                  seconds, end-to-end nt/s, and the same batch plan with resident inputs (kernel-only) beside it.
+  mfma         - model / executed FLOPs per nucleotide and the matrix-pipe rates they give.
   recovery     - closed-form weights (flat logits: chance) AND weights trained here for ``--recovery-steps`` seeded steps
                  (bf16-mixed, dropout 0.4) so the logits separate: f32 CPU oracle vs bf16 HIP on the CPU sample.
+  weak_c2      - N > 1 only (see above).
 """
 from __future__ import annotations
 
@@ -58,6 +67,7 @@ MFMA_BF16_PEAK_TFLOPS = 2500.0 # dense bf16 MFMA peak
 MFMA_F32_PEAK_TFLOPS = 157.3
 C4_RNAS, C4_LEN = 10000, 200
 C4_MICRO = int(os.environ.get("RNAMPNN_C4_MICRO", "2500"))      # RNAs per forward of a rank's share (tuning knob)
+DUMP_MAX_BYTES = 60 * 10 ** 6  # --dump-outputs: the arrays of all ranks together; with .npy headers and sample row numbers < 64 MB
 
 
 def parse(argv=None):
@@ -69,17 +79,26 @@ def parse(argv=None):
     ap.add_argument("--precision", default=os.environ.get("RNAMPNN_BENCH_PRECISION", "bf16"), choices=["bf16", "f32"])
     ap.add_argument("--batch", type=int, default=0, help="c2: RNAs per step per rank; c4: total RNAs of the job")
     ap.add_argument("--neighbours", type=int, default=30)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    # the options of the extra legs take effect with --full only
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and the trained-weights recovery")
     ap.add_argument("--cpu-sample", type=int, default=16)
-    ap.add_argument("--train-steps", type=int, default=-1, help="training-step leg (default: 5 at N > 1, 0 at N = 1)")
-    ap.add_argument("--train-epoch", type=int, default=-1, help="config-3 epoch leg: 1 on, 0 off (default: on at N = 1 with the default workload)")
-    ap.add_argument("--recovery-steps", type=int, default=-1, help="training steps before the trained-weights recovery check (default 300 at N = 1; 0 = off)")
-    ap.add_argument("--train-batch", type=int, default=64, help="RNAs per rank per training step")
+    ap.add_argument("--train-steps", type=int, default=-1, help="training-step leg of --full (default: 5 at N > 1, 0 at N = 1)")
+    ap.add_argument("--train-epoch", type=int, default=-1, help="config-3 epoch leg of --full: 1 on, 0 off (default: on at N = 1 with the default workload)")
+    ap.add_argument("--recovery-steps", type=int, default=-1, help="training steps before the trained-weights recovery check of --full (default 300 at N = 1; 0 = off)")
+    ap.add_argument("--train-batch", type=int, default=64, help="RNAs per rank per training step (--full)")
     ap.add_argument("--no-build", action="store_true",
                     help="load the prebuilt library only (required under rocprofv3: a hipcc child of a profiled process is a forbidden exec hop)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / reduction plumbing only: no model, no kernels, no GPU (CPU test of the N > 1 path)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every extra leg: roofline and MFMA figures (profiled timed launches), recovery checks, CPU baseline, "
+                         "trained-weights recovery, config-3 epoch, and at N > 1 the training-step and weak-scaling legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits of the last timed step as DIR/logits.npy (float32; DIR/logits_rank<r>.npy per rank at N > 1)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port() -> int:
@@ -204,13 +223,11 @@ def main():
     dev_batches = [(torch.from_numpy(c).to(dev), torch.from_numpy(m).to(dev), torch.from_numpy(y).to(dev)) for c, m, y in batches]
 
     def run_forward(batch_list, steps, warmup, profile):
-        """W untimed + K timed passes over the resident batches -> (elapsed seconds of this rank, last logits, timed fused launches by kind)."""
+        """W untimed + K timed passes over the resident batches -> (elapsed seconds of this rank, logits of every micro-batch of the
+        last pass, timed fused launches by kind)."""
         def one():
-            o = None
-            for c, m, _ in batch_list:
-                o = model(c, m) if model is not None else None
-            return o
-        o = None
+            return [model(c, m) for c, m, _ in batch_list] if model is not None else []
+        o = []
         for _ in range(warmup):
             o = one()
         if model is not None and profile:
@@ -228,13 +245,17 @@ def main():
             model.profile_enable(False)
         return el, o, km, nl
 
-    elapsed, logits, prof_em, prof_first = run_forward(dev_batches, args.steps, args.warmup, True)
+    elapsed, outs, prof_em, prof_first = run_forward(dev_batches, args.steps, args.warmup, args.full)
+    logits = outs[-1] if outs else None
     t_max, nt_total = shard.reduce_job(elapsed, float(nt_rank), red_dev)
     value = nt_total * args.steps / t_max
+    if args.dump_outputs:
+        dump_outputs(outs, args.dump_outputs, rank, world)
+    del outs
 
     # N > 1: the N = 1 workload on every rank (weak scaling), directly comparable with this script's N = 1 line
     weak = None
-    if world > 1 and args.workload == "c4":
+    if args.full and world > 1 and args.workload == "c4":
         wargs = argparse.Namespace(**vars(args))
         wargs.workload, wargs.batch = "c2", 0
         wname, wb, wlens, _ = build_workload(wargs, rank, world)
@@ -255,71 +276,16 @@ def main():
         del w_dev, wmodel
 
     rec_gpu = None
-    if model is not None:       # recovery of the GPU path on its last micro-batch (synthetic labels, closed-form weights)
+    if args.full and model is not None:       # recovery of the GPU path on its last micro-batch (synthetic labels, closed-form weights)
         _, correct, nvalid = argmax_recovery(logits, dev_batches[-1][1], dev_batches[-1][2])
         rec_gpu = float(correct.sum()) / float(nvalid.sum())
 
     train = None
     n_train = args.train_steps if args.train_steps >= 0 else (5 if world > 1 else 0)
-    if n_train > 0:
+    if args.full and n_train > 0:
         train = train_leg(args, model, dev_batches, n_train, world, dev, red_dev, barrier, dry)
 
     if rank == 0:
-        n_mean = float(lens.mean())
-        w = 2 if args.precision == "bf16" else 4
-        # Roofline of the dominant kernel = the <edge update of layer l, message of layer l + 1> launch of the fused ResMPNN kernel (L - 1 = 9 per
-        # forward), timed live with HIP events on the launch stream, separately from the message-only launch of layer 1.
-        #   achieved = SURVEY section 8(d)'s algorithmic bytes of one ResMPNN layer per nucleotide - e read + write 2 k 128 w, h read / write 4 * 128 w,
-        #   neighbour index 2 * 4 k (16,624 B at k = 30, w = 2) - x the nucleotides of a launch / the launch's duration.
-        #   kernel_bytes_per_nt = what THIS kernel moves per nucleotide at its stored widths: e read + write (f16), index once, its own P rows of both
-        #   MLPs (f16), the gathered Q rows counted once per table row (f16, L2-resident), the residue's h (f32) and the h + mean row it writes (f32).
-        L = 10
-        survey_bytes_nt = k * (2 * 128 * w + 2 * 4) + 4 * 128 * w
-        kernel_bytes_nt = k * (2 * 128 * w + 4) + 4 * 128 * 2 + 2 * 128 * 4
-        # layer 1: message only - one P and one Q table; e0 is WRITTEN once by the same launch when the edge embedding is fused into it (k > 16,
-        # default; + the residue's 256-byte geometry record), READ once in the two-launch form (RNAMPNN_EMBED_FUSED=0)
-        embed_fused = args.precision == "bf16" and k > 16 and os.environ.get("RNAMPNN_EMBED_FUSED") != "0" and os.environ.get("RNAMPNN_MPNN_V3") != "1"
-        first_bytes_nt = k * (128 * w + 4) + 2 * 128 * 2 + 2 * 128 * 4 + (256 if embed_fused else 0)
-        first_name = ("edge embedding + message launch of layer 1 (k_resmpnn<false, true, true>)" if embed_fused
-                      else "message-only launch of layer 1 (k_resmpnn<false, true>)")
-        (ms_em, n_em), (ms_first, n_first) = prof_em, prof_first
-        launch_ms = ms_em / max(n_em, 1)
-        first_ms = ms_first / max(n_first, 1)
-        nt_call = nt_rank / len(batches)                                    # nucleotides one launch works on
-        measured_cfg = args.workload == "c2" and args.precision == "bf16" and k == 30 and not args.batch and world == 1
-        traffic, traffic_src, first_traffic = None, None, None   # HBM bytes per launch from PMC counters, when a profile of this workload is committed
-        for cand in ("r04_pmc_traffic.json", "r03_pmc_traffic.json"):
-            try:
-                prof = json.load(open(os.path.join(REPO, "profiles", cand)))
-                if measured_cfg:
-                    traffic, traffic_src = prof["traffic_bytes_per_launch"], cand
-                    first_traffic = prof.get("first_launch_embed_fused", {}).get("traffic_bytes_per_launch")
-                break
-            except Exception:
-                continue
-        achieved_gbs = survey_bytes_nt * nt_call / (launch_ms * 1e-3) / 1e9 if n_em else 0.0
-        exec_flops_nt = flops_per_nt(k, n_mean, factored=True)
-        model_flops_nt = flops_per_nt(k, n_mean)
-        per_rank_rate = nt_rank * args.steps / elapsed
-        # matrix-pipe share of the same launch: one 32-slot block per residue (k > 16), 128 v_mfma_f32_32x32x16 per block (160 in the round-3
-        # kernel, RNAMPNN_MPNN_V3=1: 32 helper MFMAs), 32,768 FLOP each; useful = the k real edge slots of the 32
-        mfma_per_block = 160 if os.environ.get("RNAMPNN_MPNN_V3") == "1" else 128
-        peak_tf = MFMA_BF16_PEAK_TFLOPS if args.precision == "bf16" else MFMA_F32_PEAK_TFLOPS
-        issued_tf = nt_call * mfma_per_block * 32768 / (launch_ms * 1e-3) / 1e12 if (n_em and args.precision == "bf16" and k > 16) else None
-        roof = {"bound": "hbm", "kernel": "fused ResMPNN kernel, <edge update, message> launch (k_resmpnn<true, true>)",
-                "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic,
-                "launch_ms": launch_ms, "launches_timed": n_em,
-                "algorithmic_bytes_per_nt_per_launch": survey_bytes_nt, "kernel_bytes_per_nt": kernel_bytes_nt,
-                "nucleotides_per_launch": nt_call,
-                "mfma_issued_frac": issued_tf / peak_tf if issued_tf else None,
-                "mfma_useful_frac": issued_tf * min(k, 32) / 32 * 128 / mfma_per_block / peak_tf if issued_tf else None,
-                "first_launch": {"kernel": first_name, "launch_ms": first_ms, "launches_timed": n_first,
-                                 "algorithmic_bytes_per_nt": first_bytes_nt,
-                                 "achieved": first_bytes_nt * nt_call / (first_ms * 1e-3) / 1e9 if n_first else None,
-                                 "traffic": first_traffic if embed_fused else None}}
-        if measured_cfg and traffic_src:    # measured on exactly this configuration (profiles/)
-            roof["traffic_note"] = f"bytes per launch, rocprofv3 FETCH_SIZE x2 (gfx950 correction) + WRITE_SIZE, profiles/{traffic_src}"
         out = {
             "metric": "nucleotides/sec (forward), k=30 RNA graphs",
             "value": value, "unit": "nucleotides/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -327,26 +293,23 @@ def main():
             "vs_baseline": None, "dtype": args.precision, "data": "synthetic" if not dry else "dry-run: no kernels launched (launcher test)",
             "config": {"workload": name, "max_len": T, "nucleotides_per_step_per_gpu": nt_rank,
                        "weights": "closed-form deterministic init (3,536,900 params)", "parallelism": f"dp{world}"},
-            "roofline": roof,
-            "mfma": {"model_flops_per_nt": model_flops_nt, "executed_flops_per_nt": exec_flops_nt,
-                     "model_tflops": model_flops_nt * per_rank_rate / 1e12,
-                     "executed_tflops": exec_flops_nt * per_rank_rate / 1e12,
-                     "peak_tflops": MFMA_BF16_PEAK_TFLOPS if args.precision == "bf16" else MFMA_F32_PEAK_TFLOPS},
-            "recovery": {"gpu_micro": rec_gpu},
         }
+        if args.full:
+            out["roofline"], out["mfma"] = roofline_legs(args, k, lens, nt_rank, len(batches), world, elapsed, prof_em, prof_first)
+            out["recovery"] = {"gpu_micro": rec_gpu}
         if train is not None:
             out["train"] = train
         if weak is not None:
             out["weak_c2"] = weak
         default_cfg = args.workload == "c2" and not args.batch and k == 30
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dry:
             c0, m0, y0 = batches[0]
             out["cpu_baseline"] = cpu_baseline(args, hp, sd, c0, m0, y0, lens, logits, out)
             n_rec = args.recovery_steps if args.recovery_steps >= 0 else (300 if default_cfg and args.precision == "bf16" else 0)
             if n_rec > 0:
                 out["recovery"]["trained"] = guarded(lambda: trained_recovery(args, hp, sd, c0, m0, y0, lens, dev, n_rec))
         want_epoch = args.train_epoch if args.train_epoch >= 0 else int(world == 1 and default_cfg and not dry and args.precision == "bf16")
-        if world == 1 and want_epoch and not dry:
+        if args.full and world == 1 and want_epoch and not dry:
             del dev_batches[:]
             out["train_epoch"] = guarded(lambda: train_epoch_leg(args, dev))
         print(json.dumps(out), flush=True)
@@ -354,6 +317,90 @@ def main():
         import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
+
+
+def roofline_legs(args, k, lens, nt_rank, n_batches, world, elapsed, prof_em, prof_first):
+    """--full: -> (roofline, mfma) objects of the JSON line from the fused launches profiled inside the timed region."""
+    n_mean = float(lens.mean())
+    w = 2 if args.precision == "bf16" else 4
+    # Roofline of the dominant kernel = the <edge update of layer l, message of layer l + 1> launch of the fused ResMPNN kernel (L - 1 = 9 per
+    # forward), timed live with HIP events on the launch stream, separately from the message-only launch of layer 1.
+    #   achieved = SURVEY section 8(d)'s algorithmic bytes of one ResMPNN layer per nucleotide - e read + write 2 k 128 w, h read / write 4 * 128 w,
+    #   neighbour index 2 * 4 k (16,624 B at k = 30, w = 2) - x the nucleotides of a launch / the launch's duration.
+    #   kernel_bytes_per_nt = what THIS kernel moves per nucleotide at its stored widths: e read + write (f16), index once, its own P rows of both
+    #   MLPs (f16), the gathered Q rows counted once per table row (f16, L2-resident), the residue's h (f32) and the h + mean row it writes (f32).
+    L = 10
+    survey_bytes_nt = k * (2 * 128 * w + 2 * 4) + 4 * 128 * w
+    kernel_bytes_nt = k * (2 * 128 * w + 4) + 4 * 128 * 2 + 2 * 128 * 4
+    # layer 1: message only - one P and one Q table; e0 is WRITTEN once by the same launch when the edge embedding is fused into it (k > 16,
+    # default; + the residue's 256-byte geometry record), READ once in the two-launch form (RNAMPNN_EMBED_FUSED=0)
+    embed_fused = args.precision == "bf16" and k > 16 and os.environ.get("RNAMPNN_EMBED_FUSED") != "0" and os.environ.get("RNAMPNN_MPNN_V3") != "1"
+    first_bytes_nt = k * (128 * w + 4) + 2 * 128 * 2 + 2 * 128 * 4 + (256 if embed_fused else 0)
+    first_name = ("edge embedding + message launch of layer 1 (k_resmpnn<false, true, true>)" if embed_fused
+                  else "message-only launch of layer 1 (k_resmpnn<false, true>)")
+    (ms_em, n_em), (ms_first, n_first) = prof_em, prof_first
+    launch_ms = ms_em / max(n_em, 1)
+    first_ms = ms_first / max(n_first, 1)
+    nt_call = nt_rank / n_batches                                        # nucleotides one launch works on
+    measured_cfg = args.workload == "c2" and args.precision == "bf16" and k == 30 and not args.batch and world == 1
+    traffic, traffic_src, first_traffic = None, None, None   # HBM bytes per launch from PMC counters, when a profile of this workload is committed
+    for cand in ("r04_pmc_traffic.json", "r03_pmc_traffic.json"):
+        try:
+            prof = json.load(open(os.path.join(REPO, "profiles", cand)))
+            if measured_cfg:
+                traffic, traffic_src = prof["traffic_bytes_per_launch"], cand
+                first_traffic = prof.get("first_launch_embed_fused", {}).get("traffic_bytes_per_launch")
+            break
+        except Exception:
+            continue
+    achieved_gbs = survey_bytes_nt * nt_call / (launch_ms * 1e-3) / 1e9 if n_em else 0.0
+    exec_flops_nt = flops_per_nt(k, n_mean, factored=True)
+    model_flops_nt = flops_per_nt(k, n_mean)
+    per_rank_rate = nt_rank * args.steps / elapsed
+    # matrix-pipe share of the same launch: one 32-slot block per residue (k > 16), 128 v_mfma_f32_32x32x16 per block (160 in the round-3
+    # kernel, RNAMPNN_MPNN_V3=1: 32 helper MFMAs), 32,768 FLOP each; useful = the k real edge slots of the 32
+    mfma_per_block = 160 if os.environ.get("RNAMPNN_MPNN_V3") == "1" else 128
+    peak_tf = MFMA_BF16_PEAK_TFLOPS if args.precision == "bf16" else MFMA_F32_PEAK_TFLOPS
+    issued_tf = nt_call * mfma_per_block * 32768 / (launch_ms * 1e-3) / 1e12 if (n_em and args.precision == "bf16" and k > 16) else None
+    roof = {"bound": "hbm", "kernel": "fused ResMPNN kernel, <edge update, message> launch (k_resmpnn<true, true>)",
+            "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic,
+            "launch_ms": launch_ms, "launches_timed": n_em,
+            "algorithmic_bytes_per_nt_per_launch": survey_bytes_nt, "kernel_bytes_per_nt": kernel_bytes_nt,
+            "nucleotides_per_launch": nt_call,
+            "mfma_issued_frac": issued_tf / peak_tf if issued_tf else None,
+            "mfma_useful_frac": issued_tf * min(k, 32) / 32 * 128 / mfma_per_block / peak_tf if issued_tf else None,
+            "first_launch": {"kernel": first_name, "launch_ms": first_ms, "launches_timed": n_first,
+                             "algorithmic_bytes_per_nt": first_bytes_nt,
+                             "achieved": first_bytes_nt * nt_call / (first_ms * 1e-3) / 1e9 if n_first else None,
+                             "traffic": first_traffic if embed_fused else None}}
+    if measured_cfg and traffic_src:    # measured on exactly this configuration (profiles/, DESIGN.md section 4)
+        roof["traffic_note"] = f"bytes per launch, rocprofv3 FETCH_SIZE x2 (gfx950 correction) + WRITE_SIZE, profiles/{traffic_src}"
+    mfma = {"model_flops_per_nt": model_flops_nt, "executed_flops_per_nt": exec_flops_nt,
+            "model_tflops": model_flops_nt * per_rank_rate / 1e12,
+            "executed_tflops": exec_flops_nt * per_rank_rate / 1e12,
+            "peak_tflops": MFMA_BF16_PEAK_TFLOPS if args.precision == "bf16" else MFMA_F32_PEAK_TFLOPS}
+    return roof, mfma
+
+
+def dump_outputs(outs, directory, rank, world):
+    """--dump-outputs: the logits of every micro-batch of this rank's last timed step, in order, as one float32 array (B, T, 4) in
+    ``directory/logits.npy`` (``logits_rank<r>.npy`` at N > 1).  The files of all ranks stay within DUMP_MAX_BYTES: a larger array is
+    replaced by a fixed seeded sample of its RNAs, whose row numbers are written beside it as ``<name>_rows.npy`` (float64)."""
+    import numpy as np
+    if not outs:
+        print("bench.py: --dump-outputs: no outputs (dry run), nothing written", file=sys.stderr)
+        return
+    name = "logits" if world == 1 else f"logits_rank{rank}"
+    arr = np.concatenate([o.detach().float().cpu().numpy() for o in outs])
+    budget = DUMP_MAX_BYTES // world
+    os.makedirs(directory, exist_ok=True)
+    if arr.nbytes > budget:
+        n = max(1, budget // (arr.nbytes // arr.shape[0]))
+        rows = np.sort(np.random.default_rng(0).choice(arr.shape[0], n, replace=False))
+        np.save(os.path.join(directory, name + "_rows.npy"), rows.astype(np.float64))
+        arr = arr[rows]
+    np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
 
 
 def guarded(fn):

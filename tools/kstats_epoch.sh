@@ -4,7 +4,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/$1; shift; mkdir -p $OUT
 python3 $ROOT/__graft_entry__.py || exit 1
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $ROOT/bench.py --no-build --steps 1 --warmup 0 --no-cpu-baseline --recovery-steps 0 --train-epoch 1 > $OUT/run.log 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $ROOT/bench.py --no-build --full --steps 1 --warmup 0 --no-cpu-baseline --recovery-steps 0 --train-epoch 1 > $OUT/run.log 2>&1
 python3 - <<PY
 import csv, glob
 f = sorted(glob.glob("$OUT/*/*kernel_stats.csv"))[-1]

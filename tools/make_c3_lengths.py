@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Build tests/data/c3_train_lengths.npy: the sequence lengths (an int32 array, DATA only) of the 2,083 ids of the reference's
 data/train_data.csv, in file order - the length mix of BASELINE.json configs[2] ("train.py one epoch on data/train_data.csv").
-The config-3 epoch leg of bench.py (--train-epoch) and rna-mpnn_amd/train.py --lengths-file run seeded synthetic RNAs of exactly
+The config-3 epoch leg of bench.py (--full, --train-epoch) and rna-mpnn_amd/train.py --lengths-file run seeded synthetic RNAs of exactly
 these lengths.  Runs in the build container only."""
 import csv, os, sys
 import numpy as np
