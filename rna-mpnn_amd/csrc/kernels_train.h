@@ -25,25 +25,29 @@ static inline TDrop t_drop(float p, unsigned long long seed, const unsigned long
 
 void t_gemm(const TRows& rows, const float* X, int ldx, int K, const float* Wt, int ldw, const float* bias, int N,
             float* Y, int ldy, int beta, hipStream_t s);                      // Y = beta*Y + X.Wt + bias   (Wt K-major, row stride ldw)
-struct TScratch { float* p; size_t floats; };                // partial results of the ordered two-stage reductions
-// deferred, batched reductions of one backward (kernels_train.hip: RedQueue): between red_begin and red_end the producers' ordered reductions are
-// recorded and run many per launch; red_flush makes everything recorded so far final (before a gradient chunk's event)
-void red_begin(const TScratch& sc, hipStream_t s);
+// Ordered reductions of one backward (kernels_train.hip: RedQueue).  Between red_begin and red_end every producer of partial tiles (t_gemm_tn,
+// t_colsum, tm_gemm_tn[_pq], te_gemm_tn, te_gemm_bwd1[x2], te_gemm_bwd2, t_gn_bwd) takes an exact extent of the arena (red_alloc) and records its
+// reduction, and the recorded reductions run many per launch; calling one outside a queue is an error.  red_flush makes everything recorded so far
+// final (before a gradient chunk's event); red_end flushes, closes the queue and returns false when a request or job was refused since the last
+// red_end (nothing of it was launched).  An arena holds at least one producer's budget of RED_VIEW floats.
+struct TScratch { float* p; size_t floats; };
+static constexpr size_t RED_VIEW = (size_t)16 << 20;
+void red_begin(const TScratch& arena, hipStream_t s);
+float* red_alloc(size_t floats);
 void red_flush();
-void red_end();
-TScratch red_acquire(const TScratch& sc);
+bool red_end();
 void t_gemm_tn(const TRows& rows, const float* A, int lda, int M, const float* B, int ldb, int K, float* dW, int ldw,
-               const TScratch& sc, hipStream_t s);                                                           // dW += A^T B
-// bf16-mixed MFMA versions (kernels_train.hip, second half).  _nt / _nn return false when the shape is not covered
-// (K not a multiple of 16, unaligned rows): the caller then uses the f32 kernel.
+               hipStream_t s);                                                                               // dW += A^T B
+// bf16-mixed MFMA versions (kernels_train.hip, second half).  _nt / _nn / _tn return false (nothing launched) when the shape is not covered
+// (K not a multiple of 16, unaligned rows; _tn with actB: a partial tile larger than its budget): the caller then uses the f32 kernels.
 bool tm_gemm_nt(const TRows& rows, const float* X, int ldx, int K, const float* W, int ldw, const float* bias, int N, float* Y,
                 int ldy, int beta, bool actA, const TDrop& dr, unsigned site, hipStream_t s);
 bool tm_gemm_nn(const TRows& rows, const float* X, int ldx, int K, const float* W, int ldw, const float* bias, int N, float* Y,
                 int ldy, int beta, const float* epi_pre, int ld_epi, const TDrop& dr, unsigned site, hipStream_t s);
 // dbias (optional): += column sums of A, computed from the tiles the kernel stages anyway (the bias gradient of the same Linear)
-void tm_gemm_tn(const TRows& rows, const float* A, int lda, int M, const float* B, int ldb, int K, float* dW, int ldw,
-                const TScratch& sc, bool actB, const TDrop& dr, unsigned site, float* dbias, hipStream_t s);
-void t_colsum(const TRows& rows, const float* A, int lda, int M, float* out, const TScratch& sc, hipStream_t s);   // out += column sums
+bool tm_gemm_tn(const TRows& rows, const float* A, int lda, int M, const float* B, int ldb, int K, float* dW, int ldw,
+                bool actB, const TDrop& dr, unsigned site, float* dbias, hipStream_t s);
+void t_colsum(const TRows& rows, const float* A, int lda, int M, float* out, hipStream_t s);   // out += column sums
 void t_gelu_fwd(const TRows& rows, const float* x, float* y, int D, const TDrop& dr, unsigned site, hipStream_t s);   // y = drop(gelu(x))
 void t_gelu_bwd(const TRows& rows, const float* dy, const float* pre, float* dx, int D, const TDrop& dr, unsigned site,
                 hipStream_t s);                                                                             // dx = dy * mask * gelu'(pre)
@@ -63,7 +67,7 @@ void t_edge_res_bwd(const PackInfo& pk, int k, const int* nbr, const float* de, 
 void t_build_reverse(const PackInfo& pk, int k, const int* nbr, int* deg, int* start, int* fill, int* list, int* tmp, hipStream_t s);   // tmp: [Nmax*k] ints of scratch
 void t_edge_pq_bwd(const PackInfo& pk, int k, const float* dpre1, const int* start, const int* list, float* dpq, hipStream_t s);
 void t_gn_bwd(const PackInfo& pk, const float* x, const float* dy, const float* scale, int t_tot, float* dx, float* dscale,
-              float* dshift, const TScratch& sc, hipStream_t s);
+              float* dshift, hipStream_t s);
 // stat [N][heads][3]: the forward writes (row max, normaliser) per (query, head); the backward reads them and adds delta (it is a TAPE: one per attention layer)
 int  t_attention_fwd(const PackInfo& pk, const float* qkv, int heads, float* out, float* stat, const TDrop& dr, unsigned site, hipStream_t s);
 int  t_attention_bwd(const PackInfo& pk, const float* qkv, const float* O, const float* dO, int heads, float* dqkv, float* stat,
@@ -74,8 +78,8 @@ int  te_attention_bwd(const PackInfo& pk, const float* qkv, const float* O, cons
                       const TDrop& dr, unsigned site, hipStream_t s);
 // loss = mean_valid CE(softmax(logits), label) and d loss / d logits (packed rows)
 void t_pack_dlogits(const PackInfo& pk, const float* dlogits_padded, float* dlogits_p, hipStream_t s);
-void t_loss_grad(const PackInfo& pk, const float* logits, const int32_t* labels, float* dlogits, float* loss, const TScratch& sc,
-                 hipStream_t s);
+void t_loss_grad(const PackInfo& pk, const float* logits, const int32_t* labels, float* dlogits, float* loss, float* part,
+                 hipStream_t s);                                                                             // part: grid-size floats of scratch
 void t_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float wd,
                  int step, hipStream_t s);
 
@@ -96,11 +100,11 @@ struct EFuse {                       // optional epilogue fusions of te_gemm
 bool te_gemm(const TRows& rows, const void* X, bool x_bf16, int ldx, const float* W, int ldw, bool w_rows, const float* bias, tb16* Y,
              int beta, bool actA, const tb16* epi_pre, const EFuse* fuse, const TDrop& dr, unsigned site, hipStream_t s, int kvalid = 128);   // kvalid: live columns of X (the rest is zero padding)
 // dW[128][ldw] += A^T . actB(B), dbias += colsum(A)     (A, B bf16 [R][128])
-void te_gemm_tn(const TRows& rows, const tb16* A, const tb16* B, float* dW, int ldw, const TScratch& sc, bool actB, const TDrop& dr,
+void te_gemm_tn(const TRows& rows, const tb16* A, const tb16* B, float* dW, int ldw, bool actB, const TDrop& dr,
                 unsigned site, float* dbias, hipStream_t s, int cols_keep = 128);      // cols_keep: live columns of B
 // the node-side GEMMs of a factored first Linear, each pair as one launch: P / Q tables, [dWa ; dWb] (+ db1), dh += dP Wa + dQ Wb
 void te_gemm_pq(const TRows& rows, const float* h, const float* w0, const float* b1, tb16* Pt, tb16* Qt, hipStream_t s);
-void tm_gemm_tn_pq(const TRows& rows, const float* dpq, const float* h, float* gw0, float* db1, const TScratch& sc, hipStream_t s);
+void tm_gemm_tn_pq(const TRows& rows, const float* dpq, const float* h, float* gw0, float* db1, hipStream_t s);
 bool tm_gemm_nn_pq(const TRows& rows, const float* dpq, const float* w0, float* dh, hipStream_t s);
 // forward of a depth-2 per-edge MLP in one kernel (the hidden activation stays in registers; pre1 / pre2 written once as the tape;
 // pre1 = null: not kept)
@@ -108,7 +112,7 @@ void te_mlp2_fwd(const TRows& rows, const tb16* X, const float* W1, int ldw1, co
                  tb16* pre2, const EFuse& f, const TDrop& dr, unsigned site, hipStream_t s, bool g2tape = false);   // g2tape (edge update only): pre2 receives gelu'(pre2) * mask(site2)
 // fused pair of a first Linear's backward: dW += dY^T X, DE += dY . W   (one pass over dY)
 void te_gemm_bwd1(const TRows& rows, const tb16* dY, const tb16* X, tb16* DE, const float* W, int ldw, float* dW, int ldw_out,
-                  const TScratch& sc, hipStream_t s);
+                  hipStream_t s);
 // fused pair of a depth-2 MLP's backward: dW += dY^T drop(gelu(PRE)), dbias += colsum(dY), DX = (dY . W) gelu'(PRE) mask   (one pass over dY and PRE)
 // `from` (optional): d pre2 is formed on the fly while the tile is staged - mode 1: dY = d e_out, d pre2 = valid ? dY gelu'(pre2) mask(site2) : 0
 // (the edge update's residual backward); mode 2: d pre2 = valid ? dagg[row / k] inv_cnt[row / k] gelu'(pre2) mask(site2) : 0 (the message mean's)
@@ -116,9 +120,9 @@ void te_gemm_bwd1(const TRows& rows, const tb16* dY, const tb16* X, tb16* DE, co
 // multiplies, where it evaluated a sigmoid, an exp2 and a dropout hash per element
 struct EBwd2Src { int mode; const tb16* pre2; const int* nbr; const float* dagg; const float* inv_cnt; int k; unsigned site2; int g2tape; };
 void te_gemm_bwd1x2(const TRows& rows, const tb16* dY1, const tb16* dY2, const tb16* X, tb16* DE, const float* W1, const float* W2, int ldw,
-                    float* dW1, float* dW2, int ldw_out, const TScratch& sc, hipStream_t s);
+                    float* dW1, float* dW2, int ldw_out, hipStream_t s);
 void te_gemm_bwd2(const TRows& rows, const tb16* dY, const tb16* PRE, tb16* DX, const float* W, int ldw, float* dW, int ldw_out,
-                  const TScratch& sc, const TDrop& dr, unsigned site, float* dbias, hipStream_t s, const EBwd2Src* from = nullptr);
+                  const TDrop& dr, unsigned site, float* dbias, hipStream_t s, const EBwd2Src* from = nullptr);
 void te_inv_count(const PackInfo& pk, int k, const int* nbr, float* inv_cnt, hipStream_t s);   // 1 / max(#valid slots, 1) per residue
 // g2_out (optional, may alias pre2): gelu'(pre2) * mask(site) per element - what the message MLP's backward needs of pre2
 void te_seg_mean(const PackInfo& pk, int k, const int* nbr, const tb16* pre2, const float* h, float* out, const TDrop& dr, unsigned site, hipStream_t s,

@@ -9,6 +9,8 @@
 #include <cstdio>
 #include <vector>
 #include <cstdlib>
+#include <algorithm>
+#include <climits>
 
 static constexpr float kSEPS = 1.0e-6f;
 #define TLD 132
@@ -124,41 +126,14 @@ void t_gemm(const TRows& rows, const float* X, int ldx, int K, const float* Wt, 
     hipLaunchKernelGGL(k_tgemm, grid, dim3(256), 0, s, rows, X, ldx, K, Wt, ldw, bias, N, Y, ldy, beta);
 }
 
-// Ordered reduction of partial results: out[(i / cols) * ld_out + i % cols] += sum_{s < nparts} part[s * count + i], s ascending.
-// Every cross-workgroup sum of the backward goes through this (no float atomics): gradients are bit-reproducible.
-// Elements i >= split_at belong to a second, dense output (the bias gradient riding behind a weight-gradient tile): out2[i - split_at].
-__global__ void k_reduce_parts(const float* __restrict__ part, int nparts, size_t stride, int count, int cols,
-                               float* __restrict__ out, int ld_out, int split_at, float* __restrict__ out2, int cols_keep,
-                               int out2_keep, int wrap_rows, int wrap_shift) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    float s = 0.f;
-#pragma unroll 8
-    for (int p = 0; p < nparts; ++p) s += part[(size_t)p * stride + i];       // (loads batched by the unroll, additions in order)
-    if (i < split_at) {
-        // (columns >= cols_keep: padding of the operand;  wrap_rows: output rows beyond it continue wrap_shift columns to the right -
-        //  the [Wa | Wb] blocks of a first Linear's weight gradient, produced as one 256-row product)
-        const int row = i / cols, c = i % cols;
-        if (c < cols_keep) out[(size_t)(wrap_rows ? row % wrap_rows : row) * ld_out + (wrap_rows ? (row / wrap_rows) * wrap_shift : 0) + c] += s;
-    } else if (i - split_at < out2_keep) out2[i - split_at] += s;
-}
-// first level of a two-level reduction: group g sums its contiguous run of partials (ascending) into tmp[g][count]
-__global__ void k_reduce_groups(const float* __restrict__ part, int nparts, size_t stride, int count, int per_group,
-                                float* __restrict__ tmp) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x, g = blockIdx.y;
-    if (i >= count) return;
-    const int p0 = g * per_group, p1 = min(nparts, p0 + per_group);
-    float s = 0.f;
-#pragma unroll 8
-    for (int p = p0; p < p1; ++p) s += part[(size_t)p * stride + i];
-    tmp[(size_t)g * count + i] = s;
-}
-// ---- deferred, batched form (the backward of a training step): a kernel boundary costs ~4.7 us on this part and a step has ~180 of these
-// reductions, each a few microseconds of work.  While a queue is active (red_begin .. red_end, one per backward), every producer takes its
-// partial buffer from a bump arena (red_acquire) and reduce_parts only RECORDS the job; k_reduce_batch runs up to RED_MAX jobs per launch
-// (job table by value in the kernel arguments) when the arena is full, a job targets an output a pending job also targets, a gradient chunk
-// becomes final (red_flush) or the backward ends.  Per job the association order is a function of nparts alone: four contiguous runs of
-// partials summed in ascending order, then ((g0 + g1) + g2) + g3 - bit-reproducible.
+// ---- ordered reductions of the backward.  A producer writes one partial tile per split of its row range into an extent it takes from the arena of
+// the active queue (red_alloc: red_begin .. red_end, one queue per backward), then records a job that adds the partials into the gradient:
+//   out[(i / cols) * ld_out + i % cols] += sum_{p < nparts} part[p * stride + i]     for i < split_at (columns >= cols_keep: operand padding;
+//   wrap_rows: output rows beyond it continue wrap_shift columns to the right - the [Wa | Wb] blocks of a first Linear's weight gradient, produced
+//   as one 256-row product);  out2[i - split_at] += ... for split_at <= i < split_at + out2_keep (the bias gradient riding behind a weight tile).
+// No float atomics: gradients are bit-reproducible.  k_reduce_batch runs up to RED_MAX jobs per launch (job table by value in the kernel arguments): a
+// kernel boundary costs ~4.7 us on this part and a step has ~180 of these reductions, each a few microseconds of work.  Per job the association order
+// is a function of nparts alone: four contiguous runs of partials summed in ascending order, then ((g0 + g1) + g2) + g3.
 struct RedJob {
     const float* part; float* out; float* out2; size_t stride;
     int nparts, count, cols, ld_out, split_at, cols_keep, out2_keep, wrap_rows, wrap_shift, blk0;
@@ -189,68 +164,118 @@ __global__ void __launch_bounds__(256) k_reduce_batch(RedBatch b) {
             J.out[(size_t)(J.wrap_rows ? row % J.wrap_rows : row) * J.ld_out + (J.wrap_rows ? (row / J.wrap_rows) * J.wrap_shift : 0) + c] += s;
     } else if (i - J.split_at < J.out2_keep) J.out2[i - J.split_at] += s;
 }
+
+// Host side.  The queue launches what it holds (red_flush) when the arena cannot hold the next extent, before a job whose output footprint meets a
+// pending job's (the jobs of one launch add with plain +=), when the table is full, when a gradient chunk becomes final and at red_end;
+// RNAMPNN_NO_RED_BATCH=1 launches every job on its own.  A request or job outside an active queue, an extent larger than the arena and a job whose
+// partials are not inside the extents handed out or meet a pending job's partials are refused: nothing is launched and red_end reports false.
 struct RedQueue {
-    bool active = false;
+    bool active = false, one = false, bad = false;      // one: a launch per job;  bad: sticky until red_end reports it
     float* arena = nullptr; size_t floats = 0, used = 0;
     hipStream_t s = nullptr;
     RedBatch b;
     int blocks = 0;
 };
 static thread_local RedQueue g_rq;
-static constexpr size_t RED_VIEW = (size_t)16 << 20;       // what one producer may assume (the pre-queue scratch size)
-void red_flush() {
+static void red_launch() {
     RedQueue& q = g_rq;
     if (q.active && q.b.n > 0) hipLaunchKernelGGL(k_reduce_batch, dim3(q.blocks), dim3(256), 0, q.s, q.b);
-    q.b.n = 0; q.blocks = 0; q.used = 0;
+    q.b.n = 0; q.blocks = 0;
 }
-void red_begin(const TScratch& sc, hipStream_t s) {
+void red_flush() { red_launch(); g_rq.used = 0; }
+void red_begin(const TScratch& arena, hipStream_t s) {
     RedQueue& q = g_rq;
-    const char* off = getenv("RNAMPNN_NO_RED_BATCH");      // A/B switch (read per call): one reduction launch per producer, as before
-    q.active = sc.floats >= 2 * RED_VIEW && !(off && off[0] == '1');
-    q.arena = sc.p; q.floats = sc.floats; q.used = 0; q.s = s; q.b.n = 0; q.blocks = 0;
+    const char* one = getenv("RNAMPNN_NO_RED_BATCH");      // A/B switch (read per call)
+    q.active = true; q.one = one && one[0] == '1';
+    q.arena = arena.p; q.floats = arena.floats; q.used = 0; q.s = s; q.b.n = 0; q.blocks = 0;
 }
-void red_end() { red_flush(); g_rq.active = false; }
-// the scratch a producer works in: the whole buffer without a queue; with one, the free tail of the arena (flushed first if a producer's
-// worst case no longer fits)
-TScratch red_acquire(const TScratch& sc) {
+bool red_end() {
     RedQueue& q = g_rq;
-    if (!q.active || sc.p != q.arena) return sc;
-    if (q.floats - q.used < RED_VIEW) red_flush();
-    return TScratch{q.arena + q.used, RED_VIEW};
+    red_flush();
+    const bool ok = !q.bad;
+    q.active = false; q.bad = false;
+    return ok;
 }
+float* red_alloc(size_t floats) {
+    RedQueue& q = g_rq;
+    const size_t n = (floats + 63) & ~(size_t)63;          // (extents 256-byte aligned)
+    if (!q.active || n > q.floats) { q.bad = true; return nullptr; }
+    if (q.floats - q.used < n) red_flush();
+    float* p = q.arena + q.used;
+    q.used += n;
+    return p;
+}
+
+// rows x [p + r * ld, p + r * ld + width) floats: the partials or one output of a job
+struct RedSpan { const float* p; size_t ld, rows, width; };
+static bool spans_meet(const RedSpan& a, const RedSpan& b) {
+    if (!a.rows || !a.width || !b.rows || !b.width) return false;
+    const long long d = ((intptr_t)b.p - (intptr_t)a.p) / (intptr_t)sizeof(float);
+    const long long ha = (long long)((a.rows - 1) * a.ld + a.width), hb = (long long)((b.rows - 1) * b.ld + b.width);
+    if (d >= ha || -d >= hb) return false;                 // hulls apart
+    if (a.ld != b.ld) return true;
+    // row i of a meets row j of b iff -b.width < d + (j - i) ld < a.width: the least m = j - i above the lower bound decides
+    const long long ld = (long long)a.ld, lo = -(long long)b.width - d;
+    long long m = (lo >= 0 ? lo / ld : -((-lo + ld - 1) / ld)) + 1;
+    if (m < 1 - (long long)a.rows) m = 1 - (long long)a.rows;
+    return m <= (long long)b.rows - 1 && d + m * ld < (long long)a.width;
+}
+static RedSpan part_span(const RedJob& J) { return RedSpan{J.part, J.stride, (size_t)J.nparts, (size_t)J.count}; }
+static RedSpan out_span(const RedJob& J) {             // (wrap: the hull of the wrapped column blocks)
+    const int rows = (J.split_at + J.cols - 1) / J.cols;
+    if (!J.wrap_rows) return RedSpan{J.out, (size_t)J.ld_out, (size_t)rows, (size_t)J.cols_keep};
+    return RedSpan{J.out, (size_t)J.ld_out, (size_t)min(rows, J.wrap_rows), (size_t)((rows - 1) / J.wrap_rows * J.wrap_shift + J.cols_keep)};
+}
+static RedSpan out2_span(const RedJob& J) {
+    const size_t n = J.out2 ? (size_t)min(J.out2_keep, J.count - J.split_at) : 0;
+    return RedSpan{J.out2, n, 1, n};
+}
+static bool outputs_meet(const RedJob& a, const RedJob& b) {
+    const RedSpan sa[2] = {out_span(a), out2_span(a)}, sb[2] = {out_span(b), out2_span(b)};
+    for (const RedSpan& x : sa)
+        for (const RedSpan& y : sb)
+            if (spans_meet(x, y)) return true;
+    return false;
+}
+// records the ordered reduction of nparts partials (part + p * stride)[0 .. count): see k_reduce_batch for the index map
 static void reduce_parts(const float* part, int nparts, size_t stride, int count, int cols, float* out, int ld_out, hipStream_t s,
-                         float* tmp = nullptr, int split_at = -1, float* out2 = nullptr, int cols_keep = -1, int out2_keep = -1,
-                         int wrap_rows = 0, int wrap_shift = 0) {
-    if (split_at < 0) split_at = count;
-    if (cols_keep < 0) cols_keep = cols;
-    if (out2_keep < 0) out2_keep = count;
+                         int split_at = -1, float* out2 = nullptr, int cols_keep = -1, int out2_keep = -1, int wrap_rows = 0, int wrap_shift = 0) {
     RedQueue& q = g_rq;
-    if (q.active && s == q.s && part >= q.arena && part < q.arena + q.floats) {
-        bool clash = q.b.n == RED_MAX;
-        for (int t = 0; t < q.b.n && !clash; ++t) {
-            const RedJob& J = q.b.j[t];
-            clash = J.out == out || (out2 && (J.out2 == out2 || J.out == out2)) || (J.out2 && J.out2 == out);
-        }
-        const size_t keep_used = q.used;
-        if (clash) { red_flush(); q.used = keep_used; }     // (the partials of THIS job are already in the arena: keep its extent)
-        RedJob& J = q.b.j[q.b.n++];
-        J = RedJob{part, out, out2, stride, nparts, count, cols, ld_out, split_at, cols_keep, out2_keep, wrap_rows, wrap_shift, q.blocks};
-        q.blocks += (count + 63) / 64;
-        const size_t end = (size_t)(part - q.arena) + (size_t)(nparts - 1) * stride + (size_t)count;
-        if (end > q.used) q.used = (end + 63) & ~(size_t)63;
+    RedJob J{part, out, out2, stride, nparts, count, cols, ld_out, split_at < 0 ? count : split_at, cols_keep < 0 ? cols : cols_keep,
+             out2_keep < 0 ? count : out2_keep, wrap_rows, wrap_shift, 0};
+    const RedSpan ps = part_span(J);
+    if (!q.active || s != q.s || nparts < 1 || part < q.arena || (size_t)(part - q.arena) + ps.ld * (ps.rows - 1) + ps.width > q.used) {
+        q.bad = true;
         return;
     }
-    if (tmp && nparts > 96) {
-        const int G = 16, per = (nparts + G - 1) / G;
-        hipLaunchKernelGGL(k_reduce_groups, dim3((count + 255) / 256, G), dim3(256), 0, s, part, nparts, stride, count, per, tmp);
-        hipLaunchKernelGGL(k_reduce_parts, dim3((count + 255) / 256), dim3(256), 0, s, tmp, G, (size_t)count, count, cols, out, ld_out, split_at, out2, cols_keep, out2_keep, wrap_rows, wrap_shift);
-        return;
+    bool clash = q.b.n == RED_MAX;
+    for (int t = 0; t < q.b.n; ++t) {
+        if (spans_meet(part_span(q.b.j[t]), ps)) { q.bad = true; return; }
+        clash = clash || outputs_meet(q.b.j[t], J);
     }
-    hipLaunchKernelGGL(k_reduce_parts, dim3((count + 255) / 256), dim3(256), 0, s, part, nparts, stride, count, cols, out, ld_out, split_at, out2, cols_keep, out2_keep, wrap_rows, wrap_shift);
+    if (clash) red_launch();                                // (not red_flush: this job's partials stay where they are)
+    J.blk0 = q.blocks;
+    q.b.j[q.b.n++] = J;
+    q.blocks += (count + 63) / 64;
+    if (q.one) red_launch();
+}
+
+// The split count of a producer of partial tiles: one split per min_rows rows, at most `want` (enough workgroups for the chip), hard_max and the
+// budget `cap`; rows per split rounded up to `align`.  red_budget is the cap every producer had before it allocated exact extents: the RED_VIEW
+// floats it was handed, less `reserve` floats and `reserve_splits` partial tiles that the retired two-level reduction kept free behind the partials.
+// Those reserve terms look dead but stay: the cap binds (t_gemm_tn in the f32 trainer beyond ~131 K rows of a 512 x 512 Linear), and another split
+// count changes the bits of the gradient.
+struct RedSplit { int n, rows; };
+static long long red_budget(size_t per_split, size_t reserve, int reserve_splits) {
+    return (long long)((RED_VIEW - reserve) / per_split) - reserve_splits;
+}
+static RedSplit red_split(int maxrows, int min_rows, int align, long long want, long long hard_max, long long cap) {
+    const long long n = std::max(1LL, std::min({((long long)maxrows + min_rows - 1) / min_rows, want, hard_max, cap}));
+    return RedSplit{(int)n, (int)((((long long)maxrows + n - 1) / n + align - 1) / align * align)};
 }
 
 // dW[m][k] += sum_p A[p][m] * B[p][k]   (32 x 32 tile per block; the row range is split over blockIdx.z, every split
-// writes its own partial tile, k_reduce_parts adds them in split order)
+// writes its own partial tile, the ordered reduction adds them in split order)
 __global__ void __launch_bounds__(256) k_tgemm_tn(TRows rows, const float* __restrict__ A, int lda, int M,
         const float* __restrict__ B, int ldb, int K, float* __restrict__ part, int rows_per_split) {
     __shared__ float As[32][33], Bs[32][33];
@@ -282,18 +307,13 @@ __global__ void __launch_bounds__(256) k_tgemm_tn(TRows rows, const float* __res
     if (mB < M && kA < K) dst[(size_t)mB * K + kA] = a10;
     if (mB < M && kB < K) dst[(size_t)mB * K + kB] = a11;
 }
-void t_gemm_tn(const TRows& rows, const float* A, int lda, int M, const float* B, int ldb, int K, float* dW, int ldw,
-               const TScratch& sc_in, hipStream_t s) {
-    const TScratch sc = red_acquire(sc_in);
-    long long cap = (long long)(sc.floats / ((size_t)M * K));
-    int splits = (rows.maxrows + 2047) / 2048;
-    if (splits > 512) splits = 512;
-    if (splits > cap) splits = (int)cap;
-    if (splits < 1) splits = 1;
-    int rps = ((rows.maxrows + splits - 1) / splits + 31) / 32 * 32;
-    dim3 grid((M + 31) / 32, (K + 31) / 32, splits);
-    hipLaunchKernelGGL(k_tgemm_tn, grid, dim3(256), 0, s, rows, A, lda, M, B, ldb, K, sc.p, rps);
-    reduce_parts(sc.p, splits, (size_t)M * K, M * K, K, dW, ldw, s);
+void t_gemm_tn(const TRows& rows, const float* A, int lda, int M, const float* B, int ldb, int K, float* dW, int ldw, hipStream_t s) {
+    const size_t mk = (size_t)M * K;
+    const RedSplit sp = red_split(rows.maxrows, 2048, 32, LLONG_MAX, 512, red_budget(mk, 0, 0));
+    float* part = red_alloc(sp.n * mk);
+    if (!part) return;
+    hipLaunchKernelGGL(k_tgemm_tn, dim3((M + 31) / 32, (K + 31) / 32, sp.n), dim3(256), 0, s, rows, A, lda, M, B, ldb, K, part, sp.rows);
+    reduce_parts(part, sp.n, mk, (int)mk, K, dW, ldw, s);
 }
 
 // out[m] += sum_p A[p][m]   (per-block partial rows, ordered reduction)
@@ -307,15 +327,13 @@ __global__ void __launch_bounds__(256) k_colsum(TRows rows, const float* __restr
         part[(size_t)blockIdx.x * M + m] = s;
     }
 }
-void t_colsum(const TRows& rows, const float* A, int lda, int M, float* out, const TScratch& sc_in, hipStream_t s) {
-    const TScratch sc = red_acquire(sc_in);
-    int nb = (int)(sc.floats / (size_t)M) - 16;
-    if (nb > 512) nb = 512;
-    int rpb = (rows.maxrows + nb - 1) / nb;
-    if (rpb < 64) rpb = 64;
-    nb = (rows.maxrows + rpb - 1) / rpb;
-    hipLaunchKernelGGL(k_colsum, dim3(nb), dim3(256), 0, s, rows, A, lda, M, sc.p, rpb);
-    reduce_parts(sc.p, nb, (size_t)M, M, M, out, M, s, sc.p + (size_t)nb * M);
+void t_colsum(const TRows& rows, const float* A, int lda, int M, float* out, hipStream_t s) {
+    const int rpb = std::max(64, red_split(rows.maxrows, 1, 1, LLONG_MAX, 512, red_budget(M, 0, 16)).rows);   // >= 64 rows per block
+    const int nb = (rows.maxrows + rpb - 1) / rpb;
+    float* part = red_alloc((size_t)nb * M);
+    if (!part) return;
+    hipLaunchKernelGGL(k_colsum, dim3(nb), dim3(256), 0, s, rows, A, lda, M, part, rpb);
+    reduce_parts(part, nb, (size_t)M, M, M, out, M, s);
 }
 
 // element-wise over rows x D (contiguous, ld = D)
@@ -691,21 +709,23 @@ __global__ void __launch_bounds__(256) k_gn_bwd_apply(PackInfo pk, const float* 
     }
 }
 void t_gn_bwd(const PackInfo& pk, const float* x, const float* dy, const float* scale, int t_tot, float* dx, float* dscale,
-              float* dshift, const TScratch& sc_in, hipStream_t s) {
-    const TScratch sc = red_acquire(sc_in);
-    // per-RNA partials of (dscale, dshift), added in RNA order (needs B * 256 floats of scratch)
+              float* dshift, hipStream_t s) {
+    // per-RNA partials of (dscale, dshift), added in RNA order: B * 256 floats, then the split form's per-split sums
     const int nsplit = (pk.T + GN_SPLIT_ROWS - 1) / GN_SPLIT_ROWS;
     const size_t need = (size_t)pk.B * 256 + (size_t)pk.B * nsplit * 512;
     const char* nosplit = getenv("RNAMPNN_GN_NOSPLIT");          // A/B switch (read per call)
-    if (pk.T > GN_SPLIT_T && need <= sc.floats && !(nosplit && nosplit[0] == '1')) {
-        float* sums = sc.p + (size_t)pk.B * 256;
+    const bool split = pk.T > GN_SPLIT_T && need <= RED_VIEW && !(nosplit && nosplit[0] == '1');
+    float* part = red_alloc(split ? need : (size_t)pk.B * 256);
+    if (!part) return;
+    if (split) {
+        float* sums = part + (size_t)pk.B * 256;
         hipLaunchKernelGGL(k_gn_bwd_sums, dim3(pk.B, 4, nsplit), dim3(256), 0, s, pk, x, dy, nsplit, sums);
-        hipLaunchKernelGGL(k_gn_bwd_apply, dim3(pk.B, 4, nsplit), dim3(256), 0, s, pk, x, dy, scale, t_tot, nsplit, sums, dx, sc.p);
+        hipLaunchKernelGGL(k_gn_bwd_apply, dim3(pk.B, 4, nsplit), dim3(256), 0, s, pk, x, dy, scale, t_tot, nsplit, sums, dx, part);
     } else {
-        hipLaunchKernelGGL(k_gn_bwd, dim3(pk.B, 4), dim3(256), 0, s, pk, x, dy, scale, t_tot, dx, sc.p);
+        hipLaunchKernelGGL(k_gn_bwd, dim3(pk.B, 4), dim3(256), 0, s, pk, x, dy, scale, t_tot, dx, part);
     }
-    if (dscale) reduce_parts(sc.p, pk.B, 256, 128, 128, dscale, 128, s);
-    if (dshift) reduce_parts(sc.p + 128, pk.B, 256, 128, 128, dshift, 128, s);
+    if (dscale) reduce_parts(part, pk.B, 256, 128, 128, dscale, 128, s);
+    if (dshift) reduce_parts(part + 128, pk.B, 256, 128, 128, dshift, 128, s);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -891,12 +911,11 @@ __global__ void k_loss_sum(const float* __restrict__ part, int n, float* __restr
     for (int i = 0; i < n; ++i) s += part[i];
     *loss = s;
 }
-void t_loss_grad(const PackInfo& pk, const float* logits, const int32_t* labels, float* dlogits, float* loss, const TScratch& sc,
-                 hipStream_t s) {
+void t_loss_grad(const PackInfo& pk, const float* logits, const int32_t* labels, float* dlogits, float* loss, float* part, hipStream_t s) {
     int grid = (pk.Nmax + 255) / 256;
     if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(k_loss_grad, dim3(grid), dim3(256), 0, s, pk, logits, labels, dlogits, sc.p);
-    hipLaunchKernelGGL(k_loss_sum, dim3(1), dim3(1), 0, s, sc.p, grid, loss);
+    hipLaunchKernelGGL(k_loss_grad, dim3(grid), dim3(256), 0, s, pk, logits, labels, dlogits, part);
+    hipLaunchKernelGGL(k_loss_sum, dim3(1), dim3(1), 0, s, part, grid, loss);
 }
 
 // d loss / d logits handed in by the caller (autograd) in the padded (B,T,4) layout -> packed rows
@@ -1578,50 +1597,36 @@ __global__ void __launch_bounds__(256) k_mm_tn(TRows rows, const float* __restri
             }
         }
 }
-void tm_gemm_tn(const TRows& rows, const float* A, int lda, int M, const float* B, int ldb, int K, float* dW, int ldw,
-                const TScratch& sc_in, bool actB, const TDrop& dr, unsigned site, float* dbias, hipStream_t s) {
-    const TScratch sc = red_acquire(sc_in);
+bool tm_gemm_tn(const TRows& rows, const float* A, int lda, int M, const float* B, int ldb, int K, float* dW, int ldw,
+                bool actB, const TDrop& dr, unsigned site, float* dbias, hipStream_t s) {
     const size_t mk = (size_t)M * K;
     const int tiles = ((M + 127) / 128) * ((K + 127) / 128);
-    long long cap = (long long)((sc.floats - (size_t)520 * M) / mk) - 16;   // behind the partials: 16 * mk floats for the two-level reduction, 520 * M for the column sums
-    int splits = (rows.maxrows + 255) / 256;                  // >= 256 rows (4 tiles) per workgroup
-    const int want = (2 * rn_num_cus() + tiles - 1) / tiles;  // enough workgroups for the chip
-    if (splits > want) splits = want;
-    if (splits > cap) splits = (int)cap;
-    if (splits > 500) splits = 500;
-    if (splits < 1) splits = 1;
-    const int rps = ((rows.maxrows + splits - 1) / splits + 63) / 64 * 64;
-    if ((lda % 4) || (ldb % 4) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15) || actB && cap < 1) {     // 16-byte row loads need aligned rows
-        t_gemm_tn(rows, A, lda, M, B, ldb, K, dW, ldw, sc, s);
-        if (dbias) t_colsum(rows, A, lda, M, dbias, sc, s);
-        return;
-    }
+    const long long cap = red_budget(mk, (size_t)520 * M, 16);
+    if ((lda % 4) || (ldb % 4) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15) || actB && cap < 1) return false;   // 16-byte row loads need aligned rows
+    // >= 256 rows (4 tiles) per workgroup, enough workgroups for the chip
+    const RedSplit sp = red_split(rows.maxrows, 256, 64, (2 * rn_num_cus() + tiles - 1) / tiles, 500, cap);
     // partial of split z: [M*K tile][M column sums (with dbias)]: one ordered reduction adds both into dW / dbias
     const size_t pstride = mk + (dbias ? (size_t)M : 0);
-    float* tmp = sc.p + (size_t)splits * pstride;             // [16][pstride] second-level buffer
-    dim3 grid((M + 127) / 128, (K + 127) / 128, splits);
-    hipLaunchKernelGGL(k_mm_tn, grid, dim3(256), 0, s, rows, A, lda, M, B, ldb, K, sc.p, pstride, rps, actB ? 1 : 0, dr, site,
-                       dbias ? sc.p + mk : (float*)nullptr);
-    reduce_parts(sc.p, splits, pstride, (int)pstride, K, dW, ldw, s, tmp, (int)mk, dbias);
+    float* part = red_alloc(sp.n * pstride);
+    if (!part) return true;                                   // (refused: red_end reports it)
+    dim3 grid((M + 127) / 128, (K + 127) / 128, sp.n);
+    hipLaunchKernelGGL(k_mm_tn, grid, dim3(256), 0, s, rows, A, lda, M, B, ldb, K, part, pstride, sp.rows, actB ? 1 : 0, dr, site,
+                       dbias ? part + mk : (float*)nullptr);
+    reduce_parts(part, sp.n, pstride, (int)pstride, K, dW, ldw, s, (int)mk, dbias);
+    return true;
 }
 
 // The node-side weight gradients of a factored first Linear in ONE product: [dWa ; dWb] = [dP | dQ]^T h (256 x 128), db1 = colsum(dP).
 // gw0 = the [128][384] gradient of the Linear's weight ([Wa | Wb | Wc] blocks): rows 0..127 of the product go to columns 0..127, rows
 // 128..255 to columns 128..255 of the same 128 output rows (the reduction's wrap).
-void tm_gemm_tn_pq(const TRows& rows, const float* dpq, const float* h, float* gw0, float* db1, const TScratch& sc_in, hipStream_t s) {
-    const TScratch sc = red_acquire(sc_in);
+void tm_gemm_tn_pq(const TRows& rows, const float* dpq, const float* h, float* gw0, float* db1, hipStream_t s) {
     const int M = 256, K = 128;
     const size_t mk = (size_t)M * K, pstride = mk + M;
-    long long cap = (long long)(sc.floats / pstride) - 16;
-    int splits = (rows.maxrows + 255) / 256;
-    const int want = rn_num_cus();                            // two 128-row output tiles per split
-    if (splits > want) splits = want;
-    if (splits > cap) splits = (int)cap;
-    if (splits < 1) splits = 1;
-    const int rps = ((rows.maxrows + splits - 1) / splits + 63) / 64 * 64;
-    float* tmp = sc.p + (size_t)splits * pstride;
-    hipLaunchKernelGGL(k_mm_tn, dim3(2, 1, splits), dim3(256), 0, s, rows, dpq, 256, M, h, 128, K, sc.p, pstride, rps, 0, TDrop{0ull, 0u, 1.f}, 0u, sc.p + mk);
-    reduce_parts(sc.p, splits, pstride, (int)pstride, K, gw0, 3 * 128, s, tmp, (int)mk, db1, K, 128, 128, 128);
+    const RedSplit sp = red_split(rows.maxrows, 256, 64, rn_num_cus(), LLONG_MAX, red_budget(pstride, 0, 16));   // two 128-row output tiles per split
+    float* part = red_alloc(sp.n * pstride);
+    if (!part) return;
+    hipLaunchKernelGGL(k_mm_tn, dim3(2, 1, sp.n), dim3(256), 0, s, rows, dpq, 256, M, h, 128, K, part, pstride, sp.rows, 0, TDrop{0ull, 0u, 1.f}, 0u, part + mk);
+    reduce_parts(part, sp.n, pstride, (int)pstride, K, gw0, 3 * 128, s, (int)mk, db1, K, 128, 128, 128);
 }
 // dh += dP . Wa + dQ . Wb as one K = 256 product (w0 = [128][384] weight: Wa = columns 0..127, Wb = columns 128..255)
 bool tm_gemm_nn_pq(const TRows& rows, const float* dpq, const float* w0, float* dh, hipStream_t s) {
@@ -2170,23 +2175,16 @@ __global__ void __launch_bounds__(256, 3) k_emm_tn(TRows rows, const tb16* __res
             for (int i = 0; i < 16; ++i) dst[(size_t)(64 * wr + 32 * a + (i & 3) + 8 * (i >> 2) + 4 * h) * 128 + col] = acc[a][b][i];
         }
 }
-void te_gemm_tn(const TRows& rows, const tb16* A, const tb16* B, float* dW, int ldw, const TScratch& sc_in, bool actB, const TDrop& dr,
+void te_gemm_tn(const TRows& rows, const tb16* A, const tb16* B, float* dW, int ldw, bool actB, const TDrop& dr,
                 unsigned site, float* dbias, hipStream_t s, int cols_keep) {
-    const TScratch sc = red_acquire(sc_in);
     const size_t mk = 128 * 128;
-    long long cap = (long long)((sc.floats - (size_t)800 * 128) / mk) - 16;
-    int splits = (rows.maxrows + 1023) / 1024;
-    const int want = 3 * rn_num_cus();                       // three resident workgroups per CU
-    if (splits > want) splits = want;
-    if (splits > cap) splits = (int)cap;
-    if (splits > 768) splits = 768;
-    if (splits < 1) splits = 1;
-    const int rps = ((rows.maxrows + splits - 1) / splits + 63) / 64 * 64;
+    const RedSplit sp = red_split(rows.maxrows, 1024, 64, 3 * rn_num_cus(), 768, red_budget(mk, 800 * 128, 16));   // three resident workgroups per CU
     const size_t pstride = mk + (dbias ? 128 : 0);
-    float* tmp = sc.p + (size_t)splits * pstride;
-    hipLaunchKernelGGL(k_emm_tn, dim3(1, 1, splits), dim3(256), 0, s, rows, A, B, sc.p, pstride, rps, actB ? 1 : 0, dr, site,
-                       dbias ? sc.p + mk : (float*)nullptr);
-    reduce_parts(sc.p, splits, pstride, (int)pstride, 128, dW, ldw, s, tmp, (int)mk, dbias, cols_keep);
+    float* part = red_alloc(sp.n * pstride);
+    if (!part) return;
+    hipLaunchKernelGGL(k_emm_tn, dim3(1, 1, sp.n), dim3(256), 0, s, rows, A, B, part, pstride, sp.rows, actB ? 1 : 0, dr, site,
+                       dbias ? part + mk : (float*)nullptr);
+    reduce_parts(part, sp.n, pstride, (int)pstride, 128, dW, ldw, s, (int)mk, dbias, cols_keep);
 }
 
 // ---- the two kernels that consume d pre2 of a depth-2 per-edge MLP, fused: dW2 += dpre2^T a1, db2 += colsum(dpre2) (k_emm_tn with
@@ -2497,19 +2495,14 @@ __global__ void __launch_bounds__(256, 2) k_emm_bwd1(TRows rows, const tb16* __r
 }
 // dW[128][ldw_out] += dY^T X,  DE += dY . W       (W [128 out][ldw]: the Wc block of a first Linear)
 void te_gemm_bwd1(const TRows& rows, const tb16* dY, const tb16* X, tb16* DE, const float* W, int ldw, float* dW, int ldw_out,
-                  const TScratch& sc_in, hipStream_t s) {
-    const TScratch sc = red_acquire(sc_in);
+                  hipStream_t s) {
     const size_t mk = 128 * 128;
-    long long cap = (long long)((sc.floats - (size_t)800 * 128) / mk) - 16;
-    int splits = (rows.maxrows + 511) / 512;                 // >= 8 tiles per workgroup; fills the chip from ~130 K rows on
-    const int want = 2 * rn_num_cus();
-    if (splits > want) splits = want;
-    if (splits > cap) splits = (int)cap;
-    if (splits < 1) splits = 1;
-    const int rps = ((rows.maxrows + splits - 1) / splits + 63) / 64 * 64;
-    float* tmp = sc.p + (size_t)splits * mk;
-    hipLaunchKernelGGL(k_emm_bwd1, dim3(1, 1, splits), dim3(256), 0, s, rows, dY, X, DE, W, ldw, wimg_lookup(W, ldw, false, 1), sc.p, mk, rps);
-    reduce_parts(sc.p, splits, mk, (int)mk, 128, dW, ldw_out, s, tmp);
+    // >= 8 tiles per workgroup; fills the chip from ~130 K rows on
+    const RedSplit sp = red_split(rows.maxrows, 512, 64, 2 * rn_num_cus(), LLONG_MAX, red_budget(mk, 800 * 128, 16));
+    float* part = red_alloc(sp.n * mk);
+    if (!part) return;
+    hipLaunchKernelGGL(k_emm_bwd1, dim3(1, 1, sp.n), dim3(256), 0, s, rows, dY, X, DE, W, ldw, wimg_lookup(W, ldw, false, 1), part, mk, sp.rows);
+    reduce_parts(part, sp.n, mk, (int)mk, 128, dW, ldw_out, s);
 }
 // ---- the first-Linear backward of the TWO per-edge MLPs of a layer that share their input e (edge update and message MLP, mpnn.py:212-262) in one
 // pass: dW1 += dY1^T e, dW2 += dY2^T e, dE += dY1 . W1 + dY2 . W2.  As two k_emm_bwd1 launches e and dE are read twice and dE is written twice
@@ -2614,44 +2607,34 @@ __global__ void __launch_bounds__(512, 1) k_emm_bwd1x2(TRows rows, const tb16* _
 }
 // dW1[128][ldw_out] += dY1^T X, dW2 += dY2^T X, DE += dY1 . W1 + dY2 . W2      (W1, W2 [128 out][ldw]: the Wc blocks of the two first Linears)
 void te_gemm_bwd1x2(const TRows& rows, const tb16* dY1, const tb16* dY2, const tb16* X, tb16* DE, const float* W1, const float* W2, int ldw,
-                    float* dW1, float* dW2, int ldw_out, const TScratch& sc_in, hipStream_t s) {
-    const TScratch sc = red_acquire(sc_in);
+                    float* dW1, float* dW2, int ldw_out, hipStream_t s) {
     const size_t mk = 128 * 128, pstride = 2 * mk;
-    long long cap = (long long)((sc.floats - (size_t)800 * 128) / pstride) - 16;
-    int splits = (rows.maxrows + 1023) / 1024;               // >= 16 tiles per workgroup
-    const int want = rn_num_cus();                           // one 8-wave workgroup per CU (127 KiB of LDS)
-    if (splits > want) splits = want;
-    if (splits > cap) splits = (int)cap;
-    if (splits < 1) splits = 1;
-    const int rps = ((rows.maxrows + splits - 1) / splits + 63) / 64 * 64;
-    float* tmp = sc.p + (size_t)splits * pstride;
-    hipLaunchKernelGGL(k_emm_bwd1x2, dim3(1, 1, splits), dim3(512), 0, s, rows, dY1, dY2, X, DE, W1, W2, ldw, wimg_lookup(W1, ldw, false, 1),
-                       wimg_lookup(W2, ldw, false, 1), sc.p, pstride, rps);
-    reduce_parts(sc.p, splits, pstride, (int)mk, 128, dW1, ldw_out, s, tmp);
-    reduce_parts(sc.p + mk, splits, pstride, (int)mk, 128, dW2, ldw_out, s, tmp);
+    // >= 16 tiles per workgroup, one 8-wave workgroup per CU (127 KiB of LDS)
+    const RedSplit sp = red_split(rows.maxrows, 1024, 64, rn_num_cus(), LLONG_MAX, red_budget(pstride, 800 * 128, 16));
+    float* part = red_alloc(sp.n * pstride);
+    if (!part) return;
+    hipLaunchKernelGGL(k_emm_bwd1x2, dim3(1, 1, sp.n), dim3(512), 0, s, rows, dY1, dY2, X, DE, W1, W2, ldw, wimg_lookup(W1, ldw, false, 1),
+                       wimg_lookup(W2, ldw, false, 1), part, pstride, sp.rows);
+    reduce_parts(part, sp.n, pstride, (int)mk, 128, dW1, ldw_out, s);
+    reduce_parts(part + mk, sp.n, pstride, (int)mk, 128, dW2, ldw_out, s);
 }
 // dW[128][ldw_out] += dY^T drop(gelu(PRE)), dbias += colsum(dY), DX = (dY . W) gelu'(PRE) mask        (W [128 out][ldw] as nn.Linear stores it)
 void te_gemm_bwd2(const TRows& rows, const tb16* dY, const tb16* PRE, tb16* DX, const float* W, int ldw, float* dW, int ldw_out,
-                  const TScratch& sc_in, const TDrop& dr, unsigned site, float* dbias, hipStream_t s, const EBwd2Src* from) {
-    const TScratch sc = red_acquire(sc_in);
+                  const TDrop& dr, unsigned site, float* dbias, hipStream_t s, const EBwd2Src* from) {
     const size_t mk = 128 * 128;
-    long long cap = (long long)((sc.floats - (size_t)800 * 128) / mk) - 16;
-    int splits = (rows.maxrows + 511) / 512;                 // >= 8 tiles per workgroup; fills the chip from ~130 K rows on
-    const int want = 2 * rn_num_cus();                       // two resident workgroups per CU (72 KiB of LDS each)
-    if (splits > want) splits = want;
-    if (splits > cap) splits = (int)cap;
-    if (splits < 1) splits = 1;
-    const int rps = ((rows.maxrows + splits - 1) / splits + 63) / 64 * 64;
+    // >= 8 tiles per workgroup (fills the chip from ~130 K rows on), two resident workgroups per CU (72 KiB of LDS each)
+    const RedSplit sp = red_split(rows.maxrows, 512, 64, 2 * rn_num_cus(), LLONG_MAX, red_budget(mk, 800 * 128, 16));
     const size_t pstride = mk + (dbias ? 128 : 0);
-    float* tmp = sc.p + (size_t)splits * pstride;
+    float* part = red_alloc(sp.n * pstride);
+    if (!part) return;
     Bwd2Src src{nullptr, nullptr, nullptr, nullptr, 1, 0u, 0};
     const int mode = from ? from->mode : 0;
     if (from) src = Bwd2Src{from->pre2, from->nbr, from->dagg, from->inv_cnt, from->k, from->site2, from->g2tape};
-#define BWD2_GO(M) hipLaunchKernelGGL(k_emm_bwd2<M>, dim3(1, 1, splits), dim3(256), 0, s, rows, dY, PRE, DX, W, ldw, wimg_lookup(W, ldw, false, 1), \
-                                       sc.p, pstride, rps, dr, site, dbias ? sc.p + mk : (float*)nullptr, src)
+#define BWD2_GO(M) hipLaunchKernelGGL(k_emm_bwd2<M>, dim3(1, 1, sp.n), dim3(256), 0, s, rows, dY, PRE, DX, W, ldw, wimg_lookup(W, ldw, false, 1), \
+                                       part, pstride, sp.rows, dr, site, dbias ? part + mk : (float*)nullptr, src)
     if (mode == 1) BWD2_GO(1); else if (mode == 2) BWD2_GO(2); else BWD2_GO(0);
 #undef BWD2_GO
-    reduce_parts(sc.p, splits, pstride, (int)pstride, 128, dW, ldw_out, s, tmp, (int)mk, dbias);
+    reduce_parts(part, sp.n, pstride, (int)pstride, 128, dW, ldw_out, s, (int)mk, dbias);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -28,7 +28,7 @@ struct TW {                        // training workspace
     int *len, *cu, *node_b, *nbr;
     int *rdeg, *rstart, *rfill, *rlist;   // reverse adjacency of the k-NN graph (t_build_reverse)
     float *geom, *raw_p;
-    TScratch sc;                          // partials of the ordered reductions
+    TScratch sc;                          // arena of the backward's ordered reductions (red_begin); the loss partials before it
     // tape
     float *F, *pe1, *pe2;
     std::vector<float*> e, pm1, pm2, pu1, pu2, h, hpre;
@@ -55,7 +55,9 @@ static size_t carve_train(const rnampnn_ctx* c, int B, int T, char* base, TW* ou
     w.nbr = (int*)takeb(E * sizeof(int));
     w.rdeg = (int*)takeb((N + 1) * sizeof(int)); w.rstart = (int*)takeb((N + 1) * sizeof(int));
     w.rfill = (int*)takeb((N + 1) * sizeof(int)); w.rlist = (int*)takeb(E * sizeof(int));
-    w.sc.floats = (size_t)64 << 20;        // 256 MB: arena of the backward's batched reductions (four producers' worst case)
+    // 256 MB: four producer budgets (RED_VIEW) of the backward's batched reductions, and never less than the largest single extent (a budget, or
+    // t_gn_bwd's B * 256 per-RNA partials)
+    w.sc.floats = 4 * RED_VIEW;
     if (w.sc.floats < (size_t)B * 256 + 4096) w.sc.floats = (size_t)B * 256 + 4096;
     w.sc.p = takef(w.sc.floats);
     w.geom = takef((N + B) * RN_GEOM); w.raw_p = takef(N * RN_RAWP);
@@ -167,9 +169,9 @@ void mm_nt(Tr& t, const TRows& rows, const float* X, int ldx, int K, const float
 // dbias (optional) += column sums of A: the bias gradient of the same Linear (fused into the MFMA kernel's staging pass)
 void mm_tn(Tr& t, const TRows& rows, const float* A, int lda, int M, const float* B, int ldb, int K, float* dW, int ldw,
            float* dbias = nullptr) {
-    if (t.mixed) { tm_gemm_tn(rows, A, lda, M, B, ldb, K, dW, ldw, t.w.sc, false, t.dr, 0u, dbias, t.s); return; }
-    t_gemm_tn(rows, A, lda, M, B, ldb, K, dW, ldw, t.w.sc, t.s);
-    if (dbias) t_colsum(rows, A, lda, M, dbias, t.w.sc, t.s);
+    if (t.mixed && tm_gemm_tn(rows, A, lda, M, B, ldb, K, dW, ldw, false, t.dr, 0u, dbias, t.s)) return;
+    t_gemm_tn(rows, A, lda, M, B, ldb, K, dW, ldw, t.s);
+    if (dbias) t_colsum(rows, A, lda, M, dbias, t.s);
 }
 
 void lin_fwd(Tr& t, const Lin& l, const float* X, int ldx, float* Y, int ldy) {
@@ -217,10 +219,10 @@ void ffn_bwd(Tr& t, const std::vector<Lin>& L, const float* X, int ldx, const st
     float* bufs[2] = {t.w.dA, t.w.dB};
     for (int i = (int)L.size() - 1; i >= 0; --i) {
         float* din = i == 0 ? dX : bufs[i & 1];
-        if (i > 0 && t.mixed && fusable(L[i], pre[i - 1], L[i - 1].out) && L[i].out % 16 == 0 && (((uintptr_t)d) & 15) == 0) {
-            // dW += dY^T drop(gelu(pre)), db += colsum(dY): the activation recomputed in the staging pass;  d pre = (dY . W) gelu'(pre) mask
-            const unsigned site = site0 + (unsigned)(i - 1);
-            tm_gemm_tn(t.rn(), d, L[i].out, L[i].out, pre[i - 1], L[i].in, L[i].in, t.gw(L[i].w), L[i].in, t.w.sc, true, t.dr, site, t.gw(L[i].b), t.s);
+        const unsigned site = site0 + (unsigned)(i - 1);
+        // dW += dY^T drop(gelu(pre)), db += colsum(dY): the activation recomputed in the staging pass;  d pre = (dY . W) gelu'(pre) mask
+        if (i > 0 && t.mixed && fusable(L[i], pre[i - 1], L[i - 1].out) && L[i].out % 16 == 0 && (((uintptr_t)d) & 15) == 0 &&
+            tm_gemm_tn(t.rn(), d, L[i].out, L[i].out, pre[i - 1], L[i].in, L[i].in, t.gw(L[i].w), L[i].in, true, t.dr, site, t.gw(L[i].b), t.s)) {
             if (tm_gemm_nn(t.rn(), d, L[i].out, L[i].out, rawp(t.c, L[i].w), L[i].in, nullptr, L[i].in, din, L[i].in, 0, pre[i - 1], L[i].in, t.dr, site, t.s)) {
                 d = din;
                 continue;
@@ -233,9 +235,9 @@ void ffn_bwd(Tr& t, const std::vector<Lin>& L, const float* X, int ldx, const st
         const float* in;
         int ldin;
         if (i == 0) { in = X; ldin = ldx; }
-        else { t_gelu_fwd(t.rn(), pre[i - 1], t.w.act, L[i - 1].out, t.dr, site0 + (unsigned)(i - 1), t.s); in = t.w.act; ldin = L[i - 1].out; }
+        else { t_gelu_fwd(t.rn(), pre[i - 1], t.w.act, L[i - 1].out, t.dr, site, t.s); in = t.w.act; ldin = L[i - 1].out; }
         lin_bwd(t, L[i], in, ldin, d, L[i].out, din, i == 0 ? lddx : L[i].in);
-        if (i > 0) { t_gelu_bwd(t.rn(), din, pre[i - 1], din, L[i - 1].out, t.dr, site0 + (unsigned)(i - 1), t.s); d = din; }
+        if (i > 0) { t_gelu_bwd(t.rn(), din, pre[i - 1], din, L[i - 1].out, t.dr, site, t.s); d = din; }
     }
 }
 
@@ -270,7 +272,7 @@ int bert_bwd(Tr& t, const Bert& b, BertTape& tp, const float* dOut, float* dIn, 
     for (int j = (int)J - 1; j >= 0; --j) {
         const Attn& a = b.attn[j];
         // GraphNorm backward: dIn = d x[j+1]  ->  nscr = d t[j]
-        t_gn_bwd(t.pk, tp.t[j], dIn, rawp(t.c, a.gn_scale), t.c->cfg.padding_len, t.w.nscr, t.gw(a.gn_scale), t.gw(a.gn_shift), t.w.sc, t.s);
+        t_gn_bwd(t.pk, tp.t[j], dIn, rawp(t.c, a.gn_scale), t.c->cfg.padding_len, t.w.nscr, t.gw(a.gn_scale), t.gw(a.gn_shift), t.s);
         // out_proj backward: d o = d t . Wout
         lin_bwd(t, a.out, tp.o[j], RN_D, t.w.nscr, RN_D, t.w.dh2, RN_D);
         if (!(att_mfma(t) && te_attention_bwd(t.pk, tp.qkv[j], tp.o[j], t.w.dh2, b.heads, t.w.dqkv, tp.st[j], t.dr, site_att0 + (unsigned)j, t.s) == 0))
@@ -308,10 +310,9 @@ void mlp_edge_fwd(Tr& t, const Mlp2& m, const float* h, const float* e, float* p
 void mlp_edge_bwd(Tr& t, const Mlp2& m, const float* h, const float* e, const float* pre1, float* dE, float* dh_acc, unsigned site0) {
     rnampnn_ctx* c = t.c;
     float* dpre1 = t.w.E2;
-    if (m.depth > 1 && t.mixed) {
-        // E2 = d pre2.  dW2 += dpre2^T drop(gelu(pre1)) and db2 += colsum(dpre2) in one kernel (the activation is recomputed
-        // from the taped pre-activation while the tile is staged); d pre1 = (dpre2 . W2) * gelu'(pre1) * mask in the epilogue
-        tm_gemm_tn(t.re(), t.w.E2, RN_D, RN_D, pre1, RN_D, RN_D, t.gw(m.w[1]), RN_D, t.w.sc, true, t.dr, site0, t.gw(m.b[1]), t.s);
+    // mixed: E2 = d pre2.  dW2 += dpre2^T drop(gelu(pre1)) and db2 += colsum(dpre2) in one kernel (the activation is recomputed
+    // from the taped pre-activation while the tile is staged); d pre1 = (dpre2 . W2) * gelu'(pre1) * mask in the epilogue
+    if (m.depth > 1 && t.mixed && tm_gemm_tn(t.re(), t.w.E2, RN_D, RN_D, pre1, RN_D, RN_D, t.gw(m.w[1]), RN_D, true, t.dr, site0, t.gw(m.b[1]), t.s)) {
         tm_gemm_nn(t.re(), t.w.E2, RN_D, RN_D, rawp(c, m.w[1]), RN_D, nullptr, RN_D, t.w.E1, RN_D, 0, pre1, RN_D, t.dr, site0, t.s);
         dpre1 = t.w.E1;
     } else if (m.depth > 1) {
@@ -381,12 +382,12 @@ void mlp_edge_bwd_mixed(Tr& t, const Mlp2& m, const float* h, const tb16* e, con
     if (m.depth > 1) {
         static const bool split = getenv("RNAMPNN_SPLIT_BWD") && atoi(getenv("RNAMPNN_SPLIT_BWD")) != 0;     // A/B switch: the two kernels the fused one replaces
         if (from) {
-            te_gemm_bwd2(t.re(), dy_in, pre1, dpre1_keep ? dpre1_keep : eb(t.w.E1), rawp(c, m.w[1]), RN_D, t.gw(m.w[1]), RN_D, t.w.sc, t.dr, site0, t.gw(m.b[1]), t.s, from);
+            te_gemm_bwd2(t.re(), dy_in, pre1, dpre1_keep ? dpre1_keep : eb(t.w.E1), rawp(c, m.w[1]), RN_D, t.gw(m.w[1]), RN_D, t.dr, site0, t.gw(m.b[1]), t.s, from);
         } else if (split) {
-            te_gemm_tn(t.re(), eb(t.w.E2), pre1, t.gw(m.w[1]), RN_D, t.w.sc, true, t.dr, site0, t.gw(m.b[1]), t.s);      // dW2, db2
+            te_gemm_tn(t.re(), eb(t.w.E2), pre1, t.gw(m.w[1]), RN_D, true, t.dr, site0, t.gw(m.b[1]), t.s);      // dW2, db2
             t.bad |= !te_gemm(t.re(), t.w.E2, true, RN_D, rawp(c, m.w[1]), RN_D, false, nullptr, eb(t.w.E1), 0, false, pre1, nullptr, t.dr, site0, t.s);   // d pre1
         } else {
-            te_gemm_bwd2(t.re(), eb(t.w.E2), pre1, eb(t.w.E1), rawp(c, m.w[1]), RN_D, t.gw(m.w[1]), RN_D, t.w.sc, t.dr, site0, t.gw(m.b[1]), t.s);
+            te_gemm_bwd2(t.re(), eb(t.w.E2), pre1, eb(t.w.E1), rawp(c, m.w[1]), RN_D, t.gw(m.w[1]), RN_D, t.dr, site0, t.gw(m.b[1]), t.s);
         }
         dpre1 = (from && dpre1_keep) ? dpre1_keep : eb(t.w.E1);
     }
@@ -396,13 +397,13 @@ void mlp_edge_bwd_mixed(Tr& t, const Mlp2& m, const float* h, const tb16* e, con
     if (from && dpre1_keep && m.depth > 1) {
         // (deferred to mlp_edge_bwd1_pair)
     } else if (split1) {
-        te_gemm_tn(t.re(), dpre1, e, gw0 + 2 * RN_D, 3 * RN_D, t.w.sc, false, t.dr, 0u, nullptr, t.s);                   // dWc += dpre1^T e
+        te_gemm_tn(t.re(), dpre1, e, gw0 + 2 * RN_D, 3 * RN_D, false, t.dr, 0u, nullptr, t.s);                   // dWc += dpre1^T e
         t.bad |= !te_gemm(t.re(), dpre1, true, RN_D, w0 + 2 * RN_D, 3 * RN_D, false, nullptr, dE, 1, false, nullptr, nullptr, t.dr, 0u, t.s);   // dE += dpre1 . Wc
     } else {
-        te_gemm_bwd1(t.re(), dpre1, e, dE, w0 + 2 * RN_D, 3 * RN_D, gw0 + 2 * RN_D, 3 * RN_D, t.w.sc, t.s);           // both, one pass over dpre1
+        te_gemm_bwd1(t.re(), dpre1, e, dE, w0 + 2 * RN_D, 3 * RN_D, gw0 + 2 * RN_D, 3 * RN_D, t.s);           // both, one pass over dpre1
     }
     te_edge_pq_bwd(t.pk, t.k, dpre1, t.w.rstart, t.w.rlist, t.w.dpq, t.s);
-    tm_gemm_tn_pq(t.rn(), t.w.dpq, h, gw0, t.gw(m.b[0]), t.w.sc, t.s);                 // [dWa ; dWb] += [dP | dQ]^T h, db1 += colsum(dP)
+    tm_gemm_tn_pq(t.rn(), t.w.dpq, h, gw0, t.gw(m.b[0]), t.s);                 // [dWa ; dWb] += [dP | dQ]^T h, db1 += colsum(dP)
     if (!tm_gemm_nn_pq(t.rn(), t.w.dpq, w0, dh_acc, t.s)) {                            // dh += dP . Wa + dQ . Wb
         mm_nn(t, t.rn(), t.w.dpq, 256, RN_D, w0, 3 * RN_D, nullptr, RN_D, dh_acc, RN_D, 1);
         mm_nn(t, t.rn(), t.w.dpq + RN_D, 256, RN_D, w0 + RN_D, 3 * RN_D, nullptr, RN_D, dh_acc, RN_D, 1);
@@ -412,7 +413,7 @@ void mlp_edge_bwd_mixed(Tr& t, const Mlp2& m, const float* h, const tb16* e, con
 void mlp_edge_bwd1_pair(Tr& t, const Mlp2& me, const Mlp2& mm, const tb16* e, const tb16* dpre1_e, const tb16* dpre1_m, tb16* dE) {
     rnampnn_ctx* c = t.c;
     te_gemm_bwd1x2(t.re(), dpre1_e, dpre1_m, e, dE, rawp(c, me.w[0]) + 2 * RN_D, rawp(c, mm.w[0]) + 2 * RN_D, 3 * RN_D,
-                   t.gw(me.w[0]) + 2 * RN_D, t.gw(mm.w[0]) + 2 * RN_D, 3 * RN_D, t.w.sc, t.s);
+                   t.gw(me.w[0]) + 2 * RN_D, t.gw(mm.w[0]) + 2 * RN_D, 3 * RN_D, t.s);
 }
 }  // namespace
 
@@ -535,7 +536,6 @@ static int train_forward_impl(Tr& t, const float* coords, const float* mask, flo
         }
     }
     if (logits) launch_unpack_nodes(t.pk, w.logits_p, 4, 4, logits, s);
-    red_end();
     HIP_TRY(hipGetLastError());
     if (t.bad) return fail(RNAMPNN_ERR_UNSUPPORTED, "bf16-mixed training: a GEMM variant this configuration needs is not built");
     return RNAMPNN_OK;
@@ -550,6 +550,7 @@ static int train_backward_impl(Tr& t, int accumulate) {
     const int L = g.num_res_mpnn_layers, k = t.k;
     const size_t N = (size_t)t.pk.Nmax;
     if (!accumulate) launch_zero_bytes(t.g, c->raw_floats * sizeof(float), s, 2);
+    // one reduction queue per backward, closed on every return (the normal one reports what it refused: red_end below)
     struct RedScope { RedScope(const TScratch& sc, hipStream_t st) { red_begin(sc, st); } ~RedScope() { red_end(); } } red_scope(w.sc, s);
     {   // readout
         const float* d = w.dlogits;
@@ -570,7 +571,7 @@ static int train_backward_impl(Tr& t, int accumulate) {
         mm_tn(t, t.rn(), d, r0.out, r0.out, w.re, RN_D, RN_D, t.gw(r0.w) + RN_D, 2 * RN_D);
     }
     // raw embedding branch
-    t_gn_bwd(t.pk, w.r1, w.dre, rawp(c, c->rawffn_gn_scale), t.t_norm, w.nscr, t.gw(c->rawffn_gn_scale), t.gw(c->rawffn_gn_shift), w.sc, s);
+    t_gn_bwd(t.pk, w.r1, w.dre, rawp(c, c->rawffn_gn_scale), t.t_norm, w.nscr, t.gw(c->rawffn_gn_scale), t.gw(c->rawffn_gn_shift), s);
     ffn_bwd(t, c->raw_ffn, w.raw_p, RN_RAWP, w.raw_pre, w.nscr, nullptr, 0, site_raw(0));
     // post fusion -> dh = d h[L]
     if (bert_bwd(t, c->post, w.post, w.dhp, w.dh, site_post_att(0), site_post_ffn(0))) return fail(RNAMPNN_ERR_UNSUPPORTED, "head dim unsupported");
@@ -600,7 +601,7 @@ static int train_backward_impl(Tr& t, int accumulate) {
                     mlp_edge_bwd_mixed(t, m.edge, w.h[l + 1], eb(w.e[l]), eb(w.pu1[l]), eb(w.dE), w.dh, site_edge(l, 0));
                 }
             }
-            t_gn_bwd(t.pk, w.hpre[l], w.dh, rawp(c, m.gn_scale), t.t_norm, w.dh2, t.gw(m.gn_scale), t.gw(m.gn_shift), w.sc, s);
+            t_gn_bwd(t.pk, w.hpre[l], w.dh, rawp(c, m.gn_scale), t.t_norm, w.dh2, t.gw(m.gn_scale), t.gw(m.gn_shift), s);
             if (m.msg.depth > 1 && !nofold) {          // ... and so does the backward of the message mean (dagg = dh2)
                 launch_copy_bytes(w.dh, w.dh2, N * RN_D * sizeof(float), s);
                 EBwd2Src from{2, eb(w.pm2[l]), w.nbr, w.dh2, w.invc, k, site_msg(l, 1), tape_g2() ? 1 : 0};
@@ -619,7 +620,7 @@ static int train_backward_impl(Tr& t, int accumulate) {
             mlp_edge_bwd(t, m.edge, w.h[l + 1], w.e[l], w.pu1[l], w.dE, w.dh, site_edge(l, 0));
         }
         // GraphNorm: dh = d h[l+1] -> dh2 = d hpre[l]
-        t_gn_bwd(t.pk, w.hpre[l], w.dh, rawp(c, m.gn_scale), t.t_norm, w.dh2, t.gw(m.gn_scale), t.gw(m.gn_shift), w.sc, s);
+        t_gn_bwd(t.pk, w.hpre[l], w.dh, rawp(c, m.gn_scale), t.t_norm, w.dh2, t.gw(m.gn_scale), t.gw(m.gn_shift), s);
         // hpre = h[l] + agg: d h[l] starts as dh2; messages get d agg = dh2
         const float* plast = m.msg.depth > 1 ? w.pm2[l] : w.pm1[l];
         t_seg_mean_bwd(t.pk, k, w.nbr, w.dh2, plast, w.E2, t.dr, site_msg(l, m.msg.depth - 1), s);        // E2 = d pre_last of the message MLP
@@ -628,7 +629,7 @@ static int train_backward_impl(Tr& t, int accumulate) {
     }
     if (L / 2 == 0) { red_flush(); if (c->grad_ev[1]) HIP_TRY(hipEventRecord(c->grad_ev[1], s)); }              // (L == 1: chunk 1 = the one layer)
     // ResFeature: node side  dh = d h[0]
-    t_gn_bwd(t.pk, w.n1, w.dh, rawp(c, c->feat_gn_scale), t.t_norm, w.dh2, t.gw(c->feat_gn_scale), t.gw(c->feat_gn_shift), w.sc, s);
+    t_gn_bwd(t.pk, w.n1, w.dh, rawp(c, c->feat_gn_scale), t.t_norm, w.dh2, t.gw(c->feat_gn_scale), t.gw(c->feat_gn_shift), s);
     if (bert_bwd(t, c->emb, w.emb, w.dh2, w.dh, site_emb_att(0), site_emb_ffn(0))) return fail(RNAMPNN_ERR_UNSUPPORTED, "head dim unsupported");
     lin_bwd(t, c->raw_project, w.raw_p, RN_RAWP, w.dh, RN_D, nullptr, 0);
     // ResFeature: edge side  dE = d e[0] (masked output of the embedding MLP)
@@ -638,12 +639,12 @@ static int train_backward_impl(Tr& t, int accumulate) {
         if (g.depth_res_edge_feature > 1) {
             const Lin& ee1 = c->edge_embed[1];
             te_edge_res_bwd(t.pk, k, w.nbr, eb(w.dE), eb(w.pe2), eb(w.E2), t.dr, site_ee(1), s);                              // d pe2 (absent edges: 0)
-            te_gemm_tn(t.re(), eb(w.E2), eb(w.pe1), t.gw(ee1.w), RN_D, w.sc, true, t.dr, site_ee(0), t.gw(ee1.b), s);
+            te_gemm_tn(t.re(), eb(w.E2), eb(w.pe1), t.gw(ee1.w), RN_D, true, t.dr, site_ee(0), t.gw(ee1.b), s);
             t.bad |= !te_gemm(t.re(), w.E2, true, RN_D, rawp(c, ee1.w), RN_D, false, nullptr, dpe1, 0, false, eb(w.pe1), nullptr, t.dr, site_ee(0), s);   // d pe1
         } else {
             te_edge_res_bwd(t.pk, k, w.nbr, eb(w.dE), eb(w.pe1), dpe1, t.dr, site_ee(0), s);
         }
-        te_gemm_tn(t.re(), dpe1, eb(w.F), t.gw(ee0.w), RN_ERAW, w.sc, false, t.dr, 0u, t.gw(ee0.b), s, RN_ERAW);
+        te_gemm_tn(t.re(), dpe1, eb(w.F), t.gw(ee0.w), RN_ERAW, false, t.dr, 0u, t.gw(ee0.b), s, RN_ERAW);
     } else {
         const Lin& ee0 = c->edge_embed[0];
         t_edge_zero_invalid(t.pk, k, w.nbr, w.dE, s);
@@ -659,8 +660,10 @@ static int train_backward_impl(Tr& t, int accumulate) {
         }
         mm_tn(t, t.re(), w.E1, RN_D, RN_D, w.F, RN_ERAWP, RN_ERAW, t.gw(ee0.w), RN_ERAW, t.gw(ee0.b));
     }
+    t.bad |= !red_end();
     HIP_TRY(hipGetLastError());
-    if (t.bad) return fail(RNAMPNN_ERR_UNSUPPORTED, "bf16-mixed training: a GEMM variant this configuration needs is not built");
+    if (t.bad) return fail(RNAMPNN_ERR_UNSUPPORTED, "training backward: a GEMM variant this configuration needs is not built, or the reduction "
+                           "queue refused a request (kernels_train.hip: RedQueue)");
     return RNAMPNN_OK;
 }
 
@@ -744,7 +747,7 @@ extern "C" int rnampnn_loss_and_grad(rnampnn_handle h, const float* coords, cons
     tape_drop_ws(h, ws);
     rc = train_forward_impl(t, coords, mask, logits);
     if (rc) { t_wimg_bind(nullptr); return rc; }
-    t_loss_grad(t.pk, t.w.logits_p, labels, t.w.dlogits, loss, t.w.sc, t.s);
+    t_loss_grad(t.pk, t.w.logits_p, labels, t.w.dlogits, loss, t.w.sc.p, t.s);
     rc = train_backward_impl(t, 0);
     t_wimg_bind(nullptr);
     return rc;
