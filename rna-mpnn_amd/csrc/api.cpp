@@ -619,8 +619,6 @@ static void node_pq(Run& r, const Mlp2& m, const float* h, bool edge) {
                         derp<float>(c, m.pq_b), 256, 0, nullptr, 0, edge ? r.w.pq_e : r.w.pq_m, 256, r.s);
 }
 
-static bool embed_fused_env() { const char* v = getenv("RNAMPNN_EMBED_FUSED"); return !(v && v[0] == '0'); }      // RNAMPNN_EMBED_FUSED=0: two launches (A/B; read per call)
-
 static MpnnW32 w32(rnampnn_ctx* c, const Mlp2& m) {
     MpnnW32 w;
     w.wc_t = derp<float>(c, m.wc_t);
@@ -767,7 +765,7 @@ static int forward_core(Run& r, rnampnn_handle h, const RnaMpnnForwardIO* io, co
     if (rc) return rc;
     if (launch_knn(io->coords, r.pk, k, w.nbr, io->edge_index, s))
         return fail(RNAMPNN_ERR_UNSUPPORTED, "max_len %d too long for the LDS-resident k-NN row", io->T);
-    const bool embed_first = fused_first && L >= 1 && !io->e0 && resmpnn_covers(k, false, false) && embed_fused_env();
+    const bool embed_first = fused_first && L >= 1 && !io->e0 && resmpnn_covers(k, false, false) && !ab_switch("RNAMPNN_EMBED_TWO_LAUNCH");
     if (embed_first) { }
     else if (r.fast)
         launch_edge_embed_bf16(r.pk, k, w.geomh, w.nbr, derp<bf16_t>(c, c->edge_embed_img), rawp(c, c->edge_embed[0].b),

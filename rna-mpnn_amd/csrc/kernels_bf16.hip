@@ -1599,9 +1599,8 @@ void launch_node_update(const PackInfo& pk, const float* x, const float* add, co
                         float* coef, float* h_out, int njobs, const NodeJob& job0, const NodeJob& job1, hipStream_t s) {
     const PqJob j0 = job0, j1 = njobs > 1 ? job1 : NodeJob{};
     // Every RNA of the batch fits the rows of one workgroup (padded length <= 256) and is long enough for a workgroup of its own: the statistics
-    // are computed inside the update kernel (RNAMPNN_NODE_UPDATE_RNA=0: the two-launch form; read per call)
-    static const auto rna_form_env = []() { const char* v = getenv("RNAMPNN_NODE_UPDATE_RNA"); return !(v && v[0] == '0'); };
-    if (scale && pk.T >= 48 && pk.T <= 256 && rna_form_env()) {
+    // are computed inside the update kernel (RNAMPNN_NODE_UPDATE_TWO_LAUNCH=1: the two-launch form)
+    if (scale && pk.T >= 48 && pk.T <= 256 && !ab_switch("RNAMPNN_NODE_UPDATE_TWO_LAUNCH")) {
 #define NU_RNA(J, NBK)                                                                                                          \
         do {                                                                                                                    \
             static DevAttr attr;                                                                                                \
@@ -1980,8 +1979,7 @@ __global__ void __launch_bounds__(AL_NW * 64) k_attn_layer_rna(PackInfo pk, floa
 // wqkv / wout: the fragment images of launch_build_attn_images.
 int launch_attn_layer_rna(const PackInfo& pk, float* x, const bf16_t* wqkv, const float* bqkv, const bf16_t* wout, const float* bout,
                           int heads, const float* gscale, const float* gshift, int t_tot, hipStream_t s) {
-    static const bool off = [] { const char* e = getenv("RNAMPNN_NO_ATTN_FUSE"); return e && e[0] == '1'; }();
-    if (off || heads != 8 || pk.T > AL_NR) return 1;
+    if (heads != 8 || pk.T > AL_NR) return 1;
     static DevAttr attr;
     ensure_dyn_lds((const void*)k_attn_layer_rna, AL_LDS, attr);
     hipLaunchKernelGGL(k_attn_layer_rna, dim3(pk.B), dim3(AL_NW * 64), AL_LDS, s, pk, x, wqkv, bqkv, wout, bout, gscale, gshift, t_tot);

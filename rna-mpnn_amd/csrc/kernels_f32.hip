@@ -97,15 +97,8 @@ __global__ void k_zero_bytes(uint4* __restrict__ p, size_t n16, unsigned char* _
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) p[i] = z;
     if (blockIdx.x == 0 && (int)threadIdx.x < ntail) tail[threadIdx.x] = 0;
 }
-// RNAMPNN_DBG_MEMNODE (diagnostic, read per call): bit 0 routes launch_zero_bytes through hipMemsetAsync, bit 1 launch_copy_bytes through
-// hipMemcpyAsync - the forms round 3 replaced - so that the captured training step can be compared with and without runtime memset / copy nodes
-// RNAMPNN_DBG_MEMNODE_SITES: bit mask of the launch_zero_bytes call sites (1 row zeroes of the taped forward, 2 flat gradient, 4 dE, 8 reverse-
-// adjacency counts) that take the runtime path; default all
-static int dbg_memnode() { const char* e = getenv("RNAMPNN_DBG_MEMNODE"); return e ? atoi(e) : 0; }
-static int dbg_memnode_sites() { const char* e = getenv("RNAMPNN_DBG_MEMNODE_SITES"); return e ? atoi(e) : 0xff; }
-void launch_zero_bytes(void* ptr, size_t bytes, hipStream_t s, int site) {       // ptr 16-byte aligned
+void launch_zero_bytes(void* ptr, size_t bytes, hipStream_t s) {       // ptr 16-byte aligned
     if (!bytes) return;
-    if ((dbg_memnode() & 1) && (dbg_memnode_sites() & site)) { (void)hipMemsetAsync(ptr, 0, bytes, s); return; }
     const size_t n16 = bytes / 16;
     size_t g = (n16 + 255) / 256;
     if (g > 2048) g = 2048;
@@ -119,7 +112,6 @@ __global__ void k_copy16(const uint4* __restrict__ src, uint4* __restrict__ dst,
 void launch_copy_bytes(void* dst, const void* src, size_t bytes, hipStream_t s) {       // both 16-byte aligned, bytes a multiple of 16
     const size_t n16 = bytes / 16;
     if (!n16) return;
-    if (dbg_memnode() & 2) { (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s); return; }
     size_t g = (n16 + 255) / 256;
     if (g > 2048) g = 2048;
     hipLaunchKernelGGL(k_copy16, dim3((unsigned)g), dim3(256), 0, s, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), n16);
@@ -510,8 +502,7 @@ __global__ void __launch_bounds__(256) k_knn_queue(const float* __restrict__ coo
 }
 
 int launch_knn(const float* coords, const PackInfo& pk, int k, int* nbr, int64_t* eidx, hipStream_t s) {
-    static const bool no_queue = [] { const char* e = getenv("RNAMPNN_KNN_SCAN"); return e && e[0] == '1'; }();
-    if (!no_queue && pk.T <= 256) {                  // register-resident sorted queues
+    if (pk.T <= 256) {                  // register-resident sorted queues
         const int rpb = 32;
         dim3 grid(pk.B, (pk.T + rpb - 1) / rpb);
         const size_t lds = (size_t)3 * pk.T * sizeof(float);

@@ -515,8 +515,8 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
 #undef RM_FRAG
 }
 
-static bool rm_enabled() { const char* v = getenv("RNAMPNN_MPNN_V3"); return !(v && v[0] == '1'); }      // RNAMPNN_MPNN_V3=1: the round-3 kernel (A/B; read per call)
-bool resmpnn_covers(int k, bool edge1, bool msg_out) { return k > 16 && k <= 32 && !edge1 && !msg_out && rm_enabled(); }
+// RNAMPNN_MPNN_V3=1: the round-3 kernel (A/B switch)
+bool resmpnn_covers(int k, bool edge1, bool msg_out) { return k > 16 && k <= 32 && !edge1 && !msg_out && !ab_switch("RNAMPNN_MPNN_V3"); }
 
 void launch_resmpnn_bf16(const PackInfo& pk, int k, bool do_edge, bool do_msg, const int* nbr, bf16_t* e, const bf16_t* p_e, const bf16_t* q_e,
                          const bf16_t* p_m, const bf16_t* q_m, MpnnWB we, MpnnWB wm, float* agg, const float* h_res, hipStream_t s) {

@@ -94,11 +94,11 @@ struct EFuse {                       // optional epilogue fusions of te_gemm
     const tb16* res_in; tb16* res_out;   // res_out = res_in + (nbr[row] >= 0 ? drop(gelu(v), site2) : 0)     (edge update, mpnn.py:250-262)
     unsigned site2;
 };
-// Y[R][128] (bf16) = [beta Y] + actA(X)[R][128] . W' + bias, [* gelu'(epi_pre) * mask(site)]; W' = W^T (w_rows: W [128][ldw] as
+// Y[R][128] (bf16) = actA(X)[R][128] . W' + bias, [* gelu'(epi_pre) * mask(site)]; W' = W^T (w_rows: W [128][ldw] as
 // nn.Linear stores it) or W (W [128][ldw] k-major).  X is bf16 (x_bf16) or f32, row stride ldx.  Returns false (nothing launched) for a
 // combination of options that is not instantiated.
 bool te_gemm(const TRows& rows, const void* X, bool x_bf16, int ldx, const float* W, int ldw, bool w_rows, const float* bias, tb16* Y,
-             int beta, bool actA, const tb16* epi_pre, const EFuse* fuse, const TDrop& dr, unsigned site, hipStream_t s, int kvalid = 128);   // kvalid: live columns of X (the rest is zero padding)
+             bool actA, const tb16* epi_pre, const EFuse* fuse, const TDrop& dr, unsigned site, hipStream_t s, int kvalid = 128);   // kvalid: live columns of X (the rest is zero padding)
 // dW[128][ldw] += A^T . actB(B), dbias += colsum(A)     (A, B bf16 [R][128])
 void te_gemm_tn(const TRows& rows, const tb16* A, const tb16* B, float* dW, int ldw, bool actB, const TDrop& dr,
                 unsigned site, float* dbias, hipStream_t s, int cols_keep = 128);      // cols_keep: live columns of B
@@ -107,22 +107,23 @@ void te_gemm_pq(const TRows& rows, const float* h, const float* w0, const float*
 void tm_gemm_tn_pq(const TRows& rows, const float* dpq, const float* h, float* gw0, float* db1, hipStream_t s);
 bool tm_gemm_nn_pq(const TRows& rows, const float* dpq, const float* w0, float* dh, hipStream_t s);
 // forward of a depth-2 per-edge MLP in one kernel (the hidden activation stays in registers; pre1 / pre2 written once as the tape;
-// pre1 = null: not kept)
+// pre1 = null: not kept).  pre1 is taped with its dropped elements replaced by TE_DROPPED; with f.res_out (edge update) pre2 receives
+// gelu'(pre2) * mask(site2) - the tapes te_gemm_bwd2 reads
 void te_mlp2_fwd(const TRows& rows, const tb16* X, const float* W1, int ldw1, const float* W2, int ldw2, const float* bias2, tb16* pre1,
-                 tb16* pre2, const EFuse& f, const TDrop& dr, unsigned site, hipStream_t s, bool g2tape = false);   // g2tape (edge update only): pre2 receives gelu'(pre2) * mask(site2)
+                 tb16* pre2, const EFuse& f, const TDrop& dr, unsigned site, hipStream_t s);
 // fused pair of a first Linear's backward: dW += dY^T X, DE += dY . W   (one pass over dY)
 void te_gemm_bwd1(const TRows& rows, const tb16* dY, const tb16* X, tb16* DE, const float* W, int ldw, float* dW, int ldw_out,
                   hipStream_t s);
-// fused pair of a depth-2 MLP's backward: dW += dY^T drop(gelu(PRE)), dbias += colsum(dY), DX = (dY . W) gelu'(PRE) mask   (one pass over dY and PRE)
-// `from` (optional): d pre2 is formed on the fly while the tile is staged - mode 1: dY = d e_out, d pre2 = valid ? dY gelu'(pre2) mask(site2) : 0
-// (the edge update's residual backward); mode 2: d pre2 = valid ? dagg[row / k] inv_cnt[row / k] gelu'(pre2) mask(site2) : 0 (the message mean's)
-// g2tape: the `pre2` tensor holds gelu'(pre2) * mask(site2) as the forward left it (k_emm_fwd2 / k_eseg_mean, below) instead of pre2: the staging pass
-// multiplies, where it evaluated a sigmoid, an exp2 and a dropout hash per element
-struct EBwd2Src { int mode; const tb16* pre2; const int* nbr; const float* dagg; const float* inv_cnt; int k; unsigned site2; int g2tape; };
+// fused pair of a depth-2 MLP's backward: dW += d pre2^T drop(gelu(PRE)), dbias += colsum(d pre2), DX = (d pre2 . W) gelu'(PRE) mask   (one pass
+// over PRE).  d pre2 is formed on the fly while the tile is staged - mode 1: dY = d e_out, d pre2 = valid ? dY gelu'(pre2) mask(site2) : 0 (the
+// edge update's residual backward); mode 2: d pre2 = valid ? dagg[row / k] inv_cnt[row / k] gelu'(pre2) mask(site2) : 0 (the message mean's).
+// The `pre2` tensor holds gelu'(pre2) * mask(site2) as the forward left it (k_emm_fwd2 / k_eseg_mean, below) and PRE the TE_DROPPED tape of
+// k_emm_fwd2: the staging pass multiplies, and evaluates no dropout hash
+struct EBwd2Src { int mode; const tb16* pre2; const int* nbr; const float* dagg; const float* inv_cnt; int k; };
 void te_gemm_bwd1x2(const TRows& rows, const tb16* dY1, const tb16* dY2, const tb16* X, tb16* DE, const float* W1, const float* W2, int ldw,
                     float* dW1, float* dW2, int ldw_out, hipStream_t s);
 void te_gemm_bwd2(const TRows& rows, const tb16* dY, const tb16* PRE, tb16* DX, const float* W, int ldw, float* dW, int ldw_out,
-                  const TDrop& dr, unsigned site, float* dbias, hipStream_t s, const EBwd2Src* from = nullptr);
+                  const TDrop& dr, float* dbias, hipStream_t s, const EBwd2Src& from);
 void te_inv_count(const PackInfo& pk, int k, const int* nbr, float* inv_cnt, hipStream_t s);   // 1 / max(#valid slots, 1) per residue
 // g2_out (optional, may alias pre2): gelu'(pre2) * mask(site) per element - what the message MLP's backward needs of pre2
 void te_seg_mean(const PackInfo& pk, int k, const int* nbr, const tb16* pre2, const float* h, float* out, const TDrop& dr, unsigned site, hipStream_t s,

@@ -185,8 +185,7 @@ static void red_launch() {
 void red_flush() { red_launch(); g_rq.used = 0; }
 void red_begin(const TScratch& arena, hipStream_t s) {
     RedQueue& q = g_rq;
-    const char* one = getenv("RNAMPNN_NO_RED_BATCH");      // A/B switch (read per call)
-    q.active = true; q.one = one && one[0] == '1';
+    q.active = true; q.one = ab_switch("RNAMPNN_NO_RED_BATCH");
     q.arena = arena.p; q.floats = arena.floats; q.used = 0; q.s = s; q.b.n = 0; q.blocks = 0;
 }
 bool red_end() {
@@ -566,7 +565,7 @@ __global__ void k_rev_rank(PackInfo pk, const int* __restrict__ nbr, const int* 
     }
 }
 void t_build_reverse(const PackInfo& pk, int k, const int* nbr, int* deg, int* start, int* fill, int* list, int* tmp, hipStream_t s) {
-    launch_zero_bytes(deg, (size_t)pk.Nmax * sizeof(int), s, 8);
+    launch_zero_bytes(deg, (size_t)pk.Nmax * sizeof(int), s);
     size_t E = (size_t)pk.Nmax * k;
     unsigned g = (unsigned)((E + 255) / 256); if (g > 8192) g = 8192; if (g < 1) g = 1;
     hipLaunchKernelGGL(k_rev_count, dim3(g), dim3(256), 0, s, pk, k, nbr, deg);
@@ -713,8 +712,7 @@ void t_gn_bwd(const PackInfo& pk, const float* x, const float* dy, const float* 
     // per-RNA partials of (dscale, dshift), added in RNA order: B * 256 floats, then the split form's per-split sums
     const int nsplit = (pk.T + GN_SPLIT_ROWS - 1) / GN_SPLIT_ROWS;
     const size_t need = (size_t)pk.B * 256 + (size_t)pk.B * nsplit * 512;
-    const char* nosplit = getenv("RNAMPNN_GN_NOSPLIT");          // A/B switch (read per call)
-    const bool split = pk.T > GN_SPLIT_T && need <= RED_VIEW && !(nosplit && nosplit[0] == '1');
+    const bool split = pk.T > GN_SPLIT_T && need <= RED_VIEW;
     float* part = red_alloc(split ? need : (size_t)pk.B * 256);
     if (!part) return;
     if (split) {
@@ -1672,7 +1670,7 @@ struct EmmArgs {
     TRows rows;
     const void* X; int ldx;
     const float* W; int ldw; const float* bias;
-    tb16* Y; int beta; int actA; const tb16* epi_pre;
+    tb16* Y; int actA; const tb16* epi_pre;
     EFuse f; int has_pq, has_res;
     TDrop dr; unsigned site;
     const unsigned short* wimg;      // prebuilt fragment image of W (WImageCache) or null
@@ -1689,9 +1687,11 @@ struct EmmArgs {
 // wave's loads and VALU run under the other's MFMAs, the next tile's X and THIS tile's epilogue operands are requested before the MFMA
 // block, and every load of the epilogue sits in registers before the first store (stores would otherwise fence the later loads: the
 // compiler cannot prove that Y does not alias them).
-// EP: 0 none, 1 + P[row / k] + Q[nbr[row]], 2 * gelu'(pre) * mask, 3 + old Y;  ACT: X' = drop(gelu(X));  RES: second output res_in + drop(gelu(v))
+// EP: 0 none, 1 + P[row / k] + Q[nbr[row]], 2 * gelu'(pre) * mask;  ACT: X' = drop(gelu(X));  RES (EP 1: depth-1 edge update): second output
+// res_in + drop(gelu(v))
 template <bool B_ROWS, typename TX, int EP, bool ACT, bool RES>
 __global__ void __launch_bounds__(256, 2) k_emm128(EmmArgs a) {
+    static_assert(!RES || EP == 1, "the residual epilogue rides with the P + Q one");
     __shared__ __attribute__((aligned(16))) unsigned short img[32 * 64 * 8];      // [ks][cb][lane][8] bf16 A fragments
     __shared__ __attribute__((aligned(16))) float lds_bias[128];
     const int R = nrows(a.rows);
@@ -1706,7 +1706,7 @@ __global__ void __launch_bounds__(256, 2) k_emm128(EmmArgs a) {
     const int tstride = gridDim.x * 4;
     const unsigned key1 = drop_key(a.dr, a.site), key2 = drop_key(a.dr, a.f.site2);
     constexpr bool XB = sizeof(TX) == 2;
-    constexpr bool NEED_J = EP == 1 || RES;
+    constexpr bool NEED_J = EP == 1;
     tu32x4 rawb[XB ? 8 : 1];           // bf16 X: the fragments themselves
     tf32x4 rawf[XB ? 1 : 16];          // f32 X
     int jn = -1;                       // neighbour of the prefetched tile's row
@@ -1735,7 +1735,7 @@ __global__ void __launch_bounds__(256, 2) k_emm128(EmmArgs a) {
         const int rowc = rok ? row : R - 1;
         const int j = jn;
         // ---- epilogue operands of this tile, group u = channels 16u + 8h .. +7 of this lane's row
-        tu32x4 e0[EP ? 8 : 1], e1[(EP == 1 || RES) ? 8 : 1];      // e0: P row | taped pre-activation | old Y;  e1: Q row | residual input
+        tu32x4 e0[EP ? 8 : 1], e1[EP == 1 ? 8 : 1];      // e0: P row | taped pre-activation;  e1: Q row
         {
             const size_t ro = (size_t)rowc * 128 + 8 * h;
             if constexpr (EP == 1) {
@@ -1746,13 +1746,6 @@ __global__ void __launch_bounds__(256, 2) k_emm128(EmmArgs a) {
             } else if constexpr (EP == 2) {
 #pragma unroll
                 for (int u = 0; u < 8; ++u) e0[u] = *reinterpret_cast<const tu32x4*>(a.epi_pre + ro + 16 * u);
-            } else if constexpr (EP == 3) {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) e0[u] = *reinterpret_cast<const tu32x4*>(Yp + ro + 16 * u);
-            }
-            if constexpr (RES && EP != 1) {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) e1[u] = *reinterpret_cast<const tu32x4*>(a.f.res_in + ro + 16 * u);
             }
         }
         tu32x4 xf[8];
@@ -1825,17 +1818,11 @@ __global__ void __launch_bounds__(256, 2) k_emm128(EmmArgs a) {
                     drop8(a.dr, key1, (unsigned)row * 16u + (c >> 3), dm);
 #pragma unroll
                     for (int q = 0; q < 8; ++q) v[q] *= gelu_d_fast(pr[q]) * dm[q];
-                } else if constexpr (EP == 3) {
-                    float old[8];
-                    unpack8(e0[u], old);
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) v[q] += old[q];
                 }
                 yo[uu] = tpack8(v);
                 if constexpr (RES) {
                     float ei[8];
-                    if constexpr (EP == 1) unpack8(*reinterpret_cast<const tu32x4*>(a.f.res_in + (size_t)rowc * 128 + c), ei);   // (depth-1 MLPs only)
-                    else unpack8(e1[u], ei);
+                    unpack8(*reinterpret_cast<const tu32x4*>(a.f.res_in + (size_t)rowc * 128 + c), ei);
                     if (j >= 0) {
                         float dm[8];
                         drop8(a.dr, key2, (unsigned)row * 16u + (c >> 3), dm);
@@ -1859,9 +1846,9 @@ __global__ void __launch_bounds__(256, 2) k_emm128(EmmArgs a) {
     }
 }
 bool te_gemm(const TRows& rows, const void* X, bool x_bf16, int ldx, const float* W, int ldw, bool w_rows, const float* bias, tb16* Y,
-             int beta, bool actA, const tb16* epi_pre, const EFuse* fuse, const TDrop& dr, unsigned site, hipStream_t s, int kvalid) {
+             bool actA, const tb16* epi_pre, const EFuse* fuse, const TDrop& dr, unsigned site, hipStream_t s, int kvalid) {
     EmmArgs a;
-    a.rows = rows; a.X = X; a.ldx = ldx; a.W = W; a.ldw = ldw; a.bias = bias; a.Y = Y; a.beta = beta; a.actA = actA ? 1 : 0;
+    a.rows = rows; a.X = X; a.ldx = ldx; a.W = W; a.ldw = ldw; a.bias = bias; a.Y = Y; a.actA = actA ? 1 : 0;
     a.epi_pre = epi_pre; a.dr = dr; a.site = site;
     if (fuse) a.f = *fuse; else a.f = EFuse{nullptr, nullptr, nullptr, 1, 0, nullptr, nullptr, 0u};
     a.has_pq = a.f.P != nullptr; a.has_res = a.f.res_out != nullptr;
@@ -1871,16 +1858,14 @@ bool te_gemm(const TRows& rows, const void* X, bool x_bf16, int ldx, const float
     int g = (rows.maxrows + 127) / 128;                      // 4 waves x one 32-row tile each
     const int cap = 2 * rn_num_cus();                        // two workgroups per CU (two waves per SIMD)
     const dim3 grid(g > cap ? cap : (g < 1 ? 1 : g));
-    const int ep = a.has_pq ? 1 : (epi_pre ? 2 : (beta ? 3 : 0));
+    const int ep = a.has_pq ? 1 : (epi_pre ? 2 : 0);
 #define EMM_GO(BR, TXT, EPV, ACTV, RESV) hipLaunchKernelGGL((k_emm128<BR, TXT, EPV, ACTV, RESV>), grid, dim3(256), 0, s, a)
     if (!x_bf16 && w_rows && ep == 0 && !actA && !a.has_res) EMM_GO(true, float, 0, false, false);                 // node rows -> bf16 P / Q tables
     else if (x_bf16 && w_rows && ep == 0 && !actA && !a.has_res) EMM_GO(true, tb16, 0, false, false);             // edge embedding: raw features -> pe1
     else if (x_bf16 && w_rows && ep == 1 && !actA && !a.has_res) EMM_GO(true, tb16, 1, false, false);             // first Linear + P + Q
     else if (x_bf16 && w_rows && ep == 1 && !actA && a.has_res) EMM_GO(true, tb16, 1, false, true);               // ... of a depth-1 edge update
     else if (x_bf16 && w_rows && ep == 0 && actA && !a.has_res) EMM_GO(true, tb16, 0, true, false);               // second Linear (message)
-    else if (x_bf16 && w_rows && ep == 0 && actA && a.has_res) EMM_GO(true, tb16, 0, true, true);                 // second Linear + edge update
     else if (x_bf16 && !w_rows && ep == 2 && !actA && !a.has_res) EMM_GO(false, tb16, 2, false, false);           // d pre1 = (d pre2 . W2) gelu' mask
-    else if (x_bf16 && !w_rows && ep == 3 && !actA && !a.has_res) EMM_GO(false, tb16, 3, false, false);           // dE += d pre1 . Wc
     else return false;                                   // combination not instantiated: nothing was launched
 #undef EMM_GO
     return true;
@@ -1889,7 +1874,7 @@ bool te_gemm(const TRows& rows, const void* X, bool x_bf16, int ldx, const float
 // P = h Wa^T + b1 and Q = h Wb^T (bf16 tables [rows][128]) in one launch: w0 = [128][384] weight, Wa = columns 0..127, Wb = columns 128..255
 void te_gemm_pq(const TRows& rows, const float* h, const float* w0, const float* b1, tb16* Pt, tb16* Qt, hipStream_t s) {
     EmmArgs a;
-    a.rows = rows; a.X = h; a.ldx = 128; a.W = w0; a.ldw = 3 * 128; a.bias = b1; a.Y = Pt; a.beta = 0; a.actA = 0; a.epi_pre = nullptr;
+    a.rows = rows; a.X = h; a.ldx = 128; a.W = w0; a.ldw = 3 * 128; a.bias = b1; a.Y = Pt; a.actA = 0; a.epi_pre = nullptr;
     a.dr = TDrop{0ull, 0u, 1.f}; a.site = 0u;
     a.f = EFuse{nullptr, nullptr, nullptr, 1, 0, nullptr, nullptr, 0u};
     a.has_pq = 0; a.has_res = 0; a.kvalid = 128;
@@ -1916,10 +1901,10 @@ struct Emm2Args {
     tb16* pre1; tb16* pre2;
     EFuse f;                         // P, Q, nbr, k, zero_row ; res_out (optional), site2
     TDrop dr; unsigned site;         // dropout site of the hidden activation
-    int g2tape;                      // RES: pre2 receives gelu'(pre2) * mask(site2) - all the backward needs of it - instead of pre2
-    int p1mask;                      // pre1 is taped with its DROPPED elements replaced by TE_DROPPED (gelu = gelu' = 0 there): the backward needs no hash
 };
-template <bool RES, bool TAPE1>       // TAPE1: pre1 is written (training tape); inference callers keep only pre2
+// TAPE1: pre1 is written (training tape) with its DROPPED elements replaced by TE_DROPPED (gelu = gelu' = 0 there): the backward needs no hash;
+// inference callers keep only pre2.  RES: pre2 receives gelu'(pre2) * mask(site2) - all the backward needs of it - instead of pre2
+template <bool RES, bool TAPE1>
 // tape stores (written once, read a whole backward later): TE_EXP_NT_TAPE builds them as non-temporal stores - measured 30.3 ms per step at the C2
 // batch against 23.6 (the 16-byte-per-lane pieces of a row no longer merge in L2): kept as the experiment's switch only
 #ifdef TE_EXP_NT_TAPE
@@ -2006,14 +1991,10 @@ __global__ void __launch_bounds__(256, 2) k_emm_fwd2(Emm2Args a) {
             const tu32x4 y = tpack8(v);
             drop8(a.dr, key1, (unsigned)row * 16u + 2 * u + h, dm);
             if (TAPE1 && rok) {
-                if (a.p1mask) {                  // (uniform)
-                    float vm[8];
+                float vm[8];
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) vm[q] = dm[q] != 0.f ? v[q] : TE_DROPPED;
-                    TE_TAPE_STORE(a.pre1 + (size_t)row * 128 + 16 * u + 8 * h, tpack8(vm));
-                } else {
-                    TE_TAPE_STORE(a.pre1 + (size_t)row * 128 + 16 * u + 8 * h, y);
-                }
+                for (int q = 0; q < 8; ++q) vm[q] = dm[q] != 0.f ? v[q] : TE_DROPPED;
+                TE_TAPE_STORE(a.pre1 + (size_t)row * 128 + 16 * u + 8 * h, tpack8(vm));
             }
             unpack8(y, v);
 #pragma unroll
@@ -2033,17 +2014,12 @@ __global__ void __launch_bounds__(256, 2) k_emm_fwd2(Emm2Args a) {
                 float ei[8], dm[8];
                 unpack8(xe[u], ei);
                 drop8(a.dr, key2, (unsigned)row * 16u + 2 * u + h, dm);
-                if (a.g2tape) {                  // (uniform) the tape gets gelu' * mask, evaluated on the unrounded pre-activation, sharing the sigmoid with the update
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        float g, d;
-                        gelu_both_fast(v[q], g, d);
-                        if (j >= 0) ei[q] += g * dm[q];
-                        v[q] = d * dm[q];
-                    }
-                } else if (j >= 0) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) ei[q] += gelu_fast(v[q]) * dm[q];
+                for (int q = 0; q < 8; ++q) {    // the tape gets gelu' * mask, evaluated on the unrounded pre-activation, sharing the sigmoid with the update
+                    float g, d;
+                    gelu_both_fast(v[q], g, d);
+                    if (j >= 0) ei[q] += g * dm[q];
+                    v[q] = d * dm[q];
                 }
                 if (rok) TE_TAPE_STORE(a.pre2 + (size_t)row * 128 + c, tpack8(v));
                 if (rok) *reinterpret_cast<tu32x4*>(a.f.res_out + (size_t)row * 128 + c) = tpack8(ei);
@@ -2055,10 +2031,8 @@ __global__ void __launch_bounds__(256, 2) k_emm_fwd2(Emm2Args a) {
 }
 // pre1 = X . W1^T + P[row / k] + Q[nbr[row]] ; pre2 = drop(gelu(pre1), site) . W2^T + bias2 ; [res_out = X + valid drop(gelu(pre2), site2)]
 void te_mlp2_fwd(const TRows& rows, const tb16* X, const float* W1, int ldw1, const float* W2, int ldw2, const float* bias2, tb16* pre1,
-                 tb16* pre2, const EFuse& f, const TDrop& dr, unsigned site, hipStream_t s, bool g2tape) {
+                 tb16* pre2, const EFuse& f, const TDrop& dr, unsigned site, hipStream_t s) {
     Emm2Args a;
-    a.g2tape = (g2tape && f.res_out) ? 1 : 0;
-    a.p1mask = (g2tape && pre1) ? 1 : 0;
     a.rows = rows; a.X = X; a.W1 = W1; a.ldw1 = ldw1; a.W2 = W2; a.ldw2 = ldw2; a.bias2 = bias2; a.pre1 = pre1; a.pre2 = pre2; a.f = f;
     a.dr = dr; a.site = site;
     a.wimg1 = wimg_lookup(W1, ldw1, true, 1); a.wimg2 = wimg_lookup(W2, ldw2, true, 1);
@@ -2202,15 +2176,16 @@ __device__ __forceinline__ void gelu_both_fast(float x, float& g, float& d) {   
     g = x * sg;
     d = fmaf(x * 0.3989422804f, __builtin_amdgcn_exp2f(x * x * -0.72134752f), sg);
 }
-// MODE: where d pre2 comes from.  0: the tensor dY.  1 (edge update, mpnn.py:250-262): d pre2 = valid ? dY * gelu'(PRE2) * mask(site2) : 0 with
-// dY = d e_out - the residual backward formed while the tile is staged instead of by a kernel of its own (one read and one write of an
-// [E][128] tensor less).  2 (message mean, mpnn.py:212-219): d pre2 = valid ? dagg[row / k] / cnt[row / k] * gelu'(PRE2) * mask(site2) : 0.
-// The staged values are rounded to bf16 exactly as the stand-alone kernels stored them: results are bit-identical to the two-kernel form.
-struct Bwd2Src { const tb16* pre2; const int* nbr; const float* dagg; const float* inv_cnt; int k; unsigned site2; int g2tape; };
+// MODE: where d pre2 comes from.  1 (edge update, mpnn.py:250-262): d pre2 = valid ? dY * gelu'(PRE2) * mask(site2) : 0 with dY = d e_out - the
+// residual backward formed while the tile is staged instead of by a kernel of its own (one read and one write of an [E][128] tensor less).
+// 2 (message mean, mpnn.py:212-219): d pre2 = valid ? dagg[row / k] / cnt[row / k] * gelu'(PRE2) * mask(site2) : 0.
+// The forward tapes (k_emm_fwd2, k_eseg_mean) hold gelu'(PRE2) * mask(site2) in place of PRE2, and PRE with its dropped elements replaced by
+// TE_DROPPED: the staging pass multiplies, and evaluates no dropout hash.
+struct Bwd2Src { const tb16* pre2; const int* nbr; const float* dagg; const float* inv_cnt; int k; };
 template <int MODE>
 __global__ void __launch_bounds__(256, 2) k_emm_bwd2(TRows rows, const tb16* __restrict__ dY, const tb16* __restrict__ PRE, tb16* __restrict__ DX,
         const float* __restrict__ W, int ldw, const unsigned short* __restrict__ wimg, float* __restrict__ part, size_t pstride,
-        int rows_per_split, TDrop dr, unsigned site, float* __restrict__ cs_part, Bwd2Src src) {
+        int rows_per_split, TDrop dr, float* __restrict__ cs_part, Bwd2Src src) {
     __shared__ __attribute__((aligned(16))) unsigned short tA[64 * TN_PITCH], tB[64 * TN_PITCH];
     __shared__ __attribute__((aligned(16))) unsigned short tG[32 * 64 * 8];          // W2 image (32 KiB) first, then the g' tile [64][TN_PITCH]
     float (*cs_red)[128] = reinterpret_cast<float (*)[128]>(tA);
@@ -2219,7 +2194,6 @@ __global__ void __launch_bounds__(256, 2) k_emm_bwd2(TRows rows, const tb16* __r
     const int wr = wave >> 1, wc = wave & 1;
     const int p_begin = blockIdx.z * rows_per_split, p_end = min(R, p_begin + rows_per_split);
     const int ch = tid & 15, rg = tid >> 4;
-    const unsigned key = drop_key(dr, site);
     float csum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const tu32x4 z4 = {0u, 0u, 0u, 0u};
     // this wave's share of d pre1: rows 32 wr .. 32 wr + 31 of the tile, channel blocks 2 wc and 2 wc + 1
@@ -2230,7 +2204,6 @@ __global__ void __launch_bounds__(256, 2) k_emm_bwd2(TRows rows, const tb16* __r
     for (int ks = 0; ks < 8; ++ks)
 #pragma unroll
         for (int u = 0; u < 2; ++u) wf[ks][u] = reinterpret_cast<const tu32x4*>(tG)[(ks * 4 + 2 * wc + u) * 64 + lane];
-    const unsigned key2 = drop_key(dr, src.site2);
     tu32x4 c0[MODE == 1 ? 4 : 1];                             // MODE 1: the taped pre2 chunk (MODE 2 carries it in the dY slot)
     auto load_tile = [&](int m0, tu32x4 (&xa)[4], tu32x4 (&xb)[4]) {
 #pragma unroll
@@ -2255,10 +2228,7 @@ __global__ void __launch_bounds__(256, 2) k_emm_bwd2(TRows rows, const tb16* __r
     while (m0 < p_end) {
         __syncthreads();                                      // the previous tile's fragment reads (and, first time, the image reads) are done
         tu32x4 dy4[4];                                        // d pre2 of this thread's four chunks
-        if constexpr (MODE == 0) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) dy4[i] = a0[i];
-        } else {
+        {
             int jv[4];
             tf32x4 ga[MODE == 2 ? 4 : 1], gb[MODE == 2 ? 4 : 1];
             float ic[MODE == 2 ? 4 : 1];
@@ -2276,22 +2246,15 @@ __global__ void __launch_bounds__(256, 2) k_emm_bwd2(TRows rows, const tb16* __r
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int m = m0 + rg + 16 * i;
-                float up[8], p2[8], dm2[8];
+                float up[8], p2[8];
                 if constexpr (MODE == 1) { unpack8(a0[i], up); unpack8(c0[i], p2); }
                 else {
                     unpack8(a0[i], p2);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) { up[q] = ga[i][q] * ic[i]; up[4 + q] = gb[i][q] * ic[i]; }
                 }
-                if (src.g2tape) {                // (uniform) the tape holds gelu'(pre2) * mask already
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) up[q] *= p2[q];
-                } else {
-                    drop8(dr, key2, (unsigned)m * 16u + ch, dm2);
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) up[q] = MODE == 1 ? up[q] * (gelu_d_fast(p2[q]) * dm2[q]) : up[q] * gelu_d_fast(p2[q]) * dm2[q];   // (the stand-alone kernels' association)
-                }
+                for (int q = 0; q < 8; ++q) up[q] *= p2[q];      // the tape holds gelu'(pre2) * mask already
                 dy4[i] = jv[i] >= 0 ? tpack8(up) : z4;
             }
         }
@@ -2300,15 +2263,13 @@ __global__ void __launch_bounds__(256, 2) k_emm_bwd2(TRows rows, const tb16* __r
             const int m = m0 + rg + 16 * i;
             const bool ok = m < p_end;
             const tu32x4 va = ok ? dy4[i] : z4;
-            float v[8], dm[8], a1[8], gp[8];
+            float v[8], a1[8], gp[8];
             unpack8(b0[i], v);
-            if (MODE != 0 && src.g2tape) {       // (uniform) dropped elements are TE_DROPPED on the tape: both functions vanish there, no hash
 #pragma unroll
-                for (int q = 0; q < 8; ++q) { float g, d; gelu_both_fast(v[q], g, d); a1[q] = g * dr.scale; gp[q] = d * dr.scale; }
-            } else {
-                drop8(dr, key, (unsigned)m * 16u + ch, dm);
-#pragma unroll
-                for (int q = 0; q < 8; ++q) { float g, d; gelu_both_fast(v[q], g, d); a1[q] = g * dm[q]; gp[q] = d * dm[q]; }
+            for (int q = 0; q < 8; ++q) {        // dropped elements are TE_DROPPED on the tape: both functions vanish there, no hash
+                float g, d;
+                gelu_both_fast(v[q], g, d);
+                a1[q] = g * dr.scale; gp[q] = d * dr.scale;
             }
             *reinterpret_cast<tu32x4*>(tA + (rg + 16 * i) * TN_PITCH + 8 * ch) = va;
             *reinterpret_cast<tu32x4*>(tB + (rg + 16 * i) * TN_PITCH + 8 * ch) = ok ? tpack8(a1) : z4;
@@ -2620,19 +2581,17 @@ void te_gemm_bwd1x2(const TRows& rows, const tb16* dY1, const tb16* dY2, const t
 }
 // dW[128][ldw_out] += dY^T drop(gelu(PRE)), dbias += colsum(dY), DX = (dY . W) gelu'(PRE) mask        (W [128 out][ldw] as nn.Linear stores it)
 void te_gemm_bwd2(const TRows& rows, const tb16* dY, const tb16* PRE, tb16* DX, const float* W, int ldw, float* dW, int ldw_out,
-                  const TDrop& dr, unsigned site, float* dbias, hipStream_t s, const EBwd2Src* from) {
+                  const TDrop& dr, float* dbias, hipStream_t s, const EBwd2Src& from) {
     const size_t mk = 128 * 128;
     // >= 8 tiles per workgroup (fills the chip from ~130 K rows on), two resident workgroups per CU (72 KiB of LDS each)
     const RedSplit sp = red_split(rows.maxrows, 512, 64, 2 * rn_num_cus(), LLONG_MAX, red_budget(mk, 800 * 128, 16));
     const size_t pstride = mk + (dbias ? 128 : 0);
     float* part = red_alloc(sp.n * pstride);
     if (!part) return;
-    Bwd2Src src{nullptr, nullptr, nullptr, nullptr, 1, 0u, 0};
-    const int mode = from ? from->mode : 0;
-    if (from) src = Bwd2Src{from->pre2, from->nbr, from->dagg, from->inv_cnt, from->k, from->site2, from->g2tape};
+    const Bwd2Src src{from.pre2, from.nbr, from.dagg, from.inv_cnt, from.k};
 #define BWD2_GO(M) hipLaunchKernelGGL(k_emm_bwd2<M>, dim3(1, 1, sp.n), dim3(256), 0, s, rows, dY, PRE, DX, W, ldw, wimg_lookup(W, ldw, false, 1), \
-                                       part, pstride, sp.rows, dr, site, dbias ? part + mk : (float*)nullptr, src)
-    if (mode == 1) BWD2_GO(1); else if (mode == 2) BWD2_GO(2); else BWD2_GO(0);
+                                       part, pstride, sp.rows, dr, dbias ? part + mk : (float*)nullptr, src)
+    if (from.mode == 1) BWD2_GO(1); else BWD2_GO(2);
 #undef BWD2_GO
     reduce_parts(part, sp.n, pstride, (int)pstride, 128, dW, ldw_out, s, (int)mk, dbias);
 }

@@ -506,8 +506,8 @@ extern "C" int rdesign_forward(rdesign_handle h, const float* X, const float* ma
             tb16* Pt = reinterpret_cast<tb16*>(w.pq);
             tb16* Qt = Pt + (Nmax + 1) * RD_H;
             const float* w0 = rdp(c, L.msg[0].w);                                                            // [128][384] = [W_e | W_centre | W_neighbour]
-            r.bad |= !te_gemm(r.rn(), w.hV, false, RD_H, w0 + RD_H, 3 * RD_H, true, rdp(c, L.msg[0].b), Pt, 0, false, nullptr, nullptr, r.nodrop, 0u, s);
-            r.bad |= !te_gemm(r.rn(), w.hV, false, RD_H, w0 + 2 * RD_H, 3 * RD_H, true, nullptr, Qt, 0, false, nullptr, nullptr, r.nodrop, 0u, s);
+            r.bad |= !te_gemm(r.rn(), w.hV, false, RD_H, w0 + RD_H, 3 * RD_H, true, rdp(c, L.msg[0].b), Pt, false, nullptr, nullptr, r.nodrop, 0u, s);
+            r.bad |= !te_gemm(r.rn(), w.hV, false, RD_H, w0 + 2 * RD_H, 3 * RD_H, true, nullptr, Qt, false, nullptr, nullptr, r.nodrop, 0u, s);
             EFuse f{Pt, Qt, w.nbr, K, (int)Nmax, nullptr, nullptr, 0u};
             tb16* cur = reinterpret_cast<tb16*>(w.E1);
             tb16* nxt = reinterpret_cast<tb16*>(w.E2);
@@ -516,10 +516,10 @@ extern "C" int rdesign_forward(rdesign_handle h, const float* X, const float* ma
                 te_mlp2_fwd(r.re(), reinterpret_cast<const tb16*>(w.hE), w0, 3 * RD_H, rdp(c, L.msg[1].w), RD_H, rdp(c, L.msg[1].b), nullptr, cur, f, r.nodrop, 0u, s);
                 first = 2;
             } else {
-                r.bad |= !te_gemm(r.re(), w.hE, true, RD_H, w0, 3 * RD_H, true, nullptr, cur, 0, false, nullptr, &f, r.nodrop, 0u, s);
+                r.bad |= !te_gemm(r.re(), w.hE, true, RD_H, w0, 3 * RD_H, true, nullptr, cur, false, nullptr, &f, r.nodrop, 0u, s);
             }
             for (size_t i = first; i < L.msg.size(); ++i) {
-                r.bad |= !te_gemm(r.re(), cur, true, RD_H, rdp(c, L.msg[i].w), RD_H, true, rdp(c, L.msg[i].b), nxt, 0, true, nullptr, nullptr, r.nodrop, 0u, s);
+                r.bad |= !te_gemm(r.re(), cur, true, RD_H, rdp(c, L.msg[i].w), RD_H, true, rdp(c, L.msg[i].b), nxt, true, nullptr, nullptr, r.nodrop, 0u, s);
                 tb16* t = cur; cur = nxt; nxt = t;
             }
             hipLaunchKernelGGL(k_rd_segsum_b, dim3((unsigned)((Nmax + 3) / 4)), dim3(256), 0, s, r.pk, K, w.nbr, cur, 1.0f / 30.0f, w.dh);

@@ -244,10 +244,7 @@ void ffn_bwd(Tr& t, const std::vector<Lin>& L, const float* X, int ldx, const st
 // RNAMPNN_F32_ATTN is read when a FORWARD starts (tests flip it inside one process); the backward of that forward takes the value from the tape:
 // with tapes outliving a call (leases, several outstanding forwards) an environment flip in between would otherwise recompute S from other
 // operands than the taped (m, l) statistics belong to
-static inline bool att_mfma_env(bool mixed) {
-    const char* e = getenv("RNAMPNN_F32_ATTN");
-    return mixed && !(e && e[0] == '1');
-}
+static inline bool att_mfma_env(bool mixed) { return mixed && !ab_switch("RNAMPNN_F32_ATTN"); }
 static inline bool att_mfma(const Tr& t) { return t.att_mfma; }
 int bert_fwd(Tr& t, const Bert& b, BertTape& tp, float* x_in, float* out, unsigned site_att0, unsigned site_ffn0) {
     tp.x[0] = x_in;
@@ -339,15 +336,7 @@ void mlp_edge_bwd(Tr& t, const Mlp2& m, const float* h, const float* e, const fl
 inline tb16* eb(float* p) { return reinterpret_cast<tb16*>(p); }
 inline const tb16* eb(const float* p) { return reinterpret_cast<const tb16*>(p); }
 // bf16-mixed, depth-2 per-edge MLPs on the fused kernels: the pre2 tapes (pu2, pm2) hold gelu'(pre2) * mask - all the backward needs of them -
-// written by the forward where it evaluates the activation anyway (k_emm_fwd2's edge update; k_eseg_mean, in place).  The A/B switches that run the
-// stand-alone element-wise kernels (RNAMPNN_SPLIT_FWD, RNAMPNN_NO_BWD_FOLD) and RNAMPNN_PRE2_TAPE=1 keep pre2 itself on the tape.
-static bool tape_g2() {
-    static const bool on = [] {
-        auto set = [](const char* n) { const char* e = getenv(n); return e && atoi(e) != 0; };
-        return !set("RNAMPNN_SPLIT_FWD") && !set("RNAMPNN_NO_BWD_FOLD") && !set("RNAMPNN_PRE2_TAPE");
-    }();
-    return on;
-}
+// written by the forward where it evaluates the activation anyway (k_emm_fwd2's edge update; k_eseg_mean, in place).
 void mlp_edge_fwd_mixed(Tr& t, const Mlp2& m, const float* h, const tb16* e, tb16* pre1, tb16* pre2, unsigned site0,
                         tb16* res_out, unsigned site_res) {
     rnampnn_ctx* c = t.c;
@@ -356,52 +345,27 @@ void mlp_edge_fwd_mixed(Tr& t, const Mlp2& m, const float* h, const tb16* e, tb1
     tb16* Pt = eb(t.w.pq);
     tb16* Qt = Pt + (size_t)(t.pk.Nmax + 1) * RN_D;
     te_gemm_pq(t.rn(), h, w0, rawp(c, m.b[0]), Pt, Qt, t.s);
-    const bool two = m.depth > 1;
-    static const bool split_fwd = getenv("RNAMPNN_SPLIT_FWD") && atoi(getenv("RNAMPNN_SPLIT_FWD")) != 0;      // A/B switch: the two-kernel form
-    if (two && !split_fwd) {
-        EFuse f{Pt, Qt, t.w.nbr, t.k, t.pk.Nmax, e, res_out, site_res};
-        te_mlp2_fwd(t.re(), e, w0 + 2 * RN_D, 3 * RN_D, rawp(c, m.w[1]), RN_D, rawp(c, m.b[1]), pre1, pre2, f, t.dr, site0, t.s, tape_g2());
-        return;
-    }
-    EFuse f1{Pt, Qt, t.w.nbr, t.k, t.pk.Nmax, two ? nullptr : e, two ? nullptr : res_out, site_res};
-    t.bad |= !te_gemm(t.re(), e, true, RN_D, w0 + 2 * RN_D, 3 * RN_D, true, nullptr, pre1, 0, false, nullptr, &f1, t.dr, 0u, t.s);
-    if (two) {
-        EFuse f2{nullptr, nullptr, t.w.nbr, t.k, t.pk.Nmax, e, res_out, site_res};
-        t.bad |= !te_gemm(t.re(), pre1, true, RN_D, rawp(c, m.w[1]), RN_D, true, rawp(c, m.b[1]), pre2, 0, true, nullptr, res_out ? &f2 : nullptr,
-                t.dr, site0, t.s);
-    }
+    EFuse f{Pt, Qt, t.w.nbr, t.k, t.pk.Nmax, e, res_out, site_res};
+    if (m.depth > 1)
+        te_mlp2_fwd(t.re(), e, w0 + 2 * RN_D, 3 * RN_D, rawp(c, m.w[1]), RN_D, rawp(c, m.b[1]), pre1, pre2, f, t.dr, site0, t.s);
+    else
+        t.bad |= !te_gemm(t.re(), e, true, RN_D, w0 + 2 * RN_D, 3 * RN_D, true, nullptr, pre1, false, nullptr, &f, t.dr, 0u, t.s);
 }
-// On entry E2 (bf16) holds d(pre_last).  Accumulates parameter grads, dE (bf16) += d e, dh_acc (f32) += d h.
-// `from` (depth-2 MLPs): d pre2 is formed inside the fused kernel from the upstream gradient (EBwd2Src) instead of being read from E2.
-// `dpre1_keep` (depth-2 MLPs, with `from`): d pre1 is left in that buffer and the e-side pass (dWc, dE) is NOT run - the caller runs it for both
-// MLPs of the layer at once (mlp_edge_bwd1_pair).
-void mlp_edge_bwd_mixed(Tr& t, const Mlp2& m, const float* h, const tb16* e, const tb16* pre1, tb16* dE, float* dh_acc, unsigned site0,
+// Accumulates parameter grads, dE (bf16) += d e, dh_acc (f32) += d h.  Depth 1: on entry E2 (bf16) holds d pre1.  Depth 2: `from` is required;
+// d pre2 is formed inside the fused kernel from the upstream gradient (EBwd2Src).
+// `dpre1_keep` (depth-2 MLPs): d pre1 is left in that buffer and the e-side pass (dWc, dE) is NOT run - the caller runs it for both MLPs of the
+// layer at once (mlp_edge_bwd1_pair).
+void mlp_edge_bwd_mixed(Tr& t, const Mlp2& m, const float* h, const tb16* e, const tb16* pre1, tb16* dE, float* dh_acc,
                         const EBwd2Src* from = nullptr, const tb16* dy_in = nullptr, tb16* dpre1_keep = nullptr) {
     rnampnn_ctx* c = t.c;
     tb16* dpre1 = eb(t.w.E2);
     if (m.depth > 1) {
-        static const bool split = getenv("RNAMPNN_SPLIT_BWD") && atoi(getenv("RNAMPNN_SPLIT_BWD")) != 0;     // A/B switch: the two kernels the fused one replaces
-        if (from) {
-            te_gemm_bwd2(t.re(), dy_in, pre1, dpre1_keep ? dpre1_keep : eb(t.w.E1), rawp(c, m.w[1]), RN_D, t.gw(m.w[1]), RN_D, t.dr, site0, t.gw(m.b[1]), t.s, from);
-        } else if (split) {
-            te_gemm_tn(t.re(), eb(t.w.E2), pre1, t.gw(m.w[1]), RN_D, true, t.dr, site0, t.gw(m.b[1]), t.s);      // dW2, db2
-            t.bad |= !te_gemm(t.re(), t.w.E2, true, RN_D, rawp(c, m.w[1]), RN_D, false, nullptr, eb(t.w.E1), 0, false, pre1, nullptr, t.dr, site0, t.s);   // d pre1
-        } else {
-            te_gemm_bwd2(t.re(), eb(t.w.E2), pre1, eb(t.w.E1), rawp(c, m.w[1]), RN_D, t.gw(m.w[1]), RN_D, t.dr, site0, t.gw(m.b[1]), t.s);
-        }
-        dpre1 = (from && dpre1_keep) ? dpre1_keep : eb(t.w.E1);
+        dpre1 = dpre1_keep ? dpre1_keep : eb(t.w.E1);
+        te_gemm_bwd2(t.re(), dy_in, pre1, dpre1, rawp(c, m.w[1]), RN_D, t.gw(m.w[1]), RN_D, t.dr, t.gw(m.b[1]), t.s, *from);
     }
     float* gw0 = t.gw(m.w[0]);
     const float* w0 = rawp(c, m.w[0]);
-    static const bool split1 = getenv("RNAMPNN_SPLIT_BWD") && atoi(getenv("RNAMPNN_SPLIT_BWD")) != 0;
-    if (from && dpre1_keep && m.depth > 1) {
-        // (deferred to mlp_edge_bwd1_pair)
-    } else if (split1) {
-        te_gemm_tn(t.re(), dpre1, e, gw0 + 2 * RN_D, 3 * RN_D, false, t.dr, 0u, nullptr, t.s);                   // dWc += dpre1^T e
-        t.bad |= !te_gemm(t.re(), dpre1, true, RN_D, w0 + 2 * RN_D, 3 * RN_D, false, nullptr, dE, 1, false, nullptr, nullptr, t.dr, 0u, t.s);   // dE += dpre1 . Wc
-    } else {
-        te_gemm_bwd1(t.re(), dpre1, e, dE, w0 + 2 * RN_D, 3 * RN_D, gw0 + 2 * RN_D, 3 * RN_D, t.s);           // both, one pass over dpre1
-    }
+    if (!dpre1_keep) te_gemm_bwd1(t.re(), dpre1, e, dE, w0 + 2 * RN_D, 3 * RN_D, gw0 + 2 * RN_D, 3 * RN_D, t.s);   // dWc, dE: one pass over dpre1
     te_edge_pq_bwd(t.pk, t.k, dpre1, t.w.rstart, t.w.rlist, t.w.dpq, t.s);
     tm_gemm_tn_pq(t.rn(), t.w.dpq, h, gw0, t.gw(m.b[0]), t.s);                 // [dWa ; dWb] += [dP | dQ]^T h, db1 += colsum(dP)
     if (!tm_gemm_nn_pq(t.rn(), t.w.dpq, w0, dh_acc, t.s)) {                            // dh += dP . Wa + dQ . Wb
@@ -449,9 +413,9 @@ static int train_forward_impl(Tr& t, const float* coords, const float* mask, flo
     hipStream_t s = t.s;
     const int L = g.num_res_mpnn_layers, k = t.k;
     const size_t N = (size_t)t.pk.Nmax;
-    launch_zero_bytes(w.pq + N * 256, 256 * sizeof(float), s, 1);
-    if (t.mixed) launch_zero_bytes(eb(w.pq) + (2 * N + 1) * RN_D, RN_D * sizeof(tb16), s, 1);      // row N of the bf16 Q table
-    for (int l = 0; l <= L; ++l) launch_zero_bytes(w.h[l] + N * RN_D, RN_D * sizeof(float), s, 1);
+    launch_zero_bytes(w.pq + N * 256, 256 * sizeof(float), s);
+    if (t.mixed) launch_zero_bytes(eb(w.pq) + (2 * N + 1) * RN_D, RN_D * sizeof(tb16), s);      // row N of the bf16 Q table
+    for (int l = 0; l <= L; ++l) launch_zero_bytes(w.h[l] + N * RN_D, RN_D * sizeof(float), s);
     if (t.mixed) t_wimg_refresh(c->wimg, s);                    // weight-fragment images of every 128 x 128 block seen so far, from the current weights
     if (t.mixed)       // K-major copies of the two weights whose in-dim (28) the MFMA form does not take
         for (const Lin* l : {&c->raw_project, &c->raw_ffn[0]})
@@ -465,10 +429,10 @@ static int train_forward_impl(Tr& t, const float* coords, const float* mask, flo
     if (t.mixed) {     // bf16 chain: raw features [E][128] (90 live columns) -> pe1 -> pe2 -> e[0], the activations fused into the GEMM operand loads
         const Lin& ee0 = c->edge_embed[0];
         te_edge_features(t.pk, k, w.geom, w.nbr, eb(w.F), s);
-        t.bad |= !te_gemm(t.re(), w.F, true, RN_D, rawp(c, ee0.w), RN_ERAW, true, rawp(c, ee0.b), eb(w.pe1), 0, false, nullptr, nullptr, t.dr, 0u, s, RN_ERAW);
+        t.bad |= !te_gemm(t.re(), w.F, true, RN_D, rawp(c, ee0.w), RN_ERAW, true, rawp(c, ee0.b), eb(w.pe1), false, nullptr, nullptr, t.dr, 0u, s, RN_ERAW);
         if (g.depth_res_edge_feature > 1) {
             const Lin& ee1 = c->edge_embed[1];
-            t.bad |= !te_gemm(t.re(), w.pe1, true, RN_D, rawp(c, ee1.w), RN_D, true, rawp(c, ee1.b), eb(w.pe2), 0, true, nullptr, nullptr, t.dr, site_ee(0), s);
+            t.bad |= !te_gemm(t.re(), w.pe1, true, RN_D, rawp(c, ee1.w), RN_D, true, rawp(c, ee1.b), eb(w.pe2), true, nullptr, nullptr, t.dr, site_ee(0), s);
             te_edge_act(t.pk, k, w.nbr, eb(w.pe2), eb(w.e[0]), t.dr, site_ee(1), s);
         } else {
             te_edge_act(t.pk, k, w.nbr, eb(w.pe1), eb(w.e[0]), t.dr, site_ee(0), s);
@@ -497,7 +461,7 @@ static int train_forward_impl(Tr& t, const float* coords, const float* mask, flo
         if (t.mixed) {      // bf16 tape (the layout of every w.e / w.pm / w.pu tensor in this mode)
             mlp_edge_fwd_mixed(t, m.msg, w.h[l], eb(w.e[l]), eb(w.pm1[l]), eb(w.pm2[l]), site_msg(l, 0), nullptr, 0u);
             te_seg_mean(t.pk, k, w.nbr, eb(m.msg.depth > 1 ? w.pm2[l] : w.pm1[l]), w.h[l], w.hpre[l], t.dr, site_msg(l, m.msg.depth - 1), s,
-                        (m.msg.depth > 1 && tape_g2()) ? eb(w.pm2[l]) : nullptr);
+                        m.msg.depth > 1 ? eb(w.pm2[l]) : nullptr);
             launch_graph_norm_packed(t.pk, w.hpre[l], nullptr, w.h[l + 1], rawp(c, m.gn_scale), rawp(c, m.gn_shift), t.t_norm, s);
             if (l + 1 < L)
                 mlp_edge_fwd_mixed(t, m.edge, w.h[l + 1], eb(w.e[l]), eb(w.pu1[l]), eb(w.pu2[l]), site_edge(l, 0), eb(w.e[l + 1]),
@@ -549,7 +513,7 @@ static int train_backward_impl(Tr& t, int accumulate) {
     hipStream_t s = t.s;
     const int L = g.num_res_mpnn_layers, k = t.k;
     const size_t N = (size_t)t.pk.Nmax;
-    if (!accumulate) launch_zero_bytes(t.g, c->raw_floats * sizeof(float), s, 2);
+    if (!accumulate) launch_zero_bytes(t.g, c->raw_floats * sizeof(float), s);
     // one reduction queue per backward, closed on every return (the normal one reports what it refused: red_end below)
     struct RedScope { RedScope(const TScratch& sc, hipStream_t st) { red_begin(sc, st); } ~RedScope() { red_end(); } } red_scope(w.sc, s);
     {   // readout
@@ -579,38 +543,36 @@ static int train_backward_impl(Tr& t, int accumulate) {
     red_flush();
     if (c->grad_ev[0]) HIP_TRY(hipEventRecord(c->grad_ev[0], s));
     // ResMPNN layers, reverse.  dE = d e[l+1] (zero for the last layer: its edge update is dead)
-    launch_zero_bytes(w.dE, N * k * RN_D * (t.mixed ? sizeof(tb16) : sizeof(float)), s, 4);
+    launch_zero_bytes(w.dE, N * k * RN_D * (t.mixed ? sizeof(tb16) : sizeof(float)), s);
     for (int l = L - 1; l >= 0; --l) {
         const MpnnLayer& m = c->mpnn[l];
         if (l == L / 2 - 1) { red_flush(); if (c->grad_ev[1]) HIP_TRY(hipEventRecord(c->grad_ev[1], s)); }    // chunk 1 (layers L/2 .. L-1) is final
         if (t.mixed) {
-            static const bool nofold = getenv("RNAMPNN_NO_BWD_FOLD") && atoi(getenv("RNAMPNN_NO_BWD_FOLD")) != 0;      // A/B switch
-            const char* nopair_e = getenv("RNAMPNN_NO_BWD1_PAIR");                  // A/B switch, read per call (tests flip it within one process)
-            const bool nopair = nopair_e && atoi(nopair_e) != 0;
+            const bool nopair = ab_switch("RNAMPNN_NO_BWD1_PAIR");
             // both MLPs of the layer read e[l] and add into dE: their e-side passes (dWc, dE) run as ONE kernel after the message MLP's (the two
             // d pre1 tensors live in the two bf16 halves of E1, which is carved for f32)
-            const bool pair = l + 1 < L && m.edge.depth > 1 && m.msg.depth > 1 && !nofold && !nopair;
+            const bool pair = l + 1 < L && m.edge.depth > 1 && m.msg.depth > 1 && !nopair;
             tb16* dp1_e = pair ? eb(w.E1) : nullptr;
             tb16* dp1_m = pair ? eb(w.E1) + N * k * RN_D : nullptr;
             if (l + 1 < L) {
-                if (m.edge.depth > 1 && !nofold) {     // the residual backward rides in the fused kernel's staging pass
-                    EBwd2Src from{1, eb(w.pu2[l]), w.nbr, nullptr, nullptr, k, site_edge(l, 1), tape_g2() ? 1 : 0};
-                    mlp_edge_bwd_mixed(t, m.edge, w.h[l + 1], eb(w.e[l]), eb(w.pu1[l]), eb(w.dE), w.dh, site_edge(l, 0), &from, eb(w.dE), dp1_e);
+                if (m.edge.depth > 1) {     // the residual backward rides in the fused kernel's staging pass
+                    EBwd2Src from{1, eb(w.pu2[l]), w.nbr, nullptr, nullptr, k};
+                    mlp_edge_bwd_mixed(t, m.edge, w.h[l + 1], eb(w.e[l]), eb(w.pu1[l]), eb(w.dE), w.dh, &from, eb(w.dE), dp1_e);
                 } else {
-                    te_edge_res_bwd(t.pk, k, w.nbr, eb(w.dE), eb(m.edge.depth > 1 ? w.pu2[l] : w.pu1[l]), eb(w.E2), t.dr, site_edge(l, m.edge.depth - 1), s);
-                    mlp_edge_bwd_mixed(t, m.edge, w.h[l + 1], eb(w.e[l]), eb(w.pu1[l]), eb(w.dE), w.dh, site_edge(l, 0));
+                    te_edge_res_bwd(t.pk, k, w.nbr, eb(w.dE), eb(w.pu1[l]), eb(w.E2), t.dr, site_edge(l, 0), s);
+                    mlp_edge_bwd_mixed(t, m.edge, w.h[l + 1], eb(w.e[l]), eb(w.pu1[l]), eb(w.dE), w.dh);
                 }
             }
             t_gn_bwd(t.pk, w.hpre[l], w.dh, rawp(c, m.gn_scale), t.t_norm, w.dh2, t.gw(m.gn_scale), t.gw(m.gn_shift), s);
-            if (m.msg.depth > 1 && !nofold) {          // ... and so does the backward of the message mean (dagg = dh2)
+            if (m.msg.depth > 1) {          // ... and so does the backward of the message mean (dagg = dh2)
                 launch_copy_bytes(w.dh, w.dh2, N * RN_D * sizeof(float), s);
-                EBwd2Src from{2, eb(w.pm2[l]), w.nbr, w.dh2, w.invc, k, site_msg(l, 1), tape_g2() ? 1 : 0};
-                mlp_edge_bwd_mixed(t, m.msg, w.h[l], eb(w.e[l]), eb(w.pm1[l]), eb(w.dE), w.dh, site_msg(l, 0), &from, nullptr, dp1_m);
+                EBwd2Src from{2, eb(w.pm2[l]), w.nbr, w.dh2, w.invc, k};
+                mlp_edge_bwd_mixed(t, m.msg, w.h[l], eb(w.e[l]), eb(w.pm1[l]), eb(w.dE), w.dh, &from, nullptr, dp1_m);
                 if (pair) mlp_edge_bwd1_pair(t, m.edge, m.msg, eb(w.e[l]), dp1_e, dp1_m, eb(w.dE));
             } else {
-                te_seg_mean_bwd(t.pk, k, w.nbr, w.dh2, eb(m.msg.depth > 1 ? w.pm2[l] : w.pm1[l]), eb(w.E2), t.dr, site_msg(l, m.msg.depth - 1), s);
+                te_seg_mean_bwd(t.pk, k, w.nbr, w.dh2, eb(w.pm1[l]), eb(w.E2), t.dr, site_msg(l, 0), s);
                 launch_copy_bytes(w.dh, w.dh2, N * RN_D * sizeof(float), s);
-                mlp_edge_bwd_mixed(t, m.msg, w.h[l], eb(w.e[l]), eb(w.pm1[l]), eb(w.dE), w.dh, site_msg(l, 0));
+                mlp_edge_bwd_mixed(t, m.msg, w.h[l], eb(w.e[l]), eb(w.pm1[l]), eb(w.dE), w.dh);
             }
             continue;
         }
@@ -640,7 +602,7 @@ static int train_backward_impl(Tr& t, int accumulate) {
             const Lin& ee1 = c->edge_embed[1];
             te_edge_res_bwd(t.pk, k, w.nbr, eb(w.dE), eb(w.pe2), eb(w.E2), t.dr, site_ee(1), s);                              // d pe2 (absent edges: 0)
             te_gemm_tn(t.re(), eb(w.E2), eb(w.pe1), t.gw(ee1.w), RN_D, true, t.dr, site_ee(0), t.gw(ee1.b), s);
-            t.bad |= !te_gemm(t.re(), w.E2, true, RN_D, rawp(c, ee1.w), RN_D, false, nullptr, dpe1, 0, false, eb(w.pe1), nullptr, t.dr, site_ee(0), s);   // d pe1
+            t.bad |= !te_gemm(t.re(), w.E2, true, RN_D, rawp(c, ee1.w), RN_D, false, nullptr, dpe1, false, eb(w.pe1), nullptr, t.dr, site_ee(0), s);   // d pe1
         } else {
             te_edge_res_bwd(t.pk, k, w.nbr, eb(w.dE), eb(w.pe1), dpe1, t.dr, site_ee(0), s);
         }

@@ -123,3 +123,30 @@ def test_training_path_issues_no_runtime_memset():
     body = inc[:inc.index("rnampnn_edge_raw_features")] if "rnampnn_edge_raw_features" in inc else inc
     assert "hipMemsetAsync" not in body, "train.inc: a runtime memset inside the (capturable) training entry points"
     assert len(re.findall(r"launch_zero_bytes\(", body)) >= 4
+    # ... and the two helpers themselves launch kernels, never the runtime's memset / copy
+    f32 = open(os.path.join(csrc, "kernels_f32.hip")).read()
+    for fn in ("launch_zero_bytes", "launch_copy_bytes"):
+        m = re.search(r"^void " + fn + r"\(.*?^\}", f32, flags=re.S | re.M)
+        assert m, fn
+        assert "hipMemsetAsync" not in m.group(0) and "hipMemcpyAsync" not in m.group(0), fn
+
+
+AB_SWITCHES = {"RNAMPNN_MPNN_V3", "RNAMPNN_NO_BWD1_PAIR", "RNAMPNN_F32_ATTN", "RNAMPNN_NO_RED_BATCH", "RNAMPNN_EMBED_TWO_LAUNCH",
+               "RNAMPNN_NODE_UPDATE_TWO_LAUNCH"}
+
+
+def test_ab_switch_inventory():
+    """The library reads exactly the run-time A/B switches a GPU test uses as its reference form, each through ab_switch (rnampnn_internal.h),
+    and DESIGN.md section 5 lists every one of them."""
+    import glob
+    csrc = os.path.join(REPO, "rna-mpnn_amd", "csrc")
+    srcs = {p: open(p).read() for ext in ("hip", "cpp", "h", "inc") for p in glob.glob(os.path.join(csrc, "*." + ext))}
+    read = set()
+    for text in srcs.values():
+        read |= set(re.findall(r'\b(?:getenv|ab_switch)\("([^"]+)"\)', text))
+    assert read == AB_SWITCHES
+    getenv_calls = [(os.path.basename(p), n) for p, t in srcs.items() for n in re.findall(r"\bgetenv\(([^)]*)\)", t)]
+    assert getenv_calls == [("rnampnn_internal.h", "name")], getenv_calls
+    design = open(os.path.join(REPO, "DESIGN.md")).read()
+    for name in AB_SWITCHES:
+        assert name in design, name

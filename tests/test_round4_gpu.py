@@ -120,9 +120,9 @@ def test_two_ranks_on_one_gpu_overlap_equals_flat_allreduce():
     assert out.returncode == 0 and "DDP_OVERLAP_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
 
 
-def test_embed_fused_first_launch_is_bit_identical_to_the_two_launch_form(monkeypatch):
+def test_embed_fused_first_launch_is_bit_identical_to_the_two_launch_reference(monkeypatch):
     """at k > 16 the edge embedding (feature.py:386-571) runs inside layer 1's message launch (k_resmpnn<false, true, true>:
-    e0 goes from the embedding's accumulators to the message MLP's operand registers and is stored once); RNAMPNN_EMBED_FUSED=0 runs
+    e0 goes from the embedding's accumulators to the message MLP's operand registers and is stored once); RNAMPNN_EMBED_TWO_LAUNCH=1 runs
     k_edge_embed_bf16 + the plain message launch.  Same arithmetic in the same order: logits, the layer-1 node tap and the layer-1 edge tap
     (which re-reads the stored e0) are equal bit for bit on a ragged batch with a 1-residue and a 64-residue (= padding_len) RNA."""
     from rnampnn.utils import synth
@@ -133,10 +133,10 @@ def test_embed_fused_first_launch_is_bit_identical_to_the_two_launch_form(monkey
     fused = model(c, m).clone()
     n_fused = model.profile_read()[1]
     taps_f = {k: v.clone() for k, v in model.forward_taps(c, m, ["h_layer", "e_layer"], tap_layer=1).items() if torch.is_tensor(v)}
-    monkeypatch.setenv("RNAMPNN_EMBED_FUSED", "0")
+    monkeypatch.setenv("RNAMPNN_EMBED_TWO_LAUNCH", "1")
     two = model(c, m).clone()
     taps_t = {k: v.clone() for k, v in model.forward_taps(c, m, ["h_layer", "e_layer"], tap_layer=1).items() if torch.is_tensor(v)}
-    monkeypatch.delenv("RNAMPNN_EMBED_FUSED")
+    monkeypatch.delenv("RNAMPNN_EMBED_TWO_LAUNCH")
     model.profile_enable(False)
     assert n_fused == 4                                     # (one timed fused-step launch per layer either way)
     assert torch.isfinite(fused).all() and torch.equal(fused, two)
@@ -145,10 +145,10 @@ def test_embed_fused_first_launch_is_bit_identical_to_the_two_launch_form(monkey
         assert torch.equal(taps_f[name], taps_t[name]), name
 
 
-def test_node_update_with_in_kernel_graphnorm_statistics_matches_the_two_launch_form(monkeypatch):
+def test_node_update_with_in_kernel_graphnorm_statistics_matches_the_two_launch_reference(monkeypatch):
     """Between two ResMPNN steps the residual + GraphNormalization (functional.py:33-46) + [P | Q] projections run as ONE kernel per RNA
     when the padded length is 48..256 (k_node_update_rna: the per-RNA statistics from a fixed-order lane tree, two passes);
-    RNAMPNN_NODE_UPDATE_RNA=0 runs k_gn_coef + k_node_update.  Same arithmetic up to the f32 summation order of the statistics:
+    RNAMPNN_NODE_UPDATE_TWO_LAUNCH=1 runs k_gn_coef + k_node_update.  Same arithmetic up to the f32 summation order of the statistics:
     layer taps and logits agree to 2e-3 of their scale; padded lengths 64 (4 row blocks, two waves each), 150 (5 row blocks, two waves each:
     the C2 shape) and 200 (8 row blocks, one wave each), RNAs of 1 and T residues."""
     from rnampnn.utils import synth
@@ -158,10 +158,10 @@ def test_node_update_with_in_kernel_graphnorm_statistics_matches_the_two_launch_
         c, m = torch.from_numpy(coords), torch.from_numpy(mask)
         new = model(c, m).clone()
         taps_n = {k: v.clone() for k, v in model.forward_taps(c, m, ["h_layer", "e_layer"], tap_layer=2).items() if torch.is_tensor(v)}
-        monkeypatch.setenv("RNAMPNN_NODE_UPDATE_RNA", "0")
+        monkeypatch.setenv("RNAMPNN_NODE_UPDATE_TWO_LAUNCH", "1")
         old = model(c, m).clone()
         taps_o = {k: v.clone() for k, v in model.forward_taps(c, m, ["h_layer", "e_layer"], tap_layer=2).items() if torch.is_tensor(v)}
-        monkeypatch.delenv("RNAMPNN_NODE_UPDATE_RNA")
+        monkeypatch.delenv("RNAMPNN_NODE_UPDATE_TWO_LAUNCH")
         assert torch.isfinite(new).all() and (new[mask == 0] == 0).all()
         assert not torch.equal(new, old)                          # (a different kernel really ran)
         for a, b in [(new, old)] + [(taps_n[k], taps_o[k]) for k in ("h_layer", "e_layer")]:

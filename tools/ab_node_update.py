@@ -1,4 +1,4 @@
-"""Per-layer differences between the per-RNA node update (in-kernel GraphNorm statistics) and the two-launch form (RNAMPNN_NODE_UPDATE_RNA=0)."""
+"""Per-layer differences between the per-RNA node update (in-kernel GraphNorm statistics) and the two-launch form (RNAMPNN_NODE_UPDATE_TWO_LAUNCH=1)."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "rna-mpnn_amd"))
@@ -14,9 +14,9 @@ for T, lens in ((64, [64, 20, 47, 33, 5, 58, 31, 1]), (150, [150, 97, 1, 129, 33
     c, m = torch.from_numpy(coords), torch.from_numpy(mask)
     for layer in (0, 1, 2, 3):
         names = ["h0"] if layer == 0 else ["h_layer", "e_layer"]
-        os.environ.pop("RNAMPNN_NODE_UPDATE_RNA", None)
+        os.environ.pop("RNAMPNN_NODE_UPDATE_TWO_LAUNCH", None)
         a = {k: v.clone() for k, v in model.forward_taps(c, m, names, tap_layer=layer).items() if torch.is_tensor(v)}
-        os.environ["RNAMPNN_NODE_UPDATE_RNA"] = "0"
+        os.environ["RNAMPNN_NODE_UPDATE_TWO_LAUNCH"] = "1"
         b = {k: v.clone() for k, v in model.forward_taps(c, m, names, tap_layer=layer).items() if torch.is_tensor(v)}
         for k in a:
             d = (a[k] - b[k]).abs()
