@@ -80,8 +80,11 @@ typedef struct RnaMpnnForwardIO {
     const float* coords;      /* (B,T,7,3) */
     const float* mask;        /* (B,T)     */
     int32_t B, T;
-    int32_t T_norm;           /* node-axis length seen by GraphNormalization (functional.py:33-38);
-                                 0 = T.  A data-parallel shard passes the GLOBAL batch max_len here. */
+    int32_t T_norm;           /* the padded length this call stands for; 0 = T.  A data-parallel shard passes the
+                                 GLOBAL batch max_len here.  It is the node-axis length GraphNormalization sees
+                                 (functional.py:33-38) AND the padded length of the phantom-edge rule (an RNA with
+                                 n - 1 < k keeps an edge to a padded residue iff n < max(T, T_norm)), so an
+                                 edge_index tap may name index T: a padded residue that exists only in the global batch. */
     int32_t stop_after;       /* 0 = whole forward; 1 = stop after ResFeature.forward (feature.py:573-592) */
     float*   logits;          /* (B,T,4)    RNAMPNN.forward          rnampnn.py:161-185 (required if stop_after==0) */
     float*   embedding;       /* (B,T,256)  RNAMPNN.embedding        rnampnn.py:269-278 */
@@ -119,8 +122,9 @@ int rnampnn_forward(rnampnn_handle h, const RnaMpnnForwardIO* io, void* workspac
 /* Packed (var-len) form of the same forward - SURVEY.md section 8 row F1: the reference's collate pads every
  * RNA to the batch max_len (rnampnn/utils/data.py:110-142); here the caller hands over the valid residues
  * only, back to back: coords_packed (N_total,7,3) f32, cu_seqlens (B+1) i32 on the device (exclusive prefix
- * sum of the lengths), T_max = longest RNA (host value; decides the phantom-edge rule exactly as a batch
- * padded to T_max would), T_norm as above (0 = T_max).  Outputs are packed rows as well:
+ * sum of the lengths), T_max = longest RNA (host value; when T_norm is 0 it decides the phantom-edge rule exactly
+ * as a batch padded to T_max would), T_norm as above (0 = T_max; otherwise it decides the phantom edge, like a batch
+ * padded to T_norm).  Outputs are packed rows as well:
  * logits_packed (N_total,4), embedding_packed (N_total,256); either may be null. */
 size_t rnampnn_workspace_bytes_packed(rnampnn_handle h, int32_t B, int32_t N_total);
 int rnampnn_forward_packed(rnampnn_handle h, const float* coords_packed, const int32_t* cu_seqlens, int32_t B,

@@ -746,7 +746,7 @@ static int forward_core(Run& r, rnampnn_handle h, const RnaMpnnForwardIO* io, co
     hipStream_t s = r.s;
 
     // ---- ResFeature.forward (feature.py:588-592)
-    launch_geom(io->coords, r.pk, io->raw, w.raw_p, w.geom, r.fast ? w.geomh : nullptr, s);
+    launch_geom(io->coords, r.pk, t_norm, io->raw, w.raw_p, w.geom, r.fast ? w.geomh : nullptr, s);
     const bool fused_first = r.fast && io->stop_after != 1;
     {   // raw_project (feature.py:183, 28 -> 128) in exact f32 on both paths: the GraphNorm behind the embedding stack removes the common part of
         // its output and amplifies the rounding of the inputs (bf16 operands here cost 4 % of h0: tools/tap_errors.py); 0.1 GFLOP at the C2 batch
@@ -763,7 +763,7 @@ static int forward_core(Run& r, rnampnn_handle h, const RnaMpnnForwardIO* io, co
             launch_graph_norm_packed(r.pk, w.n1, nullptr, w.hA, rawp(c, c->feat_gn_scale), rawp(c, c->feat_gn_shift), t_norm, r.s);
     }
     if (rc) return rc;
-    if (launch_knn(io->coords, r.pk, k, w.nbr, io->edge_index, s))
+    if (launch_knn(io->coords, r.pk, t_norm, k, w.nbr, io->edge_index, s))
         return fail(RNAMPNN_ERR_UNSUPPORTED, "max_len %d too long for the LDS-resident k-NN row", io->T);
     const bool embed_first = fused_first && L >= 1 && !io->e0 && resmpnn_covers(k, false, false) && !ab_switch("RNAMPNN_EMBED_TWO_LAUNCH");
     if (embed_first) { }

@@ -134,7 +134,10 @@ void launch_lengths(const float* mask, const PackInfo& pk, hipStream_t s) {
 // record the edge kernels gather per neighbour: 21 coordinates, 5 unit bond vectors
 // (F.normalize eps 1e-12, feature.py:455-456), 4 unit plane normals (cross of consecutive
 // raw bond vectors, eps 1e-6, feature.py:496-505).  One thread per (b, t); t == n_b also
-// fills the record of the RNA's phantom neighbour (row Nmax + b), see k_knn.
+// fills the record of the RNA's phantom neighbour (row Nmax + b), see k_knn.  An RNA with
+// n_b == T has no padded residue in the tensor: when the call stands for a longer batch
+// (Tp > T), one extra thread per RNA builds its phantom record from the zero coordinates
+// every padded residue of that batch has.
 __device__ __forceinline__ void geom_record(const float* c, float* g) {
 #pragma unroll
     for (int i = 0; i < 21; ++i) g[i] = c[i];
@@ -226,10 +229,28 @@ __device__ __forceinline__ void store_geomh(const float* g, float* __restrict__ 
     for (int i = 0; i < RN_GEOMH; i += 4) *reinterpret_cast<float4*>(dst + i) = make_float4(gh[i], gh[i + 1], gh[i + 2], gh[i + 3]);
 }
 
-__global__ void k_geom(const float* __restrict__ coords, PackInfo pk, float* __restrict__ raw_out,
+__device__ __forceinline__ void store_geom(const float* c, float* __restrict__ geom, float* __restrict__ geomh, size_t row) {
+    float g[RN_GEOM];
+    geom_record(c, g);
+    float* gp = geom + row * RN_GEOM;
+#pragma unroll
+    for (int i = 0; i < RN_GEOM; ++i) gp[i] = g[i];
+    if (geomh) store_geomh(g, geomh + row * RN_GEOMH);
+}
+
+__global__ void k_geom(const float* __restrict__ coords, PackInfo pk, int Tp, float* __restrict__ raw_out,
                        float* __restrict__ raw_p, float* __restrict__ geom, float* __restrict__ geomh) {
     int id = blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= pk.B * pk.T) return;
+    if (id >= pk.B * pk.T) {                                    // threads B*T + b: phantom record of an RNA with n == T < Tp
+        const int b = id - pk.B * pk.T;
+        if (b < pk.B && pk.len[b] == pk.T && pk.T < Tp) {
+            float c[21];
+#pragma unroll
+            for (int i = 0; i < 21; ++i) c[i] = 0.f;
+            store_geom(c, geom, geomh, (size_t)(pk.Nmax + b));
+        }
+        return;
+    }
     int b = id / pk.T, t = id - b * pk.T;
     int n = pk.len[b];
     float c[21];
@@ -253,12 +274,7 @@ __global__ void k_geom(const float* __restrict__ coords, PackInfo pk, float* __r
 #pragma unroll
             for (int i = 0; i < 28; ++i) ro[i] = f[i];
         }
-        float g[RN_GEOM];
-        geom_record(c, g);
-        float* gp = geom + (size_t)p * RN_GEOM;
-#pragma unroll
-        for (int i = 0; i < RN_GEOM; ++i) gp[i] = g[i];
-        if (geomh) store_geomh(g, geomh + (size_t)p * RN_GEOMH);
+        store_geom(c, geom, geomh, (size_t)p);
     } else {
         if (raw_out) {                                          // padded rows: 1e6 distances, 0 cosines
             float* ro = raw_out + (size_t)id * RN_RAW;
@@ -267,20 +283,13 @@ __global__ void k_geom(const float* __restrict__ coords, PackInfo pk, float* __r
 #pragma unroll
             for (int i = 21; i < 28; ++i) ro[i] = 0.f;
         }
-        if (t == n) {                                           // phantom neighbour of RNA b
-            float g[RN_GEOM];
-            geom_record(c, g);
-            float* gp = geom + (size_t)(pk.Nmax + b) * RN_GEOM;
-#pragma unroll
-            for (int i = 0; i < RN_GEOM; ++i) gp[i] = g[i];
-            if (geomh) store_geomh(g, geomh + (size_t)(pk.Nmax + b) * RN_GEOMH);
-        }
+        if (t == n) store_geom(c, geom, geomh, (size_t)(pk.Nmax + b));      // phantom neighbour of RNA b
     }
 }
 
-void launch_geom(const float* coords, const PackInfo& pk, float* raw_out, float* raw_p, float* geom, float* geomh, hipStream_t s) {
-    int total = pk.B * pk.T;
-    hipLaunchKernelGGL(k_geom, dim3((total + 63) / 64), dim3(64), 0, s, coords, pk, raw_out, raw_p, geom, geomh);
+void launch_geom(const float* coords, const PackInfo& pk, int Tp, float* raw_out, float* raw_p, float* geom, float* geomh, hipStream_t s) {
+    int total = pk.B * (pk.T + 1);
+    hipLaunchKernelGGL(k_geom, dim3((total + 63) / 64), dim3(64), 0, s, coords, pk, Tp, raw_out, raw_p, geom, geomh);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -290,12 +299,14 @@ void launch_geom(const float* coords, const PackInfo& pk, float* raw_out, float*
 // of a packed 64-bit key.  Self and padded residues all sit at exactly 1e6 in the reference
 // and are never real neighbours.  Slot n-1 (when n-1 < k): the reference keeps one extra edge
 // to a PADDED residue iff T > n -> the phantom neighbour (index n in the
-// API tensor, row Nmax + b in the packed index); all later slots are -1.
+// API tensor, row Nmax + b in the packed index); all later slots are -1.  T here is Tp, the
+// padded length the call stands for (max(T, T_norm)): with n == T < Tp the phantom is index T,
+// a padded residue that exists only in the global batch.
 // G = lanes cooperating on one row (64: one wave per row, any T that fits LDS; 16: four rows per
 // wave, 4x the rows in flight - the extraction loop is a chain of dependent cross-lane reductions,
 // so throughput comes from rows in flight, not from lanes per row).
 template <int G>
-__global__ void __launch_bounds__(256) k_knn(const float* __restrict__ coords, PackInfo pk, int k, int rows_per_block,
+__global__ void __launch_bounds__(256) k_knn(const float* __restrict__ coords, PackInfo pk, int Tp, int k, int rows_per_block,
                                               int* __restrict__ nbr, int64_t* __restrict__ eidx) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     constexpr int GROUPS = 256 / G;
@@ -398,7 +409,7 @@ __global__ void __launch_bounds__(256) k_knn(const float* __restrict__ coords, P
         }
         if (real) {
             for (int s = nreal + gl; s < k; s += G) {
-                bool phantom = (s == n - 1) && (n < T);
+                bool phantom = (s == n - 1) && (n < Tp);
                 nbr[pbase + s] = phantom ? pk.Nmax + b : -1;
                 if (eidx) eidx[obase + s] = phantom ? n : -1;
             }
@@ -411,7 +422,7 @@ __global__ void __launch_bounds__(256) k_knn(const float* __restrict__ coords, P
 // conditional shift of the winner's queue - no re-scan of the row per round (the re-scan was 3/4 of the instructions of k_knn<16>).
 // Identical output: ascending (distance, index) order, same phantom / -1 rule.
 template <int NK>
-__global__ void __launch_bounds__(256) k_knn_queue(const float* __restrict__ coords, PackInfo pk, int k, int rows_per_block,
+__global__ void __launch_bounds__(256) k_knn_queue(const float* __restrict__ coords, PackInfo pk, int Tp, int k, int rows_per_block,
                                                     int* __restrict__ nbr, int64_t* __restrict__ eidx) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     constexpr int G = 16, GROUPS = 256 / G;
@@ -493,7 +504,7 @@ __global__ void __launch_bounds__(256) k_knn_queue(const float* __restrict__ coo
         }
         if (real) {
             for (int s = nreal + gl; s < k; s += G) {
-                const bool phantom = (s == n - 1) && (n < T);
+                const bool phantom = (s == n - 1) && (n < Tp);
                 nbr[pbase + s] = phantom ? pk.Nmax + b : -1;
                 if (eidx) eidx[obase + s] = phantom ? n : -1;
             }
@@ -501,21 +512,21 @@ __global__ void __launch_bounds__(256) k_knn_queue(const float* __restrict__ coo
     }
 }
 
-int launch_knn(const float* coords, const PackInfo& pk, int k, int* nbr, int64_t* eidx, hipStream_t s) {
+int launch_knn(const float* coords, const PackInfo& pk, int Tp, int k, int* nbr, int64_t* eidx, hipStream_t s) {
     if (pk.T <= 256) {                  // register-resident sorted queues
         const int rpb = 32;
         dim3 grid(pk.B, (pk.T + rpb - 1) / rpb);
         const size_t lds = (size_t)3 * pk.T * sizeof(float);
-        if (pk.T <= 64) hipLaunchKernelGGL(k_knn_queue<4>, grid, dim3(256), lds, s, coords, pk, k, rpb, nbr, eidx);
-        else if (pk.T <= 144) hipLaunchKernelGGL(k_knn_queue<9>, grid, dim3(256), lds, s, coords, pk, k, rpb, nbr, eidx);
-        else hipLaunchKernelGGL(k_knn_queue<16>, grid, dim3(256), lds, s, coords, pk, k, rpb, nbr, eidx);
+        if (pk.T <= 64) hipLaunchKernelGGL(k_knn_queue<4>, grid, dim3(256), lds, s, coords, pk, Tp, k, rpb, nbr, eidx);
+        else if (pk.T <= 144) hipLaunchKernelGGL(k_knn_queue<9>, grid, dim3(256), lds, s, coords, pk, Tp, k, rpb, nbr, eidx);
+        else hipLaunchKernelGGL(k_knn_queue<16>, grid, dim3(256), lds, s, coords, pk, Tp, k, rpb, nbr, eidx);
         return 0;
     }
     const size_t lds16 = (size_t)(3 + 16) * pk.T * sizeof(float);
     if (lds16 <= 48 * 1024) {                        // four rows per wave
         int rpb = 32;
         dim3 grid(pk.B, (pk.T + rpb - 1) / rpb);
-        hipLaunchKernelGGL(k_knn<16>, grid, dim3(256), lds16, s, coords, pk, k, rpb, nbr, eidx);
+        hipLaunchKernelGGL(k_knn<16>, grid, dim3(256), lds16, s, coords, pk, Tp, k, rpb, nbr, eidx);
         return 0;
     }
     size_t lds = (size_t)(3 + 4) * pk.T * sizeof(float);
@@ -524,7 +535,7 @@ int launch_knn(const float* coords, const PackInfo& pk, int k, int* nbr, int64_t
     ensure_dyn_lds((const void*)k_knn<64>, lds, attr);
     int rpb = pk.T <= 512 ? 16 : 64;
     dim3 grid(pk.B, (pk.T + rpb - 1) / rpb);
-    hipLaunchKernelGGL(k_knn<64>, grid, dim3(256), lds, s, coords, pk, k, rpb, nbr, eidx);
+    hipLaunchKernelGGL(k_knn<64>, grid, dim3(256), lds, s, coords, pk, Tp, k, rpb, nbr, eidx);
     return 0;
 }
 

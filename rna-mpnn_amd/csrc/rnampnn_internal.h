@@ -67,8 +67,10 @@ void launch_zero_bytes(void* ptr, size_t bytes, hipStream_t s);                 
 void launch_copy_bytes(void* dst, const void* src, size_t bytes, hipStream_t s);   // kernel copy, 16-byte aligned, bytes % 16 == 0
 void launch_lengths(const float* mask, const PackInfo& pk, hipStream_t s);
 void launch_lengths_from_cu(const int32_t* cu_seqlens, const PackInfo& pk, hipStream_t s);
-void launch_geom(const float* coords, const PackInfo& pk, float* raw_out, float* raw_p, float* geom, float* geomh, hipStream_t s);
-int  launch_knn(const float* coords, const PackInfo& pk, int k, int* nbr, int64_t* edge_index_out, hipStream_t s);
+// Tp = the padded length the call stands for, max(T, T_norm): it decides the phantom neighbour of an RNA with n - 1 < k
+// (pk.T still sizes the tensors and selects the kernel variant)
+void launch_geom(const float* coords, const PackInfo& pk, int Tp, float* raw_out, float* raw_p, float* geom, float* geomh, hipStream_t s);
+int  launch_knn(const float* coords, const PackInfo& pk, int Tp, int k, int* nbr, int64_t* edge_index_out, hipStream_t s);
 void launch_edge_embed_f32(const PackInfo& pk, int k, const float* geom, const int* nbr,
                            const float* w0t, const float* b0, const float* w1t, const float* b1, int depth,
                            float* e, hipStream_t s);

@@ -421,8 +421,8 @@ static int train_forward_impl(Tr& t, const float* coords, const float* mask, flo
         for (const Lin* l : {&c->raw_project, &c->raw_ffn[0]})
             launch_transpose(rawp(c, l->w), l->in, l->out, l->in, derp<float>(c, l->wt), l->out, s);
     launch_lengths(mask, t.pk, s);
-    launch_geom(coords, t.pk, nullptr, w.raw_p, w.geom, nullptr, s);
-    if (launch_knn(coords, t.pk, k, w.nbr, nullptr, s)) return fail(RNAMPNN_ERR_UNSUPPORTED, "max_len too long for k-NN");
+    launch_geom(coords, t.pk, t.t_norm, nullptr, w.raw_p, w.geom, nullptr, s);
+    if (launch_knn(coords, t.pk, t.t_norm, k, w.nbr, nullptr, s)) return fail(RNAMPNN_ERR_UNSUPPORTED, "max_len too long for k-NN");
     t_build_reverse(t.pk, k, w.nbr, w.rdeg, w.rstart, w.rfill, w.rlist, reinterpret_cast<int*>(w.E1), s);
     if (t.mixed) te_inv_count(t.pk, k, w.nbr, w.invc, s);
     // edge embedding (feature.py:540-571)
@@ -761,8 +761,8 @@ extern "C" int rnampnn_edge_raw_features(rnampnn_handle h, const float* coords, 
     PackInfo pk;
     pk.len = w.len; pk.cu = w.cu; pk.node_b = w.node_b; pk.B = B; pk.T = T; pk.Nmax = B * T; pk.packed_in = 0;
     launch_lengths(mask, pk, s);
-    launch_geom(coords, pk, nullptr, w.raw_p, w.geom, nullptr, s);
-    if (launch_knn(coords, pk, k, w.nbr, edge_index, s)) return fail(RNAMPNN_ERR_UNSUPPORTED, "max_len too long for k-NN");
+    launch_geom(coords, pk, pk.T, nullptr, w.raw_p, w.geom, nullptr, s);
+    if (launch_knn(coords, pk, pk.T, k, w.nbr, edge_index, s)) return fail(RNAMPNN_ERR_UNSUPPORTED, "max_len too long for k-NN");
     t_edge_features(pk, k, w.geom, w.nbr, w.F, s);
     HIP_TRY(hipMemsetAsync(feats, 0, (size_t)B * T * k * RN_ERAWP * sizeof(float), s));
     launch_unpack_nodes(pk, w.F, k * RN_ERAWP, k * RN_ERAWP, feats, s);

@@ -119,9 +119,15 @@ def test_f32_matches_oracle_on_synthetic_batch():
     assert abs(float(loss) - float(ref_loss)) < 1e-5
 
 
-def test_T_norm_reproduces_global_batch_padding():
+@pytest.mark.parametrize("case", ["cut_past_longest", "short_k30", "short_k16"])
+def test_T_norm_reproduces_global_batch_padding(case):
     """A shard that passes the global max_len as T_norm reproduces the padded-batch result
-    (padding-dependent GraphNorm)."""
+    (padding-dependent GraphNorm).  short_k30 / short_k16: the shard's longest RNA has n <= k
+    and the shard is cut to T = n, so no padded residue of the shard tensor exists; the global batch gives that RNA the
+    phantom neighbour (index n, a padded residue), and T_norm must too (_short_rna_shard)."""
+    if case != "cut_past_longest":
+        _short_rna_shard(case)
+        return
     from rnampnn.utils import synth
     from rnampnn.model._schema import DEFAULT_HPARAMS, state_dict_shapes
     lens = [50, 20, 35, 41]
@@ -135,6 +141,38 @@ def test_T_norm_reproduces_global_batch_padding():
     assert (part[:, :35] - full[1:3, :35]).abs().max() < 2e-5
     own = model(torch.from_numpy(c3), torch.from_numpy(m3)).cpu()
     assert (own[:, :35] - full[1:3, :35]).abs().max() > 1e-4       # without T_norm the result differs
+
+
+def _short_rna_shard(case):
+    """short_k30: global lens [40, 12, 20, 27] at k = 30, shard [12, 27] cut to T = 27, T_norm = 40.  short_k16: global lens
+    [140, 5, 9, 16] at k = 16, shard [5, 9, 16] cut to T = 16, T_norm = 140.  In bf16 and f32 the shard's logits equal the
+    full batch's rows bit for bit, through the padded and the packed (forward_packed, max_len = T) form; the shard's
+    edge_index tap equals the full batch's (slot n - 1 of the longest RNA names index n = T)."""
+    from rnampnn.utils import synth
+    from rnampnn.utils.data import pack_batch
+    from rnampnn.model._schema import DEFAULT_HPARAMS, state_dict_shapes
+    lens, k, sel = ([40, 12, 20, 27], 30, [1, 3]) if case == "short_k30" else ([140, 5, 9, 16], 16, [1, 2, 3])
+    coords, mask, _ = synth.synth_batch(lens, first_index=3100 if case == "short_k30" else 3200)
+    Tg, ts = max(lens), max(lens[i] for i in sel)
+    assert ts <= k
+    hp = dict(DEFAULT_HPARAMS, num_res_neighbours=k, padding_len=Tg)
+    cs, ms = torch.from_numpy(coords[sel][:, :ts].copy()), torch.from_numpy(mask[sel][:, :ts].copy())
+    valid = ms.bool()
+    for precision in ("f32", "bf16"):
+        model, _ = _model(hp, state_dict_shapes(hp), precision)
+        want = model(torch.from_numpy(coords), torch.from_numpy(mask)).cpu()[sel][:, :ts]
+        got = model(cs, ms, T_norm=Tg).cpu()
+        print(f"{case} {precision}: shard vs full max |dlogit| {float((got - want).abs().max()):.2e}")
+        assert torch.equal(got, want), precision
+        full = model.forward_taps(torch.from_numpy(coords), torch.from_numpy(mask), ["edge_index"])
+        part = model.forward_taps(cs, ms, ["edge_index"], T_norm=Tg)
+        assert torch.equal(part["edge_index"].cpu(), full["edge_index"].cpu()[sel][:, :ts]), precision
+        assert int(part["edge_index"][-1, 0, ts - 1]) == ts                      # the phantom of the longest RNA: index T
+        assert torch.equal(part["logits"].cpu(), full["logits"].cpu()[sel][:, :ts]), precision
+        packed, cu, max_len = pack_batch([cs[b, :lens[i]] for b, i in enumerate(sel)])
+        assert max_len == ts
+        lp = model.forward_packed(packed.cuda(), cu.cuda(), max_len, T_norm=Tg).cpu()
+        assert torch.equal(lp, want[valid]), precision
 
 
 def test_standalone_stage_modules_match_oracle():

@@ -1,0 +1,314 @@
+"""The trainers at production shapes against fp64 oracle autograd, and ``T_norm`` in training.
+
+Reference: ``oracle.rnampnn_oracle`` in float64 (state dict, coordinates and arithmetic) with the HIP dropout masks (``Drop``
+indexes them by packed row, as the kernels do).  The k-NN graph is the oracle's fp32 one: the neighbour set and the slot order
+are a discrete function of the fp32 coordinates in the reference model, and fp64 distances could reorder a near-tie, which
+moves the per-slot dropout masks of that row.  One fp64 forward + backward per case, shared by the f32 and the bf16-mixed
+trainer (module-scoped cache).
+
+Per-tensor error = max|g - r| / max|r| over one parameter's gradient; tensors whose reference gradient is exactly zero (the
+dead edge update of the last MPNN layer) must stay below an absolute 1e-6 instead.
+"""
+import numpy as np
+import pytest
+import torch
+
+from test_hip_parity import BF16_GRAD_REL, F32_LOGIT_TOL, _model, bf16_tol
+
+pytestmark = pytest.mark.gpu
+
+F32_LOSS_TOL = 1e-5
+BF16_LOSS_TOL = 2e-3
+BF16_COS = 0.9995
+F32_COS = 0.999999
+DEAD_ABS = 1e-6              # |gradient| of a tensor the fp64 reference leaves exactly zero
+# f32 trainer, per-tensor error vs fp64 autograd: ~4x the worst of the case measured on an MI355X (printed by the test):
+# 4.8e-5, 6.6e-6, 4.8e-6 and 9.2e-5.  The fp32 oracle itself is off by 6.7e-5 on default_k30 (worst: the GraphNorm shift
+# of MPNN layer 0, whose gradient is a near-cancelling sum), so these are at the f32 noise floor of each shape.
+F32_GRAD_REL = {"default_k30": 2e-4, "default_k30_dropout": 3e-5, "large_edges": 2e-5, "large_nodes": 4e-4}
+CASES = list(F32_GRAD_REL)
+# Open finding: at the 10-layer production shape the bf16-mixed gradient misses BF16_GRAD_REL per tensor (measured on an
+# MI355X: 50 tensors without dropout, worst res_mpnn_layers.0.graph_norm.shift at 37x its largest entry; 2 tensors with
+# dropout 0.4, worst res_mpnn_layers.1.graph_norm.shift at 0.15); loss, logits and flat cosine stay within their bounds.
+# These gradients are tiny (~1e-6) near-cancelling sums: rounding only the WEIGHTS to bf16 already moves the fp64 gradients
+# of several tensors by 0.2-0.33 of their largest entry without dropout.  The cause of the remaining gap is not found
+# yet, so the bound is not moved: these cases xfail on the per-tensor bound only, after every other assertion, and fail
+# once it holds (then drop them from this set).
+BF16_PER_TENSOR_OPEN = {"default_k30", "default_k30_dropout"}
+
+
+def _longest_last(lens):
+    """The longest RNA moved to the end of the batch: masking its last residue (the negative control) then moves no packed
+    row of another RNA, so every dropout mask stays where it was."""
+    lens = [int(x) for x in lens]
+    lens.append(lens.pop(int(np.argmax(lens))))
+    return lens
+
+
+def _case(name):
+    """-> (hp, lens, first_index, dropout, seed).  Kernel forms from one kernel trace of one step per trainer (MI355X).
+
+    default_k30 / default_k30_dropout: DEFAULT_HPARAMS with k = 30 and the full 10-layer stack, 472 nt; dropout 0 and 0.4.
+      n = 1 (no edge at all), n <= k (the phantom neighbour), n = k and k + 1, both post-fusion attention layers, the
+      512-wide FFN backward; k_knn_queue<9>, the bf16 per-edge kernels (k_emm128, k_emm_fwd2, k_emm_bwd1/2) at one tile
+      per workgroup (361 workgroups), k_tmm<., 1>.  fp64 oracle forward + backward: ~8.5 s on 8 CPUs.
+    large_edges: k = 30, 2 MPNN layers, default widths; 36 RNAs of 110-140 nt plus four of 5-30 nt (4,615 nt, 138,450 edge
+      rows > 65,536): k_emm128 / k_emm_fwd2 at the 2 x CUs cap of 512 workgroups with 1,082 row tiles, i.e. their
+      grid-stride loops; the f32 trainer's k_tgemm / k_tgemm_tn over 138 K edge rows.  fp64 oracle: ~7 s, 9 GB peak RSS.
+    large_nodes: k = 4, 1 MPNN layer, default widths; the 136 RNAs of 110-140 nt (17,105 nt) of
+      test_bf16_mixed_training_large_batch_tracks_f32, longest last; dropout 0.4: the bf16-mixed node GEMMs on 128-row
+      tiles (k_tmm<false, 2> and k_tmm<true, 2>, 596 workgroups at N = 512), k_mm128 on 149 row tiles.
+      fp64 oracle: ~15 s, 9.2 GB peak RSS."""
+    from rnampnn.model._schema import DEFAULT_HPARAMS
+    from rnampnn.utils import synth
+    if name.startswith("default_k30"):
+        lens = [1, 2, 5, 17, 29, 30, 31, 33, 64, 120, 140]
+        hp = dict(DEFAULT_HPARAMS, num_res_neighbours=30)
+        (p, seed), first = ((0.4, 71) if name.endswith("dropout") else (0.0, 0)), 500
+    elif name == "large_edges":
+        lens = _longest_last(list(synth.synth_lengths(36, 110, 140, seed=6)) + [5, 12, 23, 30])
+        hp = dict(DEFAULT_HPARAMS, num_res_neighbours=30, num_res_mpnn_layers=2)
+        p, seed, first = 0.4, 72, 1200
+    elif name == "large_nodes":
+        lens = _longest_last(synth.synth_lengths(136, 110, 140, seed=4))
+        hp = dict(DEFAULT_HPARAMS, num_res_neighbours=4, num_res_mpnn_layers=1)
+        p, seed, first = 0.4, 73, 900
+    else:
+        raise KeyError(name)
+    hp["padding_len"] = max(lens)
+    return hp, lens, first, p, seed
+
+
+def oracle_loss_and_grad(hp, sd_np, coords, mask, labels, dropout=0.0, seed=0):
+    """fp64 oracle forward + double-softmax loss + autograd -> (loss, logits (B,T,4) f64, {key: grad f64})."""
+    from oracle import rnampnn_oracle as O
+    knn = O.knn_graph
+    O.knn_graph = lambda c, m, k: knn(c.float(), m.float(), k)        # the reference's fp32 graph (module docstring)
+    try:
+        sd = {k: torch.from_numpy(v).double().requires_grad_(True) for k, v in sd_np.items()}
+        cfg = O.OracleConfig(**{k: v for k, v in hp.items() if k in O.OracleConfig.__dataclass_fields__})
+        m = torch.from_numpy(mask).double()
+        logits, _ = O.forward(torch.from_numpy(coords).double(), m, sd, cfg, dropout=dropout, seed=seed)
+        loss = O.loss_double_softmax(logits, m, torch.from_numpy(labels))
+        loss.backward()
+    finally:
+        O.knn_graph = knn
+    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)).detach() for k, v in sd.items()}
+    return float(loss.detach()), logits.detach(), grads
+
+
+def grad_dict(model):
+    return {k: p.grad.detach().cpu().double().clone() for k, p in model.named_parameters()}
+
+
+def grad_errors(g, r):
+    """-> ({key: max|g - r| / max|r|} over the tensors with a nonzero reference, worst |g| over the others, flat cosine)."""
+    rel, dead, dot, n1, n2 = {}, 0.0, 0.0, 0.0, 0.0
+    for key, rv in r.items():
+        gv = g[key].double()
+        dot += float((gv * rv).sum()); n1 += float((gv * gv).sum()); n2 += float((rv * rv).sum())
+        scale = float(rv.abs().max())
+        if scale == 0.0:
+            dead = max(dead, float(gv.abs().max()))
+        else:
+            rel[key] = float((gv - rv).abs().max()) / scale
+    return rel, dead, dot / max((n1 * n2) ** 0.5, 1e-300)
+
+
+@pytest.fixture(scope="module")
+def reference():
+    """case -> dict(hp, lens, dropout, seed, coords, mask, labels, sd, loss, logits, grads); one fp64 oracle run per case."""
+    from rnampnn.model._schema import state_dict_shapes
+    from rnampnn.utils import synth
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            hp, lens, first, p, seed = _case(name)
+            coords, mask, labels = synth.synth_batch(lens, first_index=first)
+            sd = synth.closed_form_state_dict(state_dict_shapes(hp))
+            loss, logits, grads = oracle_loss_and_grad(hp, sd, coords, mask, labels, p, seed)
+            cache[name] = dict(hp=hp, lens=lens, dropout=p, seed=seed, coords=coords, mask=mask, labels=labels, sd=sd,
+                               loss=loss, logits=logits, grads=grads)
+        return cache[name]
+    return get
+
+
+def _trainer(ref, precision):
+    from rnampnn.model._schema import state_dict_shapes
+    model, _ = _model(ref["hp"], state_dict_shapes(ref["hp"]), precision)
+    assert model.train_precision == precision
+    return model
+
+
+def _step(model, ref, coords=None, mask=None):
+    c = torch.from_numpy(ref["coords"] if coords is None else coords)
+    m = torch.from_numpy(ref["mask"] if mask is None else mask)
+    loss, logits = model.loss_and_grad(torch.from_numpy(ref["labels"]), c, m, return_logits=True, dropout=ref["dropout"],
+                                       seed=ref["seed"])
+    return float(loss), logits.cpu().double(), grad_dict(model)
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_f32_trainer_matches_fp64_oracle_autograd(case, reference):
+    """f32 trainer: loss within 1e-5, logits within F32_LOGIT_TOL, every parameter gradient within F32_GRAD_REL[case] of its
+    largest reference entry, flat cosine > 1 - 1e-6.  Negative control: the HIP gradient of the same batch with the last
+    residue of the longest RNA masked out (its 30 edge rows at k = 30, 4 at k = 4) misses the FULL-batch reference by more
+    than the bound in the median tensor - the bound resolves a one-residue change."""
+    ref = reference(case)
+    model = _trainer(ref, "f32")
+    loss, logits, g = _step(model, ref)
+    rel, dead, cos = grad_errors(g, ref["grads"])
+    worst_key = max(rel, key=rel.get)
+    m = torch.from_numpy(ref["mask"]).bool()
+    dlogit = float((logits - ref["logits"])[m].abs().max())
+    b = len(ref["lens"]) - 1
+    n = ref["lens"][b]
+    c2, m2 = ref["coords"].copy(), ref["mask"].copy()
+    c2[b, n - 1], m2[b, n - 1] = 0.0, 0.0
+    _, _, g2 = _step(model, ref, c2, m2)
+    rel2, _, _ = grad_errors(g2, ref["grads"])
+    med2 = float(np.median(list(rel2.values())))
+    bound = F32_GRAD_REL[case]
+    print(f"{case} f32: |dloss| {abs(loss - ref['loss']):.2e}, max|dlogit| {dlogit:.2e}, worst per-tensor {rel[worst_key]:.2e} "
+          f"({worst_key}), median {np.median(list(rel.values())):.2e}, cos 1-{1 - cos:.1e}, dead {dead:.1e}; "
+          f"bound {bound:.1e}; one residue masked: median {med2:.2e} (margin {med2 / bound:.1f}x)")
+    assert abs(loss - ref["loss"]) < F32_LOSS_TOL
+    assert dlogit < F32_LOGIT_TOL
+    assert rel[worst_key] < bound, f"{worst_key}: {rel[worst_key]:.2e}"
+    assert dead < DEAD_ABS
+    assert cos > F32_COS
+    assert med2 > bound, f"negative control: masking one residue moves the median tensor by only {med2:.2e}"
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_bf16_mixed_trainer_matches_fp64_oracle_autograd(case, reference):
+    """bf16-mixed trainer, the bounds of test_bf16_mixed_gradients_match_oracle_autograd at production shapes: loss within
+    2e-3, logits within bf16_tol, every parameter gradient within BF16_GRAD_REL of its largest reference entry, flat cosine
+    > 0.9995."""
+    ref = reference(case)
+    model = _trainer(ref, "bf16")
+    loss, logits, g = _step(model, ref)
+    rel, dead, cos = grad_errors(g, ref["grads"])
+    worst_key = max(rel, key=rel.get)
+    m = torch.from_numpy(ref["mask"]).bool()
+    dlogit = float((logits - ref["logits"])[m].abs().max())
+    tol = bf16_tol(ref["logits"], ref["mask"])
+    over = sorted(((v, k) for k, v in rel.items() if v >= BF16_GRAD_REL), reverse=True)
+    print(f"{case} bf16-mixed: |dloss| {abs(loss - ref['loss']):.2e}, max|dlogit| {dlogit:.2e} (tol {tol:.1e}), worst per-tensor "
+          f"{rel[worst_key]:.2e} ({worst_key}), median {np.median(list(rel.values())):.2e}, cos {cos:.6f}, dead {dead:.1e}; "
+          f"over {BF16_GRAD_REL}: " + ", ".join(f"{k} {v:.2e}" for v, k in over))
+    assert abs(loss - ref["loss"]) < BF16_LOSS_TOL
+    assert dlogit < tol
+    assert dead < DEAD_ABS
+    assert cos > BF16_COS
+    if case in BF16_PER_TENSOR_OPEN:
+        assert over, f"{case}: every tensor is within BF16_GRAD_REL now - remove it from BF16_PER_TENSOR_OPEN"
+        pytest.xfail(f"open finding (BF16_PER_TENSOR_OPEN): {len(over)} tensor(s) over BF16_GRAD_REL, worst {worst_key}")
+    assert rel[worst_key] < BF16_GRAD_REL, f"{worst_key}: {rel[worst_key]:.2e}"
+
+
+# ---------------------------------------------------------------------------------------------------------------- T_norm
+# shard with T_norm vs the padded global batch, per tensor relative to its largest entry: ~4x the measured f32 reordering
+# difference (3.1e-7 f32, 4.2e-7 bf16-mixed; the loss was bit-identical).  Before the phantom rule followed T_norm, the shard
+# missed by 0.36 (worst tensor) and 0.16 (median tensor) in both trainers.
+REORDER_REL = 1.6e-6
+REORDER_LOSS = 5e-7          # ~4 ulp of the ~1.39 loss
+# the autograd path (torch's double-softmax loss and its dlogits) vs the native loss_and_grad: measured 3.8e-6 and 2.4e-7
+AUTOGRAD_REL = 1.5e-5
+AUTOGRAD_LOSS = 1e-6
+
+
+def _shard_and_padded():
+    """Global batch [40, 12, 20, 27] at k = 30; shard = RNAs 1 and 3 ([12, 27]).  -> (hp, (coords, mask, labels) of the shard
+    cut to its own T = 27, the same of the two RNAs zero-padded to the global T = 40)."""
+    from rnampnn.model._schema import DEFAULT_HPARAMS
+    from rnampnn.utils import synth
+    coords, mask, labels = synth.synth_batch([40, 12, 20, 27], first_index=3100)
+    hp = dict(DEFAULT_HPARAMS, num_res_neighbours=30, padding_len=40)
+    sel = [1, 3]
+    shard = tuple(np.ascontiguousarray(a[sel][:, :27]) for a in (coords, mask, labels))
+    padded = tuple(np.ascontiguousarray(a[sel]) for a in (coords, mask, labels))
+    return hp, shard, padded
+
+
+def _max_rel(g, r):
+    out = {}
+    for key, rv in r.items():
+        scale = float(rv.abs().max())
+        d = float((g[key] - rv).abs().max())
+        out[key] = d / scale if scale > 0 else (0.0 if d == 0 else float("inf"))
+    return out
+
+
+@pytest.mark.parametrize("precision", ["f32", "bf16"])
+def test_T_norm_training_shard_equals_the_padded_global_batch(precision):
+    """A shard [12, 27] of the global batch [40, 12, 20, 27] (k = 30), cut to its own T = 27 and run with T_norm = 40, against
+    the same two RNAs zero-padded to T = 40 (dropout 0.4).  The 27-nt RNA has n - 1 < k, so its slot 26 is the phantom
+    neighbour of the global batch; the shard has no padded residue to name, so the phantom rule and its geometry record
+    follow max(T, T_norm).
+
+    The packed rows and the dropout masks are the same either way; the reduction split counts are not (they follow the host
+    row bound B*T of TRows), so the gradient is compared up to f32 reordering: REORDER_REL per tensor (~4x the measured
+    difference).  The forward's reductions run per RNA, so the logits are bit-identical.  Both runs are within the
+    part-1 bounds of fp64 oracle autograd on the padded tensor.  Negative control: without T_norm the shard's gradient
+    misses the padded run's by more than the f32 oracle bound in the median tensor.  The f32 run also goes once through
+    the autograd path (model(c, m, T_norm=40), double-softmax loss, .backward())."""
+    from rnampnn.model._schema import state_dict_shapes
+    hp, (cs, ms, ys), (cp, mp, yp) = _shard_and_padded()
+    model, sd = _model(hp, state_dict_shapes(hp), precision)
+    p, seed = 0.4, 909
+
+    def run(c, m, y, T_norm=0):
+        loss, logits = model.loss_and_grad(torch.from_numpy(y), torch.from_numpy(c), torch.from_numpy(m), T_norm=T_norm,
+                                           return_logits=True, dropout=p, seed=seed)
+        return float(loss), logits.cpu(), grad_dict(model)
+
+    lp, zp, gp = run(cp, mp, yp)
+    ls, zs, gs = run(cs, ms, ys, T_norm=40)
+    lo, zo, go = run(cs, ms, ys)
+    d_shard = _max_rel(gs, gp)
+    d_own = _max_rel(go, gp)
+    worst = max(d_shard, key=d_shard.get)
+    same_logits = torch.equal(zs, zp[:, :27])
+    print(f"{precision}: T_norm shard vs padded: logits bit-identical {same_logits} (max diff "
+          f"{float((zs - zp[:, :27]).abs().max()):.2e}), |dloss| {abs(ls - lp):.2e}, worst per-tensor {d_shard[worst]:.2e} "
+          f"({worst}), median {np.median(list(d_shard.values())):.2e}; without T_norm: median {np.median(list(d_own.values())):.2e}")
+    ref_loss, ref_logits, ref_grads = oracle_loss_and_grad(hp, sd, cp, mp, yp, p, seed)
+    mval = torch.from_numpy(mp).bool()
+    for tag, loss, logits, g in (("padded", lp, zp, gp), ("shard", ls, torch.nn.functional.pad(zs, (0, 0, 0, 13)), gs)):
+        rel, dead, cos = grad_errors(g, ref_grads)
+        dlogit = float((logits.double() - ref_logits)[mval].abs().max())
+        print(f"  {tag} vs fp64 oracle: |dloss| {abs(loss - ref_loss):.2e}, max|dlogit| {dlogit:.2e}, worst per-tensor "
+              f"{max(rel.values()):.2e}, cos {cos:.7f}")
+        if precision == "f32":
+            assert abs(loss - ref_loss) < F32_LOSS_TOL and dlogit < F32_LOGIT_TOL, tag
+            assert max(rel.values()) < F32_GRAD_REL["default_k30_dropout"] and cos > F32_COS, tag
+        else:
+            assert abs(loss - ref_loss) < BF16_LOSS_TOL and dlogit < bf16_tol(ref_logits, mp), tag
+            assert max(rel.values()) < BF16_GRAD_REL and cos > BF16_COS, tag
+        assert dead < DEAD_ABS, tag
+    assert same_logits
+    assert abs(ls - lp) < REORDER_LOSS
+    assert d_shard[worst] < REORDER_REL, f"{worst}: {d_shard[worst]:.2e}"
+    assert np.median(list(d_own.values())) > F32_GRAD_REL["default_k30_dropout"]
+    if precision != "f32":
+        return
+    # the autograd path: train mode (dropout = the module's 0.4), the same seed through manual_seed
+    model.train()
+    model.manual_seed(5)
+    native = float(model.loss_and_grad(torch.from_numpy(yp), torch.from_numpy(cp), torch.from_numpy(mp)))
+    g_native = grad_dict(model)
+    model.zero_grad(set_to_none=True)
+    model.manual_seed(5)
+    logits = model(torch.from_numpy(cs), torch.from_numpy(ms), T_norm=40)
+    assert logits.requires_grad
+    valid = torch.from_numpy(ms).bool().cuda()
+    onehot = torch.nn.functional.one_hot(torch.from_numpy(ys), 4).float().cuda()
+    loss = model.mix_loss(torch.softmax(logits, dim=-1)[valid], onehot[valid])
+    loss.backward()
+    d_auto = _max_rel(grad_dict(model), g_native)
+    loss = float(loss.detach())
+    print(f"  autograd path: |dloss| {abs(loss - native):.2e}, worst per-tensor {max(d_auto.values()):.2e}")
+    assert abs(loss - native) < AUTOGRAD_LOSS
+    assert max(d_auto.values()) < AUTOGRAD_REL
