@@ -269,6 +269,42 @@ int rnampnn_gbdt_predict(rnampnn_gbdt_handle g, const float* X, int32_t n_rows, 
                          int32_t* argmax_out /* (n_rows) or null */, void* stream);
 const char* rnampnn_gbdt_last_error(void);
 
+/* ---- Fitting that read-out on the device (PARITY UNPINNED as above: XGBoost's published multi:softmax gradient /
+ * hessian, split gain and leaf weight are restated, the cuts, the binning and the sampling are this library's own).
+ * Histogram method: X is binned once into uint8 with per-feature cuts, gradients are quantised onto the grid 2^-20 and summed as integers,
+ * the split search is fp64, trees grow level by level to max_depth; the result is bit-reproducible for one seed and independent of ldx.
+ * `cuts` (num_feature, 255) f32 and `n_cuts` (num_feature) i32 are DEVICE arrays the caller prepares (the library holds no sort): per
+ * feature the ascending distinct values v[floor(i * n_rows / max_bin)], i = 1 .. max_bin - 1, of the sorted column v, without any equal
+ * to v[0]; bin(x) = number of cuts <= x, and a split at cut j (bin <= j goes left) carries split_condition = cuts[j].
+ * Sampling: row i takes part in round r iff u(seed, 2r, i) < subsample; tree t = r * num_class + c keeps the
+ * max(1, floor(colsample_bytree * num_feature)) features of smallest u(seed, 2t + 1, f), ties to the lower index (u: DESIGN section 9).
+ * X (n_rows, ldx >= num_feature) f32 and y (n_rows) i32 in [0, num_class) are device arrays; a non-finite X or a label out of range is
+ * RNAMPNN_ERR_BAD_ARG, found by the one check that precedes the fit.  All work is enqueued on `stream`; the call synchronises it twice
+ * (after that check, and at the end to learn the model's size).  The handle is the evaluator's: rnampnn_gbdt_predict / _destroy take it. */
+typedef struct rnampnn_gbdt_params {
+    int32_t num_class, n_estimators, max_depth /* 1..10 */, max_bin /* 2..256 */;
+    double learning_rate, subsample, colsample_bytree, reg_lambda, gamma, min_child_weight, base_score;
+    uint64_t seed;
+} rnampnn_gbdt_params;
+int rnampnn_gbdt_fit(const rnampnn_gbdt_params* params, const float* X, int32_t n_rows, int32_t ldx, int32_t num_feature, const int32_t* y,
+                     const float* cuts, const int32_t* n_cuts, void* stream, rnampnn_gbdt_handle* out);
+/* A model leaves the process as the arrays rnampnn_gbdt_create reads.  Every pointer may be null: call once for the sizes
+ * (tree_offsets holds num_trees + 1 entries, tree_class num_trees, the five node arrays total_nodes), then with host buffers. */
+int rnampnn_gbdt_export(rnampnn_gbdt_handle g, int32_t* num_trees, int32_t* total_nodes, int32_t* num_class, int32_t* num_feature,
+                        float* base_score, int32_t* tree_offsets, int32_t* tree_class, int32_t* left_children, int32_t* right_children,
+                        int32_t* split_indices, float* split_conditions, uint8_t* default_left);
+/* Stage taps of the fit.  _bin: X, cuts -> bins (n_rows, num_feature) u8, device, on `stream`.
+ * _grow_tree: ONE tree from integer gradients g, h (n_rows) i32 on the grid 2^-20 over the rows with row_mask != 0 and the features with
+ * feat_mask != 0 (device bytes, null = all); uses max_depth, learning_rate, reg_lambda, gamma, min_child_weight of `params`.  The tree
+ * comes back in HOST arrays of capacity 2^(max_depth + 1) - 1, nodes numbered breadth-first, leaves with left = right = -1 and their
+ * value in split_conditions; the call synchronises `stream`. */
+int rnampnn_gbdt_bin(const float* X, int32_t n_rows, int32_t ldx, int32_t num_feature, const float* cuts, const int32_t* n_cuts,
+                     uint8_t* bins, void* stream);
+int rnampnn_gbdt_grow_tree(const rnampnn_gbdt_params* params, const uint8_t* bins, int32_t n_rows, int32_t num_feature, const float* cuts,
+                           const int32_t* n_cuts, const int32_t* g, const int32_t* h, const uint8_t* row_mask, const uint8_t* feat_mask,
+                           int32_t* left_children, int32_t* right_children, int32_t* split_indices, float* split_conditions,
+                           int32_t* n_nodes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

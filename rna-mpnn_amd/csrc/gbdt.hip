@@ -12,16 +12,9 @@
 #include <cstring>
 #include <vector>
 
-struct rnampnn_gbdt {
-    int num_trees = 0, num_class = 0, num_feature = 0, total_nodes = 0;
-    float base_score = 0.f;
-    int *d_off = nullptr, *d_cls = nullptr;
-    int4* d_nodes = nullptr;           // {left, right, feature | default_left << 31, threshold / leaf value bits}
-};
-
 static thread_local char gb_err[256] = "";
 extern "C" const char* rnampnn_gbdt_last_error(void) { return gb_err; }
-static int gb_fail(int code, const char* msg) { snprintf(gb_err, sizeof(gb_err), "%s", msg); return code; }
+int gb_fail(int code, const char* msg) { snprintf(gb_err, sizeof(gb_err), "%s", msg); return code; }
 
 // One WAVE per row, one LANE per tree (64 trees at a time): the row's features sit in LDS (every lane reads them at data-dependent
 // offsets), a node is ONE 16-byte record {left, right, feature | default_left << 31, threshold bits} (a walk is a chain of dependent

@@ -104,3 +104,12 @@ void launch_argmax_recovery(const float* logits, const float* mask, const int32_
                             int8_t* pred, int32_t* correct, int32_t* valid, hipStream_t s);
 void launch_sample(const float* logits, const float* mask, int B, int T, float temperature, int n_samples,
                    uint64_t seed, const uint64_t* seed_dev, int8_t* out, hipStream_t s);
+
+// A gradient-boosted-tree model on the device (gbdt.hip evaluates it, gbdt_fit.hip grows it)
+struct rnampnn_gbdt {
+    int num_trees = 0, num_class = 0, num_feature = 0, total_nodes = 0;
+    float base_score = 0.f;
+    int *d_off = nullptr, *d_cls = nullptr;
+    int4* d_nodes = nullptr;           // {left, right, feature | default_left << 31, threshold / leaf value bits}
+};
+int gb_fail(int code, const char* msg);    // records the text rnampnn_gbdt_last_error returns (thread-local), returns code

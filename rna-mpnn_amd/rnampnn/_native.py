@@ -45,6 +45,12 @@ class RnaMpnnForwardIO(C.Structure):
                 ("h_post", C.c_void_p), ("raw_emb", C.c_void_p)]
 
 
+class GbdtParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("num_class", "n_estimators", "max_depth", "max_bin")] + \
+               [(n, C.c_double) for n in ("learning_rate", "subsample", "colsample_bytree", "reg_lambda", "gamma", "min_child_weight",
+                                          "base_score")] + [("seed", C.c_uint64)]
+
+
 # every symbol include/rnampnn_hip.h declares: (restype, argtypes)
 _VP, _I32, _I64, _SZ, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t, C.c_float
 SYMBOLS = {
@@ -86,6 +92,11 @@ SYMBOLS = {
     "rnampnn_gbdt_destroy": (C.c_int, [_VP]),
     "rnampnn_gbdt_predict": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP]),
     "rnampnn_gbdt_last_error": (C.c_char_p, []),
+    "rnampnn_gbdt_fit": (C.c_int, [C.POINTER(GbdtParams), _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, C.POINTER(_VP)]),
+    "rnampnn_gbdt_export": (C.c_int, [_VP] + [C.POINTER(_I32)] * 4 + [C.POINTER(_F)] + [_VP] * 7),
+    "rnampnn_gbdt_bin": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
+    "rnampnn_gbdt_grow_tree": (C.c_int, [C.POINTER(GbdtParams), _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                         C.POINTER(_I32), _VP]),
     "rnampnn_last_error": (C.c_char_p, []),
     "rnampnn_version": (C.c_char_p, []),
 }

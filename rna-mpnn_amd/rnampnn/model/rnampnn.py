@@ -18,7 +18,7 @@ from torch import nn
 import torch.nn.functional as F
 
 from .. import _native
-from ..config.glob import REVERSE_VOCAB
+from ..config.glob import DEFAULT_SEED, REVERSE_VOCAB
 from ..utils.data import check_prefix_mask
 from ._base import NativeModule, _prep, _ptr, _stream
 from ._schema import DEFAULT_HPARAMS
@@ -278,6 +278,37 @@ class RNAMPNN(NativeModule):
         ``XGB-V*.pkl`` in ``on_load_checkpoint`` (rnampnn.py:232-266); pickles are never loaded here."""
         from .xgb import GBDTReadout
         self.xgb_readout = GBDTReadout.from_xgboost_json(model)
+
+    @torch.no_grad()
+    def embed_valid(self, batches):
+        """The reference's ``XGBTrainer._generate_embedding`` (utils/train.py:76-89) without leaving the device: ``batches`` yields
+        (labels, coords, mask, ...) - labels (B, T) class ids or (B, T, 4) one-hot; -> X (n_valid, 256) f32, y (n_valid) int64, the
+        embeddings and labels of the valid positions only, on the model's device."""
+        device = self._device()
+        xs, ys = [], []
+        for batch in batches:
+            labels, coords, mask = batch[0], batch[1], batch[2]
+            valid = mask.to(device) == 1
+            xs.append(self.embedding(coords, mask)[valid])
+            labels = labels.to(device)
+            ys.append((labels.argmax(-1) if labels.dim() == 3 else labels)[valid].to(torch.int64))
+        if not xs:
+            raise ValueError("embed_valid: no batches")
+        return torch.cat(xs), torch.cat(ys)
+
+    @torch.no_grad()
+    def fit_xgb_readout(self, batches, seed: int = DEFAULT_SEED):
+        """``XGBTrainer.on_fit_end`` (utils/train.py:50-75 of the reference): embed every valid nucleotide of ``batches``, fit the tree
+        read-out on those rows ON THE DEVICE (``GBDTReadout.fit``; DESIGN section 9, parity with XGBoost unpinned) with the five
+        hyper-parameters of ``self.hparams`` and attach it as ``self.xgb_readout``, so ``predict_sequences`` takes the tree route.
+        Returns the score on the rows it was fitted on."""
+        from .xgb import GBDTReadout
+        X, y = self.embed_valid(batches)
+        hp = self._hp
+        self.xgb_readout = GBDTReadout.fit(X, y, num_class=4, n_estimators=int(hp["n_estimators"]), max_depth=int(hp["xgb_max_depth"]),
+                                           learning_rate=float(hp["xgb_learning_rate"]), subsample=float(hp["xgb_subsample"]),
+                                           colsample_bytree=float(hp["xgb_colsample_bytree"]), seed=int(seed))
+        return self.xgb_readout.score(X, y)
 
     @torch.no_grad()
     def predict_sequences(self, coords: torch.Tensor, mask: torch.Tensor) -> List[str]:

@@ -31,7 +31,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 
 from rnampnn.model.rnampnn import RNAMPNN  # noqa: E402
 from rnampnn.utils import synth  # noqa: E402
-from rnampnn.utils.data import load_rna_dir  # noqa: E402
+from rnampnn.utils.data import PaddedLoader, bucket_batches, load_rna_dir  # noqa: E402
 from rnampnn.utils.train import Trainer  # noqa: E402
 
 
@@ -58,6 +58,10 @@ def parse(argv=None):
                          "default: each rank its own batch length, as the reference's DDP ranks do")
     ap.add_argument("--no-validation", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--fit-xgb", action="store_true",
+                    help="after the last epoch fit the gradient-boosted-tree read-out on the training embeddings, on the device "
+                         "(the reference's XGBTrainer.on_fit_end, utils/train.py:50-75) and print train / validation score")
+    ap.add_argument("--xgb-out", default=None, help="with --fit-xgb: write the fitted model as XGBoost-schema JSON")
     return ap.parse_args(argv)
 
 
@@ -108,8 +112,31 @@ def run(args, log=print):
         if rank == 0:
             log(f"epoch {epoch}: train_loss {rec['train_loss']:.4f}  val_recovery micro {micro:.4f} macro {macro:.4f}  "
                 f"{rec['nt_per_s']:.0f} nt/s end to end ({rec['steps']} steps, {rec['seconds']:.2f} s, {world} rank(s))")
+    if args.fit_xgb and rank == 0:
+        out["xgb"] = fit_xgb(model, train, train_lens, val, val_lens, args, dev, log)
     out["model"] = model
     return out
+
+
+def fit_xgb(model, train, train_lens, val, val_lens, args, dev, log=print):
+    """``XGBTrainer.on_fit_end``: embeddings of every valid training nucleotide -> tree read-out fitted on the device -> train and
+    validation score; the embeddings never leave the device."""
+    model.eval()
+    loader = lambda items, lens: PaddedLoader(items, bucket_batches(lens, args.batch_size, args.max_nt, seed=0), device=dev)
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    train_score = model.fit_xgb_readout(loader(train, train_lens), seed=args.seed)
+    torch.cuda.synchronize(dev)
+    rec = dict(train_score=train_score, val_score=float("nan"), seconds=time.perf_counter() - t0, trees=len(model.xgb_readout.arrays["tree_class"]))
+    if val:
+        X, y = model.embed_valid(loader(val, val_lens))
+        rec["val_score"] = model.xgb_readout.score(X, y)
+    log(f"tree read-out: {rec['trees']} trees fitted in {rec['seconds']:.2f} s (embedding included)  "
+        f"training score {rec['train_score']:.4f}  validation score {rec['val_score']:.4f}")
+    if args.xgb_out:
+        model.xgb_readout.save_json(args.xgb_out)
+        log(f"tree read-out written to {args.xgb_out}")
+    return rec
 
 
 def main():
