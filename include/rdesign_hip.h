@@ -10,6 +10,8 @@
  * pytorch_lightning and seaborn - absent from this image - and no rdesign fixture or checkpoint ships with the reference.
  * The checker is the CPU restatement `oracle/rdesign_oracle.py` (numpy, citing the reference line by line) alone.
  *
+ * Inference (rdesign_forward / rdesign_readout, f32 or bf16) and the exact-f32 training step (rdesign_loss_and_grad).
+ *
  * Conventions: as rnampnn_hip.h (device pointers, caller's stream, no synchronisation, 0 = success).
  *   X (B,T,6,3) f32 backbone atoms P, O5', C5', C4', C3', O3' (rdesign/utils/data.py:90-115, zero-filled padding),
  *   mask (B,T) f32 0/1 prefix masks.  Outputs are PACKED: the reference drops padded residues
@@ -81,6 +83,21 @@ int rdesign_forward(rdesign_handle h, const float* X, const float* mask, int32_t
  * Workspace: rdesign_readout_workspace_bytes(h, n_rows) (node-sized buffers only). */
 size_t rdesign_readout_workspace_bytes(rdesign_handle h, int32_t n_rows);
 int rdesign_readout(rdesign_handle h, const float* h_V, int32_t n_rows, float* logits, void* ws, size_t ws_bytes, void* stream);
+
+/* Exact-f32 training step: `training_step` + `loss.backward()` of the reference (rdesign.py:95-104) in ONE call - taped forward with
+ * dropout after every GELU the reference follows with nn.Dropout, loss = CrossEntropyLoss()(readout(h_V), S) over the valid residues
+ * (one softmax, mean over N) and the gradient of every parameter.  RDESIGN_PREC_F32 handles only (the reference's rdesign trainer runs
+ * Lightning's 32-bit default): a RDESIGN_PREC_BF16 handle gets RDESIGN_ERR_UNSUPPORTED (the two size queries return 0 and set the error text).
+ *   labels   (B,T) i32 class ids 0..3, padding ignored
+ *   dropout  in [0,1); the keep masks are a pure function of (seed, site, element) - csrc/rdesign_train.hip states the addressing
+ *   loss     device scalar;  logits optional, packed (B*T,4)
+ *   grad     rdesign_param_numel() floats laid out like the weight arena (rdesign_weight_info offsets), OVERWRITTEN; padding floats are zero
+ * Bit-reproducible (no float atomics); rows are bounded by the 32-bit pair index of the dropout hash: B*T*k < 2^26, else RDESIGN_ERR_BAD_ARG.
+ * rdesign_train_tape_bytes: the part of the workspace that holds the tape (a figure for reports). */
+size_t rdesign_train_workspace_bytes(rdesign_handle h, int32_t B, int32_t T);
+size_t rdesign_train_tape_bytes(rdesign_handle h, int32_t B, int32_t T);
+int rdesign_loss_and_grad(rdesign_handle h, const float* X, const float* mask, const int32_t* labels, int32_t B, int32_t T,
+                          float dropout, uint64_t seed, float* loss, float* logits, float* grad, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,9 +8,7 @@
 // exact f32 (`t_gemm`, K-major weight copies) or bf16 MFMA with f32 accumulate (`tm_gemm_nt`, weights as stored, GELU fused into the
 // operand load).  The first message Linear is factored W.[h_E | h_i | h_j] = W_e.h_E + P[i] + Q[j] like the rnampnn kernels.
 // PARITY UNPINNED: see oracle/rdesign_oracle.py (the reference modules cannot be imported here, no fixture ships).
-#include "../../include/rdesign_hip.h"
-#include "rnampnn_internal.h"
-#include "kernels_train.h"
+#include "rdesign_internal.h"
 
 #include <cstdarg>
 #include <cstdio>
@@ -18,15 +16,8 @@
 #include <string>
 #include <vector>
 
-#define RD_H 128
-#define RD_NODE 101
-#define RD_NODEP 104
-#define RD_EDGE 115
-#define RD_EDGEP 116
-#define RD_KMAX 64
-
 static thread_local char rd_err[512] = "";
-static int rd_fail(int code, const char* fmt, ...) {
+int rd_fail(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(rd_err, sizeof(rd_err), fmt, ap);
@@ -34,7 +25,6 @@ static int rd_fail(int code, const char* fmt, ...) {
     return code;
 }
 extern "C" const char* rdesign_last_error(void) { return rd_err; }
-#define RD_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return rd_fail(RDESIGN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); } while (0)
 
 // ------------------------------------------------------------------------------------------ device helpers
 struct V3 { float x, y, z; };
@@ -255,8 +245,8 @@ __global__ void __launch_bounds__(256) k_rd_rownorm(const int* __restrict__ ntot
         else { y[row * RD_H + lane] = o0; y[row * RD_H + 64 + lane] = o1; }
     }
 }
-static void rd_rownorm(const int* ntot, int mul, size_t maxrows, const float* x, const float* res, const float* gain, const float* bias, int mode,
-                       float* y, hipStream_t s, tb16* yb = nullptr) {
+void rd_rownorm(const int* ntot, int mul, size_t maxrows, const float* x, const float* res, const float* gain, const float* bias, int mode,
+                float* y, hipStream_t s, tb16* yb) {
     size_t g = (maxrows + 3) / 4;
     if (g > 8192) g = 8192;
     if (g < 1) g = 1;
@@ -296,23 +286,6 @@ __global__ void __launch_bounds__(256) k_rd_segsum_b(PackInfo pk, int K, const i
 }
 
 // ------------------------------------------------------------------------------------------ handle
-struct RdT { std::string key; int64_t numel; size_t off; };
-struct RdLin { int in, out, w, b; size_t wt; };          // wt: K-major f32 copy [in_pad][out] (f32 path, and K % 16 != 0 shapes)
-struct RdLayer { int n1w, n1b, n2w, n2b; std::vector<RdLin> msg, dense; };
-struct rdesign_ctx {
-    RDesignConfig cfg;
-    std::vector<RdT> raw;
-    size_t raw_floats = 0, der_floats = 0;
-    float* arena = nullptr;          // caller's flat parameter buffer
-    float* der = nullptr;
-    bool finalized = false;
-    WImageCache* wimg = nullptr;     // prebuilt bf16 fragment images of the 128 x 128 weight blocks (bf16 path; kernels_train.h)
-    bool wimg_fresh = false;         // images match the weights (reset by finalize)
-    RdLin node_emb, edge_emb;
-    int nn_g, nn_b, ne_g, ne_b;
-    std::vector<RdLayer> layers;
-    std::vector<RdLin> readout;
-};
 static int rd_add(rdesign_ctx* c, const std::string& key, int64_t numel) {
     c->raw.push_back(RdT{key, numel, c->raw_floats});
     c->raw_floats += (size_t)((numel + 3) / 4 * 4);
@@ -327,7 +300,6 @@ static RdLin rd_lin(rdesign_ctx* c, const std::string& prefix, int in, int out) 
     c->der_floats += (size_t)((in + 3) / 4 * 4) * out;
     return l;
 }
-static inline float* rdp(rdesign_ctx* c, int i) { return c->arena + c->raw[i].off; }
 
 extern "C" int rdesign_create(const RDesignConfig* cfg, rdesign_handle* out) {
     if (!cfg || !out) return rd_fail(RDESIGN_ERR_BAD_ARG, "rdesign_create: null argument");
@@ -404,12 +376,7 @@ extern "C" int rdesign_finalize_weights(rdesign_handle h, void* stream) {
 }
 
 // ------------------------------------------------------------------------------------------ forward
-struct RdWs {
-    int *len, *cu, *node_b, *nbr;
-    float *coords_p, *frame, *node_raw, *edge_raw, *hV, *hV2, *hE, *E1, *E2, *pq, *dh, *dA, *dB, *logits;
-    size_t total;
-};
-static size_t rd_carve(const rdesign_ctx* c, int B, size_t Nmax, char* base, RdWs* w, bool edges = true) {
+size_t rd_carve(const rdesign_ctx* c, int B, size_t Nmax, char* base, RdWs* w, bool edges) {
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return base ? base + o : (char*)nullptr; };
     const size_t K = c->cfg.k_neighbors, E = edges ? Nmax * K : 0, D = c->cfg.dim_dense_layers > c->cfg.readout_hidden_dim ? c->cfg.dim_dense_layers : c->cfg.readout_hidden_dim;
@@ -437,9 +404,6 @@ extern "C" size_t rdesign_workspace_bytes(rdesign_handle h, int32_t B, int32_t T
 }
 
 namespace {
-struct RdRun { rdesign_ctx* c; PackInfo pk; RdWs w; hipStream_t s; bool mixed; TDrop nodrop; int K; bool bad = false;
-    TRows rn() const { return TRows{pk.cu + pk.B, 1, pk.Nmax}; }
-    TRows re() const { return TRows{pk.cu + pk.B, K, pk.Nmax * K}; } };
 // Y = [beta Y] + act(X)[:, 0:Kc] . W[:, k0:k0+Kc]^T + bias        (act = GELU of the stored pre-activation when `gelu_in`)
 void rd_mm(RdRun& r, const TRows& rows, const float* X, int ldx, const RdLin& l, int k0, int Kc, bool use_bias, float* Y, int ldy, int beta,
            bool gelu_in, float* scratch) {
@@ -453,30 +417,12 @@ void rd_mm(RdRun& r, const TRows& rows, const float* X, int ldx, const RdLin& l,
 }
 }  // namespace
 
-extern "C" int rdesign_forward(rdesign_handle h, const float* X, const float* mask, int32_t B, int32_t T, float* h_V, float* logits,
-                               int64_t* edge_index, float* node_raw, float* edge_raw, void* ws, size_t ws_bytes, void* stream) {
-    if (!h || !X || !mask || !ws || B <= 0 || T <= 0) return rd_fail(RDESIGN_ERR_BAD_ARG, "rdesign_forward: null pointer or non-positive B/T");
-    if (!h->arena) return rd_fail(RDESIGN_ERR_WEIGHTS, "no weight arena set");
-    if (!h->finalized) return rd_fail(RDESIGN_ERR_WEIGHTS, "weights not finalized (call rdesign_finalize_weights)");
-    rdesign_ctx* c = h;
-    const size_t Nmax = (size_t)B * T;
-    const int K = c->cfg.k_neighbors;
-    if ((long long)Nmax * K > 0x3fffffffLL / 4) return rd_fail(RDESIGN_ERR_BAD_ARG, "row count out of range for 32-bit edge indexing");
-    if (ws_bytes < rd_carve(c, B, Nmax, nullptr, nullptr)) return rd_fail(RDESIGN_ERR_WORKSPACE, "workspace too small");
-    if (((uintptr_t)ws & 255) != 0) return rd_fail(RDESIGN_ERR_BAD_ARG, "workspace must be 256-byte aligned");
-    const size_t knn_lds = (size_t)(3 + 4) * T * sizeof(float);
-    if (knn_lds > 160 * 1024 - 256) return rd_fail(RDESIGN_ERR_UNSUPPORTED, "max_len %d too long for the LDS-resident k-NN row", T);
-    RdRun r;
-    r.c = c; r.s = (hipStream_t)stream; r.mixed = c->cfg.precision == RDESIGN_PREC_BF16; r.nodrop = TDrop{0ull, 0u, 1.f}; r.K = K;
-    rd_carve(c, B, Nmax, (char*)ws, &r.w);
+size_t rd_knn_lds_bytes(int T) { return (size_t)(3 + 4) * T * sizeof(float); }
+void rd_front(RdRun& r, const float* X, const float* mask, int64_t* edge_index) {
     RdWs& w = r.w;
     hipStream_t s = r.s;
-    r.pk.len = w.len; r.pk.cu = w.cu; r.pk.node_b = w.node_b; r.pk.B = B; r.pk.T = T; r.pk.Nmax = (int)Nmax; r.pk.packed_in = 0;
-    if (r.mixed) {      // weights are static between finalize calls: the images are rebuilt once, blocks first seen in this call build their own
-        if (!c->wimg) c->wimg = t_wimg_create(256);
-        if (c->wimg && (!c->wimg_fresh || t_wimg_pending(c->wimg) > 0)) { t_wimg_refresh(c->wimg, s); c->wimg_fresh = true; }
-        t_wimg_bind(c->wimg);
-    }
+    const int B = r.pk.B, T = r.pk.T, K = r.K;
+    const size_t Nmax = (size_t)r.pk.Nmax, knn_lds = rd_knn_lds_bytes(T);
     launch_lengths(mask, r.pk, s);
     ZeroRegions z{};
     z.ptr[0] = w.hV + Nmax * RD_H; z.words[0] = RD_H; z.ptr[1] = w.hV2 + Nmax * RD_H; z.words[1] = RD_H;
@@ -492,6 +438,33 @@ extern "C" int rdesign_forward(rdesign_handle h, const float* X, const float* ma
         hipLaunchKernelGGL(k_rd_knn, grid, dim3(256), knn_lds, s, w.coords_p, r.pk, K, w.nbr, edge_index);
     }
     hipLaunchKernelGGL(k_rd_edge, dim3((unsigned)((Nmax * K + 127) / 128)), dim3(128), 0, s, r.pk, K, w.nbr, w.coords_p, w.frame, w.edge_raw);
+}
+
+extern "C" int rdesign_forward(rdesign_handle h, const float* X, const float* mask, int32_t B, int32_t T, float* h_V, float* logits,
+                               int64_t* edge_index, float* node_raw, float* edge_raw, void* ws, size_t ws_bytes, void* stream) {
+    if (!h || !X || !mask || !ws || B <= 0 || T <= 0) return rd_fail(RDESIGN_ERR_BAD_ARG, "rdesign_forward: null pointer or non-positive B/T");
+    if (!h->arena) return rd_fail(RDESIGN_ERR_WEIGHTS, "no weight arena set");
+    if (!h->finalized) return rd_fail(RDESIGN_ERR_WEIGHTS, "weights not finalized (call rdesign_finalize_weights)");
+    rdesign_ctx* c = h;
+    const size_t Nmax = (size_t)B * T;
+    const int K = c->cfg.k_neighbors;
+    if ((long long)Nmax * K > 0x3fffffffLL / 4) return rd_fail(RDESIGN_ERR_BAD_ARG, "row count out of range for 32-bit edge indexing");
+    if (ws_bytes < rd_carve(c, B, Nmax, nullptr, nullptr)) return rd_fail(RDESIGN_ERR_WORKSPACE, "workspace too small");
+    if (((uintptr_t)ws & 255) != 0) return rd_fail(RDESIGN_ERR_BAD_ARG, "workspace must be 256-byte aligned");
+    const size_t knn_lds = rd_knn_lds_bytes(T);
+    if (knn_lds > 160 * 1024 - 256) return rd_fail(RDESIGN_ERR_UNSUPPORTED, "max_len %d too long for the LDS-resident k-NN row", T);
+    RdRun r;
+    r.c = c; r.s = (hipStream_t)stream; r.mixed = c->cfg.precision == RDESIGN_PREC_BF16; r.nodrop = TDrop{0ull, 0u, 1.f}; r.K = K;
+    rd_carve(c, B, Nmax, (char*)ws, &r.w);
+    RdWs& w = r.w;
+    hipStream_t s = r.s;
+    r.pk.len = w.len; r.pk.cu = w.cu; r.pk.node_b = w.node_b; r.pk.B = B; r.pk.T = T; r.pk.Nmax = (int)Nmax; r.pk.packed_in = 0;
+    if (r.mixed) {      // weights are static between finalize calls: the images are rebuilt once, blocks first seen in this call build their own
+        if (!c->wimg) c->wimg = t_wimg_create(256);
+        if (c->wimg && (!c->wimg_fresh || t_wimg_pending(c->wimg) > 0)) { t_wimg_refresh(c->wimg, s); c->wimg_fresh = true; }
+        t_wimg_bind(c->wimg);
+    }
+    rd_front(r, X, mask, edge_index);
     if (node_raw) RD_TRY(hipMemcpy2DAsync(node_raw, RD_NODE * sizeof(float), w.node_raw, RD_NODEP * sizeof(float), RD_NODE * sizeof(float), Nmax, hipMemcpyDeviceToDevice, s));
     if (edge_raw) RD_TRY(hipMemcpy2DAsync(edge_raw, RD_EDGE * sizeof(float), w.edge_raw, RD_EDGEP * sizeof(float), RD_EDGE * sizeof(float), Nmax * K, hipMemcpyDeviceToDevice, s));
     // embeddings: Linear (101 / 115 inputs: exact-f32 GEMM on the K-major copy in both precisions) + Normalize

@@ -3,9 +3,13 @@
 The module tree (``features.node_embedding`` ... ``mpnn_layers.{i}.message_layers.{0,3,6}`` ... ``readout.readout_layers.{j}``)
 reproduces the reference's ``state_dict`` keys and shapes, so a reference checkpoint's ``state_dict`` loads with
 ``load_state_dict``; the sub-modules are parameter holders, the arithmetic is ``rdesign_forward`` of ``librnampnn_hip.so``.
-Inference surface only (``forward``, ``readout``, ``validation_step`` / ``test_step`` metrics, ``predict``); the XGBoost head of
-``predict`` is out of scope like the main model's (xgboost is not installed: the reference's own ``NotFittedError`` branch, argmax of
-``Readout``, is the one taken - ``rdesign.py:152-155``).  PARITY UNPINNED (``oracle/rdesign_oracle.py``).
+Inference surface (``forward``, ``readout``, ``validation_step`` / ``test_step`` metrics, ``predict``) in f32 or bf16, and the
+exact-f32 TRAINING STEP: ``loss_and_grad`` (``rdesign_loss_and_grad``: taped forward with dropout, cross-entropy, HIP backward into ONE
+flat gradient buffer), ``training_step`` (the same behind an autograd node) and ``configure_optimizers(fused=True)`` (the main model's
+``FlatAdam`` on this model's flat buffers).  f32 is the reference arithmetic of this model (its trainer sets no ``precision``,
+``rdesign/utils/train.py:107-115``); a bf16-mixed training step is not built, nor a differentiable ``forward`` / ``readout`` pair.
+The XGBoost head of ``predict`` is out of scope like the main model's (xgboost is not installed: the reference's own
+``NotFittedError`` branch, argmax of ``Readout``, is the one taken - ``rdesign.py:152-155``).  PARITY UNPINNED (``oracle/rdesign_oracle.py``).
 """
 from __future__ import annotations
 
@@ -81,6 +85,33 @@ class Readout(nn.Module):
         return self._owner._readout_native(res_embedding)
 
 
+class _TrainStep(torch.autograd.Function):
+    """The loss of one ``rdesign_loss_and_grad`` call as an autograd leaf-maker: forward runs the native step into a private
+    gradient buffer, backward ACCUMULATES ``incoming * gradient`` into the module's ``flat_grad`` (torch semantics: ``p.grad`` grows
+    until ``zero_grad``).  The parameters are inputs only so that the node is part of the graph; they get no gradient through
+    autograd's own return values (None) - ``p.grad`` are views of ``flat_grad``."""
+
+    @staticmethod
+    def forward(ctx, model, X, S, mask, p, seed, *params):
+        g = torch.empty_like(model._flat)
+        loss = model._step_native(X, S, mask, p, seed, g)[0]
+        ctx.model, ctx.g = model, g
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        m, g = ctx.model, ctx.g
+        if g is None:
+            raise RuntimeError("the gradient of this training_step was already consumed (backward ran twice on one step)")
+        ctx.g = None
+        dev = g.device
+        fresh = m._bind_flat_grad(dev)
+        if fresh:                                   # the views were dropped (zero_grad(set_to_none=True)): gradients restart from zero
+            m.flat_grad.zero_()
+        m.flat_grad.add_(g * dloss.to(dev))
+        return (None,) * (6 + len(m._slices))
+
+
 class RNAModel(nn.Module):
     def __init__(self, hidden_dim: int = 128, vocab_size: int = 4, k_neighbors: int = 25, dropout: float = 0.1,
                  node_feat_types=None, edge_feat_types=None, num_message_layers: int = 3, num_dense_layers: int = 3,
@@ -120,13 +151,18 @@ class RNAModel(nn.Module):
         self._sig = None
         self._ws: Optional[torch.Tensor] = None
         self._ext_version = 0
+        self._seed_base, self._seed_ctr = 0, 0
+        self.flat_grad: Optional[torch.Tensor] = None
+        self._tws: Optional[torch.Tensor] = None
 
     # ------------------------------------------------------------------ native state
     @property
     def device(self) -> torch.device:
         return next(self.parameters()).device
 
-    def _ensure(self) -> torch.device:
+    def _ensure(self, for_mixed_training: bool = False) -> torch.device:
+        """Parameters aliased to the flat arena, kernel-side weight copies current.  ``for_mixed_training`` is accepted for
+        ``FlatAdam`` (the main model skips its finalize with it); this model's only training path is f32 and always finalizes."""
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("the rdesign HIP path runs on an MI355X: move the module to 'cuda' first (there is no CPU fallback)")
@@ -147,6 +183,41 @@ class RNAModel(nn.Module):
                 _native.check(lib.rdesign_finalize_weights(self._handle.ptr, _stream(dev)))
             self._sig = sig
         return dev
+
+    # what ``rnampnn.model.rnampnn.FlatAdam`` reads of a model
+    @property
+    def _flat_param(self) -> torch.Tensor:
+        return self._flat
+
+    @property
+    def _param_slices(self):
+        return self._slices
+
+    def _weights_touched(self) -> None:
+        """An in-place update of the flat buffer (``FlatAdam.step``) bypasses the parameters' version counters."""
+        self._ext_version += 1
+
+    def _bind_flat_grad(self, device) -> bool:
+        """(Re-)bind every ``p.grad`` to its slice of ONE flat buffer laid out like the weight arena; True when a view had to be
+        (re)made, i.e. ``zero_grad(set_to_none=True)`` dropped the gradients since the last backward."""
+        if self.flat_grad is None or self.flat_grad.device != device:
+            self.flat_grad = torch.zeros(int(_native.lib().rdesign_param_numel(self._handle.ptr)), dtype=torch.float32, device=device)
+        base = self.flat_grad.data_ptr()
+        fresh = False
+        for p, off, n in self._slices:
+            if p.grad is None or p.grad.data_ptr() != base + 4 * off:
+                p.grad = self.flat_grad[off: off + n].view(p.shape)
+                fresh = True
+        return fresh
+
+    def manual_seed(self, seed: int) -> None:
+        """Seed of the dropout masks: call ``i`` after this draws its masks from ``seed + i``."""
+        self._seed_base, self._seed_ctr = int(seed), 0
+
+    def _next_seed(self) -> int:
+        sd = self._seed_base + self._seed_ctr
+        self._seed_ctr += 1
+        return sd
 
     def _ws_args(self, B: int, T: int, dev, readout_rows: int = 0):
         lib = _native.lib()
@@ -213,7 +284,8 @@ class RNAModel(nn.Module):
     def forward(self, X, S, mask, is_predict: bool = False):
         """-> (h_V (N, 128), S (N,)): packed over the valid residues (``rdesign.py:82-88``, ``feature.py:187-189``)."""
         if self.training:
-            raise NotImplementedError("the rdesign HIP path is inference-only (training stays on the main model, SURVEY.md 8 F3): call .eval()")
+            raise NotImplementedError("forward() of the rdesign HIP path is not differentiable: train with training_step(batch) or "
+                                      "loss_and_grad(X, S, mask) (one native call: forward, loss and backward); call .eval() for inference")
         out = self._run(X, mask, want=("h_V",))
         S_packed = torch.masked_select(S.to(out["h_V"].device), mask.to(out["h_V"].device) == 1)
         return out["h_V"], S_packed
@@ -222,13 +294,78 @@ class RNAModel(nn.Module):
         """``readout(forward(...)[0])`` in one call (no second launch sequence)."""
         return self._run(X, mask, want=("logits",))["logits"]
 
-    def configure_optimizers(self):
-        optimizer = torch.optim.Adam(self.parameters(), lr=self.hparams["lr"])
+    def configure_optimizers(self, fused: bool = False):
+        """``rdesign.py:90-93``: Adam(lr) + StepLR(40, 0.8).  ``fused=True``: the main model's ``FlatAdam`` (one launch per step on
+        the flat parameter / gradient buffers, weight decay 0) instead of ``torch.optim.Adam``."""
+        if fused:
+            from rnampnn.model.rnampnn import FlatAdam
+            self._ensure()
+            optimizer = FlatAdam(self, lr=self.hparams["lr"], weight_decay=0.0)
+        else:
+            optimizer = torch.optim.Adam(self.parameters(), lr=self.hparams["lr"])
         scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=40, gamma=0.8)
         return [optimizer], [scheduler]
 
+    # ------------------------------------------------------------------ training step (exact f32)
+    def _train_args(self, dropout, seed):
+        if self.precision != "f32":
+            raise NotImplementedError("the rdesign training step is built for precision='f32' only (the reference trains this model "
+                                      "in f32; a bf16-mixed step is not built)")
+        p = float((self.hparams["dropout"] if self.training else 0.0) if dropout is None else dropout)
+        return p, (self._next_seed() if seed is None else int(seed))
+
+    def _step_native(self, X, S, mask, p: float, seed: int, grad: torch.Tensor, return_logits: bool = False):
+        """One ``rdesign_loss_and_grad`` call; the gradient of every parameter OVERWRITES ``grad`` (laid out like the weight arena)."""
+        dev = self._ensure()
+        if X.dim() != 4 or X.shape[2:] != (6, 3) or tuple(mask.shape) != tuple(X.shape[:2]) or tuple(S.shape) != tuple(mask.shape):
+            raise ValueError(f"X must be (B, T, 6, 3), S and mask (B, T); got {tuple(X.shape)}, {tuple(S.shape)}, {tuple(mask.shape)}")
+        B, T = int(X.shape[0]), int(X.shape[1])
+        if B == 0 or T == 0:
+            raise ValueError("empty batch")
+        Xd, md, lab = _prep(X, dev), _prep(mask, dev), _prep(S, dev, torch.int32)
+        lib = _native.lib()
+        need = int(lib.rdesign_train_workspace_bytes(self._handle.ptr, B, T))
+        if need == 0:                                # refused sizes (B*T*k beyond the dropout hash's index range): the library has set the text
+            _native.check(_native.ERR_BAD_ARG)
+        if self._tws is None or self._tws.numel() < need + 256 or self._tws.device != dev:
+            self._tws = None
+            self._tws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
+        base = self._tws.data_ptr()
+        aligned = (base + 255) // 256 * 256
+        loss = torch.zeros((), dtype=torch.float32, device=dev)
+        logits = torch.zeros(B * T, 4, dtype=torch.float32, device=dev) if return_logits else None
+        with torch.cuda.device(dev):
+            _native.check(lib.rdesign_loss_and_grad(self._handle.ptr, C.c_void_p(Xd.data_ptr()), C.c_void_p(md.data_ptr()),
+                                                    C.c_void_p(lab.data_ptr()), B, T, C.c_float(p), C.c_uint64(seed & (2 ** 64 - 1)),
+                                                    C.c_void_p(loss.data_ptr()), C.c_void_p(logits.data_ptr()) if return_logits else None,
+                                                    C.c_void_p(grad.data_ptr()), C.c_void_p(aligned),
+                                                    C.c_size_t(self._tws.numel() - (aligned - base)), _stream(dev)))
+        return loss, logits
+
+    def loss_and_grad(self, X, S, mask, dropout: Optional[float] = None, seed: Optional[int] = None, return_logits: bool = False):
+        """``training_step`` + ``loss.backward()`` of the reference (``rdesign.py:95-104``) in one native call (f32 HIP kernels,
+        bit-reproducible): -> loss (device scalar) [, logits (N, 4) packed over the valid residues].  ``dropout``: None = the module's
+        hyper-parameter in train mode and 0 in eval mode; the masks are a function of ``seed`` (None = the module's running counter,
+        ``manual_seed``).  Afterwards every ``p.grad`` is a view of ONE flat buffer ``self.flat_grad`` (OVERWRITTEN), so a
+        data-parallel job averages gradients with one ``dist.all_reduce(model.flat_grad)``."""
+        p, sd = self._train_args(dropout, seed)
+        dev = self._ensure()
+        self._bind_flat_grad(dev)
+        loss, logits = self._step_native(X, S, mask, p, sd, self.flat_grad, return_logits)
+        if return_logits:
+            self._check_mask(mask)
+            return loss, logits[:int(mask.sum().item())]
+        return loss
+
     def training_step(self, batch):
-        raise NotImplementedError("the rdesign HIP path is inference-only; its backward is not built (DESIGN.md section 9)")
+        """``rdesign.py:95-104``: -> scalar loss carrying an autograd node; ``loss.backward()`` ACCUMULATES the HIP gradient, scaled by
+        the incoming gradient, into ``p.grad`` (views of ``flat_grad``) until ``zero_grad``."""
+        X, S, mask, lengths, _ = batch
+        p, sd = self._train_args(None, None)
+        self._ensure()
+        if not torch.is_grad_enabled():
+            return self._step_native(X, S, mask, p, sd, torch.empty_like(self._flat))[0]
+        return _TrainStep.apply(self, X, S, mask, p, sd, *[q for q, _, _ in self._slices])
 
     def _eval_step(self, batch, store, loss_key):
         X, S, mask, lengths, _ = batch
