@@ -131,11 +131,8 @@ void te_seg_mean(const PackInfo& pk, int k, const int* nbr, const tb16* pre2, co
 void te_seg_mean_bwd(const PackInfo& pk, int k, const int* nbr, const float* dagg, const tb16* pre2, tb16* dpre2, const TDrop& dr, unsigned site, hipStream_t s);
 void te_edge_res_bwd(const PackInfo& pk, int k, const int* nbr, const tb16* de, const tb16* pre2, tb16* dpre2, const TDrop& dr, unsigned site, hipStream_t s);
 void te_edge_pq_bwd(const PackInfo& pk, int k, const tb16* dpre1, const int* start, const int* list, float* dpq, hipStream_t s);
-void te_zero_invalid(const PackInfo& pk, int k, const int* nbr, tb16* x, hipStream_t s);
 void te_edge_features(const PackInfo& pk, int k, const float* geom, const int* nbr, tb16* F, hipStream_t s);          // raw edge features, bf16 [E][128] (90 live columns)
 void te_edge_act(const PackInfo& pk, int k, const int* nbr, const tb16* pre, tb16* out, const TDrop& dr, unsigned site, hipStream_t s);   // out = valid ? drop(gelu(pre)) : 0
-void te_gelu_fwd_out(const TRows& rows, const float* x, tb16* y, int D, const TDrop& dr, unsigned site, hipStream_t s);      // y = bf16(drop(gelu(x)))
-void te_gelu_bwd_in(const TRows& rows, const tb16* dy, const float* pre, float* dx, int D, const TDrop& dr, unsigned site, hipStream_t s);   // dx = dy gelu'(pre) mask
 
 // ---- cache of prebuilt bf16 fragment images of the 128 x 128 weight blocks the weights-resident GEMMs use (kernels_train.hip):
 // bind it for the calling thread, refresh at the start of a training forward (one launch rebuilds every image registered so far).

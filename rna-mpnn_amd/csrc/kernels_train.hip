@@ -6,6 +6,7 @@
 // (loss = cross_entropy(softmax(logits)[valid], label), mean over valid nucleotides) and the forward
 // lines cited in kernels_f32.hip.  Dropout: counter-hash masks (TDrop, kernels_train.h); every cross-workgroup sum is an ordered two-stage reduction (no float atomics).
 #include "kernels_train.h"
+#include "train_dev.h"
 #include <cstdio>
 #include <vector>
 #include <cstdlib>
@@ -14,62 +15,6 @@
 
 static constexpr float kSEPS = 1.0e-6f;
 #define TLD 132
-
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_d(float x) {     // d/dx [x Phi(x)] = Phi(x) + x phi(x)
-    return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
-}
-__device__ __forceinline__ int nrows(const TRows& r) { return *r.ntot * r.mul; }
-// dropout multiplier of one element: 0 or 1/(1-p) (kernels_train.h: TDrop; restated by the oracle's dropout_multiplier).
-__device__ __forceinline__ unsigned drop_key(const TDrop& d, unsigned site) {         // wave-uniform part of the hash input
-    const unsigned long long sd = d.seed_dev ? *d.seed_dev : d.seed;
-    return site * 0x85EBCA6Bu + (unsigned)sd + (unsigned)(sd >> 32) * 0x27D4EB2Fu;
-}
-__device__ __forceinline__ unsigned drop_hash(unsigned x) {
-    x ^= x >> 16; x *= 0x85EBCA6Bu;
-    x ^= x >> 13; x *= 0xC2B2AE35u;
-    x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ float drop_mul(const TDrop& d, unsigned site, unsigned long long idx) {
-    if (d.thresh == 0u) return 1.f;
-    const unsigned long long P = idx >> 1;
-    const unsigned x = drop_hash((unsigned)P + (unsigned)(P >> 32) * 0xC2B2AE35u + drop_key(d, site));
-    return ((idx & 1ull) ? x >> 16 : x & 0xffffu) >= d.thresh ? d.scale : 0.f;
-}
-// both elements of pair P (element indices 2P, 2P + 1) when P is known to fit 32 bits (every [rows][D] tensor of the trainer: the
-// entry points bound rows * D / 2 < 2^32); key = drop_key(d, site)
-__device__ __forceinline__ void drop_pair(const TDrop& d, unsigned key, unsigned P, float& m0, float& m1) {
-#ifdef TE_EXP_NOHASH      // timing experiment only (wrong masks): what the hash costs
-    m0 = m1 = __uint_as_float((P + key) & 0x3f800000u); return;
-#endif
-    if (d.thresh == 0u) { m0 = 1.f; m1 = 1.f; return; }
-    const unsigned x = drop_hash(P + key);
-    m0 = (x & 0xffffu) >= d.thresh ? d.scale : 0.f;
-    m1 = (x >> 16) >= d.thresh ? d.scale : 0.f;
-}
-// the 8 multipliers of elements 8 * P8 .. 8 * P8 + 7  (P8 = element index / 8)
-__device__ __forceinline__ void drop8(const TDrop& d, unsigned key, unsigned P8, float (&m)[8]) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) drop_pair(d, key, 4u * P8 + q, m[2 * q], m[2 * q + 1]);
-}
-// GELU and its derivative for the fused prologues / epilogues of the bf16-mixed GEMMs: Phi(x) ~ sigmoid(x (c0 + c1 x^2)),
-// coefficients minimax-fitted to the erf form (max |x Phi - gelu| 2.7e-4, below the bf16 rounding of the operands these
-// values are converted to); derivative = Phi + x phi.  The f32 kernels (parity grade) keep erff.
-__device__ __forceinline__ float phi_fast(float x) {
-#ifdef TE_EXP_NOACT       // timing experiment only (wrong values): what the transcendental GELU costs
-    return fmaf(x, 0.25f, 0.5f);
-#endif
-    const float p = fmaf(x * x, -0.10012571f, -2.3087657f);           // -log2(e) (c0 + c1 x^2)
-    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * p));
-}
-__device__ __forceinline__ float gelu_fast(float x) { return x * phi_fast(x); }
-__device__ __forceinline__ float gelu_d_fast(float x) {
-#ifdef TE_EXP_NOACT
-    return fmaf(x, 0.5f, 0.5f);
-#endif
-    return fmaf(x * 0.3989422804f, __builtin_amdgcn_exp2f(x * x * -0.72134752f), phi_fast(x));
-}
 
 // ------------------------------------------------------------------------------------------
 // Y[p][0:N] = (beta ? Y : 0) + X[p][0:K] . Wt[0:K][0:N] + bias      (32 x 128 tile, K % 4 == 0)
@@ -3015,9 +2960,6 @@ void te_edge_res_bwd(const PackInfo& pk, int k, const int* nbr, const tb16* de, 
 void te_edge_act(const PackInfo& pk, int k, const int* nbr, const tb16* pre, tb16* out, const TDrop& dr, unsigned site, hipStream_t s) {
     hipLaunchKernelGGL(k_eelem, dim3(eelem_grid(pk, k)), dim3(256), 0, s, pk, k, nbr, 2, nullptr, pre, out, dr, site);
 }
-void te_zero_invalid(const PackInfo& pk, int k, const int* nbr, tb16* x, hipStream_t s) {
-    hipLaunchKernelGGL(k_eelem, dim3(eelem_grid(pk, k)), dim3(256), 0, s, pk, k, nbr, 1, nullptr, nullptr, x, TDrop{0, 0, 1.f}, 0u);
-}
 // one wave per residue: lane = (row group g of 4, 16-byte chunk c16 of the 256-byte row); the 4 groups are folded with fixed-order shuffles
 __global__ void __launch_bounds__(256) k_epq_bwd(PackInfo pk, int k, const tb16* __restrict__ dpre1, const int* __restrict__ start,
                                                  const int* __restrict__ list, float* __restrict__ dpq) {
@@ -3053,29 +2995,4 @@ __global__ void __launch_bounds__(256) k_epq_bwd(PackInfo pk, int k, const tb16*
 }
 void te_edge_pq_bwd(const PackInfo& pk, int k, const tb16* dpre1, const int* start, const int* list, float* dpq, hipStream_t s) {
     hipLaunchKernelGGL(k_epq_bwd, dim3((pk.Nmax + 3) / 4), dim3(256), 0, s, pk, k, dpre1, start, list, dpq);
-}
-__global__ void k_egelu_fwd_out(TRows rows, const float* __restrict__ x, tb16* __restrict__ y, int D, TDrop dr, unsigned site) {
-    const size_t n = (size_t)nrows(rows) * D / 2;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const tf32x2 v = reinterpret_cast<const tf32x2*>(x)[i];
-        float m0, m1;
-        drop_pair(dr, drop_key(dr, site), (unsigned)i, m0, m1);
-        reinterpret_cast<unsigned*>(y)[i] = tpack2(gelu_f(v[0]) * m0, gelu_f(v[1]) * m1);
-    }
-}
-__global__ void k_egelu_bwd_in(TRows rows, const tb16* __restrict__ dy, const float* __restrict__ pre, float* __restrict__ dx, int D, TDrop dr, unsigned site) {
-    const size_t n = (size_t)nrows(rows) * D / 2;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const unsigned w = reinterpret_cast<const unsigned*>(dy)[i];
-        const tf32x2 p = reinterpret_cast<const tf32x2*>(pre)[i];
-        float m0, m1;
-        drop_pair(dr, drop_key(dr, site), (unsigned)i, m0, m1);
-        reinterpret_cast<tf32x2*>(dx)[i] = tf32x2{tbf_lo(w) * gelu_d(p[0]) * m0, tbf_hi(w) * gelu_d(p[1]) * m1};
-    }
-}
-void te_gelu_fwd_out(const TRows& rows, const float* x, tb16* y, int D, const TDrop& dr, unsigned site, hipStream_t s) {
-    hipLaunchKernelGGL(k_egelu_fwd_out, dim3(ew_grid(rows, D)), dim3(256), 0, s, rows, x, y, D, dr, site);
-}
-void te_gelu_bwd_in(const TRows& rows, const tb16* dy, const float* pre, float* dx, int D, const TDrop& dr, unsigned site, hipStream_t s) {
-    hipLaunchKernelGGL(k_egelu_bwd_in, dim3(ew_grid(rows, D)), dim3(256), 0, s, rows, dy, pre, dx, D, dr, site);
 }

@@ -11,24 +11,7 @@
 // element = row * width + channel, row = packed node row p or packed edge row p K + slot.
 // PARITY UNPINNED as the forward: the checker is a restatement (oracle/rdesign_oracle.py) differentiated by torch autograd in float64.
 #include "rdesign_internal.h"
-
-__device__ __forceinline__ float rdt_gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
-__device__ __forceinline__ float rdt_gelu_d(float x) {     // d/dx [x Phi(x)] = Phi(x) + x phi(x)
-    return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
-}
-// the dropout multiplier of one element, 0 or 1/(1-p): the counter hash of kernels_train.hip (drop_mul), restated here because that one is private to
-// its translation unit; the element-wise kernels of that file and these two segment kernels must agree bit for bit
-__device__ __forceinline__ float rdt_drop_mul(const TDrop& d, unsigned site, unsigned long long idx) {
-    if (d.thresh == 0u) return 1.f;
-    const unsigned long long sd = d.seed_dev ? *d.seed_dev : d.seed;
-    const unsigned key = site * 0x85EBCA6Bu + (unsigned)sd + (unsigned)(sd >> 32) * 0x27D4EB2Fu;
-    const unsigned long long P = idx >> 1;
-    unsigned x = (unsigned)P + (unsigned)(P >> 32) * 0xC2B2AE35u + key;
-    x ^= x >> 16; x *= 0x85EBCA6Bu;
-    x ^= x >> 13; x *= 0xC2B2AE35u;
-    x ^= x >> 16;
-    return ((idx & 1ull) ? x >> 16 : x & 0xffffu) >= d.thresh ? d.scale : 0.f;
-}
+#include "train_dev.h"      // gelu_f, gelu_d, drop_mul: the dropout hash the element-wise kernels of kernels_train.hip use - one definition
 
 // ------------------------------------------------------------------------------------------ row-normalisation backward
 // One wave per 128-wide row, two channels per lane; the row statistics are recomputed from the taped input v = x (+ res).
@@ -87,7 +70,7 @@ __global__ void __launch_bounds__(128) k_rdt_segsum(PackInfo pk, int K, const in
         for (int sl = 0; sl < K; ++sl)
             if (nbr[(size_t)p * K + sl] >= 0) {
                 const size_t o = ((size_t)p * K + sl) * RD_H + c;
-                s += rdt_gelu(pre[o]) * rdt_drop_mul(dr, site, o);
+                s += gelu_f(pre[o]) * drop_mul(dr, site, o);
             }
         out[(size_t)p * RD_H + c] = s * inv_scale;
     }
@@ -101,7 +84,7 @@ __global__ void __launch_bounds__(128) k_rdt_segsum_bwd(PackInfo pk, int K, cons
         const float g = ddh[(size_t)p * RD_H + c] * inv_scale;
         for (int sl = 0; sl < K; ++sl) {
             const size_t o = ((size_t)p * K + sl) * RD_H + c;
-            dpre[o] = nbr[(size_t)p * K + sl] >= 0 ? g * rdt_gelu_d(pre[o]) * rdt_drop_mul(dr, site, o) : 0.f;
+            dpre[o] = nbr[(size_t)p * K + sl] >= 0 ? g * gelu_d(pre[o]) * drop_mul(dr, site, o) : 0.f;
         }
     }
 }

@@ -1,4 +1,4 @@
-// Training path of librnampnn_hip.so (included at the end of api.cpp): taped f32 forward and the gradient of every
+// Training path of librnampnn_hip.so (the handle and the model structure come from api_internal.h): taped f32 forward and the gradient of every
 // parameter.  Reference surface: RNAMPNN.training_step (rnampnn.py:187-207) + Lightning's `loss.backward()`:
 //   rnampnn_train_forward  = `self(coords, mask)` in train mode: dropout p after every GELU and on the attention
 //                            probabilities (mpnn.py:140,150; feature.py:200; functional.py:69,109,124,184), masks from a
@@ -10,7 +10,10 @@
 // generic row kernels (kernels_train.hip); the tape lives in the caller's workspace between the two calls.
 // Gradients land in a flat f32 buffer laid out like the weight arena (rnampnn_weight_offset), ready for ONE RCCL
 // all-reduce.  Every cross-workgroup sum is an ordered two-stage reduction: gradients are bit-reproducible.
-#include "kernels_train.h"
+// Layout of this file: workspace and small entry points; the node-level helpers (one dispatch per GEMM: MFMA form when the shape is covered, f32
+// kernel otherwise); the edge side TWICE, once per precision (f32, bf16-mixed: edge embedding, per-edge MLPs, layer loops - each readable top to
+// bottom without a precision flag); the shared forward / backward skeletons that pick one of the two; the C entry points.
+#include "api_internal.h"
 
 // dropout sites (must match oracle/rnampnn_oracle.py: SITE_*)
 static inline unsigned site_ee(int i) { return 1u + i; }
@@ -136,6 +139,12 @@ extern "C" int rnampnn_weight_offset(rnampnn_handle h, int32_t i, int64_t* offse
 }
 
 namespace {
+// the weight-image cache bound to the calling thread for the length of one training call: train_begin binds, every return of the entry point unbinds
+struct WimgScope {
+    bool bound = false;
+    void bind(WImageCache* c) { t_wimg_bind(c); bound = true; }
+    ~WimgScope() { if (bound) t_wimg_bind(nullptr); }
+};
 struct Tr {                        // one training call
     rnampnn_ctx* c;
     PackInfo pk;
@@ -146,6 +155,7 @@ struct Tr {                        // one training call
     TDrop dr;
     bool bad = false;              // a bf16-storage GEMM variant that is not instantiated was requested (reported at the end of the pass)
     bool mixed;                    // bf16-mixed: GEMMs on MFMA with bf16 operands / f32 accumulate (kernels_train.hip, second half)
+    WimgScope wimg;
     bool att_mfma = false;         // the MFMA attention kernels (bf16-mixed unless RNAMPNN_F32_ATTN=1); decided ONCE per forward and kept on the tape
     TRows rn() const { return TRows{pk.cu + pk.B, 1, pk.Nmax}; }
     TRows re() const { return TRows{pk.cu + pk.B, k, pk.Nmax * k}; }
@@ -245,14 +255,13 @@ void ffn_bwd(Tr& t, const std::vector<Lin>& L, const float* X, int ldx, const st
 // with tapes outliving a call (leases, several outstanding forwards) an environment flip in between would otherwise recompute S from other
 // operands than the taped (m, l) statistics belong to
 static inline bool att_mfma_env(bool mixed) { return mixed && !ab_switch("RNAMPNN_F32_ATTN"); }
-static inline bool att_mfma(const Tr& t) { return t.att_mfma; }
 int bert_fwd(Tr& t, const Bert& b, BertTape& tp, float* x_in, float* out, unsigned site_att0, unsigned site_ffn0) {
     tp.x[0] = x_in;
     for (size_t j = 0; j < b.attn.size(); ++j) {
         const Attn& a = b.attn[j];
         lin_fwd(t, a.qkv, tp.x[j], RN_D, tp.qkv[j], 3 * RN_D);
         // bf16-mixed: the MFMA attention (forward and backward recompute S from the same bf16 operands); RNAMPNN_F32_ATTN=1 keeps the f32 kernels (A/B)
-        if (!(att_mfma(t) && te_attention_fwd(t.pk, tp.qkv[j], b.heads, tp.o[j], tp.st[j], t.dr, site_att0 + (unsigned)j, t.s) == 0))
+        if (!(t.att_mfma && te_attention_fwd(t.pk, tp.qkv[j], b.heads, tp.o[j], tp.st[j], t.dr, site_att0 + (unsigned)j, t.s) == 0))
             if (t_attention_fwd(t.pk, tp.qkv[j], b.heads, tp.o[j], tp.st[j], t.dr, site_att0 + (unsigned)j, t.s)) return 1;
         lin_fwd(t, a.out, tp.o[j], RN_D, tp.t[j], RN_D);
         t_add(t.rn(), tp.x[j], tp.t[j], RN_D, t.s);                                          // residual (functional.py:165)
@@ -272,7 +281,7 @@ int bert_bwd(Tr& t, const Bert& b, BertTape& tp, const float* dOut, float* dIn, 
         t_gn_bwd(t.pk, tp.t[j], dIn, rawp(t.c, a.gn_scale), t.c->cfg.padding_len, t.w.nscr, t.gw(a.gn_scale), t.gw(a.gn_shift), t.s);
         // out_proj backward: d o = d t . Wout
         lin_bwd(t, a.out, tp.o[j], RN_D, t.w.nscr, RN_D, t.w.dh2, RN_D);
-        if (!(att_mfma(t) && te_attention_bwd(t.pk, tp.qkv[j], tp.o[j], t.w.dh2, b.heads, t.w.dqkv, tp.st[j], t.dr, site_att0 + (unsigned)j, t.s) == 0))
+        if (!(t.att_mfma && te_attention_bwd(t.pk, tp.qkv[j], tp.o[j], t.w.dh2, b.heads, t.w.dqkv, tp.st[j], t.dr, site_att0 + (unsigned)j, t.s) == 0))
             if (t_attention_bwd(t.pk, tp.qkv[j], tp.o[j], t.w.dh2, b.heads, t.w.dqkv, tp.st[j], t.dr, site_att0 + (unsigned)j, t.s)) return 1;
         lin_bwd(t, a.qkv, tp.x[j], RN_D, t.w.dqkv, 3 * RN_D, dIn, RN_D);                     // d x[j] (through q,k,v)
         t_add(t.rn(), t.w.nscr, dIn, RN_D, t.s);                                              // + residual path
@@ -280,26 +289,17 @@ int bert_bwd(Tr& t, const Bert& b, BertTape& tp, const float* dOut, float* dIn, 
     return 0;
 }
 
+// ================================================================ edge side, f32: every [E][128] tensor of the tape and the scratch is f32; the
+// GEMMs are the plain FMA kernels on the K-major weight copies rnampnn_finalize_weights builds (parity grade)
 // one per-edge MLP on the tape:  pre1 = e.Wc + P[i] + Q[j] ; pre2 = gelu(pre1).W2^T + b2
 void mlp_edge_fwd(Tr& t, const Mlp2& m, const float* h, const float* e, float* pre1, float* pre2, unsigned site0) {
     rnampnn_ctx* c = t.c;
-    const float* w0 = rawp(c, m.w[0]);             // [128][384] = [Wa | Wb | Wc]
-    if (t.mixed) {                                 // P = h Wa^T + b1, Q = h Wb^T, pre1 = e Wc^T straight from the raw weight
-        tm_gemm_nt(t.rn(), h, RN_D, RN_D, w0, 3 * RN_D, rawp(c, m.b[0]), RN_D, t.w.pq, 256, 0, false, t.dr, 0u, t.s);
-        tm_gemm_nt(t.rn(), h, RN_D, RN_D, w0 + RN_D, 3 * RN_D, nullptr, RN_D, t.w.pq + RN_D, 256, 0, false, t.dr, 0u, t.s);
-        tm_gemm_nt(t.re(), e, RN_D, RN_D, w0 + 2 * RN_D, 3 * RN_D, nullptr, RN_D, pre1, RN_D, 0, false, t.dr, 0u, t.s);
-    } else {
-        t_gemm(t.rn(), h, RN_D, RN_D, derp<float>(c, m.pq_t), 256, derp<float>(c, m.pq_b), 256, t.w.pq, 256, 0, t.s);
-        t_gemm(t.re(), e, RN_D, RN_D, derp<float>(c, m.wc_t), RN_D, nullptr, RN_D, pre1, RN_D, 0, t.s);
-    }
+    t_gemm(t.rn(), h, RN_D, RN_D, derp<float>(c, m.pq_t), 256, derp<float>(c, m.pq_b), 256, t.w.pq, 256, 0, t.s);   // [P | Q] = h [Wa | Wb]^T + [b1 | 0]
+    t_gemm(t.re(), e, RN_D, RN_D, derp<float>(c, m.wc_t), RN_D, nullptr, RN_D, pre1, RN_D, 0, t.s);
     t_edge_add_pq(t.pk, t.k, t.w.nbr, t.w.pq, pre1, t.s);
     if (m.depth > 1) {
-        if (t.mixed) {   // a1 = drop(gelu(pre1)) is formed while the A fragments are loaded: never written to HBM
-            tm_gemm_nt(t.re(), pre1, RN_D, RN_D, rawp(c, m.w[1]), RN_D, rawp(c, m.b[1]), RN_D, pre2, RN_D, 0, true, t.dr, site0, t.s);
-        } else {
-            t_gelu_fwd(t.re(), pre1, t.w.E1, RN_D, t.dr, site0, t.s);
-            t_gemm(t.re(), t.w.E1, RN_D, RN_D, derp<float>(c, m.w2_t), RN_D, rawp(c, m.b[1]), RN_D, pre2, RN_D, 0, t.s);
-        }
+        t_gelu_fwd(t.re(), pre1, t.w.E1, RN_D, t.dr, site0, t.s);
+        t_gemm(t.re(), t.w.E1, RN_D, RN_D, derp<float>(c, m.w2_t), RN_D, rawp(c, m.b[1]), RN_D, pre2, RN_D, 0, t.s);
     }
 }
 // backward of one per-edge MLP.  On entry E2 holds d(pre_last) [E][128] (already multiplied by gelu' of the
@@ -307,12 +307,7 @@ void mlp_edge_fwd(Tr& t, const Mlp2& m, const float* h, const float* e, float* p
 void mlp_edge_bwd(Tr& t, const Mlp2& m, const float* h, const float* e, const float* pre1, float* dE, float* dh_acc, unsigned site0) {
     rnampnn_ctx* c = t.c;
     float* dpre1 = t.w.E2;
-    // mixed: E2 = d pre2.  dW2 += dpre2^T drop(gelu(pre1)) and db2 += colsum(dpre2) in one kernel (the activation is recomputed
-    // from the taped pre-activation while the tile is staged); d pre1 = (dpre2 . W2) * gelu'(pre1) * mask in the epilogue
-    if (m.depth > 1 && t.mixed && tm_gemm_tn(t.re(), t.w.E2, RN_D, RN_D, pre1, RN_D, RN_D, t.gw(m.w[1]), RN_D, true, t.dr, site0, t.gw(m.b[1]), t.s)) {
-        tm_gemm_nn(t.re(), t.w.E2, RN_D, RN_D, rawp(c, m.w[1]), RN_D, nullptr, RN_D, t.w.E1, RN_D, 0, pre1, RN_D, t.dr, site0, t.s);
-        dpre1 = t.w.E1;
-    } else if (m.depth > 1) {
+    if (m.depth > 1) {
         // E2 = d pre2 ; a1 = gelu(pre1) -> E1
         t_gelu_fwd(t.re(), pre1, t.w.E1, RN_D, t.dr, site0, t.s);
         mm_tn(t, t.re(), t.w.E2, RN_D, RN_D, t.w.E1, RN_D, RN_D, t.gw(m.w[1]), RN_D, t.gw(m.b[1]));  // dW2 += dpre2^T a1, db2
@@ -330,8 +325,79 @@ void mlp_edge_bwd(Tr& t, const Mlp2& m, const float* h, const float* e, const fl
     mm_nn(t, t.rn(), t.w.dpq, 256, RN_D, w0, 3 * RN_D, nullptr, RN_D, dh_acc, RN_D, 1);            // dh += dP . Wa
     mm_nn(t, t.rn(), t.w.dpq + RN_D, 256, RN_D, w0 + RN_D, 3 * RN_D, nullptr, RN_D, dh_acc, RN_D, 1);   // dh += dQ . Wb
 }
+// edge embedding (feature.py:540-571): raw features F [E][96] -> pe1 [-> pe2] -> e[0], absent slots zeroed
+void edge_embed_fwd_f32(Tr& t) {
+    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.s;
+    const int k = t.k;
+    t_edge_features(t.pk, k, w.geom, w.nbr, w.F, s);
+    const Lin& ee0 = c->edge_embed[0];
+    mm_nn(t, t.re(), w.F, RN_ERAWP, RN_ERAWP, derp<float>(c, ee0.wt), RN_D, rawp(c, ee0.b), RN_D, w.pe1, RN_D, 0);   // K-major copy: 90 -> 96 padded
+    if (c->cfg.depth_res_edge_feature > 1) {
+        const Lin& ee1 = c->edge_embed[1];
+        t_gelu_fwd(t.re(), w.pe1, w.E1, RN_D, t.dr, site_ee(0), s);
+        mm_nt(t, t.re(), w.E1, RN_D, RN_D, rawp(c, ee1.w), RN_D, derp<float>(c, ee1.wt), RN_D, rawp(c, ee1.b), RN_D, w.pe2, RN_D, 0);
+        t_gelu_fwd(t.re(), w.pe2, w.e[0], RN_D, t.dr, site_ee(1), s);
+    } else {
+        t_gelu_fwd(t.re(), w.pe1, w.e[0], RN_D, t.dr, site_ee(0), s);
+    }
+    t_edge_zero_invalid(t.pk, k, w.nbr, w.e[0], s);
+}
+// ResMPNN layers (mpnn.py:283-294)
+void layers_fwd_f32(Tr& t) {
+    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.s;
+    const int L = c->cfg.num_res_mpnn_layers, k = t.k;
+    for (int l = 0; l < L; ++l) {
+        const MpnnLayer& m = c->mpnn[l];
+        mlp_edge_fwd(t, m.msg, w.h[l], w.e[l], w.pm1[l], w.pm2[l], site_msg(l, 0));
+        t_seg_mean(t.pk, k, w.nbr, m.msg.depth > 1 ? w.pm2[l] : w.pm1[l], w.h[l], w.hpre[l], t.dr, site_msg(l, m.msg.depth - 1), s);
+        launch_graph_norm_packed(t.pk, w.hpre[l], nullptr, w.h[l + 1], rawp(c, m.gn_scale), rawp(c, m.gn_shift), t.t_norm, s);
+        if (l + 1 < L) {
+            mlp_edge_fwd(t, m.edge, w.h[l + 1], w.e[l], w.pu1[l], w.pu2[l], site_edge(l, 0));
+            t_edge_residual(t.pk, k, w.nbr, w.e[l], m.edge.depth > 1 ? w.pu2[l] : w.pu1[l], w.e[l + 1], t.dr, site_edge(l, m.edge.depth - 1), s);
+        }
+    }
+}
+// backward of layers l_hi .. l_lo (descending).  On entry dh = d h[l_hi + 1], dE = d e[l_hi + 1]; on return dh = d h[l_lo], dE = d e[l_lo]
+void layers_bwd_f32(Tr& t, int l_hi, int l_lo) {
+    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.s;
+    const int L = c->cfg.num_res_mpnn_layers, k = t.k;
+    const size_t N = (size_t)t.pk.Nmax;
+    for (int l = l_hi; l >= l_lo; --l) {
+        const MpnnLayer& m = c->mpnn[l];
+        if (l + 1 < L) {     // edge update of layer l: e[l+1] = e[l] + drop(gelu(pre_last)) (valid slots); inputs h[l+1], e[l]
+            const float* plast = m.edge.depth > 1 ? w.pu2[l] : w.pu1[l];
+            t_edge_res_bwd(t.pk, k, w.nbr, w.dE, plast, w.E2, t.dr, site_edge(l, m.edge.depth - 1), s);   // E2 = d pre_last ; dE stays = identity path into e[l]
+            mlp_edge_bwd(t, m.edge, w.h[l + 1], w.e[l], w.pu1[l], w.dE, w.dh, site_edge(l, 0));
+        }
+        // GraphNorm: dh = d h[l+1] -> dh2 = d hpre[l]
+        t_gn_bwd(t.pk, w.hpre[l], w.dh, rawp(c, m.gn_scale), t.t_norm, w.dh2, t.gw(m.gn_scale), t.gw(m.gn_shift), s);
+        // hpre = h[l] + agg: d h[l] starts as dh2; messages get d agg = dh2
+        const float* plast = m.msg.depth > 1 ? w.pm2[l] : w.pm1[l];
+        t_seg_mean_bwd(t.pk, k, w.nbr, w.dh2, plast, w.E2, t.dr, site_msg(l, m.msg.depth - 1), s);        // E2 = d pre_last of the message MLP
+        launch_copy_bytes(w.dh, w.dh2, N * RN_D * sizeof(float), s);
+        mlp_edge_bwd(t, m.msg, w.h[l], w.e[l], w.pm1[l], w.dE, w.dh, site_msg(l, 0));
+    }
+}
+// ResFeature, edge side: dE = d e[0] (masked output of the embedding MLP)
+void edge_embed_bwd_f32(Tr& t) {
+    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.s;
+    const Lin& ee0 = c->edge_embed[0];
+    t_edge_zero_invalid(t.pk, t.k, w.nbr, w.dE, s);
+    if (c->cfg.depth_res_edge_feature > 1) {
+        const Lin& ee1 = c->edge_embed[1];
+        t_gelu_bwd(t.re(), w.dE, w.pe2, w.E2, RN_D, t.dr, site_ee(1), s);                      // d pe2
+        t_gelu_fwd(t.re(), w.pe1, w.E1, RN_D, t.dr, site_ee(0), s);
+        mm_tn(t, t.re(), w.E2, RN_D, RN_D, w.E1, RN_D, RN_D, t.gw(ee1.w), RN_D, t.gw(ee1.b));
+        mm_nn(t, t.re(), w.E2, RN_D, RN_D, rawp(c, ee1.w), RN_D, nullptr, RN_D, w.E1, RN_D, 0);
+        t_gelu_bwd(t.re(), w.E1, w.pe1, w.E1, RN_D, t.dr, site_ee(0), s);                      // d pe1
+    } else {
+        t_gelu_bwd(t.re(), w.dE, w.pe1, w.E1, RN_D, t.dr, site_ee(0), s);
+    }
+    mm_tn(t, t.re(), w.E1, RN_D, RN_D, w.F, RN_ERAWP, RN_ERAW, t.gw(ee0.w), RN_ERAW, t.gw(ee0.b));
+}
 
-// ---- bf16-mixed versions: every [E][128] tensor is bf16 in HBM (kernels_train.h, last part); P + Q and the edge update's residual
+// ================================================================ edge side, bf16-mixed: every [E][128] tensor is bf16 in HBM - the layout of every
+// w.F / w.pe / w.e / w.pm / w.pu tensor and of E1, E2, dE in this mode (kernels_train.h, last part); P + Q and the edge update's residual
 // ride in the GEMM epilogues, so a forward MLP is two passes: (read e, write pre1) and (read pre1, write pre2 [, read e, write e_out]).
 inline tb16* eb(float* p) { return reinterpret_cast<tb16*>(p); }
 inline const tb16* eb(const float* p) { return reinterpret_cast<const tb16*>(p); }
@@ -379,6 +445,88 @@ void mlp_edge_bwd1_pair(Tr& t, const Mlp2& me, const Mlp2& mm, const tb16* e, co
     te_gemm_bwd1x2(t.re(), dpre1_e, dpre1_m, e, dE, rawp(c, me.w[0]) + 2 * RN_D, rawp(c, mm.w[0]) + 2 * RN_D, 3 * RN_D,
                    t.gw(me.w[0]) + 2 * RN_D, t.gw(mm.w[0]) + 2 * RN_D, 3 * RN_D, t.s);
 }
+// edge embedding (feature.py:540-571), bf16 chain: raw features [E][128] (90 live columns) -> pe1 -> pe2 -> e[0], the activations fused into the
+// GEMM operand loads
+void edge_embed_fwd_mixed(Tr& t) {
+    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.s;
+    const int k = t.k;
+    const Lin& ee0 = c->edge_embed[0];
+    te_edge_features(t.pk, k, w.geom, w.nbr, eb(w.F), s);
+    t.bad |= !te_gemm(t.re(), w.F, true, RN_D, rawp(c, ee0.w), RN_ERAW, true, rawp(c, ee0.b), eb(w.pe1), false, nullptr, nullptr, t.dr, 0u, s, RN_ERAW);
+    if (c->cfg.depth_res_edge_feature > 1) {
+        const Lin& ee1 = c->edge_embed[1];
+        t.bad |= !te_gemm(t.re(), w.pe1, true, RN_D, rawp(c, ee1.w), RN_D, true, rawp(c, ee1.b), eb(w.pe2), true, nullptr, nullptr, t.dr, site_ee(0), s);
+        te_edge_act(t.pk, k, w.nbr, eb(w.pe2), eb(w.e[0]), t.dr, site_ee(1), s);
+    } else {
+        te_edge_act(t.pk, k, w.nbr, eb(w.pe1), eb(w.e[0]), t.dr, site_ee(0), s);
+    }
+}
+// ResMPNN layers (mpnn.py:283-294)
+void layers_fwd_mixed(Tr& t) {
+    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.s;
+    const int L = c->cfg.num_res_mpnn_layers, k = t.k;
+    for (int l = 0; l < L; ++l) {
+        const MpnnLayer& m = c->mpnn[l];
+        mlp_edge_fwd_mixed(t, m.msg, w.h[l], eb(w.e[l]), eb(w.pm1[l]), eb(w.pm2[l]), site_msg(l, 0), nullptr, 0u);
+        te_seg_mean(t.pk, k, w.nbr, eb(m.msg.depth > 1 ? w.pm2[l] : w.pm1[l]), w.h[l], w.hpre[l], t.dr, site_msg(l, m.msg.depth - 1), s,
+                    m.msg.depth > 1 ? eb(w.pm2[l]) : nullptr);
+        launch_graph_norm_packed(t.pk, w.hpre[l], nullptr, w.h[l + 1], rawp(c, m.gn_scale), rawp(c, m.gn_shift), t.t_norm, s);
+        if (l + 1 < L)
+            mlp_edge_fwd_mixed(t, m.edge, w.h[l + 1], eb(w.e[l]), eb(w.pu1[l]), eb(w.pu2[l]), site_edge(l, 0), eb(w.e[l + 1]),
+                               site_edge(l, m.edge.depth - 1));
+    }
+}
+// backward of layers l_hi .. l_lo (descending).  On entry dh = d h[l_hi + 1], dE (bf16) = d e[l_hi + 1]; on return dh = d h[l_lo], dE = d e[l_lo]
+void layers_bwd_mixed(Tr& t, int l_hi, int l_lo) {
+    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.s;
+    const int L = c->cfg.num_res_mpnn_layers, k = t.k;
+    const size_t N = (size_t)t.pk.Nmax;
+    for (int l = l_hi; l >= l_lo; --l) {
+        const MpnnLayer& m = c->mpnn[l];
+        const bool nopair = ab_switch("RNAMPNN_NO_BWD1_PAIR");
+        // both MLPs of the layer read e[l] and add into dE: their e-side passes (dWc, dE) run as ONE kernel after the message MLP's (the two
+        // d pre1 tensors live in the two bf16 halves of E1, which is carved for f32)
+        const bool pair = l + 1 < L && m.edge.depth > 1 && m.msg.depth > 1 && !nopair;
+        tb16* dp1_e = pair ? eb(w.E1) : nullptr;
+        tb16* dp1_m = pair ? eb(w.E1) + N * k * RN_D : nullptr;
+        if (l + 1 < L) {
+            if (m.edge.depth > 1) {     // the residual backward rides in the fused kernel's staging pass
+                EBwd2Src from{1, eb(w.pu2[l]), w.nbr, nullptr, nullptr, k};
+                mlp_edge_bwd_mixed(t, m.edge, w.h[l + 1], eb(w.e[l]), eb(w.pu1[l]), eb(w.dE), w.dh, &from, eb(w.dE), dp1_e);
+            } else {
+                te_edge_res_bwd(t.pk, k, w.nbr, eb(w.dE), eb(w.pu1[l]), eb(w.E2), t.dr, site_edge(l, 0), s);
+                mlp_edge_bwd_mixed(t, m.edge, w.h[l + 1], eb(w.e[l]), eb(w.pu1[l]), eb(w.dE), w.dh);
+            }
+        }
+        t_gn_bwd(t.pk, w.hpre[l], w.dh, rawp(c, m.gn_scale), t.t_norm, w.dh2, t.gw(m.gn_scale), t.gw(m.gn_shift), s);
+        if (m.msg.depth > 1) {          // ... and so does the backward of the message mean (dagg = dh2)
+            launch_copy_bytes(w.dh, w.dh2, N * RN_D * sizeof(float), s);
+            EBwd2Src from{2, eb(w.pm2[l]), w.nbr, w.dh2, w.invc, k};
+            mlp_edge_bwd_mixed(t, m.msg, w.h[l], eb(w.e[l]), eb(w.pm1[l]), eb(w.dE), w.dh, &from, nullptr, dp1_m);
+            if (pair) mlp_edge_bwd1_pair(t, m.edge, m.msg, eb(w.e[l]), dp1_e, dp1_m, eb(w.dE));
+        } else {
+            te_seg_mean_bwd(t.pk, k, w.nbr, w.dh2, eb(w.pm1[l]), eb(w.E2), t.dr, site_msg(l, 0), s);
+            launch_copy_bytes(w.dh, w.dh2, N * RN_D * sizeof(float), s);
+            mlp_edge_bwd_mixed(t, m.msg, w.h[l], eb(w.e[l]), eb(w.pm1[l]), eb(w.dE), w.dh);
+        }
+    }
+}
+// ResFeature, edge side: dE (bf16) = d e[0]
+void edge_embed_bwd_mixed(Tr& t) {
+    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.s;
+    const int k = t.k;
+    const Lin& ee0 = c->edge_embed[0];
+    tb16* dpe1 = eb(w.E1);
+    if (c->cfg.depth_res_edge_feature > 1) {
+        const Lin& ee1 = c->edge_embed[1];
+        te_edge_res_bwd(t.pk, k, w.nbr, eb(w.dE), eb(w.pe2), eb(w.E2), t.dr, site_ee(1), s);                              // d pe2 (absent edges: 0)
+        te_gemm_tn(t.re(), eb(w.E2), eb(w.pe1), t.gw(ee1.w), RN_D, true, t.dr, site_ee(0), t.gw(ee1.b), s);
+        t.bad |= !te_gemm(t.re(), w.E2, true, RN_D, rawp(c, ee1.w), RN_D, false, nullptr, dpe1, false, eb(w.pe1), nullptr, t.dr, site_ee(0), s);   // d pe1
+    } else {
+        te_edge_res_bwd(t.pk, k, w.nbr, eb(w.dE), eb(w.pe1), dpe1, t.dr, site_ee(0), s);
+    }
+    te_gemm_tn(t.re(), dpe1, eb(w.F), t.gw(ee0.w), RN_ERAW, false, t.dr, 0u, t.gw(ee0.b), s, RN_ERAW);
+}
 }  // namespace
 
 // shared argument checks + workspace carve of the three training entry points
@@ -400,7 +548,7 @@ static int train_begin(Tr& t, rnampnn_handle h, int B, int T, void* ws, size_t w
     if (((uintptr_t)ws & 255) != 0) return fail(RNAMPNN_ERR_BAD_ARG, "workspace must be 256-byte aligned");
     t.c = h; t.s = (hipStream_t)stream; t.g = nullptr; t.k = h->cfg.num_res_neighbours; t.mixed = mixed;
     if (mixed && !h->wimg) h->wimg = t_wimg_create(1024);      // (null on allocation failure: the kernels then build their images themselves)
-    t_wimg_bind(mixed ? h->wimg : nullptr);
+    t.wimg.bind(mixed ? h->wimg : nullptr);
     carve_train(h, B, T, (char*)ws, &t.w);
     t.pk.len = t.w.len; t.pk.cu = t.w.cu; t.pk.node_b = t.w.node_b; t.pk.B = B; t.pk.T = T; t.pk.Nmax = B * T; t.pk.packed_in = 0;
     return RNAMPNN_OK;
@@ -408,10 +556,9 @@ static int train_begin(Tr& t, rnampnn_handle h, int B, int T, void* ws, size_t w
 
 static int train_forward_impl(Tr& t, const float* coords, const float* mask, float* logits) {
     rnampnn_ctx* c = t.c;
-    const RnaMpnnConfig& g = c->cfg;
     TW& w = t.w;
     hipStream_t s = t.s;
-    const int L = g.num_res_mpnn_layers, k = t.k;
+    const int L = c->cfg.num_res_mpnn_layers, k = t.k;
     const size_t N = (size_t)t.pk.Nmax;
     launch_zero_bytes(w.pq + N * 256, 256 * sizeof(float), s);
     if (t.mixed) launch_zero_bytes(eb(w.pq) + (2 * N + 1) * RN_D, RN_D * sizeof(tb16), s);      // row N of the bf16 Q table
@@ -425,57 +572,14 @@ static int train_forward_impl(Tr& t, const float* coords, const float* mask, flo
     if (launch_knn(coords, t.pk, t.t_norm, k, w.nbr, nullptr, s)) return fail(RNAMPNN_ERR_UNSUPPORTED, "max_len too long for k-NN");
     t_build_reverse(t.pk, k, w.nbr, w.rdeg, w.rstart, w.rfill, w.rlist, reinterpret_cast<int*>(w.E1), s);
     if (t.mixed) te_inv_count(t.pk, k, w.nbr, w.invc, s);
-    // edge embedding (feature.py:540-571)
-    if (t.mixed) {     // bf16 chain: raw features [E][128] (90 live columns) -> pe1 -> pe2 -> e[0], the activations fused into the GEMM operand loads
-        const Lin& ee0 = c->edge_embed[0];
-        te_edge_features(t.pk, k, w.geom, w.nbr, eb(w.F), s);
-        t.bad |= !te_gemm(t.re(), w.F, true, RN_D, rawp(c, ee0.w), RN_ERAW, true, rawp(c, ee0.b), eb(w.pe1), false, nullptr, nullptr, t.dr, 0u, s, RN_ERAW);
-        if (g.depth_res_edge_feature > 1) {
-            const Lin& ee1 = c->edge_embed[1];
-            t.bad |= !te_gemm(t.re(), w.pe1, true, RN_D, rawp(c, ee1.w), RN_D, true, rawp(c, ee1.b), eb(w.pe2), true, nullptr, nullptr, t.dr, site_ee(0), s);
-            te_edge_act(t.pk, k, w.nbr, eb(w.pe2), eb(w.e[0]), t.dr, site_ee(1), s);
-        } else {
-            te_edge_act(t.pk, k, w.nbr, eb(w.pe1), eb(w.e[0]), t.dr, site_ee(0), s);
-        }
-    } else {
-    t_edge_features(t.pk, k, w.geom, w.nbr, w.F, s);
-    const Lin& ee0 = c->edge_embed[0];
-    mm_nn(t, t.re(), w.F, RN_ERAWP, RN_ERAWP, derp<float>(c, ee0.wt), RN_D, rawp(c, ee0.b), RN_D, w.pe1, RN_D, 0);   // K-major copy: 90 -> 96 padded
-    if (g.depth_res_edge_feature > 1) {
-        const Lin& ee1 = c->edge_embed[1];
-        t_gelu_fwd(t.re(), w.pe1, w.E1, RN_D, t.dr, site_ee(0), s);
-        mm_nt(t, t.re(), w.E1, RN_D, RN_D, rawp(c, ee1.w), RN_D, derp<float>(c, ee1.wt), RN_D, rawp(c, ee1.b), RN_D, w.pe2, RN_D, 0);
-        t_gelu_fwd(t.re(), w.pe2, w.e[0], RN_D, t.dr, site_ee(1), s);
-    } else {
-        t_gelu_fwd(t.re(), w.pe1, w.e[0], RN_D, t.dr, site_ee(0), s);
-    }
-    t_edge_zero_invalid(t.pk, k, w.nbr, w.e[0], s);
-    }
+    // edge embedding: the launch sequence of the call's precision
+    if (t.mixed) edge_embed_fwd_mixed(t); else edge_embed_fwd_f32(t);
     // node embedding (feature.py:531-538, 591)
     lin_fwd(t, c->raw_project, w.raw_p, RN_RAWP, w.x0, RN_D);
     if (bert_fwd(t, c->emb, w.emb, w.x0, w.n1, site_emb_att(0), site_emb_ffn(0))) return fail(RNAMPNN_ERR_UNSUPPORTED, "head dim unsupported");
     launch_graph_norm_packed(t.pk, w.n1, nullptr, w.h[0], rawp(c, c->feat_gn_scale), rawp(c, c->feat_gn_shift), t.t_norm, s);
-    // ResMPNN layers (mpnn.py:283-294)
-    for (int l = 0; l < L; ++l) {
-        const MpnnLayer& m = c->mpnn[l];
-        if (t.mixed) {      // bf16 tape (the layout of every w.e / w.pm / w.pu tensor in this mode)
-            mlp_edge_fwd_mixed(t, m.msg, w.h[l], eb(w.e[l]), eb(w.pm1[l]), eb(w.pm2[l]), site_msg(l, 0), nullptr, 0u);
-            te_seg_mean(t.pk, k, w.nbr, eb(m.msg.depth > 1 ? w.pm2[l] : w.pm1[l]), w.h[l], w.hpre[l], t.dr, site_msg(l, m.msg.depth - 1), s,
-                        m.msg.depth > 1 ? eb(w.pm2[l]) : nullptr);
-            launch_graph_norm_packed(t.pk, w.hpre[l], nullptr, w.h[l + 1], rawp(c, m.gn_scale), rawp(c, m.gn_shift), t.t_norm, s);
-            if (l + 1 < L)
-                mlp_edge_fwd_mixed(t, m.edge, w.h[l + 1], eb(w.e[l]), eb(w.pu1[l]), eb(w.pu2[l]), site_edge(l, 0), eb(w.e[l + 1]),
-                                   site_edge(l, m.edge.depth - 1));
-            continue;
-        }
-        mlp_edge_fwd(t, m.msg, w.h[l], w.e[l], w.pm1[l], w.pm2[l], site_msg(l, 0));
-        t_seg_mean(t.pk, k, w.nbr, m.msg.depth > 1 ? w.pm2[l] : w.pm1[l], w.h[l], w.hpre[l], t.dr, site_msg(l, m.msg.depth - 1), s);
-        launch_graph_norm_packed(t.pk, w.hpre[l], nullptr, w.h[l + 1], rawp(c, m.gn_scale), rawp(c, m.gn_shift), t.t_norm, s);
-        if (l + 1 < L) {
-            mlp_edge_fwd(t, m.edge, w.h[l + 1], w.e[l], w.pu1[l], w.pu2[l], site_edge(l, 0));
-            t_edge_residual(t.pk, k, w.nbr, w.e[l], m.edge.depth > 1 ? w.pu2[l] : w.pu1[l], w.e[l + 1], t.dr, site_edge(l, m.edge.depth - 1), s);
-        }
-    }
+    // ResMPNN layers
+    if (t.mixed) layers_fwd_mixed(t); else layers_fwd_f32(t);
     // post fusion, raw embedding, readout (rnampnn.py:179-181)
     if (bert_fwd(t, c->post, w.post, w.h[L], w.hp, site_post_att(0), site_post_ffn(0))) return fail(RNAMPNN_ERR_UNSUPPORTED, "head dim unsupported");
     ffn_fwd(t, c->raw_ffn, w.raw_p, RN_RAWP, w.raw_pre, w.r1, site_raw(0));
@@ -508,10 +612,9 @@ static int train_forward_impl(Tr& t, const float* coords, const float* mask, flo
 // backward from w.dlogits (packed rows) into t.g; `accumulate` = 0 overwrites the gradient buffer
 static int train_backward_impl(Tr& t, int accumulate) {
     rnampnn_ctx* c = t.c;
-    const RnaMpnnConfig& g = c->cfg;
     TW& w = t.w;
     hipStream_t s = t.s;
-    const int L = g.num_res_mpnn_layers, k = t.k;
+    const int L = c->cfg.num_res_mpnn_layers, k = t.k;
     const size_t N = (size_t)t.pk.Nmax;
     if (!accumulate) launch_zero_bytes(t.g, c->raw_floats * sizeof(float), s);
     // one reduction queue per backward, closed on every return (the normal one reports what it refused: red_end below)
@@ -544,84 +647,18 @@ static int train_backward_impl(Tr& t, int accumulate) {
     if (c->grad_ev[0]) HIP_TRY(hipEventRecord(c->grad_ev[0], s));
     // ResMPNN layers, reverse.  dE = d e[l+1] (zero for the last layer: its edge update is dead)
     launch_zero_bytes(w.dE, N * k * RN_D * (t.mixed ? sizeof(tb16) : sizeof(float)), s);
-    for (int l = L - 1; l >= 0; --l) {
-        const MpnnLayer& m = c->mpnn[l];
-        if (l == L / 2 - 1) { red_flush(); if (c->grad_ev[1]) HIP_TRY(hipEventRecord(c->grad_ev[1], s)); }    // chunk 1 (layers L/2 .. L-1) is final
-        if (t.mixed) {
-            const bool nopair = ab_switch("RNAMPNN_NO_BWD1_PAIR");
-            // both MLPs of the layer read e[l] and add into dE: their e-side passes (dWc, dE) run as ONE kernel after the message MLP's (the two
-            // d pre1 tensors live in the two bf16 halves of E1, which is carved for f32)
-            const bool pair = l + 1 < L && m.edge.depth > 1 && m.msg.depth > 1 && !nopair;
-            tb16* dp1_e = pair ? eb(w.E1) : nullptr;
-            tb16* dp1_m = pair ? eb(w.E1) + N * k * RN_D : nullptr;
-            if (l + 1 < L) {
-                if (m.edge.depth > 1) {     // the residual backward rides in the fused kernel's staging pass
-                    EBwd2Src from{1, eb(w.pu2[l]), w.nbr, nullptr, nullptr, k};
-                    mlp_edge_bwd_mixed(t, m.edge, w.h[l + 1], eb(w.e[l]), eb(w.pu1[l]), eb(w.dE), w.dh, &from, eb(w.dE), dp1_e);
-                } else {
-                    te_edge_res_bwd(t.pk, k, w.nbr, eb(w.dE), eb(w.pu1[l]), eb(w.E2), t.dr, site_edge(l, 0), s);
-                    mlp_edge_bwd_mixed(t, m.edge, w.h[l + 1], eb(w.e[l]), eb(w.pu1[l]), eb(w.dE), w.dh);
-                }
-            }
-            t_gn_bwd(t.pk, w.hpre[l], w.dh, rawp(c, m.gn_scale), t.t_norm, w.dh2, t.gw(m.gn_scale), t.gw(m.gn_shift), s);
-            if (m.msg.depth > 1) {          // ... and so does the backward of the message mean (dagg = dh2)
-                launch_copy_bytes(w.dh, w.dh2, N * RN_D * sizeof(float), s);
-                EBwd2Src from{2, eb(w.pm2[l]), w.nbr, w.dh2, w.invc, k};
-                mlp_edge_bwd_mixed(t, m.msg, w.h[l], eb(w.e[l]), eb(w.pm1[l]), eb(w.dE), w.dh, &from, nullptr, dp1_m);
-                if (pair) mlp_edge_bwd1_pair(t, m.edge, m.msg, eb(w.e[l]), dp1_e, dp1_m, eb(w.dE));
-            } else {
-                te_seg_mean_bwd(t.pk, k, w.nbr, w.dh2, eb(w.pm1[l]), eb(w.E2), t.dr, site_msg(l, 0), s);
-                launch_copy_bytes(w.dh, w.dh2, N * RN_D * sizeof(float), s);
-                mlp_edge_bwd_mixed(t, m.msg, w.h[l], eb(w.e[l]), eb(w.pm1[l]), eb(w.dE), w.dh);
-            }
-            continue;
-        }
-        if (l + 1 < L) {     // edge update of layer l: e[l+1] = e[l] + drop(gelu(pre_last)) (valid slots); inputs h[l+1], e[l]
-            const float* plast = m.edge.depth > 1 ? w.pu2[l] : w.pu1[l];
-            t_edge_res_bwd(t.pk, k, w.nbr, w.dE, plast, w.E2, t.dr, site_edge(l, m.edge.depth - 1), s);   // E2 = d pre_last ; dE stays = identity path into e[l]
-            mlp_edge_bwd(t, m.edge, w.h[l + 1], w.e[l], w.pu1[l], w.dE, w.dh, site_edge(l, 0));
-        }
-        // GraphNorm: dh = d h[l+1] -> dh2 = d hpre[l]
-        t_gn_bwd(t.pk, w.hpre[l], w.dh, rawp(c, m.gn_scale), t.t_norm, w.dh2, t.gw(m.gn_scale), t.gw(m.gn_shift), s);
-        // hpre = h[l] + agg: d h[l] starts as dh2; messages get d agg = dh2
-        const float* plast = m.msg.depth > 1 ? w.pm2[l] : w.pm1[l];
-        t_seg_mean_bwd(t.pk, k, w.nbr, w.dh2, plast, w.E2, t.dr, site_msg(l, m.msg.depth - 1), s);        // E2 = d pre_last of the message MLP
-        launch_copy_bytes(w.dh, w.dh2, N * RN_D * sizeof(float), s);
-        mlp_edge_bwd(t, m.msg, w.h[l], w.e[l], w.pm1[l], w.dE, w.dh, site_msg(l, 0));
-    }
-    if (L / 2 == 0) { red_flush(); if (c->grad_ev[1]) HIP_TRY(hipEventRecord(c->grad_ev[1], s)); }              // (L == 1: chunk 1 = the one layer)
+    const auto layers_bwd = t.mixed ? layers_bwd_mixed : layers_bwd_f32;
+    layers_bwd(t, L - 1, L / 2);
+    // chunk 1 (layers L/2 .. L-1; L == 1: the one layer) is final
+    red_flush();
+    if (c->grad_ev[1]) HIP_TRY(hipEventRecord(c->grad_ev[1], s));
+    layers_bwd(t, L / 2 - 1, 0);
     // ResFeature: node side  dh = d h[0]
     t_gn_bwd(t.pk, w.n1, w.dh, rawp(c, c->feat_gn_scale), t.t_norm, w.dh2, t.gw(c->feat_gn_scale), t.gw(c->feat_gn_shift), s);
     if (bert_bwd(t, c->emb, w.emb, w.dh2, w.dh, site_emb_att(0), site_emb_ffn(0))) return fail(RNAMPNN_ERR_UNSUPPORTED, "head dim unsupported");
     lin_bwd(t, c->raw_project, w.raw_p, RN_RAWP, w.dh, RN_D, nullptr, 0);
-    // ResFeature: edge side  dE = d e[0] (masked output of the embedding MLP)
-    if (t.mixed) {
-        const Lin& ee0 = c->edge_embed[0];
-        tb16* dpe1 = eb(w.E1);
-        if (g.depth_res_edge_feature > 1) {
-            const Lin& ee1 = c->edge_embed[1];
-            te_edge_res_bwd(t.pk, k, w.nbr, eb(w.dE), eb(w.pe2), eb(w.E2), t.dr, site_ee(1), s);                              // d pe2 (absent edges: 0)
-            te_gemm_tn(t.re(), eb(w.E2), eb(w.pe1), t.gw(ee1.w), RN_D, true, t.dr, site_ee(0), t.gw(ee1.b), s);
-            t.bad |= !te_gemm(t.re(), w.E2, true, RN_D, rawp(c, ee1.w), RN_D, false, nullptr, dpe1, false, eb(w.pe1), nullptr, t.dr, site_ee(0), s);   // d pe1
-        } else {
-            te_edge_res_bwd(t.pk, k, w.nbr, eb(w.dE), eb(w.pe1), dpe1, t.dr, site_ee(0), s);
-        }
-        te_gemm_tn(t.re(), dpe1, eb(w.F), t.gw(ee0.w), RN_ERAW, false, t.dr, 0u, t.gw(ee0.b), s, RN_ERAW);
-    } else {
-        const Lin& ee0 = c->edge_embed[0];
-        t_edge_zero_invalid(t.pk, k, w.nbr, w.dE, s);
-        if (g.depth_res_edge_feature > 1) {
-            const Lin& ee1 = c->edge_embed[1];
-            t_gelu_bwd(t.re(), w.dE, w.pe2, w.E2, RN_D, t.dr, site_ee(1), s);                      // d pe2
-            t_gelu_fwd(t.re(), w.pe1, w.E1, RN_D, t.dr, site_ee(0), s);
-            mm_tn(t, t.re(), w.E2, RN_D, RN_D, w.E1, RN_D, RN_D, t.gw(ee1.w), RN_D, t.gw(ee1.b));
-            mm_nn(t, t.re(), w.E2, RN_D, RN_D, rawp(c, ee1.w), RN_D, nullptr, RN_D, w.E1, RN_D, 0);
-            t_gelu_bwd(t.re(), w.E1, w.pe1, w.E1, RN_D, t.dr, site_ee(0), s);                      // d pe1
-        } else {
-            t_gelu_bwd(t.re(), w.dE, w.pe1, w.E1, RN_D, t.dr, site_ee(0), s);
-        }
-        mm_tn(t, t.re(), w.E1, RN_D, RN_D, w.F, RN_ERAWP, RN_ERAW, t.gw(ee0.w), RN_ERAW, t.gw(ee0.b));
-    }
+    // ResFeature: edge side  dE = d e[0]
+    if (t.mixed) edge_embed_bwd_mixed(t); else edge_embed_bwd_f32(t);
     t.bad |= !red_end();
     HIP_TRY(hipGetLastError());
     if (t.bad) return fail(RNAMPNN_ERR_UNSUPPORTED, "training backward: a GEMM variant this configuration needs is not built, or the reduction "
@@ -651,12 +688,11 @@ extern "C" int rnampnn_train_forward(rnampnn_handle h, const float* coords, cons
     rc = train_begin(t, h, B, T, ws, ws_bytes, stream, (flags & RNAMPNN_TRAIN_BF16_MIXED) != 0);
     if (rc) return rc;
     t.t_norm = T_norm > 0 ? T_norm : T;
-    if (t.t_norm < T) { t_wimg_bind(nullptr); return fail(RNAMPNN_ERR_BAD_ARG, "T_norm %d < T %d", t.t_norm, T); }
+    if (t.t_norm < T) return fail(RNAMPNN_ERR_BAD_ARG, "T_norm %d < T %d", t.t_norm, T);
     t.dr = t_drop(dropout, seed, h->seed_dev);
     t.att_mfma = att_mfma_env(t.mixed);
     tape_drop_ws(h, ws);
     rc = train_forward_impl(t, coords, mask, logits);
-    t_wimg_bind(nullptr);
     if (rc) return rc;
     // a record dies when its workspace is reused (tape_drop_ws) or its backward... never: the cap only bounds a caller that keeps opening NEW
     // workspaces without ever running a backward (a record is 64 bytes; gradient accumulation over thousands of outstanding forwards stays valid)
@@ -686,9 +722,7 @@ extern "C" int rnampnn_train_backward(rnampnn_handle h, int64_t tape_id, const f
     t.att_mfma = tape.att_mfma;
     t.g = grad;
     t_pack_dlogits(t.pk, dlogits, t.w.dlogits, t.s);
-    rc = train_backward_impl(t, accumulate);
-    t_wimg_bind(nullptr);
-    return rc;
+    return train_backward_impl(t, accumulate);
 }
 
 extern "C" int rnampnn_loss_and_grad(rnampnn_handle h, const float* coords, const float* mask, const int32_t* labels,
@@ -702,17 +736,15 @@ extern "C" int rnampnn_loss_and_grad(rnampnn_handle h, const float* coords, cons
     rc = train_begin(t, h, B, T, ws, ws_bytes, stream, (flags & RNAMPNN_TRAIN_BF16_MIXED) != 0);
     if (rc) return rc;
     t.t_norm = T_norm > 0 ? T_norm : T;
-    if (t.t_norm < T) { t_wimg_bind(nullptr); return fail(RNAMPNN_ERR_BAD_ARG, "T_norm %d < T %d", t.t_norm, T); }
+    if (t.t_norm < T) return fail(RNAMPNN_ERR_BAD_ARG, "T_norm %d < T %d", t.t_norm, T);
     t.dr = t_drop(dropout, seed, h->seed_dev);
     t.att_mfma = att_mfma_env(t.mixed);
     t.g = grad;
     tape_drop_ws(h, ws);
     rc = train_forward_impl(t, coords, mask, logits);
-    if (rc) { t_wimg_bind(nullptr); return rc; }
+    if (rc) return rc;
     t_loss_grad(t.pk, t.w.logits_p, labels, t.w.dlogits, loss, t.w.sc.p, t.s);
-    rc = train_backward_impl(t, 0);
-    t_wimg_bind(nullptr);
-    return rc;
+    return train_backward_impl(t, 0);
 }
 
 // torch.optim.Adam(lr, betas, eps, weight_decay) step (rnampnn.py:156-159: lr 2e-3, weight_decay 2e-4, L2 form: the decay

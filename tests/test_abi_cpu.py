@@ -116,12 +116,12 @@ def test_training_path_issues_no_runtime_memset():
     set-up code and a test tap that are never captured."""
     import re
     csrc = os.path.join(REPO, "rna-mpnn_amd", "csrc")
-    for name in ("kernels_train.hip", "kernels_train.h"):
+    for name in ("kernels_train.hip", "kernels_train.h", "train_dev.h"):
         src = open(os.path.join(csrc, name)).read()
         assert "hipMemsetAsync" not in src and "hipMemset(" not in src, name
-    inc = open(os.path.join(csrc, "train.inc")).read()
+    inc = open(os.path.join(csrc, "train.cpp")).read()
     body = inc[:inc.index("rnampnn_edge_raw_features")] if "rnampnn_edge_raw_features" in inc else inc
-    assert "hipMemsetAsync" not in body, "train.inc: a runtime memset inside the (capturable) training entry points"
+    assert "hipMemsetAsync" not in body, "train.cpp: a runtime memset inside the (capturable) training entry points"
     assert len(re.findall(r"launch_zero_bytes\(", body)) >= 4
     # ... and the two helpers themselves launch kernels, never the runtime's memset / copy
     f32 = open(os.path.join(csrc, "kernels_f32.hip")).read()

@@ -253,7 +253,8 @@ def test_T_norm_training_shard_equals_the_padded_global_batch(precision):
     difference).  The forward's reductions run per RNA, so the logits are bit-identical.  Both runs are within the
     part-1 bounds of fp64 oracle autograd on the padded tensor.  Negative control: without T_norm the shard's gradient
     misses the padded run's by more than the f32 oracle bound in the median tensor.  The f32 run also goes once through
-    the autograd path (model(c, m, T_norm=40), double-softmax loss, .backward())."""
+    the autograd path (model(c, m, T_norm=40), double-softmax loss, .backward()).  A call with T_norm < T fails inside the
+    trainer: it raises with the library's message, and the next valid call repeats the first one bit for bit."""
     from rnampnn.model._schema import state_dict_shapes
     hp, (cs, ms, ys), (cp, mp, yp) = _shard_and_padded()
     model, sd = _model(hp, state_dict_shapes(hp), precision)
@@ -265,6 +266,12 @@ def test_T_norm_training_shard_equals_the_padded_global_batch(precision):
         return float(loss), logits.cpu(), grad_dict(model)
 
     lp, zp, gp = run(cp, mp, yp)
+    # an error raised inside the trainer (after its weight-image cache is bound) reaches the caller with the library's text and
+    # leaves nothing behind: the same valid call afterwards gives the same bits
+    with pytest.raises(ValueError, match="T_norm 27 < T 40"):
+        run(cp, mp, yp, T_norm=27)
+    lp2, zp2, gp2 = run(cp, mp, yp)
+    assert lp2 == lp and torch.equal(zp2, zp) and all(torch.equal(gp2[key], gp[key]) for key in gp)
     ls, zs, gs = run(cs, ms, ys, T_norm=40)
     lo, zo, go = run(cs, ms, ys)
     d_shard = _max_rel(gs, gp)
