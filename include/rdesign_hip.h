@@ -10,7 +10,8 @@
  * pytorch_lightning and seaborn - absent from this image - and no rdesign fixture or checkpoint ships with the reference.
  * The checker is the CPU restatement `oracle/rdesign_oracle.py` (numpy, citing the reference line by line) alone.
  *
- * Inference (rdesign_forward / rdesign_readout, f32 or bf16) and the exact-f32 training step (rdesign_loss_and_grad).
+ * Inference (rdesign_forward / rdesign_readout, f32 or bf16), the exact-f32 training step (rdesign_loss_and_grad) and the opt-in
+ * bf16-mixed training step (rdesign_loss_and_grad_ex with RDESIGN_TRAIN_BF16_MIXED).
  *
  * Conventions: as rnampnn_hip.h (device pointers, caller's stream, no synchronisation, 0 = success).
  *   X (B,T,6,3) f32 backbone atoms P, O5', C5', C4', C3', O3' (rdesign/utils/data.py:90-115, zero-filled padding),
@@ -98,6 +99,21 @@ size_t rdesign_train_workspace_bytes(rdesign_handle h, int32_t B, int32_t T);
 size_t rdesign_train_tape_bytes(rdesign_handle h, int32_t B, int32_t T);
 int rdesign_loss_and_grad(rdesign_handle h, const float* X, const float* mask, const int32_t* labels, int32_t B, int32_t T,
                           float dropout, uint64_t seed, float* loss, float* logits, float* grad, void* ws, size_t ws_bytes, void* stream);
+
+/* The training step with its arithmetic chosen per call.  flags = RDESIGN_TRAIN_F32: exactly the three entry points above (a
+ * RDESIGN_PREC_BF16 handle is refused).  flags = RDESIGN_TRAIN_BF16_MIXED: the same step - same dropout sites and addressing, same loss,
+ * same gradient layout, bit-reproducible - with every per-edge tensor stored as bf16 and the GEMMs on the MFMA kernels of the main model's
+ * bf16-mixed trainer (f32 accumulate; node-level tensors and every reduction stay f32; csrc/rdesign_train_bf16.hip states the tape).  It
+ * reads the nn.Linear-layout weights of the arena and accepts a handle of either precision; it is built for num_message_layers 2 and 3,
+ * any other depth gets RDESIGN_ERR_UNSUPPORTED (size queries: 0 and the error text), as does a configuration an MFMA edge kernel does not
+ * cover.  The row limits are those of rdesign_loss_and_grad.  Any other flags value: RDESIGN_ERR_BAD_ARG (size queries: 0). */
+#define RDESIGN_TRAIN_F32        0
+#define RDESIGN_TRAIN_BF16_MIXED 1
+size_t rdesign_train_workspace_bytes_ex(rdesign_handle h, int32_t B, int32_t T, int32_t flags);
+size_t rdesign_train_tape_bytes_ex(rdesign_handle h, int32_t B, int32_t T, int32_t flags);
+int rdesign_loss_and_grad_ex(rdesign_handle h, const float* X, const float* mask, const int32_t* labels, int32_t B, int32_t T,
+                             float dropout, uint64_t seed, int32_t flags, float* loss, float* logits, float* grad, void* ws,
+                             size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

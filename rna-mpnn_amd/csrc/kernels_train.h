@@ -106,6 +106,7 @@ void te_gemm_tn(const TRows& rows, const tb16* A, const tb16* B, float* dW, int 
 void te_gemm_pq(const TRows& rows, const float* h, const float* w0, const float* b1, tb16* Pt, tb16* Qt, hipStream_t s);
 void tm_gemm_tn_pq(const TRows& rows, const float* dpq, const float* h, float* gw0, float* db1, hipStream_t s);
 bool tm_gemm_nn_pq(const TRows& rows, const float* dpq, const float* w0, float* dh, hipStream_t s);
+#define TE_DROPPED (-1.0e4f)         // taped in place of a dropped pre-activation: gelu_fast, gelu_d_fast and gelu_both_fast give exactly (-)0 there
 // forward of a depth-2 per-edge MLP in one kernel (the hidden activation stays in registers; pre1 / pre2 written once as the tape;
 // pre1 = null: not kept).  pre1 is taped with its dropped elements replaced by TE_DROPPED; with f.res_out (edge update) pre2 receives
 // gelu'(pre2) * mask(site2) - the tapes te_gemm_bwd2 reads

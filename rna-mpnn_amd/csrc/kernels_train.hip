@@ -1836,7 +1836,6 @@ void te_gemm_pq(const TRows& rows, const float* h, const float* w0, const float*
 // operand of the first Linear is still in registers when the edge update needs it.  Against the two-kernel form this saves the read of pre1
 // and (edge update) the second read of e.  Both weight images live in LDS (64 KiB, two workgroups per CU).
 __device__ __forceinline__ void gelu_both_fast(float x, float& g, float& d);
-#define TE_DROPPED (-1.0e4f)         // taped in place of a dropped pre-activation: gelu_fast, gelu_d_fast and gelu_both_fast give exactly (-)0 there
 struct Emm2Args {
     TRows rows;
     const tb16* X;                   // e [R][128]

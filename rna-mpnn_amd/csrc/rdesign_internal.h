@@ -1,5 +1,5 @@
-// Declarations shared by the two translation units of the `rdesign` path: rdesign.hip (handle, features, inference forward) and
-// rdesign_train.hip (taped forward + backward of the f32 training step).
+// Declarations shared by the translation units of the `rdesign` path: rdesign.hip (handle, features, inference forward), rdesign_train.hip
+// (taped forward + backward of the f32 training step) and rdesign_train_bf16.hip (the bf16-mixed training step).
 #pragma once
 #include "../../include/rdesign_hip.h"
 #include "rnampnn_internal.h"
@@ -55,3 +55,10 @@ size_t rd_knn_lds_bytes(int T);
 // row normalisations on 128-wide rows: mode 0 functional.Normalize, mode 1 nn.LayerNorm(x + res)
 void rd_rownorm(const int* ntot, int mul, size_t maxrows, const float* x, const float* res, const float* gain, const float* bias, int mode,
                 float* y, hipStream_t s, tb16* yb = nullptr);
+
+// ---- shared by the two training steps (defined in rdesign_train.hip)
+#define RDT_CE_BLOCKS 1024
+int rdt_dm(const rdesign_ctx* c);                                  // widest node-level activation: max(128, dense width, hidden read-out width)
+int rdt_check_rows(rdesign_handle h, int32_t B, int32_t T);        // B, T > 0 and the row limits of the dropout hash / 32-bit edge indexing (h non-null)
+// loss = mean over the valid residues of the cross-entropy, dlogits = d loss / d logits (packed rows); part: RDT_CE_BLOCKS floats of scratch
+void rdt_ce_loss(const PackInfo& pk, const float* logits, const int32_t* labels, float* dlogits, float* part, float* loss, hipStream_t s);

@@ -92,7 +92,6 @@ __global__ void __launch_bounds__(128) k_rdt_segsum_bwd(PackInfo pk, int K, cons
 // ------------------------------------------------------------------------------------------ cross-entropy on packed rows
 // loss = mean over the valid residues of -log softmax(logits[p])[S[b][t]] (nn.CrossEntropyLoss(), rdesign.py:73,101) and d loss / d logits.  The label of
 // packed row p is read from the padded (B, T) tensor (packing on the fly); per-block partial losses, summed in block order by one thread.
-#define RDT_CE_BLOCKS 1024
 __global__ void __launch_bounds__(256) k_rdt_ce(PackInfo pk, const float* __restrict__ logits, const int32_t* __restrict__ labels,
                                                 float* __restrict__ dlogits, float* __restrict__ part) {
     __shared__ float red[4];
@@ -127,8 +126,27 @@ __global__ void k_rdt_loss_sum(const float* __restrict__ part, int n, float* __r
     for (int i = 0; i < n; ++i) s += part[i];
     *loss = s;
 }
+void rdt_ce_loss(const PackInfo& pk, const float* logits, const int32_t* labels, float* dlogits, float* part, float* loss, hipStream_t s) {
+    int grid = (pk.Nmax + 255) / 256;
+    if (grid > RDT_CE_BLOCKS) grid = RDT_CE_BLOCKS;
+    hipLaunchKernelGGL(k_rdt_ce, dim3(grid), dim3(256), 0, s, pk, logits, labels, dlogits, part);
+    hipLaunchKernelGGL(k_rdt_loss_sum, dim3(1), dim3(1), 0, s, part, grid, loss);
+}
 
 // ------------------------------------------------------------------------------------------ workspace
+int rdt_dm(const rdesign_ctx* c) {
+    int d = RD_H;
+    if (c->cfg.dim_dense_layers > d) d = c->cfg.dim_dense_layers;
+    if (c->cfg.num_readout_layers > 1 && c->cfg.readout_hidden_dim > d) d = c->cfg.readout_hidden_dim;
+    return d;
+}
+int rdt_check_rows(rdesign_handle h, int32_t B, int32_t T) {
+    if (B <= 0 || T <= 0) return rd_fail(RDESIGN_ERR_BAD_ARG, "training step: non-positive B/T");
+    // 32-bit element-pair indices of the dropout hash (kernels_train.h) and 32-bit edge-row indexing: rows * width / 2 < 2^32
+    if ((long long)B * T * h->cfg.k_neighbors >= (1LL << 26) || (long long)B * T * rdt_dm(h) >= (1LL << 32))
+        return rd_fail(RDESIGN_ERR_BAD_ARG, "row count out of range for the training path (B*T*k < 2^26); split the batch");
+    return RDESIGN_OK;
+}
 namespace {
 struct RdtLayer { std::vector<float*> msg, dense; float *dh, *h1, *y; };      // pre-activations of the message / hidden dense Linears, dh, norm1 output, dense output
 struct RdtWs {
@@ -144,12 +162,6 @@ struct RdtWs {
     TScratch sc;                             // arena of the ordered reductions
     size_t tape_bytes;
 };
-int rdt_dm(const rdesign_ctx* c) {
-    int d = RD_H;
-    if (c->cfg.dim_dense_layers > d) d = c->cfg.dim_dense_layers;
-    if (c->cfg.num_readout_layers > 1 && c->cfg.readout_hidden_dim > d) d = c->cfg.readout_hidden_dim;
-    return d;
-}
 size_t rdt_carve(const rdesign_ctx* c, int B, size_t Nmax, char* base, RdtWs* out) {
     RdtWs tmp;
     RdtWs& w = out ? *out : tmp;
@@ -185,11 +197,7 @@ int rdt_check(rdesign_handle h, int32_t B, int32_t T) {
     if (!h) return rd_fail(RDESIGN_ERR_BAD_ARG, "null handle");
     if (h->cfg.precision != RDESIGN_PREC_F32)
         return rd_fail(RDESIGN_ERR_UNSUPPORTED, "the rdesign training step is built for the exact-f32 path only (create the handle with RDESIGN_PREC_F32)");
-    if (B <= 0 || T <= 0) return rd_fail(RDESIGN_ERR_BAD_ARG, "training step: non-positive B/T");
-    // 32-bit element-pair indices of the dropout hash (kernels_train.h) and 32-bit edge-row indexing: rows * width / 2 < 2^32
-    if ((long long)B * T * h->cfg.k_neighbors >= (1LL << 26) || (long long)B * T * rdt_dm(h) >= (1LL << 32))
-        return rd_fail(RDESIGN_ERR_BAD_ARG, "row count out of range for the training path (B*T*k < 2^26); split the batch");
-    return RDESIGN_OK;
+    return rdt_check_rows(h, B, T);
 }
 }  // namespace
 
@@ -276,12 +284,7 @@ extern "C" int rdesign_loss_and_grad(rdesign_handle h, const float* X, const flo
     if (logits) launch_copy_bytes(logits, w.logits, Nmax * 4 * sizeof(float), s);
 
     // ================================================================ loss and backward
-    {
-        int grid = (int)((Nmax + 255) / 256);
-        if (grid > RDT_CE_BLOCKS) grid = RDT_CE_BLOCKS;
-        hipLaunchKernelGGL(k_rdt_ce, dim3(grid), dim3(256), 0, s, pk, w.logits, labels, w.dlogits, w.part);
-        hipLaunchKernelGGL(k_rdt_loss_sum, dim3(1), dim3(1), 0, s, w.part, grid, loss);
-    }
+    rdt_ce_loss(pk, w.logits, labels, w.dlogits, w.part, loss, s);
     launch_zero_bytes(grad, c->raw_floats * sizeof(float), s);
     auto G = [&](int i) { return grad + c->raw[i].off; };
     red_begin(w.sc, s);

@@ -7,6 +7,7 @@ import ctypes as C
 from rnampnn import _native as _rn
 
 PREC_F32, PREC_BF16 = 0, 1
+TRAIN_F32, TRAIN_BF16_MIXED = 0, 1
 ERR_BAD_ARG = 1
 _EXC = {1: ValueError, 2: NotImplementedError, 5: RuntimeError, 6: KeyError, 7: RuntimeError}
 
@@ -34,6 +35,9 @@ SYMBOLS = {
     "rdesign_train_workspace_bytes": (_SZ, [_VP, _I32, _I32]),
     "rdesign_train_tape_bytes": (_SZ, [_VP, _I32, _I32]),
     "rdesign_loss_and_grad": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, C.c_float, C.c_uint64, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "rdesign_train_workspace_bytes_ex": (_SZ, [_VP, _I32, _I32, _I32]),
+    "rdesign_train_tape_bytes_ex": (_SZ, [_VP, _I32, _I32, _I32]),
+    "rdesign_loss_and_grad_ex": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, C.c_float, C.c_uint64, _I32, _VP, _VP, _VP, _VP, _SZ, _VP]),
 }
 _bound = False
 

@@ -7,7 +7,9 @@ Inference surface (``forward``, ``readout``, ``validation_step`` / ``test_step``
 exact-f32 TRAINING STEP: ``loss_and_grad`` (``rdesign_loss_and_grad``: taped forward with dropout, cross-entropy, HIP backward into ONE
 flat gradient buffer), ``training_step`` (the same behind an autograd node) and ``configure_optimizers(fused=True)`` (the main model's
 ``FlatAdam`` on this model's flat buffers).  f32 is the reference arithmetic of this model (its trainer sets no ``precision``,
-``rdesign/utils/train.py:107-115``); a bf16-mixed training step is not built, nor a differentiable ``forward`` / ``readout`` pair.
+``rdesign/utils/train.py:107-115``) and the default of the step; ``train_precision="bf16"`` opts into the bf16-mixed step
+(``rdesign_loss_and_grad_ex``: bf16 per-edge tensors, MFMA GEMMs) on a model of either ``precision``.  A differentiable
+``forward`` / ``readout`` pair is not built.
 The XGBoost head of ``predict`` is out of scope like the main model's (xgboost is not installed: the reference's own
 ``NotFittedError`` branch, argmax of ``Readout``, is the one taken - ``rdesign.py:152-155``).  PARITY UNPINNED (``oracle/rdesign_oracle.py``).
 """
@@ -25,6 +27,7 @@ from .. import _native
 from rnampnn.model._base import _prep, _stream
 
 _PREC = {"f32": _native.PREC_F32, "bf16": _native.PREC_BF16}
+_TRAIN = {"f32": _native.TRAIN_F32, "bf16": _native.TRAIN_BF16_MIXED}
 
 
 class _Holder(nn.Module):
@@ -118,7 +121,7 @@ class RNAModel(nn.Module):
                  dim_dense_layers: int = 256, num_mpnn_layers: int = 9, readout_hidden_dim: int = 256,
                  num_readout_layers: int = 0, lr: float = 0.002, n_estimators: int = 100, xgb_max_depth: int = 6,
                  xgb_learning_rate: float = 0.1, xgb_subsample: float = 0.8, xgb_colsample_bytree: float = 0.8,
-                 precision: str = "bf16"):
+                 precision: str = "bf16", train_precision: Optional[str] = None):
         super().__init__()
         if node_feat_types not in (None, ["angle", "distance", "direction"]) or \
                 edge_feat_types not in (None, ["orientation", "distance", "direction"]):
@@ -128,6 +131,7 @@ class RNAModel(nn.Module):
         if precision not in _PREC:
             raise ValueError(f"precision must be one of {sorted(_PREC)}")
         self.name, self.version, self.precision = "RDesign-X", 0, precision
+        self.train_precision = "f32" if train_precision is None else train_precision      # not a hyper-parameter of the handle, not in the state dict
         self.hparams = dict(hidden_dim=hidden_dim, vocab_size=vocab_size, k_neighbors=k_neighbors, dropout=dropout,
                             num_message_layers=num_message_layers, num_dense_layers=num_dense_layers,
                             dim_dense_layers=dim_dense_layers, num_mpnn_layers=num_mpnn_layers,
@@ -157,12 +161,24 @@ class RNAModel(nn.Module):
 
     # ------------------------------------------------------------------ native state
     @property
+    def train_precision(self) -> str:
+        """Arithmetic of the training step: ``"f32"`` (exact f32, ``precision="f32"`` models only) or ``"bf16"`` (bf16-mixed, any model)."""
+        return self._train_precision
+
+    @train_precision.setter
+    def train_precision(self, value: str) -> None:
+        if value not in _TRAIN:
+            raise ValueError(f"train_precision must be one of {sorted(_TRAIN)}")
+        object.__setattr__(self, "_train_precision", value)
+
+    @property
     def device(self) -> torch.device:
         return next(self.parameters()).device
 
     def _ensure(self, for_mixed_training: bool = False) -> torch.device:
         """Parameters aliased to the flat arena, kernel-side weight copies current.  ``for_mixed_training`` is accepted for
-        ``FlatAdam`` (the main model skips its finalize with it); this model's only training path is f32 and always finalizes."""
+        ``FlatAdam`` (the main model skips its finalize with it); this model always finalizes: both training steps read the K-major
+        copies of the embedding Linears, and finalize is what tells a bf16 model's inference path to rebuild its weight images."""
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("the rdesign HIP path runs on an MI355X: move the module to 'cuda' first (there is no CPU fallback)")
@@ -306,16 +322,16 @@ class RNAModel(nn.Module):
         scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=40, gamma=0.8)
         return [optimizer], [scheduler]
 
-    # ------------------------------------------------------------------ training step (exact f32)
+    # ------------------------------------------------------------------ training step (exact f32, or bf16-mixed by train_precision)
     def _train_args(self, dropout, seed):
-        if self.precision != "f32":
-            raise NotImplementedError("the rdesign training step is built for precision='f32' only (the reference trains this model "
-                                      "in f32; a bf16-mixed step is not built)")
+        if self.train_precision == "f32" and self.precision != "f32":
+            raise NotImplementedError("the exact-f32 rdesign training step (train_precision='f32', the default) is built for precision='f32' "
+                                      "models only (the reference trains this model in f32); set train_precision='bf16' for the bf16-mixed step")
         p = float((self.hparams["dropout"] if self.training else 0.0) if dropout is None else dropout)
         return p, (self._next_seed() if seed is None else int(seed))
 
     def _step_native(self, X, S, mask, p: float, seed: int, grad: torch.Tensor, return_logits: bool = False):
-        """One ``rdesign_loss_and_grad`` call; the gradient of every parameter OVERWRITES ``grad`` (laid out like the weight arena)."""
+        """One ``rdesign_loss_and_grad_ex`` call in the arithmetic of ``train_precision``; the gradient of every parameter OVERWRITES ``grad`` (laid out like the weight arena)."""
         dev = self._ensure()
         if X.dim() != 4 or X.shape[2:] != (6, 3) or tuple(mask.shape) != tuple(X.shape[:2]) or tuple(S.shape) != tuple(mask.shape):
             raise ValueError(f"X must be (B, T, 6, 3), S and mask (B, T); got {tuple(X.shape)}, {tuple(S.shape)}, {tuple(mask.shape)}")
@@ -324,8 +340,13 @@ class RNAModel(nn.Module):
             raise ValueError("empty batch")
         Xd, md, lab = _prep(X, dev), _prep(mask, dev), _prep(S, dev, torch.int32)
         lib = _native.lib()
-        need = int(lib.rdesign_train_workspace_bytes(self._handle.ptr, B, T))
-        if need == 0:                                # refused sizes (B*T*k beyond the dropout hash's index range): the library has set the text
+        flags = _TRAIN[self.train_precision]
+        need = int(lib.rdesign_train_workspace_bytes_ex(self._handle.ptr, B, T, flags))
+        if need == 0:
+            # refused (rows beyond the dropout hash's index range, a message depth the mixed step lacks): the step itself, asked with no
+            # buffers, returns the code that goes with the text the library has set
+            _native.check(lib.rdesign_loss_and_grad_ex(self._handle.ptr, None, None, None, B, T, C.c_float(p), C.c_uint64(0), flags,
+                                                       None, None, None, None, C.c_size_t(0), None))
             _native.check(_native.ERR_BAD_ARG)
         if self._tws is None or self._tws.numel() < need + 256 or self._tws.device != dev:
             self._tws = None
@@ -335,16 +356,16 @@ class RNAModel(nn.Module):
         loss = torch.zeros((), dtype=torch.float32, device=dev)
         logits = torch.zeros(B * T, 4, dtype=torch.float32, device=dev) if return_logits else None
         with torch.cuda.device(dev):
-            _native.check(lib.rdesign_loss_and_grad(self._handle.ptr, C.c_void_p(Xd.data_ptr()), C.c_void_p(md.data_ptr()),
-                                                    C.c_void_p(lab.data_ptr()), B, T, C.c_float(p), C.c_uint64(seed & (2 ** 64 - 1)),
-                                                    C.c_void_p(loss.data_ptr()), C.c_void_p(logits.data_ptr()) if return_logits else None,
-                                                    C.c_void_p(grad.data_ptr()), C.c_void_p(aligned),
-                                                    C.c_size_t(self._tws.numel() - (aligned - base)), _stream(dev)))
+            _native.check(lib.rdesign_loss_and_grad_ex(self._handle.ptr, C.c_void_p(Xd.data_ptr()), C.c_void_p(md.data_ptr()),
+                                                       C.c_void_p(lab.data_ptr()), B, T, C.c_float(p), C.c_uint64(seed & (2 ** 64 - 1)), flags,
+                                                       C.c_void_p(loss.data_ptr()), C.c_void_p(logits.data_ptr()) if return_logits else None,
+                                                       C.c_void_p(grad.data_ptr()), C.c_void_p(aligned),
+                                                       C.c_size_t(self._tws.numel() - (aligned - base)), _stream(dev)))
         return loss, logits
 
     def loss_and_grad(self, X, S, mask, dropout: Optional[float] = None, seed: Optional[int] = None, return_logits: bool = False):
-        """``training_step`` + ``loss.backward()`` of the reference (``rdesign.py:95-104``) in one native call (f32 HIP kernels,
-        bit-reproducible): -> loss (device scalar) [, logits (N, 4) packed over the valid residues].  ``dropout``: None = the module's
+        """``training_step`` + ``loss.backward()`` of the reference (``rdesign.py:95-104``) in one native call (HIP kernels in the
+        arithmetic of ``train_precision``, bit-reproducible): -> loss (device scalar) [, logits (N, 4) packed over the valid residues].  ``dropout``: None = the module's
         hyper-parameter in train mode and 0 in eval mode; the masks are a function of ``seed`` (None = the module's running counter,
         ``manual_seed``).  Afterwards every ``p.grad`` is a view of ONE flat buffer ``self.flat_grad`` (OVERWRITTEN), so a
         data-parallel job averages gradients with one ``dist.all_reduce(model.flat_grad)``."""

@@ -2,7 +2,8 @@
 """Throughput of the rdesign forward (row F3) on a C2-shaped batch (64 RNAs x 100..500 nt): tools/rdesign_probe.py [precision] [steps].
 Prints one JSON line (nt/s, ms/step).  Run under tools/kstats_rdesign.sh for the per-kernel breakdown.
 
-tools/rdesign_probe.py --train [steps] [--no-trace] [--out DIR]: the f32 TRAINING step at the same shape (dropout 0.1): HIP events around
+tools/rdesign_probe.py --train [steps] [--train-precision {f32,bf16}] [--no-trace] [--out DIR]: the TRAINING step (exact f32 by default, or the
+bf16-mixed one) of a precision="f32" model at the same shape (dropout 0.1): HIP events around
 >= 20 warmed steps of loss_and_grad + FlatAdam.step, the f32 forward of the same run next to it, workspace / tape bytes; before that (and
 before this process touches the GPU) one traced run of three steps in a child process under `rocprofv3 --kernel-trace --stats`, whose
 per-kernel table is printed and kept under DIR (default build/rdesign_train)."""
@@ -15,13 +16,20 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _trace(out_dir):
+def _train_precision(argv):
+    tp = argv[argv.index("--train-precision") + 1] if "--train-precision" in argv else "f32"
+    if tp not in ("f32", "bf16"):
+        raise SystemExit("--train-precision takes f32 or bf16")
+    return tp
+
+
+def _trace(out_dir, train_precision):
     """One `rocprofv3 --kernel-trace --stats` run of a fresh child (this process has not opened the GPU yet) -> per-kernel table."""
     import csv
     import glob
     os.makedirs(out_dir, exist_ok=True)
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out_dir, "--", sys.executable, os.path.abspath(__file__),
-           "--train", "3", "--no-trace"]
+           "--train", "3", "--no-trace", "--train-precision", train_precision]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=420, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"))
     open(os.path.join(out_dir, "prof.log"), "wb").write(r.stdout)
     if r.returncode != 0:
@@ -43,7 +51,7 @@ def _out_dir(argv):
 
 
 if "--train" in sys.argv and "--no-trace" not in sys.argv:      # first, while this process has loaded nothing of the GPU stack
-    _trace(_out_dir(sys.argv))
+    _trace(_out_dir(sys.argv), _train_precision(sys.argv))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -71,7 +79,8 @@ def _train(argv):
     steps = max(int(next((a for a in argv if a.isdigit()), 20)), 1)      # (--out takes a path, not a number)
     from rdesign import _native
     torch.manual_seed(0)
-    m = RNAModel(precision="f32").cuda().train()
+    tp = _train_precision(argv)
+    m = RNAModel(precision="f32", train_precision=tp).cuda().train()
     Xd, md, Sd, n_valid = _batch()
     opt = m.configure_optimizers(fused=True)[0][0]
 
@@ -95,10 +104,11 @@ def _train(argv):
     ms_fwd = timed(lambda: m._run(Xd, md, want=("logits",), n_valid=n_valid), steps)
     B, T = md.shape
     lib = _native.lib()
+    flags = _native.TRAIN_BF16_MIXED if tp == "bf16" else _native.TRAIN_F32
     print(json.dumps(dict(metric="rdesign_train_step_nt_per_s", value=n_valid / (ms_step * 1e-3), ms_per_step=ms_step, ms_f32_forward=ms_fwd,
-                          step_over_f32_forward=ms_step / ms_fwd, nt=n_valid, steps=steps, precision="f32", dropout=m.hparams["dropout"],
-                          workspace_bytes=int(lib.rdesign_train_workspace_bytes(m._handle.ptr, B, T)),
-                          tape_bytes=int(lib.rdesign_train_tape_bytes(m._handle.ptr, B, T)),
+                          step_over_f32_forward=ms_step / ms_fwd, nt=n_valid, steps=steps, precision="f32", train_precision=tp, dropout=m.hparams["dropout"],
+                          workspace_bytes=int(lib.rdesign_train_workspace_bytes_ex(m._handle.ptr, B, T, flags)),
+                          tape_bytes=int(lib.rdesign_train_tape_bytes_ex(m._handle.ptr, B, T, flags)),
                           config="RNAModel defaults (k=25, 9 layers, dense 256), 64 RNAs x 100..500 nt synthetic; loss_and_grad + FlatAdam.step")))
 
 
