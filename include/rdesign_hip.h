@@ -6,9 +6,10 @@
  * `train.py:67-80` of the reference run today).  Every entry point names the reference interface it replaces;
  * `rna-mpnn_amd/rdesign/model/rdesign.py` binds these symbols with ctypes and re-exposes the reference's names.
  *
- * PARITY UNPINNED: the reference's `rdesign.model` modules import `rdesign/utils/data.py`, which needs BioPython,
- * pytorch_lightning and seaborn - absent from this image - and no rdesign fixture or checkpoint ships with the reference.
- * The checker is the CPU restatement `oracle/rdesign_oracle.py` (numpy, citing the reference line by line) alone.
+ * PARITY: the eval-mode forward, the graph, the raw features and the p = 0 gradients are pinned to the reference's own
+ * `RNAFeatures` / `MPNNLayer` / `Readout` through `tests/golden/rdesign_*.npz` (tools/gen_golden_rdesign.py,
+ * tests/test_rdesign_golden_{cpu,gpu}.py); the CPU restatement `oracle/rdesign_oracle.py` is pinned to the same fixtures.
+ * Not pinned: dropout masks (torch's RNG), the xgboost branch of `predict`, the Lightning plumbing.
  *
  * Inference (rdesign_forward / rdesign_readout, f32 or bf16), the exact-f32 training step (rdesign_loss_and_grad) and the opt-in
  * bf16-mixed training step (rdesign_loss_and_grad_ex with RDESIGN_TRAIN_BF16_MIXED).

@@ -7,7 +7,7 @@
 // Layout: packed residues (row p = cu[b] + t) as in the rnampnn path; the GEMMs are the training path's (kernels_train.hip):
 // exact f32 (`t_gemm`, K-major weight copies) or bf16 MFMA with f32 accumulate (`tm_gemm_nt`, weights as stored, GELU fused into the
 // operand load).  The first message Linear is factored W.[h_E | h_i | h_j] = W_e.h_E + P[i] + Q[j] like the rnampnn kernels.
-// PARITY UNPINNED: see oracle/rdesign_oracle.py (the reference modules cannot be imported here, no fixture ships).
+// PARITY: pinned to the reference's own modules in eval mode (graph, raw features, h_V, logits) by tests/golden/rdesign_*.npz - see oracle/rdesign_oracle.py.
 #include "rdesign_internal.h"
 
 #include <cstdarg>

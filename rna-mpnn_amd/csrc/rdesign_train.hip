@@ -9,7 +9,8 @@
 // Dropout addressing (restated by tests/_rdesign_train_ref.py): the TDrop counter hash; site = index of the Dropout module in forward order from 1 -
 // layer l, message Linear i: 1 + l (M + D) + i; layer l, hidden dense Linear i: 1 + l (M + D) + M + i; hidden read-out Linear j: 1 + L (M + D) + j;
 // element = row * width + channel, row = packed node row p or packed edge row p K + slot.
-// PARITY UNPINNED as the forward: the checker is a restatement (oracle/rdesign_oracle.py) differentiated by torch autograd in float64.
+// PARITY: the p = 0 loss and gradients are pinned to the reference's own float64 autograd (tests/golden/rdesign_*.npz); the dropout masks are not
+// (torch's RNG cannot be matched): with dropout the checker is the restatement tests/_rdesign_train_ref.py, itself pinned at p = 0.
 #include "rdesign_internal.h"
 #include "train_dev.h"      // gelu_f, gelu_d, drop_mul: the dropout hash the element-wise kernels of kernels_train.hip use - one definition
 

@@ -11,7 +11,9 @@ flat gradient buffer), ``training_step`` (the same behind an autograd node) and 
 (``rdesign_loss_and_grad_ex``: bf16 per-edge tensors, MFMA GEMMs) on a model of either ``precision``.  A differentiable
 ``forward`` / ``readout`` pair is not built.
 The XGBoost head of ``predict`` is out of scope like the main model's (xgboost is not installed: the reference's own
-``NotFittedError`` branch, argmax of ``Readout``, is the one taken - ``rdesign.py:152-155``).  PARITY UNPINNED (``oracle/rdesign_oracle.py``).
+``NotFittedError`` branch, argmax of ``Readout``, is the one taken - ``rdesign.py:152-155``).  
+Parity: eval-mode forward, graph, features and p = 0 gradients are pinned to the reference's own modules (``tests/golden/rdesign_*.npz``);
+dropout masks, the XGBoost branch of ``predict`` and the Lightning plumbing are not.
 """
 from __future__ import annotations
 

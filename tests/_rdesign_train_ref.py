@@ -1,10 +1,11 @@
 """fp64 reference of the rdesign TRAINING step (test helper; imported by test_rdesign_train_cpu.py / test_rdesign_train_gpu.py).
 
-`oracle.rdesign_oracle.forward` has no dropout and computes its own features, and `oracle/` does not change; this module restates
+`oracle.rdesign_oracle.forward` has no dropout and computes its own features; this module restates
 its layer loop from that module's own pieces (`_custom_norm`, `_gelu`, `F.layer_norm`, the `src` / `dst` construction) with
 `oracle.rnampnn_oracle.dropout_multiplier` at the sites `csrc/rdesign_train.hip` documents, takes the raw features as ARGUMENTS
 (so a GPU test can feed the device's own taps and compare only the training code), runs in float64 and is differentiated by torch
-autograd with `F.cross_entropy`.  PARITY UNPINNED like the oracle it restates.
+autograd with `F.cross_entropy`.  At p = 0 its loss and gradients are PINNED to float64 autograd through the reference's own modules
+(tests/golden/rdesign_*.npz, tests/test_rdesign_golden_cpu.py: per tensor within 1e-10); the dropout masks have no reference counterpart.
 
 Dropout addressing: site = index of the Dropout module in forward order from 1 (layer l, message Linear i: 1 + l (M + D) + i;
 layer l, hidden dense Linear i: 1 + l (M + D) + M + i; hidden read-out Linear j: 1 + L (M + D) + j); element = row * width +

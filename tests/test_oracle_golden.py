@@ -6,6 +6,8 @@ import pytest
 import torch
 
 from conftest import FULL_CASES, GOLDEN_CASES
+
+GOLDEN_CASES = [c for c in GOLDEN_CASES if not c.startswith("rdesign_")]     # rdesign_*.npz: the sibling model's fixtures (test_rdesign_golden_*.py)
 from oracle import rnampnn_oracle as O
 from rnampnn.utils import synth
 

@@ -1,5 +1,6 @@
 """CPU checks of the `rdesign` row: the C ABI of include/rdesign_hip.h is exported, the parameter table
-equals the oracle's restatement of the reference state_dict, and the oracle (PARITY UNPINNED - oracle/rdesign_oracle.py) is
+equals the oracle's restatement of the reference state_dict, the reference-made fixtures tests/golden/rdesign_*.npz load with their
+documented keys, and the oracle (oracle/rdesign_oracle.py; pinned to the reference's own modules by tests/test_rdesign_golden_cpu.py) is
 self-consistent: shapes, rigid-motion invariance, batch/padding independence, neighbour ordering."""
 import os
 import re
@@ -10,30 +11,7 @@ import torch
 
 from conftest import REPO
 from oracle import rdesign_oracle as O
-
-
-def _batch(lengths, seed=0):
-    from rnampnn.utils import synth
-    T = max(lengths)
-    X = np.zeros((len(lengths), T, 6, 3), np.float32)
-    mask = np.zeros((len(lengths), T), np.float32)
-    for i, n in enumerate(lengths):
-        X[i, :n] = synth.synth_rna(n, i, seed=seed)[:, :6]
-        mask[i, :n] = 1
-    return torch.from_numpy(X), torch.from_numpy(mask)
-
-
-def _weights(cfg, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for k, shp in O.state_dict_shapes(cfg).items():
-        if k.endswith("gain") or (("norm1" in k or "norm2" in k) and k.endswith("weight")):
-            sd[k] = 1.0 + 0.1 * torch.randn(shp, generator=g)
-        elif len(shp) == 2:
-            sd[k] = torch.randn(shp, generator=g) / shp[1] ** 0.5
-        else:
-            sd[k] = 0.1 * torch.randn(shp, generator=g)
-    return sd
+from _rdesign_cases import FORWARD_KEYS, FULL_KEYS, GRAD_GOLDEN, GRAD_KEYS, GRAD_META_KEYS, META_KEYS, RDESIGN_GOLDEN, _batch, _weights, load_rdesign_golden
 
 
 def test_library_exports_every_declared_rdesign_symbol():
@@ -126,3 +104,27 @@ def test_oracle_interior_rows_do_not_depend_on_batch_padding():
     node1, edge1, _, attend1 = O.raw_features(X1, m1, cfg)
     assert torch.allclose(node[0, :5], node1[0, :5], atol=1e-6)
     assert (attend[0, :7] == attend1[0]).all()
+
+
+def test_every_rdesign_golden_loads_and_carries_the_documented_keys():
+    """tests/golden/rdesign_*.npz (tools/gen_golden_rdesign.py; key list: tests/_rdesign_cases.py)."""
+    assert len(RDESIGN_GOLDEN) >= 12
+    n_full = 0
+    for name in RDESIGN_GOLDEN:
+        a, meta = load_rdesign_golden(name)
+        assert set(FORWARD_KEYS) <= set(a) and set(META_KEYS) <= set(meta), name
+        assert "xgboost" not in meta["stubbed"]                                      # the composite never imports the LightningModule
+        cfg = O.RDesignConfig(**meta["cfg"])
+        n, rs, rs64 = int(a["mask"].sum()), meta["row_stride"], meta["f64_row_stride"]
+        assert a["X"].shape[2:] == (6, 3) and a["mask"].shape == a["X"].shape[:2] and a["X"].dtype == np.float32
+        assert a["h_V"].shape == (n, 128) and a["logits"].shape == (n, 4) and a["logits_f64"].dtype == np.float64
+        assert a["node_raw"].shape == (len(range(0, n, rs)), 101) and a["edge_raw"].shape[1] == 115 and a["E_idx"].shape[0] == 2
+        assert a["h_V_f64"].shape == (len(range(0, n, rs64)), 128) and a["h_V_f64"].dtype == np.float64
+        assert a["s2.h_V"].shape == (len(range(0, n, meta["s2_row_stride"])), 128) and a["s2.logits"].shape == (n, 4)
+        if all(k in a for k in FULL_KEYS):
+            n_full += 1
+        if name in GRAD_GOLDEN:
+            assert set(GRAD_KEYS) <= set(a) and set(GRAD_META_KEYS) <= set(meta), name
+            assert {p + "grad." + k for k in O.state_dict_shapes(cfg) for p in ("", "s2.")} <= set(a), name
+            assert a["grad_norm"].shape == (len(O.state_dict_shapes(cfg)),)
+    assert n_full >= 5 and len(GRAD_GOLDEN) == 3

@@ -1,6 +1,6 @@
 """GPU parity of the `rdesign` row: `rdesign_forward` / `rdesign_readout` through the C ABI vs the CPU
-restatement oracle/rdesign_oracle.py on the same seeded inputs.  PARITY UNPINNED: the oracle itself has no reference-produced
-vector behind it (see its header); these tests pin the HIP path to the restatement, not to the reference."""
+restatement oracle/rdesign_oracle.py on the same seeded inputs.  The oracle is pinned to the reference's own modules by
+tests/test_rdesign_golden_cpu.py; tests/test_rdesign_golden_gpu.py compares the HIP path with the reference-made fixtures directly."""
 import numpy as np
 import pytest
 import torch

@@ -1,7 +1,8 @@
 """CPU checks of the rdesign bf16-mixed training step: the `_ex` C ABI is declared, bound and exported; the new translation unit keeps the
 code base's rules (no runtime fill / copy calls, no atomics, no environment switches, ordered reductions); the default stays the exact-f32
 step and its refusal; there is no CPU fallback; the host-only size queries accept either handle and the bf16 tape is at most 0.6 of the f32
-one.  PARITY UNPINNED like every rdesign test: the checker of the GPU file is a restatement (oracle/rdesign_oracle.py)."""
+one.  Parity: the checker of the GPU file is a restatement (tests/_rdesign_train_ref.py), pinned at p = 0 to the reference's own autograd by
+tests/test_rdesign_golden_cpu.py; the step itself is compared with the reference directly in tests/test_rdesign_golden_gpu.py."""
 import os
 import re
 

@@ -2,7 +2,8 @@
 "bf16")`) against the fp64 restatement tests/_rdesign_train_ref.py differentiated by torch autograd - the checker of the f32 step
 (tests/test_rdesign_train_gpu.py), fed the DEVICE's raw features in the same way, with the same dropout masks.  The bounds are the ones the
 project uses for its bf16-mixed trainer (imported, not copied): BF16_LOSS_TOL, bf16_tol, BF16_GRAD_REL, BF16_COS.
-PARITY UNPINNED: the checker is a restatement, not the reference's own modules (oracle/rdesign_oracle.py)."""
+The checker is a restatement; at p = 0 it is pinned to the reference's own autograd (tests/test_rdesign_golden_cpu.py), and
+tests/test_rdesign_golden_gpu.py compares this step with the reference directly.  The dropout masks have no reference counterpart."""
 import numpy as np
 import pytest
 import torch

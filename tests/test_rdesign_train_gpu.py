@@ -1,7 +1,8 @@
 """GPU checks of the rdesign f32 training step (`rdesign_loss_and_grad`, `RNAModel.loss_and_grad` / `training_step`, `FlatAdam`)
 against the fp64 restatement tests/_rdesign_train_ref.py differentiated by torch autograd.  The reference is fed the DEVICE's raw
 features (taps of `rdesign_forward`, parent-commit code with its own test), so the comparison sees only the training code.
-PARITY UNPINNED: the checker is a restatement, not the reference's own modules (oracle/rdesign_oracle.py)."""
+The checker is a restatement; at p = 0 it is pinned to the reference's own autograd (tests/test_rdesign_golden_cpu.py), and
+tests/test_rdesign_golden_gpu.py compares this step with the reference directly.  The dropout masks have no reference counterpart."""
 import ctypes as C
 
 import numpy as np
