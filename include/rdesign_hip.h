@@ -11,8 +11,9 @@
  * tests/test_rdesign_golden_{cpu,gpu}.py); the CPU restatement `oracle/rdesign_oracle.py` is pinned to the same fixtures.
  * Not pinned: dropout masks (torch's RNG), the xgboost branch of `predict`, the Lightning plumbing.
  *
- * Inference (rdesign_forward / rdesign_readout, f32 or bf16), the exact-f32 training step (rdesign_loss_and_grad) and the opt-in
- * bf16-mixed training step (rdesign_loss_and_grad_ex with RDESIGN_TRAIN_BF16_MIXED).
+ * Inference (rdesign_forward / rdesign_readout, f32 or bf16), the exact-f32 training step (rdesign_loss_and_grad), the opt-in
+ * bf16-mixed training step (rdesign_loss_and_grad_ex with RDESIGN_TRAIN_BF16_MIXED) and the per-RNA validation metrics on the device
+ * (rdesign_score: what the epoch trainer's `validate` and `RNAModel.score_batch` / `predict_sequences` run after one forward).
  *
  * Conventions: as rnampnn_hip.h (device pointers, caller's stream, no synchronisation, 0 = success).
  *   X (B,T,6,3) f32 backbone atoms P, O5', C5', C4', C3', O3' (rdesign/utils/data.py:90-115, zero-filled padding),
@@ -115,6 +116,21 @@ size_t rdesign_train_tape_bytes_ex(rdesign_handle h, int32_t B, int32_t T, int32
 int rdesign_loss_and_grad_ex(rdesign_handle h, const float* X, const float* mask, const int32_t* labels, int32_t B, int32_t T,
                              float dropout, uint64_t seed, int32_t flags, float* loss, float* logits, float* grad, void* ws,
                              size_t ws_bytes, void* stream);
+
+/* The metrics of validation_step / test_step (rdesign.py:106-141) per RNA, on the device: argmax against the labels, and the cross-entropy.
+ * Exactly one of
+ *   logits   (n_rows,4) f32 packed as rdesign_forward writes them (16-byte aligned), or
+ *   pred     (n_rows) i32 packed class ids (the tree read-out's route)
+ * is non-null; n_rows = rows the packed buffers hold (>= mask.sum(); rows beyond it are never touched).
+ *   mask (B,T) f32 prefix masks, labels (B,T) i32 in the padded layout of the training step (padding ignored)
+ *   correct (B) i32, valid (B) i32: matches and length per RNA (an RNA of length 0 gives 0 / 0 / 0)
+ *   nll     (B) f32, optional, logits only (non-null with pred: RDESIGN_ERR_BAD_ARG): per-RNA SUM of logsumexp(x) - x[label]
+ *   pred_out (n_rows) i32, optional: the packed argmax (ties to the lowest class, as numpy.argmax) / a copy of pred
+ * Both or neither of logits / pred, B <= 0 or T <= 0: RDESIGN_ERR_BAD_ARG.  Needs no handle.  Fixed-order reductions without atomics (two
+ * calls give identical bytes), no runtime memset / memcpy, no synchronisation.  ws: rdesign_score_workspace_bytes(B), 16-byte aligned. */
+size_t rdesign_score_workspace_bytes(int32_t B);
+int rdesign_score(const float* logits, const int32_t* pred, int32_t n_rows, const float* mask, const int32_t* labels, int32_t B, int32_t T,
+                  int32_t* correct, int32_t* valid, float* nll, int32_t* pred_out, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

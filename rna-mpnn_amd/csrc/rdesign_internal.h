@@ -1,5 +1,5 @@
 // Declarations shared by the translation units of the `rdesign` path: rdesign.hip (handle, features, inference forward), rdesign_train.hip
-// (taped forward + backward of the f32 training step) and rdesign_train_bf16.hip (the bf16-mixed training step).
+// (taped forward + backward of the f32 training step), rdesign_train_bf16.hip (the bf16-mixed training step) and rdesign_score.hip (per-RNA metrics).
 #pragma once
 #include "../../include/rdesign_hip.h"
 #include "rnampnn_internal.h"

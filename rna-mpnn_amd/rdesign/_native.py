@@ -38,6 +38,8 @@ SYMBOLS = {
     "rdesign_train_workspace_bytes_ex": (_SZ, [_VP, _I32, _I32, _I32]),
     "rdesign_train_tape_bytes_ex": (_SZ, [_VP, _I32, _I32, _I32]),
     "rdesign_loss_and_grad_ex": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, C.c_float, C.c_uint64, _I32, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "rdesign_score_workspace_bytes": (_SZ, [_I32]),
+    "rdesign_score": (C.c_int, [_VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
 }
 _bound = False
 

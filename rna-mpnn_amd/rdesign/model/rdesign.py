@@ -10,8 +10,12 @@ flat gradient buffer), ``training_step`` (the same behind an autograd node) and 
 ``rdesign/utils/train.py:107-115``) and the default of the step; ``train_precision="bf16"`` opts into the bf16-mixed step
 (``rdesign_loss_and_grad_ex``: bf16 per-edge tensors, MFMA GEMMs) on a model of either ``precision``.  A differentiable
 ``forward`` / ``readout`` pair is not built.
-The XGBoost head of ``predict`` is out of scope like the main model's (xgboost is not installed: the reference's own
-``NotFittedError`` branch, argmax of ``Readout``, is the one taken - ``rdesign.py:152-155``).  
+Epoch-level surface: ``score_batch`` (one forward + ``rdesign_score``: per-RNA correct / valid / NLL as device tensors, no host round
+trip when the loader's host ``lengths`` are passed), ``reserve_training``, ``allreduce_gradients`` (one flat all-reduce) - what
+``rdesign.utils.train.Trainer`` drives.  The XGBoost head: ``xgb_readout`` is None until ``fit_xgb_readout`` / ``load_xgb_readout`` attach
+the main model's device tree read-out (``rnampnn/model/xgb.py``, parity with XGBoost unpinned) to the packed 128-wide ``h_V``
+(``rdesign/utils/train.py:58-89``, ``rdesign.py:151-153``); without one ``predict`` takes the reference's ``NotFittedError`` branch,
+argmax of ``Readout`` (``rdesign.py:152-155``).
 Parity: eval-mode forward, graph, features and p = 0 gradients are pinned to the reference's own modules (``tests/golden/rdesign_*.npz``);
 dropout masks, the XGBoost branch of ``predict`` and the Lightning plumbing are not.
 """
@@ -138,6 +142,9 @@ class RNAModel(nn.Module):
                             num_message_layers=num_message_layers, num_dense_layers=num_dense_layers,
                             dim_dense_layers=dim_dense_layers, num_mpnn_layers=num_mpnn_layers,
                             readout_hidden_dim=readout_hidden_dim, num_readout_layers=num_readout_layers, lr=lr)
+        self.xgb_hparams = dict(n_estimators=n_estimators, xgb_max_depth=xgb_max_depth, xgb_learning_rate=xgb_learning_rate,
+                                xgb_subsample=xgb_subsample, xgb_colsample_bytree=xgb_colsample_bytree)      # not the handle's business
+        self.xgb_readout = None                        # a ``GBDTReadout`` once fitted / loaded: ``predict`` then takes the tree route
         self.hidden_dim, self.vocab = hidden_dim, vocab_size
         self._handle = _native.Handle(self.hparams, _PREC[precision])      # validates like the reference constructor would fail later
         self.features = RNAFeatures(hidden_dim)
@@ -176,6 +183,18 @@ class RNAModel(nn.Module):
     @property
     def device(self) -> torch.device:
         return next(self.parameters()).device
+
+    @property
+    def init_kwargs(self) -> dict:
+        """Constructor arguments that rebuild this module (plain types: what a checkpoint stores next to the ``state_dict``)."""
+        return dict(self.hparams, **self.xgb_hparams, precision=self.precision, train_precision=self.train_precision)
+
+    def _device(self) -> torch.device:
+        """The CUDA device of the parameters (the name the main model's helpers use); raises on a CPU module."""
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("the rdesign HIP path runs on an MI355X: move the module to 'cuda' first (there is no CPU fallback)")
+        return dev
 
     def _ensure(self, for_mixed_training: bool = False) -> torch.device:
         """Parameters aliased to the flat arena, kernel-side weight copies current.  ``for_mixed_training`` is accepted for
@@ -324,6 +343,130 @@ class RNAModel(nn.Module):
         scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=40, gamma=0.8)
         return [optimizer], [scheduler]
 
+    # ------------------------------------------------------------------ epoch-level surface (rdesign.utils.train.Trainer)
+    def reserve_training(self, shapes) -> None:
+        """Size the training workspace for the largest of ``shapes`` = iterable of (B, T) BEFORE a timed loop (``RNAMPNN.reserve_training``):
+        growing a multi-gigabyte tape in the middle of an epoch costs a free + allocate + the allocator's synchronisation."""
+        dev = self._ensure()
+        lib, flags = _native.lib(), _TRAIN[self.train_precision]
+        need = max((int(lib.rdesign_train_workspace_bytes_ex(self._handle.ptr, int(B), int(T), flags)) for B, T in shapes), default=0)
+        if need and (self._tws is None or self._tws.numel() < need + 256 or self._tws.device != dev):
+            self._tws = None
+            self._tws = torch.empty(int(need * 1.05) + 256, dtype=torch.uint8, device=dev)
+
+    def allreduce_gradients(self, force: bool = False) -> None:
+        """Average ``flat_grad`` over the ranks of the default process group: ONE ``all_reduce`` of the flat buffer on the caller's stream,
+        then a scale by 1 / world.  A no-op without a process group or at world size 1 unless ``force`` (tests drive the RCCL path on one
+        GPU with it).  No chunks, no side stream."""
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or force)):
+            return
+        dist.all_reduce(self.flat_grad, op=dist.ReduceOp.SUM)
+        world = dist.get_world_size()
+        if world > 1:
+            self.flat_grad.mul_(1.0 / world)
+
+    def _score_native(self, logits, pred, mask, S, want_nll: bool = True, want_pred: bool = False):
+        """``rdesign_score`` on packed ``logits`` (n, 4) f32 XOR packed ``pred`` (n,) int32 -> (correct (B,) i32, valid (B,) i32,
+        nll (B,) f32 or None, pred_out (n,) i32 or None), all on the device, nothing synchronised."""
+        dev = self._device()
+        if mask.dim() != 2 or tuple(S.shape) != tuple(mask.shape):
+            raise ValueError(f"mask and S must be (B, T); got {tuple(mask.shape)}, {tuple(S.shape)}")
+        B, T = int(mask.shape[0]), int(mask.shape[1])
+        md, lab = _prep(mask, dev), _prep(S, dev, torch.int32)
+        lg = None if logits is None else _prep(logits, dev)
+        pr = None if pred is None else _prep(pred, dev, torch.int32)
+        src = lg if lg is not None else pr
+        n = 0 if src is None else int(src.shape[0])
+        correct = torch.empty(B, dtype=torch.int32, device=dev)
+        valid = torch.empty(B, dtype=torch.int32, device=dev)
+        nll = torch.empty(B, dtype=torch.float32, device=dev) if want_nll else None
+        pred_out = torch.empty(n, dtype=torch.int32, device=dev) if want_pred else None
+        lib = _native.lib()
+        ws = torch.empty(max(int(lib.rdesign_score_workspace_bytes(B)), 16), dtype=torch.uint8, device=dev)
+        vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        with torch.cuda.device(dev):
+            _native.check(lib.rdesign_score(vp(lg), vp(pr), n, vp(md), vp(lab), B, T, vp(correct), vp(valid), vp(nll), vp(pred_out),
+                                            vp(ws), C.c_size_t(ws.numel()), _stream(dev)))
+        return correct, valid, nll, pred_out
+
+    @staticmethod
+    def _n_valid(lengths) -> Optional[int]:
+        return None if lengths is None else int(sum(int(v) for v in lengths))
+
+    @torch.no_grad()
+    def score_batch(self, X, S, mask, lengths=None, use_trees: bool = False):
+        """What ``validation_step`` accumulates, per RNA and on the device: one forward + ``rdesign_score`` ->
+        (correct (B,) int32, valid (B,) int32, nll (B,) f32 = per-RNA SUM of the cross-entropy; None on the tree route).  ``lengths``:
+        the host-side lengths the loader already has - with them nothing here touches the host (the caller vouches for the prefix mask);
+        without them ``_run`` checks the mask and counts its ones on the host.  ``use_trees``: score ``xgb_readout.predict(h_V)``."""
+        n = self._n_valid(lengths)
+        if use_trees:
+            if self.xgb_readout is None:
+                raise RuntimeError("score_batch(use_trees=True) needs a tree read-out: call fit_xgb_readout or load_xgb_readout first")
+            h_V = self._run(X, mask, want=("h_V",), n_valid=n)["h_V"]
+            return self._score_native(None, self.xgb_readout.predict(h_V), mask, S, want_nll=False)[:3]
+        logits = self._run(X, mask, want=("logits",), n_valid=n)["logits"]
+        return self._score_native(logits, None, mask, S)[:3]
+
+    # ------------------------------------------------------------------ tree head (rdesign/utils/train.py:51-89, rdesign.py:151-153)
+    def load_xgb_readout(self, model_json) -> None:
+        """Attach a fitted multi:softmax model in XGBoost's JSON schema (path or dict) over this model's 128 ``h_V`` features.  The
+        reference unpickles ``XGB-V*.pkl``; pickles are never loaded here."""
+        from rnampnn.model.xgb import GBDTReadout
+        self.xgb_readout = GBDTReadout.from_xgboost_json(model_json)
+
+    @torch.no_grad()
+    def embed_valid(self, batches):
+        """``XGBTrainer._generate_embedding`` (rdesign/utils/train.py:75-89) without leaving the device: ``batches`` yields the loader's
+        (S, X, mask, lengths, ...) -> (h_V (N, 128) f32, labels (N,) int64) packed over the valid residues."""
+        dev = self._device()
+        xs, ys = [], []
+        for batch in batches:
+            S, X, mask = batch[0], batch[1], batch[2]
+            n = self._n_valid(batch[3]) if len(batch) > 3 else None
+            xs.append(self._run(X, mask, want=("h_V",), n_valid=n)["h_V"])
+            ys.append(S.to(dev)[mask.to(dev) == 1].to(torch.int64))
+        if not xs:
+            raise ValueError("embed_valid: no batches")
+        return torch.cat(xs), torch.cat(ys)
+
+    @torch.no_grad()
+    def fit_xgb_readout(self, batches, seed: int = 0) -> float:
+        """``XGBTrainer.on_fit_end``: embed every valid nucleotide of ``batches``, fit the tree read-out on those rows ON THE DEVICE
+        (``GBDTReadout.fit``) with the five constructor hyper-parameters (``xgb_hparams``; the reference's defaults: 100 rounds, depth 6,
+        0.1 / 0.8 / 0.8) and attach it.  Returns the score on the rows it was fitted on."""
+        from rnampnn.model.xgb import GBDTReadout
+        X, y = self.embed_valid(batches)
+        hp = self.xgb_hparams
+        self.xgb_readout = GBDTReadout.fit(X, y, num_class=4, n_estimators=int(hp["n_estimators"]), max_depth=int(hp["xgb_max_depth"]),
+                                           learning_rate=float(hp["xgb_learning_rate"]), subsample=float(hp["xgb_subsample"]),
+                                           colsample_bytree=float(hp["xgb_colsample_bytree"]), seed=int(seed))
+        return self.xgb_readout.score(X, y)
+
+    @torch.no_grad()
+    def _predict_packed(self, X, mask, lengths=None) -> torch.Tensor:
+        """Packed class ids (N,) on the device: ``xgb_readout.predict(h_V)`` when a tree model is attached (``rdesign.py:151-153``), else
+        the argmax of the read-out from ``rdesign_score`` (ties to the lowest class)."""
+        n = self._n_valid(lengths)
+        if self.xgb_readout is not None:
+            return self.xgb_readout.predict(self._run(X, mask, want=("h_V",), n_valid=n)["h_V"])
+        logits = self._run(X, mask, want=("logits",), n_valid=n)["logits"]
+        zeros = torch.zeros(mask.shape, dtype=torch.int32, device=logits.device)
+        return self._score_native(logits, None, mask, zeros, want_nll=False, want_pred=True)[3]
+
+    @torch.no_grad()
+    def predict_sequences(self, X, mask, lengths=None):
+        """The sequences ``predict`` writes, one string per RNA of the batch (one device-to-host copy of the packed class ids)."""
+        if lengths is None:
+            lengths = mask.sum(dim=1).to(torch.int64).tolist()
+        ids = self._predict_packed(X, mask, lengths).tolist()
+        out, start = [], 0
+        for n in (int(v) for v in lengths):
+            out.append("".join("AUCG"[i] for i in ids[start:start + n]))
+            start += n
+        return out
+
     # ------------------------------------------------------------------ training step (exact f32, or bf16-mixed by train_precision)
     def _train_args(self, dropout, seed):
         if self.train_precision == "f32" and self.precision != "f32":
@@ -415,10 +558,14 @@ class RNAModel(nn.Module):
         return {"test loss": loss, "recovery_rates": rates}
 
     def predict(self, batch, batch_id, output_dir, filename):
-        """``rdesign.py:143-173``: argmax of the read-out (the reference's branch for an unfitted XGBoost head), one CSV row per RNA."""
+        """``rdesign.py:143-173``: the classes of the attached tree read-out, or - the reference's branch for an unfitted XGBoost head -
+        the argmax of the read-out; one CSV row per RNA."""
         self.eval()
         X, S, mask, lengths, pdb_ids = batch
-        samples = self._run(X, mask, want=("logits",))["logits"].argmax(dim=-1).tolist()
+        if self.xgb_readout is not None:
+            samples = self._predict_packed(X, mask).tolist()
+        else:
+            samples = self._run(X, mask, want=("logits",))["logits"].argmax(dim=-1).tolist()
         os.makedirs(output_dir, exist_ok=True)
         start = 0
         with open(os.path.join(output_dir, filename), "a") as f:

@@ -197,19 +197,20 @@ class PackedLoader:
         th.join()
 
 
-def pad_batch(items: Sequence, pin: bool = True):
+def pad_batch(items: Sequence, pin: bool = True, atoms: int = 7):
     """The reference collate's layout (``featurize``, utils/data.py:110-142) for (coords (L,7,3), labels (L,)) pairs, built in
     pinned host memory: (labels (B,T) int32, coords (B,T,7,3) f32, mask (B,T) f32, lengths (B,) list).  Labels are class ids
-    (the one-hot of the reference is an argmax away and 4x the bytes)."""
+    (the one-hot of the reference is an argmax away and 4x the bytes).  ``atoms``: keep the first ``atoms`` backbone atoms of every
+    residue (6 = the ``rdesign`` model's P, O5', C5', C4', C3', O3'); the default is the 7-atom layout unchanged."""
     lens = [int(c.shape[0]) for c, _ in items]
     B, T = len(items), max(lens)
     pin = pin and torch.cuda.is_available()
-    coords = torch.zeros((B, T, 7, 3), dtype=torch.float32, pin_memory=pin)
+    coords = torch.zeros((B, T, atoms, 3), dtype=torch.float32, pin_memory=pin)
     mask = torch.zeros((B, T), dtype=torch.float32, pin_memory=pin)
     labels = torch.zeros((B, T), dtype=torch.int32, pin_memory=pin)
     for i, (c, y) in enumerate(items):
         n = lens[i]
-        coords[i, :n] = torch.as_tensor(c, dtype=torch.float32)
+        coords[i, :n] = torch.as_tensor(c, dtype=torch.float32)[:, :atoms]
         labels[i, :n] = torch.as_tensor(y).to(torch.int32)
         mask[i, :n] = 1.0
     return labels, coords, mask, lens
@@ -220,11 +221,12 @@ class PaddedLoader:
     builds the next batches with ``pad_batch`` in pinned memory and issues their host-to-device copies on a side stream;
     ``__iter__`` yields (labels, coords, mask, lengths, indices) with the three tensors already on the device and the
     consumer's stream waiting on the copy's event only.  ``lengths`` stays on the host: the trainer counts nucleotides without
-    a device round trip.  ``items``: (id, coords, labels) tuples (``load_rna_dir``) or (coords, labels) pairs."""
+    a device round trip.  ``items``: (id, coords, labels) tuples (``load_rna_dir``) or (coords, labels) pairs.  ``atoms``: as ``pad_batch``."""
 
-    def __init__(self, items, batches: Sequence[Sequence[int]], device=None, prefetch: int = 2):
+    def __init__(self, items, batches: Sequence[Sequence[int]], device=None, prefetch: int = 2, atoms: int = 7):
         self.items, self.batches, self.prefetch = items, [list(b) for b in batches], max(1, int(prefetch))
         self.device = torch.device(device) if device is not None else None
+        self.atoms = int(atoms)
 
     def _pair(self, i):
         it = self.items[i]
@@ -241,7 +243,7 @@ class PaddedLoader:
         def worker():
             try:
                 for b in self.batches:
-                    y, c, m, lens = pad_batch([self._pair(i) for i in b], pin=use_gpu)
+                    y, c, m, lens = pad_batch([self._pair(i) for i in b], pin=use_gpu, atoms=self.atoms)
                     if use_gpu:
                         with torch.cuda.stream(side):
                             dy, dc, dm = (t.to(self.device, non_blocking=True) for t in (y, c, m))

@@ -8,11 +8,16 @@ runs are one process per GPU with ONE flat RCCL all-reduce per step (``RNAMPNN.a
     python rna-mpnn_amd/train.py --data /path/to/data --epochs 2                    # coords/*.npy + seqs/*.fasta
     python rna-mpnn_amd/train.py --synthetic 512 --epochs 3                         # seeded synthetic RNAs
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 rna-mpnn_amd/train.py --synthetic 4096
+    python rna-mpnn_amd/train.py --model rdesign --data /path/to/data --epochs 230 --fit-xgb --out runs/rdesign   # the sibling model
 
 Batches are length-bucketed (``rnampnn.utils.train.plan_epoch``): the reference's collate pads every RNA of a batch
 to the longest one, so mixing a 2,436-nt ribosomal RNA with 20-nt hairpins would spend > 99 % of the rows on padding.
 The loop itself is ``rnampnn.utils.train.Trainer``: inputs through ``PaddedLoader`` (pinned memory, copies on a side stream),
 loss accumulated on the device, no host synchronisation inside an epoch.
+
+``--model rdesign`` trains the reference's sibling model instead (the reference's own ``train.py:62-80``: ``rdesign.model.rdesign.RNAModel``,
+Adam(lr) + StepLR(40, 0.8), checkpoint of the epoch with the best ``val_recovery_rate``, XGBoost head fitted at the end) through
+``rdesign.utils.train.Trainer``; ``--out DIR`` receives ``Final.pt`` (and ``XGB.json`` with ``--fit-xgb``), which ``predict.py`` reads.
 """
 from __future__ import annotations
 
@@ -37,6 +42,8 @@ from rnampnn.utils.train import Trainer  # noqa: E402
 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="rnampnn", choices=["rnampnn", "rdesign"],
+                    help="rnampnn = RNAMPNN (the default); rdesign = the sibling RNAModel (6 backbone atoms, k = 25, 9 layers, dropout 0.1)")
     ap.add_argument("--data", default=None)
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--lengths-file", default=None,
@@ -46,9 +53,9 @@ def parse(argv=None):
     ap.add_argument("--batch-size", type=int, default=512, help="upper bound on RNAs per step per rank")
     ap.add_argument("--max-nt", type=int, default=32768, help="upper bound on padded rows (B*T) of one step per rank")
     ap.add_argument("--max-len", type=int, default=4500, help="longest RNA kept (= padding_len; the reference trained with 100, train.py:57)")
-    ap.add_argument("--neighbours", type=int, default=30)
-    ap.add_argument("--layers", type=int, default=10)
-    ap.add_argument("--dropout", type=float, default=None, help="default: the reference's 0.4 (rnampnn.py:47)")
+    ap.add_argument("--neighbours", type=int, default=None, help="default: 30 (rnampnn), 25 (rdesign)")
+    ap.add_argument("--layers", type=int, default=None, help="default: 10 (rnampnn), 9 (rdesign)")
+    ap.add_argument("--dropout", type=float, default=None, help="default: the reference's 0.4 (rnampnn.py:47); rdesign: 0.1")
     ap.add_argument("--nan-policy", default="skip", choices=["skip", "fill"])
     ap.add_argument("--train-precision", default="bf16", choices=["bf16", "f32"],
                     help="bf16 = the reference's bf16-mixed trainer setting (utils/train.py:109); f32 = exact")
@@ -62,30 +69,52 @@ def parse(argv=None):
                     help="after the last epoch fit the gradient-boosted-tree read-out on the training embeddings, on the device "
                          "(the reference's XGBTrainer.on_fit_end, utils/train.py:50-75) and print train / validation score")
     ap.add_argument("--xgb-out", default=None, help="with --fit-xgb: write the fitted model as XGBoost-schema JSON")
+    ap.add_argument("--out", default=None,
+                    help="--model rdesign: directory for Final.pt (weights of the epoch with the best val_recovery_rate + constructor "
+                         "arguments) and, with --fit-xgb, XGB.json")
     return ap.parse_args(argv)
 
 
-def run(args, log=print):
-    """-> dict(epochs=[dict(train_loss, val_micro, val_macro, nt_per_s, steps, seconds)], n_train, n_val)."""
+def rdesign_precisions(train_precision: str) -> dict:
+    """--train-precision -> RNAModel's two precision arguments: bf16 (the CLI default) = bf16 inference + the bf16-mixed step; f32 = the
+    reference's arithmetic, exact-f32 inference and step."""
+    return dict(precision="bf16", train_precision="bf16") if train_precision == "bf16" else dict(precision="f32", train_precision="f32")
+
+
+def _init_dist():
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", "0"), ("WORLD_SIZE", "1"), ("LOCAL_RANK", "0")))
     if world > 1 and not dist.is_initialized():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
+    return rank, world, torch.device("cuda", local)
+
+
+def _synthetic_items(args):
+    if args.lengths_file:
+        lens = [int(n) for n in np.load(args.lengths_file, allow_pickle=False) if 0 < int(n) <= args.max_len]
+    else:
+        lens = synth.synth_lengths(args.synthetic or 256, 30, min(140, args.max_len), seed=1)
+    return [(synth.synth_rna(int(n), i, seed=1), synth.synth_labels(int(n), i, seed=1)) for i, n in enumerate(lens)]
+
+
+def _split(items, args):
+    n_val = 0 if args.no_validation else max(1, len(items) // 20)
+    order0 = np.random.RandomState(args.seed).permutation(len(items))          # id-order-independent split
+    return [items[i] for i in order0[n_val:]], [items[i] for i in order0[:n_val]]
+
+
+def run(args, log=print):
+    """-> dict(epochs=[dict(train_loss, val_micro, val_macro, nt_per_s, steps, seconds)], n_train, n_val)."""
+    if args.model == "rdesign":
+        return run_rdesign(args, log)
+    rank, world, dev = _init_dist()
     if args.data:
         items = [(c, y) for _, c, y in load_rna_dir(args.data, max_len=args.max_len, nan_policy=args.nan_policy)]
     else:
-        if args.lengths_file:
-            lens = [int(n) for n in np.load(args.lengths_file, allow_pickle=False) if 0 < int(n) <= args.max_len]
-        else:
-            lens = synth.synth_lengths(args.synthetic or 256, 30, min(140, args.max_len), seed=1)
-        items = [(synth.synth_rna(int(n), i, seed=1), synth.synth_labels(int(n), i, seed=1)) for i, n in enumerate(lens)]
-    n_val = 0 if args.no_validation else max(1, len(items) // 20)
-    order0 = np.random.RandomState(args.seed).permutation(len(items))          # id-order-independent split
-    val = [items[i] for i in order0[:n_val]]
-    train = [items[i] for i in order0[n_val:]]
-    hp = dict(num_res_neighbours=args.neighbours, num_res_mpnn_layers=args.layers, padding_len=max(args.max_len, 1))
+        items = _synthetic_items(args)
+    train, val = _split(items, args)
+    hp = dict(num_res_neighbours=args.neighbours or 30, num_res_mpnn_layers=args.layers or 10, padding_len=max(args.max_len, 1))
     if args.dropout is not None:
         hp["dropout"] = args.dropout
     model = RNAMPNN(**hp).to(dev)
@@ -118,11 +147,76 @@ def run(args, log=print):
     return out
 
 
-def fit_xgb(model, train, train_lens, val, val_lens, args, dev, log=print):
+def run_rdesign(args, log=print):
+    """``--model rdesign`` -> dict(epochs=[dict(train_loss, val_loss, weighted_val_recovery_rate, val_recovery_rate, nt_per_s, steps,
+    seconds)], n_train, n_val, best_epoch, model[, xgb]).  The model that is returned (and that the tree read-out is fitted on) carries
+    the weights of the best epoch, as the reference's ``XGBTrainer`` reloads its ``Final`` checkpoint."""
+    from rdesign.model.rdesign import RNAModel
+    from rdesign.utils import data as rdata
+    from rdesign.utils.train import Trainer as RDesignTrainer, load_checkpoint, save_checkpoint
+    rank, world, dev = _init_dist()
+    if args.data:
+        items = [(c, y) for _, c, y in rdata.load_rna_dir(args.data, max_len=args.max_len)]        # missing atoms -> 0, as the reference's collate
+    else:
+        items = _synthetic_items(args)                                                             # 7-atom records: the loader keeps the first six
+    train, val = _split(items, args)
+    kw = dict(k_neighbors=args.neighbours or 25, num_mpnn_layers=args.layers or 9, **rdesign_precisions(args.train_precision))
+    if args.dropout is not None:
+        kw["dropout"] = args.dropout
+    model = RNAModel(**kw).to(dev)
+    if world > 1:                                   # identical initial weights on every rank
+        for p in model.parameters():
+            dist.broadcast(p.data, 0)
+        model._weights_touched()
+    (opt,), (sched,) = model.configure_optimizers(fused=not args.torch_adam)
+    trainer = RDesignTrainer(model, opt, sched, world=world, rank=rank, seed=args.seed)
+    train_lens = [c.shape[0] for c, _ in train]
+    val_lens = [c.shape[0] for c, _ in val]
+    out = dict(epochs=[], n_train=len(train), n_val=len(val), best_epoch=None)
+    ckpt = os.path.join(args.out, "Final.pt") if args.out else None
+    if ckpt and rank == 0:
+        os.makedirs(args.out, exist_ok=True)
+    best, nan = float("-inf"), float("nan")
+    for epoch in range(args.epochs):
+        rec = trainer.run_epoch(train, train_lens, epoch, args.batch_size, args.max_nt)
+        if world > 1:       # whole-job rate: all nucleotides / slowest rank
+            t = torch.tensor([rec["seconds"], float(rec["nt"])], dtype=torch.float64, device=dev)
+            tmax = t.clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            rec["nt_per_s"] = float(t[1] / tmax[0])
+        rec.update(trainer.validate(val, val_lens, args.batch_size, args.max_nt) if val
+                   else dict(val_loss=nan, weighted_val_recovery_rate=nan, val_recovery_rate=nan))
+        out["epochs"].append(rec)
+        score = rec["val_recovery_rate"]
+        if not val or out["best_epoch"] is None or score > best:        # ModelCheckpoint(monitor='val_recovery_rate', mode='max'); no split: the last epoch
+            best, out["best_epoch"] = score, epoch
+            if ckpt and rank == 0:
+                save_checkpoint(ckpt, model, epoch=epoch, val_recovery_rate=float(score))
+        if rank == 0:
+            log(f"epoch {epoch}: train_loss {rec['train_loss']:.4f}  val_loss {rec['val_loss']:.4f}  val_recovery_rate {score:.4f} "
+                f"(weighted {rec['weighted_val_recovery_rate']:.4f})  {rec['nt_per_s']:.0f} nt/s end to end "
+                f"({rec['steps']} steps, {rec['seconds']:.2f} s, {world} rank(s))")
+    if ckpt:
+        if world > 1:
+            dist.barrier()
+        if out["best_epoch"] != args.epochs - 1:
+            model.load_state_dict(load_checkpoint(ckpt)[1]["state_dict"])
+        if rank == 0:
+            log(f"checkpoint of epoch {out['best_epoch']} written to {ckpt}")
+    if args.fit_xgb and rank == 0:
+        out["xgb"] = fit_xgb(model, train, train_lens, val, val_lens, args, dev, log, atoms=6)
+        if args.out:
+            model.xgb_readout.save_json(os.path.join(args.out, "XGB.json"))
+            log(f"tree read-out written to {os.path.join(args.out, 'XGB.json')}")
+    out["model"] = model
+    return out
+
+
+def fit_xgb(model, train, train_lens, val, val_lens, args, dev, log=print, atoms=7):
     """``XGBTrainer.on_fit_end``: embeddings of every valid training nucleotide -> tree read-out fitted on the device -> train and
     validation score; the embeddings never leave the device."""
     model.eval()
-    loader = lambda items, lens: PaddedLoader(items, bucket_batches(lens, args.batch_size, args.max_nt, seed=0), device=dev)
+    loader = lambda items, lens: PaddedLoader(items, bucket_batches(lens, args.batch_size, args.max_nt, seed=0), device=dev, atoms=atoms)
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     train_score = model.fit_xgb_readout(loader(train, train_lens), seed=args.seed)
