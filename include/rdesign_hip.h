@@ -17,7 +17,9 @@
  *
  * Conventions: as rnampnn_hip.h (device pointers, caller's stream, no synchronisation, 0 = success).
  *   X (B,T,6,3) f32 backbone atoms P, O5', C5', C4', C3', O3' (rdesign/utils/data.py:90-115, zero-filled padding),
- *   mask (B,T) f32 0/1 prefix masks.  Outputs are PACKED: the reference drops padded residues
+ *   mask (B,T) f32 0/1 prefix masks.  Padded rows of X and labels are never read: "zero-filled padding" says what the result
+ *   equals (the reference's, which does read those zeros), it is no precondition - the rows may hold anything, NaN included.
+ *   A workspace may hold anything on entry.  Outputs are PACKED: the reference drops padded residues
  *   (feature.py:206 `mask_select`), row p = (number of valid residues of RNAs < b) + t, N = mask.sum().
  */
 #ifndef RDESIGN_HIP_H
@@ -75,10 +77,11 @@ size_t rdesign_workspace_bytes(rdesign_handle h, int32_t B, int32_t T);
 
 /* RNAModel.forward (rdesign.py:82-88) followed by Readout (rdesign.py:104): every output is optional (null = skipped).
  *   h_V      (B*T,128) packed node embeddings after the MPNN stack (rows >= N untouched)
- *   logits   (B*T,4)   packed read-out logits
+ *   logits   (B*T,4)   packed read-out logits (rows >= N untouched)
  *   edge_index (B,T,k) i64: neighbour position inside the RNA per slot, -1 for padded residues and for the slots
  *            beyond the RNA's length (the edges the reference's `mask_attend` filter removes, feature.py:186-194)
- *   node_raw (B*T,101) / edge_raw (B*T*k,115): raw geometric features (feature.py:221-236), test taps */
+ *   node_raw (B*T,101) / edge_raw (B*T*k,115): raw geometric features (feature.py:221-236), test taps; rows >= N / >= N*k untouched,
+ *            the slots of edge_raw that edge_index marks -1 are zero */
 int rdesign_forward(rdesign_handle h, const float* X, const float* mask, int32_t B, int32_t T, float* h_V, float* logits,
                     int64_t* edge_index, float* node_raw, float* edge_raw, void* ws, size_t ws_bytes, void* stream);
 
@@ -93,7 +96,7 @@ int rdesign_readout(rdesign_handle h, const float* h_V, int32_t n_rows, float* l
  * Lightning's 32-bit default): a RDESIGN_PREC_BF16 handle gets RDESIGN_ERR_UNSUPPORTED (the two size queries return 0 and set the error text).
  *   labels   (B,T) i32 class ids 0..3, padding ignored
  *   dropout  in [0,1); the keep masks are a pure function of (seed, site, element) - csrc/rdesign_train.hip states the addressing
- *   loss     device scalar;  logits optional, packed (B*T,4)
+ *   loss     device scalar;  logits optional, packed (B*T,4), rows >= N untouched
  *   grad     rdesign_param_numel() floats laid out like the weight arena (rdesign_weight_info offsets), OVERWRITTEN; padding floats are zero
  * Bit-reproducible (no float atomics); rows are bounded by the 32-bit pair index of the dropout hash: B*T*k < 2^26, else RDESIGN_ERR_BAD_ARG.
  * rdesign_train_tape_bytes: the part of the workspace that holds the tape (a figure for reports). */

@@ -75,9 +75,15 @@ typedef struct RnaMpnnConfig {
 } RnaMpnnConfig;
 
 /* Inputs, outputs and optional intermediate taps of one forward pass.  Null taps are skipped.
- * All taps are written in the reference's padded layouts with the reference's padding values. */
+ * All taps are written in the reference's padded layouts with the reference's padding values: every requested tap is written
+ * in full, all B*T rows (the caller need not clear it).  A padded row (t >= n) holds 0 in logits, embedding, h0, e0, h_layer,
+ * e_layer, h_post and raw_emb, -1 in edge_index, and in raw the reference's 1e6 in the 21 distances and 0 in the 7 cosines.
+ * The workspace may hold anything on entry; nothing outside [workspace, workspace + rnampnn_workspace_bytes()) is written. */
 typedef struct RnaMpnnForwardIO {
-    const float* coords;      /* (B,T,7,3) */
+    const float* coords;      /* (B,T,7,3).  Of the padded rows (t >= n) exactly one belongs to the result: row t == n of an RNA with
+                                 n - 1 < k is the record of its phantom neighbour (the T_norm text below) and holds what the collate
+                                 left there, zeros.  No other padded row reaches an output: it may hold anything, NaN included
+                                 (row n is loaded but unused when n - 1 >= k; rows t > n are loaded and dropped). */
     const float* mask;        /* (B,T)     */
     int32_t B, T;
     int32_t T_norm;           /* the padded length this call stands for; 0 = T.  A data-parallel shard passes the
@@ -190,6 +196,8 @@ int rnampnn_sample_dev_seed(const float* logits, const float* mask, int32_t B, i
  *   rnampnn_loss_and_grad  - both in one call around the reference loss: cross_entropy(softmax(logits)[valid], label)
  *       (softmax twice, rnampnn.py:151-154), mean over valid nucleotides.  labels (B,T) int32 class ids (ignored on
  *       padding); loss: device scalar; logits optional; grad overwritten.
+ *   Padding: the padded rows of coords follow the rule of RnaMpnnForwardIO.coords; the padded rows of labels and of dlogits are
+ *   never read; logits come back with all B*T rows written, zeros on padding; floats of grad that belong to no parameter are 0.
  *   grad: flat f32 buffer of rnampnn_grad_numel() elements; parameter i of rnampnn_weight_info() lies at
  *   rnampnn_weight_offset(i) - one buffer = ONE RCCL all-reduce per step (what Lightning DDP does for the reference,
  *   rnampnn/utils/train.py:106-117).  Every cross-workgroup sum of the backward is an ordered two-stage reduction (no

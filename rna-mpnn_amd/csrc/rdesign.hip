@@ -417,6 +417,21 @@ void rd_mm(RdRun& r, const TRows& rows, const float* X, int ldx, const RdLin& l,
 }
 }  // namespace
 
+__global__ void __launch_bounds__(256) k_rd_copy_rows(const int* __restrict__ ntot, int mul, const float* __restrict__ src, int ld_src,
+                                                      float* __restrict__ dst, int ld_dst, int width) {
+    const size_t total = (size_t)*ntot * mul * width;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t row = i / width;
+        const int col = (int)(i - row * width);
+        dst[row * ld_dst + col] = src[row * ld_src + col];
+    }
+}
+void rd_copy_rows(const int* ntot, int mul, size_t maxrows, const float* src, int ld_src, float* dst, int ld_dst, int width, hipStream_t s) {
+    size_t blocks = (maxrows * width + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_rd_copy_rows, dim3((unsigned)(blocks ? blocks : 1)), dim3(256), 0, s, ntot, mul, src, ld_src, dst, ld_dst, width);
+}
+
 size_t rd_knn_lds_bytes(int T) { return (size_t)(3 + 4) * T * sizeof(float); }
 void rd_front(RdRun& r, const float* X, const float* mask, int64_t* edge_index) {
     RdWs& w = r.w;
@@ -465,8 +480,10 @@ extern "C" int rdesign_forward(rdesign_handle h, const float* X, const float* ma
         t_wimg_bind(c->wimg);
     }
     rd_front(r, X, mask, edge_index);
-    if (node_raw) RD_TRY(hipMemcpy2DAsync(node_raw, RD_NODE * sizeof(float), w.node_raw, RD_NODEP * sizeof(float), RD_NODE * sizeof(float), Nmax, hipMemcpyDeviceToDevice, s));
-    if (edge_raw) RD_TRY(hipMemcpy2DAsync(edge_raw, RD_EDGE * sizeof(float), w.edge_raw, RD_EDGEP * sizeof(float), RD_EDGE * sizeof(float), Nmax * K, hipMemcpyDeviceToDevice, s));
+    // the packed outputs are copied by row count N, known to the device only: rows >= N of the caller's tensors stay untouched (a copy of Nmax rows
+    // would hand out whatever the workspace held there)
+    if (node_raw) rd_copy_rows(r.pk.cu + B, 1, Nmax, w.node_raw, RD_NODEP, node_raw, RD_NODE, RD_NODE, s);
+    if (edge_raw) rd_copy_rows(r.pk.cu + B, K, Nmax * K, w.edge_raw, RD_EDGEP, edge_raw, RD_EDGE, RD_EDGE, s);
     // embeddings: Linear (101 / 115 inputs: exact-f32 GEMM on the K-major copy in both precisions) + Normalize
     t_gemm(r.rn(), w.node_raw, RD_NODEP, RD_NODEP, c->der + c->node_emb.wt, RD_H, rdp(c, c->node_emb.b), RD_H, w.hV2, RD_H, 0, s);
     rd_rownorm(r.pk.cu + B, 1, Nmax, w.hV2, nullptr, rdp(c, c->nn_g), rdp(c, c->nn_b), 0, w.hV, s);
@@ -536,8 +553,8 @@ extern "C" int rdesign_forward(rdesign_handle h, const float* X, const float* ma
     }
     t_wimg_bind(nullptr);
     if (r.bad) return rd_fail(RDESIGN_ERR_UNSUPPORTED, "bf16 path: a GEMM variant this configuration needs is not built");
-    if (h_V) RD_TRY(hipMemcpyAsync(h_V, w.hV, Nmax * RD_H * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (logits) RD_TRY(hipMemcpyAsync(logits, w.logits, Nmax * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (h_V) rd_copy_rows(r.pk.cu + B, 1, Nmax, w.hV, RD_H, h_V, RD_H, RD_H, s);
+    if (logits) rd_copy_rows(r.pk.cu + B, 1, Nmax, w.logits, 4, logits, 4, 4, s);
     RD_TRY(hipGetLastError());
     return RDESIGN_OK;
 }

@@ -55,6 +55,9 @@ size_t rd_knn_lds_bytes(int T);
 // row normalisations on 128-wide rows: mode 0 functional.Normalize, mode 1 nn.LayerNorm(x + res)
 void rd_rownorm(const int* ntot, int mul, size_t maxrows, const float* x, const float* res, const float* gain, const float* bias, int mode,
                 float* y, hipStream_t s, tb16* yb = nullptr);
+// packed output: rows [0, *ntot * mul) of src (row stride ld_src floats) -> dst (row stride ld_dst), `width` floats each.  The row count is the device's
+// (no host sync), so rows >= N of the caller's tensor are left untouched; maxrows sizes the grid.
+void rd_copy_rows(const int* ntot, int mul, size_t maxrows, const float* src, int ld_src, float* dst, int ld_dst, int width, hipStream_t s);
 
 // ---- shared by the two training steps (defined in rdesign_train.hip)
 #define RDT_CE_BLOCKS 1024

@@ -282,7 +282,7 @@ extern "C" int rdesign_loss_and_grad(rdesign_handle h, const float* X, const flo
             fwd(rn, x, ld, c->readout[j], 0, c->readout[j].in, true, j + 1 < R ? w.rpre[j] : w.logits, c->readout[j].out);
         }
     }
-    if (logits) launch_copy_bytes(logits, w.logits, Nmax * 4 * sizeof(float), s);
+    if (logits) rd_copy_rows(pk.cu + B, 1, Nmax, w.logits, 4, logits, 4, 4, s);      // rows >= N of the caller's tensor stay untouched
 
     // ================================================================ loss and backward
     rdt_ce_loss(pk, w.logits, labels, w.dlogits, w.part, loss, s);
