@@ -7,6 +7,8 @@
 // Layout: packed residues (row p = cu[b] + t) as in the rnampnn path; the GEMMs are the training path's (kernels_train.hip):
 // exact f32 (`t_gemm`, K-major weight copies) or bf16 MFMA with f32 accumulate (`tm_gemm_nt`, weights as stored, GELU fused into the
 // operand load).  The first message Linear is factored W.[h_E | h_i | h_j] = W_e.h_E + P[i] + Q[j] like the rnampnn kernels.
+// rd_run (the run set-up over a carved workspace) and rd_mm (the node-level Linear dispatch, dropout-aware) also serve the training steps
+// (rdesign_train.hip, rdesign_train_bf16.hip); the inference forward passes the no-dropout TDrop and its in-place GELU scratch.
 // PARITY: pinned to the reference's own modules in eval mode (graph, raw features, h_V, logits) by tests/golden/rdesign_*.npz - see oracle/rdesign_oracle.py.
 #include "rdesign_internal.h"
 
@@ -403,19 +405,22 @@ extern "C" size_t rdesign_workspace_bytes(rdesign_handle h, int32_t B, int32_t T
     return rd_carve(h, B, (size_t)B * T, nullptr, nullptr);
 }
 
-namespace {
-// Y = [beta Y] + act(X)[:, 0:Kc] . W[:, k0:k0+Kc]^T + bias        (act = GELU of the stored pre-activation when `gelu_in`)
+RdRun rd_run(rdesign_ctx* c, void* stream, bool mixed, const RdWs& w, int B, int T) {
+    RdRun r;
+    r.c = c; r.s = (hipStream_t)stream; r.mixed = mixed; r.nodrop = TDrop{0ull, 0u, 1.f, nullptr}; r.K = c->cfg.k_neighbors; r.w = w;
+    r.pk.len = w.len; r.pk.cu = w.cu; r.pk.node_b = w.node_b; r.pk.B = B; r.pk.T = T; r.pk.Nmax = B * T; r.pk.packed_in = 0;
+    return r;
+}
 void rd_mm(RdRun& r, const TRows& rows, const float* X, int ldx, const RdLin& l, int k0, int Kc, bool use_bias, float* Y, int ldy, int beta,
-           bool gelu_in, float* scratch) {
+           bool gelu_in, float* scratch, const TDrop& dr, unsigned site) {
     rdesign_ctx* c = r.c;
     const float* bias = use_bias ? rdp(c, l.b) : nullptr;
-    if (r.mixed && tm_gemm_nt(rows, X, ldx, Kc, rdp(c, l.w) + k0, l.in, bias, l.out, Y, ldy, beta, gelu_in, r.nodrop, 0u, r.s)) return;
+    if (r.mixed && tm_gemm_nt(rows, X, ldx, Kc, rdp(c, l.w) + k0, l.in, bias, l.out, Y, ldy, beta, gelu_in, dr, site, r.s)) return;
     const float* xin = X;
-    if (gelu_in) { t_gelu_fwd(rows, X, scratch, ldx, r.nodrop, 0u, r.s); xin = scratch; }      // (ldx == width of the activation here)
+    if (gelu_in) { t_gelu_fwd(rows, X, scratch, ldx, dr, site, r.s); xin = scratch; }
     const int Kp = (Kc + 3) / 4 * 4;
     t_gemm(rows, xin, ldx, Kp, c->der + l.wt + (size_t)k0 * l.out, l.out, bias, l.out, Y, ldy, beta, r.s);
 }
-}  // namespace
 
 __global__ void __launch_bounds__(256) k_rd_copy_rows(const int* __restrict__ ntot, int mul, const float* __restrict__ src, int ld_src,
                                                       float* __restrict__ dst, int ld_dst, int width) {
@@ -468,12 +473,11 @@ extern "C" int rdesign_forward(rdesign_handle h, const float* X, const float* ma
     if (((uintptr_t)ws & 255) != 0) return rd_fail(RDESIGN_ERR_BAD_ARG, "workspace must be 256-byte aligned");
     const size_t knn_lds = rd_knn_lds_bytes(T);
     if (knn_lds > 160 * 1024 - 256) return rd_fail(RDESIGN_ERR_UNSUPPORTED, "max_len %d too long for the LDS-resident k-NN row", T);
-    RdRun r;
-    r.c = c; r.s = (hipStream_t)stream; r.mixed = c->cfg.precision == RDESIGN_PREC_BF16; r.nodrop = TDrop{0ull, 0u, 1.f}; r.K = K;
-    rd_carve(c, B, Nmax, (char*)ws, &r.w);
+    RdWs carved;
+    rd_carve(c, B, Nmax, (char*)ws, &carved);
+    RdRun r = rd_run(c, stream, c->cfg.precision == RDESIGN_PREC_BF16, carved, B, T);
     RdWs& w = r.w;
     hipStream_t s = r.s;
-    r.pk.len = w.len; r.pk.cu = w.cu; r.pk.node_b = w.node_b; r.pk.B = B; r.pk.T = T; r.pk.Nmax = (int)Nmax; r.pk.packed_in = 0;
     if (r.mixed) {      // weights are static between finalize calls: the images are rebuilt once, blocks first seen in this call build their own
         if (!c->wimg) c->wimg = t_wimg_create(256);
         if (c->wimg && (!c->wimg_fresh || t_wimg_pending(c->wimg) > 0)) { t_wimg_refresh(c->wimg, s); c->wimg_fresh = true; }
@@ -514,14 +518,14 @@ extern "C" int rdesign_forward(rdesign_handle h, const float* X, const float* ma
             }
             hipLaunchKernelGGL(k_rd_segsum_b, dim3((unsigned)((Nmax + 3) / 4)), dim3(256), 0, s, r.pk, K, w.nbr, cur, 1.0f / 30.0f, w.dh);
         } else {
-        rd_mm(r, r.rn(), w.hV, RD_H, L.msg[0], RD_H, RD_H, true, w.pq, 256, 0, false, nullptr);            // P = h_V W_c^T + b
-        rd_mm(r, r.rn(), w.hV, RD_H, L.msg[0], 2 * RD_H, RD_H, false, w.pq + RD_H, 256, 0, false, nullptr); // Q = h_V W_n^T
-        rd_mm(r, r.re(), w.hE, RD_H, L.msg[0], 0, RD_H, false, w.E1, RD_H, 0, false, nullptr);
+        rd_mm(r, r.rn(), w.hV, RD_H, L.msg[0], RD_H, RD_H, true, w.pq, 256, 0, false, nullptr, r.nodrop, 0u);            // P = h_V W_c^T + b
+        rd_mm(r, r.rn(), w.hV, RD_H, L.msg[0], 2 * RD_H, RD_H, false, w.pq + RD_H, 256, 0, false, nullptr, r.nodrop, 0u); // Q = h_V W_n^T
+        rd_mm(r, r.re(), w.hE, RD_H, L.msg[0], 0, RD_H, false, w.E1, RD_H, 0, false, nullptr, r.nodrop, 0u);
         t_edge_add_pq(r.pk, K, w.nbr, w.pq, w.E1, s);
         float* cur = w.E1;
         float* nxt = w.E2;
         for (size_t i = 1; i < L.msg.size(); ++i) {                                                         // GELU of the previous Linear fused into / before this one
-            rd_mm(r, r.re(), cur, RD_H, L.msg[i], 0, RD_H, true, nxt, RD_H, 0, true, cur == w.E1 ? w.E1 : w.E2);
+            rd_mm(r, r.re(), cur, RD_H, L.msg[i], 0, RD_H, true, nxt, RD_H, 0, true, cur == w.E1 ? w.E1 : w.E2, r.nodrop, 0u);
             float* t = cur; cur = nxt; nxt = t;
         }
         hipLaunchKernelGGL(k_rd_segsum, dim3((unsigned)Nmax), dim3(128), 0, s, r.pk, K, w.nbr, cur, 1.0f / 30.0f, w.dh);
@@ -534,7 +538,7 @@ extern "C" int rdesign_forward(rdesign_handle h, const float* X, const float* ma
         for (size_t i = 0; i < L.dense.size(); ++i) {
             const bool last = i + 1 == L.dense.size();
             float* dst = last ? w.dh : bufs[i & 1];
-            rd_mm(r, r.rn(), x, ld, L.dense[i], 0, L.dense[i].in, true, dst, L.dense[i].out, 0, i > 0, const_cast<float*>(x));
+            rd_mm(r, r.rn(), x, ld, L.dense[i], 0, L.dense[i].in, true, dst, L.dense[i].out, 0, i > 0, const_cast<float*>(x), r.nodrop, 0u);
             x = dst; ld = L.dense[i].out;
         }
         rd_rownorm(r.pk.cu + B, 1, Nmax, w.hV2, w.dh, rdp(c, L.n2w), rdp(c, L.n2b), 1, w.hV, s);            // norm2(h_V + dense(h_V))
@@ -547,7 +551,7 @@ extern "C" int rdesign_forward(rdesign_handle h, const float* X, const float* ma
         for (size_t i = 0; i < c->readout.size(); ++i) {
             const bool last = i + 1 == c->readout.size();
             float* dst = last ? w.logits : bufs[i & 1];
-            rd_mm(r, r.rn(), x, ld, c->readout[i], 0, c->readout[i].in, true, dst, c->readout[i].out, 0, i > 0, const_cast<float*>(x));
+            rd_mm(r, r.rn(), x, ld, c->readout[i], 0, c->readout[i].in, true, dst, c->readout[i].out, 0, i > 0, const_cast<float*>(x), r.nodrop, 0u);
             x = dst; ld = c->readout[i].out;
         }
     }
@@ -566,10 +570,9 @@ extern "C" int rdesign_readout(rdesign_handle h, const float* h_V, int32_t n_row
     if (!h->arena || !h->finalized) return rd_fail(RDESIGN_ERR_WEIGHTS, "weights not set / not finalized");
     if (ws_bytes < rd_carve(h, 1, (size_t)n_rows, nullptr, nullptr, false)) return rd_fail(RDESIGN_ERR_WORKSPACE, "workspace too small");
     if (((uintptr_t)ws & 255) != 0) return rd_fail(RDESIGN_ERR_BAD_ARG, "workspace must be 256-byte aligned");
-    RdRun r;
-    r.c = h; r.s = (hipStream_t)stream; r.mixed = h->cfg.precision == RDESIGN_PREC_BF16; r.nodrop = TDrop{0ull, 0u, 1.f}; r.K = h->cfg.k_neighbors;
-    rd_carve(h, 1, (size_t)n_rows, (char*)ws, &r.w, false);
-    r.pk.len = r.w.len; r.pk.cu = r.w.cu; r.pk.node_b = r.w.node_b; r.pk.B = 1; r.pk.T = n_rows; r.pk.Nmax = n_rows; r.pk.packed_in = 0;
+    RdWs carved;
+    rd_carve(h, 1, (size_t)n_rows, (char*)ws, &carved, false);
+    RdRun r = rd_run(h, stream, h->cfg.precision == RDESIGN_PREC_BF16, carved, 1, n_rows);
     hipLaunchKernelGGL(k_rd_seti, dim3(1), dim3(1), 0, r.s, r.w.cu + 1, (int)n_rows);
     const float* x = h_V;
     int ld = RD_H;
@@ -577,7 +580,7 @@ extern "C" int rdesign_readout(rdesign_handle h, const float* h_V, int32_t n_row
     for (size_t i = 0; i < h->readout.size(); ++i) {
         const bool last = i + 1 == h->readout.size();
         float* dst = last ? logits : bufs[i & 1];
-        rd_mm(r, r.rn(), x, ld, h->readout[i], 0, h->readout[i].in, true, dst, h->readout[i].out, 0, i > 0, const_cast<float*>(x));
+        rd_mm(r, r.rn(), x, ld, h->readout[i], 0, h->readout[i].in, true, dst, h->readout[i].out, 0, i > 0, const_cast<float*>(x), r.nodrop, 0u);
         x = dst; ld = h->readout[i].out;
     }
     RD_TRY(hipGetLastError());

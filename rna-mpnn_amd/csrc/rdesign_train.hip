@@ -1,14 +1,15 @@
-// Exact-f32 TRAINING STEP of the `rdesign` model (C ABI: include/rdesign_hip.h, rdesign_loss_and_grad): `training_step` + `loss.backward()` of the
+// TRAINING STEP of the `rdesign` model (C ABI: include/rdesign_hip.h, rdesign_loss_and_grad[_ex]): `training_step` + `loss.backward()` of the
 // reference (rdesign/model/rdesign.py:95-104) in one call.  The reference's rdesign trainer sets no `precision` (rdesign/utils/train.py:107-115), so
-// f32 IS its arithmetic.  Forward = the f32 branch of rdesign_forward (rdesign.hip) with every pre-activation kept in the workspace (the tape) and
-// dropout after every GELU the reference follows with nn.Dropout (mpnn.py:16-18,24-26, functional.py:113-121); loss = CrossEntropyLoss()(logits, S)
-// over the valid residues (ONE softmax, mean over N); backward walks the tape with the trainer's f32 blocks (kernels_train.h: t_gemm, t_gemm_tn,
-// t_colsum, t_gelu_fwd / t_gelu_bwd, t_build_reverse, t_edge_pq_bwd) and the kernels below.  The gradient lands in ONE flat buffer laid out like
-// the weight arena.  No float atomics: every cross-workgroup sum is an ordered reduction (red_begin .. red_end) or a fixed-order per-block partial, so
-// two calls give bit-identical results.  No runtime fill / copy nodes: launch_zero_bytes / launch_copy_bytes.
-// Dropout addressing (restated by tests/_rdesign_train_ref.py): the TDrop counter hash; site = index of the Dropout module in forward order from 1 -
-// layer l, message Linear i: 1 + l (M + D) + i; layer l, hidden dense Linear i: 1 + l (M + D) + M + i; hidden read-out Linear j: 1 + L (M + D) + j;
-// element = row * width + channel, row = packed node row p or packed edge row p K + slot.
+// f32 IS its arithmetic and RDESIGN_TRAIN_F32 the default; RDESIGN_TRAIN_BF16_MIXED is the opt-in step of rdesign_train_bf16.hip.  Forward = the
+// forward of rdesign.hip with every pre-activation kept in the workspace (the tape) and dropout after every GELU the reference follows with
+// nn.Dropout (mpnn.py:16-18,24-26, functional.py:113-121); loss = CrossEntropyLoss()(logits, S) over the valid residues (ONE softmax, mean over N);
+// backward walks the tape.  The gradient lands in ONE flat buffer laid out like the weight arena.  No float atomics: every cross-workgroup sum is
+// an ordered reduction (red_begin .. red_end) or a fixed-order per-block partial, so two calls give bit-identical results.  No runtime fill / copy
+// nodes: launch_zero_bytes / launch_copy_bytes.
+// Layout of this file: the kernels of the f32 step and the cross-entropy; what both steps share (rdesign_internal.h) - row limits, the workspace
+// both carve alike, the argument checks and run set-up, the backward companions of the node-level Linear dispatch (rd_mm, rdesign.hip), the node
+// side (dense FFN and read-out forward / backward, node embedding backward), loss and the reduction bracket; the f32 edge sequence, readable top to
+// bottom without a precision flag (its bf16-mixed twin: rdesign_train_bf16.hip); the one dispatch on `flags` and the C entry points.
 // PARITY: the p = 0 loss and gradients are pinned to the reference's own float64 autograd (tests/golden/rdesign_*.npz); the dropout masks are not
 // (torch's RNG cannot be matched): with dropout the checker is the restatement tests/_rdesign_train_ref.py, itself pinned at p = 0.
 #include "rdesign_internal.h"
@@ -18,7 +19,8 @@
 // One wave per 128-wide row, two channels per lane; the row statistics are recomputed from the taped input v = x (+ res).
 //   y = gain d / sig + bias, d = v - mean(v);  mode 0 (functional.Normalize): sig = sqrt(q / 127 + 1e-6) + 1e-6;  mode 1 (LayerNorm): sig = sqrt(q / 128 + 1e-5)
 //   with g = dy gain, r = the square root in sig, n = 127 | 128:   dv = (g - mean(g)) / sig - d sum(g d) / (n r sig^2)
-// t = dy d / sig: its column sums are d gain (the column sums of dy are d bias); both go through the ordered reduction path (t_colsum).
+// t = dy d / sig: its column sums are d gain (the column sums of dy are d bias); both go through the ordered reduction path (t_colsum).  (The
+// bf16-mixed step folds per-block partials instead - k_rdb_rownorm_bwd; merging the two would change the f32 bits.)
 __global__ void __launch_bounds__(256) k_rdt_rownorm_bwd(const int* __restrict__ ntot_p, int mul, const float* __restrict__ x, const float* __restrict__ res,
                                                          const float* __restrict__ dy, const float* __restrict__ gain, int mode,
                                                          float* __restrict__ dx, float* __restrict__ t) {
@@ -127,263 +129,263 @@ __global__ void k_rdt_loss_sum(const float* __restrict__ part, int n, float* __r
     for (int i = 0; i < n; ++i) s += part[i];
     *loss = s;
 }
-void rdt_ce_loss(const PackInfo& pk, const float* logits, const int32_t* labels, float* dlogits, float* part, float* loss, hipStream_t s) {
+static void rdt_ce_loss(const PackInfo& pk, const float* logits, const int32_t* labels, float* dlogits, float* part, float* loss, hipStream_t s) {
     int grid = (pk.Nmax + 255) / 256;
     if (grid > RDT_CE_BLOCKS) grid = RDT_CE_BLOCKS;
     hipLaunchKernelGGL(k_rdt_ce, dim3(grid), dim3(256), 0, s, pk, logits, labels, dlogits, part);
     hipLaunchKernelGGL(k_rdt_loss_sum, dim3(1), dim3(1), 0, s, part, grid, loss);
 }
 
-// ------------------------------------------------------------------------------------------ workspace
+// ------------------------------------------------------------------------------------------ shared by the two steps: workspace, checks, run
 int rdt_dm(const rdesign_ctx* c) {
     int d = RD_H;
     if (c->cfg.dim_dense_layers > d) d = c->cfg.dim_dense_layers;
     if (c->cfg.num_readout_layers > 1 && c->cfg.readout_hidden_dim > d) d = c->cfg.readout_hidden_dim;
     return d;
 }
-int rdt_check_rows(rdesign_handle h, int32_t B, int32_t T) {
-    if (B <= 0 || T <= 0) return rd_fail(RDESIGN_ERR_BAD_ARG, "training step: non-positive B/T");
-    // 32-bit element-pair indices of the dropout hash (kernels_train.h) and 32-bit edge-row indexing: rows * width / 2 < 2^32
-    if ((long long)B * T * h->cfg.k_neighbors >= (1LL << 26) || (long long)B * T * rdt_dm(h) >= (1LL << 32))
-        return rd_fail(RDESIGN_ERR_BAD_ARG, "row count out of range for the training path (B*T*k < 2^26); split the batch");
-    return RDESIGN_OK;
-}
-namespace {
-struct RdtLayer { std::vector<float*> msg, dense; float *dh, *h1, *y; };      // pre-activations of the message / hidden dense Linears, dh, norm1 output, dense output
-struct RdtWs {
-    RdWs f;                                  // the forward's buffers: features, k-NN table, h_E, P/Q table; E1 / E2 are edge scratch of the backward
-    float *embN, *embE;                      // tape: embedding Linear outputs (inputs of the two Normalize)
-    std::vector<float*> hv;                  // tape: h_V entering layer l (hv[L] = the stack's output)
-    std::vector<RdtLayer> layers;
-    std::vector<float*> rpre;                // tape: hidden read-out pre-activations
-    float *logits, *dlogits, *part;
-    float *gH, *gX, *bA, *bB, *bC;           // node-sized gradient / scratch buffers ([N][128] and [N][Dm])
-    float *eS, *dhE;                         // edge-sized: third scratch buffer, d h_E accumulated over the layers
-    int *rdeg, *rstart, *rfill, *rlist;      // reverse adjacency (t_build_reverse)
-    TScratch sc;                             // arena of the ordered reductions
-    size_t tape_bytes;
-};
-size_t rdt_carve(const rdesign_ctx* c, int B, size_t Nmax, char* base, RdtWs* out) {
-    RdtWs tmp;
-    RdtWs& w = out ? *out : tmp;
-    size_t off = rd_carve(c, B, Nmax, base, &w.f);
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return base ? base + o : (char*)nullptr; };
-    auto tf = [&](size_t floats) { return (float*)take(floats * sizeof(float)); };
+void rdt_carve(const rdesign_ctx* c, int B, size_t Nmax, char* base, RdtWs& w) {
+    w.base = base; w.tape_bytes = 0;
+    w.off = rd_carve(c, B, Nmax, base, &w.f);
     const RDesignConfig& g = c->cfg;
-    const size_t E = Nmax * g.k_neighbors, NH = Nmax * RD_H, EH = E * RD_H, Dm = (size_t)rdt_dm(c);
-    const size_t tape0 = off;
-    w.embN = tf(NH); w.embE = tf(EH);
+    const size_t E = Nmax * g.k_neighbors, NH = Nmax * RD_H, Dm = (size_t)rdt_dm(c);
+    w.embN = w.tf(NH, true);
     w.hv.clear(); w.layers.clear(); w.rpre.clear();
-    for (int l = 0; l <= g.num_mpnn_layers; ++l) w.hv.push_back(tf(NH));
+    for (int l = 0; l <= g.num_mpnn_layers; ++l) w.hv.push_back(w.tf(NH, true));
     for (int l = 0; l < g.num_mpnn_layers; ++l) {
         RdtLayer L;
-        for (int i = 0; i < g.num_message_layers; ++i) L.msg.push_back(tf(EH));
-        for (int i = 0; i < g.num_dense_layers; ++i) L.dense.push_back(tf(Nmax * g.dim_dense_layers));
-        L.dh = tf(NH); L.h1 = tf(NH); L.y = tf(NH);
+        for (int i = 0; i < g.num_dense_layers; ++i) L.dense.push_back(w.tf(Nmax * g.dim_dense_layers, true));
+        L.dh = w.tf(NH, true); L.h1 = w.tf(NH, true); L.y = w.tf(NH, true);
         w.layers.push_back(L);
     }
-    for (int j = 0; j + 1 < g.num_readout_layers; ++j) w.rpre.push_back(tf(Nmax * g.readout_hidden_dim));
-    w.logits = tf(Nmax * 4);
-    w.tape_bytes = off - tape0;
-    w.dlogits = tf(Nmax * 4); w.part = tf(RDT_CE_BLOCKS);
-    w.gH = tf(NH); w.gX = tf(NH); w.bA = tf(Nmax * Dm); w.bB = tf(Nmax * Dm); w.bC = tf(Nmax * Dm);
-    w.eS = tf(EH); w.dhE = tf(EH);
-    w.rdeg = (int*)take((Nmax + 1) * sizeof(int)); w.rstart = (int*)take((Nmax + 1) * sizeof(int)); w.rfill = (int*)take((Nmax + 1) * sizeof(int));
-    w.rlist = (int*)take((E + 1) * sizeof(int));
+    for (int j = 0; j + 1 < g.num_readout_layers; ++j) w.rpre.push_back(w.tf(Nmax * g.readout_hidden_dim, true));
+    w.logits = w.tf(Nmax * 4, true);
+    w.dlogits = w.tf(Nmax * 4); w.part = w.tf(RDT_CE_BLOCKS);
+    w.gH = w.tf(NH); w.gX = w.tf(NH); w.bA = w.tf(Nmax * Dm); w.bB = w.tf(Nmax * Dm); w.bC = w.tf(Nmax * Dm);
+    w.rdeg = (int*)w.take((Nmax + 1) * sizeof(int)); w.rstart = (int*)w.take((Nmax + 1) * sizeof(int)); w.rfill = (int*)w.take((Nmax + 1) * sizeof(int));
+    w.rlist = (int*)w.take((E + 1) * sizeof(int));
     w.sc.floats = RED_VIEW;                  // one producer budget: no single extent is larger (kernels_train.h)
-    w.sc.p = tf(w.sc.floats);
-    return off;
+    w.sc.p = w.tf(w.sc.floats);
 }
-int rdt_check(rdesign_handle h, int32_t B, int32_t T) {
-    if (!h) return rd_fail(RDESIGN_ERR_BAD_ARG, "null handle");
-    if (h->cfg.precision != RDESIGN_PREC_F32)
-        return rd_fail(RDESIGN_ERR_UNSUPPORTED, "the rdesign training step is built for the exact-f32 path only (create the handle with RDESIGN_PREC_F32)");
-    return rdt_check_rows(h, B, T);
-}
-}  // namespace
-
-extern "C" size_t rdesign_train_workspace_bytes(rdesign_handle h, int32_t B, int32_t T) {
-    if (rdt_check(h, B, T) != RDESIGN_OK) return 0;
-    return rdt_carve(h, B, (size_t)B * T, nullptr, nullptr);
-}
-
-extern "C" int rdesign_loss_and_grad(rdesign_handle h, const float* X, const float* mask, const int32_t* labels, int32_t B, int32_t T, float dropout,
-                                     uint64_t seed, float* loss, float* logits, float* grad, void* ws, size_t ws_bytes, void* stream) {
-    if (const int rc = rdt_check(h, B, T)) return rc;
-    if (!X || !mask || !labels || !loss || !grad || !ws) return rd_fail(RDESIGN_ERR_BAD_ARG, "rdesign_loss_and_grad: null pointer");
-    if (!(dropout >= 0.f && dropout < 1.f)) return rd_fail(RDESIGN_ERR_BAD_ARG, "dropout must be in [0, 1)");
+int rdt_begin(RdtStep& t, rdesign_handle h, const RdtArgs& a, bool mixed, size_t need, const char* who) {
+    if (!a.X || !a.mask || !a.labels || !a.loss || !a.grad || !a.ws) return rd_fail(RDESIGN_ERR_BAD_ARG, "%s: null pointer", who);
+    if (!(a.dropout >= 0.f && a.dropout < 1.f)) return rd_fail(RDESIGN_ERR_BAD_ARG, "dropout must be in [0, 1)");
     if (!h->arena) return rd_fail(RDESIGN_ERR_WEIGHTS, "no weight arena set");
     if (!h->finalized) return rd_fail(RDESIGN_ERR_WEIGHTS, "weights not finalized (call rdesign_finalize_weights)");
-    if (((uintptr_t)grad & 15) != 0) return rd_fail(RDESIGN_ERR_BAD_ARG, "gradient buffer must be 16-byte aligned");
+    if (((uintptr_t)a.grad & 15) != 0) return rd_fail(RDESIGN_ERR_BAD_ARG, "gradient buffer must be 16-byte aligned");
+    if (a.ws_bytes < need) return rd_fail(RDESIGN_ERR_WORKSPACE, "training workspace %zu bytes < required %zu", a.ws_bytes, need);
+    if (((uintptr_t)a.ws & 255) != 0) return rd_fail(RDESIGN_ERR_BAD_ARG, "workspace must be 256-byte aligned");
+    if (rd_knn_lds_bytes(a.T) > 160 * 1024 - 256) return rd_fail(RDESIGN_ERR_UNSUPPORTED, "max_len %d too long for the LDS-resident k-NN row", a.T);
+    t.r = rd_run(h, a.stream, mixed, t.w.f, a.B, a.T);
+    t.dr = t_drop(a.dropout, a.seed);
+    t.grad = a.grad;
+    t.L = h->cfg.num_mpnn_layers; t.M = h->cfg.num_message_layers; t.D = h->cfg.num_dense_layers;
+    return RDESIGN_OK;
+}
+
+// ------------------------------------------------------------------------------------------ shared: node-level Linear backward, node side
+void rd_mm_wb(RdRun& r, const TRows& rows, const float* dy, const RdLin& l, const float* x, bool act, float* scratch, const TDrop& dr, unsigned site,
+              float* grad) {
+    float *dW = grad + r.c->raw[l.w].off, *db = grad + r.c->raw[l.b].off;
+    if (r.mixed && tm_gemm_tn(rows, dy, l.out, l.out, x, l.in, l.in, dW, l.in, act, dr, site, db, r.s)) return;
+    if (act) { t_gelu_fwd(rows, x, scratch, l.in, dr, site, r.s); x = scratch; }
+    t_gemm_tn(rows, dy, l.out, l.out, x, l.in, l.in, dW, l.in, r.s);
+    t_colsum(rows, dy, l.out, l.out, db, r.s);
+}
+void rd_mm_dx(RdRun& r, const TRows& rows, const float* dy, const RdLin& l, float* dx, int beta, const float* pre, float* scratch, const TDrop& dr,
+              unsigned site) {
+    const float* W = rdp(r.c, l.w);          // as nn.Linear stores it, [out][in]: K-major for this product
+    if (r.mixed && tm_gemm_nn(rows, dy, l.out, l.out, W, l.in, nullptr, l.in, dx, l.in, beta, pre, l.in, dr, site, r.s)) return;
+    t_gemm(rows, dy, l.out, l.out, W, l.in, nullptr, l.in, pre ? scratch : dx, l.in, pre ? 0 : beta, r.s);
+    if (pre) t_gelu_bwd(rows, scratch, pre, dx, l.in, dr, site, r.s);
+}
+void rdt_ffn_fwd(RdtStep& t, const std::vector<RdLin>& lin, const float* x, const std::vector<float*>& pre, float* out, unsigned site0) {
+    const int n = (int)lin.size();
+    for (int i = 0; i < n; ++i) {            // (the GELU of a taped pre-activation goes to w.bC: the tape is never overwritten)
+        float* y = i + 1 < n ? pre[i] : out;
+        rd_mm(t.r, t.r.rn(), x, lin[i].in, lin[i], 0, lin[i].in, true, y, lin[i].out, 0, i > 0, t.w.bC, t.dr, i > 0 ? site0 + i - 1 : 0u);
+        x = y;
+    }
+}
+void rdt_ffn_bwd(RdtStep& t, const std::vector<RdLin>& lin, const float* x, const std::vector<float*>& pre, const float* dy, float* dx, bool acc,
+                 unsigned site0) {
+    const TRows rn = t.r.rn();
+    float* bufs[2] = {t.w.bA, t.w.bB};       // d pre alternates between the two: a Linear reads its dy while it writes its dx
+    for (int i = (int)lin.size() - 1; i >= 0; --i) {
+        const unsigned site = i > 0 ? site0 + i - 1 : 0u;
+        rd_mm_wb(t.r, rn, dy, lin[i], i > 0 ? pre[i - 1] : x, i > 0, t.w.bC, t.dr, site, t.grad);
+        if (i > 0) { float* d = bufs[i & 1]; rd_mm_dx(t.r, rn, dy, lin[i], d, 0, pre[i - 1], t.w.bC, t.dr, site); dy = d; }
+        else rd_mm_dx(t.r, rn, dy, lin[i], dx, acc && dy != dx ? 1 : 0, nullptr, nullptr, t.dr, 0u);
+    }
+}
+void rdt_node_emb_bwd(RdtStep& t) {         // 101 inputs: the f32 blocks in both precisions (nothing flows into the raw features)
+    const rdesign_ctx* c = t.r.c;
+    t_gemm_tn(t.r.rn(), t.w.gX, RD_H, RD_H, t.w.f.node_raw, RD_NODEP, RD_NODE, t.G(c->node_emb.w), RD_NODE, t.r.s);
+    t_colsum(t.r.rn(), t.w.gX, RD_H, RD_H, t.G(c->node_emb.b), t.r.s);
+}
+void rdt_loss(RdtStep& t, const RdtArgs& a) {
+    const PackInfo& pk = t.r.pk;
+    if (a.logits) rd_copy_rows(pk.cu + pk.B, 1, pk.Nmax, t.w.logits, 4, a.logits, 4, 4, t.r.s);      // rows >= N of the caller's tensor stay untouched
+    rdt_ce_loss(pk, t.w.logits, a.labels, t.w.dlogits, t.w.part, a.loss, t.r.s);
+    launch_zero_bytes(t.grad, t.r.c->raw_floats * sizeof(float), t.r.s);
+    red_begin(t.w.sc, t.r.s);
+}
+int rdt_end(const char* who) {
+    return red_end() ? RDESIGN_OK : rd_fail(RDESIGN_ERR_HIP, "%s: an ordered reduction was refused (reduction arena)", who);
+}
+
+// ------------------------------------------------------------------------------------------ the exact-f32 step: edge sequence around the node side
+namespace {
+// f32 [E][128]; tape: edge embedding Linear output (input of Normalize), message pre-activations per layer; scratch: a third edge buffer next to
+// f.E1 / f.E2, d h_E accumulated over the layers
+struct RdtEdges { float* embE; std::vector<std::vector<float*>> msg; float *eS, *dhE; };
+size_t rdt_f32_carve(const rdesign_ctx* c, int B, size_t Nmax, char* base, RdtWs& w, RdtEdges& e) {
+    rdt_carve(c, B, Nmax, base, w);
+    const size_t EH = Nmax * c->cfg.k_neighbors * RD_H;
+    e.embE = w.tf(EH, true);
+    e.msg.assign(c->cfg.num_mpnn_layers, {});
+    for (auto& m : e.msg)
+        for (int i = 0; i < c->cfg.num_message_layers; ++i) m.push_back(w.tf(EH, true));
+    e.eS = w.tf(EH); e.dhE = w.tf(EH);
+    return w.off;
+}
+int rdt_f32_step(rdesign_handle h, const RdtArgs& a, size_t* sizes) {
+    static const char* const who = "rdesign_loss_and_grad";
+    RdtStep t;
+    RdtEdges e;
+    const size_t Nmax = (size_t)a.B * a.T;
+    const size_t need = rdt_f32_carve(h, a.B, Nmax, (char*)a.ws, t.w, e);      // (addresses only: checked before anything is launched)
+    if (sizes) { sizes[0] = need; sizes[1] = t.w.tape_bytes; return RDESIGN_OK; }
+    if (const int rc = rdt_begin(t, h, a, false, need, who)) return rc;
     rdesign_ctx* c = h;
-    const RDesignConfig& g = c->cfg;
-    const size_t Nmax = (size_t)B * T;
-    const int K = g.k_neighbors, L = g.num_mpnn_layers, M = g.num_message_layers, D = g.num_dense_layers, DD = g.dim_dense_layers;
-    const size_t need = rdt_carve(c, B, Nmax, nullptr, nullptr);
-    if (ws_bytes < need) return rd_fail(RDESIGN_ERR_WORKSPACE, "training workspace %zu bytes < required %zu", ws_bytes, need);
-    if (((uintptr_t)ws & 255) != 0) return rd_fail(RDESIGN_ERR_BAD_ARG, "workspace must be 256-byte aligned");
-    if (rd_knn_lds_bytes(T) > 160 * 1024 - 256) return rd_fail(RDESIGN_ERR_UNSUPPORTED, "max_len %d too long for the LDS-resident k-NN row", T);
-    RdtWs w;
-    rdt_carve(c, B, Nmax, (char*)ws, &w);
-    RdRun r;
-    r.c = c; r.s = (hipStream_t)stream; r.mixed = false; r.nodrop = TDrop{0ull, 0u, 1.f, nullptr}; r.K = K; r.w = w.f;
-    r.pk.len = w.f.len; r.pk.cu = w.f.cu; r.pk.node_b = w.f.node_b; r.pk.B = B; r.pk.T = T; r.pk.Nmax = (int)Nmax; r.pk.packed_in = 0;
+    RdRun& r = t.r;
+    RdtWs& w = t.w;
     hipStream_t s = r.s;
     const PackInfo& pk = r.pk;
-    const int* ntot = pk.cu + B;
+    const int K = r.K, L = t.L, M = t.M;
+    const int* ntot = pk.cu + pk.B;
     const TRows rn = r.rn(), re = r.re();
-    const TDrop dr = t_drop(dropout, seed);
+    const TDrop dr = t.dr;
     const float inv_scale = 1.0f / 30.0f;
-    auto site_msg = [&](int l, int i) { return (unsigned)(1 + l * (M + D) + i); };
-    auto site_dense = [&](int l, int i) { return (unsigned)(1 + l * (M + D) + M + i); };
-    auto site_ro = [&](int j) { return (unsigned)(1 + L * (M + D) + j); };
-    // Y = X . W[:, k0:k0+Kc]^T (+ bias) on the K-major copy finalize built: the forward's GEMM (rdesign.hip: rd_mm, f32 branch)
+    // Y = X . W[:, k0:k0+Kc]^T (+ bias): the forward's GEMM on the K-major copy finalize built
     auto fwd = [&](const TRows& rows, const float* Xin, int ldx, const RdLin& l, int k0, int Kc, bool use_bias, float* Y, int ldy) {
-        t_gemm(rows, Xin, ldx, (Kc + 3) / 4 * 4, c->der + l.wt + (size_t)k0 * l.out, l.out, use_bias ? rdp(c, l.b) : nullptr, l.out, Y, ldy, 0, s);
+        rd_mm(r, rows, Xin, ldx, l, k0, Kc, use_bias, Y, ldy, 0, false, nullptr, r.nodrop, 0u);
+    };
+    // dx = [beta dx] + dy . W[:, k0:k0+128] of the factored first message Linear
+    auto dx0 = [&](const TRows& rows, const float* dy, int ldy, const RdLin& l, int k0, float* dx, int beta) {
+        t_gemm(rows, dy, ldy, l.out, rdp(c, l.w) + k0, l.in, nullptr, RD_H, dx, RD_H, beta, s);
     };
     const unsigned seg_grid = (unsigned)(Nmax < 65536 ? Nmax : 65536);
 
     // ================================================================ taped forward
-    rd_front(r, X, mask, nullptr);
+    rd_front(r, a.X, a.mask, nullptr);
     t_build_reverse(pk, K, w.f.nbr, w.rdeg, w.rstart, w.rfill, w.rlist, reinterpret_cast<int*>(w.f.E2), s);
     fwd(rn, w.f.node_raw, RD_NODEP, c->node_emb, 0, RD_NODE, true, w.embN, RD_H);
     rd_rownorm(ntot, 1, Nmax, w.embN, nullptr, rdp(c, c->nn_g), rdp(c, c->nn_b), 0, w.hv[0], s);
-    fwd(re, w.f.edge_raw, RD_EDGEP, c->edge_emb, 0, RD_EDGE, true, w.embE, RD_H);
-    rd_rownorm(ntot, K, Nmax * K, w.embE, nullptr, rdp(c, c->ne_g), rdp(c, c->ne_b), 0, w.f.hE, s);
+    fwd(re, w.f.edge_raw, RD_EDGEP, c->edge_emb, 0, RD_EDGE, true, e.embE, RD_H);
+    rd_rownorm(ntot, K, Nmax * K, e.embE, nullptr, rdp(c, c->ne_g), rdp(c, c->ne_b), 0, w.f.hE, s);
     for (int l = 0; l < L; ++l) {
         const RdLayer& Lw = c->layers[l];
-        RdtLayer& t = w.layers[l];
+        RdtLayer& tl = w.layers[l];
+        const std::vector<float*>& msg = e.msg[l];
         const float* hv = w.hv[l];
         // message Linear 0 on cat[h_E, h_V[centre], h_V[neighbour]] = W_e.h_E + P[centre] + Q[neighbour]
         fwd(rn, hv, RD_H, Lw.msg[0], RD_H, RD_H, true, w.f.pq, 256);
         fwd(rn, hv, RD_H, Lw.msg[0], 2 * RD_H, RD_H, false, w.f.pq + RD_H, 256);
-        fwd(re, w.f.hE, RD_H, Lw.msg[0], 0, RD_H, false, t.msg[0], RD_H);
-        t_edge_add_pq(pk, K, w.f.nbr, w.f.pq, t.msg[0], s);
-        for (int i = 1; i < M; ++i) {
-            t_gelu_fwd(re, t.msg[i - 1], w.f.E1, RD_H, dr, site_msg(l, i - 1), s);
-            fwd(re, w.f.E1, RD_H, Lw.msg[i], 0, RD_H, true, t.msg[i], RD_H);
-        }
-        hipLaunchKernelGGL(k_rdt_segsum, dim3(seg_grid), dim3(128), 0, s, pk, K, w.f.nbr, t.msg[M - 1], inv_scale, t.dh, dr, site_msg(l, M - 1));
-        rd_rownorm(ntot, 1, Nmax, hv, t.dh, rdp(c, Lw.n1w), rdp(c, Lw.n1b), 1, t.h1, s);                    // norm1(h_V + dh)
-        const float* x = t.h1;
-        int ld = RD_H;
-        for (int i = 0; i <= D; ++i) {
-            if (i > 0) { t_gelu_fwd(rn, t.dense[i - 1], w.bA, DD, dr, site_dense(l, i - 1), s); x = w.bA; ld = DD; }
-            fwd(rn, x, ld, Lw.dense[i], 0, Lw.dense[i].in, true, i < D ? t.dense[i] : t.y, Lw.dense[i].out);
-        }
-        rd_rownorm(ntot, 1, Nmax, t.h1, t.y, rdp(c, Lw.n2w), rdp(c, Lw.n2b), 1, w.hv[l + 1], s);            // norm2(h_V + dense(h_V))
+        fwd(re, w.f.hE, RD_H, Lw.msg[0], 0, RD_H, false, msg[0], RD_H);
+        t_edge_add_pq(pk, K, w.f.nbr, w.f.pq, msg[0], s);
+        for (int i = 1; i < M; ++i)
+            rd_mm(r, re, msg[i - 1], RD_H, Lw.msg[i], 0, RD_H, true, msg[i], RD_H, 0, true, w.f.E1, dr, t.site_msg(l, i - 1));
+        hipLaunchKernelGGL(k_rdt_segsum, dim3(seg_grid), dim3(128), 0, s, pk, K, w.f.nbr, msg[M - 1], inv_scale, tl.dh, dr, t.site_msg(l, M - 1));
+        rd_rownorm(ntot, 1, Nmax, hv, tl.dh, rdp(c, Lw.n1w), rdp(c, Lw.n1b), 1, tl.h1, s);                  // norm1(h_V + dh)
+        rdt_ffn_fwd(t, Lw.dense, tl.h1, tl.dense, tl.y, t.site_dense(l, 0));
+        rd_rownorm(ntot, 1, Nmax, tl.h1, tl.y, rdp(c, Lw.n2w), rdp(c, Lw.n2b), 1, w.hv[l + 1], s);          // norm2(h_V + dense(h_V))
     }
-    const int R = (int)c->readout.size();
-    {
-        const float* x = w.hv[L];
-        int ld = RD_H;
-        for (int j = 0; j < R; ++j) {
-            if (j > 0) { t_gelu_fwd(rn, w.rpre[j - 1], w.bA, c->readout[j].in, dr, site_ro(j - 1), s); x = w.bA; ld = c->readout[j].in; }
-            fwd(rn, x, ld, c->readout[j], 0, c->readout[j].in, true, j + 1 < R ? w.rpre[j] : w.logits, c->readout[j].out);
-        }
-    }
-    if (logits) rd_copy_rows(pk.cu + B, 1, Nmax, w.logits, 4, logits, 4, 4, s);      // rows >= N of the caller's tensor stay untouched
+    rdt_ffn_fwd(t, c->readout, w.hv[L], w.rpre, w.logits, t.site_ro(0));
 
     // ================================================================ loss and backward
-    rdt_ce_loss(pk, w.logits, labels, w.dlogits, w.part, loss, s);
-    launch_zero_bytes(grad, c->raw_floats * sizeof(float), s);
-    auto G = [&](int i) { return grad + c->raw[i].off; };
-    red_begin(w.sc, s);
-    // gradients of one Linear y = x W^T + b from dy [rows][out] and its input x [rows][>= in]:  dW += dy^T x,  db += colsum(dy)
-    auto lin_wb = [&](const TRows& rows, const float* dy, int ldy, const RdLin& l, const float* x, int ldx) {
-        t_gemm_tn(rows, dy, ldy, l.out, x, ldx, l.in, G(l.w), l.in, s);
-        t_colsum(rows, dy, ldy, l.out, G(l.b), s);
-    };
-    // dx = [beta dx] + dy . W[:, k0:k0+n]      (W as nn.Linear stores it, [out][in]: K-major for this product)
-    auto lin_dx = [&](const TRows& rows, const float* dy, int ldy, const RdLin& l, int k0, int n, float* dx, int ldx, int beta) {
-        t_gemm(rows, dy, ldy, l.out, rdp(c, l.w) + k0, l.in, nullptr, n, dx, ldx, beta, s);
-    };
-    // ---- read-out
-    {
-        const float* dy = w.dlogits;
-        for (int j = R - 1; j >= 0; --j) {
-            const RdLin& l = c->readout[j];
-            const float* x = w.hv[L];
-            if (j > 0) { t_gelu_fwd(rn, w.rpre[j - 1], w.bC, l.in, dr, site_ro(j - 1), s); x = w.bC; }
-            lin_wb(rn, dy, l.out, l, x, l.in);
-            if (j > 0) {
-                lin_dx(rn, dy, l.out, l, 0, l.in, w.bA, l.in, 0);
-                t_gelu_bwd(rn, w.bA, w.rpre[j - 1], w.bB, l.in, dr, site_ro(j - 1), s);
-                dy = w.bB;
-            } else {
-                lin_dx(rn, dy, l.out, l, 0, RD_H, w.gH, RD_H, 0);
-            }
-        }
-    }
+    rdt_loss(t, a);
+    rdt_ffn_bwd(t, c->readout, w.hv[L], w.rpre, w.dlogits, w.gH, false, t.site_ro(0));
     // ---- L x MPNNLayer, last first; w.gH = d loss / d (h_V leaving the layer)
     for (int l = L - 1; l >= 0; --l) {
         const RdLayer& Lw = c->layers[l];
-        RdtLayer& t = w.layers[l];
+        RdtLayer& tl = w.layers[l];
+        const std::vector<float*>& msg = e.msg[l];
         // norm2(h1 + y)
-        rdt_rownorm_bwd(ntot, 1, Nmax, t.h1, t.y, w.gH, rdp(c, Lw.n2w), 1, w.gX, w.bA, s);
-        t_colsum(rn, w.bA, RD_H, RD_H, G(Lw.n2w), s);
-        t_colsum(rn, w.gH, RD_H, RD_H, G(Lw.n2b), s);
-        // dense FFN: w.gX is both d y and the residual part of d h1
-        {
-            const float* dy = w.gX;
-            for (int i = D; i >= 0; --i) {
-                const RdLin& lin = Lw.dense[i];
-                const float* x = t.h1;
-                if (i > 0) { t_gelu_fwd(rn, t.dense[i - 1], w.bC, DD, dr, site_dense(l, i - 1), s); x = w.bC; }
-                lin_wb(rn, dy, lin.out, lin, x, lin.in);
-                if (i > 0) {
-                    lin_dx(rn, dy, lin.out, lin, 0, lin.in, w.bA, lin.in, 0);
-                    t_gelu_bwd(rn, w.bA, t.dense[i - 1], w.bB, DD, dr, site_dense(l, i - 1), s);
-                    dy = w.bB;
-                } else {
-                    lin_dx(rn, dy, lin.out, lin, 0, RD_H, w.gX, RD_H, dy == w.gX ? 0 : 1);
-                }
-            }
-        }
+        rdt_rownorm_bwd(ntot, 1, Nmax, tl.h1, tl.y, w.gH, rdp(c, Lw.n2w), 1, w.gX, w.bA, s);
+        t_colsum(rn, w.bA, RD_H, RD_H, t.G(Lw.n2w), s);
+        t_colsum(rn, w.gH, RD_H, RD_H, t.G(Lw.n2b), s);
+        rdt_ffn_bwd(t, Lw.dense, tl.h1, tl.dense, w.gX, w.gX, true, t.site_dense(l, 0));     // w.gX is both d y and the residual part of d h1
         // norm1(h_V + dh): w.gH <- d (h_V + dh)
-        rdt_rownorm_bwd(ntot, 1, Nmax, w.hv[l], t.dh, w.gX, rdp(c, Lw.n1w), 1, w.gH, w.bA, s);
-        t_colsum(rn, w.bA, RD_H, RD_H, G(Lw.n1w), s);
-        t_colsum(rn, w.gX, RD_H, RD_H, G(Lw.n1b), s);
-        // segment sum, then the message Linears M-1 .. 1
+        rdt_rownorm_bwd(ntot, 1, Nmax, w.hv[l], tl.dh, w.gX, rdp(c, Lw.n1w), 1, w.gH, w.bA, s);
+        t_colsum(rn, w.bA, RD_H, RD_H, t.G(Lw.n1w), s);
+        t_colsum(rn, w.gX, RD_H, RD_H, t.G(Lw.n1b), s);
+        // segment sum, then the message Linears M-1 .. 1: dW, db from GELU(pre[i-1]) in e.eS; d pre[i-1] through w.f.E2, in place of d pre[i]
         float* dpre = w.f.E1;
-        float* da = w.f.E2;
-        hipLaunchKernelGGL(k_rdt_segsum_bwd, dim3(seg_grid), dim3(128), 0, s, pk, K, w.f.nbr, w.gH, t.msg[M - 1], inv_scale, dpre, dr, site_msg(l, M - 1));
+        hipLaunchKernelGGL(k_rdt_segsum_bwd, dim3(seg_grid), dim3(128), 0, s, pk, K, w.f.nbr, w.gH, msg[M - 1], inv_scale, dpre, dr, t.site_msg(l, M - 1));
         for (int i = M - 1; i >= 1; --i) {
-            const RdLin& lin = Lw.msg[i];
-            t_gelu_fwd(re, t.msg[i - 1], w.eS, RD_H, dr, site_msg(l, i - 1), s);
-            lin_wb(re, dpre, RD_H, lin, w.eS, RD_H);
-            lin_dx(re, dpre, RD_H, lin, 0, RD_H, da, RD_H, 0);
-            t_gelu_bwd(re, da, t.msg[i - 1], dpre, RD_H, dr, site_msg(l, i - 1), s);
+            rd_mm_wb(r, re, dpre, Lw.msg[i], msg[i - 1], true, e.eS, dr, t.site_msg(l, i - 1), t.grad);
+            rd_mm_dx(r, re, dpre, Lw.msg[i], dpre, 0, msg[i - 1], w.f.E2, dr, t.site_msg(l, i - 1));
         }
         // factored first Linear: pre0 = W_e h_E + (W_c h_V + b)[centre] + (W_n h_V)[neighbour]
         const RdLin& l0 = Lw.msg[0];
-        t_gemm_tn(re, dpre, RD_H, RD_H, w.f.hE, RD_H, RD_H, G(l0.w), 3 * RD_H, s);                            // dW_e
-        lin_dx(re, dpre, RD_H, l0, 0, RD_H, w.dhE, RD_H, l == L - 1 ? 0 : 1);                                 // d h_E (shared by all layers)
+        t_gemm_tn(re, dpre, RD_H, RD_H, w.f.hE, RD_H, RD_H, t.G(l0.w), 3 * RD_H, s);                          // dW_e
+        dx0(re, dpre, RD_H, l0, 0, e.dhE, l == L - 1 ? 0 : 1);                                                // d h_E (shared by all layers)
         t_edge_pq_bwd(pk, K, dpre, w.rstart, w.rlist, w.f.pq, s);                                             // dP = own slots, dQ = gather over the reverse adjacency
-        t_colsum(rn, w.f.pq, 256, RD_H, G(l0.b), s);                                                          // db (the bias rides in P)
-        t_gemm_tn(rn, w.f.pq, 256, RD_H, w.hv[l], RD_H, RD_H, G(l0.w) + RD_H, 3 * RD_H, s);                   // dW_c
-        t_gemm_tn(rn, w.f.pq + RD_H, 256, RD_H, w.hv[l], RD_H, RD_H, G(l0.w) + 2 * RD_H, 3 * RD_H, s);        // dW_n
-        lin_dx(rn, w.f.pq, 256, l0, RD_H, RD_H, w.gH, RD_H, 1);                                               // d h_V += dP W_c + dQ W_n
-        lin_dx(rn, w.f.pq + RD_H, 256, l0, 2 * RD_H, RD_H, w.gH, RD_H, 1);
+        t_colsum(rn, w.f.pq, 256, RD_H, t.G(l0.b), s);                                                        // db (the bias rides in P)
+        t_gemm_tn(rn, w.f.pq, 256, RD_H, w.hv[l], RD_H, RD_H, t.G(l0.w) + RD_H, 3 * RD_H, s);                 // dW_c
+        t_gemm_tn(rn, w.f.pq + RD_H, 256, RD_H, w.hv[l], RD_H, RD_H, t.G(l0.w) + 2 * RD_H, 3 * RD_H, s);      // dW_n
+        dx0(rn, w.f.pq, 256, l0, RD_H, w.gH, 1);                                                              // d h_V += dP W_c + dQ W_n
+        dx0(rn, w.f.pq + RD_H, 256, l0, 2 * RD_H, w.gH, 1);
     }
     // ---- embeddings: Normalize backward, then the 101- / 115-input Linears (nothing flows into the raw features)
     rdt_rownorm_bwd(ntot, 1, Nmax, w.embN, nullptr, w.gH, rdp(c, c->nn_g), 0, w.gX, w.bA, s);
-    t_colsum(rn, w.bA, RD_H, RD_H, G(c->nn_g), s);
-    t_colsum(rn, w.gH, RD_H, RD_H, G(c->nn_b), s);
-    lin_wb(rn, w.gX, RD_H, c->node_emb, w.f.node_raw, RD_NODEP);
-    rdt_rownorm_bwd(ntot, K, Nmax * K, w.embE, nullptr, w.dhE, rdp(c, c->ne_g), 0, w.f.E1, w.eS, s);
-    t_colsum(re, w.eS, RD_H, RD_H, G(c->ne_g), s);
-    t_colsum(re, w.dhE, RD_H, RD_H, G(c->ne_b), s);
-    lin_wb(re, w.f.E1, RD_H, c->edge_emb, w.f.edge_raw, RD_EDGEP);
-    if (!red_end()) return rd_fail(RDESIGN_ERR_HIP, "rdesign_loss_and_grad: an ordered reduction was refused (reduction arena)");
+    t_colsum(rn, w.bA, RD_H, RD_H, t.G(c->nn_g), s);
+    t_colsum(rn, w.gH, RD_H, RD_H, t.G(c->nn_b), s);
+    rdt_node_emb_bwd(t);
+    rdt_rownorm_bwd(ntot, K, Nmax * K, e.embE, nullptr, e.dhE, rdp(c, c->ne_g), 0, w.f.E1, e.eS, s);
+    t_colsum(re, e.eS, RD_H, RD_H, t.G(c->ne_g), s);
+    t_colsum(re, e.dhE, RD_H, RD_H, t.G(c->ne_b), s);
+    t_gemm_tn(re, w.f.E1, RD_H, RD_H, w.f.edge_raw, RD_EDGEP, RD_EDGE, t.G(c->edge_emb.w), RD_EDGE, s);
+    t_colsum(re, w.f.E1, RD_H, RD_H, t.G(c->edge_emb.b), s);
+    if (const int rc = rdt_end(who)) return rc;
     RD_TRY(hipGetLastError());
     return RDESIGN_OK;
 }
 
-// bytes of the tape alone (the pre-activations and layer inputs kept between forward and backward): a figure for tools/rdesign_probe.py
-extern "C" size_t rdesign_train_tape_bytes(rdesign_handle h, int32_t B, int32_t T) {
-    if (rdt_check(h, B, T) != RDESIGN_OK) return 0;
-    RdtWs w;
-    rdt_carve(h, B, (size_t)B * T, nullptr, &w);
-    return w.tape_bytes;
+// ------------------------------------------------------------------------------------------ one dispatch on `flags`, C entry points
+// sizes != null: the host-only size query (sizes[0] = workspace bytes, sizes[1] = bytes of the tape alone, a figure for tools/rdesign_probe.py)
+int rdt_dispatch(rdesign_handle h, const RdtArgs& a, int32_t flags, size_t* sizes) {
+    if (flags != RDESIGN_TRAIN_F32 && flags != RDESIGN_TRAIN_BF16_MIXED) return rd_fail(RDESIGN_ERR_BAD_ARG, "unknown training flags %d", flags);
+    if (!h) return rd_fail(RDESIGN_ERR_BAD_ARG, "null handle");
+    if (flags == RDESIGN_TRAIN_F32 && h->cfg.precision != RDESIGN_PREC_F32)
+        return rd_fail(RDESIGN_ERR_UNSUPPORTED, "the rdesign training step is built for the exact-f32 path only (create the handle with RDESIGN_PREC_F32)");
+    if (flags == RDESIGN_TRAIN_BF16_MIXED && h->cfg.num_message_layers != 2 && h->cfg.num_message_layers != 3)
+        return rd_fail(RDESIGN_ERR_UNSUPPORTED, "the bf16-mixed rdesign training step is built for num_message_layers 2 and 3 (got %d): train with RDESIGN_TRAIN_F32",
+                       h->cfg.num_message_layers);
+    if (a.B <= 0 || a.T <= 0) return rd_fail(RDESIGN_ERR_BAD_ARG, "training step: non-positive B/T");
+    // 32-bit element-pair indices of the dropout hash (kernels_train.h) and 32-bit edge-row indexing: rows * width / 2 < 2^32
+    if ((long long)a.B * a.T * h->cfg.k_neighbors >= (1LL << 26) || (long long)a.B * a.T * rdt_dm(h) >= (1LL << 32))
+        return rd_fail(RDESIGN_ERR_BAD_ARG, "row count out of range for the training path (B*T*k < 2^26); split the batch");
+    return flags == RDESIGN_TRAIN_F32 ? rdt_f32_step(h, a, sizes) : rdb_step(h, a, sizes);
+}
+size_t rdt_size(rdesign_handle h, int32_t B, int32_t T, int32_t flags, int which) {
+    RdtArgs a{};
+    a.B = B; a.T = T;
+    size_t sizes[2];
+    return rdt_dispatch(h, a, flags, sizes) == RDESIGN_OK ? sizes[which] : 0;
+}
+}  // namespace
+
+extern "C" size_t rdesign_train_workspace_bytes_ex(rdesign_handle h, int32_t B, int32_t T, int32_t flags) { return rdt_size(h, B, T, flags, 0); }
+extern "C" size_t rdesign_train_tape_bytes_ex(rdesign_handle h, int32_t B, int32_t T, int32_t flags) { return rdt_size(h, B, T, flags, 1); }
+extern "C" int rdesign_loss_and_grad_ex(rdesign_handle h, const float* X, const float* mask, const int32_t* labels, int32_t B, int32_t T, float dropout,
+                                        uint64_t seed, int32_t flags, float* loss, float* logits, float* grad, void* ws, size_t ws_bytes, void* stream) {
+    return rdt_dispatch(h, RdtArgs{X, mask, labels, B, T, dropout, seed, loss, logits, grad, ws, ws_bytes, stream}, flags, nullptr);
+}
+// the entry points older than `flags`: the exact-f32 step
+extern "C" size_t rdesign_train_workspace_bytes(rdesign_handle h, int32_t B, int32_t T) { return rdesign_train_workspace_bytes_ex(h, B, T, RDESIGN_TRAIN_F32); }
+extern "C" size_t rdesign_train_tape_bytes(rdesign_handle h, int32_t B, int32_t T) { return rdesign_train_tape_bytes_ex(h, B, T, RDESIGN_TRAIN_F32); }
+extern "C" int rdesign_loss_and_grad(rdesign_handle h, const float* X, const float* mask, const int32_t* labels, int32_t B, int32_t T, float dropout,
+                                     uint64_t seed, float* loss, float* logits, float* grad, void* ws, size_t ws_bytes, void* stream) {
+    return rdesign_loss_and_grad_ex(h, X, mask, labels, B, T, dropout, seed, RDESIGN_TRAIN_F32, loss, logits, grad, ws, ws_bytes, stream);
 }

@@ -13,7 +13,7 @@ from conftest import REPO
 from test_rdesign_cpu import _batch
 
 NEW = ("rdesign_train_workspace_bytes_ex", "rdesign_train_tape_bytes_ex", "rdesign_loss_and_grad_ex")
-TU = os.path.join(REPO, "rna-mpnn_amd", "csrc", "rdesign_train_bf16.hip")
+TUS = ("rdesign_train.hip", "rdesign_train_bf16.hip")          # every translation unit that holds training-step code
 F32, MIXED = 0, 1
 
 
@@ -37,16 +37,24 @@ def test_ex_entry_points_are_declared_bound_and_exported():
 
 
 def test_new_translation_unit_keeps_the_rules():
-    src = open(TU).read()
-    code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
-    for call in ("hipMemset", "hipMemcpy", "memset(", "memcpy("):
-        assert call not in code, f"{call} in rdesign_train_bf16.hip: use launch_zero_bytes / launch_copy_bytes"
-    assert "atomic" not in code, "no atomics in rdesign_train_bf16.hip: cross-workgroup sums go through ordered reductions / fixed-order partials"
-    assert "getenv" not in code and "ab_switch" not in code
-    assert "hipDeviceSynchronize" not in code and "hipStreamSynchronize" not in code
+    """Every unit on its own keeps the bans; the reduction bracket and the gradient zeroing are written once for both steps, so their presence
+    is asked of the units together; the tape convention stays with the bf16 sequence."""
+    from __graft_entry__ import SOURCES
+    srcs = {}
+    for tu in TUS:
+        assert tu in SOURCES
+        srcs[tu] = open(os.path.join(REPO, "rna-mpnn_amd", "csrc", tu)).read()
+    codes = {tu: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S)) for tu, src in srcs.items()}
+    for tu, code in codes.items():
+        for call in ("hipMemset", "hipMemcpy", "memset(", "memcpy("):
+            assert call not in code, f"{call} in {tu}: use launch_zero_bytes / launch_copy_bytes"
+        assert "atomic" not in code, f"no atomics in {tu}: cross-workgroup sums go through ordered reductions / fixed-order partials"
+        assert "getenv" not in code and "ab_switch" not in code, tu
+        assert "hipDeviceSynchronize" not in code and "hipStreamSynchronize" not in code, tu
     for fn in ("red_begin", "red_end", "launch_zero_bytes"):
-        assert fn in code
-    assert "tape convention" in src.lower()                     # the header comment states it per tensor
+        assert any(fn in code for code in codes.values())
+    assert "launch_zero_bytes" in codes["rdesign_train_bf16.hip"]
+    assert "tape convention" in srcs["rdesign_train_bf16.hip"].lower()      # the header comment states it per tensor
 
 
 def test_default_is_the_f32_step_and_there_is_no_cpu_fallback():
@@ -109,3 +117,32 @@ def test_size_queries_accept_either_handle_and_the_bf16_tape_is_smaller():
         if not ok:
             assert b"num_message_layers" in lib.rdesign_last_error()
             assert lib.rdesign_loss_and_grad_ex(h.ptr, None, None, None, 3, 12, 0.0, 0, MIXED, None, None, None, None, 0, None) == 2   # UNSUPPORTED
+
+
+# rdesign_train_workspace_bytes_ex F32, rdesign_train_tape_bytes_ex F32, the same two for MIXED, rdesign_workspace_bytes: the values of the
+# build before the two steps shared one workspace description (every tensor is rounded to 256 bytes on its own: no total depends on carve order)
+_K6 = dict(k_neighbors=6, num_mpnn_layers=2)
+PINNED_SIZES = (
+    (_K6, 3, 12, (69286656, 1180416, 69350400, 793344, 622080)),
+    (_K6, 4, 40, (76756736, 5245440, 75233792, 3525120, 2750976)),
+    ({}, 3, 12, (84779264, 14598912, 78428672, 8147712, 1992960)),
+    ({}, 64, 500, (15766188800, 12976640000, 9655609088, 7242240000, 1768066816)),
+    (dict(k_neighbors=30, num_mpnn_layers=3, dim_dense_layers=512, num_readout_layers=2, readout_hidden_dim=128, num_message_layers=2,
+          num_dense_layers=1), 4, 40, (103390976, 19417600, 93020672, 10816000, 10774016)),
+    (dict(k_neighbors=8, num_mpnn_layers=1, dim_dense_layers=128, num_dense_layers=2, num_readout_layers=3, readout_hidden_dim=128),
+     3, 12, (69007104, 774912, 69126144, 480000, 729344)),
+)
+
+
+@pytest.mark.parametrize("case", range(len(PINNED_SIZES)))
+def test_size_queries_of_an_f32_handle_are_pinned(case):
+    """Host-only: byte totals and tape totals are part of what callers allocate by; sharing the workspace description must not move them."""
+    from rdesign.model.rdesign import RNAModel
+    _, _native, lib = _lib()
+    kw, B, T, want = PINNED_SIZES[case]
+    h = RNAModel(precision="f32", **kw)._handle
+    got = (lib.rdesign_train_workspace_bytes_ex(h.ptr, B, T, F32), lib.rdesign_train_tape_bytes_ex(h.ptr, B, T, F32),
+           lib.rdesign_train_workspace_bytes_ex(h.ptr, B, T, MIXED), lib.rdesign_train_tape_bytes_ex(h.ptr, B, T, MIXED),
+           lib.rdesign_workspace_bytes(h.ptr, B, T))
+    assert got == want
+    assert (lib.rdesign_train_workspace_bytes(h.ptr, B, T), lib.rdesign_train_tape_bytes(h.ptr, B, T)) == want[:2]
