@@ -99,7 +99,10 @@ int rdesign_readout(rdesign_handle h, const float* h_V, int32_t n_rows, float* l
  *   loss     device scalar;  logits optional, packed (B*T,4), rows >= N untouched
  *   grad     rdesign_param_numel() floats laid out like the weight arena (rdesign_weight_info offsets), OVERWRITTEN; padding floats are zero
  * Bit-reproducible (no float atomics); rows are bounded by the 32-bit pair index of the dropout hash: B*T*k < 2^26, else RDESIGN_ERR_BAD_ARG.
- * rdesign_train_tape_bytes: the part of the workspace that holds the tape (a figure for reports). */
+ * rdesign_train_tape_bytes: the part of the workspace that holds the tape (a figure for reports).
+ * RNAFeatures(augment_eps) (feature.py:157-158: X + eps * randn_like(X) on a training forward) is not part of this call: the step reads X
+ * as given.  RNAModel(augment_eps) noises X ahead of it with rnampnn_augment_coords (include/rnampnn_hip.h: atoms = 6, sigma = eps for every
+ * row, no keys, seed = this call's seed), as do the noisy copies of a training set (rnampnn/utils/augment.py). */
 size_t rdesign_train_workspace_bytes(rdesign_handle h, int32_t B, int32_t T);
 size_t rdesign_train_tape_bytes(rdesign_handle h, int32_t B, int32_t T);
 int rdesign_loss_and_grad(rdesign_handle h, const float* X, const float* mask, const int32_t* labels, int32_t B, int32_t T,

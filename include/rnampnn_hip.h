@@ -238,6 +238,30 @@ int     rnampnn_use_weight_arena(rnampnn_handle h, float* arena, void* stream);
 int     rnampnn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel, float lr,
                           float beta1, float beta2, float eps, float weight_decay, int32_t step, void* stream);
 
+/* -- training-set augmentation ----------------------------------------------------------- */
+/* Gaussian coordinate noise on a padded batch, on the device (csrc/augment.hip): the role of RNADataset.noise_augmentation
+ * (rnampnn/utils/data.py:278-295: stored copies with coordinates + N(0, 1e-2)) and of RNAFeatures(augment_eps) of the rdesign sibling
+ * (rdesign/model/feature.py:157-158: X + eps * randn_like(X) on every training forward).  The reference draws from torch's global RNG;
+ * here the noise of a value is a pure function of (stream of its row, residue index in the SOURCE RNA, atom, axis), so a noisy copy is a
+ * row of the (sigma, key, offset) table and never a stored array.  coords / out (B,T,atoms,3) f32, atoms = 6 or 7; sigma (B) f32,
+ * key (B) u64 or null, offset (B) i32 >= 0 or null (= 0): DEVICE arrays, read at kernel time.  For a valid residue t (mask[b,t] != 0) of a
+ * row with sigma[b] != 0:
+ *     out[b,t,a,x] = coords[b,t,a,x] + sigma[b] * normal01(stream_b, ((offset[b] + t) * atoms + a) * 3 + x)      (one f32 product, one f32 add)
+ * with the generator of rnampnn/utils/synth.py restated in f32 (logf, sqrtf, cospif; mix64 = the splitmix64 finaliser, 64-bit wrap-around):
+ *     uniform01(s, i) = (mix64(mix64((i + 1) * 0x9E3779B97F4A7C15 + s) ^ (s * 0xD6E8FEB86659FD93)) >> 40) * 2^-24
+ *     normal01(s, i)  = sqrt(-2 * log(1 - uniform01(s, 2 i))) * cos(2 pi * uniform01(s, 2 i + 1))
+ *     stream_b        = key[b] when key is given, else mix64(mix64(seed) + (b + 1) * 0x9E3779B97F4A7C15)   (seed is ignored with a key)
+ * A slice of a noisy copy that starts at residue s of its source passes offset = s and gets that copy's noise.  Padded residues and every
+ * row with sigma[b] == 0 are copied bit for bit (-0.0 stays -0.0); a NaN coordinate stays NaN and its neighbours are noised.  out == coords
+ * (in place) is allowed; any other overlap is not.  One kernel whose launch depends on (B, T, atoms) only: no runtime fill / copy node, no
+ * atomics, no synchronisation, so the call can sit inside a captured training step.  RNAMPNN_ERR_BAD_ARG: atoms outside {6, 7}, B or
+ * T <= 0, null coords / mask / sigma / out.  rnampnn/utils/augment.py: noise_reference restates it in numpy (the checker). */
+int rnampnn_augment_coords(const float* coords, const float* mask, int32_t B, int32_t T, int32_t atoms,
+                           const float* sigma      /* (B) */,
+                           const uint64_t* key     /* (B) or null */,
+                           const int32_t* offset   /* (B) or null = 0 */,
+                           uint64_t seed, float* out, void* stream);
+
 /* -- measurement ------------------------------------------------------------------------- */
 /* Live timing of the dominant kernel (the fused ResMPNN edge kernel, mpnn.py:154-265): when
  * enabled, HIP events bracket its launches on the caller's stream - every `enable`-th launch (1 = all; an event

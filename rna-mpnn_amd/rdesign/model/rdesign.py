@@ -8,7 +8,9 @@ exact-f32 TRAINING STEP: ``loss_and_grad`` (``rdesign_loss_and_grad``: taped for
 flat gradient buffer), ``training_step`` (the same behind an autograd node) and ``configure_optimizers(fused=True)`` (the main model's
 ``FlatAdam`` on this model's flat buffers).  f32 is the reference arithmetic of this model (its trainer sets no ``precision``,
 ``rdesign/utils/train.py:107-115``) and the default of the step; ``train_precision="bf16"`` opts into the bf16-mixed step
-(``rdesign_loss_and_grad_ex``: bf16 per-edge tensors, MFMA GEMMs) on a model of either ``precision``.  A differentiable
+(``rdesign_loss_and_grad_ex``: bf16 per-edge tensors, MFMA GEMMs) on a model of either ``precision``.  ``augment_eps > 0`` is the
+reference's ``RNAFeatures(augment_eps)`` (``feature.py:157-158``): train-mode steps see ``X + eps * N(0, 1)``, added on the device as a
+function of the step's seed (``rnampnn_augment_coords``); eval-mode paths never look at it.  A differentiable
 ``forward`` / ``readout`` pair is not built.
 Epoch-level surface: ``score_batch`` (one forward + ``rdesign_score``: per-RNA correct / valid / NLL as device tensors, no host round
 trip when the loader's host ``lengths`` are passed), ``reserve_training``, ``allreduce_gradients`` (one flat all-reduce) - what
@@ -127,7 +129,7 @@ class RNAModel(nn.Module):
                  dim_dense_layers: int = 256, num_mpnn_layers: int = 9, readout_hidden_dim: int = 256,
                  num_readout_layers: int = 0, lr: float = 0.002, n_estimators: int = 100, xgb_max_depth: int = 6,
                  xgb_learning_rate: float = 0.1, xgb_subsample: float = 0.8, xgb_colsample_bytree: float = 0.8,
-                 precision: str = "bf16", train_precision: Optional[str] = None):
+                 precision: str = "bf16", train_precision: Optional[str] = None, augment_eps: float = 0.0):
         super().__init__()
         if node_feat_types not in (None, ["angle", "distance", "direction"]) or \
                 edge_feat_types not in (None, ["orientation", "distance", "direction"]):
@@ -138,6 +140,9 @@ class RNAModel(nn.Module):
             raise ValueError(f"precision must be one of {sorted(_PREC)}")
         self.name, self.version, self.precision = "RDesign-X", 0, precision
         self.train_precision = "f32" if train_precision is None else train_precision      # not a hyper-parameter of the handle, not in the state dict
+        if not float(augment_eps) >= 0.0:
+            raise ValueError("augment_eps must be >= 0")
+        self.augment_eps = float(augment_eps)          # RNAFeatures(augment_eps), feature.py:157-158: train-mode steps only, not the handle's business
         self.hparams = dict(hidden_dim=hidden_dim, vocab_size=vocab_size, k_neighbors=k_neighbors, dropout=dropout,
                             num_message_layers=num_message_layers, num_dense_layers=num_dense_layers,
                             dim_dense_layers=dim_dense_layers, num_mpnn_layers=num_mpnn_layers,
@@ -187,7 +192,7 @@ class RNAModel(nn.Module):
     @property
     def init_kwargs(self) -> dict:
         """Constructor arguments that rebuild this module (plain types: what a checkpoint stores next to the ``state_dict``)."""
-        return dict(self.hparams, **self.xgb_hparams, precision=self.precision, train_precision=self.train_precision)
+        return dict(self.hparams, **self.xgb_hparams, precision=self.precision, train_precision=self.train_precision, augment_eps=self.augment_eps)
 
     def _device(self) -> torch.device:
         """The CUDA device of the parameters (the name the main model's helpers use); raises on a CPU module."""
@@ -475,6 +480,18 @@ class RNAModel(nn.Module):
         p = float((self.hparams["dropout"] if self.training else 0.0) if dropout is None else dropout)
         return p, (self._next_seed() if seed is None else int(seed))
 
+    def _augmented(self, X, mask, seed: int):
+        """``X + augment_eps * randn_like(X)`` of the reference's training forward (``feature.py:157-158``) on the device: every row with
+        sigma = ``augment_eps``, no keys, ``seed`` = the step's dropout seed, so the noise is fresh each step and a function of that seed
+        (``rnampnn_augment_coords``).  Eval-mode calls return ``X`` untouched without looking at ``augment_eps``."""
+        if not self.training or self.augment_eps <= 0.0:
+            return X
+        from rnampnn.utils.augment import augment_coords
+        dev = self._device()
+        Xd, md = _prep(X, dev), _prep(mask, dev)
+        sigma = torch.full((int(Xd.shape[0]),), self.augment_eps, dtype=torch.float32, device=dev)
+        return augment_coords(Xd, md, sigma, seed=seed)
+
     def _step_native(self, X, S, mask, p: float, seed: int, grad: torch.Tensor, return_logits: bool = False):
         """One ``rdesign_loss_and_grad_ex`` call in the arithmetic of ``train_precision``; the gradient of every parameter OVERWRITES ``grad`` (laid out like the weight arena)."""
         dev = self._ensure()
@@ -512,12 +529,12 @@ class RNAModel(nn.Module):
         """``training_step`` + ``loss.backward()`` of the reference (``rdesign.py:95-104``) in one native call (HIP kernels in the
         arithmetic of ``train_precision``, bit-reproducible): -> loss (device scalar) [, logits (N, 4) packed over the valid residues].  ``dropout``: None = the module's
         hyper-parameter in train mode and 0 in eval mode; the masks are a function of ``seed`` (None = the module's running counter,
-        ``manual_seed``).  Afterwards every ``p.grad`` is a view of ONE flat buffer ``self.flat_grad`` (OVERWRITTEN), so a
+        ``manual_seed``).  In train mode with ``augment_eps > 0`` the step sees ``X`` + N(0, augment_eps^2) noise drawn from the same seed.  Afterwards every ``p.grad`` is a view of ONE flat buffer ``self.flat_grad`` (OVERWRITTEN), so a
         data-parallel job averages gradients with one ``dist.all_reduce(model.flat_grad)``."""
         p, sd = self._train_args(dropout, seed)
         dev = self._ensure()
         self._bind_flat_grad(dev)
-        loss, logits = self._step_native(X, S, mask, p, sd, self.flat_grad, return_logits)
+        loss, logits = self._step_native(self._augmented(X, mask, sd), S, mask, p, sd, self.flat_grad, return_logits)
         if return_logits:
             self._check_mask(mask)
             return loss, logits[:int(mask.sum().item())]
@@ -529,6 +546,7 @@ class RNAModel(nn.Module):
         X, S, mask, lengths, _ = batch
         p, sd = self._train_args(None, None)
         self._ensure()
+        X = self._augmented(X, mask, sd)
         if not torch.is_grad_enabled():
             return self._step_native(X, S, mask, p, sd, torch.empty_like(self._flat))[0]
         return _TrainStep.apply(self, X, S, mask, p, sd, *[q for q, _, _ in self._slices])

@@ -14,6 +14,7 @@ import torch
 import torch.distributed as dist
 
 from rnampnn.utils import shard
+from rnampnn.utils.augment import EpochNoise
 from rnampnn.utils.data import bucket_batches
 from rnampnn.utils.train import plan_epoch
 
@@ -58,16 +59,21 @@ class Trainer:
 
     def run_epoch(self, items, lengths: Sequence[int], epoch: int, batch_size: int, max_rows: int) -> Dict:
         """One pass over ``items`` ((id, coords, labels) or (coords, labels)); -> dict(train_loss, steps, nt, seconds, nt_per_s) for THIS
-        rank's share.  The only host synchronisation is the one at the end of the epoch."""
+        rank's share.  The only host synchronisation is the one at the end of the epoch.  ``items`` may be an ``AugmentedItems``
+        (``lengths`` = its virtual lengths): its noisy samples get their noise on the device ahead of each step, on the six atoms the
+        loader keeps; ``validate`` never augments."""
         self.model.train()
         mine = self.plan(lengths, epoch, batch_size, max_rows)
         loader = padded_loader(items, mine, device=self.device)
         self.model.reserve_training((len(b), max(int(lengths[i]) for i in b)) for b in mine)
+        noise = EpochNoise.of(items, mine, self.device)     # AugmentedItems with noisy samples: this epoch's (sigma, key, offset) rows, uploaded once
         self._loss.zero_()
         torch.cuda.synchronize(self.device)
         t0 = time.perf_counter()
         nt = 0
         for it, (S, X, mask, lens, _) in enumerate(loader):
+            if noise is not None:
+                X = noise.apply(it, X, mask)
             self._loss += self.step(S, X, mask, seed=self.step_seed(epoch, it))
             nt += sum(lens)
         if self.sched is not None:

@@ -83,6 +83,7 @@ SYMBOLS = {
     "rnampnn_adam_step": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _F, _F, _F, _F, _F, _I32, _VP]),
     "rnampnn_train_backward": (C.c_int, [_VP, _I64, _VP, _I32, _I32, _I32, _VP, _VP, _SZ, _VP]),
     "rnampnn_loss_and_grad": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _F, C.c_uint64, _I32, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "rnampnn_augment_coords": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, C.c_uint64, _VP, _VP]),
     "rnampnn_profile_enable": (C.c_int, [_VP, _I32]),
     "rnampnn_profile_read": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(_I64), _I32]),
     "rnampnn_profile_read_kinds": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(_I64), _I32]),

@@ -17,6 +17,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import shard
+from .augment import EpochNoise
 from .data import PaddedLoader, bucket_batches
 
 
@@ -85,17 +86,22 @@ class Trainer:
 
     def run_epoch(self, items, lengths: Sequence[int], epoch: int, batch_size: int, max_rows: int) -> Dict:
         """One pass over ``items`` ((id, coords, labels) or (coords, labels)); -> dict(train_loss, steps, nt, seconds, nt_per_s)
-        for THIS rank's share.  The only host synchronisation is the one at the end of the epoch."""
+        for THIS rank's share.  The only host synchronisation is the one at the end of the epoch.  ``items`` may be an
+        ``AugmentedItems`` (``lengths`` = its virtual lengths): its noisy samples get their noise on the device ahead of each step
+        (``rnampnn_augment_coords``); ``validate`` never augments."""
         self.model.train()
         mine, t_glob = plan_epoch(lengths, self.rank, self.world, batch_size, max_rows, self.seed + epoch)
         loader = PaddedLoader(items, mine, device=self.device)
         # (the jittered plan has other batch shapes in every epoch: size the tape for this epoch's largest step before the clock starts)
         self.model.reserve_training((len(b), max(int(lengths[i]) for i in b)) for b in mine)
+        noise = EpochNoise.of(items, mine, self.device)     # AugmentedItems with noisy samples: this epoch's (sigma, key, offset) rows, uploaded once
         self._loss.zero_()
         torch.cuda.synchronize(self.device)
         t0 = time.perf_counter()
         nt = 0
         for it, (y, c, m, lens, _) in enumerate(loader):
+            if noise is not None:
+                c = noise.apply(it, c, m)
             tn = t_glob[it] if (self.global_t_norm and self.world > 1) else 0
             loss = self.step(y, c, m, T_norm=tn, seed=((self.seed << 20) + epoch * 100003 + it) * max(self.world, 1) + self.rank)
             self._loss += loss

@@ -72,6 +72,16 @@ def parse(argv=None):
     ap.add_argument("--out", default=None,
                     help="--model rdesign: directory for Final.pt (weights of the epoch with the best val_recovery_rate + constructor "
                          "arguments) and, with --fit-xgb, XGB.json")
+    ap.add_argument("--noise-augmentation", type=int, default=0, metavar="N",
+                    help="N noisy copies of training RNAs drawn with replacement, coordinates + N(0, --noise-std^2) added on the device "
+                         "(the reference's RNADataset.noise_augmentation, utils/data.py:278-295); training split only")
+    ap.add_argument("--slice-augmentation", type=int, default=0, metavar="N",
+                    help="N windows of exactly --slice-len residues cut from training RNAs (noisy copies included) longer than that "
+                         "(RNADataset.slice_augmentation, utils/data.py:297-324); training split only")
+    ap.add_argument("--slice-len", type=int, default=1000, help="window length of --slice-augmentation (the reference's MIN_LEN)")
+    ap.add_argument("--noise-std", type=float, default=1e-2, help="standard deviation of --noise-augmentation's noise")
+    ap.add_argument("--augment-eps", type=float, default=0.0,
+                    help="--model rdesign: X + eps * N(0, 1) on every training step (the reference's RNAFeatures(augment_eps))")
     return ap.parse_args(argv)
 
 
@@ -98,6 +108,18 @@ def _synthetic_items(args):
     return [(synth.synth_rna(int(n), i, seed=1), synth.synth_labels(int(n), i, seed=1)) for i, n in enumerate(lens)]
 
 
+def _augment(train, train_lens, args):
+    """--noise-augmentation / --slice-augmentation -> (training items, their lengths).  The TRAINING split only: the reference augments the
+    whole set before it splits (utils/data.py:402-438), which puts noisy copies of training RNAs into validation.  With both flags at 0
+    the list comes back as it is."""
+    if args.noise_augmentation or args.slice_augmentation:
+        from rnampnn.utils.augment import AugmentedItems
+        train = AugmentedItems(train, noise=args.noise_augmentation, slices=args.slice_augmentation, min_len=args.slice_len,
+                               noise_std=args.noise_std, seed=args.seed)
+        return train, [int(n) for n in train.lengths]
+    return train, train_lens
+
+
 def _split(items, args):
     n_val = 0 if args.no_validation else max(1, len(items) // 20)
     order0 = np.random.RandomState(args.seed).permutation(len(items))          # id-order-independent split
@@ -108,6 +130,8 @@ def run(args, log=print):
     """-> dict(epochs=[dict(train_loss, val_micro, val_macro, nt_per_s, steps, seconds)], n_train, n_val)."""
     if args.model == "rdesign":
         return run_rdesign(args, log)
+    if args.augment_eps:
+        raise ValueError("--augment-eps belongs to --model rdesign (the reference's RNAMPNN has no such argument)")
     rank, world, dev = _init_dist()
     if args.data:
         items = [(c, y) for _, c, y in load_rna_dir(args.data, max_len=args.max_len, nan_policy=args.nan_policy)]
@@ -127,9 +151,10 @@ def run(args, log=print):
     trainer = Trainer(model, opt, sched, world=world, rank=rank, global_t_norm=args.global_t_norm, seed=args.seed)
     train_lens = [c.shape[0] for c, _ in train]
     val_lens = [c.shape[0] for c, _ in val]
-    out = dict(epochs=[], n_train=len(train), n_val=len(val))
+    epoch_items, epoch_lens = _augment(train, train_lens, args)         # the tree read-out below is fitted on the plain training RNAs
+    out = dict(epochs=[], n_train=len(epoch_items), n_val=len(val))
     for epoch in range(args.epochs):
-        rec = trainer.run_epoch(train, train_lens, epoch, args.batch_size, args.max_nt)
+        rec = trainer.run_epoch(epoch_items, epoch_lens, epoch, args.batch_size, args.max_nt)
         if world > 1:       # whole-job rate: all nucleotides / slowest rank
             t = torch.tensor([rec["seconds"], float(rec["nt"])], dtype=torch.float64, device=dev)
             tmax = t.clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -161,6 +186,8 @@ def run_rdesign(args, log=print):
         items = _synthetic_items(args)                                                             # 7-atom records: the loader keeps the first six
     train, val = _split(items, args)
     kw = dict(k_neighbors=args.neighbours or 25, num_mpnn_layers=args.layers or 9, **rdesign_precisions(args.train_precision))
+    if args.augment_eps:
+        kw["augment_eps"] = args.augment_eps
     if args.dropout is not None:
         kw["dropout"] = args.dropout
     model = RNAModel(**kw).to(dev)
@@ -172,13 +199,14 @@ def run_rdesign(args, log=print):
     trainer = RDesignTrainer(model, opt, sched, world=world, rank=rank, seed=args.seed)
     train_lens = [c.shape[0] for c, _ in train]
     val_lens = [c.shape[0] for c, _ in val]
-    out = dict(epochs=[], n_train=len(train), n_val=len(val), best_epoch=None)
+    epoch_items, epoch_lens = _augment(train, train_lens, args)         # the tree read-out below is fitted on the plain training RNAs
+    out = dict(epochs=[], n_train=len(epoch_items), n_val=len(val), best_epoch=None)
     ckpt = os.path.join(args.out, "Final.pt") if args.out else None
     if ckpt and rank == 0:
         os.makedirs(args.out, exist_ok=True)
     best, nan = float("-inf"), float("nan")
     for epoch in range(args.epochs):
-        rec = trainer.run_epoch(train, train_lens, epoch, args.batch_size, args.max_nt)
+        rec = trainer.run_epoch(epoch_items, epoch_lens, epoch, args.batch_size, args.max_nt)
         if world > 1:       # whole-job rate: all nucleotides / slowest rank
             t = torch.tensor([rec["seconds"], float(rec["nt"])], dtype=torch.float64, device=dev)
             tmax = t.clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
