@@ -544,19 +544,21 @@ static MpnnWB wbf(rnampnn_ctx* c, const Mlp2& m) {
     return w;
 }
 
-// one fused step: [edge update with `we`] then [message + aggregation with `wm`]
-static void mpnn_step(Run& r, const Mlp2* we, const Mlp2* wm, const float* h_in, float* h_pre, float* msg_out, bool embed_first = false) {
+// one fused step: [edge update with `we`] then [message + aggregation with `wm`].  reverse (the round-4 kernel only, kernels_mpnn.hip): sweep the
+// blocks descending
+static void mpnn_step(Run& r, const Mlp2* we, const Mlp2* wm, const float* h_in, float* h_pre, float* msg_out, bool embed_first = false,
+                      int reverse = 0) {
     rnampnn_ctx* c = r.c;
     int k = c->cfg.num_res_neighbours;
     bool timed = c->prof && c->ev_used + 2 <= c->ev.size() && (c->prof_seen++ % c->prof_stride) == 0;
     if (timed) { c->ev_kind[c->ev_used / 2] = (we && wm) ? 0 : 1; (void)hipEventRecord(c->ev[c->ev_used], r.s); }
     if (embed_first) {      // layer 1's message with the edge embedding computed in front of it (e0 written once, never re-read)
         launch_resmpnn_embed_bf16(r.pk, k, r.w.nbr, (bf16_t*)r.w.e, r.w.geomh, derp<bf16_t>(c, c->edge_embed_img), rawp(c, c->edge_embed[0].b),
-                                  derp<float>(c, c->edge_embed_b1p), r.w.p_m, r.w.q_m, wbf(c, *wm), h_pre, h_in, r.s);
+                                  derp<float>(c, c->edge_embed_b1p), r.w.p_m, r.w.q_m, wbf(c, *wm), h_pre, h_in, reverse, r.s);
     } else if (r.fast) {
         launch_mpnn_bf16(r.pk, k, we != nullptr, wm != nullptr, r.w.nbr, (bf16_t*)r.w.e, r.w.p_e, r.w.q_e, r.w.p_m,
                          r.w.q_m, we ? wbf(c, *we) : MpnnWB{}, wm ? wbf(c, *wm) : MpnnWB{}, h_pre, msg_out, we && we->depth == 1,
-                         wm ? h_in : nullptr, r.s);      // h_pre = h_in + mean of the messages (both paths)
+                         wm ? h_in : nullptr, reverse, r.s);      // h_pre = h_in + mean of the messages (both paths)
     } else {
         MpnnW32 e32 = we ? w32(c, *we) : MpnnW32{}, m32 = wm ? w32(c, *wm) : MpnnW32{};
         launch_mpnn_f32(r.pk, k, we != nullptr, wm != nullptr, r.w.nbr, (float*)r.w.e, r.w.pq_e, r.w.pq_m, e32, m32,
@@ -691,9 +693,12 @@ static int forward_core(Run& r, rnampnn_handle h, const RnaMpnnForwardIO* io, co
 
     // ---- L x ResMPNN.forward (mpnn.py:283-294), edge update of layer l fused with the message of l+1
     if (!fused_first) node_pq(r, c->mpnn[0].msg, w.hA, false);
+    // The fused launches sweep e in alternating directions (layer 1 ascending): each reads first what the one before wrote last, which is what
+    // can still be in the Infinity Cache.
     bool edge_pending = false;                                 // layer l-1's edge update not yet applied
+    int n_fused = 0;                                           // ordinal of the next fused launch within this forward
     for (int l = 0; l < L; ++l) {
-        mpnn_step(r, edge_pending ? &c->mpnn[l - 1].edge : nullptr, &c->mpnn[l].msg, w.hA, w.hB, nullptr, l == 0 && embed_first);
+        mpnn_step(r, edge_pending ? &c->mpnn[l - 1].edge : nullptr, &c->mpnn[l].msg, w.hA, w.hB, nullptr, l == 0 && embed_first, n_fused++ & 1);
         bool tap_e = io->tap_layer == l + 1 && io->e_layer;
         edge_pending = l + 1 < L;                              // layer L's edge update is dead work
         const bool need_e = edge_pending || tap_e, need_m = l + 1 < L;
@@ -713,7 +718,7 @@ static int forward_core(Run& r, rnampnn_handle h, const RnaMpnnForwardIO* io, co
         if (io->tap_layer == l + 1) {
             if (io->h_layer) launch_unpack_nodes(r.pk, w.hA, RN_D, RN_D, io->h_layer, s);
             if (tap_e) {
-                mpnn_step(r, &c->mpnn[l].edge, nullptr, w.hA, w.hB, nullptr);
+                mpnn_step(r, &c->mpnn[l].edge, nullptr, w.hA, w.hB, nullptr, false, n_fused++ & 1);
                 edge_pending = false;
                 unpack_e(r, io->e_layer);
             }

@@ -27,14 +27,15 @@ void launch_edge_embed_bf16(const PackInfo& pk, int k, const float* geom, const 
 // node tables (launch_node_update): p_* = h.Wa^T + b1, q_* = h.Wb^T, f16 [N+1][128], natural channel order (row Nmax of q_* = zeros)
 void launch_mpnn_bf16(const PackInfo& pk, int k, bool do_edge, bool do_msg, const int* nbr, bf16_t* e,
                       const bf16_t* p_e, const bf16_t* q_e, const bf16_t* p_m, const bf16_t* q_m, MpnnWB we, MpnnWB wm,
-                      float* agg, float* msg_out, bool edge1, const float* h_res, hipStream_t s);   // agg [N][128]: h_res + masked mean of the messages (h_res null: the mean alone); edge1: the edge MLP has one Linear
+                      float* agg, float* msg_out, bool edge1, const float* h_res, int reverse, hipStream_t s);   // agg [N][128]: h_res + masked mean of the messages (h_res null: the mean alone); edge1: the edge MLP has one Linear
 
-// round-4 form of the fused step (kernels_mpnn.hip: two waves per SIMD, no helper MFMAs; layer 1 with the edge embedding in front); launch_mpnn_bf16 routes to it when it covers the case
+// round-4 form of the fused step (kernels_mpnn.hip: two waves per SIMD, no helper MFMAs; layer 1 with the edge embedding in front); launch_mpnn_bf16 routes to it when it covers the case.
+// reverse: the launch sweeps the blocks descending (ignored by the round-3 kernel)
 bool resmpnn_covers(int k, bool edge1, bool msg_out);
 void launch_resmpnn_embed_bf16(const PackInfo& pk, int k, const int* nbr, bf16_t* e, const float* geomh, const bf16_t* ee_img, const float* ee_b0,
-                               const float* ee_b1p, const bf16_t* p_m, const bf16_t* q_m, MpnnWB wm, float* agg, const float* h_res, hipStream_t s);
+                               const float* ee_b1p, const bf16_t* p_m, const bf16_t* q_m, MpnnWB wm, float* agg, const float* h_res, int reverse, hipStream_t s);
 void launch_resmpnn_bf16(const PackInfo& pk, int k, bool do_edge, bool do_msg, const int* nbr, bf16_t* e, const bf16_t* p_e, const bf16_t* q_e,
-                         const bf16_t* p_m, const bf16_t* q_m, MpnnWB we, MpnnWB wm, float* agg, const float* h_res, hipStream_t s);
+                         const bf16_t* p_m, const bf16_t* q_m, MpnnWB we, MpnnWB wm, float* agg, const float* h_res, int reverse, hipStream_t s);
 
 // fused FFN chain  X -> Linear(K0,H)+GELU -> NH x [Linear(H,H)+GELU] -> Linear(H,NOUT)  (see kernels_bf16.hip)
 void launch_build_chain_image(const float* wraw, int K_real, int K, int N, int n_real, int position, bf16_t* dst, hipStream_t s);   // position: 0 first, 1 hidden, 2 last Linear

@@ -643,9 +643,9 @@ static int num_cus() { return rn_num_cus(); }
 
 void launch_mpnn_bf16(const PackInfo& pk, int k, bool do_edge, bool do_msg, const int* nbr, bf16_t* e,
                       const bf16_t* p_e, const bf16_t* q_e, const bf16_t* p_m, const bf16_t* q_m, MpnnWB we, MpnnWB wm,
-                      float* agg, float* msg_out, bool edge1, const float* h_res, hipStream_t s) {
+                      float* agg, float* msg_out, bool edge1, const float* h_res, int reverse, hipStream_t s) {
     if (resmpnn_covers(k, edge1, msg_out != nullptr)) {
-        launch_resmpnn_bf16(pk, k, do_edge, do_msg, nbr, e, p_e, q_e, p_m, q_m, we, wm, agg, h_res, s);
+        launch_resmpnn_bf16(pk, k, do_edge, do_msg, nbr, e, p_e, q_e, p_m, q_m, we, wm, agg, h_res, reverse, s);
         return;
     }
     const int npb = k > 16 ? 1 : 32 / k;

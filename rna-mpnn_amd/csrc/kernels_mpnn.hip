@@ -23,6 +23,13 @@
 // memory skeleton only 123 - 127, compute only (no e / Q traffic) 135; of the compute-only 135: no LDS weight / init reads 100, no MFMA 85, no
 // activation arithmetic 98.  Its issue slots per block - ~1,115 vector instructions x 4.3 cycles, 128 MFMA x 8, 184 LDS reads x 4.5 - are 77 % of
 // the compute-only time: the kernel is bound by instruction issue; three waves per SIMD (RM_WAVES=12, <= 168 VGPRs, 9 - 14 spilled) are slower.
+// SWEEP DIRECTION: a launch walks its blocks ascending or descending (kernel argument `reverse`; the dealing scheme works on a logical block id, one
+// scalar translation gives the physical one), and a forward alternates the direction from launch to launch.  e (239 MiB at C2) is updated in place and
+// exceeds the 256 MiB Infinity Cache together with the node tables; swept the same way every time, no e line survives from its write to its next read.
+// Swept back and forth, a launch starts on what the launch before finished with.  Measured (C2, one box, interleaved, 6 rounds, profiles/sweep_ab_table.txt):
+// 2.214 - 2.230 ms per forward before, 2.182 - 2.194 with it, 2.224 - 2.242 for the same code with every launch ascending (-DRM_EXP_FWDSWEEP); 1.8 - 3.3 us per
+// launch under rocprofv3, 3.9 us live.  Results are bit-identical.  Measured and NOT kept (docs/experiments.md R9.1): the last launch without its e
+// write-back (-6 us for that launch, inside the step's noise), non-temporal e loads / stores (null).
 // Block = 32 edge slots of one residue (k > 16; slots >= k are padding and stay zero), one wave per block.
 #include "kernels_bf16.h"
 #include "bf16_dev.h"
@@ -33,7 +40,7 @@ static_assert(RN_E_F16 == 1 && RN_P_F16 == 1, "k_resmpnn works on f16 e and f16 
 // compile-time switches behind ONE build flag: tools/build_mpnn_variant.sh passes -DRN_EXPERIMENTS; build() never does.
 #if !defined(RN_EXPERIMENTS) && (defined(RM_EXP_NOQ) || defined(RM_EXP_NOESTORE) || defined(RM_EXP_NOELOAD) || defined(RM_EXP_NOMFMA) || defined(RM_EXP_NOGELU) || \
                                  defined(RM_EXP_NOLDS) || defined(RM_EXP_STAGGER) || defined(RM_EXP_PRIO) || defined(RM_WAVES) || defined(RM_RING8) || defined(RM_EDB) || \
-                                 defined(RM_QROLL) || defined(RM_NO_EPI_FENCE))
+                                 defined(RM_QROLL) || defined(RM_NO_EPI_FENCE) || defined(RM_EXP_FWDSWEEP))
 #error "experimental variants of k_resmpnn need -DRN_EXPERIMENTS (tools/build_mpnn_variant.sh)"
 #endif
 
@@ -80,7 +87,7 @@ __device__ __forceinline__ f16x4 rm_h4(unsigned w0, unsigned w1) {
 #define phi4s(y) (y)
 #endif
 template <bool DO_EDGE, bool DO_MSG, bool EMBED = false>
-__global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInfo pk, int k, const int* __restrict__ nbr, bf16_t* __restrict__ e,
+__global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInfo pk, int k, int reverse, const int* __restrict__ nbr, bf16_t* __restrict__ e,
         const bf16_t* __restrict__ p_e, const bf16_t* __restrict__ q_e, const bf16_t* __restrict__ p_m, const bf16_t* __restrict__ q_m,
         const float* __restrict__ h_res, const bf16_t* __restrict__ img_e_g, const float* __restrict__ b2e,
         const bf16_t* __restrict__ img_m_g, const float* __restrict__ b2m, float* __restrict__ agg,
@@ -104,15 +111,24 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
     // (tools/ubench/mfma_valu_coexec.hip: a static equal split waits for the slowest wave, 453 cycles per chain + epilogue per SIMD; with both
     // waves busy to the end it is 390).  Which wave computes a block does not change its result.  A wave claims its next-but-one block at the
     // top of every block and reads the answer at the bottom.
-    int blk_end, stride, first;
+    //
+    // SWEEP DIRECTION.  Everything above works on a LOGICAL block id.  Memory is indexed with the PHYSICAL id: the same id when the launch sweeps
+    // ascending, the mirror image inside the workgroup's own range [lo, blk_end) when it sweeps descending (`reverse`, wave-uniform).  The
+    // forward alternates the direction from one fused launch to the next (api.cpp: mpnn_step), so a launch reads first the part of e that the
+    // launch before it wrote last - the part that can still be in the 256 MiB Infinity Cache (e is 239 MiB at C2 and is updated in place; swept
+    // the same way every time, a line is evicted before it is read again).  Which wave computes a block, and when, does not enter its arithmetic.
+    int blk_end, stride, first, lo = 0;
     if ((gridDim.x & 7) == 0) {
         const int chunk = (nblocks + 7) >> 3, x = blockIdx.x & 7;
         blk_end = min(nblocks, (x + 1) * chunk);
         stride = (gridDim.x >> 3) * NW;
-        first = x * chunk + (blockIdx.x >> 3) * NW;
+        lo = x * chunk;
+        first = lo + (blockIdx.x >> 3) * NW;
     } else {
         blk_end = nblocks; stride = gridDim.x * NW; first = blockIdx.x * NW;
     }
+    const int mirror = lo + blk_end - 1;
+    auto phys = [&](int b) -> int { return __builtin_amdgcn_readfirstlane(reverse ? mirror - b : b); };      // (b: a wave-uniform logical id in [lo, blk_end))
     int* lds_ctr = reinterpret_cast<int*>(smem + RM_LDS_CTR);
     auto claim_issue = [&]() -> int {                    // lane 0 draws the ordinal ...
         int v = 0;
@@ -128,8 +144,8 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
     u32x4 ef[8];
     unsigned pn_e = 0u, pn_m = 0u;
     int jraw = -1;
+    const int b0 = __builtin_amdgcn_readfirstlane(blk < blk_end ? (reverse ? mirror - blk : blk) : 0);
     if (nblocks > 0) {
-        const int b0 = blk < blk_end ? blk : 0;
         const int i0 = b0 * k + r;
         jraw = nbr[i0 > last_idx ? last_idx : i0];
         if (!EMBED) {
@@ -315,7 +331,7 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
         for (int v = 0; v < 7; ++v) nrec[v] = src[v];
     };
     // ---- prologue: state of the first block, fragments and accumulator init of its first chain
-    int j = (slot_ok && blk < ntot) ? jraw : -1;
+    int j = (slot_ok && b0 < ntot) ? jraw : -1;
     if constexpr (EMBED) load_rec(j);
     gather_q(std::integral_constant<int, 0>{}, DO_EDGE ? q_e : q_m, j);
     gather_q(std::integral_constant<int, 1>{}, DO_EDGE ? q_e : q_m, j);
@@ -339,7 +355,8 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
         const int nblk = nxt;
         const int claim_v = claim_issue();
         const bool has_next = nblk < blk_end;
-        const int nb_c = has_next ? nblk : blk;            // the last iteration re-reads its own block (results unused)
+        const int pblk = phys(blk);                        // physical ids: every memory index below
+        const int nb_c = phys(has_next ? nblk : blk);      // the last iteration re-reads its own block (results unused)
         const int in_ = nb_c * k + r;
         const int jn_raw = nbr[in_ > last_idx ? last_idx : in_];
         if (DO_EDGE) pn_e = reinterpret_cast<const unsigned*>(p_e + (size_t)nb_c * RN_D)[lane];
@@ -368,17 +385,17 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
             chain(std::integral_constant<int, 2>{}, no_extra); epi_first(I2{}, a_pe + 384);
             chain(std::integral_constant<int, 3>{}, no_extra); epi_first(I3{}, a_be);
             // edge Linear 2: T = b2 + W2_e . hidden;  e += GELU(T)
-            chain(std::integral_constant<int, 4>{}, no_extra); if constexpr (DO_MSG) RM_GQ_FULL(q_m, j); epi_edge(I0{}, a_be + 128, blk);
-            chain(std::integral_constant<int, 5>{}, no_extra); epi_edge(I1{}, a_be + 256, blk);
+            chain(std::integral_constant<int, 4>{}, no_extra); if constexpr (DO_MSG) RM_GQ_FULL(q_m, j); epi_edge(I0{}, a_be + 128, pblk);
+            chain(std::integral_constant<int, 5>{}, no_extra); epi_edge(I1{}, a_be + 256, pblk);
             if constexpr (DO_MSG) {
-                chain(std::integral_constant<int, 6>{}, no_extra); RM_GQ_ROLL(I0{}, q_m, j); epi_edge(I2{}, a_be + 384, blk);
-                chain(std::integral_constant<int, 7>{}, no_extra); RM_GQ_ROLL(I1{}, q_m, j); epi_edge(I3{}, a_pm, blk);
+                chain(std::integral_constant<int, 6>{}, no_extra); RM_GQ_ROLL(I0{}, q_m, j); epi_edge(I2{}, a_be + 384, pblk);
+                chain(std::integral_constant<int, 7>{}, no_extra); RM_GQ_ROLL(I1{}, q_m, j); epi_edge(I3{}, a_pm, pblk);
             } else {
-                chain(std::integral_constant<int, 6>{}, no_extra); epi_edge(I2{}, a_be + 384, blk);
+                chain(std::integral_constant<int, 6>{}, no_extra); epi_edge(I2{}, a_be + 384, pblk);
                 chain(std::integral_constant<int, 7>{}, no_extra);
                 // edge update only (taps, stage API): the last epilogue rewrites e, so the next block's state is requested behind it
                 stage_p();
-                epi_edge(I3{}, a_next, blk);
+                epi_edge(I3{}, a_next, pblk);
                 RM_GQ_ROLL(I0{}, q_e, jn); RM_GQ_ROLL(I1{}, q_e, jn); RM_GQ_FULL(q_e, jn);
 #pragma unroll
                 for (int s = 0; s < 8; ++s) ef[s] = rm_efrag(e, nb_c, lane)[64 * s];
@@ -388,7 +405,7 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
             // ---- edge featurisation + embedding MLP of THIS block (feature.py:386-571; the arithmetic of k_edge_embed_bf16): e0 is formed in the
             // registers the message MLP reads it from and stored once - the 236 MB re-read of e0 and one launch disappear.  The CENTRAL residue
             // is wave-uniform: its record is read with scalar loads and enters the vector arithmetic as SGPR operands.
-            const float* __restrict__ gc = geomh + (size_t)__builtin_amdgcn_readfirstlane(blk) * RN_GEOMH;
+            const float* __restrict__ gc = geomh + (size_t)pblk * RN_GEOMH;
             auto catom = [&](int a, int d) { return a < 4 ? gc[3 * a + d] : gc[32 + 3 * (a - 4) + d]; };
             auto cbond = [&](int a, int d) { return a < 3 ? gc[12 + 3 * a + d] : gc[32 + 12 + 3 * (a - 3) + d]; };
             auto cnorm = [&](int a, int d) { return a < 2 ? gc[21 + 3 * a + d] : gc[32 + 21 + 3 * (a - 2) + d]; };
@@ -454,7 +471,7 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
                     const int sp = v >> 1, t = 2 * (v & 1);
                     ef[2 * ob + sp][t] = __builtin_bit_cast(unsigned, lo2(g)) & emask;
                     ef[2 * ob + sp][t + 1] = __builtin_bit_cast(unsigned, hi2(g)) & emask;
-                    if (v & 1) rm_efrag(e, blk, lane)[64 * (2 * ob + sp)] = ef[2 * ob + sp];
+                    if (v & 1) rm_efrag(e, pblk, lane)[64 * (2 * ob + sp)] = ef[2 * ob + sp];
                 }
                 RM_FENCE();
             });
@@ -478,13 +495,13 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
             float hres[4] = {0.f, 0.f, 0.f, 0.f};
             if (h_res) {
 #pragma unroll
-                for (int nb = 0; nb < 4; ++nb) hres[nb] = h_res[(size_t)blk * RN_D + 32 * nb + r];
+                for (int nb = 0; nb < 4; ++nb) hres[nb] = h_res[(size_t)pblk * RN_D + 32 * nb + r];
             }
             // message Linear 2, un-transposed: T[edge][channel] = hidden . W2_m^T
-            chain(std::integral_constant<int, 12>{}, no_extra); RM_GQ_FULL(DO_EDGE ? q_e : q_m, jn); epi_mean(I0{}, -1, blk, cabs, inv, hres[0]);
-            chain(std::integral_constant<int, 13>{}, no_extra); epi_mean(I1{}, -1, blk, cabs, inv, hres[1]);
-            chain(std::integral_constant<int, 14>{}, no_extra); RM_GQ_ROLL(I0{}, DO_EDGE ? q_e : q_m, jn); epi_mean(I2{}, -1, blk, cabs, inv, hres[2]);
-            chain(std::integral_constant<int, 15>{}, no_extra); RM_GQ_ROLL(I1{}, DO_EDGE ? q_e : q_m, jn); epi_mean(I3{}, EMBED ? -1 : a_next, blk, cabs, inv, hres[3]);
+            chain(std::integral_constant<int, 12>{}, no_extra); RM_GQ_FULL(DO_EDGE ? q_e : q_m, jn); epi_mean(I0{}, -1, pblk, cabs, inv, hres[0]);
+            chain(std::integral_constant<int, 13>{}, no_extra); epi_mean(I1{}, -1, pblk, cabs, inv, hres[1]);
+            chain(std::integral_constant<int, 14>{}, no_extra); RM_GQ_ROLL(I0{}, DO_EDGE ? q_e : q_m, jn); epi_mean(I2{}, -1, pblk, cabs, inv, hres[2]);
+            chain(std::integral_constant<int, 15>{}, no_extra); RM_GQ_ROLL(I1{}, DO_EDGE ? q_e : q_m, jn); epi_mean(I3{}, EMBED ? -1 : a_next, pblk, cabs, inv, hres[3]);
         }
 #ifdef RM_EDB
 #pragma unroll
@@ -518,8 +535,12 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
 // RNAMPNN_MPNN_V3=1: the round-3 kernel (A/B switch)
 bool resmpnn_covers(int k, bool edge1, bool msg_out) { return k > 16 && k <= 32 && !edge1 && !msg_out && !ab_switch("RNAMPNN_MPNN_V3"); }
 
+// reverse: sweep the blocks descending (see SWEEP DIRECTION in the kernel)
 void launch_resmpnn_bf16(const PackInfo& pk, int k, bool do_edge, bool do_msg, const int* nbr, bf16_t* e, const bf16_t* p_e, const bf16_t* q_e,
-                         const bf16_t* p_m, const bf16_t* q_m, MpnnWB we, MpnnWB wm, float* agg, const float* h_res, hipStream_t s) {
+                         const bf16_t* p_m, const bf16_t* q_m, MpnnWB we, MpnnWB wm, float* agg, const float* h_res, int reverse, hipStream_t s) {
+#ifdef RM_EXP_FWDSWEEP      /* A/B arm: every launch sweeps ascending */
+    reverse = 0;
+#endif
     const int max_blocks = pk.Nmax;
     int grid = (max_blocks + RM_WAVES - 1) / RM_WAVES;
     if (grid >= 8) grid = (grid + 7) & ~7;            // a multiple of 8 switches the kernel to its XCD-aware block mapping
@@ -530,8 +551,8 @@ void launch_resmpnn_bf16(const PackInfo& pk, int k, bool do_edge, bool do_msg, c
     do {                                                                                                       \
         static DevAttr attr;                                                                                   \
         ensure_dyn_lds((const void*)k_resmpnn<E, M>, RM_LDS_BYTES, attr);                                      \
-        hipLaunchKernelGGL((k_resmpnn<E, M>), dim3(grid), dim3(RM_WAVES * 64), RM_LDS_BYTES, s, pk, k, nbr, e, p_e, q_e, p_m, q_m, h_res, \
-                           we.img, we.b2p, wm.img, wm.b2p, agg);                                               \
+        hipLaunchKernelGGL((k_resmpnn<E, M>), dim3(grid), dim3(RM_WAVES * 64), RM_LDS_BYTES, s, pk, k, reverse ? 1 : 0, nbr, e, p_e, q_e, p_m, \
+                           q_m, h_res, we.img, we.b2p, wm.img, wm.b2p, agg, (const float*)nullptr, (const float*)nullptr); \
     } while (0)
     if (do_edge && do_msg) RM_LAUNCH(true, true);
     else if (do_edge) RM_LAUNCH(true, false);
@@ -541,7 +562,11 @@ void launch_resmpnn_bf16(const PackInfo& pk, int k, bool do_edge, bool do_msg, c
 
 // Layer 1's message launch with the edge embedding in front of it: e0 is computed from the geometry records, stored once and consumed from registers.
 void launch_resmpnn_embed_bf16(const PackInfo& pk, int k, const int* nbr, bf16_t* e, const float* geomh, const bf16_t* ee_img, const float* ee_b0,
-                               const float* ee_b1p, const bf16_t* p_m, const bf16_t* q_m, MpnnWB wm, float* agg, const float* h_res, hipStream_t s) {
+                               const float* ee_b1p, const bf16_t* p_m, const bf16_t* q_m, MpnnWB wm, float* agg, const float* h_res, int reverse,
+                               hipStream_t s) {
+#ifdef RM_EXP_FWDSWEEP
+    reverse = 0;
+#endif
     int grid = (pk.Nmax + RM_WAVES - 1) / RM_WAVES;
     if (grid >= 8) grid = (grid + 7) & ~7;
     const int cus = rn_num_cus();
@@ -549,6 +574,6 @@ void launch_resmpnn_embed_bf16(const PackInfo& pk, int k, const int* nbr, bf16_t
     if (grid < 1) grid = 1;
     static DevAttr attr;
     ensure_dyn_lds((const void*)k_resmpnn<false, true, true>, RM_LDS_BYTES, attr);
-    hipLaunchKernelGGL((k_resmpnn<false, true, true>), dim3(grid), dim3(RM_WAVES * 64), RM_LDS_BYTES, s, pk, k, nbr, e, (const bf16_t*)nullptr,
+    hipLaunchKernelGGL((k_resmpnn<false, true, true>), dim3(grid), dim3(RM_WAVES * 64), RM_LDS_BYTES, s, pk, k, reverse ? 1 : 0, nbr, e, (const bf16_t*)nullptr,
                        (const bf16_t*)nullptr, p_m, q_m, h_res, ee_img, ee_b1p, wm.img, wm.b2p, agg, geomh, ee_b0);
 }
