@@ -1,45 +1,12 @@
-// Device-side helpers shared by the bf16 / f16 MFMA kernels (kernels_bf16.hip, kernels_mpnn.hip): vector types, conversions,
-// the packed-f16 activation arithmetic, LDS staging of weight images, and the channel orders of a 32 x 32 accumulator tile.
+// Device-side helpers shared by the bf16 / f16 MFMA kernels (kernels_bf16.hip, kernels_mpnn.hip): on top of the bf16 primitives of
+// bf16_core.h, the packed-f16 activation arithmetic, LDS staging of weight images, and the channel orders of a 32 x 32 accumulator tile.
 #pragma once
-#include "rnampnn_internal.h"
+#include "bf16_core.h"            // vector types, f2bf / bf2f / pack2 / lo_bf / hi_bf, mfma32, gelu_erf / gelu_fast, kSEPS
 #include <type_traits>
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
-static constexpr float kSEPS = 1.0e-6f;
 #define RN_E_F16 1                // the edge tensor e is stored as f16 of a e (bf16 in rounds 1 - 2)
 #define RN_P_F16 1                // the P / Q tables are f16
 #define RN_PHI_DEG 4              // coefficients of Phi's polynomial in the per-edge kernels
-
-__device__ __forceinline__ bf16_t f2bf(float x) { return __builtin_bit_cast(bf16_t, (__bf16)x); }   // RNE, NaN kept
-__device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((unsigned)v) << 16); }
-__device__ __forceinline__ unsigned pack2(float a, float b) {        // one v_cvt_pk_bf16_f32
-    f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_bf(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float hi_bf(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
-
-__device__ __forceinline__ f32x16 mfma32(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// GELU for the bf16 path: x * sigmoid(x * (c0 + c1 x^2)), coefficients minimax-fitted to the exact
-// erf form (max |err| 2.7e-4 at |x| ~ 2-3, 15-30x below the bf16 rounding of the result there);
-// monotone argument, so no clamp: 7 VALU instructions, 2 of them transcendental.
-// The f32 path and the node-level GEMM epilogues keep erff().
-__device__ __forceinline__ float gelu_fast(float x) {
-    float t = x * x;
-    float p = fmaf(t, -0.10012571f, -2.3087657f);          // -log2(e) * (c0 + c1 t), c0 = 1.60031416, c1 = 0.06940179
-    float ex = __builtin_amdgcn_exp2f(x * p);              // exp(-x (c0 + c1 t))
-    return x * __builtin_amdgcn_rcpf(1.0f + ex);
-}
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 
 // Packed-f16 activation arithmetic of the fused ResMPNN kernel: the kernel is VALU-issue
 // bound on GELU, and v_pk_*_f16 evaluates two activations per instruction with no transcendental.

@@ -5,15 +5,11 @@
 // the graph / geometry / normalisation / decode kernels here serve both precisions.
 // Reference lines restated by each kernel are cited at its head.
 #include "rnampnn_internal.h"
+#include "bf16_core.h"             // kSEPS, gelu_erf
 #include <cstdlib>
 
 #define WAVE 64
 static constexpr float kLEPS = 1.0e6f;
-static constexpr float kSEPS = 1.0e-6f;
-
-__device__ __forceinline__ float gelu_erf(float x) {           // nn.GELU() default (erf form)
-    return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
-}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -23,6 +23,9 @@ static inline TDrop t_drop(float p, unsigned long long seed, const unsigned long
     return d;
 }
 
+// blocks of a grid-stride element-wise launch over `units` work items, 256 per block: at least one, at most 16384
+static inline unsigned ew_grid(size_t units) { const size_t g = (units + 255) / 256; return (unsigned)(g < 16384 ? (g ? g : 1) : 16384); }
+
 void t_gemm(const TRows& rows, const float* X, int ldx, int K, const float* Wt, int ldw, const float* bias, int N,
             float* Y, int ldy, int beta, hipStream_t s);                      // Y = beta*Y + X.Wt + bias   (Wt K-major, row stride ldw)
 // Ordered reductions of one backward (kernels_train.hip: RedQueue).  Between red_begin and red_end every producer of partial tiles (t_gemm_tn,

@@ -5,6 +5,8 @@
 // segment mean / scatter, GraphNorm and attention backward).  Reference: rnampnn.py:151-154,187-207
 // (loss = cross_entropy(softmax(logits)[valid], label), mean over valid nucleotides) and the forward
 // lines cited in kernels_f32.hip.  Dropout: counter-hash masks (TDrop, kernels_train.h); every cross-workgroup sum is an ordered two-stage reduction (no float atomics).
+// Device primitives: bf16_core.h (bf16 packs, mfma32, gelu_erf / gelu_fast) through train_dev.h (GELU derivatives, dropout hash); the 128 x 128
+// weight-gradient kernels (k_mm_tn, k_emm_tn, k_emm_bwd1, k_emm_bwd2) share one tile core: tn_row .. wf_dn beside tr_frag.
 #include "kernels_train.h"
 #include "train_dev.h"
 #include <cstdio>
@@ -13,7 +15,6 @@
 #include <algorithm>
 #include <climits>
 
-static constexpr float kSEPS = 1.0e-6f;
 #define TLD 132
 
 // ------------------------------------------------------------------------------------------
@@ -284,7 +285,7 @@ void t_colsum(const TRows& rows, const float* A, int lda, int M, float* out, hip
 __global__ void k_gelu_fwd(TRows rows, const float* __restrict__ x, float* __restrict__ y, int D, TDrop dr, unsigned site) {
     const size_t n = (size_t)nrows(rows) * D;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        y[i] = gelu_f(x[i]) * drop_mul(dr, site, i);
+        y[i] = gelu_erf(x[i]) * drop_mul(dr, site, i);
 }
 __global__ void k_gelu_bwd(TRows rows, const float* __restrict__ dy, const float* __restrict__ pre, float* __restrict__ dx, int D,
                            TDrop dr, unsigned site) {
@@ -296,16 +297,15 @@ __global__ void k_add(TRows rows, const float* __restrict__ a, float* __restrict
     const size_t n = (size_t)nrows(rows) * D;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] += a[i];
 }
-static unsigned ew_grid(const TRows& r, int D) { size_t g = ((size_t)r.maxrows * D + 255) / 256; return (unsigned)(g < 16384 ? (g ? g : 1) : 16384); }
 void t_gelu_fwd(const TRows& rows, const float* x, float* y, int D, const TDrop& dr, unsigned site, hipStream_t s) {
-    hipLaunchKernelGGL(k_gelu_fwd, dim3(ew_grid(rows, D)), dim3(256), 0, s, rows, x, y, D, dr, site);
+    hipLaunchKernelGGL(k_gelu_fwd, dim3(ew_grid((size_t)rows.maxrows * D)), dim3(256), 0, s, rows, x, y, D, dr, site);
 }
 void t_gelu_bwd(const TRows& rows, const float* dy, const float* pre, float* dx, int D, const TDrop& dr, unsigned site,
                 hipStream_t s) {
-    hipLaunchKernelGGL(k_gelu_bwd, dim3(ew_grid(rows, D)), dim3(256), 0, s, rows, dy, pre, dx, D, dr, site);
+    hipLaunchKernelGGL(k_gelu_bwd, dim3(ew_grid((size_t)rows.maxrows * D)), dim3(256), 0, s, rows, dy, pre, dx, D, dr, site);
 }
 void t_add(const TRows& rows, const float* a, float* dst, int D, hipStream_t s) {
-    hipLaunchKernelGGL(k_add, dim3(ew_grid(rows, D)), dim3(256), 0, s, rows, a, dst, D);
+    hipLaunchKernelGGL(k_add, dim3(ew_grid((size_t)rows.maxrows * D)), dim3(256), 0, s, rows, a, dst, D);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -355,13 +355,8 @@ __global__ void k_edge_features_b(PackInfo pk, int k, const float* __restrict__ 
         for (int b = 0; b < 4; ++b)
             v[74 + a * 4 + b] = gi[36 + a * 3] * gj[36 + b * 3] + gi[37 + a * 3] * gj[37 + b * 3] + gi[38 + a * 3] * gj[38 + b * 3];
     for (int i = RN_ERAW; i < 96; ++i) v[i] = 0.f;
-    auto pk2 = [](float a, float b) {                     // round-to-nearest-even bf16 pair (tpack2 is defined further down)
-        typedef __attribute__((ext_vector_type(2))) float f2; typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-        f2 t = {a, b};
-        return __builtin_bit_cast(unsigned, __builtin_convertvector(t, b2));
-    };
 #pragma unroll
-    for (int i = 0; i < 12; ++i) x[i] = make_uint4(pk2(v[8 * i], v[8 * i + 1]), pk2(v[8 * i + 2], v[8 * i + 3]), pk2(v[8 * i + 4], v[8 * i + 5]), pk2(v[8 * i + 6], v[8 * i + 7]));
+    for (int i = 0; i < 12; ++i) x[i] = make_uint4(pack2(v[8 * i], v[8 * i + 1]), pack2(v[8 * i + 2], v[8 * i + 3]), pack2(v[8 * i + 4], v[8 * i + 5]), pack2(v[8 * i + 6], v[8 * i + 7]));
     for (int i = 12; i < 16; ++i) x[i] = make_uint4(0u, 0u, 0u, 0u);
 }
 void te_edge_features(const PackInfo& pk, int k, const float* geom, const int* nbr, tb16* F, hipStream_t s) {
@@ -398,23 +393,22 @@ __global__ void k_edge_elem(PackInfo pk, int k, const int* __restrict__ nbr, int
             if (j >= 0) {
                 const float4 g = reinterpret_cast<const float4*>(src2 + er * RN_D)[q];
                 const unsigned long long i0 = (unsigned long long)er * RN_D + 4 * q;
-                a.x += gelu_f(g.x) * drop_mul(dr, site, i0); a.y += gelu_f(g.y) * drop_mul(dr, site, i0 + 1);
-                a.z += gelu_f(g.z) * drop_mul(dr, site, i0 + 2); a.w += gelu_f(g.w) * drop_mul(dr, site, i0 + 3);
+                a.x += gelu_erf(g.x) * drop_mul(dr, site, i0); a.y += gelu_erf(g.y) * drop_mul(dr, site, i0 + 1);
+                a.z += gelu_erf(g.z) * drop_mul(dr, site, i0 + 2); a.w += gelu_erf(g.w) * drop_mul(dr, site, i0 + 3);
             }
             *xp = a;
         }
     }
 }
-static unsigned edge_grid(const PackInfo& pk, int k) { size_t g = ((size_t)pk.Nmax * k * 32 + 255) / 256; return (unsigned)(g < 16384 ? (g ? g : 1) : 16384); }
 void t_edge_add_pq(const PackInfo& pk, int k, const int* nbr, const float* pq, float* pre, hipStream_t s) {
-    hipLaunchKernelGGL(k_edge_elem, dim3(edge_grid(pk, k)), dim3(256), 0, s, pk, k, nbr, 0, pq, pre, nullptr, nullptr, TDrop{0, 0, 1.f}, 0u);
+    hipLaunchKernelGGL(k_edge_elem, dim3(ew_grid((size_t)pk.Nmax * k * 32)), dim3(256), 0, s, pk, k, nbr, 0, pq, pre, nullptr, nullptr, TDrop{0, 0, 1.f}, 0u);
 }
 void t_edge_zero_invalid(const PackInfo& pk, int k, const int* nbr, float* x, hipStream_t s) {
-    hipLaunchKernelGGL(k_edge_elem, dim3(edge_grid(pk, k)), dim3(256), 0, s, pk, k, nbr, 1, nullptr, x, nullptr, nullptr, TDrop{0, 0, 1.f}, 0u);
+    hipLaunchKernelGGL(k_edge_elem, dim3(ew_grid((size_t)pk.Nmax * k * 32)), dim3(256), 0, s, pk, k, nbr, 1, nullptr, x, nullptr, nullptr, TDrop{0, 0, 1.f}, 0u);
 }
 void t_edge_residual(const PackInfo& pk, int k, const int* nbr, const float* e_in, const float* pre2, float* e_out,
                      const TDrop& dr, unsigned site, hipStream_t s) {
-    hipLaunchKernelGGL(k_edge_elem, dim3(edge_grid(pk, k)), dim3(256), 0, s, pk, k, nbr, 2, nullptr, e_out, e_in, pre2, dr, site);
+    hipLaunchKernelGGL(k_edge_elem, dim3(ew_grid((size_t)pk.Nmax * k * 32)), dim3(256), 0, s, pk, k, nbr, 2, nullptr, e_out, e_in, pre2, dr, site);
 }
 
 // forward: out[p] = h[p] + sum_valid gelu(pre2[e]) / max(cnt,1);   backward: dpre2[e] = valid ? dagg[p]/cnt * gelu'(pre2[e]) : 0
@@ -427,7 +421,7 @@ __global__ void __launch_bounds__(128) k_seg_mean(PackInfo pk, int k, const int*
     for (int sl = 0; sl < k; ++sl) {
         if (nbr[(size_t)p * k + sl] >= 0) {
             const size_t o = ((size_t)p * k + sl) * RN_D + c;
-            s += gelu_f(pre2[o]) * drop_mul(dr, site, o);
+            s += gelu_erf(pre2[o]) * drop_mul(dr, site, o);
             ++cnt;
         }
     }
@@ -463,7 +457,7 @@ __global__ void k_edge_res_bwd(PackInfo pk, int k, const int* __restrict__ nbr, 
 }
 void t_edge_res_bwd(const PackInfo& pk, int k, const int* nbr, const float* de, const float* pre2, float* dpre2,
                     const TDrop& dr, unsigned site, hipStream_t s) {
-    hipLaunchKernelGGL(k_edge_res_bwd, dim3(edge_grid(pk, k)), dim3(256), 0, s, pk, k, nbr, de, pre2, dpre2, dr, site);
+    hipLaunchKernelGGL(k_edge_res_bwd, dim3(ew_grid((size_t)pk.Nmax * k * 32)), dim3(256), 0, s, pk, k, nbr, de, pre2, dpre2, dr, site);
 }
 // Reverse adjacency of the k-NN graph (built once per training forward): for every packed row j the edge rows
 // (p*k + slot) whose neighbour is j, ascending - the gather form of the backward's only true scatter (d Q[j] += ...).
@@ -886,29 +880,13 @@ void t_pack_dlogits(const PackInfo& pk, const float* dlogits_padded, float* dlog
 // Optional fused element-wise work (saves whole passes over the [E][128] f32 tape):
 //   operand prologue  a = drop(gelu(pre))         (GELU + dropout of a taped pre-activation, never materialised)
 //   result epilogue   y = acc * gelu'(pre) * mask (backward through GELU + dropout)
-typedef __attribute__((ext_vector_type(8))) __bf16 tbf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 tbf16x2;
-typedef __attribute__((ext_vector_type(2))) float tf32x2;
-typedef __attribute__((ext_vector_type(4))) float tf32x4;
-typedef __attribute__((ext_vector_type(16))) float tf32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned tu32x4;
-__device__ __forceinline__ unsigned tpack2(float a, float b) {
-    tf32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, tbf16x2));
-}
-__device__ __forceinline__ tf32x16 tmfma(tu32x4 a, tu32x4 b, tf32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(tbf16x8, a), __builtin_bit_cast(tbf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ tu32x4 tpack8(const float (&v)[8]) {
-    return tu32x4{tpack2(v[0], v[1]), tpack2(v[2], v[3]), tpack2(v[4], v[5]), tpack2(v[6], v[7])};
-}
 // fragment whose k index runs along a ROW of src: 8 consecutive floats at src[row][k0 .. k0+7] (two 16-byte loads);
 // act: a = drop(gelu(x)), dropout index row * ld_idx + k
-__device__ __forceinline__ tu32x4 frag_row(const float* __restrict__ src, int ld, int row, int nrows, int k0, bool act,
+__device__ __forceinline__ u32x4 frag_row(const float* __restrict__ src, int ld, int row, int nrows, int k0, bool act,
                                            const TDrop& dr, unsigned site, int ld_idx) {
     const bool ok = row < nrows;
     const float* p = src + (size_t)(ok ? row : 0) * ld + k0;
-    const tf32x4 a = *reinterpret_cast<const tf32x4*>(p), b = *reinterpret_cast<const tf32x4*>(p + 4);
+    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
     float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
     if (act) {                                  // (ld_idx and k0 are multiples of 8)
         float dm[8];
@@ -920,10 +898,10 @@ __device__ __forceinline__ tu32x4 frag_row(const float* __restrict__ src, int ld
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = 0.f;
     }
-    return tpack8(v);
+    return pack8(v);
 }
 // fragment whose k index runs DOWN a column of src: src[k0 + j][col], j = 0..7 (8 dword loads, coalesced across lanes)
-__device__ __forceinline__ tu32x4 frag_col(const float* __restrict__ src, int ld, int k0, int nk, int col, int ncols, bool act,
+__device__ __forceinline__ u32x4 frag_col(const float* __restrict__ src, int ld, int k0, int nk, int col, int ncols, bool act,
                                            const TDrop& dr, unsigned site, int ld_idx) {
     float v[8];
     const int cc = col < ncols ? col : 0;
@@ -935,7 +913,7 @@ __device__ __forceinline__ tu32x4 frag_col(const float* __restrict__ src, int ld
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) if (k0 + j >= nk || col >= ncols) v[j] = 0.f;
-    return tpack8(v);
+    return pack8(v);
 }
 
 // ---- bf16 fragment images of 128 x 128 weight blocks (32 KiB: [k-step 8][channel block 4][lane 64][8 bf16]) for the
@@ -953,13 +931,13 @@ __device__ __forceinline__ void build_wimage(unsigned short* img, const float* _
         const int ks = k >> 4, hh = (k >> 3) & 1, j = k & 7, cb = c >> 5, c5 = c & 31;
         int rr = c5;
         if (layout == 1) { const int i = 8 * (c5 >> 4) + (c5 & 7), hq = (c5 >> 3) & 1; rr = (i & 3) + 8 * (i >> 2) + 4 * hq; }
-        *reinterpret_cast<unsigned*>(img + (((ks * 4 + cb) * 64 + hh * 32 + rr) * 8 + j)) = tpack2(v0, v1);
+        *reinterpret_cast<unsigned*>(img + (((ks * 4 + cb) * 64 + hh * 32 + rr) * 8 + j)) = pack2(v0, v1);
     }
 }
 __device__ __forceinline__ void stage_wimage(unsigned short* img, const unsigned short* __restrict__ prebuilt, const float* __restrict__ W, int ldw,
                                              bool b_rows, int layout, int tid, int kvalid = 128) {
     if (prebuilt) {
-        for (int e = tid; e < 2048; e += 256) reinterpret_cast<tu32x4*>(img)[e] = reinterpret_cast<const tu32x4*>(prebuilt)[e];
+        for (int e = tid; e < 2048; e += 256) reinterpret_cast<u32x4*>(img)[e] = reinterpret_cast<const u32x4*>(prebuilt)[e];
     } else {
         build_wimage(img, W, ldw, b_rows, layout, kvalid, tid, 256);
     }
@@ -1029,7 +1007,7 @@ __global__ void __launch_bounds__(256) k_mm(TRows rows, const float* __restrict_
     const int m0 = blockIdx.x * (128 * MT) + wave * (32 * MT);
     if (blockIdx.x * (128 * MT) >= R) return;
     const int n0 = blockIdx.y * 128;
-    tf32x16 acc[MT][4];
+    f32x16 acc[MT][4];
 #pragma unroll
     for (int a = 0; a < MT; ++a)
 #pragma unroll
@@ -1044,7 +1022,7 @@ __global__ void __launch_bounds__(256) k_mm(TRows rows, const float* __restrict_
         for (int a = 0; a < MT; ++a) {
             const int row = m0 + 32 * a + r;
             const float* p = X + (size_t)(row < R ? row : 0) * ldx + k0 + 8 * h;
-            const tf32x4 u = *reinterpret_cast<const tf32x4*>(p), v = *reinterpret_cast<const tf32x4*>(p + 4);
+            const f32x4 u = *reinterpret_cast<const f32x4*>(p), v = *reinterpret_cast<const f32x4*>(p + 4);
 #pragma unroll
             for (int q = 0; q < 4; ++q) { ra[a][q] = u[q]; ra[a][4 + q] = v[q]; }
         }
@@ -1054,7 +1032,7 @@ __global__ void __launch_bounds__(256) k_mm(TRows rows, const float* __restrict_
             const int cc = col < N ? col : 0;
             if (B_ROWS) {
                 const float* p = W + (size_t)cc * ldw + k0 + 8 * h;
-                const tf32x4 u = *reinterpret_cast<const tf32x4*>(p), v = *reinterpret_cast<const tf32x4*>(p + 4);
+                const f32x4 u = *reinterpret_cast<const f32x4*>(p), v = *reinterpret_cast<const f32x4*>(p + 4);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) { rb[b][q] = u[q]; rb[b][4 + q] = v[q]; }
             } else {
@@ -1065,7 +1043,7 @@ __global__ void __launch_bounds__(256) k_mm(TRows rows, const float* __restrict_
     };
     load_step(0);
     for (int k0 = 0; k0 < K; k0 += 16) {
-        tu32x4 af[MT], bf[4];
+        u32x4 af[MT], bf[4];
 #pragma unroll
         for (int a = 0; a < MT; ++a) {
             const int row = m0 + 32 * a + r;
@@ -1082,7 +1060,7 @@ __global__ void __launch_bounds__(256) k_mm(TRows rows, const float* __restrict_
 #pragma unroll
                 for (int q = 0; q < 8; ++q) v[q] = 0.f;
             }
-            af[a] = tpack8(v);
+            af[a] = pack8(v);
         }
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
@@ -1090,13 +1068,13 @@ __global__ void __launch_bounds__(256) k_mm(TRows rows, const float* __restrict_
             float v[8];
 #pragma unroll
             for (int q = 0; q < 8; ++q) v[q] = (col < N && (B_ROWS || k0 + 8 * h + q < K)) ? rb[b][q] : 0.f;
-            bf[b] = tpack8(v);
+            bf[b] = pack8(v);
         }
         if (k0 + 16 < K) load_step(k0 + 16);
 #pragma unroll
         for (int a = 0; a < MT; ++a)
 #pragma unroll
-            for (int b = 0; b < 4; ++b) acc[a][b] = tmfma(af[a], bf[b], acc[a][b]);
+            for (int b = 0; b < 4; ++b) acc[a][b] = mfma32(af[a], bf[b], acc[a][b]);
     }
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
@@ -1140,31 +1118,31 @@ __global__ void __launch_bounds__(256, 1) k_mm128(TRows rows, const float* __res
     stage_wimage(img, wimg, W, ldw, B_ROWS, 0, tid);
     __syncthreads();
     // one wave per SIMD with the whole 512-register file: 128 registers of weight fragments + a full tile of X in flight
-    tu32x4 bf[8][4];
+    u32x4 bf[8][4];
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks)
 #pragma unroll
-        for (int cb = 0; cb < 4; ++cb) bf[ks][cb] = reinterpret_cast<const tu32x4*>(img)[(ks * 4 + cb) * 64 + lane];
+        for (int cb = 0; cb < 4; ++cb) bf[ks][cb] = reinterpret_cast<const u32x4*>(img)[(ks * 4 + cb) * 64 + lane];
     float bv[4];
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) bv[cb] = bias ? bias[32 * cb + r] : 0.f;
     const int ntiles = (R + 31) / 32;
     const int tstride = gridDim.x * 4;
-    tf32x4 raw[16];
+    f32x4 raw[16];
     auto load_raw = [&](int t) {                              // this lane's row of tile t: 8 floats per k-step (rows clamped)
         const int row = min(32 * t + r, R - 1);
         const float* p = X + (size_t)row * ldx + 8 * h;
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
-            raw[2 * ks] = *reinterpret_cast<const tf32x4*>(p + 16 * ks);
-            raw[2 * ks + 1] = *reinterpret_cast<const tf32x4*>(p + 16 * ks + 4);
+            raw[2 * ks] = *reinterpret_cast<const f32x4*>(p + 16 * ks);
+            raw[2 * ks + 1] = *reinterpret_cast<const f32x4*>(p + 16 * ks + 4);
         }
     };
     int t = blockIdx.x * 4 + wave;
     if (t < ntiles) load_raw(t);
     for (; t < ntiles; t += tstride) {
         const int row = 32 * t + r;
-        tu32x4 af[8];
+        u32x4 af[8];
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
             float v[8] = {raw[2 * ks][0], raw[2 * ks][1], raw[2 * ks][2], raw[2 * ks][3],
@@ -1179,10 +1157,10 @@ __global__ void __launch_bounds__(256, 1) k_mm128(TRows rows, const float* __res
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[j] = 0.f;
             }
-            af[ks] = tpack8(v);
+            af[ks] = pack8(v);
         }
         if (t + tstride < ntiles) load_raw(t + tstride);      // next tile's loads fly under this tile's MFMAs and stores
-        tf32x16 acc[4];
+        f32x16 acc[4];
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
@@ -1190,7 +1168,7 @@ __global__ void __launch_bounds__(256, 1) k_mm128(TRows rows, const float* __res
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks)
 #pragma unroll
-            for (int cb = 0; cb < 4; ++cb) acc[cb] = tmfma(af[ks], bf[ks][cb], acc[cb]);
+            for (int cb = 0; cb < 4; ++cb) acc[cb] = mfma32(af[ks], bf[ks][cb], acc[cb]);
         // epilogue: the loads of a column block (old Y for beta, the taped pre-activation for the GELU backward) go out as
         // one batch with clamped rows - a load -> use -> store chain per element would expose one memory round trip each
 #pragma unroll
@@ -1281,14 +1259,83 @@ bool tm_gemm_nn(const TRows& rows, const float* X, int ldx, int K, const float* 
 // blockIdx.z, every split writes its own partial tile, reduce_parts adds them in order.
 #define TN_PITCH 160                                          // bf16 elements per LDS row (128 data + 32 pad)
 typedef __attribute__((ext_vector_type(4))) short ts16x4;
-__device__ __forceinline__ tu32x4 tr_frag(const unsigned short* tile, int row0, int col0, int lane) {
+__device__ __forceinline__ u32x4 tr_frag(const unsigned short* tile, int row0, int col0, int lane) {
     const int g = (lane >> 4) & 1, q = (lane >> 2) & 3, p = lane & 3, h = lane >> 5;
     const unsigned short* a = tile + (row0 + 8 * h + q) * TN_PITCH + col0 + 16 * g + 4 * p;
     const ts16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ts16x4*)a);
     const ts16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ts16x4*)(a + 4 * TN_PITCH));
-    typedef __attribute__((ext_vector_type(2))) unsigned tu32x2;
-    const tu32x2 l2 = __builtin_bit_cast(tu32x2, lo), h2 = __builtin_bit_cast(tu32x2, hi);
-    return tu32x4{l2[0], l2[1], h2[0], h2[1]};
+    const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
+    return u32x4{l2[0], l2[1], h2[0], h2[1]};
+}
+// ---- the core the 128 x 128 TN weight-gradient kernels share (k_mm_tn and the bf16-storage k_emm_tn, k_emm_bwd1, k_emm_bwd2): a wave's 64 x 64
+// quadrant (wr, wc) of the output tile as 2 x 2 accumulators, one 64-row step of the contraction from the staged tiles, the store of the
+// split's partial tile, and the source row of a staging load.
+__device__ __forceinline__ int tn_row(int m, int p_end, int R) { return m < p_end ? m : (R > 0 ? R - 1 : 0); }   // past the split: any live row (its tile cells are zeroed)
+__device__ __forceinline__ void tn_zero(f32x16 (&acc)[2][2]) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+}
+// acc += A^T B over the 64 rows of the staged tiles (four k-steps of transposed reads)
+__device__ __forceinline__ void tn_mfma(f32x16 (&acc)[2][2], const unsigned short* tA, const unsigned short* tB, int wr, int wc, int lane) {
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+        u32x4 af[2], bf[2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a) af[a] = tr_frag(tA, 16 * ks, 64 * wr + 32 * a, lane);
+#pragma unroll
+        for (int b = 0; b < 2; ++b) bf[b] = tr_frag(tB, 16 * ks, 64 * wc + 32 * b, lane);
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) acc[a][b] = mfma32(af[a], bf[b], acc[a][b]);
+    }
+}
+// the quadrant into a [128][128] partial tile (r = lane & 31, h = lane >> 5)
+__device__ __forceinline__ void tn_store(float* dst, const f32x16 (&acc)[2][2], int wr, int wc, int r, int h) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int col = 64 * wc + 32 * b + r;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) dst[(size_t)(64 * wr + 32 * a + (i & 3) + 8 * (i >> 2) + 4 * h) * 128 + col] = acc[a][b][i];
+        }
+}
+// column sums of the A tiles (the bias gradient): thread (rg, ch) summed chunk ch of rows rg, rg + 16, ...; the 16 row groups are folded in order
+__device__ __forceinline__ void tn_colsum_fold(float (*cs_red)[128], const float (&csum)[8], int rg, int ch, int tid, float* out) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) cs_red[rg][8 * ch + q] = csum[q];
+    __syncthreads();
+    if (tid < 128) {
+        float t = 0.f;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) t += cs_red[g][tid];
+        out[tid] = t;
+    }
+}
+// the fused NN product of k_emm_bwd1 / k_emm_bwd2: channel blocks 2 wc, 2 wc + 1 of a staged layout-1 weight image in registers, and
+// dn = W' . x^T for the 32 tile rows of which xrow is this lane's (row-major fragments of the A tile)
+__device__ __forceinline__ void wf_load(u32x4 (&wf)[8][2], const unsigned short* img, int wc, int lane) {
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) wf[ks][u] = reinterpret_cast<const u32x4*>(img)[(ks * 4 + 2 * wc + u) * 64 + lane];
+}
+__device__ __forceinline__ void wf_dn(f32x16 (&dn)[2], const u32x4 (&wf)[8][2], const unsigned short* xrow) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) dn[u][i] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+        const u32x4 xf = *reinterpret_cast<const u32x4*>(xrow + 16 * ks);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) dn[u] = mfma32(wf[ks][u], xf, dn[u]);
+    }
 }
 // ---- LDS-tiled NT / NN for the node-level shapes (K or N = 256 .. 512): a (64 MT) x 128 tile per workgroup (2 x 2 waves), K staged in
 // steps of 64 with the next tile's global loads in flight.  X tile: f32 rows -> [GELU + dropout] -> bf16, k-contiguous in LDS.  W tile:
@@ -1309,7 +1356,7 @@ __global__ void __launch_bounds__(256) k_tmm(TRows rows, const float* __restrict
     const int col0 = blockIdx.y * 128;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int wr = wave >> 1, wc = wave & 1;
-    tf32x16 acc[MT][2];
+    f32x16 acc[MT][2];
 #pragma unroll
     for (int a = 0; a < MT; ++a)
 #pragma unroll
@@ -1319,28 +1366,27 @@ __global__ void __launch_bounds__(256) k_tmm(TRows rows, const float* __restrict
     // staging maps.  A: thread -> (row tid / (4 / MT) ..., 16 * MT floats);  B (NT): (n = tid >> 1, 32 floats);  B (NN): (k = tid >> 2, 32 floats of n)
     constexpr int AV = 4 * MT;                                // float4 loads of A per thread: BM * 64 / 256 / 4
     const int arow = MT == 2 ? tid >> 1 : tid >> 2, acol = MT == 2 ? (tid & 1) * 32 : (tid & 3) * 16;
-    tf32x4 ar[AV], br[8];
+    f32x4 ar[AV], br[8];
     const unsigned key = drop_key(dr, site);
     auto load_tile = [&](int k0) {
         const int row = row0 + arow, kk = k0 + acol;
         const float* src = X + (size_t)(row < R ? row : R - 1) * ldx + (kk < K ? kk : 0);
 #pragma unroll
-        for (int v = 0; v < AV; ++v) ar[v] = *reinterpret_cast<const tf32x4*>(src + 4 * v);
+        for (int v = 0; v < AV; ++v) ar[v] = *reinterpret_cast<const f32x4*>(src + 4 * v);
         if (!WT) {
             const int n = col0 + (tid >> 1), kb = k0 + (tid & 1) * 32;
             const float* ws = W + (size_t)(n < N ? n : 0) * ldw + (kb < K ? kb : 0);
 #pragma unroll
-            for (int v = 0; v < 8; ++v) br[v] = *reinterpret_cast<const tf32x4*>(ws + 4 * v);
+            for (int v = 0; v < 8; ++v) br[v] = *reinterpret_cast<const f32x4*>(ws + 4 * v);
         } else {
             const int k = k0 + (tid >> 2), nb = col0 + (tid & 3) * 32;
             const int kc = k < K ? k : 0;                     // (NN: rows k >= k_split of W' come from a second block, W_hi)
             const float* ws = (kc < k_split ? W + (size_t)kc * ldw : W_hi + (size_t)(kc - k_split) * ldw) + (nb + 31 < N ? nb : 0);
 #pragma unroll
-            for (int v = 0; v < 8; ++v) br[v] = *reinterpret_cast<const tf32x4*>(ws + 4 * v);
+            for (int v = 0; v < 8; ++v) br[v] = *reinterpret_cast<const f32x4*>(ws + 4 * v);
         }
     };
     auto store_tile = [&](int k0) {
-        typedef __attribute__((ext_vector_type(2))) unsigned tu32x2;
         {
             const int row = row0 + arow, kk = k0 + acol;
             const bool ok = row < R && kk < K;
@@ -1353,8 +1399,8 @@ __global__ void __launch_bounds__(256) k_tmm(TRows rows, const float* __restrict
                     drop_pair(dr, key, P, m0, m1); drop_pair(dr, key, P + 1, m2, m3);
                     x[0] = gelu_fast(x[0]) * m0; x[1] = gelu_fast(x[1]) * m1; x[2] = gelu_fast(x[2]) * m2; x[3] = gelu_fast(x[3]) * m3;
                 }
-                const tu32x2 w = ok ? tu32x2{tpack2(x[0], x[1]), tpack2(x[2], x[3])} : tu32x2{0u, 0u};
-                *reinterpret_cast<tu32x2*>(As + arow * TM_LD + acol + 4 * v) = w;
+                const u32x2 w = ok ? u32x2{pack2(x[0], x[1]), pack2(x[2], x[3])} : u32x2{0u, 0u};
+                *reinterpret_cast<u32x2*>(As + arow * TM_LD + acol + 4 * v) = w;
             }
         }
         if (!WT) {
@@ -1362,16 +1408,16 @@ __global__ void __launch_bounds__(256) k_tmm(TRows rows, const float* __restrict
             const bool ok = n < N && kb < K;
 #pragma unroll
             for (int v = 0; v < 8; ++v) {
-                const tu32x2 w = ok ? tu32x2{tpack2(br[v][0], br[v][1]), tpack2(br[v][2], br[v][3])} : tu32x2{0u, 0u};
-                *reinterpret_cast<tu32x2*>(Bs + (tid >> 1) * TM_LD + (tid & 1) * 32 + 4 * v) = w;
+                const u32x2 w = ok ? u32x2{pack2(br[v][0], br[v][1]), pack2(br[v][2], br[v][3])} : u32x2{0u, 0u};
+                *reinterpret_cast<u32x2*>(Bs + (tid >> 1) * TM_LD + (tid & 1) * 32 + 4 * v) = w;
             }
         } else {
             const int k = k0 + (tid >> 2), nb = col0 + (tid & 3) * 32;
             const bool ok = k < K && nb + 31 < N;
 #pragma unroll
             for (int v = 0; v < 8; ++v) {
-                const tu32x2 w = ok ? tu32x2{tpack2(br[v][0], br[v][1]), tpack2(br[v][2], br[v][3])} : tu32x2{0u, 0u};
-                *reinterpret_cast<tu32x2*>(Bs + (tid >> 2) * TN_PITCH + (tid & 3) * 32 + 4 * v) = w;
+                const u32x2 w = ok ? u32x2{pack2(br[v][0], br[v][1]), pack2(br[v][2], br[v][3])} : u32x2{0u, 0u};
+                *reinterpret_cast<u32x2*>(Bs + (tid >> 2) * TN_PITCH + (tid & 3) * 32 + 4 * v) = w;
             }
         }
     };
@@ -1383,18 +1429,18 @@ __global__ void __launch_bounds__(256) k_tmm(TRows rows, const float* __restrict
         if (k0 + 64 < K) load_tile(k0 + 64);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            tu32x4 af[MT], bf[2];
+            u32x4 af[MT], bf[2];
 #pragma unroll
-            for (int a = 0; a < MT; ++a) af[a] = *reinterpret_cast<const tu32x4*>(As + (32 * MT * wr + 32 * a + r) * TM_LD + 16 * ks + 8 * h);
+            for (int a = 0; a < MT; ++a) af[a] = *reinterpret_cast<const u32x4*>(As + (32 * MT * wr + 32 * a + r) * TM_LD + 16 * ks + 8 * h);
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
-                if (!WT) bf[b] = *reinterpret_cast<const tu32x4*>(Bs + (64 * wc + 32 * b + r) * TM_LD + 16 * ks + 8 * h);
+                if (!WT) bf[b] = *reinterpret_cast<const u32x4*>(Bs + (64 * wc + 32 * b + r) * TM_LD + 16 * ks + 8 * h);
                 else bf[b] = tr_frag(Bs, 16 * ks, 64 * wc + 32 * b, lane);
             }
 #pragma unroll
             for (int a = 0; a < MT; ++a)
 #pragma unroll
-                for (int b = 0; b < 2; ++b) acc[a][b] = tmfma(af[a], bf[b], acc[a][b]);
+                for (int b = 0; b < 2; ++b) acc[a][b] = mfma32(af[a], bf[b], acc[a][b]);
         }
     }
 #pragma unroll
@@ -1456,44 +1502,38 @@ __global__ void __launch_bounds__(256) k_mm_tn(TRows rows, const float* __restri
     const int p_begin = blockIdx.z * rows_per_split, p_end = min(R, p_begin + rows_per_split);
     // staging map: thread -> 8 (row, 4-column group) cells of the 64 x 128 tile; cg fastest: coalesced 512-B rows
     const int cg = tid & 31, rg = tid >> 5;                   // columns 4cg .. 4cg+3; rows rg, rg+8, ...
-    tf32x4 ra[8], rb[8];
-    tf32x4 csum = {0.f, 0.f, 0.f, 0.f};                       // column sums of A over this thread's rows (bias gradient, optional)
+    f32x4 ra[8], rb[8];
+    f32x4 csum = {0.f, 0.f, 0.f, 0.f};                       // column sums of A over this thread's rows (bias gradient, optional)
     auto load_tile = [&](int m0) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int m = m0 + rg + 8 * i;
             const bool ok = m < p_end;
-            const int mc = ok ? m : (R > 0 ? R - 1 : 0);
+            const int mc = tn_row(m, p_end, R);
             const int ca = n0 + 4 * cg, cb = kk0 + 4 * cg;
-            tf32x4 va = {0.f, 0.f, 0.f, 0.f}, vb = {0.f, 0.f, 0.f, 0.f};
-            if (ca + 3 < M) va = *reinterpret_cast<const tf32x4*>(A + (size_t)mc * lda + ca);
+            f32x4 va = {0.f, 0.f, 0.f, 0.f}, vb = {0.f, 0.f, 0.f, 0.f};
+            if (ca + 3 < M) va = *reinterpret_cast<const f32x4*>(A + (size_t)mc * lda + ca);
             else for (int c = 0; c < 4; ++c) if (ca + c < M) va[c] = A[(size_t)mc * lda + ca + c];
-            if (cb + 3 < K) vb = *reinterpret_cast<const tf32x4*>(B + (size_t)mc * ldb + cb);
+            if (cb + 3 < K) vb = *reinterpret_cast<const f32x4*>(B + (size_t)mc * ldb + cb);
             else for (int c = 0; c < 4; ++c) if (cb + c < K) vb[c] = B[(size_t)mc * ldb + cb + c];
             if (actB) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) vb[c] = gelu_fast(vb[c]) * drop_mul(dr, site, (unsigned long long)m * K + cb + c);
             }
-            if (!ok) { va = tf32x4{0.f, 0.f, 0.f, 0.f}; vb = va; }
+            if (!ok) { va = f32x4{0.f, 0.f, 0.f, 0.f}; vb = va; }
             ra[i] = va; rb[i] = vb;
         }
     };
     auto store_tile = [&]() {
-        typedef __attribute__((ext_vector_type(2))) unsigned tu32x2;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int row = rg + 8 * i;
-            *reinterpret_cast<tu32x2*>(tA + row * TN_PITCH + 4 * cg) = tu32x2{tpack2(ra[i][0], ra[i][1]), tpack2(ra[i][2], ra[i][3])};
-            *reinterpret_cast<tu32x2*>(tB + row * TN_PITCH + 4 * cg) = tu32x2{tpack2(rb[i][0], rb[i][1]), tpack2(rb[i][2], rb[i][3])};
+            *reinterpret_cast<u32x2*>(tA + row * TN_PITCH + 4 * cg) = u32x2{pack2(ra[i][0], ra[i][1]), pack2(ra[i][2], ra[i][3])};
+            *reinterpret_cast<u32x2*>(tB + row * TN_PITCH + 4 * cg) = u32x2{pack2(rb[i][0], rb[i][1]), pack2(rb[i][2], rb[i][3])};
         }
     };
-    tf32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+    f32x16 acc[2][2];
+    tn_zero(acc);
     if (p_begin < p_end) load_tile(p_begin);
     for (int m0 = p_begin; m0 < p_end; m0 += 64) {
         __syncthreads();                                      // the previous tile's fragment reads are done
@@ -1504,21 +1544,10 @@ __global__ void __launch_bounds__(256) k_mm_tn(TRows rows, const float* __restri
         }
         __syncthreads();
         if (m0 + 64 < p_end) load_tile(m0 + 64);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            tu32x4 af[2], bf[2];
-#pragma unroll
-            for (int a = 0; a < 2; ++a) af[a] = tr_frag(tA, 16 * ks, 64 * wr + 32 * a, lane);
-#pragma unroll
-            for (int b = 0; b < 2; ++b) bf[b] = tr_frag(tB, 16 * ks, 64 * wc + 32 * b, lane);
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) acc[a][b] = tmfma(af[a], bf[b], acc[a][b]);
-        }
+        tn_mfma(acc, tA, tB, wr, wc, lane);
     }
     if (cs_part && blockIdx.y == 0) {                         // rows rg, rg+8, ... were summed per thread: fold the 8 row groups in order
-        *reinterpret_cast<tf32x4*>(&cs_red[rg][4 * cg]) = csum;
+        *reinterpret_cast<f32x4*>(&cs_red[rg][4 * cg]) = csum;
         __syncthreads();
         if (tid < 128 && n0 + tid < M) {
             float t = 0.f;
@@ -1602,14 +1631,6 @@ void t_adam_step(float* p, const float* g, float* m, float* v, long long n, floa
 
 // ==========================================================================================
 // bf16-STORAGE edge kernels of the bf16-mixed trainer (declared at the end of kernels_train.h).
-__device__ __forceinline__ float tbf_lo(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float tbf_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ float tbf(tb16 v) { return __uint_as_float((unsigned)v << 16); }
-__device__ __forceinline__ tb16 to_tb(float v) { return (tb16)(tpack2(v, 0.f) & 0xffffu); }
-__device__ __forceinline__ void unpack8(const tu32x4& u, float (&v)[8]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { v[2 * i] = tbf_lo(u[i]); v[2 * i + 1] = tbf_hi(u[i]); }
-}
 
 struct EmmArgs {
     TRows rows;
@@ -1646,28 +1667,28 @@ __global__ void __launch_bounds__(256, 2) k_emm128(EmmArgs a) {
     stage_wimage(img, second ? a.wimg2 : a.wimg, second ? a.W + a.w_yoff : a.W, a.ldw, B_ROWS, 1, tid, a.kvalid);
     if (tid < 128) lds_bias[tid] = (a.bias && !second) ? a.bias[tid] : 0.f;
     __syncthreads();
-    const tu32x4* wimg = reinterpret_cast<const tu32x4*>(img) + lane;
+    const u32x4* wimg = reinterpret_cast<const u32x4*>(img) + lane;
     const int ntiles = (R + 31) / 32;
     const int tstride = gridDim.x * 4;
     const unsigned key1 = drop_key(a.dr, a.site), key2 = drop_key(a.dr, a.f.site2);
     constexpr bool XB = sizeof(TX) == 2;
     constexpr bool NEED_J = EP == 1;
-    tu32x4 rawb[XB ? 8 : 1];           // bf16 X: the fragments themselves
-    tf32x4 rawf[XB ? 1 : 16];          // f32 X
+    u32x4 rawb[XB ? 8 : 1];           // bf16 X: the fragments themselves
+    f32x4 rawf[XB ? 1 : 16];          // f32 X
     int jn = -1;                       // neighbour of the prefetched tile's row
     const TX* __restrict__ X = reinterpret_cast<const TX*>(a.X);
-    const tu32x4 z4 = {0u, 0u, 0u, 0u};
+    const u32x4 z4 = {0u, 0u, 0u, 0u};
     auto load_raw = [&](int t) {
         const int row = min(32 * t + r, R - 1);
         const TX* p = X + (size_t)row * a.ldx + 8 * h;
         if constexpr (XB) {
 #pragma unroll
-            for (int ks = 0; ks < 8; ++ks) rawb[ks] = *reinterpret_cast<const tu32x4*>(p + 16 * ks);
+            for (int ks = 0; ks < 8; ++ks) rawb[ks] = *reinterpret_cast<const u32x4*>(p + 16 * ks);
         } else {
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks) {
-                rawf[2 * ks] = *reinterpret_cast<const tf32x4*>(p + 16 * ks);
-                rawf[2 * ks + 1] = *reinterpret_cast<const tf32x4*>(p + 16 * ks + 4);
+                rawf[2 * ks] = *reinterpret_cast<const f32x4*>(p + 16 * ks);
+                rawf[2 * ks + 1] = *reinterpret_cast<const f32x4*>(p + 16 * ks + 4);
             }
         }
         if constexpr (NEED_J) jn = a.f.nbr[row];
@@ -1680,20 +1701,20 @@ __global__ void __launch_bounds__(256, 2) k_emm128(EmmArgs a) {
         const int rowc = rok ? row : R - 1;
         const int j = jn;
         // ---- epilogue operands of this tile, group u = channels 16u + 8h .. +7 of this lane's row
-        tu32x4 e0[EP ? 8 : 1], e1[EP == 1 ? 8 : 1];      // e0: P row | taped pre-activation;  e1: Q row
+        u32x4 e0[EP ? 8 : 1], e1[EP == 1 ? 8 : 1];      // e0: P row | taped pre-activation;  e1: Q row
         {
             const size_t ro = (size_t)rowc * 128 + 8 * h;
             if constexpr (EP == 1) {
                 const tb16* prow = a.f.P + (size_t)(rowc / a.f.k) * 128 + 8 * h;
                 const tb16* qrow = a.f.Q + (size_t)(j < 0 ? a.f.zero_row : (j > a.f.zero_row ? a.f.zero_row : j)) * 128 + 8 * h;
 #pragma unroll
-                for (int u = 0; u < 8; ++u) { e0[u] = *reinterpret_cast<const tu32x4*>(prow + 16 * u); e1[u] = *reinterpret_cast<const tu32x4*>(qrow + 16 * u); }
+                for (int u = 0; u < 8; ++u) { e0[u] = *reinterpret_cast<const u32x4*>(prow + 16 * u); e1[u] = *reinterpret_cast<const u32x4*>(qrow + 16 * u); }
             } else if constexpr (EP == 2) {
 #pragma unroll
-                for (int u = 0; u < 8; ++u) e0[u] = *reinterpret_cast<const tu32x4*>(a.epi_pre + ro + 16 * u);
+                for (int u = 0; u < 8; ++u) e0[u] = *reinterpret_cast<const u32x4*>(a.epi_pre + ro + 16 * u);
             }
         }
-        tu32x4 xf[8];
+        u32x4 xf[8];
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
             if constexpr (XB && !ACT) { xf[ks] = rawb[ks]; }
@@ -1710,18 +1731,18 @@ __global__ void __launch_bounds__(256, 2) k_emm128(EmmArgs a) {
 #pragma unroll
                     for (int q = 0; q < 8; ++q) v[q] = gelu_fast(v[q]) * dm[q];
                 }
-                xf[ks] = tpack8(v);
+                xf[ks] = pack8(v);
             }
             if (!rok) xf[ks] = z4;
         }
         if (t + tstride < ntiles) load_raw(t + tstride);
-        tf32x16 acc[4];
+        f32x16 acc[4];
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[cb][i] = 0.f;
         // weight fragments from LDS, one k-step ahead of the MFMAs that use them (pinned: hoisting all 32 reads costs 128 registers)
-        tu32x4 wa[4], wb[4];
+        u32x4 wa[4], wb[4];
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb) wa[cb] = wimg[cb * 64];
 #pragma unroll
@@ -1729,27 +1750,27 @@ __global__ void __launch_bounds__(256, 2) k_emm128(EmmArgs a) {
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb) wb[cb] = wimg[((ks + 1) * 4 + cb) * 64];
 #pragma unroll
-            for (int cb = 0; cb < 4; ++cb) acc[cb] = tmfma(wa[cb], xf[ks], acc[cb]);
+            for (int cb = 0; cb < 4; ++cb) acc[cb] = mfma32(wa[cb], xf[ks], acc[cb]);
             __builtin_amdgcn_sched_barrier(0);
             if (ks + 2 < 8) {
 #pragma unroll
                 for (int cb = 0; cb < 4; ++cb) wa[cb] = wimg[((ks + 2) * 4 + cb) * 64];
             }
 #pragma unroll
-            for (int cb = 0; cb < 4; ++cb) acc[cb] = tmfma(wb[cb], xf[ks + 1], acc[cb]);
+            for (int cb = 0; cb < 4; ++cb) acc[cb] = mfma32(wb[cb], xf[ks + 1], acc[cb]);
             __builtin_amdgcn_sched_barrier(0);
         }
         // ---- epilogue in two halves of 64 channels: compute, then store (all loads are already in registers)
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-            tu32x4 yo[4], ro2[RES ? 4 : 1];
+            u32x4 yo[4], ro2[RES ? 4 : 1];
 #pragma unroll
             for (int uu = 0; uu < 4; ++uu) {
                 const int u = 4 * half + uu, cb = u >> 1, g = u & 1, c = 16 * u + 8 * h;
                 float v[8];
 #pragma unroll
                 for (int q = 0; q < 8; ++q) v[q] = acc[cb][8 * g + q];
-                const tf32x4 b0 = *reinterpret_cast<const tf32x4*>(lds_bias + c), b1 = *reinterpret_cast<const tf32x4*>(lds_bias + c + 4);
+                const f32x4 b0 = *reinterpret_cast<const f32x4*>(lds_bias + c), b1 = *reinterpret_cast<const f32x4*>(lds_bias + c + 4);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) { v[q] += b0[q]; v[4 + q] += b1[q]; }
                 if constexpr (EP == 1) {
@@ -1764,27 +1785,27 @@ __global__ void __launch_bounds__(256, 2) k_emm128(EmmArgs a) {
 #pragma unroll
                     for (int q = 0; q < 8; ++q) v[q] *= gelu_d_fast(pr[q]) * dm[q];
                 }
-                yo[uu] = tpack8(v);
+                yo[uu] = pack8(v);
                 if constexpr (RES) {
                     float ei[8];
-                    unpack8(*reinterpret_cast<const tu32x4*>(a.f.res_in + (size_t)rowc * 128 + c), ei);
+                    unpack8(*reinterpret_cast<const u32x4*>(a.f.res_in + (size_t)rowc * 128 + c), ei);
                     if (j >= 0) {
                         float dm[8];
                         drop8(a.dr, key2, (unsigned)row * 16u + (c >> 3), dm);
 #pragma unroll
                         for (int q = 0; q < 8; ++q) ei[q] += gelu_fast(v[q]) * dm[q];
                     }
-                    ro2[uu] = tpack8(ei);
+                    ro2[uu] = pack8(ei);
                 }
             }
             if (rok) {
                 tb16* yrow = Yp + (size_t)row * 128 + 64 * half + 8 * h;
 #pragma unroll
-                for (int uu = 0; uu < 4; ++uu) *reinterpret_cast<tu32x4*>(yrow + 16 * uu) = yo[uu];
+                for (int uu = 0; uu < 4; ++uu) *reinterpret_cast<u32x4*>(yrow + 16 * uu) = yo[uu];
                 if constexpr (RES) {
                     tb16* rrow = a.f.res_out + (size_t)row * 128 + 64 * half + 8 * h;
 #pragma unroll
-                    for (int uu = 0; uu < 4; ++uu) *reinterpret_cast<tu32x4*>(rrow + 16 * uu) = ro2[uu];
+                    for (int uu = 0; uu < 4; ++uu) *reinterpret_cast<u32x4*>(rrow + 16 * uu) = ro2[uu];
                 }
             }
         }
@@ -1835,7 +1856,6 @@ void te_gemm_pq(const TRows& rows, const float* h, const float* w0, const float*
 // block cb): the hidden activation never leaves the registers, pre1 / pre2 are written once as the tape, and the e tile that was the
 // operand of the first Linear is still in registers when the edge update needs it.  Against the two-kernel form this saves the read of pre1
 // and (edge update) the second read of e.  Both weight images live in LDS (64 KiB, two workgroups per CU).
-__device__ __forceinline__ void gelu_both_fast(float x, float& g, float& d);
 struct Emm2Args {
     TRows rows;
     const tb16* X;                   // e [R][128]
@@ -1849,13 +1869,6 @@ struct Emm2Args {
 // TAPE1: pre1 is written (training tape) with its DROPPED elements replaced by TE_DROPPED (gelu = gelu' = 0 there): the backward needs no hash;
 // inference callers keep only pre2.  RES: pre2 receives gelu'(pre2) * mask(site2) - all the backward needs of it - instead of pre2
 template <bool RES, bool TAPE1>
-// tape stores (written once, read a whole backward later): TE_EXP_NT_TAPE builds them as non-temporal stores - measured 30.3 ms per step at the C2
-// batch against 23.6 (the 16-byte-per-lane pieces of a row no longer merge in L2): kept as the experiment's switch only
-#ifdef TE_EXP_NT_TAPE
-#define TE_TAPE_STORE(ptr, val) __builtin_nontemporal_store((val), reinterpret_cast<tu32x4*>(ptr))
-#else
-#define TE_TAPE_STORE(ptr, val) (*reinterpret_cast<tu32x4*>(ptr) = (val))
-#endif
 __global__ void __launch_bounds__(256, 2) k_emm_fwd2(Emm2Args a) {
     __shared__ __attribute__((aligned(16))) unsigned short img1[32 * 64 * 8], img2[32 * 64 * 8];
     __shared__ __attribute__((aligned(16))) float lds_bias[128];
@@ -1865,26 +1878,26 @@ __global__ void __launch_bounds__(256, 2) k_emm_fwd2(Emm2Args a) {
     stage_wimage(img2, a.wimg2, a.W2, a.ldw2, true, 1, tid);
     if (tid < 128) lds_bias[tid] = a.bias2 ? a.bias2[tid] : 0.f;
     __syncthreads();
-    const tu32x4* w1 = reinterpret_cast<const tu32x4*>(img1) + lane;
-    const tu32x4* w2 = reinterpret_cast<const tu32x4*>(img2) + lane;
+    const u32x4* w1 = reinterpret_cast<const u32x4*>(img1) + lane;
+    const u32x4* w2 = reinterpret_cast<const u32x4*>(img2) + lane;
     const int ntiles = (R + 31) / 32;
     const int tstride = gridDim.x * 4;
     const unsigned key1 = drop_key(a.dr, a.site), key2 = drop_key(a.dr, a.f.site2);
-    tu32x4 raw[8];
+    u32x4 raw[8];
     int jn = -1;
     auto load_raw = [&](int t) {
         const int row = min(32 * t + r, R - 1);
         const tb16* p = a.X + (size_t)row * 128 + 8 * h;
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) raw[ks] = *reinterpret_cast<const tu32x4*>(p + 16 * ks);
+        for (int ks = 0; ks < 8; ++ks) raw[ks] = *reinterpret_cast<const u32x4*>(p + 16 * ks);
         jn = a.f.nbr[row];
     };
-    auto gemm = [&](const tu32x4* wimg, const tu32x4 (&xf)[8], tf32x16 (&acc)[4]) {
+    auto gemm = [&](const u32x4* wimg, const u32x4 (&xf)[8], f32x16 (&acc)[4]) {
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[cb][i] = 0.f;
-        tu32x4 wa[4], wb[4];
+        u32x4 wa[4], wb[4];
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb) wa[cb] = wimg[cb * 64];
 #pragma unroll
@@ -1892,14 +1905,14 @@ __global__ void __launch_bounds__(256, 2) k_emm_fwd2(Emm2Args a) {
 #pragma unroll
             for (int cb = 0; cb < 4; ++cb) wb[cb] = wimg[((ks + 1) * 4 + cb) * 64];
 #pragma unroll
-            for (int cb = 0; cb < 4; ++cb) acc[cb] = tmfma(wa[cb], xf[ks], acc[cb]);
+            for (int cb = 0; cb < 4; ++cb) acc[cb] = mfma32(wa[cb], xf[ks], acc[cb]);
             __builtin_amdgcn_sched_barrier(0);
             if (ks + 2 < 8) {
 #pragma unroll
                 for (int cb = 0; cb < 4; ++cb) wa[cb] = wimg[((ks + 2) * 4 + cb) * 64];
             }
 #pragma unroll
-            for (int cb = 0; cb < 4; ++cb) acc[cb] = tmfma(wb[cb], xf[ks + 1], acc[cb]);
+            for (int cb = 0; cb < 4; ++cb) acc[cb] = mfma32(wb[cb], xf[ks + 1], acc[cb]);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -1910,21 +1923,21 @@ __global__ void __launch_bounds__(256, 2) k_emm_fwd2(Emm2Args a) {
         const bool rok = row < R;
         const int rowc = rok ? row : R - 1;
         const int j = jn;
-        tu32x4 xe[8];                                        // this row of e: operand of the first Linear, residual input of the edge update
+        u32x4 xe[8];                                        // this row of e: operand of the first Linear, residual input of the edge update
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) xe[ks] = rok ? raw[ks] : tu32x4{0u, 0u, 0u, 0u};
-        tu32x4 pp[8], qq[8];
+        for (int ks = 0; ks < 8; ++ks) xe[ks] = rok ? raw[ks] : u32x4{0u, 0u, 0u, 0u};
+        u32x4 pp[8], qq[8];
         {
             const tb16* prow = a.f.P + (size_t)(rowc / a.f.k) * 128 + 8 * h;
             const tb16* qrow = a.f.Q + (size_t)(j < 0 ? a.f.zero_row : (j > a.f.zero_row ? a.f.zero_row : j)) * 128 + 8 * h;
 #pragma unroll
-            for (int u = 0; u < 8; ++u) { pp[u] = *reinterpret_cast<const tu32x4*>(prow + 16 * u); qq[u] = *reinterpret_cast<const tu32x4*>(qrow + 16 * u); }
+            for (int u = 0; u < 8; ++u) { pp[u] = *reinterpret_cast<const u32x4*>(prow + 16 * u); qq[u] = *reinterpret_cast<const u32x4*>(qrow + 16 * u); }
         }
         if (t + tstride < ntiles) load_raw(t + tstride);
-        tf32x16 acc[4];
+        f32x16 acc[4];
         gemm(w1, xe, acc);
         // epilogue 1: pre1 = acc + P + Q (tape, bf16) ; hidden = drop(gelu(pre1 as stored)) -> operand fragments of the second Linear
-        tu32x4 xh[8];
+        u32x4 xh[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int cb = u >> 1, g = u & 1;
@@ -1932,18 +1945,18 @@ __global__ void __launch_bounds__(256, 2) k_emm_fwd2(Emm2Args a) {
             unpack8(pp[u], pv); unpack8(qq[u], qv);
 #pragma unroll
             for (int q = 0; q < 8; ++q) v[q] = acc[cb][8 * g + q] + pv[q] + qv[q];
-            const tu32x4 y = tpack8(v);
+            const u32x4 y = pack8(v);
             drop8(a.dr, key1, (unsigned)row * 16u + 2 * u + h, dm);
             if (TAPE1 && rok) {
                 float vm[8];
 #pragma unroll
                 for (int q = 0; q < 8; ++q) vm[q] = dm[q] != 0.f ? v[q] : TE_DROPPED;
-                TE_TAPE_STORE(a.pre1 + (size_t)row * 128 + 16 * u + 8 * h, tpack8(vm));
+                *reinterpret_cast<u32x4*>(a.pre1 + (size_t)row * 128 + 16 * u + 8 * h) = pack8(vm);
             }
             unpack8(y, v);
 #pragma unroll
             for (int q = 0; q < 8; ++q) v[q] = gelu_fast(v[q]) * dm[q];
-            xh[u] = rok ? tpack8(v) : tu32x4{0u, 0u, 0u, 0u};
+            xh[u] = rok ? pack8(v) : u32x4{0u, 0u, 0u, 0u};
         }
         gemm(w2, xh, acc);
         // epilogue 2: pre2 (tape) [+ edge update from the e row still in registers]
@@ -1951,7 +1964,7 @@ __global__ void __launch_bounds__(256, 2) k_emm_fwd2(Emm2Args a) {
         for (int u = 0; u < 8; ++u) {
             const int cb = u >> 1, g = u & 1, c = 16 * u + 8 * h;
             float v[8];
-            const tf32x4 b0 = *reinterpret_cast<const tf32x4*>(lds_bias + c), b1 = *reinterpret_cast<const tf32x4*>(lds_bias + c + 4);
+            const f32x4 b0 = *reinterpret_cast<const f32x4*>(lds_bias + c), b1 = *reinterpret_cast<const f32x4*>(lds_bias + c + 4);
 #pragma unroll
             for (int q = 0; q < 4; ++q) { v[q] = acc[cb][8 * g + q] + b0[q]; v[4 + q] = acc[cb][8 * g + 4 + q] + b1[q]; }
             if constexpr (RES) {
@@ -1965,10 +1978,10 @@ __global__ void __launch_bounds__(256, 2) k_emm_fwd2(Emm2Args a) {
                     if (j >= 0) ei[q] += g * dm[q];
                     v[q] = d * dm[q];
                 }
-                if (rok) TE_TAPE_STORE(a.pre2 + (size_t)row * 128 + c, tpack8(v));
-                if (rok) *reinterpret_cast<tu32x4*>(a.f.res_out + (size_t)row * 128 + c) = tpack8(ei);
+                if (rok) *reinterpret_cast<u32x4*>(a.pre2 + (size_t)row * 128 + c) = pack8(v);
+                if (rok) *reinterpret_cast<u32x4*>(a.f.res_out + (size_t)row * 128 + c) = pack8(ei);
             } else {
-                if (rok) TE_TAPE_STORE(a.pre2 + (size_t)row * 128 + c, tpack8(v));
+                if (rok) *reinterpret_cast<u32x4*>(a.pre2 + (size_t)row * 128 + c) = pack8(v);
             }
         }
     }
@@ -2003,42 +2016,37 @@ __global__ void __launch_bounds__(256, 3) k_emm_tn(TRows rows, const tb16* __res
     const int ch = tid & 15, rg = tid >> 4;                   // 16-byte chunk ch of rows rg, rg+16, rg+32, rg+48
     const unsigned key = drop_key(dr, site);
     float csum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const tu32x4 z4 = {0u, 0u, 0u, 0u};
+    const u32x4 z4 = {0u, 0u, 0u, 0u};
     // raw tile loads one tile ahead of the MFMAs; the activation prologue runs when the tile is moved to LDS
-    auto load_tile = [&](int m0, tu32x4 (&xa)[4], tu32x4 (&xb)[4]) {
+    auto load_tile = [&](int m0, u32x4 (&xa)[4], u32x4 (&xb)[4]) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int m = m0 + rg + 16 * i;
-            const int mc = m < p_end ? m : (R > 0 ? R - 1 : 0);
-            xa[i] = *reinterpret_cast<const tu32x4*>(A + (size_t)mc * 128 + 8 * ch);
-            xb[i] = *reinterpret_cast<const tu32x4*>(B + (size_t)mc * 128 + 8 * ch);
+            const int mc = tn_row(m, p_end, R);
+            xa[i] = *reinterpret_cast<const u32x4*>(A + (size_t)mc * 128 + 8 * ch);
+            xb[i] = *reinterpret_cast<const u32x4*>(B + (size_t)mc * 128 + 8 * ch);
         }
     };
-    tf32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
-    auto stage = [&](int m0, tu32x4 (&xa)[4], tu32x4 (&xb)[4]) {
+    f32x16 acc[2][2];
+    tn_zero(acc);
+    auto stage = [&](int m0, u32x4 (&xa)[4], u32x4 (&xb)[4]) {
         __syncthreads();                                      // the previous tile's fragment reads are done
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int m = m0 + rg + 16 * i;
             const bool ok = m < p_end;
-            tu32x4 va = ok ? xa[i] : z4, vb = xb[i];
+            u32x4 va = ok ? xa[i] : z4, vb = xb[i];
             if (actB) {
                 float v[8], dm[8];
                 unpack8(vb, v);
                 drop8(dr, key, (unsigned)m * 16u + ch, dm);
 #pragma unroll
                 for (int q = 0; q < 8; ++q) v[q] = gelu_fast(v[q]) * dm[q];
-                vb = tpack8(v);
+                vb = pack8(v);
             }
             if (!ok) vb = z4;
-            *reinterpret_cast<tu32x4*>(tA + (rg + 16 * i) * TN_PITCH + 8 * ch) = va;
-            *reinterpret_cast<tu32x4*>(tB + (rg + 16 * i) * TN_PITCH + 8 * ch) = vb;
+            *reinterpret_cast<u32x4*>(tA + (rg + 16 * i) * TN_PITCH + 8 * ch) = va;
+            *reinterpret_cast<u32x4*>(tB + (rg + 16 * i) * TN_PITCH + 8 * ch) = vb;
             if (cs_part) {
                 float v[8];
                 unpack8(va, v);
@@ -2049,20 +2057,9 @@ __global__ void __launch_bounds__(256, 3) k_emm_tn(TRows rows, const tb16* __res
         __syncthreads();
     };
     auto compute = [&]() {
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            tu32x4 af[2], bf[2];
-#pragma unroll
-            for (int a = 0; a < 2; ++a) af[a] = tr_frag(tA, 16 * ks, 64 * wr + 32 * a, lane);
-#pragma unroll
-            for (int b = 0; b < 2; ++b) bf[b] = tr_frag(tB, 16 * ks, 64 * wc + 32 * b, lane);
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) acc[a][b] = tmfma(af[a], bf[b], acc[a][b]);
-        }
+        tn_mfma(acc, tA, tB, wr, wc, lane);
     };
-    tu32x4 a0[4], b0[4];
+    u32x4 a0[4], b0[4];
     int m0 = p_begin;
     if (m0 < p_end) load_tile(m0, a0, b0);
     while (m0 < p_end) {
@@ -2073,25 +2070,9 @@ __global__ void __launch_bounds__(256, 3) k_emm_tn(TRows rows, const tb16* __res
     }
     if (cs_part) {                                            // rows rg, rg+16, ... were summed per thread: fold the 16 row groups in order
         __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 8; ++q) cs_red[rg][8 * ch + q] = csum[q];
-        __syncthreads();
-        if (tid < 128) {
-            float t = 0.f;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) t += cs_red[g][tid];
-            cs_part[(size_t)blockIdx.z * pstride + tid] = t;
-        }
+        tn_colsum_fold(cs_red, csum, rg, ch, tid, cs_part + (size_t)blockIdx.z * pstride);
     }
-    float* dst = part + (size_t)blockIdx.z * pstride;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int col = 64 * wc + 32 * b + r;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) dst[(size_t)(64 * wr + 32 * a + (i & 3) + 8 * (i >> 2) + 4 * h) * 128 + col] = acc[a][b][i];
-        }
+    tn_store(part + (size_t)blockIdx.z * pstride, acc, wr, wc, r, h);
 }
 void te_gemm_tn(const TRows& rows, const tb16* A, const tb16* B, float* dW, int ldw, bool actB, const TDrop& dr,
                 unsigned site, float* dbias, hipStream_t s, int cols_keep) {
@@ -2111,15 +2092,6 @@ void te_gemm_tn(const TRows& rows, const tb16* A, const tb16* B, float* dW, int 
 // pre1 produces a1 = gelu * mask (the TN operand) and g' = gelu' * mask (an LDS tile for the NN epilogue), and the same dpre2 tile in LDS
 // feeds the transposed reads of the weight-gradient MFMAs and, as row-major fragments, the MFMAs of d pre1 (output transposed in the
 // accumulators as in k_emm128: lane = row, 16-byte stores).  W2's fragment image is staged through the LDS region that then holds g'.
-__device__ __forceinline__ void gelu_both_fast(float x, float& g, float& d) {          // (gelu_fast(x), gelu_d_fast(x)) sharing the sigmoid
-#ifdef TE_EXP_NOACT
-    g = x * fmaf(x, 0.25f, 0.5f); d = fmaf(x, 0.5f, 0.5f); return;
-#endif
-    const float p = fmaf(x * x, -0.10012571f, -2.3087657f);
-    const float sg = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * p));
-    g = x * sg;
-    d = fmaf(x * 0.3989422804f, __builtin_amdgcn_exp2f(x * x * -0.72134752f), sg);
-}
 // MODE: where d pre2 comes from.  1 (edge update, mpnn.py:250-262): d pre2 = valid ? dY * gelu'(PRE2) * mask(site2) : 0 with dY = d e_out - the
 // residual backward formed while the tile is staged instead of by a kernel of its own (one read and one write of an [E][128] tensor less).
 // 2 (message mean, mpnn.py:212-219): d pre2 = valid ? dagg[row / k] / cnt[row / k] * gelu'(PRE2) * mask(site2) : 0.
@@ -2139,52 +2111,49 @@ __global__ void __launch_bounds__(256, 2) k_emm_bwd2(TRows rows, const tb16* __r
     const int p_begin = blockIdx.z * rows_per_split, p_end = min(R, p_begin + rows_per_split);
     const int ch = tid & 15, rg = tid >> 4;
     float csum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const tu32x4 z4 = {0u, 0u, 0u, 0u};
+    const u32x4 z4 = {0u, 0u, 0u, 0u};
     // this wave's share of d pre1: rows 32 wr .. 32 wr + 31 of the tile, channel blocks 2 wc and 2 wc + 1
     stage_wimage(tG, wimg, W, ldw, false, 1, tid);
     __syncthreads();
-    tu32x4 wf[8][2];
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) wf[ks][u] = reinterpret_cast<const tu32x4*>(tG)[(ks * 4 + 2 * wc + u) * 64 + lane];
-    tu32x4 c0[MODE == 1 ? 4 : 1];                             // MODE 1: the taped pre2 chunk (MODE 2 carries it in the dY slot)
-    auto load_tile = [&](int m0, tu32x4 (&xa)[4], tu32x4 (&xb)[4]) {
+    u32x4 wf[8][2];
+    wf_load(wf, tG, wc, lane);
+    u32x4 c0[MODE == 1 ? 4 : 1];                             // MODE 1: the taped pre2 chunk (MODE 2 carries it in the dY slot)
+    auto load_tile = [&](int m0, u32x4 (&xa)[4], u32x4 (&xb)[4]) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int m = m0 + rg + 16 * i;
-            const int mc = m < p_end ? m : (R > 0 ? R - 1 : 0);
-            xa[i] = *reinterpret_cast<const tu32x4*>((MODE == 2 ? src.pre2 : dY) + (size_t)mc * 128 + 8 * ch);
-            xb[i] = *reinterpret_cast<const tu32x4*>(PRE + (size_t)mc * 128 + 8 * ch);
-            if constexpr (MODE == 1) c0[i] = *reinterpret_cast<const tu32x4*>(src.pre2 + (size_t)mc * 128 + 8 * ch);
+            const int mc = tn_row(m, p_end, R);
+            xa[i] = *reinterpret_cast<const u32x4*>((MODE == 2 ? src.pre2 : dY) + (size_t)mc * 128 + 8 * ch);
+            xb[i] = *reinterpret_cast<const u32x4*>(PRE + (size_t)mc * 128 + 8 * ch);
+            if constexpr (MODE == 1) c0[i] = *reinterpret_cast<const u32x4*>(src.pre2 + (size_t)mc * 128 + 8 * ch);
         }
     };
-    tf32x16 acc[2][2];
+    f32x16 acc[2][2];                                         // zeroed inline: with tn_zero, tn_mfma AND tn_store as helpers the kernel spills (316 / 252 B of scratch per lane)
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
-    tu32x4 a0[4], b0[4];
+    u32x4 a0[4], b0[4];
     int m0 = p_begin;
     if (m0 < p_end) load_tile(m0, a0, b0);
     while (m0 < p_end) {
         __syncthreads();                                      // the previous tile's fragment reads (and, first time, the image reads) are done
-        tu32x4 dy4[4];                                        // d pre2 of this thread's four chunks
+        u32x4 dy4[4];                                        // d pre2 of this thread's four chunks
         {
             int jv[4];
-            tf32x4 ga[MODE == 2 ? 4 : 1], gb[MODE == 2 ? 4 : 1];
+            f32x4 ga[MODE == 2 ? 4 : 1], gb[MODE == 2 ? 4 : 1];
             float ic[MODE == 2 ? 4 : 1];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {                     // (all loads of the phase first)
                 const int m = m0 + rg + 16 * i;
-                const int mc = m < p_end ? m : (R > 0 ? R - 1 : 0);
+                const int mc = tn_row(m, p_end, R);
                 jv[i] = src.nbr[mc];
                 if constexpr (MODE == 2) {
                     const int res = mc / src.k;
-                    ga[i] = *reinterpret_cast<const tf32x4*>(src.dagg + (size_t)res * 128 + 8 * ch);
-                    gb[i] = *reinterpret_cast<const tf32x4*>(src.dagg + (size_t)res * 128 + 8 * ch + 4);
+                    ga[i] = *reinterpret_cast<const f32x4*>(src.dagg + (size_t)res * 128 + 8 * ch);
+                    gb[i] = *reinterpret_cast<const f32x4*>(src.dagg + (size_t)res * 128 + 8 * ch + 4);
                     ic[i] = src.inv_cnt[res];
                 }
             }
@@ -2199,14 +2168,14 @@ __global__ void __launch_bounds__(256, 2) k_emm_bwd2(TRows rows, const tb16* __r
                 }
 #pragma unroll
                 for (int q = 0; q < 8; ++q) up[q] *= p2[q];      // the tape holds gelu'(pre2) * mask already
-                dy4[i] = jv[i] >= 0 ? tpack8(up) : z4;
+                dy4[i] = jv[i] >= 0 ? pack8(up) : z4;
             }
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int m = m0 + rg + 16 * i;
             const bool ok = m < p_end;
-            const tu32x4 va = ok ? dy4[i] : z4;
+            const u32x4 va = ok ? dy4[i] : z4;
             float v[8], a1[8], gp[8];
             unpack8(b0[i], v);
 #pragma unroll
@@ -2215,9 +2184,9 @@ __global__ void __launch_bounds__(256, 2) k_emm_bwd2(TRows rows, const tb16* __r
                 gelu_both_fast(v[q], g, d);
                 a1[q] = g * dr.scale; gp[q] = d * dr.scale;
             }
-            *reinterpret_cast<tu32x4*>(tA + (rg + 16 * i) * TN_PITCH + 8 * ch) = va;
-            *reinterpret_cast<tu32x4*>(tB + (rg + 16 * i) * TN_PITCH + 8 * ch) = ok ? tpack8(a1) : z4;
-            *reinterpret_cast<tu32x4*>(tG + (rg + 16 * i) * TN_PITCH + 8 * ch) = ok ? tpack8(gp) : z4;
+            *reinterpret_cast<u32x4*>(tA + (rg + 16 * i) * TN_PITCH + 8 * ch) = va;
+            *reinterpret_cast<u32x4*>(tB + (rg + 16 * i) * TN_PITCH + 8 * ch) = ok ? pack8(a1) : z4;
+            *reinterpret_cast<u32x4*>(tG + (rg + 16 * i) * TN_PITCH + 8 * ch) = ok ? pack8(gp) : z4;
             if (cs_part) {
                 float w8[8];
                 unpack8(va, w8);
@@ -2228,32 +2197,12 @@ __global__ void __launch_bounds__(256, 2) k_emm_bwd2(TRows rows, const tb16* __r
         __syncthreads();
         load_tile(m0 + 64, a0, b0);
         // weight gradient: acc += dpre2^T a1 (transposed reads of both tiles)
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            tu32x4 af[2], bf[2];
-#pragma unroll
-            for (int a = 0; a < 2; ++a) af[a] = tr_frag(tA, 16 * ks, 64 * wr + 32 * a, lane);
-#pragma unroll
-            for (int b = 0; b < 2; ++b) bf[b] = tr_frag(tB, 16 * ks, 64 * wc + 32 * b, lane);
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) acc[a][b] = tmfma(af[a], bf[b], acc[a][b]);
-        }
+        tn_mfma(acc, tA, tB, wr, wc, lane);
         // d pre1 of this wave's 32 rows x 64 channels: D = W2' . dpre2^T, the dpre2 rows as row-major fragments of the same LDS tile
         {
             const unsigned short* xrow = tA + (32 * wr + r) * TN_PITCH + 8 * h;
-            tf32x16 dn[2];
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) dn[u][i] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                const tu32x4 xf = *reinterpret_cast<const tu32x4*>(xrow + 16 * ks);
-#pragma unroll
-                for (int u = 0; u < 2; ++u) dn[u] = tmfma(wf[ks][u], xf, dn[u]);
-            }
+            f32x16 dn[2];
+            wf_dn(dn, wf, xrow);
             const int m = m0 + 32 * wr + r;
             const unsigned short* grow = tG + (32 * wr + r) * TN_PITCH + 8 * h;
 #pragma unroll
@@ -2262,35 +2211,19 @@ __global__ void __launch_bounds__(256, 2) k_emm_bwd2(TRows rows, const tb16* __r
                 for (int g = 0; g < 2; ++g) {
                     const int c = 32 * (2 * wc + u) + 16 * g;           // + 8 h (in grow / the store address)
                     float gq[8], o[8];
-                    unpack8(*reinterpret_cast<const tu32x4*>(grow + c), gq);
+                    unpack8(*reinterpret_cast<const u32x4*>(grow + c), gq);
 #pragma unroll
                     for (int q = 0; q < 8; ++q) o[q] = dn[u][8 * g + q] * gq[q];
-                    if (m < p_end) *reinterpret_cast<tu32x4*>(DX + (size_t)m * 128 + c + 8 * h) = tpack8(o);
+                    if (m < p_end) *reinterpret_cast<u32x4*>(DX + (size_t)m * 128 + c + 8 * h) = pack8(o);
                 }
         }
         m0 += 64;
     }
     if (cs_part) {
         __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 8; ++q) cs_red[rg][8 * ch + q] = csum[q];
-        __syncthreads();
-        if (tid < 128) {
-            float t = 0.f;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) t += cs_red[g][tid];
-            cs_part[(size_t)blockIdx.z * pstride + tid] = t;
-        }
+        tn_colsum_fold(cs_red, csum, rg, ch, tid, cs_part + (size_t)blockIdx.z * pstride);
     }
-    float* dst = part + (size_t)blockIdx.z * pstride;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int col = 64 * wc + 32 * b + r;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) dst[(size_t)(64 * wr + 32 * a + (i & 3) + 8 * (i >> 2) + 4 * h) * 128 + col] = acc[a][b][i];
-        }
+    tn_store(part + (size_t)blockIdx.z * pstride, acc, wr, wc, r, h);
 }
 // ---- the two kernels that consume d pre1, fused the same way: dWc += dpre1^T e (k_emm_tn, no activation) AND dE += dpre1 . Wc (k_emm128
 // with the old-Y epilogue): one pass over dpre1 instead of two.  The weight image is staged through the tile region before the first tile.
@@ -2305,31 +2238,28 @@ __global__ void __launch_bounds__(256, 2) k_emm_bwd1(TRows rows, const tb16* __r
     const int wr = wave >> 1, wc = wave & 1;
     const int p_begin = blockIdx.z * rows_per_split, p_end = min(R, p_begin + rows_per_split);
     const int ch = tid & 15, rg = tid >> 4;
-    const tu32x4 z4 = {0u, 0u, 0u, 0u};
+    const u32x4 z4 = {0u, 0u, 0u, 0u};
     stage_wimage(tAB, wimg, W, ldw, false, 1, tid);
     __syncthreads();
-    tu32x4 wf[8][2];
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) wf[ks][u] = reinterpret_cast<const tu32x4*>(tAB)[(ks * 4 + 2 * wc + u) * 64 + lane];
-    auto load_tile = [&](int m0, tu32x4 (&xa)[4], tu32x4 (&xb)[4]) {
+    u32x4 wf[8][2];
+    wf_load(wf, tAB, wc, lane);
+    auto load_tile = [&](int m0, u32x4 (&xa)[4], u32x4 (&xb)[4]) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int m = m0 + rg + 16 * i;
-            const int mc = m < p_end ? m : (R > 0 ? R - 1 : 0);
-            xa[i] = *reinterpret_cast<const tu32x4*>(dY + (size_t)mc * 128 + 8 * ch);
-            xb[i] = *reinterpret_cast<const tu32x4*>(Xin + (size_t)mc * 128 + 8 * ch);
+            const int mc = tn_row(m, p_end, R);
+            xa[i] = *reinterpret_cast<const u32x4*>(dY + (size_t)mc * 128 + 8 * ch);
+            xb[i] = *reinterpret_cast<const u32x4*>(Xin + (size_t)mc * 128 + 8 * ch);
         }
     };
-    tf32x16 acc[2][2];
+    f32x16 acc[2][2];                                         // zeroed inline: with tn_zero, tn_mfma AND tn_store as helpers the kernel spills (172 B of scratch per lane)
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
-    tu32x4 a0[4], b0[4];
+    u32x4 a0[4], b0[4];
     int m0 = p_begin;
     if (m0 < p_end) load_tile(m0, a0, b0);
     while (m0 < p_end) {
@@ -2337,44 +2267,24 @@ __global__ void __launch_bounds__(256, 2) k_emm_bwd1(TRows rows, const tb16* __r
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const bool ok = m0 + rg + 16 * i < p_end;
-            *reinterpret_cast<tu32x4*>(tA + (rg + 16 * i) * TN_PITCH + 8 * ch) = ok ? a0[i] : z4;
-            *reinterpret_cast<tu32x4*>(tB + (rg + 16 * i) * TN_PITCH + 8 * ch) = ok ? b0[i] : z4;
+            *reinterpret_cast<u32x4*>(tA + (rg + 16 * i) * TN_PITCH + 8 * ch) = ok ? a0[i] : z4;
+            *reinterpret_cast<u32x4*>(tB + (rg + 16 * i) * TN_PITCH + 8 * ch) = ok ? b0[i] : z4;
         }
         __syncthreads();
         load_tile(m0 + 64, a0, b0);
         // the old dE of this lane's row (4 x 16 bytes: channel groups of its two channel blocks) goes out before the MFMAs
         const int m = m0 + 32 * wr + r;
-        const int mc = m < p_end ? m : (R > 0 ? R - 1 : 0);
-        tu32x4 old[2][2];
+        const int mc = tn_row(m, p_end, R);
+        u32x4 old[2][2];
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int g = 0; g < 2; ++g) old[u][g] = *reinterpret_cast<const tu32x4*>(DE + (size_t)mc * 128 + 32 * (2 * wc + u) + 16 * g + 8 * h);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            tu32x4 af[2], bf[2];
-#pragma unroll
-            for (int a = 0; a < 2; ++a) af[a] = tr_frag(tA, 16 * ks, 64 * wr + 32 * a, lane);
-#pragma unroll
-            for (int b = 0; b < 2; ++b) bf[b] = tr_frag(tB, 16 * ks, 64 * wc + 32 * b, lane);
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) acc[a][b] = tmfma(af[a], bf[b], acc[a][b]);
-        }
+            for (int g = 0; g < 2; ++g) old[u][g] = *reinterpret_cast<const u32x4*>(DE + (size_t)mc * 128 + 32 * (2 * wc + u) + 16 * g + 8 * h);
+        tn_mfma(acc, tA, tB, wr, wc, lane);
         {
             const unsigned short* xrow = tA + (32 * wr + r) * TN_PITCH + 8 * h;
-            tf32x16 dn[2];
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) dn[u][i] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-                const tu32x4 xf = *reinterpret_cast<const tu32x4*>(xrow + 16 * ks);
-#pragma unroll
-                for (int u = 0; u < 2; ++u) dn[u] = tmfma(wf[ks][u], xf, dn[u]);
-            }
+            f32x16 dn[2];
+            wf_dn(dn, wf, xrow);
 #pragma unroll
             for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -2383,20 +2293,12 @@ __global__ void __launch_bounds__(256, 2) k_emm_bwd1(TRows rows, const tb16* __r
                     unpack8(old[u][g], ov);
 #pragma unroll
                     for (int q = 0; q < 8; ++q) o[q] = dn[u][8 * g + q] + ov[q];
-                    if (m < p_end) *reinterpret_cast<tu32x4*>(DE + (size_t)m * 128 + 32 * (2 * wc + u) + 16 * g + 8 * h) = tpack8(o);
+                    if (m < p_end) *reinterpret_cast<u32x4*>(DE + (size_t)m * 128 + 32 * (2 * wc + u) + 16 * g + 8 * h) = pack8(o);
                 }
         }
         m0 += 64;
     }
-    float* dst = part + (size_t)blockIdx.z * pstride;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int col = 64 * wc + 32 * b + r;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) dst[(size_t)(64 * wr + 32 * a + (i & 3) + 8 * (i >> 2) + 4 * h) * 128 + col] = acc[a][b][i];
-        }
+    tn_store(part + (size_t)blockIdx.z * pstride, acc, wr, wc, r, h);
 }
 // dW[128][ldw_out] += dY^T X,  DE += dY . W       (W [128 out][ldw]: the Wc block of a first Linear)
 void te_gemm_bwd1(const TRows& rows, const tb16* dY, const tb16* X, tb16* DE, const float* W, int ldw, float* dW, int ldw_out,
@@ -2428,27 +2330,27 @@ __global__ void __launch_bounds__(512, 1) k_emm_bwd1x2(TRows rows, const tb16* _
     const int rh = wave >> 2, cbw = wave & 3;                 // dE share
     const int p_begin = blockIdx.z * rows_per_split, p_end = min(R, p_begin + rows_per_split);
     const int ch = tid & 15, rg = tid >> 4;                   // 16-byte chunk ch of rows rg, rg + 32
-    const tu32x4 z4 = {0u, 0u, 0u, 0u};
+    const u32x4 z4 = {0u, 0u, 0u, 0u};
     if (tid < 256) stage_wimage(img1, wimg1, W1, ldw, false, 1, tid);
     else stage_wimage(img2, wimg2, W2, ldw, false, 1, tid - 256);
-    auto load_tile = [&](int m0, tu32x4 (&x1)[2], tu32x4 (&x2)[2], tu32x4 (&xb)[2]) {
+    auto load_tile = [&](int m0, u32x4 (&x1)[2], u32x4 (&x2)[2], u32x4 (&xb)[2]) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int m = m0 + rg + 32 * i;
-            const int mc = m < p_end ? m : (R > 0 ? R - 1 : 0);
-            x1[i] = *reinterpret_cast<const tu32x4*>(dY1 + (size_t)mc * 128 + 8 * ch);
-            x2[i] = *reinterpret_cast<const tu32x4*>(dY2 + (size_t)mc * 128 + 8 * ch);
-            xb[i] = *reinterpret_cast<const tu32x4*>(Xin + (size_t)mc * 128 + 8 * ch);
+            const int mc = tn_row(m, p_end, R);
+            x1[i] = *reinterpret_cast<const u32x4*>(dY1 + (size_t)mc * 128 + 8 * ch);
+            x2[i] = *reinterpret_cast<const u32x4*>(dY2 + (size_t)mc * 128 + 8 * ch);
+            xb[i] = *reinterpret_cast<const u32x4*>(Xin + (size_t)mc * 128 + 8 * ch);
         }
     };
-    tf32x16 acc1[2], acc2[2];
+    f32x16 acc1[2], acc2[2];
 #pragma unroll
     for (int b = 0; b < 2; ++b)
 #pragma unroll
         for (int i = 0; i < 16; ++i) { acc1[b][i] = 0.f; acc2[b][i] = 0.f; }
-    const tu32x4* w1 = reinterpret_cast<const tu32x4*>(img1) + cbw * 64 + lane;
-    const tu32x4* w2 = reinterpret_cast<const tu32x4*>(img2) + cbw * 64 + lane;
-    tu32x4 a1[2], a2[2], b0[2];
+    const u32x4* w1 = reinterpret_cast<const u32x4*>(img1) + cbw * 64 + lane;
+    const u32x4* w2 = reinterpret_cast<const u32x4*>(img2) + cbw * 64 + lane;
+    u32x4 a1[2], a2[2], b0[2];
     int m0 = p_begin;
     if (m0 < p_end) load_tile(m0, a1, a2, b0);
     while (m0 < p_end) {
@@ -2456,36 +2358,36 @@ __global__ void __launch_bounds__(512, 1) k_emm_bwd1x2(TRows rows, const tb16* _
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const bool ok = m0 + rg + 32 * i < p_end;
-            *reinterpret_cast<tu32x4*>(tA1 + (rg + 32 * i) * TN_PITCH + 8 * ch) = ok ? a1[i] : z4;
-            *reinterpret_cast<tu32x4*>(tA2 + (rg + 32 * i) * TN_PITCH + 8 * ch) = ok ? a2[i] : z4;
-            *reinterpret_cast<tu32x4*>(tB + (rg + 32 * i) * TN_PITCH + 8 * ch) = ok ? b0[i] : z4;
+            *reinterpret_cast<u32x4*>(tA1 + (rg + 32 * i) * TN_PITCH + 8 * ch) = ok ? a1[i] : z4;
+            *reinterpret_cast<u32x4*>(tA2 + (rg + 32 * i) * TN_PITCH + 8 * ch) = ok ? a2[i] : z4;
+            *reinterpret_cast<u32x4*>(tB + (rg + 32 * i) * TN_PITCH + 8 * ch) = ok ? b0[i] : z4;
         }
         __syncthreads();
         load_tile(m0 + 64, a1, a2, b0);
         const int m = m0 + 32 * rh + r;
-        const int mc = m < p_end ? m : (R > 0 ? R - 1 : 0);
-        tu32x4 old[2];
+        const int mc = tn_row(m, p_end, R);
+        u32x4 old[2];
 #pragma unroll
-        for (int g = 0; g < 2; ++g) old[g] = *reinterpret_cast<const tu32x4*>(DE + (size_t)mc * 128 + 32 * cbw + 16 * g + 8 * h);
+        for (int g = 0; g < 2; ++g) old[g] = *reinterpret_cast<const u32x4*>(DE + (size_t)mc * 128 + 32 * cbw + 16 * g + 8 * h);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            const tu32x4 af1 = tr_frag(tA1, 16 * ks, 32 * wr, lane), af2 = tr_frag(tA2, 16 * ks, 32 * wr, lane);
-            tu32x4 bf[2];
+            const u32x4 af1 = tr_frag(tA1, 16 * ks, 32 * wr, lane), af2 = tr_frag(tA2, 16 * ks, 32 * wr, lane);
+            u32x4 bf[2];
 #pragma unroll
             for (int b = 0; b < 2; ++b) bf[b] = tr_frag(tB, 16 * ks, 64 * wc + 32 * b, lane);
 #pragma unroll
-            for (int b = 0; b < 2; ++b) { acc1[b] = tmfma(af1, bf[b], acc1[b]); acc2[b] = tmfma(af2, bf[b], acc2[b]); }
+            for (int b = 0; b < 2; ++b) { acc1[b] = mfma32(af1, bf[b], acc1[b]); acc2[b] = mfma32(af2, bf[b], acc2[b]); }
         }
         {
             const unsigned short* x1 = tA1 + (32 * rh + r) * TN_PITCH + 8 * h;
             const unsigned short* x2 = tA2 + (32 * rh + r) * TN_PITCH + 8 * h;
-            tf32x16 dn;
+            f32x16 dn;
 #pragma unroll
             for (int i = 0; i < 16; ++i) dn[i] = 0.f;
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks) {
-                dn = tmfma(w1[ks * 4 * 64], *reinterpret_cast<const tu32x4*>(x1 + 16 * ks), dn);
-                dn = tmfma(w2[ks * 4 * 64], *reinterpret_cast<const tu32x4*>(x2 + 16 * ks), dn);
+                dn = mfma32(w1[ks * 4 * 64], *reinterpret_cast<const u32x4*>(x1 + 16 * ks), dn);
+                dn = mfma32(w2[ks * 4 * 64], *reinterpret_cast<const u32x4*>(x2 + 16 * ks), dn);
             }
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
@@ -2493,7 +2395,7 @@ __global__ void __launch_bounds__(512, 1) k_emm_bwd1x2(TRows rows, const tb16* _
                 unpack8(old[g], ov);
 #pragma unroll
                 for (int q = 0; q < 8; ++q) o[q] = dn[8 * g + q] + ov[q];
-                if (m < p_end) *reinterpret_cast<tu32x4*>(DE + (size_t)m * 128 + 32 * cbw + 16 * g + 8 * h) = tpack8(o);
+                if (m < p_end) *reinterpret_cast<u32x4*>(DE + (size_t)m * 128 + 32 * cbw + 16 * g + 8 * h) = pack8(o);
             }
         }
         m0 += 64;
@@ -2563,18 +2465,18 @@ __device__ __forceinline__ unsigned att_hash_base(const TDrop& d, unsigned key_s
     return (unsigned)P + (unsigned)(P >> 32) * 0xC2B2AE35u + key_site;
 }
 // rows [row0, row0 + 32 nb) of qkv column block `col` (+ 16 hd) -> [row][2 halves] A-fragment image (8 bf16 each), scaled; rows >= n are zero
-__device__ __forceinline__ void att_stage_rows(tu32x4* img, const float* __restrict__ src, int ld, int base, int row0, int nb, int n, float scl, int tid, int nthr) {
-    const tu32x4 z4 = {0u, 0u, 0u, 0u};
+__device__ __forceinline__ void att_stage_rows(u32x4* img, const float* __restrict__ src, int ld, int base, int row0, int nb, int n, float scl, int tid, int nthr) {
+    const u32x4 z4 = {0u, 0u, 0u, 0u};
     for (int idx = tid; idx < nb * 64; idx += nthr) {
         const int row = row0 + (idx >> 1), hh = idx & 1;
         const float* p = src + (size_t)(base + (row < n ? row : n - 1)) * ld + 8 * hh;
-        const tf32x4 a = *reinterpret_cast<const tf32x4*>(p), c = *reinterpret_cast<const tf32x4*>(p + 4);
-        const tu32x4 v = {tpack2(scl * a[0], scl * a[1]), tpack2(scl * a[2], scl * a[3]), tpack2(scl * c[0], scl * c[1]), tpack2(scl * c[2], scl * c[3])};
+        const f32x4 a = *reinterpret_cast<const f32x4*>(p), c = *reinterpret_cast<const f32x4*>(p + 4);
+        const u32x4 v = {pack2(scl * a[0], scl * a[1]), pack2(scl * a[2], scl * a[3]), pack2(scl * c[0], scl * c[1]), pack2(scl * c[2], scl * c[3])};
         img[idx] = row < n ? v : z4;
     }
 }
 // the same rows TRANSPOSED: [block][s][h][d 0..15] = 8 rows in the order the packed accumulator registers carry them (A operand of X^T . tile)
-__device__ __forceinline__ void att_stage_rows_t(tu32x4* img, const float* __restrict__ src, int ld, int base, int row0, int nb, int n, float scl, int tid, int nthr) {
+__device__ __forceinline__ void att_stage_rows_t(u32x4* img, const float* __restrict__ src, int ld, int base, int row0, int nb, int n, float scl, int tid, int nthr) {
     for (int idx = tid; idx < nb * 64; idx += nthr) {
         const int d = idx & 15, hh = (idx >> 4) & 1, sblk = (idx >> 5) & 1, blk = idx >> 6;
         float vals[8];
@@ -2588,13 +2490,13 @@ __device__ __forceinline__ void att_stage_rows_t(tu32x4* img, const float* __res
             const int row = row0 + 32 * blk + 16 * sblk + 8 * (j >> 2) + 4 * hh + (j & 3);
             vals[j] = row < n ? scl * vals[j] : 0.f;
         }
-        img[idx] = tu32x4{tpack2(vals[0], vals[1]), tpack2(vals[2], vals[3]), tpack2(vals[4], vals[5]), tpack2(vals[6], vals[7])};
+        img[idx] = u32x4{pack2(vals[0], vals[1]), pack2(vals[2], vals[3]), pack2(vals[4], vals[5]), pack2(vals[6], vals[7])};
     }
 }
 #define ATT_CHUNK 32            // 32-row blocks per LDS chunk
 __global__ void __launch_bounds__(512) k_attn_fwd_m16(PackInfo pk, const float* __restrict__ qkv, int heads, float* __restrict__ out,
                                                       float* __restrict__ stat, TDrop dr, unsigned site) {
-    __shared__ __attribute__((aligned(16))) tu32x4 Kimg[ATT_CHUNK * 64], Vt[ATT_CHUNK * 64];
+    __shared__ __attribute__((aligned(16))) u32x4 Kimg[ATT_CHUNK * 64], Vt[ATT_CHUNK * 64];
     const int b = blockIdx.x, hd = blockIdx.y;
     const int n = pk.len[b];
     const int qbase = blockIdx.z * 256;
@@ -2602,19 +2504,19 @@ __global__ void __launch_bounds__(512) k_attn_fwd_m16(PackInfo pk, const float* 
     const int base = pk.cu[b];
     const int nkb = (n + 31) / 32;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-    const tu32x4 z4 = {0u, 0u, 0u, 0u};
+    const u32x4 z4 = {0u, 0u, 0u, 0u};
     const int q0 = qbase + 32 * wave;
     const bool wave_live = q0 < n;
     const int qi = q0 + r;
     const int qrow = base + (qi < n ? qi : n - 1);
-    tu32x4 qf = z4;
+    u32x4 qf = z4;
     if (qi < n) {
         const float* qp = qkv + (size_t)qrow * 384 + hd * 16 + 8 * h;
-        const tf32x4 a = *reinterpret_cast<const tf32x4*>(qp), c = *reinterpret_cast<const tf32x4*>(qp + 4);
-        qf = tu32x4{tpack2(0.25f * a[0], 0.25f * a[1]), tpack2(0.25f * a[2], 0.25f * a[3]), tpack2(0.25f * c[0], 0.25f * c[1]), tpack2(0.25f * c[2], 0.25f * c[3])};
+        const f32x4 a = *reinterpret_cast<const f32x4*>(qp), c = *reinterpret_cast<const f32x4*>(qp + 4);
+        qf = u32x4{pack2(0.25f * a[0], 0.25f * a[1]), pack2(0.25f * a[2], 0.25f * a[3]), pack2(0.25f * c[0], 0.25f * c[1]), pack2(0.25f * c[2], 0.25f * c[3])};
     }
     const unsigned hb = att_hash_base(dr, drop_key(dr, site), qrow, heads, hd);
-    tf32x16 acc;
+    f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     float m_run = -3.0e38f, l_run = 0.f;
@@ -2627,10 +2529,10 @@ __global__ void __launch_bounds__(512) k_attn_fwd_m16(PackInfo pk, const float* 
         if (!wave_live) continue;
         for (int kl = 0; kl < cb; ++kl) {
             const int kb = kb0 + kl;
-            tf32x16 sc;
+            f32x16 sc;
 #pragma unroll
             for (int i = 0; i < 16; ++i) sc[i] = 0.f;
-            sc = tmfma(Kimg[(32 * kl + r) * 2 + h], qf, sc);                      // S^T[key][query]
+            sc = mfma32(Kimg[(32 * kl + r) * 2 + h], qf, sc);                      // S^T[key][query]
             float mx = -3.0e38f;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
@@ -2652,10 +2554,10 @@ __global__ void __launch_bounds__(512) k_attn_fwd_m16(PackInfo pk, const float* 
             for (int i = 0; i < 16; ++i) sc[i] *= att_mask(dr, hb, 32 * kb + (i & 3) + 8 * (i >> 2) + 4 * h);       // (adjacent registers = adjacent keys: the compiler shares the pair's hash)
 #pragma unroll
             for (int sblk = 0; sblk < 2; ++sblk) {
-                const tu32x4 pf = {tpack2(sc[8 * sblk], sc[8 * sblk + 1]), tpack2(sc[8 * sblk + 2], sc[8 * sblk + 3]),
-                                   tpack2(sc[8 * sblk + 4], sc[8 * sblk + 5]), tpack2(sc[8 * sblk + 6], sc[8 * sblk + 7])};
-                const tu32x4 vf = r < 16 ? Vt[((kl * 2 + sblk) * 2 + h) * 16 + r] : z4;
-                acc = tmfma(vf, pf, acc);                                       // O^T[d][query]
+                const u32x4 pf = {pack2(sc[8 * sblk], sc[8 * sblk + 1]), pack2(sc[8 * sblk + 2], sc[8 * sblk + 3]),
+                                   pack2(sc[8 * sblk + 4], sc[8 * sblk + 5]), pack2(sc[8 * sblk + 6], sc[8 * sblk + 7])};
+                const u32x4 vf = r < 16 ? Vt[((kl * 2 + sblk) * 2 + h) * 16 + r] : z4;
+                acc = mfma32(vf, pf, acc);                                       // O^T[d][query]
             }
         }
     }
@@ -2663,14 +2565,14 @@ __global__ void __launch_bounds__(512) k_attn_fwd_m16(PackInfo pk, const float* 
     if (qi < n) {
         const float inv = 1.0f / l_tot;
         float* op = out + (size_t)qrow * RN_D + hd * 16 + 4 * h;                // rows d = (i&3) + 8(i>>2) + 4h, i < 8
-        *reinterpret_cast<tf32x4*>(op) = tf32x4{acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv};
-        *reinterpret_cast<tf32x4*>(op + 8) = tf32x4{acc[4] * inv, acc[5] * inv, acc[6] * inv, acc[7] * inv};
+        *reinterpret_cast<f32x4*>(op) = f32x4{acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv};
+        *reinterpret_cast<f32x4*>(op + 8) = f32x4{acc[4] * inv, acc[5] * inv, acc[6] * inv, acc[7] * inv};
         if (h == 0) { float* st = stat + ((size_t)qrow * heads + hd) * 3; st[0] = m_run; st[1] = l_tot; }
     }
 }
 __global__ void __launch_bounds__(512) k_attn_bwd_q_m16(PackInfo pk, const float* __restrict__ qkv, const float* __restrict__ O,
         const float* __restrict__ dO, float* __restrict__ dqkv, float* __restrict__ stat, int heads, TDrop dr, unsigned site) {
-    __shared__ __attribute__((aligned(16))) tu32x4 Kimg[ATT_CHUNK * 64], Vimg[ATT_CHUNK * 64], Kt[ATT_CHUNK * 64];
+    __shared__ __attribute__((aligned(16))) u32x4 Kimg[ATT_CHUNK * 64], Vimg[ATT_CHUNK * 64], Kt[ATT_CHUNK * 64];
     const int b = blockIdx.x, hd = blockIdx.y;
     const int n = pk.len[b];
     const int qbase = blockIdx.z * 256;
@@ -2678,22 +2580,22 @@ __global__ void __launch_bounds__(512) k_attn_bwd_q_m16(PackInfo pk, const float
     const int base = pk.cu[b];
     const int nkb = (n + 31) / 32;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-    const tu32x4 z4 = {0u, 0u, 0u, 0u};
+    const u32x4 z4 = {0u, 0u, 0u, 0u};
     const int q0 = qbase + 32 * wave;
     const bool wave_live = q0 < n;
     const int qi = q0 + r;
     const int qrow = base + (qi < n ? qi : n - 1);
-    tu32x4 qf = z4, gf = z4;
+    u32x4 qf = z4, gf = z4;
     float delta = 0.f;
     if (qi < n) {
         const float* qp = qkv + (size_t)qrow * 384 + hd * 16 + 8 * h;
-        const tf32x4 a = *reinterpret_cast<const tf32x4*>(qp), c = *reinterpret_cast<const tf32x4*>(qp + 4);
-        qf = tu32x4{tpack2(0.25f * a[0], 0.25f * a[1]), tpack2(0.25f * a[2], 0.25f * a[3]), tpack2(0.25f * c[0], 0.25f * c[1]), tpack2(0.25f * c[2], 0.25f * c[3])};
+        const f32x4 a = *reinterpret_cast<const f32x4*>(qp), c = *reinterpret_cast<const f32x4*>(qp + 4);
+        qf = u32x4{pack2(0.25f * a[0], 0.25f * a[1]), pack2(0.25f * a[2], 0.25f * a[3]), pack2(0.25f * c[0], 0.25f * c[1]), pack2(0.25f * c[2], 0.25f * c[3])};
         const float* gp = dO + (size_t)qrow * RN_D + hd * 16 + 8 * h;
         const float* op = O + (size_t)qrow * RN_D + hd * 16 + 8 * h;
-        const tf32x4 g0 = *reinterpret_cast<const tf32x4*>(gp), g1 = *reinterpret_cast<const tf32x4*>(gp + 4);
-        const tf32x4 o0 = *reinterpret_cast<const tf32x4*>(op), o1 = *reinterpret_cast<const tf32x4*>(op + 4);
-        gf = tu32x4{tpack2(g0[0], g0[1]), tpack2(g0[2], g0[3]), tpack2(g1[0], g1[1]), tpack2(g1[2], g1[3])};
+        const f32x4 g0 = *reinterpret_cast<const f32x4*>(gp), g1 = *reinterpret_cast<const f32x4*>(gp + 4);
+        const f32x4 o0 = *reinterpret_cast<const f32x4*>(op), o1 = *reinterpret_cast<const f32x4*>(op + 4);
+        gf = u32x4{pack2(g0[0], g0[1]), pack2(g0[2], g0[3]), pack2(g1[0], g1[1]), pack2(g1[2], g1[3])};
 #pragma unroll
         for (int d = 0; d < 4; ++d) delta = fmaf(g0[d], o0[d], fmaf(g1[d], o1[d], delta));
     }
@@ -2701,7 +2603,7 @@ __global__ void __launch_bounds__(512) k_attn_bwd_q_m16(PackInfo pk, const float
     const float* stp = stat + ((size_t)qrow * heads + hd) * 3;
     const float m = stp[0], linv = 1.0f / stp[1];
     const unsigned hb = att_hash_base(dr, drop_key(dr, site), qrow, heads, hd);
-    tf32x16 acc;
+    f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     for (int kb0 = 0; kb0 < nkb; kb0 += ATT_CHUNK) {
@@ -2714,11 +2616,11 @@ __global__ void __launch_bounds__(512) k_attn_bwd_q_m16(PackInfo pk, const float
         if (!wave_live) continue;
         for (int kl = 0; kl < cb; ++kl) {
             const int kb = kb0 + kl;
-            tf32x16 sc, dp;
+            f32x16 sc, dp;
 #pragma unroll
             for (int i = 0; i < 16; ++i) { sc[i] = 0.f; dp[i] = 0.f; }
-            sc = tmfma(Kimg[(32 * kl + r) * 2 + h], qf, sc);                      // S^T[key][query]
-            dp = tmfma(Vimg[(32 * kl + r) * 2 + h], gf, dp);                      // dP^T[key][query] = v_key . dO_query
+            sc = mfma32(Kimg[(32 * kl + r) * 2 + h], qf, sc);                      // S^T[key][query]
+            dp = mfma32(Vimg[(32 * kl + r) * 2 + h], gf, dp);                      // dP^T[key][query] = v_key . dO_query
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int key = 32 * kb + (i & 3) + 8 * (i >> 2) + 4 * h;
@@ -2728,23 +2630,23 @@ __global__ void __launch_bounds__(512) k_attn_bwd_q_m16(PackInfo pk, const float
             }
 #pragma unroll
             for (int sblk = 0; sblk < 2; ++sblk) {
-                const tu32x4 df = {tpack2(sc[8 * sblk], sc[8 * sblk + 1]), tpack2(sc[8 * sblk + 2], sc[8 * sblk + 3]),
-                                   tpack2(sc[8 * sblk + 4], sc[8 * sblk + 5]), tpack2(sc[8 * sblk + 6], sc[8 * sblk + 7])};
-                const tu32x4 kf = r < 16 ? Kt[((kl * 2 + sblk) * 2 + h) * 16 + r] : z4;
-                acc = tmfma(kf, df, acc);                                       // dQ^T[d][query]
+                const u32x4 df = {pack2(sc[8 * sblk], sc[8 * sblk + 1]), pack2(sc[8 * sblk + 2], sc[8 * sblk + 3]),
+                                   pack2(sc[8 * sblk + 4], sc[8 * sblk + 5]), pack2(sc[8 * sblk + 6], sc[8 * sblk + 7])};
+                const u32x4 kf = r < 16 ? Kt[((kl * 2 + sblk) * 2 + h) * 16 + r] : z4;
+                acc = mfma32(kf, df, acc);                                       // dQ^T[d][query]
             }
         }
     }
     if (qi < n) {
         float* o = dqkv + (size_t)qrow * 384 + hd * 16 + 4 * h;
-        *reinterpret_cast<tf32x4*>(o) = tf32x4{0.25f * acc[0], 0.25f * acc[1], 0.25f * acc[2], 0.25f * acc[3]};
-        *reinterpret_cast<tf32x4*>(o + 8) = tf32x4{0.25f * acc[4], 0.25f * acc[5], 0.25f * acc[6], 0.25f * acc[7]};
+        *reinterpret_cast<f32x4*>(o) = f32x4{0.25f * acc[0], 0.25f * acc[1], 0.25f * acc[2], 0.25f * acc[3]};
+        *reinterpret_cast<f32x4*>(o + 8) = f32x4{0.25f * acc[4], 0.25f * acc[5], 0.25f * acc[6], 0.25f * acc[7]};
         if (h == 0) stat[((size_t)qrow * heads + hd) * 3 + 2] = delta;
     }
 }
 __global__ void __launch_bounds__(512) k_attn_bwd_kv_m16(PackInfo pk, const float* __restrict__ qkv, const float* __restrict__ dO,
         float* __restrict__ dqkv, const float* __restrict__ stat, int heads, TDrop dr, unsigned site) {
-    __shared__ __attribute__((aligned(16))) tu32x4 Qimg[ATT_CHUNK * 64], Gimg[ATT_CHUNK * 64], Qt[ATT_CHUNK * 64], Gt[ATT_CHUNK * 64];
+    __shared__ __attribute__((aligned(16))) u32x4 Qimg[ATT_CHUNK * 64], Gimg[ATT_CHUNK * 64], Qt[ATT_CHUNK * 64], Gt[ATT_CHUNK * 64];
     __shared__ float s_m[ATT_CHUNK * 32], s_li[ATT_CHUNK * 32], s_de[ATT_CHUNK * 32];
     __shared__ unsigned s_hb[ATT_CHUNK * 32];
     const int b = blockIdx.x, hd = blockIdx.y;
@@ -2754,21 +2656,21 @@ __global__ void __launch_bounds__(512) k_attn_bwd_kv_m16(PackInfo pk, const floa
     const int base = pk.cu[b];
     const int nqb = (n + 31) / 32;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-    const tu32x4 z4 = {0u, 0u, 0u, 0u};
+    const u32x4 z4 = {0u, 0u, 0u, 0u};
     const int k0 = kbase + 32 * wave;
     const bool wave_live = k0 < n;
     const int kj = k0 + r;
     const int krow = base + (kj < n ? kj : n - 1);
-    tu32x4 kf = z4, vf = z4;
+    u32x4 kf = z4, vf = z4;
     if (kj < n) {
         const float* kp = qkv + (size_t)krow * 384 + 128 + hd * 16 + 8 * h;
-        const tf32x4 a = *reinterpret_cast<const tf32x4*>(kp), c = *reinterpret_cast<const tf32x4*>(kp + 4);
-        const tf32x4 v0 = *reinterpret_cast<const tf32x4*>(kp + 128), v1 = *reinterpret_cast<const tf32x4*>(kp + 132);
-        kf = tu32x4{tpack2(a[0], a[1]), tpack2(a[2], a[3]), tpack2(c[0], c[1]), tpack2(c[2], c[3])};
-        vf = tu32x4{tpack2(v0[0], v0[1]), tpack2(v0[2], v0[3]), tpack2(v1[0], v1[1]), tpack2(v1[2], v1[3])};
+        const f32x4 a = *reinterpret_cast<const f32x4*>(kp), c = *reinterpret_cast<const f32x4*>(kp + 4);
+        const f32x4 v0 = *reinterpret_cast<const f32x4*>(kp + 128), v1 = *reinterpret_cast<const f32x4*>(kp + 132);
+        kf = u32x4{pack2(a[0], a[1]), pack2(a[2], a[3]), pack2(c[0], c[1]), pack2(c[2], c[3])};
+        vf = u32x4{pack2(v0[0], v0[1]), pack2(v0[2], v0[3]), pack2(v1[0], v1[1]), pack2(v1[2], v1[3])};
     }
     const unsigned key_site = drop_key(dr, site);
-    tf32x16 dk, dv;
+    f32x16 dk, dv;
 #pragma unroll
     for (int i = 0; i < 16; ++i) { dk[i] = 0.f; dv[i] = 0.f; }
     for (int qb0 = 0; qb0 < nqb; qb0 += ATT_CHUNK) {
@@ -2789,12 +2691,12 @@ __global__ void __launch_bounds__(512) k_attn_bwd_kv_m16(PackInfo pk, const floa
         if (!wave_live) continue;
         for (int ql = 0; ql < cb; ++ql) {
             const int qb = qb0 + ql;
-            tf32x16 sc, dp;
+            f32x16 sc, dp;
 #pragma unroll
             for (int i = 0; i < 16; ++i) { sc[i] = 0.f; dp[i] = 0.f; }
-            sc = tmfma(Qimg[(32 * ql + r) * 2 + h], kf, sc);                      // S[query][key], one key per lane
-            dp = tmfma(Gimg[(32 * ql + r) * 2 + h], vf, dp);                      // dP[query][key] = dO_query . v_key
-            tf32x16 pm;
+            sc = mfma32(Qimg[(32 * ql + r) * 2 + h], kf, sc);                      // S[query][key], one key per lane
+            dp = mfma32(Gimg[(32 * ql + r) * 2 + h], vf, dp);                      // dP[query][key] = dO_query . v_key
+            f32x16 pm;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int ql_i = (i & 3) + 8 * (i >> 2) + 4 * h, q = 32 * qb + ql_i;
@@ -2807,23 +2709,23 @@ __global__ void __launch_bounds__(512) k_attn_bwd_kv_m16(PackInfo pk, const floa
             }
 #pragma unroll
             for (int sblk = 0; sblk < 2; ++sblk) {
-                const tu32x4 pf = {tpack2(pm[8 * sblk], pm[8 * sblk + 1]), tpack2(pm[8 * sblk + 2], pm[8 * sblk + 3]),
-                                   tpack2(pm[8 * sblk + 4], pm[8 * sblk + 5]), tpack2(pm[8 * sblk + 6], pm[8 * sblk + 7])};
-                const tu32x4 df = {tpack2(sc[8 * sblk], sc[8 * sblk + 1]), tpack2(sc[8 * sblk + 2], sc[8 * sblk + 3]),
-                                   tpack2(sc[8 * sblk + 4], sc[8 * sblk + 5]), tpack2(sc[8 * sblk + 6], sc[8 * sblk + 7])};
-                const tu32x4 gt = r < 16 ? Gt[((ql * 2 + sblk) * 2 + h) * 16 + r] : z4;
-                const tu32x4 qt = r < 16 ? Qt[((ql * 2 + sblk) * 2 + h) * 16 + r] : z4;
-                dv = tmfma(gt, pf, dv);                                         // dV^T[d][key] += dO^T . (P M)
-                dk = tmfma(qt, df, dk);                                         // dK^T[d][key] += (Q / 4)^T . dS
+                const u32x4 pf = {pack2(pm[8 * sblk], pm[8 * sblk + 1]), pack2(pm[8 * sblk + 2], pm[8 * sblk + 3]),
+                                   pack2(pm[8 * sblk + 4], pm[8 * sblk + 5]), pack2(pm[8 * sblk + 6], pm[8 * sblk + 7])};
+                const u32x4 df = {pack2(sc[8 * sblk], sc[8 * sblk + 1]), pack2(sc[8 * sblk + 2], sc[8 * sblk + 3]),
+                                   pack2(sc[8 * sblk + 4], sc[8 * sblk + 5]), pack2(sc[8 * sblk + 6], sc[8 * sblk + 7])};
+                const u32x4 gt = r < 16 ? Gt[((ql * 2 + sblk) * 2 + h) * 16 + r] : z4;
+                const u32x4 qt = r < 16 ? Qt[((ql * 2 + sblk) * 2 + h) * 16 + r] : z4;
+                dv = mfma32(gt, pf, dv);                                         // dV^T[d][key] += dO^T . (P M)
+                dk = mfma32(qt, df, dk);                                         // dK^T[d][key] += (Q / 4)^T . dS
             }
         }
     }
     if (kj < n) {
         float* o = dqkv + (size_t)krow * 384 + 128 + hd * 16 + 4 * h;
-        *reinterpret_cast<tf32x4*>(o) = tf32x4{dk[0], dk[1], dk[2], dk[3]};
-        *reinterpret_cast<tf32x4*>(o + 8) = tf32x4{dk[4], dk[5], dk[6], dk[7]};
-        *reinterpret_cast<tf32x4*>(o + 128) = tf32x4{dv[0], dv[1], dv[2], dv[3]};
-        *reinterpret_cast<tf32x4*>(o + 136) = tf32x4{dv[4], dv[5], dv[6], dv[7]};
+        *reinterpret_cast<f32x4*>(o) = f32x4{dk[0], dk[1], dk[2], dk[3]};
+        *reinterpret_cast<f32x4*>(o + 8) = f32x4{dk[4], dk[5], dk[6], dk[7]};
+        *reinterpret_cast<f32x4*>(o + 128) = f32x4{dv[0], dv[1], dv[2], dv[3]};
+        *reinterpret_cast<f32x4*>(o + 136) = f32x4{dv[4], dv[5], dv[6], dv[7]};
     }
 }
 // returns 0 when handled (head dim 16); the caller falls back to the f32 kernels otherwise
@@ -2863,18 +2765,18 @@ __global__ void __launch_bounds__(256) k_eseg_mean(PackInfo pk, int k, const int
         const bool valid = (vm >> sl) & 1ull;               // (a select, not a multiply by 0: an absent slot's row may hold anything)
         if (g2_out) {                                       // (uniform) leave gelu' * mask for the backward, in place of pre2 when the two alias
             float g0, d0, g1, d1;
-            gelu_both_fast(tbf_lo(w), g0, d0); gelu_both_fast(tbf_hi(w), g1, d1);
+            gelu_both_fast(lo_bf(w), g0, d0); gelu_both_fast(hi_bf(w), g1, d1);
             s0 += valid ? g0 * m0 : 0.f;
             s1 += valid ? g1 * m1 : 0.f;
-            *reinterpret_cast<unsigned*>(g2_out + (size_t)p * k * RN_D + c + (size_t)sl * RN_D) = valid ? tpack2(d0 * m0, d1 * m1) : 0u;
+            *reinterpret_cast<unsigned*>(g2_out + (size_t)p * k * RN_D + c + (size_t)sl * RN_D) = valid ? pack2(d0 * m0, d1 * m1) : 0u;
         } else {
-            s0 += valid ? gelu_fast(tbf_lo(w)) * m0 : 0.f;
-            s1 += valid ? gelu_fast(tbf_hi(w)) * m1 : 0.f;
+            s0 += valid ? gelu_fast(lo_bf(w)) * m0 : 0.f;
+            s1 += valid ? gelu_fast(hi_bf(w)) * m1 : 0.f;
         }
     }
     const float inv = 1.0f / (float)(cnt > 0 ? cnt : 1);
-    const tf32x2 hv = *reinterpret_cast<const tf32x2*>(hin + (size_t)p * RN_D + c);
-    *reinterpret_cast<tf32x2*>(out + (size_t)p * RN_D + c) = tf32x2{hv[0] + s0 * inv, hv[1] + s1 * inv};
+    const f32x2 hv = *reinterpret_cast<const f32x2*>(hin + (size_t)p * RN_D + c);
+    *reinterpret_cast<f32x2*>(out + (size_t)p * RN_D + c) = f32x2{hv[0] + s0 * inv, hv[1] + s1 * inv};
 }
 __global__ void __launch_bounds__(256) k_eseg_mean_bwd(PackInfo pk, int k, const int* __restrict__ nbr, const float* __restrict__ dagg,
                                                        const tb16* __restrict__ pre2, tb16* __restrict__ dpre2, TDrop dr, unsigned site) {
@@ -2885,7 +2787,7 @@ __global__ void __launch_bounds__(256) k_eseg_mean_bwd(PackInfo pk, int k, const
     const unsigned long long vm = __ballot(lane < k && nbr[(size_t)p * k + (lane < k ? lane : 0)] >= 0);
     const int cnt = __popcll(vm);
     const float inv = 1.0f / (float)(cnt > 0 ? cnt : 1);
-    const tf32x2 g = *reinterpret_cast<const tf32x2*>(dagg + (size_t)p * RN_D + c);
+    const f32x2 g = *reinterpret_cast<const f32x2*>(dagg + (size_t)p * RN_D + c);
     const float g0 = g[0] * inv, g1 = g[1] * inv;
     const tb16* base = pre2 + (size_t)p * k * RN_D + c;
     tb16* obase = dpre2 + (size_t)p * k * RN_D + c;
@@ -2895,7 +2797,7 @@ __global__ void __launch_bounds__(256) k_eseg_mean_bwd(PackInfo pk, int k, const
         float m0, m1;
         drop_pair(dr, key, (unsigned)(p * k + sl) * 64u + lane, m0, m1);
         const bool valid = (vm >> sl) & 1ull;
-        const unsigned o = tpack2(g0 * gelu_d_fast(tbf_lo(w)) * m0, g1 * gelu_d_fast(tbf_hi(w)) * m1);
+        const unsigned o = pack2(g0 * gelu_d_fast(lo_bf(w)) * m0, g1 * gelu_d_fast(hi_bf(w)) * m1);
         *reinterpret_cast<unsigned*>(obase + (size_t)sl * RN_D) = valid ? o : 0u;
     }
 }
@@ -2923,41 +2825,40 @@ __global__ void k_eelem(PackInfo pk, int k, const int* __restrict__ nbr, int mod
     const size_t n = (size_t)pk.cu[pk.B] * k * 16;
     for (size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x; id < n; id += (size_t)gridDim.x * blockDim.x) {
         const bool valid = nbr[id >> 4] >= 0;
-        tu32x4* xp = reinterpret_cast<tu32x4*>(x) + id;
-        if (mode == 1) { if (!valid) *xp = tu32x4{0u, 0u, 0u, 0u}; continue; }
+        u32x4* xp = reinterpret_cast<u32x4*>(x) + id;
+        if (mode == 1) { if (!valid) *xp = u32x4{0u, 0u, 0u, 0u}; continue; }
         if (mode == 2) {                                      // x = valid ? drop(gelu(pre2)) : 0
-            tu32x4 o2 = {0u, 0u, 0u, 0u};
+            u32x4 o2 = {0u, 0u, 0u, 0u};
             if (valid) {
                 float pr[8], dm[8];
-                unpack8(reinterpret_cast<const tu32x4*>(pre2)[id], pr);
+                unpack8(reinterpret_cast<const u32x4*>(pre2)[id], pr);
                 drop8(dr, drop_key(dr, site), (unsigned)id, dm);
 #pragma unroll
                 for (int q = 0; q < 8; ++q) pr[q] = gelu_fast(pr[q]) * dm[q];
-                o2 = tpack8(pr);
+                o2 = pack8(pr);
             }
             *xp = o2;
             continue;
         }
-        tu32x4 o = {0u, 0u, 0u, 0u};
+        u32x4 o = {0u, 0u, 0u, 0u};
         if (valid) {
             float d[8], pr[8];
-            unpack8(reinterpret_cast<const tu32x4*>(de)[id], d);
-            unpack8(reinterpret_cast<const tu32x4*>(pre2)[id], pr);
+            unpack8(reinterpret_cast<const u32x4*>(de)[id], d);
+            unpack8(reinterpret_cast<const u32x4*>(pre2)[id], pr);
             float dm[8];
             drop8(dr, drop_key(dr, site), (unsigned)id, dm);
 #pragma unroll
             for (int q = 0; q < 8; ++q) d[q] *= gelu_d_fast(pr[q]) * dm[q];
-            o = tpack8(d);
+            o = pack8(d);
         }
         *xp = o;
     }
 }
-static unsigned eelem_grid(const PackInfo& pk, int k) { size_t g = ((size_t)pk.Nmax * k * 16 + 255) / 256; return (unsigned)(g < 16384 ? (g ? g : 1) : 16384); }
 void te_edge_res_bwd(const PackInfo& pk, int k, const int* nbr, const tb16* de, const tb16* pre2, tb16* dpre2, const TDrop& dr, unsigned site, hipStream_t s) {
-    hipLaunchKernelGGL(k_eelem, dim3(eelem_grid(pk, k)), dim3(256), 0, s, pk, k, nbr, 0, de, pre2, dpre2, dr, site);
+    hipLaunchKernelGGL(k_eelem, dim3(ew_grid((size_t)pk.Nmax * k * 16)), dim3(256), 0, s, pk, k, nbr, 0, de, pre2, dpre2, dr, site);
 }
 void te_edge_act(const PackInfo& pk, int k, const int* nbr, const tb16* pre, tb16* out, const TDrop& dr, unsigned site, hipStream_t s) {
-    hipLaunchKernelGGL(k_eelem, dim3(eelem_grid(pk, k)), dim3(256), 0, s, pk, k, nbr, 2, nullptr, pre, out, dr, site);
+    hipLaunchKernelGGL(k_eelem, dim3(ew_grid((size_t)pk.Nmax * k * 16)), dim3(256), 0, s, pk, k, nbr, 2, nullptr, pre, out, dr, site);
 }
 // one wave per residue: lane = (row group g of 4, 16-byte chunk c16 of the 256-byte row); the 4 groups are folded with fixed-order shuffles
 __global__ void __launch_bounds__(256) k_epq_bwd(PackInfo pk, int k, const tb16* __restrict__ dpre1, const int* __restrict__ start,
@@ -2968,14 +2869,14 @@ __global__ void __launch_bounds__(256) k_epq_bwd(PackInfo pk, int k, const tb16*
     float sp[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, sq[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int sl = g; sl < k; sl += 4) {
         float v[8];
-        unpack8(*reinterpret_cast<const tu32x4*>(dpre1 + ((size_t)p * k + sl) * RN_D + c), v);
+        unpack8(*reinterpret_cast<const u32x4*>(dpre1 + ((size_t)p * k + sl) * RN_D + c), v);
 #pragma unroll
         for (int q = 0; q < 8; ++q) sp[q] += v[q];
     }
     const int t1 = start[p + 1];
     for (int t = start[p] + g; t < t1; t += 4) {
         float v[8];
-        unpack8(*reinterpret_cast<const tu32x4*>(dpre1 + (size_t)list[t] * RN_D + c), v);
+        unpack8(*reinterpret_cast<const u32x4*>(dpre1 + (size_t)list[t] * RN_D + c), v);
 #pragma unroll
         for (int q = 0; q < 8; ++q) sq[q] += v[q];
     }
@@ -2986,10 +2887,10 @@ __global__ void __launch_bounds__(256) k_epq_bwd(PackInfo pk, int k, const tb16*
     }
     if (g == 0) {
         float* o = dpq + (size_t)p * 256 + c;
-        *reinterpret_cast<tf32x4*>(o) = tf32x4{sp[0], sp[1], sp[2], sp[3]};
-        *reinterpret_cast<tf32x4*>(o + 4) = tf32x4{sp[4], sp[5], sp[6], sp[7]};
-        *reinterpret_cast<tf32x4*>(o + 128) = tf32x4{sq[0], sq[1], sq[2], sq[3]};
-        *reinterpret_cast<tf32x4*>(o + 132) = tf32x4{sq[4], sq[5], sq[6], sq[7]};
+        *reinterpret_cast<f32x4*>(o) = f32x4{sp[0], sp[1], sp[2], sp[3]};
+        *reinterpret_cast<f32x4*>(o + 4) = f32x4{sp[4], sp[5], sp[6], sp[7]};
+        *reinterpret_cast<f32x4*>(o + 128) = f32x4{sq[0], sq[1], sq[2], sq[3]};
+        *reinterpret_cast<f32x4*>(o + 132) = f32x4{sq[4], sq[5], sq[6], sq[7]};
     }
 }
 void te_edge_pq_bwd(const PackInfo& pk, int k, const tb16* dpre1, const int* start, const int* list, float* dpq, hipStream_t s) {

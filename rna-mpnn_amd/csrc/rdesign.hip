@@ -11,6 +11,7 @@
 // (rdesign_train.hip, rdesign_train_bf16.hip); the inference forward passes the no-dropout TDrop and its in-place GELU scratch.
 // PARITY: pinned to the reference's own modules in eval mode (graph, raw features, h_V, logits) by tests/golden/rdesign_*.npz - see oracle/rdesign_oracle.py.
 #include "rdesign_internal.h"
+#include "bf16_core.h"
 
 #include <cstdarg>
 #include <cstdio>
@@ -39,12 +40,6 @@ __device__ __forceinline__ V3 scale(V3 a, float s) { return V3{a.x * s, a.y * s,
 __device__ __forceinline__ V3 unit_nan0(V3 a) { const float n = sqrtf(dot(a, a)); return n > 0.f ? scale(a, 1.0f / n) : V3{0.f, 0.f, 0.f}; }
 // F.normalize: v / max(|v|, 1e-12)
 __device__ __forceinline__ V3 unit_eps(V3 a) { return scale(a, 1.0f / fmaxf(sqrtf(dot(a, a)), 1e-12f)); }
-__device__ __forceinline__ float gelu_e(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
-__device__ __forceinline__ tb16 rd_bf(float v) {          // round-to-nearest-even bf16
-    typedef __attribute__((ext_vector_type(2))) float f2; typedef __attribute__((ext_vector_type(2))) __bf16 b2;
-    f2 t = {v, 0.f};
-    return (tb16)(__builtin_bit_cast(unsigned, __builtin_convertvector(t, b2)) & 0xffffu);
-}
 
 // atom q of the FLATTENED 6-atom chain of batch row b (feature.py:85-86,138): coordinates of a valid residue, zeros for a padded
 // one (the collate zero-fills, utils/data.py:113-115); `inside` = the position exists in the (B, T) tensor at all
@@ -243,7 +238,7 @@ __global__ void __launch_bounds__(256) k_rd_rownorm(const int* __restrict__ ntot
         if (mode == 0) inv = 1.0f / (sqrtf(q / 127.f + 1e-6f) + 1e-6f);
         else inv = 1.0f / sqrtf(q / 128.f + 1e-5f);
         const float o0 = gain[lane] * d0 * inv + bias[lane], o1 = gain[64 + lane] * d1 * inv + bias[64 + lane];
-        if (yb) { yb[row * RD_H + lane] = rd_bf(o0); yb[row * RD_H + 64 + lane] = rd_bf(o1); }      // bf16 edge tensors of the bf16 path
+        if (yb) { yb[row * RD_H + lane] = f2bf(o0); yb[row * RD_H + 64 + lane] = f2bf(o1); }      // bf16 edge tensors of the bf16 path
         else { y[row * RD_H + lane] = o0; y[row * RD_H + 64 + lane] = o1; }
     }
 }
@@ -263,7 +258,7 @@ __global__ void __launch_bounds__(128) k_rd_segsum(PackInfo pk, int K, const int
     const int c = threadIdx.x;
     float s = 0.f;
     for (int sl = 0; sl < K; ++sl)
-        if (nbr[(size_t)p * K + sl] >= 0) s += gelu_e(pre[((size_t)p * K + sl) * RD_H + c]);
+        if (nbr[(size_t)p * K + sl] >= 0) s += gelu_erf(pre[((size_t)p * K + sl) * RD_H + c]);
     out[(size_t)p * RD_H + c] = s * inv_scale;
 }
 
@@ -281,8 +276,8 @@ __global__ void __launch_bounds__(256) k_rd_segsum_b(PackInfo pk, int K, const i
     for (int sl = 0; sl < K; ++sl) {
         const unsigned w = *reinterpret_cast<const unsigned*>(base + (size_t)sl * RD_H);
         const bool valid = (vm >> sl) & 1ull;
-        s0 += valid ? gelu_e(__uint_as_float(w << 16)) : 0.f;
-        s1 += valid ? gelu_e(__uint_as_float(w & 0xffff0000u)) : 0.f;
+        s0 += valid ? gelu_erf(lo_bf(w)) : 0.f;
+        s1 += valid ? gelu_erf(hi_bf(w)) : 0.f;
     }
     out[(size_t)p * RD_H + c] = s0 * inv_scale; out[(size_t)p * RD_H + c + 1] = s1 * inv_scale;
 }

@@ -13,7 +13,7 @@
 // PARITY: the p = 0 loss and gradients are pinned to the reference's own float64 autograd (tests/golden/rdesign_*.npz); the dropout masks are not
 // (torch's RNG cannot be matched): with dropout the checker is the restatement tests/_rdesign_train_ref.py, itself pinned at p = 0.
 #include "rdesign_internal.h"
-#include "train_dev.h"      // gelu_f, gelu_d, drop_mul: the dropout hash the element-wise kernels of kernels_train.hip use - one definition
+#include "train_dev.h"      // gelu_erf, gelu_d, drop_mul: the dropout hash the element-wise kernels of kernels_train.hip use - one definition
 
 // ------------------------------------------------------------------------------------------ row-normalisation backward
 // One wave per 128-wide row, two channels per lane; the row statistics are recomputed from the taped input v = x (+ res).
@@ -73,7 +73,7 @@ __global__ void __launch_bounds__(128) k_rdt_segsum(PackInfo pk, int K, const in
         for (int sl = 0; sl < K; ++sl)
             if (nbr[(size_t)p * K + sl] >= 0) {
                 const size_t o = ((size_t)p * K + sl) * RD_H + c;
-                s += gelu_f(pre[o]) * drop_mul(dr, site, o);
+                s += gelu_erf(pre[o]) * drop_mul(dr, site, o);
             }
         out[(size_t)p * RD_H + c] = s * inv_scale;
     }

@@ -23,17 +23,6 @@
 #include "rdesign_internal.h"
 #include "train_dev.h"
 
-typedef __attribute__((ext_vector_type(2))) float rbf2;
-typedef __attribute__((ext_vector_type(4))) float rbf4;
-typedef __attribute__((ext_vector_type(4))) unsigned rbu4;
-typedef __attribute__((ext_vector_type(2))) __bf16 rbb2;
-__device__ __forceinline__ unsigned rb_pack2(float a, float b) {          // two round-to-nearest-even bf16 in one word (even channel low)
-    rbf2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, rbb2));
-}
-__device__ __forceinline__ float rb_lo(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float rb_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
-
 // ------------------------------------------------------------------------------------------ raw edge features as a bf16 GEMM operand
 // F[e][0:128] (bf16) = edge_raw[e][0:115] | zeros: the operand te_gemm (kvalid 115) and te_gemm_tn (cols_keep 115) read.  One thread = 8 channels.
 __global__ void __launch_bounds__(256) k_rdb_eraw16(const int* __restrict__ ntot_p, int K, const float* __restrict__ raw, tb16* __restrict__ F) {
@@ -45,7 +34,7 @@ __global__ void __launch_bounds__(256) k_rdb_eraw16(const int* __restrict__ ntot
         float v[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) v[q] = c + q < RD_EDGE ? src[q] : 0.f;
-        reinterpret_cast<rbu4*>(F)[id] = rbu4{rb_pack2(v[0], v[1]), rb_pack2(v[2], v[3]), rb_pack2(v[4], v[5]), rb_pack2(v[6], v[7])};
+        reinterpret_cast<u32x4*>(F)[id] = pack8(v);
     }
 }
 
@@ -55,10 +44,10 @@ __global__ void __launch_bounds__(256) k_rdb_normalize16(const int* __restrict__
                                                          const float* __restrict__ bias, tb16* __restrict__ y) {
     const size_t R = (size_t)*ntot_p * mul;
     const int lane = threadIdx.x & 63, c = 2 * lane;
-    const rbf2 gw = *reinterpret_cast<const rbf2*>(gain + c), bw = *reinterpret_cast<const rbf2*>(bias + c);
+    const f32x2 gw = *reinterpret_cast<const f32x2*>(gain + c), bw = *reinterpret_cast<const f32x2*>(bias + c);
     for (size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < R; row += (size_t)gridDim.x * 4) {
         const unsigned w = *reinterpret_cast<const unsigned*>(x + row * RD_H + c);
-        const float v0 = rb_lo(w), v1 = rb_hi(w);
+        const float v0 = lo_bf(w), v1 = hi_bf(w);
         float s = v0 + v1;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
@@ -68,7 +57,7 @@ __global__ void __launch_bounds__(256) k_rdb_normalize16(const int* __restrict__
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
         const float inv = 1.0f / (sqrtf(q / 127.f + 1e-6f) + 1e-6f);
-        *reinterpret_cast<unsigned*>(y + row * RD_H + c) = rb_pack2(gw[0] * d0 * inv + bw[0], gw[1] * d1 * inv + bw[1]);
+        *reinterpret_cast<unsigned*>(y + row * RD_H + c) = pack2(gw[0] * d0 * inv + bw[0], gw[1] * d1 * inv + bw[1]);
     }
 }
 
@@ -85,19 +74,19 @@ __global__ void __launch_bounds__(256) k_rdb_rownorm_bwd(const int* __restrict__
     __shared__ float red[4][256];
     const size_t R = (size_t)*ntot_p * mul;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = 2 * lane;
-    const rbf2 gw = *reinterpret_cast<const rbf2*>(gain + c);
+    const f32x2 gw = *reinterpret_cast<const f32x2*>(gain + c);
     float sg0 = 0.f, sg1 = 0.f, sb0 = 0.f, sb1 = 0.f;
     for (size_t row = (size_t)blockIdx.x * 4 + wave; row < R; row += (size_t)gridDim.x * 4) {
         float v0, v1;
         if constexpr (XB) {
             const unsigned w = *reinterpret_cast<const unsigned*>(reinterpret_cast<const tb16*>(xv) + row * RD_H + c);
-            v0 = rb_lo(w); v1 = rb_hi(w);
+            v0 = lo_bf(w); v1 = hi_bf(w);
         } else {
-            const rbf2 w = *reinterpret_cast<const rbf2*>(reinterpret_cast<const float*>(xv) + row * RD_H + c);
+            const f32x2 w = *reinterpret_cast<const f32x2*>(reinterpret_cast<const float*>(xv) + row * RD_H + c);
             v0 = w[0]; v1 = w[1];
-            if (res) { const rbf2 r2 = *reinterpret_cast<const rbf2*>(res + row * RD_H + c); v0 += r2[0]; v1 += r2[1]; }
+            if (res) { const f32x2 r2 = *reinterpret_cast<const f32x2*>(res + row * RD_H + c); v0 += r2[0]; v1 += r2[1]; }
         }
-        const rbf2 yv = *reinterpret_cast<const rbf2*>(dy + row * RD_H + c);
+        const f32x2 yv = *reinterpret_cast<const f32x2*>(dy + row * RD_H + c);
         float s = v0 + v1;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
@@ -116,8 +105,8 @@ __global__ void __launch_bounds__(256) k_rdb_rownorm_bwd(const int* __restrict__
         for (int o = 32; o > 0; o >>= 1) { sg += __shfl_xor(sg, o, 64); sgd += __shfl_xor(sgd, o, 64); }
         const float mg = sg / 128.f, k = sgd * inv * inv / (n * root);
         const float o0 = (g0 - mg) * inv - d0 * k, o1 = (g1 - mg) * inv - d1 * k;
-        if constexpr (OB) *reinterpret_cast<unsigned*>(reinterpret_cast<tb16*>(dxv) + row * RD_H + c) = rb_pack2(o0, o1);
-        else *reinterpret_cast<rbf2*>(reinterpret_cast<float*>(dxv) + row * RD_H + c) = rbf2{o0, o1};
+        if constexpr (OB) *reinterpret_cast<unsigned*>(reinterpret_cast<tb16*>(dxv) + row * RD_H + c) = pack2(o0, o1);
+        else *reinterpret_cast<f32x2*>(reinterpret_cast<float*>(dxv) + row * RD_H + c) = f32x2{o0, o1};
         sg0 += yv[0] * d0 * inv; sg1 += yv[1] * d1 * inv;
         sb0 += yv[0]; sb1 += yv[1];
     }
@@ -154,12 +143,12 @@ __global__ void __launch_bounds__(256) k_rdb_segsum(PackInfo pk, int K, const in
         float m0, m1;
         drop_pair(dr, key, (unsigned)(p * K + sl) * 64u + lane, m0, m1);
         const bool valid = (vm >> sl) & 1ull;               // (a select: an absent slot's row may hold anything)
-        const float x0 = rb_lo(w), x1 = rb_hi(w);
+        const float x0 = lo_bf(w), x1 = hi_bf(w);
         s0 += valid ? gelu_fast(x0) * m0 : 0.f;
         s1 += valid ? gelu_fast(x1) * m1 : 0.f;
-        *reinterpret_cast<unsigned*>(base + (size_t)sl * RD_H) = valid ? rb_pack2(gelu_d_fast(x0) * m0, gelu_d_fast(x1) * m1) : 0u;
+        *reinterpret_cast<unsigned*>(base + (size_t)sl * RD_H) = valid ? pack2(gelu_d_fast(x0) * m0, gelu_d_fast(x1) * m1) : 0u;
     }
-    *reinterpret_cast<rbf2*>(out + (size_t)p * RD_H + c) = rbf2{s0 * inv_scale, s1 * inv_scale};
+    *reinterpret_cast<f32x2*>(out + (size_t)p * RD_H + c) = f32x2{s0 * inv_scale, s1 * inv_scale};
 }
 
 // ------------------------------------------------------------------------------------------ element-wise helpers of the edge chain
@@ -167,9 +156,9 @@ __global__ void __launch_bounds__(256) k_rdb_segsum(PackInfo pk, int K, const in
 __global__ void __launch_bounds__(256) k_rdb_mark_dropped(const int* __restrict__ ntot_p, int K, tb16* __restrict__ pre, TDrop dr, unsigned site) {
     const size_t n = (size_t)*ntot_p * K * 16;
     const unsigned key = drop_key(dr, site);
-    const unsigned dropped = rb_pack2(TE_DROPPED, TE_DROPPED);
+    const unsigned dropped = pack2(TE_DROPPED, TE_DROPPED);
     for (size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x; id < n; id += (size_t)gridDim.x * blockDim.x) {
-        rbu4 v = reinterpret_cast<const rbu4*>(pre)[id];
+        u32x4 v = reinterpret_cast<const u32x4*>(pre)[id];
         float dm[8];
         drop8(dr, key, (unsigned)id, dm);
 #pragma unroll
@@ -178,7 +167,7 @@ __global__ void __launch_bounds__(256) k_rdb_mark_dropped(const int* __restrict_
             const unsigned hi = dm[2 * q + 1] == 0.f ? (dropped & 0xffff0000u) : (v[q] & 0xffff0000u);
             v[q] = lo | hi;
         }
-        reinterpret_cast<rbu4*>(pre)[id] = v;
+        reinterpret_cast<u32x4*>(pre)[id] = v;
     }
 }
 // acc[e][c] = (first ? 0 : acc[e][c]) + de[e][c];  de = 0: the f32 accumulator of d h_E over the L layers; te_gemm_bwd1 ADDS into its bf16 DE
@@ -186,13 +175,13 @@ __global__ void __launch_bounds__(256) k_rdb_mark_dropped(const int* __restrict_
 __global__ void __launch_bounds__(256) k_rdb_acc(const int* __restrict__ ntot_p, int K, tb16* __restrict__ de, float* __restrict__ acc, int first) {
     const size_t n = (size_t)*ntot_p * K * 16;
     for (size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x; id < n; id += (size_t)gridDim.x * blockDim.x) {
-        const rbu4 v = reinterpret_cast<const rbu4*>(de)[id];
-        rbf4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
-        if (!first) { a = reinterpret_cast<const rbf4*>(acc)[2 * id]; b = reinterpret_cast<const rbf4*>(acc)[2 * id + 1]; }
-        a[0] += rb_lo(v[0]); a[1] += rb_hi(v[0]); a[2] += rb_lo(v[1]); a[3] += rb_hi(v[1]);
-        b[0] += rb_lo(v[2]); b[1] += rb_hi(v[2]); b[2] += rb_lo(v[3]); b[3] += rb_hi(v[3]);
-        reinterpret_cast<rbf4*>(acc)[2 * id] = a; reinterpret_cast<rbf4*>(acc)[2 * id + 1] = b;
-        reinterpret_cast<rbu4*>(de)[id] = rbu4{0u, 0u, 0u, 0u};
+        const u32x4 v = reinterpret_cast<const u32x4*>(de)[id];
+        f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
+        if (!first) { a = reinterpret_cast<const f32x4*>(acc)[2 * id]; b = reinterpret_cast<const f32x4*>(acc)[2 * id + 1]; }
+        a[0] += lo_bf(v[0]); a[1] += hi_bf(v[0]); a[2] += lo_bf(v[1]); a[3] += hi_bf(v[1]);
+        b[0] += lo_bf(v[2]); b[1] += hi_bf(v[2]); b[2] += lo_bf(v[3]); b[3] += hi_bf(v[3]);
+        reinterpret_cast<f32x4*>(acc)[2 * id] = a; reinterpret_cast<f32x4*>(acc)[2 * id + 1] = b;
+        reinterpret_cast<u32x4*>(de)[id] = u32x4{0u, 0u, 0u, 0u};
     }
 }
 // t[i] = v for i < n: the per-residue table of te_gemm_bwd2 mode 2 (1 / scale for every residue here, 1 / count in the main model)
@@ -223,7 +212,6 @@ size_t rdb_carve(const rdesign_ctx* c, int B, size_t Nmax, char* base, RdtWs& w,
     e.dB = reinterpret_cast<tb16*>(w.f.E2);                                        // (before the first layer: scratch of t_build_reverse)
     return w.off;
 }
-unsigned ew_grid(size_t units) { const size_t g = (units + 255) / 256; return (unsigned)(g < 16384 ? (g ? g : 1) : 16384); }
 unsigned row_grid(size_t maxrows, size_t cap) { size_t g = (maxrows + 3) / 4; if (g > cap) g = cap; return (unsigned)(g ? g : 1); }
 }  // namespace
 

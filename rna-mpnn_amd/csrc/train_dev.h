@@ -1,10 +1,11 @@
-// Device primitives shared by the translation units with training kernels (kernels_train.hip, rdesign_train.hip): GELU, the row count of a
-// TRows, and the dropout counter hash.  ONE definition: every kernel of the trainer and oracle/rnampnn_oracle.py: dropout_multiplier must
+// Device primitives shared by the translation units with training kernels (kernels_train.hip, rdesign_train.hip, rdesign_train_bf16.hip): on top of
+// bf16_core.h (bf16 packs, MFMA, gelu_erf, gelu_fast / phi_fast) the derivatives of both GELU forms, the row count of a TRows, and the dropout
+// counter hash.  ONE definition: every kernel of the trainer and oracle/rnampnn_oracle.py: dropout_multiplier must
 // agree on the mask bit for bit.  Include from device code only.
 #pragma once
 #include "kernels_train.h"
+#include "bf16_core.h"
 
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_d(float x) {     // d/dx [x Phi(x)] = Phi(x) + x phi(x)
     return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
 }
@@ -29,9 +30,6 @@ __device__ __forceinline__ float drop_mul(const TDrop& d, unsigned site, unsigne
 // both elements of pair P (element indices 2P, 2P + 1) when P is known to fit 32 bits (every [rows][D] tensor of the trainer: the
 // entry points bound rows * D / 2 < 2^32); key = drop_key(d, site)
 __device__ __forceinline__ void drop_pair(const TDrop& d, unsigned key, unsigned P, float& m0, float& m1) {
-#ifdef TE_EXP_NOHASH      // timing experiment only (wrong masks): what the hash costs
-    m0 = m1 = __uint_as_float((P + key) & 0x3f800000u); return;
-#endif
     if (d.thresh == 0u) { m0 = 1.f; m1 = 1.f; return; }
     const unsigned x = drop_hash(P + key);
     m0 = (x & 0xffffu) >= d.thresh ? d.scale : 0.f;
@@ -42,20 +40,13 @@ __device__ __forceinline__ void drop8(const TDrop& d, unsigned key, unsigned P8,
 #pragma unroll
     for (int q = 0; q < 4; ++q) drop_pair(d, key, 4u * P8 + q, m[2 * q], m[2 * q + 1]);
 }
-// GELU and its derivative for the fused prologues / epilogues of the bf16-mixed GEMMs: Phi(x) ~ sigmoid(x (c0 + c1 x^2)),
-// coefficients minimax-fitted to the erf form (max |x Phi - gelu| 2.7e-4, below the bf16 rounding of the operands these
-// values are converted to); derivative = Phi + x phi.  The f32 kernels (parity grade) keep erff.
-__device__ __forceinline__ float phi_fast(float x) {
-#ifdef TE_EXP_NOACT       // timing experiment only (wrong values): what the transcendental GELU costs
-    return fmaf(x, 0.25f, 0.5f);
-#endif
-    const float p = fmaf(x * x, -0.10012571f, -2.3087657f);           // -log2(e) (c0 + c1 x^2)
-    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * p));
-}
-__device__ __forceinline__ float gelu_fast(float x) { return x * phi_fast(x); }
+// The derivative of gelu_fast (bf16_core.h) for the fused prologues / epilogues of the bf16-mixed GEMMs: Phi + x phi with the same sigmoid-form
+// Phi (below the bf16 rounding of the operands these values are converted to).  The f32 kernels (parity grade) keep erff.
 __device__ __forceinline__ float gelu_d_fast(float x) {
-#ifdef TE_EXP_NOACT
-    return fmaf(x, 0.5f, 0.5f);
-#endif
     return fmaf(x * 0.3989422804f, __builtin_amdgcn_exp2f(x * x * -0.72134752f), phi_fast(x));
+}
+__device__ __forceinline__ void gelu_both_fast(float x, float& g, float& d) {          // (gelu_fast(x), gelu_d_fast(x)) sharing the sigmoid
+    const float sg = phi_fast(x);
+    g = x * sg;
+    d = fmaf(x * 0.3989422804f, __builtin_amdgcn_exp2f(x * x * -0.72134752f), sg);
 }
