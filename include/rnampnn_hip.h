@@ -90,7 +90,9 @@ typedef struct RnaMpnnForwardIO {
                                  GLOBAL batch max_len here.  It is the node-axis length GraphNormalization sees
                                  (functional.py:33-38) AND the padded length of the phantom-edge rule (an RNA with
                                  n - 1 < k keeps an edge to a padded residue iff n < max(T, T_norm)), so an
-                                 edge_index tap may name index T: a padded residue that exists only in the global batch. */
+                                 edge_index tap may name index T: a padded residue that exists only in the global batch.
+                                 The rule is unconditional: where max(T, T_norm) - n is 1 or 2 the reference's topk tie-break leaves -1
+                                 in that slot in part of the rows ("The k-NN tie class"). */
     int32_t stop_after;       /* 0 = whole forward; 1 = stop after ResFeature.forward (feature.py:573-592) */
     float*   logits;          /* (B,T,4)    RNAMPNN.forward          rnampnn.py:161-185 (required if stop_after==0) */
     float*   embedding;       /* (B,T,256)  RNAMPNN.embedding        rnampnn.py:269-278 */

@@ -184,15 +184,34 @@ def graph_norm(x: Tensor, mask: Tensor, scale: Tensor, shift: Tensor) -> Tensor:
 
 
 # ----------------------------------------------------------------------------- A2
-def knn_graph(coords: Tensor, mask: Tensor, k: int) -> Tensor:
+def knn_graph(coords: Tensor, mask: Tensor, k: int, edge_index: Optional[Tensor] = None) -> Tensor:
     """Residue k-NN graph (feature.py:205-256) -> edge_index (B,T,k) int64, -1 = no edge.
 
     Canonical form of the reference result: real neighbours ascending by centroid distance
-    (ties by lower index); if a valid row has fewer than k real neighbours and the batch is
-    padded (T > n) the reference keeps ONE extra edge to a padded residue (fp32: self and all
-    padded residues tie at exactly 1e6 and CPU topk returns a padded index).  All padded
-    residues are interchangeable (zero coords from the collate, zero embedding), so the
-    oracle names the first one, index n.  With T == n that slot is the row itself -> -1."""
+    (ties by lower index).  A valid row with fewer than k real neighbours (n - 1 < k) in a padded
+    batch (T > n) has the row itself and every padded residue tied at exactly 1e6 behind its real
+    neighbours; ``topk`` takes them in an order the model does not define, and the reference then
+    drops a self-pick (-1) and keeps one padded pick in slot n - 1.  What the reference's CPU run
+    gives there (measured through ``tools/gen_golden.py``):
+
+      T - n >= 3        slot n - 1 holds a padded index in every row   (all top-level goldens)
+      1 <= T - n <= 2   slot n - 1 holds a padded index or -1, row by row (-1 in 30 - 70 % of the rows)
+      T == n            -1 (the slot is the row itself)
+
+    All padded residues are interchangeable (zero coords from the collate, zero embedding), so the
+    class of graphs the reference can return is: slot n - 1 in {-1, phantom n} when n - 1 < k and
+    T > n, everything else fixed (``edge_index_in_class``).  The project's rule - oracle and
+    kernels - is the unconditional member, the phantom whenever n - 1 < k and T > n: it is
+    deterministic, and it is the same for a shard that stands for a longer batch (``T_norm``), which
+    a rule depending on T - n could not be.  Cost of the choice, oracle on its own graph against the
+    oracle on the reference's graph, max |dlogit| on the short RNA (k = 30, 10 layers;
+    tests/golden/rnampnn_ties/): lens [20, 21] 1.5e-4, [20, 22] 1.5e-4, [27, 28, 25] 1.0e-4,
+    [12, 13] 1.2e-4, [5, 6] at k = 5 and 2 layers 2.9e-5; the other RNAs of those batches and
+    everything behind the graph agree with the reference to 7e-7.
+
+    ``edge_index`` (test infrastructure): a given graph is returned as it is, in place of the search."""
+    if edge_index is not None:
+        return edge_index.to(torch.int64)
     B, T = mask.shape
     cen = coords.mean(dim=2)                                            # :218
     d = torch.sqrt(((cen.unsqueeze(1) - cen.unsqueeze(2)) ** 2).sum(-1) + SEPS)   # :220-221
@@ -216,9 +235,23 @@ def knn_graph(coords: Tensor, mask: Tensor, k: int) -> Tensor:
 
 
 def canonical_edge_index(edge_index: Tensor, mask: Tensor) -> Tensor:
-    """Map any padded neighbour index (>= n) to n: the equivalence class the tie rule allows."""
+    """Map any padded neighbour index (>= n) to n: the padded residues are interchangeable."""
     n = mask.sum(-1).long().view(-1, 1, 1)
     return torch.where(edge_index >= n, n.expand_as(edge_index), edge_index)
+
+
+def edge_index_in_class(ref: Tensor, got: Tensor, mask: Tensor, k: int) -> bool:
+    """True iff two graphs agree after ``canonical_edge_index`` except where the reference's tie-break is free (``knn_graph``):
+    slot n - 1 of a valid row with n - 1 < k and T > n may hold -1 in one and the phantom index n in the other."""
+    B, T = mask.shape
+    if tuple(ref.shape) != (B, T, k) or tuple(got.shape) != (B, T, k):
+        return False
+    a, b = canonical_edge_index(ref.long(), mask), canonical_edge_index(got.long(), mask)
+    n = mask.sum(-1).long().view(B, 1, 1)
+    slot = torch.arange(k).view(1, 1, k)
+    free = (slot == n - 1) & (n - 1 < k) & (n < T) & (n >= 1) & (mask > 0).unsqueeze(-1)
+    either = ((a == -1) | (a == n)) & ((b == -1) | (b == n))
+    return bool(torch.where(free, either, a == b).all())
 
 
 # ----------------------------------------------------------------------------- A6
@@ -318,10 +351,10 @@ def _graph_norm_ttot(x: Tensor, m: Tensor, scale: Tensor, shift: Tensor, t_tot: 
 
 
 # ----------------------------------------------------------------------------- A1-A7
-def res_feature(coords: Tensor, mask: Tensor, sd, cfg: OracleConfig, drop: Optional["Drop"] = None
-                ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    """ResFeature.forward (feature.py:573-592) -> (raw, h0, e0, edge_index)."""
-    idx = knn_graph(coords, mask, cfg.num_res_neighbours)
+def res_feature(coords: Tensor, mask: Tensor, sd, cfg: OracleConfig, drop: Optional["Drop"] = None,
+                edge_index: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """ResFeature.forward (feature.py:573-592) -> (raw, h0, e0, edge_index).  ``edge_index``: see ``knn_graph``."""
+    idx = knn_graph(coords, mask, cfg.num_res_neighbours) if edge_index is None else knn_graph(coords, mask, cfg.num_res_neighbours, edge_index)
     x = edge_raw_features(coords, mask, idx)
     e = _mlp_all_gelu(x, sd, "res_feature.res_edge_embedding_layers", cfg.depth_res_edge_feature, drop, SITE_EE)
     e = e.masked_fill((idx == -1).unsqueeze(-1), 0.0)                   # :564-568
@@ -396,12 +429,14 @@ def readout(x: Tensor, mask: Tensor, sd, cfg: OracleConfig, drop: Optional["Drop
 
 
 def forward(coords: Tensor, mask: Tensor, sd, cfg: OracleConfig, taps: Optional[dict] = None,
-            skip_dead_edge_update: bool = True, dropout: float = 0.0, seed: int = 0) -> Tuple[Tensor, Tensor]:
+            skip_dead_edge_update: bool = True, dropout: float = 0.0, seed: int = 0,
+            edge_index: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """RNAMPNN.forward + embedding (rnampnn.py:173-185, 269-278) -> (logits (B,T,4), embedding (B,T,256)).
     ``taps`` (a dict) receives named intermediates when given.  ``dropout`` > 0: train-mode forward with the
-    counter-hash masks of ``Drop`` (eval mode, the default, is what the golden fixtures pin)."""
+    counter-hash masks of ``Drop`` (eval mode, the default, is what the golden fixtures pin).  ``edge_index`` (test infrastructure):
+    run on this graph in place of ``knn_graph``'s own, e.g. the fp32 graph under fp64 arithmetic or the reference's."""
     drop = Drop(dropout, seed, mask) if dropout > 0.0 else None
-    raw, h, e, idx = res_feature(coords, mask, sd, cfg, drop)
+    raw, h, e, idx = res_feature(coords, mask, sd, cfg, drop, edge_index)
     if taps is not None:
         taps.update(raw=raw, h0=h, e0=e, edge_index=idx)
     L = cfg.num_res_mpnn_layers

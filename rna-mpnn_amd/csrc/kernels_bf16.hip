@@ -246,7 +246,8 @@ struct NodeTabs {             // per-residue parts of the first Linears (k_node_
 // Q rows of the next block are requested during the last four chains of this one.
 // EDGE1: the edge MLP has ONE Linear (num_mpnn_edge_layers = 1, the reference's recorded alternative configuration, train.py:9-43):
 // chains 0..3 carry the residual epilogue themselves (their rows are in e-fragment order: image, P words and routing fragments are
-// built for that), chains 4..7 do not exist.
+// built for that), chains 4..7 do not exist.  Chains 1..3 still read the OLD e while the epilogues of chains 0..2 run, so those write their updated
+// fragments to hb, idle here, and ef takes them behind chain 3's last MFMA (new_e, RN_EDGE1_COMMIT).
 template <bool DO_EDGE, bool DO_MSG, bool SMALLK, bool MSGOUT, bool EDGE1 = false>
 __global__ void __launch_bounds__(RN_MPNN_WAVES * 64, RN_MPNN_WAVES / 4) k_mpnn_bf16(PackInfo pk, int k, const int* __restrict__ nbr, bf16_t* __restrict__ e,
         NodeTabs tab, MpnnWB we, MpnnWB wm, float* __restrict__ agg, float* __restrict__ msg_out) {
@@ -442,6 +443,15 @@ __global__ void __launch_bounds__(RN_MPNN_WAVES * 64, RN_MPNN_WAVES / 4) k_mpnn_
     float s0 = 0.f, s1 = 0.f;
     float ghres[4] = {0.f, 0.f, 0.f, 0.f};           // h of the block whose message epilogues are running (channel 32 cb + r)
     f16x4 gx = h4(0.f), gs = h4(0.f), gq = h4(0.f);    // state carried between the granules of a quarter
+    // Where the residual epilogue of chain c puts the updated e fragment 2 cb + sp.  Two-Linear edge MLP: in place - the residual chains 4..7 run
+    // after every reader of the old e (chains 0..3).  EDGE1: chains 0..3 carry the residual themselves while the later ones of them still
+    // multiply the OLD e by Wc, so the fragments of chains 0..2 are staged in hb (idle until the message MLP's first epilogue) and move to ef
+    // behind chain 3's last MFMA (RN_EDGE1_COMMIT); chain 3's own fragments have no later reader of the old e and are updated in place.
+    auto new_e = [&](auto cc, auto spc) -> u32x4& {
+        constexpr int c = decltype(cc)::value, sp = decltype(spc)::value;
+        if constexpr (EDGE1 && c < 3) return hb[2 * c + sp];
+        else return ef[2 * (c & 3) + sp];
+    };
     auto epi_granule = [&](auto cc, auto gg, f32x16& T, int gblk, unsigned gvmask, float gcntf, float ginv) {
         constexpr int c = decltype(cc)::value, g = decltype(gg)::value;
         constexpr int kind = c >> 2, cb = c & 3;
@@ -464,17 +474,19 @@ __global__ void __launch_bounds__(RN_MPNN_WAVES * 64, RN_MPNN_WAVES / 4) k_mpnn_
             }
             if constexpr (resid) {                     // e <- e + GELU(.): e is f16 as stored, x Phi + e is one packed fma per fragment word
                 constexpr int sp = v >> 1, t = 2 * (v & 1);
+                u32x4& en = new_e(cc, std::integral_constant<int, sp>{});
                 const unsigned o0 = ef[2 * cb + sp][t], o1 = ef[2 * cb + sp][t + 1];
-                ef[2 * cb + sp][t] = __builtin_bit_cast(unsigned, __builtin_elementwise_fma(lo2(gx), lo2(gq), __builtin_bit_cast(f16x2, o0)));
-                ef[2 * cb + sp][t + 1] = __builtin_bit_cast(unsigned, __builtin_elementwise_fma(hi2(gx), hi2(gq), __builtin_bit_cast(f16x2, o1)));
-                if constexpr (v & 1) efrag_ptr(e, gblk, lane)[64 * (2 * cb + sp)] = ef[2 * cb + sp];
+                en[t] = __builtin_bit_cast(unsigned, __builtin_elementwise_fma(lo2(gx), lo2(gq), __builtin_bit_cast(f16x2, o0)));
+                en[t + 1] = __builtin_bit_cast(unsigned, __builtin_elementwise_fma(hi2(gx), hi2(gq), __builtin_bit_cast(f16x2, o1)));
+                if constexpr (v & 1) efrag_ptr(e, gblk, lane)[64 * (2 * cb + sp)] = en;
             }
         } else if constexpr (resid) {                  // (bf16 storage) e <- e + GELU(.), registers 8sp + 2t.. <-> ef[2ob + sp][t]
             constexpr int sp = v >> 1, t = 2 * (v & 1);
+            u32x4& en = new_e(cc, std::integral_constant<int, sp>{});
             const unsigned o0 = ef[2 * cb + sp][t], o1 = ef[2 * cb + sp][t + 1];
-            ef[2 * cb + sp][t] = pack2(fma_mix_lo(T[4 * v], lo2(gq), lo_bf(o0)), fma_mix_hi(T[4 * v + 1], lo2(gq), hi_bf(o0)));
-            ef[2 * cb + sp][t + 1] = pack2(fma_mix_lo(T[4 * v + 2], hi2(gq), lo_bf(o1)), fma_mix_hi(T[4 * v + 3], hi2(gq), hi_bf(o1)));
-            if constexpr (v & 1) efrag_ptr(e, gblk, lane)[64 * (2 * cb + sp)] = ef[2 * cb + sp];
+            en[t] = pack2(fma_mix_lo(T[4 * v], lo2(gq), lo_bf(o0)), fma_mix_hi(T[4 * v + 1], lo2(gq), hi_bf(o0)));
+            en[t + 1] = pack2(fma_mix_lo(T[4 * v + 2], hi2(gq), lo_bf(o1)), fma_mix_hi(T[4 * v + 3], hi2(gq), hi_bf(o1)));
+            if constexpr (v & 1) efrag_ptr(e, gblk, lane)[64 * (2 * cb + sp)] = en;
         } else if constexpr (!SMALLK && !MSGOUT) {     // mean over the real edges of the residue
             // every one of the 32 rows is summed unmasked; rows of absent edges hold GELU(bias) exactly and are taken out again
             if constexpr (v == 0) { s0 = 0.f; s1 = 0.f; gbv = lds_gb[32 * cb + r]; }
@@ -592,6 +604,10 @@ __global__ void __launch_bounds__(RN_MPNN_WAVES * 64, RN_MPNN_WAVES / 4) k_mpnn_
 #define RN_EXTRA_QM(i) do { if constexpr ((i) >= 1 && (i) <= 8 && DO_MSG) gather_q(q, tab.q_m, RN_QROW(j), (i) - 1); } while (0)
         if constexpr (DO_EDGE) {
             RN_SLOT(1, 0, true, RN_NOEXTRA); RN_SLOT(2, 1, true, RN_NOEXTRA); RN_SLOT(3, 2, true, RN_NOEXTRA);
+            if constexpr (EDGE1) {                     // RN_EDGE1_COMMIT: every reader of the old e has issued, the updated fragments 0..5 take their place
+#pragma unroll
+                for (int s = 0; s < 6; ++s) ef[s] = hb[s];
+            }
             if constexpr (!EDGE1) {
                 RN_SLOT(4, 3, true, RN_EXTRA_QM); RN_SLOT(5, 4, true, RN_NOEXTRA); RN_SLOT(6, 5, true, RN_NOEXTRA); RN_SLOT(7, 6, true, RN_NOEXTRA);
             }

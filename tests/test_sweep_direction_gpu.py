@@ -3,7 +3,8 @@ computes a block, and when, does not enter its arithmetic.
 
 k = 30, bf16, L = 4: launch 1 (edge embedding + message 1) sweeps ascending, 2 descending, 3 ascending, 4 descending; an e tap at layer l
 puts an edge-only launch behind launch l, which takes the next direction.  Taps at layer 2 and at layer 3 therefore see the e of a descending
-and of an ascending <edge, message> launch, through an ascending and a descending edge-only launch.  The closed-form weights give nearly flat logits, so the h / e taps carry the checks.
+and of an ascending <edge, message> launch, through an ascending and a descending edge-only launch.  The closed-form weights give nearly flat logits, so the h / e taps carry the checks.  (Against the
+oracle the same taps are held in test_mpnn_taps_gpu.py; here two kernels and two batch compositions are compared.)
 
 Batches, chosen for where the logical -> physical block mapping can break (8 waves per workgroup; 8 or more workgroups: eight contiguous
 ranges, one per XCD):

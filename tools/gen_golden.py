@@ -9,7 +9,11 @@ the weights with the closed-form deterministic init of ``rnampnn/utils/synth.py`
 inputs + outputs as small ``.npz`` fixtures.  ``seeding()`` is deliberately not called
 (it would set float32 matmul precision to 'medium').
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py [top] [taps] [ties]
+
+``top``: the eight top-level fixtures; ``taps``: rnampnn_taps/all_layers_k6.npz, h and e after every ResMPNN layer;
+``ties``: rnampnn_ties/*.npz, batches in which the reference's k-NN tie-break leaves slot n - 1 of a short RNA at -1 in
+some rows (1 <= T - n <= 2).  No argument = all three.
 """
 from __future__ import annotations
 
@@ -159,11 +163,74 @@ def run_case(name, hp, coords, mask, labels, e_nodes=4, outdir=None, full=True):
           f"|logits32-logits64|max={d:.2e} loss={float(res['loss']):.6f} -> {os.path.getsize(path) / 1024:.0f} KB")
 
 
+def taps_case(outdir):
+    """h_l, e_l of the reference modules for l = 1 .. L at k = 6, 10 layers, lens [12, 7, 3]: the fp32 run at every layer, the fp64 run at
+    layer L (all layers in fp64 would pass the size limit of a committed file), and max |fp32 - fp64| of every tap (``noise_h``, ``noise_e``,
+    index l; l = 0 is h0 / e0).  Slots the model never reads - invalid edges, padded residues, where the reference leaves unmasked residual
+    values - are stored as 0."""
+    lens, hp = [12, 7, 3], dict(num_res_neighbours=6, padding_len=12)
+    coords, mask, labels = synth.synth_batch(lens, first_index=800)
+    L = DEFAULTS["num_res_mpnn_layers"]
+    outs = {}
+    for dtype in (torch.float32, torch.float64):
+        model, shapes = build(hp, dtype)
+        outs[dtype] = model.run(torch.from_numpy(coords).to(dtype), torch.from_numpy(mask).to(dtype), tap_layers=range(1, L + 1))
+    o32, o64 = outs[torch.float32], outs[torch.float64]
+    idx = o32["edge_index"]
+    n = torch.from_numpy(mask).sum(-1).long().view(-1, 1, 1)
+    canon = lambda i: torch.where(i >= n, n.expand_as(i), i)              # padded residues are interchangeable
+    assert torch.equal(canon(idx), canon(o64["edge_index"]))
+    ve = ((idx != -1) & (torch.from_numpy(mask) > 0).unsqueeze(-1)).unsqueeze(-1)
+    vh = (torch.from_numpy(mask) > 0).unsqueeze(-1)
+    res = dict(coords=coords, mask=mask, labels=labels, edge_index=idx.numpy().astype(np.int32), hL=o32["hL"].numpy(),
+               logits=o32["logits"].numpy(), logits_f64=o64["logits"].numpy())
+    noise_h, noise_e = np.zeros(L + 1), np.zeros(L + 1)
+    for l in range(L + 1):
+        h32, e32, h64, e64 = (o[f"{n}{l}"] * v for o in (o32, o64) for n, v in (("h", vh), ("e", ve)))
+        res[f"h{l}"], res[f"e{l}"] = h32.numpy(), e32.numpy()
+        noise_h[l], noise_e[l] = float((h32.double() - h64).abs().max()), float((e32.double() - e64).abs().max())
+        if l == L:
+            res[f"h{l}_f64"], res[f"e{l}_f64"] = h64.numpy(), e64.numpy()
+    res["noise_h"], res["noise_e"] = noise_h, noise_e
+    res["hparams"] = np.frombuffer(json.dumps({**DEFAULTS, **hp}).encode(), dtype=np.uint8)
+    res["state_keys"] = np.frombuffer(json.dumps({k: list(s) for k, s in shapes.items()}).encode(), dtype=np.uint8)
+    path = os.path.join(outdir, "all_layers_k6.npz")
+    np.savez_compressed(path, **res)
+    print(f"all_layers_k6: noise_h max {noise_h.max():.2e} noise_e max {noise_e.max():.2e} max|e| {max(float(np.abs(res[f'e{l}']).max()) for l in range(L + 1)):.2f}"
+          f" -> {os.path.getsize(path) / 1024:.0f} KB")
+    assert os.path.getsize(path) < 1000000
+
+
+# batches of synth RNAs whose short RNAs have n - 1 < k next to one or two padded rows: (name, lens, hyper-parameters)
+TIE_CASES = (("k30_20_21", [20, 21], dict(num_res_neighbours=30)),
+             ("k30_20_22", [20, 22], dict(num_res_neighbours=30)),
+             ("k30_27_28_25", [27, 28, 25], dict(num_res_neighbours=30)),
+             ("k5_L2_5_6", [5, 6], dict(num_res_neighbours=5, num_res_mpnn_layers=2)))
+
+
+def ties_cases(outdir):
+    for name, lens, hp in TIE_CASES:
+        co, ma, la = synth.synth_batch(lens, first_index=700)
+        run_case(name, dict(hp, padding_len=max(lens)), co, ma, la, outdir=outdir, full=False)
+        idx = np.load(os.path.join(outdir, name + ".npz"))["edge_index"]
+        for b, n in enumerate(lens):
+            if n - 1 < hp["num_res_neighbours"] and n < max(lens):
+                print(f"  RNA {b} ({n} nt): slot n - 1 is -1 in {int((idx[b, :n, n - 1] == -1).sum())} of {n} rows")
+
+
 def main():
     torch.manual_seed(0)
     torch.set_num_threads(8)
     outdir = os.path.join(REPO, "tests", "golden")
     os.makedirs(outdir, exist_ok=True)
+    groups = set(sys.argv[1:]) or {"top", "taps", "ties"}
+    assert groups <= {"top", "taps", "ties"}, groups
+    for g, fn in (("taps", taps_case), ("ties", ties_cases)):
+        if g in groups:
+            os.makedirs(os.path.join(outdir, "rnampnn_" + g), exist_ok=True)
+            fn(os.path.join(outdir, "rnampnn_" + g))
+    if "top" not in groups:
+        return
 
     # C1: the real 66-nt RNA 1B23_1_R (NaN-free), k=16, T=n, P in {66, 4500}
     real = np.load(os.path.join(REF, "data", "coords", "1B23_1_R.npy")).astype(np.float32)

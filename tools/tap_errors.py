@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Where does the bf16 path's logit error come from?  bf16 vs f32 kernels on the same weights, tap by tap, for the real RNA 1B23_1_R
-(66 nt, T = 80) at several k: h0, e0, h / e after every ResMPNN layer, h_post, logits - max and mean |delta| next to the tensor's own scale.
+(66 nt, T = 80) at several k: h0, e0, h / e after every ResMPNN layer, h_post, logits - the per-channel / per-row / absmax figures of
+tests/_tap_metrics.py (the metric test_mpnn_taps_gpu.py asserts against the oracle) next to the tensor's own scale.
 usage (GPU box): python tools/tap_errors.py [k ...]"""
 import os, sys
 import numpy as np
 import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "rna-mpnn_amd"))
+sys.path.insert(0, os.path.join(REPO, "tests"))
+from _tap_metrics import tap_error
 from rnampnn.model.rnampnn import RNAMPNN
 from rnampnn.utils import synth
 
@@ -31,8 +34,7 @@ for k in ks:
         ok = (tf["edge_index"] >= 0).cpu()
         def rep(name, sel):
             a, b = tf[name].cpu()[sel], tb[name].cpu()[sel]
-            d = (a - b).abs()
-            print(f"  layer {layer:2d} {name:8s} |ref| mean {a.abs().mean():.3e}  |d| max {d.max():.3e} mean {d.mean():.3e}  rel(mean) {d.mean() / a.abs().mean():.3e}")
+            print(f"  layer {layer:2d} {name:8s} |ref| mean {a.abs().mean():.3e}  {tap_error(b, a)}")
         if layer == 1:
             rep("h0", valid); rep("e0", ok)
         rep("h_layer", valid)
