@@ -175,6 +175,25 @@ int rnampnn_sample(const float* logits, const float* mask, int32_t B, int32_t T,
  * "hipGraph-captured decode step"). */
 int rnampnn_sample_dev_seed(const float* logits, const float* mask, int32_t B, int32_t T, float temperature,
                             int32_t n_samples, const uint64_t* seed_device, int8_t* out, void* stream);
+/* Per-RNA scores of one batch of f32 logits in ONE launch (csrc/score.hip): what validation_step / test_step reduce (rnampnn.py:209-236)
+ * and the likelihood of given sequences.  Two layouts of the logits, the same kernel and the same per-RNA reduction order (so the same
+ * bytes for the same rows): padded - logits (B,T,4) + the prefix `mask` (B,T), cu_seqlens null; packed - logits (n_rows,4) + `cu_seqlens`
+ * (B+1), mask null (what rnampnn_forward_packed writes; n_rows is ignored in the padded layout).  `labels` (B,T) int32 class ids and `seqs`
+ * (S,B,T) int8 (the output of rnampnn_sample) are PADDED in both layouts; their entries at t >= n_b are never read.  Outputs, each nullable:
+ *   valid (B) i32        n_b
+ *   pred (B,T) i8        argmax, first maximum wins as rnampnn_argmax_recovery; -1 at t >= n_b
+ *   correct (B) i32      #(argmax == label)
+ *   label_nll (B) f32    sum_t logsumexp(x_t) - x_t[y_t]
+ *   label_loss (B) f32   sum_t -log_softmax(softmax(x_t))[y_t]: the reference's mix_loss (cross-entropy of PROBABILITIES, rnampnn.py:151-154)
+ *   seq_nll (S,B) f32    label_nll of candidate sequence s;   seq_match (S,B) i32   #(seq == label)
+ * An RNA with n_b = 0 gives zeros.  Lengths and cu are clamped to the tensors' extents: a malformed mask gives meaningless numbers, never an
+ * out-of-bounds access.  Fixed reduction order (per-thread ascending rows, wave butterfly, one LDS hop), no atomics, no workspace, no
+ * runtime fill / copy node, no synchronisation: two calls give identical bytes and the call can sit inside a captured graph.
+ * RNAMPNN_ERR_BAD_ARG: neither or both of mask and cu_seqlens, logits not 16-byte aligned, S < 0, S > 0 without seqs (or seqs with S = 0),
+ * seq_nll / seq_match without seqs, correct / seq_match / label_nll / label_loss without labels, B or T <= 0. */
+int rnampnn_score(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, const int32_t* labels,
+                  const int8_t* seqs, int32_t S, int32_t B, int32_t T, int32_t* valid, int8_t* pred, int32_t* correct,
+                  float* label_nll, float* label_loss, float* seq_nll, int32_t* seq_match, void* stream);
 
 /* -- training ---------------------------------------------------------------------------- */
 /* The training surface of RNAMPNN (rnampnn.py:187-207 + Lightning's loss.backward()):

@@ -1,0 +1,171 @@
+// rnampnn_score: the per-RNA metrics of RNAMPNN.validation_step / test_step (rnampnn.py:209-236 of the reference: argmax of the read-out
+// against the labels, recovery per RNA, mix_loss = cross-entropy applied to the softmax PROBABILITIES, rnampnn.py:151-154) and the
+// likelihood of given sequences, on the device, from f32 logits in the padded (B,T,4) + prefix-mask layout rnampnn_forward writes or the
+// packed (N,4) + cu_seqlens layout rnampnn_forward_packed writes.  A sibling of rdesign_score.hip: one 256-thread workgroup per
+// (RNA, pass) - pass 0 scores the labels, pass 1 + s the candidate sequence s - a thread walks its rows in ascending order (one 16-byte
+// load per row), then a wave butterfly and one LDS hop over the four waves: a fixed order that depends on the RNA's length only, so the two
+// layouts give the same bytes for the same rows and two calls give identical bytes.  ONE launch: the workgroup finds its own length (the
+// sum of its mask row, or the difference of two cu entries), so there is no workspace, no runtime fill / copy node, no atomics and no host
+// synchronisation.  About 20 bytes per nucleotide and pass: the call is bounded by its launch, not by bandwidth.
+#include "api_internal.h"
+
+namespace {
+constexpr int SC_THREADS = 256;
+constexpr int SC_WAVES = SC_THREADS / 64;
+
+__device__ __forceinline__ int sc_wave_sum(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float sc_wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+struct ScoreArgs {
+    const float4* logits;        // (B*T) or (n_rows) rows of 4
+    const float* mask;           // (B,T) prefix mask, or null
+    const int32_t* cu;           // (B+1), or null
+    const int32_t* labels;       // (B,T) or null
+    const int8_t* seqs;          // (S,B,T) or null
+    long long n_rows;            // rows the logits tensor holds
+    int B, T, S;
+    int pass0;                   // 1: pass 0 (the label / decode pass) has an output to write
+    int32_t* valid;              // (B)
+    int8_t* pred;                // (B,T)
+    int32_t* correct;            // (B)
+    float* label_nll;            // (B)
+    float* label_loss;           // (B)
+    float* seq_nll;              // (S,B)
+    int32_t* seq_match;          // (S,B)
+};
+
+// The length and the first logits row of RNA b.  Both come from caller data (a mask that need not be the collate's prefix mask, a cu that
+// need not be a prefix sum): they are clamped to the tensors' extents, so a malformed input gives meaningless numbers but no out-of-bounds
+// access.  The mask row is summed as k_lengths sums it (the forward's own length of the RNA).
+__device__ __forceinline__ void sc_extent(const ScoreArgs& a, int b, int tid, float* s_tmp, int& n, long long& row0) {
+    if (a.cu) {
+        const long long lo = min(max((long long)a.cu[b], 0ll), a.n_rows);
+        const long long len = min(max((long long)a.cu[b + 1] - (long long)a.cu[b], 0ll), (long long)a.T);
+        n = (int)min(len, a.n_rows - lo);
+        row0 = lo;
+        return;
+    }
+    float s = 0.f;
+    for (int t = tid; t < a.T; t += SC_THREADS) s += a.mask[(size_t)b * a.T + t];
+    s = sc_wave_sum(s);
+    if ((tid & 63) == 0) s_tmp[tid >> 6] = s;
+    __syncthreads();
+    float tot = 0.f;
+#pragma unroll
+    for (int w = 0; w < SC_WAVES; ++w) tot += s_tmp[w];
+    __syncthreads();                                           // s_tmp is reused by the reductions below
+    n = tot >= 0.f ? (int)fminf(tot + 0.5f, (float)a.T) : 0;    // (a NaN sum compares false: 0)
+    n = min(max(n, 0), a.T);
+    row0 = (long long)b * a.T;
+}
+
+__global__ void __launch_bounds__(SC_THREADS) k_score(ScoreArgs a) {
+    __shared__ int s_i[SC_WAVES];
+    __shared__ float s_f[2][SC_WAVES];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int pass = (int)blockIdx.y + (a.pass0 ? 0 : 1);
+    int n;
+    long long row0;
+    sc_extent(a, b, tid, s_f[0], n, row0);
+    const size_t lab0 = (size_t)b * a.T;
+    int cnt = 0;
+    float nll = 0.f, loss = 0.f;
+    if (pass == 0) {
+        for (int t = tid; t < n; t += SC_THREADS) {
+            const float4 x = a.logits[row0 + t];
+            float m = x.x;                                     // first maximum wins (torch.argmax, rnampnn_argmax_recovery)
+            int best = 0;
+            if (x.y > m) { m = x.y; best = 1; }
+            if (x.z > m) { m = x.z; best = 2; }
+            if (x.w > m) { m = x.w; best = 3; }
+            if (a.pred) a.pred[lab0 + t] = (int8_t)best;
+            if (a.labels) {
+                const int lab = a.labels[lab0 + t];
+                cnt += best == lab ? 1 : 0;
+                if (a.label_nll || a.label_loss) {
+                    const float e0 = expf(x.x - m), e1 = expf(x.y - m), e2 = expf(x.z - m), e3 = expf(x.w - m);
+                    const float se = (e0 + e1) + (e2 + e3);
+                    const float xl = lab == 0 ? x.x : lab == 1 ? x.y : lab == 2 ? x.z : x.w;
+                    nll += (m - xl) + logf(se);                // logsumexp(x) - x[label]
+                    const float inv = 1.0f / se;               // mix_loss: -log_softmax(softmax(x))[label]; the probabilities lie in [0, 1]
+                    const float p0 = e0 * inv, p1 = e1 * inv, p2 = e2 * inv, p3 = e3 * inv;
+                    const float pl = lab == 0 ? p0 : lab == 1 ? p1 : lab == 2 ? p2 : p3;
+                    loss += logf((expf(p0) + expf(p1)) + (expf(p2) + expf(p3))) - pl;
+                }
+            }
+        }
+        if (a.pred)
+            for (int t = n + tid; t < a.T; t += SC_THREADS) a.pred[lab0 + t] = (int8_t)-1;
+    } else {
+        const int8_t* seq = a.seqs + ((size_t)(pass - 1) * a.B + b) * a.T;
+        for (int t = tid; t < n; t += SC_THREADS) {
+            const int q = seq[t];
+            if (a.seq_nll) {
+                const float4 x = a.logits[row0 + t];
+                const float m = fmaxf(fmaxf(x.x, x.y), fmaxf(x.z, x.w));
+                const float se = (expf(x.x - m) + expf(x.y - m)) + (expf(x.z - m) + expf(x.w - m));
+                const float xl = q == 0 ? x.x : q == 1 ? x.y : q == 2 ? x.z : x.w;
+                nll += (m - xl) + logf(se);
+            }
+            if (a.seq_match) cnt += q == a.labels[lab0 + t] ? 1 : 0;
+        }
+    }
+    cnt = sc_wave_sum(cnt);
+    nll = sc_wave_sum(nll);
+    loss = sc_wave_sum(loss);
+    if ((tid & 63) == 0) { s_i[tid >> 6] = cnt; s_f[0][tid >> 6] = nll; s_f[1][tid >> 6] = loss; }
+    __syncthreads();
+    if (tid != 0) return;
+    int ct = 0;
+    float nt = 0.f, lt = 0.f;
+#pragma unroll
+    for (int w = 0; w < SC_WAVES; ++w) { ct += s_i[w]; nt += s_f[0][w]; lt += s_f[1][w]; }
+    if (pass == 0) {
+        if (a.valid) a.valid[b] = n;
+        if (a.correct) a.correct[b] = ct;
+        if (a.label_nll) a.label_nll[b] = nt;
+        if (a.label_loss) a.label_loss[b] = lt;
+    } else {
+        const size_t o = (size_t)(pass - 1) * a.B + b;
+        if (a.seq_nll) a.seq_nll[o] = nt;
+        if (a.seq_match) a.seq_match[o] = ct;
+    }
+}
+}  // namespace
+
+extern "C" int rnampnn_score(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, const int32_t* labels,
+                             const int8_t* seqs, int32_t S, int32_t B, int32_t T, int32_t* valid, int8_t* pred, int32_t* correct,
+                             float* label_nll, float* label_loss, float* seq_nll, int32_t* seq_match, void* stream) {
+    if (!logits || B <= 0 || T <= 0) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: null logits or empty batch (B = %d, T = %d)", (int)B, (int)T);
+    if ((mask != nullptr) == (cu_seqlens != nullptr))
+        return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: pass exactly one of mask (padded logits) and cu_seqlens (packed logits)");
+    if (((uintptr_t)logits & 15) != 0) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: logits must be 16-byte aligned");
+    if (S < 0) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: S = %d candidate sequences", (int)S);
+    if ((S > 0) != (seqs != nullptr)) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: seqs and S > 0 go together");
+    if ((seq_nll || seq_match) && !seqs) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: seq_nll / seq_match need seqs");
+    if ((correct || seq_match || label_nll || label_loss) && !labels)
+        return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: correct / seq_match / label_nll / label_loss need labels");
+    if (cu_seqlens && n_rows < 0) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: negative row count");
+    if (S + 1 > 65535) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: at most 65534 sequences per call");
+    ScoreArgs a{};
+    a.logits = reinterpret_cast<const float4*>(logits);
+    a.mask = mask; a.cu = cu_seqlens; a.labels = labels; a.seqs = seqs;
+    a.n_rows = mask ? (long long)B * T : (long long)n_rows;
+    a.B = B; a.T = T; a.S = S;
+    a.pass0 = (valid || pred || correct || label_nll || label_loss) ? 1 : 0;
+    a.valid = valid; a.pred = pred; a.correct = correct; a.label_nll = label_nll; a.label_loss = label_loss;
+    a.seq_nll = seq_nll; a.seq_match = seq_match;
+    const int passes = a.pass0 + ((seq_nll || seq_match) ? S : 0);
+    if (passes == 0) return RNAMPNN_OK;                        // nothing asked for
+    hipLaunchKernelGGL(k_score, dim3(B, passes), dim3(SC_THREADS), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return RNAMPNN_OK;
+}

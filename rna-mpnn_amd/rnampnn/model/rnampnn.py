@@ -4,8 +4,10 @@ state-dict keys, loss (``:151-154``), optimiser (``:156-159``) and validation me
 running on hand-written HIP kernels through the C ABI of ``include/rnampnn_hip.h``.
 
 Not mirrored: the Lightning base class, the XGBoost read-out (third-party, not installed, no
-pickle ships; ``predict`` uses the ``Readout`` argmax as ``rdesign/model/rdesign.py:152-155`` does)
-and checkpoint hooks.  New (no reference counterpart): ``sample()``.
+pickle ships; ``predict`` uses the device-side tree read-out when one is attached and the ``Readout``
+argmax otherwise, as ``rdesign/model/rdesign.py:152-155`` does) and the Lightning checkpoint hooks
+(``rnampnn/utils/train.py``: ``save_checkpoint`` / ``load_checkpoint`` on ``init_kwargs``).  New (no
+reference counterpart): ``sample()``, ``design()``, ``score_sequences()``.
 """
 from __future__ import annotations
 
@@ -30,7 +32,7 @@ _FIXED_ATOMS = dict(num_inside_dist_atoms=7, num_inside_angle_atoms=6, num_insid
 
 
 class RNAMPNN(NativeModule):
-    def __init__(self, precision: Optional[str] = None, **hparams):
+    def __init__(self, precision: Optional[str] = None, train_precision: Optional[str] = None, **hparams):
         super().__init__()
         unknown = set(hparams) - set(DEFAULT_HPARAMS)
         if unknown:
@@ -45,8 +47,18 @@ class RNAMPNN(NativeModule):
         self.hparams = dict(self._hp)
         # GEMM arithmetic of the TRAINING kernels: "bf16" = the reference's bf16-mixed (MFMA, bf16 operands, f32 accumulate),
         # "f32" = exact (gradient-parity grade).  Follows the inference precision unless set.
-        self.train_precision = self.precision
+        if train_precision not in (None, "f32", "bf16"):
+            raise ValueError("train_precision must be 'f32' or 'bf16'")
+        self.train_precision = train_precision or self.precision
         self.val_step_outputs = {'val_loss': [], 'correct': [], 'len': [], 'recovery_rates': []}
+        self.test_step_outputs = {'test_loss': [], 'correct': [], 'len': [], 'recovery_rates': []}
+
+    @property
+    def init_kwargs(self) -> dict:
+        """Constructor arguments that rebuild this module (plain types: what a checkpoint stores next to the ``state_dict``)."""
+        kw = {k: (v if isinstance(v, (bool, int, str)) else float(v)) for k, v in self.hparams.items()}
+        kw.update(precision=str(self.precision), train_precision=str(self.train_precision))
+        return kw
 
     # ------------------------------------------------------------------ forward surface
     def _run(self, coords, mask, want_logits=True, want_embedding=False, T_norm: int = 0, taps: Optional[Dict] = None,
@@ -497,6 +509,86 @@ class RNAMPNN(NativeModule):
         self.val_step_outputs['recovery_rates'] += recovery_rates
         return {'validation loss': loss, 'recovery_rates': recovery_rates}
 
+    # ------------------------------------------------------------------ device-side scoring (rnampnn_score, csrc/score.hip)
+    @torch.no_grad()
+    def score_batch(self, labels: torch.Tensor, coords: torch.Tensor, mask: torch.Tensor, use_trees: bool = False):
+        """What ``validation_step`` accumulates, per RNA and on the device: one eval-mode forward + one ``rnampnn_score`` ->
+        (correct (B,) int32, valid (B,) int32, label_loss (B,) f32 = per-RNA SUM of ``mix_loss``'s terms, label_nll (B,) f32 = per-RNA
+        sum of logsumexp(x) - x[label]).  Nothing here touches the host.  ``labels``: the collate's one-hot (B,T,4) or class ids (B,T).
+        ``use_trees``: score the class ids of the attached tree read-out on the embedding instead; loss and NLL are then None."""
+        device = self._device()
+        lab = labels.to(device)
+        lab = lab.argmax(dim=-1) if lab.dim() == 3 else lab
+        if use_trees:
+            if getattr(self, "xgb_readout", None) is None:
+                raise RuntimeError("score_batch(use_trees=True) needs a tree read-out: call fit_xgb_readout or load_xgb_readout first")
+            ids = self.xgb_readout.predict(self.embedding(coords, mask))
+            out = score_logits(F.one_hot(ids, 4).to(torch.float32), mask=mask, labels=lab, want=("correct", "valid"))
+            return out["correct"], out["valid"], None, None
+        logits = self._run(coords, mask)["logits"]
+        out = score_logits(logits, mask=mask, labels=lab, want=("correct", "valid", "label_loss", "label_nll"))
+        return out["correct"], out["valid"], out["label_loss"], out["label_nll"]
+
+    @torch.no_grad()
+    def score_sequences(self, coords: torch.Tensor, mask: torch.Tensor, seqs: torch.Tensor, labels: Optional[torch.Tensor] = None):
+        """Likelihood of given sequences under this model: ``seqs`` (S,B,T) or (B,T) class ids (``sample``'s int8 output; entries on
+        padding are never read) -> (seq_nll (S,B) f32 = sum over the RNA of -log p(seq_t), seq_match (S,B) int32 = #(seq == label) or
+        None without ``labels``, valid (B,) int32).  One eval-mode forward + one ``rnampnn_score``; device tensors, no host round trip."""
+        logits = self._run(coords, mask)["logits"]
+        want = ("seq_nll", "valid") + (("seq_match",) if labels is not None else ())
+        if labels is not None:
+            labels = labels.argmax(dim=-1) if labels.dim() == 3 else labels
+        out = score_logits(logits, mask=mask, labels=labels, seqs=seqs if seqs.dim() == 3 else seqs.unsqueeze(0), want=want)
+        return out["seq_nll"], out.get("seq_match"), out["valid"]
+
+    @torch.no_grad()
+    def design(self, coords: torch.Tensor, mask: torch.Tensor, n_samples: int = 8, temperature: float = 0.1, seed: int = 0,
+               T_norm: int = 0):
+        """``sample`` plus the score of every draw against the SAME logits, with one forward: -> (seqs int8 (n_samples,B,T), -1 on
+        padding; seq_nll (n_samples,B) f32).  The NLL is the model's own (temperature 1) likelihood, so designs drawn at different
+        temperatures rank on one scale."""
+        logits = self._run(coords, mask, T_norm=T_norm)["logits"]
+        seqs = sample_from_logits(logits, mask, temperature, n_samples, seed)
+        return seqs, score_logits(logits, mask=mask, seqs=seqs, want=("seq_nll",))["seq_nll"]
+
+    @torch.no_grad()
+    def test_step(self, batch):
+        """rnampnn.py:239-267 through ``score_batch``: the same accumulators as ``validation_step`` under the key ``'test_loss'`` (the
+        reference appends to a ``'val_loss'`` key its ``test_step_outputs`` does not have).  One device-to-host copy per batch."""
+        sequences, coords, mask, _ = batch
+        correct, valid, loss, _ = self.score_batch(sequences, coords, mask)
+        c, v = torch.stack([correct, valid]).cpu().tolist()
+        n_tot = sum(v)
+        loss_sum = loss.sum()
+        rates = [ci / max(vi, 1) for ci, vi in zip(c, v)]
+        self.test_step_outputs['test_loss'].append(loss_sum)
+        self.test_step_outputs['correct'].append(sum(c))
+        self.test_step_outputs['len'].append(n_tot)
+        self.test_step_outputs['recovery_rates'] += rates
+        return {'test loss': loss_sum / max(n_tot, 1), 'recovery_rates': rates}
+
+    @torch.no_grad()
+    def _predict_ids(self, coords: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+        """(B,T) int8 class ids on the device, -1 on padding: the attached tree read-out on the embedding (rnampnn.py:297-298), else
+        the read-out's argmax."""
+        device = self._device()
+        if getattr(self, "xgb_readout", None) is not None:
+            ids = self.xgb_readout.predict(self.embedding(coords, mask)).to(torch.int8)
+            return torch.where(_prep(mask, device) != 0, ids, torch.full_like(ids, -1))
+        return score_logits(self._run(coords, mask)["logits"], mask=mask, want=("pred",))["pred"]
+
+    def predict(self, batch, batch_id, output_dir, filename):
+        """rnampnn.py:280-316: one ``pdb_id,seq`` row per RNA of the batch appended to ``output_dir/filename`` (header on batch 0)."""
+        self.eval()
+        _, coords, mask, pdb_ids = batch
+        seqs = letters_padded(self._predict_ids(coords, mask))
+        os.makedirs(output_dir, exist_ok=True)
+        with open(os.path.join(output_dir, filename), "a") as f:
+            if batch_id == 0:
+                f.write("pdb_id,seq\n")
+            for pdb_id, seq in zip(pdb_ids, seqs):
+                f.write(f"{pdb_id},{seq}\n")
+
 
 class FlatAdam(torch.optim.Optimizer):
     """``torch.optim.Adam`` (default betas / eps, L2 weight decay) for an ``RNAMPNN`` whose parameters and gradients are
@@ -654,6 +746,85 @@ def sample_from_logits(logits: torch.Tensor, mask: torch.Tensor, temperature: fl
         _native.check(_native.lib().rnampnn_sample(_ptr(lg), _ptr(m), B, T, float(temperature), int(n_samples),
                                                    C.c_uint64(int(seed) & (2 ** 64 - 1)), _ptr(out), _stream(device)))
     return out
+
+
+SCORE_OUTPUTS = {"valid": torch.int32, "pred": torch.int8, "correct": torch.int32, "label_nll": torch.float32, "label_loss": torch.float32,
+                 "seq_nll": torch.float32, "seq_match": torch.int32}
+
+
+def score_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
+                 labels: Optional[torch.Tensor] = None, seqs: Optional[torch.Tensor] = None,
+                 want=("valid", "correct", "label_nll", "label_loss"), max_len: Optional[int] = None, out: Optional[Dict] = None,
+                 n_seqs: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """``rnampnn_score`` (include/rnampnn_hip.h): per-RNA scores of f32 logits in one launch -> dict of the outputs named in ``want``
+    (``SCORE_OUTPUTS``).  Padded layout: logits (B,T,4) + ``mask`` (B,T); packed layout: logits (N,4) + ``cu_seqlens`` (B+1), with the
+    padded extent T taken from ``labels`` / ``seqs`` / ``max_len``.  ``labels`` (B,T) class ids and ``seqs`` (S,B,T) are padded in both.
+    ``out``: caller-owned tensors to write into (by name); ``n_seqs``: S when it is not ``seqs.shape[0]``.  No host synchronisation."""
+    device = logits.device
+    if device.type != "cuda":
+        raise RuntimeError("rnampnn_score runs on an MI355X: pass CUDA logits (there is no CPU fallback)")
+    unknown = set(want) - set(SCORE_OUTPUTS)
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}; choose from {sorted(SCORE_OUTPUTS)}")
+    lg = _prep(logits, device)
+    m = None if mask is None else _prep(mask, device)
+    cu = None if cu_seqlens is None else _prep(cu_seqlens, device, torch.int32)
+    lab = None if labels is None else _prep(labels, device, torch.int32)
+    sq = None if seqs is None else _prep(seqs, device, torch.int8)
+    if m is not None:
+        B, T = int(m.shape[0]), int(m.shape[1])
+    else:
+        B = (int(cu.numel()) - 1) if cu is not None else int(lg.shape[0])
+        T = int(lab.shape[-1]) if lab is not None else int(sq.shape[-1]) if sq is not None else int(max_len or 0)
+    if max_len is not None and m is None:
+        T = int(max_len)
+    S = int(n_seqs) if n_seqs is not None else (0 if sq is None else int(sq.shape[0]))
+    for name, t in (("labels", lab), ("seqs", sq)):
+        if t is not None and (tuple(t.shape[-2:]) != (B, T) or (name == "seqs" and (t.dim() != 3 or t.shape[0] < S))):
+            raise ValueError(f"{name} must be padded to (..., B, T) = {(B, T)}, got {tuple(t.shape)}")
+    if lg.shape[-1] != 4 or lg.numel() < (4 * B * T if m is not None else 0):
+        raise ValueError(f"logits must be (B, T, 4) with the mask or (N, 4) with cu_seqlens, got {tuple(lg.shape)}")
+    shapes = {"valid": (B,), "pred": (B, T), "correct": (B,), "label_nll": (B,), "label_loss": (B,), "seq_nll": (max(S, 0), B),
+              "seq_match": (max(S, 0), B)}
+    res, ptrs = {}, {}
+    for name in want:
+        t = None if out is None else out.get(name)
+        if t is None:
+            # (an output asked for is a non-null pointer even where S = 0 leaves it empty: the library decides what that means)
+            numel = int(torch.Size(shapes[name]).numel())
+            buf = torch.empty(max(numel, 1), dtype=SCORE_OUTPUTS[name], device=device)
+            t, ptrs[name] = buf[:numel].view(shapes[name]), C.c_void_p(buf.data_ptr())
+        elif t.dtype != SCORE_OUTPUTS[name] or tuple(t.shape) != shapes[name] or not t.is_contiguous() or t.device != device:
+            raise ValueError(f"out[{name!r}] must be a contiguous {SCORE_OUTPUTS[name]} tensor of shape {shapes[name]} on {device}")
+        else:
+            ptrs[name] = _ptr(t)
+        res[name] = t
+    n_rows = int(lg.numel()) // 4
+    with torch.cuda.device(device):
+        _native.check(_native.lib().rnampnn_score(_ptr(lg), n_rows, _ptr(m), _ptr(cu), _ptr(lab), _ptr(sq), S, B, T,
+                                                  *[ptrs.get(name) for name in SCORE_OUTPUTS], _stream(device)))
+    return res
+
+
+_LETTERS = b"\0" + "".join(REVERSE_VOCAB[i] for i in range(len(REVERSE_VOCAB))).encode()
+
+
+def letters_padded(pred: torch.Tensor) -> List[str]:
+    """(B,T) class ids with -1 on padding (``rnampnn_score``'s ``pred``) -> one string per RNA: one lookup on the device, one copy."""
+    lut = torch.frombuffer(bytearray(_LETTERS), dtype=torch.uint8).to(pred.device)
+    rows = lut[pred.to(torch.int64) + 1].cpu().numpy()
+    return [row.tobytes().split(b"\0", 1)[0].decode() for row in rows]
+
+
+def letters_packed(ids: torch.Tensor, lengths) -> List[str]:
+    """Packed class ids (N,) + host-side lengths -> one string per RNA: one lookup on the device, one copy."""
+    lut = torch.frombuffer(bytearray(_LETTERS[1:]), dtype=torch.uint8).to(ids.device)
+    flat = lut[ids.to(torch.int64)].cpu().numpy().tobytes().decode()
+    res, start = [], 0
+    for n in (int(v) for v in lengths):
+        res.append(flat[start:start + n])
+        start += n
+    return res
 
 
 class CapturedSampler:

@@ -1,0 +1,102 @@
+"""Directory of structures -> ``pdb_id,seq`` CSV: the role of the reference's ``rnampnn/utils/predict.py:11-29`` (a Lightning ``Trainer`` that
+calls ``RNAMPNN.predict`` batch by batch) on the var-len path: ``PackedLoader`` + ``forward_packed``, so no padding is built, copied or
+computed, and the letters of a batch come from one device lookup and one copy."""
+from __future__ import annotations
+
+import glob
+import os
+from typing import List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from ..config.glob import VOCAB
+from ..model.rnampnn import letters_packed, letters_padded, sample_from_logits, score_logits
+from .data import PackedLoader, bucket_batches, fill_nan_deterministic, read_fasta
+
+
+def load_structures(path: str, max_len: int = 1 << 30):
+    """``coords/<id>.npy`` (L,7,3) [+ ``seqs/<id>.fasta``] -> list of (id, coords f32, labels int64 (L,) or None) in id order.  The fasta
+    is optional (the reference predicts on dummy sequences): a missing one, one of another length or one with letters outside AUCG gives
+    ``None``.  Missing atoms go through ``fill_nan_deterministic``, so every structure of a usable shape gets a row."""
+    items = []
+    for f in sorted(glob.glob(os.path.join(path, "coords", "*.npy"))):
+        rid = os.path.splitext(os.path.basename(f))[0]
+        c = np.load(f, allow_pickle=False).astype(np.float32)
+        if c.ndim != 3 or c.shape[1:] != (7, 3) or c.shape[0] == 0 or c.shape[0] > max_len:
+            continue
+        if np.isnan(c).any():
+            c = fill_nan_deterministic(c, rid)
+        fa, y = os.path.join(path, "seqs", rid + ".fasta"), None
+        if os.path.exists(fa):
+            seq = read_fasta(fa)
+            if len(seq) == c.shape[0] and all(ch in VOCAB for ch in seq):
+                y = np.array([VOCAB[ch] for ch in seq], dtype=np.int64)
+        items.append((rid, c, y))
+    return items
+
+
+@torch.no_grad()
+def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
+            seed: int = 0, designs_csv: Optional[str] = None) -> List[Tuple[str, str]]:
+    """Design a sequence for every structure under ``data_path`` in length-bucketed var-len batches (``forward_packed``): the tree
+    read-out on the packed embedding when one is attached, else the read-out's argmax (``rnampnn_score``'s ``pred``); write ``out_csv``
+    with one ``pdb_id,seq`` row per structure in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure
+    at ``temperature`` (``rnampnn_sample``), score them against the same logits and write ``designs_csv`` with the columns
+    ``pdb_id,sample,seq,nll_per_nt,recovery`` (``recovery`` = fraction equal to the fasta's sequence, empty without one)."""
+    model.eval()
+    device = model._device()
+    items = load_structures(data_path, max_len=int(model.hparams["padding_len"]))
+    if not items:
+        raise ValueError(f"no usable structure under {data_path} (coords/<id>.npy (L,7,3))")
+    if samples > 0 and not designs_csv:
+        designs_csv = os.path.splitext(out_csv)[0] + "_designs.csv"
+    lengths = [int(c.shape[0]) for _, c, _ in items]
+    trees = getattr(model, "xgb_readout", None)
+    seqs, designs = {}, {}
+    for bi, (coords, cu, max_len, idx) in enumerate(PackedLoader(items, bucket_batches(lengths, batch_size, max_rows, seed=0), device=device)):
+        lens = [lengths[i] for i in idx]
+        B = len(idx)
+        if trees is not None:
+            logits, emb = model.forward_packed(coords, cu, max_len, want_embedding=True)
+            names = letters_packed(trees.predict(emb), lens)
+        else:
+            logits = model.forward_packed(coords, cu, max_len)
+            names = letters_padded(score_logits(logits, cu_seqlens=cu, want=("pred",), max_len=max_len)["pred"])
+        for i, s in zip(idx, names):
+            seqs[i] = s
+        if samples > 0:
+            # rnampnn_sample takes the padded layout: scatter the packed logits once (row cu[b] + t -> (b, t)); the mask comes from cu
+            t = torch.arange(max_len, device=device)
+            mask = (t[None, :] < (cu[1:] - cu[:-1])[:, None]).to(torch.float32)
+            rows_of = (cu[:-1].to(torch.int64)[:, None] + t[None, :]).clamp_(max=int(logits.shape[0]) - 1)
+            padded = torch.where(mask[..., None] != 0, logits[rows_of], torch.zeros((), dtype=torch.float32, device=device))
+            draws = sample_from_logits(padded, mask, temperature, samples, seed + bi)
+            have = [items[i][2] is not None for i in idx]
+            lab = None
+            if any(have):
+                lab = torch.zeros(B, max_len, dtype=torch.int32)
+                for r, i in enumerate(idx):
+                    if have[r]:
+                        lab[r, :lens[r]] = torch.from_numpy(items[i][2]).to(torch.int32)
+            sc = score_logits(logits, cu_seqlens=cu, labels=lab, seqs=draws, want=("seq_nll",) + (("seq_match",) if lab is not None else ()))
+            nll = sc["seq_nll"].cpu().tolist()
+            match = sc["seq_match"].cpu().tolist() if lab is not None else None
+            for s in range(samples):
+                for r, (i, text) in enumerate(zip(idx, letters_padded(draws[s]))):
+                    rec = f"{match[s][r] / lens[r]:.6f}" if match is not None and have[r] else ""
+                    designs.setdefault(i, []).append((s, text, nll[s][r] / lens[r], rec))
+    rows = [(items[i][0], seqs[i]) for i in range(len(items))]
+    os.makedirs(os.path.dirname(os.path.abspath(out_csv)), exist_ok=True)
+    with open(out_csv, "w") as f:
+        f.write("pdb_id,seq\n")
+        for rid, s in rows:
+            f.write(f"{rid},{s}\n")
+    if samples > 0:
+        os.makedirs(os.path.dirname(os.path.abspath(designs_csv)), exist_ok=True)
+        with open(designs_csv, "w") as f:
+            f.write("pdb_id,sample,seq,nll_per_nt,recovery\n")
+            for i in range(len(items)):
+                for s, text, nll_nt, rec in designs[i]:
+                    f.write(f"{items[i][0]},{s},{text},{nll_nt:.6f},{rec}\n")
+    return rows

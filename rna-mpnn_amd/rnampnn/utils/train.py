@@ -15,6 +15,7 @@ import time
 from typing import Dict, List, Optional, Sequence
 
 import torch
+import torch.distributed as dist
 
 from . import shard
 from .augment import EpochNoise
@@ -76,6 +77,7 @@ class Trainer:
         if self.world > 1 and overlap_allreduce:
             model.enable_allreduce_overlap(True)
         self._loss = torch.zeros((), dtype=torch.float32, device=self.device)
+        self.last_validation = None
 
     def step(self, labels, coords, mask, T_norm: int = 0, seed: Optional[int] = None, timing=None):
         """forward + backward (one native call), gradient exchange, optimiser step; returns the device loss (no sync)."""
@@ -129,3 +131,83 @@ class Trainer:
         else:
             c = v = torch.zeros(0, dtype=torch.int32, device=self.device)
         return shard.reduce_recovery(c, v)
+
+    @torch.no_grad()
+    def validate_metrics(self, items, lengths: Sequence[int], batch_size: int, max_rows: int, use_trees: bool = False) -> Dict[str, float]:
+        """-> dict(val_loss, weighted_val_recovery_rate, val_recovery_rate) over all ranks (``validation_metrics``): what the reference's
+        ``LossMonitor`` logs.  Every rank scores a strided share of the ``bucket_batches(seed=0)`` plan - the batches ``validate`` takes -
+        through ``RNAMPNN.score_batch`` (one forward + one ``rnampnn_score`` per batch, per-RNA device tensors); there is no host
+        synchronisation between the first and the last batch, the per-RNA tensors are reduced once at the end.  ``last_validation`` keeps
+        this rank's per-RNA tensors in batch order.  ``use_trees``: score the tree read-out instead (val_loss is then NaN)."""
+        self.model.eval()
+        batches = bucket_batches(lengths, batch_size, max_rows, seed=0)[self.rank::self.world]
+        cs, vs, ls, ns = [], [], [], []
+        for y, c, m, _, _ in PaddedLoader(items, batches, device=self.device):
+            correct, valid, loss, nll = self.model.score_batch(y, c, m, use_trees=use_trees)
+            cs.append(correct); vs.append(valid)
+            if loss is not None:
+                ls.append(loss); ns.append(nll)
+        cat = lambda parts, dt: torch.cat(parts) if parts else torch.zeros(0, dtype=dt, device=self.device)
+        c, v, l, n = cat(cs, torch.int32), cat(vs, torch.int32), cat(ls, torch.float32), cat(ns, torch.float32)
+        self.last_validation = dict(correct=c, valid=v, loss=l, nll=n)
+        out = validation_metrics(c, v, l)
+        if use_trees:
+            out["val_loss"] = float("nan")
+        return out
+
+
+def validation_metrics(correct: torch.Tensor, valid: torch.Tensor, loss: torch.Tensor) -> Dict[str, float]:
+    """``LossMonitor.on_validation_epoch_end`` (utils/train.py:15-26 of the reference) from per-RNA (correct, valid, summed loss), in
+    float64 and summed over the ranks: val_loss = sum(loss) / sum(valid) (the reference sums batch mean x batch tokens),
+    weighted_val_recovery_rate = sum(correct) / sum(valid), val_recovery_rate = mean over the RNAs of correct / valid."""
+    micro, macro = shard.reduce_recovery(correct, valid)
+    sums = torch.stack([loss.to(torch.float64).sum(), valid.to(torch.float64).sum()])
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM)
+    return dict(val_loss=float(sums[0] / sums[1].clamp(min=1)), weighted_val_recovery_rate=micro, val_recovery_rate=macro)
+
+
+# ---------------------------------------------------------------------------------------------------------------- checkpoints
+def _plain(obj):
+    """Tensors -> detached CPU clones, containers rebuilt from plain dict / list / tuple: what ``torch.load(weights_only=True)`` reads."""
+    if isinstance(obj, torch.Tensor):
+        return obj.detach().cpu().clone()
+    if isinstance(obj, dict):
+        return {k: _plain(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_plain(v) for v in obj) if type(obj) in (list, tuple) else [_plain(v) for v in obj]
+    if obj is None or isinstance(obj, (bool, int, float, str)):
+        return obj
+    raise TypeError(f"a checkpoint holds tensors and plain types only, got {type(obj).__name__}")
+
+
+def save_checkpoint(path: str, model, optimizer=None, scheduler=None, **extra) -> None:
+    """``Final.pt`` / ``last.pt``: model="rnampnn", state_dict (CPU tensors), constructor kwargs, name / version, optionally the
+    optimiser's (``FlatAdam`` or ``torch.optim.Adam``) and the scheduler's ``state_dict`` and plain-typed ``extra`` (the epoch, its
+    ``val_recovery_rate``).  Tensors and plain types only, so ``torch.load(weights_only=True)`` reads it back."""
+    ck = dict(model="rnampnn", state_dict=_plain(dict(model.state_dict())), init_kwargs=_plain(dict(model.init_kwargs)),
+              name=str(model.name), version=int(model.version))
+    if optimizer is not None:
+        ck["optimizer"] = _plain(optimizer.state_dict())
+    if scheduler is not None:
+        ck["scheduler"] = _plain(scheduler.state_dict())
+    clash = set(extra) & set(ck)
+    if clash:
+        raise ValueError(f"extra keys {sorted(clash)} are the checkpoint's own")
+    ck.update(_plain(extra))
+    torch.save(ck, path)
+
+
+def load_checkpoint(path: str, device=None):
+    """-> (RNAMPNN rebuilt from a ``save_checkpoint`` file, the file's dict; ``optimizer`` / ``scheduler`` entries go to the
+    ``load_state_dict`` of objects the caller builds on the model).  ``weights_only=True``: pickled objects are never loaded."""
+    from ..model.rnampnn import RNAMPNN
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(ck, dict) or ck.get("model") != "rnampnn":
+        raise ValueError(f"{path} is not an RNAMPNN checkpoint (model = {ck.get('model') if isinstance(ck, dict) else type(ck).__name__!r})")
+    model = RNAMPNN(**ck["init_kwargs"])
+    model.load_state_dict(ck["state_dict"])
+    model.name, model.version = ck["name"], ck["version"]
+    if device is not None:
+        model = model.to(device)
+    return model, ck

@@ -7,13 +7,17 @@ runs are one process per GPU with ONE flat RCCL all-reduce per step (``RNAMPNN.a
 
     python rna-mpnn_amd/train.py --data /path/to/data --epochs 2                    # coords/*.npy + seqs/*.fasta
     python rna-mpnn_amd/train.py --synthetic 512 --epochs 3                         # seeded synthetic RNAs
+    python rna-mpnn_amd/train.py --data /path/to/data --epochs 60 --fit-xgb --out runs/rnampnn           # Final.pt (best epoch), last.pt, XGB.json
+    python rna-mpnn_amd/train.py --data /path/to/data --epochs 60 --out runs/rnampnn --resume runs/rnampnn/last.pt
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 rna-mpnn_amd/train.py --synthetic 4096
     python rna-mpnn_amd/train.py --model rdesign --data /path/to/data --epochs 230 --fit-xgb --out runs/rdesign   # the sibling model
 
 Batches are length-bucketed (``rnampnn.utils.train.plan_epoch``): the reference's collate pads every RNA of a batch
 to the longest one, so mixing a 2,436-nt ribosomal RNA with 20-nt hairpins would spend > 99 % of the rows on padding.
 The loop itself is ``rnampnn.utils.train.Trainer``: inputs through ``PaddedLoader`` (pinned memory, copies on a side stream),
-loss accumulated on the device, no host synchronisation inside an epoch.
+loss accumulated on the device, no host synchronisation inside an epoch or a validation pass (``Trainer.validate_metrics``: per-RNA
+scores from ``rnampnn_score``).  ``--out DIR`` keeps ``Final.pt`` of the epoch with the best ``val_recovery_rate`` (the reference's
+``ModelCheckpoint``, ``rnampnn/utils/train.py:98-104``) and ``last.pt`` with optimiser and scheduler state, which ``--resume`` continues from.
 
 ``--model rdesign`` trains the reference's sibling model instead (the reference's own ``train.py:62-80``: ``rdesign.model.rdesign.RNAModel``,
 Adam(lr) + StepLR(40, 0.8), checkpoint of the epoch with the best ``val_recovery_rate``, XGBoost head fitted at the end) through
@@ -37,7 +41,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 from rnampnn.model.rnampnn import RNAMPNN  # noqa: E402
 from rnampnn.utils import synth  # noqa: E402
 from rnampnn.utils.data import PaddedLoader, bucket_batches, load_rna_dir  # noqa: E402
-from rnampnn.utils.train import Trainer  # noqa: E402
+from rnampnn.utils.train import Trainer, load_checkpoint, save_checkpoint  # noqa: E402
 
 
 def parse(argv=None):
@@ -70,8 +74,10 @@ def parse(argv=None):
                          "(the reference's XGBTrainer.on_fit_end, utils/train.py:50-75) and print train / validation score")
     ap.add_argument("--xgb-out", default=None, help="with --fit-xgb: write the fitted model as XGBoost-schema JSON")
     ap.add_argument("--out", default=None,
-                    help="--model rdesign: directory for Final.pt (weights of the epoch with the best val_recovery_rate + constructor "
-                         "arguments) and, with --fit-xgb, XGB.json")
+                    help="directory for Final.pt (weights of the epoch with the best val_recovery_rate + constructor arguments) and, with "
+                         "--fit-xgb, XGB.json; --model rnampnn also writes last.pt (weights, optimiser and scheduler state) after every epoch")
+    ap.add_argument("--resume", default=None, metavar="FILE",
+                    help="--model rnampnn: continue from a last.pt - weights, optimiser, scheduler and epoch counter (--epochs is the total)")
     ap.add_argument("--noise-augmentation", type=int, default=0, metavar="N",
                     help="N noisy copies of training RNAs drawn with replacement, coordinates + N(0, --noise-std^2) added on the device "
                          "(the reference's RNADataset.noise_augmentation, utils/data.py:278-295); training split only")
@@ -127,8 +133,13 @@ def _split(items, args):
 
 
 def run(args, log=print):
-    """-> dict(epochs=[dict(train_loss, val_micro, val_macro, nt_per_s, steps, seconds)], n_train, n_val)."""
+    """-> dict(epochs=[dict(train_loss, val_loss, weighted_val_recovery_rate, val_recovery_rate, val_micro, val_macro, nt_per_s, steps,
+    seconds)], n_train, n_val, best_epoch, model[, xgb]).  ``--out DIR``: ``Final.pt`` whenever ``val_recovery_rate`` improves (no
+    validation split: every epoch, so the last one stays) and ``last.pt`` with optimiser / scheduler state after every epoch, written
+    by rank 0 ahead of a barrier; ``--resume FILE`` continues from such a ``last.pt``."""
     if args.model == "rdesign":
+        if args.resume:
+            raise ValueError("--resume belongs to --model rnampnn (the rdesign trainer writes no last.pt)")
         return run_rdesign(args, log)
     if args.augment_eps:
         raise ValueError("--augment-eps belongs to --model rdesign (the reference's RNAMPNN has no such argument)")
@@ -141,33 +152,72 @@ def run(args, log=print):
     hp = dict(num_res_neighbours=args.neighbours or 30, num_res_mpnn_layers=args.layers or 10, padding_len=max(args.max_len, 1))
     if args.dropout is not None:
         hp["dropout"] = args.dropout
-    model = RNAMPNN(**hp).to(dev)
+    resume = None
+    if args.resume:                                 # every rank reads the same file: identical weights without a broadcast
+        model, resume = load_checkpoint(args.resume, device=dev)
+    else:
+        model = RNAMPNN(**hp).to(dev)
     model.train_precision = args.train_precision
-    if world > 1:                                   # identical initial weights on every rank
+    if world > 1 and resume is None:                # identical initial weights on every rank
         for p in model.parameters():
             dist.broadcast(p.data, 0)
         model._weights_touched()
     (opt,), (sched,) = model.configure_optimizers(fused=not args.torch_adam)
+    if resume is not None:
+        if "optimizer" not in resume or "epoch" not in resume:
+            raise ValueError(f"{args.resume} carries no optimiser state / epoch counter: --resume takes the last.pt that --out writes")
+        opt.load_state_dict(resume["optimizer"])
+        if "scheduler" in resume:
+            sched.load_state_dict(resume["scheduler"])
     trainer = Trainer(model, opt, sched, world=world, rank=rank, global_t_norm=args.global_t_norm, seed=args.seed)
     train_lens = [c.shape[0] for c, _ in train]
     val_lens = [c.shape[0] for c, _ in val]
     epoch_items, epoch_lens = _augment(train, train_lens, args)         # the tree read-out below is fitted on the plain training RNAs
-    out = dict(epochs=[], n_train=len(epoch_items), n_val=len(val))
-    for epoch in range(args.epochs):
+    out = dict(epochs=[], n_train=len(epoch_items), n_val=len(val), best_epoch=None)
+    final = os.path.join(args.out, "Final.pt") if args.out else None
+    last = os.path.join(args.out, "last.pt") if args.out else None
+    if args.out and rank == 0:
+        os.makedirs(args.out, exist_ok=True)
+    best, nan = float("-inf"), float("nan")
+    first = 0
+    if resume is not None:
+        first = int(resume["epoch"]) + 1
+        if resume.get("best_epoch", -1) >= 0:
+            best, out["best_epoch"] = float(resume["best_val_recovery_rate"]), int(resume["best_epoch"])
+    for epoch in range(first, args.epochs):
         rec = trainer.run_epoch(epoch_items, epoch_lens, epoch, args.batch_size, args.max_nt)
         if world > 1:       # whole-job rate: all nucleotides / slowest rank
             t = torch.tensor([rec["seconds"], float(rec["nt"])], dtype=torch.float64, device=dev)
             tmax = t.clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dist.all_reduce(t, op=dist.ReduceOp.SUM)
             rec["nt_per_s"] = float(t[1] / tmax[0])
-        micro, macro = trainer.validate(val, val_lens, args.batch_size, args.max_nt) if val else (float("nan"), float("nan"))
+        rec.update(trainer.validate_metrics(val, val_lens, args.batch_size, args.max_nt) if val
+                   else dict(val_loss=nan, weighted_val_recovery_rate=nan, val_recovery_rate=nan))
+        micro, macro = rec["weighted_val_recovery_rate"], rec["val_recovery_rate"]      # (what Trainer.validate returns, from the same counts)
         rec.update(val_micro=micro, val_macro=macro)
         out["epochs"].append(rec)
+        if not val or out["best_epoch"] is None or macro > best:        # ModelCheckpoint(monitor='val_recovery_rate', mode='max'); no split: the last epoch
+            best, out["best_epoch"] = macro, epoch
+            if final and rank == 0:
+                save_checkpoint(final, model, epoch=epoch, val_recovery_rate=float(macro), val_loss=float(rec["val_loss"]))
+        if last and rank == 0:
+            save_checkpoint(last, model, opt, sched, epoch=epoch, val_recovery_rate=float(macro), best_epoch=int(out["best_epoch"]),
+                            best_val_recovery_rate=float(best))
+        if args.out and world > 1:
+            dist.barrier()
         if rank == 0:
             log(f"epoch {epoch}: train_loss {rec['train_loss']:.4f}  val_recovery micro {micro:.4f} macro {macro:.4f}  "
                 f"{rec['nt_per_s']:.0f} nt/s end to end ({rec['steps']} steps, {rec['seconds']:.2f} s, {world} rank(s))")
+    if final and out["epochs"]:
+        if args.fit_xgb and out["best_epoch"] != args.epochs - 1:      # XGBTrainer.on_fit_end reloads the Final checkpoint before the fit
+            model.load_state_dict(load_checkpoint(final)[1]["state_dict"])
+        if rank == 0:
+            log(f"checkpoint of epoch {out['best_epoch']} written to {final}")
     if args.fit_xgb and rank == 0:
         out["xgb"] = fit_xgb(model, train, train_lens, val, val_lens, args, dev, log)
+        if args.out:
+            model.xgb_readout.save_json(os.path.join(args.out, "XGB.json"))
+            log(f"tree read-out written to {os.path.join(args.out, 'XGB.json')}")
     out["model"] = model
     return out
 
