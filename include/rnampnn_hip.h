@@ -194,6 +194,41 @@ int rnampnn_sample_dev_seed(const float* logits, const float* mask, int32_t B, i
 int rnampnn_score(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, const int32_t* labels,
                   const int8_t* seqs, int32_t S, int32_t B, int32_t T, int32_t* valid, int8_t* pred, int32_t* correct,
                   float* label_nll, float* label_loss, float* seq_nll, int32_t* seq_match, void* stream);
+/* Constrained sequence design in ONE launch (csrc/design.hip): S sequences per RNA drawn from f32 logits under three kinds of constraint,
+ * each draw scored.  The logits come in either layout of rnampnn_score (exactly one of `mask` and `cu_seqlens`; lengths and row offsets are
+ * found and clamped as there).  `allowed`, `partner`, a per-position `bias` and `seqs` are PADDED (B,T) in both layouts.  Class ids: AUCG = 0..3.
+ *   allowed (B,T) u8, nullable   bit c set = class c may be drawn (0xF free, one bit = a fixed nucleotide, IUPAC codes / omitted letters =
+ *                                other masks); bits above 3 are ignored
+ *   partner (B,T) i32, nullable  partner[b,t] = j pairs t with j; t counts as paired only if 0 <= j < n_b, j != t and partner[b,j] == t,
+ *                                anything else (-1 by convention) is unpaired - a malformed table never causes an out-of-range access
+ *   wobble                       != 0 admits GU and UG next to AU, UA, GC and CG
+ *   bias, nullable               bias_per_position = 0: four device floats, one per class; 1: (B,T,4) padded, 16-byte aligned
+ *   seed_dev, nullable           when present, *seed_dev (device memory, read at kernel time) replaces `seed`, as in rnampnn_sample_dev_seed
+ * Outputs, each nullable:
+ *   seqs (S,B,T) i8        the draws; -1 at t >= n_b; every valid position holds an id in 0..3 whatever the inputs hold (NaN included)
+ *   seq_nll (S,B) f32      the model's own NLL of the draw (temperature 1, no bias, no constraints): byte for byte rnampnn_score's seq_nll
+ *   infeasible (B) i32     valid positions whose constraint could not be honoured (below); the same for every sample
+ * The draw.  z_t(c) = (logit_t(c) + bias_t(c)) / temperature for the classes `allowed` admits.  The uniform of (sample s, RNA b, position t),
+ * with mix64 the splitmix64 finaliser and all arithmetic modulo 2^64:
+ *   h = mix64(seed + 0x9E3779B97F4A7C15 * (s+1));  h = mix64(h ^ 0xD6E8FEB86659FD93 * (b+1));  h = mix64(h ^ 0xBF58476D1CE4E5B9 * (t+1));
+ *   u24 = h >> 40
+ * so a draw is a pure function of (seed, s, b, t) and the logits: it does not depend on B, T, S or the layout.
+ *   Unpaired position: w(c) = exp(z(c) - max over the admitted classes) in class order 0..3; u = u24 * 2^-24 * (the running sum's final
+ *     value); the first class whose running sum exceeds u is chosen; if none does (rounding, NaN) the last admitted class.
+ *   Pair (i < j): cells (a,b) in a-major order, weight exp(z_i(a) + z_j(b) - m) over the compatible cells both masks admit, m the maximum
+ *     over exactly those cells (the log domain: a feasible pair cannot underflow to a zero total at a low temperature); the uniform is
+ *     that of (s, b, i); the same selection rule and fallback; i receives a, j receives b.
+ *   Infeasible: a position whose mask admits no class is drawn as free and counts 1.  A pair without a compatible cell that both masks admit
+ *     (two incompatible fixed nucleotides, say) makes both ends draw as unpaired positions, each with its own mask and its own (s,b,t)
+ *     uniform, and counts 2.
+ * No workspace, no runtime fill / copy node, no atomics, no host synchronisation: two calls give identical bytes and the call can sit inside
+ * a captured graph.  RNAMPNN_ERR_BAD_ARG, before anything is launched: null logits; B, T or S <= 0; S + 1 > 65535; neither or both of mask
+ * and cu_seqlens; a temperature that is not positive and finite; logits (or a per-position bias) not 16-byte aligned; n_rows < 0 with
+ * cu_seqlens.  With every output null the call returns RNAMPNN_OK without a launch. */
+int rnampnn_design(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
+                   float temperature, int32_t S, uint64_t seed, const uint64_t* seed_dev, const uint8_t* allowed,
+                   const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position, int8_t* seqs,
+                   float* seq_nll, int32_t* infeasible, void* stream);
 
 /* -- training ---------------------------------------------------------------------------- */
 /* The training surface of RNAMPNN (rnampnn.py:187-207 + Lightning's loss.backward()):

@@ -17,6 +17,12 @@ __attribute__((visibility("hidden"))) int fail(int code, const char* fmt, ...);
         if (_e != hipSuccess) return fail(RNAMPNN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
 
+// splitmix64 finaliser: the counter hash behind the draws of k_sample (kernels_f32.hip) and k_design (design.hip)
+__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
+    return x;
+}
+
 struct RawT {                 // one state_dict entry in the reference's layout
     std::string key;
     int64_t numel;

@@ -4,7 +4,7 @@
 // The bf16/MFMA kernels in kernels_bf16.hip replace the GEMM-shaped ones on the fast path;
 // the graph / geometry / normalisation / decode kernels here serve both precisions.
 // Reference lines restated by each kernel are cited at its head.
-#include "rnampnn_internal.h"
+#include "api_internal.h"          // mix64
 #include "bf16_core.h"             // kSEPS, gelu_erf
 #include <cstdlib>
 
@@ -1268,10 +1268,6 @@ void launch_argmax_recovery(const float* logits, const float* mask, const int32_
 }
 
 // sample(): independent categorical draw per position from softmax(logits / temperature).
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
-    return x;
-}
 __global__ void k_sample(const float* __restrict__ logits, const float* __restrict__ mask, int B, int T, float inv_temp,
                          int n_samples, unsigned long long seed, const unsigned long long* __restrict__ seed_dev,
                          int8_t* __restrict__ out) {

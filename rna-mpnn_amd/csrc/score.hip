@@ -7,23 +7,9 @@
 // layouts give the same bytes for the same rows and two calls give identical bytes.  ONE launch: the workgroup finds its own length (the
 // sum of its mask row, or the difference of two cu entries), so there is no workspace, no runtime fill / copy node, no atomics and no host
 // synchronisation.  About 20 bytes per nucleotide and pass: the call is bounded by its launch, not by bandwidth.
-#include "api_internal.h"
+#include "score_dev.h"
 
 namespace {
-constexpr int SC_THREADS = 256;
-constexpr int SC_WAVES = SC_THREADS / 64;
-
-__device__ __forceinline__ int sc_wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float sc_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 struct ScoreArgs {
     const float4* logits;        // (B*T) or (n_rows) rows of 4
     const float* mask;           // (B,T) prefix mask, or null
@@ -42,31 +28,6 @@ struct ScoreArgs {
     int32_t* seq_match;          // (S,B)
 };
 
-// The length and the first logits row of RNA b.  Both come from caller data (a mask that need not be the collate's prefix mask, a cu that
-// need not be a prefix sum): they are clamped to the tensors' extents, so a malformed input gives meaningless numbers but no out-of-bounds
-// access.  The mask row is summed as k_lengths sums it (the forward's own length of the RNA).
-__device__ __forceinline__ void sc_extent(const ScoreArgs& a, int b, int tid, float* s_tmp, int& n, long long& row0) {
-    if (a.cu) {
-        const long long lo = min(max((long long)a.cu[b], 0ll), a.n_rows);
-        const long long len = min(max((long long)a.cu[b + 1] - (long long)a.cu[b], 0ll), (long long)a.T);
-        n = (int)min(len, a.n_rows - lo);
-        row0 = lo;
-        return;
-    }
-    float s = 0.f;
-    for (int t = tid; t < a.T; t += SC_THREADS) s += a.mask[(size_t)b * a.T + t];
-    s = sc_wave_sum(s);
-    if ((tid & 63) == 0) s_tmp[tid >> 6] = s;
-    __syncthreads();
-    float tot = 0.f;
-#pragma unroll
-    for (int w = 0; w < SC_WAVES; ++w) tot += s_tmp[w];
-    __syncthreads();                                           // s_tmp is reused by the reductions below
-    n = tot >= 0.f ? (int)fminf(tot + 0.5f, (float)a.T) : 0;    // (a NaN sum compares false: 0)
-    n = min(max(n, 0), a.T);
-    row0 = (long long)b * a.T;
-}
-
 __global__ void __launch_bounds__(SC_THREADS) k_score(ScoreArgs a) {
     __shared__ int s_i[SC_WAVES];
     __shared__ float s_f[2][SC_WAVES];
@@ -74,7 +35,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_score(ScoreArgs a) {
     const int pass = (int)blockIdx.y + (a.pass0 ? 0 : 1);
     int n;
     long long row0;
-    sc_extent(a, b, tid, s_f[0], n, row0);
+    sc_extent(a.mask, a.cu, a.n_rows, a.T, b, tid, s_f[0], n, row0);
     const size_t lab0 = (size_t)b * a.T;
     int cnt = 0;
     float nll = 0.f, loss = 0.f;
@@ -108,26 +69,14 @@ __global__ void __launch_bounds__(SC_THREADS) k_score(ScoreArgs a) {
         const int8_t* seq = a.seqs + ((size_t)(pass - 1) * a.B + b) * a.T;
         for (int t = tid; t < n; t += SC_THREADS) {
             const int q = seq[t];
-            if (a.seq_nll) {
-                const float4 x = a.logits[row0 + t];
-                const float m = fmaxf(fmaxf(x.x, x.y), fmaxf(x.z, x.w));
-                const float se = (expf(x.x - m) + expf(x.y - m)) + (expf(x.z - m) + expf(x.w - m));
-                const float xl = q == 0 ? x.x : q == 1 ? x.y : q == 2 ? x.z : x.w;
-                nll += (m - xl) + logf(se);
-            }
+            if (a.seq_nll) nll += sc_row_nll(a.logits[row0 + t], q);
             if (a.seq_match) cnt += q == a.labels[lab0 + t] ? 1 : 0;
         }
     }
-    cnt = sc_wave_sum(cnt);
-    nll = sc_wave_sum(nll);
-    loss = sc_wave_sum(loss);
-    if ((tid & 63) == 0) { s_i[tid >> 6] = cnt; s_f[0][tid >> 6] = nll; s_f[1][tid >> 6] = loss; }
-    __syncthreads();
+    sc_block_sums(cnt, nll, loss, tid, s_i, s_f);
     if (tid != 0) return;
-    int ct = 0;
-    float nt = 0.f, lt = 0.f;
-#pragma unroll
-    for (int w = 0; w < SC_WAVES; ++w) { ct += s_i[w]; nt += s_f[0][w]; lt += s_f[1][w]; }
+    const int ct = cnt;
+    const float nt = nll, lt = loss;
     if (pass == 0) {
         if (a.valid) a.valid[b] = n;
         if (a.correct) a.correct[b] = ct;

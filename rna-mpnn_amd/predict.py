@@ -8,8 +8,16 @@
 loaded).  Its ``model`` key chooses the family: ``"rnampnn"`` = ``RNAMPNN``; a file without the key is an ``rdesign`` checkpoint (the files
 ``train.py --model rdesign`` has always written).  ``--xgb`` is the tree read-out in XGBoost's JSON schema - without it the read-out's argmax
 decides, as in the reference with an unfitted XGBoost head.  ``--data`` holds ``coords/<id>.npy`` (L,7,3) and ``seqs/<id>.fasta`` (optional for
-``RNAMPNN``); the CSV has one ``pdb_id,seq`` row per structure in id order.  ``--samples N`` (``RNAMPNN``) also draws N sequences per
-structure at ``--temperature`` and writes them with their per-nucleotide NLL and recovery to ``--designs-out``."""
+``RNAMPNN``); the CSV has one ``pdb_id,seq`` row per structure in id order.  ``--samples N`` also draws N sequences per structure at
+``--temperature`` and writes them with their per-nucleotide NLL and recovery to ``--designs-out``.
+
+    python rna-mpnn_amd/predict.py --ckpt Final.pt --data DIR --samples 8 --constraints cons.csv --bias G=-0.5 --omit "" --no-wobble
+
+Constrained design (``rnampnn_design``, one launch on the packed logits): ``--constraints`` is a CSV ``pdb_id,fixed,structure`` - ``fixed`` a
+pattern of AUCG / IUPAC codes with ``.`` or ``-`` for free positions, ``structure`` a dot-bracket string whose pairs are drawn together as
+AU UA GC CG (GU UG unless ``--no-wobble``); either may be empty and ids not listed are unconstrained.  ``--bias A=..,U=..,C=..,G=..`` is added
+to the logits, ``--omit LETTERS`` never draws these letters.  With any of the four the designs CSV gains the column ``infeasible`` (positions
+whose constraint could not be honoured)."""
 from __future__ import annotations
 
 import argparse
@@ -30,11 +38,25 @@ def parse(argv=None):
     ap.add_argument("--out", default="submit.csv")
     ap.add_argument("--batch-size", type=int, default=32)
     ap.add_argument("--device", default="cuda:0")
-    ap.add_argument("--samples", type=int, default=0, help="rnampnn: sequences drawn per structure (0 = none)")
-    ap.add_argument("--temperature", type=float, default=0.1, help="rnampnn: sampling temperature of --samples")
-    ap.add_argument("--seed", type=int, default=0, help="rnampnn: seed of --samples")
-    ap.add_argument("--designs-out", default=None, help="rnampnn: CSV of the sampled designs (default: <out>_designs.csv)")
+    ap.add_argument("--samples", type=int, default=0, help="sequences drawn per structure (0 = none)")
+    ap.add_argument("--temperature", type=float, default=0.1, help="sampling temperature of --samples")
+    ap.add_argument("--seed", type=int, default=0, help="seed of --samples")
+    ap.add_argument("--designs-out", default=None, help="CSV of the sampled designs (default: <out>_designs.csv)")
+    ap.add_argument("--constraints", default=None, help="CSV pdb_id,fixed,structure: sequence pattern and dot-bracket structure per id")
+    ap.add_argument("--bias", default=None, help="A=..,U=..,C=..,G=..: added to the logits of --samples")
+    ap.add_argument("--omit", default="", help="letters --samples never draws")
+    ap.add_argument("--no-wobble", action="store_true", help="base pairs of --constraints exclude GU / UG")
     return ap.parse_args(argv)
+
+
+def design_options(args) -> dict:
+    """The constrained-design keywords of ``predict`` from the flags; empty when none of them is given."""
+    if not (args.constraints or args.bias or args.omit or args.no_wobble):
+        return {}
+    from rnampnn.utils.constraints import omit_mask, parse_bias, read_constraints_csv
+    omit_mask(args.omit)                                           # a letter outside AUCG fails here, before the model is loaded
+    return dict(constraints=read_constraints_csv(args.constraints) if args.constraints else None,
+                bias=parse_bias(args.bias) if args.bias else None, omit=args.omit, wobble=not args.no_wobble)
 
 
 def checkpoint_family(path: str) -> str:
@@ -51,13 +73,10 @@ def run(args, log=print):
     if family == "rnampnn":
         from rnampnn.utils.predict import predict
         from rnampnn.utils.train import load_checkpoint
-        extra = dict(samples=args.samples, temperature=args.temperature, seed=args.seed, designs_csv=args.designs_out)
     else:
         from rdesign.utils.predict import predict
         from rdesign.utils.train import load_checkpoint
-        if args.samples:
-            raise ValueError("--samples belongs to RNAMPNN checkpoints (the rdesign model has no sampler)")
-        extra = {}
+    extra = dict(samples=args.samples, temperature=args.temperature, seed=args.seed, designs_csv=args.designs_out, **design_options(args))
     model, ck = load_checkpoint(args.ckpt, device=torch.device(args.device))
     if args.xgb:
         model.load_xgb_readout(args.xgb)

@@ -414,6 +414,38 @@ class RNAModel(nn.Module):
         logits = self._run(X, mask, want=("logits",), n_valid=n)["logits"]
         return self._score_native(logits, None, mask, S)[:3]
 
+    # ------------------------------------------------------------------ constrained design on the packed logits (rnampnn_design / rnampnn_score)
+    def _packed_logits(self, X, mask, lengths):
+        """-> (packed logits (n, 4), cu_seqlens (B+1,) int32 built on the device from the mask's row sums, T): nothing here waits for the
+        device when the loader's host ``lengths`` are passed (``score_batch``)."""
+        logits = self._run(X, mask, want=("logits",), n_valid=self._n_valid(lengths))["logits"]
+        md = _prep(mask, logits.device)
+        cu = torch.zeros(md.shape[0] + 1, dtype=torch.int32, device=logits.device)
+        cu[1:] = torch.cumsum(md.sum(dim=1), 0).to(torch.int32)
+        return logits, cu, int(md.shape[1])
+
+    @torch.no_grad()
+    def design(self, X, mask, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None, lengths=None):
+        """``n_samples`` sequences per RNA drawn from this model's read-out at ``temperature`` and scored, in one ``rnampnn_design`` launch
+        on the packed logits -> (seqs int8 (n_samples,B,T), -1 on padding; seq_nll (n_samples,B) f32, the model's own temperature-1 NLL of
+        each draw; infeasible (B,) int32).  ``constraints``: a ``rnampnn.utils.constraints.DesignConstraints`` (fixed nucleotides, base
+        pairs, bias) or None for free draws.  ``lengths`` as in ``score_batch``."""
+        from rnampnn.model.rnampnn import design_from_logits
+        logits, cu, T = self._packed_logits(X, mask, lengths)
+        return design_from_logits(logits, cu_seqlens=cu, max_len=T, n_samples=n_samples, temperature=temperature, seed=seed,
+                                  constraints=constraints)
+
+    @torch.no_grad()
+    def score_sequences(self, X, mask, seqs, labels=None, lengths=None):
+        """Likelihood of given sequences under this model: ``seqs`` (S,B,T) or (B,T) class ids (``design``'s int8 output; entries on
+        padding are never read) -> (seq_nll (S,B) f32, seq_match (S,B) int32 = #(seq == label) or None without ``labels`` (B,T) class
+        ids, valid (B,) int32).  One forward + one ``rnampnn_score`` on the packed logits."""
+        from rnampnn.model.rnampnn import score_logits
+        logits, cu, T = self._packed_logits(X, mask, lengths)
+        want = ("seq_nll", "valid") + (("seq_match",) if labels is not None else ())
+        out = score_logits(logits, cu_seqlens=cu, labels=labels, seqs=seqs if seqs.dim() == 3 else seqs.unsqueeze(0), want=want, max_len=T)
+        return out["seq_nll"], out.get("seq_match"), out["valid"]
+
     # ------------------------------------------------------------------ tree head (rdesign/utils/train.py:51-89, rdesign.py:151-153)
     def load_xgb_readout(self, model_json) -> None:
         """Attach a fitted multi:softmax model in XGBoost's JSON schema (path or dict) over this model's 128 ``h_V`` features.  The

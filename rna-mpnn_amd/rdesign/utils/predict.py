@@ -2,26 +2,47 @@
 from __future__ import annotations
 
 import os
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
+from rnampnn.model.rnampnn import design_from_logits, letters_padded, score_logits
+from rnampnn.utils.constraints import batch_constraints
 from rnampnn.utils.data import bucket_batches
 
 from .data import load_rna_dir, padded_loader
 
 
-def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768) -> List[Tuple[str, str]]:
+def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
+            seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
+            wobble: bool = True) -> List[Tuple[str, str]]:
     """Read ``data_path`` (``coords/<id>.npy`` + ``seqs/<id>.fasta``), design a sequence for every structure in length-bucketed batches
     (``RNAModel.predict_sequences``: the tree read-out when one is attached, else the read-out's argmax) and write ``out_csv`` with one
-    ``pdb_id,seq`` row per input in id order.  -> the rows."""
+    ``pdb_id,seq`` row per input in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure at
+    ``temperature`` from the packed read-out logits with ``rnampnn_design`` - under ``constraints`` ({pdb_id: (pattern, structure)}; ids
+    not in it are unconstrained), ``bias`` (4 per-class floats), ``omit`` (letters never drawn) and ``wobble`` - and write ``designs_csv``
+    with the columns ``pdb_id,sample,seq,nll_per_nt,recovery,infeasible``."""
     model.eval()
     items = load_rna_dir(data_path)
     if not items:
         raise ValueError(f"no usable structure under {data_path} (coords/<id>.npy (L,7,3) + seqs/<id>.fasta)")
+    if samples > 0 and not designs_csv:
+        designs_csv = os.path.splitext(out_csv)[0] + "_designs.csv"
     batches = bucket_batches([c.shape[0] for _, c, _ in items], batch_size, max_rows, seed=0)
-    seqs = {}
-    for _, X, mask, lengths, idx in padded_loader(items, batches, device=model._device()):
+    device = model._device()
+    seqs, designs = {}, {}
+    for bi, (S, X, mask, lengths, idx) in enumerate(padded_loader(items, batches, device=device)):
         for i, s in zip(idx, model.predict_sequences(X, mask, lengths)):
             seqs[i] = s
+        if samples > 0:
+            lens = [int(v) for v in lengths]
+            logits, cu, T = model._packed_logits(X, mask, lengths)
+            cons = batch_constraints(constraints, [items[i][0] for i in idx], lens, T, bias=bias, wobble=wobble, omit=omit)
+            draws, nll, bad = design_from_logits(logits, cu_seqlens=cu, max_len=T, n_samples=samples, temperature=temperature,
+                                                 seed=seed + bi, constraints=cons.to_device(device))
+            match = score_logits(logits, cu_seqlens=cu, labels=S, seqs=draws, want=("seq_match",))["seq_match"].cpu().tolist()
+            nll, bad = nll.cpu().tolist(), bad.cpu().tolist()
+            for s in range(samples):
+                for r, (i, text) in enumerate(zip(idx, letters_padded(draws[s]))):
+                    designs.setdefault(i, []).append((s, text, nll[s][r] / lens[r], match[s][r] / lens[r], bad[r]))
     rows = [(items[i][0], seqs[i]) for i in range(len(items))]
     out_dir = os.path.dirname(os.path.abspath(out_csv))
     os.makedirs(out_dir, exist_ok=True)
@@ -29,4 +50,11 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
         f.write("pdb_id,seq\n")
         for rid, s in rows:
             f.write(f"{rid},{s}\n")
+    if samples > 0:
+        os.makedirs(os.path.dirname(os.path.abspath(designs_csv)), exist_ok=True)
+        with open(designs_csv, "w") as f:
+            f.write("pdb_id,sample,seq,nll_per_nt,recovery,infeasible\n")
+            for i in range(len(items)):
+                for s, text, nll_nt, rec, n_bad in designs[i]:
+                    f.write(f"{items[i][0]},{s},{text},{nll_nt:.6f},{rec:.6f},{n_bad}\n")
     return rows

@@ -543,11 +543,15 @@ class RNAMPNN(NativeModule):
 
     @torch.no_grad()
     def design(self, coords: torch.Tensor, mask: torch.Tensor, n_samples: int = 8, temperature: float = 0.1, seed: int = 0,
-               T_norm: int = 0):
+               T_norm: int = 0, constraints=None):
         """``sample`` plus the score of every draw against the SAME logits, with one forward: -> (seqs int8 (n_samples,B,T), -1 on
         padding; seq_nll (n_samples,B) f32).  The NLL is the model's own (temperature 1) likelihood, so designs drawn at different
-        temperatures rank on one scale."""
+        temperatures rank on one scale.  ``constraints`` (``rnampnn.utils.constraints.DesignConstraints``: fixed nucleotides, base
+        pairs of a target structure, bias): the draws come from ``rnampnn_design`` instead, which honours them and scores in the same
+        launch -> (seqs, seq_nll, infeasible (B,) int32 = positions whose constraint could not be honoured)."""
         logits = self._run(coords, mask, T_norm=T_norm)["logits"]
+        if constraints is not None:
+            return design_from_logits(logits, mask=mask, n_samples=n_samples, temperature=temperature, seed=seed, constraints=constraints)
         seqs = sample_from_logits(logits, mask, temperature, n_samples, seed)
         return seqs, score_logits(logits, mask=mask, seqs=seqs, want=("seq_nll",))["seq_nll"]
 
@@ -746,6 +750,53 @@ def sample_from_logits(logits: torch.Tensor, mask: torch.Tensor, temperature: fl
         _native.check(_native.lib().rnampnn_sample(_ptr(lg), _ptr(m), B, T, float(temperature), int(n_samples),
                                                    C.c_uint64(int(seed) & (2 ** 64 - 1)), _ptr(out), _stream(device)))
     return out
+
+
+def design_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
+                       max_len: Optional[int] = None, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None
+                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``rnampnn_design`` (include/rnampnn_hip.h): ``n_samples`` constrained draws per RNA from f32 logits and their scores in one launch
+    -> (seqs int8 (S,B,T), -1 on padding; seq_nll (S,B) f32 = ``score_logits``' ``seq_nll`` of the draws; infeasible (B,) int32).  Padded
+    layout: logits (B,T,4) + ``mask`` (B,T); packed layout: logits (N,4) + ``cu_seqlens`` (B+1), the padded extent T from the constraints'
+    tensors or ``max_len``.  ``constraints``: a ``DesignConstraints`` (padded (B,T) tensors in both layouts) or None for a free draw.
+    CUDA logits only (there is no CPU fallback); no host synchronisation."""
+    device = logits.device
+    if device.type != "cuda":
+        raise RuntimeError("rnampnn_design runs on an MI355X: pass CUDA logits (there is no CPU fallback)")
+    lg = _prep(logits, device)
+    m = None if mask is None else _prep(mask, device)
+    cu = None if cu_seqlens is None else _prep(cu_seqlens, device, torch.int32)
+    c = constraints
+    al = None if c is None or c.allowed is None else _prep(c.allowed, device, torch.uint8)
+    pa = None if c is None or c.partner is None else _prep(c.partner, device, torch.int32)
+    bi = None if c is None or c.bias is None else _prep(c.bias, device)
+    if m is not None:
+        B, T = int(m.shape[0]), int(m.shape[1])
+    else:
+        B = (int(cu.numel()) - 1) if cu is not None else int(lg.shape[0])
+        shaped = next((t for t in (al, pa) if t is not None), None)
+        T = int(max_len) if max_len is not None else int(shaped.shape[-1]) if shaped is not None else 0
+    for name, t in (("allowed", al), ("partner", pa)):
+        if t is not None and tuple(t.shape) != (B, T):
+            raise ValueError(f"constraints.{name} must be padded to (B, T) = {(B, T)}, got {tuple(t.shape)}")
+    per_position = 0
+    if bi is not None:
+        if tuple(bi.shape) == (B, T, 4):
+            per_position = 1
+        elif tuple(bi.shape) != (4,):
+            raise ValueError(f"constraints.bias must be (4,) or (B, T, 4) = {(B, T, 4)}, got {tuple(bi.shape)}")
+    if lg.shape[-1] != 4 or lg.numel() < (4 * B * T if m is not None else 0):
+        raise ValueError(f"logits must be (B, T, 4) with the mask or (N, 4) with cu_seqlens, got {tuple(lg.shape)}")
+    S = int(n_samples)
+    seqs = torch.empty(max(S, 0), max(B, 0), max(T, 0), dtype=torch.int8, device=device)
+    nll = torch.empty(max(S, 0), max(B, 0), dtype=torch.float32, device=device)
+    bad = torch.empty(max(B, 0), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _native.check(_native.lib().rnampnn_design(
+            _ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(cu), B, T, float(temperature), S, C.c_uint64(int(seed) & (2 ** 64 - 1)), None,
+            _ptr(al), _ptr(pa), int(bool(c.wobble)) if c is not None else 1, _ptr(bi), per_position, _ptr(seqs), _ptr(nll), _ptr(bad),
+            _stream(device)))
+    return seqs, nll, bad
 
 
 SCORE_OUTPUTS = {"valid": torch.int32, "pred": torch.int8, "correct": torch.int32, "label_nll": torch.float32, "label_loss": torch.float32,

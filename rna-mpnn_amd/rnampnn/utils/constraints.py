@@ -1,0 +1,158 @@
+"""Design constraints for ``rnampnn_design`` (include/rnampnn_hip.h), built on the host: a sequence pattern -> the 4-bit ``allowed`` set of
+every position, a dot-bracket secondary structure -> the ``partner`` table, a per-class or per-position ``bias``.  Nothing here touches a
+device until ``DesignConstraints.to_device``."""
+from __future__ import annotations
+
+import csv
+from dataclasses import dataclass
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from ..config.glob import VOCAB
+
+FREE = 0xF
+_BRACKETS = {"(": ")", "[": "]", "{": "}", "<": ">"}
+_CLOSERS = {v: k for k, v in _BRACKETS.items()}
+
+
+def _bits(letters: str) -> int:
+    return sum(1 << VOCAB[ch] for ch in letters)
+
+
+# IUPAC nucleotide codes (T is read as U); '.' and '-' leave the position free
+IUPAC = {"A": _bits("A"), "U": _bits("U"), "T": _bits("U"), "C": _bits("C"), "G": _bits("G"),
+         "R": _bits("AG"), "Y": _bits("CU"), "S": _bits("CG"), "W": _bits("AU"), "K": _bits("GU"), "M": _bits("AC"),
+         "B": _bits("CGU"), "D": _bits("AGU"), "H": _bits("ACU"), "V": _bits("ACG"), "N": FREE, ".": FREE, "-": FREE}
+
+
+def parse_dot_bracket(text: str) -> np.ndarray:
+    """Dot-bracket string -> int32 partner array (-1 = unpaired).  ``()``, ``[]``, ``{}`` and ``<>`` nest independently of each other
+    (pseudoknots); ``.`` is unpaired.  ``ValueError`` on an unbalanced string or an unknown character."""
+    partner = np.full(len(text), -1, dtype=np.int32)
+    stacks = {k: [] for k in _BRACKETS}
+    for i, ch in enumerate(text):
+        if ch == ".":
+            continue
+        if ch in _BRACKETS:
+            stacks[ch].append(i)
+        elif ch in _CLOSERS:
+            st = stacks[_CLOSERS[ch]]
+            if not st:
+                raise ValueError(f"dot-bracket: {ch!r} at position {i} closes nothing")
+            j = st.pop()
+            partner[i], partner[j] = j, i
+        else:
+            raise ValueError(f"dot-bracket: unknown character {ch!r} at position {i}")
+    for k, st in stacks.items():
+        if st:
+            raise ValueError(f"dot-bracket: {k!r} at position {st[-1]} is never closed")
+    return partner
+
+
+def parse_pattern(text: str) -> np.ndarray:
+    """Sequence pattern -> uint8 ``allowed`` array: AUCG (and T = U) fix a nucleotide, the IUPAC codes R Y S W K M B D H V N admit their
+    sets, ``.`` and ``-`` leave the position free; case is ignored.  ``ValueError`` on any other character."""
+    out = np.empty(len(text), dtype=np.uint8)
+    for i, ch in enumerate(text.upper()):
+        if ch not in IUPAC:
+            raise ValueError(f"pattern: unknown character {text[i]!r} at position {i}")
+        out[i] = IUPAC[ch]
+    return out
+
+
+def parse_bias(text: str) -> np.ndarray:
+    """``A=..,U=..,C=..,G=..`` (any subset, T = U) -> float32 (4,) in class order; classes not named get 0."""
+    out = np.zeros(4, dtype=np.float32)
+    for item in filter(None, (s.strip() for s in text.split(","))):
+        key, sep, val = item.partition("=")
+        key = key.strip().upper().replace("T", "U")
+        if not sep or key not in VOCAB:
+            raise ValueError(f"bias: expected LETTER=VALUE with a letter of AUCG, got {item!r}")
+        out[VOCAB[key]] = float(val)
+    return out
+
+
+def omit_mask(letters: str) -> int:
+    """``--omit`` letters -> the ``allowed`` set without them."""
+    m = FREE
+    for ch in letters.upper().replace("T", "U"):
+        if ch not in VOCAB:
+            raise ValueError(f"omit: {ch!r} is not one of AUCG")
+        m &= ~(1 << VOCAB[ch])
+    return m
+
+
+@dataclass
+class DesignConstraints:
+    """Per-batch padded tensors: ``allowed`` (B,T) uint8, ``partner`` (B,T) int32, ``bias`` (4,) or (B,T,4) float32; each may be None."""
+    allowed: Optional[torch.Tensor] = None
+    partner: Optional[torch.Tensor] = None
+    bias: Optional[torch.Tensor] = None
+    wobble: bool = True
+
+    @classmethod
+    def from_specs(cls, specs: Sequence[Tuple[Optional[str], Optional[str]]], lengths: Sequence[int], T: int, bias=None,
+                   wobble: bool = True, omit: str = "") -> "DesignConstraints":
+        """One ``(pattern or None, structure or None)`` per RNA -> padded host tensors (free / unpaired where nothing is given and on
+        padding).  ``omit``: letters no position may draw.  ``ValueError`` when a pattern or structure is not as long as its RNA."""
+        B = len(specs)
+        if len(lengths) != B:
+            raise ValueError(f"{B} specs for {len(lengths)} lengths")
+        keep = omit_mask(omit)
+        allowed = np.full((B, T), FREE, dtype=np.uint8)
+        partner = np.full((B, T), -1, dtype=np.int32)
+        for b, ((pattern, structure), n) in enumerate(zip(specs, lengths)):
+            n = int(n)
+            if n > T:
+                raise ValueError(f"RNA {b}: length {n} exceeds T = {T}")
+            if pattern:
+                if len(pattern) != n:
+                    raise ValueError(f"RNA {b}: pattern of length {len(pattern)} for an RNA of length {n}")
+                allowed[b, :n] = parse_pattern(pattern)
+            if structure:
+                if len(structure) != n:
+                    raise ValueError(f"RNA {b}: structure of length {len(structure)} for an RNA of length {n}")
+                partner[b, :n] = parse_dot_bracket(structure)
+        allowed &= np.uint8(keep)
+        have_allowed = keep != FREE or any(p for p, _ in specs)
+        have_partner = any(s for _, s in specs)
+        return cls(allowed=torch.from_numpy(allowed) if have_allowed else None,
+                   partner=torch.from_numpy(partner) if have_partner else None,
+                   bias=None if bias is None else torch.as_tensor(np.asarray(bias, dtype=np.float32)), wobble=wobble)
+
+    def to_device(self, device) -> "DesignConstraints":
+        mv = lambda t, dt: None if t is None else t.to(device=device, dtype=dt).contiguous()
+        return DesignConstraints(mv(self.allowed, torch.uint8), mv(self.partner, torch.int32), mv(self.bias, torch.float32), self.wobble)
+
+
+def read_constraints_csv(path: str) -> Dict[str, Tuple[str, str]]:
+    """CSV with the columns ``pdb_id,fixed,structure`` -> {pdb_id: (pattern, structure)}; either field may be empty."""
+    out = {}
+    with open(path, newline="") as f:
+        rd = csv.DictReader(f)
+        missing = {"pdb_id", "fixed", "structure"} - set(rd.fieldnames or ())
+        if missing:
+            raise ValueError(f"{path}: missing column(s) {sorted(missing)} (expected pdb_id,fixed,structure)")
+        for row in rd:
+            out[row["pdb_id"].strip()] = ((row["fixed"] or "").strip(), (row["structure"] or "").strip())
+    return out
+
+
+def batch_constraints(table: Optional[Dict[str, Tuple[str, str]]], ids: Sequence[str], lengths: Sequence[int], T: int, bias=None,
+                      wobble: bool = True, omit: str = "") -> DesignConstraints:
+    """The constraints of one batch from a ``read_constraints_csv`` table: ids not in it are unconstrained; a row whose pattern or structure
+    is not as long as its structure file is an error that names the id."""
+    specs = []
+    for rid, n in zip(ids, lengths):
+        pattern, structure = (table or {}).get(rid, ("", ""))
+        for what, text in (("fixed", pattern), ("structure", structure)):
+            if text and len(text) != int(n):
+                raise ValueError(f"constraints for {rid}: {what} has {len(text)} characters, the structure has {int(n)} nucleotides")
+        try:                                                      # a malformed row names its id too
+            parse_pattern(pattern), parse_dot_bracket(structure)
+        except ValueError as exc:
+            raise ValueError(f"constraints for {rid}: {exc}") from None
+        specs.append((pattern or None, structure or None))
+    return DesignConstraints.from_specs(specs, lengths, T, bias=bias, wobble=wobble, omit=omit)

@@ -11,7 +11,8 @@ import numpy as np
 import torch
 
 from ..config.glob import VOCAB
-from ..model.rnampnn import letters_packed, letters_padded, sample_from_logits, score_logits
+from ..model.rnampnn import design_from_logits, letters_packed, letters_padded, sample_from_logits, score_logits
+from .constraints import batch_constraints
 from .data import PackedLoader, bucket_batches, fill_nan_deterministic, read_fasta
 
 
@@ -38,12 +39,16 @@ def load_structures(path: str, max_len: int = 1 << 30):
 
 @torch.no_grad()
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
-            seed: int = 0, designs_csv: Optional[str] = None) -> List[Tuple[str, str]]:
+            seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
+            wobble: bool = True) -> List[Tuple[str, str]]:
     """Design a sequence for every structure under ``data_path`` in length-bucketed var-len batches (``forward_packed``): the tree
     read-out on the packed embedding when one is attached, else the read-out's argmax (``rnampnn_score``'s ``pred``); write ``out_csv``
     with one ``pdb_id,seq`` row per structure in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure
     at ``temperature`` (``rnampnn_sample``), score them against the same logits and write ``designs_csv`` with the columns
-    ``pdb_id,sample,seq,nll_per_nt,recovery`` (``recovery`` = fraction equal to the fasta's sequence, empty without one)."""
+    ``pdb_id,sample,seq,nll_per_nt,recovery`` (``recovery`` = fraction equal to the fasta's sequence, empty without one).
+    ``constraints`` ({pdb_id: (pattern, structure)}, ``read_constraints_csv``; ids not in it are unconstrained), ``bias`` (4 per-class
+    floats), ``omit`` (letters never drawn) or ``wobble=False``: the draws come from ``rnampnn_design`` on the packed logits instead (no
+    scatter to the padded layout) and ``designs_csv`` gains a last column ``infeasible``."""
     model.eval()
     device = model._device()
     items = load_structures(data_path, max_len=int(model.hparams["padding_len"]))
@@ -53,6 +58,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
         designs_csv = os.path.splitext(out_csv)[0] + "_designs.csv"
     lengths = [int(c.shape[0]) for _, c, _ in items]
     trees = getattr(model, "xgb_readout", None)
+    constrained = constraints is not None or bias is not None or bool(omit) or not wobble
     seqs, designs = {}, {}
     for bi, (coords, cu, max_len, idx) in enumerate(PackedLoader(items, bucket_batches(lengths, batch_size, max_rows, seed=0), device=device)):
         lens = [lengths[i] for i in idx]
@@ -66,12 +72,19 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
         for i, s in zip(idx, names):
             seqs[i] = s
         if samples > 0:
-            # rnampnn_sample takes the padded layout: scatter the packed logits once (row cu[b] + t -> (b, t)); the mask comes from cu
-            t = torch.arange(max_len, device=device)
-            mask = (t[None, :] < (cu[1:] - cu[:-1])[:, None]).to(torch.float32)
-            rows_of = (cu[:-1].to(torch.int64)[:, None] + t[None, :]).clamp_(max=int(logits.shape[0]) - 1)
-            padded = torch.where(mask[..., None] != 0, logits[rows_of], torch.zeros((), dtype=torch.float32, device=device))
-            draws = sample_from_logits(padded, mask, temperature, samples, seed + bi)
+            bad = dnll = None
+            if constrained:
+                cons = batch_constraints(constraints, [items[i][0] for i in idx], lens, max_len, bias=bias, wobble=wobble, omit=omit)
+                draws, dnll, bad = design_from_logits(logits, cu_seqlens=cu, max_len=max_len, n_samples=samples, temperature=temperature,
+                                                   seed=seed + bi, constraints=cons.to_device(device))
+                bad = bad.cpu().tolist()
+            else:
+                # rnampnn_sample takes the padded layout: scatter the packed logits once (row cu[b] + t -> (b, t)); the mask comes from cu
+                t = torch.arange(max_len, device=device)
+                mask = (t[None, :] < (cu[1:] - cu[:-1])[:, None]).to(torch.float32)
+                rows_of = (cu[:-1].to(torch.int64)[:, None] + t[None, :]).clamp_(max=int(logits.shape[0]) - 1)
+                padded = torch.where(mask[..., None] != 0, logits[rows_of], torch.zeros((), dtype=torch.float32, device=device))
+                draws = sample_from_logits(padded, mask, temperature, samples, seed + bi)
             have = [items[i][2] is not None for i in idx]
             lab = None
             if any(have):
@@ -79,13 +92,14 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
                 for r, i in enumerate(idx):
                     if have[r]:
                         lab[r, :lens[r]] = torch.from_numpy(items[i][2]).to(torch.int32)
-            sc = score_logits(logits, cu_seqlens=cu, labels=lab, seqs=draws, want=("seq_nll",) + (("seq_match",) if lab is not None else ()))
-            nll = sc["seq_nll"].cpu().tolist()
+            want = (("seq_nll",) if dnll is None else ()) + (("seq_match",) if lab is not None else ())      # rnampnn_design scores its own draws
+            sc = score_logits(logits, cu_seqlens=cu, labels=lab, seqs=draws, want=want) if want else {}
+            nll = (sc["seq_nll"] if dnll is None else dnll).cpu().tolist()
             match = sc["seq_match"].cpu().tolist() if lab is not None else None
             for s in range(samples):
                 for r, (i, text) in enumerate(zip(idx, letters_padded(draws[s]))):
                     rec = f"{match[s][r] / lens[r]:.6f}" if match is not None and have[r] else ""
-                    designs.setdefault(i, []).append((s, text, nll[s][r] / lens[r], rec))
+                    designs.setdefault(i, []).append((s, text, nll[s][r] / lens[r], rec + (f",{bad[r]}" if bad is not None else "")))
     rows = [(items[i][0], seqs[i]) for i in range(len(items))]
     os.makedirs(os.path.dirname(os.path.abspath(out_csv)), exist_ok=True)
     with open(out_csv, "w") as f:
@@ -95,7 +109,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     if samples > 0:
         os.makedirs(os.path.dirname(os.path.abspath(designs_csv)), exist_ok=True)
         with open(designs_csv, "w") as f:
-            f.write("pdb_id,sample,seq,nll_per_nt,recovery\n")
+            f.write("pdb_id,sample,seq,nll_per_nt,recovery" + (",infeasible" if constrained else "") + "\n")
             for i in range(len(items)):
                 for s, text, nll_nt, rec in designs[i]:
                     f.write(f"{items[i][0]},{s},{text},{nll_nt:.6f},{rec}\n")

@@ -1,0 +1,58 @@
+#!/usr/bin/env python3
+"""The measurement behind DESIGN.md section 9 "Constrained design" (profiles/design_kernel_stats.txt): the C2 batch (256 RNAs x 100..140 nt),
+S = 8 sequences per RNA.
+usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + rnampnn_score (seq_nll): the unconstrained pair of launches
+       python tools/design_probe.py design [calls=50]         rnampnn_design: free, then with a hairpin's pairs + a fixed GNRA loop per RNA
+HIP events around each loop of back-to-back calls of the Python wrappers.  Run either under `rocprofv3 --kernel-trace --stats -- python ...`
+(a run of its own) for the kernels' own times.  RNAMPNN_PROBE_ROOT: another checkout (with its library built) to take the package from -
+the `sample_score` leg uses nothing newer than rnampnn_score, so it runs on the parent commit as well."""
+import os
+import sys
+
+REPO = os.environ.get("RNAMPNN_PROBE_ROOT") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, os.path.join(REPO, "rna-mpnn_amd"))
+import torch
+from rnampnn.model import rnampnn as M
+from rnampnn.utils import synth
+
+what = sys.argv[1] if len(sys.argv) > 1 else "design"
+n_calls = int(sys.argv[2]) if len(sys.argv) > 2 else 50
+S = 8
+lens = [int(n) for n in synth.synth_lengths(256, 100, 140, seed=0)]
+_, mask, _ = synth.synth_batch(lens)
+B, T = mask.shape
+m = torch.from_numpy(mask).cuda()
+logits = (3.0 * torch.randn(B, T, 4, generator=torch.Generator().manual_seed(0))).cuda() * m[..., None]
+
+
+def timed(name, fn):
+    for _ in range(5):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n_calls):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    print(f"B {B} T {T} nt {int(mask.sum())} S {S} {name}: {e0.elapsed_time(e1) * 1e3 / n_calls:.2f} us per call (events, back to back, "
+          f"output allocation included)")
+
+
+if what == "sample_score":
+    def two_launches():
+        seqs = M.sample_from_logits(logits, m, 0.1, S, seed=1)
+        return seqs, M.score_logits(logits, mask=m, seqs=seqs, want=("seq_nll",))["seq_nll"]
+    timed("rnampnn_sample + rnampnn_score(seq_nll)", two_launches)
+else:
+    from rnampnn.utils.constraints import DesignConstraints
+    specs = []
+    for n in lens:                                                  # a hairpin: a stem of (n - 4) // 2 pairs closed by a GNRA tetraloop
+        stem = (n - 4) // 2
+        specs.append(("." * stem + "GNRA" + "." * (n - stem - 4), "(" * stem + "...." + ")" * stem + "." * (n - 2 * stem - 4)))
+    cons = DesignConstraints.from_specs(specs, lens, T, bias=[0.0, 0.0, 0.0, -0.5]).to_device("cuda")
+    timed("rnampnn_design, no constraints", lambda: M.design_from_logits(logits, mask=m, n_samples=S, temperature=0.1, seed=1))
+    timed("rnampnn_design, hairpin pairs + GNRA + bias", lambda: M.design_from_logits(logits, mask=m, n_samples=S, temperature=0.1, seed=1,
+                                                                                      constraints=cons))
+    seqs, nll, bad = M.design_from_logits(logits, mask=m, n_samples=S, temperature=0.1, seed=1, constraints=cons)
+    print(f"infeasible positions {int(bad.sum())}, mean NLL per nt {float(nll.sum()) / (S * int(mask.sum())):.4f}")
