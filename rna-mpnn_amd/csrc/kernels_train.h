@@ -1,6 +1,7 @@
 // Training-path building blocks (kernels_train.hip): f32, packed rows.
 #pragma once
 #include "rnampnn_internal.h"
+#include "red_queue.h"
 
 struct TRows { const int* ntot; int mul; int maxrows; };   // row count = *ntot * mul (device side), maxrows = host upper bound
 
@@ -28,29 +29,32 @@ static inline unsigned ew_grid(size_t units) { const size_t g = (units + 255) / 
 
 void t_gemm(const TRows& rows, const float* X, int ldx, int K, const float* Wt, int ldw, const float* bias, int N,
             float* Y, int ldy, int beta, hipStream_t s);                      // Y = beta*Y + X.Wt + bias   (Wt K-major, row stride ldw)
-// Ordered reductions of one backward (kernels_train.hip: RedQueue).  Between red_begin and red_end every producer of partial tiles (t_gemm_tn,
-// t_colsum, tm_gemm_tn[_pq], te_gemm_tn, te_gemm_bwd1[x2], te_gemm_bwd2, t_gn_bwd) takes an exact extent of the arena (red_alloc) and records its
-// reduction, and the recorded reductions run many per launch; calling one outside a queue is an error.  red_flush makes everything recorded so far
-// final (before a gradient chunk's event); red_end flushes, closes the queue and returns false when a request or job was refused since the last
-// red_end (nothing of it was launched).  An arena holds at least one producer's budget of RED_VIEW floats.
+// One training or inference call as the launchers below see it: its stream, the ordered reductions of its backward and the weight-image cache of
+// its handle (null: kernels build their images themselves).  Tr (train.cpp) and RdRun (rdesign_internal.h) each own one; the launchers that
+// allocate partials or look up an image take it in place of the stream.
+// Ordered reductions (red_queue.h: RedQueue): between red_begin and red_end every producer of partial tiles (t_gemm_tn, t_colsum, tm_gemm_tn[_pq],
+// te_gemm_tn, te_gemm_bwd1[x2], te_gemm_bwd2, t_gn_bwd) takes an exact extent of the arena and records its reduction, and the recorded reductions
+// run many per launch (RNAMPNN_NO_RED_BATCH=1, read at red_begin: one per launch); a producer called outside the two is refused.  red_flush makes
+// everything recorded so far final (before a gradient chunk's event); red_end flushes, closes the queue and returns false when a request or job was
+// refused since red_begin (nothing of it was launched).  An arena holds at least one producer's budget of RED_VIEW floats.
 struct TScratch { float* p; size_t floats; };
 static constexpr size_t RED_VIEW = (size_t)16 << 20;
-void red_begin(const TScratch& arena, hipStream_t s);
-float* red_alloc(size_t floats);
-void red_flush();
-bool red_end();
-void t_gemm_tn(const TRows& rows, const float* A, int lda, int M, const float* B, int ldb, int K, float* dW, int ldw,
-               hipStream_t s);                                                                               // dW += A^T B
+struct WImageCache;
+struct TCall { hipStream_t s = nullptr; RedQueue red; WImageCache* wimg = nullptr; };
+static inline void red_begin(TCall& cx, const TScratch& arena) { cx.red.open(arena.p, arena.floats, cx.s, ab_switch("RNAMPNN_NO_RED_BATCH")); }
+static inline void red_flush(TCall& cx) { cx.red.flush(); }
+static inline bool red_end(TCall& cx) { return cx.red.end(); }
+void t_gemm_tn(const TRows& rows, const float* A, int lda, int M, const float* B, int ldb, int K, float* dW, int ldw, TCall& cx);   // dW += A^T B
 // bf16-mixed MFMA versions (kernels_train.hip, second half).  _nt / _nn / _tn return false (nothing launched) when the shape is not covered
 // (K not a multiple of 16, unaligned rows; _tn with actB: a partial tile larger than its budget): the caller then uses the f32 kernels.
 bool tm_gemm_nt(const TRows& rows, const float* X, int ldx, int K, const float* W, int ldw, const float* bias, int N, float* Y,
-                int ldy, int beta, bool actA, const TDrop& dr, unsigned site, hipStream_t s);
+                int ldy, int beta, bool actA, const TDrop& dr, unsigned site, TCall& cx);
 bool tm_gemm_nn(const TRows& rows, const float* X, int ldx, int K, const float* W, int ldw, const float* bias, int N, float* Y,
-                int ldy, int beta, const float* epi_pre, int ld_epi, const TDrop& dr, unsigned site, hipStream_t s);
+                int ldy, int beta, const float* epi_pre, int ld_epi, const TDrop& dr, unsigned site, TCall& cx);
 // dbias (optional): += column sums of A, computed from the tiles the kernel stages anyway (the bias gradient of the same Linear)
 bool tm_gemm_tn(const TRows& rows, const float* A, int lda, int M, const float* B, int ldb, int K, float* dW, int ldw,
-                bool actB, const TDrop& dr, unsigned site, float* dbias, hipStream_t s);
-void t_colsum(const TRows& rows, const float* A, int lda, int M, float* out, hipStream_t s);   // out += column sums
+                bool actB, const TDrop& dr, unsigned site, float* dbias, TCall& cx);
+void t_colsum(const TRows& rows, const float* A, int lda, int M, float* out, TCall& cx);   // out += column sums
 void t_gelu_fwd(const TRows& rows, const float* x, float* y, int D, const TDrop& dr, unsigned site, hipStream_t s);   // y = drop(gelu(x))
 void t_gelu_bwd(const TRows& rows, const float* dy, const float* pre, float* dx, int D, const TDrop& dr, unsigned site,
                 hipStream_t s);                                                                             // dx = dy * mask * gelu'(pre)
@@ -70,7 +74,7 @@ void t_edge_res_bwd(const PackInfo& pk, int k, const int* nbr, const float* de, 
 void t_build_reverse(const PackInfo& pk, int k, const int* nbr, int* deg, int* start, int* fill, int* list, int* tmp, hipStream_t s);   // tmp: [Nmax*k] ints of scratch
 void t_edge_pq_bwd(const PackInfo& pk, int k, const float* dpre1, const int* start, const int* list, float* dpq, hipStream_t s);
 void t_gn_bwd(const PackInfo& pk, const float* x, const float* dy, const float* scale, int t_tot, float* dx, float* dscale,
-              float* dshift, hipStream_t s);
+              float* dshift, TCall& cx);
 // stat [N][heads][3]: the forward writes (row max, normaliser) per (query, head); the backward reads them and adds delta (it is a TAPE: one per attention layer)
 int  t_attention_fwd(const PackInfo& pk, const float* qkv, int heads, float* out, float* stat, const TDrop& dr, unsigned site, hipStream_t s);
 int  t_attention_bwd(const PackInfo& pk, const float* qkv, const float* O, const float* dO, int heads, float* dqkv, float* stat,
@@ -101,23 +105,22 @@ struct EFuse {                       // optional epilogue fusions of te_gemm
 // nn.Linear stores it) or W (W [128][ldw] k-major).  X is bf16 (x_bf16) or f32, row stride ldx.  Returns false (nothing launched) for a
 // combination of options that is not instantiated.
 bool te_gemm(const TRows& rows, const void* X, bool x_bf16, int ldx, const float* W, int ldw, bool w_rows, const float* bias, tb16* Y,
-             bool actA, const tb16* epi_pre, const EFuse* fuse, const TDrop& dr, unsigned site, hipStream_t s, int kvalid = 128);   // kvalid: live columns of X (the rest is zero padding)
+             bool actA, const tb16* epi_pre, const EFuse* fuse, const TDrop& dr, unsigned site, TCall& cx, int kvalid = 128);   // kvalid: live columns of X (the rest is zero padding)
 // dW[128][ldw] += A^T . actB(B), dbias += colsum(A)     (A, B bf16 [R][128])
 void te_gemm_tn(const TRows& rows, const tb16* A, const tb16* B, float* dW, int ldw, bool actB, const TDrop& dr,
-                unsigned site, float* dbias, hipStream_t s, int cols_keep = 128);      // cols_keep: live columns of B
+                unsigned site, float* dbias, TCall& cx, int cols_keep = 128);      // cols_keep: live columns of B
 // the node-side GEMMs of a factored first Linear, each pair as one launch: P / Q tables, [dWa ; dWb] (+ db1), dh += dP Wa + dQ Wb
-void te_gemm_pq(const TRows& rows, const float* h, const float* w0, const float* b1, tb16* Pt, tb16* Qt, hipStream_t s);
-void tm_gemm_tn_pq(const TRows& rows, const float* dpq, const float* h, float* gw0, float* db1, hipStream_t s);
+void te_gemm_pq(const TRows& rows, const float* h, const float* w0, const float* b1, tb16* Pt, tb16* Qt, TCall& cx);
+void tm_gemm_tn_pq(const TRows& rows, const float* dpq, const float* h, float* gw0, float* db1, TCall& cx);
 bool tm_gemm_nn_pq(const TRows& rows, const float* dpq, const float* w0, float* dh, hipStream_t s);
 #define TE_DROPPED (-1.0e4f)         // taped in place of a dropped pre-activation: gelu_fast, gelu_d_fast and gelu_both_fast give exactly (-)0 there
 // forward of a depth-2 per-edge MLP in one kernel (the hidden activation stays in registers; pre1 / pre2 written once as the tape;
 // pre1 = null: not kept).  pre1 is taped with its dropped elements replaced by TE_DROPPED; with f.res_out (edge update) pre2 receives
 // gelu'(pre2) * mask(site2) - the tapes te_gemm_bwd2 reads
 void te_mlp2_fwd(const TRows& rows, const tb16* X, const float* W1, int ldw1, const float* W2, int ldw2, const float* bias2, tb16* pre1,
-                 tb16* pre2, const EFuse& f, const TDrop& dr, unsigned site, hipStream_t s);
+                 tb16* pre2, const EFuse& f, const TDrop& dr, unsigned site, TCall& cx);
 // fused pair of a first Linear's backward: dW += dY^T X, DE += dY . W   (one pass over dY)
-void te_gemm_bwd1(const TRows& rows, const tb16* dY, const tb16* X, tb16* DE, const float* W, int ldw, float* dW, int ldw_out,
-                  hipStream_t s);
+void te_gemm_bwd1(const TRows& rows, const tb16* dY, const tb16* X, tb16* DE, const float* W, int ldw, float* dW, int ldw_out, TCall& cx);
 // fused pair of a depth-2 MLP's backward: dW += d pre2^T drop(gelu(PRE)), dbias += colsum(d pre2), DX = (d pre2 . W) gelu'(PRE) mask   (one pass
 // over PRE).  d pre2 is formed on the fly while the tile is staged - mode 1: dY = d e_out, d pre2 = valid ? dY gelu'(pre2) mask(site2) : 0 (the
 // edge update's residual backward); mode 2: d pre2 = valid ? dagg[row / k] inv_cnt[row / k] gelu'(pre2) mask(site2) : 0 (the message mean's).
@@ -125,9 +128,9 @@ void te_gemm_bwd1(const TRows& rows, const tb16* dY, const tb16* X, tb16* DE, co
 // k_emm_fwd2: the staging pass multiplies, and evaluates no dropout hash
 struct EBwd2Src { int mode; const tb16* pre2; const int* nbr; const float* dagg; const float* inv_cnt; int k; };
 void te_gemm_bwd1x2(const TRows& rows, const tb16* dY1, const tb16* dY2, const tb16* X, tb16* DE, const float* W1, const float* W2, int ldw,
-                    float* dW1, float* dW2, int ldw_out, hipStream_t s);
+                    float* dW1, float* dW2, int ldw_out, TCall& cx);
 void te_gemm_bwd2(const TRows& rows, const tb16* dY, const tb16* PRE, tb16* DX, const float* W, int ldw, float* dW, int ldw_out,
-                  const TDrop& dr, float* dbias, hipStream_t s, const EBwd2Src& from);
+                  const TDrop& dr, float* dbias, TCall& cx, const EBwd2Src& from);
 void te_inv_count(const PackInfo& pk, int k, const int* nbr, float* inv_cnt, hipStream_t s);   // 1 / max(#valid slots, 1) per residue
 // g2_out (optional, may alias pre2): gelu'(pre2) * mask(site) per element - what the message MLP's backward needs of pre2
 void te_seg_mean(const PackInfo& pk, int k, const int* nbr, const tb16* pre2, const float* h, float* out, const TDrop& dr, unsigned site, hipStream_t s,
@@ -138,12 +141,10 @@ void te_edge_pq_bwd(const PackInfo& pk, int k, const tb16* dpre1, const int* sta
 void te_edge_features(const PackInfo& pk, int k, const float* geom, const int* nbr, tb16* F, hipStream_t s);          // raw edge features, bf16 [E][128] (90 live columns)
 void te_edge_act(const PackInfo& pk, int k, const int* nbr, const tb16* pre, tb16* out, const TDrop& dr, unsigned site, hipStream_t s);   // out = valid ? drop(gelu(pre)) : 0
 
-// ---- cache of prebuilt bf16 fragment images of the 128 x 128 weight blocks the weights-resident GEMMs use (kernels_train.hip):
-// bind it for the calling thread, refresh at the start of a training forward (one launch rebuilds every image registered so far).
-struct WImageCache;
+// ---- cache of prebuilt bf16 fragment images of the 128 x 128 weight blocks the weights-resident GEMMs use (kernels_train.hip): a handle owns one
+// and hands it to its calls (TCall::wimg); refresh at the start of a training forward (one launch rebuilds every image registered so far).
 WImageCache* t_wimg_create(int capacity);
 void t_wimg_destroy(WImageCache* c);
-void t_wimg_bind(WImageCache* c);            // null: kernels build their images themselves
 void t_wimg_clear(WImageCache* c);           // the weights moved (new arena)
 void t_wimg_refresh(WImageCache* c, hipStream_t s);
 int t_wimg_pending(const WImageCache* c);     // blocks registered since the last refresh (their kernels still build their own image)

@@ -72,21 +72,8 @@ void t_gemm(const TRows& rows, const float* X, int ldx, int K, const float* Wt, 
     hipLaunchKernelGGL(k_tgemm, grid, dim3(256), 0, s, rows, X, ldx, K, Wt, ldw, bias, N, Y, ldy, beta);
 }
 
-// ---- ordered reductions of the backward.  A producer writes one partial tile per split of its row range into an extent it takes from the arena of
-// the active queue (red_alloc: red_begin .. red_end, one queue per backward), then records a job that adds the partials into the gradient:
-//   out[(i / cols) * ld_out + i % cols] += sum_{p < nparts} part[p * stride + i]     for i < split_at (columns >= cols_keep: operand padding;
-//   wrap_rows: output rows beyond it continue wrap_shift columns to the right - the [Wa | Wb] blocks of a first Linear's weight gradient, produced
-//   as one 256-row product);  out2[i - split_at] += ... for split_at <= i < split_at + out2_keep (the bias gradient riding behind a weight tile).
-// No float atomics: gradients are bit-reproducible.  k_reduce_batch runs up to RED_MAX jobs per launch (job table by value in the kernel arguments): a
-// kernel boundary costs ~4.7 us on this part and a step has ~180 of these reductions, each a few microseconds of work.  Per job the association order
+// ---- ordered reductions of the backward (red_queue.h has the index map of a job and the queue that batches them).  Per job the association order
 // is a function of nparts alone: four contiguous runs of partials summed in ascending order, then ((g0 + g1) + g2) + g3.
-struct RedJob {
-    const float* part; float* out; float* out2; size_t stride;
-    int nparts, count, cols, ld_out, split_at, cols_keep, out2_keep, wrap_rows, wrap_shift, blk0;
-};
-#define RED_MAX 48
-struct RedBatch { RedJob j[RED_MAX]; int n; };
-static_assert(sizeof(RedBatch) <= 4000, "job table travels in the kernel arguments");
 __global__ void __launch_bounds__(256) k_reduce_batch(RedBatch b) {
     __shared__ float red[4][64];
     int jb = 0;
@@ -110,99 +97,12 @@ __global__ void __launch_bounds__(256) k_reduce_batch(RedBatch b) {
             J.out[(size_t)(J.wrap_rows ? row % J.wrap_rows : row) * J.ld_out + (J.wrap_rows ? (row / J.wrap_rows) * J.wrap_shift : 0) + c] += s;
     } else if (i - J.split_at < J.out2_keep) J.out2[i - J.split_at] += s;
 }
-
-// Host side.  The queue launches what it holds (red_flush) when the arena cannot hold the next extent, before a job whose output footprint meets a
-// pending job's (the jobs of one launch add with plain +=), when the table is full, when a gradient chunk becomes final and at red_end;
-// RNAMPNN_NO_RED_BATCH=1 launches every job on its own.  A request or job outside an active queue, an extent larger than the arena and a job whose
-// partials are not inside the extents handed out or meet a pending job's partials are refused: nothing is launched and red_end reports false.
-struct RedQueue {
-    bool active = false, one = false, bad = false;      // one: a launch per job;  bad: sticky until red_end reports it
-    float* arena = nullptr; size_t floats = 0, used = 0;
-    hipStream_t s = nullptr;
-    RedBatch b;
-    int blocks = 0;
-};
-static thread_local RedQueue g_rq;
-static void red_launch() {
-    RedQueue& q = g_rq;
-    if (q.active && q.b.n > 0) hipLaunchKernelGGL(k_reduce_batch, dim3(q.blocks), dim3(256), 0, q.s, q.b);
-    q.b.n = 0; q.blocks = 0;
-}
-void red_flush() { red_launch(); g_rq.used = 0; }
-void red_begin(const TScratch& arena, hipStream_t s) {
-    RedQueue& q = g_rq;
-    q.active = true; q.one = ab_switch("RNAMPNN_NO_RED_BATCH");
-    q.arena = arena.p; q.floats = arena.floats; q.used = 0; q.s = s; q.b.n = 0; q.blocks = 0;
-}
-bool red_end() {
-    RedQueue& q = g_rq;
-    red_flush();
-    const bool ok = !q.bad;
-    q.active = false; q.bad = false;
-    return ok;
-}
-float* red_alloc(size_t floats) {
-    RedQueue& q = g_rq;
-    const size_t n = (floats + 63) & ~(size_t)63;          // (extents 256-byte aligned)
-    if (!q.active || n > q.floats) { q.bad = true; return nullptr; }
-    if (q.floats - q.used < n) red_flush();
-    float* p = q.arena + q.used;
-    q.used += n;
-    return p;
-}
-
-// rows x [p + r * ld, p + r * ld + width) floats: the partials or one output of a job
-struct RedSpan { const float* p; size_t ld, rows, width; };
-static bool spans_meet(const RedSpan& a, const RedSpan& b) {
-    if (!a.rows || !a.width || !b.rows || !b.width) return false;
-    const long long d = ((intptr_t)b.p - (intptr_t)a.p) / (intptr_t)sizeof(float);
-    const long long ha = (long long)((a.rows - 1) * a.ld + a.width), hb = (long long)((b.rows - 1) * b.ld + b.width);
-    if (d >= ha || -d >= hb) return false;                 // hulls apart
-    if (a.ld != b.ld) return true;
-    // row i of a meets row j of b iff -b.width < d + (j - i) ld < a.width: the least m = j - i above the lower bound decides
-    const long long ld = (long long)a.ld, lo = -(long long)b.width - d;
-    long long m = (lo >= 0 ? lo / ld : -((-lo + ld - 1) / ld)) + 1;
-    if (m < 1 - (long long)a.rows) m = 1 - (long long)a.rows;
-    return m <= (long long)b.rows - 1 && d + m * ld < (long long)a.width;
-}
-static RedSpan part_span(const RedJob& J) { return RedSpan{J.part, J.stride, (size_t)J.nparts, (size_t)J.count}; }
-static RedSpan out_span(const RedJob& J) {             // (wrap: the hull of the wrapped column blocks)
-    const int rows = (J.split_at + J.cols - 1) / J.cols;
-    if (!J.wrap_rows) return RedSpan{J.out, (size_t)J.ld_out, (size_t)rows, (size_t)J.cols_keep};
-    return RedSpan{J.out, (size_t)J.ld_out, (size_t)min(rows, J.wrap_rows), (size_t)((rows - 1) / J.wrap_rows * J.wrap_shift + J.cols_keep)};
-}
-static RedSpan out2_span(const RedJob& J) {
-    const size_t n = J.out2 ? (size_t)min(J.out2_keep, J.count - J.split_at) : 0;
-    return RedSpan{J.out2, n, 1, n};
-}
-static bool outputs_meet(const RedJob& a, const RedJob& b) {
-    const RedSpan sa[2] = {out_span(a), out2_span(a)}, sb[2] = {out_span(b), out2_span(b)};
-    for (const RedSpan& x : sa)
-        for (const RedSpan& y : sb)
-            if (spans_meet(x, y)) return true;
-    return false;
-}
-// records the ordered reduction of nparts partials (part + p * stride)[0 .. count): see k_reduce_batch for the index map
-static void reduce_parts(const float* part, int nparts, size_t stride, int count, int cols, float* out, int ld_out, hipStream_t s,
+void red_launch_batch(const RedBatch& b, int blocks, hipStream_t s) { hipLaunchKernelGGL(k_reduce_batch, dim3(blocks), dim3(256), 0, s, b); }
+// records the ordered reduction of nparts partials (part + p * stride)[0 .. count) that a producer launched on cx.s
+static void reduce_parts(TCall& cx, const float* part, int nparts, size_t stride, int count, int cols, float* out, int ld_out,
                          int split_at = -1, float* out2 = nullptr, int cols_keep = -1, int out2_keep = -1, int wrap_rows = 0, int wrap_shift = 0) {
-    RedQueue& q = g_rq;
-    RedJob J{part, out, out2, stride, nparts, count, cols, ld_out, split_at < 0 ? count : split_at, cols_keep < 0 ? cols : cols_keep,
-             out2_keep < 0 ? count : out2_keep, wrap_rows, wrap_shift, 0};
-    const RedSpan ps = part_span(J);
-    if (!q.active || s != q.s || nparts < 1 || part < q.arena || (size_t)(part - q.arena) + ps.ld * (ps.rows - 1) + ps.width > q.used) {
-        q.bad = true;
-        return;
-    }
-    bool clash = q.b.n == RED_MAX;
-    for (int t = 0; t < q.b.n; ++t) {
-        if (spans_meet(part_span(q.b.j[t]), ps)) { q.bad = true; return; }
-        clash = clash || outputs_meet(q.b.j[t], J);
-    }
-    if (clash) red_launch();                                // (not red_flush: this job's partials stay where they are)
-    J.blk0 = q.blocks;
-    q.b.j[q.b.n++] = J;
-    q.blocks += (count + 63) / 64;
-    if (q.one) red_launch();
+    cx.red.record(RedJob{part, out, out2, stride, nparts, count, cols, ld_out, split_at < 0 ? count : split_at, cols_keep < 0 ? cols : cols_keep,
+                         out2_keep < 0 ? count : out2_keep, wrap_rows, wrap_shift, 0}, cx.s);
 }
 
 // The split count of a producer of partial tiles: one split per min_rows rows, at most `want` (enough workgroups for the chip), hard_max and the
@@ -252,13 +152,13 @@ __global__ void __launch_bounds__(256) k_tgemm_tn(TRows rows, const float* __res
     if (mB < M && kA < K) dst[(size_t)mB * K + kA] = a10;
     if (mB < M && kB < K) dst[(size_t)mB * K + kB] = a11;
 }
-void t_gemm_tn(const TRows& rows, const float* A, int lda, int M, const float* B, int ldb, int K, float* dW, int ldw, hipStream_t s) {
+void t_gemm_tn(const TRows& rows, const float* A, int lda, int M, const float* B, int ldb, int K, float* dW, int ldw, TCall& cx) {
     const size_t mk = (size_t)M * K;
     const RedSplit sp = red_split(rows.maxrows, 2048, 32, LLONG_MAX, 512, red_budget(mk, 0, 0));
-    float* part = red_alloc(sp.n * mk);
+    float* part = cx.red.alloc(sp.n * mk);
     if (!part) return;
-    hipLaunchKernelGGL(k_tgemm_tn, dim3((M + 31) / 32, (K + 31) / 32, sp.n), dim3(256), 0, s, rows, A, lda, M, B, ldb, K, part, sp.rows);
-    reduce_parts(part, sp.n, mk, (int)mk, K, dW, ldw, s);
+    hipLaunchKernelGGL(k_tgemm_tn, dim3((M + 31) / 32, (K + 31) / 32, sp.n), dim3(256), 0, cx.s, rows, A, lda, M, B, ldb, K, part, sp.rows);
+    reduce_parts(cx, part, sp.n, mk, (int)mk, K, dW, ldw);
 }
 
 // out[m] += sum_p A[p][m]   (per-block partial rows, ordered reduction)
@@ -272,13 +172,13 @@ __global__ void __launch_bounds__(256) k_colsum(TRows rows, const float* __restr
         part[(size_t)blockIdx.x * M + m] = s;
     }
 }
-void t_colsum(const TRows& rows, const float* A, int lda, int M, float* out, hipStream_t s) {
+void t_colsum(const TRows& rows, const float* A, int lda, int M, float* out, TCall& cx) {
     const int rpb = std::max(64, red_split(rows.maxrows, 1, 1, LLONG_MAX, 512, red_budget(M, 0, 16)).rows);   // >= 64 rows per block
     const int nb = (rows.maxrows + rpb - 1) / rpb;
-    float* part = red_alloc((size_t)nb * M);
+    float* part = cx.red.alloc((size_t)nb * M);
     if (!part) return;
-    hipLaunchKernelGGL(k_colsum, dim3(nb), dim3(256), 0, s, rows, A, lda, M, part, rpb);
-    reduce_parts(part, nb, (size_t)M, M, M, out, M, s);
+    hipLaunchKernelGGL(k_colsum, dim3(nb), dim3(256), 0, cx.s, rows, A, lda, M, part, rpb);
+    reduce_parts(cx, part, nb, (size_t)M, M, M, out, M);
 }
 
 // element-wise over rows x D (contiguous, ld = D)
@@ -647,22 +547,22 @@ __global__ void __launch_bounds__(256) k_gn_bwd_apply(PackInfo pk, const float* 
     }
 }
 void t_gn_bwd(const PackInfo& pk, const float* x, const float* dy, const float* scale, int t_tot, float* dx, float* dscale,
-              float* dshift, hipStream_t s) {
+              float* dshift, TCall& cx) {
     // per-RNA partials of (dscale, dshift), added in RNA order: B * 256 floats, then the split form's per-split sums
     const int nsplit = (pk.T + GN_SPLIT_ROWS - 1) / GN_SPLIT_ROWS;
     const size_t need = (size_t)pk.B * 256 + (size_t)pk.B * nsplit * 512;
     const bool split = pk.T > GN_SPLIT_T && need <= RED_VIEW;
-    float* part = red_alloc(split ? need : (size_t)pk.B * 256);
+    float* part = cx.red.alloc(split ? need : (size_t)pk.B * 256);
     if (!part) return;
     if (split) {
         float* sums = part + (size_t)pk.B * 256;
-        hipLaunchKernelGGL(k_gn_bwd_sums, dim3(pk.B, 4, nsplit), dim3(256), 0, s, pk, x, dy, nsplit, sums);
-        hipLaunchKernelGGL(k_gn_bwd_apply, dim3(pk.B, 4, nsplit), dim3(256), 0, s, pk, x, dy, scale, t_tot, nsplit, sums, dx, part);
+        hipLaunchKernelGGL(k_gn_bwd_sums, dim3(pk.B, 4, nsplit), dim3(256), 0, cx.s, pk, x, dy, nsplit, sums);
+        hipLaunchKernelGGL(k_gn_bwd_apply, dim3(pk.B, 4, nsplit), dim3(256), 0, cx.s, pk, x, dy, scale, t_tot, nsplit, sums, dx, part);
     } else {
-        hipLaunchKernelGGL(k_gn_bwd, dim3(pk.B, 4), dim3(256), 0, s, pk, x, dy, scale, t_tot, dx, part);
+        hipLaunchKernelGGL(k_gn_bwd, dim3(pk.B, 4), dim3(256), 0, cx.s, pk, x, dy, scale, t_tot, dx, part);
     }
-    if (dscale) reduce_parts(part, pk.B, 256, 128, 128, dscale, 128, s);
-    if (dshift) reduce_parts(part + 128, pk.B, 256, 128, 128, dshift, 128, s);
+    if (dscale) reduce_parts(cx, part, pk.B, 256, 128, 128, dscale, 128);
+    if (dshift) reduce_parts(cx, part + 128, pk.B, 256, 128, 128, dshift, 128);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -952,7 +852,6 @@ struct WImageCache {
     unsigned short* arena = nullptr;
     int cap = 0, synced = 0, built = 0;
 };
-static thread_local WImageCache* g_wimg = nullptr;
 WImageCache* t_wimg_create(int capacity) {
     WImageCache* c = new WImageCache();
     c->cap = capacity;
@@ -966,11 +865,9 @@ WImageCache* t_wimg_create(int capacity) {
 }
 void t_wimg_destroy(WImageCache* c) {
     if (!c) return;
-    if (g_wimg == c) g_wimg = nullptr;
     (void)hipFree(c->dev); (void)hipFree(c->arena);
     delete c;
 }
-void t_wimg_bind(WImageCache* c) { g_wimg = c; }
 int t_wimg_pending(const WImageCache* c) { return c ? (int)c->host.size() - c->built : 0; }
 void t_wimg_clear(WImageCache* c) { if (c) { c->host.clear(); c->synced = 0; c->built = 0; } }
 void t_wimg_refresh(WImageCache* c, hipStream_t s) {
@@ -982,9 +879,8 @@ void t_wimg_refresh(WImageCache* c, hipStream_t s) {
     hipLaunchKernelGGL(k_wimg_build, dim3(c->synced), dim3(256), 0, s, c->dev, c->arena);
     c->built = c->synced;
 }
-// image of (W, ldw, orientation, layout) if the bound cache has built it; unknown blocks are registered for the next refresh
-static const unsigned short* wimg_lookup(const float* W, int ldw, bool b_rows, int layout, int kvalid = 128) {
-    WImageCache* c = g_wimg;
+// image of (W, ldw, orientation, layout) if cache c (may be null) has built it; unknown blocks are registered for the next refresh
+static const unsigned short* wimg_lookup(WImageCache* c, const float* W, int ldw, bool b_rows, int layout, int kvalid = 128) {
     if (!c) return nullptr;
     const int n = (int)c->host.size();
     for (int i = 0; i < n; ++i) {
@@ -1209,44 +1105,44 @@ static bool launch_tmm(bool wt, const TRows& rows, const float* X, int ldx, int 
                        const float* W_hi = nullptr, int k_split = 0);
 // Y = [beta Y] + actA(X) . W^T + bias            (W [N][K] row-major: nn.Linear.weight as it is stored)
 bool tm_gemm_nt(const TRows& rows, const float* X, int ldx, int K, const float* W, int ldw, const float* bias, int N, float* Y,
-                int ldy, int beta, bool actA, const TDrop& dr, unsigned site, hipStream_t s) {
+                int ldy, int beta, bool actA, const TDrop& dr, unsigned site, TCall& cx) {
     if (!mm_ok(X, ldx, K, W, ldw, true)) return false;
     if (K == 128 && N == 128 && ldw % 2 == 0) {
-        hipLaunchKernelGGL(k_mm128<true>, dim3(mm128_grid(rows)), dim3(256), 0, s, rows, X, ldx, W, ldw, bias, Y, ldy, beta,
-                           actA ? 1 : 0, (const float*)nullptr, dr, site, wimg_lookup(W, ldw, true, 0));
+        hipLaunchKernelGGL(k_mm128<true>, dim3(mm128_grid(rows)), dim3(256), 0, cx.s, rows, X, ldx, W, ldw, bias, Y, ldy, beta,
+                           actA ? 1 : 0, (const float*)nullptr, dr, site, wimg_lookup(cx.wimg, W, ldw, true, 0));
         return true;
     }
-    if (launch_tmm(false, rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, actA, nullptr, 0, dr, site, s)) return true;
+    if (launch_tmm(false, rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, actA, nullptr, 0, dr, site, cx.s)) return true;
     // 64-row wave tiles reuse the B fragments twice; with few rows (node tensors) 32-row tiles fill more of the chip
     const bool small = (long long)((rows.maxrows + 255) / 256) * ((N + 127) / 128) < 2 * rn_num_cus();
     if (small) {
         dim3 grid((rows.maxrows + 127) / 128, (N + 127) / 128);
-        hipLaunchKernelGGL((k_mm<true, 1>), grid, dim3(256), 0, s, rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, actA ? 1 : 0,
+        hipLaunchKernelGGL((k_mm<true, 1>), grid, dim3(256), 0, cx.s, rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, actA ? 1 : 0,
                            (const float*)nullptr, 0, dr, site);
     } else {
         dim3 grid((rows.maxrows + 255) / 256, (N + 127) / 128);
-        hipLaunchKernelGGL((k_mm<true, 2>), grid, dim3(256), 0, s, rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, actA ? 1 : 0,
+        hipLaunchKernelGGL((k_mm<true, 2>), grid, dim3(256), 0, cx.s, rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, actA ? 1 : 0,
                            (const float*)nullptr, 0, dr, site);
     }
     return true;
 }
 // Y = [beta Y] + (X . W) [* gelu'(pre) * mask]    (W [K][N] row-major; backward dX = dY . W with W = nn.Linear.weight [out][in])
 bool tm_gemm_nn(const TRows& rows, const float* X, int ldx, int K, const float* W, int ldw, const float* bias, int N, float* Y,
-                int ldy, int beta, const float* epi_pre, int ld_epi, const TDrop& dr, unsigned site, hipStream_t s) {
+                int ldy, int beta, const float* epi_pre, int ld_epi, const TDrop& dr, unsigned site, TCall& cx) {
     if (!mm_ok(X, ldx, K, W, ldw, false)) return false;
     if (K == 128 && N == 128 && (!epi_pre || ld_epi == 128)) {
-        hipLaunchKernelGGL(k_mm128<false>, dim3(mm128_grid(rows)), dim3(256), 0, s, rows, X, ldx, W, ldw, bias, Y, ldy, beta, 0,
-                           epi_pre, dr, site, wimg_lookup(W, ldw, false, 0));
+        hipLaunchKernelGGL(k_mm128<false>, dim3(mm128_grid(rows)), dim3(256), 0, cx.s, rows, X, ldx, W, ldw, bias, Y, ldy, beta, 0,
+                           epi_pre, dr, site, wimg_lookup(cx.wimg, W, ldw, false, 0));
         return true;
     }
-    if (launch_tmm(true, rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, false, epi_pre, ld_epi, dr, site, s)) return true;
+    if (launch_tmm(true, rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, false, epi_pre, ld_epi, dr, site, cx.s)) return true;
     const bool small = (long long)((rows.maxrows + 255) / 256) * ((N + 127) / 128) < 2 * rn_num_cus();
     if (small) {
         dim3 grid((rows.maxrows + 127) / 128, (N + 127) / 128);
-        hipLaunchKernelGGL((k_mm<false, 1>), grid, dim3(256), 0, s, rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, 0, epi_pre, ld_epi, dr, site);
+        hipLaunchKernelGGL((k_mm<false, 1>), grid, dim3(256), 0, cx.s, rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, 0, epi_pre, ld_epi, dr, site);
     } else {
         dim3 grid((rows.maxrows + 255) / 256, (N + 127) / 128);
-        hipLaunchKernelGGL((k_mm<false, 2>), grid, dim3(256), 0, s, rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, 0, epi_pre, ld_epi, dr, site);
+        hipLaunchKernelGGL((k_mm<false, 2>), grid, dim3(256), 0, cx.s, rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, 0, epi_pre, ld_epi, dr, site);
     }
     return true;
 }
@@ -1570,7 +1466,7 @@ __global__ void __launch_bounds__(256) k_mm_tn(TRows rows, const float* __restri
         }
 }
 bool tm_gemm_tn(const TRows& rows, const float* A, int lda, int M, const float* B, int ldb, int K, float* dW, int ldw,
-                bool actB, const TDrop& dr, unsigned site, float* dbias, hipStream_t s) {
+                bool actB, const TDrop& dr, unsigned site, float* dbias, TCall& cx) {
     const size_t mk = (size_t)M * K;
     const int tiles = ((M + 127) / 128) * ((K + 127) / 128);
     const long long cap = red_budget(mk, (size_t)520 * M, 16);
@@ -1579,26 +1475,26 @@ bool tm_gemm_tn(const TRows& rows, const float* A, int lda, int M, const float* 
     const RedSplit sp = red_split(rows.maxrows, 256, 64, (2 * rn_num_cus() + tiles - 1) / tiles, 500, cap);
     // partial of split z: [M*K tile][M column sums (with dbias)]: one ordered reduction adds both into dW / dbias
     const size_t pstride = mk + (dbias ? (size_t)M : 0);
-    float* part = red_alloc(sp.n * pstride);
+    float* part = cx.red.alloc(sp.n * pstride);
     if (!part) return true;                                   // (refused: red_end reports it)
     dim3 grid((M + 127) / 128, (K + 127) / 128, sp.n);
-    hipLaunchKernelGGL(k_mm_tn, grid, dim3(256), 0, s, rows, A, lda, M, B, ldb, K, part, pstride, sp.rows, actB ? 1 : 0, dr, site,
+    hipLaunchKernelGGL(k_mm_tn, grid, dim3(256), 0, cx.s, rows, A, lda, M, B, ldb, K, part, pstride, sp.rows, actB ? 1 : 0, dr, site,
                        dbias ? part + mk : (float*)nullptr);
-    reduce_parts(part, sp.n, pstride, (int)pstride, K, dW, ldw, s, (int)mk, dbias);
+    reduce_parts(cx, part, sp.n, pstride, (int)pstride, K, dW, ldw, (int)mk, dbias);
     return true;
 }
 
 // The node-side weight gradients of a factored first Linear in ONE product: [dWa ; dWb] = [dP | dQ]^T h (256 x 128), db1 = colsum(dP).
 // gw0 = the [128][384] gradient of the Linear's weight ([Wa | Wb | Wc] blocks): rows 0..127 of the product go to columns 0..127, rows
 // 128..255 to columns 128..255 of the same 128 output rows (the reduction's wrap).
-void tm_gemm_tn_pq(const TRows& rows, const float* dpq, const float* h, float* gw0, float* db1, hipStream_t s) {
+void tm_gemm_tn_pq(const TRows& rows, const float* dpq, const float* h, float* gw0, float* db1, TCall& cx) {
     const int M = 256, K = 128;
     const size_t mk = (size_t)M * K, pstride = mk + M;
     const RedSplit sp = red_split(rows.maxrows, 256, 64, rn_num_cus(), LLONG_MAX, red_budget(pstride, 0, 16));   // two 128-row output tiles per split
-    float* part = red_alloc(sp.n * pstride);
+    float* part = cx.red.alloc(sp.n * pstride);
     if (!part) return;
-    hipLaunchKernelGGL(k_mm_tn, dim3(2, 1, sp.n), dim3(256), 0, s, rows, dpq, 256, M, h, 128, K, part, pstride, sp.rows, 0, TDrop{0ull, 0u, 1.f}, 0u, part + mk);
-    reduce_parts(part, sp.n, pstride, (int)pstride, K, gw0, 3 * 128, s, (int)mk, db1, K, 128, 128, 128);
+    hipLaunchKernelGGL(k_mm_tn, dim3(2, 1, sp.n), dim3(256), 0, cx.s, rows, dpq, 256, M, h, 128, K, part, pstride, sp.rows, 0, TDrop{0ull, 0u, 1.f}, 0u, part + mk);
+    reduce_parts(cx, part, sp.n, pstride, (int)pstride, K, gw0, 3 * 128, (int)mk, db1, K, 128, 128, 128);
 }
 // dh += dP . Wa + dQ . Wb as one K = 256 product (w0 = [128][384] weight: Wa = columns 0..127, Wb = columns 128..255)
 bool tm_gemm_nn_pq(const TRows& rows, const float* dpq, const float* w0, float* dh, hipStream_t s) {
@@ -1812,20 +1708,20 @@ __global__ void __launch_bounds__(256, 2) k_emm128(EmmArgs a) {
     }
 }
 bool te_gemm(const TRows& rows, const void* X, bool x_bf16, int ldx, const float* W, int ldw, bool w_rows, const float* bias, tb16* Y,
-             bool actA, const tb16* epi_pre, const EFuse* fuse, const TDrop& dr, unsigned site, hipStream_t s, int kvalid) {
+             bool actA, const tb16* epi_pre, const EFuse* fuse, const TDrop& dr, unsigned site, TCall& cx, int kvalid) {
     EmmArgs a;
     a.rows = rows; a.X = X; a.ldx = ldx; a.W = W; a.ldw = ldw; a.bias = bias; a.Y = Y; a.actA = actA ? 1 : 0;
     a.epi_pre = epi_pre; a.dr = dr; a.site = site;
     if (fuse) a.f = *fuse; else a.f = EFuse{nullptr, nullptr, nullptr, 1, 0, nullptr, nullptr, 0u};
     a.has_pq = a.f.P != nullptr; a.has_res = a.f.res_out != nullptr;
     a.kvalid = kvalid;
-    a.wimg = wimg_lookup(W, ldw, w_rows, 1, kvalid);
+    a.wimg = wimg_lookup(cx.wimg, W, ldw, w_rows, 1, kvalid);
     a.w_yoff = 0; a.Y2 = nullptr; a.wimg2 = nullptr;
     int g = (rows.maxrows + 127) / 128;                      // 4 waves x one 32-row tile each
     const int cap = 2 * rn_num_cus();                        // two workgroups per CU (two waves per SIMD)
     const dim3 grid(g > cap ? cap : (g < 1 ? 1 : g));
     const int ep = a.has_pq ? 1 : (epi_pre ? 2 : 0);
-#define EMM_GO(BR, TXT, EPV, ACTV, RESV) hipLaunchKernelGGL((k_emm128<BR, TXT, EPV, ACTV, RESV>), grid, dim3(256), 0, s, a)
+#define EMM_GO(BR, TXT, EPV, ACTV, RESV) hipLaunchKernelGGL((k_emm128<BR, TXT, EPV, ACTV, RESV>), grid, dim3(256), 0, cx.s, a)
     if (!x_bf16 && w_rows && ep == 0 && !actA && !a.has_res) EMM_GO(true, float, 0, false, false);                 // node rows -> bf16 P / Q tables
     else if (x_bf16 && w_rows && ep == 0 && !actA && !a.has_res) EMM_GO(true, tb16, 0, false, false);             // edge embedding: raw features -> pe1
     else if (x_bf16 && w_rows && ep == 1 && !actA && !a.has_res) EMM_GO(true, tb16, 1, false, false);             // first Linear + P + Q
@@ -1838,16 +1734,16 @@ bool te_gemm(const TRows& rows, const void* X, bool x_bf16, int ldx, const float
 }
 
 // P = h Wa^T + b1 and Q = h Wb^T (bf16 tables [rows][128]) in one launch: w0 = [128][384] weight, Wa = columns 0..127, Wb = columns 128..255
-void te_gemm_pq(const TRows& rows, const float* h, const float* w0, const float* b1, tb16* Pt, tb16* Qt, hipStream_t s) {
+void te_gemm_pq(const TRows& rows, const float* h, const float* w0, const float* b1, tb16* Pt, tb16* Qt, TCall& cx) {
     EmmArgs a;
     a.rows = rows; a.X = h; a.ldx = 128; a.W = w0; a.ldw = 3 * 128; a.bias = b1; a.Y = Pt; a.actA = 0; a.epi_pre = nullptr;
     a.dr = TDrop{0ull, 0u, 1.f}; a.site = 0u;
     a.f = EFuse{nullptr, nullptr, nullptr, 1, 0, nullptr, nullptr, 0u};
     a.has_pq = 0; a.has_res = 0; a.kvalid = 128;
-    a.wimg = wimg_lookup(w0, 3 * 128, true, 1); a.w_yoff = 128; a.Y2 = Qt; a.wimg2 = wimg_lookup(w0 + 128, 3 * 128, true, 1);
+    a.wimg = wimg_lookup(cx.wimg, w0, 3 * 128, true, 1); a.w_yoff = 128; a.Y2 = Qt; a.wimg2 = wimg_lookup(cx.wimg, w0 + 128, 3 * 128, true, 1);
     int g = (rows.maxrows + 127) / 128;
     const int cap = rn_num_cus();
-    hipLaunchKernelGGL((k_emm128<true, float, 0, false, false>), dim3(g > cap ? cap : (g < 1 ? 1 : g), 2), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((k_emm128<true, float, 0, false, false>), dim3(g > cap ? cap : (g < 1 ? 1 : g), 2), dim3(256), 0, cx.s, a);
 }
 
 // ---- the forward of a depth-2 per-edge MLP in ONE kernel: pre1 = e . Wc^T + P[i] + Q[j] ; pre2 = drop(gelu(pre1)) . W2^T + b2 ;
@@ -1988,17 +1884,17 @@ __global__ void __launch_bounds__(256, 2) k_emm_fwd2(Emm2Args a) {
 }
 // pre1 = X . W1^T + P[row / k] + Q[nbr[row]] ; pre2 = drop(gelu(pre1), site) . W2^T + bias2 ; [res_out = X + valid drop(gelu(pre2), site2)]
 void te_mlp2_fwd(const TRows& rows, const tb16* X, const float* W1, int ldw1, const float* W2, int ldw2, const float* bias2, tb16* pre1,
-                 tb16* pre2, const EFuse& f, const TDrop& dr, unsigned site, hipStream_t s) {
+                 tb16* pre2, const EFuse& f, const TDrop& dr, unsigned site, TCall& cx) {
     Emm2Args a;
     a.rows = rows; a.X = X; a.W1 = W1; a.ldw1 = ldw1; a.W2 = W2; a.ldw2 = ldw2; a.bias2 = bias2; a.pre1 = pre1; a.pre2 = pre2; a.f = f;
     a.dr = dr; a.site = site;
-    a.wimg1 = wimg_lookup(W1, ldw1, true, 1); a.wimg2 = wimg_lookup(W2, ldw2, true, 1);
+    a.wimg1 = wimg_lookup(cx.wimg, W1, ldw1, true, 1); a.wimg2 = wimg_lookup(cx.wimg, W2, ldw2, true, 1);
     int g = (rows.maxrows + 127) / 128;
     const int cap = 2 * rn_num_cus();
     const dim3 grid(g > cap ? cap : (g < 1 ? 1 : g));
-    if (f.res_out) hipLaunchKernelGGL((k_emm_fwd2<true, true>), grid, dim3(256), 0, s, a);
-    else if (pre1) hipLaunchKernelGGL((k_emm_fwd2<false, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_emm_fwd2<false, false>), grid, dim3(256), 0, s, a);
+    if (f.res_out) hipLaunchKernelGGL((k_emm_fwd2<true, true>), grid, dim3(256), 0, cx.s, a);
+    else if (pre1) hipLaunchKernelGGL((k_emm_fwd2<false, true>), grid, dim3(256), 0, cx.s, a);
+    else hipLaunchKernelGGL((k_emm_fwd2<false, false>), grid, dim3(256), 0, cx.s, a);
 }
 
 // ---- TN with bf16 operands: dW[n][kk] += sum_m A[m][n] actB(B[m][kk]), M = K = 128.  Same scheme as k_mm_tn (64-row tiles row-major
@@ -2075,15 +1971,15 @@ __global__ void __launch_bounds__(256, 3) k_emm_tn(TRows rows, const tb16* __res
     tn_store(part + (size_t)blockIdx.z * pstride, acc, wr, wc, r, h);
 }
 void te_gemm_tn(const TRows& rows, const tb16* A, const tb16* B, float* dW, int ldw, bool actB, const TDrop& dr,
-                unsigned site, float* dbias, hipStream_t s, int cols_keep) {
+                unsigned site, float* dbias, TCall& cx, int cols_keep) {
     const size_t mk = 128 * 128;
     const RedSplit sp = red_split(rows.maxrows, 1024, 64, 3 * rn_num_cus(), 768, red_budget(mk, 800 * 128, 16));   // three resident workgroups per CU
     const size_t pstride = mk + (dbias ? 128 : 0);
-    float* part = red_alloc(sp.n * pstride);
+    float* part = cx.red.alloc(sp.n * pstride);
     if (!part) return;
-    hipLaunchKernelGGL(k_emm_tn, dim3(1, 1, sp.n), dim3(256), 0, s, rows, A, B, part, pstride, sp.rows, actB ? 1 : 0, dr, site,
+    hipLaunchKernelGGL(k_emm_tn, dim3(1, 1, sp.n), dim3(256), 0, cx.s, rows, A, B, part, pstride, sp.rows, actB ? 1 : 0, dr, site,
                        dbias ? part + mk : (float*)nullptr);
-    reduce_parts(part, sp.n, pstride, (int)pstride, 128, dW, ldw, s, (int)mk, dbias, cols_keep);
+    reduce_parts(cx, part, sp.n, pstride, (int)pstride, 128, dW, ldw, (int)mk, dbias, cols_keep);
 }
 
 // ---- the two kernels that consume d pre2 of a depth-2 per-edge MLP, fused: dW2 += dpre2^T a1, db2 += colsum(dpre2) (k_emm_tn with
@@ -2301,15 +2197,14 @@ __global__ void __launch_bounds__(256, 2) k_emm_bwd1(TRows rows, const tb16* __r
     tn_store(part + (size_t)blockIdx.z * pstride, acc, wr, wc, r, h);
 }
 // dW[128][ldw_out] += dY^T X,  DE += dY . W       (W [128 out][ldw]: the Wc block of a first Linear)
-void te_gemm_bwd1(const TRows& rows, const tb16* dY, const tb16* X, tb16* DE, const float* W, int ldw, float* dW, int ldw_out,
-                  hipStream_t s) {
+void te_gemm_bwd1(const TRows& rows, const tb16* dY, const tb16* X, tb16* DE, const float* W, int ldw, float* dW, int ldw_out, TCall& cx) {
     const size_t mk = 128 * 128;
     // >= 8 tiles per workgroup; fills the chip from ~130 K rows on
     const RedSplit sp = red_split(rows.maxrows, 512, 64, 2 * rn_num_cus(), LLONG_MAX, red_budget(mk, 800 * 128, 16));
-    float* part = red_alloc(sp.n * mk);
+    float* part = cx.red.alloc(sp.n * mk);
     if (!part) return;
-    hipLaunchKernelGGL(k_emm_bwd1, dim3(1, 1, sp.n), dim3(256), 0, s, rows, dY, X, DE, W, ldw, wimg_lookup(W, ldw, false, 1), part, mk, sp.rows);
-    reduce_parts(part, sp.n, mk, (int)mk, 128, dW, ldw_out, s);
+    hipLaunchKernelGGL(k_emm_bwd1, dim3(1, 1, sp.n), dim3(256), 0, cx.s, rows, dY, X, DE, W, ldw, wimg_lookup(cx.wimg, W, ldw, false, 1), part, mk, sp.rows);
+    reduce_parts(cx, part, sp.n, mk, (int)mk, 128, dW, ldw_out);
 }
 // ---- the first-Linear backward of the TWO per-edge MLPs of a layer that share their input e (edge update and message MLP, mpnn.py:212-262) in one
 // pass: dW1 += dY1^T e, dW2 += dY2^T e, dE += dY1 . W1 + dY2 . W2.  As two k_emm_bwd1 launches e and dE are read twice and dE is written twice
@@ -2414,32 +2309,32 @@ __global__ void __launch_bounds__(512, 1) k_emm_bwd1x2(TRows rows, const tb16* _
 }
 // dW1[128][ldw_out] += dY1^T X, dW2 += dY2^T X, DE += dY1 . W1 + dY2 . W2      (W1, W2 [128 out][ldw]: the Wc blocks of the two first Linears)
 void te_gemm_bwd1x2(const TRows& rows, const tb16* dY1, const tb16* dY2, const tb16* X, tb16* DE, const float* W1, const float* W2, int ldw,
-                    float* dW1, float* dW2, int ldw_out, hipStream_t s) {
+                    float* dW1, float* dW2, int ldw_out, TCall& cx) {
     const size_t mk = 128 * 128, pstride = 2 * mk;
     // >= 16 tiles per workgroup, one 8-wave workgroup per CU (127 KiB of LDS)
     const RedSplit sp = red_split(rows.maxrows, 1024, 64, rn_num_cus(), LLONG_MAX, red_budget(pstride, 800 * 128, 16));
-    float* part = red_alloc(sp.n * pstride);
+    float* part = cx.red.alloc(sp.n * pstride);
     if (!part) return;
-    hipLaunchKernelGGL(k_emm_bwd1x2, dim3(1, 1, sp.n), dim3(512), 0, s, rows, dY1, dY2, X, DE, W1, W2, ldw, wimg_lookup(W1, ldw, false, 1),
-                       wimg_lookup(W2, ldw, false, 1), part, pstride, sp.rows);
-    reduce_parts(part, sp.n, pstride, (int)mk, 128, dW1, ldw_out, s);
-    reduce_parts(part + mk, sp.n, pstride, (int)mk, 128, dW2, ldw_out, s);
+    hipLaunchKernelGGL(k_emm_bwd1x2, dim3(1, 1, sp.n), dim3(512), 0, cx.s, rows, dY1, dY2, X, DE, W1, W2, ldw, wimg_lookup(cx.wimg, W1, ldw, false, 1),
+                       wimg_lookup(cx.wimg, W2, ldw, false, 1), part, pstride, sp.rows);
+    reduce_parts(cx, part, sp.n, pstride, (int)mk, 128, dW1, ldw_out);
+    reduce_parts(cx, part + mk, sp.n, pstride, (int)mk, 128, dW2, ldw_out);
 }
 // dW[128][ldw_out] += dY^T drop(gelu(PRE)), dbias += colsum(dY), DX = (dY . W) gelu'(PRE) mask        (W [128 out][ldw] as nn.Linear stores it)
 void te_gemm_bwd2(const TRows& rows, const tb16* dY, const tb16* PRE, tb16* DX, const float* W, int ldw, float* dW, int ldw_out,
-                  const TDrop& dr, float* dbias, hipStream_t s, const EBwd2Src& from) {
+                  const TDrop& dr, float* dbias, TCall& cx, const EBwd2Src& from) {
     const size_t mk = 128 * 128;
     // >= 8 tiles per workgroup (fills the chip from ~130 K rows on), two resident workgroups per CU (72 KiB of LDS each)
     const RedSplit sp = red_split(rows.maxrows, 512, 64, 2 * rn_num_cus(), LLONG_MAX, red_budget(mk, 800 * 128, 16));
     const size_t pstride = mk + (dbias ? 128 : 0);
-    float* part = red_alloc(sp.n * pstride);
+    float* part = cx.red.alloc(sp.n * pstride);
     if (!part) return;
     const Bwd2Src src{from.pre2, from.nbr, from.dagg, from.inv_cnt, from.k};
-#define BWD2_GO(M) hipLaunchKernelGGL(k_emm_bwd2<M>, dim3(1, 1, sp.n), dim3(256), 0, s, rows, dY, PRE, DX, W, ldw, wimg_lookup(W, ldw, false, 1), \
+#define BWD2_GO(M) hipLaunchKernelGGL(k_emm_bwd2<M>, dim3(1, 1, sp.n), dim3(256), 0, cx.s, rows, dY, PRE, DX, W, ldw, wimg_lookup(cx.wimg, W, ldw, false, 1), \
                                        part, pstride, sp.rows, dr, dbias ? part + mk : (float*)nullptr, src)
     if (from.mode == 1) BWD2_GO(1); else BWD2_GO(2);
 #undef BWD2_GO
-    reduce_parts(part, sp.n, pstride, (int)pstride, 128, dW, ldw_out, s, (int)mk, dbias);
+    reduce_parts(cx, part, sp.n, pstride, (int)pstride, 128, dW, ldw_out, (int)mk, dbias);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -402,7 +402,7 @@ extern "C" size_t rdesign_workspace_bytes(rdesign_handle h, int32_t B, int32_t T
 
 RdRun rd_run(rdesign_ctx* c, void* stream, bool mixed, const RdWs& w, int B, int T) {
     RdRun r;
-    r.c = c; r.s = (hipStream_t)stream; r.mixed = mixed; r.nodrop = TDrop{0ull, 0u, 1.f, nullptr}; r.K = c->cfg.k_neighbors; r.w = w;
+    r.c = c; r.cx.s = (hipStream_t)stream; r.mixed = mixed; r.nodrop = TDrop{0ull, 0u, 1.f, nullptr}; r.K = c->cfg.k_neighbors; r.w = w;
     r.pk.len = w.len; r.pk.cu = w.cu; r.pk.node_b = w.node_b; r.pk.B = B; r.pk.T = T; r.pk.Nmax = B * T; r.pk.packed_in = 0;
     return r;
 }
@@ -410,11 +410,11 @@ void rd_mm(RdRun& r, const TRows& rows, const float* X, int ldx, const RdLin& l,
            bool gelu_in, float* scratch, const TDrop& dr, unsigned site) {
     rdesign_ctx* c = r.c;
     const float* bias = use_bias ? rdp(c, l.b) : nullptr;
-    if (r.mixed && tm_gemm_nt(rows, X, ldx, Kc, rdp(c, l.w) + k0, l.in, bias, l.out, Y, ldy, beta, gelu_in, dr, site, r.s)) return;
+    if (r.mixed && tm_gemm_nt(rows, X, ldx, Kc, rdp(c, l.w) + k0, l.in, bias, l.out, Y, ldy, beta, gelu_in, dr, site, r.cx)) return;
     const float* xin = X;
-    if (gelu_in) { t_gelu_fwd(rows, X, scratch, ldx, dr, site, r.s); xin = scratch; }
+    if (gelu_in) { t_gelu_fwd(rows, X, scratch, ldx, dr, site, r.cx.s); xin = scratch; }
     const int Kp = (Kc + 3) / 4 * 4;
-    t_gemm(rows, xin, ldx, Kp, c->der + l.wt + (size_t)k0 * l.out, l.out, bias, l.out, Y, ldy, beta, r.s);
+    t_gemm(rows, xin, ldx, Kp, c->der + l.wt + (size_t)k0 * l.out, l.out, bias, l.out, Y, ldy, beta, r.cx.s);
 }
 
 __global__ void __launch_bounds__(256) k_rd_copy_rows(const int* __restrict__ ntot, int mul, const float* __restrict__ src, int ld_src,
@@ -435,7 +435,7 @@ void rd_copy_rows(const int* ntot, int mul, size_t maxrows, const float* src, in
 size_t rd_knn_lds_bytes(int T) { return (size_t)(3 + 4) * T * sizeof(float); }
 void rd_front(RdRun& r, const float* X, const float* mask, int64_t* edge_index) {
     RdWs& w = r.w;
-    hipStream_t s = r.s;
+    hipStream_t s = r.cx.s;
     const int B = r.pk.B, T = r.pk.T, K = r.K;
     const size_t Nmax = (size_t)r.pk.Nmax, knn_lds = rd_knn_lds_bytes(T);
     launch_lengths(mask, r.pk, s);
@@ -472,11 +472,11 @@ extern "C" int rdesign_forward(rdesign_handle h, const float* X, const float* ma
     rd_carve(c, B, Nmax, (char*)ws, &carved);
     RdRun r = rd_run(c, stream, c->cfg.precision == RDESIGN_PREC_BF16, carved, B, T);
     RdWs& w = r.w;
-    hipStream_t s = r.s;
+    hipStream_t s = r.cx.s;
     if (r.mixed) {      // weights are static between finalize calls: the images are rebuilt once, blocks first seen in this call build their own
         if (!c->wimg) c->wimg = t_wimg_create(256);
         if (c->wimg && (!c->wimg_fresh || t_wimg_pending(c->wimg) > 0)) { t_wimg_refresh(c->wimg, s); c->wimg_fresh = true; }
-        t_wimg_bind(c->wimg);
+        r.cx.wimg = c->wimg;
     }
     rd_front(r, X, mask, edge_index);
     // the packed outputs are copied by row count N, known to the device only: rows >= N of the caller's tensors stay untouched (a copy of Nmax rows
@@ -495,20 +495,20 @@ extern "C" int rdesign_forward(rdesign_handle h, const float* X, const float* ma
             tb16* Pt = reinterpret_cast<tb16*>(w.pq);
             tb16* Qt = Pt + (Nmax + 1) * RD_H;
             const float* w0 = rdp(c, L.msg[0].w);                                                            // [128][384] = [W_e | W_centre | W_neighbour]
-            r.bad |= !te_gemm(r.rn(), w.hV, false, RD_H, w0 + RD_H, 3 * RD_H, true, rdp(c, L.msg[0].b), Pt, false, nullptr, nullptr, r.nodrop, 0u, s);
-            r.bad |= !te_gemm(r.rn(), w.hV, false, RD_H, w0 + 2 * RD_H, 3 * RD_H, true, nullptr, Qt, false, nullptr, nullptr, r.nodrop, 0u, s);
+            r.bad |= !te_gemm(r.rn(), w.hV, false, RD_H, w0 + RD_H, 3 * RD_H, true, rdp(c, L.msg[0].b), Pt, false, nullptr, nullptr, r.nodrop, 0u, r.cx);
+            r.bad |= !te_gemm(r.rn(), w.hV, false, RD_H, w0 + 2 * RD_H, 3 * RD_H, true, nullptr, Qt, false, nullptr, nullptr, r.nodrop, 0u, r.cx);
             EFuse f{Pt, Qt, w.nbr, K, (int)Nmax, nullptr, nullptr, 0u};
             tb16* cur = reinterpret_cast<tb16*>(w.E1);
             tb16* nxt = reinterpret_cast<tb16*>(w.E2);
             size_t first = 1;
             if (L.msg.size() >= 2) {      // Linears 0 and 1 in one kernel: the hidden activation stays in registers, only the second pre-activation is written
-                te_mlp2_fwd(r.re(), reinterpret_cast<const tb16*>(w.hE), w0, 3 * RD_H, rdp(c, L.msg[1].w), RD_H, rdp(c, L.msg[1].b), nullptr, cur, f, r.nodrop, 0u, s);
+                te_mlp2_fwd(r.re(), reinterpret_cast<const tb16*>(w.hE), w0, 3 * RD_H, rdp(c, L.msg[1].w), RD_H, rdp(c, L.msg[1].b), nullptr, cur, f, r.nodrop, 0u, r.cx);
                 first = 2;
             } else {
-                r.bad |= !te_gemm(r.re(), w.hE, true, RD_H, w0, 3 * RD_H, true, nullptr, cur, false, nullptr, &f, r.nodrop, 0u, s);
+                r.bad |= !te_gemm(r.re(), w.hE, true, RD_H, w0, 3 * RD_H, true, nullptr, cur, false, nullptr, &f, r.nodrop, 0u, r.cx);
             }
             for (size_t i = first; i < L.msg.size(); ++i) {
-                r.bad |= !te_gemm(r.re(), cur, true, RD_H, rdp(c, L.msg[i].w), RD_H, true, rdp(c, L.msg[i].b), nxt, true, nullptr, nullptr, r.nodrop, 0u, s);
+                r.bad |= !te_gemm(r.re(), cur, true, RD_H, rdp(c, L.msg[i].w), RD_H, true, rdp(c, L.msg[i].b), nxt, true, nullptr, nullptr, r.nodrop, 0u, r.cx);
                 tb16* t = cur; cur = nxt; nxt = t;
             }
             hipLaunchKernelGGL(k_rd_segsum_b, dim3((unsigned)((Nmax + 3) / 4)), dim3(256), 0, s, r.pk, K, w.nbr, cur, 1.0f / 30.0f, w.dh);
@@ -550,7 +550,6 @@ extern "C" int rdesign_forward(rdesign_handle h, const float* X, const float* ma
             x = dst; ld = c->readout[i].out;
         }
     }
-    t_wimg_bind(nullptr);
     if (r.bad) return rd_fail(RDESIGN_ERR_UNSUPPORTED, "bf16 path: a GEMM variant this configuration needs is not built");
     if (h_V) rd_copy_rows(r.pk.cu + B, 1, Nmax, w.hV, RD_H, h_V, RD_H, RD_H, s);
     if (logits) rd_copy_rows(r.pk.cu + B, 1, Nmax, w.logits, 4, logits, 4, 4, s);
@@ -568,7 +567,7 @@ extern "C" int rdesign_readout(rdesign_handle h, const float* h_V, int32_t n_row
     RdWs carved;
     rd_carve(h, 1, (size_t)n_rows, (char*)ws, &carved, false);
     RdRun r = rd_run(h, stream, h->cfg.precision == RDESIGN_PREC_BF16, carved, 1, n_rows);
-    hipLaunchKernelGGL(k_rd_seti, dim3(1), dim3(1), 0, r.s, r.w.cu + 1, (int)n_rows);
+    hipLaunchKernelGGL(k_rd_seti, dim3(1), dim3(1), 0, r.cx.s, r.w.cu + 1, (int)n_rows);
     const float* x = h_V;
     int ld = RD_H;
     float* bufs[2] = {r.w.dA, r.w.dB};

@@ -45,10 +45,11 @@ struct RdWs {
 };
 size_t rd_carve(const rdesign_ctx* c, int B, size_t Nmax, char* base, RdWs* w, bool edges = true);
 
-struct RdRun { rdesign_ctx* c; PackInfo pk; RdWs w; hipStream_t s; bool mixed; TDrop nodrop; int K; bool bad = false;
+struct RdRun { rdesign_ctx* c; PackInfo pk; RdWs w; TCall cx; bool mixed; TDrop nodrop; int K; bool bad = false;
     TRows rn() const { return TRows{pk.cu + pk.B, 1, pk.Nmax}; }
     TRows re() const { return TRows{pk.cu + pk.B, K, pk.Nmax * K}; } };
-// the run over a carved workspace: stream, precision, the no-dropout TDrop, K and the PackInfo of B x T padded rows on w's length tables
+// the run over a carved workspace: the call context (its stream; the bf16 callers hand it the handle's weight-image cache), precision, the
+// no-dropout TDrop, K and the PackInfo of B x T padded rows on w's length tables
 RdRun rd_run(rdesign_ctx* c, void* stream, bool mixed, const RdWs& w, int B, int T);
 // One node-level Linear, one dispatch per GEMM: the MFMA form (tm_gemm_*) when r.mixed and the shape is covered, otherwise the f32 blocks.
 // Y = [beta Y] + [drop(gelu(] X[:, 0:Kc] [))] . W[:, k0:k0+Kc]^T [+ b]; f32 form: t_gelu_fwd into `scratch` (may be X itself where X is not a taped
@@ -117,8 +118,9 @@ void rdt_ffn_fwd(RdtStep& t, const std::vector<RdLin>& lin, const float* x, cons
 void rdt_ffn_bwd(RdtStep& t, const std::vector<RdLin>& lin, const float* x, const std::vector<float*>& pre, const float* dy, float* dx, bool acc,
                  unsigned site0);
 void rdt_node_emb_bwd(RdtStep& t);                                 // w.gX = d (node embedding Linear output): the 101-input Linear's dW, db
-// between forward and backward: logits copy-out (the N valid rows), loss and w.dlogits, zeroed gradient, red_begin;  rdt_end: red_end
+// between forward and backward: logits copy-out (the N valid rows), loss and w.dlogits, zeroed gradient, red_begin on the
+// queue of the step's own context (t.r.cx);  rdt_end: red_end of that queue
 void rdt_loss(RdtStep& t, const RdtArgs& a);
-int rdt_end(const char* who);
+int rdt_end(RdtStep& t, const char* who);
 // the bf16-mixed step (rdesign_train_bf16.hip); sizes != null: no launch, sizes[0] = workspace bytes, sizes[1] = tape bytes
 int rdb_step(rdesign_handle h, const RdtArgs& a, size_t* sizes);

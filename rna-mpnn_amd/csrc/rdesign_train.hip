@@ -186,17 +186,17 @@ int rdt_begin(RdtStep& t, rdesign_handle h, const RdtArgs& a, bool mixed, size_t
 void rd_mm_wb(RdRun& r, const TRows& rows, const float* dy, const RdLin& l, const float* x, bool act, float* scratch, const TDrop& dr, unsigned site,
               float* grad) {
     float *dW = grad + r.c->raw[l.w].off, *db = grad + r.c->raw[l.b].off;
-    if (r.mixed && tm_gemm_tn(rows, dy, l.out, l.out, x, l.in, l.in, dW, l.in, act, dr, site, db, r.s)) return;
-    if (act) { t_gelu_fwd(rows, x, scratch, l.in, dr, site, r.s); x = scratch; }
-    t_gemm_tn(rows, dy, l.out, l.out, x, l.in, l.in, dW, l.in, r.s);
-    t_colsum(rows, dy, l.out, l.out, db, r.s);
+    if (r.mixed && tm_gemm_tn(rows, dy, l.out, l.out, x, l.in, l.in, dW, l.in, act, dr, site, db, r.cx)) return;
+    if (act) { t_gelu_fwd(rows, x, scratch, l.in, dr, site, r.cx.s); x = scratch; }
+    t_gemm_tn(rows, dy, l.out, l.out, x, l.in, l.in, dW, l.in, r.cx);
+    t_colsum(rows, dy, l.out, l.out, db, r.cx);
 }
 void rd_mm_dx(RdRun& r, const TRows& rows, const float* dy, const RdLin& l, float* dx, int beta, const float* pre, float* scratch, const TDrop& dr,
               unsigned site) {
     const float* W = rdp(r.c, l.w);          // as nn.Linear stores it, [out][in]: K-major for this product
-    if (r.mixed && tm_gemm_nn(rows, dy, l.out, l.out, W, l.in, nullptr, l.in, dx, l.in, beta, pre, l.in, dr, site, r.s)) return;
-    t_gemm(rows, dy, l.out, l.out, W, l.in, nullptr, l.in, pre ? scratch : dx, l.in, pre ? 0 : beta, r.s);
-    if (pre) t_gelu_bwd(rows, scratch, pre, dx, l.in, dr, site, r.s);
+    if (r.mixed && tm_gemm_nn(rows, dy, l.out, l.out, W, l.in, nullptr, l.in, dx, l.in, beta, pre, l.in, dr, site, r.cx)) return;
+    t_gemm(rows, dy, l.out, l.out, W, l.in, nullptr, l.in, pre ? scratch : dx, l.in, pre ? 0 : beta, r.cx.s);
+    if (pre) t_gelu_bwd(rows, scratch, pre, dx, l.in, dr, site, r.cx.s);
 }
 void rdt_ffn_fwd(RdtStep& t, const std::vector<RdLin>& lin, const float* x, const std::vector<float*>& pre, float* out, unsigned site0) {
     const int n = (int)lin.size();
@@ -219,18 +219,18 @@ void rdt_ffn_bwd(RdtStep& t, const std::vector<RdLin>& lin, const float* x, cons
 }
 void rdt_node_emb_bwd(RdtStep& t) {         // 101 inputs: the f32 blocks in both precisions (nothing flows into the raw features)
     const rdesign_ctx* c = t.r.c;
-    t_gemm_tn(t.r.rn(), t.w.gX, RD_H, RD_H, t.w.f.node_raw, RD_NODEP, RD_NODE, t.G(c->node_emb.w), RD_NODE, t.r.s);
-    t_colsum(t.r.rn(), t.w.gX, RD_H, RD_H, t.G(c->node_emb.b), t.r.s);
+    t_gemm_tn(t.r.rn(), t.w.gX, RD_H, RD_H, t.w.f.node_raw, RD_NODEP, RD_NODE, t.G(c->node_emb.w), RD_NODE, t.r.cx);
+    t_colsum(t.r.rn(), t.w.gX, RD_H, RD_H, t.G(c->node_emb.b), t.r.cx);
 }
 void rdt_loss(RdtStep& t, const RdtArgs& a) {
     const PackInfo& pk = t.r.pk;
-    if (a.logits) rd_copy_rows(pk.cu + pk.B, 1, pk.Nmax, t.w.logits, 4, a.logits, 4, 4, t.r.s);      // rows >= N of the caller's tensor stay untouched
-    rdt_ce_loss(pk, t.w.logits, a.labels, t.w.dlogits, t.w.part, a.loss, t.r.s);
-    launch_zero_bytes(t.grad, t.r.c->raw_floats * sizeof(float), t.r.s);
-    red_begin(t.w.sc, t.r.s);
+    if (a.logits) rd_copy_rows(pk.cu + pk.B, 1, pk.Nmax, t.w.logits, 4, a.logits, 4, 4, t.r.cx.s);      // rows >= N of the caller's tensor stay untouched
+    rdt_ce_loss(pk, t.w.logits, a.labels, t.w.dlogits, t.w.part, a.loss, t.r.cx.s);
+    launch_zero_bytes(t.grad, t.r.c->raw_floats * sizeof(float), t.r.cx.s);
+    red_begin(t.r.cx, t.w.sc);
 }
-int rdt_end(const char* who) {
-    return red_end() ? RDESIGN_OK : rd_fail(RDESIGN_ERR_HIP, "%s: an ordered reduction was refused (reduction arena)", who);
+int rdt_end(RdtStep& t, const char* who) {
+    return red_end(t.r.cx) ? RDESIGN_OK : rd_fail(RDESIGN_ERR_HIP, "%s: an ordered reduction was refused (reduction arena)", who);
 }
 
 // ------------------------------------------------------------------------------------------ the exact-f32 step: edge sequence around the node side
@@ -259,7 +259,7 @@ int rdt_f32_step(rdesign_handle h, const RdtArgs& a, size_t* sizes) {
     rdesign_ctx* c = h;
     RdRun& r = t.r;
     RdtWs& w = t.w;
-    hipStream_t s = r.s;
+    hipStream_t s = r.cx.s;
     const PackInfo& pk = r.pk;
     const int K = r.K, L = t.L, M = t.M;
     const int* ntot = pk.cu + pk.B;
@@ -312,13 +312,13 @@ int rdt_f32_step(rdesign_handle h, const RdtArgs& a, size_t* sizes) {
         const std::vector<float*>& msg = e.msg[l];
         // norm2(h1 + y)
         rdt_rownorm_bwd(ntot, 1, Nmax, tl.h1, tl.y, w.gH, rdp(c, Lw.n2w), 1, w.gX, w.bA, s);
-        t_colsum(rn, w.bA, RD_H, RD_H, t.G(Lw.n2w), s);
-        t_colsum(rn, w.gH, RD_H, RD_H, t.G(Lw.n2b), s);
+        t_colsum(rn, w.bA, RD_H, RD_H, t.G(Lw.n2w), r.cx);
+        t_colsum(rn, w.gH, RD_H, RD_H, t.G(Lw.n2b), r.cx);
         rdt_ffn_bwd(t, Lw.dense, tl.h1, tl.dense, w.gX, w.gX, true, t.site_dense(l, 0));     // w.gX is both d y and the residual part of d h1
         // norm1(h_V + dh): w.gH <- d (h_V + dh)
         rdt_rownorm_bwd(ntot, 1, Nmax, w.hv[l], tl.dh, w.gX, rdp(c, Lw.n1w), 1, w.gH, w.bA, s);
-        t_colsum(rn, w.bA, RD_H, RD_H, t.G(Lw.n1w), s);
-        t_colsum(rn, w.gX, RD_H, RD_H, t.G(Lw.n1b), s);
+        t_colsum(rn, w.bA, RD_H, RD_H, t.G(Lw.n1w), r.cx);
+        t_colsum(rn, w.gX, RD_H, RD_H, t.G(Lw.n1b), r.cx);
         // segment sum, then the message Linears M-1 .. 1: dW, db from GELU(pre[i-1]) in e.eS; d pre[i-1] through w.f.E2, in place of d pre[i]
         float* dpre = w.f.E1;
         hipLaunchKernelGGL(k_rdt_segsum_bwd, dim3(seg_grid), dim3(128), 0, s, pk, K, w.f.nbr, w.gH, msg[M - 1], inv_scale, dpre, dr, t.site_msg(l, M - 1));
@@ -328,26 +328,26 @@ int rdt_f32_step(rdesign_handle h, const RdtArgs& a, size_t* sizes) {
         }
         // factored first Linear: pre0 = W_e h_E + (W_c h_V + b)[centre] + (W_n h_V)[neighbour]
         const RdLin& l0 = Lw.msg[0];
-        t_gemm_tn(re, dpre, RD_H, RD_H, w.f.hE, RD_H, RD_H, t.G(l0.w), 3 * RD_H, s);                          // dW_e
+        t_gemm_tn(re, dpre, RD_H, RD_H, w.f.hE, RD_H, RD_H, t.G(l0.w), 3 * RD_H, r.cx);                       // dW_e
         dx0(re, dpre, RD_H, l0, 0, e.dhE, l == L - 1 ? 0 : 1);                                                // d h_E (shared by all layers)
         t_edge_pq_bwd(pk, K, dpre, w.rstart, w.rlist, w.f.pq, s);                                             // dP = own slots, dQ = gather over the reverse adjacency
-        t_colsum(rn, w.f.pq, 256, RD_H, t.G(l0.b), s);                                                        // db (the bias rides in P)
-        t_gemm_tn(rn, w.f.pq, 256, RD_H, w.hv[l], RD_H, RD_H, t.G(l0.w) + RD_H, 3 * RD_H, s);                 // dW_c
-        t_gemm_tn(rn, w.f.pq + RD_H, 256, RD_H, w.hv[l], RD_H, RD_H, t.G(l0.w) + 2 * RD_H, 3 * RD_H, s);      // dW_n
+        t_colsum(rn, w.f.pq, 256, RD_H, t.G(l0.b), r.cx);                                                     // db (the bias rides in P)
+        t_gemm_tn(rn, w.f.pq, 256, RD_H, w.hv[l], RD_H, RD_H, t.G(l0.w) + RD_H, 3 * RD_H, r.cx);              // dW_c
+        t_gemm_tn(rn, w.f.pq + RD_H, 256, RD_H, w.hv[l], RD_H, RD_H, t.G(l0.w) + 2 * RD_H, 3 * RD_H, r.cx);   // dW_n
         dx0(rn, w.f.pq, 256, l0, RD_H, w.gH, 1);                                                              // d h_V += dP W_c + dQ W_n
         dx0(rn, w.f.pq + RD_H, 256, l0, 2 * RD_H, w.gH, 1);
     }
     // ---- embeddings: Normalize backward, then the 101- / 115-input Linears (nothing flows into the raw features)
     rdt_rownorm_bwd(ntot, 1, Nmax, w.embN, nullptr, w.gH, rdp(c, c->nn_g), 0, w.gX, w.bA, s);
-    t_colsum(rn, w.bA, RD_H, RD_H, t.G(c->nn_g), s);
-    t_colsum(rn, w.gH, RD_H, RD_H, t.G(c->nn_b), s);
+    t_colsum(rn, w.bA, RD_H, RD_H, t.G(c->nn_g), r.cx);
+    t_colsum(rn, w.gH, RD_H, RD_H, t.G(c->nn_b), r.cx);
     rdt_node_emb_bwd(t);
     rdt_rownorm_bwd(ntot, K, Nmax * K, e.embE, nullptr, e.dhE, rdp(c, c->ne_g), 0, w.f.E1, e.eS, s);
-    t_colsum(re, e.eS, RD_H, RD_H, t.G(c->ne_g), s);
-    t_colsum(re, e.dhE, RD_H, RD_H, t.G(c->ne_b), s);
-    t_gemm_tn(re, w.f.E1, RD_H, RD_H, w.f.edge_raw, RD_EDGEP, RD_EDGE, t.G(c->edge_emb.w), RD_EDGE, s);
-    t_colsum(re, w.f.E1, RD_H, RD_H, t.G(c->edge_emb.b), s);
-    if (const int rc = rdt_end(who)) return rc;
+    t_colsum(re, e.eS, RD_H, RD_H, t.G(c->ne_g), r.cx);
+    t_colsum(re, e.dhE, RD_H, RD_H, t.G(c->ne_b), r.cx);
+    t_gemm_tn(re, w.f.E1, RD_H, RD_H, w.f.edge_raw, RD_EDGEP, RD_EDGE, t.G(c->edge_emb.w), RD_EDGE, r.cx);
+    t_colsum(re, w.f.E1, RD_H, RD_H, t.G(c->edge_emb.b), r.cx);
+    if (const int rc = rdt_end(t, who)) return rc;
     RD_TRY(hipGetLastError());
     return RDESIGN_OK;
 }

@@ -226,7 +226,7 @@ int rdb_step(rdesign_handle h, const RdtArgs& a, size_t* sizes) {
     rdesign_ctx* c = h;
     RdRun& r = t.r;
     RdtWs& w = t.w;
-    hipStream_t s = r.s;
+    hipStream_t s = r.cx.s;
     const PackInfo& pk = r.pk;
     const int K = r.K, L = t.L, M = t.M;
     const int* ntot = pk.cu + pk.B;
@@ -238,7 +238,7 @@ int rdb_step(rdesign_handle h, const RdtArgs& a, size_t* sizes) {
     // the weights change every step: every fragment image registered so far is rebuilt from the arena, blocks first seen in this call build their own
     if (!c->wimg) c->wimg = t_wimg_create(256);
     if (c->wimg) { t_wimg_refresh(c->wimg, s); c->wimg_fresh = true; }
-    t_wimg_bind(c->wimg);
+    r.cx.wimg = c->wimg;
     const unsigned seg_grid = (unsigned)((Nmax + 3) / 4);
     // row-normalisation backward with the parameter gradients: fixed-order partials per block, then one block adds them in order
     auto norm_bwd = [&](bool edge, const void* x, const float* res, const float* dy, int gain_i, int bias_i, int mode, void* dx) {
@@ -258,7 +258,7 @@ int rdb_step(rdesign_handle h, const RdtArgs& a, size_t* sizes) {
     rd_rownorm(ntot, 1, Nmax, w.embN, nullptr, rdp(c, c->nn_g), rdp(c, c->nn_b), 0, w.hv[0], s);
     // edge embedding (115 inputs) on the MFMA edge GEMM + Normalize, bf16 rows
     hipLaunchKernelGGL(k_rdb_eraw16, dim3(ew_grid(Emax * 16)), dim3(256), 0, s, ntot, K, w.f.edge_raw, e.eraw);
-    bad |= !te_gemm(re, e.eraw, true, RD_H, rdp(c, c->edge_emb.w), RD_EDGE, true, rdp(c, c->edge_emb.b), e.embE, false, nullptr, nullptr, nodrop, 0u, s, RD_EDGE);
+    bad |= !te_gemm(re, e.eraw, true, RD_H, rdp(c, c->edge_emb.w), RD_EDGE, true, rdp(c, c->edge_emb.b), e.embE, false, nullptr, nullptr, nodrop, 0u, r.cx, RD_EDGE);
     hipLaunchKernelGGL(k_rdb_normalize16, dim3(row_grid(Emax, 8192)), dim3(256), 0, s, ntot, K, e.embE, rdp(c, c->ne_g), rdp(c, c->ne_b), e.hE);
     tb16* Pt = reinterpret_cast<tb16*>(w.f.pq);
     tb16* Qt = Pt + (Nmax + 1) * RD_H;                       // (row Nmax of Q: zeros, the gather target of absent slots - rd_front)
@@ -268,12 +268,12 @@ int rdb_step(rdesign_handle h, const RdtArgs& a, size_t* sizes) {
         const std::vector<tb16*>& msg = e.msg[l];
         const float* hv = w.hv[l];
         const float* w0 = rdp(c, Lw.msg[0].w);               // [128][384] = [W_e | W_centre | W_neighbour]
-        te_gemm_pq(rn, hv, w0 + RD_H, rdp(c, Lw.msg[0].b), Pt, Qt, s);
+        te_gemm_pq(rn, hv, w0 + RD_H, rdp(c, Lw.msg[0].b), Pt, Qt, r.cx);
         const EFuse f{Pt, Qt, w.f.nbr, K, (int)Nmax, nullptr, nullptr, 0u};
         // Linears 0 and 1 in one kernel: msg[0] taped with TE_DROPPED marks, msg[1] plain
-        te_mlp2_fwd(re, e.hE, w0, 3 * RD_H, rdp(c, Lw.msg[1].w), RD_H, rdp(c, Lw.msg[1].b), msg[0], msg[1], f, dr, t.site_msg(l, 0), s);
+        te_mlp2_fwd(re, e.hE, w0, 3 * RD_H, rdp(c, Lw.msg[1].w), RD_H, rdp(c, Lw.msg[1].b), msg[0], msg[1], f, dr, t.site_msg(l, 0), r.cx);
         if (M == 3) {
-            bad |= !te_gemm(re, msg[1], true, RD_H, rdp(c, Lw.msg[2].w), RD_H, true, rdp(c, Lw.msg[2].b), msg[2], true, nullptr, nullptr, dr, t.site_msg(l, 1), s);
+            bad |= !te_gemm(re, msg[1], true, RD_H, rdp(c, Lw.msg[2].w), RD_H, true, rdp(c, Lw.msg[2].b), msg[2], true, nullptr, nullptr, dr, t.site_msg(l, 1), r.cx);
             if (dr.thresh) hipLaunchKernelGGL(k_rdb_mark_dropped, dim3(ew_grid(Emax * 16)), dim3(256), 0, s, ntot, K, msg[1], dr, t.site_msg(l, 1));
         }
         hipLaunchKernelGGL(k_rdb_segsum, dim3(seg_grid), dim3(256), 0, s, pk, K, w.f.nbr, msg[M - 1], 1.0f / 30.0f, tl.dh, dr, t.site_msg(l, M - 1));
@@ -296,22 +296,22 @@ int rdb_step(rdesign_handle h, const RdtArgs& a, size_t* sizes) {
         norm_bwd(false, w.hv[l], tl.dh, w.gX, Lw.n1w, Lw.n1b, 1, w.gH);                                      // norm1(h_V + dh): w.gH <- d (h_V + dh)
         // last message Linear: d pre[M-1] = valid ? gH[row / K] / 30 * g : 0 formed while its tile is staged; dW, db, d pre[M-2] in one pass
         const RdLin& last = Lw.msg[M - 1];
-        te_gemm_bwd2(re, nullptr, msg[M - 2], e.dA, rdp(c, last.w), RD_H, t.G(last.w), RD_H, dr, t.G(last.b), s,
+        te_gemm_bwd2(re, nullptr, msg[M - 2], e.dA, rdp(c, last.w), RD_H, t.G(last.w), RD_H, dr, t.G(last.b), r.cx,
                      EBwd2Src{2, msg[M - 1], w.f.nbr, w.gH, e.inv_scale, K});
         tb16* dpre0 = e.dA;
         if (M == 3) {       // the middle Linear takes its dY as given: weight gradient and input gradient as two passes over it
             const RdLin& mid = Lw.msg[1];
-            te_gemm_tn(re, e.dA, msg[0], t.G(mid.w), RD_H, true, dr, t.site_msg(l, 0), t.G(mid.b), s);
-            bad |= !te_gemm(re, e.dA, true, RD_H, rdp(c, mid.w), RD_H, false, nullptr, e.dB, false, msg[0], nullptr, dr, t.site_msg(l, 0), s);
+            te_gemm_tn(re, e.dA, msg[0], t.G(mid.w), RD_H, true, dr, t.site_msg(l, 0), t.G(mid.b), r.cx);
+            bad |= !te_gemm(re, e.dA, true, RD_H, rdp(c, mid.w), RD_H, false, nullptr, e.dB, false, msg[0], nullptr, dr, t.site_msg(l, 0), r.cx);
             dpre0 = e.dB;
         }
         // factored first Linear: pre0 = W_e h_E + (W_c h_V + b)[centre] + (W_n h_V)[neighbour]
         const RdLin& l0 = Lw.msg[0];
         const float* w0 = rdp(c, l0.w);
-        te_gemm_bwd1(re, dpre0, e.hE, e.de, w0, 3 * RD_H, t.G(l0.w), 3 * RD_H, s);                           // dW_e, this layer's d h_E
+        te_gemm_bwd1(re, dpre0, e.hE, e.de, w0, 3 * RD_H, t.G(l0.w), 3 * RD_H, r.cx);                        // dW_e, this layer's d h_E
         hipLaunchKernelGGL(k_rdb_acc, dim3(ew_grid(Emax * 16)), dim3(256), 0, s, ntot, K, e.de, e.dhE, l == L - 1 ? 1 : 0);
         te_edge_pq_bwd(pk, K, dpre0, w.rstart, w.rlist, e.dpq, s);                                           // dP = own slots, dQ = gather over the reverse adjacency
-        tm_gemm_tn_pq(rn, e.dpq, w.hv[l], t.G(l0.w) + RD_H, t.G(l0.b), s);                                   // [dW_c ; dW_n], db (the bias rides in P)
+        tm_gemm_tn_pq(rn, e.dpq, w.hv[l], t.G(l0.w) + RD_H, t.G(l0.b), r.cx);                                // [dW_c ; dW_n], db (the bias rides in P)
         if (!tm_gemm_nn_pq(rn, e.dpq, w0 + RD_H, w.gH, s)) {                                                 // d h_V += dP W_c + dQ W_n
             t_gemm(rn, e.dpq, 256, RD_H, w0 + RD_H, l0.in, nullptr, RD_H, w.gH, RD_H, 1, s);
             t_gemm(rn, e.dpq + RD_H, 256, RD_H, w0 + 2 * RD_H, l0.in, nullptr, RD_H, w.gH, RD_H, 1, s);
@@ -321,10 +321,8 @@ int rdb_step(rdesign_handle h, const RdtArgs& a, size_t* sizes) {
     norm_bwd(false, w.embN, nullptr, w.gH, c->nn_g, c->nn_b, 0, w.gX);
     rdt_node_emb_bwd(t);
     norm_bwd(true, e.embE, nullptr, e.dhE, c->ne_g, c->ne_b, 0, e.dB);
-    te_gemm_tn(re, e.dB, e.eraw, t.G(c->edge_emb.w), RD_EDGE, false, nodrop, 0u, t.G(c->edge_emb.b), s, RD_EDGE);
-    const int rc = rdt_end(who);
-    t_wimg_bind(nullptr);
-    if (rc) return rc;
+    te_gemm_tn(re, e.dB, e.eraw, t.G(c->edge_emb.w), RD_EDGE, false, nodrop, 0u, t.G(c->edge_emb.b), r.cx, RD_EDGE);
+    if (const int rc = rdt_end(t, who)) return rc;
     if (bad) return rd_fail(RDESIGN_ERR_UNSUPPORTED, "bf16-mixed training step: an MFMA edge GEMM variant this configuration needs is not built");
     RD_TRY(hipGetLastError());
     return RDESIGN_OK;

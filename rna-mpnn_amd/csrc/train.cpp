@@ -139,23 +139,16 @@ extern "C" int rnampnn_weight_offset(rnampnn_handle h, int32_t i, int64_t* offse
 }
 
 namespace {
-// the weight-image cache bound to the calling thread for the length of one training call: train_begin binds, every return of the entry point unbinds
-struct WimgScope {
-    bool bound = false;
-    void bind(WImageCache* c) { t_wimg_bind(c); bound = true; }
-    ~WimgScope() { if (bound) t_wimg_bind(nullptr); }
-};
 struct Tr {                        // one training call
     rnampnn_ctx* c;
     PackInfo pk;
     TW w;
-    hipStream_t s;
+    TCall cx;                      // stream, the backward's reduction queue, the handle's weight-image cache (bf16-mixed)
     float* g;                      // flat gradient buffer (arena layout)
     int k, t_norm;
     TDrop dr;
     bool bad = false;              // a bf16-storage GEMM variant that is not instantiated was requested (reported at the end of the pass)
     bool mixed;                    // bf16-mixed: GEMMs on MFMA with bf16 operands / f32 accumulate (kernels_train.hip, second half)
-    WimgScope wimg;
     bool att_mfma = false;         // the MFMA attention kernels (bf16-mixed unless RNAMPNN_F32_ATTN=1); decided ONCE per forward and kept on the tape
     TRows rn() const { return TRows{pk.cu + pk.B, 1, pk.Nmax}; }
     TRows re() const { return TRows{pk.cu + pk.B, k, pk.Nmax * k}; }
@@ -166,29 +159,29 @@ struct Tr {                        // one training call
 // Y = beta Y + X . W + bias            W [K][N] row-major (ldw)
 void mm_nn(Tr& t, const TRows& rows, const float* X, int ldx, int K, const float* W, int ldw, const float* bias, int N,
            float* Y, int ldy, int beta) {
-    if (t.mixed && tm_gemm_nn(rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, nullptr, 0, t.dr, 0u, t.s)) return;
-    t_gemm(rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, t.s);
+    if (t.mixed && tm_gemm_nn(rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, nullptr, 0, t.dr, 0u, t.cx)) return;
+    t_gemm(rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, t.cx.s);
 }
 // Y = beta Y + X . W^T + bias          W [N][K] row-major (nn.Linear.weight); wt = its K-major copy for the f32 kernel
 void mm_nt(Tr& t, const TRows& rows, const float* X, int ldx, int K, const float* W, int ldw, const float* wt, int ldwt,
            const float* bias, int N, float* Y, int ldy, int beta) {
-    if (t.mixed && tm_gemm_nt(rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, false, t.dr, 0u, t.s)) return;
-    t_gemm(rows, X, ldx, K, wt, ldwt, bias, N, Y, ldy, beta, t.s);
+    if (t.mixed && tm_gemm_nt(rows, X, ldx, K, W, ldw, bias, N, Y, ldy, beta, false, t.dr, 0u, t.cx)) return;
+    t_gemm(rows, X, ldx, K, wt, ldwt, bias, N, Y, ldy, beta, t.cx.s);
 }
 // dW += A^T B                          (contraction over the rows; ordered two-stage reduction in both modes)
 // dbias (optional) += column sums of A: the bias gradient of the same Linear (fused into the MFMA kernel's staging pass)
 void mm_tn(Tr& t, const TRows& rows, const float* A, int lda, int M, const float* B, int ldb, int K, float* dW, int ldw,
            float* dbias = nullptr) {
-    if (t.mixed && tm_gemm_tn(rows, A, lda, M, B, ldb, K, dW, ldw, false, t.dr, 0u, dbias, t.s)) return;
-    t_gemm_tn(rows, A, lda, M, B, ldb, K, dW, ldw, t.s);
-    if (dbias) t_colsum(rows, A, lda, M, dbias, t.s);
+    if (t.mixed && tm_gemm_tn(rows, A, lda, M, B, ldb, K, dW, ldw, false, t.dr, 0u, dbias, t.cx)) return;
+    t_gemm_tn(rows, A, lda, M, B, ldb, K, dW, ldw, t.cx);
+    if (dbias) t_colsum(rows, A, lda, M, dbias, t.cx);
 }
 
 void lin_fwd(Tr& t, const Lin& l, const float* X, int ldx, float* Y, int ldy) {
     // (X carries in_pad columns; the weight has `in`: when they differ - the 28 raw features - the MFMA form is skipped)
     const bool mm = t.mixed && l.in == l.in_pad;
-    if (mm && tm_gemm_nt(t.rn(), X, ldx, l.in, rawp(t.c, l.w), l.in, rawp(t.c, l.b), l.out, Y, ldy, 0, false, t.dr, 0u, t.s)) return;
-    t_gemm(t.rn(), X, ldx, l.in_pad, derp<float>(t.c, l.wt), l.out, rawp(t.c, l.b), l.out, Y, ldy, 0, t.s);
+    if (mm && tm_gemm_nt(t.rn(), X, ldx, l.in, rawp(t.c, l.w), l.in, rawp(t.c, l.b), l.out, Y, ldy, 0, false, t.dr, 0u, t.cx)) return;
+    t_gemm(t.rn(), X, ldx, l.in_pad, derp<float>(t.c, l.wt), l.out, rawp(t.c, l.b), l.out, Y, ldy, 0, t.cx.s);
 }
 // dX (optional) = dY . W ; dW += dY^T X ; db += colsum(dY)
 void lin_bwd(Tr& t, const Lin& l, const float* X, int ldx, const float* dY, int lddy, float* dX, int lddx) {
@@ -211,11 +204,11 @@ void ffn_fwd(Tr& t, const std::vector<Lin>& L, const float* X, int ldx, std::vec
         if (cur_is_pre) {
             if (t.mixed && fusable(L[i], cur, ld) &&
                 tm_gemm_nt(t.rn(), cur, ld, L[i].in, rawp(t.c, L[i].w), L[i].in, rawp(t.c, L[i].b), L[i].out, dst, L[i].out, 0, true, t.dr,
-                           site0 + (unsigned)(i - 1), t.s)) {
+                           site0 + (unsigned)(i - 1), t.cx)) {
                 cur = dst; ld = L[i].out; cur_is_pre = true;
                 continue;
             }
-            t_gelu_fwd(t.rn(), cur, t.w.act, ld, t.dr, site0 + (unsigned)(i - 1), t.s);
+            t_gelu_fwd(t.rn(), cur, t.w.act, ld, t.dr, site0 + (unsigned)(i - 1), t.cx.s);
             cur = t.w.act;
         }
         lin_fwd(t, L[i], cur, ld, dst, L[i].out);
@@ -232,22 +225,22 @@ void ffn_bwd(Tr& t, const std::vector<Lin>& L, const float* X, int ldx, const st
         const unsigned site = site0 + (unsigned)(i - 1);
         // dW += dY^T drop(gelu(pre)), db += colsum(dY): the activation recomputed in the staging pass;  d pre = (dY . W) gelu'(pre) mask
         if (i > 0 && t.mixed && fusable(L[i], pre[i - 1], L[i - 1].out) && L[i].out % 16 == 0 && (((uintptr_t)d) & 15) == 0 &&
-            tm_gemm_tn(t.rn(), d, L[i].out, L[i].out, pre[i - 1], L[i].in, L[i].in, t.gw(L[i].w), L[i].in, true, t.dr, site, t.gw(L[i].b), t.s)) {
-            if (tm_gemm_nn(t.rn(), d, L[i].out, L[i].out, rawp(t.c, L[i].w), L[i].in, nullptr, L[i].in, din, L[i].in, 0, pre[i - 1], L[i].in, t.dr, site, t.s)) {
+            tm_gemm_tn(t.rn(), d, L[i].out, L[i].out, pre[i - 1], L[i].in, L[i].in, t.gw(L[i].w), L[i].in, true, t.dr, site, t.gw(L[i].b), t.cx)) {
+            if (tm_gemm_nn(t.rn(), d, L[i].out, L[i].out, rawp(t.c, L[i].w), L[i].in, nullptr, L[i].in, din, L[i].in, 0, pre[i - 1], L[i].in, t.dr, site, t.cx)) {
                 d = din;
                 continue;
             }
             mm_nn(t, t.rn(), d, L[i].out, L[i].out, rawp(t.c, L[i].w), L[i].in, nullptr, L[i].in, din, L[i].in, 0);
-            t_gelu_bwd(t.rn(), din, pre[i - 1], din, L[i - 1].out, t.dr, site, t.s);
+            t_gelu_bwd(t.rn(), din, pre[i - 1], din, L[i - 1].out, t.dr, site, t.cx.s);
             d = din;
             continue;
         }
         const float* in;
         int ldin;
         if (i == 0) { in = X; ldin = ldx; }
-        else { t_gelu_fwd(t.rn(), pre[i - 1], t.w.act, L[i - 1].out, t.dr, site, t.s); in = t.w.act; ldin = L[i - 1].out; }
+        else { t_gelu_fwd(t.rn(), pre[i - 1], t.w.act, L[i - 1].out, t.dr, site, t.cx.s); in = t.w.act; ldin = L[i - 1].out; }
         lin_bwd(t, L[i], in, ldin, d, L[i].out, din, i == 0 ? lddx : L[i].in);
-        if (i > 0) { t_gelu_bwd(t.rn(), din, pre[i - 1], din, L[i - 1].out, t.dr, site, t.s); d = din; }
+        if (i > 0) { t_gelu_bwd(t.rn(), din, pre[i - 1], din, L[i - 1].out, t.dr, site, t.cx.s); d = din; }
     }
 }
 
@@ -261,12 +254,12 @@ int bert_fwd(Tr& t, const Bert& b, BertTape& tp, float* x_in, float* out, unsign
         const Attn& a = b.attn[j];
         lin_fwd(t, a.qkv, tp.x[j], RN_D, tp.qkv[j], 3 * RN_D);
         // bf16-mixed: the MFMA attention (forward and backward recompute S from the same bf16 operands); RNAMPNN_F32_ATTN=1 keeps the f32 kernels (A/B)
-        if (!(t.att_mfma && te_attention_fwd(t.pk, tp.qkv[j], b.heads, tp.o[j], tp.st[j], t.dr, site_att0 + (unsigned)j, t.s) == 0))
-            if (t_attention_fwd(t.pk, tp.qkv[j], b.heads, tp.o[j], tp.st[j], t.dr, site_att0 + (unsigned)j, t.s)) return 1;
+        if (!(t.att_mfma && te_attention_fwd(t.pk, tp.qkv[j], b.heads, tp.o[j], tp.st[j], t.dr, site_att0 + (unsigned)j, t.cx.s) == 0))
+            if (t_attention_fwd(t.pk, tp.qkv[j], b.heads, tp.o[j], tp.st[j], t.dr, site_att0 + (unsigned)j, t.cx.s)) return 1;
         lin_fwd(t, a.out, tp.o[j], RN_D, tp.t[j], RN_D);
-        t_add(t.rn(), tp.x[j], tp.t[j], RN_D, t.s);                                          // residual (functional.py:165)
+        t_add(t.rn(), tp.x[j], tp.t[j], RN_D, t.cx.s);                                          // residual (functional.py:165)
         launch_graph_norm_packed(t.pk, tp.t[j], nullptr, tp.x[j + 1], rawp(t.c, a.gn_scale), rawp(t.c, a.gn_shift),
-                                 t.c->cfg.padding_len, t.s);
+                                 t.c->cfg.padding_len, t.cx.s);
     }
     ffn_fwd(t, b.ffn, tp.x[b.attn.size()], RN_D, tp.pre, out, site_ffn0);
     return 0;
@@ -278,13 +271,13 @@ int bert_bwd(Tr& t, const Bert& b, BertTape& tp, const float* dOut, float* dIn, 
     for (int j = (int)J - 1; j >= 0; --j) {
         const Attn& a = b.attn[j];
         // GraphNorm backward: dIn = d x[j+1]  ->  nscr = d t[j]
-        t_gn_bwd(t.pk, tp.t[j], dIn, rawp(t.c, a.gn_scale), t.c->cfg.padding_len, t.w.nscr, t.gw(a.gn_scale), t.gw(a.gn_shift), t.s);
+        t_gn_bwd(t.pk, tp.t[j], dIn, rawp(t.c, a.gn_scale), t.c->cfg.padding_len, t.w.nscr, t.gw(a.gn_scale), t.gw(a.gn_shift), t.cx);
         // out_proj backward: d o = d t . Wout
         lin_bwd(t, a.out, tp.o[j], RN_D, t.w.nscr, RN_D, t.w.dh2, RN_D);
-        if (!(t.att_mfma && te_attention_bwd(t.pk, tp.qkv[j], tp.o[j], t.w.dh2, b.heads, t.w.dqkv, tp.st[j], t.dr, site_att0 + (unsigned)j, t.s) == 0))
-            if (t_attention_bwd(t.pk, tp.qkv[j], tp.o[j], t.w.dh2, b.heads, t.w.dqkv, tp.st[j], t.dr, site_att0 + (unsigned)j, t.s)) return 1;
+        if (!(t.att_mfma && te_attention_bwd(t.pk, tp.qkv[j], tp.o[j], t.w.dh2, b.heads, t.w.dqkv, tp.st[j], t.dr, site_att0 + (unsigned)j, t.cx.s) == 0))
+            if (t_attention_bwd(t.pk, tp.qkv[j], tp.o[j], t.w.dh2, b.heads, t.w.dqkv, tp.st[j], t.dr, site_att0 + (unsigned)j, t.cx.s)) return 1;
         lin_bwd(t, a.qkv, tp.x[j], RN_D, t.w.dqkv, 3 * RN_D, dIn, RN_D);                     // d x[j] (through q,k,v)
-        t_add(t.rn(), t.w.nscr, dIn, RN_D, t.s);                                              // + residual path
+        t_add(t.rn(), t.w.nscr, dIn, RN_D, t.cx.s);                                              // + residual path
     }
     return 0;
 }
@@ -294,12 +287,12 @@ int bert_bwd(Tr& t, const Bert& b, BertTape& tp, const float* dOut, float* dIn, 
 // one per-edge MLP on the tape:  pre1 = e.Wc + P[i] + Q[j] ; pre2 = gelu(pre1).W2^T + b2
 void mlp_edge_fwd(Tr& t, const Mlp2& m, const float* h, const float* e, float* pre1, float* pre2, unsigned site0) {
     rnampnn_ctx* c = t.c;
-    t_gemm(t.rn(), h, RN_D, RN_D, derp<float>(c, m.pq_t), 256, derp<float>(c, m.pq_b), 256, t.w.pq, 256, 0, t.s);   // [P | Q] = h [Wa | Wb]^T + [b1 | 0]
-    t_gemm(t.re(), e, RN_D, RN_D, derp<float>(c, m.wc_t), RN_D, nullptr, RN_D, pre1, RN_D, 0, t.s);
-    t_edge_add_pq(t.pk, t.k, t.w.nbr, t.w.pq, pre1, t.s);
+    t_gemm(t.rn(), h, RN_D, RN_D, derp<float>(c, m.pq_t), 256, derp<float>(c, m.pq_b), 256, t.w.pq, 256, 0, t.cx.s);   // [P | Q] = h [Wa | Wb]^T + [b1 | 0]
+    t_gemm(t.re(), e, RN_D, RN_D, derp<float>(c, m.wc_t), RN_D, nullptr, RN_D, pre1, RN_D, 0, t.cx.s);
+    t_edge_add_pq(t.pk, t.k, t.w.nbr, t.w.pq, pre1, t.cx.s);
     if (m.depth > 1) {
-        t_gelu_fwd(t.re(), pre1, t.w.E1, RN_D, t.dr, site0, t.s);
-        t_gemm(t.re(), t.w.E1, RN_D, RN_D, derp<float>(c, m.w2_t), RN_D, rawp(c, m.b[1]), RN_D, pre2, RN_D, 0, t.s);
+        t_gelu_fwd(t.re(), pre1, t.w.E1, RN_D, t.dr, site0, t.cx.s);
+        t_gemm(t.re(), t.w.E1, RN_D, RN_D, derp<float>(c, m.w2_t), RN_D, rawp(c, m.b[1]), RN_D, pre2, RN_D, 0, t.cx.s);
     }
 }
 // backward of one per-edge MLP.  On entry E2 holds d(pre_last) [E][128] (already multiplied by gelu' of the
@@ -309,17 +302,17 @@ void mlp_edge_bwd(Tr& t, const Mlp2& m, const float* h, const float* e, const fl
     float* dpre1 = t.w.E2;
     if (m.depth > 1) {
         // E2 = d pre2 ; a1 = gelu(pre1) -> E1
-        t_gelu_fwd(t.re(), pre1, t.w.E1, RN_D, t.dr, site0, t.s);
+        t_gelu_fwd(t.re(), pre1, t.w.E1, RN_D, t.dr, site0, t.cx.s);
         mm_tn(t, t.re(), t.w.E2, RN_D, RN_D, t.w.E1, RN_D, RN_D, t.gw(m.w[1]), RN_D, t.gw(m.b[1]));  // dW2 += dpre2^T a1, db2
         mm_nn(t, t.re(), t.w.E2, RN_D, RN_D, rawp(c, m.w[1]), RN_D, nullptr, RN_D, t.w.E1, RN_D, 0);  // d a1 = dpre2 . W2
-        t_gelu_bwd(t.re(), t.w.E1, pre1, t.w.E1, RN_D, t.dr, site0, t.s);                           // d pre1
+        t_gelu_bwd(t.re(), t.w.E1, pre1, t.w.E1, RN_D, t.dr, site0, t.cx.s);                           // d pre1
         dpre1 = t.w.E1;
     }
     float* gw0 = t.gw(m.w[0]);                     // [128][384] = [Wa | Wb | Wc]
     const float* w0 = rawp(c, m.w[0]);
     mm_tn(t, t.re(), dpre1, RN_D, RN_D, e, RN_D, RN_D, gw0 + 2 * RN_D, 3 * RN_D);                  // dWc += dpre1^T e
     mm_nn(t, t.re(), dpre1, RN_D, RN_D, w0 + 2 * RN_D, 3 * RN_D, nullptr, RN_D, dE, RN_D, 1);      // dE += dpre1 . Wc
-    t_edge_pq_bwd(t.pk, t.k, dpre1, t.w.rstart, t.w.rlist, t.w.dpq, t.s);                          // dP (segment sum), dQ (gather over incoming edges)
+    t_edge_pq_bwd(t.pk, t.k, dpre1, t.w.rstart, t.w.rlist, t.w.dpq, t.cx.s);                          // dP (segment sum), dQ (gather over incoming edges)
     mm_tn(t, t.rn(), t.w.dpq, 256, RN_D, h, RN_D, RN_D, gw0, 3 * RN_D, t.gw(m.b[0]));              // dWa += dP^T h, db1 += sum dP
     mm_tn(t, t.rn(), t.w.dpq + RN_D, 256, RN_D, h, RN_D, RN_D, gw0 + RN_D, 3 * RN_D);              // dWb += dQ^T h
     mm_nn(t, t.rn(), t.w.dpq, 256, RN_D, w0, 3 * RN_D, nullptr, RN_D, dh_acc, RN_D, 1);            // dh += dP . Wa
@@ -327,7 +320,7 @@ void mlp_edge_bwd(Tr& t, const Mlp2& m, const float* h, const float* e, const fl
 }
 // edge embedding (feature.py:540-571): raw features F [E][96] -> pe1 [-> pe2] -> e[0], absent slots zeroed
 void edge_embed_fwd_f32(Tr& t) {
-    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.s;
+    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.cx.s;
     const int k = t.k;
     t_edge_features(t.pk, k, w.geom, w.nbr, w.F, s);
     const Lin& ee0 = c->edge_embed[0];
@@ -344,7 +337,7 @@ void edge_embed_fwd_f32(Tr& t) {
 }
 // ResMPNN layers (mpnn.py:283-294)
 void layers_fwd_f32(Tr& t) {
-    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.s;
+    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.cx.s;
     const int L = c->cfg.num_res_mpnn_layers, k = t.k;
     for (int l = 0; l < L; ++l) {
         const MpnnLayer& m = c->mpnn[l];
@@ -359,7 +352,7 @@ void layers_fwd_f32(Tr& t) {
 }
 // backward of layers l_hi .. l_lo (descending).  On entry dh = d h[l_hi + 1], dE = d e[l_hi + 1]; on return dh = d h[l_lo], dE = d e[l_lo]
 void layers_bwd_f32(Tr& t, int l_hi, int l_lo) {
-    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.s;
+    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.cx.s;
     const int L = c->cfg.num_res_mpnn_layers, k = t.k;
     const size_t N = (size_t)t.pk.Nmax;
     for (int l = l_hi; l >= l_lo; --l) {
@@ -370,7 +363,7 @@ void layers_bwd_f32(Tr& t, int l_hi, int l_lo) {
             mlp_edge_bwd(t, m.edge, w.h[l + 1], w.e[l], w.pu1[l], w.dE, w.dh, site_edge(l, 0));
         }
         // GraphNorm: dh = d h[l+1] -> dh2 = d hpre[l]
-        t_gn_bwd(t.pk, w.hpre[l], w.dh, rawp(c, m.gn_scale), t.t_norm, w.dh2, t.gw(m.gn_scale), t.gw(m.gn_shift), s);
+        t_gn_bwd(t.pk, w.hpre[l], w.dh, rawp(c, m.gn_scale), t.t_norm, w.dh2, t.gw(m.gn_scale), t.gw(m.gn_shift), t.cx);
         // hpre = h[l] + agg: d h[l] starts as dh2; messages get d agg = dh2
         const float* plast = m.msg.depth > 1 ? w.pm2[l] : w.pm1[l];
         t_seg_mean_bwd(t.pk, k, w.nbr, w.dh2, plast, w.E2, t.dr, site_msg(l, m.msg.depth - 1), s);        // E2 = d pre_last of the message MLP
@@ -380,7 +373,7 @@ void layers_bwd_f32(Tr& t, int l_hi, int l_lo) {
 }
 // ResFeature, edge side: dE = d e[0] (masked output of the embedding MLP)
 void edge_embed_bwd_f32(Tr& t) {
-    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.s;
+    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.cx.s;
     const Lin& ee0 = c->edge_embed[0];
     t_edge_zero_invalid(t.pk, t.k, w.nbr, w.dE, s);
     if (c->cfg.depth_res_edge_feature > 1) {
@@ -410,12 +403,12 @@ void mlp_edge_fwd_mixed(Tr& t, const Mlp2& m, const float* h, const tb16* e, tb1
     // P = h Wa^T + b1 and Q = h Wb^T as bf16 tables [N+1][128] inside the pq buffer (row N of Q stays zero: absent neighbours)
     tb16* Pt = eb(t.w.pq);
     tb16* Qt = Pt + (size_t)(t.pk.Nmax + 1) * RN_D;
-    te_gemm_pq(t.rn(), h, w0, rawp(c, m.b[0]), Pt, Qt, t.s);
+    te_gemm_pq(t.rn(), h, w0, rawp(c, m.b[0]), Pt, Qt, t.cx);
     EFuse f{Pt, Qt, t.w.nbr, t.k, t.pk.Nmax, e, res_out, site_res};
     if (m.depth > 1)
-        te_mlp2_fwd(t.re(), e, w0 + 2 * RN_D, 3 * RN_D, rawp(c, m.w[1]), RN_D, rawp(c, m.b[1]), pre1, pre2, f, t.dr, site0, t.s);
+        te_mlp2_fwd(t.re(), e, w0 + 2 * RN_D, 3 * RN_D, rawp(c, m.w[1]), RN_D, rawp(c, m.b[1]), pre1, pre2, f, t.dr, site0, t.cx);
     else
-        t.bad |= !te_gemm(t.re(), e, true, RN_D, w0 + 2 * RN_D, 3 * RN_D, true, nullptr, pre1, false, nullptr, &f, t.dr, 0u, t.s);
+        t.bad |= !te_gemm(t.re(), e, true, RN_D, w0 + 2 * RN_D, 3 * RN_D, true, nullptr, pre1, false, nullptr, &f, t.dr, 0u, t.cx);
 }
 // Accumulates parameter grads, dE (bf16) += d e, dh_acc (f32) += d h.  Depth 1: on entry E2 (bf16) holds d pre1.  Depth 2: `from` is required;
 // d pre2 is formed inside the fused kernel from the upstream gradient (EBwd2Src).
@@ -427,14 +420,14 @@ void mlp_edge_bwd_mixed(Tr& t, const Mlp2& m, const float* h, const tb16* e, con
     tb16* dpre1 = eb(t.w.E2);
     if (m.depth > 1) {
         dpre1 = dpre1_keep ? dpre1_keep : eb(t.w.E1);
-        te_gemm_bwd2(t.re(), dy_in, pre1, dpre1, rawp(c, m.w[1]), RN_D, t.gw(m.w[1]), RN_D, t.dr, t.gw(m.b[1]), t.s, *from);
+        te_gemm_bwd2(t.re(), dy_in, pre1, dpre1, rawp(c, m.w[1]), RN_D, t.gw(m.w[1]), RN_D, t.dr, t.gw(m.b[1]), t.cx, *from);
     }
     float* gw0 = t.gw(m.w[0]);
     const float* w0 = rawp(c, m.w[0]);
-    if (!dpre1_keep) te_gemm_bwd1(t.re(), dpre1, e, dE, w0 + 2 * RN_D, 3 * RN_D, gw0 + 2 * RN_D, 3 * RN_D, t.s);   // dWc, dE: one pass over dpre1
-    te_edge_pq_bwd(t.pk, t.k, dpre1, t.w.rstart, t.w.rlist, t.w.dpq, t.s);
-    tm_gemm_tn_pq(t.rn(), t.w.dpq, h, gw0, t.gw(m.b[0]), t.s);                 // [dWa ; dWb] += [dP | dQ]^T h, db1 += colsum(dP)
-    if (!tm_gemm_nn_pq(t.rn(), t.w.dpq, w0, dh_acc, t.s)) {                            // dh += dP . Wa + dQ . Wb
+    if (!dpre1_keep) te_gemm_bwd1(t.re(), dpre1, e, dE, w0 + 2 * RN_D, 3 * RN_D, gw0 + 2 * RN_D, 3 * RN_D, t.cx);   // dWc, dE: one pass over dpre1
+    te_edge_pq_bwd(t.pk, t.k, dpre1, t.w.rstart, t.w.rlist, t.w.dpq, t.cx.s);
+    tm_gemm_tn_pq(t.rn(), t.w.dpq, h, gw0, t.gw(m.b[0]), t.cx);                 // [dWa ; dWb] += [dP | dQ]^T h, db1 += colsum(dP)
+    if (!tm_gemm_nn_pq(t.rn(), t.w.dpq, w0, dh_acc, t.cx.s)) {                            // dh += dP . Wa + dQ . Wb
         mm_nn(t, t.rn(), t.w.dpq, 256, RN_D, w0, 3 * RN_D, nullptr, RN_D, dh_acc, RN_D, 1);
         mm_nn(t, t.rn(), t.w.dpq + RN_D, 256, RN_D, w0 + RN_D, 3 * RN_D, nullptr, RN_D, dh_acc, RN_D, 1);
     }
@@ -443,19 +436,19 @@ void mlp_edge_bwd_mixed(Tr& t, const Mlp2& m, const float* h, const tb16* e, con
 void mlp_edge_bwd1_pair(Tr& t, const Mlp2& me, const Mlp2& mm, const tb16* e, const tb16* dpre1_e, const tb16* dpre1_m, tb16* dE) {
     rnampnn_ctx* c = t.c;
     te_gemm_bwd1x2(t.re(), dpre1_e, dpre1_m, e, dE, rawp(c, me.w[0]) + 2 * RN_D, rawp(c, mm.w[0]) + 2 * RN_D, 3 * RN_D,
-                   t.gw(me.w[0]) + 2 * RN_D, t.gw(mm.w[0]) + 2 * RN_D, 3 * RN_D, t.s);
+                   t.gw(me.w[0]) + 2 * RN_D, t.gw(mm.w[0]) + 2 * RN_D, 3 * RN_D, t.cx);
 }
 // edge embedding (feature.py:540-571), bf16 chain: raw features [E][128] (90 live columns) -> pe1 -> pe2 -> e[0], the activations fused into the
 // GEMM operand loads
 void edge_embed_fwd_mixed(Tr& t) {
-    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.s;
+    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.cx.s;
     const int k = t.k;
     const Lin& ee0 = c->edge_embed[0];
     te_edge_features(t.pk, k, w.geom, w.nbr, eb(w.F), s);
-    t.bad |= !te_gemm(t.re(), w.F, true, RN_D, rawp(c, ee0.w), RN_ERAW, true, rawp(c, ee0.b), eb(w.pe1), false, nullptr, nullptr, t.dr, 0u, s, RN_ERAW);
+    t.bad |= !te_gemm(t.re(), w.F, true, RN_D, rawp(c, ee0.w), RN_ERAW, true, rawp(c, ee0.b), eb(w.pe1), false, nullptr, nullptr, t.dr, 0u, t.cx, RN_ERAW);
     if (c->cfg.depth_res_edge_feature > 1) {
         const Lin& ee1 = c->edge_embed[1];
-        t.bad |= !te_gemm(t.re(), w.pe1, true, RN_D, rawp(c, ee1.w), RN_D, true, rawp(c, ee1.b), eb(w.pe2), true, nullptr, nullptr, t.dr, site_ee(0), s);
+        t.bad |= !te_gemm(t.re(), w.pe1, true, RN_D, rawp(c, ee1.w), RN_D, true, rawp(c, ee1.b), eb(w.pe2), true, nullptr, nullptr, t.dr, site_ee(0), t.cx);
         te_edge_act(t.pk, k, w.nbr, eb(w.pe2), eb(w.e[0]), t.dr, site_ee(1), s);
     } else {
         te_edge_act(t.pk, k, w.nbr, eb(w.pe1), eb(w.e[0]), t.dr, site_ee(0), s);
@@ -463,7 +456,7 @@ void edge_embed_fwd_mixed(Tr& t) {
 }
 // ResMPNN layers (mpnn.py:283-294)
 void layers_fwd_mixed(Tr& t) {
-    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.s;
+    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.cx.s;
     const int L = c->cfg.num_res_mpnn_layers, k = t.k;
     for (int l = 0; l < L; ++l) {
         const MpnnLayer& m = c->mpnn[l];
@@ -478,7 +471,7 @@ void layers_fwd_mixed(Tr& t) {
 }
 // backward of layers l_hi .. l_lo (descending).  On entry dh = d h[l_hi + 1], dE (bf16) = d e[l_hi + 1]; on return dh = d h[l_lo], dE = d e[l_lo]
 void layers_bwd_mixed(Tr& t, int l_hi, int l_lo) {
-    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.s;
+    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.cx.s;
     const int L = c->cfg.num_res_mpnn_layers, k = t.k;
     const size_t N = (size_t)t.pk.Nmax;
     for (int l = l_hi; l >= l_lo; --l) {
@@ -498,7 +491,7 @@ void layers_bwd_mixed(Tr& t, int l_hi, int l_lo) {
                 mlp_edge_bwd_mixed(t, m.edge, w.h[l + 1], eb(w.e[l]), eb(w.pu1[l]), eb(w.dE), w.dh);
             }
         }
-        t_gn_bwd(t.pk, w.hpre[l], w.dh, rawp(c, m.gn_scale), t.t_norm, w.dh2, t.gw(m.gn_scale), t.gw(m.gn_shift), s);
+        t_gn_bwd(t.pk, w.hpre[l], w.dh, rawp(c, m.gn_scale), t.t_norm, w.dh2, t.gw(m.gn_scale), t.gw(m.gn_shift), t.cx);
         if (m.msg.depth > 1) {          // ... and so does the backward of the message mean (dagg = dh2)
             launch_copy_bytes(w.dh, w.dh2, N * RN_D * sizeof(float), s);
             EBwd2Src from{2, eb(w.pm2[l]), w.nbr, w.dh2, w.invc, k};
@@ -513,19 +506,19 @@ void layers_bwd_mixed(Tr& t, int l_hi, int l_lo) {
 }
 // ResFeature, edge side: dE (bf16) = d e[0]
 void edge_embed_bwd_mixed(Tr& t) {
-    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.s;
+    rnampnn_ctx* c = t.c; TW& w = t.w; hipStream_t s = t.cx.s;
     const int k = t.k;
     const Lin& ee0 = c->edge_embed[0];
     tb16* dpe1 = eb(w.E1);
     if (c->cfg.depth_res_edge_feature > 1) {
         const Lin& ee1 = c->edge_embed[1];
         te_edge_res_bwd(t.pk, k, w.nbr, eb(w.dE), eb(w.pe2), eb(w.E2), t.dr, site_ee(1), s);                              // d pe2 (absent edges: 0)
-        te_gemm_tn(t.re(), eb(w.E2), eb(w.pe1), t.gw(ee1.w), RN_D, true, t.dr, site_ee(0), t.gw(ee1.b), s);
-        t.bad |= !te_gemm(t.re(), w.E2, true, RN_D, rawp(c, ee1.w), RN_D, false, nullptr, dpe1, false, eb(w.pe1), nullptr, t.dr, site_ee(0), s);   // d pe1
+        te_gemm_tn(t.re(), eb(w.E2), eb(w.pe1), t.gw(ee1.w), RN_D, true, t.dr, site_ee(0), t.gw(ee1.b), t.cx);
+        t.bad |= !te_gemm(t.re(), w.E2, true, RN_D, rawp(c, ee1.w), RN_D, false, nullptr, dpe1, false, eb(w.pe1), nullptr, t.dr, site_ee(0), t.cx);   // d pe1
     } else {
         te_edge_res_bwd(t.pk, k, w.nbr, eb(w.dE), eb(w.pe1), dpe1, t.dr, site_ee(0), s);
     }
-    te_gemm_tn(t.re(), dpe1, eb(w.F), t.gw(ee0.w), RN_ERAW, false, t.dr, 0u, t.gw(ee0.b), s, RN_ERAW);
+    te_gemm_tn(t.re(), dpe1, eb(w.F), t.gw(ee0.w), RN_ERAW, false, t.dr, 0u, t.gw(ee0.b), t.cx, RN_ERAW);
 }
 }  // namespace
 
@@ -546,9 +539,9 @@ static int train_begin(Tr& t, rnampnn_handle h, int B, int T, void* ws, size_t w
     size_t need = carve_train(h, B, T, nullptr, nullptr);
     if (ws_bytes < need) return fail(RNAMPNN_ERR_WORKSPACE, "training workspace %zu bytes < required %zu", ws_bytes, need);
     if (((uintptr_t)ws & 255) != 0) return fail(RNAMPNN_ERR_BAD_ARG, "workspace must be 256-byte aligned");
-    t.c = h; t.s = (hipStream_t)stream; t.g = nullptr; t.k = h->cfg.num_res_neighbours; t.mixed = mixed;
+    t.c = h; t.cx.s = (hipStream_t)stream; t.g = nullptr; t.k = h->cfg.num_res_neighbours; t.mixed = mixed;
     if (mixed && !h->wimg) h->wimg = t_wimg_create(1024);      // (null on allocation failure: the kernels then build their images themselves)
-    t.wimg.bind(mixed ? h->wimg : nullptr);
+    t.cx.wimg = mixed ? h->wimg : nullptr;
     carve_train(h, B, T, (char*)ws, &t.w);
     t.pk.len = t.w.len; t.pk.cu = t.w.cu; t.pk.node_b = t.w.node_b; t.pk.B = B; t.pk.T = T; t.pk.Nmax = B * T; t.pk.packed_in = 0;
     return RNAMPNN_OK;
@@ -557,7 +550,7 @@ static int train_begin(Tr& t, rnampnn_handle h, int B, int T, void* ws, size_t w
 static int train_forward_impl(Tr& t, const float* coords, const float* mask, float* logits) {
     rnampnn_ctx* c = t.c;
     TW& w = t.w;
-    hipStream_t s = t.s;
+    hipStream_t s = t.cx.s;
     const int L = c->cfg.num_res_mpnn_layers, k = t.k;
     const size_t N = (size_t)t.pk.Nmax;
     launch_zero_bytes(w.pq + N * 256, 256 * sizeof(float), s);
@@ -613,12 +606,11 @@ static int train_forward_impl(Tr& t, const float* coords, const float* mask, flo
 static int train_backward_impl(Tr& t, int accumulate) {
     rnampnn_ctx* c = t.c;
     TW& w = t.w;
-    hipStream_t s = t.s;
+    hipStream_t s = t.cx.s;
     const int L = c->cfg.num_res_mpnn_layers, k = t.k;
     const size_t N = (size_t)t.pk.Nmax;
     if (!accumulate) launch_zero_bytes(t.g, c->raw_floats * sizeof(float), s);
-    // one reduction queue per backward, closed on every return (the normal one reports what it refused: red_end below)
-    struct RedScope { RedScope(const TScratch& sc, hipStream_t st) { red_begin(sc, st); } ~RedScope() { red_end(); } } red_scope(w.sc, s);
+    red_begin(t.cx, w.sc);         // the queue of this backward; it lives in the call's context and dies with it on every return
     {   // readout
         const float* d = w.dlogits;
         float* bufs[2] = {w.dA, w.dB};
@@ -638,31 +630,31 @@ static int train_backward_impl(Tr& t, int accumulate) {
         mm_tn(t, t.rn(), d, r0.out, r0.out, w.re, RN_D, RN_D, t.gw(r0.w) + RN_D, 2 * RN_D);
     }
     // raw embedding branch
-    t_gn_bwd(t.pk, w.r1, w.dre, rawp(c, c->rawffn_gn_scale), t.t_norm, w.nscr, t.gw(c->rawffn_gn_scale), t.gw(c->rawffn_gn_shift), s);
+    t_gn_bwd(t.pk, w.r1, w.dre, rawp(c, c->rawffn_gn_scale), t.t_norm, w.nscr, t.gw(c->rawffn_gn_scale), t.gw(c->rawffn_gn_shift), t.cx);
     ffn_bwd(t, c->raw_ffn, w.raw_p, RN_RAWP, w.raw_pre, w.nscr, nullptr, 0, site_raw(0));
     // post fusion -> dh = d h[L]
     if (bert_bwd(t, c->post, w.post, w.dhp, w.dh, site_post_att(0), site_post_ffn(0))) return fail(RNAMPNN_ERR_UNSUPPORTED, "head dim unsupported");
     // gradient chunk 0 (post_fusion, raw_embedding, readout: the tail of the flat buffer) is final
-    red_flush();
+    red_flush(t.cx);
     if (c->grad_ev[0]) HIP_TRY(hipEventRecord(c->grad_ev[0], s));
     // ResMPNN layers, reverse.  dE = d e[l+1] (zero for the last layer: its edge update is dead)
     launch_zero_bytes(w.dE, N * k * RN_D * (t.mixed ? sizeof(tb16) : sizeof(float)), s);
     const auto layers_bwd = t.mixed ? layers_bwd_mixed : layers_bwd_f32;
     layers_bwd(t, L - 1, L / 2);
     // chunk 1 (layers L/2 .. L-1; L == 1: the one layer) is final
-    red_flush();
+    red_flush(t.cx);
     if (c->grad_ev[1]) HIP_TRY(hipEventRecord(c->grad_ev[1], s));
     layers_bwd(t, L / 2 - 1, 0);
     // ResFeature: node side  dh = d h[0]
-    t_gn_bwd(t.pk, w.n1, w.dh, rawp(c, c->feat_gn_scale), t.t_norm, w.dh2, t.gw(c->feat_gn_scale), t.gw(c->feat_gn_shift), s);
+    t_gn_bwd(t.pk, w.n1, w.dh, rawp(c, c->feat_gn_scale), t.t_norm, w.dh2, t.gw(c->feat_gn_scale), t.gw(c->feat_gn_shift), t.cx);
     if (bert_bwd(t, c->emb, w.emb, w.dh2, w.dh, site_emb_att(0), site_emb_ffn(0))) return fail(RNAMPNN_ERR_UNSUPPORTED, "head dim unsupported");
     lin_bwd(t, c->raw_project, w.raw_p, RN_RAWP, w.dh, RN_D, nullptr, 0);
     // ResFeature: edge side  dE = d e[0]
     if (t.mixed) edge_embed_bwd_mixed(t); else edge_embed_bwd_f32(t);
-    t.bad |= !red_end();
+    t.bad |= !red_end(t.cx);
     HIP_TRY(hipGetLastError());
     if (t.bad) return fail(RNAMPNN_ERR_UNSUPPORTED, "training backward: a GEMM variant this configuration needs is not built, or the reduction "
-                           "queue refused a request (kernels_train.hip: RedQueue)");
+                           "queue refused a request (red_queue.h: RedQueue)");
     return RNAMPNN_OK;
 }
 
@@ -721,7 +713,7 @@ extern "C" int rnampnn_train_backward(rnampnn_handle h, int64_t tape_id, const f
     t.dr = t_drop(tape.p, tape.seed, tape.seed_dev);
     t.att_mfma = tape.att_mfma;
     t.g = grad;
-    t_pack_dlogits(t.pk, dlogits, t.w.dlogits, t.s);
+    t_pack_dlogits(t.pk, dlogits, t.w.dlogits, t.cx.s);
     return train_backward_impl(t, accumulate);
 }
 
@@ -743,7 +735,7 @@ extern "C" int rnampnn_loss_and_grad(rnampnn_handle h, const float* coords, cons
     tape_drop_ws(h, ws);
     rc = train_forward_impl(t, coords, mask, logits);
     if (rc) return rc;
-    t_loss_grad(t.pk, t.w.logits_p, labels, t.w.dlogits, loss, t.w.sc.p, t.s);
+    t_loss_grad(t.pk, t.w.logits_p, labels, t.w.dlogits, loss, t.w.sc.p, t.cx.s);
     return train_backward_impl(t, 0);
 }
 

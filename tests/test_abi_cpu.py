@@ -118,7 +118,7 @@ def test_training_path_issues_no_runtime_memset():
     set-up code and a test tap that are never captured."""
     import re
     csrc = os.path.join(REPO, "rna-mpnn_amd", "csrc")
-    for name in ("kernels_train.hip", "kernels_train.h", "train_dev.h", "bf16_core.h"):
+    for name in ("kernels_train.hip", "kernels_train.h", "red_queue.h", "train_dev.h", "bf16_core.h"):
         src = open(os.path.join(csrc, name)).read()
         assert "hipMemsetAsync" not in src and "hipMemset(" not in src, name
     inc = open(os.path.join(csrc, "train.cpp")).read()
