@@ -229,6 +229,56 @@ int rnampnn_design(const float* logits, int64_t n_rows, const float* mask, const
                    float temperature, int32_t S, uint64_t seed, const uint64_t* seed_dev, const uint8_t* allowed,
                    const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position, int8_t* seqs,
                    float* seq_nll, int32_t* infeasible, void* stream);
+/* Multi-state design in ONE launch (csrc/design_tied.hip): one sequence per sample for a GROUP of batch rows, its STATES (the conformers of
+ * an ensemble, the two backbones of a switch), drawn exactly from the product of the states' distributions under the union of their
+ * base-pair tables.  Layouts, the padded constraint tensors, seed_dev, the clamping of lengths and offsets and the alignment rules are
+ * those of rnampnn_design; rnampnn_design itself is unchanged.
+ *   group_cu (G+1) i32, device   group g = the consecutive rows [group_cu[g], group_cu[g+1]); values are clamped to [0, B], a decreasing
+ *                                pair is an empty group.  An empty group writes nothing; rows no group covers are not written.
+ *   weight (B) f32, nullable     per state row (null = 1 everywhere); may be negative (design AGAINST a state) or zero
+ * Group quantities.  n_g = the minimum of the states' lengths (states of different lengths give the common prefix).
+ *   z_t(c) = (sum_m weight_m * logit_{m,t}(c) + bias_t(c)) / temperature, summed in state order; a per-position bias is read from the group's
+ *   first row.  (A product of experts: the states' log-partition terms are constant in c and cancel.)  The mask of t is the AND of the
+ *   states' `allowed` sets; an empty AND is drawn as free and counts 1.
+ * Dependency graph.  t is adjacent to j if in at least one state partner[m,t] = j is well formed (0 <= j < n_g, j != t, partner[m,j] == t).
+ *   A position KEEPS its first two distinct neighbours in state order; one with more counts 1.  An edge is LIVE iff both ends keep it, so
+ *   every component of the live graph is an isolated position, a path or a cycle.  Every walk is capped at n_g steps.
+ * The draw, all of it in fp64 (z, the weights, the running sums).  The uniform of position t is u24(seed, s, b0, t) of rnampnn_design with b0
+ * the group's first row.  SELECT(cells, w, u24) is the documented rule: the first cell whose running sum of w exceeds u24 * 2^-24 * total,
+ * else the last cell.  omega_t(c) = exp(z_t(c) - max over the classes the mask admits), 0 for the others.  C(a,c) = 1 iff a pairs with c
+ * (wobble as in rnampnn_design).  For the chain draws the cells are the classes the node's mask admits, in class order.
+ *   Isolated position: SELECT over omega_t.
+ *   2-node path: the pair rule of rnampnn_design (16 cells in a-major order, log-domain maximum, the uniform of the lower index).
+ *   Path v_0 .. v_{L-1}, L >= 3, v_0 the end with the smaller index: alpha_0 = omega_0; alpha_k(c) = omega_k(c) * sum_a alpha_{k-1}(a) C(a,c),
+ *     then divided by its largest component.  c_{L-1} = SELECT(alpha_{L-1}) with the uniform of v_{L-1}; then for k = L-2 .. 0
+ *     c_k = SELECT(alpha_k(a) C(a, c_{k+1})) with the uniform of v_k.
+ *   Cycle, v_0 its smallest index and v_1 the smaller of v_0's neighbours: for every head class h the mask of v_0 admits the forward pass from
+ *     alpha_0 = omega_0(h) e_h, log Z_h = log sum_c alpha_{L-1}(c) C(c,h) + the sum of the logs of the normalisers; h = SELECT(exp(log Z_h -
+ *     max)) with the uniform of v_0; the forward pass again with h fixed; c_{L-1} = SELECT(alpha_{L-1}(c) C(c,h)), then backwards down to
+ *     k = 1 as for a path.
+ *   The log domain, as for the pair: the recursion is carried as lambda_k = log alpha_k - lambda_k(c) = z_k(c) + log sum_{a: C(a,c)}
+ *     exp(lambda_{k-1}(a)), -inf for a class the mask does not admit, minus its largest component - and the weights of a chain SELECT are
+ *     exp(lambda_k(c) - max over the classes eligible in that draw), 0 for the others.  The distribution is the one above; what changes is
+ *     that nothing underflows: at temperature 1e-3 omega is 0 for every class but one and the constrained optimum need not use that one.
+ *   Infeasible component (no assignment that the masks admit is compatible along every edge: a largest component of some lambda_k that is
+ *     not above -inf; no head with log Z_h above -inf; a 2-node path without a cell): every node draws as an isolated position with its own
+ *     uniform and counts 1.
+ * Outputs, each nullable:
+ *   seqs (S,B,T) i8       every state row of a group receives the same sequence; -1 at t >= n_g
+ *   seq_nll (S,B) f32     the NLL of the group's draw under THAT row's own logits (temperature 1, no bias): byte for byte rnampnn_score's
+ *                         seq_nll of the written row (a row longer than n_g reads class 3 at its -1 entries, as rnampnn_score does)
+ *   infeasible (B) i32    the group's count, written to each of its rows; the same for every sample
+ * One workgroup per (group, sample); alpha lives in dynamic LDS indexed by position (32 bytes per position, requested only with a partner
+ * table, + 1 byte per position always): RNAMPNN_ERR_UNSUPPORTED when that exceeds 160 KiB (T <= 4962 with a partner table).  No atomics, no
+ * workspace, no runtime fill / copy node, no host synchronisation: two calls give identical bytes, the call can sit inside a captured graph,
+ * and a draw is a pure function of (seed, s, b0, t) and the rows of its group - independent of B, T, S, G, the layout and the other groups.
+ * RNAMPNN_ERR_BAD_ARG, before anything is launched: the cases of rnampnn_design; group_cu null; G <= 0.  With every output null the call
+ * returns RNAMPNN_OK without a launch. */
+int rnampnn_design_tied(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
+                        const int32_t* group_cu, int32_t G, const float* weight,
+                        float temperature, int32_t S, uint64_t seed, const uint64_t* seed_dev,
+                        const uint8_t* allowed, const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position,
+                        int8_t* seqs, float* seq_nll, int32_t* infeasible, void* stream);
 
 /* -- training ---------------------------------------------------------------------------- */
 /* The training surface of RNAMPNN (rnampnn.py:187-207 + Lightning's loss.backward()):

@@ -8,7 +8,7 @@
 // ends of a pair compute the pair's cell on their own (the partner's row is one more 16-byte load) and each writes its own component: no
 // exchange between threads, so a pair may span waves or 256-strides.  No workspace, no runtime fill / copy node, no atomics, no host
 // synchronisation; the draw is a pure function of (seed, s, b, t) and the rows it reads.
-#include "score_dev.h"
+#include "design_dev.h"
 
 namespace {
 struct DesignArgs {
@@ -45,13 +45,6 @@ __device__ __forceinline__ DsPos ds_load(const DesignArgs& a, size_t pad0, long 
     return p;
 }
 
-__device__ __forceinline__ unsigned ds_u24(unsigned long long seed, int s, int b, int t) {
-    unsigned long long h = mix64(seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(s + 1));
-    h = mix64(h ^ (0xD6E8FEB86659FD93ull * (unsigned long long)(b + 1)));
-    h = mix64(h ^ (0xBF58476D1CE4E5B9ull * (unsigned long long)(t + 1)));
-    return (unsigned)(h >> 40);
-}
-
 // the first admitted class whose running sum of exp(z - max) exceeds u24 * 2^-24 * total; the last admitted one if none does
 __device__ __forceinline__ int ds_draw_single(const DsPos& p, unsigned u24) {
     float mx = -INFINITY;
@@ -75,11 +68,6 @@ __device__ __forceinline__ int ds_draw_single(const DsPos& p, unsigned u24) {
         if (!found) { q = c; found = run > u; }                 // (q ends on the last admitted class when nothing is found)
     }
     return q;
-}
-
-// the classes that pair with class a (AUCG = 0..3): A-U, U-A, C-G, G-C, and with wobble G-U, U-G
-__device__ __forceinline__ int ds_compat(int a, int wobble) {
-    return a == 0 ? 2 : a == 1 ? (wobble ? 9 : 1) : a == 2 ? 8 : (wobble ? 6 : 4);
 }
 
 // the pair (lo at the smaller index, hi at the larger): cells (a, b) in a-major order, weight exp(z_lo(a) + z_hi(b) - max) over the compatible

@@ -17,7 +17,16 @@ Constrained design (``rnampnn_design``, one launch on the packed logits): ``--co
 pattern of AUCG / IUPAC codes with ``.`` or ``-`` for free positions, ``structure`` a dot-bracket string whose pairs are drawn together as
 AU UA GC CG (GU UG unless ``--no-wobble``); either may be empty and ids not listed are unconstrained.  ``--bias A=..,U=..,C=..,G=..`` is added
 to the logits, ``--omit LETTERS`` never draws these letters.  With any of the four the designs CSV gains the column ``infeasible`` (positions
-whose constraint could not be honoured)."""
+whose constraint could not be honoured).
+
+    python rna-mpnn_amd/predict.py --ckpt Final.pt --data DIR --samples 8 --states states.csv [--constraints cons.csv]
+
+Multi-state design (``rnampnn_design_tied``, ``rnampnn`` checkpoints): ``--states`` is a CSV ``design_id,pdb_id,weight`` - the structures
+listed under one ``design_id`` (conformers of an ensemble, the two backbones of a switch) are the states of ONE design and receive the same
+sequence, drawn from the product of their distributions; ``weight`` may be empty (1) or negative (design against that state); structures
+not listed are designs of their own.  ``--constraints`` rows still go by ``pdb_id``, so each state brings its own structure, and the one
+sequence is pair-compatible in all of them.  The designs CSV then has one row per (design, sample):
+``design_id,sample,seq,infeasible,states,nll_per_nt,recovery``, the last three ``;``-joined per state."""
 from __future__ import annotations
 
 import argparse
@@ -46,6 +55,7 @@ def parse(argv=None):
     ap.add_argument("--bias", default=None, help="A=..,U=..,C=..,G=..: added to the logits of --samples")
     ap.add_argument("--omit", default="", help="letters --samples never draws")
     ap.add_argument("--no-wobble", action="store_true", help="base pairs of --constraints exclude GU / UG")
+    ap.add_argument("--states", default=None, help="CSV design_id,pdb_id,weight: the structures of one design_id share one sequence")
     return ap.parse_args(argv)
 
 
@@ -77,6 +87,14 @@ def run(args, log=print):
         from rdesign.utils.predict import predict
         from rdesign.utils.train import load_checkpoint
     extra = dict(samples=args.samples, temperature=args.temperature, seed=args.seed, designs_csv=args.designs_out, **design_options(args))
+    if args.states:
+        if family != "rnampnn":
+            raise ValueError("--states designs with rnampnn checkpoints only; for an rdesign checkpoint call RNAModel.design(states=...) "
+                             "from Python")
+        if args.samples <= 0:
+            raise ValueError("--states needs --samples N > 0")
+        from rnampnn.utils.constraints import read_states_csv
+        extra["states"] = read_states_csv(args.states)
     model, ck = load_checkpoint(args.ckpt, device=torch.device(args.device))
     if args.xgb:
         model.load_xgb_readout(args.xgb)

@@ -425,15 +425,20 @@ class RNAModel(nn.Module):
         return logits, cu, int(md.shape[1])
 
     @torch.no_grad()
-    def design(self, X, mask, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None, lengths=None):
+    def design(self, X, mask, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None, lengths=None, states=None,
+               state_weights=None):
         """``n_samples`` sequences per RNA drawn from this model's read-out at ``temperature`` and scored, in one ``rnampnn_design`` launch
         on the packed logits -> (seqs int8 (n_samples,B,T), -1 on padding; seq_nll (n_samples,B) f32, the model's own temperature-1 NLL of
         each draw; infeasible (B,) int32).  ``constraints``: a ``rnampnn.utils.constraints.DesignConstraints`` (fixed nucleotides, base
-        pairs, bias) or None for free draws.  ``lengths`` as in ``score_batch``."""
-        from rnampnn.model.rnampnn import design_from_logits
+        pairs, bias) or None for free draws.  ``lengths`` as in ``score_batch``.  ``states`` / ``state_weights``: multi-state design
+        (``rnampnn_design_tied`` through ``design_from_logits``): consecutive rows of a group are states of ONE design and receive the same
+        sequence; with host ``lengths`` a group whose states differ in length is a ``ValueError`` naming the group."""
+        from rnampnn.model.rnampnn import check_state_lengths, design_from_logits
+        if states is not None and lengths is not None:
+            check_state_lengths(states, lengths)
         logits, cu, T = self._packed_logits(X, mask, lengths)
         return design_from_logits(logits, cu_seqlens=cu, max_len=T, n_samples=n_samples, temperature=temperature, seed=seed,
-                                  constraints=constraints)
+                                  constraints=constraints, states=states, state_weights=state_weights)
 
     @torch.no_grad()
     def score_sequences(self, X, mask, seqs, labels=None, lengths=None):

@@ -12,6 +12,7 @@ reference counterpart): ``sample()``, ``design()``, ``score_s
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import os
 from typing import Dict, List, Optional, Tuple
 
@@ -543,15 +544,21 @@ class RNAMPNN(NativeModule):
 
     @torch.no_grad()
     def design(self, coords: torch.Tensor, mask: torch.Tensor, n_samples: int = 8, temperature: float = 0.1, seed: int = 0,
-               T_norm: int = 0, constraints=None):
+               T_norm: int = 0, constraints=None, states=None, state_weights=None, lengths=None):
         """``sample`` plus the score of every draw against the SAME logits, with one forward: -> (seqs int8 (n_samples,B,T), -1 on
         padding; seq_nll (n_samples,B) f32).  The NLL is the model's own (temperature 1) likelihood, so designs drawn at different
         temperatures rank on one scale.  ``constraints`` (``rnampnn.utils.constraints.DesignConstraints``: fixed nucleotides, base
         pairs of a target structure, bias): the draws come from ``rnampnn_design`` instead, which honours them and scores in the same
-        launch -> (seqs, seq_nll, infeasible (B,) int32 = positions whose constraint could not be honoured)."""
+        launch -> (seqs, seq_nll, infeasible (B,) int32 = positions whose constraint could not be honoured).  ``states`` / ``state_weights``:
+        multi-state design (``design_from_logits``): the rows of a group are states of one design -> the same triple.  ``lengths``: the
+        loader's host-side lengths; with them a group whose states differ in length is a ``ValueError`` naming the group (nothing here reads
+        the mask on the host; without them such a group is designed over its common prefix)."""
+        if states is not None and lengths is not None:
+            check_state_lengths(states, lengths)
         logits = self._run(coords, mask, T_norm=T_norm)["logits"]
-        if constraints is not None:
-            return design_from_logits(logits, mask=mask, n_samples=n_samples, temperature=temperature, seed=seed, constraints=constraints)
+        if constraints is not None or states is not None:
+            return design_from_logits(logits, mask=mask, n_samples=n_samples, temperature=temperature, seed=seed, constraints=constraints,
+                                      states=states, state_weights=state_weights)
         seqs = sample_from_logits(logits, mask, temperature, n_samples, seed)
         return seqs, score_logits(logits, mask=mask, seqs=seqs, want=("seq_nll",))["seq_nll"]
 
@@ -752,13 +759,30 @@ def sample_from_logits(logits: torch.Tensor, mask: torch.Tensor, temperature: fl
     return out
 
 
+def check_state_lengths(states, lengths) -> None:
+    """Multi-state design: the states of a group are conformers of ONE RNA.  ``ValueError`` naming the group when ``states`` does not
+    partition the rows or a group's rows differ in length."""
+    counts = [int(v) for v in states]
+    if any(v < 0 for v in counts) or sum(counts) != len(lengths):
+        raise ValueError(f"states must be non-negative row counts that sum to B = {len(lengths)}, got {counts}")
+    lo = 0
+    for g, k in enumerate(counts):
+        if len({int(n) for n in lengths[lo:lo + k]}) > 1:
+            raise ValueError(f"group {g} (rows {lo}..{lo + k - 1}): its states differ in length {[int(n) for n in lengths[lo:lo + k]]}")
+        lo += k
+
+
 def design_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
-                       max_len: Optional[int] = None, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None
-                       ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                       max_len: Optional[int] = None, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None,
+                       states=None, state_weights=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``rnampnn_design`` (include/rnampnn_hip.h): ``n_samples`` constrained draws per RNA from f32 logits and their scores in one launch
     -> (seqs int8 (S,B,T), -1 on padding; seq_nll (S,B) f32 = ``score_logits``' ``seq_nll`` of the draws; infeasible (B,) int32).  Padded
     layout: logits (B,T,4) + ``mask`` (B,T); packed layout: logits (N,4) + ``cu_seqlens`` (B+1), the padded extent T from the constraints'
     tensors or ``max_len``.  ``constraints``: a ``DesignConstraints`` (padded (B,T) tensors in both layouts) or None for a free draw.
+    ``states``: multi-state design (``rnampnn_design_tied``) - a sequence of row counts, one per group, that sums to B; the consecutive rows
+    of a group are the states (conformers, the backbones of a switch) of ONE design: they receive the same sequence, drawn exactly from the
+    product of their distributions under the union of their base-pair tables; ``seq_nll`` stays per row, ``infeasible`` is the group's count
+    on each of its rows.  ``state_weights`` (B,) per row (default 1; negative = design against that state).  ``None`` keeps ``rnampnn_design``.
     CUDA logits only (there is no CPU fallback); no host synchronisation."""
     device = logits.device
     if device.type != "cuda":
@@ -791,6 +815,22 @@ def design_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None
     seqs = torch.empty(max(S, 0), max(B, 0), max(T, 0), dtype=torch.int8, device=device)
     nll = torch.empty(max(S, 0), max(B, 0), dtype=torch.float32, device=device)
     bad = torch.empty(max(B, 0), dtype=torch.int32, device=device)
+    if states is None and state_weights is not None:
+        raise ValueError("state_weights belong to multi-state design: pass states as well")
+    if states is not None:
+        counts = [int(v) for v in states]
+        if any(v < 0 for v in counts) or sum(counts) != B:
+            raise ValueError(f"states must be non-negative row counts that sum to B = {B}, got {counts}")
+        gcu = torch.tensor([0] + list(itertools.accumulate(counts)), dtype=torch.int32).to(device, non_blocking=True)
+        sw = None if state_weights is None else _prep(torch.as_tensor(state_weights, dtype=torch.float32), device)
+        if sw is not None and tuple(sw.shape) != (B,):
+            raise ValueError(f"state_weights must be (B,) = {(B,)}, got {tuple(sw.shape)}")
+        with torch.cuda.device(device):
+            _native.check(_native.lib().rnampnn_design_tied(
+                _ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(cu), B, T, _ptr(gcu), len(counts), _ptr(sw), float(temperature), S,
+                C.c_uint64(int(seed) & (2 ** 64 - 1)), None, _ptr(al), _ptr(pa), int(bool(c.wobble)) if c is not None else 1, _ptr(bi),
+                per_position, _ptr(seqs), _ptr(nll), _ptr(bad), _stream(device)))
+        return seqs, nll, bad
     with torch.cuda.device(device):
         _native.check(_native.lib().rnampnn_design(
             _ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(cu), B, T, float(temperature), S, C.c_uint64(int(seed) & (2 ** 64 - 1)), None,

@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import csv
 from dataclasses import dataclass
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -156,3 +156,26 @@ def batch_constraints(table: Optional[Dict[str, Tuple[str, str]]], ids: Sequence
             raise ValueError(f"constraints for {rid}: {exc}") from None
         specs.append((pattern or None, structure or None))
     return DesignConstraints.from_specs(specs, lengths, T, bias=bias, wobble=wobble, omit=omit)
+
+
+def read_states_csv(path: str) -> Dict[str, List[Tuple[str, float]]]:
+    """Multi-state design: CSV with the columns ``design_id,pdb_id,weight`` -> {design_id: [(pdb_id, weight), ...]}, designs and their states
+    in file order.  The structures listed under one ``design_id`` are the states of ONE design; an empty ``weight`` is 1 (a negative one
+    designs against that state).  ``ValueError`` naming a missing column or a ``pdb_id`` listed twice."""
+    out: Dict[str, List[Tuple[str, float]]] = {}
+    seen = set()
+    with open(path, newline="") as f:
+        rd = csv.DictReader(f)
+        missing = {"design_id", "pdb_id", "weight"} - set(rd.fieldnames or ())
+        if missing:
+            raise ValueError(f"{path}: missing column(s) {sorted(missing)} (expected design_id,pdb_id,weight)")
+        for row in rd:
+            did, rid, w = (row["design_id"] or "").strip(), (row["pdb_id"] or "").strip(), (row["weight"] or "").strip()
+            if rid in seen:
+                raise ValueError(f"{path}: pdb_id {rid!r} is listed twice (a structure is a state of one design)")
+            seen.add(rid)
+            try:
+                out.setdefault(did, []).append((rid, float(w) if w else 1.0))
+            except ValueError:
+                raise ValueError(f"{path}: weight {w!r} of pdb_id {rid!r} is not a number") from None
+    return out

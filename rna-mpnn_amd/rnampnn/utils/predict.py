@@ -37,10 +37,50 @@ def load_structures(path: str, max_len: int = 1 << 30):
     return items
 
 
+def state_groups(states: dict, ids: List[str], lengths: List[int]):
+    """``read_states_csv`` table + the loaded structures -> [(design_id, [item index per state, file order], [weight per state])] sorted by
+    ``design_id``; a structure the table does not list is a one-state design named after itself.  ``ValueError`` naming the id or the design
+    for a listed structure that is not there, a ``design_id`` that is also an unlisted structure, and states that differ in length."""
+    index = {rid: i for i, rid in enumerate(ids)}
+    groups, listed = [], set()
+    for did, rows in states.items():
+        for rid, _ in rows:
+            if rid not in index:
+                raise ValueError(f"states: design {did!r} lists pdb_id {rid!r}, which is not among the structures")
+        idx = [index[rid] for rid, _ in rows]
+        if len({lengths[i] for i in idx}) > 1:
+            raise ValueError(f"states: the states of design {did!r} differ in length: " + ", ".join(f"{ids[i]} = {lengths[i]}" for i in idx))
+        listed.update(idx)
+        groups.append((did, idx, [float(w) for _, w in rows]))
+    for i, rid in enumerate(ids):
+        if i not in listed:
+            if rid in states:
+                raise ValueError(f"states: design_id {rid!r} is also the id of a structure that no design lists")
+            groups.append((rid, [i], [1.0]))
+    return sorted(groups, key=lambda g: g[0])
+
+
+def group_batches(groups, lengths: List[int], batch_size: int, max_rows: int) -> List[List[int]]:
+    """``bucket_batches`` over whole groups: groups sorted by length are cut greedily into batches of at most ``batch_size`` rows and
+    ``max_rows`` padded rows; a group larger than either gets a batch of its own.  -> lists of group indices."""
+    order = sorted(range(len(groups)), key=lambda g: (lengths[groups[g][1][0]], g))
+    batches, cur, rows = [], [], 0
+    for g in order:
+        k, n = len(groups[g][1]), lengths[groups[g][1][0]]          # ascending, so n is the longest of cur + [g]
+        if cur and (rows + k > batch_size or (rows + k) * n > max_rows):
+            batches.append(cur)
+            cur, rows = [], 0
+        cur.append(g)
+        rows += k
+    if cur:
+        batches.append(cur)
+    return batches
+
+
 @torch.no_grad()
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
-            wobble: bool = True) -> List[Tuple[str, str]]:
+            wobble: bool = True, states: Optional[dict] = None) -> List[Tuple[str, str]]:
     """Design a sequence for every structure under ``data_path`` in length-bucketed var-len batches (``forward_packed``): the tree
     read-out on the packed embedding when one is attached, else the read-out's argmax (``rnampnn_score``'s ``pred``); write ``out_csv``
     with one ``pdb_id,seq`` row per structure in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure
@@ -48,7 +88,10 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     ``pdb_id,sample,seq,nll_per_nt,recovery`` (``recovery`` = fraction equal to the fasta's sequence, empty without one).
     ``constraints`` ({pdb_id: (pattern, structure)}, ``read_constraints_csv``; ids not in it are unconstrained), ``bias`` (4 per-class
     floats), ``omit`` (letters never drawn) or ``wobble=False``: the draws come from ``rnampnn_design`` on the packed logits instead (no
-    scatter to the padded layout) and ``designs_csv`` gains a last column ``infeasible``."""
+    scatter to the padded layout) and ``designs_csv`` gains a last column ``infeasible``.
+    ``states`` (``read_states_csv``: {design_id: [(pdb_id, weight)]}): multi-state design - the batches are formed from whole designs with
+    their states as consecutive rows, the draws come from ``rnampnn_design_tied`` and ``designs_csv`` has one row per (design, sample):
+    ``design_id,sample,seq,infeasible,states,nll_per_nt,recovery``, the last three ``;``-joined per state."""
     model.eval()
     device = model._device()
     items = load_structures(data_path, max_len=int(model.hparams["padding_len"]))
@@ -60,7 +103,16 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     trees = getattr(model, "xgb_readout", None)
     constrained = constraints is not None or bias is not None or bool(omit) or not wobble
     seqs, designs = {}, {}
-    for bi, (coords, cu, max_len, idx) in enumerate(PackedLoader(items, bucket_batches(lengths, batch_size, max_rows, seed=0), device=device)):
+    groups = batch_groups = None
+    if states is not None:
+        if samples <= 0:
+            raise ValueError("multi-state design needs samples > 0")
+        groups = state_groups(states, [it[0] for it in items], lengths)
+        batch_groups = group_batches(groups, lengths, batch_size, max_rows)
+        batches = [[i for g in gs for i in groups[g][1]] for gs in batch_groups]
+    else:
+        batches = bucket_batches(lengths, batch_size, max_rows, seed=0)
+    for bi, (coords, cu, max_len, idx) in enumerate(PackedLoader(items, batches, device=device)):
         lens = [lengths[i] for i in idx]
         B = len(idx)
         if trees is not None:
@@ -73,7 +125,16 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             seqs[i] = s
         if samples > 0:
             bad = dnll = None
-            if constrained:
+            if groups is not None:
+                cons = None
+                if constrained:
+                    cons = batch_constraints(constraints, [items[i][0] for i in idx], lens, max_len, bias=bias, wobble=wobble,
+                                             omit=omit).to_device(device)
+                draws, dnll, bad = design_from_logits(logits, cu_seqlens=cu, max_len=max_len, n_samples=samples, temperature=temperature,
+                                                      seed=seed + bi, constraints=cons, states=[len(groups[g][1]) for g in batch_groups[bi]],
+                                                      state_weights=[w for g in batch_groups[bi] for w in groups[g][2]])
+                bad = bad.cpu().tolist()
+            elif constrained:
                 cons = batch_constraints(constraints, [items[i][0] for i in idx], lens, max_len, bias=bias, wobble=wobble, omit=omit)
                 draws, dnll, bad = design_from_logits(logits, cu_seqlens=cu, max_len=max_len, n_samples=samples, temperature=temperature,
                                                    seed=seed + bi, constraints=cons.to_device(device))
@@ -96,6 +157,16 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             sc = score_logits(logits, cu_seqlens=cu, labels=lab, seqs=draws, want=want) if want else {}
             nll = (sc["seq_nll"] if dnll is None else dnll).cpu().tolist()
             match = sc["seq_match"].cpu().tolist() if lab is not None else None
+            if groups is not None:                                  # one row per (design, sample); the states are consecutive rows
+                for s in range(samples):
+                    text, r = letters_padded(draws[s]), 0
+                    for g in batch_groups[bi]:
+                        rows = range(r, r + len(groups[g][1]))
+                        recs = [f"{match[s][k] / lens[k]:.6f}" if match is not None and have[k] else "" for k in rows]
+                        designs.setdefault(g, []).append((s, text[r], bad[r], ";".join(items[idx[k]][0] for k in rows),
+                                                          ";".join(f"{nll[s][k] / lens[k]:.6f}" for k in rows), ";".join(recs)))
+                        r += len(rows)
+                continue
             for s in range(samples):
                 for r, (i, text) in enumerate(zip(idx, letters_padded(draws[s]))):
                     rec = f"{match[s][r] / lens[r]:.6f}" if match is not None and have[r] else ""
@@ -106,7 +177,14 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
         f.write("pdb_id,seq\n")
         for rid, s in rows:
             f.write(f"{rid},{s}\n")
-    if samples > 0:
+    if groups is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(designs_csv)), exist_ok=True)
+        with open(designs_csv, "w") as f:
+            f.write("design_id,sample,seq,infeasible,states,nll_per_nt,recovery\n")
+            for g in range(len(groups)):
+                for s, text, n_bad, names, nll_nt, rec in designs[g]:
+                    f.write(f"{groups[g][0]},{s},{text},{n_bad},{names},{nll_nt},{rec}\n")
+    elif samples > 0:
         os.makedirs(os.path.dirname(os.path.abspath(designs_csv)), exist_ok=True)
         with open(designs_csv, "w") as f:
             f.write("pdb_id,sample,seq,nll_per_nt,recovery" + (",infeasible" if constrained else "") + "\n")

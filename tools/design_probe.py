@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
-"""The measurement behind DESIGN.md section 9 "Constrained design" (profiles/design_kernel_stats.txt): the C2 batch (256 RNAs x 100..140 nt),
+"""The measurement behind DESIGN.md section 9 "Constrained design" and "Multi-state design" (profiles/design_kernel_stats.txt,
+profiles/design_tied_kernel_stats.txt): the C2 batch (256 RNAs x 100..140 nt),
 S = 8 sequences per RNA.
 usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + rnampnn_score (seq_nll): the unconstrained pair of launches
        python tools/design_probe.py design [calls=50]         rnampnn_design: free, then with a hairpin's pairs + a fixed GNRA loop per RNA
+       python tools/design_probe.py tied [calls=50]           rnampnn_design (free, hairpin) and then rnampnn_design_tied: one state per group
+                                                              free, one state per group with the hairpins, 64 groups x 4 states with one 3-node chain
 HIP events around each loop of back-to-back calls of the Python wrappers.  Run either under `rocprofv3 --kernel-trace --stats -- python ...`
 (a run of its own) for the kernels' own times.  RNAMPNN_PROBE_ROOT: another checkout (with its library built) to take the package from -
 the `sample_score` leg uses nothing newer than rnampnn_score, so it runs on the parent commit as well."""
@@ -46,6 +49,7 @@ if what == "sample_score":
     timed("rnampnn_sample + rnampnn_score(seq_nll)", two_launches)
 else:
     from rnampnn.utils.constraints import DesignConstraints
+    import numpy as np
     specs = []
     for n in lens:                                                  # a hairpin: a stem of (n - 4) // 2 pairs closed by a GNRA tetraloop
         stem = (n - 4) // 2
@@ -56,3 +60,30 @@ else:
                                                                                       constraints=cons))
     seqs, nll, bad = M.design_from_logits(logits, mask=m, n_samples=S, temperature=0.1, seed=1, constraints=cons)
     print(f"infeasible positions {int(bad.sum())}, mean NLL per nt {float(nll.sum()) / (S * int(mask.sum())):.4f}")
+    if what == "tied":
+        one = [1] * B
+        timed("rnampnn_design_tied, one state per group, no constraints",
+              lambda: M.design_from_logits(logits, mask=m, n_samples=S, temperature=0.1, seed=1, states=one))
+        timed("rnampnn_design_tied, one state per group, hairpin pairs + GNRA + bias",
+              lambda: M.design_from_logits(logits, mask=m, n_samples=S, temperature=0.1, seed=1, constraints=cons, states=one))
+        t_seqs, t_nll, t_bad = M.design_from_logits(logits, mask=m, n_samples=S, temperature=0.1, seed=1, constraints=cons, states=one)
+        print(f"one state per group against rnampnn_design: {int((t_seqs != seqs).sum())} of {S * int(mask.sum())} ids differ, "
+              f"infeasible equal {bool((t_bad == bad).all())}")
+        # 64 groups x 4 states (conformers of one length); states 0 and 1 share position n // 2: the 3-node chain 5 - n // 2 - n - 6
+        lens4 = [lens[g] for g in range(B // 4) for _ in range(4)]
+        m4 = torch.zeros(B, T)
+        partner = np.full((B, T), -1, dtype=np.int32)
+        for b, n in enumerate(lens4):
+            m4[b, :n] = 1
+            if b % 4 == 0:
+                partner[b, 5], partner[b, n // 2] = n // 2, 5
+            if b % 4 == 1:
+                partner[b, n // 2], partner[b, n - 6] = n - 6, n // 2
+        m4 = m4.cuda()
+        logits4 = logits * m4[..., None]
+        cons4 = DesignConstraints(None, torch.from_numpy(partner), None, True).to_device("cuda")
+        four = [4] * (B // 4)
+        timed("rnampnn_design_tied, 64 groups x 4 states, one 3-node chain per group",
+              lambda: M.design_from_logits(logits4, mask=m4, n_samples=S, temperature=0.1, seed=1, constraints=cons4, states=four))
+        q, _, bad4 = M.design_from_logits(logits4, mask=m4, n_samples=S, temperature=0.1, seed=1, constraints=cons4, states=four)
+        print(f"64 x 4: infeasible positions {int(bad4.sum())}, rows of a group identical {bool((q.view(S, B // 4, 4, T) == q.view(S, B // 4, 4, T)[:, :, :1]).all())}")
