@@ -6,8 +6,9 @@
 // that one), the last node from lambda, then backwards each node given its successor; a cycle first draws its head class from the four
 // conditioned partition sums.  The contract is the one include/rnampnn_hip.h documents and tests/_design_tied_ref.py restates; all of the
 // draw is fp64.
-// A sibling of design.hip: one 256-thread workgroup per (group, sample), the extent / NLL / reduction of score_dev.h per state row, so
-// seq_nll is byte for byte rnampnn_score's for the written rows.  Three phases separated by barriers: (A) the thread that owns v_0 of a
+// An isolated position, a 2-node path and every selection along a chain are design_dev.h's rule - the templates k_design instantiates in
+// f32 - so one state per group draws what rnampnn_design draws.  One 256-thread workgroup per (group, sample), the extent / NLL /
+// reduction of score_dev.h per state row, so seq_nll is byte for byte rnampnn_score's for the written rows.  Three phases separated by barriers: (A) the thread that owns v_0 of a
 // component walks it and leaves the classes of its nodes in LDS (`sq`, one byte per position; lambda_k is parked in LDS at 32 bytes per
 // position, both indexed by position: nothing is allocated, nothing depends on timing); (B) every thread draws what is still open as an
 // isolated position and writes the group's rows; (C) per state the NLL.  Neighbour lists are never stored: a step recomputes them from the
@@ -15,35 +16,15 @@
 #include "design_dev.h"
 
 namespace {
-struct TiedArgs {
-    const float4* logits;        // (B*T) or (n_rows) rows of 4
-    const float* mask;           // (B,T) prefix mask, or null
-    const int32_t* cu;           // (B+1), or null
+struct TiedArgs : DesignArgs {
     const int32_t* group_cu;     // (G+1)
     const float* weight;         // (B) or null
-    const uint8_t* allowed;      // (B,T) or null
-    const int32_t* partner;      // (B,T) or null
-    const float* bias;           // 4 floats, (B,T,4), or null
-    const unsigned long long* seed_dev;
-    unsigned long long seed;
-    long long n_rows;
-    int B, T;
-    int wobble, bias_per_position;
-    float temperature;
     unsigned lds_alpha, lds_sq;  // bytes of the two LDS arrays (alpha: 0 without a partner table)
-    int8_t* seqs;                // (S,B,T)
-    float* seq_nll;              // (S,B)
-    int32_t* infeasible;         // (B)
 };
 
 struct TdGroup { int b0, M, n; };        // first row, number of states, common length
-struct TdPos { double z[4]; int m; };    // z = (sum_m weight_m logit_m + bias) / temperature; m = the AND of the states' masks (never empty)
+using TdPos = DsPos<double>;              // z = (sum_m weight_m logit_m + bias) / temperature; m = the AND of the states' masks (never empty)
 struct TdKeep { int k0, k1, over; };     // the first two distinct well-formed partners of a position in state order; over: there was a third
-
-// the first logits row of batch row b, clamped as sc_extent clamps it
-__device__ __forceinline__ long long td_row0(const TiedArgs& a, int b) {
-    return a.cu ? min(max((long long)a.cu[b], 0ll), a.n_rows) : (long long)b * a.T;
-}
 
 __device__ __forceinline__ int td_mask(const TiedArgs& a, const TdGroup& g, int t, bool& empty) {
     int m = 15;
@@ -57,7 +38,7 @@ __device__ __forceinline__ int td_mask(const TiedArgs& a, const TdGroup& g, int 
 __device__ __forceinline__ TdPos td_load(const TiedArgs& a, const TdGroup& g, int t, bool& empty) {
     double z0 = 0.0, z1 = 0.0, z2 = 0.0, z3 = 0.0;
     for (int i = 0; i < g.M; ++i) {
-        const float4 x = a.logits[td_row0(a, g.b0 + i) + t];
+        const float4 x = a.logits[sc_row0(a, g.b0 + i) + t];
         const double w = a.weight ? (double)a.weight[g.b0 + i] : 1.0;
         z0 += w * (double)x.x; z1 += w * (double)x.y; z2 += w * (double)x.z; z3 += w * (double)x.w;
     }
@@ -71,75 +52,6 @@ __device__ __forceinline__ TdPos td_load(const TiedArgs& a, const TdGroup& g, in
     p.z[0] = z0 / temp; p.z[1] = z1 / temp; p.z[2] = z2 / temp; p.z[3] = z3 / temp;
     p.m = td_mask(a, g, t, empty);
     return p;
-}
-
-// omega(c) = exp(z(c) - max over the admitted classes), 0 for a class the mask does not admit
-__device__ __forceinline__ void td_omega(const TdPos& p, double (&w)[4]) {
-    double mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-        if ((p.m >> c) & 1) mx = fmax(mx, p.z[c]);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) w[c] = ((p.m >> c) & 1) ? exp(p.z[c] - mx) : 0.0;
-}
-
-// the selection rule over the classes m admits: the first whose running sum of w exceeds u24 * 2^-24 * total, else the last admitted
-__device__ __forceinline__ int td_select(const double (&w)[4], int m, unsigned u24) {
-    double tot = 0.0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-        if ((m >> c) & 1) tot += w[c];
-    const double u = (double)u24 * (1.0 / 16777216.0) * tot;
-    int q = 0;
-    bool found = false;
-    double run = 0.0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        if (!((m >> c) & 1)) continue;
-        run += w[c];
-        if (!found) { q = c; found = run > u; }
-    }
-    return q;
-}
-
-__device__ __forceinline__ int td_draw_single(const TdPos& p, unsigned u24) {
-    double w[4];
-    td_omega(p, w);
-    return td_select(w, p.m, u24);
-}
-
-// the 2-node path: the joint-cell rule of k_design in fp64.  -> 4 a + b, or -1 when no cell exists
-__device__ __forceinline__ int td_draw_pair(const TdPos& lo, const TdPos& hi, int wobble, unsigned u24) {
-    double mx = -INFINITY;
-    int any = 0;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        const int ca = c >> 2, cb = c & 3;
-        const bool ok = ((lo.m >> ca) & 1) && ((hi.m >> cb) & 1) && ((ds_compat(ca, wobble) >> cb) & 1);
-        if (ok) { any = 1; mx = fmax(mx, lo.z[ca] + hi.z[cb]); }
-    }
-    if (!any) return -1;
-    double e[16], tot = 0.0;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        const int ca = c >> 2, cb = c & 3;
-        const bool ok = ((lo.m >> ca) & 1) && ((hi.m >> cb) & 1) && ((ds_compat(ca, wobble) >> cb) & 1);
-        e[c] = ok ? exp((lo.z[ca] + hi.z[cb]) - mx) : 0.0;
-        if (ok) tot += e[c];
-    }
-    const double u = (double)u24 * (1.0 / 16777216.0) * tot;
-    int q = 0;
-    bool found = false;
-    double run = 0.0;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        const int ca = c >> 2, cb = c & 3;
-        const bool ok = ((lo.m >> ca) & 1) && ((hi.m >> cb) & 1) && ((ds_compat(ca, wobble) >> cb) & 1);
-        if (!ok) continue;
-        run += e[c];
-        if (!found) { q = c; found = run > u; }
-    }
-    return q;
 }
 
 // every index is checked before it is used: a malformed table never causes an out-of-range access
@@ -190,16 +102,6 @@ __device__ __forceinline__ bool td_step(const TdPos& p, double (&la)[4], int wob
     return true;
 }
 
-// the weights of a chain draw: exp(lambda(c) - max over the eligible classes) for the classes in `eligible`, 0 for the others
-__device__ __forceinline__ void td_weights(const double (&la)[4], int eligible, double (&w)[4]) {
-    double mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-        if ((eligible >> c) & 1) mx = fmax(mx, la[c]);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) w[c] = ((eligible >> c) & 1) ? exp(la[c] - mx) : 0.0;
-}
-
 // The component v_0, v_1, ... of L nodes (a path from its smaller end, or a cycle from its smallest node towards the smaller neighbour),
 // walked by one thread.  Leaves the drawn classes in sq; an infeasible component leaves sq untouched (-1: every node then draws as an
 // isolated position in phase B) and counts its nodes.
@@ -209,7 +111,7 @@ __device__ __forceinline__ void td_component(const TiedArgs& a, const TdGroup& g
     const TdPos p0 = td_load(a, g, v0, e);
     if (!cyc && L == 2) {
         const TdPos p1 = td_load(a, g, v1, e);
-        const int cell = td_draw_pair(p0, p1, a.wobble, ds_u24(seed, s, g.b0, v0));
+        const int cell = ds_draw_pair(p0, p1, a.wobble, ds_u24(seed, s, g.b0, v0));
         if (cell >= 0) { sq[v0] = (int8_t)(cell >> 2); sq[v1] = (int8_t)(cell & 3); }
         else bad += 2;
         return;
@@ -230,7 +132,7 @@ __device__ __forceinline__ void td_component(const TiedArgs& a, const TdGroup& g
             const double mx = fmax(fmax(lz0, lz1), fmax(lz2, lz3));
             if (!(mx > -INFINITY)) { bad += L; return; }
             const double w[4] = {exp(lz0 - mx), exp(lz1 - mx), exp(lz2 - mx), exp(lz3 - mx)};
-            head = td_select(w, p0.m, ds_u24(seed, s, g.b0, v0));
+            head = ds_select(w, p0.m, ds_u24(seed, s, g.b0, v0));
         }
         const int hh = pass < 4 ? pass : head;
 #pragma unroll
@@ -269,17 +171,17 @@ __device__ __forceinline__ void td_component(const TiedArgs& a, const TdGroup& g
     }
     // v_{L-1} from lambda_{L-1} (a cycle: over the classes that pair with the head), then backwards: v_k from lambda_k over the classes
     // that pair with c_{k+1}
-    double w[4];
-    td_weights(la, cyc ? ds_compat(head, a.wobble) : 15, w);
-    int c_succ = td_select(w, td_mask(a, g, last, e), ds_u24(seed, s, g.b0, last));
+    double w[4];                                                   // exp(lambda(c) - max over the eligible classes), 0 for the others
+    ds_weights(la, cyc ? ds_compat(head, a.wobble) : 15, w);
+    int c_succ = ds_select(w, td_mask(a, g, last, e), ds_u24(seed, s, g.b0, last));
     sq[last] = (int8_t)c_succ;
     const int stop = cyc ? 1 : 0;
     int succ = last, cur = before;
     for (int k = L - 2; k >= stop && cur >= 0; --k) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) la[c] = alpha[(size_t)cur * 4 + c];
-        td_weights(la, ds_compat(c_succ, a.wobble), w);
-        c_succ = td_select(w, td_mask(a, g, cur, e), ds_u24(seed, s, g.b0, cur));
+        ds_weights(la, ds_compat(c_succ, a.wobble), w);
+        c_succ = ds_select(w, td_mask(a, g, cur, e), ds_u24(seed, s, g.b0, cur));
         sq[cur] = (int8_t)c_succ;
         if (k > stop) {
             const int nx = td_next(a, g, cur, succ);
@@ -305,7 +207,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_tied(TiedArgs a) {
     for (int i = 0; i < g.M; ++i) {
         int n;
         long long row0;
-        sc_extent(a.mask, a.cu, a.n_rows, a.T, g.b0 + i, tid, s_f[0], n, row0);
+        sc_extent(a, g.b0 + i, tid, s_f[0], n, row0);
         g.n = min(g.n, n);
     }
     int bad = 0;
@@ -350,7 +252,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_tied(TiedArgs a) {
         bool empty;
         if (q < 0) {
             const TdPos p = td_load(a, g, t, empty);
-            q = td_draw_single(p, ds_u24(seed, s, g.b0, t));
+            q = ds_draw_single(p, ds_u24(seed, s, g.b0, t));
         } else {
             td_mask(a, g, t, empty);
         }
@@ -371,7 +273,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_tied(TiedArgs a) {
         if (a.seq_nll) {
             int n;
             long long row0;
-            sc_extent(a.mask, a.cu, a.n_rows, a.T, g.b0 + i, tid, s_f[0], n, row0);
+            sc_extent(a, g.b0 + i, tid, s_f[0], n, row0);
             for (int t = tid; t < n; t += SC_THREADS) nll += sc_row_nll(a.logits[row0 + t], t < g.n ? (int)sq[t] : -1);
         }
         sc_block_sums(cnt, nll, unused, tid, s_i, s_f);
@@ -390,19 +292,14 @@ extern "C" int rnampnn_design_tied(const float* logits, int64_t n_rows, const fl
                                    const uint64_t* seed_dev, const uint8_t* allowed, const int32_t* partner, int32_t wobble,
                                    const float* bias, int32_t bias_per_position, int8_t* seqs, float* seq_nll, int32_t* infeasible,
                                    void* stream) {
-    if (!logits || B <= 0 || T <= 0)
-        return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_tied: null logits or empty batch (B = %d, T = %d)", (int)B, (int)T);
-    if (!group_cu || G <= 0) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_tied: null group_cu or no group (G = %d)", (int)G);
-    if (S <= 0) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_tied: S = %d sequences per group", (int)S);
-    if (S + 1 > 65535) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_tied: at most 65534 sequences per call");
-    if ((mask != nullptr) == (cu_seqlens != nullptr))
-        return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_tied: pass exactly one of mask (padded logits) and cu_seqlens (packed logits)");
-    if (!(temperature > 0.f) || !(temperature <= 3.402823466e38f))
-        return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_tied: the temperature must be positive and finite (got %g)", (double)temperature);
-    if (((uintptr_t)logits & 15) != 0) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_tied: logits must be 16-byte aligned");
-    if (bias && bias_per_position && ((uintptr_t)bias & 15) != 0)
-        return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_tied: a per-position bias must be 16-byte aligned");
-    if (cu_seqlens && n_rows < 0) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_tied: negative row count");
+    TiedArgs a{};
+    const ScDraw draw{S, "group", temperature, bias, bias_per_position};
+    const int rc = sc_check_args("rnampnn_design_tied", logits, n_rows, mask, cu_seqlens, B, T, &draw, a, [&](int slot) {
+        if (slot == 0 && (!group_cu || G <= 0))
+            return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_tied: null group_cu or no group (G = %d)", (int)G);
+        return RNAMPNN_OK;
+    });
+    if (rc != RNAMPNN_OK) return rc;
     if (!seqs && !seq_nll && !infeasible) return RNAMPNN_OK;    // nothing asked for
     // LDS by position: 32 bytes of alpha (with a partner table only) + 1 byte of class id, + the reduction's 48 bytes
     constexpr size_t LDS_MAX = 160 * 1024;
@@ -410,17 +307,9 @@ extern "C" int rnampnn_design_tied(const float* logits, int64_t n_rows, const fl
     if (lds > LDS_MAX)
         return fail(RNAMPNN_ERR_UNSUPPORTED, "rnampnn_design_tied: T = %d needs %zu bytes of LDS, the limit is %zu (T <= %d with a partner table)",
                     (int)T, lds, LDS_MAX, (int)((LDS_MAX - 64 - 15) / 33));
-    TiedArgs a{};
-    a.logits = reinterpret_cast<const float4*>(logits);
-    a.mask = mask; a.cu = cu_seqlens; a.group_cu = group_cu; a.weight = weight;
-    a.allowed = allowed; a.partner = partner; a.bias = bias;
-    a.seed_dev = reinterpret_cast<const unsigned long long*>(seed_dev);
-    a.seed = (unsigned long long)seed;
-    a.n_rows = mask ? (long long)B * T : (long long)n_rows;
-    a.B = B; a.T = T; a.wobble = wobble ? 1 : 0; a.bias_per_position = bias_per_position ? 1 : 0;
-    a.temperature = temperature;
+    ds_fill(a, seed, seed_dev, allowed, partner, wobble, bias, bias_per_position, temperature, seqs, seq_nll, infeasible);
+    a.group_cu = group_cu; a.weight = weight;
     a.lds_alpha = (unsigned)lds_alpha; a.lds_sq = (unsigned)lds_sq;
-    a.seqs = seqs; a.seq_nll = seq_nll; a.infeasible = infeasible;
     const int passes = (seqs || seq_nll) ? S : 1;               // the count of infeasible positions is that of sample 0
     static DevAttr attr;
     ensure_dyn_lds((const void*)k_design_tied, lds, attr);

@@ -5,20 +5,10 @@
 // atomics, so two calls give identical bytes.  About 20 bytes per nucleotide: the call is bounded by its three launches, not by bandwidth.
 // No runtime fill / copy nodes, no host synchronisation.
 #include "rdesign_internal.h"
+#include "score_dev.h"
 
 namespace {
 constexpr int RDS_THREADS = 256;
-
-__device__ __forceinline__ int rds_wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float rds_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // len / cu come from the mask the caller handed in: they are clamped to the tensors' extents (T, n_rows), so a mask that is not the
 // collate's prefix mask gives meaningless numbers but no out-of-bounds access.
@@ -40,11 +30,8 @@ __global__ void __launch_bounds__(RDS_THREADS) k_rd_score(const float4* __restri
         int best;
         if (FROM_LOGITS) {
             const float4 x = logits[p];
-            float m = x.x;                                     // first maximum wins (numpy.argmax)
-            best = 0;
-            if (x.y > m) { m = x.y; best = 1; }
-            if (x.z > m) { m = x.z; best = 2; }
-            if (x.w > m) { m = x.w; best = 3; }
+            float m;
+            best = sc_argmax(x, m);
             if (nll) {                                         // logsumexp(x) - x[label]
                 const float se = expf(x.x - m) + expf(x.y - m) + expf(x.z - m) + expf(x.w - m);
                 const float xl = lab == 0 ? x.x : lab == 1 ? x.y : lab == 2 ? x.z : x.w;
@@ -56,8 +43,8 @@ __global__ void __launch_bounds__(RDS_THREADS) k_rd_score(const float4* __restri
         c += best == lab ? 1 : 0;
         if (pred_out) pred_out[p] = best;
     }
-    c = rds_wave_sum(c);
-    l = rds_wave_sum(l);
+    c = sc_wave_sum(c);
+    l = sc_wave_sum(l);
     if ((tid & 63) == 0) { s_c[tid >> 6] = c; s_l[tid >> 6] = l; }
     __syncthreads();
     if (tid == 0) {

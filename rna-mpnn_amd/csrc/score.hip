@@ -10,14 +10,10 @@
 #include "score_dev.h"
 
 namespace {
-struct ScoreArgs {
-    const float4* logits;        // (B*T) or (n_rows) rows of 4
-    const float* mask;           // (B,T) prefix mask, or null
-    const int32_t* cu;           // (B+1), or null
+struct ScoreArgs : ScRows {
     const int32_t* labels;       // (B,T) or null
     const int8_t* seqs;          // (S,B,T) or null
-    long long n_rows;            // rows the logits tensor holds
-    int B, T, S;
+    int S;
     int pass0;                   // 1: pass 0 (the label / decode pass) has an output to write
     int32_t* valid;              // (B)
     int8_t* pred;                // (B,T)
@@ -35,18 +31,15 @@ __global__ void __launch_bounds__(SC_THREADS) k_score(ScoreArgs a) {
     const int pass = (int)blockIdx.y + (a.pass0 ? 0 : 1);
     int n;
     long long row0;
-    sc_extent(a.mask, a.cu, a.n_rows, a.T, b, tid, s_f[0], n, row0);
+    sc_extent(a, b, tid, s_f[0], n, row0);
     const size_t lab0 = (size_t)b * a.T;
     int cnt = 0;
     float nll = 0.f, loss = 0.f;
     if (pass == 0) {
         for (int t = tid; t < n; t += SC_THREADS) {
             const float4 x = a.logits[row0 + t];
-            float m = x.x;                                     // first maximum wins (torch.argmax, rnampnn_argmax_recovery)
-            int best = 0;
-            if (x.y > m) { m = x.y; best = 1; }
-            if (x.z > m) { m = x.z; best = 2; }
-            if (x.w > m) { m = x.w; best = 3; }
+            float m;
+            const int best = sc_argmax(x, m);
             if (a.pred) a.pred[lab0 + t] = (int8_t)best;
             if (a.labels) {
                 const int lab = a.labels[lab0 + t];
@@ -93,22 +86,19 @@ __global__ void __launch_bounds__(SC_THREADS) k_score(ScoreArgs a) {
 extern "C" int rnampnn_score(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, const int32_t* labels,
                              const int8_t* seqs, int32_t S, int32_t B, int32_t T, int32_t* valid, int8_t* pred, int32_t* correct,
                              float* label_nll, float* label_loss, float* seq_nll, int32_t* seq_match, void* stream) {
-    if (!logits || B <= 0 || T <= 0) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: null logits or empty batch (B = %d, T = %d)", (int)B, (int)T);
-    if ((mask != nullptr) == (cu_seqlens != nullptr))
-        return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: pass exactly one of mask (padded logits) and cu_seqlens (packed logits)");
-    if (((uintptr_t)logits & 15) != 0) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: logits must be 16-byte aligned");
-    if (S < 0) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: S = %d candidate sequences", (int)S);
-    if ((S > 0) != (seqs != nullptr)) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: seqs and S > 0 go together");
-    if ((seq_nll || seq_match) && !seqs) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: seq_nll / seq_match need seqs");
-    if ((correct || seq_match || label_nll || label_loss) && !labels)
-        return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: correct / seq_match / label_nll / label_loss need labels");
-    if (cu_seqlens && n_rows < 0) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: negative row count");
-    if (S + 1 > 65535) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: at most 65534 sequences per call");
     ScoreArgs a{};
-    a.logits = reinterpret_cast<const float4*>(logits);
-    a.mask = mask; a.cu = cu_seqlens; a.labels = labels; a.seqs = seqs;
-    a.n_rows = mask ? (long long)B * T : (long long)n_rows;
-    a.B = B; a.T = T; a.S = S;
+    const int rc = sc_check_args("rnampnn_score", logits, n_rows, mask, cu_seqlens, B, T, nullptr, a, [&](int slot) {
+        if (slot != 1) return RNAMPNN_OK;
+        if (S < 0) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: S = %d candidate sequences", (int)S);
+        if ((S > 0) != (seqs != nullptr)) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: seqs and S > 0 go together");
+        if ((seq_nll || seq_match) && !seqs) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: seq_nll / seq_match need seqs");
+        if ((correct || seq_match || label_nll || label_loss) && !labels)
+            return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: correct / seq_match / label_nll / label_loss need labels");
+        return RNAMPNN_OK;
+    });
+    if (rc != RNAMPNN_OK) return rc;
+    if (S + 1 > 65535) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_score: at most 65534 sequences per call");
+    a.labels = labels; a.seqs = seqs; a.S = S;
     a.pass0 = (valid || pred || correct || label_nll || label_loss) ? 1 : 0;
     a.valid = valid; a.pred = pred; a.correct = correct; a.label_nll = label_nll; a.label_loss = label_loss;
     a.seq_nll = seq_nll; a.seq_match = seq_match;

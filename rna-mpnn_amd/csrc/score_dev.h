@@ -1,12 +1,48 @@
-// Device pieces shared by the two per-(RNA, pass) kernels on f32 logits, k_score (score.hip) and k_design (design.hip): the extent of an
-// RNA in either layout, the NLL of one row and the fixed-order workgroup sums.  One definition of each, so that the likelihood k_design
-// writes for its own draws is byte for byte the one k_score returns for them.
+// Pieces shared by the per-(RNA, pass) kernels on f32 logits, k_score (score.hip), k_design (design.hip) and k_design_tied
+// (design_tied.hip), and by k_rd_score (rdesign_score.hip): the argument checks of the three entries, the extent of an RNA in either
+// layout, the first-maximum argmax and the NLL of one row, and the fixed-order workgroup sums.  One definition of each, so that the
+// likelihood the design kernels write for their own draws is byte for byte the one k_score returns for them.
 #pragma once
 #include "api_internal.h"
 
 namespace {
 constexpr int SC_THREADS = 256;
 constexpr int SC_WAVES = SC_THREADS / 64;
+
+struct ScRows {                  // the logits of a batch in either layout: what the three kernels' argument structs start with
+    const float4* logits;        // (B*T) or (n_rows) rows of 4
+    const float* mask;           // (B,T) prefix mask, or null
+    const int32_t* cu;           // (B+1), or null
+    int B, T;
+    long long n_rows;            // rows the logits tensor holds
+};
+struct ScDraw { int S; const char* per; float temperature; const float* bias; int bias_per_position; };   // what only a design entry checks
+
+// The argument checks rnampnn_score, rnampnn_design and rnampnn_design_tied share, in the order they fire, and the fields of ScRows.
+// `draw`: the S / temperature / bias checks of a design entry (null for rnampnn_score).  `own(slot)`: the entry's own checks that fire
+// in between - slot 0 after the batch check, slot 1 after the alignment checks; it returns what fail() returned, or RNAMPNN_OK.
+template <typename Own>
+int sc_check_args(const char* name, const float* logits, int64_t n_rows, const float* mask, const int32_t* cu, int32_t B, int32_t T,
+                  const ScDraw* draw, ScRows& a, Own own) {
+    if (!logits || B <= 0 || T <= 0) return fail(RNAMPNN_ERR_BAD_ARG, "%s: null logits or empty batch (B = %d, T = %d)", name, (int)B, (int)T);
+    if (int rc = own(0)) return rc;
+    if (draw && draw->S <= 0) return fail(RNAMPNN_ERR_BAD_ARG, "%s: S = %d sequences per %s", name, draw->S, draw->per);
+    if (draw && draw->S + 1 > 65535) return fail(RNAMPNN_ERR_BAD_ARG, "%s: at most 65534 sequences per call", name);
+    if ((mask != nullptr) == (cu != nullptr))
+        return fail(RNAMPNN_ERR_BAD_ARG, "%s: pass exactly one of mask (padded logits) and cu_seqlens (packed logits)", name);
+    if (draw && (!(draw->temperature > 0.f) || !(draw->temperature <= 3.402823466e38f)))
+        return fail(RNAMPNN_ERR_BAD_ARG, "%s: the temperature must be positive and finite (got %g)", name, (double)draw->temperature);
+    if (((uintptr_t)logits & 15) != 0) return fail(RNAMPNN_ERR_BAD_ARG, "%s: logits must be 16-byte aligned", name);
+    if (draw && draw->bias && draw->bias_per_position && ((uintptr_t)draw->bias & 15) != 0)
+        return fail(RNAMPNN_ERR_BAD_ARG, "%s: a per-position bias must be 16-byte aligned", name);
+    if (int rc = own(1)) return rc;
+    if (cu && n_rows < 0) return fail(RNAMPNN_ERR_BAD_ARG, "%s: negative row count", name);
+    a.logits = reinterpret_cast<const float4*>(logits);
+    a.mask = mask; a.cu = cu;
+    a.n_rows = mask ? (long long)B * T : (long long)n_rows;
+    a.B = B; a.T = T;
+    return RNAMPNN_OK;
+}
 
 __device__ __forceinline__ int sc_wave_sum(int v) {
 #pragma unroll
@@ -19,21 +55,25 @@ __device__ __forceinline__ float sc_wave_sum(float v) {
     return v;
 }
 
+// the first logits row of batch row b: b * T in the padded layout, cu[b] clamped to the rows the tensor holds in the packed one
+__device__ __forceinline__ long long sc_row0(const ScRows& a, int b) {
+    return a.cu ? min(max((long long)a.cu[b], 0ll), a.n_rows) : (long long)b * a.T;
+}
+
 // The length and the first logits row of RNA b.  Both come from caller data (a mask that need not be the collate's prefix mask, a cu that
 // need not be a prefix sum): they are clamped to the tensors' extents, so a malformed input gives meaningless numbers but no out-of-bounds
 // access.  The mask row is summed as k_lengths sums it (the forward's own length of the RNA).  Every thread of the workgroup calls it
 // (two barriers in the padded layout); s_tmp holds SC_WAVES floats and is free again on return.
-__device__ __forceinline__ void sc_extent(const float* mask, const int32_t* cu, long long n_rows, int T, int b, int tid, float* s_tmp,
-                                          int& n, long long& row0) {
-    if (cu) {
-        const long long lo = min(max((long long)cu[b], 0ll), n_rows);
-        const long long len = min(max((long long)cu[b + 1] - (long long)cu[b], 0ll), (long long)T);
-        n = (int)min(len, n_rows - lo);
-        row0 = lo;
+__device__ __forceinline__ void sc_extent(const ScRows& a, int b, int tid, float* s_tmp, int& n, long long& row0) {
+    const int T = a.T;
+    if (a.cu) {
+        row0 = sc_row0(a, b);
+        const long long len = min(max((long long)a.cu[b + 1] - (long long)a.cu[b], 0ll), (long long)T);
+        n = (int)min(len, a.n_rows - row0);
         return;
     }
     float s = 0.f;
-    for (int t = tid; t < T; t += SC_THREADS) s += mask[(size_t)b * T + t];
+    for (int t = tid; t < T; t += SC_THREADS) s += a.mask[(size_t)b * T + t];
     s = sc_wave_sum(s);
     if ((tid & 63) == 0) s_tmp[tid >> 6] = s;
     __syncthreads();
@@ -43,7 +83,17 @@ __device__ __forceinline__ void sc_extent(const float* mask, const int32_t* cu, 
     __syncthreads();                                           // s_tmp is reused by the reductions below
     n = tot >= 0.f ? (int)fminf(tot + 0.5f, (float)T) : 0;      // (a NaN sum compares false: 0)
     n = min(max(n, 0), T);
-    row0 = (long long)b * T;
+    row0 = sc_row0(a, b);
+}
+
+// argmax of a row, the first maximum wins (torch.argmax, numpy.argmax, rnampnn_argmax_recovery); m <- the maximum
+__device__ __forceinline__ int sc_argmax(const float4 x, float& m) {
+    int best = 0;
+    m = x.x;
+    if (x.y > m) { m = x.y; best = 1; }
+    if (x.z > m) { m = x.z; best = 2; }
+    if (x.w > m) { m = x.w; best = 3; }
+    return best;
 }
 
 // logsumexp(x) - x[q]: the NLL of class q under one row of logits (any q outside 0..2 reads class 3)

@@ -33,6 +33,7 @@ import torch.nn.functional as F
 
 from .. import _native
 from rnampnn.model._base import _prep, _stream
+from rnampnn.model.decode import check_state_lengths, design_from_logits, letters_packed, score_logits
 
 _PREC = {"f32": _native.PREC_F32, "bf16": _native.PREC_BF16}
 _TRAIN = {"f32": _native.TRAIN_F32, "bf16": _native.TRAIN_BF16_MIXED}
@@ -433,7 +434,6 @@ class RNAModel(nn.Module):
         pairs, bias) or None for free draws.  ``lengths`` as in ``score_batch``.  ``states`` / ``state_weights``: multi-state design
         (``rnampnn_design_tied`` through ``design_from_logits``): consecutive rows of a group are states of ONE design and receive the same
         sequence; with host ``lengths`` a group whose states differ in length is a ``ValueError`` naming the group."""
-        from rnampnn.model.rnampnn import check_state_lengths, design_from_logits
         if states is not None and lengths is not None:
             check_state_lengths(states, lengths)
         logits, cu, T = self._packed_logits(X, mask, lengths)
@@ -445,7 +445,6 @@ class RNAModel(nn.Module):
         """Likelihood of given sequences under this model: ``seqs`` (S,B,T) or (B,T) class ids (``design``'s int8 output; entries on
         padding are never read) -> (seq_nll (S,B) f32, seq_match (S,B) int32 = #(seq == label) or None without ``labels`` (B,T) class
         ids, valid (B,) int32).  One forward + one ``rnampnn_score`` on the packed logits."""
-        from rnampnn.model.rnampnn import score_logits
         logits, cu, T = self._packed_logits(X, mask, lengths)
         want = ("seq_nll", "valid") + (("seq_match",) if labels is not None else ())
         out = score_logits(logits, cu_seqlens=cu, labels=labels, seqs=seqs if seqs.dim() == 3 else seqs.unsqueeze(0), want=want, max_len=T)
@@ -502,12 +501,7 @@ class RNAModel(nn.Module):
         """The sequences ``predict`` writes, one string per RNA of the batch (one device-to-host copy of the packed class ids)."""
         if lengths is None:
             lengths = mask.sum(dim=1).to(torch.int64).tolist()
-        ids = self._predict_packed(X, mask, lengths).tolist()
-        out, start = [], 0
-        for n in (int(v) for v in lengths):
-            out.append("".join("AUCG"[i] for i in ids[start:start + n]))
-            start += n
-        return out
+        return letters_packed(self._predict_packed(X, mask, lengths), lengths)
 
     # ------------------------------------------------------------------ training step (exact f32, or bf16-mixed by train_precision)
     def _train_args(self, dropout, seed):

@@ -4,9 +4,10 @@ from __future__ import annotations
 import os
 from typing import List, Optional, Tuple
 
-from rnampnn.model.rnampnn import design_from_logits, letters_padded, score_logits
+from rnampnn.model.decode import design_from_logits, letters_padded, score_logits
 from rnampnn.utils.constraints import batch_constraints
 from rnampnn.utils.data import bucket_batches
+from rnampnn.utils.predict import write_csv
 
 from .data import load_rna_dir, padded_loader
 
@@ -42,19 +43,10 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             nll, bad = nll.cpu().tolist(), bad.cpu().tolist()
             for s in range(samples):
                 for r, (i, text) in enumerate(zip(idx, letters_padded(draws[s]))):
-                    designs.setdefault(i, []).append((s, text, nll[s][r] / lens[r], match[s][r] / lens[r], bad[r]))
+                    designs.setdefault(i, []).append((s, text, f"{nll[s][r] / lens[r]:.6f}", f"{match[s][r] / lens[r]:.6f}", bad[r]))
     rows = [(items[i][0], seqs[i]) for i in range(len(items))]
-    out_dir = os.path.dirname(os.path.abspath(out_csv))
-    os.makedirs(out_dir, exist_ok=True)
-    with open(out_csv, "w") as f:
-        f.write("pdb_id,seq\n")
-        for rid, s in rows:
-            f.write(f"{rid},{s}\n")
+    write_csv(out_csv, "pdb_id,seq", rows)
     if samples > 0:
-        os.makedirs(os.path.dirname(os.path.abspath(designs_csv)), exist_ok=True)
-        with open(designs_csv, "w") as f:
-            f.write("pdb_id,sample,seq,nll_per_nt,recovery,infeasible\n")
-            for i in range(len(items)):
-                for s, text, nll_nt, rec, n_bad in designs[i]:
-                    f.write(f"{items[i][0]},{s},{text},{nll_nt:.6f},{rec:.6f},{n_bad}\n")
+        write_csv(designs_csv, "pdb_id,sample,seq,nll_per_nt,recovery,infeasible",
+                  [(it[0],) + row for i, it in enumerate(items) for row in designs[i]])
     return rows

@@ -12,9 +12,8 @@ reference counterpart): ``sample()``, ``design()``, ``score_s
 from __future__ import annotations
 
 import ctypes as C
-import itertools
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import List, Optional
 
 import torch
 from torch import nn
@@ -24,6 +23,8 @@ from .. import _native
 from ..config.glob import DEFAULT_SEED, REVERSE_VOCAB
 from ..utils.data import check_prefix_mask
 from ._base import NativeModule, _prep, _ptr, _stream
+from .decode import (SCORE_OUTPUTS, argmax_recovery, check_state_lengths, design_from_logits, letters_packed,  # noqa: F401
+                     letters_padded, sample_from_logits, score_logits)
 from ._schema import DEFAULT_HPARAMS
 
 _CHECK_MASKS = os.environ.get("RNAMPNN_CHECK_MASKS", "0") == "1"
@@ -729,193 +730,6 @@ class _TrainForward(torch.autograd.Function):
     def backward(ctx, dlogits):
         ctx.model._train_backward_native(dlogits, ctx.lease)
         return (None,) * (6 + ctx.n_params)
-
-
-def argmax_recovery(logits: torch.Tensor, mask: torch.Tensor, labels: Optional[torch.Tensor]
-                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """HIP decode kernel: (pred int8 (B,T) with -1 on padding, correct int32 (B,), valid int32 (B,))."""
-    device = logits.device
-    B, T = int(logits.shape[0]), int(logits.shape[1])
-    lg, m = _prep(logits, device), _prep(mask, device)
-    lab = None if labels is None else _prep(labels, device, torch.int32)
-    pred = torch.empty(B, T, dtype=torch.int8, device=device)
-    correct = torch.zeros(B, dtype=torch.int32, device=device)
-    nvalid = torch.zeros(B, dtype=torch.int32, device=device)
-    with torch.cuda.device(device):
-        _native.check(_native.lib().rnampnn_argmax_recovery(_ptr(lg), _ptr(m), _ptr(lab), B, T, _ptr(pred),
-                                                            _ptr(correct), _ptr(nvalid), _stream(device)))
-    return pred, correct, nvalid
-
-
-def sample_from_logits(logits: torch.Tensor, mask: torch.Tensor, temperature: float, n_samples: int, seed: int = 0
-                       ) -> torch.Tensor:
-    device = logits.device
-    B, T = int(logits.shape[0]), int(logits.shape[1])
-    lg, m = _prep(logits, device), _prep(mask, device)
-    out = torch.empty(n_samples, B, T, dtype=torch.int8, device=device)
-    with torch.cuda.device(device):
-        _native.check(_native.lib().rnampnn_sample(_ptr(lg), _ptr(m), B, T, float(temperature), int(n_samples),
-                                                   C.c_uint64(int(seed) & (2 ** 64 - 1)), _ptr(out), _stream(device)))
-    return out
-
-
-def check_state_lengths(states, lengths) -> None:
-    """Multi-state design: the states of a group are conformers of ONE RNA.  ``ValueError`` naming the group when ``states`` does not
-    partition the rows or a group's rows differ in length."""
-    counts = [int(v) for v in states]
-    if any(v < 0 for v in counts) or sum(counts) != len(lengths):
-        raise ValueError(f"states must be non-negative row counts that sum to B = {len(lengths)}, got {counts}")
-    lo = 0
-    for g, k in enumerate(counts):
-        if len({int(n) for n in lengths[lo:lo + k]}) > 1:
-            raise ValueError(f"group {g} (rows {lo}..{lo + k - 1}): its states differ in length {[int(n) for n in lengths[lo:lo + k]]}")
-        lo += k
-
-
-def design_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
-                       max_len: Optional[int] = None, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None,
-                       states=None, state_weights=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """``rnampnn_design`` (include/rnampnn_hip.h): ``n_samples`` constrained draws per RNA from f32 logits and their scores in one launch
-    -> (seqs int8 (S,B,T), -1 on padding; seq_nll (S,B) f32 = ``score_logits``' ``seq_nll`` of the draws; infeasible (B,) int32).  Padded
-    layout: logits (B,T,4) + ``mask`` (B,T); packed layout: logits (N,4) + ``cu_seqlens`` (B+1), the padded extent T from the constraints'
-    tensors or ``max_len``.  ``constraints``: a ``DesignConstraints`` (padded (B,T) tensors in both layouts) or None for a free draw.
-    ``states``: multi-state design (``rnampnn_design_tied``) - a sequence of row counts, one per group, that sums to B; the consecutive rows
-    of a group are the states (conformers, the backbones of a switch) of ONE design: they receive the same sequence, drawn exactly from the
-    product of their distributions under the union of their base-pair tables; ``seq_nll`` stays per row, ``infeasible`` is the group's count
-    on each of its rows.  ``state_weights`` (B,) per row (default 1; negative = design against that state).  ``None`` keeps ``rnampnn_design``.
-    CUDA logits only (there is no CPU fallback); no host synchronisation."""
-    device = logits.device
-    if device.type != "cuda":
-        raise RuntimeError("rnampnn_design runs on an MI355X: pass CUDA logits (there is no CPU fallback)")
-    lg = _prep(logits, device)
-    m = None if mask is None else _prep(mask, device)
-    cu = None if cu_seqlens is None else _prep(cu_seqlens, device, torch.int32)
-    c = constraints
-    al = None if c is None or c.allowed is None else _prep(c.allowed, device, torch.uint8)
-    pa = None if c is None or c.partner is None else _prep(c.partner, device, torch.int32)
-    bi = None if c is None or c.bias is None else _prep(c.bias, device)
-    if m is not None:
-        B, T = int(m.shape[0]), int(m.shape[1])
-    else:
-        B = (int(cu.numel()) - 1) if cu is not None else int(lg.shape[0])
-        shaped = next((t for t in (al, pa) if t is not None), None)
-        T = int(max_len) if max_len is not None else int(shaped.shape[-1]) if shaped is not None else 0
-    for name, t in (("allowed", al), ("partner", pa)):
-        if t is not None and tuple(t.shape) != (B, T):
-            raise ValueError(f"constraints.{name} must be padded to (B, T) = {(B, T)}, got {tuple(t.shape)}")
-    per_position = 0
-    if bi is not None:
-        if tuple(bi.shape) == (B, T, 4):
-            per_position = 1
-        elif tuple(bi.shape) != (4,):
-            raise ValueError(f"constraints.bias must be (4,) or (B, T, 4) = {(B, T, 4)}, got {tuple(bi.shape)}")
-    if lg.shape[-1] != 4 or lg.numel() < (4 * B * T if m is not None else 0):
-        raise ValueError(f"logits must be (B, T, 4) with the mask or (N, 4) with cu_seqlens, got {tuple(lg.shape)}")
-    S = int(n_samples)
-    seqs = torch.empty(max(S, 0), max(B, 0), max(T, 0), dtype=torch.int8, device=device)
-    nll = torch.empty(max(S, 0), max(B, 0), dtype=torch.float32, device=device)
-    bad = torch.empty(max(B, 0), dtype=torch.int32, device=device)
-    if states is None and state_weights is not None:
-        raise ValueError("state_weights belong to multi-state design: pass states as well")
-    if states is not None:
-        counts = [int(v) for v in states]
-        if any(v < 0 for v in counts) or sum(counts) != B:
-            raise ValueError(f"states must be non-negative row counts that sum to B = {B}, got {counts}")
-        gcu = torch.tensor([0] + list(itertools.accumulate(counts)), dtype=torch.int32).to(device, non_blocking=True)
-        sw = None if state_weights is None else _prep(torch.as_tensor(state_weights, dtype=torch.float32), device)
-        if sw is not None and tuple(sw.shape) != (B,):
-            raise ValueError(f"state_weights must be (B,) = {(B,)}, got {tuple(sw.shape)}")
-        with torch.cuda.device(device):
-            _native.check(_native.lib().rnampnn_design_tied(
-                _ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(cu), B, T, _ptr(gcu), len(counts), _ptr(sw), float(temperature), S,
-                C.c_uint64(int(seed) & (2 ** 64 - 1)), None, _ptr(al), _ptr(pa), int(bool(c.wobble)) if c is not None else 1, _ptr(bi),
-                per_position, _ptr(seqs), _ptr(nll), _ptr(bad), _stream(device)))
-        return seqs, nll, bad
-    with torch.cuda.device(device):
-        _native.check(_native.lib().rnampnn_design(
-            _ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(cu), B, T, float(temperature), S, C.c_uint64(int(seed) & (2 ** 64 - 1)), None,
-            _ptr(al), _ptr(pa), int(bool(c.wobble)) if c is not None else 1, _ptr(bi), per_position, _ptr(seqs), _ptr(nll), _ptr(bad),
-            _stream(device)))
-    return seqs, nll, bad
-
-
-SCORE_OUTPUTS = {"valid": torch.int32, "pred": torch.int8, "correct": torch.int32, "label_nll": torch.float32, "label_loss": torch.float32,
-                 "seq_nll": torch.float32, "seq_match": torch.int32}
-
-
-def score_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
-                 labels: Optional[torch.Tensor] = None, seqs: Optional[torch.Tensor] = None,
-                 want=("valid", "correct", "label_nll", "label_loss"), max_len: Optional[int] = None, out: Optional[Dict] = None,
-                 n_seqs: Optional[int] = None) -> Dict[str, torch.Tensor]:
-    """``rnampnn_score`` (include/rnampnn_hip.h): per-RNA scores of f32 logits in one launch -> dict of the outputs named in ``want``
-    (``SCORE_OUTPUTS``).  Padded layout: logits (B,T,4) + ``mask`` (B,T); packed layout: logits (N,4) + ``cu_seqlens`` (B+1), with the
-    padded extent T taken from ``labels`` / ``seqs`` / ``max_len``.  ``labels`` (B,T) class ids and ``seqs`` (S,B,T) are padded in both.
-    ``out``: caller-owned tensors to write into (by name); ``n_seqs``: S when it is not ``seqs.shape[0]``.  No host synchronisation."""
-    device = logits.device
-    if device.type != "cuda":
-        raise RuntimeError("rnampnn_score runs on an MI355X: pass CUDA logits (there is no CPU fallback)")
-    unknown = set(want) - set(SCORE_OUTPUTS)
-    if unknown:
-        raise ValueError(f"unknown outputs {sorted(unknown)}; choose from {sorted(SCORE_OUTPUTS)}")
-    lg = _prep(logits, device)
-    m = None if mask is None else _prep(mask, device)
-    cu = None if cu_seqlens is None else _prep(cu_seqlens, device, torch.int32)
-    lab = None if labels is None else _prep(labels, device, torch.int32)
-    sq = None if seqs is None else _prep(seqs, device, torch.int8)
-    if m is not None:
-        B, T = int(m.shape[0]), int(m.shape[1])
-    else:
-        B = (int(cu.numel()) - 1) if cu is not None else int(lg.shape[0])
-        T = int(lab.shape[-1]) if lab is not None else int(sq.shape[-1]) if sq is not None else int(max_len or 0)
-    if max_len is not None and m is None:
-        T = int(max_len)
-    S = int(n_seqs) if n_seqs is not None else (0 if sq is None else int(sq.shape[0]))
-    for name, t in (("labels", lab), ("seqs", sq)):
-        if t is not None and (tuple(t.shape[-2:]) != (B, T) or (name == "seqs" and (t.dim() != 3 or t.shape[0] < S))):
-            raise ValueError(f"{name} must be padded to (..., B, T) = {(B, T)}, got {tuple(t.shape)}")
-    if lg.shape[-1] != 4 or lg.numel() < (4 * B * T if m is not None else 0):
-        raise ValueError(f"logits must be (B, T, 4) with the mask or (N, 4) with cu_seqlens, got {tuple(lg.shape)}")
-    shapes = {"valid": (B,), "pred": (B, T), "correct": (B,), "label_nll": (B,), "label_loss": (B,), "seq_nll": (max(S, 0), B),
-              "seq_match": (max(S, 0), B)}
-    res, ptrs = {}, {}
-    for name in want:
-        t = None if out is None else out.get(name)
-        if t is None:
-            # (an output asked for is a non-null pointer even where S = 0 leaves it empty: the library decides what that means)
-            numel = int(torch.Size(shapes[name]).numel())
-            buf = torch.empty(max(numel, 1), dtype=SCORE_OUTPUTS[name], device=device)
-            t, ptrs[name] = buf[:numel].view(shapes[name]), C.c_void_p(buf.data_ptr())
-        elif t.dtype != SCORE_OUTPUTS[name] or tuple(t.shape) != shapes[name] or not t.is_contiguous() or t.device != device:
-            raise ValueError(f"out[{name!r}] must be a contiguous {SCORE_OUTPUTS[name]} tensor of shape {shapes[name]} on {device}")
-        else:
-            ptrs[name] = _ptr(t)
-        res[name] = t
-    n_rows = int(lg.numel()) // 4
-    with torch.cuda.device(device):
-        _native.check(_native.lib().rnampnn_score(_ptr(lg), n_rows, _ptr(m), _ptr(cu), _ptr(lab), _ptr(sq), S, B, T,
-                                                  *[ptrs.get(name) for name in SCORE_OUTPUTS], _stream(device)))
-    return res
-
-
-_LETTERS = b"\0" + "".join(REVERSE_VOCAB[i] for i in range(len(REVERSE_VOCAB))).encode()
-
-
-def letters_padded(pred: torch.Tensor) -> List[str]:
-    """(B,T) class ids with -1 on padding (``rnampnn_score``'s ``pred``) -> one string per RNA: one lookup on the device, one copy."""
-    lut = torch.frombuffer(bytearray(_LETTERS), dtype=torch.uint8).to(pred.device)
-    rows = lut[pred.to(torch.int64) + 1].cpu().numpy()
-    return [row.tobytes().split(b"\0", 1)[0].decode() for row in rows]
-
-
-def letters_packed(ids: torch.Tensor, lengths) -> List[str]:
-    """Packed class ids (N,) + host-side lengths -> one string per RNA: one lookup on the device, one copy."""
-    lut = torch.frombuffer(bytearray(_LETTERS[1:]), dtype=torch.uint8).to(ids.device)
-    flat = lut[ids.to(torch.int64)].cpu().numpy().tobytes().decode()
-    res, start = [], 0
-    for n in (int(v) for v in lengths):
-        res.append(flat[start:start + n])
-        start += n
-    return res
 
 
 class CapturedSampler:

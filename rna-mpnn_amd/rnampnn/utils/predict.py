@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from ..config.glob import VOCAB
-from ..model.rnampnn import design_from_logits, letters_packed, letters_padded, sample_from_logits, score_logits
+from ..model.decode import design_from_logits, letters_packed, letters_padded, sample_from_logits, score_logits
 from .constraints import batch_constraints
 from .data import PackedLoader, bucket_batches, fill_nan_deterministic, read_fasta
 
@@ -77,6 +77,41 @@ def group_batches(groups, lengths: List[int], batch_size: int, max_rows: int) ->
     return batches
 
 
+def draw_batch(logits, cu, max_len: int, samples: int, temperature: float, seed: int, cons=None, states=None, state_weights=None):
+    """``samples`` draws per row of one packed batch -> (draws int8 (S,B,T), seq_nll (S,B) or None, infeasible (B,) or None): from
+    ``rnampnn_design`` / ``_tied`` under constraints or ``states`` (they score their own draws), else free draws from ``rnampnn_sample``."""
+    if cons is not None or states is not None:
+        return design_from_logits(logits, cu_seqlens=cu, max_len=max_len, n_samples=samples, temperature=temperature, seed=seed,
+                                  constraints=cons, states=states, state_weights=state_weights)
+    # rnampnn_sample takes the padded layout: scatter the packed logits once (row cu[b] + t -> (b, t)); the mask comes from cu
+    t = torch.arange(max_len, device=logits.device)
+    mask = (t[None, :] < (cu[1:] - cu[:-1])[:, None]).to(torch.float32)
+    rows_of = (cu[:-1].to(torch.int64)[:, None] + t[None, :]).clamp_(max=int(logits.shape[0]) - 1)
+    padded = torch.where(mask[..., None] != 0, logits[rows_of], torch.zeros((), dtype=torch.float32, device=logits.device))
+    return sample_from_logits(padded, mask, temperature, samples, seed), None, None
+
+
+def padded_labels(items, idx, max_len: int):
+    """The fasta sequences of a batch -> (labels int32 (B, max_len), zero where there is none, or None when no row has one; have [B])."""
+    have = [items[i][2] is not None for i in idx]
+    if not any(have):
+        return None, have
+    lab = torch.zeros(len(idx), max_len, dtype=torch.int32)
+    for r, i in enumerate(idx):
+        if have[r]:
+            lab[r, :len(items[i][2])] = torch.from_numpy(items[i][2]).to(torch.int32)
+    return lab, have
+
+
+def write_csv(path: str, header: str, rows) -> None:
+    """``header`` and one line per row; a row is a sequence of fields that are already formatted (or ints)."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        f.write(header + "\n")
+        for row in rows:
+            f.write(",".join(str(v) for v in row) + "\n")
+
+
 @torch.no_grad()
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
@@ -99,7 +134,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
         raise ValueError(f"no usable structure under {data_path} (coords/<id>.npy (L,7,3))")
     if samples > 0 and not designs_csv:
         designs_csv = os.path.splitext(out_csv)[0] + "_designs.csv"
-    lengths = [int(c.shape[0]) for _, c, _ in items]
+    ids, lengths = [it[0] for it in items], [int(it[1].shape[0]) for it in items]
     trees = getattr(model, "xgb_readout", None)
     constrained = constraints is not None or bias is not None or bool(omit) or not wobble
     seqs, designs = {}, {}
@@ -107,88 +142,54 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     if states is not None:
         if samples <= 0:
             raise ValueError("multi-state design needs samples > 0")
-        groups = state_groups(states, [it[0] for it in items], lengths)
+        groups = state_groups(states, ids, lengths)
         batch_groups = group_batches(groups, lengths, batch_size, max_rows)
         batches = [[i for g in gs for i in groups[g][1]] for gs in batch_groups]
     else:
         batches = bucket_batches(lengths, batch_size, max_rows, seed=0)
     for bi, (coords, cu, max_len, idx) in enumerate(PackedLoader(items, batches, device=device)):
         lens = [lengths[i] for i in idx]
-        B = len(idx)
         if trees is not None:
             logits, emb = model.forward_packed(coords, cu, max_len, want_embedding=True)
             names = letters_packed(trees.predict(emb), lens)
         else:
             logits = model.forward_packed(coords, cu, max_len)
             names = letters_padded(score_logits(logits, cu_seqlens=cu, want=("pred",), max_len=max_len)["pred"])
-        for i, s in zip(idx, names):
-            seqs[i] = s
-        if samples > 0:
-            bad = dnll = None
-            if groups is not None:
-                cons = None
-                if constrained:
-                    cons = batch_constraints(constraints, [items[i][0] for i in idx], lens, max_len, bias=bias, wobble=wobble,
-                                             omit=omit).to_device(device)
-                draws, dnll, bad = design_from_logits(logits, cu_seqlens=cu, max_len=max_len, n_samples=samples, temperature=temperature,
-                                                      seed=seed + bi, constraints=cons, states=[len(groups[g][1]) for g in batch_groups[bi]],
-                                                      state_weights=[w for g in batch_groups[bi] for w in groups[g][2]])
-                bad = bad.cpu().tolist()
-            elif constrained:
-                cons = batch_constraints(constraints, [items[i][0] for i in idx], lens, max_len, bias=bias, wobble=wobble, omit=omit)
-                draws, dnll, bad = design_from_logits(logits, cu_seqlens=cu, max_len=max_len, n_samples=samples, temperature=temperature,
-                                                   seed=seed + bi, constraints=cons.to_device(device))
-                bad = bad.cpu().tolist()
-            else:
-                # rnampnn_sample takes the padded layout: scatter the packed logits once (row cu[b] + t -> (b, t)); the mask comes from cu
-                t = torch.arange(max_len, device=device)
-                mask = (t[None, :] < (cu[1:] - cu[:-1])[:, None]).to(torch.float32)
-                rows_of = (cu[:-1].to(torch.int64)[:, None] + t[None, :]).clamp_(max=int(logits.shape[0]) - 1)
-                padded = torch.where(mask[..., None] != 0, logits[rows_of], torch.zeros((), dtype=torch.float32, device=device))
-                draws = sample_from_logits(padded, mask, temperature, samples, seed + bi)
-            have = [items[i][2] is not None for i in idx]
-            lab = None
-            if any(have):
-                lab = torch.zeros(B, max_len, dtype=torch.int32)
+        seqs.update(zip(idx, names))
+        if samples <= 0:
+            continue
+        gs = None if groups is None else batch_groups[bi]
+        cons = None
+        if constrained:
+            cons = batch_constraints(constraints, [ids[i] for i in idx], lens, max_len, bias=bias, wobble=wobble, omit=omit).to_device(device)
+        draws, dnll, bad = draw_batch(logits, cu, max_len, samples, temperature, seed + bi, cons,
+                                      states=None if gs is None else [len(groups[g][1]) for g in gs],
+                                      state_weights=None if gs is None else [w for g in gs for w in groups[g][2]])
+        bad = None if bad is None else bad.cpu().tolist()
+        lab, have = padded_labels(items, idx, max_len)
+        want = (("seq_nll",) if dnll is None else ()) + (("seq_match",) if lab is not None else ())      # rnampnn_design scores its own draws
+        sc = score_logits(logits, cu_seqlens=cu, labels=lab, seqs=draws, want=want) if want else {}
+        nll = (sc["seq_nll"] if dnll is None else dnll).cpu().tolist()
+        match = sc["seq_match"].cpu().tolist() if lab is not None else None
+        for s in range(samples):
+            text = letters_padded(draws[s])
+            recs = [f"{match[s][r] / lens[r]:.6f}" if have[r] else "" for r in range(len(idx))]
+            if gs is None:
                 for r, i in enumerate(idx):
-                    if have[r]:
-                        lab[r, :lens[r]] = torch.from_numpy(items[i][2]).to(torch.int32)
-            want = (("seq_nll",) if dnll is None else ()) + (("seq_match",) if lab is not None else ())      # rnampnn_design scores its own draws
-            sc = score_logits(logits, cu_seqlens=cu, labels=lab, seqs=draws, want=want) if want else {}
-            nll = (sc["seq_nll"] if dnll is None else dnll).cpu().tolist()
-            match = sc["seq_match"].cpu().tolist() if lab is not None else None
-            if groups is not None:                                  # one row per (design, sample); the states are consecutive rows
-                for s in range(samples):
-                    text, r = letters_padded(draws[s]), 0
-                    for g in batch_groups[bi]:
-                        rows = range(r, r + len(groups[g][1]))
-                        recs = [f"{match[s][k] / lens[k]:.6f}" if match is not None and have[k] else "" for k in rows]
-                        designs.setdefault(g, []).append((s, text[r], bad[r], ";".join(items[idx[k]][0] for k in rows),
-                                                          ";".join(f"{nll[s][k] / lens[k]:.6f}" for k in rows), ";".join(recs)))
-                        r += len(rows)
+                    designs.setdefault(i, []).append((s, text[r], f"{nll[s][r] / lens[r]:.6f}", recs[r]) + (() if bad is None else (bad[r],)))
                 continue
-            for s in range(samples):
-                for r, (i, text) in enumerate(zip(idx, letters_padded(draws[s]))):
-                    rec = f"{match[s][r] / lens[r]:.6f}" if match is not None and have[r] else ""
-                    designs.setdefault(i, []).append((s, text, nll[s][r] / lens[r], rec + (f",{bad[r]}" if bad is not None else "")))
-    rows = [(items[i][0], seqs[i]) for i in range(len(items))]
-    os.makedirs(os.path.dirname(os.path.abspath(out_csv)), exist_ok=True)
-    with open(out_csv, "w") as f:
-        f.write("pdb_id,seq\n")
-        for rid, s in rows:
-            f.write(f"{rid},{s}\n")
+            r = 0
+            for g in gs:                                            # one row per (design, sample); the states are consecutive rows
+                rows = range(r, r + len(groups[g][1]))
+                designs.setdefault(g, []).append((s, text[r], bad[r], ";".join(ids[idx[k]] for k in rows),
+                                                  ";".join(f"{nll[s][k] / lens[k]:.6f}" for k in rows), ";".join(recs[k] for k in rows)))
+                r += len(rows)
+    rows = [(rid, seqs[i]) for i, rid in enumerate(ids)]
+    write_csv(out_csv, "pdb_id,seq", rows)
     if groups is not None:
-        os.makedirs(os.path.dirname(os.path.abspath(designs_csv)), exist_ok=True)
-        with open(designs_csv, "w") as f:
-            f.write("design_id,sample,seq,infeasible,states,nll_per_nt,recovery\n")
-            for g in range(len(groups)):
-                for s, text, n_bad, names, nll_nt, rec in designs[g]:
-                    f.write(f"{groups[g][0]},{s},{text},{n_bad},{names},{nll_nt},{rec}\n")
+        write_csv(designs_csv, "design_id,sample,seq,infeasible,states,nll_per_nt,recovery",
+                  [(group[0],) + row for g, group in enumerate(groups) for row in designs[g]])
     elif samples > 0:
-        os.makedirs(os.path.dirname(os.path.abspath(designs_csv)), exist_ok=True)
-        with open(designs_csv, "w") as f:
-            f.write("pdb_id,sample,seq,nll_per_nt,recovery" + (",infeasible" if constrained else "") + "\n")
-            for i in range(len(items)):
-                for s, text, nll_nt, rec in designs[i]:
-                    f.write(f"{items[i][0]},{s},{text},{nll_nt:.6f},{rec}\n")
+        write_csv(designs_csv, "pdb_id,sample,seq,nll_per_nt,recovery" + (",infeasible" if constrained else ""),
+                  [(rid,) + row for i, rid in enumerate(ids) for row in designs[i]])
     return rows
