@@ -279,6 +279,53 @@ int rnampnn_design_tied(const float* logits, int64_t n_rows, const float* mask, 
                         float temperature, int32_t S, uint64_t seed, const uint64_t* seed_dev,
                         const uint8_t* allowed, const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position,
                         int8_t* seqs, float* seq_nll, int32_t* infeasible, void* stream);
+/* Design under a G+C content window in ONE launch (csrc/design_gc.hip): the draws of rnampnn_design, conditioned EXACTLY on the number of
+ * C and G among the n_b nucleotides of RNA b lying in [gc_lo[b], gc_hi[b]].  The arguments are those of rnampnn_design plus
+ *   gc_lo, gc_hi (B) i32, device   absolute counts per RNA, read at kernel time
+ * and the outputs, each nullable, are those of rnampnn_design plus
+ *   gc_count (S,B) i32   the number of C or G ids actually written for that draw
+ *   gc_miss (B) i32      0 when the window is reachable, else the distance from the window to the nearest reachable count; the same for
+ *                        every sample
+ * Extent, masks, bias, temperature, z_t(c), `allowed`, the validation of `partner`, wobble, "an empty mask is drawn free and counts 1" and "a
+ * pair without an admitted compatible cell makes both ends single positions and counts 2" are rnampnn_design's.  All arithmetic is fp64, as
+ * in rnampnn_design_tied: z_t(c) = ((double) logit_t(c) + (double) bias_t(c)) / (double) temperature.  G+C of a class: A, U = 0; C, G = 1.
+ * LSE(x_1 .. x_k) = m + log(sum_i exp(x_i - m)) with m the maximum (NaN ignored), summed in the order given; -inf when m is not above -inf.
+ *   Leaf polynomials, log domain, p_t(d), d = 0..2.  A single position: p_t(d) = LSE of z_t(c) over the admitted classes with G+C d in class
+ *     order (d = 2: -inf).  A feasible pair i < j: p_i(d) = LSE of z_i(a) + z_j(b) over its admitted compatible cells with G+C(a) + G+C(b) = d
+ *     in a-major order; p_j = "1" (0 at d = 0, -inf otherwise).
+ *   Tree.  Node (l, i) covers the positions [i 2^l, min((i+1) 2^l, n_b)), has degree deg = min(2 * positions covered, n_b) and, for l >= 1,
+ *     coefficients c(k) = LSE over a = max(0, k - deg_R) .. min(k, deg_L) of L(a) + R(k - a), L and R its halves (l-1, 2i) and (l-1, 2i+1); a node
+ *     whose right half is empty equals its left half.  The root is node (ceil(log2 n_b), 0).  The shape depends on n_b only.
+ *   Window.  lo and hi are clamped to [0, n_b], then hi = max(hi, lo).  If no count in the window has a finite root coefficient the target is
+ *     the nearest count that has one, the lower count on a tie, and gc_miss is its distance (0 when no count at all has one: the target is lo).
+ *   SELECT(candidates in order, log-weights x, u24): w = exp(x - max x) (NaN ignored in the maximum); the first candidate whose running sum of
+ *     w exceeds u24 * 2^-24 * (the sum of w); else the last candidate with a finite x; else the first candidate.  The ORDER in which a
+ *     node's weights are summed is not part of the contract (the total and the splits of the top levels are summed by a wave-wide scan), so
+ *     a uniform within rounding (about 1e-15, relative) of a cumulative boundary may fall on either side of it.
+ *   Draw, top down.  The total K = SELECT(lo .. hi, root coefficients).  A node holding k hands its left half a = SELECT(max(0, k - deg_R) ..
+ *     min(k, deg_L), L(a) + R(k - a)) and its right half k - a (an empty right half: all of k, no uniform).  A leaf holding d draws its class -
+ *     a pair its cell, in a-major order - among the admitted ones with G+C d by rnampnn_design's rule in fp64 (weights exp(z - max over those
+ *     candidates), the first whose running sum exceeds u24 * 2^-24 * total, else the last of them); i receives a, j receives b.
+ *   Uniforms, u24 of rnampnn_design: a leaf uses u24(seed, s, b, t), a pair that of its lower index; a split uses u24(seed ^ SALT, s, b, first
+ *     position of the right half); the total uses u24(seed ^ SALT, s, b, 0) - position 0 never starts a right half.  With seed_dev the XOR is
+ *     taken on the device.
+ *   Robustness.  NaN or +-inf logits, a NaN bias or a malformed partner table still give ids in 0..3; every index and every count is clamped
+ *     before use.  A leaf that cannot realise the count it was handed draws as rnampnn_design would (its whole admitted set).  Such a miss
+ *     (non-finite inputs only) does not change gc_miss, which comes from the root alone; gc_count reports what was written.
+ * seq_nll is byte for byte rnampnn_score's for the written draw and `infeasible` keeps its meaning, as in rnampnn_design.  One workgroup per
+ * (RNA, sample); the levels 1 .. ceil(log2 T) live in dynamic LDS, node (l, i) at min(2 * (its extent within T), T) + 1 doubles (14,328 bytes at
+ * T = 128, 73,720 at 512, 159,816 at 1000), + T rounded up to 16 bytes of class ids + 96 bytes: RNAMPNN_ERR_UNSUPPORTED when that exceeds
+ * 160 KiB = 163,840 bytes (T <= 1017, which needs 163,800); the message names the byte count and that T.  A tree in global memory for longer RNAs is not built.  No workspace, no
+ * atomics, no runtime fill / copy node, no host synchronisation: two calls give identical bytes, the call can sit inside a captured graph,
+ * and a draw is a pure function of (seed, s, b) and the rows of RNA b - independent of B, T, S and the layout.
+ * RNAMPNN_ERR_BAD_ARG, before anything is launched: the cases of rnampnn_design; null gc_lo or gc_hi.  With every output null the call
+ * returns RNAMPNN_OK without a launch. */
+#define RNAMPNN_DESIGN_GC_SALT 0xA0761D6478BD642Full
+int rnampnn_design_gc(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
+                      float temperature, int32_t S, uint64_t seed, const uint64_t* seed_dev, const uint8_t* allowed,
+                      const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position,
+                      const int32_t* gc_lo, const int32_t* gc_hi, int8_t* seqs, float* seq_nll, int32_t* infeasible,
+                      int32_t* gc_count, int32_t* gc_miss, void* stream);
 
 /* -- training ---------------------------------------------------------------------------- */
 /* The training surface of RNAMPNN (rnampnn.py:187-207 + Lightning's loss.backward()):

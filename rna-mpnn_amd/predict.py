@@ -26,7 +26,14 @@ listed under one ``design_id`` (conformers of an ensemble, the two backbones of 
 sequence, drawn from the product of their distributions; ``weight`` may be empty (1) or negative (design against that state); structures
 not listed are designs of their own.  ``--constraints`` rows still go by ``pdb_id``, so each state brings its own structure, and the one
 sequence is pair-compatible in all of them.  The designs CSV then has one row per (design, sample):
-``design_id,sample,seq,infeasible,states,nll_per_nt,recovery``, the last three ``;``-joined per state."""
+``design_id,sample,seq,infeasible,states,nll_per_nt,recovery``, the last three ``;``-joined per state.
+
+    python rna-mpnn_amd/predict.py --ckpt Final.pt --data DIR --samples 8 --gc-content 0.45:0.60 [--constraints cons.csv --bias .. --omit .. --no-wobble]
+
+G+C content window (``rnampnn_design_gc``, both families): every draw holds a fraction of C and G between LO and HI of its length - drawn
+exactly from the model's distribution conditioned on that (and on the other constraints), not filtered.  The designs CSV gains the columns
+``gc`` (the fraction of the draw) and ``gc_miss`` (0, or by how many nucleotides the nearest count the constraints can reach lies outside
+the window; the draws then hold that count).  Not built together with ``--states``."""
 from __future__ import annotations
 
 import argparse
@@ -56,6 +63,7 @@ def parse(argv=None):
     ap.add_argument("--omit", default="", help="letters --samples never draws")
     ap.add_argument("--no-wobble", action="store_true", help="base pairs of --constraints exclude GU / UG")
     ap.add_argument("--states", default=None, help="CSV design_id,pdb_id,weight: the structures of one design_id share one sequence")
+    ap.add_argument("--gc-content", default=None, help="LO:HI: every draw of --samples holds a G+C fraction in this window")
     return ap.parse_args(argv)
 
 
@@ -69,6 +77,19 @@ def design_options(args) -> dict:
                 bias=parse_bias(args.bias) if args.bias else None, omit=args.omit, wobble=not args.no_wobble)
 
 
+def gc_option(args) -> dict:
+    """The ``gc_content`` keyword of ``predict`` from ``--gc-content``; empty without the flag.  ``ValueError`` naming the flags for a
+    malformed window, with ``--states`` and without ``--samples``."""
+    if args.gc_content is None:
+        return {}
+    from rnampnn.utils.constraints import parse_gc_content
+    if args.states:
+        raise ValueError("--gc-content together with --states is not built: the G+C window conditions single-state designs only")
+    if args.samples <= 0:
+        raise ValueError("--gc-content needs --samples N > 0")
+    return dict(gc_content=parse_gc_content(args.gc_content))
+
+
 def checkpoint_family(path: str) -> str:
     """The ``model`` key of a checkpoint file; a file without one is an ``rdesign`` checkpoint.  ``weights_only=True``."""
     ck = torch.load(path, map_location="cpu", weights_only=True)
@@ -79,6 +100,7 @@ def checkpoint_family(path: str) -> str:
 
 
 def run(args, log=print):
+    gc = gc_option(args)                                           # a bad window fails here, before the model is loaded
     family = checkpoint_family(args.ckpt)
     if family == "rnampnn":
         from rnampnn.utils.predict import predict
@@ -86,7 +108,7 @@ def run(args, log=print):
     else:
         from rdesign.utils.predict import predict
         from rdesign.utils.train import load_checkpoint
-    extra = dict(samples=args.samples, temperature=args.temperature, seed=args.seed, designs_csv=args.designs_out, **design_options(args))
+    extra = dict(samples=args.samples, temperature=args.temperature, seed=args.seed, designs_csv=args.designs_out, **design_options(args), **gc)
     if args.states:
         if family != "rnampnn":
             raise ValueError("--states designs with rnampnn checkpoints only; for an rdesign checkpoint call RNAModel.design(states=...) "

@@ -1,6 +1,7 @@
 """Decoding from logits, as free functions over the C ABI's decode family: argmax + recovery (``rnampnn_argmax_recovery``), free draws
-(``rnampnn_sample``), scores (``rnampnn_score``), constrained and multi-state design (``rnampnn_design``, ``rnampnn_design_tied``) and the
-letters of class ids.  Needs the library and ``_base`` only, so both model packages import it at module level."""
+(``rnampnn_sample``), scores (``rnampnn_score``), constrained and multi-state design (``rnampnn_design``, ``rnampnn_design_tied``), design
+under a G+C content window (``rnampnn_design_gc``) and the letters of class ids.  Needs the library and ``_base`` only, so both model
+packages import it at module level."""
 from __future__ import annotations
 
 import ctypes as C
@@ -127,6 +128,74 @@ def design_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None
     with torch.cuda.device(device):
         _native.check(_native.lib().rnampnn_design_tied(*rows, _ptr(gcu), len(counts), _ptr(sw), *draw))
     return seqs, nll, bad
+
+
+def gc_fractions(gc_content, B: int) -> torch.Tensor:
+    """``gc_content`` - a pair of fractions for every RNA, or a (B,2) tensor - -> (B,2) f64 on its own device.  ``ValueError`` for another
+    shape; a host value is also checked for fractions outside [0, 1] and lo > hi (a device tensor is not read here: the kernel clamps)."""
+    fr = gc_content if torch.is_tensor(gc_content) else torch.as_tensor([float(v) for v in gc_content], dtype=torch.float64)
+    fr = fr.to(torch.float64)
+    if tuple(fr.shape) == (2,):
+        fr = fr.expand(B, 2)
+    if tuple(fr.shape) != (B, 2):
+        raise ValueError(f"gc_content must be a pair (lo, hi) of fractions or a (B, 2) = {(B, 2)} tensor, got {tuple(fr.shape)}")
+    if fr.device.type == "cpu":
+        if not bool(((fr >= 0) & (fr <= 1)).all()):
+            raise ValueError(f"gc_content holds fractions of the length: they must lie in [0, 1]")
+        if bool((fr[:, 0] > fr[:, 1]).any()):
+            raise ValueError("gc_content: lo > hi")
+    return fr
+
+
+def gc_counts(fractions: torch.Tensor, lengths: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(B,2) fractions and (B,) lengths on one device -> the window in absolute counts, int32: lo = ceil(f_lo n - 1e-6),
+    hi = floor(f_hi n + 1e-6) (the slack keeps 0.5 * 12 = 6 whatever the rounding of the product)."""
+    n = lengths.to(torch.float64)
+    lo = torch.ceil(fractions[:, 0].to(torch.float64) * n - 1e-6)
+    hi = torch.floor(fractions[:, 1].to(torch.float64) * n + 1e-6)
+    return lo.to(torch.int32).contiguous(), hi.to(torch.int32).contiguous()
+
+
+def design_gc_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
+                          max_len: Optional[int] = None, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None,
+                          gc_content=(0.0, 1.0)) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``rnampnn_design_gc`` (include/rnampnn_hip.h): the draws of ``design_from_logits`` conditioned exactly on the G+C content of every
+    RNA lying in a window, in one launch -> (seqs, seq_nll, infeasible, gc_count (S,B) int32 = C or G ids written, gc_miss (B,) int32 = 0
+    when the window is reachable under the constraints, else its distance to the nearest reachable count, which the draws then hold).
+    Layouts and ``constraints`` as in ``design_from_logits``.  ``gc_content``: a pair of fractions (lo, hi) in [0, 1] for every RNA, or a
+    (B,2) tensor of them (float64: a float32 fraction carries its rounding into f * n); the counts are formed on the device from the mask
+    or ``cu_seqlens`` (``gc_counts``), without a host synchronisation.  Fractions outside [0, 1] or lo > hi raise ``ValueError`` (a device
+    tensor is not read back for that: the kernel clamps it).  CUDA logits only (there is no CPU fallback)."""
+    device = logits.device
+    if device.type != "cuda":
+        raise RuntimeError("rnampnn_design_gc runs on an MI355X: pass CUDA logits (there is no CPU fallback)")
+    c = constraints
+    al = None if c is None or c.allowed is None else _prep(c.allowed, device, torch.uint8)
+    pa = None if c is None or c.partner is None else _prep(c.partner, device, torch.int32)
+    bi = None if c is None or c.bias is None else _prep(c.bias, device)
+    lg, m, cu, B, T = _layout(logits, mask, cu_seqlens, (al, pa), max_len)
+    for name, t in (("allowed", al), ("partner", pa)):
+        if t is not None and tuple(t.shape) != (B, T):
+            raise ValueError(f"constraints.{name} must be padded to (B, T) = {(B, T)}, got {tuple(t.shape)}")
+    per_position = int(bi is not None and tuple(bi.shape) == (B, T, 4))
+    if bi is not None and not per_position and tuple(bi.shape) != (4,):
+        raise ValueError(f"constraints.bias must be (4,) or (B, T, 4) = {(B, T, 4)}, got {tuple(bi.shape)}")
+    _check_logits(lg, m, B, T)
+    fr = gc_fractions(gc_content, max(B, 0)).to(device, non_blocking=True)
+    lengths = (m.sum(dim=1) + 0.5).floor() if m is not None else (cu[1:] - cu[:-1]).clamp(0, max(T, 0))
+    lo, hi = gc_counts(fr, lengths)
+    S = int(n_samples)
+    seqs = torch.empty(max(S, 0), max(B, 0), max(T, 0), dtype=torch.int8, device=device)
+    nll = torch.empty(max(S, 0), max(B, 0), dtype=torch.float32, device=device)
+    bad = torch.empty(max(B, 0), dtype=torch.int32, device=device)
+    count = torch.empty(max(S, 0), max(B, 0), dtype=torch.int32, device=device)
+    miss = torch.empty(max(B, 0), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _native.check(_native.lib().rnampnn_design_gc(
+            _ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(cu), B, T, float(temperature), S, _seed64(seed), None, _ptr(al), _ptr(pa),
+            int(bool(c.wobble)) if c is not None else 1, _ptr(bi), per_position, _ptr(lo), _ptr(hi), _ptr(seqs), _ptr(nll), _ptr(bad),
+            _ptr(count), _ptr(miss), _stream(device)))
+    return seqs, nll, bad, count, miss
 
 
 SCORE_OUTPUTS = {"valid": torch.int32, "pred": torch.int8, "correct": torch.int32, "label_nll": torch.float32, "label_loss": torch.float32,

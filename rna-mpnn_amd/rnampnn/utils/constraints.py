@@ -74,6 +74,18 @@ def parse_bias(text: str) -> np.ndarray:
     return out
 
 
+def parse_gc_content(text: str) -> Tuple[float, float]:
+    """``LO:HI`` - the G+C content window as fractions of the length, 0 <= LO <= HI <= 1 - -> (lo, hi).  ``ValueError`` otherwise."""
+    lo, sep, hi = text.partition(":")
+    try:
+        window = (float(lo), float(hi))
+    except ValueError:
+        window = None
+    if not sep or window is None or not 0.0 <= window[0] <= window[1] <= 1.0:
+        raise ValueError(f"gc-content: expected LO:HI with fractions 0 <= LO <= HI <= 1, got {text!r}")
+    return window
+
+
 def omit_mask(letters: str) -> int:
     """``--omit`` letters -> the ``allowed`` set without them."""
     m = FREE

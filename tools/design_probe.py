@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""The measurement behind DESIGN.md section 9 "Constrained design" and "Multi-state design" (profiles/design_kernel_stats.txt,
-profiles/design_tied_kernel_stats.txt): the C2 batch (256 RNAs x 100..140 nt),
-S = 8 sequences per RNA.
+"""The measurement behind DESIGN.md section 9 "Constrained design", "Multi-state design" and "Design under a G+C window"
+(profiles/design_kernel_stats.txt, profiles/design_tied_kernel_stats.txt, profiles/design_gc_kernel_stats.txt): the C2 batch (256 RNAs x
+100..140 nt), S = 8 sequences per RNA.
 usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + rnampnn_score (seq_nll): the unconstrained pair of launches
        python tools/design_probe.py design [calls=50]         rnampnn_design: free, then with a hairpin's pairs + a fixed GNRA loop per RNA
        python tools/design_probe.py tied [calls=50]           rnampnn_design (free, hairpin) and then rnampnn_design_tied: one state per group
                                                               free, one state per group with the hairpins, 64 groups x 4 states with one 3-node chain
+       python tools/design_probe.py gc [calls=50]             rnampnn_design (free, hairpin) and then rnampnn_design_gc with the window 40..60 %:
+                                                              free, then with the hairpins
 HIP events around each loop of back-to-back calls of the Python wrappers.  Run either under `rocprofv3 --kernel-trace --stats -- python ...`
 (a run of its own) for the kernels' own times.  RNAMPNN_PROBE_ROOT: another checkout (with its library built) to take the package from -
 the `sample_score` leg uses nothing newer than rnampnn_score, so it runs on the parent commit as well."""
@@ -60,6 +62,16 @@ else:
                                                                                       constraints=cons))
     seqs, nll, bad = M.design_from_logits(logits, mask=m, n_samples=S, temperature=0.1, seed=1, constraints=cons)
     print(f"infeasible positions {int(bad.sum())}, mean NLL per nt {float(nll.sum()) / (S * int(mask.sum())):.4f}")
+    if what == "gc":
+        gc = dict(n_samples=S, temperature=0.1, seed=1, gc_content=(0.4, 0.6))
+        timed("rnampnn_design_gc 40..60 %, no constraints", lambda: M.design_gc_from_logits(logits, mask=m, **gc))
+        timed("rnampnn_design_gc 40..60 %, hairpin pairs + GNRA + bias", lambda: M.design_gc_from_logits(logits, mask=m, constraints=cons, **gc))
+        g_seqs, g_nll, g_bad, g_count, g_miss = M.design_gc_from_logits(logits, mask=m, constraints=cons, **gc)
+        frac = g_count.double() / m.sum(dim=1).double()
+        print(f"G+C fraction of the draws {float(frac.min()):.3f} .. {float(frac.max()):.3f} (unconstrained hairpin draws: "
+              f"{float(((seqs >= 2).sum(-1).double() / m.sum(dim=1).double()).min()):.3f} .. "
+              f"{float(((seqs >= 2).sum(-1).double() / m.sum(dim=1).double()).max()):.3f}), gc_miss total {int(g_miss.sum())}, "
+              f"infeasible equal {bool((g_bad == bad).all())}, mean NLL per nt {float(g_nll.sum()) / (S * int(mask.sum())):.4f}")
     if what == "tied":
         one = [1] * B
         timed("rnampnn_design_tied, one state per group, no constraints",

@@ -1,11 +1,13 @@
 #!/bin/bash
-# tools/design_probe.py under rocprofv3 --kernel-trace --stats, each leg in a run of its own.  usage: tools/kstats_design.sh <outdir>  (a git-ignored
-# place such as build/design_stats)
+# tools/design_probe.py under rocprofv3 --kernel-trace --stats, each leg in a run of its own.  usage: tools/kstats_design.sh <outdir> [leg ...]
+# (outdir: a git-ignored place such as build/design_stats; legs: sample_score design tied gc, all four by default)
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-mkdir -p "${1:?usage: tools/kstats_design.sh <outdir>}" && OUT=$(cd "$1" && pwd) || exit 1
+mkdir -p "${1:?usage: tools/kstats_design.sh <outdir> [leg ...]}" && OUT=$(cd "$1" && pwd) || exit 1
+shift
+LEGS=${*:-sample_score design tied gc}
 python3 $ROOT/__graft_entry__.py || exit 1    # build OUTSIDE the profiler: the profiled process only loads the library
 cd $OUT
-for name in sample_score design tied; do
+for name in $LEGS; do
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -- python3 $ROOT/tools/design_probe.py $name 50 > $OUT/$name.log 2>&1 || { tail -20 $OUT/$name.log; exit 1; }
     cat $OUT/$name.log | grep -v "^W2\|^E2\|rocprof" | tail -20
     python3 - <<PY
@@ -20,12 +22,16 @@ t = sorted(glob.glob("$OUT/$name/*/*kernel_trace.csv"))[-1]
 # the "tied" leg adds, after those, 55 + 55 + 1 + 55 + 1 launches of k_design_tied: one state per group free / with the hairpins, 64 groups x 4 states
 def launches(match):
     return sorted(((int(r['Start_Timestamp']), int(r['End_Timestamp']) - int(r['Start_Timestamp'])) for r in csv.DictReader(open(t)) if match(r['Kernel_Name'])))
-d = launches(lambda n: 'k_design' in n and 'k_design_tied' not in n)
+# the "gc" leg adds, after those of k_design, 55 + 55 + 1 launches of k_design_gc: the window 40..60 % free / with the hairpins
+d = launches(lambda n: 'k_design' in n and 'k_design_tied' not in n and 'k_design_gc' not in n)
 e = launches(lambda n: 'k_design_tied' in n)
+f = launches(lambda n: 'k_design_gc' in n)
 for kernel, label, part in (("k_design", "no constraints", d[:55]), ("k_design", "hairpin pairs + GNRA + bias", d[55:]),
                             ("k_design_tied", "one state per group, no constraints", e[:55]),
                             ("k_design_tied", "one state per group, hairpin pairs + GNRA + bias", e[55:111]),
-                            ("k_design_tied", "64 groups x 4 states, one 3-node chain per group", e[111:])):
+                            ("k_design_tied", "64 groups x 4 states, one 3-node chain per group", e[111:]),
+                            ("k_design_gc", "window 40..60 %, no constraints", f[:55]),
+                            ("k_design_gc", "window 40..60 %, hairpin pairs + GNRA + bias", f[55:])):
     if part:
         v = sorted(x[1] / 1e3 for x in part)
         print(f"{kernel}, {label}: {len(v)} launches, mean {sum(v) / len(v):.2f} us ({v[0]:.2f} .. {v[-1]:.2f}, median {v[len(v) // 2]:.2f})")
