@@ -326,6 +326,62 @@ int rnampnn_design_gc(const float* logits, int64_t n_rows, const float* mask, co
                       const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position,
                       const int32_t* gc_lo, const int32_t* gc_hi, int8_t* seqs, float* seq_nll, int32_t* infeasible,
                       int32_t* gc_count, int32_t* gc_miss, void* stream);
+/* Distinct designs in ONE launch (csrc/design_distinct.hip): S pairwise DIFFERENT sequences per RNA under the constraints of rnampnn_design -
+ * with noise != 0 an exact sample WITHOUT replacement from the constrained, tempered distribution, in sampling order; with noise == 0 the S
+ * most probable admitted sequences, in descending order - each with its log-probability under that distribution.  One algorithm, a beam of
+ * width S over the units with conditioned Gumbel keys (Kool, van Hoof, Welling 2019, "Stochastic Beams and Where to Find Them"); it is exact
+ * because the units are independent.  The arguments are those of rnampnn_design plus
+ *   noise                 != 0: sample without replacement; 0: the S best
+ * and the outputs, each nullable, are those of rnampnn_design plus
+ *   logp (S,B) f32        phi of the slot (below), rounded once: the log-probability of the sequence under the constrained, tempered
+ *                         distribution it was drawn from; -inf for an empty slot
+ *   n_distinct (B) i32    slots filled = min(S, the number of admitted sequences); filled slots are pairwise different
+ * with  seqs (S,B,T) i8   the sequence of slot s; -1 at t >= n_b and -1 everywhere in a slot s >= n_distinct[b]; every valid position of a
+ *                         filled slot holds an id in 0..3 whatever the inputs hold
+ *       seq_nll (S,B) f32 byte for byte rnampnn_score's seq_nll of a filled slot; +inf for an empty one
+ *       infeasible (B)    as in rnampnn_design.
+ * Both layouts, the padded `allowed` / `partner` / per-position `bias`, wobble, seed_dev, the clamping of lengths and offsets, the alignment
+ * rules, "an empty mask is drawn free and counts 1" and "a pair without an admitted compatible cell makes both ends single positions and
+ * counts 2" are rnampnn_design's.  All arithmetic is fp64: z_t(c) = ((double) logit_t(c) + (double) bias_t(c)) / (double) temperature.
+ *   Units, walking t = 0 .. n_b - 1.  A single position is a unit; its cells are the admitted classes in class order.  The lower end of a
+ *     feasible pair i < j is a unit; its cells are the admitted compatible cells (a,b) in a-major order (at most 6), z = z_i(a) + z_j(b);
+ *     i receives a, j receives b.  The upper end of a feasible pair is no unit.  l_u(c) = z(c) - LSE(z over the unit's cells), LSE as in
+ *     rnampnn_design_gc.  phi(prefix) = the sum of l over its units, added in unit order.
+ *   Beam.  One empty prefix at slot 0 with phi = 0, G = 0.  At a unit every slot i, in slot order, gives one candidate per cell c with
+ *     phi_ic = phi_i + l_u(c) and the key
+ *       noise == 0:  kappa_ic = phi_ic
+ *       noise != 0:  g_ic = phi_ic - log(-log u_ic);  Z_i = max_c g_ic (NaN ignored);  the children with g_ic == Z_i get kappa_ic = G_i exactly;
+ *                    the others v = G_i - g_ic + log1p(-exp(g_ic - Z_i)),  kappa_ic = G_i - max(0, v) - log1p(exp(-|v|))
+ *     and a NaN key is replaced by -inf.  The candidates with the S largest keys survive, ordered by key descending, then parent slot
+ *     ascending, then cell ascending; they become slots 0, 1, .. in that order with G = kappa.  A unit with ONE cell makes no selection: every
+ *     slot keeps its place, phi += l (0 for a finite z), G stays (noise == 0: G = phi).  After the last unit slot s is output s.  An RNA
+ *     of length 0 has the one empty sequence: n_distinct = 1, logp = 0, seq_nll = 0.
+ *   Uniforms, keyed by the PREFIX, not by the slot; mix64 as in rnampnn_design, arithmetic modulo 2^64, SALT the constant below:
+ *       H(empty) = mix64(mix64(seed ^ SALT) ^ 0xD6E8FEB86659FD93 * (b+1))
+ *       H(child) = mix64(H(parent) ^ 0xBF58476D1CE4E5B9 * (16 * (t+1) + cell)),  t the unit's position, cell = c or 4 a + b
+ *       u = ((double) (H(child) >> 11) + 0.5) * 2^-53
+ *     With seed_dev the XOR is taken on the device.
+ *   Consequences.  The result is a pure function of (seed, b, the rows of RNA b, S): it does not depend on B, T or the layout.  Slots
+ *     0 .. S'-1 of a call with S are the call with S' (the survivors of a narrower beam are the best of the wider one's, by induction over the
+ *     units).  With noise, slot 0 is ONE exact draw from the constrained tempered distribution and slots 0..s are an exact sample without
+ *     replacement in sampling order: P(slot 1 = y | slot 0 = x) = p(y) / (1 - p(x)).  A device result differs from a float64 restatement
+ *     only where two keys that a selection compared lie within the rounding of exp / log of one another (about 1e-14, relative).
+ * One 256-thread workgroup per RNA.  The beam lives in dynamic LDS, whose size depends on (S, T) alone:
+ *       bytes(S, T) = 144 S + 16 ceil(S / 8) + 6,752 + 16 ceil((S + ceil(S / 2)) T / 16)
+ *     (slot state 48 S, two candidate arrays 96 S, the survivors' table, the cells of 128 positions and the reduction's scratch, the history
+ *     of 12 bits per slot and position): 61,920 at (S = 8, T = 4500), 113,728 at (64, 1017), 93,280 at (256, 128), 159,328 at (256, 300).
+ *     RNAMPNN_ERR_UNSUPPORTED when that exceeds 160 KiB = 163,840 bytes; the message names the bytes, the limit and the largest T at that S
+ *     (1539 at S = 64, 311 at S = 256).
+ *   S <= RNAMPNN_DESIGN_DISTINCT_MAX_S = 256; a larger S is RNAMPNN_ERR_BAD_ARG and the message names the limit.
+ * No workspace, no atomics, no runtime fill / copy node, no host synchronisation: two calls give identical bytes and the call can sit inside
+ * a captured graph.  RNAMPNN_ERR_BAD_ARG, before anything is launched: the cases of rnampnn_design; S > 256.  The LDS check comes next; then,
+ * with every output null, the call returns RNAMPNN_OK without a launch. */
+#define RNAMPNN_DESIGN_DISTINCT_SALT 0xE7037ED1A0B428DBull
+#define RNAMPNN_DESIGN_DISTINCT_MAX_S 256
+int rnampnn_design_distinct(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
+                            float temperature, int32_t S, uint64_t seed, const uint64_t* seed_dev, const uint8_t* allowed,
+                            const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position, int32_t noise,
+                            int8_t* seqs, float* seq_nll, int32_t* infeasible, float* logp, int32_t* n_distinct, void* stream);
 
 /* -- training ---------------------------------------------------------------------------- */
 /* The training surface of RNAMPNN (rnampnn.py:187-207 + Lightning's loss.backward()):

@@ -33,7 +33,14 @@ sequence is pair-compatible in all of them.  The designs CSV then has one row pe
 G+C content window (``rnampnn_design_gc``, both families): every draw holds a fraction of C and G between LO and HI of its length - drawn
 exactly from the model's distribution conditioned on that (and on the other constraints), not filtered.  The designs CSV gains the columns
 ``gc`` (the fraction of the draw) and ``gc_miss`` (0, or by how many nucleotides the nearest count the constraints can reach lies outside
-the window; the draws then hold that count).  Not built together with ``--states``."""
+the window; the draws then hold that count).  Not built together with ``--states``.
+
+    python rna-mpnn_amd/predict.py --ckpt Final.pt --data DIR --samples 8 --distinct sample [--constraints cons.csv --bias .. --omit .. --no-wobble]
+
+Distinct designs (``rnampnn_design_distinct``, both families, at most 256 per structure): the N sequences of a structure are pairwise
+different - ``sample`` draws them without replacement from the model's (constrained, tempered) distribution, ``best`` lists its N most
+probable sequences in descending order.  The designs CSV gains a last column ``logp`` (the log-probability of the sequence under that
+distribution); a structure that admits fewer than N sequences has fewer rows.  Not built together with ``--states`` or ``--gc-content``."""
 from __future__ import annotations
 
 import argparse
@@ -64,6 +71,8 @@ def parse(argv=None):
     ap.add_argument("--no-wobble", action="store_true", help="base pairs of --constraints exclude GU / UG")
     ap.add_argument("--states", default=None, help="CSV design_id,pdb_id,weight: the structures of one design_id share one sequence")
     ap.add_argument("--gc-content", default=None, help="LO:HI: every draw of --samples holds a G+C fraction in this window")
+    ap.add_argument("--distinct", default=None, choices=("sample", "best"),
+                    help="the draws of --samples are pairwise different: sampled without replacement, or the most probable ones")
     return ap.parse_args(argv)
 
 
@@ -90,6 +99,19 @@ def gc_option(args) -> dict:
     return dict(gc_content=parse_gc_content(args.gc_content))
 
 
+def distinct_option(args) -> dict:
+    """The ``distinct`` keyword of ``predict`` from ``--distinct``; empty without the flag.  ``ValueError`` naming the flags with ``--states``
+    or ``--gc-content`` and without ``--samples``."""
+    if args.distinct is None:
+        return {}
+    for flag, value in (("--states", args.states), ("--gc-content", args.gc_content)):
+        if value:
+            raise ValueError(f"--distinct together with {flag} is not built: distinct designs are single-state and have no G+C window")
+    if args.samples <= 0:
+        raise ValueError("--distinct needs --samples N > 0")
+    return dict(distinct=args.distinct)
+
+
 def checkpoint_family(path: str) -> str:
     """The ``model`` key of a checkpoint file; a file without one is an ``rdesign`` checkpoint.  ``weights_only=True``."""
     ck = torch.load(path, map_location="cpu", weights_only=True)
@@ -100,6 +122,7 @@ def checkpoint_family(path: str) -> str:
 
 
 def run(args, log=print):
+    distinct = distinct_option(args)                               # a combination that is not built fails here, before the model is loaded
     gc = gc_option(args)                                           # a bad window fails here, before the model is loaded
     family = checkpoint_family(args.ckpt)
     if family == "rnampnn":
@@ -108,7 +131,7 @@ def run(args, log=print):
     else:
         from rdesign.utils.predict import predict
         from rdesign.utils.train import load_checkpoint
-    extra = dict(samples=args.samples, temperature=args.temperature, seed=args.seed, designs_csv=args.designs_out, **design_options(args), **gc)
+    extra = dict(samples=args.samples, temperature=args.temperature, seed=args.seed, designs_csv=args.designs_out, **design_options(args), **gc, **distinct)
     if args.states:
         if family != "rnampnn":
             raise ValueError("--states designs with rnampnn checkpoints only; for an rdesign checkpoint call RNAModel.design(states=...) "

@@ -4,7 +4,7 @@ from __future__ import annotations
 import os
 from typing import List, Optional, Tuple
 
-from rnampnn.model.decode import design_from_logits, design_gc_from_logits, letters_padded, score_logits
+from rnampnn.model.decode import check_distinct, design_distinct_from_logits, design_from_logits, design_gc_from_logits, letters_padded, score_logits
 from rnampnn.utils.constraints import batch_constraints
 from rnampnn.utils.data import bucket_batches
 from rnampnn.utils.predict import write_csv
@@ -14,7 +14,7 @@ from .data import load_rna_dir, padded_loader
 
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
-            wobble: bool = True, gc_content=None) -> List[Tuple[str, str]]:
+            wobble: bool = True, gc_content=None, distinct=None) -> List[Tuple[str, str]]:
     """Read ``data_path`` (``coords/<id>.npy`` + ``seqs/<id>.fasta``), design a sequence for every structure in length-bucketed batches
     (``RNAModel.predict_sequences``: the tree read-out when one is attached, else the read-out's argmax) and write ``out_csv`` with one
     ``pdb_id,seq`` row per input in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure at
@@ -22,7 +22,10 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     not in it are unconstrained), ``bias`` (4 per-class floats), ``omit`` (letters never drawn) and ``wobble`` - and write ``designs_csv``
     with the columns ``pdb_id,sample,seq,nll_per_nt,recovery,infeasible``.  ``gc_content`` (lo, hi): the draws come from
     ``rnampnn_design_gc``, conditioned exactly on the G+C fraction of every structure lying in that window, and ``designs_csv`` gains the
-    last columns ``gc`` (the fraction of the draw) and ``gc_miss``."""
+    last columns ``gc`` (the fraction of the draw) and ``gc_miss``.  ``distinct`` ("sample" / "best"): the draws come from
+    ``rnampnn_design_distinct`` and are pairwise different per structure; ``designs_csv`` gains a last column ``logp`` and holds no row for
+    a slot the structure's admitted sequences do not fill.  Not built together with ``gc_content``."""
+    check_distinct(distinct, None, gc_content)
     model.eval()
     items = load_rna_dir(data_path)
     if not items:
@@ -39,8 +42,14 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             lens = [int(v) for v in lengths]
             logits, cu, T = model._packed_logits(X, mask, lengths)
             cons = batch_constraints(constraints, [items[i][0] for i in idx], lens, T, bias=bias, wobble=wobble, omit=omit)
-            gcs = None
-            if gc_content is not None:
+            gcs = logp = None
+            filled = [samples] * len(idx)
+            if distinct is not None:
+                draws, nll, bad, logp, filled = design_distinct_from_logits(logits, cu_seqlens=cu, max_len=T, n_samples=samples,
+                                                                            temperature=temperature, seed=seed + bi,
+                                                                            constraints=cons.to_device(device), mode=distinct)
+                logp, filled = logp.cpu().tolist(), filled.cpu().tolist()
+            elif gc_content is not None:
                 draws, nll, bad, count, miss = design_gc_from_logits(logits, cu_seqlens=cu, max_len=T, n_samples=samples,
                                                                      temperature=temperature, seed=seed + bi,
                                                                      constraints=cons.to_device(device), gc_content=gc_content)
@@ -52,11 +61,15 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             nll, bad = nll.cpu().tolist(), bad.cpu().tolist()
             for s in range(samples):
                 for r, (i, text) in enumerate(zip(idx, letters_padded(draws[s]))):
+                    if s >= filled[r]:
+                        continue                                    # fewer admitted sequences than samples: the slot is empty
                     designs.setdefault(i, []).append((s, text, f"{nll[s][r] / lens[r]:.6f}", f"{match[s][r] / lens[r]:.6f}", bad[r])
-                                                     + (() if gcs is None else (f"{gcs[0][s][r] / lens[r]:.6f}", gcs[1][r])))
+                                                     + (() if gcs is None else (f"{gcs[0][s][r] / lens[r]:.6f}", gcs[1][r]))
+                                                     + (() if logp is None else (f"{logp[s][r]:.6f}",)))
     rows = [(items[i][0], seqs[i]) for i in range(len(items))]
     write_csv(out_csv, "pdb_id,seq", rows)
     if samples > 0:
-        write_csv(designs_csv, "pdb_id,sample,seq,nll_per_nt,recovery,infeasible" + (",gc,gc_miss" if gc_content is not None else ""),
+        write_csv(designs_csv, "pdb_id,sample,seq,nll_per_nt,recovery,infeasible" + (",gc,gc_miss" if gc_content is not None else "")
+                  + (",logp" if distinct is not None else ""),
                   [(it[0],) + row for i, it in enumerate(items) for row in designs[i]])
     return rows

@@ -1,6 +1,6 @@
 """Decoding from logits, as free functions over the C ABI's decode family: argmax + recovery (``rnampnn_argmax_recovery``), free draws
 (``rnampnn_sample``), scores (``rnampnn_score``), constrained and multi-state design (``rnampnn_design``, ``rnampnn_design_tied``), design
-under a G+C content window (``rnampnn_design_gc``) and the letters of class ids.  Needs the library and ``_base`` only, so both model
+under a G+C content window (``rnampnn_design_gc``), distinct designs (``rnampnn_design_distinct``) and the letters of class ids.  Needs the library and ``_base`` only, so both model
 packages import it at module level."""
 from __future__ import annotations
 
@@ -196,6 +196,61 @@ def design_gc_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = N
             int(bool(c.wobble)) if c is not None else 1, _ptr(bi), per_position, _ptr(lo), _ptr(hi), _ptr(seqs), _ptr(nll), _ptr(bad),
             _ptr(count), _ptr(miss), _stream(device)))
     return seqs, nll, bad, count, miss
+
+
+DISTINCT_MODES = {"sample": 1, "best": 0}
+
+
+def design_distinct_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
+                                max_len: Optional[int] = None, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None,
+                                mode: str = "sample") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``rnampnn_design_distinct`` (include/rnampnn_hip.h): ``n_samples`` (at most 256) pairwise DIFFERENT sequences per RNA under the
+    constraints of ``design_from_logits``, in one launch -> (seqs, seq_nll, infeasible, logp (S,B) f32 = the log-probability of each
+    sequence under the constrained, tempered distribution, n_distinct (B,) int32 = slots filled = min(S, admitted sequences)).
+    ``mode="sample"``: an exact sample without replacement, in sampling order (slot 0 is one exact draw); ``mode="best"``: the most probable
+    admitted sequences, in descending order.  A slot s >= n_distinct[b] holds -1 everywhere, seq_nll +inf and logp -inf.  The slots do
+    not depend on the batch or the layout, and the first S' of S slots are the call with S'.  Layouts and ``constraints`` as in
+    ``design_from_logits``.  CUDA logits only (there is no CPU fallback); no host synchronisation."""
+    if mode not in DISTINCT_MODES:
+        raise ValueError(f"mode must be one of {sorted(DISTINCT_MODES)}, got {mode!r}")
+    device = logits.device
+    if device.type != "cuda":
+        raise RuntimeError("rnampnn_design_distinct runs on an MI355X: pass CUDA logits (there is no CPU fallback)")
+    c = constraints
+    al = None if c is None or c.allowed is None else _prep(c.allowed, device, torch.uint8)
+    pa = None if c is None or c.partner is None else _prep(c.partner, device, torch.int32)
+    bi = None if c is None or c.bias is None else _prep(c.bias, device)
+    lg, m, cu, B, T = _layout(logits, mask, cu_seqlens, (al, pa), max_len)
+    for name, t in (("allowed", al), ("partner", pa)):
+        if t is not None and tuple(t.shape) != (B, T):
+            raise ValueError(f"constraints.{name} must be padded to (B, T) = {(B, T)}, got {tuple(t.shape)}")
+    per_position = int(bi is not None and tuple(bi.shape) == (B, T, 4))
+    if bi is not None and not per_position and tuple(bi.shape) != (4,):
+        raise ValueError(f"constraints.bias must be (4,) or (B, T, 4) = {(B, T, 4)}, got {tuple(bi.shape)}")
+    _check_logits(lg, m, B, T)
+    S = int(n_samples)
+    seqs = torch.empty(max(S, 0), max(B, 0), max(T, 0), dtype=torch.int8, device=device)
+    nll = torch.empty(max(S, 0), max(B, 0), dtype=torch.float32, device=device)
+    bad = torch.empty(max(B, 0), dtype=torch.int32, device=device)
+    logp = torch.empty(max(S, 0), max(B, 0), dtype=torch.float32, device=device)
+    filled = torch.empty(max(B, 0), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _native.check(_native.lib().rnampnn_design_distinct(
+            _ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(cu), B, T, float(temperature), S, _seed64(seed), None, _ptr(al), _ptr(pa),
+            int(bool(c.wobble)) if c is not None else 1, _ptr(bi), per_position, DISTINCT_MODES[mode], _ptr(seqs), _ptr(nll), _ptr(bad),
+            _ptr(logp), _ptr(filled), _stream(device)))
+    return seqs, nll, bad, logp, filled
+
+
+def check_distinct(distinct, states=None, gc_content=None) -> None:
+    """``design(..., distinct=...)``: ``ValueError`` for an unknown mode or a combination that is not built; touches no device."""
+    if distinct is None:
+        return
+    if distinct not in DISTINCT_MODES:
+        raise ValueError(f"distinct must be None or one of {sorted(DISTINCT_MODES)}, got {distinct!r}")
+    for name, value in (("states", states), ("gc_content", gc_content)):
+        if value is not None:
+            raise ValueError(f"distinct together with {name} is not built: the beam runs over the units of rnampnn_design only")
 
 
 SCORE_OUTPUTS = {"valid": torch.int32, "pred": torch.int8, "correct": torch.int32, "label_nll": torch.float32, "label_loss": torch.float32,

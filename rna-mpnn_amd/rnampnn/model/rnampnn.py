@@ -23,7 +23,7 @@ from .. import _native
 from ..config.glob import DEFAULT_SEED, REVERSE_VOCAB
 from ..utils.data import check_prefix_mask
 from ._base import NativeModule, _prep, _ptr, _stream
-from .decode import (SCORE_OUTPUTS, argmax_recovery, check_state_lengths, design_from_logits, design_gc_from_logits,  # noqa: F401
+from .decode import (SCORE_OUTPUTS, argmax_recovery, check_distinct, check_state_lengths, design_distinct_from_logits, design_from_logits, design_gc_from_logits,  # noqa: F401
                      letters_packed, letters_padded, sample_from_logits, score_logits)
 from ._schema import DEFAULT_HPARAMS
 
@@ -545,7 +545,7 @@ class RNAMPNN(NativeModule):
 
     @torch.no_grad()
     def design(self, coords: torch.Tensor, mask: torch.Tensor, n_samples: int = 8, temperature: float = 0.1, seed: int = 0,
-               T_norm: int = 0, constraints=None, states=None, state_weights=None, lengths=None, gc_content=None):
+               T_norm: int = 0, constraints=None, states=None, state_weights=None, lengths=None, gc_content=None, distinct=None):
         """``sample`` plus the score of every draw against the SAME logits, with one forward: -> (seqs int8 (n_samples,B,T), -1 on
         padding; seq_nll (n_samples,B) f32).  The NLL is the model's own (temperature 1) likelihood, so designs drawn at different
         temperatures rank on one scale.  ``constraints`` (``rnampnn.utils.constraints.DesignConstraints``: fixed nucleotides, base
@@ -556,12 +556,19 @@ class RNAMPNN(NativeModule):
         the mask on the host; without them such a group is designed over its common prefix).  ``gc_content`` (a pair of fractions, or
         (B,2)): the draws - under ``constraints`` or free - are conditioned exactly on the G+C content of every RNA lying in that window
         (``design_gc_from_logits``) -> (seqs, seq_nll, infeasible, gc_count (n_samples,B) int32, gc_miss (B,) int32); not built together
-        with ``states``."""
+        with ``states``.  ``distinct`` ("sample" or "best"; ``None`` is everything above, unchanged): ``n_samples`` pairwise DIFFERENT
+        sequences per RNA (``design_distinct_from_logits``) - an exact sample without replacement, or the most probable admitted sequences
+        in descending order - under ``constraints`` or free -> (seqs, seq_nll, infeasible, logp (n_samples,B) f32, n_distinct (B,) int32); not
+        built together with ``states`` or ``gc_content``."""
+        check_distinct(distinct, states, gc_content)
         if gc_content is not None and states is not None:
             raise ValueError("gc_content together with states is not built: the G+C window conditions the draws of rnampnn_design only")
         if states is not None and lengths is not None:
             check_state_lengths(states, lengths)
         logits = self._run(coords, mask, T_norm=T_norm)["logits"]
+        if distinct is not None:
+            return design_distinct_from_logits(logits, mask=mask, n_samples=n_samples, temperature=temperature, seed=seed,
+                                               constraints=constraints, mode=distinct)
         if gc_content is not None:
             return design_gc_from_logits(logits, mask=mask, n_samples=n_samples, temperature=temperature, seed=seed, constraints=constraints,
                                          gc_content=gc_content)

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from ..config.glob import VOCAB
-from ..model.decode import design_from_logits, design_gc_from_logits, letters_packed, letters_padded, sample_from_logits, score_logits
+from ..model.decode import check_distinct, design_distinct_from_logits, design_from_logits, design_gc_from_logits, letters_packed, letters_padded, sample_from_logits, score_logits
 from .constraints import batch_constraints
 from .data import PackedLoader, bucket_batches, fill_nan_deterministic, read_fasta
 
@@ -115,7 +115,7 @@ def write_csv(path: str, header: str, rows) -> None:
 @torch.no_grad()
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
-            wobble: bool = True, states: Optional[dict] = None, gc_content=None) -> List[Tuple[str, str]]:
+            wobble: bool = True, states: Optional[dict] = None, gc_content=None, distinct=None) -> List[Tuple[str, str]]:
     """Design a sequence for every structure under ``data_path`` in length-bucketed var-len batches (``forward_packed``): the tree
     read-out on the packed embedding when one is attached, else the read-out's argmax (``rnampnn_score``'s ``pred``); write ``out_csv``
     with one ``pdb_id,seq`` row per structure in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure
@@ -129,7 +129,12 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     ``design_id,sample,seq,infeasible,states,nll_per_nt,recovery``, the last three ``;``-joined per state.
     ``gc_content`` (lo, hi): the draws - constrained or free - come from ``rnampnn_design_gc``, conditioned exactly on the G+C fraction of
     every structure lying in that window; ``designs_csv`` gains the last columns ``gc`` (the fraction of the draw) and ``gc_miss`` (0, or
-    how many nucleotides the nearest reachable count lies outside the window).  Not built together with ``states``."""
+    how many nucleotides the nearest reachable count lies outside the window).  Not built together with ``states``.
+    ``distinct`` ("sample" / "best"): the draws - constrained or free - come from ``rnampnn_design_distinct`` and are pairwise different per
+    structure (a sample without replacement / the most probable sequences in descending order); ``designs_csv`` gains a last column
+    ``logp`` and holds no row for a slot the structure's admitted sequences do not fill.  Not built together with ``states`` or
+    ``gc_content``."""
+    check_distinct(distinct, states, gc_content)
     if gc_content is not None and states is not None:
         raise ValueError("gc_content together with states is not built")
     model.eval()
@@ -167,8 +172,14 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
         cons = None
         if constrained:
             cons = batch_constraints(constraints, [ids[i] for i in idx], lens, max_len, bias=bias, wobble=wobble, omit=omit).to_device(device)
-        gcs = None
-        if gc_content is not None:
+        gcs = logp = None
+        filled = [samples] * len(idx)
+        if distinct is not None:
+            draws, dnll, bad, logp, filled = design_distinct_from_logits(logits, cu_seqlens=cu, max_len=max_len, n_samples=samples,
+                                                                         temperature=temperature, seed=seed + bi, constraints=cons,
+                                                                         mode=distinct)
+            bad, logp, filled = (bad if constrained else None), logp.cpu().tolist(), filled.cpu().tolist()
+        elif gc_content is not None:
             draws, dnll, bad, count, miss = design_gc_from_logits(logits, cu_seqlens=cu, max_len=max_len, n_samples=samples,
                                                                   temperature=temperature, seed=seed + bi, constraints=cons,
                                                                   gc_content=gc_content)
@@ -188,8 +199,11 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             recs = [f"{match[s][r] / lens[r]:.6f}" if have[r] else "" for r in range(len(idx))]
             if gs is None:
                 for r, i in enumerate(idx):
+                    if s >= filled[r]:
+                        continue                                    # fewer admitted sequences than samples: the slot is empty
                     designs.setdefault(i, []).append((s, text[r], f"{nll[s][r] / lens[r]:.6f}", recs[r]) + (() if bad is None else (bad[r],))
-                                                     + (() if gcs is None else (f"{gcs[0][s][r] / lens[r]:.6f}", gcs[1][r])))
+                                                     + (() if gcs is None else (f"{gcs[0][s][r] / lens[r]:.6f}", gcs[1][r]))
+                                                     + (() if logp is None else (f"{logp[s][r]:.6f}",)))
                 continue
             r = 0
             for g in gs:                                            # one row per (design, sample); the states are consecutive rows
@@ -204,5 +218,5 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
                   [(group[0],) + row for g, group in enumerate(groups) for row in designs[g]])
     elif samples > 0:
         write_csv(designs_csv, "pdb_id,sample,seq,nll_per_nt,recovery" + (",infeasible" if constrained else "")
-                  + (",gc,gc_miss" if gc_content is not None else ""), [(rid,) + row for i, rid in enumerate(ids) for row in designs[i]])
+                  + (",gc,gc_miss" if gc_content is not None else "") + (",logp" if distinct is not None else ""), [(rid,) + row for i, rid in enumerate(ids) for row in designs[i]])
     return rows

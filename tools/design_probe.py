@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""The measurement behind DESIGN.md section 9 "Constrained design", "Multi-state design" and "Design under a G+C window"
-(profiles/design_kernel_stats.txt, profiles/design_tied_kernel_stats.txt, profiles/design_gc_kernel_stats.txt): the C2 batch (256 RNAs x
-100..140 nt), S = 8 sequences per RNA.
+"""The measurement behind DESIGN.md section 9 "Constrained design", "Multi-state design", "Design under a G+C window" and "Distinct designs"
+(profiles/design_kernel_stats.txt, profiles/design_tied_kernel_stats.txt, profiles/design_gc_kernel_stats.txt,
+profiles/design_distinct_kernel_stats.txt): the C2 batch (256 RNAs x 100..140 nt), S = 8 sequences per RNA.
 usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + rnampnn_score (seq_nll): the unconstrained pair of launches
        python tools/design_probe.py design [calls=50]         rnampnn_design: free, then with a hairpin's pairs + a fixed GNRA loop per RNA
        python tools/design_probe.py tied [calls=50]           rnampnn_design (free, hairpin) and then rnampnn_design_tied: one state per group
                                                               free, one state per group with the hairpins, 64 groups x 4 states with one 3-node chain
        python tools/design_probe.py gc [calls=50]             rnampnn_design (free, hairpin) and then rnampnn_design_gc with the window 40..60 %:
                                                               free, then with the hairpins
+       python tools/design_probe.py distinct [calls=50]       rnampnn_design (free, hairpin) and then rnampnn_design_distinct at S = 8 and S = 64,
+                                                              "sample" then "best", each free and then with the hairpins (8 legs)
 HIP events around each loop of back-to-back calls of the Python wrappers.  Run either under `rocprofv3 --kernel-trace --stats -- python ...`
 (a run of its own) for the kernels' own times.  RNAMPNN_PROBE_ROOT: another checkout (with its library built) to take the package from -
 the `sample_score` leg uses nothing newer than rnampnn_score, so it runs on the parent commit as well."""
@@ -72,6 +74,19 @@ else:
               f"{float(((seqs >= 2).sum(-1).double() / m.sum(dim=1).double()).min()):.3f} .. "
               f"{float(((seqs >= 2).sum(-1).double() / m.sum(dim=1).double()).max()):.3f}), gc_miss total {int(g_miss.sum())}, "
               f"infeasible equal {bool((g_bad == bad).all())}, mean NLL per nt {float(g_nll.sum()) / (S * int(mask.sum())):.4f}")
+    if what == "distinct":
+        for S in (8, 64):                                           # (timed() prints the global S)
+            for mode in ("sample", "best"):
+                kw = dict(n_samples=S, temperature=0.1, seed=1, mode=mode)
+                timed(f"rnampnn_design_distinct {mode}, no constraints", lambda: M.design_distinct_from_logits(logits, mask=m, **kw))
+                timed(f"rnampnn_design_distinct {mode}, hairpin pairs + GNRA + bias",
+                      lambda: M.design_distinct_from_logits(logits, mask=m, constraints=cons, **kw))
+            d_seqs, d_nll, d_bad, d_logp, d_n = M.design_distinct_from_logits(logits, mask=m, n_samples=S, temperature=0.1, seed=1, mode="sample")
+            dup = sum(S - len({r.tobytes() for r in q.cpu().numpy()})
+                      for q in M.design_from_logits(logits, mask=m, n_samples=S, temperature=0.1, seed=1)[0].permute(1, 0, 2))
+            print(f"S {S}: slots filled {int(d_n.min())} .. {int(d_n.max())}, total probability of an RNA's {S} distinct designs "
+                  f"{float(d_logp.double().exp().sum(0).min()):.4f} .. {float(d_logp.double().exp().sum(0).max()):.4f}; of rnampnn_design's "
+                  f"{S * B} independent free draws at the same temperature {dup} repeat an earlier draw of their RNA")
     if what == "tied":
         one = [1] * B
         timed("rnampnn_design_tied, one state per group, no constraints",

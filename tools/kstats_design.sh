@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/design_probe.py under rocprofv3 --kernel-trace --stats, each leg in a run of its own.  usage: tools/kstats_design.sh <outdir> [leg ...]
-# (outdir: a git-ignored place such as build/design_stats; legs: sample_score design tied gc, all four by default)
+# (outdir: a git-ignored place such as build/design_stats; legs: sample_score design tied gc distinct, the first four by default)
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "${1:?usage: tools/kstats_design.sh <outdir> [leg ...]}" && OUT=$(cd "$1" && pwd) || exit 1
 shift
@@ -23,15 +23,20 @@ t = sorted(glob.glob("$OUT/$name/*/*kernel_trace.csv"))[-1]
 def launches(match):
     return sorted(((int(r['Start_Timestamp']), int(r['End_Timestamp']) - int(r['Start_Timestamp'])) for r in csv.DictReader(open(t)) if match(r['Kernel_Name'])))
 # the "gc" leg adds, after those of k_design, 55 + 55 + 1 launches of k_design_gc: the window 40..60 % free / with the hairpins
-d = launches(lambda n: 'k_design' in n and 'k_design_tied' not in n and 'k_design_gc' not in n)
+# the "distinct" leg adds 8 x 55 launches of k_design_distinct (+ 1 after every fourth): S = 8 then 64, sample then best, free then hairpins
+d = launches(lambda n: 'k_design' in n and 'k_design_tied' not in n and 'k_design_gc' not in n and 'k_design_distinct' not in n)
+g = launches(lambda n: 'k_design_distinct' in n)
 e = launches(lambda n: 'k_design_tied' in n)
 f = launches(lambda n: 'k_design_gc' in n)
-for kernel, label, part in (("k_design", "no constraints", d[:55]), ("k_design", "hairpin pairs + GNRA + bias", d[55:]),
+for kernel, label, part in (("k_design", "no constraints", d[:55]), ("k_design", "hairpin pairs + GNRA + bias", d[55:111]),
                             ("k_design_tied", "one state per group, no constraints", e[:55]),
                             ("k_design_tied", "one state per group, hairpin pairs + GNRA + bias", e[55:111]),
                             ("k_design_tied", "64 groups x 4 states, one 3-node chain per group", e[111:]),
                             ("k_design_gc", "window 40..60 %, no constraints", f[:55]),
-                            ("k_design_gc", "window 40..60 %, hairpin pairs + GNRA + bias", f[55:])):
+                            ("k_design_gc", "window 40..60 %, hairpin pairs + GNRA + bias", f[55:])) + tuple(
+        ("k_design_distinct", f"S = {S}, {mode}, {leg}", g[221 * i + 110 * j + 55 * k:221 * i + 110 * j + 55 * k + 55])
+        for i, S in enumerate((8, 64)) for j, mode in enumerate(("sample", "best"))
+        for k, leg in enumerate(("no constraints", "hairpin pairs + GNRA + bias"))):
     if part:
         v = sorted(x[1] / 1e3 for x in part)
         print(f"{kernel}, {label}: {len(v)} launches, mean {sum(v) / len(v):.2f} us ({v[0]:.2f} .. {v[-1]:.2f}, median {v[len(v) // 2]:.2f})")
