@@ -326,6 +326,56 @@ int rnampnn_design_gc(const float* logits, int64_t n_rows, const float* mask, co
                       const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position,
                       const int32_t* gc_lo, const int32_t* gc_hi, int8_t* seqs, float* seq_nll, int32_t* infeasible,
                       int32_t* gc_count, int32_t* gc_miss, void* stream);
+/* Design within a count window in ONE launch (csrc/design_count.hip): the draws of rnampnn_design, conditioned EXACTLY on the number of
+ * positions of RNA b whose class falls in that position's COUNTED SET lying in [count_lo[b], count_hi[b]].  With the sets 15 ^ (1 << id of a
+ * reference sequence) the count is the number of mutations against the reference and the window a mutation budget; with 12 (C|G) everywhere
+ * and count_cap >= T the call returns the bytes of rnampnn_design_gc.  The arguments are those of rnampnn_design_gc with gc_lo / gc_hi
+ * replaced by
+ *   counted (B,T) u8, device, non-null   padded in both layouts; bits 0..3 mark the classes (AUCG) that count 1 at this position, the higher
+ *                                        bits are ignored; 0: the position never counts.  bit(m, c) = (m >> c) & 1
+ *   count_lo, count_hi (B) i32, device   absolute counts per RNA, read at kernel time
+ *   count_cap i32, host                  no count above it is ever targeted or stored; it sizes the tree.  cap = min(count_cap, T) below
+ * and the outputs, each nullable, are those of rnampnn_design plus
+ *   count (S,B) i32        the sum over the ids written for that draw of bit(counted[b,t], id_t)
+ *   count_miss (B) i32     0 when the window is reachable, else the distance from the window to the target (below); the same for every sample
+ * Extent, masks, bias, temperature, z_t(c), `allowed`, the validation of `partner`, wobble, "an empty mask is drawn free and counts 1" and "a
+ * pair without an admitted compatible cell makes both ends single positions and counts 2" are rnampnn_design's.  All arithmetic is fp64, LSE,
+ * SELECT, the uniforms and the salt (RNAMPNN_DESIGN_GC_SALT) are rnampnn_design_gc's.
+ *   Leaf polynomials, log domain, p_t(d), d = 0..2.  A single position: p_t(d) = LSE of z_t(c) over the admitted classes with
+ *     bit(counted_t, c) = d in class order (d = 2: -inf).  A feasible pair i < j: p_i(d) = LSE of z_i(a) + z_j(b) over its admitted compatible
+ *     cells with bit(counted_i, a) + bit(counted_j, b) = d in a-major order; p_j = "1" (0 at d = 0, -inf otherwise).
+ *   Tree.  Node (l, i) covers the positions [i 2^l, min((i+1) 2^l, n_b)), has degree deg = min(2 * positions covered, n_b, cap) and, for
+ *     l >= 1, coefficients c(k), k = 0..deg, = LSE over a = max(0, k - deg_R) .. min(k, deg_L) of L(a) + R(k - a), L and R its halves; a node
+ *     whose right half is empty equals its left half.  The root is node (ceil(log2 n_b), 0).  Truncation is exact: c(k) reads child
+ *     coefficients of index <= k only, and for k <= cap the candidate range is the same with and without the cap, so the outputs of an RNA
+ *     do not depend on count_cap, byte for byte, as long as its window and its target (below) lie within the cap.
+ *   Window.  lo and hi are clamped to [0, min(n_b, cap)], then hi = max(hi, lo).  If no count in the window has a finite root coefficient
+ *     the target is the nearest count within 0 .. min(n_b, cap) that has one, the lower count on a tie, and count_miss is its distance.  If no
+ *     count at all is finite there, the target is k_min = the sum over the leaves of the smallest d with a finite p_t(d) (0 for a leaf with
+ *     none) - the smallest reachable count - every leaf draws at its own smallest d (no total, no split, no salted uniform), which is the
+ *     exact conditional on "count = k_min", and count_miss is the distance from the window to k_min (k_min - hi when k_min > hi, lo - k_min
+ *     when k_min < lo, else 0).  When every input is finite this rule is used only when k_min > cap.
+ *   Draw, top down, as in rnampnn_design_gc: the total K = SELECT(lo .. hi, root coefficients) or the target; a node holding k hands its
+ *     left half a = SELECT(max(0, k - deg_R) .. min(k, deg_L), L(a) + R(k - a)) and its right half k - a; a leaf holding d draws its class - a
+ *     pair its cell, in a-major order - among the admitted ones that count d by rnampnn_design's rule in fp64; i receives a, j receives b.
+ *   Robustness.  NaN or +-inf logits, a NaN bias or a malformed partner table still give ids in 0..3; every index and every count is clamped
+ *     before use.  A leaf that cannot realise the count it was handed draws as rnampnn_design would (its whole admitted set); `count` reports
+ *     what was written.
+ * seq_nll is byte for byte rnampnn_score's for the written draw and `infeasible` keeps its meaning, as in rnampnn_design.  One 256-thread
+ * workgroup per (RNA, sample).  Dynamic LDS: 8 * doubles(T, cap) + T rounded up to 16 + 96 bytes (the k_min reduction borrows the 96),
+ * doubles(T, cap) = the sum over the nodes of the levels 1 .. ceil(log2 T) of min(2 * (extent within T), T, cap) + 1: 7,320 bytes at
+ * (T = 128, cap 8), 14,552 at (128, 128), 57,176 at (1000, 8).  RNAMPNN_ERR_UNSUPPORTED when that exceeds 160 KiB = 163,840 bytes; the message
+ * names the bytes, the limit and the largest T at that cap: T <= 2867 at cap 8 (163,808 bytes), 2236 at cap 16, 1833 at cap 32, 1551 at cap 64,
+ * 1017 for cap >= T.  A tree in global memory for longer RNAs is not built.  No workspace, no atomics, no runtime fill / copy node, no host
+ * synchronisation: two calls give identical bytes, the call can sit inside a captured graph, and a draw is a pure function of (seed, s, b)
+ * and the rows of RNA b - independent of B, T, S and the layout.
+ * RNAMPNN_ERR_BAD_ARG, before anything is launched: the cases of rnampnn_design; null counted, count_lo or count_hi; count_cap < 0.  With
+ * every output null the call returns RNAMPNN_OK without a launch. */
+int rnampnn_design_count(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
+                         float temperature, int32_t S, uint64_t seed, const uint64_t* seed_dev, const uint8_t* allowed,
+                         const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position,
+                         const uint8_t* counted, const int32_t* count_lo, const int32_t* count_hi, int32_t count_cap,
+                         int8_t* seqs, float* seq_nll, int32_t* infeasible, int32_t* count, int32_t* count_miss, void* stream);
 /* Distinct designs in ONE launch (csrc/design_distinct.hip): S pairwise DIFFERENT sequences per RNA under the constraints of rnampnn_design -
  * with noise != 0 an exact sample WITHOUT replacement from the constrained, tempered distribution, in sampling order; with noise == 0 the S
  * most probable admitted sequences, in descending order - each with its log-probability under that distribution.  One algorithm, a beam of

@@ -40,7 +40,16 @@ the window; the draws then hold that count).  Not built together with ``--states
 Distinct designs (``rnampnn_design_distinct``, both families, at most 256 per structure): the N sequences of a structure are pairwise
 different - ``sample`` draws them without replacement from the model's (constrained, tempered) distribution, ``best`` lists its N most
 probable sequences in descending order.  The designs CSV gains a last column ``logp`` (the log-probability of the sequence under that
-distribution); a structure that admits fewer than N sequences has fewer rows.  Not built together with ``--states`` or ``--gc-content``."""
+distribution); a structure that admits fewer than N sequences has fewer rows.  Not built together with ``--states`` or ``--gc-content``.
+
+    python rna-mpnn_amd/predict.py --ckpt Final.pt --data DIR --samples 8 --max-mutations 6 [--min-mutations 2] [--mutate-from parents.fasta]
+
+Mutation budget (``rnampnn_design_count``, both families): every draw differs from the structure's reference sequence at no more than M
+(and no fewer than m) positions - drawn exactly from the model's distribution conditioned on that and on the other constraints, not
+filtered.  The reference is the structure's own ``seqs/<id>.fasta``, or its record ``>pdb_id`` in ``--mutate-from`` (letters outside AUCG
+never count); a structure without one is an error naming its id.  The designs CSV gains the columns ``mutations`` (the Hamming distance of
+the draw to the reference) and ``mut_miss`` (0, or by how many mutations the target structure and the fixed positions alone exceed the
+budget; the draws then hold the fewest mutations they allow).  Not built together with ``--states``, ``--gc-content`` or ``--distinct``."""
 from __future__ import annotations
 
 import argparse
@@ -73,6 +82,10 @@ def parse(argv=None):
     ap.add_argument("--gc-content", default=None, help="LO:HI: every draw of --samples holds a G+C fraction in this window")
     ap.add_argument("--distinct", default=None, choices=("sample", "best"),
                     help="the draws of --samples are pairwise different: sampled without replacement, or the most probable ones")
+    ap.add_argument("--max-mutations", type=int, default=None, help="M: every draw of --samples differs from its reference at no more than M positions")
+    ap.add_argument("--min-mutations", type=int, default=None, help="m: ... and at no fewer than m positions (default 0); needs --max-mutations")
+    ap.add_argument("--mutate-from", default=None, help="FASTA with one record >pdb_id per structure: the references of --max-mutations "
+                                                        "(default: the structure's own sequence)")
     return ap.parse_args(argv)
 
 
@@ -112,6 +125,26 @@ def distinct_option(args) -> dict:
     return dict(distinct=args.distinct)
 
 
+def mutations_option(args) -> dict:
+    """The ``mutations`` keyword of ``predict`` from ``--max-mutations`` / ``--min-mutations`` / ``--mutate-from``; empty without them.
+    ``ValueError`` naming the flags for a budget that is not 0 <= m <= M, one of the other two flags without ``--max-mutations``, with
+    ``--states``, ``--gc-content`` or ``--distinct`` and without ``--samples``."""
+    if args.max_mutations is None:
+        if args.min_mutations is not None or args.mutate_from:
+            raise ValueError("--min-mutations and --mutate-from need --max-mutations M")
+        return {}
+    for flag, value in (("--states", args.states), ("--gc-content", args.gc_content), ("--distinct", args.distinct)):
+        if value:
+            raise ValueError(f"--max-mutations together with {flag} is not built: the budget conditions plain single-state designs only")
+    lo = 0 if args.min_mutations is None else args.min_mutations
+    if lo < 0 or args.max_mutations < lo:
+        raise ValueError(f"--max-mutations / --min-mutations: the budget needs 0 <= m <= M, got m = {lo}, M = {args.max_mutations}")
+    if args.samples <= 0:
+        raise ValueError("--max-mutations needs --samples N > 0")
+    from rnampnn.utils.constraints import read_reference_fasta
+    return dict(mutations=(lo, args.max_mutations, read_reference_fasta(args.mutate_from) if args.mutate_from else None))
+
+
 def checkpoint_family(path: str) -> str:
     """The ``model`` key of a checkpoint file; a file without one is an ``rdesign`` checkpoint.  ``weights_only=True``."""
     ck = torch.load(path, map_location="cpu", weights_only=True)
@@ -122,7 +155,8 @@ def checkpoint_family(path: str) -> str:
 
 
 def run(args, log=print):
-    distinct = distinct_option(args)                               # a combination that is not built fails here, before the model is loaded
+    mutations = mutations_option(args)                             # a combination that is not built fails here, before the model is loaded
+    distinct = distinct_option(args)
     gc = gc_option(args)                                           # a bad window fails here, before the model is loaded
     family = checkpoint_family(args.ckpt)
     if family == "rnampnn":
@@ -131,7 +165,8 @@ def run(args, log=print):
     else:
         from rdesign.utils.predict import predict
         from rdesign.utils.train import load_checkpoint
-    extra = dict(samples=args.samples, temperature=args.temperature, seed=args.seed, designs_csv=args.designs_out, **design_options(args), **gc, **distinct)
+    extra = dict(samples=args.samples, temperature=args.temperature, seed=args.seed, designs_csv=args.designs_out, **design_options(args), **gc, **distinct,
+                 **mutations)
     if args.states:
         if family != "rnampnn":
             raise ValueError("--states designs with rnampnn checkpoints only; for an rdesign checkpoint call RNAModel.design(states=...) "

@@ -33,8 +33,8 @@ import torch.nn.functional as F
 
 from .. import _native
 from rnampnn.model._base import _prep, _stream
-from rnampnn.model.decode import (check_distinct, check_state_lengths, design_distinct_from_logits, design_from_logits, design_gc_from_logits,
-                                  letters_packed, score_logits)
+from rnampnn.model.decode import (check_distinct, check_mutations, check_state_lengths, design_distinct_from_logits, design_from_logits,
+                                  design_gc_from_logits, design_mutations_from_logits, letters_packed, score_logits)
 
 _PREC = {"f32": _native.PREC_F32, "bf16": _native.PREC_BF16}
 _TRAIN = {"f32": _native.TRAIN_F32, "bf16": _native.TRAIN_BF16_MIXED}
@@ -428,7 +428,7 @@ class RNAModel(nn.Module):
 
     @torch.no_grad()
     def design(self, X, mask, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None, lengths=None, states=None,
-               state_weights=None, gc_content=None, distinct=None):
+               state_weights=None, gc_content=None, distinct=None, mutations=None):
         """``n_samples`` sequences per RNA drawn from this model's read-out at ``temperature`` and scored, in one ``rnampnn_design`` launch
         on the packed logits -> (seqs int8 (n_samples,B,T), -1 on padding; seq_nll (n_samples,B) f32, the model's own temperature-1 NLL of
         each draw; infeasible (B,) int32).  ``constraints``: a ``rnampnn.utils.constraints.DesignConstraints`` (fixed nucleotides, base
@@ -440,13 +440,21 @@ class RNAModel(nn.Module):
         ``states``.  ``distinct`` ("sample" or "best"; ``None`` is everything above, unchanged): ``n_samples`` pairwise DIFFERENT sequences
         per RNA (``design_distinct_from_logits``) - an exact sample without replacement, or the most probable admitted sequences in
         descending order -> (seqs, seq_nll, infeasible, logp (n_samples,B) f32, n_distinct (B,) int32); not built together with ``states``
-        or ``gc_content``."""
+        or ``gc_content``.  ``mutations`` (``(reference, max)`` or ``(reference, min, max)``, reference (B,T) class ids, e.g. the native
+        sequence): the draws - under ``constraints`` or free - differ from the reference at between min (default 0) and max positions,
+        drawn exactly from the model's distribution conditioned on that (``design_count_from_logits``) -> (seqs, seq_nll, infeasible,
+        n_mut (n_samples,B) int32, mut_miss (B,) int32 = how far the structure and the fixed positions alone push the count out of the
+        budget, 0 when it is reachable); not built together with ``states``, ``gc_content`` or ``distinct``."""
+        mutations = check_mutations(mutations, states, gc_content, distinct)
         check_distinct(distinct, states, gc_content)
         if gc_content is not None and states is not None:
             raise ValueError("gc_content together with states is not built: the G+C window conditions the draws of rnampnn_design only")
         if states is not None and lengths is not None:
             check_state_lengths(states, lengths)
         logits, cu, T = self._packed_logits(X, mask, lengths)
+        if mutations is not None:
+            return design_mutations_from_logits(logits, mutations, cu_seqlens=cu, max_len=T, n_samples=n_samples, temperature=temperature, seed=seed,
+                                                constraints=constraints)
         if distinct is not None:
             return design_distinct_from_logits(logits, cu_seqlens=cu, max_len=T, n_samples=n_samples, temperature=temperature, seed=seed,
                                                constraints=constraints, mode=distinct)

@@ -4,8 +4,9 @@ from __future__ import annotations
 import os
 from typing import List, Optional, Tuple
 
-from rnampnn.model.decode import check_distinct, design_distinct_from_logits, design_from_logits, design_gc_from_logits, letters_padded, score_logits
-from rnampnn.utils.constraints import batch_constraints
+from rnampnn.model.decode import (check_budget, check_distinct, design_distinct_from_logits, design_from_logits, design_gc_from_logits,
+                                  design_mutations_from_logits, letters_padded, score_logits)
+from rnampnn.utils.constraints import batch_constraints, mutation_references, padded_references
 from rnampnn.utils.data import bucket_batches
 from rnampnn.utils.predict import write_csv
 
@@ -14,7 +15,7 @@ from .data import load_rna_dir, padded_loader
 
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
-            wobble: bool = True, gc_content=None, distinct=None) -> List[Tuple[str, str]]:
+            wobble: bool = True, gc_content=None, distinct=None, mutations=None) -> List[Tuple[str, str]]:
     """Read ``data_path`` (``coords/<id>.npy`` + ``seqs/<id>.fasta``), design a sequence for every structure in length-bucketed batches
     (``RNAModel.predict_sequences``: the tree read-out when one is attached, else the read-out's argmax) and write ``out_csv`` with one
     ``pdb_id,seq`` row per input in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure at
@@ -24,7 +25,14 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     ``rnampnn_design_gc``, conditioned exactly on the G+C fraction of every structure lying in that window, and ``designs_csv`` gains the
     last columns ``gc`` (the fraction of the draw) and ``gc_miss``.  ``distinct`` ("sample" / "best"): the draws come from
     ``rnampnn_design_distinct`` and are pairwise different per structure; ``designs_csv`` gains a last column ``logp`` and holds no row for
-    a slot the structure's admitted sequences do not fill.  Not built together with ``gc_content``."""
+    a slot the structure's admitted sequences do not fill.  Not built together with ``gc_content``.  ``mutations`` (min, max, references):
+    a mutation budget - the draws come from ``rnampnn_design_count`` and differ from the reference sequence of the structure
+    (``references[pdb_id]``, or with None its own fasta sequence) at between min and max positions; ``designs_csv`` gains the last columns
+    ``mutations`` and ``mut_miss``.  Not built together with ``gc_content`` or ``distinct``."""
+    if mutations is not None:
+        check_budget(mutations[0], mutations[1], None, gc_content, distinct)
+        if samples <= 0:
+            raise ValueError("a mutation budget needs samples > 0")
     check_distinct(distinct, None, gc_content)
     model.eval()
     items = load_rna_dir(data_path)
@@ -32,6 +40,8 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
         raise ValueError(f"no usable structure under {data_path} (coords/<id>.npy (L,7,3) + seqs/<id>.fasta)")
     if samples > 0 and not designs_csv:
         designs_csv = os.path.splitext(out_csv)[0] + "_designs.csv"
+    refs = None if mutations is None else mutation_references(mutations[2], [it[0] for it in items], [it[1].shape[0] for it in items],
+                                                              [it[2] for it in items])
     batches = bucket_batches([c.shape[0] for _, c, _ in items], batch_size, max_rows, seed=0)
     device = model._device()
     seqs, designs = {}, {}
@@ -42,13 +52,18 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             lens = [int(v) for v in lengths]
             logits, cu, T = model._packed_logits(X, mask, lengths)
             cons = batch_constraints(constraints, [items[i][0] for i in idx], lens, T, bias=bias, wobble=wobble, omit=omit)
-            gcs = logp = None
+            gcs = muts = logp = None
             filled = [samples] * len(idx)
             if distinct is not None:
                 draws, nll, bad, logp, filled = design_distinct_from_logits(logits, cu_seqlens=cu, max_len=T, n_samples=samples,
                                                                             temperature=temperature, seed=seed + bi,
                                                                             constraints=cons.to_device(device), mode=distinct)
                 logp, filled = logp.cpu().tolist(), filled.cpu().tolist()
+            elif mutations is not None:
+                draws, nll, bad, count, miss = design_mutations_from_logits(
+                    logits, (padded_references(refs, idx, T), (mutations[0], mutations[1])), cu_seqlens=cu, max_len=T, n_samples=samples,
+                    temperature=temperature, seed=seed + bi, constraints=cons.to_device(device))
+                muts = (count.cpu().tolist(), miss.cpu().tolist())
             elif gc_content is not None:
                 draws, nll, bad, count, miss = design_gc_from_logits(logits, cu_seqlens=cu, max_len=T, n_samples=samples,
                                                                      temperature=temperature, seed=seed + bi,
@@ -65,11 +80,12 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
                         continue                                    # fewer admitted sequences than samples: the slot is empty
                     designs.setdefault(i, []).append((s, text, f"{nll[s][r] / lens[r]:.6f}", f"{match[s][r] / lens[r]:.6f}", bad[r])
                                                      + (() if gcs is None else (f"{gcs[0][s][r] / lens[r]:.6f}", gcs[1][r]))
+                                                     + (() if muts is None else (muts[0][s][r], muts[1][r]))
                                                      + (() if logp is None else (f"{logp[s][r]:.6f}",)))
     rows = [(items[i][0], seqs[i]) for i in range(len(items))]
     write_csv(out_csv, "pdb_id,seq", rows)
     if samples > 0:
         write_csv(designs_csv, "pdb_id,sample,seq,nll_per_nt,recovery,infeasible" + (",gc,gc_miss" if gc_content is not None else "")
-                  + (",logp" if distinct is not None else ""),
+                  + (",mutations,mut_miss" if mutations is not None else "") + (",logp" if distinct is not None else ""),
                   [(it[0],) + row for i, it in enumerate(items) for row in designs[i]])
     return rows

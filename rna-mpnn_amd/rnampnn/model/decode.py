@@ -1,7 +1,8 @@
 """Decoding from logits, as free functions over the C ABI's decode family: argmax + recovery (``rnampnn_argmax_recovery``), free draws
 (``rnampnn_sample``), scores (``rnampnn_score``), constrained and multi-state design (``rnampnn_design``, ``rnampnn_design_tied``), design
-under a G+C content window (``rnampnn_design_gc``), distinct designs (``rnampnn_design_distinct``) and the letters of class ids.  Needs the library and ``_base`` only, so both model
-packages import it at module level."""
+under a G+C content window (``rnampnn_design_gc``), design within a count window / a mutation budget (``rnampnn_design_count``), distinct
+designs (``rnampnn_design_distinct``) and the letters of class ids.  Needs the library and ``_base`` only, so both model packages import
+it at module level."""
 from __future__ import annotations
 
 import ctypes as C
@@ -196,6 +197,118 @@ def design_gc_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = N
             int(bool(c.wobble)) if c is not None else 1, _ptr(bi), per_position, _ptr(lo), _ptr(hi), _ptr(seqs), _ptr(nll), _ptr(bad),
             _ptr(count), _ptr(miss), _stream(device)))
     return seqs, nll, bad, count, miss
+
+
+def mutation_sets(reference: torch.Tensor) -> torch.Tensor:
+    """(B,T) class ids of a reference sequence -> the ``counted`` tensor of ``design_count_from_logits`` that counts MUTATIONS against it:
+    15 ^ (1 << id) (every class but the reference's), 0 where the id is outside 0..3 (padding, unknown letters: such a position never
+    counts).  uint8 on the reference's own device; no host synchronisation."""
+    ref = reference.to(torch.int64)
+    known = (ref >= 0) & (ref <= 3)
+    return torch.where(known, 15 ^ (1 << ref.clamp(0, 3)), torch.zeros_like(ref)).to(torch.uint8)
+
+
+def count_window(window, cap: Optional[int], B: int) -> Tuple[torch.Tensor, int]:
+    """``window`` - a pair of ints (lo, hi) for every RNA, or a (B,2) int tensor - and ``cap`` -> ((B,2) int32 on the window's own device,
+    the cap).  ``cap`` defaults to the largest hi of a HOST window; ``ValueError`` for another shape, a negative cap, a device window
+    without ``cap`` (it is not read back here) and a host hi above ``cap`` (the kernel would clamp it silently)."""
+    w = window if torch.is_tensor(window) else torch.as_tensor([int(v) for v in window], dtype=torch.int32)
+    if w.dtype.is_floating_point or w.dtype == torch.bool:
+        raise ValueError(f"window holds absolute counts: pass ints, got {w.dtype}")
+    if tuple(w.shape) == (2,):
+        w = w.expand(B, 2)
+    if tuple(w.shape) != (B, 2):
+        raise ValueError(f"window must be a pair (lo, hi) of counts or a (B, 2) = {(B, 2)} int tensor, got {tuple(w.shape)}")
+    if cap is not None and int(cap) < 0:
+        raise ValueError(f"cap = {cap} is negative")
+    if w.device.type != "cpu":
+        if cap is None:
+            raise ValueError("a window on the device needs cap: it sizes the count tree and is not read back from the device")
+        return w.to(torch.int32), int(cap)
+    top = int(w[:, 1].max()) if B > 0 else 0
+    if cap is None:
+        return w.to(torch.int32), max(top, 0)
+    if top > int(cap):
+        raise ValueError(f"window: hi = {top} lies above cap = {int(cap)}")
+    return w.to(torch.int32), int(cap)
+
+
+def design_count_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
+                             max_len: Optional[int] = None, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None,
+                             counted: Optional[torch.Tensor] = None, window=(0, 0),
+                             cap: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``rnampnn_design_count`` (include/rnampnn_hip.h): the draws of ``design_from_logits`` conditioned exactly on a count lying in a
+    window, in one launch -> (seqs, seq_nll, infeasible, count (S,B) int32, count_miss (B,) int32 = 0 when the window is reachable under
+    the constraints, else its distance to the count the draws then hold).  ``counted`` (B,T) uint8, padded in both layouts: bits 0..3 mark
+    the classes (AUCG) that count 1 at that position (``mutation_sets(reference)``: the count is the number of mutations).  ``window``: a
+    pair of ints (lo, hi) for every RNA or a (B,2) int tensor, absolute counts.  ``cap``: no count above it is ever drawn; it sizes the
+    tree in LDS (T <= 2867 at cap 8, 1017 without a cap).  It defaults to the largest hi of a host-side window; a device window without
+    ``cap`` or a host hi above ``cap`` is a ``ValueError``.  Layouts and ``constraints`` as in ``design_from_logits``.  CUDA logits only
+    (there is no CPU fallback); no host synchronisation."""
+    device = logits.device
+    if device.type != "cuda":
+        raise RuntimeError("rnampnn_design_count runs on an MI355X: pass CUDA logits (there is no CPU fallback)")
+    if counted is None:
+        raise ValueError("counted is required: the (B, T) sets of classes that count (mutation_sets(reference) for a mutation budget)")
+    c = constraints
+    al = None if c is None or c.allowed is None else _prep(c.allowed, device, torch.uint8)
+    pa = None if c is None or c.partner is None else _prep(c.partner, device, torch.int32)
+    bi = None if c is None or c.bias is None else _prep(c.bias, device)
+    cs = _prep(counted, device, torch.uint8)
+    lg, m, cu, B, T = _layout(logits, mask, cu_seqlens, (cs, al, pa), max_len)
+    for name, t in (("counted", cs), ("constraints.allowed", al), ("constraints.partner", pa)):
+        if t is not None and tuple(t.shape) != (B, T):
+            raise ValueError(f"{name} must be padded to (B, T) = {(B, T)}, got {tuple(t.shape)}")
+    per_position = int(bi is not None and tuple(bi.shape) == (B, T, 4))
+    if bi is not None and not per_position and tuple(bi.shape) != (4,):
+        raise ValueError(f"constraints.bias must be (4,) or (B, T, 4) = {(B, T, 4)}, got {tuple(bi.shape)}")
+    _check_logits(lg, m, B, T)
+    w, cap = count_window(window, cap, max(B, 0))
+    w = w.to(device, non_blocking=True)
+    lo, hi = w[:, 0].contiguous(), w[:, 1].contiguous()
+    S = int(n_samples)
+    seqs = torch.empty(max(S, 0), max(B, 0), max(T, 0), dtype=torch.int8, device=device)
+    nll = torch.empty(max(S, 0), max(B, 0), dtype=torch.float32, device=device)
+    bad = torch.empty(max(B, 0), dtype=torch.int32, device=device)
+    count = torch.empty(max(S, 0), max(B, 0), dtype=torch.int32, device=device)
+    miss = torch.empty(max(B, 0), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _native.check(_native.lib().rnampnn_design_count(
+            _ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(cu), B, T, float(temperature), S, _seed64(seed), None, _ptr(al), _ptr(pa),
+            int(bool(c.wobble)) if c is not None else 1, _ptr(bi), per_position, _ptr(cs), _ptr(lo), _ptr(hi), cap, _ptr(seqs), _ptr(nll),
+            _ptr(bad), _ptr(count), _ptr(miss), _stream(device)))
+    return seqs, nll, bad, count, miss
+
+
+def check_budget(lo: int, hi: int, states=None, gc_content=None, distinct=None) -> Tuple[int, int]:
+    """A mutation budget of between ``lo`` and ``hi`` positions -> (lo, hi).  ``ValueError`` for a negative or inverted budget and for
+    a combination that is not built; touches no device."""
+    for name, value in (("states", states), ("gc_content", gc_content), ("distinct", distinct)):
+        if value is not None:
+            raise ValueError(f"mutations together with {name} is not built: the budget conditions the draws of rnampnn_design on one count")
+    lo, hi = int(lo), int(hi)
+    if lo < 0 or hi < lo:
+        raise ValueError(f"mutations: the budget needs 0 <= min <= max, got min = {lo}, max = {hi}")
+    return lo, hi
+
+
+def check_mutations(mutations, states=None, gc_content=None, distinct=None):
+    """``design(..., mutations=(reference, max))`` or ``(reference, min, max)`` -> (reference, (min, max)), or None for None.
+    ``ValueError`` for another form and for what ``check_budget`` refuses; touches no device."""
+    if mutations is None:
+        return None
+    if not isinstance(mutations, (tuple, list)) or len(mutations) not in (2, 3) or not torch.is_tensor(mutations[0]):
+        check_budget(0, 0, states, gc_content, distinct)               # (a combination that is not built is the more useful message)
+        raise ValueError("mutations must be (reference, max) or (reference, min, max) with reference a (B, T) tensor of class ids")
+    lo, hi = (0, mutations[1]) if len(mutations) == 2 else (mutations[1], mutations[2])
+    return mutations[0], check_budget(lo, hi, states, gc_content, distinct)
+
+
+def design_mutations_from_logits(logits: torch.Tensor, mutations, **kw):
+    """``design_count_from_logits`` as a mutation budget: ``mutations`` as ``check_mutations`` returns it -> (seqs, seq_nll, infeasible,
+    n_mut (S,B) int32 = the Hamming distance of each draw to the reference, mut_miss (B,) int32)."""
+    reference, window = mutations
+    return design_count_from_logits(logits, counted=mutation_sets(reference.to(logits.device)), window=window, cap=window[1], **kw)
 
 
 DISTINCT_MODES = {"sample": 1, "best": 0}

@@ -23,8 +23,9 @@ from .. import _native
 from ..config.glob import DEFAULT_SEED, REVERSE_VOCAB
 from ..utils.data import check_prefix_mask
 from ._base import NativeModule, _prep, _ptr, _stream
-from .decode import (SCORE_OUTPUTS, argmax_recovery, check_distinct, check_state_lengths, design_distinct_from_logits, design_from_logits, design_gc_from_logits,  # noqa: F401
-                     letters_packed, letters_padded, sample_from_logits, score_logits)
+from .decode import (SCORE_OUTPUTS, argmax_recovery, check_distinct, check_mutations, check_state_lengths, design_distinct_from_logits,  # noqa: F401
+                     design_from_logits, design_gc_from_logits, design_mutations_from_logits, letters_packed, letters_padded,
+                     sample_from_logits, score_logits)
 from ._schema import DEFAULT_HPARAMS
 
 _CHECK_MASKS = os.environ.get("RNAMPNN_CHECK_MASKS", "0") == "1"
@@ -545,7 +546,7 @@ class RNAMPNN(NativeModule):
 
     @torch.no_grad()
     def design(self, coords: torch.Tensor, mask: torch.Tensor, n_samples: int = 8, temperature: float = 0.1, seed: int = 0,
-               T_norm: int = 0, constraints=None, states=None, state_weights=None, lengths=None, gc_content=None, distinct=None):
+               T_norm: int = 0, constraints=None, states=None, state_weights=None, lengths=None, gc_content=None, distinct=None, mutations=None):
         """``sample`` plus the score of every draw against the SAME logits, with one forward: -> (seqs int8 (n_samples,B,T), -1 on
         padding; seq_nll (n_samples,B) f32).  The NLL is the model's own (temperature 1) likelihood, so designs drawn at different
         temperatures rank on one scale.  ``constraints`` (``rnampnn.utils.constraints.DesignConstraints``: fixed nucleotides, base
@@ -559,13 +560,21 @@ class RNAMPNN(NativeModule):
         with ``states``.  ``distinct`` ("sample" or "best"; ``None`` is everything above, unchanged): ``n_samples`` pairwise DIFFERENT
         sequences per RNA (``design_distinct_from_logits``) - an exact sample without replacement, or the most probable admitted sequences
         in descending order - under ``constraints`` or free -> (seqs, seq_nll, infeasible, logp (n_samples,B) f32, n_distinct (B,) int32); not
-        built together with ``states`` or ``gc_content``."""
+        built together with ``states`` or ``gc_content``.  ``mutations`` (``(reference, max)`` or ``(reference, min, max)``, reference (B,T)
+        class ids, e.g. the native sequence): the draws - under ``constraints`` or free - differ from the reference at between min
+        (default 0) and max positions, drawn exactly from the model's distribution conditioned on that (``design_count_from_logits``) ->
+        (seqs, seq_nll, infeasible, n_mut (n_samples,B) int32, mut_miss (B,) int32 = how far the structure and the fixed positions alone
+        push the count out of the budget, 0 when it is reachable); not built together with ``states``, ``gc_content`` or ``distinct``."""
+        mutations = check_mutations(mutations, states, gc_content, distinct)
         check_distinct(distinct, states, gc_content)
         if gc_content is not None and states is not None:
             raise ValueError("gc_content together with states is not built: the G+C window conditions the draws of rnampnn_design only")
         if states is not None and lengths is not None:
             check_state_lengths(states, lengths)
         logits = self._run(coords, mask, T_norm=T_norm)["logits"]
+        if mutations is not None:
+            return design_mutations_from_logits(logits, mutations, mask=mask, n_samples=n_samples, temperature=temperature, seed=seed,
+                                                constraints=constraints)
         if distinct is not None:
             return design_distinct_from_logits(logits, mask=mask, n_samples=n_samples, temperature=temperature, seed=seed,
                                                constraints=constraints, mode=distinct)

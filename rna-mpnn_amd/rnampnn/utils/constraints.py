@@ -86,6 +86,51 @@ def parse_gc_content(text: str) -> Tuple[float, float]:
     return window
 
 
+def read_reference_fasta(path: str) -> Dict[str, str]:
+    """A FASTA file with one record per structure (``>pdb_id`` and what follows up to the first blank) -> {pdb_id: sequence}: the
+    references of a mutation budget (``--mutate-from``).  ``ValueError`` for sequence lines before the first header."""
+    refs: Dict[str, str] = {}
+    rid = None
+    for line in open(path):
+        line = line.strip()
+        if line.startswith(">"):
+            rid = line[1:].split()[0] if line[1:].split() else ""
+            refs[rid] = ""
+        elif line:
+            if rid is None:
+                raise ValueError(f"{path}: sequence before the first '>' header")
+            refs[rid] += line
+    return refs
+
+
+def mutation_references(references: Optional[Dict[str, str]], ids: Sequence[str], lengths: Sequence[int], natives) -> List[np.ndarray]:
+    """The reference sequence of every structure as int32 class ids (-1 for a letter outside AUCG, which never counts as a mutation;
+    T = U): ``references[pdb_id]`` when a table is given, else ``natives[i]`` (the structure's own sequence as class ids, or None).
+    ``ValueError`` naming the id for a structure without a reference and for a reference of another length."""
+    out = []
+    for i, (rid, n) in enumerate(zip(ids, lengths)):
+        if references is not None:
+            if rid not in references:
+                raise ValueError(f"mutations: the reference file has no sequence for {rid!r}")
+            ref = np.array([VOCAB.get(ch, -1) for ch in references[rid].upper().replace("T", "U")], dtype=np.int32)
+        elif natives[i] is None:
+            raise ValueError(f"mutations: structure {rid!r} has no reference sequence (no usable seqs/{rid}.fasta); pass a reference file")
+        else:
+            ref = np.asarray(natives[i], dtype=np.int32)
+        if len(ref) != int(n):
+            raise ValueError(f"mutations: the reference of {rid!r} has {len(ref)} letters, the structure {int(n)} nucleotides")
+        out.append(ref)
+    return out
+
+
+def padded_references(refs: Sequence[np.ndarray], idx: Sequence[int], max_len: int) -> torch.Tensor:
+    """The references of one batch -> (B, max_len) int32, -1 on padding."""
+    out = torch.full((len(idx), max_len), -1, dtype=torch.int32)
+    for r, i in enumerate(idx):
+        out[r, :len(refs[i])] = torch.from_numpy(refs[i])
+    return out
+
+
 def omit_mask(letters: str) -> int:
     """``--omit`` letters -> the ``allowed`` set without them."""
     m = FREE

@@ -11,8 +11,9 @@ import numpy as np
 import torch
 
 from ..config.glob import VOCAB
-from ..model.decode import check_distinct, design_distinct_from_logits, design_from_logits, design_gc_from_logits, letters_packed, letters_padded, sample_from_logits, score_logits
-from .constraints import batch_constraints
+from ..model.decode import (check_budget, check_distinct, design_distinct_from_logits, design_from_logits, design_gc_from_logits,
+                            design_mutations_from_logits, letters_packed, letters_padded, sample_from_logits, score_logits)
+from .constraints import batch_constraints, mutation_references, padded_references
 from .data import PackedLoader, bucket_batches, fill_nan_deterministic, read_fasta
 
 
@@ -115,7 +116,7 @@ def write_csv(path: str, header: str, rows) -> None:
 @torch.no_grad()
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
-            wobble: bool = True, states: Optional[dict] = None, gc_content=None, distinct=None) -> List[Tuple[str, str]]:
+            wobble: bool = True, states: Optional[dict] = None, gc_content=None, distinct=None, mutations=None) -> List[Tuple[str, str]]:
     """Design a sequence for every structure under ``data_path`` in length-bucketed var-len batches (``forward_packed``): the tree
     read-out on the packed embedding when one is attached, else the read-out's argmax (``rnampnn_score``'s ``pred``); write ``out_csv``
     with one ``pdb_id,seq`` row per structure in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure
@@ -133,7 +134,17 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     ``distinct`` ("sample" / "best"): the draws - constrained or free - come from ``rnampnn_design_distinct`` and are pairwise different per
     structure (a sample without replacement / the most probable sequences in descending order); ``designs_csv`` gains a last column
     ``logp`` and holds no row for a slot the structure's admitted sequences do not fill.  Not built together with ``states`` or
-    ``gc_content``."""
+    ``gc_content``.
+    ``mutations`` (min, max, references): a mutation budget - the draws, constrained or free, come from ``rnampnn_design_count`` and differ
+    from the structure's reference sequence at between min and max positions, drawn exactly from the model's distribution conditioned on
+    that.  ``references`` is {pdb_id: sequence} (``read_reference_fasta``) or None for the structure's own ``seqs/<id>.fasta``; a
+    structure without a reference is a ``ValueError`` naming its id.  ``designs_csv`` gains the last columns ``mutations`` (the Hamming
+    distance of the draw to the reference) and ``mut_miss`` (0, or by how many mutations the structure and the fixed positions alone
+    exceed the budget).  Not built together with ``states``, ``gc_content`` or ``distinct``."""
+    if mutations is not None:
+        check_budget(mutations[0], mutations[1], states, gc_content, distinct)
+        if samples <= 0:
+            raise ValueError("a mutation budget needs samples > 0")
     check_distinct(distinct, states, gc_content)
     if gc_content is not None and states is not None:
         raise ValueError("gc_content together with states is not built")
@@ -145,6 +156,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     if samples > 0 and not designs_csv:
         designs_csv = os.path.splitext(out_csv)[0] + "_designs.csv"
     ids, lengths = [it[0] for it in items], [int(it[1].shape[0]) for it in items]
+    refs = None if mutations is None else mutation_references(mutations[2], ids, lengths, [it[2] for it in items])
     trees = getattr(model, "xgb_readout", None)
     constrained = constraints is not None or bias is not None or bool(omit) or not wobble
     seqs, designs = {}, {}
@@ -172,13 +184,18 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
         cons = None
         if constrained:
             cons = batch_constraints(constraints, [ids[i] for i in idx], lens, max_len, bias=bias, wobble=wobble, omit=omit).to_device(device)
-        gcs = logp = None
+        gcs = muts = logp = None
         filled = [samples] * len(idx)
         if distinct is not None:
             draws, dnll, bad, logp, filled = design_distinct_from_logits(logits, cu_seqlens=cu, max_len=max_len, n_samples=samples,
                                                                          temperature=temperature, seed=seed + bi, constraints=cons,
                                                                          mode=distinct)
             bad, logp, filled = (bad if constrained else None), logp.cpu().tolist(), filled.cpu().tolist()
+        elif mutations is not None:
+            draws, dnll, bad, count, miss = design_mutations_from_logits(
+                logits, (padded_references(refs, idx, max_len), (mutations[0], mutations[1])), cu_seqlens=cu, max_len=max_len,
+                n_samples=samples, temperature=temperature, seed=seed + bi, constraints=cons)
+            bad, muts = (bad if constrained else None), (count.cpu().tolist(), miss.cpu().tolist())
         elif gc_content is not None:
             draws, dnll, bad, count, miss = design_gc_from_logits(logits, cu_seqlens=cu, max_len=max_len, n_samples=samples,
                                                                   temperature=temperature, seed=seed + bi, constraints=cons,
@@ -203,6 +220,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
                         continue                                    # fewer admitted sequences than samples: the slot is empty
                     designs.setdefault(i, []).append((s, text[r], f"{nll[s][r] / lens[r]:.6f}", recs[r]) + (() if bad is None else (bad[r],))
                                                      + (() if gcs is None else (f"{gcs[0][s][r] / lens[r]:.6f}", gcs[1][r]))
+                                                     + (() if muts is None else (muts[0][s][r], muts[1][r]))
                                                      + (() if logp is None else (f"{logp[s][r]:.6f}",)))
                 continue
             r = 0
@@ -218,5 +236,6 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
                   [(group[0],) + row for g, group in enumerate(groups) for row in designs[g]])
     elif samples > 0:
         write_csv(designs_csv, "pdb_id,sample,seq,nll_per_nt,recovery" + (",infeasible" if constrained else "")
-                  + (",gc,gc_miss" if gc_content is not None else "") + (",logp" if distinct is not None else ""), [(rid,) + row for i, rid in enumerate(ids) for row in designs[i]])
+                  + (",gc,gc_miss" if gc_content is not None else "") + (",mutations,mut_miss" if mutations is not None else "")
+                  + (",logp" if distinct is not None else ""), [(rid,) + row for i, rid in enumerate(ids) for row in designs[i]])
     return rows

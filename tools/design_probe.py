@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
-"""The measurement behind DESIGN.md section 9 "Constrained design", "Multi-state design", "Design under a G+C window" and "Distinct designs"
-(profiles/design_kernel_stats.txt, profiles/design_tied_kernel_stats.txt, profiles/design_gc_kernel_stats.txt,
-profiles/design_distinct_kernel_stats.txt): the C2 batch (256 RNAs x 100..140 nt), S = 8 sequences per RNA.
+"""The measurement behind DESIGN.md section 9 "Constrained design", "Multi-state design", "Design under a G+C window", "Distinct designs"
+and "Mutation budget" (profiles/design_kernel_stats.txt, profiles/design_tied_kernel_stats.txt, profiles/design_gc_kernel_stats.txt,
+profiles/design_distinct_kernel_stats.txt, profiles/design_count_kernel_stats.txt): the C2 batch (256 RNAs x 100..140 nt), S = 8 sequences per RNA.
 usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + rnampnn_score (seq_nll): the unconstrained pair of launches
        python tools/design_probe.py design [calls=50]         rnampnn_design: free, then with a hairpin's pairs + a fixed GNRA loop per RNA
        python tools/design_probe.py tied [calls=50]           rnampnn_design (free, hairpin) and then rnampnn_design_tied: one state per group
                                                               free, one state per group with the hairpins, 64 groups x 4 states with one 3-node chain
        python tools/design_probe.py gc [calls=50]             rnampnn_design (free, hairpin) and then rnampnn_design_gc with the window 40..60 %:
                                                               free, then with the hairpins
+       python tools/design_probe.py count                     rnampnn_design (free, hairpin) and then, in 5 alternating rounds of 10 calls each,
+                                                              rnampnn_design_gc 40..60 % and rnampnn_design_count: (a) C|G counted, cap T, the
+                                                              same windows (the work of rnampnn_design_gc), each free and with the hairpins;
+                                                              (b) at most 8 mutations from a random reference, cap 8, free; (c) the same budget
+                                                              with the hairpins and a reference that is compatible with them
        python tools/design_probe.py distinct [calls=50]       rnampnn_design (free, hairpin) and then rnampnn_design_distinct at S = 8 and S = 64,
                                                               "sample" then "best", each free and then with the hairpins (8 legs)
 HIP events around each loop of back-to-back calls of the Python wrappers.  Run either under `rocprofv3 --kernel-trace --stats -- python ...`
@@ -74,6 +79,64 @@ else:
               f"{float(((seqs >= 2).sum(-1).double() / m.sum(dim=1).double()).min()):.3f} .. "
               f"{float(((seqs >= 2).sum(-1).double() / m.sum(dim=1).double()).max()):.3f}), gc_miss total {int(g_miss.sum())}, "
               f"infeasible equal {bool((g_bad == bad).all())}, mean NLL per nt {float(g_nll.sum()) / (S * int(mask.sum())):.4f}")
+    if what == "count":
+        # Six variants in alternating rounds of one process, so that k_design_count is compared with k_design_gc of the SAME run and the
+        # round-to-round spread of either is visible: k_design_gc 40..60 % free / hairpins; (a) rnampnn_design_count with C|G counted
+        # everywhere, cap = T and the same windows - the work of k_design_gc - free / hairpins; (b) a random reference, at most 8
+        # mutations, cap 8, free; (c) the same budget with the hairpins, the reference made compatible with them (complementary over
+        # the stem, GAAA in the loop: the structure alone forces no mutation).
+        from rnampnn.model import decode as D
+        from rnampnn.model.decode import gc_counts, gc_fractions
+        rounds, per_round, warm = 5, 10, 3
+        kw = dict(n_samples=S, temperature=0.1, seed=1)
+        lo, hi = gc_counts(gc_fractions((0.4, 0.6), B).cuda(), m.sum(dim=1))
+        window = torch.stack([lo, hi], dim=1)
+        cg = torch.full((B, T), 12, dtype=torch.uint8, device="cuda")
+        ref = torch.randint(0, 4, (B, T), generator=torch.Generator().manual_seed(1))
+        ref_hp = ref.clone()
+        for b, n in enumerate(lens):
+            stem = (n - 4) // 2
+            for i in range(stem):
+                ref_hp[b, n - (n - 2 * stem - 4) - 1 - i] = (1, 0, 3, 2)[int(ref_hp[b, i])]
+            ref_hp[b, stem:stem + 4] = torch.tensor([3, 0, 0, 0])
+        sets, sets_hp = D.mutation_sets(ref.cuda()), D.mutation_sets(ref_hp.cuda())
+        variants = [
+            ("rnampnn_design_gc 40..60 %, no constraints", lambda: M.design_gc_from_logits(logits, mask=m, gc_content=(0.4, 0.6), **kw)),
+            ("rnampnn_design_count (a) C|G counted, cap T, 40..60 %, no constraints",
+             lambda: D.design_count_from_logits(logits, mask=m, counted=cg, window=window, cap=T, **kw)),
+            ("rnampnn_design_gc 40..60 %, hairpin pairs + GNRA + bias",
+             lambda: M.design_gc_from_logits(logits, mask=m, constraints=cons, gc_content=(0.4, 0.6), **kw)),
+            ("rnampnn_design_count (a) C|G counted, cap T, 40..60 %, hairpin pairs + GNRA + bias",
+             lambda: D.design_count_from_logits(logits, mask=m, constraints=cons, counted=cg, window=window, cap=T, **kw)),
+            ("rnampnn_design_count (b) random reference, 0..8 mutations, cap 8, no constraints",
+             lambda: D.design_count_from_logits(logits, mask=m, counted=sets, window=(0, 8), **kw)),
+            ("rnampnn_design_count (c) compatible reference, 0..8 mutations, cap 8, hairpin pairs + GNRA + bias",
+             lambda: D.design_count_from_logits(logits, mask=m, constraints=cons, counted=sets_hp, window=(0, 8), **kw))]
+        for _, fn in variants:
+            for _ in range(warm):
+                fn()
+        torch.cuda.synchronize()
+        times = [[] for _ in variants]
+        for _ in range(rounds):
+            for v, (_, fn) in enumerate(variants):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(per_round):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                times[v].append(e0.elapsed_time(e1) * 1e3 / per_round)
+        for (name, _), t in zip(variants, times):
+            print(f"B {B} T {T} nt {int(mask.sum())} S {S} {name}: {sum(t) / len(t):.2f} us per call, rounds {min(t):.2f} .. {max(t):.2f} "
+                  f"({rounds} alternating rounds of {per_round} back-to-back calls, events, output allocation included)")
+        g = M.design_gc_from_logits(logits, mask=m, constraints=cons, gc_content=(0.4, 0.6), **kw)
+        a = D.design_count_from_logits(logits, mask=m, constraints=cons, counted=cg, window=window, cap=T, **kw)
+        print("(a) against rnampnn_design_gc, hairpins: " + ", ".join(f"{k} equal {bool((x == y).all())}" for k, x, y in
+                                                                    zip(("seqs", "seq_nll", "infeasible", "count", "miss"), a, g)))
+        for tag, out, r in (("(b)", variants[4][1](), ref), ("(c)", variants[5][1](), ref_hp)):
+            dist = ((out[0].cpu() != r[None]) & (out[0].cpu() >= 0)).sum(-1)
+            print(f"{tag} mutations of the draws {int(out[3].min())} .. {int(out[3].max())} (Hamming distance equal {bool((dist == out[3].cpu()).all())}), "
+                  f"mut_miss total {int(out[4].sum())}, mean NLL per nt {float(out[1].sum()) / (S * int(mask.sum())):.4f}")
     if what == "distinct":
         for S in (8, 64):                                           # (timed() prints the global S)
             for mode in ("sample", "best"):
