@@ -11,26 +11,27 @@
 // candidate range max(0, k - deg_R) .. min(k, deg_L) is the same for capped and uncapped child degrees (min(k, min(D, cap)) = min(k, D),
 // max(0, k - min(D, cap)) = max(0, k - D) as k - cap <= 0), so every sum runs over the same terms in the same order: the bytes do not
 // depend on the cap.  rnampnn_design_gc passes cap = T, which bounds nothing.
-// One 256-thread workgroup per (RNA, sample) as in design.hip, the extent / NLL / reduction of score_dev.h, the masks, the pair cells and
-// the selection rule of a leaf of design_dev.h.  Three phases separated by barriers: (A) the tree bottom-up into dynamic LDS - level 1 one
-// node per thread straight from the rows (level 0 is never stored), the levels above dealt flat over (node, coefficient); with SETS the
+// One 256-thread workgroup per (RNA, sample) as in design.hip, the extent / NLL / reduction of score_dev.h; of design_dev.h the mask, the
+// fp64 row, the validated partner and the pair cells of a leaf, the logsumexp of its polynomial, the selection rule of its draw, the scratch
+// and phase C - nothing about a position under the constraints is defined here.
+// Three phases separated by barriers: (A) the tree bottom-up into dynamic LDS - level 1 one node per thread straight from the rows (level 0 is never stored), the levels above dealt flat over (node, coefficient); with SETS the
 // smallest reachable count k_min (the sum over the leaves of the smallest d with a finite p_t(d)) is reduced over the workgroup here; (B) the
 // walk down, one node per thread and level (one WAVE per node, with a wave-wide scan over the candidates, where a level has at most four
 // nodes, and for the total): a node's count is parked in slot 0 of its own coefficients, which nobody reads once its parent has split;
 // the last step recomputes the two leaves of a level-1 node, splits and draws them into `sq` (one byte per position, the owner of a pair
 // writes both ends); when no count of 0 .. min(n, cap) is reachable (SETS only) the walk is skipped and every leaf draws at its own
-// minimum; (C) the rows, the NLL and the counts as k_design writes and reduces them.  No workspace, no atomics, no runtime fill / copy
-// node, no host synchronisation; the draw is a pure function of (seed, s, b) and the rows of the RNA.
+// minimum; (C) the rows, the NLL and the counts as k_design writes and reduces them (ds_write_rows, the count as its third sum).
+// No workspace, no atomics, no runtime fill / copy node, no host synchronisation; the draw is a pure function of (seed, s, b) and the rows of the RNA.
 #pragma once
 #include "design_dev.h"
 
 namespace {
 constexpr unsigned long long CT_SALT = RNAMPNN_DESIGN_GC_SALT;
 constexpr int CT_MAX_LEVELS = 16;
-constexpr size_t CT_LDS_MAX = 160 * 1024;
-// the reduction's 48 bytes (k_min borrows its SC_WAVES ints), at 48 the flag "every leaf at its minimum", at 64 the three coefficients of
-// the only leaf of a 1-mer
+// the reduction's DS_SCRATCH = 48 bytes (k_min borrows its SC_WAVES ints), at 48 the flag "every leaf at its minimum", at 64 the three
+// coefficients of the only leaf of a 1-mer
 constexpr size_t CT_LDS_SCRATCH = 96;
+static_assert(DS_SCRATCH == 48, "the layout of the count tree's scratch");
 
 struct CtArgs : DesignArgs {
     const uint8_t* counted;      // (B,T); null with SETS = false
@@ -66,39 +67,6 @@ __device__ __forceinline__ bool ct_finite(double x) { return fabs(x) < INFINITY;
 // the smallest d with a finite coefficient, 0 for a leaf with none
 __device__ __forceinline__ int ct_min_d(double p0, double p1, double p2) { return ct_finite(p0) ? 0 : ct_finite(p1) ? 1 : ct_finite(p2) ? 2 : 0; }
 
-__device__ __forceinline__ int ct_mask(const CtArgs& a, size_t pad0, int t, bool& empty) {
-    const int m = a.allowed ? (a.allowed[pad0 + t] & 15) : 15;
-    empty = m == 0;
-    return empty ? 15 : m;
-}
-
-__device__ __forceinline__ CtPos ct_load(const CtArgs& a, size_t pad0, long long row0, int t, bool& empty) {
-    const float4 x = a.logits[row0 + t];
-    float4 bi = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a.bias) bi = a.bias_per_position ? reinterpret_cast<const float4*>(a.bias)[pad0 + t] : make_float4(a.bias[0], a.bias[1], a.bias[2], a.bias[3]);
-    const double temp = (double)a.temperature;
-    CtPos p;
-    p.z[0] = ((double)x.x + (double)bi.x) / temp; p.z[1] = ((double)x.y + (double)bi.y) / temp;
-    p.z[2] = ((double)x.z + (double)bi.z) / temp; p.z[3] = ((double)x.w + (double)bi.w) / temp;
-    p.m = ct_mask(a, pad0, t, empty);
-    return p;
-}
-
-// logsumexp of z over the cells m admits: max + log(sum of exp(z - max)) in cell order, -inf when no cell is above -inf
-template <int N>
-__device__ __forceinline__ double ct_lse(const double (&z)[N], int m) {
-    double mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < N; ++c)
-        if ((m >> c) & 1) mx = fmax(mx, z[c]);
-    if (!(mx > -INFINITY)) return -INFINITY;
-    double sum = 0.0;
-#pragma unroll
-    for (int c = 0; c < N; ++c)
-        if ((m >> c) & 1) sum += exp(z[c] - mx);
-    return mx + log(sum);
-}
-
 // Leaf t: what it is and its polynomial (p0, p1, p2).  `bad` counts as k_design counts: an empty mask 1, each end of a pair without an
 // admitted compatible cell 1.  Every index is checked before it is used.
 template <bool SETS>
@@ -106,37 +74,29 @@ __device__ __forceinline__ CtLeaf ct_leaf(const CtArgs& a, size_t pad0, long lon
                                           int& bad) {
     CtLeaf lf;
     bool empty, empty_j;
-    lf.p = ct_load(a, pad0, row0, t, empty);
+    lf.p = ds_load<double>(a, pad0, row0, t, empty);
     bad += empty ? 1 : 0;
-    int j = a.partner ? a.partner[pad0 + t] : -1;
-    if (j < 0 || j >= n || j == t || a.partner[pad0 + j] != t) j = -1;
+    const int j = ds_partner(a, pad0, n, t);
     lf.j = j; lf.kind = 0; lf.m16 = 0;
     lf.ci = lf.cj = ct_counted<SETS>(a, pad0, t);
     lf.pj = lf.p;
     if (j >= 0) {
-        const int mj = ct_mask(a, pad0, j, empty_j);
-        const int mlo = t < j ? lf.p.m : mj, mhi = t < j ? mj : lf.p.m;
-        int m = 0;
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            const int ca = c >> 2, cb = c & 3;
-            const bool ok = ((mlo >> ca) & 1) && ((mhi >> cb) & 1) && ((ds_compat(ca, a.wobble) >> cb) & 1);
-            m |= (ok ? 1 : 0) << c;
-        }
+        const int mj = ds_mask(a, pad0, j, empty_j);
+        const int m = ds_pair_mask(t < j ? lf.p.m : mj, t < j ? mj : lf.p.m, a.wobble);
         if (!m) bad += 1;
         else { lf.kind = t < j ? 1 : 2; lf.m16 = m; }
     }
     if (lf.kind == 2) { p0 = 0.0; p1 = -INFINITY; p2 = -INFINITY; return lf; }
     if (lf.kind == 0) {
-        p0 = ct_lse(lf.p.z, lf.p.m & ct_classes(lf.ci, 0)); p1 = ct_lse(lf.p.z, lf.p.m & ct_classes(lf.ci, 1)); p2 = -INFINITY;
+        p0 = ds_lse(lf.p.z, lf.p.m & ct_classes(lf.ci, 0)); p1 = ds_lse(lf.p.z, lf.p.m & ct_classes(lf.ci, 1)); p2 = -INFINITY;
         return lf;
     }
-    lf.pj = ct_load(a, pad0, row0, j, empty_j);
+    lf.pj = ds_load<double>(a, pad0, row0, j, empty_j);
     lf.cj = ct_counted<SETS>(a, pad0, j);
     double z[16];
 #pragma unroll
     for (int c = 0; c < 16; ++c) z[c] = lf.p.z[c >> 2] + lf.pj.z[c & 3];
-    // ct_lse over the cells that count 0, 1 and 2, in ONE pass over the 16 cells: per d the maximum, then the sum of exp(z - that maximum)
+    // ds_lse over the cells that count 0, 1 and 2, in ONE pass over the 16 cells: per d the maximum, then the sum of exp(z - that maximum)
     // in cell order - the same operations on the same operands, a third of the exps
     double mx[3] = {-INFINITY, -INFINITY, -INFINITY}, sum[3] = {0.0, 0.0, 0.0};
 #pragma unroll
@@ -246,8 +206,8 @@ template <bool SETS>
 __device__ __forceinline__ void ct_design(const CtArgs& a, unsigned char* lds) {
     double* tree = reinterpret_cast<double*>(lds);
     int8_t* sq = reinterpret_cast<int8_t*>(lds + a.lds_tree);                               // (T)
-    int* s_i = reinterpret_cast<int*>(lds + a.lds_tree + a.lds_sq);                         // SC_WAVES ints
-    float (*s_f)[SC_WAVES] = reinterpret_cast<float (*)[SC_WAVES]>(s_i + SC_WAVES);            // 2 x SC_WAVES floats
+    const DsScratch sc = ds_scratch(lds + a.lds_tree + a.lds_sq);
+    int* const s_i = sc.s_i;
     int* s_min = reinterpret_cast<int*>(lds + a.lds_tree + a.lds_sq + 48);                  // 1: every leaf draws at its own minimum
     double* s_leaf = reinterpret_cast<double*>(lds + a.lds_tree + a.lds_sq + 64);           // 3 doubles
     const int b = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, T = a.T, cap = a.cap;
@@ -255,7 +215,7 @@ __device__ __forceinline__ void ct_design(const CtArgs& a, unsigned char* lds) {
     const unsigned long long salted = seed ^ CT_SALT;
     int n;
     long long row0;
-    sc_extent(a, b, tid, s_f[0], n, row0);
+    sc_extent(a, b, tid, sc.s_f[0], n, row0);
     const size_t pad0 = (size_t)b * T;
     const int Ln = n > 1 ? 32 - __clz(n - 1) : 0;                  // the root is node (Ln, 0)
     int bad = 0, kmin = 0;
@@ -393,22 +353,11 @@ __device__ __forceinline__ void ct_design(const CtArgs& a, unsigned char* lds) {
         ct_leaf_draw(lr, t + 1, k - c, ds_u24(seed, s, b, t + 1), sq);
     }
     __syncthreads();
-    // ---- C: the rows, the NLL and the counts, as k_design walks and reduces them
-    int8_t* seq = a.seqs ? a.seqs + ((size_t)s * a.B + b) * T : nullptr;
-    float nll = 0.f, cnt = 0.f;
-    for (int t = tid; t < n; t += SC_THREADS) {
-        const int q = sq[t] & 3;
-        if (seq) seq[t] = (int8_t)q;
-        if (a.seq_nll) nll += sc_row_nll(a.logits[row0 + t], q);
-        cnt += ((ct_counted<SETS>(a, pad0, t) >> q) & 1) ? 1.f : 0.f;   // (whole numbers below 2^24: the float sum is exact)
-    }
-    if (seq)
-        for (int t = n + tid; t < T; t += SC_THREADS) seq[t] = (int8_t)-1;
-    sc_block_sums(bad, nll, cnt, tid, s_i, s_f);
-    if (tid != 0) return;
-    if (a.seq_nll) a.seq_nll[(size_t)s * a.B + b] = nll;
-    if (a.count) a.count[(size_t)s * a.B + b] = (int)cnt;
-    if (a.infeasible && s == 0) a.infeasible[b] = bad;
+    // ---- C: the rows, the NLL and the counts, as k_design walks and reduces them; the count rides as the third sum
+    const float cnt = ds_write_rows(a, s, b, n, row0, tid, bad, sc, [&](int t) { return sq[t] & 3; }, [&](int t, int q) {
+        return ((ct_counted<SETS>(a, pad0, t) >> q) & 1) ? 1.f : 0.f;  // (whole numbers below 2^24: the float sum is exact)
+    });
+    if (tid == 0 && a.count) a.count[(size_t)s * a.B + b] = (int)cnt;
 }
 
 // doubles of the levels 1..ceil(log2 T): node (l, i) holds min(2 * its extent within T, T, cap) + 1; base[l] (when given) = first double
@@ -431,7 +380,7 @@ inline size_t ct_lds_bytes(int T, int cap, size_t& tree, size_t& sq) {
 inline int ct_max_T(int cap) {
     int T = 1;
     size_t tree, sq;
-    while (ct_lds_bytes(T + 1, std::min(cap, T + 1), tree, sq) <= CT_LDS_MAX) ++T;
+    while (ct_lds_bytes(T + 1, std::min(cap, T + 1), tree, sq) <= DS_LDS_MAX) ++T;
     return T;
 }
 }  // namespace

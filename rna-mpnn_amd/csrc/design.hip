@@ -3,8 +3,9 @@
 // pair of the target secondary structure are drawn TOGETHER, from the joint distribution over the compatible cells AU UA CG GC [+ GU UG])
 // and `bias` (added to the logits, global or per position).  The reference has no sampler; the contract is the one include/rnampnn_hip.h
 // documents and tests/_design_ref.py restates in float64.
-// The draw rule (weights, selection, the pair's joint cell) is design_dev.h's, instantiated in f32; k_design_tied instantiates the same
-// templates in fp64.  One 256-thread workgroup per (RNA, sample) as in score.hip, the same extent (sc_extent), the same walk over the rows,
+// The mask, the row, the validated partner and the draw rule (weights, selection, the pair's joint cell) are design_dev.h's, instantiated
+// in f32; the other four design kernels instantiate the same templates in fp64.  The draw is fused into the walk over the rows, so the
+// walk is written out here and not taken from ds_write_rows, which serves the kernels that draw into LDS first.  One 256-thread workgroup per (RNA, sample) as in score.hip, the same extent (sc_extent), the same walk over the rows,
 // the same per-row NLL and the same reduction (score_dev.h), so `seq_nll` is byte for byte what rnampnn_score returns for the draws.  Both
 // ends of a pair compute the pair's cell on their own (the partner's row is one more 16-byte load) and each writes its own component: no
 // exchange between threads, so a pair may span waves or 256-strides.  No workspace, no runtime fill / copy node, no atomics, no host
@@ -13,20 +14,6 @@
 
 namespace {
 using DsPosF = DsPos<float>;
-
-// row t of RNA b.  A mask that admits no class is drawn as free; `empty` tells the caller to count it.
-__device__ __forceinline__ DsPosF ds_load(const DesignArgs& a, size_t pad0, long long row0, int t, float4& x, bool& empty) {
-    x = a.logits[row0 + t];
-    float4 bi = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a.bias) bi = a.bias_per_position ? reinterpret_cast<const float4*>(a.bias)[pad0 + t] : make_float4(a.bias[0], a.bias[1], a.bias[2], a.bias[3]);
-    DsPosF p;
-    p.z[0] = (x.x + bi.x) / a.temperature; p.z[1] = (x.y + bi.y) / a.temperature;
-    p.z[2] = (x.z + bi.z) / a.temperature; p.z[3] = (x.w + bi.w) / a.temperature;
-    const int m = a.allowed ? (a.allowed[pad0 + t] & 15) : 15;
-    empty = m == 0;
-    p.m = empty ? 15 : m;
-    return p;
-}
 
 __global__ void __launch_bounds__(SC_THREADS) k_design(DesignArgs a) {
     __shared__ int s_i[SC_WAVES];
@@ -41,16 +28,14 @@ __global__ void __launch_bounds__(SC_THREADS) k_design(DesignArgs a) {
     int bad = 0;
     float nll = 0.f, unused = 0.f;
     for (int t = tid; t < n; t += SC_THREADS) {
-        float4 x, xj;
+        float4 x;
         bool empty, empty_j;
-        const DsPosF p = ds_load(a, pad0, row0, t, x, empty);
+        const DsPosF p = ds_load<float>(a, pad0, row0, t, x, empty);
         bad += empty ? 1 : 0;
-        // paired only when the table is symmetric and stays inside the RNA: every index is checked before it is used
-        int j = a.partner ? a.partner[pad0 + t] : -1;
-        if (j < 0 || j >= n || j == t || a.partner[pad0 + j] != t) j = -1;
+        const int j = ds_partner(a, pad0, n, t);
         int q = -1;
         if (j >= 0) {
-            const DsPosF pj = ds_load(a, pad0, row0, j, xj, empty_j);
+            const DsPosF pj = ds_load<float>(a, pad0, row0, j, empty_j);
             const bool first = t < j;
             const int cell = ds_draw_pair(first ? p : pj, first ? pj : p, a.wobble, ds_u24(seed, s, b, first ? t : j));
             if (cell >= 0) q = first ? (cell >> 2) : (cell & 3);
@@ -74,11 +59,10 @@ extern "C" int rnampnn_design(const float* logits, int64_t n_rows, const float* 
                               const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position, int8_t* seqs,
                               float* seq_nll, int32_t* infeasible, void* stream) {
     DesignArgs a{};
-    const ScDraw draw{S, "RNA", temperature, bias, bias_per_position};
-    const int rc = sc_check_args("rnampnn_design", logits, n_rows, mask, cu_seqlens, B, T, &draw, a, [](int) { return RNAMPNN_OK; });
+    const int rc = ds_prepare("rnampnn_design", "RNA", logits, n_rows, mask, cu_seqlens, B, T, temperature, S, seed, seed_dev, allowed, partner,
+                              wobble, bias, bias_per_position, seqs, seq_nll, infeasible, a, [](int) { return RNAMPNN_OK; });
     if (rc != RNAMPNN_OK) return rc;
     if (!seqs && !seq_nll && !infeasible) return RNAMPNN_OK;    // nothing asked for
-    ds_fill(a, seed, seed_dev, allowed, partner, wobble, bias, bias_per_position, temperature, seqs, seq_nll, infeasible);
     const int passes = (seqs || seq_nll) ? S : 1;               // the count of infeasible positions is that of sample 0
     hipLaunchKernelGGL(k_design, dim3(B, passes), dim3(SC_THREADS), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());

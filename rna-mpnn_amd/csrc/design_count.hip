@@ -30,8 +30,8 @@ extern "C" int rnampnn_design_count(const float* logits, int64_t n_rows, const f
                                     const uint8_t* counted, const int32_t* count_lo, const int32_t* count_hi, int32_t count_cap,
                                     int8_t* seqs, float* seq_nll, int32_t* infeasible, int32_t* count, int32_t* count_miss, void* stream) {
     CtArgs a{};
-    const ScDraw draw{S, "RNA", temperature, bias, bias_per_position};
-    const int rc = sc_check_args("rnampnn_design_count", logits, n_rows, mask, cu_seqlens, B, T, &draw, a, [&](int slot) {
+    const int rc = ds_prepare("rnampnn_design_count", "RNA", logits, n_rows, mask, cu_seqlens, B, T, temperature, S, seed, seed_dev, allowed,
+                              partner, wobble, bias, bias_per_position, seqs, seq_nll, infeasible, a, [&](int slot) {
         if (slot == 0 && (!counted || !count_lo || !count_hi))
             return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_count: null counted, count_lo or count_hi");
         if (slot == 0 && count_cap < 0) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_count: count_cap = %d is negative", (int)count_cap);
@@ -42,11 +42,10 @@ extern "C" int rnampnn_design_count(const float* logits, int64_t n_rows, const f
     const int cap = std::min<int>(count_cap, T);                   // no node counts more than its positions
     size_t lds_tree = 0, lds_sq = 0;
     const size_t lds = ct_lds_bytes(T, cap, lds_tree, lds_sq);
-    if (lds > CT_LDS_MAX)
+    if (lds > DS_LDS_MAX)
         return fail(RNAMPNN_ERR_UNSUPPORTED,
                     "rnampnn_design_count: T = %d at count_cap = %d needs %zu bytes of LDS for the count tree, the limit is %zu (T <= %d at that cap)",
-                    (int)T, (int)count_cap, lds, CT_LDS_MAX, ct_max_T(count_cap));
-    ds_fill(a, seed, seed_dev, allowed, partner, wobble, bias, bias_per_position, temperature, seqs, seq_nll, infeasible);
+                    (int)T, (int)count_cap, lds, DS_LDS_MAX, ct_max_T(count_cap));
     a.counted = counted; a.lo = count_lo; a.hi = count_hi; a.count = count; a.miss = count_miss; a.cap = cap;
     ct_tree_doubles(T, cap, a.base);
     a.lds_tree = (unsigned)lds_tree; a.lds_sq = (unsigned)lds_sq;

@@ -3,15 +3,15 @@
 // units (unpaired positions, feasible base pairs), so a beam of width S over the units with conditioned Gumbel keys (Kool et al. 2019,
 // "Stochastic Beams and Where to Find Them") is exact in both readings.  The contract is the one include/rnampnn_hip.h documents and
 // tests/_design_distinct_ref.py restates; all of the draw is fp64.
-// One 256-thread workgroup per RNA (the samples of an RNA interact), the extent / NLL / reduction of score_dev.h, the masks, the pair
-// cells and the argument checks of design_dev.h.  (A) the walk over the units, 128 positions at a time: one thread per position forms the
-// unit's cells and their l = z - LSE into LDS, then per unit: one thread per candidate (slot, cell) forms its key, one thread per
+// One 256-thread workgroup per RNA (the samples of an RNA interact), the extent / NLL / reduction of score_dev.h; of design_dev.h the
+// mask, the fp64 row, the validated partner and the pair cells of a unit, the logsumexp of its cells, the scratch, phase C per slot and
+// the entry's prologue - the pieces the count tree uses, so a unit here is a leaf there.
+// (A) the walk over the units, 128 positions at a time: one thread per position forms the unit's cells and their l = z - LSE into LDS, then per unit: one thread per candidate (slot, cell) forms its key, one thread per
 // candidate counts the candidates that order before it (its rank; a rank below S is a survivor), one thread per survivor writes the new
 // slot state and its back-pointer into the history (12 bits: the parent slot in a byte, the cell's index and a pair flag in half a
 // byte).  (B) the walk back: one thread per slot follows its back-pointers and leaves the class of every position in the history's rows,
-// all slots in step.  (C) per filled slot the rows, the NLL and the counts as k_design writes and reduces them.  No workspace, no atomics,
-// no runtime fill / copy node, no host synchronisation.  (The fp64 row load and the logsumexp are k_design_gc's, restated: they live in
-// that unit, which this one leaves as it is.)
+// all slots in step.  (C) per filled slot the rows, the NLL and the counts as k_design writes and reduces them (ds_write_rows).  No
+// workspace, no atomics, no runtime fill / copy node, no host synchronisation.
 #include "design_dev.h"
 
 namespace {
@@ -19,8 +19,8 @@ constexpr unsigned long long DD_SALT = RNAMPNN_DESIGN_DISTINCT_SALT;
 constexpr int DD_MAX_S = RNAMPNN_DESIGN_DISTINCT_MAX_S;
 constexpr int DD_CELLS = 6;                    // a position admits at most 4 classes, a pair at most 6 compatible cells
 constexpr int DD_CHUNK = 128;                  // positions whose units are formed together
-constexpr size_t DD_LDS_MAX = 160 * 1024;
-constexpr size_t DD_LDS_SCRATCH = 96;          // the reduction's 48 bytes, padded
+constexpr size_t DD_LDS_SCRATCH = 96;          // the reduction's DS_SCRATCH bytes, padded
+static_assert(DS_SCRATCH <= DD_LDS_SCRATCH, "the reduction's scratch");
 constexpr unsigned DD_SKIP = 0xFFu;            // history: the first byte of the 4-bit row of a position that is no unit (an upper end)
 
 struct DdArgs : DesignArgs {
@@ -31,43 +31,10 @@ struct DdArgs : DesignArgs {
 
 using DdPos = DsPos<double>;
 
-// row t in fp64 as k_design_gc loads it: z = ((double) logit + (double) bias) / (double) temperature; an empty mask is free and counted
-__device__ __forceinline__ int dd_mask(const DdArgs& a, size_t pad0, int t, bool& empty) {
-    const int m = a.allowed ? (a.allowed[pad0 + t] & 15) : 15;
-    empty = m == 0;
-    return empty ? 15 : m;
-}
-__device__ __forceinline__ DdPos dd_load(const DdArgs& a, size_t pad0, long long row0, int t, bool& empty) {
-    const float4 x = a.logits[row0 + t];
-    float4 bi = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a.bias) bi = a.bias_per_position ? reinterpret_cast<const float4*>(a.bias)[pad0 + t] : make_float4(a.bias[0], a.bias[1], a.bias[2], a.bias[3]);
-    const double temp = (double)a.temperature;
-    DdPos p;
-    p.z[0] = ((double)x.x + (double)bi.x) / temp; p.z[1] = ((double)x.y + (double)bi.y) / temp;
-    p.z[2] = ((double)x.z + (double)bi.z) / temp; p.z[3] = ((double)x.w + (double)bi.w) / temp;
-    p.m = dd_mask(a, pad0, t, empty);
-    return p;
-}
-
-// k_design_gc's logsumexp of z over the cells m admits: max + log(sum of exp(z - max)) in cell order, -inf when no cell is above -inf
-template <int N>
-__device__ __forceinline__ double dd_lse(const double (&z)[N], int m) {
-    double mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < N; ++c)
-        if ((m >> c) & 1) mx = fmax(mx, z[c]);
-    if (!(mx > -INFINITY)) return -INFINITY;
-    double sum = 0.0;
-#pragma unroll
-    for (int c = 0; c < N; ++c)
-        if ((m >> c) & 1) sum += exp(z[c] - mx);
-    return mx + log(sum);
-}
-
 // the cells m admits, in order, with l = z - LSE -> the unit's word: bits 0..2 the number of cells, bit 3 a pair, bits 4 + 4 k.. cell k
 template <int N>
 __device__ __forceinline__ unsigned dd_cells(const double (&z)[N], int m, unsigned pair, double* ell) {
-    const double lse = dd_lse(z, m);
+    const double lse = ds_lse(z, m);
     unsigned w = pair << 3;
     int k = 0;
 #pragma unroll
@@ -80,33 +47,20 @@ __device__ __forceinline__ unsigned dd_cells(const double (&z)[N], int m, unsign
     return w | (unsigned)k;
 }
 
-// the compatible cells (a, b) = 4 a + b that the masks of a pair's lower and upper end admit
-__device__ __forceinline__ int dd_pair_mask(int mlo, int mhi, int wobble) {
-    int m = 0;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        const int ca = c >> 2, cb = c & 3;
-        const bool ok = ((mlo >> ca) & 1) && ((mhi >> cb) & 1) && ((ds_compat(ca, wobble) >> cb) & 1);
-        m |= (ok ? 1 : 0) << c;
-    }
-    return m;
-}
-
 // Position t as a unit: 0 for the upper end of a feasible pair, else its word and the l of its cells.  `bad` counts as k_design counts: an
 // empty mask 1, each end of a pair without an admitted compatible cell 1.  Every index is checked before it is used.
 __device__ __forceinline__ unsigned dd_unit(const DdArgs& a, size_t pad0, long long row0, int n, int t, double* ell, int& bad) {
     bool empty, empty_j;
-    const DdPos p = dd_load(a, pad0, row0, t, empty);
+    const DdPos p = ds_load<double>(a, pad0, row0, t, empty);
     bad += empty ? 1 : 0;
-    int j = a.partner ? a.partner[pad0 + t] : -1;
-    if (j < 0 || j >= n || j == t || a.partner[pad0 + j] != t) j = -1;
+    const int j = ds_partner(a, pad0, n, t);
     if (j >= 0) {
-        const int mj = dd_mask(a, pad0, j, empty_j);
-        const int m = t < j ? dd_pair_mask(p.m, mj, a.wobble) : dd_pair_mask(mj, p.m, a.wobble);
+        const int mj = ds_mask(a, pad0, j, empty_j);
+        const int m = t < j ? ds_pair_mask(p.m, mj, a.wobble) : ds_pair_mask(mj, p.m, a.wobble);
         if (!m) bad += 1;
         else if (t > j) return 0u;
         else {
-            const DdPos pj = dd_load(a, pad0, row0, j, empty_j);
+            const DdPos pj = ds_load<double>(a, pad0, row0, j, empty_j);
             double z[16];
 #pragma unroll
             for (int c = 0; c < 16; ++c) z[c] = p.z[c >> 2] + pj.z[c & 3];
@@ -156,15 +110,15 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_distinct(DdArgs a) {
     double* key = gk + DD_CELLS * S;                                               // [6 S]    its key
     double* ell = key + DD_CELLS * S;                                              // [128][6] l of the cells of a chunk's units
     unsigned* unit = reinterpret_cast<unsigned*>(ell + DD_CHUNK * DD_CELLS);       // [128]    their words
-    int* s_i = reinterpret_cast<int*>(unit + DD_CHUNK);                            // SC_WAVES ints
-    float (*s_f)[SC_WAVES] = reinterpret_cast<float (*)[SC_WAVES]>(s_i + SC_WAVES);            // 2 x SC_WAVES floats
-    unsigned short* sel = reinterpret_cast<unsigned short*>(reinterpret_cast<unsigned char*>(s_i) + DD_LDS_SCRATCH);   // [S], padded to 8
+    unsigned char* red = reinterpret_cast<unsigned char*>(unit + DD_CHUNK);        // the reduction's scratch
+    const DsScratch sc = ds_scratch(red);
+    unsigned short* sel = reinterpret_cast<unsigned short*>(red + DD_LDS_SCRATCH);  // [S], padded to 8
     unsigned char* hp = reinterpret_cast<unsigned char*>(sel + ((S + 7) & ~7));    // [T][S]   history: the parent slot, then the class
     unsigned char* hn = hp + (size_t)T * S;                                        // [T][NS]  history: the cell's index and the pair flag, 4 bits
     const unsigned long long seed = a.seed_dev ? *a.seed_dev : a.seed;
     int n;
     long long row0;
-    sc_extent(a, b, tid, s_f[0], n, row0);
+    sc_extent(a, b, tid, sc.s_f[0], n, row0);
     const size_t pad0 = (size_t)b * T;
     if (tid == 0) {
         phi[0] = 0.0; gum[0] = 0.0;
@@ -255,11 +209,11 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_distinct(DdArgs a) {
         const unsigned n0 = hn[t * NS];                             // (slot 0 is always filled; one address: the branches below are uniform)
         if ((n0 & 15) == DD_SKIP >> 4) continue;
         bool empty;
-        int cells = dd_mask(a, pad0, t, empty), j = -1;             // the unit's cells again: integers only
+        int cells = ds_mask(a, pad0, t, empty), j = -1;             // the unit's cells again: integers only
         if (n0 & 8) {
             j = a.partner[pad0 + t];                                // the partner the walk forward validated, checked again before use
             if (j <= t || j >= n) j = -1;
-            else cells = dd_pair_mask(cells, dd_mask(a, pad0, j, empty), a.wobble);
+            else cells = ds_pair_mask(cells, ds_mask(a, pad0, j, empty), a.wobble);
         }
         int k = 0, up = 0;
         if (tid < live) {
@@ -281,27 +235,13 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_distinct(DdArgs a) {
     __syncthreads();
     // ---- C: the rows, the NLL and the counts of every slot, as k_design walks and reduces them
     for (int s = 0; s < S; ++s) {
-        int8_t* seq = a.seqs ? a.seqs + ((size_t)s * a.B + b) * T : nullptr;
         if (s >= live) {
-            if (seq)
-                for (int t = tid; t < T; t += SC_THREADS) seq[t] = (int8_t)-1;
+            if (a.seqs)
+                for (int t = tid; t < T; t += SC_THREADS) a.seqs[((size_t)s * a.B + b) * T + t] = (int8_t)-1;
             continue;
         }
-        float nll = 0.f, unused = 0.f;
-        int cnt = s == 0 ? bad : 0;
-        for (int t = tid; t < n; t += SC_THREADS) {
-            const int q = hp[t * S + s] & 3;
-            if (seq) seq[t] = (int8_t)q;
-            if (a.seq_nll) nll += sc_row_nll(a.logits[row0 + t], q);
-        }
-        if (seq)
-            for (int t = n + tid; t < T; t += SC_THREADS) seq[t] = (int8_t)-1;
-        sc_block_sums(cnt, nll, unused, tid, s_i, s_f);
-        if (tid == 0) {
-            if (a.seq_nll) a.seq_nll[(size_t)s * a.B + b] = nll;
-            if (a.infeasible && s == 0) a.infeasible[b] = cnt;
-        }
-        __syncthreads();                                            // s_i / s_f are written again by the next slot
+        ds_write_rows(a, s, b, n, row0, tid, s == 0 ? bad : 0, sc, [&](int t) { return hp[t * S + s] & 3; }, DsNoSum{});
+        __syncthreads();                                            // the scratch is written again by the next slot
     }
     if (tid < S) {
         const size_t o = (size_t)tid * a.B + b;
@@ -319,9 +259,9 @@ size_t dd_lds_bytes(long long S, long long T) {
 }
 long long dd_max_T(long long S) {
     const size_t fixed = dd_lds_bytes(S, 0);
-    if (fixed >= DD_LDS_MAX) return 0;
-    long long T = (long long)((DD_LDS_MAX - fixed) / (size_t)(S + (S + 1) / 2));
-    while (T > 0 && dd_lds_bytes(S, T) > DD_LDS_MAX) --T;           // (the history is rounded up to 16 bytes)
+    if (fixed >= DS_LDS_MAX) return 0;
+    long long T = (long long)((DS_LDS_MAX - fixed) / (size_t)(S + (S + 1) / 2));
+    while (T > 0 && dd_lds_bytes(S, T) > DS_LDS_MAX) --T;           // (the history is rounded up to 16 bytes)
     return T;
 }
 }  // namespace
@@ -331,19 +271,18 @@ extern "C" int rnampnn_design_distinct(const float* logits, int64_t n_rows, cons
                                        const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position, int32_t noise,
                                        int8_t* seqs, float* seq_nll, int32_t* infeasible, float* logp, int32_t* n_distinct, void* stream) {
     DdArgs a{};
-    const ScDraw draw{S, "RNA", temperature, bias, bias_per_position};
-    const int rc = sc_check_args("rnampnn_design_distinct", logits, n_rows, mask, cu_seqlens, B, T, &draw, a, [&](int slot) {
+    const int rc = ds_prepare("rnampnn_design_distinct", "RNA", logits, n_rows, mask, cu_seqlens, B, T, temperature, S, seed, seed_dev, allowed,
+                              partner, wobble, bias, bias_per_position, seqs, seq_nll, infeasible, a, [&](int slot) {
         if (slot == 0 && S > DD_MAX_S)
             return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_distinct: S = %d, at most %d distinct sequences per RNA", (int)S, DD_MAX_S);
         return RNAMPNN_OK;
     });
     if (rc != RNAMPNN_OK) return rc;
     const size_t lds = dd_lds_bytes(S, T);
-    if (lds > DD_LDS_MAX)
+    if (lds > DS_LDS_MAX)
         return fail(RNAMPNN_ERR_UNSUPPORTED, "rnampnn_design_distinct: S = %d, T = %d needs %zu bytes of LDS for the beam's history, the limit is %zu "
-                    "(T <= %lld at this S)", (int)S, (int)T, lds, DD_LDS_MAX, dd_max_T(S));
+                    "(T <= %lld at this S)", (int)S, (int)T, lds, DS_LDS_MAX, dd_max_T(S));
     if (!seqs && !seq_nll && !infeasible && !logp && !n_distinct) return RNAMPNN_OK;    // nothing asked for
-    ds_fill(a, seed, seed_dev, allowed, partner, wobble, bias, bias_per_position, temperature, seqs, seq_nll, infeasible);
     a.S = S; a.noise = noise ? 1 : 0; a.logp = logp; a.n_distinct = n_distinct;
     static DevAttr attr;
     ensure_dyn_lds((const void*)k_design_distinct, lds, attr);

@@ -18,8 +18,8 @@ extern "C" int rnampnn_design_gc(const float* logits, int64_t n_rows, const floa
                                  const int32_t* gc_lo, const int32_t* gc_hi, int8_t* seqs, float* seq_nll, int32_t* infeasible,
                                  int32_t* gc_count, int32_t* gc_miss, void* stream) {
     CtArgs a{};
-    const ScDraw draw{S, "RNA", temperature, bias, bias_per_position};
-    const int rc = sc_check_args("rnampnn_design_gc", logits, n_rows, mask, cu_seqlens, B, T, &draw, a, [&](int slot) {
+    const int rc = ds_prepare("rnampnn_design_gc", "RNA", logits, n_rows, mask, cu_seqlens, B, T, temperature, S, seed, seed_dev, allowed, partner,
+                              wobble, bias, bias_per_position, seqs, seq_nll, infeasible, a, [&](int slot) {
         if (slot == 0 && (!gc_lo || !gc_hi)) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_gc: null gc_lo or gc_hi");
         return RNAMPNN_OK;
     });
@@ -27,10 +27,9 @@ extern "C" int rnampnn_design_gc(const float* logits, int64_t n_rows, const floa
     if (!seqs && !seq_nll && !infeasible && !gc_count && !gc_miss) return RNAMPNN_OK;    // nothing asked for
     size_t lds_tree = 0, lds_sq = 0;
     const size_t lds = ct_lds_bytes(T, T, lds_tree, lds_sq);
-    if (lds > CT_LDS_MAX)
+    if (lds > DS_LDS_MAX)
         return fail(RNAMPNN_ERR_UNSUPPORTED, "rnampnn_design_gc: T = %d needs %zu bytes of LDS for the count tree, the limit is %zu (T <= %d)",
-                    (int)T, lds, CT_LDS_MAX, ct_max_T(T));
-    ds_fill(a, seed, seed_dev, allowed, partner, wobble, bias, bias_per_position, temperature, seqs, seq_nll, infeasible);
+                    (int)T, lds, DS_LDS_MAX, ct_max_T(T));
     a.counted = nullptr; a.lo = gc_lo; a.hi = gc_hi; a.count = gc_count; a.miss = gc_miss; a.cap = T;
     ct_tree_doubles(T, T, a.base);
     a.lds_tree = (unsigned)lds_tree; a.lds_sq = (unsigned)lds_sq;

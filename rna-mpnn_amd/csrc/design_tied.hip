@@ -195,8 +195,9 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_tied(TiedArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char td_lds[];
     double* alpha = reinterpret_cast<double*>(td_lds);                                         // (T,4), with a partner table only
     int8_t* sq = reinterpret_cast<int8_t*>(td_lds + a.lds_alpha);                              // (T)
-    int* s_i = reinterpret_cast<int*>(td_lds + a.lds_alpha + a.lds_sq);                        // SC_WAVES ints
-    float (*s_f)[SC_WAVES] = reinterpret_cast<float (*)[SC_WAVES]>(s_i + SC_WAVES);            // 2 x SC_WAVES floats
+    const DsScratch sc = ds_scratch(td_lds + a.lds_alpha + a.lds_sq);
+    int* const s_i = sc.s_i;
+    float (*const s_f)[SC_WAVES] = sc.s_f;
     const int s = blockIdx.y, tid = threadIdx.x;
     TdGroup g;
     g.b0 = min(max((int)a.group_cu[blockIdx.x], 0), a.B);
@@ -293,21 +294,20 @@ extern "C" int rnampnn_design_tied(const float* logits, int64_t n_rows, const fl
                                    const float* bias, int32_t bias_per_position, int8_t* seqs, float* seq_nll, int32_t* infeasible,
                                    void* stream) {
     TiedArgs a{};
-    const ScDraw draw{S, "group", temperature, bias, bias_per_position};
-    const int rc = sc_check_args("rnampnn_design_tied", logits, n_rows, mask, cu_seqlens, B, T, &draw, a, [&](int slot) {
+    const int rc = ds_prepare("rnampnn_design_tied", "group", logits, n_rows, mask, cu_seqlens, B, T, temperature, S, seed, seed_dev, allowed,
+                              partner, wobble, bias, bias_per_position, seqs, seq_nll, infeasible, a, [&](int slot) {
         if (slot == 0 && (!group_cu || G <= 0))
             return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_tied: null group_cu or no group (G = %d)", (int)G);
         return RNAMPNN_OK;
     });
     if (rc != RNAMPNN_OK) return rc;
     if (!seqs && !seq_nll && !infeasible) return RNAMPNN_OK;    // nothing asked for
-    // LDS by position: 32 bytes of alpha (with a partner table only) + 1 byte of class id, + the reduction's 48 bytes
-    constexpr size_t LDS_MAX = 160 * 1024;
+    // LDS by position: 32 bytes of alpha (with a partner table only) + 1 byte of class id, + the reduction's scratch, padded to 64 bytes
+    static_assert(DS_SCRATCH <= 64, "the reduction's scratch");
     const size_t lds_alpha = partner ? (size_t)T * 32 : 0, lds_sq = ((size_t)T + 15) & ~(size_t)15, lds = lds_alpha + lds_sq + 64;
-    if (lds > LDS_MAX)
+    if (lds > DS_LDS_MAX)
         return fail(RNAMPNN_ERR_UNSUPPORTED, "rnampnn_design_tied: T = %d needs %zu bytes of LDS, the limit is %zu (T <= %d with a partner table)",
-                    (int)T, lds, LDS_MAX, (int)((LDS_MAX - 64 - 15) / 33));
-    ds_fill(a, seed, seed_dev, allowed, partner, wobble, bias, bias_per_position, temperature, seqs, seq_nll, infeasible);
+                    (int)T, lds, DS_LDS_MAX, (int)((DS_LDS_MAX - 64 - 15) / 33));
     a.group_cu = group_cu; a.weight = weight;
     a.lds_alpha = (unsigned)lds_alpha; a.lds_sq = (unsigned)lds_sq;
     const int passes = (seqs || seq_nll) ? S : 1;               // the count of infeasible positions is that of sample 0

@@ -1,7 +1,8 @@
-// Pieces shared by the per-(RNA, pass) kernels on f32 logits, k_score (score.hip), k_design (design.hip) and k_design_tied
-// (design_tied.hip), and by k_rd_score (rdesign_score.hip): the argument checks of the three entries, the extent of an RNA in either
-// layout, the first-maximum argmax and the NLL of one row, and the fixed-order workgroup sums.  One definition of each, so that the
-// likelihood the design kernels write for their own draws is byte for byte the one k_score returns for them.
+// Pieces shared by the per-(RNA, pass) kernels on f32 logits - k_score (score.hip) and the five design kernels k_design, k_design_tied,
+// k_design_gc, k_design_count and k_design_distinct (through design_dev.h) - and by k_rd_score (rdesign_score.hip): the argument checks
+// of rnampnn_score and, through ds_prepare, of the five design entries, the extent of an RNA in either layout, the first-maximum argmax
+// and the NLL of one row, and the fixed-order workgroup sums.  One definition of each, so that the likelihood every design kernel writes
+// for its own draws is byte for byte the one k_score returns for them.
 #pragma once
 #include "api_internal.h"
 
@@ -18,7 +19,7 @@ struct ScRows {                  // the logits of a batch in either layout: what
 };
 struct ScDraw { int S; const char* per; float temperature; const float* bias; int bias_per_position; };   // what only a design entry checks
 
-// The argument checks rnampnn_score, rnampnn_design and rnampnn_design_tied share, in the order they fire, and the fields of ScRows.
+// The argument checks rnampnn_score and the five design entries share, in the order they fire, and the fields of ScRows.
 // `draw`: the S / temperature / bias checks of a design entry (null for rnampnn_score).  `own(slot)`: the entry's own checks that fire
 // in between - slot 0 after the batch check, slot 1 after the alignment checks; it returns what fail() returned, or RNAMPNN_OK.
 template <typename Own>

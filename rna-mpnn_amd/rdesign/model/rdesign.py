@@ -33,8 +33,9 @@ import torch.nn.functional as F
 
 from .. import _native
 from rnampnn.model._base import _prep, _stream
-from rnampnn.model.decode import (check_distinct, check_mutations, check_state_lengths, design_distinct_from_logits, design_from_logits,
-                                  design_gc_from_logits, design_mutations_from_logits, letters_packed, score_logits)
+from rnampnn.model.decode import (check_distinct, check_mutations, check_state_lengths, design_by_mode, design_distinct_from_logits,  # noqa: F401
+                                  design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits, letters_packed,
+                                  score_logits)
 
 _PREC = {"f32": _native.PREC_F32, "bf16": _native.PREC_BF16}
 _TRAIN = {"f32": _native.TRAIN_F32, "bf16": _native.TRAIN_BF16_MIXED}
@@ -445,24 +446,14 @@ class RNAModel(nn.Module):
         drawn exactly from the model's distribution conditioned on that (``design_count_from_logits``) -> (seqs, seq_nll, infeasible,
         n_mut (n_samples,B) int32, mut_miss (B,) int32 = how far the structure and the fixed positions alone push the count out of the
         budget, 0 when it is reachable); not built together with ``states``, ``gc_content`` or ``distinct``."""
-        mutations = check_mutations(mutations, states, gc_content, distinct)
-        check_distinct(distinct, states, gc_content)
-        if gc_content is not None and states is not None:
-            raise ValueError("gc_content together with states is not built: the G+C window conditions the draws of rnampnn_design only")
+        mode = design_mode(states, gc_content, distinct, mutations)
+        mutations = check_mutations(mutations)
         if states is not None and lengths is not None:
             check_state_lengths(states, lengths)
         logits, cu, T = self._packed_logits(X, mask, lengths)
-        if mutations is not None:
-            return design_mutations_from_logits(logits, mutations, cu_seqlens=cu, max_len=T, n_samples=n_samples, temperature=temperature, seed=seed,
-                                                constraints=constraints)
-        if distinct is not None:
-            return design_distinct_from_logits(logits, cu_seqlens=cu, max_len=T, n_samples=n_samples, temperature=temperature, seed=seed,
-                                               constraints=constraints, mode=distinct)
-        if gc_content is not None:
-            return design_gc_from_logits(logits, cu_seqlens=cu, max_len=T, n_samples=n_samples, temperature=temperature, seed=seed,
-                                         constraints=constraints, gc_content=gc_content)
-        return design_from_logits(logits, cu_seqlens=cu, max_len=T, n_samples=n_samples, temperature=temperature, seed=seed,
-                                  constraints=constraints, states=states, state_weights=state_weights)
+        return design_by_mode(mode, logits, cu_seqlens=cu, max_len=T, n_samples=n_samples, temperature=temperature, seed=seed,
+                              constraints=constraints, states=states, state_weights=state_weights, gc_content=gc_content, distinct=distinct,
+                              mutations=mutations)
 
     @torch.no_grad()
     def score_sequences(self, X, mask, seqs, labels=None, lengths=None):

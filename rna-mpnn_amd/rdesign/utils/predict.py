@@ -4,11 +4,10 @@ from __future__ import annotations
 import os
 from typing import List, Optional, Tuple
 
-from rnampnn.model.decode import (check_budget, check_distinct, design_distinct_from_logits, design_from_logits, design_gc_from_logits,
-                                  design_mutations_from_logits, letters_padded, score_logits)
+from rnampnn.model.decode import check_budget, design_by_mode, design_mode, letters_padded, score_logits
 from rnampnn.utils.constraints import batch_constraints, mutation_references, padded_references
 from rnampnn.utils.data import bucket_batches
-from rnampnn.utils.predict import write_csv
+from rnampnn.utils.predict import design_columns, write_csv
 
 from .data import load_rna_dir, padded_loader
 
@@ -29,11 +28,11 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     a mutation budget - the draws come from ``rnampnn_design_count`` and differ from the reference sequence of the structure
     (``references[pdb_id]``, or with None its own fasta sequence) at between min and max positions; ``designs_csv`` gains the last columns
     ``mutations`` and ``mut_miss``.  Not built together with ``gc_content`` or ``distinct``."""
+    mode = design_mode(None, gc_content, distinct, mutations)
     if mutations is not None:
-        check_budget(mutations[0], mutations[1], None, gc_content, distinct)
+        check_budget(mutations[0], mutations[1])
         if samples <= 0:
             raise ValueError("a mutation budget needs samples > 0")
-    check_distinct(distinct, None, gc_content)
     model.eval()
     items = load_rna_dir(data_path)
     if not items:
@@ -52,40 +51,21 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             lens = [int(v) for v in lengths]
             logits, cu, T = model._packed_logits(X, mask, lengths)
             cons = batch_constraints(constraints, [items[i][0] for i in idx], lens, T, bias=bias, wobble=wobble, omit=omit)
-            gcs = muts = logp = None
-            filled = [samples] * len(idx)
-            if distinct is not None:
-                draws, nll, bad, logp, filled = design_distinct_from_logits(logits, cu_seqlens=cu, max_len=T, n_samples=samples,
-                                                                            temperature=temperature, seed=seed + bi,
-                                                                            constraints=cons.to_device(device), mode=distinct)
-                logp, filled = logp.cpu().tolist(), filled.cpu().tolist()
-            elif mutations is not None:
-                draws, nll, bad, count, miss = design_mutations_from_logits(
-                    logits, (padded_references(refs, idx, T), (mutations[0], mutations[1])), cu_seqlens=cu, max_len=T, n_samples=samples,
-                    temperature=temperature, seed=seed + bi, constraints=cons.to_device(device))
-                muts = (count.cpu().tolist(), miss.cpu().tolist())
-            elif gc_content is not None:
-                draws, nll, bad, count, miss = design_gc_from_logits(logits, cu_seqlens=cu, max_len=T, n_samples=samples,
-                                                                     temperature=temperature, seed=seed + bi,
-                                                                     constraints=cons.to_device(device), gc_content=gc_content)
-                gcs = (count.cpu().tolist(), miss.cpu().tolist())
-            else:
-                draws, nll, bad = design_from_logits(logits, cu_seqlens=cu, max_len=T, n_samples=samples, temperature=temperature,
-                                                     seed=seed + bi, constraints=cons.to_device(device))
+            draws, nll, bad, *extras = design_by_mode(
+                mode, logits, cu_seqlens=cu, max_len=T, n_samples=samples, temperature=temperature, seed=seed + bi,
+                constraints=cons.to_device(device), gc_content=gc_content, distinct=distinct,
+                mutations=None if mutations is None else (padded_references(refs, idx, T), (mutations[0], mutations[1])))
+            _, cells, filled = design_columns(mode, extras, lens)
             match = score_logits(logits, cu_seqlens=cu, labels=S, seqs=draws, want=("seq_match",))["seq_match"].cpu().tolist()
             nll, bad = nll.cpu().tolist(), bad.cpu().tolist()
             for s in range(samples):
                 for r, (i, text) in enumerate(zip(idx, letters_padded(draws[s]))):
-                    if s >= filled[r]:
+                    if filled is not None and s >= filled[r]:
                         continue                                    # fewer admitted sequences than samples: the slot is empty
-                    designs.setdefault(i, []).append((s, text, f"{nll[s][r] / lens[r]:.6f}", f"{match[s][r] / lens[r]:.6f}", bad[r])
-                                                     + (() if gcs is None else (f"{gcs[0][s][r] / lens[r]:.6f}", gcs[1][r]))
-                                                     + (() if muts is None else (muts[0][s][r], muts[1][r]))
-                                                     + (() if logp is None else (f"{logp[s][r]:.6f}",)))
+                    designs.setdefault(i, []).append((s, text, f"{nll[s][r] / lens[r]:.6f}", f"{match[s][r] / lens[r]:.6f}", bad[r]) + cells(s, r))
     rows = [(items[i][0], seqs[i]) for i in range(len(items))]
     write_csv(out_csv, "pdb_id,seq", rows)
     if samples > 0:
-        write_csv(designs_csv, "pdb_id,sample,seq,nll_per_nt,recovery,infeasible" + (",gc,gc_miss" if gc_content is not None else "")
-                  + (",mutations,mut_miss" if mutations is not None else "") + (",logp" if distinct is not None else ""),
+        write_csv(designs_csv, "pdb_id,sample,seq,nll_per_nt,recovery,infeasible" + design_columns(mode)[0],
                   [(it[0],) + row for i, it in enumerate(items) for row in designs[i]])
     return rows

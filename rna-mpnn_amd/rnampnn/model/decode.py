@@ -1,7 +1,7 @@
 """Decoding from logits, as free functions over the C ABI's decode family: argmax + recovery (``rnampnn_argmax_recovery``), free draws
 (``rnampnn_sample``), scores (``rnampnn_score``), constrained and multi-state design (``rnampnn_design``, ``rnampnn_design_tied``), design
 under a G+C content window (``rnampnn_design_gc``), design within a count window / a mutation budget (``rnampnn_design_count``), distinct
-designs (``rnampnn_design_distinct``) and the letters of class ids.  Needs the library and ``_base`` only, so both model packages import
+designs (``rnampnn_design_distinct``), the choice between them (``design_mode``, ``design_by_mode``) and the letters of class ids.  Needs the library and ``_base`` only, so both model packages import
 it at module level."""
 from __future__ import annotations
 
@@ -81,6 +81,43 @@ def check_state_lengths(states, lengths) -> None:
         lo += k
 
 
+def _design_call(name, logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints, padded=(), head=None, tail=None,
+                 outputs=(), entry=None):
+    """One call of a design entry of the C ABI -> (seqs, seq_nll, infeasible, *the entry's further outputs).  What the five entries share
+    is done here, once: the device check (it speaks of ``name``), the constraints' tensors, the layout, the shape checks, the outputs and
+    the common positional arguments.  What is an entry's own comes in: ``padded`` - further (label, tensor, dtype) inputs padded to
+    (B,T), prepared and shape-checked ahead of the constraints'; ``head`` / ``tail`` - callables (B, T, mask, cu, *the padded inputs) ->
+    the entry's own arguments, tensors or scalars, placed where the ABI has them: after the rows / after the bias; ``outputs`` -
+    (dtype, per sample ?) of the outputs past ``infeasible``: (S,B) or (B,); ``entry`` - the symbol when it is not ``name``."""
+    device = logits.device
+    if device.type != "cuda":
+        raise RuntimeError(f"{name} runs on an MI355X: pass CUDA logits (there is no CPU fallback)")
+    c = constraints
+    own = [(label, _prep(t, device, dtype)) for label, t, dtype in padded]
+    al = None if c is None or c.allowed is None else _prep(c.allowed, device, torch.uint8)
+    pa = None if c is None or c.partner is None else _prep(c.partner, device, torch.int32)
+    bi = None if c is None or c.bias is None else _prep(c.bias, device)
+    lg, m, cu, B, T = _layout(logits, mask, cu_seqlens, tuple(t for _, t in own) + (al, pa), max_len)
+    for label, t in own + [("constraints.allowed", al), ("constraints.partner", pa)]:
+        if t is not None and tuple(t.shape) != (B, T):
+            raise ValueError(f"{label} must be padded to (B, T) = {(B, T)}, got {tuple(t.shape)}")
+    per_position = int(bi is not None and tuple(bi.shape) == (B, T, 4))
+    if bi is not None and not per_position and tuple(bi.shape) != (4,):
+        raise ValueError(f"constraints.bias must be (4,) or (B, T, 4) = {(B, T, 4)}, got {tuple(bi.shape)}")
+    _check_logits(lg, m, B, T)
+    its = [() if f is None else tuple(f(B, T, m, cu, *(t for _, t in own))) for f in (head, tail)]
+    S = int(n_samples)
+    seqs = torch.empty(max(S, 0), max(B, 0), max(T, 0), dtype=torch.int8, device=device)
+    nll = torch.empty(max(S, 0), max(B, 0), dtype=torch.float32, device=device)
+    bad = torch.empty(max(B, 0), dtype=torch.int32, device=device)
+    more = [torch.empty(*((max(S, 0),) if per_sample else ()), max(B, 0), dtype=dtype, device=device) for dtype, per_sample in outputs]
+    args = [lg, int(lg.numel()) // 4, m, cu, B, T, *its[0], float(temperature), S, _seed64(seed), None, al, pa,
+            int(bool(c.wobble)) if c is not None else 1, bi, per_position, *its[1], seqs, nll, bad, *more]
+    with torch.cuda.device(device):
+        _native.check(getattr(_native.lib(), entry or name)(*[_ptr(v) if torch.is_tensor(v) else v for v in args], _stream(device)))
+    return (seqs, nll, bad, *more)
+
+
 def design_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
                        max_len: Optional[int] = None, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None,
                        states=None, state_weights=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -93,42 +130,19 @@ def design_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None
     product of their distributions under the union of their base-pair tables; ``seq_nll`` stays per row, ``infeasible`` is the group's count
     on each of its rows.  ``state_weights`` (B,) per row (default 1; negative = design against that state).  ``None`` keeps ``rnampnn_design``.
     CUDA logits only (there is no CPU fallback); no host synchronisation."""
-    device = logits.device
-    if device.type != "cuda":
-        raise RuntimeError("rnampnn_design runs on an MI355X: pass CUDA logits (there is no CPU fallback)")
-    c = constraints
-    al = None if c is None or c.allowed is None else _prep(c.allowed, device, torch.uint8)
-    pa = None if c is None or c.partner is None else _prep(c.partner, device, torch.int32)
-    bi = None if c is None or c.bias is None else _prep(c.bias, device)
-    lg, m, cu, B, T = _layout(logits, mask, cu_seqlens, (al, pa), max_len)
-    for name, t in (("allowed", al), ("partner", pa)):
-        if t is not None and tuple(t.shape) != (B, T):
-            raise ValueError(f"constraints.{name} must be padded to (B, T) = {(B, T)}, got {tuple(t.shape)}")
-    per_position = int(bi is not None and tuple(bi.shape) == (B, T, 4))
-    if bi is not None and not per_position and tuple(bi.shape) != (4,):
-        raise ValueError(f"constraints.bias must be (4,) or (B, T, 4) = {(B, T, 4)}, got {tuple(bi.shape)}")
-    _check_logits(lg, m, B, T)
-    S = int(n_samples)
-    seqs = torch.empty(max(S, 0), max(B, 0), max(T, 0), dtype=torch.int8, device=device)
-    nll = torch.empty(max(S, 0), max(B, 0), dtype=torch.float32, device=device)
-    bad = torch.empty(max(B, 0), dtype=torch.int32, device=device)
-    rows = (_ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(cu), B, T)
-    draw = (float(temperature), S, _seed64(seed), None, _ptr(al), _ptr(pa), int(bool(c.wobble)) if c is not None else 1, _ptr(bi),
-            per_position, _ptr(seqs), _ptr(nll), _ptr(bad), _stream(device))
-    if states is None and state_weights is not None:
-        raise ValueError("state_weights belong to multi-state design: pass states as well")
-    if states is None:
-        with torch.cuda.device(device):
-            _native.check(_native.lib().rnampnn_design(*rows, *draw))
-        return seqs, nll, bad
-    counts = _state_counts(states, B)
-    gcu = torch.tensor([0] + list(itertools.accumulate(counts)), dtype=torch.int32).to(device, non_blocking=True)
-    sw = None if state_weights is None else _prep(torch.as_tensor(state_weights, dtype=torch.float32), device)
-    if sw is not None and tuple(sw.shape) != (B,):
-        raise ValueError(f"state_weights must be (B,) = {(B,)}, got {tuple(sw.shape)}")
-    with torch.cuda.device(device):
-        _native.check(_native.lib().rnampnn_design_tied(*rows, _ptr(gcu), len(counts), _ptr(sw), *draw))
-    return seqs, nll, bad
+    def tied(B, T, m, cu):
+        if states is None:
+            if state_weights is not None:
+                raise ValueError("state_weights belong to multi-state design: pass states as well")
+            return ()
+        counts = _state_counts(states, B)
+        gcu = torch.tensor([0] + list(itertools.accumulate(counts)), dtype=torch.int32).to(logits.device, non_blocking=True)
+        sw = None if state_weights is None else _prep(torch.as_tensor(state_weights, dtype=torch.float32), logits.device)
+        if sw is not None and tuple(sw.shape) != (B,):
+            raise ValueError(f"state_weights must be (B,) = {(B,)}, got {tuple(sw.shape)}")
+        return gcu, len(counts), sw
+    return _design_call("rnampnn_design", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints, head=tied,
+                        entry="rnampnn_design" if states is None else "rnampnn_design_tied")
 
 
 def gc_fractions(gc_content, B: int) -> torch.Tensor:
@@ -167,36 +181,12 @@ def design_gc_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = N
     (B,2) tensor of them (float64: a float32 fraction carries its rounding into f * n); the counts are formed on the device from the mask
     or ``cu_seqlens`` (``gc_counts``), without a host synchronisation.  Fractions outside [0, 1] or lo > hi raise ``ValueError`` (a device
     tensor is not read back for that: the kernel clamps it).  CUDA logits only (there is no CPU fallback)."""
-    device = logits.device
-    if device.type != "cuda":
-        raise RuntimeError("rnampnn_design_gc runs on an MI355X: pass CUDA logits (there is no CPU fallback)")
-    c = constraints
-    al = None if c is None or c.allowed is None else _prep(c.allowed, device, torch.uint8)
-    pa = None if c is None or c.partner is None else _prep(c.partner, device, torch.int32)
-    bi = None if c is None or c.bias is None else _prep(c.bias, device)
-    lg, m, cu, B, T = _layout(logits, mask, cu_seqlens, (al, pa), max_len)
-    for name, t in (("allowed", al), ("partner", pa)):
-        if t is not None and tuple(t.shape) != (B, T):
-            raise ValueError(f"constraints.{name} must be padded to (B, T) = {(B, T)}, got {tuple(t.shape)}")
-    per_position = int(bi is not None and tuple(bi.shape) == (B, T, 4))
-    if bi is not None and not per_position and tuple(bi.shape) != (4,):
-        raise ValueError(f"constraints.bias must be (4,) or (B, T, 4) = {(B, T, 4)}, got {tuple(bi.shape)}")
-    _check_logits(lg, m, B, T)
-    fr = gc_fractions(gc_content, max(B, 0)).to(device, non_blocking=True)
-    lengths = (m.sum(dim=1) + 0.5).floor() if m is not None else (cu[1:] - cu[:-1]).clamp(0, max(T, 0))
-    lo, hi = gc_counts(fr, lengths)
-    S = int(n_samples)
-    seqs = torch.empty(max(S, 0), max(B, 0), max(T, 0), dtype=torch.int8, device=device)
-    nll = torch.empty(max(S, 0), max(B, 0), dtype=torch.float32, device=device)
-    bad = torch.empty(max(B, 0), dtype=torch.int32, device=device)
-    count = torch.empty(max(S, 0), max(B, 0), dtype=torch.int32, device=device)
-    miss = torch.empty(max(B, 0), dtype=torch.int32, device=device)
-    with torch.cuda.device(device):
-        _native.check(_native.lib().rnampnn_design_gc(
-            _ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(cu), B, T, float(temperature), S, _seed64(seed), None, _ptr(al), _ptr(pa),
-            int(bool(c.wobble)) if c is not None else 1, _ptr(bi), per_position, _ptr(lo), _ptr(hi), _ptr(seqs), _ptr(nll), _ptr(bad),
-            _ptr(count), _ptr(miss), _stream(device)))
-    return seqs, nll, bad, count, miss
+    def window(B, T, m, cu):
+        fr = gc_fractions(gc_content, max(B, 0)).to(logits.device, non_blocking=True)
+        lengths = (m.sum(dim=1) + 0.5).floor() if m is not None else (cu[1:] - cu[:-1]).clamp(0, max(T, 0))
+        return gc_counts(fr, lengths)
+    return _design_call("rnampnn_design_gc", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints, tail=window,
+                        outputs=((torch.int32, True), (torch.int32, False)))
 
 
 def mutation_sets(reference: torch.Tensor) -> torch.Tensor:
@@ -245,47 +235,21 @@ def design_count_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] 
     tree in LDS (T <= 2867 at cap 8, 1017 without a cap).  It defaults to the largest hi of a host-side window; a device window without
     ``cap`` or a host hi above ``cap`` is a ``ValueError``.  Layouts and ``constraints`` as in ``design_from_logits``.  CUDA logits only
     (there is no CPU fallback); no host synchronisation."""
-    device = logits.device
-    if device.type != "cuda":
-        raise RuntimeError("rnampnn_design_count runs on an MI355X: pass CUDA logits (there is no CPU fallback)")
     if counted is None:
         raise ValueError("counted is required: the (B, T) sets of classes that count (mutation_sets(reference) for a mutation budget)")
-    c = constraints
-    al = None if c is None or c.allowed is None else _prep(c.allowed, device, torch.uint8)
-    pa = None if c is None or c.partner is None else _prep(c.partner, device, torch.int32)
-    bi = None if c is None or c.bias is None else _prep(c.bias, device)
-    cs = _prep(counted, device, torch.uint8)
-    lg, m, cu, B, T = _layout(logits, mask, cu_seqlens, (cs, al, pa), max_len)
-    for name, t in (("counted", cs), ("constraints.allowed", al), ("constraints.partner", pa)):
-        if t is not None and tuple(t.shape) != (B, T):
-            raise ValueError(f"{name} must be padded to (B, T) = {(B, T)}, got {tuple(t.shape)}")
-    per_position = int(bi is not None and tuple(bi.shape) == (B, T, 4))
-    if bi is not None and not per_position and tuple(bi.shape) != (4,):
-        raise ValueError(f"constraints.bias must be (4,) or (B, T, 4) = {(B, T, 4)}, got {tuple(bi.shape)}")
-    _check_logits(lg, m, B, T)
-    w, cap = count_window(window, cap, max(B, 0))
-    w = w.to(device, non_blocking=True)
-    lo, hi = w[:, 0].contiguous(), w[:, 1].contiguous()
-    S = int(n_samples)
-    seqs = torch.empty(max(S, 0), max(B, 0), max(T, 0), dtype=torch.int8, device=device)
-    nll = torch.empty(max(S, 0), max(B, 0), dtype=torch.float32, device=device)
-    bad = torch.empty(max(B, 0), dtype=torch.int32, device=device)
-    count = torch.empty(max(S, 0), max(B, 0), dtype=torch.int32, device=device)
-    miss = torch.empty(max(B, 0), dtype=torch.int32, device=device)
-    with torch.cuda.device(device):
-        _native.check(_native.lib().rnampnn_design_count(
-            _ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(cu), B, T, float(temperature), S, _seed64(seed), None, _ptr(al), _ptr(pa),
-            int(bool(c.wobble)) if c is not None else 1, _ptr(bi), per_position, _ptr(cs), _ptr(lo), _ptr(hi), cap, _ptr(seqs), _ptr(nll),
-            _ptr(bad), _ptr(count), _ptr(miss), _stream(device)))
-    return seqs, nll, bad, count, miss
+
+    def sets_and_window(B, T, m, cu, cs):
+        w, top = count_window(window, cap, max(B, 0))
+        w = w.to(logits.device, non_blocking=True)
+        return cs, w[:, 0].contiguous(), w[:, 1].contiguous(), top
+    return _design_call("rnampnn_design_count", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints,
+                        padded=(("counted", counted, torch.uint8),), tail=sets_and_window, outputs=((torch.int32, True), (torch.int32, False)))
 
 
 def check_budget(lo: int, hi: int, states=None, gc_content=None, distinct=None) -> Tuple[int, int]:
     """A mutation budget of between ``lo`` and ``hi`` positions -> (lo, hi).  ``ValueError`` for a negative or inverted budget and for
     a combination that is not built; touches no device."""
-    for name, value in (("states", states), ("gc_content", gc_content), ("distinct", distinct)):
-        if value is not None:
-            raise ValueError(f"mutations together with {name} is not built: the budget conditions the draws of rnampnn_design on one count")
+    design_mode(states, gc_content, distinct, mutations=(lo, hi))
     lo, hi = int(lo), int(hi)
     if lo < 0 or hi < lo:
         raise ValueError(f"mutations: the budget needs 0 <= min <= max, got min = {lo}, max = {hi}")
@@ -326,44 +290,51 @@ def design_distinct_from_logits(logits: torch.Tensor, mask: Optional[torch.Tenso
     ``design_from_logits``.  CUDA logits only (there is no CPU fallback); no host synchronisation."""
     if mode not in DISTINCT_MODES:
         raise ValueError(f"mode must be one of {sorted(DISTINCT_MODES)}, got {mode!r}")
-    device = logits.device
-    if device.type != "cuda":
-        raise RuntimeError("rnampnn_design_distinct runs on an MI355X: pass CUDA logits (there is no CPU fallback)")
-    c = constraints
-    al = None if c is None or c.allowed is None else _prep(c.allowed, device, torch.uint8)
-    pa = None if c is None or c.partner is None else _prep(c.partner, device, torch.int32)
-    bi = None if c is None or c.bias is None else _prep(c.bias, device)
-    lg, m, cu, B, T = _layout(logits, mask, cu_seqlens, (al, pa), max_len)
-    for name, t in (("allowed", al), ("partner", pa)):
-        if t is not None and tuple(t.shape) != (B, T):
-            raise ValueError(f"constraints.{name} must be padded to (B, T) = {(B, T)}, got {tuple(t.shape)}")
-    per_position = int(bi is not None and tuple(bi.shape) == (B, T, 4))
-    if bi is not None and not per_position and tuple(bi.shape) != (4,):
-        raise ValueError(f"constraints.bias must be (4,) or (B, T, 4) = {(B, T, 4)}, got {tuple(bi.shape)}")
-    _check_logits(lg, m, B, T)
-    S = int(n_samples)
-    seqs = torch.empty(max(S, 0), max(B, 0), max(T, 0), dtype=torch.int8, device=device)
-    nll = torch.empty(max(S, 0), max(B, 0), dtype=torch.float32, device=device)
-    bad = torch.empty(max(B, 0), dtype=torch.int32, device=device)
-    logp = torch.empty(max(S, 0), max(B, 0), dtype=torch.float32, device=device)
-    filled = torch.empty(max(B, 0), dtype=torch.int32, device=device)
-    with torch.cuda.device(device):
-        _native.check(_native.lib().rnampnn_design_distinct(
-            _ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(cu), B, T, float(temperature), S, _seed64(seed), None, _ptr(al), _ptr(pa),
-            int(bool(c.wobble)) if c is not None else 1, _ptr(bi), per_position, DISTINCT_MODES[mode], _ptr(seqs), _ptr(nll), _ptr(bad),
-            _ptr(logp), _ptr(filled), _stream(device)))
-    return seqs, nll, bad, logp, filled
+    return _design_call("rnampnn_design_distinct", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints,
+                        tail=lambda B, T, m, cu: (DISTINCT_MODES[mode],), outputs=((torch.float32, True), (torch.int32, False)))
 
 
 def check_distinct(distinct, states=None, gc_content=None) -> None:
     """``design(..., distinct=...)``: ``ValueError`` for an unknown mode or a combination that is not built; touches no device."""
-    if distinct is None:
-        return
-    if distinct not in DISTINCT_MODES:
-        raise ValueError(f"distinct must be None or one of {sorted(DISTINCT_MODES)}, got {distinct!r}")
-    for name, value in (("states", states), ("gc_content", gc_content)):
-        if value is not None:
-            raise ValueError(f"distinct together with {name} is not built: the beam runs over the units of rnampnn_design only")
+    if distinct is not None:
+        design_mode(states, gc_content, distinct)
+
+
+# What conditions the draws, in the order in which it decides the mode: (the argument that selects the mode, the arguments it is not built
+# together with, why).  A mode further down is excluded by the ones above it, so every pair is named once.
+DESIGN_MODES = (("mutations", ("states", "gc_content", "distinct"), "the budget conditions the draws of rnampnn_design on one count"),
+                ("distinct", ("states", "gc_content"), "the beam runs over the units of rnampnn_design only"),
+                ("gc_content", ("states",), "the G+C window conditions the draws of rnampnn_design only"),
+                ("states", (), ""))
+
+
+def design_mode(states=None, gc_content=None, distinct=None, mutations=None) -> str:
+    """Which entry ``design(...)`` draws from: "mutations", "distinct", "gc_content", "states", or "plain" when none of them is given.
+    ``ValueError`` for a combination that is not built (``DESIGN_MODES``) and an unknown ``distinct``; touches no device, so a caller
+    refuses before its forward pass."""
+    given = {"states": states, "gc_content": gc_content, "distinct": distinct, "mutations": mutations}
+    for mode, excluded, why in DESIGN_MODES:
+        if given[mode] is None:
+            continue
+        if mode == "distinct" and distinct not in DISTINCT_MODES:
+            raise ValueError(f"distinct must be None or one of {sorted(DISTINCT_MODES)}, got {distinct!r}")
+        for name in excluded:
+            if given[name] is not None:
+                raise ValueError(f"{mode} together with {name} is not built: {why}")
+        return mode
+    return "plain"
+
+
+def design_by_mode(mode: str, logits: torch.Tensor, states=None, state_weights=None, gc_content=None, distinct=None, mutations=None, **kw):
+    """The ``*_from_logits`` call of ``mode`` (``design_mode``) -> what that function returns.  ``mutations`` as ``check_mutations``
+    returns it; ``kw``: the layout and the draw (mask / cu_seqlens / max_len, n_samples, temperature, seed, constraints)."""
+    if mode == "mutations":
+        return design_mutations_from_logits(logits, mutations, **kw)
+    if mode == "distinct":
+        return design_distinct_from_logits(logits, mode=distinct, **kw)
+    if mode == "gc_content":
+        return design_gc_from_logits(logits, gc_content=gc_content, **kw)
+    return design_from_logits(logits, states=states, state_weights=state_weights, **kw)
 
 
 SCORE_OUTPUTS = {"valid": torch.int32, "pred": torch.int8, "correct": torch.int32, "label_nll": torch.float32, "label_loss": torch.float32,

@@ -23,9 +23,9 @@ from .. import _native
 from ..config.glob import DEFAULT_SEED, REVERSE_VOCAB
 from ..utils.data import check_prefix_mask
 from ._base import NativeModule, _prep, _ptr, _stream
-from .decode import (SCORE_OUTPUTS, argmax_recovery, check_distinct, check_mutations, check_state_lengths, design_distinct_from_logits,  # noqa: F401
-                     design_from_logits, design_gc_from_logits, design_mutations_from_logits, letters_packed, letters_padded,
-                     sample_from_logits, score_logits)
+from .decode import (SCORE_OUTPUTS, argmax_recovery, check_distinct, check_mutations, check_state_lengths, design_by_mode,  # noqa: F401
+                     design_distinct_from_logits, design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits,
+                     letters_packed, letters_padded, sample_from_logits, score_logits)
 from ._schema import DEFAULT_HPARAMS
 
 _CHECK_MASKS = os.environ.get("RNAMPNN_CHECK_MASKS", "0") == "1"
@@ -565,25 +565,14 @@ class RNAMPNN(NativeModule):
         (default 0) and max positions, drawn exactly from the model's distribution conditioned on that (``design_count_from_logits``) ->
         (seqs, seq_nll, infeasible, n_mut (n_samples,B) int32, mut_miss (B,) int32 = how far the structure and the fixed positions alone
         push the count out of the budget, 0 when it is reachable); not built together with ``states``, ``gc_content`` or ``distinct``."""
-        mutations = check_mutations(mutations, states, gc_content, distinct)
-        check_distinct(distinct, states, gc_content)
-        if gc_content is not None and states is not None:
-            raise ValueError("gc_content together with states is not built: the G+C window conditions the draws of rnampnn_design only")
+        mode = design_mode(states, gc_content, distinct, mutations)
+        mutations = check_mutations(mutations)
         if states is not None and lengths is not None:
             check_state_lengths(states, lengths)
         logits = self._run(coords, mask, T_norm=T_norm)["logits"]
-        if mutations is not None:
-            return design_mutations_from_logits(logits, mutations, mask=mask, n_samples=n_samples, temperature=temperature, seed=seed,
-                                                constraints=constraints)
-        if distinct is not None:
-            return design_distinct_from_logits(logits, mask=mask, n_samples=n_samples, temperature=temperature, seed=seed,
-                                               constraints=constraints, mode=distinct)
-        if gc_content is not None:
-            return design_gc_from_logits(logits, mask=mask, n_samples=n_samples, temperature=temperature, seed=seed, constraints=constraints,
-                                         gc_content=gc_content)
-        if constraints is not None or states is not None:
-            return design_from_logits(logits, mask=mask, n_samples=n_samples, temperature=temperature, seed=seed, constraints=constraints,
-                                      states=states, state_weights=state_weights)
+        if mode != "plain" or constraints is not None:
+            return design_by_mode(mode, logits, mask=mask, n_samples=n_samples, temperature=temperature, seed=seed, constraints=constraints,
+                                  states=states, state_weights=state_weights, gc_content=gc_content, distinct=distinct, mutations=mutations)
         seqs = sample_from_logits(logits, mask, temperature, n_samples, seed)
         return seqs, score_logits(logits, mask=mask, seqs=seqs, want=("seq_nll",))["seq_nll"]
 

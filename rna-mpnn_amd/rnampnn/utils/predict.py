@@ -11,8 +11,7 @@ import numpy as np
 import torch
 
 from ..config.glob import VOCAB
-from ..model.decode import (check_budget, check_distinct, design_distinct_from_logits, design_from_logits, design_gc_from_logits,
-                            design_mutations_from_logits, letters_packed, letters_padded, sample_from_logits, score_logits)
+from ..model.decode import check_budget, design_by_mode, design_mode, letters_packed, letters_padded, sample_from_logits, score_logits
 from .constraints import batch_constraints, mutation_references, padded_references
 from .data import PackedLoader, bucket_batches, fill_nan_deterministic, read_fasta
 
@@ -78,12 +77,13 @@ def group_batches(groups, lengths: List[int], batch_size: int, max_rows: int) ->
     return batches
 
 
-def draw_batch(logits, cu, max_len: int, samples: int, temperature: float, seed: int, cons=None, states=None, state_weights=None):
-    """``samples`` draws per row of one packed batch -> (draws int8 (S,B,T), seq_nll (S,B) or None, infeasible (B,) or None): from
-    ``rnampnn_design`` / ``_tied`` under constraints or ``states`` (they score their own draws), else free draws from ``rnampnn_sample``."""
-    if cons is not None or states is not None:
-        return design_from_logits(logits, cu_seqlens=cu, max_len=max_len, n_samples=samples, temperature=temperature, seed=seed,
-                                  constraints=cons, states=states, state_weights=state_weights)
+def draw_batch(logits, cu, max_len: int, samples: int, temperature: float, seed: int, cons=None, mode: str = "plain", **own):
+    """``samples`` draws per row of one packed batch -> (draws int8 (S,B,T), seq_nll (S,B) or None, infeasible (B,) or None, *the further
+    outputs of the mode's entry): from the design entry of ``mode`` (``design_by_mode``, ``own``: that mode's arguments) under constraints
+    or in any mode but "plain" (they score their own draws), else free draws from ``rnampnn_sample``."""
+    if cons is not None or mode != "plain":
+        return design_by_mode(mode, logits, cu_seqlens=cu, max_len=max_len, n_samples=samples, temperature=temperature, seed=seed,
+                              constraints=cons, **own)
     # rnampnn_sample takes the padded layout: scatter the packed logits once (row cu[b] + t -> (b, t)); the mask comes from cu
     t = torch.arange(max_len, device=logits.device)
     mask = (t[None, :] < (cu[1:] - cu[:-1])[:, None]).to(torch.float32)
@@ -111,6 +111,20 @@ def write_csv(path: str, header: str, rows) -> None:
         f.write(header + "\n")
         for row in rows:
             f.write(",".join(str(v) for v in row) + "\n")
+
+
+def design_columns(mode: str, extras=(), lens=()):
+    """The last columns that ``designs_csv`` gains in a design mode (``design_mode``) -> (their header, cells, filled): ``cells(s, r)``
+    the fields of sample s of row r, ``filled`` [B] the slots of a row that hold a sequence, or None for all of them.  ``extras``: the
+    two outputs of the mode's entry past (seqs, seq_nll, infeasible), ``lens`` the rows' lengths; without them only the header counts."""
+    per_sample, per_row = (t.cpu().tolist() for t in extras) if extras else (None, None)
+    if mode == "gc_content":
+        return ",gc,gc_miss", lambda s, r: (f"{per_sample[s][r] / lens[r]:.6f}", per_row[r]), None
+    if mode == "mutations":
+        return ",mutations,mut_miss", lambda s, r: (per_sample[s][r], per_row[r]), None
+    if mode == "distinct":
+        return ",logp", lambda s, r: (f"{per_sample[s][r]:.6f}",), per_row
+    return "", lambda s, r: (), None
 
 
 @torch.no_grad()
@@ -141,13 +155,11 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     structure without a reference is a ``ValueError`` naming its id.  ``designs_csv`` gains the last columns ``mutations`` (the Hamming
     distance of the draw to the reference) and ``mut_miss`` (0, or by how many mutations the structure and the fixed positions alone
     exceed the budget).  Not built together with ``states``, ``gc_content`` or ``distinct``."""
+    mode = design_mode(states, gc_content, distinct, mutations)
     if mutations is not None:
-        check_budget(mutations[0], mutations[1], states, gc_content, distinct)
+        check_budget(mutations[0], mutations[1])
         if samples <= 0:
             raise ValueError("a mutation budget needs samples > 0")
-    check_distinct(distinct, states, gc_content)
-    if gc_content is not None and states is not None:
-        raise ValueError("gc_content together with states is not built")
     model.eval()
     device = model._device()
     items = load_structures(data_path, max_len=int(model.hparams["padding_len"]))
@@ -184,27 +196,14 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
         cons = None
         if constrained:
             cons = batch_constraints(constraints, [ids[i] for i in idx], lens, max_len, bias=bias, wobble=wobble, omit=omit).to_device(device)
-        gcs = muts = logp = None
-        filled = [samples] * len(idx)
-        if distinct is not None:
-            draws, dnll, bad, logp, filled = design_distinct_from_logits(logits, cu_seqlens=cu, max_len=max_len, n_samples=samples,
-                                                                         temperature=temperature, seed=seed + bi, constraints=cons,
-                                                                         mode=distinct)
-            bad, logp, filled = (bad if constrained else None), logp.cpu().tolist(), filled.cpu().tolist()
-        elif mutations is not None:
-            draws, dnll, bad, count, miss = design_mutations_from_logits(
-                logits, (padded_references(refs, idx, max_len), (mutations[0], mutations[1])), cu_seqlens=cu, max_len=max_len,
-                n_samples=samples, temperature=temperature, seed=seed + bi, constraints=cons)
-            bad, muts = (bad if constrained else None), (count.cpu().tolist(), miss.cpu().tolist())
-        elif gc_content is not None:
-            draws, dnll, bad, count, miss = design_gc_from_logits(logits, cu_seqlens=cu, max_len=max_len, n_samples=samples,
-                                                                  temperature=temperature, seed=seed + bi, constraints=cons,
-                                                                  gc_content=gc_content)
-            bad, gcs = (bad if constrained else None), (count.cpu().tolist(), miss.cpu().tolist())
-        else:
-            draws, dnll, bad = draw_batch(logits, cu, max_len, samples, temperature, seed + bi, cons,
-                                          states=None if gs is None else [len(groups[g][1]) for g in gs],
-                                          state_weights=None if gs is None else [w for g in gs for w in groups[g][2]])
+        draws, dnll, bad, *extras = draw_batch(
+            logits, cu, max_len, samples, temperature, seed + bi, cons, mode, gc_content=gc_content, distinct=distinct,
+            mutations=None if mutations is None else (padded_references(refs, idx, max_len), (mutations[0], mutations[1])),
+            states=None if gs is None else [len(groups[g][1]) for g in gs],
+            state_weights=None if gs is None else [w for g in gs for w in groups[g][2]])
+        if not constrained and gs is None:
+            bad = None                                              # the column belongs to the constrained forms
+        _, cells, filled = design_columns(mode, extras, lens)
         bad = None if bad is None else bad.cpu().tolist()
         lab, have = padded_labels(items, idx, max_len)
         want = (("seq_nll",) if dnll is None else ()) + (("seq_match",) if lab is not None else ())      # rnampnn_design scores its own draws
@@ -216,12 +215,10 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             recs = [f"{match[s][r] / lens[r]:.6f}" if have[r] else "" for r in range(len(idx))]
             if gs is None:
                 for r, i in enumerate(idx):
-                    if s >= filled[r]:
+                    if filled is not None and s >= filled[r]:
                         continue                                    # fewer admitted sequences than samples: the slot is empty
                     designs.setdefault(i, []).append((s, text[r], f"{nll[s][r] / lens[r]:.6f}", recs[r]) + (() if bad is None else (bad[r],))
-                                                     + (() if gcs is None else (f"{gcs[0][s][r] / lens[r]:.6f}", gcs[1][r]))
-                                                     + (() if muts is None else (muts[0][s][r], muts[1][r]))
-                                                     + (() if logp is None else (f"{logp[s][r]:.6f}",)))
+                                                     + cells(s, r))
                 continue
             r = 0
             for g in gs:                                            # one row per (design, sample); the states are consecutive rows
@@ -235,7 +232,6 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
         write_csv(designs_csv, "design_id,sample,seq,infeasible,states,nll_per_nt,recovery",
                   [(group[0],) + row for g, group in enumerate(groups) for row in designs[g]])
     elif samples > 0:
-        write_csv(designs_csv, "pdb_id,sample,seq,nll_per_nt,recovery" + (",infeasible" if constrained else "")
-                  + (",gc,gc_miss" if gc_content is not None else "") + (",mutations,mut_miss" if mutations is not None else "")
-                  + (",logp" if distinct is not None else ""), [(rid,) + row for i, rid in enumerate(ids) for row in designs[i]])
+        write_csv(designs_csv, "pdb_id,sample,seq,nll_per_nt,recovery" + (",infeasible" if constrained else "") + design_columns(mode)[0],
+                  [(rid,) + row for i, rid in enumerate(ids) for row in designs[i]])
     return rows

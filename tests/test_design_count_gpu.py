@@ -30,6 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _design_count_ref as R  # noqa: E402
 import _design_gc_ref as G  # noqa: E402
 from _design_ref import PAIRS  # noqa: E402
+from _design_case import SMALL, design_outputs, raw_design, _bytes, _dev, _specs, _write_data, _checkpoint  # noqa: E402
 
 LENGTHS, T, S, SEED = R.CASE_LENGTHS, R.CASE_T, R.CASE_S, R.CASE_SEED
 NEAR = 1e-8
@@ -37,36 +38,17 @@ T_MAX_CAP8 = 2867                                                  # the largest
 OUTPUTS = ("seqs", "seq_nll", "infeasible", "count", "count_miss")
 
 
-def _bytes(t):
-    return t.cpu().numpy().tobytes()
-
-
-def _dev(x, dtype=None):
-    return None if x is None else torch.as_tensor(np.ascontiguousarray(x) if isinstance(x, np.ndarray) else x, dtype=dtype).contiguous().cuda()
+FURTHER = (("count", torch.int32, True), ("count_miss", torch.int32, False))
 
 
 def _outputs(S, B, T):
-    return dict(seqs=torch.empty(S, B, T, dtype=torch.int8, device="cuda"), seq_nll=torch.empty(S, B, dtype=torch.float32, device="cuda"),
-                infeasible=torch.empty(B, dtype=torch.int32, device="cuda"), count=torch.empty(S, B, dtype=torch.int32, device="cuda"),
-                count_miss=torch.empty(B, dtype=torch.int32, device="cuda"))
+    return design_outputs(FURTHER, S, B, T)
 
 
-def design_count(logits, counted, lo, hi, cap, mask=None, cu=None, T=None, temperature=1.0, S=S, seed=SEED, allowed=None, partner=None,
-                 wobble=R.CASE_WOBBLE, bias=None, seed_dev=None, out=None):
+def design_count(logits, counted, lo, hi, cap, seed=SEED, S=S, wobble=R.CASE_WOBBLE, **kw):
     """The C entry on device tensors (numpy arrays are uploaded) -> dict of its five outputs."""
-    from rnampnn import _native
-    from rnampnn.model._base import _ptr, _stream
-    lg, m, c = _dev(logits, torch.float32), _dev(mask, torch.float32), _dev(cu, torch.int32)
-    B = int(m.shape[0]) if m is not None else int(c.numel()) - 1
-    T = int(m.shape[1]) if m is not None else int(T)
-    al, pa, bi = _dev(allowed, torch.uint8), _dev(partner, torch.int32), _dev(bias, torch.float32)
-    cs, clo, chi = _dev(counted, torch.uint8), _dev(lo, torch.int32), _dev(hi, torch.int32)
-    out = _outputs(S, B, T) if out is None else out
-    _native.check(_native.lib().rnampnn_design_count(
-        _ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(c), B, T, float(temperature), S, C.c_uint64(seed), _ptr(seed_dev), _ptr(al), _ptr(pa),
-        int(wobble), _ptr(bi), int(bi is not None and bi.dim() == 3), _ptr(cs), _ptr(clo), _ptr(chi), int(cap),
-        *[_ptr(out[k]) for k in OUTPUTS], _stream(lg.device)))
-    return out
+    return raw_design("rnampnn_design_count", (_dev(counted, torch.uint8), _dev(lo, torch.int32), _dev(hi, torch.int32), int(cap)), FURTHER,
+                      logits, seed=seed, S=S, wobble=wobble, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -417,12 +399,7 @@ def test_design_count_from_logits_in_both_layouts_and_with_a_device_window(case)
         design_count_from_logits(case["logits"], mask=case["mask"], window=window, **kw)
 
 
-SMALL = dict(num_res_neighbours=6, num_res_mpnn_layers=2, padding_len=128)
 MODEL_LENGTHS = [33, 20, 41]
-
-
-def _specs():
-    return [("GNRA" + "." * 29, "((((....))))" + "." * 21), (None, "(((..[[[)))....]]].."), ("." * 40 + "U", None)]
 
 
 def _check_budget(out, native, lengths, budget, fixed=None):
@@ -475,26 +452,6 @@ def test_both_models_design_within_a_mutation_budget():
     out = r.design(X, mask, n_samples=3, temperature=1.0, seed=5, constraints=cons, lengths=MODEL_LENGTHS, mutations=(native, 1, 4))
     _check_budget(out, native, lens, 4, fixed=[(0, 0, 3), (0, 3, 0), (2, 40, 1)])
     assert len(r.design(X, mask, n_samples=3, temperature=1.0, seed=5, constraints=cons, lengths=MODEL_LENGTHS)) == 3
-
-
-def _write_data(root, ids, lens):
-    from rnampnn.utils import synth
-    os.makedirs(root / "coords"); os.makedirs(root / "seqs")
-    for i, (rid, n) in enumerate(zip(ids, lens)):
-        np.save(root / "coords" / f"{rid}.npy", synth.synth_rna(n, 40 + i, seed=3))
-        (root / "seqs" / f"{rid}.fasta").write_text(f">{rid}\n" + "".join("AUCG"[v] for v in synth.synth_labels(n, 40 + i, seed=3)) + "\n")
-
-
-def _checkpoint(family, path):
-    torch.manual_seed(0)
-    if family == "rnampnn":
-        from rnampnn.model.rnampnn import RNAMPNN
-        from rnampnn.utils.train import save_checkpoint
-        save_checkpoint(path, RNAMPNN(precision="f32", **SMALL))
-    else:
-        from rdesign.model.rdesign import RNAModel
-        from rdesign.utils.train import save_checkpoint
-        save_checkpoint(path, RNAModel(num_mpnn_layers=1))
 
 
 @pytest.mark.parametrize("family", ["rnampnn", "rdesign"])

@@ -27,35 +27,16 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import _design_distinct_ref as D  # noqa: E402
 from _design_ref import PAIRS  # noqa: E402
+from _design_case import SMALL, raw_design, _bytes, _dev, _specs, _write_data, _checkpoint  # noqa: E402
 
 LENGTHS, T, SEED = D.CASE_LENGTHS, D.CASE_T, D.CASE_SEED
 OUTPUTS = ("seqs", "seq_nll", "infeasible", "logp", "n_distinct")
 
 
-def _bytes(t):
-    return t.cpu().numpy().tobytes()
-
-
-def _dev(x, dtype=None):
-    return None if x is None else torch.as_tensor(np.ascontiguousarray(x) if isinstance(x, np.ndarray) else x, dtype=dtype).contiguous().cuda()
-
-
-def design_distinct(logits, mask=None, cu=None, T=None, temperature=1.0, S=8, seed=SEED, noise=1, allowed=None, partner=None, wobble=True,
-                    bias=None):
+def design_distinct(logits, seed=SEED, noise=1, **kw):
     """The C entry on device tensors (numpy arrays are uploaded) -> dict of its five outputs."""
-    from rnampnn import _native
-    from rnampnn.model._base import _ptr, _stream
-    lg, m, c = _dev(logits, torch.float32), _dev(mask, torch.float32), _dev(cu, torch.int32)
-    B = int(m.shape[0]) if m is not None else int(c.numel()) - 1
-    T = int(m.shape[1]) if m is not None else int(T)
-    al, pa, bi = _dev(allowed, torch.uint8), _dev(partner, torch.int32), _dev(bias, torch.float32)
-    out = dict(seqs=torch.empty(S, B, T, dtype=torch.int8, device="cuda"), seq_nll=torch.empty(S, B, dtype=torch.float32, device="cuda"),
-               infeasible=torch.empty(B, dtype=torch.int32, device="cuda"), logp=torch.empty(S, B, dtype=torch.float32, device="cuda"),
-               n_distinct=torch.empty(B, dtype=torch.int32, device="cuda"))
-    _native.check(_native.lib().rnampnn_design_distinct(
-        _ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(c), B, T, float(temperature), S, C.c_uint64(seed), None, _ptr(al), _ptr(pa), int(wobble),
-        _ptr(bi), int(bi is not None and bi.dim() == 3), int(noise), *[_ptr(out[k]) for k in OUTPUTS], _stream(lg.device)))
-    return out
+    return raw_design("rnampnn_design_distinct", (int(noise),), (("logp", torch.float32, True), ("n_distinct", torch.int32, False)), logits,
+                      seed=seed, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -226,12 +207,7 @@ def test_nan_and_inf_logits_still_give_ids_and_an_in_range_count(case):
 
 
 # ---------------------------------------------------------------------------------------------------------------- Python surface
-SMALL = dict(num_res_neighbours=6, num_res_mpnn_layers=2, padding_len=128)
 MODEL_LENGTHS = [33, 20, 41]
-
-
-def _specs():
-    return [("GNRA" + "." * 29, "((((....))))" + "." * 21), (None, "(((..[[[)))....]]].."), ("." * 40 + "U", None)]
 
 
 def _check_designs(out, cons, lens, S):
@@ -284,26 +260,6 @@ def test_both_models_design_distinct_sequences():
         _check_designs(out, cons, lens, 5)
         assert _bytes(out[1]) == _bytes(r.score_sequences(X, mask, out[0])[0])
     assert len(r.design(X, mask, n_samples=3, temperature=1.0, seed=5, constraints=cons, lengths=MODEL_LENGTHS)) == 3
-
-
-def _write_data(root, ids, lens):
-    from rnampnn.utils import synth
-    os.makedirs(root / "coords"); os.makedirs(root / "seqs")
-    for i, (rid, n) in enumerate(zip(ids, lens)):
-        np.save(root / "coords" / f"{rid}.npy", synth.synth_rna(n, 40 + i, seed=3))
-        (root / "seqs" / f"{rid}.fasta").write_text(f">{rid}\n" + "".join("AUCG"[v] for v in synth.synth_labels(n, 40 + i, seed=3)) + "\n")
-
-
-def _checkpoint(family, path):
-    torch.manual_seed(0)
-    if family == "rnampnn":
-        from rnampnn.model.rnampnn import RNAMPNN
-        from rnampnn.utils.train import save_checkpoint
-        save_checkpoint(path, RNAMPNN(precision="f32", **SMALL))
-    else:
-        from rdesign.model.rdesign import RNAModel
-        from rdesign.utils.train import save_checkpoint
-        save_checkpoint(path, RNAModel(num_mpnn_layers=1))
 
 
 @pytest.mark.parametrize("family", ["rnampnn", "rdesign"])

@@ -26,37 +26,17 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import _design_gc_ref as G  # noqa: E402
 from _design_ref import PAIRS  # noqa: E402
+from _design_case import SMALL, raw_design, _bytes, _dev, _specs, _write_data, _checkpoint  # noqa: E402
 
 LENGTHS, T, S, SEED = G.CASE_LENGTHS, G.CASE_T, G.CASE_S, G.CASE_SEED
 NEAR = 1e-8
 T_MAX = 1017                                                       # the largest padded extent whose tree fits 160 KiB of LDS
 
 
-def _bytes(t):
-    return t.cpu().numpy().tobytes()
-
-
-def _dev(x, dtype=None):
-    return None if x is None else torch.as_tensor(np.ascontiguousarray(x) if isinstance(x, np.ndarray) else x, dtype=dtype).contiguous().cuda()
-
-
-def design_gc(logits, lo, hi, mask=None, cu=None, T=None, temperature=1.0, S=S, seed=SEED, allowed=None, partner=None, wobble=True, bias=None):
+def design_gc(logits, lo, hi, seed=SEED, S=S, **kw):
     """The C entry on device tensors (numpy arrays are uploaded) -> dict of its five outputs."""
-    from rnampnn import _native
-    from rnampnn.model._base import _ptr, _stream
-    import ctypes as C
-    lg, m, c = _dev(logits, torch.float32), _dev(mask, torch.float32), _dev(cu, torch.int32)
-    B = int(m.shape[0]) if m is not None else int(c.numel()) - 1
-    T = int(m.shape[1]) if m is not None else int(T)
-    al, pa, bi = _dev(allowed, torch.uint8), _dev(partner, torch.int32), _dev(bias, torch.float32)
-    glo, ghi = _dev(lo, torch.int32), _dev(hi, torch.int32)
-    out = dict(seqs=torch.empty(S, B, T, dtype=torch.int8, device="cuda"), seq_nll=torch.empty(S, B, dtype=torch.float32, device="cuda"),
-               infeasible=torch.empty(B, dtype=torch.int32, device="cuda"), gc_count=torch.empty(S, B, dtype=torch.int32, device="cuda"),
-               gc_miss=torch.empty(B, dtype=torch.int32, device="cuda"))
-    _native.check(_native.lib().rnampnn_design_gc(
-        _ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(c), B, T, float(temperature), S, C.c_uint64(seed), None, _ptr(al), _ptr(pa), int(wobble),
-        _ptr(bi), int(bi is not None and bi.dim() == 3), _ptr(glo), _ptr(ghi), *[_ptr(out[k]) for k in out], _stream(lg.device)))
-    return out
+    return raw_design("rnampnn_design_gc", (_dev(lo, torch.int32), _dev(hi, torch.int32)),
+                      (("gc_count", torch.int32, True), ("gc_miss", torch.int32, False)), logits, seed=seed, S=S, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -275,12 +255,7 @@ def test_design_gc_from_logits_forms_the_counts_on_the_device(case):
             assert ((count[:, b] >= lo[b]) & (count[:, b] <= max(hi[b], lo[b]))).all(), b
 
 
-SMALL = dict(num_res_neighbours=6, num_res_mpnn_layers=2, padding_len=128)
 MODEL_LENGTHS = [33, 20, 41]
-
-
-def _specs():
-    return [("GNRA" + "." * 29, "((((....))))" + "." * 21), (None, "(((..[[[)))....]]].."), ("." * 40 + "U", None)]
 
 
 def _check_window(seqs, count, lengths, lo_f, hi_f):
@@ -324,26 +299,6 @@ def test_both_models_design_under_a_gc_window():
     _check_window(out[0], out[3], lens, 0.3, 0.4)
     assert _bytes(out[1]) == _bytes(r.score_sequences(X, mask, out[0])[0])
     assert len(r.design(X, mask, n_samples=3, temperature=1.0, seed=5, constraints=cons, lengths=MODEL_LENGTHS)) == 3
-
-
-def _write_data(root, ids, lens):
-    from rnampnn.utils import synth
-    os.makedirs(root / "coords"); os.makedirs(root / "seqs")
-    for i, (rid, n) in enumerate(zip(ids, lens)):
-        np.save(root / "coords" / f"{rid}.npy", synth.synth_rna(n, 40 + i, seed=3))
-        (root / "seqs" / f"{rid}.fasta").write_text(f">{rid}\n" + "".join("AUCG"[v] for v in synth.synth_labels(n, 40 + i, seed=3)) + "\n")
-
-
-def _checkpoint(family, path):
-    torch.manual_seed(0)
-    if family == "rnampnn":
-        from rnampnn.model.rnampnn import RNAMPNN
-        from rnampnn.utils.train import save_checkpoint
-        save_checkpoint(path, RNAMPNN(precision="f32", **SMALL))
-    else:
-        from rdesign.model.rdesign import RNAModel
-        from rdesign.utils.train import save_checkpoint
-        save_checkpoint(path, RNAModel(num_mpnn_layers=1))
 
 
 @pytest.mark.parametrize("family", ["rnampnn", "rdesign"])

@@ -32,6 +32,7 @@ sys.path.insert(0, PKG)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import _design_ref as R  # noqa: E402
+from _design_case import SMALL, _bytes, _specs, _write_data, _checkpoint  # noqa: E402
 
 LENGTHS = [1, 2, 63, 64, 65, 257, 300, 0]
 T = 300
@@ -119,10 +120,6 @@ def _design(case, variant="global", temperature=1.0, n=S, seed=SEED, layout="pad
     if layout == "padded":
         return design_from_logits(case["logits"], mask=case["mask"], **kw)
     return design_from_logits(case["packed"], cu_seqlens=case["cu"], max_len=T, **kw)
-
-
-def _bytes(t):
-    return t.cpu().numpy().tobytes()
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1
@@ -282,13 +279,8 @@ def test_free_design_needs_no_constraint_tensors(case):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 6
-SMALL = dict(num_res_neighbours=6, num_res_mpnn_layers=2, padding_len=128)
 MODEL_LENGTHS = [33, 20, 41]
 # GNRA on a 4-pair stem / a pseudoknot / one fixed last nucleotide
-
-
-def _specs():
-    return [("GNRA" + "." * 29, "((((....))))" + "." * 21), (None, "(((..[[[)))....]]].."), ("." * 40 + "U", None)]
 
 
 def _check_specs(seqs, specs, lengths, wobble=True):
@@ -368,26 +360,6 @@ def test_rdesign_model_designs_and_scores():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 7
-def _write_data(root, ids, lens):
-    from rnampnn.utils import synth
-    os.makedirs(root / "coords"); os.makedirs(root / "seqs")
-    for i, (rid, n) in enumerate(zip(ids, lens)):
-        np.save(root / "coords" / f"{rid}.npy", synth.synth_rna(n, 40 + i, seed=3))
-        (root / "seqs" / f"{rid}.fasta").write_text(f">{rid}\n" + "".join("AUCG"[v] for v in synth.synth_labels(n, 40 + i, seed=3)) + "\n")
-
-
-def _checkpoint(family, path):
-    torch.manual_seed(0)
-    if family == "rnampnn":
-        from rnampnn.model.rnampnn import RNAMPNN
-        from rnampnn.utils.train import save_checkpoint
-        save_checkpoint(path, RNAMPNN(precision="f32", **SMALL))
-    else:
-        from rdesign.model.rdesign import RNAModel
-        from rdesign.utils.train import save_checkpoint
-        save_checkpoint(path, RNAModel(num_mpnn_layers=1))
-
-
 @pytest.mark.parametrize("family", ["rnampnn", "rdesign"])
 def test_predict_cli_with_a_constraints_file(family, tmp_path):
     import __graft_entry__ as g

@@ -41,6 +41,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import _design_ref as R  # noqa: E402
 import _design_tied_ref as TR  # noqa: E402
+from _design_case import SMALL, _bytes, _write_data  # noqa: E402
 
 T = 300
 S = 4
@@ -200,10 +201,6 @@ def _design(case, variant="global", temperature=1.0, n=S, seed=SEED, layout="pad
     if layout == "padded":
         return design_from_logits(case["logits"], mask=case["mask"], **kw)
     return design_from_logits(case["packed"], cu_seqlens=case["cu"], max_len=T, **kw)
-
-
-def _bytes(t):
-    return t.cpu().numpy().tobytes()
 
 
 def _compare(got, want, margin, valid, label):
@@ -409,7 +406,6 @@ def test_the_reference_padding_length_fits(case):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 7
-SMALL = dict(num_res_neighbours=6, num_res_mpnn_layers=2, padding_len=128)
 MODEL_LENGTHS = [33, 33, 41]
 # the two states of a switch (4..7 pair with 15..12 in one state and with 23..20 in the other: four 3-node chains) + one RNA alone
 SPECS = [(None, "....((((....))))" + "." * 17), (None, "....[[[[" + "." * 12 + "]]]]" + "." * 9), ("." * 40 + "U", None)]
@@ -471,14 +467,6 @@ def test_rdesign_model_designs_with_states():
     assert _bytes(m.score_sequences(X, mask, seqs, lengths=MODEL_LENGTHS)[0]) == _bytes(nll)
     with pytest.raises(ValueError, match="group 1"):
         m.design(X, mask, n_samples=1, lengths=MODEL_LENGTHS, states=[1, 2])
-
-
-def _write_data(root, ids, lens):
-    from rnampnn.utils import synth
-    os.makedirs(root / "coords"); os.makedirs(root / "seqs")
-    for i, (rid, n) in enumerate(zip(ids, lens)):
-        np.save(root / "coords" / f"{rid}.npy", synth.synth_rna(n, 40 + i, seed=3))
-        (root / "seqs" / f"{rid}.fasta").write_text(f">{rid}\n" + "".join("AUCG"[v] for v in synth.synth_labels(n, 40 + i, seed=3)) + "\n")
 
 
 def test_predict_cli_with_a_states_file(tmp_path):

@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""Every output of the design wrappers on the batches of the GPU tests, as .npy files: the byte comparison of two builds of the library
+(docs/experiments.md, "the design family folded").  Plain dumping - no timing, no profiler, no retry.
+usage: python tools/design_dump.py <outdir>            one child process per family (design tied gc count distinct), each under its own
+                                                       `timeout`, stopping at the first that fails; then the number of dumps, their size
+                                                       and one sha256 over all of them
+       python tools/design_dump.py <outdir> <family>   that family, in this process
+RNAMPNN_PROBE_ROOT: another checkout (with its library built) to take the package from, as in tools/design_probe.py - the batches always
+come from THIS checkout's tests/, and only API that the parent of this tool's commit has is used.  Compare two runs with
+`diff -r <outdir a> <outdir b>` or by the printed sha256.
+Per family the `host_case()` / `case_arrays()` batch of its GPU test file, every constraint variant that file defines, temperatures 1.0,
+0.3 and 1e-3, the padded and the packed layout, the file's seed (above 2^32); tied: STATES with its weights and one state per group;
+gc: the case's windows as fractions, 40..60 % and the free window; count: caps 8 and T; distinct: S = 8 and 64, "sample" and "best".
+With every set of draws the `seq_nll` that `score_logits` gives for it."""
+import hashlib
+import os
+import subprocess
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.environ.get("RNAMPNN_PROBE_ROOT") or os.path.join(HERE, "..")
+FAMILIES = ("design", "tied", "gc", "count", "distinct")
+TEMPERATURES = (1.0, 0.3, 1e-3)
+
+
+def dump_family(outdir: str, family: str) -> None:
+    sys.path.insert(0, os.path.join(ROOT, "rna-mpnn_amd"))
+    import numpy as np
+    import torch
+    from rnampnn import _native
+    from rnampnn.model import decode as D
+    from rnampnn.utils.constraints import DesignConstraints
+    assert os.path.realpath(_native.__file__).startswith(os.path.realpath(ROOT)), (_native.__file__, ROOT)
+    _native.lib()
+    sys.path.insert(0, os.path.join(HERE, "..", "tests"))               # (the package is imported: these only add the batches)
+    os.makedirs(outdir, exist_ok=True)
+
+    def save(tag, names, outs, logits_kw):
+        outs = list(outs)
+        outs.append(D.score_logits(seqs=outs[0], want=("seq_nll",), **logits_kw)["seq_nll"])
+        for name, t in zip(tuple(names) + ("score_seq_nll",), outs):
+            np.save(os.path.join(outdir, f"{family}.{tag}.{name}.npy"), t.cpu().numpy())
+
+    def layouts(h, T):
+        dev = {k: torch.from_numpy(h[k]).cuda() for k in ("logits", "mask", "packed", "cu")}
+        return (("padded", dict(logits=dev["logits"], mask=dev["mask"])), ("packed", dict(logits=dev["packed"], cu_seqlens=dev["cu"], max_len=T)))
+
+    def constraints(h, bias, wobble):
+        return DesignConstraints(torch.from_numpy(h["allowed"]), torch.from_numpy(h["partner"]), None if bias is None else torch.from_numpy(bias),
+                                 wobble).to_device("cuda")
+
+    triple = ("seqs", "seq_nll", "infeasible")
+    if family in ("design", "tied"):
+        mod = __import__("test_design_gpu" if family == "design" else "test_design_tied_gpu")
+        h = mod.host_case()
+        variants = {name: constraints(h, None if v["bias"] is None else h[v["bias"]], v["wobble"]) for name, v in mod.VARIANTS.items()}
+        variants["free"] = None
+        one = [1] * h["B"]
+        states = {"rows": dict(), "one": dict(states=one)} if family == "design" else {
+            "states": dict(states=mod.STATES, state_weights=torch.from_numpy(h["weight"]).cuda()), "one": dict(states=one)}
+        for vname, cons in variants.items():
+            for temperature in TEMPERATURES:
+                for lname, kw in layouts(h, mod.T):
+                    for sname, skw in states.items():
+                        out = D.design_from_logits(n_samples=mod.S, temperature=temperature, seed=mod.SEED, constraints=cons, **kw, **skw)
+                        save(f"{vname}.t{temperature:g}.{lname}.{sname}", triple, out, kw)
+    elif family == "gc":
+        import _design_gc_ref as G
+        h = G.case_arrays()
+        n = np.maximum(np.array(G.CASE_LENGTHS, dtype=np.float64), 1.0)
+        case_window = torch.from_numpy(np.stack([h["lo"] / n, h["hi"] / n], axis=1)).cuda()     # (not read back: the kernel clamps it)
+        windows = {"case": case_window, "40-60": (0.4, 0.6), "all": (0.0, 1.0)}
+        variants = {"cons": constraints(h, None, True), "bias": constraints(h, G.CASE_BIAS, True), "free": None}
+        for vname, cons in variants.items():
+            for temperature in TEMPERATURES:
+                for lname, kw in layouts(h, G.CASE_T):
+                    for wname, window in windows.items():
+                        out = D.design_gc_from_logits(n_samples=G.CASE_S, temperature=temperature, seed=G.CASE_SEED, constraints=cons,
+                                                      gc_content=window, **kw)
+                        save(f"{vname}.t{temperature:g}.{lname}.{wname}", triple + ("gc_count", "gc_miss"), out, kw)
+    elif family == "count":
+        import _design_count_ref as R
+        h = R.case_arrays()
+        counted = torch.from_numpy(h["counted"]).cuda()
+        window = torch.from_numpy(np.stack([h["lo"], h["hi"]], axis=1)).cuda()
+        variants = {"cons": constraints(h, None, R.CASE_WOBBLE), "wobble": constraints(h, None, True), "free": None}
+        for vname, cons in variants.items():
+            for temperature in TEMPERATURES:
+                for lname, kw in layouts(h, R.CASE_T):
+                    for cap in R.CASE_CAPS:
+                        out = D.design_count_from_logits(n_samples=R.CASE_S, temperature=temperature, seed=R.CASE_SEED, constraints=cons,
+                                                         counted=counted, window=window, cap=cap, **kw)
+                        save(f"{vname}.t{temperature:g}.{lname}.cap{cap}", triple + ("count", "count_miss"), out, kw)
+    elif family == "distinct":
+        import _design_distinct_ref as X
+        h = X.case_arrays()
+        variants = {"cons": constraints(h, None, True), "nowobble": constraints(h, None, False), "free": None}
+        for vname, cons in variants.items():
+            for temperature in TEMPERATURES:
+                for lname, kw in layouts(h, X.CASE_T):
+                    for S in (8, 64):
+                        for mode in ("sample", "best"):
+                            out = D.design_distinct_from_logits(n_samples=S, temperature=temperature, seed=X.CASE_SEED, constraints=cons,
+                                                                mode=mode, **kw)
+                            save(f"{vname}.t{temperature:g}.{lname}.S{S}.{mode}", triple + ("logp", "n_distinct"), out, kw)
+    else:
+        raise SystemExit(f"unknown family {family!r}: choose from {FAMILIES}")
+    torch.cuda.synchronize()
+    print(f"{family}: dumped from {os.path.realpath(_native.LIB_PATH)}")
+
+
+def main() -> int:
+    if len(sys.argv) < 2:
+        raise SystemExit(__doc__)
+    outdir = os.path.abspath(sys.argv[1])
+    if len(sys.argv) > 2:
+        dump_family(outdir, sys.argv[2])
+        return 0
+    for family in FAMILIES:
+        rc = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), outdir, family]).returncode
+        if rc != 0:
+            print(f"{family}: exit status {rc}; nothing further is started")
+            return rc
+    files = sorted(f for f in os.listdir(outdir) if f.endswith(".npy"))
+    digest, size = hashlib.sha256(), 0
+    for f in files:
+        data = open(os.path.join(outdir, f), "rb").read()
+        digest.update(f.encode() + b"\0" + data)
+        size += len(data)
+    print(f"{len(files)} dumps, {size} bytes, sha256 {digest.hexdigest()}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
