@@ -6,7 +6,8 @@ Tolerances: f32 kernels |dlogit| <= 1e-4 and identical ar
 near-ties; bf16 kernels: SURVEY's 5e-2 is 70 % of the logit spread at random init (std ~ 0.07), so the bound used here
 is relative to the spread - max(3e-2, 5 % of the std of the reference logits) - and the second half of the criterion
 (argmax agreement / recovery within +-0.5 pt on SEPARATED logits) is asserted on trained weights in
-tests/test_configs_gpu.py::test_trained_weights_bf16_tracks_f32_oracle.
+tests/test_configs_gpu.py::test_trained_weights_bf16_tracks_f32_oracle and, with every tap, at scaled closed-form weights
+(logit std 3 .. 9, saturated GELUs, peaked attention) in tests/test_weight_regimes_gpu.py.
 """
 import numpy as np
 import pytest
