@@ -8,7 +8,7 @@
 // Same mathematics, data layouts and weight images as k_mpnn_bf16 (kernels_bf16.hip: transposed per-edge Linears on
 // v_mfma_f32_32x32x16_f16, accumulator tile -> operand of the next Linear, un-transposed last message Linear).  What differs:
 //   * a wave runs plain program order on ONE accumulator tile - the 8 dependent MFMAs of a chain, then that tile's activation arithmetic -
-//     instead of the hand-placed MFMA / VALU interleave over two tiles; the two waves of a SIMD overlap the phases (what that buys and what it
+//     instead of the hand-placed MFMA / VALU interleave over two tiles; the three (EMBED: two) waves of a SIMD overlap the phases (what that buys and what it
 //     does not: tools/ubench/mfma_valu_coexec.hip - the SIMD arbitrates oldest wave first, a stagger or per-phase s_setprio changes nothing, a
 //     workgroup barrier per phase is slower);
 //   * every per-row constant that k_mpnn_bf16 adds with helper MFMAs (32 of its 160 per block) enters without the matrix pipe: the P row of the
@@ -22,7 +22,14 @@
 // this kernel (RM_EXP_*, wrong results): no Q gathers 154, no e stores 152, no e loads / stores 145, no activation arithmetic 145, no MFMA 128,
 // memory skeleton only 123 - 127, compute only (no e / Q traffic) 135; of the compute-only 135: no LDS weight / init reads 100, no MFMA 85, no
 // activation arithmetic 98.  Its issue slots per block - ~1,115 vector instructions x 4.3 cycles, 128 MFMA x 8, 184 LDS reads x 4.5 - are 77 % of
-// the compute-only time: the kernel is bound by instruction issue; three waves per SIMD (RM_WAVES=12, <= 168 VGPRs, 9 - 14 spilled) are slower.
+// the compute-only time: the kernel is bound by instruction issue.
+// THREE WAVES PER SIMD.  With per-lane 64-bit addresses the 12-wave form (<= 168 VGPRs) spilled 9 - 14 registers and was slower (176 - 180 us).  With
+// the wave-uniform part of every address in scalar registers (ADDRESSING below) <edge, message>, <message> and <edge> need 166 / 162 / 138 VGPRs
+// and run 12 waves without scratch; the EMBED variant (236) stays at 8 (profiles/resmpnn_three_waves_resource_usage.txt).  Measured (C2, one box,
+// interleaved, 6 rounds, profiles/resmpnn_three_waves_ab_table.txt): 2.289 - 2.299 ms per forward before, 2.262 - 2.277 with it, 2.269 - 2.297 for the
+// new addressing at 8 waves; per <edge, message> launch 161.0 -> 158.2 us live, 168.7 -> 160.0 us under rocprofv3.  Results are bit-identical.  The
+// third wave buys overlap (SQ_BUSY_CYCLES -7 %, MFMA / VALU co-execution +35 %), not arithmetic: compute alone is 134 - 138 us at either wave count,
+// the LDS weight reads do not get cheaper with more waves (docs/experiments.md R13.1).
 // SWEEP DIRECTION: a launch walks its blocks ascending or descending (kernel argument `reverse`; the dealing scheme works on a logical block id, one
 // scalar translation gives the physical one), and a forward alternates the direction from launch to launch.  e (239 MiB at C2) is updated in place and
 // exceeds the 256 MiB Infinity Cache together with the node tables; swept the same way every time, no e line survives from its write to its next read.
@@ -44,24 +51,55 @@ static_assert(RN_E_F16 == 1 && RN_P_F16 == 1, "k_resmpnn works on f16 e and f16 
 #error "experimental variants of k_resmpnn need -DRN_EXPERIMENTS (tools/build_mpnn_variant.sh)"
 #endif
 
-#ifndef RM_WAVES
-#define RM_WAVES 8                 // waves per workgroup (one workgroup per CU).  Measured at C2 (tools/ab_mpnn.sh, one box): 8 waves 155 - 158 us per
-#endif                             // launch, 12 waves (<= 168 VGPRs: the compiler spills 9 - 14) 176 - 180 us, the round-3 kernel 161 - 164 us
-#if RM_WAVES <= 8 && !defined(RM_QROLL)
-#define RM_QFULL 1                 // 256 VGPRs per wave: all four channel blocks of a gathered Q row one MLP phase ahead (-2 % against two chains ahead)
+// Waves per workgroup (one workgroup per CU) are a template parameter NW of the kernel, chosen per instantiation: 12 (three per SIMD, <= 168
+// VGPRs) where the instantiation fits that budget without scratch, 8 (two per SIMD, <= 256 VGPRs) where it does not - the EMBED variant.  The
+// register counts of every instantiation at both wave counts: profiles/resmpnn_three_waves_resource_usage.txt.
+// -DRM_WAVES=<n> (experiments) forces one wave count on every instantiation.
+#ifdef RM_WAVES
+#define RM_NW_PLAIN RM_WAVES
+#define RM_NW_EMBED RM_WAVES
+#else
+#define RM_NW_PLAIN 12             // <edge, message>, <message>, <edge>
+#define RM_NW_EMBED 8              // <message, EMBED>: 236 VGPRs
+#endif
+// Q prefetch: with 256 VGPRs per wave (NW <= 8) all four channel blocks of a gathered Q row are requested one MLP phase ahead (-2 % against two
+// chains ahead); with 168 (NW = 12) the rolling two-chains-ahead form (16 registers instead of 32).  -DRM_QROLL: the rolling form at any NW.
+#ifdef RM_QROLL
+#define RM_QFULL(NW) false
+#else
+#define RM_QFULL(NW) ((NW) <= 8)
 #endif
 #define RM_LDS_P 131072                              // per wave: [P_e f32 128][P_m f32 128]
-#define RM_LDS_BE (RM_LDS_P + RM_WAVES * 1024)       // bias of the edge MLP's second Linear, f32, accumulator order (MpnnWB::b2p)
-#define RM_LDS_BM (RM_LDS_BE + 512)                  // bias of the message MLP's second Linear as a splat f16 pair per channel
-#define RM_LDS_GB (RM_LDS_BM + 512)                  // GELU(bias) of that Linear as the epilogue computes it (f32)
-#define RM_LDS_Z (RM_LDS_GB + 512 + 128)             // 512 zero bytes: accumulator init of absent edges (= 128 mod 256: banks 32.. of the
+#define RM_LDS_BE(NW) (RM_LDS_P + (NW) * 1024)       // bias of the edge MLP's second Linear, f32, accumulator order (MpnnWB::b2p)
+#define RM_LDS_BM(NW) (RM_LDS_BE(NW) + 512)          // bias of the message MLP's second Linear as a splat f16 pair per channel
+#define RM_LDS_GB(NW) (RM_LDS_BM(NW) + 512)          // GELU(bias) of that Linear as the epilogue computes it (f32)
+#define RM_LDS_Z(NW) (RM_LDS_GB(NW) + 512 + 128)     // 512 zero bytes: accumulator init of absent edges (= 128 mod 256: banks 32.. of the
                                                      // row, which no P / bias read of the same instruction touches)
-#define RM_LDS_CTR (RM_LDS_Z + 512)                  // block-dealing counter of the workgroup
-#define RM_LDS_B0 (RM_LDS_CTR + 16)                  // EMBED: bias of the edge embedding's first Linear (a b0), natural channel order
-#define RM_LDS_BYTES (RM_LDS_B0 + 512)
-static_assert(RM_LDS_Z % 256 == 128 && RM_LDS_BYTES <= 160 * 1024, "LDS layout");
+#define RM_LDS_CTR(NW) (RM_LDS_Z(NW) + 512)          // block-dealing counter of the workgroup
+#define RM_LDS_B0(NW) (RM_LDS_CTR(NW) + 16)          // EMBED: bias of the edge embedding's first Linear (a b0), natural channel order
+#define RM_LDS_BYTES(NW) (RM_LDS_B0(NW) + 512)
+static_assert(RM_LDS_Z(RM_NW_PLAIN) % 256 == 128 && RM_LDS_BYTES(RM_NW_PLAIN) <= 160 * 1024, "LDS layout");
+static_assert(RM_LDS_Z(RM_NW_EMBED) % 256 == 128 && RM_LDS_BYTES(RM_NW_EMBED) <= 160 * 1024, "LDS layout");
 
-__device__ __forceinline__ u32x4* rm_efrag(bf16_t* e, int blk, int lane) { return reinterpret_cast<u32x4*>(e) + (size_t)blk * 512 + lane; }
+// ADDRESSING.  Every global access of k_resmpnn is "wave-uniform 64-bit base + unsigned 32-bit lane offset": the base - the kernel argument plus
+// the block's byte offset, formed from readfirstlane'd block ids with scalar arithmetic once per block - stays in an SGPR pair, and the
+// instruction gets one 32-bit offset register and an immediate (the global_* saddr form) instead of a 64-bit address pair per lane.  The
+// lane offsets fit 32 bits: a block's e fragments are 8 KiB, a P / h / agg row 256 - 512 B, a Q or geometry row index is at most Nmax, and
+// nbr holds ntot * k * 4 <= 0x3fffffff bytes (begin_run).  The e block offset (block x 8 KiB) does not: it is part of the 64-bit scalar base.
+// (the empty asm makes the scalar base opaque: without it the optimiser re-associates the loop-invariant lane part with the argument, hoists
+// that 64-bit per-lane pointer out of the block loop and adds the block offset to it with vector arithmetic - the form this replaces.  The
+// pointer goes through it, and comes back, in the global address space: behind an opaque value nothing else tells global from flat)
+#define RM_GLOBAL __attribute__((address_space(1)))
+template <class T> __device__ __forceinline__ RM_GLOBAL T* rm_at(T* ubase, unsigned lane_bytes) {
+    RM_GLOBAL const char* g = (RM_GLOBAL const char*)ubase;
+    asm("" : "+s"(g));
+    return (RM_GLOBAL T*)(g + lane_bytes);
+}
+// fragment s of block ublk (a wave-uniform id): two scalar bases 4 KiB apart, so that every fragment is within the immediate offset's range
+// (l16: the lane's 16 bytes of a fragment, 16 * lane)
+__device__ __forceinline__ RM_GLOBAL u32x4* rm_efrag(bf16_t* e, int ublk, unsigned l16, int s) {
+    return rm_at(reinterpret_cast<u32x4*>(e) + (size_t)ublk * 512 + (s >> 2) * 256, l16) + 64 * (s & 3);
+}
 __device__ __forceinline__ f32x16 rm_ld16(const unsigned char* smem, unsigned off) {      // 4 x ds_read_b128
     const f32x4* p = reinterpret_cast<const f32x4*>(smem + off);
     const f32x4 a = p[0], b = p[1], c = p[2], d = p[3];
@@ -86,8 +124,8 @@ __device__ __forceinline__ f16x4 rm_h4(unsigned w0, unsigned w1) {
 #ifdef RM_EXP_NOGELU
 #define phi4s(y) (y)
 #endif
-template <bool DO_EDGE, bool DO_MSG, bool EMBED = false>
-__global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInfo pk, int k, int reverse, const int* __restrict__ nbr, bf16_t* __restrict__ e,
+template <int NW, bool DO_EDGE, bool DO_MSG, bool EMBED = false>
+__global__ void __launch_bounds__(NW * 64, NW / 4) k_resmpnn(PackInfo pk, int k, int reverse, const int* __restrict__ nbr, bf16_t* __restrict__ e,
         const bf16_t* __restrict__ p_e, const bf16_t* __restrict__ q_e, const bf16_t* __restrict__ p_m, const bf16_t* __restrict__ q_m,
         const float* __restrict__ h_res, const bf16_t* __restrict__ img_e_g, const float* __restrict__ b2e,
         const bf16_t* __restrict__ img_m_g, const float* __restrict__ b2m, float* __restrict__ agg,
@@ -96,8 +134,13 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
     extern __shared__ __attribute__((aligned(256))) unsigned char smem[];
     u32x4* img_e = reinterpret_cast<u32x4*>(smem);
     u32x4* img_m = img_e + 4096;
-    constexpr int NW = RM_WAVES;
+    constexpr bool QFULL = RM_QFULL(NW);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
+    // the lane offsets of the block-based accesses.  They pass through an empty asm at the top of every block (RM_LANE_OFFSETS: no instruction, the
+    // registers stay where they are): a loop-invariant `16 * lane` is widened to 64 bits OUTSIDE the block loop, and instruction selection,
+    // which works basic block by basic block, then no longer sees a 32-bit offset to put beside the scalar base
+    unsigned l16 = 16u * lane, l4 = 4u * lane, r4 = 4u * r;
+#define RM_LANE_OFFSETS() asm volatile("" : "+v"(l16), "+v"(l4), "+v"(r4))
     const int ntot = pk.cu[pk.B];
     const int nblocks = ntot;                            // one residue per block
     const int zero_row = pk.Nmax;
@@ -129,7 +172,7 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
     }
     const int mirror = lo + blk_end - 1;
     auto phys = [&](int b) -> int { return __builtin_amdgcn_readfirstlane(reverse ? mirror - b : b); };      // (b: a wave-uniform logical id in [lo, blk_end))
-    int* lds_ctr = reinterpret_cast<int*>(smem + RM_LDS_CTR);
+    int* lds_ctr = reinterpret_cast<int*>(smem + RM_LDS_CTR(NW));
     auto claim_issue = [&]() -> int {                    // lane 0 draws the ordinal ...
         int v = 0;
         if (lane == 0) v = __hip_atomic_fetch_add(lds_ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -147,27 +190,27 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
     const int b0 = __builtin_amdgcn_readfirstlane(blk < blk_end ? (reverse ? mirror - blk : blk) : 0);
     if (nblocks > 0) {
         const int i0 = b0 * k + r;
-        jraw = nbr[i0 > last_idx ? last_idx : i0];
+        jraw = *rm_at(nbr, 4u * (unsigned)(i0 > last_idx ? last_idx : i0));
         if (!EMBED) {
 #pragma unroll
-            for (int s = 0; s < 8; ++s) ef[s] = rm_efrag(e, b0, lane)[64 * s];
+            for (int s = 0; s < 8; ++s) ef[s] = *rm_efrag(e, b0, l16, s);
         }
-        if (DO_EDGE) pn_e = reinterpret_cast<const unsigned*>(p_e + (size_t)b0 * RN_D)[lane];
-        if (DO_MSG) pn_m = reinterpret_cast<const unsigned*>(p_m + (size_t)b0 * RN_D)[lane];
+        if (DO_EDGE) pn_e = *rm_at(reinterpret_cast<const unsigned*>(p_e + (size_t)b0 * RN_D), l4);
+        if (DO_MSG) pn_m = *rm_at(reinterpret_cast<const unsigned*>(p_m + (size_t)b0 * RN_D), l4);
     }
     if (DO_EDGE) stage_image_dma<NW * 64>(img_e, reinterpret_cast<const u32x4*>(img_e_g), tid);
     if (EMBED) stage_image_dma<NW * 64, (4 * EMB_KS + 32) * 64>(img_e, reinterpret_cast<const u32x4*>(img_e_g), tid);      // [4 mb][7 s] first Linear | [4 ob][8 ks] second
     if (DO_MSG) stage_image_dma<NW * 64>(img_m, reinterpret_cast<const u32x4*>(img_m_g), tid);
-    if (EMBED && tid >= 256 + 64 && tid < 256 + 64 + 128) reinterpret_cast<float*>(smem + RM_LDS_B0)[tid - 320] = kGA * ee_b0[tid - 320];
+    if (EMBED && tid >= 256 + 64 && tid < 256 + 64 + 128) reinterpret_cast<float*>(smem + RM_LDS_B0(NW))[tid - 320] = kGA * ee_b0[tid - 320];
     if (tid < 128) {
-        reinterpret_cast<float*>(smem + RM_LDS_BE)[tid] = (DO_EDGE || EMBED) ? b2e[tid] : 0.f;       // (EMBED: the embedding's second bias, e-fragment row order)
+        reinterpret_cast<float*>(smem + RM_LDS_BE(NW))[tid] = (DO_EDGE || EMBED) ? b2e[tid] : 0.f;       // (EMBED: the embedding's second bias, e-fragment row order)
         const float bm = DO_MSG ? b2m[tid] : 0.f;            // (a b2: the images' biases are stored in the scaled activation domain)
         const f16x2 bh = cvt_h2(bm, bm);
-        reinterpret_cast<unsigned*>(smem + RM_LDS_BM)[tid] = __builtin_bit_cast(unsigned, bh);
+        reinterpret_cast<unsigned*>(smem + RM_LDS_BM(NW))[tid] = __builtin_bit_cast(unsigned, bh);
         const f16x2 ph = phi2s(bh);
-        reinterpret_cast<float*>(smem + RM_LDS_GB)[tid] = (float)bh[0] * (float)ph[0];      // exactly what a row of zeros contributes to the sum
+        reinterpret_cast<float*>(smem + RM_LDS_GB(NW))[tid] = (float)bh[0] * (float)ph[0];      // exactly what a row of zeros contributes to the sum
     } else if (tid < 256) {
-        reinterpret_cast<unsigned*>(smem + RM_LDS_Z)[tid - 128] = 0u;
+        reinterpret_cast<unsigned*>(smem + RM_LDS_Z(NW))[tid - 128] = 0u;
     } else if (tid == 256) {
         *lds_ctr = 2 * NW;
     }
@@ -175,7 +218,7 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
     __syncthreads();
     if (blk >= blk_end) return;
 
-    const unsigned off_pe = RM_LDS_P + wave * 1024 + 64 * h, off_pm = off_pe + 512, off_be = RM_LDS_BE + 64 * h;
+    const unsigned off_pe = RM_LDS_P + wave * 1024 + 64 * h, off_pm = off_pe + 512, off_be = RM_LDS_BE(NW) + 64 * h;
     float* lds_pw = reinterpret_cast<float*>(smem + RM_LDS_P + wave * 1024);
     auto stage_p = [&]() {                                    // this block's P rows: f16 words as loaded -> f32, natural channel order
         if (DO_EDGE) {
@@ -213,7 +256,7 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
     auto gather_q = [&](auto cbc, const bf16_t* table, int jj) {
         constexpr int cb = decltype(cbc)::value;
         const int row = jj >= 0 ? (jj > zero_row ? zero_row : jj) : zero_row;
-        const u32x4* src = reinterpret_cast<const u32x4*>(table + (size_t)row * RN_D + 32 * cb + 16 * h);
+        const auto* src = rm_at(reinterpret_cast<const u32x4*>(table), (unsigned)row * (2u * RN_D) + 32u * h) + 4 * cb;     // (table base | row, lane half | channel block)
 #ifdef RM_EXP_NOQ
         (void)src; q[2 * cb] = u32x4{0u, 0u, 0u, 0u}; q[2 * cb + 1] = u32x4{0u, 0u, 0u, 0u};
 #else
@@ -248,13 +291,9 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
         asm volatile("" : "+v"(T) :: "memory");
     };
     auto no_extra = [](auto) {};
-#ifdef RM_QFULL       /* all four channel blocks of a Q row one MLP phase ahead (32 registers) instead of two chains ahead (16) */
-#define RM_GQ_ROLL(cb, tab, jj) do { } while (0)
-#define RM_GQ_FULL(tab, jj) do { gather_q(std::integral_constant<int, 0>{}, tab, jj); gather_q(std::integral_constant<int, 1>{}, tab, jj); gather_q(std::integral_constant<int, 2>{}, tab, jj); gather_q(std::integral_constant<int, 3>{}, tab, jj); } while (0)
-#else
-#define RM_GQ_ROLL(cb, tab, jj) gather_q(cb, tab, jj)
-#define RM_GQ_FULL(tab, jj) do { } while (0)
-#endif
+    // QFULL: all four channel blocks of a Q row one MLP phase ahead (32 registers); otherwise two chains ahead (16)
+#define RM_GQ_ROLL(cb, tab, jj) do { if constexpr (!QFULL) gather_q(cb, tab, jj); } while (0)
+#define RM_GQ_FULL(tab, jj) do { if constexpr (QFULL) { gather_q(std::integral_constant<int, 0>{}, tab, jj); gather_q(std::integral_constant<int, 1>{}, tab, jj); gather_q(std::integral_constant<int, 2>{}, tab, jj); gather_q(std::integral_constant<int, 3>{}, tab, jj); } } while (0)
     // ---- epilogues.  All four quarter tiles are converted first (T is dead after 8 instructions), then the accumulator init of the NEXT chain
     // is requested into T (next_init: LDS byte offset of this lane's 64 bytes, or < 0: none) and lands under the activation arithmetic.
     auto cvt_tile = [&](f16x4 (&x)[4], int next_init) {
@@ -292,7 +331,7 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
             ef[2 * ob + sp][t] = __builtin_bit_cast(unsigned, __builtin_elementwise_fma(lo2(x[v]), lo2(ph), __builtin_bit_cast(f16x2, o0)));
             ef[2 * ob + sp][t + 1] = __builtin_bit_cast(unsigned, __builtin_elementwise_fma(hi2(x[v]), hi2(ph), __builtin_bit_cast(f16x2, o1)));
 #ifndef RM_EXP_NOESTORE
-            if (v & 1) rm_efrag(e, gblk, lane)[64 * (2 * ob + sp)] = ef[2 * ob + sp];
+            if (v & 1) *rm_efrag(e, gblk, l16, 2 * ob + sp) = ef[2 * ob + sp];
 #endif
         }
         RM_EFENCE();
@@ -301,8 +340,8 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
     // real edges.  Every row is summed unmasked; a row of an absent edge holds exactly GELU(bias) and is taken out again in closed form.
     auto epi_mean = [&](auto nbc, int next_init, int gblk, float cabs, float inv, float hres) {
         constexpr int nb = decltype(nbc)::value;
-        const unsigned bw = reinterpret_cast<const unsigned*>(smem + RM_LDS_BM)[32 * nb + r];
-        const float gbv = reinterpret_cast<const float*>(smem + RM_LDS_GB)[32 * nb + r];
+        const unsigned bw = reinterpret_cast<const unsigned*>(smem + RM_LDS_BM(NW))[32 * nb + r];
+        const float gbv = reinterpret_cast<const float*>(smem + RM_LDS_GB(NW))[32 * nb + r];
         f16x4 x[4];
         cvt_tile(x, next_init);
         const f16x4 bh = rm_h4(bw, bw);
@@ -319,14 +358,14 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
         float sum = s0 + s1;
         sum += __shfl_xor(sum, 32, 64);
         // both lane halves hold the total: the duplicate store of half 1 saves a divergent branch
-        agg[(size_t)gblk * RN_D + 32 * nb + r] = fmaf(sum - cabs * gbv, inv, hres);
+        rm_at(agg + (size_t)gblk * RN_D, r4)[32 * nb] = fmaf(sum - cabs * gbv, inv, hres);
         RM_EFENCE();
     };
 
     // EMBED: the neighbour's half-split geometry record (28 floats of the items this lane half owns; kernels_f32.hip: geomh_record)
     f32x4 nrec[7];
     auto load_rec = [&](int jj) {
-        const f32x4* src = reinterpret_cast<const f32x4*>(geomh + (size_t)(jj >= 0 ? jj : 0) * RN_GEOMH + 32 * h);
+        const auto* src = rm_at(reinterpret_cast<const f32x4*>(geomh), (unsigned)(jj >= 0 ? jj : 0) * (4u * RN_GEOMH) + 128u * h);
 #pragma unroll
         for (int v = 0; v < 7; ++v) nrec[v] = src[v];
     };
@@ -335,14 +374,14 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
     if constexpr (EMBED) load_rec(j);
     gather_q(std::integral_constant<int, 0>{}, DO_EDGE ? q_e : q_m, j);
     gather_q(std::integral_constant<int, 1>{}, DO_EDGE ? q_e : q_m, j);
-#ifdef RM_QFULL
-    gather_q(std::integral_constant<int, 2>{}, DO_EDGE ? q_e : q_m, j);
-    gather_q(std::integral_constant<int, 3>{}, DO_EDGE ? q_e : q_m, j);
-#endif
+    if constexpr (QFULL) {
+        gather_q(std::integral_constant<int, 2>{}, DO_EDGE ? q_e : q_m, j);
+        gather_q(std::integral_constant<int, 3>{}, DO_EDGE ? q_e : q_m, j);
+    }
     stage_p();
 #pragma unroll
     for (int s = 0; s < RM_RING; ++s) wf[s] = RM_FRAG(C_FIRST, s);
-    if constexpr (!EMBED) T = rm_ld16(smem, j >= 0 ? (DO_EDGE ? off_pe : off_pm) : (unsigned)RM_LDS_Z);
+    if constexpr (!EMBED) T = rm_ld16(smem, j >= 0 ? (DO_EDGE ? off_pe : off_pm) : (unsigned)RM_LDS_Z(NW));
     RM_FENCE();
 
 #ifdef RM_EXP_STAGGER      /* experiment: delay the second-dispatched half of the workgroup (waves that share SIMDs with the first half) */
@@ -354,25 +393,26 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
     while (true) {
         const int nblk = nxt;
         const int claim_v = claim_issue();
+        RM_LANE_OFFSETS();
         const bool has_next = nblk < blk_end;
         const int pblk = phys(blk);                        // physical ids: every memory index below
         const int nb_c = phys(has_next ? nblk : blk);      // the last iteration re-reads its own block (results unused)
         const int in_ = nb_c * k + r;
-        const int jn_raw = nbr[in_ > last_idx ? last_idx : in_];
-        if (DO_EDGE) pn_e = reinterpret_cast<const unsigned*>(p_e + (size_t)nb_c * RN_D)[lane];
-        if (DO_MSG) pn_m = reinterpret_cast<const unsigned*>(p_m + (size_t)nb_c * RN_D)[lane];
+        const int jn_raw = *rm_at(nbr, 4u * (unsigned)(in_ > last_idx ? last_idx : in_));
+        if (DO_EDGE) pn_e = *rm_at(reinterpret_cast<const unsigned*>(p_e + (size_t)nb_c * RN_D), l4);
+        if (DO_MSG) pn_m = *rm_at(reinterpret_cast<const unsigned*>(p_m + (size_t)nb_c * RN_D), l4);
         const bool valid = j >= 0;
         const unsigned vmask = (unsigned)(__ballot(valid) & 0xffffffffull);
         const int cnt = __popc(vmask);
         const float cabs = (float)(32 - cnt);
         const float inv = cnt > 0 ? kGAi * __builtin_amdgcn_rcpf((float)cnt) : 0.f;      // (the summed messages are a m)
-        const int a_pe = valid ? (int)off_pe : RM_LDS_Z, a_pm = valid ? (int)off_pm : RM_LDS_Z, a_be = valid ? (int)off_be : RM_LDS_Z;
+        const int a_pe = valid ? (int)off_pe : RM_LDS_Z(NW), a_pm = valid ? (int)off_pm : RM_LDS_Z(NW), a_be = valid ? (int)off_be : RM_LDS_Z(NW);
         const int jn = (slot_ok && nb_c < ntot) ? jn_raw : -1;   // (consumed from the message MLP on: its load has long landed by then)
-        const int a_next = jn >= 0 ? (int)(DO_EDGE ? off_pe : off_pm) : RM_LDS_Z;
+        const int a_next = jn >= 0 ? (int)(DO_EDGE ? off_pe : off_pm) : RM_LDS_Z(NW);
 #ifdef RM_EDB         /* the next block's e fragments a whole block ahead, in registers of their own (+32) */
         u32x4 efn[8];
 #pragma unroll
-        for (int s = 0; s < 8; ++s) efn[s] = rm_efrag(e, nb_c, lane)[64 * s];
+        for (int s = 0; s < 8; ++s) efn[s] = *rm_efrag(e, nb_c, l16, s);
 #endif
         using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
         using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
@@ -398,7 +438,7 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
                 epi_edge(I3{}, a_next, pblk);
                 RM_GQ_ROLL(I0{}, q_e, jn); RM_GQ_ROLL(I1{}, q_e, jn); RM_GQ_FULL(q_e, jn);
 #pragma unroll
-                for (int s = 0; s < 8; ++s) ef[s] = rm_efrag(e, nb_c, lane)[64 * s];
+                for (int s = 0; s < 8; ++s) ef[s] = *rm_efrag(e, nb_c, l16, s);
             }
         }
         if constexpr (EMBED) {
@@ -445,7 +485,7 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
             const unsigned emask = valid ? 0xffffffffu : 0u;
             static_for<4>([&](auto mbc) {                      // Linear(90, 128): T = a b0 + a W0 . features
                 constexpr int mb = decltype(mbc)::value;
-                T = rm_ld16(smem, RM_LDS_B0 + 128 * mb + 64 * h);
+                T = rm_ld16(smem, RM_LDS_B0(NW) + 128 * mb + 64 * h);
 #pragma unroll
                 for (int s7 = 0; s7 < EMB_KS; ++s7) T = mfma32h(img_e[(mb * EMB_KS + s7) * 64 + lane], xf[s7], T);
                 asm volatile("" : "+v"(T) :: "memory");
@@ -460,7 +500,7 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
             });
             static_for<4>([&](auto obc) {                      // Linear(128, 128) -> GELU -> e0 (rows in e-fragment order); absent edges and padding slots: zeros
                 constexpr int ob = decltype(obc)::value;
-                T = rm_ld16(smem, RM_LDS_BE + 128 * ob + 64 * h);
+                T = rm_ld16(smem, RM_LDS_BE(NW) + 128 * ob + 64 * h);
 #pragma unroll
                 for (int ks = 0; ks < 8; ++ks) T = mfma32h(img_e[(4 * EMB_KS + ob * 8 + ks) * 64 + lane], hb[ks], T);
                 asm volatile("" : "+v"(T) :: "memory");
@@ -471,7 +511,7 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
                     const int sp = v >> 1, t = 2 * (v & 1);
                     ef[2 * ob + sp][t] = __builtin_bit_cast(unsigned, lo2(g)) & emask;
                     ef[2 * ob + sp][t + 1] = __builtin_bit_cast(unsigned, hi2(g)) & emask;
-                    if (v & 1) rm_efrag(e, pblk, lane)[64 * (2 * ob + sp)] = ef[2 * ob + sp];
+                    if (v & 1) *rm_efrag(e, pblk, l16, 2 * ob + sp) = ef[2 * ob + sp];
                 }
                 RM_FENCE();
             });
@@ -486,7 +526,7 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
             // (k-step s of the last chain is the last reader of ef[s]: the next block's fragment is requested behind it)
             chain(std::integral_constant<int, 11>{}, [&](auto sc) {
 #if !defined(RM_EXP_NOELOAD) && !defined(RM_EDB)
-                if constexpr (!EMBED) { constexpr int s = decltype(sc)::value; ef[s] = rm_efrag(e, nb_c, lane)[64 * s]; }
+                if constexpr (!EMBED) { constexpr int s = decltype(sc)::value; ef[s] = *rm_efrag(e, nb_c, l16, s); }
 #endif
             });
             epi_first(I3{}, -1);
@@ -495,8 +535,9 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
             float hres[4] = {0.f, 0.f, 0.f, 0.f};
             if (h_res) {
 #pragma unroll
-                for (int nb = 0; nb < 4; ++nb) hres[nb] = h_res[(size_t)pblk * RN_D + 32 * nb + r];
+                for (int nb = 0; nb < 4; ++nb) hres[nb] = rm_at(h_res + (size_t)pblk * RN_D, r4)[32 * nb];
             }
+            asm volatile("" : "+v"(r4));                   // (as RM_LANE_OFFSETS: the agg stores are behind the branch above, in a basic block of their own)
             // message Linear 2, un-transposed: T[edge][channel] = hidden . W2_m^T
             chain(std::integral_constant<int, 12>{}, no_extra); RM_GQ_FULL(DO_EDGE ? q_e : q_m, jn); epi_mean(I0{}, -1, pblk, cabs, inv, hres[0]);
             chain(std::integral_constant<int, 13>{}, no_extra); epi_mean(I1{}, -1, pblk, cabs, inv, hres[1]);
@@ -524,6 +565,7 @@ __global__ void __launch_bounds__(RM_WAVES * 64, RM_WAVES / 4) k_resmpnn(PackInf
 #pragma unroll
         for (int v = 0; v < 7; ++v) asm volatile("" :: "v"(nrec[v]));
     }
+#undef RM_LANE_OFFSETS
 #undef RM_GQ_ROLL
 #undef RM_GQ_FULL
 #undef RM_EFENCE
@@ -542,7 +584,8 @@ void launch_resmpnn_bf16(const PackInfo& pk, int k, bool do_edge, bool do_msg, c
     reverse = 0;
 #endif
     const int max_blocks = pk.Nmax;
-    int grid = (max_blocks + RM_WAVES - 1) / RM_WAVES;
+    constexpr int NW = RM_NW_PLAIN;
+    int grid = (max_blocks + NW - 1) / NW;
     if (grid >= 8) grid = (grid + 7) & ~7;            // a multiple of 8 switches the kernel to its XCD-aware block mapping
     const int cus = rn_num_cus();
     if (grid > cus) grid = cus;
@@ -550,8 +593,8 @@ void launch_resmpnn_bf16(const PackInfo& pk, int k, bool do_edge, bool do_msg, c
 #define RM_LAUNCH(E, M)                                                                                        \
     do {                                                                                                       \
         static DevAttr attr;                                                                                   \
-        ensure_dyn_lds((const void*)k_resmpnn<E, M>, RM_LDS_BYTES, attr);                                      \
-        hipLaunchKernelGGL((k_resmpnn<E, M>), dim3(grid), dim3(RM_WAVES * 64), RM_LDS_BYTES, s, pk, k, reverse ? 1 : 0, nbr, e, p_e, q_e, p_m, \
+        ensure_dyn_lds((const void*)k_resmpnn<NW, E, M>, RM_LDS_BYTES(NW), attr);                              \
+        hipLaunchKernelGGL((k_resmpnn<NW, E, M>), dim3(grid), dim3(NW * 64), RM_LDS_BYTES(NW), s, pk, k, reverse ? 1 : 0, nbr, e, p_e, q_e, p_m, \
                            q_m, h_res, we.img, we.b2p, wm.img, wm.b2p, agg, (const float*)nullptr, (const float*)nullptr); \
     } while (0)
     if (do_edge && do_msg) RM_LAUNCH(true, true);
@@ -567,13 +610,14 @@ void launch_resmpnn_embed_bf16(const PackInfo& pk, int k, const int* nbr, bf16_t
 #ifdef RM_EXP_FWDSWEEP
     reverse = 0;
 #endif
-    int grid = (pk.Nmax + RM_WAVES - 1) / RM_WAVES;
+    constexpr int NW = RM_NW_EMBED;
+    int grid = (pk.Nmax + NW - 1) / NW;
     if (grid >= 8) grid = (grid + 7) & ~7;
     const int cus = rn_num_cus();
     if (grid > cus) grid = cus;
     if (grid < 1) grid = 1;
     static DevAttr attr;
-    ensure_dyn_lds((const void*)k_resmpnn<false, true, true>, RM_LDS_BYTES, attr);
-    hipLaunchKernelGGL((k_resmpnn<false, true, true>), dim3(grid), dim3(RM_WAVES * 64), RM_LDS_BYTES, s, pk, k, reverse ? 1 : 0, nbr, e, (const bf16_t*)nullptr,
+    ensure_dyn_lds((const void*)k_resmpnn<NW, false, true, true>, RM_LDS_BYTES(NW), attr);
+    hipLaunchKernelGGL((k_resmpnn<NW, false, true, true>), dim3(grid), dim3(NW * 64), RM_LDS_BYTES(NW), s, pk, k, reverse ? 1 : 0, nbr, e, (const bf16_t*)nullptr,
                        (const bf16_t*)nullptr, p_m, q_m, h_res, ee_img, ee_b1p, wm.img, wm.b2p, agg, geomh, ee_b0);
 }
