@@ -432,6 +432,50 @@ int rnampnn_design_distinct(const float* logits, int64_t n_rows, const float* ma
                             float temperature, int32_t S, uint64_t seed, const uint64_t* seed_dev, const uint8_t* allowed,
                             const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position, int32_t noise,
                             int8_t* seqs, float* seq_nll, int32_t* infeasible, float* logp, int32_t* n_distinct, void* stream);
+/* Design that avoids forbidden motifs in ONE launch (csrc/design_avoid.hip): the draws of rnampnn_design, conditioned EXACTLY on the sequence
+ * containing none of a set of substrings (no GGGG, no homopolymer run, no restriction site).  The set comes as an Aho-Corasick automaton with
+ * the failure links compiled out (rnampnn/utils/motifs.py builds it).  The arguments are those of rnampnn_design plus
+ *   delta (A,4) u8, device, non-null   delta[a,c] = the state after reading class c (AUCG = 0..3) in state a; state 0 is the start
+ *   n_states i32, host                 A, 1 .. RNAMPNN_DESIGN_AVOID_MAX_STATES = 64 (one lane of a wave per state)
+ *   terminal u64, host                 bit a set = a motif ends in state a; bits at and above A are ignored; bit 0 must be clear
+ * and the outputs, each nullable, are those of rnampnn_design plus
+ *   hits (S,B) i32         the positions of the written draw after which the automaton, following delta from state 0, is in a terminal state
+ *                          (for a delta built from motifs: the positions at which a motif ends)
+ *   avoid_miss (B) i32     1 when no admitted sequence of RNA b avoids the motifs, else 0; the same for every sample
+ * Extent, masks, bias, temperature, `allowed`, seed_dev and "an empty mask is drawn free and counts 1 in `infeasible`" are rnampnn_design's.
+ * All arithmetic is fp64: z_t(c) = ((double) logit_t(c) + (double) bias_t(c)) / (double) temperature; LSE and SELECT (weights exp(x - max over
+ * the admitted), the first whose running sum exceeds u24 * 2^-24 * total, else the last admitted) are rnampnn_design_gc's; m_t is the mask of t.
+ *   Live and dead.  A state is DEAD when its bit of `terminal` is set; a delta entry >= A is read as a dead state.  The other states are LIVE.
+ *   Backward.  l_n(a) = 0 for a live a.  For t = n-1 .. 0 and a live a: l_t(a) = LSE over the classes c in class order of
+ *     z_t(c) + l_{t+1}(delta(a,c)), a cell being admitted iff m_t has c and delta(a,c) is live.  l of a dead state is -inf.
+ *   Feasibility.  avoid_miss[b] = !(l_0(0) > -inf) (a NaN counts as not above -inf); an RNA of length 0 is feasible.
+ *   Draw of sample s, feasible RNA.  a = 0; for t = 0 .. n-1: the admitted cells are those above that also have l_{t+1}(delta(a,c)) > -inf;
+ *     c = SELECT over z_t(c) + l_{t+1}(delta(a,c)) with the uniform u24(seed, s, b, t) of rnampnn_design; a <- delta(a,c).  Every hits is 0.
+ *   Infeasible RNA (avoid_miss = 1).  Every position is drawn as rnampnn_design draws an unpaired position in fp64, with the same uniform,
+ *     ignoring the motifs; `hits` reports what the draw contains.  (Counting follows delta through dead states; after an entry >= A, which
+ *     counts, it goes on from state 0.)
+ *   Base pairs.  A non-null `partner` is RNAMPNN_ERR_UNSUPPORTED: a pair couples two distant positions, so an exact chain over (position,
+ *     state) would have to carry the class of every open pair in its state - 4^depth states.  That is not built; fixed / IUPAC sets, omitted
+ *     letters and either bias all combine with the motifs.
+ * seq_nll is byte for byte rnampnn_score's for the written draw.  One 256-thread workgroup per RNA: the rows in LDS, one wave (lane = state)
+ * runs the backward pass into an LDS table of the live states, then 64 samples at a time walk forward, one lane each.  Dynamic LDS, with
+ * L = the live states among 0 .. A-1:
+ *       bytes(T, L) = (32 + 8 L) T + 256 (ceil(T / 16) | 1) + 16 ceil(T / 16) + 864
+ *     (the fp64 rows, the table, 2 bits per position for 64 samples, the masks; the automaton, the hit counts and the reduction's scratch):
+ *     20,704 at (T = 128, L = 13), 46,832 at (300, 13).  RNAMPNN_ERR_UNSUPPORTED when that exceeds 160 KiB = 163,840 bytes; the message names
+ *     the bytes, the limit and the largest T at that automaton: T <= 2857 at L = 1, 1064 at L = 13 (no run longer than 3), 532 at L = 32,
+ *     290 at L = 64.  A table in global memory for longer RNAs is not built.
+ * No workspace, no atomics, no runtime fill / copy node, no host synchronisation: two calls give identical bytes, the call can sit inside a
+ * captured graph, and a draw is a pure function of (seed, s, b), the rows of RNA b and the automaton - independent of B, T, S and the layout;
+ * the first S' of S slots are the call with S'.  RNAMPNN_ERR_BAD_ARG, before anything is launched: the cases of rnampnn_design; null delta;
+ * n_states outside 1 .. 64; bit 0 of terminal set.  Then the partner check, then the LDS check; then, with every output null, the call
+ * returns RNAMPNN_OK without a launch. */
+#define RNAMPNN_DESIGN_AVOID_MAX_STATES 64
+int rnampnn_design_avoid(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
+                         float temperature, int32_t S, uint64_t seed, const uint64_t* seed_dev, const uint8_t* allowed,
+                         const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position,
+                         const uint8_t* delta, int32_t n_states, uint64_t terminal, int8_t* seqs, float* seq_nll,
+                         int32_t* infeasible, int32_t* hits, int32_t* avoid_miss, void* stream);
 
 /* -- training ---------------------------------------------------------------------------- */
 /* The training surface of RNAMPNN (rnampnn.py:187-207 + Lightning's loss.backward()):

@@ -1,5 +1,5 @@
-// Pieces shared by the five design kernels - k_design (design.hip, f32), k_design_tied (design_tied.hip), k_design_gc / k_design_count
-// (count_tree_dev.h) and k_design_distinct (design_distinct.hip), all fp64 - and by their entries.  Everything that is about "a position
+// Pieces shared by the six design kernels - k_design (design.hip, f32), k_design_tied (design_tied.hip), k_design_gc / k_design_count
+// (count_tree_dev.h), k_design_distinct (design_distinct.hip) and k_design_avoid (design_avoid.hip), all fp64 - and by their entries.  Everything that is about "a position
 // under the constraints" has its one definition here: the arguments and the entry prologue (ds_prepare), the mask of a position (ds_mask),
 // its row (ds_load<F>), its validated partner (ds_partner), the 16 cells of a pair (ds_pair_mask), the uniform of a position, the DRAW
 // RULE as templates over the scalar type - the weights exp(z - max over the admitted), the selection over an admitted set, the joint cell
@@ -7,7 +7,7 @@
 // phase "C" of the kernels that draw into LDS first (ds_write_rows).  So every entry draws under the same constraints as rnampnn_design
 // by construction, and one state per group draws what rnampnn_design draws.  Who uses what: k_design everything up to ds_draw_pair (its
 // draw is fused into its row loop, so it keeps that loop); k_design_tied the draw rule, the prologue, the ceiling and the scratch (its
-// td_load / td_mask sum and AND over the states of a group: other functions); the count tree and k_design_distinct all of it.
+// td_load / td_mask sum and AND over the states of a group: other functions); the count tree and k_design_distinct all of it; k_design_avoid all of it but the partner and the pair (it refuses pairs).
 #pragma once
 #include <type_traits>
 #include "score_dev.h"

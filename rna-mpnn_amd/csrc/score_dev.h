@@ -1,6 +1,6 @@
-// Pieces shared by the per-(RNA, pass) kernels on f32 logits - k_score (score.hip) and the five design kernels k_design, k_design_tied,
-// k_design_gc, k_design_count and k_design_distinct (through design_dev.h) - and by k_rd_score (rdesign_score.hip): the argument checks
-// of rnampnn_score and, through ds_prepare, of the five design entries, the extent of an RNA in either layout, the first-maximum argmax
+// Pieces shared by the per-(RNA, pass) kernels on f32 logits - k_score (score.hip) and the six design kernels k_design, k_design_tied,
+// k_design_gc, k_design_count, k_design_distinct and k_design_avoid (through design_dev.h) - and by k_rd_score (rdesign_score.hip): the argument checks
+// of rnampnn_score and, through ds_prepare, of the six design entries, the extent of an RNA in either layout, the first-maximum argmax
 // and the NLL of one row, and the fixed-order workgroup sums.  One definition of each, so that the likelihood every design kernel writes
 // for its own draws is byte for byte the one k_score returns for them.
 #pragma once
@@ -19,7 +19,7 @@ struct ScRows {                  // the logits of a batch in either layout: what
 };
 struct ScDraw { int S; const char* per; float temperature; const float* bias; int bias_per_position; };   // what only a design entry checks
 
-// The argument checks rnampnn_score and the five design entries share, in the order they fire, and the fields of ScRows.
+// The argument checks rnampnn_score and the six design entries share, in the order they fire, and the fields of ScRows.
 // `draw`: the S / temperature / bias checks of a design entry (null for rnampnn_score).  `own(slot)`: the entry's own checks that fire
 // in between - slot 0 after the batch check, slot 1 after the alignment checks; it returns what fail() returned, or RNAMPNN_OK.
 template <typename Own>

@@ -49,7 +49,16 @@ Mutation budget (``rnampnn_design_count``, both families): every draw differs fr
 filtered.  The reference is the structure's own ``seqs/<id>.fasta``, or its record ``>pdb_id`` in ``--mutate-from`` (letters outside AUCG
 never count); a structure without one is an error naming its id.  The designs CSV gains the columns ``mutations`` (the Hamming distance of
 the draw to the reference) and ``mut_miss`` (0, or by how many mutations the target structure and the fixed positions alone exceed the
-budget; the draws then hold the fewest mutations they allow).  Not built together with ``--states``, ``--gc-content`` or ``--distinct``."""
+budget; the draws then hold the fewest mutations they allow).  Not built together with ``--states``, ``--gc-content`` or ``--distinct``.
+
+    python rna-mpnn_amd/predict.py --ckpt Final.pt --data DIR --samples 8 --avoid GGGG,GAAUUC [--max-run 3] [--constraints cons.csv --bias .. --omit ..]
+
+Forbidden motifs (``rnampnn_design_avoid``, both families): no draw contains one of the comma-separated motifs (AUCG, T read as U, IUPAC
+codes expand) or, with ``--max-run R``, a run of more than R equal letters - drawn exactly from the model's distribution conditioned on
+that and on the fixed positions, not filtered.  The designs CSV gains the columns ``motif_hits`` (positions of the draw at which a motif
+ends) and ``avoid_miss`` (1 for a structure whose fixed positions spell a motif: its draws ignore the motifs and ``motif_hits`` reports
+them).  Not built together with the other modes or with a ``structure`` in ``--constraints``; the automaton of the set has at most 64
+states."""
 from __future__ import annotations
 
 import argparse
@@ -86,6 +95,8 @@ def parse(argv=None):
     ap.add_argument("--min-mutations", type=int, default=None, help="m: ... and at no fewer than m positions (default 0); needs --max-mutations")
     ap.add_argument("--mutate-from", default=None, help="FASTA with one record >pdb_id per structure: the references of --max-mutations "
                                                         "(default: the structure's own sequence)")
+    ap.add_argument("--avoid", default=None, help="MOTIF[,MOTIF..]: no draw of --samples contains one of these substrings (AUCG, T = U, IUPAC codes)")
+    ap.add_argument("--max-run", type=int, default=None, help="R: no draw of --samples holds a run of more than R equal letters")
     return ap.parse_args(argv)
 
 
@@ -145,6 +156,21 @@ def mutations_option(args) -> dict:
     return dict(mutations=(lo, args.max_mutations, read_reference_fasta(args.mutate_from) if args.mutate_from else None))
 
 
+def avoid_option(args) -> dict:
+    """The ``avoid`` keyword of ``predict`` from ``--avoid`` / ``--max-run``: the automaton, built (and refused) before the model is loaded;
+    empty without the flags.  ``ValueError`` naming the flags with another mode and without ``--samples``."""
+    if args.avoid is None and args.max_run is None:
+        return {}
+    for flag, value in (("--states", args.states), ("--gc-content", args.gc_content), ("--distinct", args.distinct),
+                        ("--max-mutations", args.max_mutations)):
+        if value is not None:
+            raise ValueError(f"--avoid / --max-run together with {flag} is not built: the automaton conditions plain single-state designs only")
+    if args.samples <= 0:
+        raise ValueError("--avoid / --max-run need --samples N > 0")
+    from rnampnn.utils.motifs import MotifAutomaton
+    return dict(avoid=MotifAutomaton.from_motifs([m for m in (args.avoid or "").split(",") if m.strip()], max_run=args.max_run))
+
+
 def checkpoint_family(path: str) -> str:
     """The ``model`` key of a checkpoint file; a file without one is an ``rdesign`` checkpoint.  ``weights_only=True``."""
     ck = torch.load(path, map_location="cpu", weights_only=True)
@@ -155,7 +181,8 @@ def checkpoint_family(path: str) -> str:
 
 
 def run(args, log=print):
-    mutations = mutations_option(args)                             # a combination that is not built fails here, before the model is loaded
+    avoid = avoid_option(args)                                     # a combination that is not built fails here, before the model is loaded
+    mutations = mutations_option(args)
     distinct = distinct_option(args)
     gc = gc_option(args)                                           # a bad window fails here, before the model is loaded
     family = checkpoint_family(args.ckpt)
@@ -166,7 +193,7 @@ def run(args, log=print):
         from rdesign.utils.predict import predict
         from rdesign.utils.train import load_checkpoint
     extra = dict(samples=args.samples, temperature=args.temperature, seed=args.seed, designs_csv=args.designs_out, **design_options(args), **gc, **distinct,
-                 **mutations)
+                 **mutations, **avoid)
     if args.states:
         if family != "rnampnn":
             raise ValueError("--states designs with rnampnn checkpoints only; for an rdesign checkpoint call RNAModel.design(states=...) "

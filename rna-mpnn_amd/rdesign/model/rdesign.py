@@ -33,7 +33,7 @@ import torch.nn.functional as F
 
 from .. import _native
 from rnampnn.model._base import _prep, _stream
-from rnampnn.model.decode import (check_distinct, check_mutations, check_state_lengths, design_by_mode, design_distinct_from_logits,  # noqa: F401
+from rnampnn.model.decode import (check_avoid, check_distinct, check_mutations, check_state_lengths, design_by_mode, design_distinct_from_logits,  # noqa: F401
                                   design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits, letters_packed,
                                   score_logits)
 
@@ -429,7 +429,7 @@ class RNAModel(nn.Module):
 
     @torch.no_grad()
     def design(self, X, mask, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None, lengths=None, states=None,
-               state_weights=None, gc_content=None, distinct=None, mutations=None):
+               state_weights=None, gc_content=None, distinct=None, mutations=None, avoid=None):
         """``n_samples`` sequences per RNA drawn from this model's read-out at ``temperature`` and scored, in one ``rnampnn_design`` launch
         on the packed logits -> (seqs int8 (n_samples,B,T), -1 on padding; seq_nll (n_samples,B) f32, the model's own temperature-1 NLL of
         each draw; infeasible (B,) int32).  ``constraints``: a ``rnampnn.utils.constraints.DesignConstraints`` (fixed nucleotides, base
@@ -445,15 +445,20 @@ class RNAModel(nn.Module):
         sequence): the draws - under ``constraints`` or free - differ from the reference at between min (default 0) and max positions,
         drawn exactly from the model's distribution conditioned on that (``design_count_from_logits``) -> (seqs, seq_nll, infeasible,
         n_mut (n_samples,B) int32, mut_miss (B,) int32 = how far the structure and the fixed positions alone push the count out of the
-        budget, 0 when it is reachable); not built together with ``states``, ``gc_content`` or ``distinct``."""
-        mode = design_mode(states, gc_content, distinct, mutations)
+        budget, 0 when it is reachable); not built together with ``states``, ``gc_content`` or ``distinct``.  ``avoid`` (a
+        ``rnampnn.utils.motifs.MotifAutomaton`` or motif strings): no draw contains one of the motifs - drawn exactly from the model's
+        distribution conditioned on that (``design_avoid_from_logits``) -> (seqs, seq_nll, infeasible, hits (n_samples,B) int32,
+        avoid_miss (B,) int32); not built together with the other modes, and constraints that carry base pairs are a ``ValueError``
+        before the forward pass."""
+        mode = design_mode(states, gc_content, distinct, mutations, avoid)
         mutations = check_mutations(mutations)
+        avoid = check_avoid(avoid, constraints)
         if states is not None and lengths is not None:
             check_state_lengths(states, lengths)
         logits, cu, T = self._packed_logits(X, mask, lengths)
         return design_by_mode(mode, logits, cu_seqlens=cu, max_len=T, n_samples=n_samples, temperature=temperature, seed=seed,
                               constraints=constraints, states=states, state_weights=state_weights, gc_content=gc_content, distinct=distinct,
-                              mutations=mutations)
+                              mutations=mutations, avoid=avoid)
 
     @torch.no_grad()
     def score_sequences(self, X, mask, seqs, labels=None, lengths=None):

@@ -4,7 +4,7 @@ from __future__ import annotations
 import os
 from typing import List, Optional, Tuple
 
-from rnampnn.model.decode import check_budget, design_by_mode, design_mode, letters_padded, score_logits
+from rnampnn.model.decode import check_avoid, check_budget, design_by_mode, design_mode, letters_padded, score_logits
 from rnampnn.utils.constraints import batch_constraints, mutation_references, padded_references
 from rnampnn.utils.data import bucket_batches
 from rnampnn.utils.predict import design_columns, write_csv
@@ -14,7 +14,7 @@ from .data import load_rna_dir, padded_loader
 
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
-            wobble: bool = True, gc_content=None, distinct=None, mutations=None) -> List[Tuple[str, str]]:
+            wobble: bool = True, gc_content=None, distinct=None, mutations=None, avoid=None) -> List[Tuple[str, str]]:
     """Read ``data_path`` (``coords/<id>.npy`` + ``seqs/<id>.fasta``), design a sequence for every structure in length-bucketed batches
     (``RNAModel.predict_sequences``: the tree read-out when one is attached, else the read-out's argmax) and write ``out_csv`` with one
     ``pdb_id,seq`` row per input in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure at
@@ -27,8 +27,18 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     a slot the structure's admitted sequences do not fill.  Not built together with ``gc_content``.  ``mutations`` (min, max, references):
     a mutation budget - the draws come from ``rnampnn_design_count`` and differ from the reference sequence of the structure
     (``references[pdb_id]``, or with None its own fasta sequence) at between min and max positions; ``designs_csv`` gains the last columns
-    ``mutations`` and ``mut_miss``.  Not built together with ``gc_content`` or ``distinct``."""
-    mode = design_mode(None, gc_content, distinct, mutations)
+    ``mutations`` and ``mut_miss``.  Not built together with ``gc_content`` or ``distinct``.  ``avoid`` (a ``MotifAutomaton`` or motif
+    strings): the draws come from ``rnampnn_design_avoid`` and contain none of the motifs; ``designs_csv`` gains the last columns
+    ``motif_hits`` and ``avoid_miss``.  Not built together with the other modes or with a structure in ``constraints``."""
+    mode = design_mode(None, gc_content, distinct, mutations, avoid)
+    avoid = check_avoid(avoid)
+    if avoid is not None:
+        if samples <= 0:
+            raise ValueError("forbidden motifs need samples > 0")
+        paired = sorted(rid for rid, (_, structure) in (constraints or {}).items() if structure)
+        if paired:
+            raise ValueError(f"avoid together with base pairs is not built (an exact draw would carry every open pair in the automaton's "
+                             f"state): drop `structure` from the constraints of {paired[:3]}{' ...' if len(paired) > 3 else ''}")
     if mutations is not None:
         check_budget(mutations[0], mutations[1])
         if samples <= 0:
@@ -53,7 +63,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             cons = batch_constraints(constraints, [items[i][0] for i in idx], lens, T, bias=bias, wobble=wobble, omit=omit)
             draws, nll, bad, *extras = design_by_mode(
                 mode, logits, cu_seqlens=cu, max_len=T, n_samples=samples, temperature=temperature, seed=seed + bi,
-                constraints=cons.to_device(device), gc_content=gc_content, distinct=distinct,
+                constraints=cons.to_device(device), gc_content=gc_content, distinct=distinct, avoid=avoid,
                 mutations=None if mutations is None else (padded_references(refs, idx, T), (mutations[0], mutations[1])))
             _, cells, filled = design_columns(mode, extras, lens)
             match = score_logits(logits, cu_seqlens=cu, labels=S, seqs=draws, want=("seq_match",))["seq_match"].cpu().tolist()

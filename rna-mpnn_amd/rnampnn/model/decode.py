@@ -1,7 +1,7 @@
 """Decoding from logits, as free functions over the C ABI's decode family: argmax + recovery (``rnampnn_argmax_recovery``), free draws
 (``rnampnn_sample``), scores (``rnampnn_score``), constrained and multi-state design (``rnampnn_design``, ``rnampnn_design_tied``), design
 under a G+C content window (``rnampnn_design_gc``), design within a count window / a mutation budget (``rnampnn_design_count``), distinct
-designs (``rnampnn_design_distinct``), the choice between them (``design_mode``, ``design_by_mode``) and the letters of class ids.  Needs the library and ``_base`` only, so both model packages import
+designs (``rnampnn_design_distinct``), design that avoids forbidden motifs (``rnampnn_design_avoid``), the choice between them (``design_mode``, ``design_by_mode``) and the letters of class ids.  Needs the library and ``_base`` only, so both model packages import
 it at module level."""
 from __future__ import annotations
 
@@ -83,7 +83,7 @@ def check_state_lengths(states, lengths) -> None:
 
 def _design_call(name, logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints, padded=(), head=None, tail=None,
                  outputs=(), entry=None):
-    """One call of a design entry of the C ABI -> (seqs, seq_nll, infeasible, *the entry's further outputs).  What the five entries share
+    """One call of a design entry of the C ABI -> (seqs, seq_nll, infeasible, *the entry's further outputs).  What the entries share
     is done here, once: the device check (it speaks of ``name``), the constraints' tensors, the layout, the shape checks, the outputs and
     the common positional arguments.  What is an entry's own comes in: ``padded`` - further (label, tensor, dtype) inputs padded to
     (B,T), prepared and shape-checked ahead of the constraints'; ``head`` / ``tail`` - callables (B, T, mask, cu, *the padded inputs) ->
@@ -294,6 +294,38 @@ def design_distinct_from_logits(logits: torch.Tensor, mask: Optional[torch.Tenso
                         tail=lambda B, T, m, cu: (DISTINCT_MODES[mode],), outputs=((torch.float32, True), (torch.int32, False)))
 
 
+def check_avoid(avoid, constraints=None, max_run=None):
+    """``design(..., avoid=...)`` -> the ``MotifAutomaton`` (``as_automaton``), or None for None.  ``ValueError`` when the constraints carry
+    base pairs: a pair couples two distant positions, which the exact chain over (position, automaton state) does not carry.  Touches no
+    device, so a caller refuses before its forward pass."""
+    from ..utils.motifs import as_automaton
+    auto = as_automaton(avoid, max_run)
+    if auto is not None and constraints is not None and constraints.partner is not None:
+        raise ValueError("avoid together with base pairs is not built: a pair couples two distant positions, so an exact draw would carry the "
+                         "class of every open pair in the automaton's state; drop `structure` from the constraints (fixed nucleotides, IUPAC "
+                         "sets, omit and bias all combine with avoid)")
+    return auto
+
+
+def design_avoid_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
+                             max_len: Optional[int] = None, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None,
+                             avoid=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``rnampnn_design_avoid`` (include/rnampnn_hip.h): the draws of ``design_from_logits`` conditioned exactly on the sequence containing
+    none of a set of forbidden motifs, in one launch -> (seqs, seq_nll, infeasible, hits (S,B) int32 = positions of the draw at which a
+    motif ends: 0 on every RNA that can avoid them, avoid_miss (B,) int32 = 1 when no admitted sequence of the RNA avoids the motifs: it is
+    then drawn as ``design_from_logits`` draws it and ``hits`` reports what it holds).  ``avoid``: a ``MotifAutomaton``
+    (``rnampnn.utils.motifs``), a motif string or an iterable of them.  Fixed / IUPAC sets and either bias of ``constraints`` combine with
+    it; base pairs are a ``ValueError`` (``check_avoid``).  The table of partition sums lives in LDS: T <= 1064 for ``max_run=3`` (13 live
+    states), 290 at 64 live states; beyond it the library raises ``NotImplementedError`` naming the limit.  Layouts as in
+    ``design_from_logits``.  CUDA logits only (there is no CPU fallback); no host synchronisation."""
+    auto = check_avoid(avoid, constraints)
+    if auto is None:
+        raise ValueError("avoid is required: a MotifAutomaton or motif strings (MotifAutomaton.from_motifs(['GGGG'], max_run=3))")
+    return _design_call("rnampnn_design_avoid", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints,
+                        tail=lambda B, T, m, cu: (auto.delta_on(logits.device), auto.n_states, C.c_uint64(auto.terminal)),
+                        outputs=((torch.int32, True), (torch.int32, False)))
+
+
 def check_distinct(distinct, states=None, gc_content=None) -> None:
     """``design(..., distinct=...)``: ``ValueError`` for an unknown mode or a combination that is not built; touches no device."""
     if distinct is not None:
@@ -302,17 +334,19 @@ def check_distinct(distinct, states=None, gc_content=None) -> None:
 
 # What conditions the draws, in the order in which it decides the mode: (the argument that selects the mode, the arguments it is not built
 # together with, why).  A mode further down is excluded by the ones above it, so every pair is named once.
-DESIGN_MODES = (("mutations", ("states", "gc_content", "distinct"), "the budget conditions the draws of rnampnn_design on one count"),
+DESIGN_MODES = (("avoid", ("states", "gc_content", "distinct", "mutations"),
+                 "the automaton conditions the draws of rnampnn_design on the motifs alone"),
+                ("mutations", ("states", "gc_content", "distinct"), "the budget conditions the draws of rnampnn_design on one count"),
                 ("distinct", ("states", "gc_content"), "the beam runs over the units of rnampnn_design only"),
                 ("gc_content", ("states",), "the G+C window conditions the draws of rnampnn_design only"),
                 ("states", (), ""))
 
 
-def design_mode(states=None, gc_content=None, distinct=None, mutations=None) -> str:
-    """Which entry ``design(...)`` draws from: "mutations", "distinct", "gc_content", "states", or "plain" when none of them is given.
+def design_mode(states=None, gc_content=None, distinct=None, mutations=None, avoid=None) -> str:
+    """Which entry ``design(...)`` draws from: "avoid", "mutations", "distinct", "gc_content", "states", or "plain" when none of them is given.
     ``ValueError`` for a combination that is not built (``DESIGN_MODES``) and an unknown ``distinct``; touches no device, so a caller
     refuses before its forward pass."""
-    given = {"states": states, "gc_content": gc_content, "distinct": distinct, "mutations": mutations}
+    given = {"states": states, "gc_content": gc_content, "distinct": distinct, "mutations": mutations, "avoid": avoid}
     for mode, excluded, why in DESIGN_MODES:
         if given[mode] is None:
             continue
@@ -325,9 +359,13 @@ def design_mode(states=None, gc_content=None, distinct=None, mutations=None) -> 
     return "plain"
 
 
-def design_by_mode(mode: str, logits: torch.Tensor, states=None, state_weights=None, gc_content=None, distinct=None, mutations=None, **kw):
+def design_by_mode(mode: str, logits: torch.Tensor, states=None, state_weights=None, gc_content=None, distinct=None, mutations=None,
+                   avoid=None, **kw):
     """The ``*_from_logits`` call of ``mode`` (``design_mode``) -> what that function returns.  ``mutations`` as ``check_mutations``
-    returns it; ``kw``: the layout and the draw (mask / cu_seqlens / max_len, n_samples, temperature, seed, constraints)."""
+    returns it, ``avoid`` as ``check_avoid`` does; ``kw``: the layout and the draw (mask / cu_seqlens / max_len, n_samples, temperature,
+    seed, constraints)."""
+    if mode == "avoid":
+        return design_avoid_from_logits(logits, avoid=avoid, **kw)
     if mode == "mutations":
         return design_mutations_from_logits(logits, mutations, **kw)
     if mode == "distinct":

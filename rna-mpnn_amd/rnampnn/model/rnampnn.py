@@ -23,7 +23,7 @@ from .. import _native
 from ..config.glob import DEFAULT_SEED, REVERSE_VOCAB
 from ..utils.data import check_prefix_mask
 from ._base import NativeModule, _prep, _ptr, _stream
-from .decode import (SCORE_OUTPUTS, argmax_recovery, check_distinct, check_mutations, check_state_lengths, design_by_mode,  # noqa: F401
+from .decode import (SCORE_OUTPUTS, argmax_recovery, check_avoid, check_distinct, check_mutations, check_state_lengths, design_by_mode,  # noqa: F401
                      design_distinct_from_logits, design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits,
                      letters_packed, letters_padded, sample_from_logits, score_logits)
 from ._schema import DEFAULT_HPARAMS
@@ -546,7 +546,8 @@ class RNAMPNN(NativeModule):
 
     @torch.no_grad()
     def design(self, coords: torch.Tensor, mask: torch.Tensor, n_samples: int = 8, temperature: float = 0.1, seed: int = 0,
-               T_norm: int = 0, constraints=None, states=None, state_weights=None, lengths=None, gc_content=None, distinct=None, mutations=None):
+               T_norm: int = 0, constraints=None, states=None, state_weights=None, lengths=None, gc_content=None, distinct=None, mutations=None,
+               avoid=None):
         """``sample`` plus the score of every draw against the SAME logits, with one forward: -> (seqs int8 (n_samples,B,T), -1 on
         padding; seq_nll (n_samples,B) f32).  The NLL is the model's own (temperature 1) likelihood, so designs drawn at different
         temperatures rank on one scale.  ``constraints`` (``rnampnn.utils.constraints.DesignConstraints``: fixed nucleotides, base
@@ -564,15 +565,22 @@ class RNAMPNN(NativeModule):
         class ids, e.g. the native sequence): the draws - under ``constraints`` or free - differ from the reference at between min
         (default 0) and max positions, drawn exactly from the model's distribution conditioned on that (``design_count_from_logits``) ->
         (seqs, seq_nll, infeasible, n_mut (n_samples,B) int32, mut_miss (B,) int32 = how far the structure and the fixed positions alone
-        push the count out of the budget, 0 when it is reachable); not built together with ``states``, ``gc_content`` or ``distinct``."""
-        mode = design_mode(states, gc_content, distinct, mutations)
+        push the count out of the budget, 0 when it is reachable); not built together with ``states``, ``gc_content`` or ``distinct``.
+        ``avoid`` (a ``rnampnn.utils.motifs.MotifAutomaton`` or motif strings such as ``["GGGG", "GAAUUC"]``): no draw contains one of the
+        motifs - drawn exactly from the model's distribution conditioned on that, under the fixed positions and the bias of
+        ``constraints`` or free (``design_avoid_from_logits``) -> (seqs, seq_nll, infeasible, hits (n_samples,B) int32, avoid_miss (B,)
+        int32 = 1 for an RNA whose fixed positions spell a motif); not built together with the other modes, and constraints that carry
+        base pairs are a ``ValueError`` before the forward pass."""
+        mode = design_mode(states, gc_content, distinct, mutations, avoid)
         mutations = check_mutations(mutations)
+        avoid = check_avoid(avoid, constraints)
         if states is not None and lengths is not None:
             check_state_lengths(states, lengths)
         logits = self._run(coords, mask, T_norm=T_norm)["logits"]
         if mode != "plain" or constraints is not None:
             return design_by_mode(mode, logits, mask=mask, n_samples=n_samples, temperature=temperature, seed=seed, constraints=constraints,
-                                  states=states, state_weights=state_weights, gc_content=gc_content, distinct=distinct, mutations=mutations)
+                                  states=states, state_weights=state_weights, gc_content=gc_content, distinct=distinct, mutations=mutations,
+                                  avoid=avoid)
         seqs = sample_from_logits(logits, mask, temperature, n_samples, seed)
         return seqs, score_logits(logits, mask=mask, seqs=seqs, want=("seq_nll",))["seq_nll"]
 

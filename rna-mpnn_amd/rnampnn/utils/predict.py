@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from ..config.glob import VOCAB
-from ..model.decode import check_budget, design_by_mode, design_mode, letters_packed, letters_padded, sample_from_logits, score_logits
+from ..model.decode import check_avoid, check_budget, design_by_mode, design_mode, letters_packed, letters_padded, sample_from_logits, score_logits
 from .constraints import batch_constraints, mutation_references, padded_references
 from .data import PackedLoader, bucket_batches, fill_nan_deterministic, read_fasta
 
@@ -122,6 +122,8 @@ def design_columns(mode: str, extras=(), lens=()):
         return ",gc,gc_miss", lambda s, r: (f"{per_sample[s][r] / lens[r]:.6f}", per_row[r]), None
     if mode == "mutations":
         return ",mutations,mut_miss", lambda s, r: (per_sample[s][r], per_row[r]), None
+    if mode == "avoid":
+        return ",motif_hits,avoid_miss", lambda s, r: (per_sample[s][r], per_row[r]), None
     if mode == "distinct":
         return ",logp", lambda s, r: (f"{per_sample[s][r]:.6f}",), per_row
     return "", lambda s, r: (), None
@@ -130,7 +132,8 @@ def design_columns(mode: str, extras=(), lens=()):
 @torch.no_grad()
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
-            wobble: bool = True, states: Optional[dict] = None, gc_content=None, distinct=None, mutations=None) -> List[Tuple[str, str]]:
+            wobble: bool = True, states: Optional[dict] = None, gc_content=None, distinct=None, mutations=None,
+            avoid=None) -> List[Tuple[str, str]]:
     """Design a sequence for every structure under ``data_path`` in length-bucketed var-len batches (``forward_packed``): the tree
     read-out on the packed embedding when one is attached, else the read-out's argmax (``rnampnn_score``'s ``pred``); write ``out_csv``
     with one ``pdb_id,seq`` row per structure in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure
@@ -154,8 +157,21 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     that.  ``references`` is {pdb_id: sequence} (``read_reference_fasta``) or None for the structure's own ``seqs/<id>.fasta``; a
     structure without a reference is a ``ValueError`` naming its id.  ``designs_csv`` gains the last columns ``mutations`` (the Hamming
     distance of the draw to the reference) and ``mut_miss`` (0, or by how many mutations the structure and the fixed positions alone
-    exceed the budget).  Not built together with ``states``, ``gc_content`` or ``distinct``."""
-    mode = design_mode(states, gc_content, distinct, mutations)
+    exceed the budget).  Not built together with ``states``, ``gc_content`` or ``distinct``.
+    ``avoid`` (a ``MotifAutomaton`` or motif strings): forbidden motifs - the draws come from ``rnampnn_design_avoid`` and contain none of
+    them, drawn exactly from the model's distribution conditioned on that and on the fixed positions, ``omit`` and ``bias``.
+    ``designs_csv`` gains the last columns ``motif_hits`` (positions of the draw at which a motif ends: 0 unless ``avoid_miss``) and
+    ``avoid_miss`` (1 for a structure whose fixed positions spell a motif).  Not built together with the other modes; a constraints
+    table with a structure column that is not empty is a ``ValueError`` before the first forward pass."""
+    mode = design_mode(states, gc_content, distinct, mutations, avoid)
+    avoid = check_avoid(avoid)
+    if avoid is not None:
+        if samples <= 0:
+            raise ValueError("forbidden motifs need samples > 0")
+        paired = sorted(rid for rid, (_, structure) in (constraints or {}).items() if structure)
+        if paired:
+            raise ValueError(f"avoid together with base pairs is not built (an exact draw would carry every open pair in the automaton's "
+                             f"state): drop `structure` from the constraints of {paired[:3]}{' ...' if len(paired) > 3 else ''}")
     if mutations is not None:
         check_budget(mutations[0], mutations[1])
         if samples <= 0:
@@ -197,7 +213,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
         if constrained:
             cons = batch_constraints(constraints, [ids[i] for i in idx], lens, max_len, bias=bias, wobble=wobble, omit=omit).to_device(device)
         draws, dnll, bad, *extras = draw_batch(
-            logits, cu, max_len, samples, temperature, seed + bi, cons, mode, gc_content=gc_content, distinct=distinct,
+            logits, cu, max_len, samples, temperature, seed + bi, cons, mode, gc_content=gc_content, distinct=distinct, avoid=avoid,
             mutations=None if mutations is None else (padded_references(refs, idx, max_len), (mutations[0], mutations[1])),
             states=None if gs is None else [len(groups[g][1]) for g in gs],
             state_weights=None if gs is None else [w for g in gs for w in groups[g][2]])

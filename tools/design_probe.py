@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""The measurement behind DESIGN.md section 9 "Constrained design", "Multi-state design", "Design under a G+C window", "Distinct designs"
-and "Mutation budget" (profiles/design_kernel_stats.txt, profiles/design_tied_kernel_stats.txt, profiles/design_gc_kernel_stats.txt,
-profiles/design_distinct_kernel_stats.txt, profiles/design_count_kernel_stats.txt): the C2 batch (256 RNAs x 100..140 nt), S = 8 sequences per RNA.
+"""The measurement behind DESIGN.md section 9 "Constrained design", "Multi-state design", "Design under a G+C window", "Distinct designs",
+"Mutation budget" and "Forbidden motifs" (profiles/design_kernel_stats.txt, profiles/design_tied_kernel_stats.txt, profiles/design_gc_kernel_stats.txt,
+profiles/design_distinct_kernel_stats.txt, profiles/design_count_kernel_stats.txt, profiles/design_avoid_kernel_stats.txt): the C2 batch (256 RNAs x 100..140 nt), S = 8 sequences per RNA.
 usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + rnampnn_score (seq_nll): the unconstrained pair of launches
        python tools/design_probe.py design [calls=50]         rnampnn_design: free, then with a hairpin's pairs + a fixed GNRA loop per RNA
        python tools/design_probe.py tied [calls=50]           rnampnn_design (free, hairpin) and then rnampnn_design_tied: one state per group
@@ -15,6 +15,10 @@ usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + r
                                                               with the hairpins and a reference that is compatible with them
        python tools/design_probe.py distinct [calls=50]       rnampnn_design (free, hairpin) and then rnampnn_design_distinct at S = 8 and S = 64,
                                                               "sample" then "best", each free and then with the hairpins (8 legs)
+       python tools/design_probe.py avoid                     rnampnn_design (free, hairpin) and then, in 5 alternating rounds of 10 calls each,
+                                                              rnampnn_design_count (b) (S = 8, cap 8: the yardstick) and rnampnn_design_avoid:
+                                                              S = 8 with max_run = 3 (13 live states), S = 8 with a 64-state set, S = 64 with
+                                                              max_run = 3; all without constraints
 HIP events around each loop of back-to-back calls of the Python wrappers.  Run either under `rocprofv3 --kernel-trace --stats -- python ...`
 (a run of its own) for the kernels' own times.  RNAMPNN_PROBE_ROOT: another checkout (with its library built) to take the package from -
 the `sample_score` leg uses nothing newer than rnampnn_score, so it runs on the parent commit as well."""
@@ -137,6 +141,45 @@ else:
             dist = ((out[0].cpu() != r[None]) & (out[0].cpu() >= 0)).sum(-1)
             print(f"{tag} mutations of the draws {int(out[3].min())} .. {int(out[3].max())} (Hamming distance equal {bool((dist == out[3].cpu()).all())}), "
                   f"mut_miss total {int(out[4].sum())}, mean NLL per nt {float(out[1].sum()) / (S * int(mask.sum())):.4f}")
+    if what == "avoid":
+        # Four variants in alternating rounds of one process, so that k_design_avoid is compared with k_design_count of the SAME run.
+        from rnampnn.model import decode as D
+        from rnampnn.utils.motifs import MotifAutomaton
+        rounds, per_round, warm = 5, 10, 3
+        kw = dict(temperature=0.1, seed=1)
+        sets = D.mutation_sets(torch.randint(0, 4, (B, T), generator=torch.Generator().manual_seed(1)).cuda())
+        run3 = MotifAutomaton.from_motifs([], max_run=3)
+        wide = MotifAutomaton.from_motifs(["GGGG", "GAAUUCAAGC", "CUGCAGUCGA", "AAGCUUGCAU", "UCUAGAGGCC", "CCCGGGAUAU", "AUCGAUCGGUAC"])
+        variants = [
+            ("rnampnn_design_count (b) random reference, 0..8 mutations, cap 8, S 8",
+             lambda: D.design_count_from_logits(logits, mask=m, counted=sets, window=(0, 8), n_samples=8, **kw)),
+            (f"rnampnn_design_avoid max_run 3 ({run3.n_live} live states), S 8",
+             lambda: D.design_avoid_from_logits(logits, mask=m, avoid=run3, n_samples=8, **kw)),
+            (f"rnampnn_design_avoid {wide.n_states}-state set ({wide.n_live} live states), S 8",
+             lambda: D.design_avoid_from_logits(logits, mask=m, avoid=wide, n_samples=8, **kw)),
+            (f"rnampnn_design_avoid max_run 3 ({run3.n_live} live states), S 64",
+             lambda: D.design_avoid_from_logits(logits, mask=m, avoid=run3, n_samples=64, **kw))]
+        for _, fn in variants:
+            for _ in range(warm):
+                fn()
+        torch.cuda.synchronize()
+        times = [[] for _ in variants]
+        for _ in range(rounds):
+            for v, (_, fn) in enumerate(variants):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(per_round):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                times[v].append(e0.elapsed_time(e1) * 1e3 / per_round)
+        for (name, _), t in zip(variants, times):
+            print(f"B {B} T {T} nt {int(mask.sum())} {name}: {sum(t) / len(t):.2f} us per call, rounds {min(t):.2f} .. {max(t):.2f} "
+                  f"({rounds} alternating rounds of {per_round} back-to-back calls, events, output allocation included)")
+        free = M.design_from_logits(logits, mask=m, n_samples=8, **kw)[0]
+        for tag, auto, out in (("max_run 3", run3, variants[1][1]()), ("64-state set", wide, variants[2][1]())):
+            print(f"{tag}: hits of the draws {int(out[3].sum())} (recounted {int(auto.hits(out[0]).sum())}), avoid_miss total {int(out[4].sum())}, "
+                  f"mean NLL per nt {float(out[1].sum()) / (8 * int(mask.sum())):.4f}; rnampnn_design's free draws hold {int(auto.hits(free).sum())} hits")
     if what == "distinct":
         for S in (8, 64):                                           # (timed() prints the global S)
             for mode in ("sample", "best"):

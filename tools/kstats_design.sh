@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/design_probe.py under rocprofv3 --kernel-trace --stats, each leg in a run of its own.  usage: tools/kstats_design.sh <outdir> [leg ...]
-# (outdir: a git-ignored place such as build/design_stats; legs: sample_score design tied gc distinct count, the first four by default)
+# (outdir: a git-ignored place such as build/design_stats; legs: sample_score design tied gc distinct count avoid, the first four by default)
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "${1:?usage: tools/kstats_design.sh <outdir> [leg ...]}" && OUT=$(cd "$1" && pwd) || exit 1
 shift
@@ -24,27 +24,37 @@ def launches(match):
     return sorted(((int(r['Start_Timestamp']), int(r['End_Timestamp']) - int(r['Start_Timestamp'])) for r in csv.DictReader(open(t)) if match(r['Kernel_Name'])))
 # the "gc" leg adds, after those of k_design, 55 + 55 + 1 launches of k_design_gc: the window 40..60 % free / with the hairpins
 # the "distinct" leg adds 8 x 55 launches of k_design_distinct (+ 1 after every fourth): S = 8 then 64, sample then best, free then hairpins
-d = launches(lambda n: 'k_design' in n and 'k_design_tied' not in n and 'k_design_gc' not in n and 'k_design_distinct' not in n and 'k_design_count' not in n)
+d = launches(lambda n: 'k_design' in n and 'k_design_tied' not in n and 'k_design_gc' not in n and 'k_design_distinct' not in n and 'k_design_count' not in n and 'k_design_avoid' not in n)
 g = launches(lambda n: 'k_design_distinct' in n)
 e = launches(lambda n: 'k_design_tied' in n)
 f = launches(lambda n: 'k_design_gc' in n)
 # the "count" leg: after 3 warm launches per variant, 5 alternating rounds of 10 launches per variant - k_design_gc free / hairpins (2 variants
 # of its launches) and k_design_count (a) free / (a) hairpins / (b) / (c) (4 variants of its launches); per variant the mean of every round
 c = launches(lambda n: 'k_design_count' in n)
-if c:
-    def by_round(seq, variants, v):
-        body = seq[3 * variants:]
-        return [[x[1] / 1e3 for x in body[10 * (variants * r + v):10 * (variants * r + v) + 10]] for r in range(5)]
-    for kernel, label, rs in (("k_design_gc", "window 40..60 %, no constraints", by_round(f, 2, 0)),
-                              ("k_design_count", "(a) C|G counted, cap T, window 40..60 %, no constraints", by_round(c, 4, 0)),
-                              ("k_design_gc", "window 40..60 %, hairpin pairs + GNRA + bias", by_round(f, 2, 1)),
-                              ("k_design_count", "(a) C|G counted, cap T, window 40..60 %, hairpin pairs + GNRA + bias", by_round(c, 4, 1)),
-                              ("k_design_count", "(b) random reference, 0..8 mutations, cap 8, no constraints", by_round(c, 4, 2)),
-                              ("k_design_count", "(c) compatible reference, 0..8 mutations, cap 8, hairpins", by_round(c, 4, 3))):
+# the "avoid" leg: the same rounds - k_design_count (b) (1 variant of its launches: the yardstick of the same run) and k_design_avoid
+# S = 8 max_run 3 / S = 8 64-state set / S = 64 max_run 3 (3 variants of its launches)
+av = launches(lambda n: 'k_design_avoid' in n)
+def by_round(seq, variants, v):
+    body = seq[3 * variants:]
+    return [[x[1] / 1e3 for x in body[10 * (variants * r + v):10 * (variants * r + v) + 10]] for r in range(5)]
+def report(table):
+    for kernel, label, rs in table:
         means = [sum(r) / len(r) for r in rs]
         flat = sorted(x for r in rs for x in r)
         print(f"{kernel}, {label}: 5 rounds x 10 launches, mean {sum(flat) / len(flat):.2f} us ({flat[0]:.2f} .. {flat[-1]:.2f}, median {flat[len(flat) // 2]:.2f}); "
               f"round means {' '.join(f'{v:.2f}' for v in means)} (spread {max(means) - min(means):.2f})")
+if av:
+    report((("k_design_count", "(b) random reference, 0..8 mutations, cap 8, S = 8, no constraints", by_round(c, 1, 0)),
+            ("k_design_avoid", "max_run 3 (13 live states), S = 8, no constraints", by_round(av, 3, 0)),
+            ("k_design_avoid", "64-state set (57 live states), S = 8, no constraints", by_round(av, 3, 1)),
+            ("k_design_avoid", "max_run 3 (13 live states), S = 64, no constraints", by_round(av, 3, 2))))
+elif c:
+    report((("k_design_gc", "window 40..60 %, no constraints", by_round(f, 2, 0)),
+                              ("k_design_count", "(a) C|G counted, cap T, window 40..60 %, no constraints", by_round(c, 4, 0)),
+                              ("k_design_gc", "window 40..60 %, hairpin pairs + GNRA + bias", by_round(f, 2, 1)),
+                              ("k_design_count", "(a) C|G counted, cap T, window 40..60 %, hairpin pairs + GNRA + bias", by_round(c, 4, 1)),
+                              ("k_design_count", "(b) random reference, 0..8 mutations, cap 8, no constraints", by_round(c, 4, 2)),
+                              ("k_design_count", "(c) compatible reference, 0..8 mutations, cap 8, hairpins", by_round(c, 4, 3))))
     f = []                                                          # (its k_design_gc launches are reported above, by round)
 for kernel, label, part in (("k_design", "no constraints", d[:55]), ("k_design", "hairpin pairs + GNRA + bias", d[55:111]),
                             ("k_design_tied", "one state per group, no constraints", e[:55]),
