@@ -484,7 +484,7 @@ static int run_bert(Run& r, const Bert& b, float* x, float* out) {
             launch_attention_f32(r.pk, r.w.s0, b.heads, r.w.n2, r.s))
             return fail(RNAMPNN_ERR_UNSUPPORTED, "head dim unsupported");
         gemm(r, a.out, r.w.n2, RN_D, r.w.s1, RN_D, x, RN_D);                          // x + out_proj(attn)
-        launch_graph_norm_packed(r.pk, r.w.s1, nullptr, x, rawp(c, a.gn_scale), rawp(c, a.gn_shift), c->cfg.padding_len, r.s);
+        launch_graph_norm_packed(r.pk, r.w.s1, x, rawp(c, a.gn_scale), rawp(c, a.gn_shift), c->cfg.padding_len, r.s);
     }
     if (run_chain(r, b.chain, b.ffn, x, RN_D, nullptr, 0, out, RN_D)) return RNAMPNN_OK;
     const float* cur = x;
@@ -522,7 +522,7 @@ static NodeJob node_job(rnampnn_ctx* c, const Mlp2& m, bf16_t* p, bf16_t* q) {
 static void node_pq(Run& r, const Mlp2& m, const float* h, bool edge) {
     rnampnn_ctx* c = r.c;
     if (r.fast)     // the fused node kernel without residual / norm
-        launch_node_update(r.pk, h, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 1,
+        launch_node_update(r.pk, h, nullptr, nullptr, 0, nullptr, nullptr, 1,
                            node_job(c, m, edge ? r.w.p_e : r.w.p_m, edge ? r.w.q_e : r.w.q_m), NodeJob{}, r.s);
     else
         launch_gemm_f32(r.ntot(), r.pk.Nmax, h, RN_D, RN_D, nullptr, 0, 0, derp<float>(c, m.pq_t),
@@ -669,10 +669,10 @@ static int forward_core(Run& r, rnampnn_handle h, const RnaMpnnForwardIO* io, co
     rc = run_bert(r, c->emb, w.n0, w.n1);
     if (!rc) {
         if (fused_first)    // GraphNorm + the [P | Q] projection of layer 1's message MLP in one pass
-            launch_node_update(r.pk, w.n1, nullptr, rawp(c, c->feat_gn_scale), rawp(c, c->feat_gn_shift), t_norm, w.coef, w.hA, 1,
+            launch_node_update(r.pk, w.n1, rawp(c, c->feat_gn_scale), rawp(c, c->feat_gn_shift), t_norm, w.coef, w.hA, 1,
                                node_job(c, c->mpnn[0].msg, w.p_m, w.q_m), NodeJob{}, r.s);
         else
-            launch_graph_norm_packed(r.pk, w.n1, nullptr, w.hA, rawp(c, c->feat_gn_scale), rawp(c, c->feat_gn_shift), t_norm, r.s);
+            launch_graph_norm_packed(r.pk, w.n1, w.hA, rawp(c, c->feat_gn_scale), rawp(c, c->feat_gn_shift), t_norm, r.s);
     }
     if (rc) return rc;
     if (launch_knn(io->coords, r.pk, t_norm, k, w.nbr, io->edge_index, s))
@@ -708,10 +708,10 @@ static int forward_core(Run& r, rnampnn_handle h, const RnaMpnnForwardIO* io, co
             // the bf16 kernel wrote h + agg; GraphNorm + both [P | Q] projections in one kernel
             const NodeJob je = need_e ? node_job(c, c->mpnn[l].edge, w.p_e, w.q_e) : NodeJob{};
             const NodeJob jm = need_m ? node_job(c, c->mpnn[l + 1].msg, w.p_m, w.q_m) : NodeJob{};
-            launch_node_update(r.pk, w.hB, nullptr, gsc, gsh, t_norm, w.coef, w.hA, (need_e && need_m) ? 2 : 1, need_e ? je : jm, jm, s);
+            launch_node_update(r.pk, w.hB, gsc, gsh, t_norm, w.coef, w.hA, (need_e && need_m) ? 2 : 1, need_e ? je : jm, jm, s);
         } else {
             // (both kernel families write h + agg)
-            launch_graph_norm_packed(r.pk, w.hB, nullptr, w.hA, gsc, gsh, t_norm, s);
+            launch_graph_norm_packed(r.pk, w.hB, w.hA, gsc, gsh, t_norm, s);
             if (need_e) node_pq(r, c->mpnn[l].edge, w.hA, true);
             if (need_m) node_pq(r, c->mpnn[l + 1].msg, w.hA, false);
         }
@@ -729,7 +729,7 @@ static int forward_core(Run& r, rnampnn_handle h, const RnaMpnnForwardIO* io, co
     rc = run_bert(r, c->post, w.hA, w.n0);                     // h_post -> n0
     if (rc) return rc;
     run_ffn(r, c->raw_chain, c->raw_ffn, w.raw_p, RN_RAWP, w.n1);
-    launch_graph_norm_packed(r.pk, w.n1, nullptr, w.n2, rawp(c, c->rawffn_gn_scale), rawp(c, c->rawffn_gn_shift), t_norm, s);   // raw_emb -> n2
+    launch_graph_norm_packed(r.pk, w.n1, w.n2, rawp(c, c->rawffn_gn_scale), rawp(c, c->rawffn_gn_shift), t_norm, s);   // raw_emb -> n2
     if (io->h_post) launch_unpack_nodes(r.pk, w.n0, RN_D, RN_D, io->h_post, s);
     if (io->raw_emb) launch_unpack_nodes(r.pk, raw_emb, RN_D, RN_D, io->raw_emb, s);
     if (io->embedding) {
@@ -792,7 +792,7 @@ extern "C" int rnampnn_mpnn_layer(rnampnn_handle h, int32_t layer, const float* 
     mpnn_step(r, nullptr, &m.msg, w.hA, w.hB, msg_p);
     if (msg_out) launch_unpack_edges(r.pk, k, w.big, nullptr, msg_out, s);
     if (h_out || e_out) {
-        launch_graph_norm_packed(r.pk, w.hB, nullptr, w.hA, rawp(c, m.gn_scale), rawp(c, m.gn_shift), t_norm, s);
+        launch_graph_norm_packed(r.pk, w.hB, w.hA, rawp(c, m.gn_scale), rawp(c, m.gn_shift), t_norm, s);
         if (h_out) launch_unpack_nodes(r.pk, w.hA, RN_D, RN_D, h_out, s);
         if (e_out) {
             node_pq(r, m.edge, w.hA, true);
@@ -839,7 +839,7 @@ extern "C" int rnampnn_raw_ffn(rnampnn_handle h, const float* raw, const float* 
     HIP_TRY(hipMemsetAsync(r.w.raw_p, 0, (size_t)r.pk.Nmax * RN_RAWP * sizeof(float), r.s));
     launch_pack_nodes(r.pk, raw, RN_RAW, r.w.raw_p, RN_RAWP, r.s);
     run_ffn(r, h->raw_chain, h->raw_ffn, r.w.raw_p, RN_RAWP, r.w.n1);
-    launch_graph_norm_packed(r.pk, r.w.n1, nullptr, r.w.n2, rawp(h, h->rawffn_gn_scale), rawp(h, h->rawffn_gn_shift),
+    launch_graph_norm_packed(r.pk, r.w.n1, r.w.n2, rawp(h, h->rawffn_gn_scale), rawp(h, h->rawffn_gn_shift),
                              T_norm > 0 ? T_norm : T, r.s);
     launch_unpack_nodes(r.pk, r.w.n2, RN_D, RN_D, y, r.s);
     HIP_TRY(hipGetLastError());

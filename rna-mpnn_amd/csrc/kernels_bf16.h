@@ -45,8 +45,8 @@ static inline size_t chain_image_bytes(int K0, int H, int NH, int NOUT) {
 int launch_ffn_chain(const int* ntot, int mmax, const float* X, int ldx, const float* X2, int ldx2, int K0, int H, int NH,
                      int NOUT, const bf16_t* img, const float* const* bias, float* Y, int ldy, int n_valid, hipStream_t s);
 
-// fused node update: h' = GraphNorm(x + add) (scale == null: h' = x + add, no norm), then the [P | Q] projections of up to two first
-// Linears.  Both tables are f16 of (a P), (a Q) in NATURAL channel order, [N+1][128]; coef = scratch [B][256]
+// fused node update: h' = GraphNorm(x) (scale == null: h' = x, no norm), then the [P | Q] projections of up to two first
+// Linears.  x is the finished residual sum h + agg (launch_mpnn_bf16 writes it: h_res).  Both tables are f16 of (a P), (a Q) in NATURAL channel order, [N+1][128]; coef = scratch [B][256]
 struct NodeJob {
     const bf16_t* img = nullptr;     // launch_build_pq_image
     const float* bias = nullptr;     // its b1p
@@ -55,8 +55,8 @@ struct NodeJob {
     int p_efrag = 0;                 // the image's P rows are in ch_efrag order (depth-1 edge MLP)
 };
 void launch_build_pq_image(const float* w0, const float* b1, int efrag, bf16_t* dst, float* b1p, hipStream_t s);   // b1p: bias in the P-row order
-void launch_node_update(const PackInfo& pk, const float* x, const float* add, const float* scale, const float* shift, int t_tot,
-                        float* coef, float* h_out, int njobs, const NodeJob& job0, const NodeJob& job1, hipStream_t s);
+void launch_node_update(const PackInfo& pk, const float* x, const float* scale, const float* shift, int t_tot, float* coef,
+                        float* h_out, int njobs, const NodeJob& job0, const NodeJob& job1, hipStream_t s);
 
 // MFMA attention over valid keys (head dim 16); returns 1 when the shape is not covered (caller uses the f32 kernel)
 int launch_attention_bf16(const PackInfo& pk, const float* qkv, int heads, float* out, hipStream_t s);

@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "bf16_dev.h"
+#include "graph_norm_dev.h"
 
 // ------------------------------------------------------------------------------------------
 // weight preparation
@@ -212,8 +213,8 @@ __device__ __forceinline__ void gelu_pack(const f32x16& acc, u32x4& lo, u32x4& h
 // ------------------------------------------------------------------------------------------
 // Fused ResMPNN step on 32-edge blocks (mpnn.py:154-265), bf16 MFMA:
 //   DO_EDGE: e <- e + MLP_e(P_e[i] + Q_e[j] + e Wc_e)   (edge update of the previous layer)
-//   DO_MSG : agg = mean_valid MLP_m(P_m[i] + Q_m[j] + e Wc_m)   (message + aggregation; the residual
-//            h + agg of mpnn.py:222 is taken by the graph-norm kernel that follows)
+//   DO_MSG : agg = mean_valid MLP_m(P_m[i] + Q_m[j] + e Wc_m)   (message + aggregation; with h_res the launch
+//            writes the residual h + agg of mpnn.py:222 itself, and the GraphNorm kernels behind it read that one tensor)
 // One wave owns one block: lanes (r, h) = (edge r of the block, k-half h).  k <= 16 packs
 // npb = 32/k residues into a block (edges of consecutive residues are contiguous in e).
 struct NodeTabs {             // per-residue parts of the first Linears (k_node_update outputs): f16 of a P / a Q, natural channel order
@@ -1215,14 +1216,14 @@ int launch_ffn_chain(const int* ntot, int mmax, const float* X, int ldx, const f
 // ------------------------------------------------------------------------------------------
 // Fused node update between two ResMPNN steps (mpnn.py:222-225, 289; functional.py:33-46):
 //   x = h + agg  ->  GraphNormalization  ->  h'  ->  [P | Q] = h' . [Wa | Wb]^T (+ b1) for up to two
-// first Linears (edge MLP of this layer, message MLP of the next).  k_gn_coef reduces the per-RNA
-// statistics to an affine map y = a x + b per (RNA, channel); k_node_update applies it to 32-row
-// blocks held as B fragments, writes h' (f32) and runs the projections on MFMA with the
-// [P | Q] weight images resident in LDS (64 KiB per job): P -> f32, Q -> bf16 (gather tables of
-// the edge kernel).
-__global__ void __launch_bounds__(256) k_gn_coef(PackInfo pk, const float* __restrict__ x, const float* __restrict__ add,
-        const float* __restrict__ scale, const float* __restrict__ shift, int t_tot, float* __restrict__ coef) {
-    // TWO-PASS statistics (mean, then sum of squared deviations): the one-pass form sum x^2 + (T - 2n) mu^2 cancels once |h| >> sigma
+// first Linears (edge MLP of this layer, message MLP of the next).  x arrives as the finished sum: the fused
+// ResMPNN launch writes h + agg (launch_mpnn_bf16: h_res).  Two forms.  k_gn_coef reduces the per-RNA
+// statistics to an affine map y = a x + b per (RNA, channel) and k_node_update applies it to 32-row
+// blocks; k_node_update_rna forms the same map inside the update, one workgroup per RNA.  Both hold the
+// rows as B fragments, write h' (f32) and run the projections on MFMA with the [P | Q] weight images
+// resident in LDS (64 KiB per job): P and Q -> f16 (gather tables of the edge kernel).
+__global__ void __launch_bounds__(256) k_gn_coef(PackInfo pk, const float* __restrict__ x, const float* __restrict__ scale,
+        const float* __restrict__ shift, int t_tot, float* __restrict__ coef) {
     __shared__ float4 red[4][8];
     const int b = blockIdx.x, cg = blockIdx.y;                 // RNA, group of 32 channels
     const int n = pk.len[b];
@@ -1231,7 +1232,6 @@ __global__ void __launch_bounds__(256) k_gn_coef(PackInfo pk, const float* __res
     const int cq = threadIdx.x & 7, g = threadIdx.x >> 3;      // channel quad, row group (32)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const float4* xb = reinterpret_cast<const float4*>(x + base) + cq;
-    const float4* ab = add ? reinterpret_cast<const float4*>(add + base) + cq : nullptr;
     // reduce a per-thread float4 over the 32 row groups: 4 lanes-of-8 per wave via shuffles, then the 4 waves via LDS (fixed order)
     auto block_sum = [&](float4 s) -> float4 {
 #pragma unroll
@@ -1247,146 +1247,70 @@ __global__ void __launch_bounds__(256) k_gn_coef(PackInfo pk, const float* __res
         return t;
     };
     const float fn = (float)n;
-    float4 S, Q;
-    if (n <= 160) {         // rows stay in registers between the two passes (all loads of the thread in flight together)
-        float4 v[5], a[5];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) { const int r = g + 32 * i, rc = r < n ? r : n - 1; v[i] = xb[(size_t)rc * 32]; }
-        if (ab) {
-#pragma unroll
-            for (int i = 0; i < 5; ++i) { const int r = g + 32 * i, rc = r < n ? r : n - 1; a[i] = ab[(size_t)rc * 32]; }
-#pragma unroll
-            for (int i = 0; i < 5; ++i) { v[i].x += a[i].x; v[i].y += a[i].y; v[i].z += a[i].z; v[i].w += a[i].w; }
-        }
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int i = 0; i < 5; ++i) if (g + 32 * i < n) { s.x += v[i].x; s.y += v[i].y; s.z += v[i].z; s.w += v[i].w; }
-        S = block_sum(s);
-        const float4 mu = make_float4(S.x / fn, S.y / fn, S.z / fn, S.w / fn);
-        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int i = 0; i < 5; ++i) if (g + 32 * i < n) {
-            const float dx = v[i].x - mu.x, dy = v[i].y - mu.y, dz = v[i].z - mu.z, dw = v[i].w - mu.w;
-            q.x = fmaf(dx, dx, q.x); q.y = fmaf(dy, dy, q.y); q.z = fmaf(dz, dz, q.z); q.w = fmaf(dw, dw, q.w);
-        }
-        Q = block_sum(q);
-    } else if (n <= 256) {  // (C4: 200 nt) the same with eight rows per thread
-        float4 v[8], a[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const int r = g + 32 * i, rc = r < n ? r : n - 1; v[i] = xb[(size_t)rc * 32]; }
-        if (ab) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { const int r = g + 32 * i, rc = r < n ? r : n - 1; a[i] = ab[(size_t)rc * 32]; }
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { v[i].x += a[i].x; v[i].y += a[i].y; v[i].z += a[i].z; v[i].w += a[i].w; }
-        }
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) if (g + 32 * i < n) { s.x += v[i].x; s.y += v[i].y; s.z += v[i].z; s.w += v[i].w; }
-        S = block_sum(s);
-        const float4 mu = make_float4(S.x / fn, S.y / fn, S.z / fn, S.w / fn);
-        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) if (g + 32 * i < n) {
-            const float dx = v[i].x - mu.x, dy = v[i].y - mu.y, dz = v[i].z - mu.z, dw = v[i].w - mu.w;
-            q.x = fmaf(dx, dx, q.x); q.y = fmaf(dy, dy, q.y); q.z = fmaf(dz, dz, q.z); q.w = fmaf(dw, dw, q.w);
-        }
-        Q = block_sum(q);
-    } else {
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int r = g; r < n; r += 32) {
-            float4 v = xb[(size_t)r * 32];
-            if (ab) { const float4 a = ab[(size_t)r * 32]; v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w; }
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-        S = block_sum(s);
-        const float4 mu = make_float4(S.x / fn, S.y / fn, S.z / fn, S.w / fn);
-        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int r = g; r < n; r += 32) {
-            float4 v = xb[(size_t)r * 32];
-            if (ab) { const float4 a = ab[(size_t)r * 32]; v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w; }
-            const float dx = v.x - mu.x, dy = v.y - mu.y, dz = v.z - mu.z, dw = v.w - mu.w;
-            q.x = fmaf(dx, dx, q.x); q.y = fmaf(dy, dy, q.y); q.z = fmaf(dz, dz, q.z); q.w = fmaf(dw, dw, q.w);
-        }
-        Q = block_sum(q);
-    }
+    float4 mu, Q;
+    auto stats = [&](const auto& rows) {                       // the two passes of graph_norm_dev.h around the one block_sum
+        const float4 S = block_sum(rows.sum());
+        mu = make_float4(S.x / fn, S.y / fn, S.z / fn, S.w / fn);
+        Q = block_sum(rows.sqdev(mu));
+    };
+    if (n <= 160) stats(GnRows<32, 5>(xb, g, n));              // rows stay in registers between the two passes
+    else if (n <= 256) stats(GnRows<32, 8>(xb, g, n));         // (C4: 200 nt) the same with eight rows per thread
+    else stats(GnRows<32, 0>(xb, g, n));
     if (threadIdx.x < 8) {
-        const float pad = (float)(t_tot - n);
         const float4 sc = reinterpret_cast<const float4*>(scale + 32 * cg)[cq], sh = reinterpret_cast<const float4*>(shift + 32 * cg)[cq];
-        const float mean[4] = {S.x / fn, S.y / fn, S.z / fn, S.w / fn};
-        const float sq[4] = {Q.x, Q.y, Q.z, Q.w}, scl[4] = {sc.x, sc.y, sc.z, sc.w}, shf[4] = {sh.x, sh.y, sh.z, sh.w};
-        float a[4], bb[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            // var = [sum_valid (x - mu)^2 + (T - n) mu^2] / n : padded rows enter as (0 - mu)^2 (functional.py:33-38)
-            const float var = (sq[i] + pad * mean[i] * mean[i]) / fn;
-            a[i] = scl[i] / sqrtf(var + kSEPS);
-            bb[i] = shf[i] - mean[i] * a[i];
-        }
+        float4 a, bb;
+        gn_affine(Q.x, mu.x, n, t_tot, sc.x, sh.x, a.x, bb.x); gn_affine(Q.y, mu.y, n, t_tot, sc.y, sh.y, a.y, bb.y);
+        gn_affine(Q.z, mu.z, n, t_tot, sc.z, sh.z, a.z, bb.z); gn_affine(Q.w, mu.w, n, t_tot, sc.w, sh.w, a.w, bb.w);
         float* cb = coef + (size_t)b * 256 + 32 * cg + 4 * cq;
-        *reinterpret_cast<float4*>(cb) = make_float4(a[0], a[1], a[2], a[3]);
-        *reinterpret_cast<float4*>(cb + 128) = make_float4(bb[0], bb[1], bb[2], bb[3]);
+        *reinterpret_cast<float4*>(cb) = a;
+        *reinterpret_cast<float4*>(cb + 128) = bb;
     }
 }
 
 typedef NodeJob PqJob;     // img: [8 ob][8 ks][64][8]; ob < 4 -> P rows, >= 4 -> Q rows
 
-template <int NJOBS>
-__global__ void __launch_bounds__(256, 2) k_node_update(PackInfo pk, const float* __restrict__ x, const float* __restrict__ add,
-        const float* __restrict__ coef, float* __restrict__ h_out, PqJob j0, PqJob j1) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    u32x4* img = reinterpret_cast<u32x4*>(smem);
-    const int ntot = pk.cu[pk.B];
-    const int row_blk = blockIdx.x * 128;
-    if (row_blk >= ntot) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-    const int row = row_blk + 32 * wave + r;
-    const bool ok = row < ntot;
-    const int rr = ok ? row : 0;
-    const float* cf = coef + (size_t)pk.node_b[rr] * 256;
-    // the HBM loads of the rows go out first; the weight images (L2-resident) are staged into LDS while they fly
-    f32x4 vx[8][2], va[8][2];
+// ---- the pieces both update kernels are made of.  A lane holds row `row` as B fragments: vx[s][0..1] = channels 16 s + 8 h + 0..7.
+// The ORDER in which the kernels call them is measured (docs/experiments.md R4.x): row loads out first, images staged while they fly.
+__device__ __forceinline__ void node_load_row(const float* __restrict__ x, int row, int h, f32x4 (&vx)[8][2]) {
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
         const int c0 = 16 * s + 8 * h;
-        vx[s][0] = *reinterpret_cast<const f32x4*>(x + (size_t)rr * RN_D + c0);
-        vx[s][1] = *reinterpret_cast<const f32x4*>(x + (size_t)rr * RN_D + c0 + 4);
-        if (add) {
-            va[s][0] = *reinterpret_cast<const f32x4*>(add + (size_t)rr * RN_D + c0);
-            va[s][1] = *reinterpret_cast<const f32x4*>(add + (size_t)rr * RN_D + c0 + 4);
-        }
+        vx[s][0] = *reinterpret_cast<const f32x4*>(x + (size_t)row * RN_D + c0);
+        vx[s][1] = *reinterpret_cast<const f32x4*>(x + (size_t)row * RN_D + c0 + 4);
     }
+}
+// the weight images by DMA (L2-resident), fenced so that they are issued behind the row loads; then the biases of the P halves: they go
+// through LDS too (a global read per channel block would expose an L2 round trip each)
+template <int NJOBS, int NT>
+__device__ __forceinline__ void node_stage(u32x4* img, float* lds_bias, const PqJob& j0, const PqJob& j1, int tid) {
     __builtin_amdgcn_sched_barrier(0);
-    stage_image_dma<256>(img, reinterpret_cast<const u32x4*>(j0.img), tid);
-    if (NJOBS > 1) stage_image_dma<256>(img + 4096, reinterpret_cast<const u32x4*>(j1.img), tid);
+    stage_image_dma<NT>(img, reinterpret_cast<const u32x4*>(j0.img), tid);
+    if (NJOBS > 1) stage_image_dma<NT>(img + 4096, reinterpret_cast<const u32x4*>(j1.img), tid);
     __builtin_amdgcn_sched_barrier(0);
-    // the biases of the P halves go through LDS too (a global read per channel block would expose an L2 round trip each)
-    float* lds_bias = reinterpret_cast<float*>(smem + NJOBS * 65536);
     if (tid < 128) lds_bias[tid] = j0.bias[tid];
-    else if (NJOBS > 1) lds_bias[tid] = j1.bias[tid - 128];
-    // residual, then GraphNorm as one branch-free pass (its 32 coefficient loads go out together), then stores + bf16 pack
-    if (add) {
+    else if (NJOBS > 1 && tid < 256) lds_bias[tid] = j1.bias[tid - 128];
+}
+// y = a x + b from a [128] a | [128] b table (global or LDS) as one branch-free pass: its 32 coefficient loads go out together
+__device__ __forceinline__ void node_affine(const float* ab, int h, f32x4 (&vx)[8][2]) {
 #pragma unroll
-        for (int s = 0; s < 8; ++s) { vx[s][0] += va[s][0]; vx[s][1] += va[s][1]; }
+    for (int s = 0; s < 8; ++s) {
+        const int c0 = 16 * s + 8 * h;
+        const f32x4 ca0 = *reinterpret_cast<const f32x4*>(ab + c0), ca1 = *reinterpret_cast<const f32x4*>(ab + c0 + 4);
+        const f32x4 cb0 = *reinterpret_cast<const f32x4*>(ab + 128 + c0), cb1 = *reinterpret_cast<const f32x4*>(ab + 128 + c0 + 4);
+        vx[s][0] = vx[s][0] * ca0 + cb0; vx[s][1] = vx[s][1] * ca1 + cb1;
     }
-    if (coef) {
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const int c0 = 16 * s + 8 * h;
-            const f32x4 ca0 = *reinterpret_cast<const f32x4*>(cf + c0), ca1 = *reinterpret_cast<const f32x4*>(cf + c0 + 4);
-            const f32x4 cb0 = *reinterpret_cast<const f32x4*>(cf + 128 + c0), cb1 = *reinterpret_cast<const f32x4*>(cf + 128 + c0 + 4);
-            vx[s][0] = vx[s][0] * ca0 + cb0; vx[s][1] = vx[s][1] * ca1 + cb1;
-        }
-    }
-    u32x4 xf[8];
+}
+// f16 pack of the finished row (f16 rows, f16 images); then, once the images have landed, the h' store.  Every row / coefficient load has been
+// consumed by then: only the image pieces can still be in flight at dma_landed(), and the h_out stores drain under the matrix work.
+__device__ __forceinline__ void node_pack_store(const f32x4 (&vx)[8][2], u32x4 (&xf)[8], float* __restrict__ h_out, int row, bool ok, int h) {
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
         const f32x4 v0 = vx[s][0], v1 = vx[s][1];
-        xf[s] = u32x4{p_pack2(v0[0], v0[1]), p_pack2(v0[2], v0[3]), p_pack2(v1[0], v1[1]), p_pack2(v1[2], v1[3])};      // f16 rows, f16 images
+        xf[s] = u32x4{p_pack2(v0[0], v0[1]), p_pack2(v0[2], v0[3]), p_pack2(v1[0], v1[1]), p_pack2(v1[2], v1[3])};
     }
     __builtin_amdgcn_sched_barrier(0);
-    dma_landed();          // (every row / coefficient load above has been consumed: only the image pieces can still be in flight; the h_out
-    __builtin_amdgcn_sched_barrier(0);     //  stores below then drain under the matrix work)
+    dma_landed();
+    __builtin_amdgcn_sched_barrier(0);
     if (ok && h_out) {
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
@@ -1395,7 +1319,11 @@ __global__ void __launch_bounds__(256, 2) k_node_update(PackInfo pk, const float
             *reinterpret_cast<f32x4*>(h_out + (size_t)row * RN_D + c0 + 4) = vx[s][1];
         }
     }
-    __syncthreads();
+}
+// [P | Q] of the row on MFMA against the staged images, stored to the jobs' tables; ends with the kernel's last wait
+template <int NJOBS>
+__device__ __forceinline__ void node_project(const u32x4* img, const float* lds_bias, const u32x4 (&xf)[8], const PqJob& j0, const PqJob& j1,
+                                             int row, bool ok, int lane, int h) {
 #pragma unroll
     for (int jb = 0; jb < NJOBS; ++jb) {
         const PqJob& jbq = jb == 0 ? j0 : j1;
@@ -1426,9 +1354,36 @@ __global__ void __launch_bounds__(256, 2) k_node_update(PackInfo pk, const float
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// 128-row blocks of the packed batch, (a, b) from the coef table of k_gn_coef (coef == null: h' = x, no norm).
+// (waves per SIMD 2 .. 3: the 64 / 128 KiB of LDS never admit more than two, and told so the compiler sends 24 of the 32 coefficient loads out
+//  together, as it always did; aiming at four waves it trickled them out in pairs: 20.3 against 19.3 us per launch.  2 .. 2 takes 202 registers.)
+template <int NJOBS>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 3))) k_node_update(PackInfo pk, const float* __restrict__ x, const float* __restrict__ coef,
+        float* __restrict__ h_out, PqJob j0, PqJob j1) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    u32x4* img = reinterpret_cast<u32x4*>(smem);
+    float* lds_bias = reinterpret_cast<float*>(smem + NJOBS * 65536);
+    const int ntot = pk.cu[pk.B];
+    const int row_blk = blockIdx.x * 128;
+    if (row_blk >= ntot) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    const int row = row_blk + 32 * wave + r;
+    const bool ok = row < ntot;
+    const int rr = ok ? row : 0;
+    const float* cf = coef + (size_t)pk.node_b[rr] * 256;
+    f32x4 vx[8][2];
+    node_load_row(x, rr, h, vx);
+    node_stage<NJOBS, 256>(img, lds_bias, j0, j1, tid);
+    if (coef) node_affine(cf, h, vx);
+    u32x4 xf[8];
+    node_pack_store(vx, xf, h_out, row, ok, h);
+    __syncthreads();
+    node_project<NJOBS>(img, lds_bias, xf, j0, j1, row, ok, lane, h);
+}
+
 // ---- the same update with the GraphNormalization statistics computed IN the kernel: one workgroup per RNA (n <= 32 NW rows), every row of the RNA
 // in the registers of its lanes.  Per-channel sums over the rows: DPP tree over the 32 lanes of a half-wave (fixed order), the waves' partials
-// combined through LDS by 128 threads in wave order - two passes (mean, then squared deviations: functional.py:33-38 and the note in k_gn_coef).
+// combined through LDS by 128 threads in wave order - two passes (mean, then squared deviations: graph_norm_dev.h).
 // Replaces the k_gn_coef launch in front of k_node_update (8 us of a 2.2 ms C2 forward, ten times) when the batch's padded length allows it.
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dpp_f32(float v) {      // (bound_ctrl with the full row mask: lets the compiler fold the move into v_add_f32_dpp)
@@ -1452,12 +1407,11 @@ __device__ __forceinline__ float half_wave_sum2(float a, float b) {
 // SIMDs - measured slower at the C2 lengths: 27.3 against 24.7 us; twice the row loads and ten waves at the barriers cost more than the better
 // spread of the MFMAs gains.)
 template <int NJOBS, int NB>
-__global__ void __launch_bounds__(NB * 64) k_node_update_rna(PackInfo pk, const float* __restrict__ x, const float* __restrict__ add,
-        const float* __restrict__ scale, const float* __restrict__ shift, int t_tot, float* __restrict__ h_out, PqJob j0, PqJob j1) {
+__global__ void __launch_bounds__(NB * 64) k_node_update_rna(PackInfo pk, const float* __restrict__ x, const float* __restrict__ scale,
+        const float* __restrict__ shift, int t_tot, float* __restrict__ h_out, PqJob j0, PqJob j1) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u32x4* img = reinterpret_cast<u32x4*>(smem);
     float* lds_bias = reinterpret_cast<float*>(smem + NJOBS * 65536);      // [2][128]
-    constexpr int NW = NB;
     float* lds_part = lds_bias + 256;                                       // [NB][128] per-row-block partial sums
     float* lds_mean = lds_part + NB * 128;                                  // [128]
     float* lds_ab = lds_mean + 128;                                         // [128] a | [128] b
@@ -1469,31 +1423,12 @@ __global__ void __launch_bounds__(NB * 64) k_node_update_rna(PackInfo pk, const 
     const int rb = wave;                                     // row block
     const int lrow = 32 * rb + r;
     const bool ok = lrow < n;
-    const bool own = ok;
     const int row = base + (ok ? lrow : 0);
-    f32x4 vx[8][2], va[8][2];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        const int c0 = 16 * s + 8 * h;
-        vx[s][0] = *reinterpret_cast<const f32x4*>(x + (size_t)row * RN_D + c0);
-        vx[s][1] = *reinterpret_cast<const f32x4*>(x + (size_t)row * RN_D + c0 + 4);
-        if (add) {
-            va[s][0] = *reinterpret_cast<const f32x4*>(add + (size_t)row * RN_D + c0);
-            va[s][1] = *reinterpret_cast<const f32x4*>(add + (size_t)row * RN_D + c0 + 4);
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    stage_image_dma<NW * 64>(img, reinterpret_cast<const u32x4*>(j0.img), tid);
-    if (NJOBS > 1) stage_image_dma<NW * 64>(img + 4096, reinterpret_cast<const u32x4*>(j1.img), tid);
-    __builtin_amdgcn_sched_barrier(0);
-    if (tid < 128) lds_bias[tid] = j0.bias[tid];
-    else if (NJOBS > 1 && tid < 256) lds_bias[tid] = j1.bias[tid - 128];
+    f32x4 vx[8][2];
+    node_load_row(x, row, h, vx);
+    node_stage<NJOBS, NB * 64>(img, lds_bias, j0, j1, tid);
     float sc_c = 0.f, sh_c = 0.f;
     if (tid < 128) { sc_c = scale[tid]; sh_c = shift[tid]; }
-    if (add) {
-#pragma unroll
-        for (int s = 0; s < 8; ++s) { vx[s][0] += va[s][0]; vx[s][1] += va[s][1]; }
-    }
     const int nwb = (n + 31) >> 5;                         // waves that hold rows
     auto reduce_rows = [&](auto&& value) {                 // value(s, p, i) of this lane -> lds_part[wave][channel]
 #pragma unroll
@@ -1513,12 +1448,11 @@ __global__ void __launch_bounds__(NB * 64) k_node_update_rna(PackInfo pk, const 
         for (int w = 1; w < nwb; ++w) t += lds_part[w * 128 + tid];
         return t;
     };
-    const float fn = (float)n;
     // pass 1: mean
-    reduce_rows([&](int s, int p, int i) { return own ? vx[s][p][i] : 0.f; });
+    reduce_rows([&](int s, int p, int i) { return ok ? vx[s][p][i] : 0.f; });
     __syncthreads();
     float mean_c = 0.f;
-    if (tid < 128) { mean_c = combine() / fn; lds_mean[tid] = mean_c; }
+    if (tid < 128) { mean_c = combine() / (float)n; lds_mean[tid] = mean_c; }
     __syncthreads();
     f32x4 mu[8][2];
 #pragma unroll
@@ -1526,69 +1460,22 @@ __global__ void __launch_bounds__(NB * 64) k_node_update_rna(PackInfo pk, const 
         mu[s][0] = *reinterpret_cast<const f32x4*>(lds_mean + 16 * s + 8 * h);
         mu[s][1] = *reinterpret_cast<const f32x4*>(lds_mean + 16 * s + 8 * h + 4);
     }
-    // pass 2: squared deviations of the valid rows; the T - n padded rows enter as (0 - mean)^2
-    reduce_rows([&](int s, int p, int i) { const float d = vx[s][p][i] - mu[s][p][i]; return own ? d * d : 0.f; });
+    // pass 2: squared deviations of the valid rows
+    reduce_rows([&](int s, int p, int i) { const float d = vx[s][p][i] - mu[s][p][i]; return ok ? d * d : 0.f; });
     __syncthreads();
     if (tid < 128) {
-        const float sq = combine(), pad = (float)(t_tot - n);
-        const float var = (sq + pad * mean_c * mean_c) / fn;
-        const float a = sc_c / sqrtf(var + kSEPS);
+        float a, bb;
+        gn_affine(combine(), mean_c, n, t_tot, sc_c, sh_c, a, bb);
         lds_ab[tid] = a;
-        lds_ab[128 + tid] = sh_c - mean_c * a;
+        lds_ab[128 + tid] = bb;
     }
     __syncthreads();
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        const int c0 = 16 * s + 8 * h;
-        const f32x4 ca0 = *reinterpret_cast<const f32x4*>(lds_ab + c0), ca1 = *reinterpret_cast<const f32x4*>(lds_ab + c0 + 4);
-        const f32x4 cb0 = *reinterpret_cast<const f32x4*>(lds_ab + 128 + c0), cb1 = *reinterpret_cast<const f32x4*>(lds_ab + 128 + c0 + 4);
-        vx[s][0] = vx[s][0] * ca0 + cb0; vx[s][1] = vx[s][1] * ca1 + cb1;
-    }
+    node_affine(lds_ab, h, vx);
     u32x4 xf[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        const f32x4 v0 = vx[s][0], v1 = vx[s][1];
-        xf[s] = u32x4{p_pack2(v0[0], v0[1]), p_pack2(v0[2], v0[3]), p_pack2(v1[0], v1[1]), p_pack2(v1[2], v1[3])};
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    dma_landed();
-    __builtin_amdgcn_sched_barrier(0);
-    if (own && h_out) {
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const int c0 = 16 * s + 8 * h;
-            *reinterpret_cast<f32x4*>(h_out + (size_t)row * RN_D + c0) = vx[s][0];
-            *reinterpret_cast<f32x4*>(h_out + (size_t)row * RN_D + c0 + 4) = vx[s][1];
-        }
-    }
+    node_pack_store(vx, xf, h_out, row, ok, h);
     __syncthreads();
     if (rb >= nwb) return;                                  // (no barrier below)
-#pragma unroll
-    for (int jb = 0; jb < NJOBS; ++jb) {
-        const PqJob& jbq = jb == 0 ? j0 : j1;
-        const u32x4* im = img + jb * 4096;
-#pragma unroll
-        for (int ob = 0; ob < 8; ++ob) {
-            f32x16 acc;
-            if (ob < 4) acc = init_vec16(lds_bias + jb * 128 + 32 * ob + 16 * h);
-            else {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-            }
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) acc = mfma32h(im[(ob * 8 + ks) * 64 + lane], xf[ks], acc);
-            if (ok) {
-                bf16_t* row_p = (ob < 4 ? jbq.p : jbq.q) + (size_t)row * RN_D + 32 * (ob & 3);
-                const bool efr = ob < 4 && jbq.p_efrag;
-                u32x4* d0 = reinterpret_cast<u32x4*>(row_p + (efr ? 8 * h : 16 * h));
-                u32x4* d1 = reinterpret_cast<u32x4*>(row_p + (efr ? 16 + 8 * h : 16 * h + 8));
-                *d0 = u32x4{p_pack2(acc[0], acc[1]), p_pack2(acc[2], acc[3]), p_pack2(acc[4], acc[5]), p_pack2(acc[6], acc[7])};
-                *d1 = u32x4{p_pack2(acc[8], acc[9]), p_pack2(acc[10], acc[11]), p_pack2(acc[12], acc[13]), p_pack2(acc[14], acc[15])};
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    node_project<NJOBS>(img, lds_bias, xf, j0, j1, row, ok, lane, h);
 }
 
 // [P | Q] image of one MLP's first Linear w0 [128][384]: ob < 4 rows ch_nat(ob) of w0[:, 0:128], ob >= 4 of w0[:, 128:256].
@@ -1611,8 +1498,8 @@ void launch_build_pq_image(const float* w0, const float* b1, int efrag, bf16_t* 
     hipLaunchKernelGGL(k_build_pq_image, dim3(8 * 8 * 64 * 8 / 256), dim3(256), 0, s, w0, b1, efrag, dst, b1p);
 }
 
-void launch_node_update(const PackInfo& pk, const float* x, const float* add, const float* scale, const float* shift, int t_tot,
-                        float* coef, float* h_out, int njobs, const NodeJob& job0, const NodeJob& job1, hipStream_t s) {
+void launch_node_update(const PackInfo& pk, const float* x, const float* scale, const float* shift, int t_tot, float* coef,
+                        float* h_out, int njobs, const NodeJob& job0, const NodeJob& job1, hipStream_t s) {
     const PqJob j0 = job0, j1 = njobs > 1 ? job1 : NodeJob{};
     // Every RNA of the batch fits the rows of one workgroup (padded length <= 256) and is long enough for a workgroup of its own: the statistics
     // are computed inside the update kernel (RNAMPNN_NODE_UPDATE_TWO_LAUNCH=1: the two-launch form)
@@ -1622,14 +1509,14 @@ void launch_node_update(const PackInfo& pk, const float* x, const float* add, co
             static DevAttr attr;                                                                                                \
             constexpr size_t lds = (size_t)(J) * 65536 + 1024 + (NBK) * 512 + 3 * 512;                                          \
             ensure_dyn_lds((const void*)k_node_update_rna<J, NBK>, lds, attr);                                                  \
-            hipLaunchKernelGGL((k_node_update_rna<J, NBK>), dim3(pk.B), dim3((NBK) * 64), lds, s, pk, x, add, scale, shift, t_tot, h_out, j0, j1); \
+            hipLaunchKernelGGL((k_node_update_rna<J, NBK>), dim3(pk.B), dim3((NBK) * 64), lds, s, pk, x, scale, shift, t_tot, h_out, j0, j1); \
         } while (0)
         if (njobs == 1) { if (pk.T <= 128) NU_RNA(1, 4); else if (pk.T <= 160) NU_RNA(1, 5); else NU_RNA(1, 8); }
         else { if (pk.T <= 128) NU_RNA(2, 4); else if (pk.T <= 160) NU_RNA(2, 5); else NU_RNA(2, 8); }
 #undef NU_RNA
         return;
     }
-    if (scale) hipLaunchKernelGGL(k_gn_coef, dim3(pk.B, 4), dim3(256), 0, s, pk, x, add, scale, shift, t_tot, coef);
+    if (scale) hipLaunchKernelGGL(k_gn_coef, dim3(pk.B, 4), dim3(256), 0, s, pk, x, scale, shift, t_tot, coef);
     dim3 grid((pk.Nmax + 127) / 128);
     // Measured and NOT kept (round 3, C2, 21.9 us per launch for this form): (a) four workgroups per 128-row block (one per job and P / Q half,
     // 32 KiB of LDS, four per CU): 28.3 us; (b) every global access coalesced through a per-wave LDS tile (1 KiB row loads, 128-byte-line
@@ -1640,8 +1527,8 @@ void launch_node_update(const PackInfo& pk, const float* x, const float* add, co
     ensure_dyn_lds((const void*)k_node_update<1>, 65536 + 1024, attr1);
     ensure_dyn_lds((const void*)k_node_update<2>, 131072 + 1024, attr2);
     const float* cf = scale ? coef : nullptr;
-    if (njobs == 1) hipLaunchKernelGGL(k_node_update<1>, grid, dim3(256), 65536 + 1024, s, pk, x, add, cf, h_out, j0, j1);
-    else hipLaunchKernelGGL(k_node_update<2>, grid, dim3(256), 131072 + 1024, s, pk, x, add, cf, h_out, j0, j1);
+    if (njobs == 1) hipLaunchKernelGGL(k_node_update<1>, grid, dim3(256), 65536 + 1024, s, pk, x, cf, h_out, j0, j1);
+    else hipLaunchKernelGGL(k_node_update<2>, grid, dim3(256), 131072 + 1024, s, pk, x, cf, h_out, j0, j1);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1983,8 +1870,8 @@ __global__ void __launch_bounds__(AL_NW * 64) k_attn_layer_rna(PackInfo pk, floa
         float sq = red[1024 + c];
 #pragma unroll
         for (int q = 1; q < 8; ++q) sq += red[1024 + q * 128 + c];
-        const float var = (sq + (float)(t_tot - n) * mu * mu) / fn;
-        const float a = gsc / sqrtf(var + kSEPS), bb = gsh - mu * a;
+        float a, bb;
+        gn_affine(sq, mu, n, t_tot, gsc, gsh, a, bb);
 #pragma unroll
         for (int q = 0; q < NRW; ++q) { const int row = g + 8 * q; if (row < n) xb[(size_t)row * RN_D + c] = fmaf(yv[q], a, bb); }
     }

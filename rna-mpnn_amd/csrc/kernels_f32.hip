@@ -6,6 +6,7 @@
 // Reference lines restated by each kernel are cited at its head.
 #include "api_internal.h"          // mix64
 #include "bf16_core.h"             // kSEPS, gelu_erf
+#include "graph_norm_dev.h"
 #include <cstdlib>
 
 #define WAVE 64
@@ -768,173 +769,33 @@ void launch_mpnn_f32(const PackInfo& pk, int k, bool do_edge, bool do_msg, const
 }
 
 // ------------------------------------------------------------------------------------------
-// GraphNormalization on packed rows (functional.py:18-48), D = 128, one workgroup per RNA:
-//   mu = sum_valid x / n ;  var = [sum_valid (x-mu)^2 + (T_tot - n) mu^2] / n
-//   y = (x - mu) / sqrt(var + 1e-6) * scale + shift         (padded rows do not exist here)
-// x may come as x + add (the residual h + agg of mpnn.py:222 on the bf16 path).  Thread layout:
-// 32 channel quads (float4) x 8 row groups; the three passes re-read the L2-resident rows.
-__global__ void __launch_bounds__(256) k_graph_norm_packed(PackInfo pk, const float* __restrict__ x, const float* __restrict__ add,
-        float* __restrict__ y, const float* __restrict__ scale, const float* __restrict__ shift, int t_tot) {
-    __shared__ float4 red[8][32];
-    __shared__ float4 stat[32];
-    int b = blockIdx.x;
-    int n = pk.len[b];
-    if (n <= 0) return;
-    const size_t base = (size_t)pk.cu[b] * RN_D;
-    const int cq = threadIdx.x & 31, g = threadIdx.x >> 5;
-    const float4* xb = reinterpret_cast<const float4*>(x + base) + cq;
-    const float4* ab = add ? reinterpret_cast<const float4*>(add + base) + cq : nullptr;
-    auto ld = [&](int r) {
-        float4 v = xb[(size_t)r * 32];
-        if (ab) { float4 a = ab[(size_t)r * 32]; v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w; }
-        return v;
-    };
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 4
-    for (int r = g; r < n; r += 8) { float4 v = ld(r); s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
-    red[g][cq] = s;
-    __syncthreads();
-    if (g == 0) {
-        float4 t = red[0][cq];
-#pragma unroll
-        for (int i = 1; i < 8; ++i) { float4 u = red[i][cq]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
-        float inv = 1.0f / (float)n;
-        stat[cq] = make_float4(t.x * inv, t.y * inv, t.z * inv, t.w * inv);
-    }
-    __syncthreads();
-    const float4 mean = stat[cq];
-    float4 ss = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 4
-    for (int r = g; r < n; r += 8) {
-        float4 v = ld(r);
-        float dx = v.x - mean.x, dy = v.y - mean.y, dz = v.z - mean.z, dw = v.w - mean.w;
-        ss.x = fmaf(dx, dx, ss.x); ss.y = fmaf(dy, dy, ss.y); ss.z = fmaf(dz, dz, ss.z); ss.w = fmaf(dw, dw, ss.w);
-    }
-    __syncthreads();
-    red[g][cq] = ss;
-    __syncthreads();
-    float4 t = red[0][cq];
-#pragma unroll
-    for (int i = 1; i < 8; ++i) { float4 u = red[i][cq]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
-    const float pad = (float)(t_tot - n), fn = (float)n;
-    float4 sd;
-    sd.x = sqrtf((t.x + pad * mean.x * mean.x) / fn + kSEPS); sd.y = sqrtf((t.y + pad * mean.y * mean.y) / fn + kSEPS);
-    sd.z = sqrtf((t.z + pad * mean.z * mean.z) / fn + kSEPS); sd.w = sqrtf((t.w + pad * mean.w * mean.w) / fn + kSEPS);
-    const float4 sc = reinterpret_cast<const float4*>(scale)[cq], sh = reinterpret_cast<const float4*>(shift)[cq];
-    float4* yb = reinterpret_cast<float4*>(y + base) + cq;
-#pragma unroll 4
-    for (int r = g; r < n; r += 8) {
-        float4 v = ld(r), o;
-        o.x = (v.x - mean.x) / sd.x * sc.x + sh.x; o.y = (v.y - mean.y) / sd.y * sc.y + sh.y;
-        o.z = (v.z - mean.z) / sd.z * sc.z + sh.z; o.w = (v.w - mean.w) / sd.w * sc.w + sh.w;
-        yb[(size_t)r * 32] = o;
-    }
-}
-
-// Same, for RNAs of at most 8 * NR residues: every thread keeps its <= NR rows in registers, so the rows are read from
-// memory once (all loads in flight together) instead of three times in dependent loops.
-template <int NR>
-__global__ void __launch_bounds__(256) k_graph_norm_packed_reg(PackInfo pk, const float* __restrict__ x, const float* __restrict__ add,
-        float* __restrict__ y, const float* __restrict__ scale, const float* __restrict__ shift, int t_tot) {
-    __shared__ float4 red[8][32];
-    __shared__ float4 stat[32];
+// GraphNormalization on packed rows (functional.py:18-48; arithmetic and row core: graph_norm_dev.h), D = 128.  x is the finished
+// sum h + agg of mpnn.py:222 (the edge kernels write it), never a pair of operands.  Thread = channel quad (float4) x row group of NG:
+//   <8, NR>   one workgroup per RNA, 32 quads x 8 row groups, RNAs of at most 8 NR residues: the rows are read from memory once;
+//   <8, 0>    the same layout, the three passes re-read the L2-resident rows;
+//   <32, 0>   LONG RNAs (T > 512): four workgroups per RNA, one per 32-channel chunk (8 quads x 32 row groups; a wave reads 128 bytes
+//             of 8 rows per instruction).  With one workgroup per RNA a batch of seven 4,400-nt RNAs used 7 of the 256 CUs (95 us per
+//             call on the config-3 epoch).  32 partial sums per channel instead of 8: agrees with NG = 8 to rounding, not bit for bit.
+// The block folds the NG partials of a channel through red[] in fixed linear order.
+template <int NG, int NR>
+__global__ void __launch_bounds__(256) k_graph_norm_packed(PackInfo pk, const float* __restrict__ x, float* __restrict__ y,
+        const float* __restrict__ scale, const float* __restrict__ shift, int t_tot) {
+    constexpr int CQ = 256 / NG;                                // channel quads per workgroup; gridDim.y = 32 / CQ
+    __shared__ float4 red[NG][CQ];
+    __shared__ float4 stat[CQ];
     const int b = blockIdx.x;
     const int n = pk.len[b];
     if (n <= 0) return;
     const size_t base = (size_t)pk.cu[b] * RN_D;
-    const int cq = threadIdx.x & 31, g = threadIdx.x >> 5;
-    const float4* xb = reinterpret_cast<const float4*>(x + base) + cq;
-    const float4* ab = add ? reinterpret_cast<const float4*>(add + base) + cq : nullptr;
-    float4 v[NR];
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        const int r = g + 8 * i, rc = r < n ? r : n - 1;
-        v[i] = xb[(size_t)rc * 32];
-    }
-    if (ab) {
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            const int r = g + 8 * i, rc = r < n ? r : n - 1;
-            const float4 a = ab[(size_t)rc * 32];
-            v[i].x += a.x; v[i].y += a.y; v[i].z += a.z; v[i].w += a.w;
-        }
-    }
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int i = 0; i < NR; ++i)
-        if (g + 8 * i < n) { s.x += v[i].x; s.y += v[i].y; s.z += v[i].z; s.w += v[i].w; }
-    red[g][cq] = s;
-    __syncthreads();
-    if (g == 0) {
-        float4 t = red[0][cq];
-#pragma unroll
-        for (int i = 1; i < 8; ++i) { float4 u = red[i][cq]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
-        const float inv = 1.0f / (float)n;
-        stat[cq] = make_float4(t.x * inv, t.y * inv, t.z * inv, t.w * inv);
-    }
-    __syncthreads();
-    const float4 mean = stat[cq];
-    float4 ss = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int i = 0; i < NR; ++i)
-        if (g + 8 * i < n) {
-            const float dx = v[i].x - mean.x, dy = v[i].y - mean.y, dz = v[i].z - mean.z, dw = v[i].w - mean.w;
-            ss.x = fmaf(dx, dx, ss.x); ss.y = fmaf(dy, dy, ss.y); ss.z = fmaf(dz, dz, ss.z); ss.w = fmaf(dw, dw, ss.w);
-        }
-    __syncthreads();
-    red[g][cq] = ss;
-    __syncthreads();
-    float4 t = red[0][cq];
-#pragma unroll
-    for (int i = 1; i < 8; ++i) { float4 u = red[i][cq]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
-    const float pad = (float)(t_tot - n), fn = (float)n;
-    float4 sd;
-    sd.x = sqrtf((t.x + pad * mean.x * mean.x) / fn + kSEPS); sd.y = sqrtf((t.y + pad * mean.y * mean.y) / fn + kSEPS);
-    sd.z = sqrtf((t.z + pad * mean.z * mean.z) / fn + kSEPS); sd.w = sqrtf((t.w + pad * mean.w * mean.w) / fn + kSEPS);
-    const float4 sc = reinterpret_cast<const float4*>(scale)[cq], sh = reinterpret_cast<const float4*>(shift)[cq];
-    float4* yb = reinterpret_cast<float4*>(y + base) + cq;
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        const int r = g + 8 * i;
-        if (r < n) {
-            float4 o;
-            o.x = (v[i].x - mean.x) / sd.x * sc.x + sh.x; o.y = (v[i].y - mean.y) / sd.y * sc.y + sh.y;
-            o.z = (v[i].z - mean.z) / sd.z * sc.z + sh.z; o.w = (v[i].w - mean.w) / sd.w * sc.w + sh.w;
-            yb[(size_t)r * 32] = o;
-        }
-    }
-}
-
-// Same, for LONG RNAs (T > 512): four workgroups per RNA, one per 32-channel chunk (thread = channel quad cq of the chunk x row group g of 32;
-// a wave reads 128 bytes of 8 rows per instruction).  With one workgroup per RNA a batch of seven 4,400-nt RNAs used 7 of the 256 CUs
-// (95 us per call on the config-3 epoch).  Per-channel arithmetic and its order over the row groups differ from the kernels above
-// (32 partial sums instead of 8): results agree to rounding, not bit for bit.
-__global__ void __launch_bounds__(256) k_graph_norm_packed_c4(PackInfo pk, const float* __restrict__ x, const float* __restrict__ add,
-        float* __restrict__ y, const float* __restrict__ scale, const float* __restrict__ shift, int t_tot) {
-    __shared__ float4 red[32][8];
-    __shared__ float4 stat[8];
-    const int b = blockIdx.x;
-    const int n = pk.len[b];
-    if (n <= 0) return;
-    const size_t base = (size_t)pk.cu[b] * RN_D;
-    const int cl = threadIdx.x & 7, g = threadIdx.x >> 3, cq = 8 * blockIdx.y + cl;
-    const float4* xb = reinterpret_cast<const float4*>(x + base) + cq;
-    const float4* ab = add ? reinterpret_cast<const float4*>(add + base) + cq : nullptr;
-    auto ld = [&](int r) {
-        float4 v = xb[(size_t)r * 32];
-        if (ab) { float4 a = ab[(size_t)r * 32]; v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w; }
-        return v;
-    };
+    const int cl = threadIdx.x % CQ, g = threadIdx.x / CQ, cq = CQ * blockIdx.y + cl;
+    const GnRows<NG, NR> rows(reinterpret_cast<const float4*>(x + base) + cq, g, n);
     auto fold = [&]() {
         float4 t = red[0][cl];
 #pragma unroll
-        for (int i = 1; i < 32; ++i) { const float4 u = red[i][cl]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
+        for (int i = 1; i < NG; ++i) { const float4 u = red[i][cl]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
         return t;
     };
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 4
-    for (int r = g; r < n; r += 32) { const float4 v = ld(r); s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
-    red[g][cl] = s;
+    red[g][cl] = rows.sum();
     __syncthreads();
     if (g == 0) {
         const float4 t = fold();
@@ -943,39 +804,29 @@ __global__ void __launch_bounds__(256) k_graph_norm_packed_c4(PackInfo pk, const
     }
     __syncthreads();
     const float4 mean = stat[cl];
-    float4 ss = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 4
-    for (int r = g; r < n; r += 32) {
-        const float4 v = ld(r);
-        const float dx = v.x - mean.x, dy = v.y - mean.y, dz = v.z - mean.z, dw = v.w - mean.w;
-        ss.x = fmaf(dx, dx, ss.x); ss.y = fmaf(dy, dy, ss.y); ss.z = fmaf(dz, dz, ss.z); ss.w = fmaf(dw, dw, ss.w);
-    }
-    red[g][cl] = ss;
+    // (no barrier between the second pass and this write: red[] was last read by the g == 0 threads BEFORE the barrier that
+    //  published stat[], and every thread has passed that barrier)
+    red[g][cl] = rows.sqdev(mean);
     __syncthreads();
     const float4 t = fold();
-    const float pad = (float)(t_tot - n), fn = (float)n;
-    float4 sd;
-    sd.x = sqrtf((t.x + pad * mean.x * mean.x) / fn + kSEPS); sd.y = sqrtf((t.y + pad * mean.y * mean.y) / fn + kSEPS);
-    sd.z = sqrtf((t.z + pad * mean.z * mean.z) / fn + kSEPS); sd.w = sqrtf((t.w + pad * mean.w * mean.w) / fn + kSEPS);
+    const float4 sd = make_float4(gn_sd(t.x, mean.x, n, t_tot), gn_sd(t.y, mean.y, n, t_tot), gn_sd(t.z, mean.z, n, t_tot), gn_sd(t.w, mean.w, n, t_tot));
     const float4 sc = reinterpret_cast<const float4*>(scale)[cq], sh = reinterpret_cast<const float4*>(shift)[cq];
     float4* yb = reinterpret_cast<float4*>(y + base) + cq;
-#pragma unroll 4
-    for (int r = g; r < n; r += 32) {
-        const float4 v = ld(r);
+    rows.each([&](int r, const float4& v) {
         float4 o;
         o.x = (v.x - mean.x) / sd.x * sc.x + sh.x; o.y = (v.y - mean.y) / sd.y * sc.y + sh.y;
         o.z = (v.z - mean.z) / sd.z * sc.z + sh.z; o.w = (v.w - mean.w) / sd.w * sc.w + sh.w;
         yb[(size_t)r * 32] = o;
-    }
+    });
 }
 
-void launch_graph_norm_packed(const PackInfo& pk, const float* x, const float* add, float* y, const float* scale,
-                              const float* shift, int t_tot, hipStream_t s) {
-    // (same arithmetic, same summation order per thread: the register variant is bit-identical to the loop variant)
-    if (pk.T <= 160) hipLaunchKernelGGL(k_graph_norm_packed_reg<20>, dim3(pk.B), dim3(256), 0, s, pk, x, add, y, scale, shift, t_tot);
-    else if (pk.T <= 256) hipLaunchKernelGGL(k_graph_norm_packed_reg<32>, dim3(pk.B), dim3(256), 0, s, pk, x, add, y, scale, shift, t_tot);      // (C4: 200 nt)
-    else if (pk.T <= 512) hipLaunchKernelGGL(k_graph_norm_packed, dim3(pk.B), dim3(256), 0, s, pk, x, add, y, scale, shift, t_tot);
-    else hipLaunchKernelGGL(k_graph_norm_packed_c4, dim3(pk.B, 4), dim3(256), 0, s, pk, x, add, y, scale, shift, t_tot);
+void launch_graph_norm_packed(const PackInfo& pk, const float* x, float* y, const float* scale, const float* shift, int t_tot,
+                              hipStream_t s) {
+    // (same arithmetic, same summation order per thread: the register instances are bit-identical to the loop instance)
+    if (pk.T <= 160) hipLaunchKernelGGL((k_graph_norm_packed<8, 20>), dim3(pk.B), dim3(256), 0, s, pk, x, y, scale, shift, t_tot);
+    else if (pk.T <= 256) hipLaunchKernelGGL((k_graph_norm_packed<8, 32>), dim3(pk.B), dim3(256), 0, s, pk, x, y, scale, shift, t_tot);      // (C4: 200 nt)
+    else if (pk.T <= 512) hipLaunchKernelGGL((k_graph_norm_packed<8, 0>), dim3(pk.B), dim3(256), 0, s, pk, x, y, scale, shift, t_tot);
+    else hipLaunchKernelGGL((k_graph_norm_packed<32, 0>), dim3(pk.B, 4), dim3(256), 0, s, pk, x, y, scale, shift, t_tot);
 }
 
 // Stand-alone GraphNormalization on the reference's padded layout, any D, mask by value.

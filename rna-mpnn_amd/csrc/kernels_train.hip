@@ -434,6 +434,26 @@ void t_edge_pq_bwd(const PackInfo& pk, int k, const float* dpre1, const int* sta
 //   y = (x - mu)/sd * scale + shift,  sd^2 = [sum (x-mu)^2 + c mu^2]/n + eps,  c = T_tot - n
 //   dx_i = g_i/sd + dL/dvar * 2 (x_i - mu)/n + dL/dmu / n,   g = dy * scale
 //   dL/dvar = -0.5 sd^-3 sum g_i (x_i - mu),   dL/dmu = -sum g_i / sd + dL/dvar * 2 c mu / n
+// The tail both backward kernels share: from the folded sums of one (RNA, channel) - Ss = sum (x - mu)^2, Sg0 = sum dy, Sgx0 = sum dy (x - mu) -
+// the coefficients above, dx for rows r0 + rg, r0 + rg + 8, ... < r1 of the RNA (xb, gb, db: its row 0), and, where `lead`, the RNA's partials
+// [dscale 128 | dshift 128] of channel c.
+__device__ __forceinline__ void gn_bwd_tail(float Ss, float Sg0, float Sgx0, float mean, int n, int t_tot, float sc, const float* __restrict__ xb,
+        const float* __restrict__ gb, float* __restrict__ db, int c, int r0, int r1, int rg, bool lead, float* __restrict__ part_b) {
+    const float cpad = (float)(t_tot - n), fn = (float)n;
+    const float var = (Ss + cpad * mean * mean) / fn + kSEPS;
+    const float sd = sqrtf(var);
+    const float Sg = Sg0 * sc, Sgx = Sgx0 * sc;                 // sums of g = dy*scale
+    const float dvar = -0.5f * Sgx / (var * sd);
+    const float dmu = -Sg / sd + dvar * 2.f * cpad * mean / fn;
+    for (int r = r0 + rg; r < r1; r += 8) {
+        const float d = xb[(size_t)r * RN_D + c] - mean;
+        db[(size_t)r * RN_D + c] = gb[(size_t)r * RN_D + c] * sc / sd + dvar * 2.f * d / fn + dmu / fn;
+    }
+    if (lead) {
+        part_b[c] = Sgx0 / sd;
+        part_b[128 + c] = Sg0;
+    }
+}
 __global__ void __launch_bounds__(256) k_gn_bwd(PackInfo pk, const float* __restrict__ x, const float* __restrict__ dy,
         const float* __restrict__ scale, int t_tot, float* __restrict__ dx, float* __restrict__ part) {
     // grid (RNA, 32-channel chunk): thread = (channel c of the chunk, row group rg of 8); the 8 groups are folded in fixed order
@@ -459,22 +479,8 @@ __global__ void __launch_bounds__(256) k_gn_bwd(PackInfo pk, const float* __rest
     }
     red[0][rg][cl] = ss; red[1][rg][cl] = sg; red[2][rg][cl] = sgx;
     __syncthreads();
-    const float cpad = (float)(t_tot - n), fn = (float)n;
     const float Ss = fold(0), Sg0 = fold(1), Sgx0 = fold(2);
-    const float var = (Ss + cpad * mean * mean) / fn + kSEPS;
-    const float sd = sqrtf(var), sc = scale[c];
-    const float Sg = Sg0 * sc, Sgx = Sgx0 * sc;                 // sums of g = dy*scale
-    const float dvar = -0.5f * Sgx / (var * sd);
-    const float dmu = -Sg / sd + dvar * 2.f * cpad * mean / fn;
-    float* db = dx + base;
-    for (int r = rg; r < n; r += 8) {
-        const float d = xb[(size_t)r * RN_D + c] - mean;
-        db[(size_t)r * RN_D + c] = gb[(size_t)r * RN_D + c] * sc / sd + dvar * 2.f * d / fn + dmu / fn;
-    }
-    if (rg == 0) {
-        part[(size_t)b * 256 + c] = Sgx0 / sd;
-        part[(size_t)b * 256 + 128 + c] = Sg0;
-    }
+    gn_bwd_tail(Ss, Sg0, Sgx0, mean, n, t_tot, scale[c], xb, gb, dx + base, c, 0, n, rg, rg == 0, part + (size_t)b * 256);
 }
 // ---- the same backward for LONG RNAs (T > GN_SPLIT_T): with one workgroup per (RNA, 32-channel chunk) a batch of a few 4,000-nt RNAs runs on 28 of
 // the 256 CUs (231 us per call on the config-3 epoch).  Here the rows of an RNA are cut into `nsplit` ranges (grid.z): pass A accumulates the four
@@ -526,25 +532,12 @@ __global__ void __launch_bounds__(256) k_gn_bwd_apply(PackInfo pk, const float* 
     const size_t base = (size_t)pk.cu[b] * RN_D;
     const float* xb = x + base;
     const float* gb = dy + base;
-    const float fn = (float)n, cpad = (float)(t_tot - n);
+    const float fn = (float)n;
     const float pv = xb[c];
     const float dm = S1 / fn, mean = pv + dm;                   // mean - pivot, mean
     const float Ss = S2 - fn * dm * dm;                         // sum (x - mean)^2
     const float Sgx0 = Sgp - dm * Sg0;                          // sum g (x - mean)
-    const float var = (Ss + cpad * mean * mean) / fn + kSEPS;
-    const float sd = sqrtf(var), sc = scale[c];
-    const float Sg = Sg0 * sc, Sgx = Sgx0 * sc;
-    const float dvar = -0.5f * Sgx / (var * sd);
-    const float dmu = -Sg / sd + dvar * 2.f * cpad * mean / fn;
-    float* db = dx + base;
-    for (int r = r0 + rg; r < r1; r += 8) {
-        const float d = xb[(size_t)r * RN_D + c] - mean;
-        db[(size_t)r * RN_D + c] = gb[(size_t)r * RN_D + c] * sc / sd + dvar * 2.f * d / fn + dmu / fn;
-    }
-    if (rg == 0 && z == 0) {
-        part[(size_t)b * 256 + c] = Sgx0 / sd;
-        part[(size_t)b * 256 + 128 + c] = Sg0;
-    }
+    gn_bwd_tail(Ss, Sg0, Sgx0, mean, n, t_tot, scale[c], xb, gb, dx + base, c, r0, r1, rg, rg == 0 && z == 0, part + (size_t)b * 256);
 }
 void t_gn_bwd(const PackInfo& pk, const float* x, const float* dy, const float* scale, int t_tot, float* dx, float* dscale,
               float* dshift, TCall& cx) {

@@ -258,7 +258,7 @@ int bert_fwd(Tr& t, const Bert& b, BertTape& tp, float* x_in, float* out, unsign
             if (t_attention_fwd(t.pk, tp.qkv[j], b.heads, tp.o[j], tp.st[j], t.dr, site_att0 + (unsigned)j, t.cx.s)) return 1;
         lin_fwd(t, a.out, tp.o[j], RN_D, tp.t[j], RN_D);
         t_add(t.rn(), tp.x[j], tp.t[j], RN_D, t.cx.s);                                          // residual (functional.py:165)
-        launch_graph_norm_packed(t.pk, tp.t[j], nullptr, tp.x[j + 1], rawp(t.c, a.gn_scale), rawp(t.c, a.gn_shift),
+        launch_graph_norm_packed(t.pk, tp.t[j], tp.x[j + 1], rawp(t.c, a.gn_scale), rawp(t.c, a.gn_shift),
                                  t.c->cfg.padding_len, t.cx.s);
     }
     ffn_fwd(t, b.ffn, tp.x[b.attn.size()], RN_D, tp.pre, out, site_ffn0);
@@ -343,7 +343,7 @@ void layers_fwd_f32(Tr& t) {
         const MpnnLayer& m = c->mpnn[l];
         mlp_edge_fwd(t, m.msg, w.h[l], w.e[l], w.pm1[l], w.pm2[l], site_msg(l, 0));
         t_seg_mean(t.pk, k, w.nbr, m.msg.depth > 1 ? w.pm2[l] : w.pm1[l], w.h[l], w.hpre[l], t.dr, site_msg(l, m.msg.depth - 1), s);
-        launch_graph_norm_packed(t.pk, w.hpre[l], nullptr, w.h[l + 1], rawp(c, m.gn_scale), rawp(c, m.gn_shift), t.t_norm, s);
+        launch_graph_norm_packed(t.pk, w.hpre[l], w.h[l + 1], rawp(c, m.gn_scale), rawp(c, m.gn_shift), t.t_norm, s);
         if (l + 1 < L) {
             mlp_edge_fwd(t, m.edge, w.h[l + 1], w.e[l], w.pu1[l], w.pu2[l], site_edge(l, 0));
             t_edge_residual(t.pk, k, w.nbr, w.e[l], m.edge.depth > 1 ? w.pu2[l] : w.pu1[l], w.e[l + 1], t.dr, site_edge(l, m.edge.depth - 1), s);
@@ -463,7 +463,7 @@ void layers_fwd_mixed(Tr& t) {
         mlp_edge_fwd_mixed(t, m.msg, w.h[l], eb(w.e[l]), eb(w.pm1[l]), eb(w.pm2[l]), site_msg(l, 0), nullptr, 0u);
         te_seg_mean(t.pk, k, w.nbr, eb(m.msg.depth > 1 ? w.pm2[l] : w.pm1[l]), w.h[l], w.hpre[l], t.dr, site_msg(l, m.msg.depth - 1), s,
                     m.msg.depth > 1 ? eb(w.pm2[l]) : nullptr);
-        launch_graph_norm_packed(t.pk, w.hpre[l], nullptr, w.h[l + 1], rawp(c, m.gn_scale), rawp(c, m.gn_shift), t.t_norm, s);
+        launch_graph_norm_packed(t.pk, w.hpre[l], w.h[l + 1], rawp(c, m.gn_scale), rawp(c, m.gn_shift), t.t_norm, s);
         if (l + 1 < L)
             mlp_edge_fwd_mixed(t, m.edge, w.h[l + 1], eb(w.e[l]), eb(w.pu1[l]), eb(w.pu2[l]), site_edge(l, 0), eb(w.e[l + 1]),
                                site_edge(l, m.edge.depth - 1));
@@ -570,13 +570,13 @@ static int train_forward_impl(Tr& t, const float* coords, const float* mask, flo
     // node embedding (feature.py:531-538, 591)
     lin_fwd(t, c->raw_project, w.raw_p, RN_RAWP, w.x0, RN_D);
     if (bert_fwd(t, c->emb, w.emb, w.x0, w.n1, site_emb_att(0), site_emb_ffn(0))) return fail(RNAMPNN_ERR_UNSUPPORTED, "head dim unsupported");
-    launch_graph_norm_packed(t.pk, w.n1, nullptr, w.h[0], rawp(c, c->feat_gn_scale), rawp(c, c->feat_gn_shift), t.t_norm, s);
+    launch_graph_norm_packed(t.pk, w.n1, w.h[0], rawp(c, c->feat_gn_scale), rawp(c, c->feat_gn_shift), t.t_norm, s);
     // ResMPNN layers
     if (t.mixed) layers_fwd_mixed(t); else layers_fwd_f32(t);
     // post fusion, raw embedding, readout (rnampnn.py:179-181)
     if (bert_fwd(t, c->post, w.post, w.h[L], w.hp, site_post_att(0), site_post_ffn(0))) return fail(RNAMPNN_ERR_UNSUPPORTED, "head dim unsupported");
     ffn_fwd(t, c->raw_ffn, w.raw_p, RN_RAWP, w.raw_pre, w.r1, site_raw(0));
-    launch_graph_norm_packed(t.pk, w.r1, nullptr, w.re, rawp(c, c->rawffn_gn_scale), rawp(c, c->rawffn_gn_shift), t.t_norm, s);
+    launch_graph_norm_packed(t.pk, w.r1, w.re, rawp(c, c->rawffn_gn_scale), rawp(c, c->rawffn_gn_shift), t.t_norm, s);
     {   // readout on cat(hp, re): first Linear split over the two sources
         const Lin& r0 = c->readout[0];
         bool single = c->readout.size() == 1;
