@@ -476,6 +476,56 @@ int rnampnn_design_avoid(const float* logits, int64_t n_rows, const float* mask,
                          const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position,
                          const uint8_t* delta, int32_t n_states, uint64_t terminal, int8_t* seqs, float* seq_nll,
                          int32_t* infeasible, int32_t* hits, int32_t* avoid_miss, void* stream);
+/* Design PROFILES in ONE launch each (csrc/design_profile.hip): what rnampnn_design_count and rnampnn_design_avoid draw FROM, not draws - the
+ * exact per-position marginals, log partition sums and entropy of the distribution the draw entry of the same mode samples, in fp64.  The
+ * inputs mean exactly what they mean in that draw entry: both layouts, z_t(c) = ((double) logit_t(c) + (double) bias_t(c)) / (double)
+ * temperature, the admitted sets, "an empty mask is drawn free and counts 1 in `infeasible`", "a pair without an admitted compatible cell
+ * becomes two single positions and counts 2", wobble and the validation of `partner`, the clamping of the window and the target rule, the live
+ * and the dead states.  There is no S, no seed and no seqs.  Outputs, each nullable:
+ *   marginals (B,T,4) f64  padded in both layouts, 16-byte aligned; P(x_t = c) under the distribution the draw entry samples from; written as 0
+ *                          at t >= n_b, so stale bytes are overwritten
+ *   log_z (B) f64          the log partition sum of z over the set drawn from
+ *   log_z_free (B) f64     the sum over t of the LSE over all four classes of z_t(c): no `allowed`, no pairs, no window, no motifs;
+ *                          log_z - log_z_free <= 0 is the log of the mass the constraints keep (0 to the rounding of two sums added in
+ *                          different orders when they keep all of it)
+ *   entropy (B) f64        log_z - sum over t, c of P_t(c) z_t(c), in nats; a term with P_t(c) = 0 is skipped
+ *   infeasible (B) i32, count_miss / avoid_miss (B) i32   the draw entry's values, byte for byte
+ * An RNA of length 0 has log_z = log_z_free = entropy = 0.
+ *   rnampnn_design_count_profile.  Leaves p_t(d), tree, window and target are rnampnn_design_count's.  K* = the counts of the window with a
+ *     finite root coefficient; on a miss, the target alone.  log_z = LSE over K* of the root coefficients.  Outside pass, top down, log domain:
+ *     O_root(k) = 0 for k in K*, else -inf; a node with outside O and halves L, R gives O_L(a) = LSE over k of O(k) + R(k - a) and
+ *     O_R(b) = LSE over k of O(k) + L(k - b), k over the node's coefficients with k - a (k - b) among the sibling's; a node whose right half is
+ *     empty hands O to its left half.  With the cap every index stays <= cap and O is -inf above K*, so truncation is exact as it is for the
+ *     inside pass.  A single position: P_t(c) = exp(z_t(c) + O_t(bit(counted_t, c)) - log_z) for the admitted c, else 0.  A feasible pair
+ *     i < j: cell (a, b) has probability exp(z_i(a) + z_j(b) + O_i(d_ab) - log_z); P_i(a) and P_j(b) are its row and column sums.  Under
+ *     the k_min rule (no finite root coefficient) every leaf is restricted to the admitted cells of its own smallest d and normalised over
+ *     them; log_z is the sum over the leaves of p_t(that d).
+ *   rnampnn_design_avoid_profile.  The backward table l_t(a) is rnampnn_design_avoid's.  Forward: alpha_0(0) = 0, alpha_0(a != 0) = -inf;
+ *     alpha_{t+1}(a') = LSE over the admitted cells (a, c) with delta(a,c) = a' live of alpha_t(a) + z_t(c).  log_z = l_0(0).
+ *     P_t(c) = the sum over a of exp(alpha_t(a) + z_t(c) + l_{t+1}(delta(a,c)) - log_z) over the admitted cells.  With avoid_miss = 1
+ *     every position is the softmax over its admitted classes - what the draw entry falls back to - and log_z is the sum of their LSEs.
+ *     A non-null `partner` is RNAMPNN_ERR_UNSUPPORTED, as in the draw entry.
+ * The order of summation is not part of the contract: the outputs agree with a float64 restatement to rounding (tests hold marginals to 1e-8
+ * absolute and the scalars to 1e-8 max(1, |value|)) and are byte-identical between two calls, between the layouts and between batches.
+ * Non-finite logits or bias of one RNA may make THAT RNA's outputs NaN; nothing faults, no index leaves its array, no other RNA changes.
+ * One 256-thread workgroup per RNA.  Dynamic LDS:
+ *   count:  bytes(T, cap) = 16 * doubles(T, cap) + 240, doubles as in rnampnn_design_count (the inside AND the outside tree: a child's outside
+ *           reads its sibling's inside): 14,432 bytes at (T = 128, cap 8), 83,296 at (300, 300); T <= 1457 at cap 8, 1128 at cap 16, 535 for cap >= T
+ *   avoid:  bytes(T, L) = (32 + 8 L) T + 16 ceil(T / 16) + 3,680, L the live states: 44,784 bytes at (T = 300, L = 13); T <= 1168 at L = 13 (163,696 bytes), 554 at L = 32, 293 at L = 64
+ * RNAMPNN_ERR_UNSUPPORTED when that exceeds 160 KiB = 163,840 bytes; the message names the bytes, the limit and the largest T.  No workspace,
+ * no atomics, no runtime fill / copy node, no host synchronisation; the call can sit inside a captured graph.  RNAMPNN_ERR_BAD_ARG, before
+ * anything is launched: the cases of the draw entry but those about S; marginals not 16-byte aligned.  Then, in both entries
+ * alike: the `partner` refusal (avoid); with every output null RNAMPNN_OK without a launch, whatever T is; the LDS check. */
+int rnampnn_design_count_profile(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
+                                 float temperature, const uint8_t* allowed, const int32_t* partner, int32_t wobble, const float* bias,
+                                 int32_t bias_per_position, const uint8_t* counted, const int32_t* count_lo, const int32_t* count_hi,
+                                 int32_t count_cap, double* marginals, double* log_z, double* log_z_free, double* entropy,
+                                 int32_t* infeasible, int32_t* count_miss, void* stream);
+int rnampnn_design_avoid_profile(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
+                                 float temperature, const uint8_t* allowed, const int32_t* partner, int32_t wobble, const float* bias,
+                                 int32_t bias_per_position, const uint8_t* delta, int32_t n_states, uint64_t terminal,
+                                 double* marginals, double* log_z, double* log_z_free, double* entropy, int32_t* infeasible,
+                                 int32_t* avoid_miss, void* stream);
 
 /* -- training ---------------------------------------------------------------------------- */
 /* The training surface of RNAMPNN (rnampnn.py:187-207 + Lightning's loss.backward()):

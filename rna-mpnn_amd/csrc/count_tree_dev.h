@@ -360,6 +360,73 @@ __device__ __forceinline__ void ct_design(const CtArgs& a, unsigned char* lds) {
     if (tid == 0 && a.count) a.count[(size_t)s * a.B + b] = (int)cnt;
 }
 
+// Phase A on its own, for a kernel that reads the tree without drawing from it (k_design_count_profile, design_profile.hip): the inside
+// tree of RNA b bottom-up into `tree`, the statements of ct_design's phase A (which stays where it is, so the draw kernels keep their
+// code), and on the way `bad`, k_min per wave into s_i (SETS only) and `free_sum` += the LSE of z_t over all four classes for every
+// position this thread loads.  Every thread calls it; the tree, s_leaf (the only leaf of a 1-mer) and s_i are valid on return.
+template <bool SETS>
+__device__ __forceinline__ void ct_inside(const CtArgs& a, double* tree, double* s_leaf, int* s_i, size_t pad0, long long row0, int n, int tid,
+                                          int& bad, double& free_sum) {
+    const int T = a.T, cap = a.cap;
+    const int Ln = n > 1 ? 32 - __clz(n - 1) : 0;
+    int kmin = 0;
+    for (int i = tid; 2 * i < n; i += SC_THREADS) {
+        const int t = 2 * i;
+        double l0, l1, l2, r0 = 0.0, r1 = -INFINITY, r2 = -INFINITY;
+        const CtLeaf ll = ct_leaf<SETS>(a, pad0, row0, n, t, l0, l1, l2, bad);
+        free_sum += ds_lse<4>(ll.p.z, 15);
+        if (t + 1 < n) {
+            const CtLeaf lr = ct_leaf<SETS>(a, pad0, row0, n, t + 1, r0, r1, r2, bad);
+            free_sum += ds_lse<4>(lr.p.z, 15);
+        }
+        if (SETS) kmin += ct_min_d(l0, l1, l2) + ct_min_d(r0, r1, r2);
+        if (n == 1) { s_leaf[0] = l0; s_leaf[1] = l1; s_leaf[2] = l2; break; }
+        double* out = tree + a.base[1] + (size_t)i * ct_stride(1, T, cap);
+        const int deg = ct_deg(1, i, n, cap);
+        const double l[3] = {l0, l1, l2}, r[3] = {r0, r1, r2};
+#pragma unroll
+        for (int k = 0; k <= 4; ++k) {
+            double mx = -INFINITY, sum = 0.0;
+#pragma unroll
+            for (int c = 0; c <= 2; ++c)
+                if (c <= k && k - c <= 2) mx = fmax(mx, l[c] + r[k - c]);
+#pragma unroll
+            for (int c = 0; c <= 2; ++c)
+                if (c <= k && k - c <= 2) sum += exp(l[c] + r[k - c] - mx);
+            if (k <= deg) out[k] = t + 1 < n ? (mx > -INFINITY ? mx + log(sum) : -INFINITY) : (k <= 2 ? l[k < 2 ? k : 2] : -INFINITY);
+        }
+    }
+    if (SETS) {
+        kmin = sc_wave_sum(kmin);
+        if ((tid & 63) == 0) s_i[tid >> 6] = kmin;
+    }
+    __syncthreads();
+    for (int l = 2; l <= Ln; ++l) {
+        const int stride = ct_stride(l, T, cap), cstride = ct_stride(l - 1, T, cap), nodes = ct_nodes(l, n), cnodes = ct_nodes(l - 1, n);
+        for (int idx = tid; idx < nodes * stride; idx += SC_THREADS) {
+            const int i = idx / stride, k = idx - i * stride;
+            if (k > ct_deg(l, i, n, cap)) continue;
+            const double* L = tree + a.base[l - 1] + (size_t)(2 * i) * cstride;
+            const double* R = L + cstride;
+            const int degL = ct_deg(l - 1, 2 * i, n, cap);
+            double v;
+            if (2 * i + 1 < cnodes) {
+                const int degR = ct_deg(l - 1, 2 * i + 1, n, cap), c0 = max(0, k - degR), c1 = min(k, degL);
+                double mx = -INFINITY, sum = 0.0;
+#pragma unroll 4
+                for (int c = c0; c <= c1; ++c) mx = fmax(mx, L[c] + R[k - c]);
+#pragma unroll 4
+                for (int c = c0; c <= c1; ++c) sum += exp(L[c] + R[k - c] - mx);
+                v = mx > -INFINITY ? mx + log(sum) : -INFINITY;
+            } else {
+                v = k <= degL ? L[k] : -INFINITY;
+            }
+            tree[a.base[l] + idx] = v;
+        }
+        __syncthreads();
+    }
+}
+
 // doubles of the levels 1..ceil(log2 T): node (l, i) holds min(2 * its extent within T, T, cap) + 1; base[l] (when given) = first double
 // of level l
 inline size_t ct_tree_doubles(int T, int cap, unsigned* base) {

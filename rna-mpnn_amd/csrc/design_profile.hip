@@ -1,0 +1,535 @@
+// rnampnn_design_count_profile / rnampnn_design_avoid_profile: INFERENCE next to the draws of rnampnn_design_count and
+// rnampnn_design_avoid.  Each returns, in one launch and in fp64, the exact distribution its draw entry samples from - per-position marginals
+// P(x_t = c), the log partition sum over the set drawn from (log_z), the free log partition sum (log_z_free) and the entropy - together with
+// the draw entry's own `infeasible` and `*_miss`.  The contract is the one include/rnampnn_hip.h documents and tests/_design_profile_ref.py
+// restates.  One 256-thread workgroup per RNA, no sample axis, no workspace, no atomics, no runtime fill / copy node, no host synchronisation.
+//
+// k_design_count_profile.  The leaves, the tree, the window, the target and the k_min rule are count_tree_dev.h's (ct_leaf, ct_inside,
+// ct_deg / ct_stride / ct_nodes, ct_min_d).  (A) ct_inside: the inside tree bottom-up into LDS, k_min and the free sum on the way.  (B) wave 0:
+// the window, the target and count_miss exactly as ct_design forms them; K* and log_z; the root's outside O(k) = 0 on K*, -inf elsewhere.
+// (C) the OUTSIDE pass top-down into a second tree of the same layout: O_L(a) = LSE_k O(k) + R(k - a), O_R(b) = LSE_k O(k) + L(k - b), dealt
+// flat over (child node, coefficient); a node whose right half is empty hands O to its left half.  (D) one level-1 node per thread: the two
+// leaves again from the rows, their outsides from the node's, then P = exp(z + O(d) - log_z) per admitted class / cell; the owner of a pair
+// writes both ends.  Under the k_min rule (C) is skipped and every leaf is normalised over the cells of its own smallest d.  (E) padding
+// rows as zeros, three fixed-order fp64 workgroup sums (free, sum of P z, the k_min log_z), thread 0 writes the scalars.
+//   LDS bytes(T, cap) = 16 * doubles(T, cap) + 240: the inside and the outside tree (the outside of a child needs its parent's outside
+//   and its SIBLING's inside at once, so neither can be overwritten), doubles(T, cap) as in rnampnn_design_count, and 240 bytes of scratch.
+//   160 KiB holds T <= 1457 at cap 8 (163,792 bytes) and T <= 535 at cap >= T (the draw kernel: 2867 and 1017).
+//
+// k_design_avoid_profile.  The rows, the automaton's tables and the backward table l_t(a) are k_design_avoid's, statement for statement.
+// Then wave 0, lane = state, walks FORWARD once: alpha_t(a) lives in the lane's register; per step the lane turns its four cells into
+// exp(alpha + z + l_{t+1}(delta) - log_z), a wave butterfly sums them into P_t(c) (lane 0 writes the row and adds P z), and alpha_{t+1}(a') is
+// gathered by lane a' over its predecessor cells - a list per state built once (counting sort over the 4 A cells, cell order, four cells to a word) - from the
+// candidates alpha + z the lanes parked in LDS: the target takes their maximum, the sources exponentiate their own four candidates
+// against it, the target adds - eight exps per lane and step whatever the fan-in of a state.  With avoid_miss = 1 there is no chain: all threads write the per-position softmax.
+//   LDS bytes(T, L) = (32 + 8 L) T + 16 ceil(T / 16) + 3,680: the fp64 rows, the table of L live states, the masks; 2,560 for the
+//   candidates and the maxima, 512 for the automaton, 448 for the predecessor lists, 160 for the sums and the reduction's scratch.
+//   160 KiB holds T <= 1168 at L = 13 (no run longer than 3) and T <= 293 at L = 64 (the draw kernel: 1064 and 290).
+// Non-finite rows can make the outputs of THAT RNA NaN; no index depends on a value, so nothing faults and no other RNA changes.
+#include "count_tree_dev.h"
+
+namespace {
+struct PfOut {
+    double* marg;                // (B,T,4) or null
+    double* log_z;               // (B) or null
+    double* log_z_free;          // (B) or null
+    double* entropy;             // (B) or null
+};
+
+// The workgroup's totals of three doubles: wave butterfly, then one LDS hop over the four waves in ascending order - a fixed order, so two
+// calls give the same bytes.  Valid in thread 0 only; every thread calls it (one barrier).  s_d holds 3 x SC_WAVES doubles.
+__device__ __forceinline__ double pf_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ void pf_block_sums(double& x, double& y, double& z, int tid, double (*s_d)[SC_WAVES]) {
+    x = pf_wave_sum(x); y = pf_wave_sum(y); z = pf_wave_sum(z);
+    if ((tid & 63) == 0) { s_d[0][tid >> 6] = x; s_d[1][tid >> 6] = y; s_d[2][tid >> 6] = z; }
+    __syncthreads();
+    if (tid != 0) return;
+    x = 0.0; y = 0.0; z = 0.0;
+#pragma unroll
+    for (int w = 0; w < SC_WAVES; ++w) { x += s_d[0][w]; y += s_d[1][w]; z += s_d[2][w]; }
+}
+// P z for the entropy: a class of probability 0 is skipped (its z may be -inf)
+__device__ __forceinline__ double pf_pz(double p, double z) { return p != 0.0 ? p * z : 0.0; }
+__device__ __forceinline__ void pf_store4(double* marg, size_t row, const double (&p)[4]) {
+    if (!marg) return;
+    double2* out = reinterpret_cast<double2*>(marg + 4 * row);
+    out[0] = make_double2(p[0], p[1]); out[1] = make_double2(p[2], p[3]);
+}
+// what every thread and the final writer share
+__device__ __forceinline__ void pf_finish(const PfOut& o, const DesignArgs& a, int32_t* miss_out, int miss, int b, int n, int tid, int bad, double free_sum,
+                                          double pz_sum, double lz_sum, bool lz_from_sum, double log_z, const DsScratch& sc, double (*s_d)[SC_WAVES]) {
+    const double zero[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int t = n + tid; t < a.T; t += SC_THREADS) pf_store4(o.marg, (size_t)b * a.T + t, zero);
+    float f0 = 0.f, f1 = 0.f;
+    sc_block_sums(bad, f0, f1, tid, sc.s_i, sc.s_f);
+    pf_block_sums(free_sum, pz_sum, lz_sum, tid, s_d);
+    if (tid != 0) return;
+    const double lz = n == 0 ? 0.0 : lz_from_sum ? lz_sum : log_z;
+    if (o.log_z) o.log_z[b] = lz;
+    if (o.log_z_free) o.log_z_free[b] = n == 0 ? 0.0 : free_sum;
+    if (o.entropy) o.entropy[b] = n == 0 ? 0.0 : lz - pz_sum;
+    if (a.infeasible) a.infeasible[b] = bad;
+    if (miss_out) miss_out[b] = miss;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the count profile
+constexpr size_t PF_CT_SCRATCH = 240;          // DS_SCRATCH 48 | at 48 two flags | at 64 the 1-mer's leaf | at 96 its outside | at 120 log_z | at 128 3 x 4 sums
+static_assert(DS_SCRATCH == 48 && CT_LDS_SCRATCH == 96, "the layout of the count profile's scratch");
+
+struct PfCtArgs : CtArgs { PfOut out; };
+
+// LSE_k over k = k0 .. k1 of O[k] + p(k - k0 .. ) with the sibling LEAF's polynomial (s0, s1, s2): the outside of a leaf below a level-1 node
+__device__ __forceinline__ double pf_leaf_outside(const double* O, int deg, int a, double s0, double s1, double s2) {
+    double v[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) v[d] = a + d <= deg ? O[a + d] + ct_pick(s0, s1, s2, d) : -INFINITY;
+    return ds_lse<3>(v, 7);
+}
+
+// The marginals of leaf t from w(d) = the log of what multiplies exp(z) of a cell that counts d; -> its share of the sum of P z.
+__device__ __forceinline__ double pf_leaf_out(const PfCtArgs& a, const CtLeaf& lf, size_t pad0, int t, double w0, double w1, double w2) {
+    if (lf.kind == 2) return 0.0;                                   // written by the owner of the pair
+    double pz = 0.0;
+    if (lf.kind == 0) {
+        double p[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            p[c] = ((lf.p.m >> c) & 1) ? exp(lf.p.z[c] + ct_pick(w0, w1, w2, (lf.ci >> c) & 1)) : 0.0;
+            pz += pf_pz(p[c], lf.p.z[c]);
+        }
+        pf_store4(a.out.marg, pad0 + t, p);
+        return pz;
+    }
+    double pi[4] = {0.0, 0.0, 0.0, 0.0}, pj[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        const int d = ((lf.ci >> (c >> 2)) & 1) + ((lf.cj >> (c & 3)) & 1);
+        const double pc = ((lf.m16 >> c) & 1) ? exp(lf.p.z[c >> 2] + lf.pj.z[c & 3] + ct_pick(w0, w1, w2, d)) : 0.0;
+        pi[c >> 2] += pc; pj[c & 3] += pc;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) pz += pf_pz(pi[c], lf.p.z[c]) + pf_pz(pj[c], lf.pj.z[c]);
+    pf_store4(a.out.marg, pad0 + t, pi);
+    pf_store4(a.out.marg, pad0 + lf.j, pj);
+    return pz;
+}
+
+__global__ void __launch_bounds__(SC_THREADS) k_design_count_profile(PfCtArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char pfc_lds[];
+    double* tree = reinterpret_cast<double*>(pfc_lds);
+    double* outs = reinterpret_cast<double*>(pfc_lds + a.lds_tree);                          // the outside tree, the inside tree's layout
+    unsigned char* scr = pfc_lds + 2 * (size_t)a.lds_tree;
+    const DsScratch sc = ds_scratch(scr);
+    int* s_flag = reinterpret_cast<int*>(scr + 48);                                          // [0]: every leaf at its own minimum; [1]: count_miss
+    double* s_leaf = reinterpret_cast<double*>(scr + 64);                                    // 3 doubles
+    double* o_leaf = reinterpret_cast<double*>(scr + 96);                                    // 3 doubles
+    double* s_logz = reinterpret_cast<double*>(scr + 120);
+    double (*s_d)[SC_WAVES] = reinterpret_cast<double (*)[SC_WAVES]>(scr + 128);
+    const int b = blockIdx.x, tid = threadIdx.x, T = a.T, cap = a.cap;
+    int n;
+    long long row0;
+    sc_extent(a, b, tid, sc.s_f[0], n, row0);
+    const size_t pad0 = (size_t)b * T;
+    const int Ln = n > 1 ? 32 - __clz(n - 1) : 0;
+    int bad = 0;
+    double free_sum = 0.0;
+    // ---- A: the inside tree
+    ct_inside<true>(a, tree, s_leaf, sc.s_i, pad0, row0, n, tid, bad, free_sum);
+    // ---- B: the window, the target, K*, log_z and the root's outside
+    if (tid < 64 && n > 0) {
+        const double* root = Ln ? tree + a.base[Ln] : s_leaf;
+        double* oroot = Ln ? outs + a.base[Ln] : o_leaf;
+        const int deg = Ln ? ct_deg(Ln, 0, n, cap) : min(1, cap);
+        const int lo = min(max((int)a.lo[b], 0), deg), hi = max(min(max((int)a.hi[b], 0), deg), lo);
+        int K = -1, miss = 0;
+        bool any = false, at_min = false;
+        for (int k = lo; k <= min(hi, deg); ++k) any = any || ct_finite(root[k]);
+        if (!any) {
+            bool found = false;
+            for (int d = 1; d <= deg && !found; ++d) {                 // the nearest reachable count, the lower one first
+                const int kl = lo - d, kh = hi + d;
+                if (kl >= 0 && kl <= deg && ct_finite(root[kl])) { K = kl; miss = d; found = true; }
+                else if (kh <= deg && ct_finite(root[kh])) { K = kh; miss = d; found = true; }
+            }
+            if (!found) {                                              // nothing in 0 .. min(n, cap): k_min, every leaf at its own minimum
+                int km = 0;
+#pragma unroll
+                for (int w = 0; w < SC_WAVES; ++w) km += sc.s_i[w];
+                miss = km < lo ? lo - km : km > hi ? km - hi : 0;
+                at_min = true;
+            }
+        }
+        // K*: the finite counts of the window, or the target alone; log_z = LSE over K* of the root, by the wave in a fixed order
+        double mx = -INFINITY, sum = 0.0;
+        for (int k = tid; k <= deg; k += 64) {
+            const bool in = (any ? (k >= lo && k <= hi) : k == K) && ct_finite(root[k]);
+            if (in) mx = fmax(mx, root[k]);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+        for (int k = tid; k <= deg; k += 64) {
+            const bool in = (any ? (k >= lo && k <= hi) : k == K) && ct_finite(root[k]);
+            if (in) sum += exp(root[k] - mx);
+            oroot[k] = in ? 0.0 : -INFINITY;
+        }
+        sum = pf_wave_sum(sum);
+        if (tid == 0) {
+            s_flag[0] = at_min ? 1 : 0; s_flag[1] = miss;
+            *s_logz = mx > -INFINITY ? mx + log(sum) : -INFINITY;
+        }
+    }
+    __syncthreads();
+    const bool at_min = n > 0 && s_flag[0] != 0;                   // the same in every thread
+    const int miss = n > 0 ? s_flag[1] : 0;
+    const double log_z = n > 0 ? *s_logz : 0.0;
+    // ---- C: the outside pass, top down: level l hands its children at level l - 1 their outsides
+    for (int l = Ln; l >= 2 && !at_min; --l) {
+        const int stride = ct_stride(l, T, cap), cstride = ct_stride(l - 1, T, cap), cnodes = ct_nodes(l - 1, n);
+        for (int idx = tid; idx < cnodes * cstride; idx += SC_THREADS) {
+            const int j = idx / cstride, c = idx - j * cstride;
+            if (c > ct_deg(l - 1, j, n, cap)) continue;
+            const int i = j >> 1, sib = j ^ 1, degP = ct_deg(l, i, n, cap);
+            const double* O = outs + a.base[l] + (size_t)i * stride;
+            double v;
+            if (sib < cnodes) {
+                const double* Sb = tree + a.base[l - 1] + (size_t)sib * cstride;
+                const int k1 = min(c + ct_deg(l - 1, sib, n, cap), degP);
+                double mx = -INFINITY, sum = 0.0;
+#pragma unroll 4
+                for (int k = c; k <= k1; ++k) mx = fmax(mx, O[k] + Sb[k - c]);
+#pragma unroll 4
+                for (int k = c; k <= k1; ++k) sum += exp(O[k] + Sb[k - c] - mx);
+                v = mx > -INFINITY ? mx + log(sum) : -INFINITY;
+            } else {
+                v = c <= degP ? O[c] : -INFINITY;                   // an empty right half: the left half is the node
+            }
+            outs[a.base[l - 1] + idx] = v;
+        }
+        __syncthreads();
+    }
+    // ---- D: the leaves of a level-1 node, their outsides and their marginals
+    double pz_sum = 0.0, lz_sum = 0.0;
+    int unused_bad = 0;
+    for (int i = tid; 2 * i < n; i += SC_THREADS) {
+        const int t = 2 * i;
+        const bool two = t + 1 < n;
+        double l0, l1, l2, r0 = 0.0, r1 = -INFINITY, r2 = -INFINITY;
+        const CtLeaf ll = ct_leaf<true>(a, pad0, row0, n, t, l0, l1, l2, unused_bad);
+        CtLeaf lr = ll;
+        if (two) lr = ct_leaf<true>(a, pad0, row0, n, t + 1, r0, r1, r2, unused_bad);
+        double wl0, wl1, wl2, wr0 = -INFINITY, wr1 = -INFINITY, wr2 = -INFINITY;
+        if (at_min) {
+            const int dl = ct_min_d(l0, l1, l2), dr = ct_min_d(r0, r1, r2);
+            const double pl = ct_pick(l0, l1, l2, dl), pr = ct_pick(r0, r1, r2, dr);
+            lz_sum += pl + (two ? pr : 0.0);
+            wl0 = dl == 0 ? -pl : -INFINITY; wl1 = dl == 1 ? -pl : -INFINITY; wl2 = dl == 2 ? -pl : -INFINITY;
+            wr0 = dr == 0 ? -pr : -INFINITY; wr1 = dr == 1 ? -pr : -INFINITY; wr2 = dr == 2 ? -pr : -INFINITY;
+        } else {
+            const double* O = n == 1 ? o_leaf : outs + a.base[1] + (size_t)i * ct_stride(1, T, cap);
+            const int deg = n == 1 ? min(1, cap) : ct_deg(1, i, n, cap);
+            if (two) {
+                wl0 = pf_leaf_outside(O, deg, 0, r0, r1, r2) - log_z; wr0 = pf_leaf_outside(O, deg, 0, l0, l1, l2) - log_z;
+                wl1 = pf_leaf_outside(O, deg, 1, r0, r1, r2) - log_z; wr1 = pf_leaf_outside(O, deg, 1, l0, l1, l2) - log_z;
+                wl2 = pf_leaf_outside(O, deg, 2, r0, r1, r2) - log_z; wr2 = pf_leaf_outside(O, deg, 2, l0, l1, l2) - log_z;
+            } else {                                                // an empty right half: the leaf is the node
+                wl0 = O[0] - log_z; wl1 = (1 <= deg ? O[1] : -INFINITY) - log_z; wl2 = (2 <= deg ? O[2] : -INFINITY) - log_z;
+            }
+        }
+        pz_sum += pf_leaf_out(a, ll, pad0, t, wl0, wl1, wl2);
+        if (two) pz_sum += pf_leaf_out(a, lr, pad0, t + 1, wr0, wr1, wr2);
+    }
+    // ---- E: padding, sums, scalars
+    pf_finish(a.out, a, a.miss, miss, b, n, tid, bad, free_sum, pz_sum, lz_sum, at_min, log_z, sc, s_d);
+}
+
+inline size_t pf_ct_lds_bytes(int T, int cap, size_t& tree) {
+    tree = ct_tree_doubles(T, cap, nullptr) * sizeof(double);
+    return 2 * tree + PF_CT_SCRATCH;
+}
+// the largest T whose two trees fit at that cap (a cap above T is T: the byte count grows with T)
+inline int pf_ct_max_T(int cap) {
+    int T = 1;
+    size_t tree;
+    while (pf_ct_lds_bytes(T + 1, std::min(cap, T + 1), tree) <= DS_LDS_MAX) ++T;
+    return T;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the avoid profile
+constexpr int PF_MAX_STATES = RNAMPNN_DESIGN_AVOID_MAX_STATES;
+constexpr unsigned PF_DEAD = 0xFFu;
+constexpr int PF_PRED_WORDS = (4 * PF_MAX_STATES + 3 * PF_MAX_STATES) / 4;         // 256 cells, each of 64 lists padded to a word
+constexpr size_t PF_AV_FIXED = 8 * 4 * PF_MAX_STATES + 8 * PF_MAX_STATES + 8 * 3 * SC_WAVES + 64 + 2 * 4 * PF_MAX_STATES + 4 * PF_PRED_WORDS;
+static_assert(PF_MAX_STATES == 64, "one lane of a wave per state; `terminal` is one 64-bit word");
+static_assert(PF_AV_FIXED == 3680 && DS_SCRATCH <= 64, "the bytes include/rnampnn_hip.h gives");
+
+struct PfAvArgs : DesignArgs {
+    const uint8_t* delta;        // (A,4)
+    unsigned long long terminal;
+    int A, live;
+    int32_t* miss;               // (B) or null
+    PfOut out;
+};
+
+__device__ __forceinline__ void pf_wave_sync() {                   // LDS written by a lane is read by another lane of the SAME wave
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ void __launch_bounds__(SC_THREADS) k_design_avoid_profile(PfAvArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char pfa_lds[];
+    const int T = a.T, b = blockIdx.x, tid = threadIdx.x, A = a.A, AL = a.live;
+    double* zs = reinterpret_cast<double*>(pfa_lds);                                // [T][4]      z of a position
+    double* tab = zs + 4 * (size_t)T;                                              // [T][AL]     l_t of a live state
+    double* cand = tab + (size_t)AL * T;                                           // [64][4]     alpha_t(a) + z_t(c) of an admitted live cell
+    double* tmax = cand + 4 * PF_MAX_STATES;                                       // [64]        the maximum over the cells that lead into a state
+    double (*s_d)[SC_WAVES] = reinterpret_cast<double (*)[SC_WAVES]>(tmax + PF_MAX_STATES);
+    unsigned char* red = reinterpret_cast<unsigned char*>(s_d + 3);                // the reduction's scratch, 64 bytes
+    const DsScratch sc = ds_scratch(red);
+    unsigned* nx = reinterpret_cast<unsigned*>(red + 64);                          // [64]        delta(a, .), a byte per class
+    unsigned* col = nx + PF_MAX_STATES;                                            // [64]        the table column of delta(a, .), or PF_DEAD
+    unsigned* pw = col + PF_MAX_STATES;                                            // [112]       the predecessor cells 4 a + c of every state, cell order,
+    unsigned char* pcell = reinterpret_cast<unsigned char*>(pw);                   //             four to a word, a state's list starting on a word
+    unsigned char* ms = pcell + 4 * PF_PRED_WORDS;                                 // [T]         the mask of a position
+    const unsigned long long term = a.terminal;
+    int n;
+    long long row0;
+    sc_extent(a, b, tid, sc.s_f[0], n, row0);
+    const size_t pad0 = (size_t)b * T;
+    // ---- A: rows, masks, the free sum and the automaton
+    int bad = 0;
+    double free_sum = 0.0;
+    for (int t = tid; t < n; t += SC_THREADS) {
+        bool empty;
+        const DsPos<double> p = ds_load<double>(a, pad0, row0, t, empty);
+        bad += empty ? 1 : 0;
+        zs[4 * t] = p.z[0]; zs[4 * t + 1] = p.z[1]; zs[4 * t + 2] = p.z[2]; zs[4 * t + 3] = p.z[3];
+        ms[t] = (unsigned char)p.m;
+        free_sum += ds_lse<4>(p.z, 15);
+    }
+    if (tid < PF_MAX_STATES) {
+        unsigned raw = 0, cl = 0;
+        for (int c = 0; c < 4; ++c) {
+            const unsigned nxt = tid < A ? a.delta[4 * tid + c] : PF_DEAD;
+            const bool dead = nxt >= (unsigned)A || ((term >> (nxt & 63u)) & 1ull);
+            raw |= (nxt & 255u) << (8 * c);
+            cl |= (dead ? PF_DEAD : (unsigned)__popcll(~term & ((1ull << (nxt & 63u)) - 1ull))) << (8 * c);      // live states before it
+        }
+        nx[tid] = raw; col[tid] = cl;
+    }
+    __syncthreads();
+    // ---- B: l_t(a), t = n-1 .. 0, as k_design_avoid forms it; one wave, lane = state; then the predecessor lists
+    const bool live = tid < A && !((term >> (tid & 63)) & 1ull);
+    int cc[4] = {0, 0, 0, 0}, ok = 0, mine = 0, pwoff = 0, pcnt = 0;
+    if (tid < PF_MAX_STATES) {
+        const unsigned cl = col[tid];
+        mine = __popcll(~term & ((1ull << tid) - 1ull));
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const unsigned k = (cl >> (8 * c)) & 255u;
+            ok |= (k != PF_DEAD ? 1 : 0) << c;
+            cc[c] = k != PF_DEAD ? (int)k : 0;
+        }
+        for (int t = n - 1; t >= 0; --t) {
+            if (live) {
+                const double* next = tab + (size_t)(t + 1) * AL;
+                double l[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) l[c] = t + 1 < n ? next[cc[c]] : 0.0;
+                const double2 z01 = *reinterpret_cast<const double2*>(zs + 4 * t), z23 = *reinterpret_cast<const double2*>(zs + 4 * t + 2);
+                const double v[4] = {z01.x + l[0], z01.y + l[1], z23.x + l[2], z23.y + l[3]};
+                tab[(size_t)t * AL + mine] = ds_lse<4>(v, (int)ms[t] & ok);
+            }
+            pf_wave_sync();
+        }
+        // the cells (a, c) of a live a < A whose delta is the live state `tid`, counted, scanned over the lanes, then listed in cell order
+        int cnt = 0;
+        for (int cell = 0; cell < 4 * A; ++cell) {
+            const int src = cell >> 2;
+            const bool src_live = !((term >> src) & 1ull);
+            cnt += live && src_live && ((nx[src] >> (8 * (cell & 3))) & 255u) == (unsigned)tid ? 1 : 0;
+        }
+        const int words = (cnt + 3) >> 2;
+        int incl = words;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_up(incl, o, 64);
+            if (tid >= o) incl += v;
+        }
+        pwoff = incl - words;                                       // <= 112 - words: 256 cells and at most three bytes of padding per list
+        pcnt = cnt;
+        for (int w = 0; w < words; ++w) pw[pwoff + w] = 0u;
+        int at = 4 * pwoff;
+        for (int cell = 0; cell < 4 * A; ++cell) {
+            const int src = cell >> 2;
+            const bool src_live = !((term >> src) & 1ull);
+            if (live && src_live && ((nx[src] >> (8 * (cell & 3))) & 255u) == (unsigned)tid) pcell[at++] = (unsigned char)cell;
+        }
+    }
+    __syncthreads();
+    const bool miss = n > 0 && !(tab[0] > -INFINITY);               // state 0 is live and has column 0
+    const double log_z = n > 0 && !miss ? tab[0] : 0.0;
+    double pz_sum = 0.0, lz_sum = 0.0;
+    if (miss) {
+        // ---- C': no admitted sequence avoids the motifs: the per-position softmax over the admitted classes, as the draw falls back to
+        for (int t = tid; t < n; t += SC_THREADS) {
+            const double z[4] = {zs[4 * t], zs[4 * t + 1], zs[4 * t + 2], zs[4 * t + 3]};
+            const int m = ms[t];
+            const double l = ds_lse<4>(z, m);
+            double p[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                p[c] = ((m >> c) & 1) ? exp(z[c] - l) : 0.0;
+                pz_sum += pf_pz(p[c], z[c]);
+            }
+            lz_sum += l;
+            pf_store4(a.out.marg, pad0 + t, p);
+        }
+    } else if (tid < PF_MAX_STATES) {
+        // ---- C: the forward walk; alpha_t(a) in the register of lane a.  The LSE of a state's incoming cells is split so that no lane
+        // runs more than four exps per step whatever the fan-in of its state: the TARGET takes the maximum over its list, the SOURCES
+        // turn their own four candidates into exp(candidate - that maximum) in place, the target adds them up in cell order.
+        double alpha = tid == 0 ? 0.0 : -INFINITY;
+        const unsigned raw = nx[tid];
+        const unsigned w0 = pcnt > 0 ? pw[pwoff] : 0u, w1 = pcnt > 4 ? pw[pwoff + 1] : 0u;      // the first eight cells of the list stay in registers
+        // over the list, four cells to a word: one read for the word (none for the first two), four independent reads of the candidates
+        auto over_list = [&](auto visit) {
+            for (int w = 0; 4 * w < pcnt; ++w) {
+                const unsigned cells = w == 0 ? w0 : w == 1 ? w1 : pw[pwoff + w];
+                double v[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = cand[(cells >> (8 * j)) & 255u];
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (4 * w + j < pcnt) visit(v[j]);
+            }
+        };
+        for (int t = 0; t < n; ++t) {
+            const double2 z01 = *reinterpret_cast<const double2*>(zs + 4 * t), z23 = *reinterpret_cast<const double2*>(zs + 4 * t + 2);
+            const double z[4] = {z01.x, z01.y, z23.x, z23.y};
+            const int m = live ? ((int)ms[t] & ok) : 0;
+            const double* next = tab + (size_t)(t + 1) * AL;
+            double p[4], av[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const bool in = (m >> c) & 1;
+                const double l = t + 1 < n ? next[cc[c]] : 0.0;     // (cc is 0 for a dead cell: in bounds, not used)
+                av[c] = alpha + z[c];
+                p[c] = pf_wave_sum(in ? exp(av[c] + l - log_z) : 0.0);
+                cand[4 * tid + c] = in ? av[c] : -INFINITY;
+            }
+            if (tid == 0) {
+                pf_store4(a.out.marg, pad0 + t, p);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) pz_sum += pf_pz(p[c], z[c]);
+            }
+            if (t + 1 == n) break;
+            pf_wave_sync();
+            double mx = -INFINITY, sum = 0.0;
+            over_list([&](double v) { mx = fmax(mx, v); });
+            tmax[tid] = mx;
+            pf_wave_sync();
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const double tm = tmax[(raw >> (8 * c)) & 63u];     // (the state this cell leads to; read only for an admitted live cell)
+                cand[4 * tid + c] = ((m >> c) & 1) && tm > -INFINITY ? exp(av[c] - tm) : 0.0;
+            }
+            pf_wave_sync();
+            over_list([&](double v) { sum += v; });
+            alpha = mx > -INFINITY ? mx + log(sum) : -INFINITY;
+            pf_wave_sync();                                         // the candidates are overwritten by the next step
+        }
+    }
+    pf_finish(a.out, a, a.miss, miss ? 1 : 0, b, n, tid, bad, free_sum, pz_sum, lz_sum, miss, log_z, sc, s_d);
+}
+
+// the bytes of dynamic LDS, from (T, live states) alone: the formula include/rnampnn_hip.h gives
+size_t pf_av_lds_bytes(long long T, long long live) {
+    const size_t t = (size_t)T;
+    return (32 + 8 * (size_t)live) * t + 16 * ((t + 15) / 16) + PF_AV_FIXED;
+}
+long long pf_av_max_T(long long live) {
+    long long T = (long long)(DS_LDS_MAX / (size_t)(32 + 8 * live));
+    while (T > 0 && pf_av_lds_bytes(T, live) > DS_LDS_MAX) --T;
+    return T;
+}
+}  // namespace
+
+extern "C" int rnampnn_design_count_profile(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
+                                            float temperature, const uint8_t* allowed, const int32_t* partner, int32_t wobble, const float* bias,
+                                            int32_t bias_per_position, const uint8_t* counted, const int32_t* count_lo, const int32_t* count_hi,
+                                            int32_t count_cap, double* marginals, double* log_z, double* log_z_free, double* entropy,
+                                            int32_t* infeasible, int32_t* count_miss, void* stream) {
+    PfCtArgs a{};
+    const int rc = ds_prepare("rnampnn_design_count_profile", "RNA", logits, n_rows, mask, cu_seqlens, B, T, temperature, 1, 0, nullptr, allowed,
+                              partner, wobble, bias, bias_per_position, nullptr, nullptr, infeasible, a, [&](int slot) {
+        if (slot == 0 && (!counted || !count_lo || !count_hi))
+            return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_count_profile: null counted, count_lo or count_hi");
+        if (slot == 0 && count_cap < 0)
+            return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_count_profile: count_cap = %d is negative", (int)count_cap);
+        if (slot == 1 && marginals && ((uintptr_t)marginals & 15) != 0)
+            return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_count_profile: marginals must be 16-byte aligned");
+        return RNAMPNN_OK;
+    });
+    if (rc != RNAMPNN_OK) return rc;
+    if (!marginals && !log_z && !log_z_free && !entropy && !infeasible && !count_miss) return RNAMPNN_OK;    // nothing asked for
+    const int cap = std::min<int>(count_cap, T);
+    size_t lds_tree = 0;
+    const size_t lds = pf_ct_lds_bytes(T, cap, lds_tree);
+    if (lds > DS_LDS_MAX)
+        return fail(RNAMPNN_ERR_UNSUPPORTED,
+                    "rnampnn_design_count_profile: T = %d at count_cap = %d needs %zu bytes of LDS for the inside and the outside tree, the limit is "
+                    "%zu (T <= %d at that cap)", (int)T, (int)count_cap, lds, DS_LDS_MAX, pf_ct_max_T(count_cap));
+    a.counted = counted; a.lo = count_lo; a.hi = count_hi; a.count = nullptr; a.miss = count_miss; a.cap = cap;
+    ct_tree_doubles(T, cap, a.base);
+    a.lds_tree = (unsigned)lds_tree; a.lds_sq = 0;
+    a.out = PfOut{marginals, log_z, log_z_free, entropy};
+    static DevAttr attr;
+    ensure_dyn_lds((const void*)k_design_count_profile, lds, attr);
+    hipLaunchKernelGGL(k_design_count_profile, dim3(B), dim3(SC_THREADS), lds, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return RNAMPNN_OK;
+}
+
+extern "C" int rnampnn_design_avoid_profile(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
+                                            float temperature, const uint8_t* allowed, const int32_t* partner, int32_t wobble, const float* bias,
+                                            int32_t bias_per_position, const uint8_t* delta, int32_t n_states, uint64_t terminal,
+                                            double* marginals, double* log_z, double* log_z_free, double* entropy, int32_t* infeasible,
+                                            int32_t* avoid_miss, void* stream) {
+    PfAvArgs a{};
+    const int rc = ds_prepare("rnampnn_design_avoid_profile", "RNA", logits, n_rows, mask, cu_seqlens, B, T, temperature, 1, 0, nullptr, allowed,
+                              partner, wobble, bias, bias_per_position, nullptr, nullptr, infeasible, a, [&](int slot) {
+        if (slot == 0 && !delta) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_avoid_profile: null delta");
+        if (slot == 0 && (n_states < 1 || n_states > PF_MAX_STATES))
+            return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_avoid_profile: n_states = %d, an automaton has 1 .. %d states", (int)n_states,
+                        PF_MAX_STATES);
+        if (slot == 0 && (terminal & 1ull))
+            return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_avoid_profile: state 0, the start, is marked terminal");
+        if (slot == 1 && marginals && ((uintptr_t)marginals & 15) != 0)
+            return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_avoid_profile: marginals must be 16-byte aligned");
+        return RNAMPNN_OK;
+    });
+    if (rc != RNAMPNN_OK) return rc;
+    if (partner)
+        return fail(RNAMPNN_ERR_UNSUPPORTED, "rnampnn_design_avoid_profile: base pairs (a non-null partner) are not built together with forbidden "
+                    "motifs: a pair couples two distant positions, so an exact chain over (position, automaton state) would carry the class of "
+                    "every open pair in its state, 4^depth states");
+    if (!marginals && !log_z && !log_z_free && !entropy && !infeasible && !avoid_miss) return RNAMPNN_OK;    // nothing asked for
+    const unsigned long long in_range = n_states == 64 ? ~0ull : ((1ull << n_states) - 1ull);
+    const int live = n_states - __builtin_popcountll(terminal & in_range);
+    const size_t lds = pf_av_lds_bytes(T, live);
+    if (lds > DS_LDS_MAX)
+        return fail(RNAMPNN_ERR_UNSUPPORTED, "rnampnn_design_avoid_profile: T = %d with %d live states needs %zu bytes of LDS for the table of "
+                    "partition sums, the limit is %zu (T <= %lld at this automaton)", (int)T, live, lds, DS_LDS_MAX, pf_av_max_T(live));
+    a.delta = delta; a.terminal = terminal & in_range; a.A = n_states; a.live = live; a.miss = avoid_miss;
+    a.out = PfOut{marginals, log_z, log_z_free, entropy};
+    static DevAttr attr;
+    ensure_dyn_lds((const void*)k_design_avoid_profile, lds, attr);
+    hipLaunchKernelGGL(k_design_avoid_profile, dim3(B), dim3(SC_THREADS), lds, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return RNAMPNN_OK;
+}

@@ -58,7 +58,17 @@ codes expand) or, with ``--max-run R``, a run of more than R equal letters - dra
 that and on the fixed positions, not filtered.  The designs CSV gains the columns ``motif_hits`` (positions of the draw at which a motif
 ends) and ``avoid_miss`` (1 for a structure whose fixed positions spell a motif: its draws ignore the motifs and ``motif_hits`` reports
 them).  Not built together with the other modes or with a ``structure`` in ``--constraints``; the automaton of the set has at most 64
-states."""
+states.
+
+    python rna-mpnn_amd/predict.py --ckpt Final.pt --data DIR --profile-out PREFIX [--gc-content .. | --max-mutations .. | --avoid ..] [--samples 8]
+
+Design profiles (``rnampnn_design_count_profile`` / ``rnampnn_design_avoid_profile``, both families): what the draws of the chosen mode come
+FROM - the exact distribution under ``--temperature``, ``--constraints``, ``--bias``, ``--omit``, ``--no-wobble`` and the mode's own flags,
+computed, not estimated from samples, with or without ``--samples``.  ``PREFIX.positions.csv`` has one row per nucleotide,
+``pdb_id,position,pA,pU,pC,pG`` (position 1-based; a sequence logo, a bias for another tool); ``PREFIX.rnas.csv`` one row per structure,
+``pdb_id,length,log_mass,entropy,infeasible,miss``: ``log_mass`` <= 0 is the log of the share of the model's mass the constraints keep,
+``entropy`` (nats) how diverse the designs can be, ``miss`` the mode's ``gc_miss`` / ``mut_miss`` / ``avoid_miss``.  Not built together with
+``--states`` or ``--distinct``."""
 from __future__ import annotations
 
 import argparse
@@ -97,6 +107,8 @@ def parse(argv=None):
                                                         "(default: the structure's own sequence)")
     ap.add_argument("--avoid", default=None, help="MOTIF[,MOTIF..]: no draw of --samples contains one of these substrings (AUCG, T = U, IUPAC codes)")
     ap.add_argument("--max-run", type=int, default=None, help="R: no draw of --samples holds a run of more than R equal letters")
+    ap.add_argument("--profile-out", default=None, help="PREFIX: write the exact distribution the draws come from to PREFIX.positions.csv "
+                                                        "(per-position marginals) and PREFIX.rnas.csv (log_mass, entropy)")
     return ap.parse_args(argv)
 
 
@@ -118,7 +130,7 @@ def gc_option(args) -> dict:
     from rnampnn.utils.constraints import parse_gc_content
     if args.states:
         raise ValueError("--gc-content together with --states is not built: the G+C window conditions single-state designs only")
-    if args.samples <= 0:
+    if args.samples <= 0 and not args.profile_out:
         raise ValueError("--gc-content needs --samples N > 0")
     return dict(gc_content=parse_gc_content(args.gc_content))
 
@@ -150,7 +162,7 @@ def mutations_option(args) -> dict:
     lo = 0 if args.min_mutations is None else args.min_mutations
     if lo < 0 or args.max_mutations < lo:
         raise ValueError(f"--max-mutations / --min-mutations: the budget needs 0 <= m <= M, got m = {lo}, M = {args.max_mutations}")
-    if args.samples <= 0:
+    if args.samples <= 0 and not args.profile_out:
         raise ValueError("--max-mutations needs --samples N > 0")
     from rnampnn.utils.constraints import read_reference_fasta
     return dict(mutations=(lo, args.max_mutations, read_reference_fasta(args.mutate_from) if args.mutate_from else None))
@@ -165,10 +177,22 @@ def avoid_option(args) -> dict:
                         ("--max-mutations", args.max_mutations)):
         if value is not None:
             raise ValueError(f"--avoid / --max-run together with {flag} is not built: the automaton conditions plain single-state designs only")
-    if args.samples <= 0:
+    if args.samples <= 0 and not args.profile_out:
         raise ValueError("--avoid / --max-run need --samples N > 0")
     from rnampnn.utils.motifs import MotifAutomaton
     return dict(avoid=MotifAutomaton.from_motifs([m for m in (args.avoid or "").split(",") if m.strip()], max_run=args.max_run))
+
+
+def profile_option(args) -> dict:
+    """The ``profile_prefix`` keyword of ``predict`` from ``--profile-out``; empty without the flag.  ``ValueError`` naming the flags with
+    ``--states`` or ``--distinct``."""
+    if args.profile_out is None:
+        return {}
+    for flag, value in (("--states", args.states), ("--distinct", args.distinct)):
+        if value:
+            raise ValueError(f"--profile-out together with {flag} is not built: the profile is the distribution of plain, G+C, mutation-budget "
+                             "and motif-avoiding single-state draws")
+    return dict(profile_prefix=args.profile_out)
 
 
 def checkpoint_family(path: str) -> str:
@@ -181,6 +205,7 @@ def checkpoint_family(path: str) -> str:
 
 
 def run(args, log=print):
+    profile = profile_option(args)                                 # refused with --states / --distinct here, before the model is loaded
     avoid = avoid_option(args)                                     # a combination that is not built fails here, before the model is loaded
     mutations = mutations_option(args)
     distinct = distinct_option(args)
@@ -193,7 +218,7 @@ def run(args, log=print):
         from rdesign.utils.predict import predict
         from rdesign.utils.train import load_checkpoint
     extra = dict(samples=args.samples, temperature=args.temperature, seed=args.seed, designs_csv=args.designs_out, **design_options(args), **gc, **distinct,
-                 **mutations, **avoid)
+                 **mutations, **avoid, **profile)
     if args.states:
         if family != "rnampnn":
             raise ValueError("--states designs with rnampnn checkpoints only; for an rdesign checkpoint call RNAModel.design(states=...) "

@@ -34,7 +34,8 @@ import torch.nn.functional as F
 from .. import _native
 from rnampnn.model._base import _prep, _stream
 from rnampnn.model.decode import (check_avoid, check_distinct, check_mutations, check_state_lengths, design_by_mode, design_distinct_from_logits,  # noqa: F401
-                                  design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits, letters_packed,
+                                  design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits, design_profile_from_logits,
+                                  letters_packed,
                                   score_logits)
 
 _PREC = {"f32": _native.PREC_F32, "bf16": _native.PREC_BF16}
@@ -459,6 +460,25 @@ class RNAModel(nn.Module):
         return design_by_mode(mode, logits, cu_seqlens=cu, max_len=T, n_samples=n_samples, temperature=temperature, seed=seed,
                               constraints=constraints, states=states, state_weights=state_weights, gc_content=gc_content, distinct=distinct,
                               mutations=mutations, avoid=avoid)
+
+    @torch.no_grad()
+    def design_profile(self, X, mask, temperature: float = 0.1, constraints=None, lengths=None, gc_content=None, mutations=None, avoid=None):
+        """What ``design`` draws FROM under the same arguments, with one eval-mode forward and one launch on the packed logits: the exact
+        per-position marginals, log partition sums and entropy of the constrained, tempered distribution (``design_profile_from_logits``)
+        -> a ``DesignProfile``.  ``constraints``, ``lengths``, ``gc_content``, ``mutations`` and ``avoid`` as in ``design``; the pairings
+        ``design`` refuses are refused here with the same messages, before the forward pass.  No profile is built for ``states`` or
+        ``distinct``."""
+        design_mode(gc_content=gc_content, mutations=mutations, avoid=avoid)
+        check_mutations(mutations)
+        check_avoid(avoid, constraints)
+        was_training = self.training
+        self.eval()
+        try:
+            logits, cu, T = self._packed_logits(X, mask, lengths)
+        finally:
+            self.train(was_training)
+        return design_profile_from_logits(logits, cu_seqlens=cu, max_len=T, temperature=temperature, constraints=constraints,
+                                          gc_content=gc_content, mutations=mutations, avoid=avoid)
 
     @torch.no_grad()
     def score_sequences(self, X, mask, seqs, labels=None, lengths=None):

@@ -7,14 +7,15 @@ from typing import List, Optional, Tuple
 from rnampnn.model.decode import check_avoid, check_budget, design_by_mode, design_mode, letters_padded, score_logits
 from rnampnn.utils.constraints import batch_constraints, mutation_references, padded_references
 from rnampnn.utils.data import bucket_batches
-from rnampnn.utils.predict import design_columns, write_csv
+from rnampnn.utils.predict import check_profile, design_columns, profile_batch, write_csv, write_profile
 
 from .data import load_rna_dir, padded_loader
 
 
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
-            wobble: bool = True, gc_content=None, distinct=None, mutations=None, avoid=None) -> List[Tuple[str, str]]:
+            wobble: bool = True, gc_content=None, distinct=None, mutations=None, avoid=None,
+            profile_prefix: Optional[str] = None) -> List[Tuple[str, str]]:
     """Read ``data_path`` (``coords/<id>.npy`` + ``seqs/<id>.fasta``), design a sequence for every structure in length-bucketed batches
     (``RNAModel.predict_sequences``: the tree read-out when one is attached, else the read-out's argmax) and write ``out_csv`` with one
     ``pdb_id,seq`` row per input in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure at
@@ -29,11 +30,15 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     (``references[pdb_id]``, or with None its own fasta sequence) at between min and max positions; ``designs_csv`` gains the last columns
     ``mutations`` and ``mut_miss``.  Not built together with ``gc_content`` or ``distinct``.  ``avoid`` (a ``MotifAutomaton`` or motif
     strings): the draws come from ``rnampnn_design_avoid`` and contain none of the motifs; ``designs_csv`` gains the last columns
-    ``motif_hits`` and ``avoid_miss``.  Not built together with the other modes or with a structure in ``constraints``."""
+    ``motif_hits`` and ``avoid_miss``.  Not built together with the other modes or with a structure in ``constraints``.
+    ``profile_prefix``: also write the design profile of every structure (``design_profile_from_logits``: the exact distribution the
+    draws of the chosen mode come from) to ``PREFIX.positions.csv`` and ``PREFIX.rnas.csv``, with or without ``samples``.  Not built
+    together with ``distinct``."""
     mode = design_mode(None, gc_content, distinct, mutations, avoid)
+    check_profile(profile_prefix, None, distinct)
     avoid = check_avoid(avoid)
     if avoid is not None:
-        if samples <= 0:
+        if samples <= 0 and not profile_prefix:
             raise ValueError("forbidden motifs need samples > 0")
         paired = sorted(rid for rid, (_, structure) in (constraints or {}).items() if structure)
         if paired:
@@ -41,7 +46,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
                              f"state): drop `structure` from the constraints of {paired[:3]}{' ...' if len(paired) > 3 else ''}")
     if mutations is not None:
         check_budget(mutations[0], mutations[1])
-        if samples <= 0:
+        if samples <= 0 and not profile_prefix:
             raise ValueError("a mutation budget needs samples > 0")
     model.eval()
     items = load_rna_dir(data_path)
@@ -53,14 +58,18 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
                                                               [it[2] for it in items])
     batches = bucket_batches([c.shape[0] for _, c, _ in items], batch_size, max_rows, seed=0)
     device = model._device()
-    seqs, designs = {}, {}
+    seqs, designs, profiles = {}, {}, {}
     for bi, (S, X, mask, lengths, idx) in enumerate(padded_loader(items, batches, device=device)):
         for i, s in zip(idx, model.predict_sequences(X, mask, lengths)):
             seqs[i] = s
-        if samples > 0:
+        if samples > 0 or profile_prefix:
             lens = [int(v) for v in lengths]
             logits, cu, T = model._packed_logits(X, mask, lengths)
             cons = batch_constraints(constraints, [items[i][0] for i in idx], lens, T, bias=bias, wobble=wobble, omit=omit)
+        if profile_prefix:
+            profile_batch(profiles, idx, lens, logits, cu, T, temperature, cons.to_device(device), gc_content,
+                          None if mutations is None else (padded_references(refs, idx, T), mutations[0], mutations[1]), avoid)
+        if samples > 0:
             draws, nll, bad, *extras = design_by_mode(
                 mode, logits, cu_seqlens=cu, max_len=T, n_samples=samples, temperature=temperature, seed=seed + bi,
                 constraints=cons.to_device(device), gc_content=gc_content, distinct=distinct, avoid=avoid,
@@ -75,6 +84,8 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
                     designs.setdefault(i, []).append((s, text, f"{nll[s][r] / lens[r]:.6f}", f"{match[s][r] / lens[r]:.6f}", bad[r]) + cells(s, r))
     rows = [(items[i][0], seqs[i]) for i in range(len(items))]
     write_csv(out_csv, "pdb_id,seq", rows)
+    if profile_prefix:
+        write_profile(profile_prefix, [it[0] for it in items], profiles)
     if samples > 0:
         write_csv(designs_csv, "pdb_id,sample,seq,nll_per_nt,recovery,infeasible" + design_columns(mode)[0],
                   [(it[0],) + row for i, it in enumerate(items) for row in designs[i]])

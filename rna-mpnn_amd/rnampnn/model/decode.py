@@ -1,13 +1,13 @@
 """Decoding from logits, as free functions over the C ABI's decode family: argmax + recovery (``rnampnn_argmax_recovery``), free draws
 (``rnampnn_sample``), scores (``rnampnn_score``), constrained and multi-state design (``rnampnn_design``, ``rnampnn_design_tied``), design
 under a G+C content window (``rnampnn_design_gc``), design within a count window / a mutation budget (``rnampnn_design_count``), distinct
-designs (``rnampnn_design_distinct``), design that avoids forbidden motifs (``rnampnn_design_avoid``), the choice between them (``design_mode``, ``design_by_mode``) and the letters of class ids.  Needs the library and ``_base`` only, so both model packages import
+designs (``rnampnn_design_distinct``), design that avoids forbidden motifs (``rnampnn_design_avoid``), the distribution those draws come from (``rnampnn_design_count_profile``, ``rnampnn_design_avoid_profile``), the choice between them (``design_mode``, ``design_by_mode``) and the letters of class ids.  Needs the library and ``_base`` only, so both model packages import
 it at module level."""
 from __future__ import annotations
 
 import ctypes as C
 import itertools
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -81,14 +81,10 @@ def check_state_lengths(states, lengths) -> None:
         lo += k
 
 
-def _design_call(name, logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints, padded=(), head=None, tail=None,
-                 outputs=(), entry=None):
-    """One call of a design entry of the C ABI -> (seqs, seq_nll, infeasible, *the entry's further outputs).  What the entries share
-    is done here, once: the device check (it speaks of ``name``), the constraints' tensors, the layout, the shape checks, the outputs and
-    the common positional arguments.  What is an entry's own comes in: ``padded`` - further (label, tensor, dtype) inputs padded to
-    (B,T), prepared and shape-checked ahead of the constraints'; ``head`` / ``tail`` - callables (B, T, mask, cu, *the padded inputs) ->
-    the entry's own arguments, tensors or scalars, placed where the ABI has them: after the rows / after the bias; ``outputs`` -
-    (dtype, per sample ?) of the outputs past ``infeasible``: (S,B) or (B,); ``entry`` - the symbol when it is not ``name``."""
+def _design_inputs(name, logits, mask, cu_seqlens, max_len, constraints, padded=()):
+    """What every entry of the design family does to its inputs, once: the device check (it speaks of ``name``), the constraints'
+    tensors, the layout and the shape checks -> (lg, m, cu, B, T, own, al, pa, bi, per_position, wobble); ``own``: the prepared
+    ``padded`` inputs - further (label, tensor, dtype) inputs padded to (B,T), shape-checked ahead of the constraints'."""
     device = logits.device
     if device.type != "cuda":
         raise RuntimeError(f"{name} runs on an MI355X: pass CUDA logits (there is no CPU fallback)")
@@ -105,14 +101,26 @@ def _design_call(name, logits, mask, cu_seqlens, max_len, n_samples, temperature
     if bi is not None and not per_position and tuple(bi.shape) != (4,):
         raise ValueError(f"constraints.bias must be (4,) or (B, T, 4) = {(B, T, 4)}, got {tuple(bi.shape)}")
     _check_logits(lg, m, B, T)
-    its = [() if f is None else tuple(f(B, T, m, cu, *(t for _, t in own))) for f in (head, tail)]
+    return lg, m, cu, B, T, [t for _, t in own], al, pa, bi, per_position, int(bool(c.wobble)) if c is not None else 1
+
+
+def _design_call(name, logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints, padded=(), head=None, tail=None,
+                 outputs=(), entry=None):
+    """One call of a design entry of the C ABI -> (seqs, seq_nll, infeasible, *the entry's further outputs).  What the entries share
+    is done here, once: the inputs (``_design_inputs``), the outputs and the common positional arguments.  What is an entry's own comes
+    in: ``padded`` - further inputs padded to (B,T), as ``_design_inputs`` takes them; ``head`` / ``tail`` - callables (B, T, mask, cu, *the padded inputs) ->
+    the entry's own arguments, tensors or scalars, placed where the ABI has them: after the rows / after the bias; ``outputs`` -
+    (dtype, per sample ?) of the outputs past ``infeasible``: (S,B) or (B,); ``entry`` - the symbol when it is not ``name``."""
+    device = logits.device
+    lg, m, cu, B, T, own, al, pa, bi, per_position, wobble = _design_inputs(name, logits, mask, cu_seqlens, max_len, constraints, padded)
+    its = [() if f is None else tuple(f(B, T, m, cu, *own)) for f in (head, tail)]
     S = int(n_samples)
     seqs = torch.empty(max(S, 0), max(B, 0), max(T, 0), dtype=torch.int8, device=device)
     nll = torch.empty(max(S, 0), max(B, 0), dtype=torch.float32, device=device)
     bad = torch.empty(max(B, 0), dtype=torch.int32, device=device)
     more = [torch.empty(*((max(S, 0),) if per_sample else ()), max(B, 0), dtype=dtype, device=device) for dtype, per_sample in outputs]
-    args = [lg, int(lg.numel()) // 4, m, cu, B, T, *its[0], float(temperature), S, _seed64(seed), None, al, pa,
-            int(bool(c.wobble)) if c is not None else 1, bi, per_position, *its[1], seqs, nll, bad, *more]
+    args = [lg, int(lg.numel()) // 4, m, cu, B, T, *its[0], float(temperature), S, _seed64(seed), None, al, pa, wobble, bi, per_position,
+            *its[1], seqs, nll, bad, *more]
     with torch.cuda.device(device):
         _native.check(getattr(_native.lib(), entry or name)(*[_ptr(v) if torch.is_tensor(v) else v for v in args], _stream(device)))
     return (seqs, nll, bad, *more)
@@ -373,6 +381,81 @@ def design_by_mode(mode: str, logits: torch.Tensor, states=None, state_weights=N
     if mode == "gc_content":
         return design_gc_from_logits(logits, gc_content=gc_content, **kw)
     return design_from_logits(logits, states=states, state_weights=state_weights, **kw)
+
+
+class DesignProfile(NamedTuple):
+    """What ``design_profile_from_logits`` returns: marginals (B,T,4) f64 - P(x_t = c) under the distribution the draws of ``mode`` come
+    from, 0 on padding; log_z, log_z_free, entropy (B,) f64; infeasible (B,) int32 and miss (B,) int32 - the draw entry's own ``infeasible``
+    and ``gc_miss`` / ``mut_miss`` / ``avoid_miss``; mode - the ``design_mode``."""
+    marginals: torch.Tensor
+    log_z: torch.Tensor
+    log_z_free: torch.Tensor
+    entropy: torch.Tensor
+    infeasible: torch.Tensor
+    miss: torch.Tensor
+    mode: str
+
+    @property
+    def log_mass(self) -> torch.Tensor:
+        """(B,) f64, <= 0: the log of the share of the model's mass that the constraints keep."""
+        return self.log_z - self.log_z_free
+
+
+PROFILE_ENTRIES = {"plain": "rnampnn_design_count_profile", "gc_content": "rnampnn_design_count_profile",
+                   "mutations": "rnampnn_design_count_profile", "avoid": "rnampnn_design_avoid_profile"}
+
+
+def profile_mode_args(mode: str, B: int, T: int, device, lengths=None, gc_content=None, reference=None, budget=None, auto=None) -> tuple:
+    """The own arguments of the profile entry of ``mode`` (``PROFILE_ENTRIES``), between the bias and the outputs, on ``device``
+    (``lengths`` (B,), read by "gc_content" alone, lives there): "plain" - nothing counts, window (0, 0), cap 0: the tree degenerates and the distribution is ``rnampnn_design``'s;
+    "gc_content" - C|G count everywhere, the window of ``gc_counts``, cap T; "mutations" - ``mutation_sets(reference)``, the budget
+    (lo, hi) as window and hi as cap; "avoid" - the automaton's tables.  No host synchronisation."""
+    if mode == "avoid":
+        return auto.delta_on(device), auto.n_states, C.c_uint64(auto.terminal)
+    if mode == "gc_content":
+        lo, hi = gc_counts(gc_fractions(gc_content, B).to(device, non_blocking=True), lengths)
+        return torch.full((B, T), 12, dtype=torch.uint8, device=device), lo, hi, T
+    if mode == "mutations":
+        w, cap = count_window(budget, budget[1], B)
+        w = w.to(device, non_blocking=True)
+        return mutation_sets(reference), w[:, 0].contiguous(), w[:, 1].contiguous(), cap
+    if mode != "plain":
+        raise ValueError(f"no profile is built for the mode {mode!r}")
+    zero = torch.zeros(B, dtype=torch.int32, device=device)
+    return torch.zeros(B, T, dtype=torch.uint8, device=device), zero, zero, 0
+
+
+def design_profile_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
+                               max_len: Optional[int] = None, temperature: float = 0.1, constraints=None, gc_content=None, mutations=None,
+                               avoid=None) -> DesignProfile:
+    """``rnampnn_design_count_profile`` / ``rnampnn_design_avoid_profile`` (include/rnampnn_hip.h): the exact distribution that the draws
+    of ``design_by_mode`` come from under the same arguments - per-position marginals, log partition sums and entropy, fp64, in one launch ->
+    ``DesignProfile``.  The mode is ``design_mode(gc_content=, mutations=, avoid=)``, so the pairings that are not built keep their messages:
+    "plain" (constraints alone: the count entry with nothing counted, the distribution of ``design_from_logits``), "gc_content" (a pair of
+    fractions or (B,2), as in ``design_gc_from_logits``), "mutations" (``(reference, max)`` or ``(reference, min, max)``, as ``design``
+    takes it) and "avoid" (a ``MotifAutomaton`` or motif strings; base pairs are the ``ValueError`` of ``check_avoid``).  The trees live in
+    LDS: T <= 535 for a G+C window, 1457 for a budget of 8, 1168 for ``max_run=3``; beyond it the library raises ``NotImplementedError``
+    naming the limit.  Layouts and ``constraints`` as in ``design_from_logits``.  CUDA logits only (there is no CPU fallback); no host
+    synchronisation."""
+    mode = design_mode(gc_content=gc_content, mutations=mutations, avoid=avoid)
+    mutations = check_mutations(mutations)
+    auto = check_avoid(avoid, constraints)
+    name = PROFILE_ENTRIES[mode]
+    padded = (("the reference of mutations", mutations[0], torch.int32),) if mode == "mutations" else ()
+    lg, m, cu, B, T, own, al, pa, bi, per_position, wobble = _design_inputs(name, logits, mask, cu_seqlens, max_len, constraints, padded)
+    device, Bn, Tn = lg.device, max(B, 0), max(T, 0)
+    lengths = None
+    if mode == "gc_content":
+        lengths = (m.sum(dim=1) + 0.5).floor() if m is not None else (cu[1:] - cu[:-1]).clamp(0, Tn)
+    its = profile_mode_args(mode, Bn, Tn, device, lengths, gc_content=gc_content, reference=own[0] if own else None,
+                            budget=None if mutations is None else mutations[1], auto=auto)
+    marg = torch.empty(Bn, Tn, 4, dtype=torch.float64, device=device)
+    log_z, free, ent = (torch.empty(Bn, dtype=torch.float64, device=device) for _ in range(3))
+    bad, miss = (torch.empty(Bn, dtype=torch.int32, device=device) for _ in range(2))
+    args = [lg, int(lg.numel()) // 4, m, cu, B, T, float(temperature), al, pa, wobble, bi, per_position, *its, marg, log_z, free, ent, bad, miss]
+    with torch.cuda.device(device):
+        _native.check(getattr(_native.lib(), name)(*[_ptr(v) if torch.is_tensor(v) else v for v in args], _stream(device)))
+    return DesignProfile(marg, log_z, free, ent, bad, miss, mode)
 
 
 SCORE_OUTPUTS = {"valid": torch.int32, "pred": torch.int8, "correct": torch.int32, "label_nll": torch.float32, "label_loss": torch.float32,

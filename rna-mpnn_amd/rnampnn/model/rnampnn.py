@@ -25,6 +25,7 @@ from ..utils.data import check_prefix_mask
 from ._base import NativeModule, _prep, _ptr, _stream
 from .decode import (SCORE_OUTPUTS, argmax_recovery, check_avoid, check_distinct, check_mutations, check_state_lengths, design_by_mode,  # noqa: F401
                      design_distinct_from_logits, design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits,
+                     design_profile_from_logits,
                      letters_packed, letters_padded, sample_from_logits, score_logits)
 from ._schema import DEFAULT_HPARAMS
 
@@ -583,6 +584,27 @@ class RNAMPNN(NativeModule):
                                   avoid=avoid)
         seqs = sample_from_logits(logits, mask, temperature, n_samples, seed)
         return seqs, score_logits(logits, mask=mask, seqs=seqs, want=("seq_nll",))["seq_nll"]
+
+    @torch.no_grad()
+    def design_profile(self, coords: torch.Tensor, mask: torch.Tensor, temperature: float = 0.1, T_norm: int = 0, constraints=None,
+                       lengths=None, gc_content=None, mutations=None, avoid=None):
+        """What ``design`` draws FROM under the same arguments, with one eval-mode forward and one launch: the exact per-position
+        marginals, log partition sums and entropy of the constrained, tempered distribution (``design_profile_from_logits``) -> a
+        ``DesignProfile`` (marginals (B,T,4) f64, log_z, log_z_free, entropy (B,) f64, infeasible, miss (B,) int32, mode; ``log_mass`` =
+        the log of the share of the model's mass the constraints keep).  ``constraints``, ``gc_content``, ``mutations`` and ``avoid`` as
+        in ``design``; the pairings that ``design`` refuses are refused here with the same messages, before the forward pass.  ``lengths``
+        is accepted for symmetry with ``design`` and not read.  No profile is built for ``states`` or ``distinct``."""
+        design_mode(gc_content=gc_content, mutations=mutations, avoid=avoid)
+        check_mutations(mutations)
+        check_avoid(avoid, constraints)
+        was_training = self.training
+        self.eval()
+        try:
+            logits = self._run(coords, mask, T_norm=T_norm)["logits"]
+        finally:
+            self.train(was_training)
+        return design_profile_from_logits(logits, mask=mask, temperature=temperature, constraints=constraints, gc_content=gc_content,
+                                          mutations=mutations, avoid=avoid)
 
     @torch.no_grad()
     def test_step(self, batch):

@@ -11,7 +11,8 @@ import numpy as np
 import torch
 
 from ..config.glob import VOCAB
-from ..model.decode import check_avoid, check_budget, design_by_mode, design_mode, letters_packed, letters_padded, sample_from_logits, score_logits
+from ..model.decode import (check_avoid, check_budget, design_by_mode, design_mode, design_profile_from_logits, letters_packed, letters_padded,
+                            sample_from_logits, score_logits)
 from .constraints import batch_constraints, mutation_references, padded_references
 from .data import PackedLoader, bucket_batches, fill_nan_deterministic, read_fasta
 
@@ -129,11 +130,39 @@ def design_columns(mode: str, extras=(), lens=()):
     return "", lambda s, r: (), None
 
 
+def check_profile(profile_prefix, states=None, distinct=None) -> None:
+    """``predict(..., profile_prefix=...)``: ``ValueError`` with ``states`` or ``distinct`` - no profile is built for multi-state or distinct
+    designs; touches no device."""
+    if profile_prefix and (states is not None or distinct is not None):
+        raise ValueError("a design profile together with states or distinct is not built: the profile is the distribution of plain, G+C, "
+                         "mutation-budget and motif-avoiding single-state draws")
+
+
+def profile_batch(store: dict, idx, lens, logits, cu, max_len: int, temperature: float, cons, gc_content, mutations, avoid) -> None:
+    """The design profile of one packed batch (``design_profile_from_logits``; ``mutations`` as ``design`` takes it) into ``store``:
+    item index -> (marginals [n][4], log_mass, entropy, infeasible, miss).  One launch, one copy per output."""
+    prof = design_profile_from_logits(logits, cu_seqlens=cu, max_len=max_len, temperature=temperature, constraints=cons, gc_content=gc_content,
+                                      mutations=mutations, avoid=avoid)
+    marg, mass, ent = prof.marginals.cpu().tolist(), prof.log_mass.cpu().tolist(), prof.entropy.cpu().tolist()
+    bad, miss = prof.infeasible.cpu().tolist(), prof.miss.cpu().tolist()
+    for r, i in enumerate(idx):
+        store[i] = (marg[r][:lens[r]], mass[r], ent[r], bad[r], miss[r])
+
+
+def write_profile(prefix: str, ids, store: dict) -> None:
+    """``PREFIX.positions.csv`` (``pdb_id,position,pA,pU,pC,pG``, one row per nucleotide, 1-based) and ``PREFIX.rnas.csv``
+    (``pdb_id,length,log_mass,entropy,infeasible,miss``) in id order; floats as ``repr`` writes them, so they read back exactly."""
+    write_csv(prefix + ".positions.csv", "pdb_id,position,pA,pU,pC,pG",
+              [(rid, t + 1) + tuple(repr(float(v)) for v in row) for i, rid in enumerate(ids) for t, row in enumerate(store[i][0])])
+    write_csv(prefix + ".rnas.csv", "pdb_id,length,log_mass,entropy,infeasible,miss",
+              [(rid, len(store[i][0]), repr(float(store[i][1])), repr(float(store[i][2])), store[i][3], store[i][4]) for i, rid in enumerate(ids)])
+
+
 @torch.no_grad()
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
             wobble: bool = True, states: Optional[dict] = None, gc_content=None, distinct=None, mutations=None,
-            avoid=None) -> List[Tuple[str, str]]:
+            avoid=None, profile_prefix: Optional[str] = None) -> List[Tuple[str, str]]:
     """Design a sequence for every structure under ``data_path`` in length-bucketed var-len batches (``forward_packed``): the tree
     read-out on the packed embedding when one is attached, else the read-out's argmax (``rnampnn_score``'s ``pred``); write ``out_csv``
     with one ``pdb_id,seq`` row per structure in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure
@@ -162,11 +191,15 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     them, drawn exactly from the model's distribution conditioned on that and on the fixed positions, ``omit`` and ``bias``.
     ``designs_csv`` gains the last columns ``motif_hits`` (positions of the draw at which a motif ends: 0 unless ``avoid_miss``) and
     ``avoid_miss`` (1 for a structure whose fixed positions spell a motif).  Not built together with the other modes; a constraints
-    table with a structure column that is not empty is a ``ValueError`` before the first forward pass."""
+    table with a structure column that is not empty is a ``ValueError`` before the first forward pass.
+    ``profile_prefix``: also write the design profile of every structure - the exact distribution the draws of the chosen mode come from
+    under ``temperature`` and the constraints (``design_profile_from_logits``) - to ``PREFIX.positions.csv`` and ``PREFIX.rnas.csv``
+    (``write_profile``), with or without ``samples``.  Not built together with ``states`` or ``distinct``."""
     mode = design_mode(states, gc_content, distinct, mutations, avoid)
+    check_profile(profile_prefix, states, distinct)
     avoid = check_avoid(avoid)
     if avoid is not None:
-        if samples <= 0:
+        if samples <= 0 and not profile_prefix:
             raise ValueError("forbidden motifs need samples > 0")
         paired = sorted(rid for rid, (_, structure) in (constraints or {}).items() if structure)
         if paired:
@@ -174,7 +207,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
                              f"state): drop `structure` from the constraints of {paired[:3]}{' ...' if len(paired) > 3 else ''}")
     if mutations is not None:
         check_budget(mutations[0], mutations[1])
-        if samples <= 0:
+        if samples <= 0 and not profile_prefix:
             raise ValueError("a mutation budget needs samples > 0")
     model.eval()
     device = model._device()
@@ -187,7 +220,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     refs = None if mutations is None else mutation_references(mutations[2], ids, lengths, [it[2] for it in items])
     trees = getattr(model, "xgb_readout", None)
     constrained = constraints is not None or bias is not None or bool(omit) or not wobble
-    seqs, designs = {}, {}
+    seqs, designs, profiles = {}, {}, {}
     groups = batch_groups = None
     if states is not None:
         if samples <= 0:
@@ -206,12 +239,17 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             logits = model.forward_packed(coords, cu, max_len)
             names = letters_padded(score_logits(logits, cu_seqlens=cu, want=("pred",), max_len=max_len)["pred"])
         seqs.update(zip(idx, names))
-        if samples <= 0:
+        if samples <= 0 and not profile_prefix:
             continue
         gs = None if groups is None else batch_groups[bi]
         cons = None
         if constrained:
             cons = batch_constraints(constraints, [ids[i] for i in idx], lens, max_len, bias=bias, wobble=wobble, omit=omit).to_device(device)
+        if profile_prefix:
+            profile_batch(profiles, idx, lens, logits, cu, max_len, temperature, cons, gc_content,
+                          None if mutations is None else (padded_references(refs, idx, max_len), mutations[0], mutations[1]), avoid)
+        if samples <= 0:
+            continue
         draws, dnll, bad, *extras = draw_batch(
             logits, cu, max_len, samples, temperature, seed + bi, cons, mode, gc_content=gc_content, distinct=distinct, avoid=avoid,
             mutations=None if mutations is None else (padded_references(refs, idx, max_len), (mutations[0], mutations[1])),
@@ -244,6 +282,8 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
                 r += len(rows)
     rows = [(rid, seqs[i]) for i, rid in enumerate(ids)]
     write_csv(out_csv, "pdb_id,seq", rows)
+    if profile_prefix:
+        write_profile(profile_prefix, ids, profiles)
     if groups is not None:
         write_csv(designs_csv, "design_id,sample,seq,infeasible,states,nll_per_nt,recovery",
                   [(group[0],) + row for g, group in enumerate(groups) for row in designs[g]])

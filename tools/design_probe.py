@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The measurement behind DESIGN.md section 9 "Constrained design", "Multi-state design", "Design under a G+C window", "Distinct designs",
-"Mutation budget" and "Forbidden motifs" (profiles/design_kernel_stats.txt, profiles/design_tied_kernel_stats.txt, profiles/design_gc_kernel_stats.txt,
+"Mutation budget", "Forbidden motifs" and "Design profiles" (profiles/design_profile_kernel_stats.txt, profiles/design_kernel_stats.txt, profiles/design_tied_kernel_stats.txt, profiles/design_gc_kernel_stats.txt,
 profiles/design_distinct_kernel_stats.txt, profiles/design_count_kernel_stats.txt, profiles/design_avoid_kernel_stats.txt): the C2 batch (256 RNAs x 100..140 nt), S = 8 sequences per RNA.
 usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + rnampnn_score (seq_nll): the unconstrained pair of launches
        python tools/design_probe.py design [calls=50]         rnampnn_design: free, then with a hairpin's pairs + a fixed GNRA loop per RNA
@@ -19,6 +19,12 @@ usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + r
                                                               rnampnn_design_count (b) (S = 8, cap 8: the yardstick) and rnampnn_design_avoid:
                                                               S = 8 with max_run = 3 (13 live states), S = 8 with a 64-state set, S = 64 with
                                                               max_run = 3; all without constraints
+       python tools/design_probe.py profile                   rnampnn_design (free, hairpin) and then, in 5 alternating rounds of 10 calls each,
+                                                              the two draw entries as yardsticks of the same run - rnampnn_design_count (b)
+                                                              and rnampnn_design_avoid max_run = 3, S = 8 - and the profile entries:
+                                                              rnampnn_design_count_profile with the G+C window 40..60 % (cap T), with 0..8
+                                                              mutations (cap 8) and plain under the hairpins (cap 0);
+                                                              rnampnn_design_avoid_profile with max_run = 3 and with the 64-state set
 HIP events around each loop of back-to-back calls of the Python wrappers.  Run either under `rocprofv3 --kernel-trace --stats -- python ...`
 (a run of its own) for the kernels' own times.  RNAMPNN_PROBE_ROOT: another checkout (with its library built) to take the package from -
 the `sample_score` leg uses nothing newer than rnampnn_score, so it runs on the parent commit as well."""
@@ -180,6 +186,50 @@ else:
         for tag, auto, out in (("max_run 3", run3, variants[1][1]()), ("64-state set", wide, variants[2][1]())):
             print(f"{tag}: hits of the draws {int(out[3].sum())} (recounted {int(auto.hits(out[0]).sum())}), avoid_miss total {int(out[4].sum())}, "
                   f"mean NLL per nt {float(out[1].sum()) / (8 * int(mask.sum())):.4f}; rnampnn_design's free draws hold {int(auto.hits(free).sum())} hits")
+    if what == "profile":
+        # Seven variants in alternating rounds of one process: the two draw kernels the profiles share their tables with, then the profiles.
+        from rnampnn.model import decode as D
+        from rnampnn.utils.motifs import MotifAutomaton
+        rounds, per_round, warm = 5, 10, 3
+        ref = torch.randint(0, 4, (B, T), generator=torch.Generator().manual_seed(1)).cuda()
+        sets = D.mutation_sets(ref)
+        run3 = MotifAutomaton.from_motifs([], max_run=3)
+        wide = MotifAutomaton.from_motifs(["GGGG", "GAAUUCAAGC", "CUGCAGUCGA", "AAGCUUGCAU", "UCUAGAGGCC", "CCCGGGAUAU", "AUCGAUCGGUAC"])
+        pk = dict(mask=m, temperature=0.1)
+        variants = [
+            ("rnampnn_design_count (b) random reference, 0..8 mutations, cap 8, S 8",
+             lambda: D.design_count_from_logits(logits, mask=m, counted=sets, window=(0, 8), n_samples=8, temperature=0.1, seed=1)),
+            (f"rnampnn_design_avoid max_run 3 ({run3.n_live} live states), S 8",
+             lambda: D.design_avoid_from_logits(logits, mask=m, avoid=run3, n_samples=8, temperature=0.1, seed=1)),
+            ("rnampnn_design_count_profile G+C 40..60 %, cap T, no constraints", lambda: D.design_profile_from_logits(logits, gc_content=(0.4, 0.6), **pk)),
+            ("rnampnn_design_count_profile 0..8 mutations, cap 8, no constraints", lambda: D.design_profile_from_logits(logits, mutations=(ref, 8), **pk)),
+            ("rnampnn_design_count_profile plain, cap 0, hairpin pairs + GNRA + bias", lambda: D.design_profile_from_logits(logits, constraints=cons, **pk)),
+            (f"rnampnn_design_avoid_profile max_run 3 ({run3.n_live} live states)", lambda: D.design_profile_from_logits(logits, avoid=run3, **pk)),
+            (f"rnampnn_design_avoid_profile {wide.n_states}-state set ({wide.n_live} live states)",
+             lambda: D.design_profile_from_logits(logits, avoid=wide, **pk))]
+        for _, fn in variants:
+            for _ in range(warm):
+                fn()
+        torch.cuda.synchronize()
+        times = [[] for _ in variants]
+        for _ in range(rounds):
+            for v, (_, fn) in enumerate(variants):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(per_round):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                times[v].append(e0.elapsed_time(e1) * 1e3 / per_round)
+        for (name, _), t in zip(variants, times):
+            print(f"B {B} T {T} nt {int(mask.sum())} {name}: {sum(t) / len(t):.2f} us per call, rounds {min(t):.2f} .. {max(t):.2f} "
+                  f"({rounds} alternating rounds of {per_round} back-to-back calls, events, output allocation included)")
+        for (name, fn) in variants[2:]:
+            p = fn()
+            rows = p.marginals.sum(-1)
+            print(f"{name.split(',')[0]}: log_mass {float(p.log_mass.min()):.3f} .. {float(p.log_mass.max()):.3f} nats, entropy "
+                  f"{float(p.entropy.min()):.3f} .. {float(p.entropy.max()):.3f} nats, miss total {int(p.miss.sum())}, "
+                  f"max |row sum - 1| on valid positions {float(((rows - 1).abs() * m).max()):.2e}")
     if what == "distinct":
         for S in (8, 64):                                           # (timed() prints the global S)
             for mode in ("sample", "best"):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/design_probe.py under rocprofv3 --kernel-trace --stats, each leg in a run of its own.  usage: tools/kstats_design.sh <outdir> [leg ...]
-# (outdir: a git-ignored place such as build/design_stats; legs: sample_score design tied gc distinct count avoid, the first four by default)
+# (outdir: a git-ignored place such as build/design_stats; legs: sample_score design tied gc distinct count avoid profile, the first four by default)
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "${1:?usage: tools/kstats_design.sh <outdir> [leg ...]}" && OUT=$(cd "$1" && pwd) || exit 1
 shift
@@ -30,10 +30,15 @@ e = launches(lambda n: 'k_design_tied' in n)
 f = launches(lambda n: 'k_design_gc' in n)
 # the "count" leg: after 3 warm launches per variant, 5 alternating rounds of 10 launches per variant - k_design_gc free / hairpins (2 variants
 # of its launches) and k_design_count (a) free / (a) hairpins / (b) / (c) (4 variants of its launches); per variant the mean of every round
-c = launches(lambda n: 'k_design_count' in n)
+c = launches(lambda n: 'k_design_count' in n and '_profile' not in n)
 # the "avoid" leg: the same rounds - k_design_count (b) (1 variant of its launches: the yardstick of the same run) and k_design_avoid
 # S = 8 max_run 3 / S = 8 64-state set / S = 64 max_run 3 (3 variants of its launches)
-av = launches(lambda n: 'k_design_avoid' in n)
+av = launches(lambda n: 'k_design_avoid' in n and '_profile' not in n)
+# the "profile" leg: the same rounds - k_design_count (b) and k_design_avoid max_run 3 (1 variant each: the yardsticks of the same run),
+# k_design_count_profile G+C cap T / 0..8 mutations cap 8 / plain under the hairpins (3 variants), k_design_avoid_profile max_run 3 /
+# 64-state set (2 variants)
+cp = launches(lambda n: 'k_design_count_profile' in n)
+ap = launches(lambda n: 'k_design_avoid_profile' in n)
 def by_round(seq, variants, v):
     body = seq[3 * variants:]
     return [[x[1] / 1e3 for x in body[10 * (variants * r + v):10 * (variants * r + v) + 10]] for r in range(5)]
@@ -43,7 +48,15 @@ def report(table):
         flat = sorted(x for r in rs for x in r)
         print(f"{kernel}, {label}: 5 rounds x 10 launches, mean {sum(flat) / len(flat):.2f} us ({flat[0]:.2f} .. {flat[-1]:.2f}, median {flat[len(flat) // 2]:.2f}); "
               f"round means {' '.join(f'{v:.2f}' for v in means)} (spread {max(means) - min(means):.2f})")
-if av:
+if cp:
+    report((("k_design_count", "(b) random reference, 0..8 mutations, cap 8, S = 8, no constraints", by_round(c, 1, 0)),
+            ("k_design_avoid", "max_run 3 (13 live states), S = 8, no constraints", by_round(av, 1, 0)),
+            ("k_design_count_profile", "G+C window 40..60 %, cap T, no constraints", by_round(cp, 3, 0)),
+            ("k_design_count_profile", "0..8 mutations, cap 8, no constraints", by_round(cp, 3, 1)),
+            ("k_design_count_profile", "plain, cap 0, hairpin pairs + GNRA + bias", by_round(cp, 3, 2)),
+            ("k_design_avoid_profile", "max_run 3 (13 live states), no constraints", by_round(ap, 2, 0)),
+            ("k_design_avoid_profile", "64-state set (57 live states), no constraints", by_round(ap, 2, 1))))
+elif av:
     report((("k_design_count", "(b) random reference, 0..8 mutations, cap 8, S = 8, no constraints", by_round(c, 1, 0)),
             ("k_design_avoid", "max_run 3 (13 live states), S = 8, no constraints", by_round(av, 3, 0)),
             ("k_design_avoid", "64-state set (57 live states), S = 8, no constraints", by_round(av, 3, 1)),
