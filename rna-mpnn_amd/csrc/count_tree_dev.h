@@ -1,4 +1,5 @@
-// The count tree shared by k_design_gc (design_gc.hip) and k_design_count (design_count.hip): a draw of rnampnn_design conditioned EXACTLY
+// The count tree shared by k_design_gc (design_gc.hip), k_design_count (design_count.hip) and, up to the target, k_design_count_profile
+// (design_profile.hip): a draw of rnampnn_design conditioned EXACTLY
 // on a count that is a sum over the independent units of an RNA - unpaired positions and base pairs - lying in a window.  Position t carries
 // a leaf polynomial p_t(d), d = 0..2, in the log domain (a pair's mass sits on its lower index, its upper index carries "1"); node (l, i)
 // covers the positions [i 2^l, min((i+1) 2^l, n)) and holds the log-domain convolution of its halves; the root's coefficients over the
@@ -14,9 +15,9 @@
 // One 256-thread workgroup per (RNA, sample) as in design.hip, the extent / NLL / reduction of score_dev.h; of design_dev.h the mask, the
 // fp64 row, the validated partner and the pair cells of a leaf, the logsumexp of its polynomial, the selection rule of its draw, the scratch
 // and phase C - nothing about a position under the constraints is defined here.
-// Three phases separated by barriers: (A) the tree bottom-up into dynamic LDS - level 1 one node per thread straight from the rows (level 0 is never stored), the levels above dealt flat over (node, coefficient); with SETS the
+// Three phases separated by barriers: (A, ct_inside) the tree bottom-up into dynamic LDS - level 1 one node per thread straight from the rows (level 0 is never stored), the levels above dealt flat over (node, coefficient); with SETS the
 // smallest reachable count k_min (the sum over the leaves of the smallest d with a finite p_t(d)) is reduced over the workgroup here; (B) the
-// walk down, one node per thread and level (one WAVE per node, with a wave-wide scan over the candidates, where a level has at most four
+// window and the target (ct_target), then the walk down, one node per thread and level (one WAVE per node, with a wave-wide scan over the candidates, where a level has at most four
 // nodes, and for the total): a node's count is parked in slot 0 of its own coefficients, which nobody reads once its parent has split;
 // the last step recomputes the two leaves of a level-1 node, splits and draws them into `sq` (one byte per position, the owner of a pair
 // writes both ends); when no count of 0 .. min(n, cap) is reachable (SETS only) the walk is skipped and every leaf draws at its own
@@ -201,30 +202,39 @@ __device__ __forceinline__ int ct_deg(int l, int i, int n, int cap) { return min
 __device__ __forceinline__ int ct_stride(int l, int T, int cap) { return min(min(2 << l, T), cap) + 1; }
 __device__ __forceinline__ int ct_nodes(int l, int n) { return (n + (1 << l) - 1) >> l; }
 
-// The body of both kernels; `lds` is the workgroup's dynamic LDS (tree, sq, scratch).
-template <bool SETS>
-__device__ __forceinline__ void ct_design(const CtArgs& a, unsigned char* lds) {
-    double* tree = reinterpret_cast<double*>(lds);
-    int8_t* sq = reinterpret_cast<int8_t*>(lds + a.lds_tree);                               // (T)
-    const DsScratch sc = ds_scratch(lds + a.lds_tree + a.lds_sq);
-    int* const s_i = sc.s_i;
-    int* s_min = reinterpret_cast<int*>(lds + a.lds_tree + a.lds_sq + 48);                  // 1: every leaf draws at its own minimum
-    double* s_leaf = reinterpret_cast<double*>(lds + a.lds_tree + a.lds_sq + 64);           // 3 doubles
-    const int b = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, T = a.T, cap = a.cap;
-    const unsigned long long seed = a.seed_dev ? *a.seed_dev : a.seed;
-    const unsigned long long salted = seed ^ CT_SALT;
-    int n;
-    long long row0;
-    sc_extent(a, b, tid, sc.s_f[0], n, row0);
-    const size_t pad0 = (size_t)b * T;
-    const int Ln = n > 1 ? 32 - __clz(n - 1) : 0;                  // the root is node (Ln, 0)
-    int bad = 0, kmin = 0;
-    // ---- A: the tree, bottom-up.  Level 1 from the rows, one node per thread
+// LSE over i = i0 .. i1 of term(i), the convolution of the tree: the maximum, then the sum of exp(term - maximum) in index order, -inf
+// when no term is above -inf (unrolled by four: the loads and the exps of four terms overlap).
+template <typename Term>
+__device__ __forceinline__ double ct_lse_terms(int i0, int i1, Term term) {
+    double mx = -INFINITY, sum = 0.0;
+#pragma unroll 4
+    for (int i = i0; i <= i1; ++i) mx = fmax(mx, term(i));
+#pragma unroll 4
+    for (int i = i0; i <= i1; ++i) sum += exp(term(i) - mx);
+    return mx > -INFINITY ? mx + log(sum) : -INFINITY;
+}
+
+// Phase A of every kernel on the tree: the inside tree of RNA b bottom-up into `tree` - level 1 one node per thread straight from the
+// rows, the levels above dealt flat over (node, coefficient) - and on the way `bad` and, SETS only, k_min per wave into s_i (free until
+// the sums of the kernel's last phase).  FREE: -> the sum, over the positions this thread loads, of the LSE of z_t over all four classes
+// (the count profile's free partition sum); 0 without it.  Every thread calls it; the tree, s_leaf (the only leaf of a 1-mer) and s_i
+// are valid on return.
+template <bool SETS, bool FREE>
+__device__ __forceinline__ double ct_inside(const CtArgs& a, double* tree, double* s_leaf, int* s_i, size_t pad0, long long row0, int n, int tid,
+                                            int& bad) {
+    const int T = a.T, cap = a.cap;
+    const int Ln = n > 1 ? 32 - __clz(n - 1) : 0;
+    int kmin = 0;
+    double free_sum = 0.0;
     for (int i = tid; 2 * i < n; i += SC_THREADS) {
         const int t = 2 * i;
         double l0, l1, l2, r0 = 0.0, r1 = -INFINITY, r2 = -INFINITY;
-        ct_leaf<SETS>(a, pad0, row0, n, t, l0, l1, l2, bad);
-        if (t + 1 < n) ct_leaf<SETS>(a, pad0, row0, n, t + 1, r0, r1, r2, bad);
+        const CtLeaf ll = ct_leaf<SETS>(a, pad0, row0, n, t, l0, l1, l2, bad);
+        if (FREE) free_sum += ds_lse<4>(ll.p.z, 15);
+        if (t + 1 < n) {
+            const CtLeaf lr = ct_leaf<SETS>(a, pad0, row0, n, t + 1, r0, r1, r2, bad);
+            if (FREE) free_sum += ds_lse<4>(lr.p.z, 15);
+        }
         if (SETS) kmin += ct_min_d(l0, l1, l2) + ct_min_d(r0, r1, r2);
         if (n == 1) { s_leaf[0] = l0; s_leaf[1] = l1; s_leaf[2] = l2; break; }
         double* out = tree + a.base[1] + (size_t)i * ct_stride(1, T, cap);
@@ -244,7 +254,7 @@ __device__ __forceinline__ void ct_design(const CtArgs& a, unsigned char* lds) {
     }
     if (SETS) {
         kmin = sc_wave_sum(kmin);
-        if ((tid & 63) == 0) s_i[tid >> 6] = kmin;                  // (free until the sums of phase C)
+        if ((tid & 63) == 0) s_i[tid >> 6] = kmin;
     }
     __syncthreads();
     for (int l = 2; l <= Ln; ++l) {
@@ -257,13 +267,8 @@ __device__ __forceinline__ void ct_design(const CtArgs& a, unsigned char* lds) {
             const int degL = ct_deg(l - 1, 2 * i, n, cap);
             double v;
             if (2 * i + 1 < cnodes) {
-                const int degR = ct_deg(l - 1, 2 * i + 1, n, cap), c0 = max(0, k - degR), c1 = min(k, degL);
-                double mx = -INFINITY, sum = 0.0;
-#pragma unroll 4
-                for (int c = c0; c <= c1; ++c) mx = fmax(mx, L[c] + R[k - c]);
-#pragma unroll 4
-                for (int c = c0; c <= c1; ++c) sum += exp(L[c] + R[k - c] - mx);      // (unrolled: the loads and the exps of four terms overlap)
-                v = mx > -INFINITY ? mx + log(sum) : -INFINITY;
+                const int degR = ct_deg(l - 1, 2 * i + 1, n, cap);
+                v = ct_lse_terms(max(0, k - degR), min(k, degL), [&](int c) { return L[c] + R[k - c]; });
             } else {
                 v = k <= degL ? L[k] : -INFINITY;
             }
@@ -271,35 +276,71 @@ __device__ __forceinline__ void ct_design(const CtArgs& a, unsigned char* lds) {
         }
         __syncthreads();
     }
+    return free_sum;
+}
+
+// The window of RNA b clamped to the root's degree, and what the count is conditioned on when the window holds no reachable count: the
+// nearest reachable one, or (SETS only) k_min with every leaf at its own minimum.  `root`: the root's coefficients, s_i: k_min per wave
+// as ct_inside left it.  any: a count of lo .. hi is reachable - the caller draws K from the window (ct_design) or sums over it (the
+// count profile); else K is the target and miss its distance from the window (K = lo, unreachable, under at_min).  Every lane of wave 0
+// calls it and gets the same answer: the draw's count_miss and the profile's are one computation.
+struct CtTarget { int lo, hi, deg, K, miss; bool any, at_min; };
+template <bool SETS>
+__device__ __forceinline__ CtTarget ct_target(const CtArgs& a, const double* root, const int* s_i, int b, int n, int Ln) {
+    CtTarget g;
+    g.deg = Ln ? ct_deg(Ln, 0, n, a.cap) : min(1, a.cap);           // = min(n, cap)
+    g.lo = min(max((int)a.lo[b], 0), g.deg);
+    g.hi = max(min(max((int)a.hi[b], 0), g.deg), g.lo);
+    g.K = g.lo; g.miss = 0;
+    g.any = false; g.at_min = false;
+    for (int k = g.lo; k <= g.hi; ++k) g.any = g.any || ct_finite(root[k]);
+    if (g.any) return g;
+    bool found = false;
+    for (int d = 1; d <= g.deg && !found; ++d) {                   // the nearest reachable count, the lower one first
+        const int kl = g.lo - d, kh = g.hi + d;
+        if (kl >= 0 && kl <= g.deg && ct_finite(root[kl])) { g.K = kl; g.miss = d; found = true; }
+        else if (kh <= g.deg && ct_finite(root[kh])) { g.K = kh; g.miss = d; found = true; }
+    }
+    if (SETS && !found) {                                          // nothing in 0 .. min(n, cap): k_min, every leaf at its own minimum
+        int km = 0;
+#pragma unroll
+        for (int w = 0; w < SC_WAVES; ++w) km += s_i[w];
+        g.miss = km < g.lo ? g.lo - km : km > g.hi ? km - g.hi : 0;
+        g.at_min = true;
+    }
+    return g;
+}
+
+// The body of both kernels; `lds` is the workgroup's dynamic LDS (tree, sq, scratch).
+template <bool SETS>
+__device__ __forceinline__ void ct_design(const CtArgs& a, unsigned char* lds) {
+    double* tree = reinterpret_cast<double*>(lds);
+    int8_t* sq = reinterpret_cast<int8_t*>(lds + a.lds_tree);                               // (T)
+    const DsScratch sc = ds_scratch(lds + a.lds_tree + a.lds_sq);
+    int* const s_i = sc.s_i;
+    int* s_min = reinterpret_cast<int*>(lds + a.lds_tree + a.lds_sq + 48);                  // 1: every leaf draws at its own minimum
+    double* s_leaf = reinterpret_cast<double*>(lds + a.lds_tree + a.lds_sq + 64);           // 3 doubles
+    const int b = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, T = a.T, cap = a.cap;
+    const unsigned long long seed = a.seed_dev ? *a.seed_dev : a.seed;
+    const unsigned long long salted = seed ^ CT_SALT;
+    int n;
+    long long row0;
+    sc_extent(a, b, tid, sc.s_f[0], n, row0);
+    const size_t pad0 = (size_t)b * T;
+    const int Ln = n > 1 ? 32 - __clz(n - 1) : 0;                  // the root is node (Ln, 0)
+    int bad = 0;
+    // ---- A: the tree, bottom-up
+    ct_inside<SETS, false>(a, tree, s_leaf, s_i, pad0, row0, n, tid, bad);
     // ---- B: the total from the root over the window, then the walk down
     if (tid < 64 && n > 0) {                                      // wave 0, every lane with the same window and target
         double* root = Ln ? tree + a.base[Ln] : s_leaf;
-        const int deg = Ln ? ct_deg(Ln, 0, n, cap) : min(1, cap);  // = min(n, cap)
-        const int lo = min(max((int)a.lo[b], 0), deg), hi = max(min(max((int)a.hi[b], 0), deg), lo);
-        int K = lo, miss = 0;
-        bool any = false, at_min = false;
-        for (int k = lo; k <= min(hi, deg); ++k) any = any || ct_finite(root[k]);
-        if (any) {
-            K = ct_select_wave(lo, min(hi, deg), ds_u24(salted, s, b, 0), tid, [&](int k) { return root[k]; });
-        } else {
-            bool found = false;
-            for (int d = 1; d <= deg && !found; ++d) {                 // the nearest reachable count, the lower one first
-                const int kl = lo - d, kh = hi + d;
-                if (kl >= 0 && kl <= deg && ct_finite(root[kl])) { K = kl; miss = d; found = true; }
-                else if (kh <= deg && ct_finite(root[kh])) { K = kh; miss = d; found = true; }
-            }
-            if (SETS && !found) {                                      // nothing in 0 .. min(n, cap): k_min, every leaf at its own minimum
-                int km = 0;
-#pragma unroll
-                for (int w = 0; w < SC_WAVES; ++w) km += s_i[w];
-                miss = km < lo ? lo - km : km > hi ? km - hi : 0;
-                at_min = true;
-            }
-        }
-        K = min(K, deg);
+        const CtTarget g = ct_target<SETS>(a, root, s_i, b, n, Ln);
+        int K = g.K;
+        if (g.any) K = ct_select_wave(g.lo, g.hi, ds_u24(salted, s, b, 0), tid, [&](int k) { return root[k]; });
+        K = min(K, g.deg);
         if (tid == 0) {
-            if (a.miss && s == 0) a.miss[b] = miss;
-            if (SETS) *s_min = at_min ? 1 : 0;
+            if (a.miss && s == 0) a.miss[b] = g.miss;
+            if (SETS) *s_min = g.at_min ? 1 : 0;
             root[0] = (double)K;
         }
     }
@@ -360,73 +401,6 @@ __device__ __forceinline__ void ct_design(const CtArgs& a, unsigned char* lds) {
     if (tid == 0 && a.count) a.count[(size_t)s * a.B + b] = (int)cnt;
 }
 
-// Phase A on its own, for a kernel that reads the tree without drawing from it (k_design_count_profile, design_profile.hip): the inside
-// tree of RNA b bottom-up into `tree`, the statements of ct_design's phase A (which stays where it is, so the draw kernels keep their
-// code), and on the way `bad`, k_min per wave into s_i (SETS only) and `free_sum` += the LSE of z_t over all four classes for every
-// position this thread loads.  Every thread calls it; the tree, s_leaf (the only leaf of a 1-mer) and s_i are valid on return.
-template <bool SETS>
-__device__ __forceinline__ void ct_inside(const CtArgs& a, double* tree, double* s_leaf, int* s_i, size_t pad0, long long row0, int n, int tid,
-                                          int& bad, double& free_sum) {
-    const int T = a.T, cap = a.cap;
-    const int Ln = n > 1 ? 32 - __clz(n - 1) : 0;
-    int kmin = 0;
-    for (int i = tid; 2 * i < n; i += SC_THREADS) {
-        const int t = 2 * i;
-        double l0, l1, l2, r0 = 0.0, r1 = -INFINITY, r2 = -INFINITY;
-        const CtLeaf ll = ct_leaf<SETS>(a, pad0, row0, n, t, l0, l1, l2, bad);
-        free_sum += ds_lse<4>(ll.p.z, 15);
-        if (t + 1 < n) {
-            const CtLeaf lr = ct_leaf<SETS>(a, pad0, row0, n, t + 1, r0, r1, r2, bad);
-            free_sum += ds_lse<4>(lr.p.z, 15);
-        }
-        if (SETS) kmin += ct_min_d(l0, l1, l2) + ct_min_d(r0, r1, r2);
-        if (n == 1) { s_leaf[0] = l0; s_leaf[1] = l1; s_leaf[2] = l2; break; }
-        double* out = tree + a.base[1] + (size_t)i * ct_stride(1, T, cap);
-        const int deg = ct_deg(1, i, n, cap);
-        const double l[3] = {l0, l1, l2}, r[3] = {r0, r1, r2};
-#pragma unroll
-        for (int k = 0; k <= 4; ++k) {
-            double mx = -INFINITY, sum = 0.0;
-#pragma unroll
-            for (int c = 0; c <= 2; ++c)
-                if (c <= k && k - c <= 2) mx = fmax(mx, l[c] + r[k - c]);
-#pragma unroll
-            for (int c = 0; c <= 2; ++c)
-                if (c <= k && k - c <= 2) sum += exp(l[c] + r[k - c] - mx);
-            if (k <= deg) out[k] = t + 1 < n ? (mx > -INFINITY ? mx + log(sum) : -INFINITY) : (k <= 2 ? l[k < 2 ? k : 2] : -INFINITY);
-        }
-    }
-    if (SETS) {
-        kmin = sc_wave_sum(kmin);
-        if ((tid & 63) == 0) s_i[tid >> 6] = kmin;
-    }
-    __syncthreads();
-    for (int l = 2; l <= Ln; ++l) {
-        const int stride = ct_stride(l, T, cap), cstride = ct_stride(l - 1, T, cap), nodes = ct_nodes(l, n), cnodes = ct_nodes(l - 1, n);
-        for (int idx = tid; idx < nodes * stride; idx += SC_THREADS) {
-            const int i = idx / stride, k = idx - i * stride;
-            if (k > ct_deg(l, i, n, cap)) continue;
-            const double* L = tree + a.base[l - 1] + (size_t)(2 * i) * cstride;
-            const double* R = L + cstride;
-            const int degL = ct_deg(l - 1, 2 * i, n, cap);
-            double v;
-            if (2 * i + 1 < cnodes) {
-                const int degR = ct_deg(l - 1, 2 * i + 1, n, cap), c0 = max(0, k - degR), c1 = min(k, degL);
-                double mx = -INFINITY, sum = 0.0;
-#pragma unroll 4
-                for (int c = c0; c <= c1; ++c) mx = fmax(mx, L[c] + R[k - c]);
-#pragma unroll 4
-                for (int c = c0; c <= c1; ++c) sum += exp(L[c] + R[k - c] - mx);
-                v = mx > -INFINITY ? mx + log(sum) : -INFINITY;
-            } else {
-                v = k <= degL ? L[k] : -INFINITY;
-            }
-            tree[a.base[l] + idx] = v;
-        }
-        __syncthreads();
-    }
-}
-
 // doubles of the levels 1..ceil(log2 T): node (l, i) holds min(2 * its extent within T, T, cap) + 1; base[l] (when given) = first double
 // of level l
 inline size_t ct_tree_doubles(int T, int cap, unsigned* base) {
@@ -445,9 +419,7 @@ inline size_t ct_lds_bytes(int T, int cap, size_t& tree, size_t& sq) {
 }
 // the largest T whose tree fits at that cap (a cap above T is T: the byte count grows with T)
 inline int ct_max_T(int cap) {
-    int T = 1;
     size_t tree, sq;
-    while (ct_lds_bytes(T + 1, std::min(cap, T + 1), tree, sq) <= DS_LDS_MAX) ++T;
-    return T;
+    return (int)ds_max_T([&](long long T) { return ct_lds_bytes((int)T, std::min(cap, (int)T), tree, sq); });
 }
 }  // namespace

@@ -12,29 +12,19 @@
 // time, one lane per sample: the forward walk, 2 bits per position into LDS words the lane owns (one write per 16 positions), then per
 // sample the rows, the NLL and the counts as k_design writes and reduces them (ds_write_rows).  64 and not 256 samples at a time: the
 // draws of a chunk cost 16 bytes of LDS per position, which the table needs more.  No workspace, no atomics, no host synchronisation.
-#include "design_dev.h"
+// The automaton's constants and arguments, the entry's checks and the bytes of the rows are avoid_chain_dev.h's, shared with the profile.
+#include "avoid_chain_dev.h"
 
 namespace {
-constexpr int AV_MAX_STATES = RNAMPNN_DESIGN_AVOID_MAX_STATES;
 constexpr int AV_CHUNK = 64;                   // samples that walk together: one wave
 constexpr size_t AV_LDS_SCRATCH = 96;          // the reduction's DS_SCRATCH bytes, padded
 static_assert(DS_SCRATCH <= AV_LDS_SCRATCH, "the reduction's scratch");
-static_assert(AV_MAX_STATES == 64, "one lane of a wave per state; `terminal` is one 64-bit word");
-constexpr unsigned AV_DEAD = 0xFFu;            // the column of a transition into a terminal state or out of the automaton
 
-struct AvArgs : DesignArgs {
-    const uint8_t* delta;        // (A,4)
-    unsigned long long terminal;
-    int A, live, S, words;       // states, live states, samples, 32-bit words of one sample's draws
+struct AvArgs : AvChainArgs {
+    int S, words;                // samples, 32-bit words of one sample's draws
     int32_t* hits;               // (S,B) or null
     int32_t* miss;               // (B) or null
 };
-
-__device__ __forceinline__ void av_wave_sync() {                   // LDS written by a lane is read by another lane of the SAME wave
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // the words of one sample's draws: 2 bits per position, an odd count (lanes a word stride apart fall into different banks)
 __host__ __device__ inline int av_words(int T) { return ((T + 15) / 16) | 1; }
@@ -99,7 +89,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_avoid(AvArgs a) {
                 const double v[4] = {z01.x + l[0], z01.y + l[1], z23.x + l[2], z23.y + l[3]};
                 tab[(size_t)t * AL + mine] = ds_lse<4>(v, (int)ms[t] & ok);
             }
-            av_wave_sync();
+            ds_wave_sync();
         }
     }
     __syncthreads();
@@ -163,13 +153,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_avoid(AvArgs a) {
 
 // the bytes of dynamic LDS, from (T, live states) alone: the formula include/rnampnn_hip.h gives
 size_t av_lds_bytes(long long T, long long live) {
-    const size_t t = (size_t)T, rows = (32 + 8 * (size_t)live) * t, chunk = (size_t)AV_CHUNK * 4 * (size_t)av_words((int)T);
-    return rows + chunk + 2 * 4 * AV_MAX_STATES + 4 * AV_CHUNK + AV_LDS_SCRATCH + 16 * ((t + 15) / 16);
-}
-long long av_max_T(long long live) {
-    long long T = (long long)(DS_LDS_MAX / (size_t)(32 + 8 * live));
-    while (T > 0 && av_lds_bytes(T, live) > DS_LDS_MAX) --T;
-    return T;
+    return av_rows_bytes(T, live) + (size_t)AV_CHUNK * 4 * (size_t)av_words((int)T) + 2 * 4 * AV_MAX_STATES + 4 * AV_CHUNK + AV_LDS_SCRATCH;
 }
 }  // namespace
 
@@ -179,31 +163,15 @@ extern "C" int rnampnn_design_avoid(const float* logits, int64_t n_rows, const f
                                     const uint8_t* delta, int32_t n_states, uint64_t terminal, int8_t* seqs, float* seq_nll,
                                     int32_t* infeasible, int32_t* hits, int32_t* avoid_miss, void* stream) {
     AvArgs a{};
-    const int rc = ds_prepare("rnampnn_design_avoid", "RNA", logits, n_rows, mask, cu_seqlens, B, T, temperature, S, seed, seed_dev, allowed,
-                              partner, wobble, bias, bias_per_position, seqs, seq_nll, infeasible, a, [&](int slot) {
-        if (slot == 0 && !delta) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_avoid: null delta");
-        if (slot == 0 && (n_states < 1 || n_states > AV_MAX_STATES))
-            return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_avoid: n_states = %d, an automaton has 1 .. %d states", (int)n_states, AV_MAX_STATES);
-        if (slot == 0 && (terminal & 1ull)) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_avoid: state 0, the start, is marked terminal");
-        return RNAMPNN_OK;
-    });
+    const int rc = av_prepare("rnampnn_design_avoid", logits, n_rows, mask, cu_seqlens, B, T, temperature, S, seed, seed_dev, allowed, partner, wobble,
+                              bias, bias_per_position, seqs, seq_nll, infeasible, delta, n_states, terminal, a, [] { return RNAMPNN_OK; });
     if (rc != RNAMPNN_OK) return rc;
-    if (partner)
-        return fail(RNAMPNN_ERR_UNSUPPORTED, "rnampnn_design_avoid: base pairs (a non-null partner) are not built together with forbidden motifs: a pair "
-                    "couples two distant positions, so an exact chain over (position, automaton state) would carry the class of every open pair "
-                    "in its state, 4^depth states");
-    const unsigned long long in_range = n_states == 64 ? ~0ull : ((1ull << n_states) - 1ull);
-    const int live = n_states - __builtin_popcountll(terminal & in_range);
-    const size_t lds = av_lds_bytes(T, live);
+    const size_t lds = av_lds_bytes(T, a.live);
     if (lds > DS_LDS_MAX)
         return fail(RNAMPNN_ERR_UNSUPPORTED, "rnampnn_design_avoid: T = %d with %d live states needs %zu bytes of LDS for the table of partition "
-                    "sums, the limit is %zu (T <= %lld at this automaton)", (int)T, live, lds, DS_LDS_MAX, av_max_T(live));
+                    "sums, the limit is %zu (T <= %lld at this automaton)", (int)T, a.live, lds, DS_LDS_MAX,
+                    ds_max_T([&](long long t) { return av_lds_bytes(t, a.live); }));
     if (!seqs && !seq_nll && !infeasible && !hits && !avoid_miss) return RNAMPNN_OK;    // nothing asked for
-    a.delta = delta; a.terminal = terminal & in_range; a.A = n_states; a.live = live; a.S = S; a.words = av_words(T);
-    a.hits = hits; a.miss = avoid_miss;
-    static DevAttr attr;
-    ensure_dyn_lds((const void*)k_design_avoid, lds, attr);
-    hipLaunchKernelGGL(k_design_avoid, dim3(B), dim3(SC_THREADS), lds, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return RNAMPNN_OK;
+    a.S = S; a.words = av_words(T); a.hits = hits; a.miss = avoid_miss;
+    return ds_launch<k_design_avoid>(dim3(B), lds, stream, a);
 }

@@ -50,9 +50,5 @@ extern "C" int rnampnn_design_count(const float* logits, int64_t n_rows, const f
     ct_tree_doubles(T, cap, a.base);
     a.lds_tree = (unsigned)lds_tree; a.lds_sq = (unsigned)lds_sq;
     const int passes = (seqs || seq_nll || count) ? S : 1;      // count_miss and the count of infeasible positions are those of sample 0
-    static DevAttr attr;
-    ensure_dyn_lds((const void*)k_design_count, lds, attr);
-    hipLaunchKernelGGL(k_design_count, dim3(B, passes), dim3(SC_THREADS), lds, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return RNAMPNN_OK;
+    return ds_launch<k_design_count>(dim3(B, passes), lds, stream, a);
 }

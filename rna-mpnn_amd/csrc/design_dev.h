@@ -1,13 +1,17 @@
-// Pieces shared by the six design kernels - k_design (design.hip, f32), k_design_tied (design_tied.hip), k_design_gc / k_design_count
-// (count_tree_dev.h), k_design_distinct (design_distinct.hip) and k_design_avoid (design_avoid.hip), all fp64 - and by their entries.  Everything that is about "a position
+// Pieces shared by the eight design kernels - k_design (design.hip, f32), k_design_tied (design_tied.hip), k_design_gc / k_design_count
+// (count_tree_dev.h), k_design_distinct (design_distinct.hip), k_design_avoid (design_avoid.hip, avoid_chain_dev.h) and the two profile
+// kernels of design_profile.hip, all fp64 - and by their entries.  Everything that is about "a position
 // under the constraints" has its one definition here: the arguments and the entry prologue (ds_prepare), the mask of a position (ds_mask),
 // its row (ds_load<F>), its validated partner (ds_partner), the 16 cells of a pair (ds_pair_mask), the uniform of a position, the DRAW
 // RULE as templates over the scalar type - the weights exp(z - max over the admitted), the selection over an admitted set, the joint cell
-// of a base pair - the logsumexp over an admitted set (ds_lse), the LDS ceiling and the reduction's scratch (DS_LDS_MAX, ds_scratch) and
-// phase "C" of the kernels that draw into LDS first (ds_write_rows).  So every entry draws under the same constraints as rnampnn_design
-// by construction, and one state per group draws what rnampnn_design draws.  Who uses what: k_design everything up to ds_draw_pair (its
-// draw is fused into its row loop, so it keeps that loop); k_design_tied the draw rule, the prologue, the ceiling and the scratch (its
-// td_load / td_mask sum and AND over the states of a group: other functions); the count tree and k_design_distinct all of it; k_design_avoid all of it but the partner and the pair (it refuses pairs).
+// of a base pair - the logsumexp over an admitted set (ds_lse), the LDS ceiling, the largest T under it and the reduction's scratch
+// (DS_LDS_MAX, ds_max_T, ds_scratch), the fence between lanes of one wave (ds_wave_sync), phase "C" of the kernels that draw into LDS first
+// (ds_write_rows) and the tail of an entry that launches with dynamic LDS (ds_launch).  So every entry draws under the same constraints as
+// rnampnn_design by construction, and one state per group draws what rnampnn_design draws.  Who uses what: k_design everything up to
+// ds_draw_pair (its draw is fused into its row loop, so it keeps that loop, and it asks for no dynamic LDS); k_design_tied the draw rule,
+// the prologue, the ceiling, the scratch and the tail (its td_load / td_mask sum and AND over the states of a group: other functions); the
+// count tree (both draw kernels and the count profile) and k_design_distinct all of it but the fence; the avoid chain (k_design_avoid and
+// the avoid profile) all of it but the partner and the pair (it refuses pairs); the profiles write no rows, so no ds_write_rows.
 #pragma once
 #include <type_traits>
 #include "score_dev.h"
@@ -46,6 +50,31 @@ int ds_prepare(const char* name, const char* per, const float* logits, int64_t n
     a.temperature = temperature;
     a.seqs = seqs; a.seq_nll = seq_nll; a.infeasible = infeasible;
     return RNAMPNN_OK;
+}
+
+// the largest T >= 0 whose workgroup fits the ceiling; bytes(T) grows with T.  Only an entry's refusal calls it.
+template <typename Bytes>
+long long ds_max_T(Bytes bytes) {
+    long long T = 0;
+    while (bytes(T + 1) <= DS_LDS_MAX) ++T;
+    return T;
+}
+
+// The tail of an entry whose kernel asks for dynamic LDS: the opt-in above 64 KiB (one DevAttr per kernel), the launch on SC_THREADS
+// threads and its error.  "Nothing asked for" and the refusal at the ceiling stay with the entry: their outputs and words are its own.
+template <auto Kernel, class Args>
+int ds_launch(dim3 grid, size_t lds, void* stream, const Args& a) {
+    static DevAttr attr;
+    ensure_dyn_lds((const void*)Kernel, lds, attr);
+    hipLaunchKernelGGL(Kernel, grid, dim3(SC_THREADS), lds, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return RNAMPNN_OK;
+}
+
+__device__ __forceinline__ void ds_wave_sync() {                   // LDS written by a lane is read by another lane of the SAME wave
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // the reduction's scratch at p (DS_SCRATCH bytes of LDS, 4-byte aligned)

@@ -284,9 +284,5 @@ extern "C" int rnampnn_design_distinct(const float* logits, int64_t n_rows, cons
                     "(T <= %lld at this S)", (int)S, (int)T, lds, DS_LDS_MAX, dd_max_T(S));
     if (!seqs && !seq_nll && !infeasible && !logp && !n_distinct) return RNAMPNN_OK;    // nothing asked for
     a.S = S; a.noise = noise ? 1 : 0; a.logp = logp; a.n_distinct = n_distinct;
-    static DevAttr attr;
-    ensure_dyn_lds((const void*)k_design_distinct, lds, attr);
-    hipLaunchKernelGGL(k_design_distinct, dim3(B), dim3(SC_THREADS), lds, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return RNAMPNN_OK;
+    return ds_launch<k_design_distinct>(dim3(B), lds, stream, a);
 }

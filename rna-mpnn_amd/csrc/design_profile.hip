@@ -4,9 +4,10 @@
 // the draw entry's own `infeasible` and `*_miss`.  The contract is the one include/rnampnn_hip.h documents and tests/_design_profile_ref.py
 // restates.  One 256-thread workgroup per RNA, no sample axis, no workspace, no atomics, no runtime fill / copy node, no host synchronisation.
 //
-// k_design_count_profile.  The leaves, the tree, the window, the target and the k_min rule are count_tree_dev.h's (ct_leaf, ct_inside,
-// ct_deg / ct_stride / ct_nodes, ct_min_d).  (A) ct_inside: the inside tree bottom-up into LDS, k_min and the free sum on the way.  (B) wave 0:
-// the window, the target and count_miss exactly as ct_design forms them; K* and log_z; the root's outside O(k) = 0 on K*, -inf elsewhere.
+// k_design_count_profile.  The leaves, the tree, the convolution, the window, the target and the k_min rule are count_tree_dev.h's (ct_leaf,
+// ct_inside, ct_lse_terms, ct_target, ct_deg / ct_stride / ct_nodes, ct_min_d).  (A) ct_inside: the inside tree bottom-up into LDS, k_min and
+// the free sum on the way.  (B) wave 0: ct_target - the window, the target and count_miss of the draw; K* and log_z; the root's outside
+// O(k) = 0 on K*, -inf elsewhere.
 // (C) the OUTSIDE pass top-down into a second tree of the same layout: O_L(a) = LSE_k O(k) + R(k - a), O_R(b) = LSE_k O(k) + L(k - b), dealt
 // flat over (child node, coefficient); a node whose right half is empty hands O to its left half.  (D) one level-1 node per thread: the two
 // leaves again from the rows, their outsides from the node's, then P = exp(z + O(d) - log_z) per admitted class / cell; the owner of a pair
@@ -16,7 +17,8 @@
 //   and its SIBLING's inside at once, so neither can be overwritten), doubles(T, cap) as in rnampnn_design_count, and 240 bytes of scratch.
 //   160 KiB holds T <= 1457 at cap 8 (163,792 bytes) and T <= 535 at cap >= T (the draw kernel: 2867 and 1017).
 //
-// k_design_avoid_profile.  The rows, the automaton's tables and the backward table l_t(a) are k_design_avoid's, statement for statement.
+// k_design_avoid_profile.  The rows, the automaton's tables and the backward table l_t(a) are k_design_avoid's, statement for statement
+// (avoid_chain_dev.h says why the two texts stay; the constants, the arguments and the entry's checks are that header's).
 // Then wave 0, lane = state, walks FORWARD once: alpha_t(a) lives in the lane's register; per step the lane turns its four cells into
 // exp(alpha + z + l_{t+1}(delta) - log_z), a wave butterfly sums them into P_t(c) (lane 0 writes the row and adds P z), and alpha_{t+1}(a') is
 // gathered by lane a' over its predecessor cells - a list per state built once (counting sort over the 4 A cells, cell order, four cells to a word) - from the
@@ -26,6 +28,7 @@
 //   candidates and the maxima, 512 for the automaton, 448 for the predecessor lists, 160 for the sums and the reduction's scratch.
 //   160 KiB holds T <= 1168 at L = 13 (no run longer than 3) and T <= 293 at L = 64 (the draw kernel: 1064 and 290).
 // Non-finite rows can make the outputs of THAT RNA NaN; no index depends on a value, so nothing faults and no other RNA changes.
+#include "avoid_chain_dev.h"
 #include "count_tree_dev.h"
 
 namespace {
@@ -38,13 +41,8 @@ struct PfOut {
 
 // The workgroup's totals of three doubles: wave butterfly, then one LDS hop over the four waves in ascending order - a fixed order, so two
 // calls give the same bytes.  Valid in thread 0 only; every thread calls it (one barrier).  s_d holds 3 x SC_WAVES doubles.
-__device__ __forceinline__ double pf_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ void pf_block_sums(double& x, double& y, double& z, int tid, double (*s_d)[SC_WAVES]) {
-    x = pf_wave_sum(x); y = pf_wave_sum(y); z = pf_wave_sum(z);
+    x = sc_wave_sum(x); y = sc_wave_sum(y); z = sc_wave_sum(z);
     if ((tid & 63) == 0) { s_d[0][tid >> 6] = x; s_d[1][tid >> 6] = y; s_d[2][tid >> 6] = z; }
     __syncthreads();
     if (tid != 0) return;
@@ -136,33 +134,15 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_count_profile(PfCtArgs a)
     const size_t pad0 = (size_t)b * T;
     const int Ln = n > 1 ? 32 - __clz(n - 1) : 0;
     int bad = 0;
-    double free_sum = 0.0;
     // ---- A: the inside tree
-    ct_inside<true>(a, tree, s_leaf, sc.s_i, pad0, row0, n, tid, bad, free_sum);
+    double free_sum = ct_inside<true, true>(a, tree, s_leaf, sc.s_i, pad0, row0, n, tid, bad);
     // ---- B: the window, the target, K*, log_z and the root's outside
     if (tid < 64 && n > 0) {
         const double* root = Ln ? tree + a.base[Ln] : s_leaf;
         double* oroot = Ln ? outs + a.base[Ln] : o_leaf;
-        const int deg = Ln ? ct_deg(Ln, 0, n, cap) : min(1, cap);
-        const int lo = min(max((int)a.lo[b], 0), deg), hi = max(min(max((int)a.hi[b], 0), deg), lo);
-        int K = -1, miss = 0;
-        bool any = false, at_min = false;
-        for (int k = lo; k <= min(hi, deg); ++k) any = any || ct_finite(root[k]);
-        if (!any) {
-            bool found = false;
-            for (int d = 1; d <= deg && !found; ++d) {                 // the nearest reachable count, the lower one first
-                const int kl = lo - d, kh = hi + d;
-                if (kl >= 0 && kl <= deg && ct_finite(root[kl])) { K = kl; miss = d; found = true; }
-                else if (kh <= deg && ct_finite(root[kh])) { K = kh; miss = d; found = true; }
-            }
-            if (!found) {                                              // nothing in 0 .. min(n, cap): k_min, every leaf at its own minimum
-                int km = 0;
-#pragma unroll
-                for (int w = 0; w < SC_WAVES; ++w) km += sc.s_i[w];
-                miss = km < lo ? lo - km : km > hi ? km - hi : 0;
-                at_min = true;
-            }
-        }
+        const CtTarget g = ct_target<true>(a, root, sc.s_i, b, n, Ln);
+        const int deg = g.deg, lo = g.lo, hi = g.hi, K = g.K;
+        const bool any = g.any;
         // K*: the finite counts of the window, or the target alone; log_z = LSE over K* of the root, by the wave in a fixed order
         double mx = -INFINITY, sum = 0.0;
         for (int k = tid; k <= deg; k += 64) {
@@ -176,9 +156,9 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_count_profile(PfCtArgs a)
             if (in) sum += exp(root[k] - mx);
             oroot[k] = in ? 0.0 : -INFINITY;
         }
-        sum = pf_wave_sum(sum);
+        sum = sc_wave_sum(sum);
         if (tid == 0) {
-            s_flag[0] = at_min ? 1 : 0; s_flag[1] = miss;
+            s_flag[0] = g.at_min ? 1 : 0; s_flag[1] = g.miss;
             *s_logz = mx > -INFINITY ? mx + log(sum) : -INFINITY;
         }
     }
@@ -197,13 +177,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_count_profile(PfCtArgs a)
             double v;
             if (sib < cnodes) {
                 const double* Sb = tree + a.base[l - 1] + (size_t)sib * cstride;
-                const int k1 = min(c + ct_deg(l - 1, sib, n, cap), degP);
-                double mx = -INFINITY, sum = 0.0;
-#pragma unroll 4
-                for (int k = c; k <= k1; ++k) mx = fmax(mx, O[k] + Sb[k - c]);
-#pragma unroll 4
-                for (int k = c; k <= k1; ++k) sum += exp(O[k] + Sb[k - c] - mx);
-                v = mx > -INFINITY ? mx + log(sum) : -INFINITY;
+                v = ct_lse_terms(c, min(c + ct_deg(l - 1, sib, n, cap), degP), [&](int k) { return O[k] + Sb[k - c]; });
             } else {
                 v = c <= degP ? O[c] : -INFINITY;                   // an empty right half: the left half is the node
             }
@@ -252,33 +226,19 @@ inline size_t pf_ct_lds_bytes(int T, int cap, size_t& tree) {
 }
 // the largest T whose two trees fit at that cap (a cap above T is T: the byte count grows with T)
 inline int pf_ct_max_T(int cap) {
-    int T = 1;
     size_t tree;
-    while (pf_ct_lds_bytes(T + 1, std::min(cap, T + 1), tree) <= DS_LDS_MAX) ++T;
-    return T;
+    return (int)ds_max_T([&](long long T) { return pf_ct_lds_bytes((int)T, std::min(cap, (int)T), tree); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the avoid profile
-constexpr int PF_MAX_STATES = RNAMPNN_DESIGN_AVOID_MAX_STATES;
-constexpr unsigned PF_DEAD = 0xFFu;
-constexpr int PF_PRED_WORDS = (4 * PF_MAX_STATES + 3 * PF_MAX_STATES) / 4;         // 256 cells, each of 64 lists padded to a word
-constexpr size_t PF_AV_FIXED = 8 * 4 * PF_MAX_STATES + 8 * PF_MAX_STATES + 8 * 3 * SC_WAVES + 64 + 2 * 4 * PF_MAX_STATES + 4 * PF_PRED_WORDS;
-static_assert(PF_MAX_STATES == 64, "one lane of a wave per state; `terminal` is one 64-bit word");
+constexpr int PF_PRED_WORDS = (4 * AV_MAX_STATES + 3 * AV_MAX_STATES) / 4;         // 256 cells, each of 64 lists padded to a word
+constexpr size_t PF_AV_FIXED = 8 * 4 * AV_MAX_STATES + 8 * AV_MAX_STATES + 8 * 3 * SC_WAVES + 64 + 2 * 4 * AV_MAX_STATES + 4 * PF_PRED_WORDS;
 static_assert(PF_AV_FIXED == 3680 && DS_SCRATCH <= 64, "the bytes include/rnampnn_hip.h gives");
 
-struct PfAvArgs : DesignArgs {
-    const uint8_t* delta;        // (A,4)
-    unsigned long long terminal;
-    int A, live;
+struct PfAvArgs : AvChainArgs {
     int32_t* miss;               // (B) or null
     PfOut out;
 };
-
-__device__ __forceinline__ void pf_wave_sync() {                   // LDS written by a lane is read by another lane of the SAME wave
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __global__ void __launch_bounds__(SC_THREADS) k_design_avoid_profile(PfAvArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char pfa_lds[];
@@ -286,13 +246,13 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_avoid_profile(PfAvArgs a)
     double* zs = reinterpret_cast<double*>(pfa_lds);                                // [T][4]      z of a position
     double* tab = zs + 4 * (size_t)T;                                              // [T][AL]     l_t of a live state
     double* cand = tab + (size_t)AL * T;                                           // [64][4]     alpha_t(a) + z_t(c) of an admitted live cell
-    double* tmax = cand + 4 * PF_MAX_STATES;                                       // [64]        the maximum over the cells that lead into a state
-    double (*s_d)[SC_WAVES] = reinterpret_cast<double (*)[SC_WAVES]>(tmax + PF_MAX_STATES);
+    double* tmax = cand + 4 * AV_MAX_STATES;                                       // [64]        the maximum over the cells that lead into a state
+    double (*s_d)[SC_WAVES] = reinterpret_cast<double (*)[SC_WAVES]>(tmax + AV_MAX_STATES);
     unsigned char* red = reinterpret_cast<unsigned char*>(s_d + 3);                // the reduction's scratch, 64 bytes
     const DsScratch sc = ds_scratch(red);
     unsigned* nx = reinterpret_cast<unsigned*>(red + 64);                          // [64]        delta(a, .), a byte per class
-    unsigned* col = nx + PF_MAX_STATES;                                            // [64]        the table column of delta(a, .), or PF_DEAD
-    unsigned* pw = col + PF_MAX_STATES;                                            // [112]       the predecessor cells 4 a + c of every state, cell order,
+    unsigned* col = nx + AV_MAX_STATES;                                            // [64]        the table column of delta(a, .), or AV_DEAD
+    unsigned* pw = col + AV_MAX_STATES;                                            // [112]       the predecessor cells 4 a + c of every state, cell order,
     unsigned char* pcell = reinterpret_cast<unsigned char*>(pw);                   //             four to a word, a state's list starting on a word
     unsigned char* ms = pcell + 4 * PF_PRED_WORDS;                                 // [T]         the mask of a position
     const unsigned long long term = a.terminal;
@@ -311,13 +271,13 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_avoid_profile(PfAvArgs a)
         ms[t] = (unsigned char)p.m;
         free_sum += ds_lse<4>(p.z, 15);
     }
-    if (tid < PF_MAX_STATES) {
+    if (tid < AV_MAX_STATES) {
         unsigned raw = 0, cl = 0;
         for (int c = 0; c < 4; ++c) {
-            const unsigned nxt = tid < A ? a.delta[4 * tid + c] : PF_DEAD;
+            const unsigned nxt = tid < A ? a.delta[4 * tid + c] : AV_DEAD;
             const bool dead = nxt >= (unsigned)A || ((term >> (nxt & 63u)) & 1ull);
             raw |= (nxt & 255u) << (8 * c);
-            cl |= (dead ? PF_DEAD : (unsigned)__popcll(~term & ((1ull << (nxt & 63u)) - 1ull))) << (8 * c);      // live states before it
+            cl |= (dead ? AV_DEAD : (unsigned)__popcll(~term & ((1ull << (nxt & 63u)) - 1ull))) << (8 * c);      // live states before it
         }
         nx[tid] = raw; col[tid] = cl;
     }
@@ -325,14 +285,14 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_avoid_profile(PfAvArgs a)
     // ---- B: l_t(a), t = n-1 .. 0, as k_design_avoid forms it; one wave, lane = state; then the predecessor lists
     const bool live = tid < A && !((term >> (tid & 63)) & 1ull);
     int cc[4] = {0, 0, 0, 0}, ok = 0, mine = 0, pwoff = 0, pcnt = 0;
-    if (tid < PF_MAX_STATES) {
+    if (tid < AV_MAX_STATES) {
         const unsigned cl = col[tid];
         mine = __popcll(~term & ((1ull << tid) - 1ull));
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const unsigned k = (cl >> (8 * c)) & 255u;
-            ok |= (k != PF_DEAD ? 1 : 0) << c;
-            cc[c] = k != PF_DEAD ? (int)k : 0;
+            ok |= (k != AV_DEAD ? 1 : 0) << c;
+            cc[c] = k != AV_DEAD ? (int)k : 0;
         }
         for (int t = n - 1; t >= 0; --t) {
             if (live) {
@@ -344,7 +304,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_avoid_profile(PfAvArgs a)
                 const double v[4] = {z01.x + l[0], z01.y + l[1], z23.x + l[2], z23.y + l[3]};
                 tab[(size_t)t * AL + mine] = ds_lse<4>(v, (int)ms[t] & ok);
             }
-            pf_wave_sync();
+            ds_wave_sync();
         }
         // the cells (a, c) of a live a < A whose delta is the live state `tid`, counted, scanned over the lanes, then listed in cell order
         int cnt = 0;
@@ -389,7 +349,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_avoid_profile(PfAvArgs a)
             lz_sum += l;
             pf_store4(a.out.marg, pad0 + t, p);
         }
-    } else if (tid < PF_MAX_STATES) {
+    } else if (tid < AV_MAX_STATES) {
         // ---- C: the forward walk; alpha_t(a) in the register of lane a.  The LSE of a state's incoming cells is split so that no lane
         // runs more than four exps per step whatever the fan-in of its state: the TARGET takes the maximum over its list, the SOURCES
         // turn their own four candidates into exp(candidate - that maximum) in place, the target adds them up in cell order.
@@ -419,7 +379,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_avoid_profile(PfAvArgs a)
                 const bool in = (m >> c) & 1;
                 const double l = t + 1 < n ? next[cc[c]] : 0.0;     // (cc is 0 for a dead cell: in bounds, not used)
                 av[c] = alpha + z[c];
-                p[c] = pf_wave_sum(in ? exp(av[c] + l - log_z) : 0.0);
+                p[c] = sc_wave_sum(in ? exp(av[c] + l - log_z) : 0.0);
                 cand[4 * tid + c] = in ? av[c] : -INFINITY;
             }
             if (tid == 0) {
@@ -428,35 +388,27 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_avoid_profile(PfAvArgs a)
                 for (int c = 0; c < 4; ++c) pz_sum += pf_pz(p[c], z[c]);
             }
             if (t + 1 == n) break;
-            pf_wave_sync();
+            ds_wave_sync();
             double mx = -INFINITY, sum = 0.0;
             over_list([&](double v) { mx = fmax(mx, v); });
             tmax[tid] = mx;
-            pf_wave_sync();
+            ds_wave_sync();
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const double tm = tmax[(raw >> (8 * c)) & 63u];     // (the state this cell leads to; read only for an admitted live cell)
                 cand[4 * tid + c] = ((m >> c) & 1) && tm > -INFINITY ? exp(av[c] - tm) : 0.0;
             }
-            pf_wave_sync();
+            ds_wave_sync();
             over_list([&](double v) { sum += v; });
             alpha = mx > -INFINITY ? mx + log(sum) : -INFINITY;
-            pf_wave_sync();                                         // the candidates are overwritten by the next step
+            ds_wave_sync();                                         // the candidates are overwritten by the next step
         }
     }
     pf_finish(a.out, a, a.miss, miss ? 1 : 0, b, n, tid, bad, free_sum, pz_sum, lz_sum, miss, log_z, sc, s_d);
 }
 
 // the bytes of dynamic LDS, from (T, live states) alone: the formula include/rnampnn_hip.h gives
-size_t pf_av_lds_bytes(long long T, long long live) {
-    const size_t t = (size_t)T;
-    return (32 + 8 * (size_t)live) * t + 16 * ((t + 15) / 16) + PF_AV_FIXED;
-}
-long long pf_av_max_T(long long live) {
-    long long T = (long long)(DS_LDS_MAX / (size_t)(32 + 8 * live));
-    while (T > 0 && pf_av_lds_bytes(T, live) > DS_LDS_MAX) --T;
-    return T;
-}
+size_t pf_av_lds_bytes(long long T, long long live) { return av_rows_bytes(T, live) + PF_AV_FIXED; }
 }  // namespace
 
 extern "C" int rnampnn_design_count_profile(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
@@ -488,11 +440,7 @@ extern "C" int rnampnn_design_count_profile(const float* logits, int64_t n_rows,
     ct_tree_doubles(T, cap, a.base);
     a.lds_tree = (unsigned)lds_tree; a.lds_sq = 0;
     a.out = PfOut{marginals, log_z, log_z_free, entropy};
-    static DevAttr attr;
-    ensure_dyn_lds((const void*)k_design_count_profile, lds, attr);
-    hipLaunchKernelGGL(k_design_count_profile, dim3(B), dim3(SC_THREADS), lds, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return RNAMPNN_OK;
+    return ds_launch<k_design_count_profile>(dim3(B), lds, stream, a);
 }
 
 extern "C" int rnampnn_design_avoid_profile(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
@@ -501,35 +449,19 @@ extern "C" int rnampnn_design_avoid_profile(const float* logits, int64_t n_rows,
                                             double* marginals, double* log_z, double* log_z_free, double* entropy, int32_t* infeasible,
                                             int32_t* avoid_miss, void* stream) {
     PfAvArgs a{};
-    const int rc = ds_prepare("rnampnn_design_avoid_profile", "RNA", logits, n_rows, mask, cu_seqlens, B, T, temperature, 1, 0, nullptr, allowed,
-                              partner, wobble, bias, bias_per_position, nullptr, nullptr, infeasible, a, [&](int slot) {
-        if (slot == 0 && !delta) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_avoid_profile: null delta");
-        if (slot == 0 && (n_states < 1 || n_states > PF_MAX_STATES))
-            return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_avoid_profile: n_states = %d, an automaton has 1 .. %d states", (int)n_states,
-                        PF_MAX_STATES);
-        if (slot == 0 && (terminal & 1ull))
-            return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_avoid_profile: state 0, the start, is marked terminal");
-        if (slot == 1 && marginals && ((uintptr_t)marginals & 15) != 0)
+    const int rc = av_prepare("rnampnn_design_avoid_profile", logits, n_rows, mask, cu_seqlens, B, T, temperature, 1, 0, nullptr, allowed, partner,
+                              wobble, bias, bias_per_position, nullptr, nullptr, infeasible, delta, n_states, terminal, a, [&] {
+        if (marginals && ((uintptr_t)marginals & 15) != 0)
             return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_avoid_profile: marginals must be 16-byte aligned");
         return RNAMPNN_OK;
     });
     if (rc != RNAMPNN_OK) return rc;
-    if (partner)
-        return fail(RNAMPNN_ERR_UNSUPPORTED, "rnampnn_design_avoid_profile: base pairs (a non-null partner) are not built together with forbidden "
-                    "motifs: a pair couples two distant positions, so an exact chain over (position, automaton state) would carry the class of "
-                    "every open pair in its state, 4^depth states");
     if (!marginals && !log_z && !log_z_free && !entropy && !infeasible && !avoid_miss) return RNAMPNN_OK;    // nothing asked for
-    const unsigned long long in_range = n_states == 64 ? ~0ull : ((1ull << n_states) - 1ull);
-    const int live = n_states - __builtin_popcountll(terminal & in_range);
-    const size_t lds = pf_av_lds_bytes(T, live);
+    const size_t lds = pf_av_lds_bytes(T, a.live);
     if (lds > DS_LDS_MAX)
         return fail(RNAMPNN_ERR_UNSUPPORTED, "rnampnn_design_avoid_profile: T = %d with %d live states needs %zu bytes of LDS for the table of "
-                    "partition sums, the limit is %zu (T <= %lld at this automaton)", (int)T, live, lds, DS_LDS_MAX, pf_av_max_T(live));
-    a.delta = delta; a.terminal = terminal & in_range; a.A = n_states; a.live = live; a.miss = avoid_miss;
-    a.out = PfOut{marginals, log_z, log_z_free, entropy};
-    static DevAttr attr;
-    ensure_dyn_lds((const void*)k_design_avoid_profile, lds, attr);
-    hipLaunchKernelGGL(k_design_avoid_profile, dim3(B), dim3(SC_THREADS), lds, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return RNAMPNN_OK;
+                    "partition sums, the limit is %zu (T <= %lld at this automaton)", (int)T, a.live, lds, DS_LDS_MAX,
+                    ds_max_T([&](long long t) { return pf_av_lds_bytes(t, a.live); }));
+    a.miss = avoid_miss; a.out = PfOut{marginals, log_z, log_z_free, entropy};
+    return ds_launch<k_design_avoid_profile>(dim3(B), lds, stream, a);
 }

@@ -311,9 +311,5 @@ extern "C" int rnampnn_design_tied(const float* logits, int64_t n_rows, const fl
     a.group_cu = group_cu; a.weight = weight;
     a.lds_alpha = (unsigned)lds_alpha; a.lds_sq = (unsigned)lds_sq;
     const int passes = (seqs || seq_nll) ? S : 1;               // the count of infeasible positions is that of sample 0
-    static DevAttr attr;
-    ensure_dyn_lds((const void*)k_design_tied, lds, attr);
-    hipLaunchKernelGGL(k_design_tied, dim3(G, passes), dim3(SC_THREADS), lds, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return RNAMPNN_OK;
+    return ds_launch<k_design_tied>(dim3(G, passes), lds, stream, a);
 }

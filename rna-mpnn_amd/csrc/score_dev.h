@@ -55,6 +55,11 @@ __device__ __forceinline__ float sc_wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ double sc_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 
 // the first logits row of batch row b: b * T in the padded layout, cu[b] clamped to the rows the tensor holds in the packed one
 __device__ __forceinline__ long long sc_row0(const ScRows& a, int b) {

@@ -104,6 +104,13 @@ def _design_inputs(name, logits, mask, cu_seqlens, max_len, constraints, padded=
     return lg, m, cu, B, T, [t for _, t in own], al, pa, bi, per_position, int(bool(c.wobble)) if c is not None else 1
 
 
+def _entry_call(name, args, device) -> None:
+    """Entry ``name`` of the C ABI on ``args`` - tensors go as their device pointers, scalars as they are - and the stream of ``device``;
+    raises what ``_native.check`` makes of the return code."""
+    with torch.cuda.device(device):
+        _native.check(getattr(_native.lib(), name)(*[_ptr(v) if torch.is_tensor(v) else v for v in args], _stream(device)))
+
+
 def _design_call(name, logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints, padded=(), head=None, tail=None,
                  outputs=(), entry=None):
     """One call of a design entry of the C ABI -> (seqs, seq_nll, infeasible, *the entry's further outputs).  What the entries share
@@ -121,8 +128,7 @@ def _design_call(name, logits, mask, cu_seqlens, max_len, n_samples, temperature
     more = [torch.empty(*((max(S, 0),) if per_sample else ()), max(B, 0), dtype=dtype, device=device) for dtype, per_sample in outputs]
     args = [lg, int(lg.numel()) // 4, m, cu, B, T, *its[0], float(temperature), S, _seed64(seed), None, al, pa, wobble, bi, per_position,
             *its[1], seqs, nll, bad, *more]
-    with torch.cuda.device(device):
-        _native.check(getattr(_native.lib(), entry or name)(*[_ptr(v) if torch.is_tensor(v) else v for v in args], _stream(device)))
+    _entry_call(entry or name, args, device)
     return (seqs, nll, bad, *more)
 
 
@@ -453,8 +459,7 @@ def design_profile_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor
     log_z, free, ent = (torch.empty(Bn, dtype=torch.float64, device=device) for _ in range(3))
     bad, miss = (torch.empty(Bn, dtype=torch.int32, device=device) for _ in range(2))
     args = [lg, int(lg.numel()) // 4, m, cu, B, T, float(temperature), al, pa, wobble, bi, per_position, *its, marg, log_z, free, ent, bad, miss]
-    with torch.cuda.device(device):
-        _native.check(getattr(_native.lib(), name)(*[_ptr(v) if torch.is_tensor(v) else v for v in args], _stream(device)))
+    _entry_call(name, args, device)
     return DesignProfile(marg, log_z, free, ent, bad, miss, mode)
 
 

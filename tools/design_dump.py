@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Every output of the design wrappers on the batches of the GPU tests, as .npy files: the byte comparison of two builds of the library
 (docs/experiments.md, "the design family folded").  Plain dumping - no timing, no profiler, no retry.
-usage: python tools/design_dump.py <outdir>            one child process per family (design tied gc count distinct), each under its own
+usage: python tools/design_dump.py <outdir>            one child process per family (design tied gc count distinct avoid profile), each under its own
                                                        `timeout`, stopping at the first that fails; then the number of dumps, their size
                                                        and one sha256 over all of them
        python tools/design_dump.py <outdir> <family>   that family, in this process
@@ -10,7 +10,9 @@ come from THIS checkout's tests/, and only API that the parent of this tool's co
 `diff -r <outdir a> <outdir b>` or by the printed sha256.
 Per family the `host_case()` / `case_arrays()` batch of its GPU test file, every constraint variant that file defines, temperatures 1.0,
 0.3 and 1e-3, the padded and the packed layout, the file's seed (above 2^32); tied: STATES with its weights and one state per group;
-gc: the case's windows as fractions, 40..60 % and the free window; count: caps 8 and T; distinct: S = 8 and 64, "sample" and "best".
+gc: the case's windows as fractions, 40..60 % and the free window; count: caps 8 and T; distinct: S = 8 and 64, "sample" and "best";
+avoid: every automaton of CASE_AUTOMATA under the case's sets and bias, and free; profile: the six outputs of `design_profile_from_logits`
+in the modes plain / gc_content / mutations on the count batch and avoid on the avoid batch.
 With every set of draws the `seq_nll` that `score_logits` gives for it."""
 import hashlib
 import os
@@ -19,7 +21,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.environ.get("RNAMPNN_PROBE_ROOT") or os.path.join(HERE, "..")
-FAMILIES = ("design", "tied", "gc", "count", "distinct")
+FAMILIES = ("design", "tied", "gc", "count", "distinct", "avoid", "profile")
 TEMPERATURES = (1.0, 0.3, 1e-3)
 
 
@@ -35,11 +37,17 @@ def dump_family(outdir: str, family: str) -> None:
     sys.path.insert(0, os.path.join(HERE, "..", "tests"))               # (the package is imported: these only add the batches)
     os.makedirs(outdir, exist_ok=True)
 
-    def save(tag, names, outs, logits_kw):
-        outs = list(outs)
-        outs.append(D.score_logits(seqs=outs[0], want=("seq_nll",), **logits_kw)["seq_nll"])
-        for name, t in zip(tuple(names) + ("score_seq_nll",), outs):
+    def save(tag, names, outs, logits_kw=None):
+        outs, names = list(outs), tuple(names)
+        if logits_kw is not None:                                       # draws: their score as rnampnn_score gives it
+            outs.append(D.score_logits(seqs=outs[0], want=("seq_nll",), **logits_kw)["seq_nll"])
+            names += ("score_seq_nll",)
+        for name, t in zip(names, outs):
             np.save(os.path.join(outdir, f"{family}.{tag}.{name}.npy"), t.cpu().numpy())
+
+    def automata(A):
+        from rnampnn.utils.motifs import MotifAutomaton
+        return {name: MotifAutomaton.from_motifs(motifs, max_run=max_run) for name, (motifs, max_run) in A.CASE_AUTOMATA.items()}
 
     def layouts(h, T):
         dev = {k: torch.from_numpy(h[k]).cuda() for k in ("logits", "mask", "packed", "cu")}
@@ -103,6 +111,38 @@ def dump_family(outdir: str, family: str) -> None:
                             out = D.design_distinct_from_logits(n_samples=S, temperature=temperature, seed=X.CASE_SEED, constraints=cons,
                                                                 mode=mode, **kw)
                             save(f"{vname}.t{temperature:g}.{lname}.S{S}.{mode}", triple + ("logp", "n_distinct"), out, kw)
+    elif family == "avoid":
+        import _design_avoid_ref as A
+        h = A.case_arrays()
+        variants = {"cons": DesignConstraints(torch.from_numpy(h["allowed"]), None, torch.from_numpy(h["bias"]), True).to_device("cuda"), "free": None}
+        for vname, cons in variants.items():
+            for aname, auto in automata(A).items():
+                for temperature in TEMPERATURES:
+                    for lname, kw in layouts(h, A.CASE_T):
+                        out = D.design_avoid_from_logits(n_samples=A.CASE_S, temperature=temperature, seed=A.CASE_SEED, constraints=cons,
+                                                         avoid=auto, **kw)
+                        save(f"{vname}.{aname}.t{temperature:g}.{lname}", triple + ("hits", "avoid_miss"), out, kw)
+    elif family == "profile":
+        import _design_avoid_ref as A
+        import _design_count_ref as R
+        six = ("marginals", "log_z", "log_z_free", "entropy", "infeasible", "miss")
+        h, ha = R.case_arrays(), A.case_arrays()
+        reference = torch.from_numpy(h["reference"]).cuda()
+        modes = {"plain": dict(), "gc_content": dict(gc_content=(0.4, 0.6)), "mutations": dict(mutations=(reference, 0, 8))}
+        variants = {"cons": constraints(h, None, R.CASE_WOBBLE), "wobble": constraints(h, None, True), "free": None}
+        for vname, cons in variants.items():
+            for mname, mkw in modes.items():
+                for temperature in TEMPERATURES:
+                    for lname, kw in layouts(h, R.CASE_T):
+                        out = D.design_profile_from_logits(temperature=temperature, constraints=cons, **mkw, **kw)
+                        save(f"{mname}.{vname}.t{temperature:g}.{lname}", six, out[:6])
+        variants = {"cons": DesignConstraints(torch.from_numpy(ha["allowed"]), None, torch.from_numpy(ha["bias"]), True).to_device("cuda"), "free": None}
+        for vname, cons in variants.items():
+            for aname, auto in automata(A).items():
+                for temperature in TEMPERATURES:
+                    for lname, kw in layouts(ha, A.CASE_T):
+                        out = D.design_profile_from_logits(temperature=temperature, constraints=cons, avoid=auto, **kw)
+                        save(f"avoid.{vname}.{aname}.t{temperature:g}.{lname}", six, out[:6])
     else:
         raise SystemExit(f"unknown family {family!r}: choose from {FAMILIES}")
     torch.cuda.synchronize()
