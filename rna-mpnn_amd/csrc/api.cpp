@@ -183,6 +183,10 @@ extern "C" int rnampnn_create(const RnaMpnnConfig* cfg, rnampnn_handle* out) {
                                       g.num_raw_ffn_dim, RN_D, false));
         make_gn(c, "raw_embedding.graph_norm", c->rawffn_gn_scale, c->rawffn_gn_shift);
         c->raw_chain = make_chain(c, c->raw_ffn);
+        // Without a fused instance the chain runs Linear by Linear.  Its input is raw distances and its output enters a GraphNormalization
+        // unaided, which amplifies per-residue rounding: bf16 operands put raw_emb 4.3e-2 off at width 96, f16 operands 6e-3 (the fused
+        // chains take f16 in their first Linear for the same reason)
+        for (auto& l : c->raw_ffn) l.h16 = true;
     }
     {
         int in = 2 * RN_D;
@@ -315,7 +319,7 @@ extern "C" int rnampnn_use_weight_arena(rnampnn_handle h, float* arena, void* st
 static void finalize_lin(rnampnn_ctx* c, const Lin& l, hipStream_t s) {
     launch_transpose(rawp(c, l.w), l.in, l.out, l.in, derp<float>(c, l.wt), l.out, s);
     if (c->cfg.precision == RNAMPNN_PREC_BF16)
-        launch_convert_rows_bf16(rawp(c, l.w), l.in, l.out, l.in, l.in_pad, derp<bf16_t>(c, l.wb), s);
+        launch_convert_rows_bf16(rawp(c, l.w), l.in, l.out, l.in, l.in_pad, derp<bf16_t>(c, l.wb), s, l.h16);
 }
 static void finalize_mlp2(rnampnn_ctx* c, const Mlp2& m, bool is_edge, hipStream_t s) {
     const float* w0 = rawp(c, m.w[0]);                 // [128][384] = [out][h_i | h_j | e]
@@ -454,7 +458,7 @@ static void gemm(Run& r, const Lin& l, const float* X, int ldx, float* Y, int ld
     int k2 = K1 < 0 ? 0 : l.in_pad - K1;
     if (r.fast && l.out >= 64)
         launch_gemm_bf16(r.ntot(), r.pk.Nmax, X, ldx, k1, X2, ldx2, k2, derp<bf16_t>(c, l.wb), rawp(c, l.b), l.out,
-                         l.gelu ? 1 : 0, res, ldres, Y, ldy, r.s);
+                         l.gelu ? 1 : 0, res, ldres, Y, ldy, r.s, l.h16);
     else
         launch_gemm_f32(r.ntot(), r.pk.Nmax, X, ldx, k1, X2, ldx2, k2, derp<float>(c, l.wt), rawp(c, l.b), l.out,
                         l.gelu ? 1 : 0, res, ldres, Y, ldy, r.s);

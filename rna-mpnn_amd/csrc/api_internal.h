@@ -34,8 +34,9 @@ struct Lin {                  // nn.Linear
     int in, out, in_pad;
     int w, b;                 // RawT indices
     size_t wt;                // derived: K-major f32 [in_pad][out]
-    size_t wb;                // derived: bf16 [out][in_pad] (fast path), or (size_t)-1
+    size_t wb;                // derived: bf16 [out][in_pad] (fast path; f16 when h16), or (size_t)-1
     bool gelu;
+    bool h16 = false;         // fast path without a fused chain: f16 (not bf16) operands in launch_gemm_bf16 (the raw chain, api.cpp)
 };
 struct Chain {                // fused FFN chain of the fast path (kernels_bf16.hip: k_ffn_chain)
     bool ok = false;

@@ -9,7 +9,7 @@ struct MpnnWB {              // one MLP of a ResMPNN layer, fast-path layouts
 };
 
 // weight preparation (run once per load_state_dict)
-void launch_convert_rows_bf16(const float* src, int ld_src, int rows, int cols, int cols_pad, bf16_t* dst, hipStream_t s);
+void launch_convert_rows_bf16(const float* src, int ld_src, int rows, int cols, int cols_pad, bf16_t* dst, hipStream_t s, bool f16 = false);   // f16: halfwords hold f16
 void launch_build_mlp_image(const float* wc, int ld_wc, const float* w2, int ld_w2, const float* b2, int out_perm,
                             bf16_t* img, float* b2p, hipStream_t s);
 void launch_build_embed_image(const float* w0, const float* w1, const float* b1, bf16_t* img, float* b1p, hipStream_t s);
@@ -18,10 +18,11 @@ void launch_build_embed_image(const float* w0, const float* w1, const float* b1,
 void launch_efrag_to_rows(const bf16_t* ef, const int* ntot, int nmax, int k, float* rows, hipStream_t s);
 void launch_rows_to_efrag(const float* rows, const int* ntot, int nmax, int k, const int* nbr, bf16_t* ef, hipStream_t s);
 static inline size_t efrag_bytes(int nmax, int k) { int npb = k > 16 ? 1 : 32 / k; return (size_t)((nmax + npb - 1) / npb) * 8192; }
-// node-level Linear on MFMA: Y = act([X | X2] . W^T + bias) (+ res);  W bf16 [N][K] row-major
+// node-level Linear on MFMA: Y = act([X | X2] . W^T + bias) (+ res);  W bf16 [N][K] row-major.  f16: W holds f16 (launch_convert_rows_bf16 with
+// f16) and X is rounded to f16, saturating at +-65504 - 11 significand bits for a chain whose output enters a GraphNormalization unaided
 void launch_gemm_bf16(const int* ntot, int mmax, const float* X, int ldx, int K1, const float* X2, int ldx2, int K2,
                       const bf16_t* W, const float* bias, int N, int act, const float* res, int ldres,
-                      float* Y, int ldy, hipStream_t s);   // cols >= col_split -> bf16 Yb (if Yb)
+                      float* Y, int ldy, hipStream_t s, bool f16 = false);   // cols >= col_split -> bf16 Yb (if Yb)
 void launch_edge_embed_bf16(const PackInfo& pk, int k, const float* geom, const int* nbr, const bf16_t* img,
                             const float* b0, const float* b1p, bf16_t* e, hipStream_t s);
 // node tables (launch_node_update): p_* = h.Wa^T + b1, q_* = h.Wb^T, f16 [N+1][128], natural channel order (row Nmax of q_* = zeros)

@@ -28,15 +28,16 @@
 // ------------------------------------------------------------------------------------------
 // weight preparation
 __global__ void k_convert_rows_bf16(const float* __restrict__ src, int ld_src, int rows, int cols, int cols_pad,
-                                    bf16_t* __restrict__ dst) {
+                                    bf16_t* __restrict__ dst, int f16) {
     int id = blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= rows * cols_pad) return;
     int r = id / cols_pad, c = id - r * cols_pad;
-    dst[id] = c < cols ? f2bf(src[(size_t)r * ld_src + c]) : (bf16_t)0;
+    const float v = c < cols ? src[(size_t)r * ld_src + c] : 0.f;
+    dst[id] = f16 ? __builtin_bit_cast(bf16_t, (_Float16)v) : f2bf(v);
 }
-void launch_convert_rows_bf16(const float* src, int ld_src, int rows, int cols, int cols_pad, bf16_t* dst, hipStream_t s) {
+void launch_convert_rows_bf16(const float* src, int ld_src, int rows, int cols, int cols_pad, bf16_t* dst, hipStream_t s, bool f16) {
     int total = rows * cols_pad;
-    hipLaunchKernelGGL(k_convert_rows_bf16, dim3((total + 255) / 256), dim3(256), 0, s, src, ld_src, rows, cols, cols_pad, dst);
+    hipLaunchKernelGGL(k_convert_rows_bf16, dim3((total + 255) / 256), dim3(256), 0, s, src, ld_src, rows, cols, cols_pad, dst, f16 ? 1 : 0);
 }
 
 // Fragment image of one 2-Linear MLP acting on e (see file head).
@@ -853,7 +854,14 @@ void launch_edge_embed_bf16(const PackInfo& pk, int k, const float* geomh, const
 // fragments are plain 16-byte LDS reads).  128 x 128 tile per 256-thread workgroup, K staged
 // through LDS in steps of 64 with a padded row stride (72 bf16 = 36 dwords: conflict-free
 // ds_read_b128 for 16 consecutive rows); next tile's global loads are issued before the MFMAs.
+// F16: both operands in f16 (W converted by launch_convert_rows_bf16(.., f16), X rounded here, saturating - NaN stays NaN), f16 MFMA.
 #define GB_LD 72
+__device__ __forceinline__ unsigned pack2h_sat(float a, float b) {
+    a = a > 65504.f ? 65504.f : (a < -65504.f ? -65504.f : a);
+    b = b > 65504.f ? 65504.f : (b < -65504.f ? -65504.f : b);
+    return p_pack2(a, b);
+}
+template <bool F16>
 __global__ void __launch_bounds__(256) k_gemm_bf16(const int* __restrict__ ntot_p, const float* __restrict__ X, int ldx, int K1,
         const float* __restrict__ X2, int ldx2, int K2, const bf16_t* __restrict__ W, const float* __restrict__ bias,
         int N, int act, const float* __restrict__ res, int ldres, float* __restrict__ Y, int ldy) {
@@ -897,8 +905,13 @@ __global__ void __launch_bounds__(256) k_gemm_bf16(const int* __restrict__ ntot_
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
             u32x4 w;
-            w[0] = pack2(ar[2 * v][0], ar[2 * v][1]); w[1] = pack2(ar[2 * v][2], ar[2 * v][3]);
-            w[2] = pack2(ar[2 * v + 1][0], ar[2 * v + 1][1]); w[3] = pack2(ar[2 * v + 1][2], ar[2 * v + 1][3]);
+            if (F16) {
+                w[0] = pack2h_sat(ar[2 * v][0], ar[2 * v][1]); w[1] = pack2h_sat(ar[2 * v][2], ar[2 * v][3]);
+                w[2] = pack2h_sat(ar[2 * v + 1][0], ar[2 * v + 1][1]); w[3] = pack2h_sat(ar[2 * v + 1][2], ar[2 * v + 1][3]);
+            } else {
+                w[0] = pack2(ar[2 * v][0], ar[2 * v][1]); w[1] = pack2(ar[2 * v][2], ar[2 * v][3]);
+                w[2] = pack2(ar[2 * v + 1][0], ar[2 * v + 1][1]); w[3] = pack2(ar[2 * v + 1][2], ar[2 * v + 1][3]);
+            }
             da[v] = w;
         }
         u32x4* db = reinterpret_cast<u32x4*>(Bs + srow * GB_LD + shalf * 32);
@@ -923,7 +936,7 @@ __global__ void __launch_bounds__(256) k_gemm_bf16(const int* __restrict__ ntot_
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
-                for (int b = 0; b < 2; ++b) acc[a][b] = mfma32(af[a], bfm[b], acc[a][b]);
+                for (int b = 0; b < 2; ++b) acc[a][b] = F16 ? mfma32h(af[a], bfm[b], acc[a][b]) : mfma32(af[a], bfm[b], acc[a][b]);
         }
     }
     // epilogue: the 16 rows a lane holds of one 32x32 tile are handled together - the residual loads go out as a batch
@@ -967,9 +980,10 @@ __global__ void __launch_bounds__(256) k_gemm_bf16(const int* __restrict__ ntot_
 
 void launch_gemm_bf16(const int* ntot, int mmax, const float* X, int ldx, int K1, const float* X2, int ldx2, int K2,
                       const bf16_t* W, const float* bias, int N, int act, const float* res, int ldres,
-                      float* Y, int ldy, hipStream_t s) {
+                      float* Y, int ldy, hipStream_t s, bool f16) {
     dim3 grid((mmax + 127) / 128, (N + 127) / 128);
-    hipLaunchKernelGGL(k_gemm_bf16, grid, dim3(256), 0, s, ntot, X, ldx, K1, X2, ldx2, K2, W, bias, N, act, res, ldres, Y, ldy);
+    if (f16) hipLaunchKernelGGL(k_gemm_bf16<true>, grid, dim3(256), 0, s, ntot, X, ldx, K1, X2, ldx2, K2, W, bias, N, act, res, ldres, Y, ldy);
+    else hipLaunchKernelGGL(k_gemm_bf16<false>, grid, dim3(256), 0, s, ntot, X, ldx, K1, X2, ldx2, K2, W, bias, N, act, res, ldres, Y, ldy);
 }
 
 // ------------------------------------------------------------------------------------------

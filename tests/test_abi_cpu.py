@@ -73,6 +73,27 @@ def test_error_codes_map_to_reference_exceptions(native):
         ResFeature(num_neighbours=3, num_inside_dist_atoms=1)               # feature.py:169
 
 
+@pytest.mark.parametrize("change, message", [
+    (dict(embedding_ffn_dim=48), "FFN widths must be multiples of 32"),
+    (dict(readout_hidden_dim=48), "FFN widths must be multiples of 32"),
+    (dict(post_fusion_ffn_dim=2080), "FFN widths must be multiples of 32"),
+    (dict(num_raw_ffn_dim=2080), "FFN widths must be multiples of 32"),
+    (dict(num_post_fusion_heads=3), "attention heads must be 2, 4, 8 or 16"),
+    (dict(num_embedding_attn_layers=1, num_embedding_heads=32), "attention heads must be 2, 4, 8 or 16"),
+    (dict(num_readout_layers=0), "layer counts must be >= 1"),
+])
+@pytest.mark.parametrize("precision", ["f32", "bf16"])
+def test_node_side_shapes_outside_the_range_are_refused_at_create(native, change, message, precision):
+    """The edges of the node-side range rnampnn_create accepts (widths: multiples of 32 in [32, 2048]; heads 2, 4, 8 or 16 where an
+    attention layer exists; every FFN / read-out count >= 1): one step outside is refused at create time with the library's message,
+    in both precisions.  The same head counts without an attention layer are legal (tests/_node_shape_cases.py, case no_attention)."""
+    from rnampnn.model._schema import DEFAULT_HPARAMS
+    prec = native.PREC_F32 if precision == "f32" else native.PREC_BF16
+    with pytest.raises(NotImplementedError, match=message):
+        native.Handle(dict(DEFAULT_HPARAMS, **change), prec)
+    native.Handle(dict(DEFAULT_HPARAMS, num_post_fusion_attn_layers=0, num_post_fusion_heads=3, num_embedding_heads=32), prec).close()
+
+
 def test_no_cpu_fallback():
     """The product path must fail loudly without a GPU instead of computing elsewhere."""
     import torch

@@ -9,11 +9,13 @@ the weights with the closed-form deterministic init of ``rnampnn/utils/synth.py`
 inputs + outputs as small ``.npz`` fixtures.  ``seeding()`` is deliberately not called
 (it would set float32 matmul precision to 'medium').
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py [top] [taps] [ties]
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_golden.py [top] [taps] [ties] [shapes]
 
 ``top``: the eight top-level fixtures; ``taps``: rnampnn_taps/all_layers_k6.npz, h and e after every ResMPNN layer;
 ``ties``: rnampnn_ties/*.npz, batches in which the reference's k-NN tie-break leaves slot n - 1 of a short RNA at -1 in
-some rows (1 <= T - n <= 2).  No argument = all three.
+some rows (1 <= T - n <= 2); ``shapes``: shapes_*.npz, the off-default node-side shapes S1 and S2 of tests/_node_shape_cases.py
+(heads 2 / 16 / 4, FFN widths 96 / 160 / 32).  No argument = the first three; ``shapes`` runs only when named, so that adding it
+rewrote no older fixture.
 """
 from __future__ import annotations
 
@@ -218,13 +220,31 @@ def ties_cases(outdir):
                 print(f"  RNA {b} ({n} nt): slot n - 1 is -1 in {int((idx[b, :n, n - 1] == -1).sum())} of {n} rows")
 
 
+def _load_by_path(name, *parts):
+    spec = importlib.util.spec_from_file_location(name, os.path.join(REPO, *parts))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def shapes_cases(outdir):
+    """Cases S1 and S2 of tests/_node_shape_cases.py (its table, its batch) with every stage tap."""
+    cases = _load_by_path("_node_shape_cases", "tests", "_node_shape_cases.py")
+    co, ma, la = synth.synth_batch(cases.LENS, first_index=cases.FIRST_INDEX)
+    for case, name in cases.GOLDEN_NAMES.items():
+        run_case(name, dict(cases.OVERRIDES[case]), co, ma, la, outdir=outdir, full=True)
+        assert os.path.getsize(os.path.join(outdir, name + ".npz")) < 800000        # no larger than ragged_k30.npz
+
+
 def main():
     torch.manual_seed(0)
     torch.set_num_threads(8)
     outdir = os.path.join(REPO, "tests", "golden")
     os.makedirs(outdir, exist_ok=True)
     groups = set(sys.argv[1:]) or {"top", "taps", "ties"}
-    assert groups <= {"top", "taps", "ties"}, groups
+    assert groups <= {"top", "taps", "ties", "shapes"}, groups
+    if "shapes" in groups:
+        shapes_cases(outdir)
     for g, fn in (("taps", taps_case), ("ties", ties_cases)):
         if g in groups:
             os.makedirs(os.path.join(outdir, "rnampnn_" + g), exist_ok=True)
