@@ -476,6 +476,56 @@ int rnampnn_design_avoid(const float* logits, int64_t n_rows, const float* mask,
                          const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position,
                          const uint8_t* delta, int32_t n_states, uint64_t terminal, int8_t* seqs, float* seq_nll,
                          int32_t* infeasible, int32_t* hits, int32_t* avoid_miss, void* stream);
+/* Design with REQUIRED motifs in ONE launch (csrc/design_dfa.hip): the draws of rnampnn_design, conditioned EXACTLY on the sequence being
+ * accepted by a deterministic finite automaton - every one of a list of motifs occurs somewhere (a GNRA tetraloop, a Shine-Dalgarno stretch,
+ * a primer word), none of another list does.  rnampnn/utils/motifs.py builds it (DesignAutomaton: the Aho-Corasick automaton of all words,
+ * times the set of required motifs seen so far).  rnampnn_design_avoid is the special case "every live state accepts"; this entry adds the
+ * acceptance set, automata of up to 256 states, and a table of partition sums that lives in GLOBAL memory.  The arguments are those of
+ * rnampnn_design up to bias_per_position, plus
+ *   delta (A,4) u8, device, non-null   as rnampnn_design_avoid's
+ *   kind (A) u8, HOST, non-null        bit 0 = the state is dead, bit 1 = it accepts (read only where bit 0 is clear); read during the call,
+ *                                      on the host (it sizes the table and travels to the kernel as 2 x 256 bits of launch arguments), so
+ *                                      the call stays free of host synchronisation; the array may be freed when the call returns;
+ *                                      kind[0] & 1 must be clear
+ *   n_states i32, host                 A, 1 .. RNAMPNN_DESIGN_DFA_MAX_STATES = 256 (one thread of the workgroup per state)
+ *   workspace, workspace_bytes         device memory, 8-byte aligned, at least rnampnn_design_dfa_workspace_bytes(B, T, L) =
+ *                                      8 B T L bytes, L = the states among 0 .. A-1 whose bit 0 is clear (0 when an argument is <= 0).  It
+ *                                      holds the table l_t(a) as [b][t][live column] and nothing else; its contents before the call do not
+ *                                      matter (every entry that is read was written by the same launch before), after it they are unspecified
+ * and the outputs, each nullable, are those of rnampnn_design plus
+ *   hits (S,B) i32         the dead states the written draw enters, following delta from state 0 (as rnampnn_design_avoid counts them)
+ *   accepted (S,B) i32     1 iff the state after the last position is live and accepting
+ *   dfa_miss (B) i32       1 when no admitted sequence of RNA b is accepted, else 0; the same for every sample
+ * Everything not named here is rnampnn_design_avoid's, word for word: extent, masks, bias, temperature, `allowed`, seed_dev, "an empty mask
+ * is drawn free and counts 1 in `infeasible`", z_t(c) in fp64, LSE in class order, SELECT, u24(seed, s, b, t), live and dead (a delta entry
+ * >= A is read as a dead state), and the refusal of a non-null `partner` (RNAMPNN_ERR_UNSUPPORTED, for the same reason).
+ *   Backward.  l_n(a) = 0 for a live ACCEPTING a, -inf for every other state.  For t = n-1 .. 0 and a live a: l_t(a) = LSE over the classes
+ *     c in class order of z_t(c) + l_{t+1}(delta(a,c)), a cell being admitted iff m_t has c and delta(a,c) is live.
+ *   Feasibility.  dfa_miss[b] = !(l_0(0) > -inf); an RNA of length 0 is feasible iff state 0 accepts.
+ *   Draw of sample s, feasible RNA.  rnampnn_design_avoid's walk over z_t(c) + l_{t+1}(delta(a,c)).  Every hits is 0, every accepted 1.
+ *   Infeasible RNA (dfa_miss = 1).  Every position is drawn as rnampnn_design draws an unpaired position in fp64, with the same uniform,
+ *     ignoring the automaton; `hits` and `accepted` report what was written (after a delta entry >= A, which counts, it goes on from 0).
+ *   Anchor.  With A <= 64 and every live state accepting, seqs, seq_nll, infeasible, hits and dfa_miss are byte for byte the outputs of
+ *     rnampnn_design_avoid on (delta, A, terminal = the dead states).
+ * One 256-thread workgroup per RNA: thread = state runs the backward pass with l_{t+1} and l_t in two LDS rows (one barrier per step) and
+ * stores l_t to the workspace; then 256 samples at a time walk forward, one lane each, reading their four candidates from the workspace
+ * (written by the same workgroup: a barrier orders them).  LDS does not grow with T x L.  Dynamic LDS:
+ *       bytes(T) = 32 T + 16 ceil(T / 16) + 1024 (ceil(T / 16) | 1) + 8,032
+ *     (the fp64 rows, the masks, 2 bits per position for 256 samples; the two rows of l, the automaton and the reduction's scratch):
+ *     37,392 at T = 300, 124,432 at T = 1200.  RNAMPNN_ERR_UNSUPPORTED when that exceeds 160 KiB = 163,840 bytes, for every automaton alike:
+ *     T <= 1587 (163,840 bytes); the message names the bytes, the limit and that T.  One code path: an LDS table for small T x L is not built.
+ * No atomics, no runtime fill / copy node, no host synchronisation: two calls give identical bytes, the call can sit inside a captured
+ * graph, and a draw is a pure function of (seed, s, b), the rows of RNA b and the automaton - independent of B, T, S, the layout and the
+ * workspace; the first S' of S slots are the call with S'.  RNAMPNN_ERR_BAD_ARG, before anything is launched: the cases of rnampnn_design;
+ * null delta; null kind; n_states outside 1 .. 256; bit 0 of kind[0] set; a null, misaligned or too small workspace.  Then the partner
+ * check, then the LDS check; then, with every output null, the call returns RNAMPNN_OK without a launch. */
+#define RNAMPNN_DESIGN_DFA_MAX_STATES 256
+size_t rnampnn_design_dfa_workspace_bytes(int32_t B, int32_t T, int32_t n_live);
+int rnampnn_design_dfa(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
+                       float temperature, int32_t S, uint64_t seed, const uint64_t* seed_dev, const uint8_t* allowed,
+                       const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position,
+                       const uint8_t* delta, const uint8_t* kind, int32_t n_states, void* workspace, size_t workspace_bytes,
+                       int8_t* seqs, float* seq_nll, int32_t* infeasible, int32_t* hits, int32_t* accepted, int32_t* dfa_miss, void* stream);
 /* Design PROFILES in ONE launch each (csrc/design_profile.hip): what rnampnn_design_count and rnampnn_design_avoid draw FROM, not draws - the
  * exact per-position marginals, log partition sums and entropy of the distribution the draw entry of the same mode samples, in fp64.  The
  * inputs mean exactly what they mean in that draw entry: both layouts, z_t(c) = ((double) logit_t(c) + (double) bias_t(c)) / (double)

@@ -60,6 +60,14 @@ ends) and ``avoid_miss`` (1 for a structure whose fixed positions spell a motif:
 them).  Not built together with the other modes or with a ``structure`` in ``--constraints``; the automaton of the set has at most 64
 states.
 
+    python rna-mpnn_amd/predict.py --ckpt Final.pt --data DIR --samples 8 --require GGAGG,GNRA [--avoid GAAUUC] [--max-run 3] [--constraints cons.csv ..]
+
+Required motifs (``rnampnn_design_dfa``, both families): every draw contains EVERY one of the comma-separated motifs somewhere (any expansion
+of an IUPAC motif counts) and none of ``--avoid`` / ``--max-run`` - drawn exactly from the model's distribution conditioned on that and on
+the fixed positions, not filtered.  The designs CSV gains the columns ``motif_hits``, ``required_found`` (1 when the draw holds every
+required motif) and ``require_miss`` (1 for a structure that cannot hold them: its draws ignore the motifs).  Not built together with the
+other modes, ``--profile-out`` or a ``structure`` in ``--constraints``; the automaton has at most 256 states and 6 required motifs.
+
     python rna-mpnn_amd/predict.py --ckpt Final.pt --data DIR --profile-out PREFIX [--gc-content .. | --max-mutations .. | --avoid ..] [--samples 8]
 
 Design profiles (``rnampnn_design_count_profile`` / ``rnampnn_design_avoid_profile``, both families): what the draws of the chosen mode come
@@ -107,6 +115,8 @@ def parse(argv=None):
                                                         "(default: the structure's own sequence)")
     ap.add_argument("--avoid", default=None, help="MOTIF[,MOTIF..]: no draw of --samples contains one of these substrings (AUCG, T = U, IUPAC codes)")
     ap.add_argument("--max-run", type=int, default=None, help="R: no draw of --samples holds a run of more than R equal letters")
+    ap.add_argument("--require", default=None, help="MOTIF[,MOTIF..]: every draw of --samples contains every one of these substrings somewhere "
+                                                    "(AUCG, T = U, IUPAC codes); usable with --avoid / --max-run")
     ap.add_argument("--profile-out", default=None, help="PREFIX: write the exact distribution the draws come from to PREFIX.positions.csv "
                                                         "(per-position marginals) and PREFIX.rnas.csv (log_mass, entropy)")
     return ap.parse_args(argv)
@@ -171,8 +181,8 @@ def mutations_option(args) -> dict:
 def avoid_option(args) -> dict:
     """The ``avoid`` keyword of ``predict`` from ``--avoid`` / ``--max-run``: the automaton, built (and refused) before the model is loaded;
     empty without the flags.  ``ValueError`` naming the flags with another mode and without ``--samples``."""
-    if args.avoid is None and args.max_run is None:
-        return {}
+    if (args.avoid is None and args.max_run is None) or args.require is not None:
+        return {}                                                  # (--require takes both into its own automaton: require_option)
     for flag, value in (("--states", args.states), ("--gc-content", args.gc_content), ("--distinct", args.distinct),
                         ("--max-mutations", args.max_mutations)):
         if value is not None:
@@ -181,6 +191,24 @@ def avoid_option(args) -> dict:
         raise ValueError("--avoid / --max-run need --samples N > 0")
     from rnampnn.utils.motifs import MotifAutomaton
     return dict(avoid=MotifAutomaton.from_motifs([m for m in (args.avoid or "").split(",") if m.strip()], max_run=args.max_run))
+
+
+def require_option(args) -> dict:
+    """The ``require`` keyword of ``predict`` from ``--require`` with ``--avoid`` / ``--max-run``: one automaton of both lists, built (and
+    refused) before the model is loaded; empty without ``--require``.  ``ValueError`` naming the flags with another mode or
+    ``--profile-out`` and without ``--samples``."""
+    if args.require is None:
+        return {}
+    for flag, value in (("--profile-out", args.profile_out), ("--states", args.states), ("--gc-content", args.gc_content),
+                        ("--distinct", args.distinct), ("--max-mutations", args.max_mutations)):
+        if value is not None:
+            raise ValueError(f"--require together with {flag} is not built: the automaton conditions plain single-state designs only, and no "
+                             "profile is built for it")
+    if args.samples <= 0:
+        raise ValueError("--require needs --samples N > 0")
+    from rnampnn.utils.motifs import DesignAutomaton
+    return dict(require=DesignAutomaton.from_motifs([m for m in args.require.split(",") if m.strip()],
+                                                    [m for m in (args.avoid or "").split(",") if m.strip()], max_run=args.max_run))
 
 
 def profile_option(args) -> dict:
@@ -205,6 +233,7 @@ def checkpoint_family(path: str) -> str:
 
 
 def run(args, log=print):
+    require = require_option(args)                                 # refused with every other mode and --profile-out, before the model is loaded
     profile = profile_option(args)                                 # refused with --states / --distinct here, before the model is loaded
     avoid = avoid_option(args)                                     # a combination that is not built fails here, before the model is loaded
     mutations = mutations_option(args)
@@ -218,7 +247,7 @@ def run(args, log=print):
         from rdesign.utils.predict import predict
         from rdesign.utils.train import load_checkpoint
     extra = dict(samples=args.samples, temperature=args.temperature, seed=args.seed, designs_csv=args.designs_out, **design_options(args), **gc, **distinct,
-                 **mutations, **avoid, **profile)
+                 **mutations, **avoid, **profile, **require)
     if args.states:
         if family != "rnampnn":
             raise ValueError("--states designs with rnampnn checkpoints only; for an rdesign checkpoint call RNAModel.design(states=...) "

@@ -1,7 +1,7 @@
 """Decoding from logits, as free functions over the C ABI's decode family: argmax + recovery (``rnampnn_argmax_recovery``), free draws
 (``rnampnn_sample``), scores (``rnampnn_score``), constrained and multi-state design (``rnampnn_design``, ``rnampnn_design_tied``), design
 under a G+C content window (``rnampnn_design_gc``), design within a count window / a mutation budget (``rnampnn_design_count``), distinct
-designs (``rnampnn_design_distinct``), design that avoids forbidden motifs (``rnampnn_design_avoid``), the distribution those draws come from (``rnampnn_design_count_profile``, ``rnampnn_design_avoid_profile``), the choice between them (``design_mode``, ``design_by_mode``) and the letters of class ids.  Needs the library and ``_base`` only, so both model packages import
+designs (``rnampnn_design_distinct``), design that avoids forbidden motifs (``rnampnn_design_avoid``), design with required motifs (``rnampnn_design_dfa``), the distribution those draws come from (``rnampnn_design_count_profile``, ``rnampnn_design_avoid_profile``), the choice between them (``design_mode``, ``design_by_mode``) and the letters of class ids.  Needs the library and ``_base`` only, so both model packages import
 it at module level."""
 from __future__ import annotations
 
@@ -340,6 +340,45 @@ def design_avoid_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] 
                         outputs=((torch.int32, True), (torch.int32, False)))
 
 
+def check_require(require, avoid=None, constraints=None, max_run=None):
+    """``design(..., require=..., avoid=...)`` -> the ``DesignAutomaton`` (``as_design_automaton``: every motif of ``require`` occurs, none
+    of ``avoid`` does), or None when ``require`` is None.  ``ValueError`` when the constraints carry base pairs, for the reason
+    ``check_avoid`` gives, and for what ``DesignAutomaton.from_motifs`` refuses.  Touches no device, so a caller refuses before its forward
+    pass."""
+    from ..utils.motifs import as_design_automaton
+    auto = as_design_automaton(require, avoid, max_run)
+    if auto is not None and constraints is not None and constraints.partner is not None:
+        raise ValueError("require together with base pairs is not built: a pair couples two distant positions, so an exact draw would carry the "
+                         "class of every open pair in the automaton's state; drop `structure` from the constraints (fixed nucleotides, IUPAC "
+                         "sets, omit and bias all combine with require)")
+    return auto
+
+
+def design_dfa_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
+                           max_len: Optional[int] = None, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None,
+                           require=None, avoid=None, max_run=None):
+    """``rnampnn_design_dfa`` (include/rnampnn_hip.h): the draws of ``design_from_logits`` conditioned exactly on the sequence containing
+    EVERY motif of ``require`` somewhere and none of ``avoid`` (nor, with ``max_run=r``, a run longer than r), in one launch -> (seqs,
+    seq_nll, infeasible, hits (S,B) int32 = positions of the draw at which an avoided word ends, accepted (S,B) int32 = 1 when the draw
+    holds every required motif, dfa_miss (B,) int32 = 1 when no admitted sequence of the RNA is accepted - too short, or its fixed positions
+    rule a required motif out: it is then drawn as ``design_from_logits`` draws it and ``hits`` / ``accepted`` report what it holds).
+    ``require``: a ``DesignAutomaton`` (``rnampnn.utils.motifs``; ``avoid`` and ``max_run`` are then not read) or motif strings.  Fixed /
+    IUPAC sets and either bias of ``constraints`` combine with it; base pairs are a ``ValueError`` (``check_require``).  The table of
+    partition sums lives in a workspace in global memory (``torch.empty`` here, 8 B T L bytes at L live states), so neither the automaton
+    (up to 256 states) nor T x L is bound by LDS: T <= 1587 for every automaton; beyond it the library raises ``NotImplementedError``
+    naming the limit.  Layouts as in ``design_from_logits``.  CUDA logits only (there is no CPU fallback); no host synchronisation."""
+    auto = check_require(require, avoid, constraints, max_run)
+    if auto is None:
+        raise ValueError("require is required: a DesignAutomaton or motif strings (DesignAutomaton.from_motifs(['GGAGG'], max_run=3))")
+
+    def automaton(B, T, m, cu):
+        need = int(_native.lib().rnampnn_design_dfa_workspace_bytes(max(B, 0), max(T, 0), auto.n_live))
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=logits.device)
+        return auto.delta_on(logits.device), auto.kind, auto.n_states, ws, C.c_size_t(need)
+    return _design_call("rnampnn_design_dfa", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints, tail=automaton,
+                        outputs=((torch.int32, True), (torch.int32, True), (torch.int32, False)))
+
+
 def check_distinct(distinct, states=None, gc_content=None) -> None:
     """``design(..., distinct=...)``: ``ValueError`` for an unknown mode or a combination that is not built; touches no device."""
     if distinct is not None:
@@ -356,11 +395,18 @@ DESIGN_MODES = (("avoid", ("states", "gc_content", "distinct", "mutations"),
                 ("states", (), ""))
 
 
-def design_mode(states=None, gc_content=None, distinct=None, mutations=None, avoid=None) -> str:
-    """Which entry ``design(...)`` draws from: "avoid", "mutations", "distinct", "gc_content", "states", or "plain" when none of them is given.
-    ``ValueError`` for a combination that is not built (``DESIGN_MODES``) and an unknown ``distinct``; touches no device, so a caller
-    refuses before its forward pass."""
+def design_mode(states=None, gc_content=None, distinct=None, mutations=None, avoid=None, require=None) -> str:
+    """Which entry ``design(...)`` draws from: "require", "avoid", "mutations", "distinct", "gc_content", "states", or "plain" when none of
+    them is given.  ``require`` decides first and absorbs ``avoid`` (one automaton holds both lists).  ``ValueError`` for a combination
+    that is not built (``DESIGN_MODES``; ``require`` with anything but ``avoid``) and an unknown ``distinct``; touches no device, so a
+    caller refuses before its forward pass."""
     given = {"states": states, "gc_content": gc_content, "distinct": distinct, "mutations": mutations, "avoid": avoid}
+    if require is not None:
+        for name in DESIGN_MODES[0][1]:
+            if given[name] is not None:
+                raise ValueError(f"require together with {name} is not built: the automaton conditions the draws of rnampnn_design on the "
+                                 "motifs alone")
+        return "require"
     for mode, excluded, why in DESIGN_MODES:
         if given[mode] is None:
             continue
@@ -374,10 +420,12 @@ def design_mode(states=None, gc_content=None, distinct=None, mutations=None, avo
 
 
 def design_by_mode(mode: str, logits: torch.Tensor, states=None, state_weights=None, gc_content=None, distinct=None, mutations=None,
-                   avoid=None, **kw):
+                   avoid=None, require=None, **kw):
     """The ``*_from_logits`` call of ``mode`` (``design_mode``) -> what that function returns.  ``mutations`` as ``check_mutations``
-    returns it, ``avoid`` as ``check_avoid`` does; ``kw``: the layout and the draw (mask / cu_seqlens / max_len, n_samples, temperature,
-    seed, constraints)."""
+    returns it, ``avoid`` as ``check_avoid`` does, ``require`` as ``check_require`` does (it holds ``avoid``); ``kw``: the layout and the
+    draw (mask / cu_seqlens / max_len, n_samples, temperature, seed, constraints)."""
+    if mode == "require":
+        return design_dfa_from_logits(logits, require=require, **kw)
     if mode == "avoid":
         return design_avoid_from_logits(logits, avoid=avoid, **kw)
     if mode == "mutations":

@@ -23,7 +23,7 @@ from .. import _native
 from ..config.glob import DEFAULT_SEED, REVERSE_VOCAB
 from ..utils.data import check_prefix_mask
 from ._base import NativeModule, _prep, _ptr, _stream
-from .decode import (SCORE_OUTPUTS, argmax_recovery, check_avoid, check_distinct, check_mutations, check_state_lengths, design_by_mode,  # noqa: F401
+from .decode import (SCORE_OUTPUTS, argmax_recovery, check_avoid, check_distinct, check_require, check_mutations, check_state_lengths, design_by_mode,  # noqa: F401
                      design_distinct_from_logits, design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits,
                      design_profile_from_logits,
                      letters_packed, letters_padded, sample_from_logits, score_logits)
@@ -548,7 +548,7 @@ class RNAMPNN(NativeModule):
     @torch.no_grad()
     def design(self, coords: torch.Tensor, mask: torch.Tensor, n_samples: int = 8, temperature: float = 0.1, seed: int = 0,
                T_norm: int = 0, constraints=None, states=None, state_weights=None, lengths=None, gc_content=None, distinct=None, mutations=None,
-               avoid=None):
+               avoid=None, require=None):
         """``sample`` plus the score of every draw against the SAME logits, with one forward: -> (seqs int8 (n_samples,B,T), -1 on
         padding; seq_nll (n_samples,B) f32).  The NLL is the model's own (temperature 1) likelihood, so designs drawn at different
         temperatures rank on one scale.  ``constraints`` (``rnampnn.utils.constraints.DesignConstraints``: fixed nucleotides, base
@@ -571,17 +571,23 @@ class RNAMPNN(NativeModule):
         motifs - drawn exactly from the model's distribution conditioned on that, under the fixed positions and the bias of
         ``constraints`` or free (``design_avoid_from_logits``) -> (seqs, seq_nll, infeasible, hits (n_samples,B) int32, avoid_miss (B,)
         int32 = 1 for an RNA whose fixed positions spell a motif); not built together with the other modes, and constraints that carry
-        base pairs are a ``ValueError`` before the forward pass."""
-        mode = design_mode(states, gc_content, distinct, mutations, avoid)
+        base pairs are a ``ValueError`` before the forward pass.
+        ``require`` (a ``rnampnn.utils.motifs.DesignAutomaton`` or motif strings such as ``["GGAGG", "GNRA"]``): every draw contains EVERY
+        one of the motifs somewhere, and none of ``avoid`` (motif strings or a ``MotifAutomaton``), which it absorbs - drawn exactly from
+        the model's distribution conditioned on that (``design_dfa_from_logits``) -> (seqs, seq_nll, infeasible, hits (n_samples,B) int32,
+        accepted (n_samples,B) int32, dfa_miss (B,) int32 = 1 for an RNA that cannot hold the motifs); not built together with the other
+        modes, and constraints that carry base pairs are a ``ValueError`` before the forward pass."""
+        mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require)
         mutations = check_mutations(mutations)
-        avoid = check_avoid(avoid, constraints)
+        require = check_require(require, avoid, constraints)
+        avoid = check_avoid(avoid, constraints) if require is None else None
         if states is not None and lengths is not None:
             check_state_lengths(states, lengths)
         logits = self._run(coords, mask, T_norm=T_norm)["logits"]
         if mode != "plain" or constraints is not None:
             return design_by_mode(mode, logits, mask=mask, n_samples=n_samples, temperature=temperature, seed=seed, constraints=constraints,
                                   states=states, state_weights=state_weights, gc_content=gc_content, distinct=distinct, mutations=mutations,
-                                  avoid=avoid)
+                                  avoid=avoid, require=require)
         seqs = sample_from_logits(logits, mask, temperature, n_samples, seed)
         return seqs, score_logits(logits, mask=mask, seqs=seqs, want=("seq_nll",))["seq_nll"]
 

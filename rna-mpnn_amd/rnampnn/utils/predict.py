@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from ..config.glob import VOCAB
-from ..model.decode import (check_avoid, check_budget, design_by_mode, design_mode, design_profile_from_logits, letters_packed, letters_padded,
+from ..model.decode import (check_avoid, check_budget, check_require, design_by_mode, design_mode, design_profile_from_logits, letters_packed, letters_padded,
                             sample_from_logits, score_logits)
 from .constraints import batch_constraints, mutation_references, padded_references
 from .data import PackedLoader, bucket_batches, fill_nan_deterministic, read_fasta
@@ -118,6 +118,9 @@ def design_columns(mode: str, extras=(), lens=()):
     """The last columns that ``designs_csv`` gains in a design mode (``design_mode``) -> (their header, cells, filled): ``cells(s, r)``
     the fields of sample s of row r, ``filled`` [B] the slots of a row that hold a sequence, or None for all of them.  ``extras``: the
     two outputs of the mode's entry past (seqs, seq_nll, infeasible), ``lens`` the rows' lengths; without them only the header counts."""
+    if mode == "require":                                           # three outputs: hits and accepted per sample, dfa_miss per row
+        hits, found, miss = (t.cpu().tolist() for t in extras) if extras else (None, None, None)
+        return ",motif_hits,required_found,require_miss", lambda s, r: (hits[s][r], found[s][r], miss[r]), None
     per_sample, per_row = (t.cpu().tolist() for t in extras) if extras else (None, None)
     if mode == "gc_content":
         return ",gc,gc_miss", lambda s, r: (f"{per_sample[s][r] / lens[r]:.6f}", per_row[r]), None
@@ -136,6 +139,24 @@ def check_profile(profile_prefix, states=None, distinct=None) -> None:
     if profile_prefix and (states is not None or distinct is not None):
         raise ValueError("a design profile together with states or distinct is not built: the profile is the distribution of plain, G+C, "
                          "mutation-budget and motif-avoiding single-state draws")
+
+
+def check_require_run(require, avoid, samples: int, profile_prefix, constraints) -> object:
+    """``predict(..., require=...)`` -> the ``DesignAutomaton`` that holds ``require`` and ``avoid``, or None without ``require``.
+    ``ValueError`` without samples, with a profile (none is built for this mode) and with a structure in ``constraints``; touches no
+    device."""
+    auto = check_require(require, avoid)
+    if auto is None:
+        return None
+    if profile_prefix:
+        raise ValueError("a design profile together with require is not built: the profile entries know forbidden motifs only")
+    if samples <= 0:
+        raise ValueError("required motifs need samples > 0")
+    paired = sorted(rid for rid, (_, structure) in (constraints or {}).items() if structure)
+    if paired:
+        raise ValueError(f"require together with base pairs is not built (an exact draw would carry every open pair in the automaton's "
+                         f"state): drop `structure` from the constraints of {paired[:3]}{' ...' if len(paired) > 3 else ''}")
+    return auto
 
 
 def profile_batch(store: dict, idx, lens, logits, cu, max_len: int, temperature: float, cons, gc_content, mutations, avoid) -> None:
@@ -162,7 +183,7 @@ def write_profile(prefix: str, ids, store: dict) -> None:
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
             wobble: bool = True, states: Optional[dict] = None, gc_content=None, distinct=None, mutations=None,
-            avoid=None, profile_prefix: Optional[str] = None) -> List[Tuple[str, str]]:
+            avoid=None, profile_prefix: Optional[str] = None, require=None) -> List[Tuple[str, str]]:
     """Design a sequence for every structure under ``data_path`` in length-bucketed var-len batches (``forward_packed``): the tree
     read-out on the packed embedding when one is attached, else the read-out's argmax (``rnampnn_score``'s ``pred``); write ``out_csv``
     with one ``pdb_id,seq`` row per structure in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure
@@ -192,12 +213,17 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     ``designs_csv`` gains the last columns ``motif_hits`` (positions of the draw at which a motif ends: 0 unless ``avoid_miss``) and
     ``avoid_miss`` (1 for a structure whose fixed positions spell a motif).  Not built together with the other modes; a constraints
     table with a structure column that is not empty is a ``ValueError`` before the first forward pass.
+    ``require`` (a ``DesignAutomaton`` or motif strings): required motifs - the draws come from ``rnampnn_design_dfa`` and contain EVERY one
+    of them somewhere and none of ``avoid``, which it absorbs.  ``designs_csv`` gains the last columns ``motif_hits``, ``required_found``
+    (1 when the draw holds every required motif) and ``require_miss`` (1 for a structure that cannot hold them: too short, or its fixed
+    positions rule one out).  Not built together with the other modes, a profile or a structure in ``constraints``.
     ``profile_prefix``: also write the design profile of every structure - the exact distribution the draws of the chosen mode come from
     under ``temperature`` and the constraints (``design_profile_from_logits``) - to ``PREFIX.positions.csv`` and ``PREFIX.rnas.csv``
     (``write_profile``), with or without ``samples``.  Not built together with ``states`` or ``distinct``."""
-    mode = design_mode(states, gc_content, distinct, mutations, avoid)
+    mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require)
     check_profile(profile_prefix, states, distinct)
-    avoid = check_avoid(avoid)
+    require = check_require_run(require, avoid, samples, profile_prefix, constraints)
+    avoid = check_avoid(avoid) if require is None else None
     if avoid is not None:
         if samples <= 0 and not profile_prefix:
             raise ValueError("forbidden motifs need samples > 0")
@@ -251,7 +277,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
         if samples <= 0:
             continue
         draws, dnll, bad, *extras = draw_batch(
-            logits, cu, max_len, samples, temperature, seed + bi, cons, mode, gc_content=gc_content, distinct=distinct, avoid=avoid,
+            logits, cu, max_len, samples, temperature, seed + bi, cons, mode, gc_content=gc_content, distinct=distinct, avoid=avoid, require=require,
             mutations=None if mutations is None else (padded_references(refs, idx, max_len), (mutations[0], mutations[1])),
             states=None if gs is None else [len(groups[g][1]) for g in gs],
             state_weights=None if gs is None else [w for g in gs for w in groups[g][2]])

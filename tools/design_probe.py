@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The measurement behind DESIGN.md section 9 "Constrained design", "Multi-state design", "Design under a G+C window", "Distinct designs",
-"Mutation budget", "Forbidden motifs" and "Design profiles" (profiles/design_profile_kernel_stats.txt, profiles/design_kernel_stats.txt, profiles/design_tied_kernel_stats.txt, profiles/design_gc_kernel_stats.txt,
+"Mutation budget", "Forbidden motifs", "Required motifs" and "Design profiles" (profiles/design_dfa_kernel_stats.txt, profiles/design_profile_kernel_stats.txt, profiles/design_kernel_stats.txt, profiles/design_tied_kernel_stats.txt, profiles/design_gc_kernel_stats.txt,
 profiles/design_distinct_kernel_stats.txt, profiles/design_count_kernel_stats.txt, profiles/design_avoid_kernel_stats.txt): the C2 batch (256 RNAs x 100..140 nt), S = 8 sequences per RNA.
 usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + rnampnn_score (seq_nll): the unconstrained pair of launches
        python tools/design_probe.py design [calls=50]         rnampnn_design: free, then with a hairpin's pairs + a fixed GNRA loop per RNA
@@ -25,6 +25,11 @@ usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + r
                                                               rnampnn_design_count_profile with the G+C window 40..60 % (cap T), with 0..8
                                                               mutations (cap 8) and plain under the hairpins (cap 0);
                                                               rnampnn_design_avoid_profile with max_run = 3 and with the 64-state set
+       python tools/design_probe.py dfa                       rnampnn_design (free, hairpin) and then, in 5 alternating rounds of 10 calls each,
+                                                              rnampnn_design_avoid max_run = 3, S = 8 (the yardstick) and rnampnn_design_dfa:
+                                                              the same automaton with every live state accepting (the same work, the table
+                                                              in global memory), require GGAGG + max_run = 3, and require GGAGG and CUUCG +
+                                                              max_run = 3 (89 states); then the yield of filtering free draws for GGAGG
 HIP events around each loop of back-to-back calls of the Python wrappers.  Run either under `rocprofv3 --kernel-trace --stats -- python ...`
 (a run of its own) for the kernels' own times.  RNAMPNN_PROBE_ROOT: another checkout (with its library built) to take the package from -
 the `sample_score` leg uses nothing newer than rnampnn_score, so it runs on the parent commit as well."""
@@ -186,6 +191,51 @@ else:
         for tag, auto, out in (("max_run 3", run3, variants[1][1]()), ("64-state set", wide, variants[2][1]())):
             print(f"{tag}: hits of the draws {int(out[3].sum())} (recounted {int(auto.hits(out[0]).sum())}), avoid_miss total {int(out[4].sum())}, "
                   f"mean NLL per nt {float(out[1].sum()) / (8 * int(mask.sum())):.4f}; rnampnn_design's free draws hold {int(auto.hits(free).sum())} hits")
+    if what == "dfa":
+        # Four variants in alternating rounds of one process, so that k_design_dfa is compared with k_design_avoid of the SAME run.
+        from rnampnn.model import decode as D
+        from rnampnn.utils.motifs import DesignAutomaton, MotifAutomaton
+        rounds, per_round, warm = 5, 10, 3
+        kw = dict(temperature=0.1, seed=1, n_samples=8)
+        run3 = MotifAutomaton.from_motifs([], max_run=3)
+        same = DesignAutomaton(run3.delta, torch.tensor([1 if (run3.terminal >> a) & 1 else 2 for a in range(run3.n_states)], dtype=torch.uint8),
+                               run3.words)
+        one = DesignAutomaton.from_motifs(["GGAGG"], max_run=3)
+        two = DesignAutomaton.from_motifs(["GGAGG", "CUUCG"], max_run=3)
+        variants = [
+            (f"rnampnn_design_avoid max_run 3 ({run3.n_live} live states), S 8", lambda: D.design_avoid_from_logits(logits, mask=m, avoid=run3, **kw)),
+            (f"rnampnn_design_dfa max_run 3, every live state accepting ({same.n_live} live states), S 8",
+             lambda: D.design_dfa_from_logits(logits, mask=m, require=same, **kw)),
+            (f"rnampnn_design_dfa require GGAGG, max_run 3 ({one.n_states} states, {one.n_live} live), S 8",
+             lambda: D.design_dfa_from_logits(logits, mask=m, require=one, **kw)),
+            (f"rnampnn_design_dfa require GGAGG and CUUCG, max_run 3 ({two.n_states} states, {two.n_live} live), S 8",
+             lambda: D.design_dfa_from_logits(logits, mask=m, require=two, **kw))]
+        for _, fn in variants:
+            for _ in range(warm):
+                fn()
+        torch.cuda.synchronize()
+        times = [[] for _ in variants]
+        for _ in range(rounds):
+            for v, (_, fn) in enumerate(variants):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(per_round):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                times[v].append(e0.elapsed_time(e1) * 1e3 / per_round)
+        for (name, _), t in zip(variants, times):
+            print(f"B {B} T {T} nt {int(mask.sum())} {name}: {sum(t) / len(t):.2f} us per call, rounds {min(t):.2f} .. {max(t):.2f} "
+                  f"({rounds} alternating rounds of {per_round} back-to-back calls, events, output allocation included)")
+        a, d = variants[0][1](), variants[1][1]()
+        print("every live state accepting against rnampnn_design_avoid: " + ", ".join(
+            f"{k} equal {bool((x == y).all())}" for k, x, y in zip(("seqs", "seq_nll", "infeasible", "hits", "miss"), a, d[:4] + d[5:])))
+        free = M.design_from_logits(logits, mask=m, **kw)[0]
+        word = DesignAutomaton.from_motifs(["GGAGG"])
+        for tag, auto, out in (("require GGAGG, max_run 3", one, variants[2][1]()), ("require GGAGG and CUUCG, max_run 3", two, variants[3][1]())):
+            print(f"{tag}: accepted {int(out[4].sum())} of {8 * B} draws, hits {int(out[3].sum())}, dfa_miss total {int(out[5].sum())}, "
+                  f"mean NLL per nt {float(out[1].sum()) / (8 * int(mask.sum())):.4f}")
+        print(f"filtering yield: {int(word.scan(free)[1].sum())} of the {8 * B} free draws of rnampnn_design at temperature 0.1 contain GGAGG")
     if what == "profile":
         # Seven variants in alternating rounds of one process: the two draw kernels the profiles share their tables with, then the profiles.
         from rnampnn.model import decode as D
