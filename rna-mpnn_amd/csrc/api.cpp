@@ -662,7 +662,8 @@ static int forward_core(Run& r, rnampnn_handle h, const RnaMpnnForwardIO* io, co
     hipStream_t s = r.s;
 
     // ---- ResFeature.forward (feature.py:588-592)
-    launch_geom(io->coords, r.pk, t_norm, io->raw, w.raw_p, w.geom, r.fast ? w.geomh : nullptr, s);
+    // (the f32 record only where it is read: the bf16 path gathers geomh)
+    launch_geom(io->coords, r.pk, t_norm, io->raw, w.raw_p, r.fast ? nullptr : w.geom, r.fast ? w.geomh : nullptr, s);
     const bool fused_first = r.fast && io->stop_after != 1;
     {   // raw_project (feature.py:183, 28 -> 128) in exact f32 on both paths: the GraphNorm behind the embedding stack removes the common part of
         // its output and amplifies the rounding of the inputs (bf16 operands here cost 4 % of h0: tools/tap_errors.py); 0.1 GFLOP at the C2 batch

@@ -229,9 +229,11 @@ __device__ __forceinline__ void store_geomh(const float* g, float* __restrict__ 
 __device__ __forceinline__ void store_geom(const float* c, float* __restrict__ geom, float* __restrict__ geomh, size_t row) {
     float g[RN_GEOM];
     geom_record(c, g);
-    float* gp = geom + row * RN_GEOM;
+    if (geom) {                                                 // null: the f32 record has no reader (the bf16 forward gathers geomh only)
+        float* gp = geom + row * RN_GEOM;
 #pragma unroll
-    for (int i = 0; i < RN_GEOM; ++i) gp[i] = g[i];
+        for (int i = 0; i < RN_GEOM; ++i) gp[i] = g[i];
+    }
     if (geomh) store_geomh(g, geomh + row * RN_GEOMH);
 }
 
@@ -414,22 +416,37 @@ __global__ void __launch_bounds__(256) k_knn(const float* __restrict__ coords, P
     }
 }
 
-// The same selection with every lane's candidates in REGISTERS as a sorted queue (max_len <= 16 NK): the 16 lanes of a row each sort
-// their NK keys once (odd-even transposition network), an extraction round is then one 16-lane min-reduction of the queue HEADS and a
-// conditional shift of the winner's queue - no re-scan of the row per round (the re-scan was 3/4 of the instructions of k_knn<16>).
-// Identical output: ascending (distance, index) order, same phantom / -1 rule.
+// The same selection with every lane's candidates as a sorted QUEUE (max_len <= 16 NK): the 16 lanes of a row each sort their NK keys once in
+// registers (odd-even transposition network) and park the queue in LDS as (distance bits, j) pairs, slot-major (slot t of thread x at word pair
+// (t - 1) * 256 + x, slot 0 being the head: a wave's heads sit on distinct banks whatever their depths); a lane keeps its HEAD in two registers.  An extraction round is the
+// lexicographic minimum of the heads in two 32-bit steps - v_min_u32 over the row's 16 lanes on the distance bits (non-negative floats order as
+// unsigned integers), then on j among the lanes that hold that distance - and only the winner moves on to its next slot: no re-scan of the row
+// (3/4 of the instructions of k_knn<16>), no shift of a register queue and no 64-bit lane traffic per round (2/3 of the instructions of the
+// register-queue form).  Slot NK of every lane is the all-ones pair an exhausted queue reads.  A row's results collect in its lanes (slot s in
+// lane s mod 16) and leave in one store per 16 slots, with the phantom / -1 tail.  Identical output: ascending (distance, index) order, same
+// phantom / -1 rule.
+template <int NK> constexpr int knn_queue_lds_bytes(int T) { return ((3 * T + 3) & ~3) * 4 + NK * 256 * 8; }
+
+__device__ __forceinline__ unsigned row16_min_u32(unsigned v) {      // all-reduce over the 16 lanes of a DPP row (row_ror 8, 4, 2, 1)
+#define KNN_ROR(n) v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x120 + (n), 0xf, 0xf, false))
+    KNN_ROR(8); KNN_ROR(4); KNN_ROR(2); KNN_ROR(1);
+#undef KNN_ROR
+    return v;
+}
+
+// Body of k_knn_queue, one 256-thread workgroup: rows [rowblk * rows_per_block, +rows_per_block) of RNA b.  sm: knn_queue_lds_bytes<NK>(T) bytes.
 template <int NK>
-__global__ void __launch_bounds__(256) k_knn_queue(const float* __restrict__ coords, PackInfo pk, int Tp, int k, int rows_per_block,
-                                                    int* __restrict__ nbr, int64_t* __restrict__ eidx) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
+__device__ __forceinline__ void knn_queue_role(const float* __restrict__ coords, const PackInfo& pk, int Tp, int k, int rows_per_block,
+                                               const int b, const int rowblk, int* __restrict__ nbr, int64_t* __restrict__ eidx, float* sm) {
     constexpr int G = 16, GROUPS = 256 / G;
-    const int b = blockIdx.x;
     const int n = pk.len[b];
     const int T = pk.T;
-    const int row0 = blockIdx.y * rows_per_block;
+    const int row0 = rowblk * rows_per_block;
     if (row0 >= T) return;
     const int gl = threadIdx.x % G, grp = threadIdx.x / G;
     float* cen = sm;                       // [T][3]
+    uint2* const qb = reinterpret_cast<uint2*>(sm + ((3 * T + 3) & ~3)) + threadIdx.x;       // this lane's slot t >= 1: qb[(t - 1) * 256]
+    qb[(NK - 1) * 256] = make_uint2(~0u, ~0u);
     if (row0 < n) {
         for (int j = threadIdx.x; j < n; j += 256) {
             const float* c = coords + (size_t)(pk.packed_in ? pk.cu[b] + j : b * T + j) * 21;
@@ -442,6 +459,7 @@ __global__ void __launch_bounds__(256) k_knn_queue(const float* __restrict__ coo
     __syncthreads();
     const int base = pk.cu[b];
     const int row_end = min(T, row0 + rows_per_block);
+    const int wave_row = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) * (64 / G);
     for (int i0 = row0; i0 < row_end; i0 += GROUPS) {
         const int i = i0 + grp;
         const bool row_live = i < row_end;
@@ -470,53 +488,56 @@ __global__ void __launch_bounds__(256) k_knn_queue(const float* __restrict__ coo
                 const unsigned long long lo = q[t] < q[t + 1] ? q[t] : q[t + 1], hi = q[t] < q[t + 1] ? q[t + 1] : q[t];
                 q[t] = lo; q[t + 1] = hi;
             }
-        const int nreal = real ? min(k, n - 1) : 0;
-        int nmax = nreal;                            // wave-uniform trip count
+        // (a lane's LDS slots are written and read by that lane only: program ordered, no barrier between row passes)
 #pragma unroll
-        for (int o = G; o < 64; o <<= 1) nmax = max(nmax, __shfl_xor(nmax, o, 64));
+        for (int t = 1; t < NK; ++t) qb[(t - 1) * 256] = make_uint2((unsigned)(q[t] >> 32), (unsigned)q[t]);
+        unsigned hd = (unsigned)(q[0] >> 32), hj = (unsigned)q[0];      // head: distance bits, j; both all ones when the queue is empty
+        int hs = 0;                                  // the slot behind the head, as an index into qb
+        const int nreal = real ? min(k, n - 1) : 0;
+        // wave-uniform trip count: the wave's rows i0 + wave_row .. + 3 share n, so the first of them decides
+        const int nmax = i0 + wave_row < min(row_end, n) ? min(k, n - 1) : 0;
         const size_t pbase = (size_t)(base + i) * k;
         const size_t obase = ((size_t)b * T + i) * k;
-        for (int s = 0; s < nmax; ++s) {
-            // all-reduce min over the 16 lanes of the row by DPP rotations within the row (row_ror 8, 4, 2, 1): VALU moves instead of
-            // four dependent trips through the LDS crossbar (ds_bpermute) - the extraction loop is a latency chain
-            unsigned long long best = q[0];
-#define KNN_ROR(n) do {                                                                                                      \
-                const unsigned lo_ = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)best, 0x120 + (n), 0xf, 0xf, false);            \
-                const unsigned hi_ = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(best >> 32), 0x120 + (n), 0xf, 0xf, false);     \
-                const unsigned long long other_ = ((unsigned long long)hi_ << 32) | lo_;                                     \
-                best = other_ < best ? other_ : best;                                                                        \
-            } while (0)
-            KNN_ROR(8); KNN_ROR(4); KNN_ROR(2); KNN_ROR(1);
-#undef KNN_ROR
-            if (q[0] == best && best != ~0ull) {     // keys are unique (they carry j): exactly one lane of the group shifts
-#pragma unroll
-                for (int t = 0; t + 1 < NK; ++t) q[t] = q[t + 1];
-                q[NK - 1] = ~0ull;
+        for (int s0 = 0; s0 < k; s0 += G) {
+            unsigned res = 0u;                       // lane gl: the neighbour of slot s0 + gl
+            for (int u = 0; u < G; ++u) {
+                if (s0 + u >= nmax) break;
+                const unsigned dmin = row16_min_u32(hd);
+                const unsigned cj = hd == dmin ? hj : ~0u;
+                const unsigned jmin = row16_min_u32(cj);
+                if (cj == jmin && jmin != ~0u) {     // (distance, j) pairs of a row are unique: one winner; an all-empty row has none
+                    const uint2 h = qb[hs];
+                    hs += 256;
+                    hd = h.x; hj = h.y;
+                }
+                res = gl == u ? jmin : res;
             }
-            if (gl == 0 && s < nreal) {
-                const int j = (int)(best & 0xffffffffu);
-                nbr[pbase + s] = base + j;
-                if (eidx) eidx[obase + s] = j;
-            }
-        }
-        if (real) {
-            for (int s = nreal + gl; s < k; s += G) {
-                const bool phantom = (s == n - 1) && (n < Tp);
-                nbr[pbase + s] = phantom ? pk.Nmax + b : -1;
-                if (eidx) eidx[obase + s] = phantom ? n : -1;
+            const int s = s0 + gl;
+            if (real && s < k) {
+                const bool found = s < nreal, phantom = (s == n - 1) && (n < Tp);
+                nbr[pbase + s] = found ? base + (int)res : phantom ? pk.Nmax + b : -1;
+                if (eidx) eidx[obase + s] = found ? (int)res : phantom ? n : -1;
             }
         }
     }
 }
 
+template <int NK>
+__global__ void __launch_bounds__(256) k_knn_queue(const float* __restrict__ coords, PackInfo pk, int Tp, int k, int rows_per_block,
+                                                    int* __restrict__ nbr, int64_t* __restrict__ eidx) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    knn_queue_role<NK>(coords, pk, Tp, k, rows_per_block, blockIdx.x, blockIdx.y, nbr, eidx, sm);
+}
+
+static constexpr int kKnnQueueRows = 32;             // rows of one k-NN workgroup (two passes of its 16 row groups)
+
 int launch_knn(const float* coords, const PackInfo& pk, int Tp, int k, int* nbr, int64_t* eidx, hipStream_t s) {
-    if (pk.T <= 256) {                  // register-resident sorted queues
-        const int rpb = 32;
+    if (pk.T <= 256) {                  // sorted per-lane queues
+        const int rpb = kKnnQueueRows;
         dim3 grid(pk.B, (pk.T + rpb - 1) / rpb);
-        const size_t lds = (size_t)3 * pk.T * sizeof(float);
-        if (pk.T <= 64) hipLaunchKernelGGL(k_knn_queue<4>, grid, dim3(256), lds, s, coords, pk, Tp, k, rpb, nbr, eidx);
-        else if (pk.T <= 144) hipLaunchKernelGGL(k_knn_queue<9>, grid, dim3(256), lds, s, coords, pk, Tp, k, rpb, nbr, eidx);
-        else hipLaunchKernelGGL(k_knn_queue<16>, grid, dim3(256), lds, s, coords, pk, Tp, k, rpb, nbr, eidx);
+        if (pk.T <= 64) hipLaunchKernelGGL(k_knn_queue<4>, grid, dim3(256), knn_queue_lds_bytes<4>(pk.T), s, coords, pk, Tp, k, rpb, nbr, eidx);
+        else if (pk.T <= 144) hipLaunchKernelGGL(k_knn_queue<9>, grid, dim3(256), knn_queue_lds_bytes<9>(pk.T), s, coords, pk, Tp, k, rpb, nbr, eidx);
+        else hipLaunchKernelGGL(k_knn_queue<16>, grid, dim3(256), knn_queue_lds_bytes<16>(pk.T), s, coords, pk, Tp, k, rpb, nbr, eidx);
         return 0;
     }
     const size_t lds16 = (size_t)(3 + 16) * pk.T * sizeof(float);
