@@ -526,6 +526,68 @@ int rnampnn_design_dfa(const float* logits, int64_t n_rows, const float* mask, c
                        const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position,
                        const uint8_t* delta, const uint8_t* kind, int32_t n_states, void* workspace, size_t workspace_bytes,
                        int8_t* seqs, float* seq_nll, int32_t* infeasible, int32_t* hits, int32_t* accepted, int32_t* dfa_miss, void* stream);
+/* Design with motifs UNDER BASE PAIRS in ONE launch (csrc/design_nested.hip): the draws of rnampnn_design on a NESTED (pseudoknot-free)
+ * structure, conditioned EXACTLY on the sequence being accepted by the automaton of rnampnn_design_dfa.  A nested structure is a tree, and
+ * on a tree the automaton is carried as a transfer table per enclosed interval (state before its first position -> state after its last):
+ * L^2 per position at L live states, whatever the depth.  The arguments are rnampnn_design_dfa's, in its order, and mean what they mean
+ * there - but `partner` is honoured instead of refused - with
+ *   n_states i32, host                 A, 1 .. 256, of which at most RNAMPNN_DESIGN_NESTED_MAX_LIVE = 64 live (bit 0 of kind clear)
+ *   workspace, workspace_bytes         device memory, 8-byte aligned, at least rnampnn_design_nested_workspace_bytes(B, T, L) =
+ *                                      8 B T L^2 + 256 B (floor(T / 2) + 1) bytes (0 when an argument is <= 0): the tables R_t as
+ *                                      [b][t][L][G] (G = L inside a pair, 1 at the top level: a top-level vector lies at the start of its
+ *                                      slot), then one byte per (b, open pair, lane) for the goals of a walking sample's open pairs.  Its
+ *                                      contents before the call do not matter (every byte that is read was written by the same launch
+ *                                      before), after it they are unspecified
+ * and the outputs, each nullable, are rnampnn_design_dfa's plus
+ *   nest_miss (B) i32      1 when two of the RNA's pairs cross (a pseudoknot), else 0
+ * z, masks, bias, temperature, `allowed`, seed_dev, u24, LSE, SELECT, live and dead states and "an empty mask is drawn free and counts 1 in
+ * `infeasible`" are rnampnn_design_dfa's, word for word; all arithmetic is fp64.  A delta entry >= A is read as a dead state.
+ *   Pairs.  `partner` is validated as in rnampnn_design (symmetric, inside the RNA, not itself).  A pair without a compatible cell that
+ *     both masks admit becomes two unpaired positions and counts 2 in `infeasible`, as in rnampnn_design.  After that nest_miss[b] = 1 iff
+ *     two remaining pairs cross: i < k < j < l.
+ *   Loops.  The loop of a pair (i, j): the positions strictly between i and j that lie inside no deeper pair, plus the openers of its child
+ *     pairs; the top level is the loop of the whole RNA.  Its elements are its unpaired positions and its child pairs, in position order.
+ *   Tables.  For a position t that is unpaired or an opener, R_t(a, g) = the log of the total weight of everything from t to the end of
+ *     t's loop that starts in live state a before t, stays live, and ends in goal g.  In an inner loop g ranges over the live states (the
+ *     state after the loop's last position) and the table behind the last element is the identity (0 on the diagonal, -inf elsewhere).  At
+ *     the top level there is one goal, "accepted", and the table behind position n-1 is 0 for a live accepting state, -inf for every other.
+ *   Recurrence, t = n-1 .. 0, N = the table of the next element of the same loop.
+ *     Unpaired t: R_t(a, g) = LSE over the classes c in class order of z_t(c) + N(delta(a,c), g); admitted iff m_t has c and delta(a,c) is live.
+ *     Opener t of the pair (t, j): P_t(a, b) = LSE over the compatible cells (c, c') in a-major order that both masks admit, and within a
+ *       cell over the live b' ascending with delta(b', c') = b, of z_t(c) + z_j(c') + R^in(delta(a,c), b'); R^in = the table of the first
+ *       element inside (t, j), the identity when j = t + 1.  Then R_t(a, g) = LSE over the live b ascending of P_t(a, b) + N(b, g), N the
+ *       table behind j in t's loop.  A top-level position thus holds exactly rnampnn_design_dfa's vector l_t.
+ *   Feasibility.  dfa_miss[b] = !(R_0(0, accepted) > -inf); an RNA of length 0 is feasible iff state 0 accepts.  On an RNA with
+ *     nest_miss = 1 no table is built and dfa_miss = 0.
+ *   Draw of sample s, feasible nested RNA.  Walk t = 0 .. n-1 with a state a, a goal g and a stack of goals.  Unpaired: SELECT over
+ *     z_t(c) + N(delta(a,c), g), only finite cells admitted, u24(seed, s, b, t); a <- delta(a, c).  Opener: ONE SELECT over (c, c', b') in
+ *     the order of P_t of z_t(c) + z_j(c') + R^in(delta(a,c), b') + N(delta(b',c'), g), only finite cells admitted, u24(seed, s, b, t) (the
+ *     pair's lower index, as in rnampnn_design); t receives c, j receives c'; push g, g <- b', a <- delta(a, c).  Closer j: a <- delta(a,
+ *     its class), pop g.  Every hits is 0, every accepted 1.
+ *   Miss (dfa_miss or nest_miss).  The RNA is drawn as rnampnn_design draws it, in fp64, ignoring the automaton: pairs jointly, unpaired
+ *     positions singly; `hits` and `accepted` report what was written, as in rnampnn_design_dfa.
+ *   Anchor.  On an RNA without a valid pair (a null `partner` included) every output is rnampnn_design_dfa's byte for byte.
+ * One 256-thread workgroup per RNA: the L x G entries of a step are dealt over the threads; an opener forms P_t in an LDS tile next to a
+ * second one that holds R^in and then N; barriers of the workgroup order the workspace accesses.  Then 256 samples at a time walk, one lane
+ * each.  Dynamic LDS:
+ *       bytes(T, L) = 36 T + max(16 L^2, 1024 (ceil(T / 16) | 1)) + 1,952
+ *     (the fp64 rows, the partners, masks and level flags; two L x L tiles, over which later lie 2 bits per position for 256 samples; the
+ *     automaton and the reduction's scratch): 103,488 at (T = 1000, L = 64), 102,464 at (1000, 13).  RNAMPNN_ERR_UNSUPPORTED when that exceeds
+ *     160 KiB = 163,840 bytes: T <= 1616 (163,552 bytes) at every L <= 64; the message names the bytes, the limit and that T.  More than 64 live states:
+ *     RNAMPNN_ERR_UNSUPPORTED, the message names the count and the limit.
+ * No atomics, no runtime fill / copy node, no host synchronisation: two calls give identical bytes, the call can sit inside a captured
+ * graph, and a draw is a pure function of (seed, s, b), the rows of RNA b, its pairs and the automaton - independent of B, T, S, the layout
+ * and the workspace; the first S' of S slots are the call with S'.  RNAMPNN_ERR_BAD_ARG, before anything is launched: the cases of
+ * rnampnn_design_dfa.  Then the live-state check, then the LDS check; then, with every output null, the call returns RNAMPNN_OK without a
+ * launch. */
+#define RNAMPNN_DESIGN_NESTED_MAX_LIVE 64
+size_t rnampnn_design_nested_workspace_bytes(int32_t B, int32_t T, int32_t n_live);
+int rnampnn_design_nested(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
+                          float temperature, int32_t S, uint64_t seed, const uint64_t* seed_dev, const uint8_t* allowed,
+                          const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position,
+                          const uint8_t* delta, const uint8_t* kind, int32_t n_states, void* workspace, size_t workspace_bytes,
+                          int8_t* seqs, float* seq_nll, int32_t* infeasible, int32_t* hits, int32_t* accepted, int32_t* dfa_miss,
+                          int32_t* nest_miss, void* stream);
 /* Design PROFILES in ONE launch each (csrc/design_profile.hip): what rnampnn_design_count and rnampnn_design_avoid draw FROM, not draws - the
  * exact per-position marginals, log partition sums and entropy of the distribution the draw entry of the same mode samples, in fp64.  The
  * inputs mean exactly what they mean in that draw entry: both layouts, z_t(c) = ((double) logit_t(c) + (double) bias_t(c)) / (double)

@@ -68,6 +68,14 @@ the fixed positions, not filtered.  The designs CSV gains the columns ``motif_hi
 required motif) and ``require_miss`` (1 for a structure that cannot hold them: its draws ignore the motifs).  Not built together with the
 other modes, ``--profile-out`` or a ``structure`` in ``--constraints``; the automaton has at most 256 states and 6 required motifs.
 
+    python rna-mpnn_amd/predict.py --ckpt Final.pt --data DIR --samples 8 --pairs nested --constraints cons.csv [--avoid GGGG] [--max-run 3] [--require GNRA]
+
+Motifs under base pairs (``rnampnn_design_nested``, both families): ``--pairs nested`` lifts the refusal of a ``structure`` in
+``--constraints`` for ``--avoid``, ``--max-run`` and ``--require``: the draws pair as the structure says AND hold the motif conditions,
+drawn exactly from the model's distribution conditioned on both.  The structures must be nested: one with a pseudoknot is an error naming
+its ids, before the checkpoint is opened.  The designs CSV gains the columns ``motif_hits``, ``required_found``, ``require_miss`` and
+``nest_miss``.  At most 64 live automaton states; not built together with the other modes or ``--profile-out``.
+
     python rna-mpnn_amd/predict.py --ckpt Final.pt --data DIR --profile-out PREFIX [--gc-content .. | --max-mutations .. | --avoid ..] [--samples 8]
 
 Design profiles (``rnampnn_design_count_profile`` / ``rnampnn_design_avoid_profile``, both families): what the draws of the chosen mode come
@@ -117,6 +125,8 @@ def parse(argv=None):
     ap.add_argument("--max-run", type=int, default=None, help="R: no draw of --samples holds a run of more than R equal letters")
     ap.add_argument("--require", default=None, help="MOTIF[,MOTIF..]: every draw of --samples contains every one of these substrings somewhere "
                                                     "(AUCG, T = U, IUPAC codes); usable with --avoid / --max-run")
+    ap.add_argument("--pairs", default=None, choices=("nested",),
+                    help="nested: --avoid / --max-run / --require hold UNDER the structures of --constraints (which must be free of pseudoknots)")
     ap.add_argument("--profile-out", default=None, help="PREFIX: write the exact distribution the draws come from to PREFIX.positions.csv "
                                                         "(per-position marginals) and PREFIX.rnas.csv (log_mass, entropy)")
     return ap.parse_args(argv)
@@ -211,6 +221,31 @@ def require_option(args) -> dict:
                                                     [m for m in (args.avoid or "").split(",") if m.strip()], max_run=args.max_run))
 
 
+def nested_option(args) -> dict:
+    """The ``pairs`` and ``require`` keywords of ``predict`` from ``--pairs nested`` with ``--avoid`` / ``--max-run`` / ``--require``: one
+    automaton of all of them, built (and refused) before the model is loaded; empty without ``--pairs``.  ``ValueError`` naming the flags
+    with another mode or ``--profile-out``, without a motif flag, without ``--samples``, and - naming the ids - for a ``--constraints``
+    table whose structures hold a pseudoknot."""
+    if args.pairs is None:
+        return {}
+    for flag, value in (("--profile-out", args.profile_out), ("--states", args.states), ("--gc-content", args.gc_content),
+                        ("--distinct", args.distinct), ("--max-mutations", args.max_mutations)):
+        if value is not None:
+            raise ValueError(f"--pairs nested together with {flag} is not built: the automaton conditions plain single-state designs only, and "
+                             "no profile is built for it")
+    if args.avoid is None and args.max_run is None and args.require is None:
+        raise ValueError("--pairs nested needs --avoid, --max-run or --require: the structures of --constraints are honoured without it")
+    if args.samples <= 0:
+        raise ValueError("--pairs nested needs --samples N > 0")
+    from rnampnn.utils.constraints import read_constraints_csv
+    from rnampnn.utils.motifs import as_nested_automaton
+    from rnampnn.utils.predict import check_nested_run
+    split = lambda text: [m for m in (text or "").split(",") if m.strip()]
+    auto = as_nested_automaton(split(args.require) if args.require is not None else None, split(args.avoid), args.max_run)
+    check_nested_run(auto, None, args.samples, None, read_constraints_csv(args.constraints) if args.constraints else None)
+    return dict(pairs="nested", require=auto)
+
+
 def profile_option(args) -> dict:
     """The ``profile_prefix`` keyword of ``predict`` from ``--profile-out``; empty without the flag.  ``ValueError`` naming the flags with
     ``--states`` or ``--distinct``."""
@@ -233,9 +268,10 @@ def checkpoint_family(path: str) -> str:
 
 
 def run(args, log=print):
-    require = require_option(args)                                 # refused with every other mode and --profile-out, before the model is loaded
+    nested = nested_option(args)                                   # --pairs nested takes the motif flags into its own automaton; a pseudoknot fails here
+    require = nested or require_option(args)                       # refused with every other mode and --profile-out, before the model is loaded
     profile = profile_option(args)                                 # refused with --states / --distinct here, before the model is loaded
-    avoid = avoid_option(args)                                     # a combination that is not built fails here, before the model is loaded
+    avoid = {} if nested else avoid_option(args)                   # a combination that is not built fails here, before the model is loaded
     mutations = mutations_option(args)
     distinct = distinct_option(args)
     gc = gc_option(args)                                           # a bad window fails here, before the model is loaded

@@ -33,7 +33,7 @@ import torch.nn.functional as F
 
 from .. import _native
 from rnampnn.model._base import _prep, _stream
-from rnampnn.model.decode import (check_avoid, check_distinct, check_mutations, check_require, check_state_lengths, design_by_mode, design_distinct_from_logits,  # noqa: F401
+from rnampnn.model.decode import (check_avoid, check_distinct, check_mutations, check_nested, check_require, check_state_lengths, design_by_mode, design_distinct_from_logits,  # noqa: F401
                                   design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits, design_profile_from_logits,
                                   letters_packed,
                                   score_logits)
@@ -430,7 +430,8 @@ class RNAModel(nn.Module):
 
     @torch.no_grad()
     def design(self, X, mask, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None, lengths=None, states=None,
-               state_weights=None, gc_content=None, distinct=None, mutations=None, avoid=None, require=None):
+               state_weights=None, gc_content=None, distinct=None, mutations=None, avoid=None, require=None,
+               pairs=None):
         """``n_samples`` sequences per RNA drawn from this model's read-out at ``temperature`` and scored, in one ``rnampnn_design`` launch
         on the packed logits -> (seqs int8 (n_samples,B,T), -1 on padding; seq_nll (n_samples,B) f32, the model's own temperature-1 NLL of
         each draw; infeasible (B,) int32).  ``constraints``: a ``rnampnn.utils.constraints.DesignConstraints`` (fixed nucleotides, base
@@ -452,11 +453,18 @@ class RNAModel(nn.Module):
         avoid_miss (B,) int32); not built together with the other modes, and constraints that carry base pairs are a ``ValueError``
         before the forward pass.  ``require`` (a ``rnampnn.utils.motifs.DesignAutomaton`` or motif strings): every draw contains EVERY one
         of the motifs somewhere and none of ``avoid``, which it absorbs (``design_dfa_from_logits``) -> (seqs, seq_nll, infeasible, hits,
-        accepted (n_samples,B) int32, dfa_miss (B,) int32); not built together with the other modes or with base pairs."""
-        mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require)
+        accepted (n_samples,B) int32, dfa_miss (B,) int32); not built together with the other modes or with base pairs.  ``pairs="nested"`` (``None`` is everything above, unchanged): ``avoid``
+        and / or ``require`` UNDER the base pairs of ``constraints`` (``design_nested_from_logits``): the structure is honoured and the
+        draws are exact as long as it is nested -> (seqs, seq_nll, infeasible, hits, accepted, dfa_miss, nest_miss (B,) int32 = 1 for an
+        RNA whose pairs cross: it is drawn as plain ``constraints`` draw it); host-side constraints whose structure crosses, another
+        mode, another value, or neither ``avoid`` nor ``require`` are a ``ValueError`` before the forward pass."""
+        mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require, pairs=pairs)
         mutations = check_mutations(mutations)
-        require = check_require(require, avoid, constraints)
-        avoid = check_avoid(avoid, constraints) if require is None else None
+        if mode == "nested":
+            require, avoid = check_nested(require, avoid, constraints), None
+        else:
+            require = check_require(require, avoid, constraints)
+            avoid = check_avoid(avoid, constraints) if require is None else None
         if states is not None and lengths is not None:
             check_state_lengths(states, lengths)
         logits, cu, T = self._packed_logits(X, mask, lengths)

@@ -7,7 +7,7 @@ from typing import List, Optional, Tuple
 from rnampnn.model.decode import check_avoid, check_budget, design_by_mode, design_mode, letters_padded, score_logits
 from rnampnn.utils.constraints import batch_constraints, mutation_references, padded_references
 from rnampnn.utils.data import bucket_batches
-from rnampnn.utils.predict import check_profile, check_require_run, design_columns, profile_batch, write_csv, write_profile
+from rnampnn.utils.predict import check_nested_run, check_profile, check_require_run, design_columns, profile_batch, write_csv, write_profile
 
 from .data import load_rna_dir, padded_loader
 
@@ -15,7 +15,7 @@ from .data import load_rna_dir, padded_loader
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
             wobble: bool = True, gc_content=None, distinct=None, mutations=None, avoid=None,
-            profile_prefix: Optional[str] = None, require=None) -> List[Tuple[str, str]]:
+            profile_prefix: Optional[str] = None, require=None, pairs=None) -> List[Tuple[str, str]]:
     """Read ``data_path`` (``coords/<id>.npy`` + ``seqs/<id>.fasta``), design a sequence for every structure in length-bucketed batches
     (``RNAModel.predict_sequences``: the tree read-out when one is attached, else the read-out's argmax) and write ``out_csv`` with one
     ``pdb_id,seq`` row per input in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure at
@@ -34,13 +34,19 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     ``require`` (a ``DesignAutomaton`` or motif strings): the draws come from ``rnampnn_design_dfa`` and contain every one of the motifs
     and none of ``avoid``, which it absorbs; ``designs_csv`` gains the last columns ``motif_hits``, ``required_found`` and
     ``require_miss``.  Not built together with the other modes, a profile or a structure in ``constraints``.
+    ``pairs="nested"``: ``avoid`` and / or ``require`` UNDER the structures of ``constraints`` - the draws come from
+    ``rnampnn_design_nested``; ``designs_csv`` gains the last columns ``motif_hits``, ``required_found``, ``require_miss`` and
+    ``nest_miss``.  A structure with a pseudoknot is a ``ValueError`` naming its ids before the first forward pass.
     ``profile_prefix``: also write the design profile of every structure (``design_profile_from_logits``: the exact distribution the
     draws of the chosen mode come from) to ``PREFIX.positions.csv`` and ``PREFIX.rnas.csv``, with or without ``samples``.  Not built
     together with ``distinct``."""
-    mode = design_mode(None, gc_content, distinct, mutations, avoid, require=require)
+    mode = design_mode(None, gc_content, distinct, mutations, avoid, require=require, pairs=pairs)
     check_profile(profile_prefix, None, distinct)
-    require = check_require_run(require, avoid, samples, profile_prefix, constraints)
-    avoid = check_avoid(avoid) if require is None else None
+    if mode == "nested":
+        require, avoid = check_nested_run(require, avoid, samples, profile_prefix, constraints), None
+    else:
+        require = check_require_run(require, avoid, samples, profile_prefix, constraints)
+        avoid = check_avoid(avoid) if require is None else None
     if avoid is not None:
         if samples <= 0 and not profile_prefix:
             raise ValueError("forbidden motifs need samples > 0")

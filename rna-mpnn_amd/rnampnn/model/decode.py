@@ -1,7 +1,7 @@
 """Decoding from logits, as free functions over the C ABI's decode family: argmax + recovery (``rnampnn_argmax_recovery``), free draws
 (``rnampnn_sample``), scores (``rnampnn_score``), constrained and multi-state design (``rnampnn_design``, ``rnampnn_design_tied``), design
 under a G+C content window (``rnampnn_design_gc``), design within a count window / a mutation budget (``rnampnn_design_count``), distinct
-designs (``rnampnn_design_distinct``), design that avoids forbidden motifs (``rnampnn_design_avoid``), design with required motifs (``rnampnn_design_dfa``), the distribution those draws come from (``rnampnn_design_count_profile``, ``rnampnn_design_avoid_profile``), the choice between them (``design_mode``, ``design_by_mode``) and the letters of class ids.  Needs the library and ``_base`` only, so both model packages import
+designs (``rnampnn_design_distinct``), design that avoids forbidden motifs (``rnampnn_design_avoid``), design with required motifs (``rnampnn_design_dfa``), motifs under a nested structure (``rnampnn_design_nested``), the distribution those draws come from (``rnampnn_design_count_profile``, ``rnampnn_design_avoid_profile``), the choice between them (``design_mode``, ``design_by_mode``) and the letters of class ids.  Needs the library and ``_base`` only, so both model packages import
 it at module level."""
 from __future__ import annotations
 
@@ -379,6 +379,49 @@ def design_dfa_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = 
                         outputs=((torch.int32, True), (torch.int32, True), (torch.int32, False)))
 
 
+def check_nested(require=None, avoid=None, constraints=None, max_run=None):
+    """``design(..., pairs="nested", require=..., avoid=...)`` -> the ``DesignAutomaton`` of ``rnampnn_design_nested``
+    (``as_nested_automaton``: ``require`` with ``avoid`` absorbed, or ``avoid`` / ``max_run`` alone with every live state accepting), or
+    None when none of them is given.  Base pairs are what this mode is for; ``ValueError`` naming the rows when HOST-side constraints hold
+    a structure whose pairs cross (a pseudoknot is not a tree; a device-side ``partner`` is not read back: the kernel's ``nest_miss``
+    reports it), and for what the automaton's constructors refuse.  Touches no device, so a caller refuses before its forward pass."""
+    from ..utils.constraints import crossing_pairs
+    from ..utils.motifs import as_nested_automaton
+    auto = as_nested_automaton(require, avoid, max_run)
+    partner = None if auto is None or constraints is None else constraints.partner
+    if partner is not None and partner.device.type == "cpu":
+        knotted = [b for b, row in enumerate(partner) if crossing_pairs(row)]
+        if knotted:
+            raise ValueError(f"pairs='nested': the structure of row(s) {knotted} holds a pseudoknot (two of its pairs cross); the exact draw "
+                             "under motifs walks a nested structure: drop the crossing pairs from `structure`")
+    return auto
+
+
+def design_nested_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
+                              max_len: Optional[int] = None, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None,
+                              require=None, avoid=None, max_run=None):
+    """``rnampnn_design_nested`` (include/rnampnn_hip.h): the draws of ``design_from_logits`` under the base pairs of a NESTED target
+    structure, conditioned exactly on the sequence containing EVERY motif of ``require`` somewhere and none of ``avoid`` (nor, with
+    ``max_run=r``, a run longer than r), in one launch -> (seqs, seq_nll, infeasible, hits (S,B) int32, accepted (S,B) int32, dfa_miss (B,)
+    int32 = 1 when no admitted sequence of the RNA is accepted, nest_miss (B,) int32 = 1 when two of its pairs cross; either way the RNA
+    is then drawn as ``design_from_logits`` draws it and ``hits`` / ``accepted`` report what it holds).  ``require``: a ``DesignAutomaton``
+    (``avoid`` and ``max_run`` are then not read), motif strings, or None for ``avoid`` / ``max_run`` alone.  Every field of
+    ``constraints`` combines with it, the structure included; without pairs the outputs are ``design_dfa_from_logits``' byte for byte.
+    The tables live in a workspace in global memory (``torch.empty`` here, about 8 B T L^2 bytes at L live states); at most 64 live states
+    and T <= 1616, beyond which the library raises ``NotImplementedError`` naming the limit.  Layouts as in ``design_from_logits``.  CUDA
+    logits only (there is no CPU fallback); no host synchronisation."""
+    auto = check_nested(require, avoid, constraints, max_run)
+    if auto is None:
+        raise ValueError("require or avoid is required: a DesignAutomaton or motif strings (require=['GNRA'], avoid=['GGGG'], max_run=3)")
+
+    def automaton(B, T, m, cu):
+        need = int(_native.lib().rnampnn_design_nested_workspace_bytes(max(B, 0), max(T, 0), auto.n_live))
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=logits.device)
+        return auto.delta_on(logits.device), auto.kind, auto.n_states, ws, C.c_size_t(need)
+    return _design_call("rnampnn_design_nested", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints, tail=automaton,
+                        outputs=((torch.int32, True), (torch.int32, True), (torch.int32, False), (torch.int32, False)))
+
+
 def check_distinct(distinct, states=None, gc_content=None) -> None:
     """``design(..., distinct=...)``: ``ValueError`` for an unknown mode or a combination that is not built; touches no device."""
     if distinct is not None:
@@ -395,12 +438,24 @@ DESIGN_MODES = (("avoid", ("states", "gc_content", "distinct", "mutations"),
                 ("states", (), ""))
 
 
-def design_mode(states=None, gc_content=None, distinct=None, mutations=None, avoid=None, require=None) -> str:
+def design_mode(states=None, gc_content=None, distinct=None, mutations=None, avoid=None, require=None, pairs=None) -> str:
     """Which entry ``design(...)`` draws from: "require", "avoid", "mutations", "distinct", "gc_content", "states", or "plain" when none of
     them is given.  ``require`` decides first and absorbs ``avoid`` (one automaton holds both lists).  ``ValueError`` for a combination
     that is not built (``DESIGN_MODES``; ``require`` with anything but ``avoid``) and an unknown ``distinct``; touches no device, so a
-    caller refuses before its forward pass."""
+    caller refuses before its forward pass.  ``pairs="nested"`` opts in to "nested" (``rnampnn_design_nested``: ``avoid`` and / or
+    ``require`` under the base pairs of a nested structure); it is a ``ValueError`` with another value, with a mode the automaton is not
+    built together with, and with neither ``avoid`` nor ``require``.  With ``pairs=None`` nothing differs."""
     given = {"states": states, "gc_content": gc_content, "distinct": distinct, "mutations": mutations, "avoid": avoid}
+    if pairs is not None:
+        if pairs != "nested":
+            raise ValueError(f"pairs must be None or 'nested', got {pairs!r}")
+        for name in DESIGN_MODES[0][1]:
+            if given[name] is not None:
+                raise ValueError(f"pairs='nested' together with {name} is not built: the automaton conditions the draws of rnampnn_design on "
+                                 "the motifs and the base pairs alone")
+        if avoid is None and require is None:
+            raise ValueError("pairs='nested' needs avoid and / or require: plain constraints already honour base pairs (drop pairs=)")
+        return "nested"
     if require is not None:
         for name in DESIGN_MODES[0][1]:
             if given[name] is not None:
@@ -423,7 +478,10 @@ def design_by_mode(mode: str, logits: torch.Tensor, states=None, state_weights=N
                    avoid=None, require=None, **kw):
     """The ``*_from_logits`` call of ``mode`` (``design_mode``) -> what that function returns.  ``mutations`` as ``check_mutations``
     returns it, ``avoid`` as ``check_avoid`` does, ``require`` as ``check_require`` does (it holds ``avoid``); ``kw``: the layout and the
-    draw (mask / cu_seqlens / max_len, n_samples, temperature, seed, constraints)."""
+    draw (mask / cu_seqlens / max_len, n_samples, temperature, seed, constraints).  "nested": ``require`` as ``check_nested`` returns it
+    (it holds ``avoid``)."""
+    if mode == "nested":
+        return design_nested_from_logits(logits, require=require, **kw)
     if mode == "require":
         return design_dfa_from_logits(logits, require=require, **kw)
     if mode == "avoid":

@@ -23,7 +23,7 @@ from .. import _native
 from ..config.glob import DEFAULT_SEED, REVERSE_VOCAB
 from ..utils.data import check_prefix_mask
 from ._base import NativeModule, _prep, _ptr, _stream
-from .decode import (SCORE_OUTPUTS, argmax_recovery, check_avoid, check_distinct, check_require, check_mutations, check_state_lengths, design_by_mode,  # noqa: F401
+from .decode import (SCORE_OUTPUTS, argmax_recovery, check_avoid, check_distinct, check_nested, check_require, check_mutations, check_state_lengths, design_by_mode,  # noqa: F401
                      design_distinct_from_logits, design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits,
                      design_profile_from_logits,
                      letters_packed, letters_padded, sample_from_logits, score_logits)
@@ -548,7 +548,7 @@ class RNAMPNN(NativeModule):
     @torch.no_grad()
     def design(self, coords: torch.Tensor, mask: torch.Tensor, n_samples: int = 8, temperature: float = 0.1, seed: int = 0,
                T_norm: int = 0, constraints=None, states=None, state_weights=None, lengths=None, gc_content=None, distinct=None, mutations=None,
-               avoid=None, require=None):
+               avoid=None, require=None, pairs=None):
         """``sample`` plus the score of every draw against the SAME logits, with one forward: -> (seqs int8 (n_samples,B,T), -1 on
         padding; seq_nll (n_samples,B) f32).  The NLL is the model's own (temperature 1) likelihood, so designs drawn at different
         temperatures rank on one scale.  ``constraints`` (``rnampnn.utils.constraints.DesignConstraints``: fixed nucleotides, base
@@ -576,11 +576,18 @@ class RNAMPNN(NativeModule):
         one of the motifs somewhere, and none of ``avoid`` (motif strings or a ``MotifAutomaton``), which it absorbs - drawn exactly from
         the model's distribution conditioned on that (``design_dfa_from_logits``) -> (seqs, seq_nll, infeasible, hits (n_samples,B) int32,
         accepted (n_samples,B) int32, dfa_miss (B,) int32 = 1 for an RNA that cannot hold the motifs); not built together with the other
-        modes, and constraints that carry base pairs are a ``ValueError`` before the forward pass."""
-        mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require)
+        modes, and constraints that carry base pairs are a ``ValueError`` before the forward pass.  ``pairs="nested"`` (``None`` is everything above, unchanged): ``avoid``
+        and / or ``require`` UNDER the base pairs of ``constraints`` (``design_nested_from_logits``): the structure is honoured and the
+        draws are exact as long as it is nested -> (seqs, seq_nll, infeasible, hits, accepted, dfa_miss, nest_miss (B,) int32 = 1 for an
+        RNA whose pairs cross: it is drawn as plain ``constraints`` draw it); host-side constraints whose structure crosses, another
+        mode, another value, or neither ``avoid`` nor ``require`` are a ``ValueError`` before the forward pass."""
+        mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require, pairs=pairs)
         mutations = check_mutations(mutations)
-        require = check_require(require, avoid, constraints)
-        avoid = check_avoid(avoid, constraints) if require is None else None
+        if mode == "nested":
+            require, avoid = check_nested(require, avoid, constraints), None
+        else:
+            require = check_require(require, avoid, constraints)
+            avoid = check_avoid(avoid, constraints) if require is None else None
         if states is not None and lengths is not None:
             check_state_lengths(states, lengths)
         logits = self._run(coords, mask, T_norm=T_norm)["logits"]

@@ -51,6 +51,22 @@ def parse_dot_bracket(text: str) -> np.ndarray:
     return partner
 
 
+def crossing_pairs(partner_row) -> bool:
+    """Does the structure of ONE RNA hold a pseudoknot?  ``partner_row``: its partner array (``parse_dot_bracket``; a tensor or a
+    sequence, -1 = unpaired).  True when two of its pairs cross, i < k < j < l.  An entry that is not symmetric or points outside the row is
+    no pair, as in ``rnampnn_design``.  Host side: one pass with a stack."""
+    row = [int(v) for v in (partner_row.tolist() if hasattr(partner_row, "tolist") else partner_row)]
+    n, open_ = len(row), []
+    for t, j in enumerate(row):
+        if not (0 <= j < n and j != t and row[j] == t):
+            continue
+        if j > t:
+            open_.append(t)
+        elif open_.pop() != j:                                     # a closer must close the innermost open pair
+            return True
+    return False
+
+
 def parse_pattern(text: str) -> np.ndarray:
     """Sequence pattern -> uint8 ``allowed`` array: AUCG (and T = U) fix a nucleotide, the IUPAC codes R Y S W K M B D H V N admit their
     sets, ``.`` and ``-`` leave the position free; case is ignored.  ``ValueError`` on any other character."""

@@ -238,6 +238,15 @@ class DesignAutomaton:
         kind = [KIND_DEAD if dead_here[node] else (KIND_ACCEPTING if seen == full else 0) for node, seen in states]
         return cls(torch.tensor(delta, dtype=torch.uint8), torch.tensor(kind, dtype=torch.uint8), sorted(banned), required)
 
+    @classmethod
+    def from_avoid(cls, avoid=(), max_run: Optional[int] = None) -> "DesignAutomaton":
+        """Forbidden motifs ALONE in the form ``rnampnn_design_nested`` takes them: ``MotifAutomaton``'s table (``avoid``: one, or motif
+        strings with ``max_run``, as its ``from_motifs`` takes them) with ``kind`` = dead where a motif ends and accepting everywhere
+        else.  ``from_motifs`` keeps refusing an empty ``require``; this is the separate door for avoid alone."""
+        auto = as_automaton(avoid if avoid is not None else (), max_run)
+        kind = [KIND_DEAD if (auto.terminal >> a) & 1 else KIND_ACCEPTING for a in range(auto.n_states)]
+        return cls(auto.delta, torch.tensor(kind, dtype=torch.uint8), auto.words, ())
+
     def letters(self) -> List[str]:
         """The expanded avoided words as strings over AUCG."""
         return ["".join(REVERSE_VOCAB[c] for c in w) for w in self.words]
@@ -276,6 +285,17 @@ def as_design_automaton(require, avoid=None, max_run: Optional[int] = None) -> O
     if isinstance(avoid, MotifAutomaton):
         avoid = avoid.letters()
     return DesignAutomaton.from_motifs(require, avoid if avoid is not None else (), max_run=max_run)
+
+
+def as_nested_automaton(require=None, avoid=None, max_run: Optional[int] = None) -> Optional[DesignAutomaton]:
+    """``design(..., pairs="nested", require=..., avoid=...)`` -> the ``DesignAutomaton`` of ``rnampnn_design_nested``: ``require`` with
+    ``avoid`` absorbed (``as_design_automaton``), or ``avoid`` / ``max_run`` alone with every live state accepting
+    (``DesignAutomaton.from_avoid``); None when none of the three is given."""
+    if require is not None:
+        return as_design_automaton(require, avoid, max_run)
+    if avoid is None and max_run is None:
+        return None
+    return DesignAutomaton.from_avoid(avoid, max_run)
 
 
 def as_automaton(avoid, max_run: Optional[int] = None) -> Optional[MotifAutomaton]:

@@ -11,9 +11,9 @@ import numpy as np
 import torch
 
 from ..config.glob import VOCAB
-from ..model.decode import (check_avoid, check_budget, check_require, design_by_mode, design_mode, design_profile_from_logits, letters_packed, letters_padded,
+from ..model.decode import (check_avoid, check_budget, check_nested, check_require, design_by_mode, design_mode, design_profile_from_logits, letters_packed, letters_padded,
                             sample_from_logits, score_logits)
-from .constraints import batch_constraints, mutation_references, padded_references
+from .constraints import batch_constraints, crossing_pairs, mutation_references, padded_references, parse_dot_bracket
 from .data import PackedLoader, bucket_batches, fill_nan_deterministic, read_fasta
 
 
@@ -118,6 +118,9 @@ def design_columns(mode: str, extras=(), lens=()):
     """The last columns that ``designs_csv`` gains in a design mode (``design_mode``) -> (their header, cells, filled): ``cells(s, r)``
     the fields of sample s of row r, ``filled`` [B] the slots of a row that hold a sequence, or None for all of them.  ``extras``: the
     two outputs of the mode's entry past (seqs, seq_nll, infeasible), ``lens`` the rows' lengths; without them only the header counts."""
+    if mode == "nested":                                            # four outputs: hits and accepted per sample, dfa_miss and nest_miss per row
+        hits, found, miss, nest = (t.cpu().tolist() for t in extras) if extras else (None, None, None, None)
+        return ",motif_hits,required_found,require_miss,nest_miss", lambda s, r: (hits[s][r], found[s][r], miss[r], nest[r]), None
     if mode == "require":                                           # three outputs: hits and accepted per sample, dfa_miss per row
         hits, found, miss = (t.cpu().tolist() for t in extras) if extras else (None, None, None)
         return ",motif_hits,required_found,require_miss", lambda s, r: (hits[s][r], found[s][r], miss[r]), None
@@ -159,6 +162,28 @@ def check_require_run(require, avoid, samples: int, profile_prefix, constraints)
     return auto
 
 
+def check_nested_run(require, avoid, samples: int, profile_prefix, constraints) -> object:
+    """``predict(..., pairs="nested")`` -> the ``DesignAutomaton`` of ``require`` and / or ``avoid`` (``check_nested``).  ``ValueError``
+    without samples, with a profile (none is built for this mode) and, naming the ids, for a constraints table whose structures hold a
+    pseudoknot; touches no device."""
+    auto = check_nested(require, avoid)
+    if profile_prefix:
+        raise ValueError("a design profile together with pairs='nested' is not built: the profile entries know no automaton under base pairs")
+    if samples <= 0:
+        raise ValueError("motifs under a nested structure need samples > 0")
+    knotted = []
+    for rid, (_, structure) in sorted((constraints or {}).items()):
+        try:
+            if structure and crossing_pairs(parse_dot_bracket(structure)):
+                knotted.append(rid)
+        except ValueError as exc:
+            raise ValueError(f"constraints for {rid}: {exc}") from None
+    if knotted:
+        raise ValueError(f"pairs='nested': the structure of {knotted[:3]}{' ...' if len(knotted) > 3 else ''} holds a pseudoknot (two of its "
+                         "pairs cross); the exact draw under motifs walks a nested structure: drop the crossing pairs")
+    return auto
+
+
 def profile_batch(store: dict, idx, lens, logits, cu, max_len: int, temperature: float, cons, gc_content, mutations, avoid) -> None:
     """The design profile of one packed batch (``design_profile_from_logits``; ``mutations`` as ``design`` takes it) into ``store``:
     item index -> (marginals [n][4], log_mass, entropy, infeasible, miss).  One launch, one copy per output."""
@@ -183,7 +208,7 @@ def write_profile(prefix: str, ids, store: dict) -> None:
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
             wobble: bool = True, states: Optional[dict] = None, gc_content=None, distinct=None, mutations=None,
-            avoid=None, profile_prefix: Optional[str] = None, require=None) -> List[Tuple[str, str]]:
+            avoid=None, profile_prefix: Optional[str] = None, require=None, pairs=None) -> List[Tuple[str, str]]:
     """Design a sequence for every structure under ``data_path`` in length-bucketed var-len batches (``forward_packed``): the tree
     read-out on the packed embedding when one is attached, else the read-out's argmax (``rnampnn_score``'s ``pred``); write ``out_csv``
     with one ``pdb_id,seq`` row per structure in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure
@@ -217,13 +242,20 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     of them somewhere and none of ``avoid``, which it absorbs.  ``designs_csv`` gains the last columns ``motif_hits``, ``required_found``
     (1 when the draw holds every required motif) and ``require_miss`` (1 for a structure that cannot hold them: too short, or its fixed
     positions rule one out).  Not built together with the other modes, a profile or a structure in ``constraints``.
+    ``pairs="nested"``: ``avoid`` and / or ``require`` UNDER the structures of ``constraints`` - the draws come from
+    ``rnampnn_design_nested``; ``designs_csv`` gains the last columns ``motif_hits``, ``required_found``, ``require_miss`` and
+    ``nest_miss``.  A structure with a pseudoknot is a ``ValueError`` naming its ids before the first forward pass; not built together with
+    the other modes or a profile.
     ``profile_prefix``: also write the design profile of every structure - the exact distribution the draws of the chosen mode come from
     under ``temperature`` and the constraints (``design_profile_from_logits``) - to ``PREFIX.positions.csv`` and ``PREFIX.rnas.csv``
     (``write_profile``), with or without ``samples``.  Not built together with ``states`` or ``distinct``."""
-    mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require)
+    mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require, pairs=pairs)
     check_profile(profile_prefix, states, distinct)
-    require = check_require_run(require, avoid, samples, profile_prefix, constraints)
-    avoid = check_avoid(avoid) if require is None else None
+    if mode == "nested":
+        require, avoid = check_nested_run(require, avoid, samples, profile_prefix, constraints), None
+    else:
+        require = check_require_run(require, avoid, samples, profile_prefix, constraints)
+        avoid = check_avoid(avoid) if require is None else None
     if avoid is not None:
         if samples <= 0 and not profile_prefix:
             raise ValueError("forbidden motifs need samples > 0")

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The measurement behind DESIGN.md section 9 "Constrained design", "Multi-state design", "Design under a G+C window", "Distinct designs",
-"Mutation budget", "Forbidden motifs", "Required motifs" and "Design profiles" (profiles/design_dfa_kernel_stats.txt, profiles/design_profile_kernel_stats.txt, profiles/design_kernel_stats.txt, profiles/design_tied_kernel_stats.txt, profiles/design_gc_kernel_stats.txt,
+"Mutation budget", "Forbidden motifs", "Required motifs", "Motifs under a nested structure" and "Design profiles" (profiles/design_nested_kernel_stats.txt, profiles/design_dfa_kernel_stats.txt, profiles/design_profile_kernel_stats.txt, profiles/design_kernel_stats.txt, profiles/design_tied_kernel_stats.txt, profiles/design_gc_kernel_stats.txt,
 profiles/design_distinct_kernel_stats.txt, profiles/design_count_kernel_stats.txt, profiles/design_avoid_kernel_stats.txt): the C2 batch (256 RNAs x 100..140 nt), S = 8 sequences per RNA.
 usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + rnampnn_score (seq_nll): the unconstrained pair of launches
        python tools/design_probe.py design [calls=50]         rnampnn_design: free, then with a hairpin's pairs + a fixed GNRA loop per RNA
@@ -30,6 +30,11 @@ usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + r
                                                               the same automaton with every live state accepting (the same work, the table
                                                               in global memory), require GGAGG + max_run = 3, and require GGAGG and CUUCG +
                                                               max_run = 3 (89 states); then the yield of filtering free draws for GGAGG
+       python tools/design_probe.py nested                    rnampnn_design (free, hairpin) and then, in 5 alternating rounds of 10 calls each,
+                                                              rnampnn_design_dfa max_run = 3 with every live state accepting, S = 8 (the
+                                                              yardstick) and rnampnn_design_nested: the same automaton without pairs (the
+                                                              same work), the same automaton under a hairpin-rich nested structure on every
+                                                              RNA (13 live states), and require GNRA + max_run = 3 under that structure (53)
 HIP events around each loop of back-to-back calls of the Python wrappers.  Run either under `rocprofv3 --kernel-trace --stats -- python ...`
 (a run of its own) for the kernels' own times.  RNAMPNN_PROBE_ROOT: another checkout (with its library built) to take the package from -
 the `sample_score` leg uses nothing newer than rnampnn_score, so it runs on the parent commit as well."""
@@ -236,6 +241,62 @@ else:
             print(f"{tag}: accepted {int(out[4].sum())} of {8 * B} draws, hits {int(out[3].sum())}, dfa_miss total {int(out[5].sum())}, "
                   f"mean NLL per nt {float(out[1].sum()) / (8 * int(mask.sum())):.4f}")
         print(f"filtering yield: {int(word.scan(free)[1].sum())} of the {8 * B} free draws of rnampnn_design at temperature 0.1 contain GGAGG")
+    if what == "nested":
+        # Four variants in alternating rounds of one process, so that k_design_nested is compared with k_design_dfa of the SAME run.  The
+        # structure: three outer pairs around a multiloop of hairpins (a stem of 4 closed by a tetraloop, 2 unpaired between them).
+        from rnampnn.model import decode as D
+        from rnampnn.utils.motifs import DesignAutomaton
+        rounds, per_round, warm = 5, 10, 3
+        kw = dict(temperature=0.1, seed=1, n_samples=8)
+        run3 = DesignAutomaton.from_avoid([], max_run=3)
+        gnra = DesignAutomaton.from_motifs(["GNRA"], max_run=3)
+        rich = []
+        for n in lens:
+            k = (n - 8) // 14
+            body = ("((((....))))" + "..") * k
+            rich.append((None, "(((" + "." + body + "." * (n - 8 - 14 * k) + "." + ")))"))
+        nest = DesignConstraints.from_specs(rich, lens, T).to_device("cuda")
+        n_pairs = int((nest.partner >= 0).sum()) // 2
+        variants = [
+            (f"rnampnn_design_dfa max_run 3, every live state accepting ({run3.n_live} live states), no pairs, S 8",
+             lambda: D.design_dfa_from_logits(logits, mask=m, require=run3, **kw)),
+            (f"rnampnn_design_nested max_run 3 ({run3.n_live} live states), no pairs, S 8",
+             lambda: D.design_nested_from_logits(logits, mask=m, require=run3, **kw)),
+            (f"rnampnn_design_nested max_run 3 ({run3.n_live} live states), {n_pairs} nested pairs in the batch, S 8",
+             lambda: D.design_nested_from_logits(logits, mask=m, require=run3, constraints=nest, **kw)),
+            (f"rnampnn_design_nested require GNRA, max_run 3 ({gnra.n_states} states, {gnra.n_live} live), {n_pairs} nested pairs in the batch, S 8",
+             lambda: D.design_nested_from_logits(logits, mask=m, require=gnra, constraints=nest, **kw))]
+        for _, fn in variants:
+            for _ in range(warm):
+                fn()
+        torch.cuda.synchronize()
+        times = [[] for _ in variants]
+        for _ in range(rounds):
+            for v, (_, fn) in enumerate(variants):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(per_round):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                times[v].append(e0.elapsed_time(e1) * 1e3 / per_round)
+        for (name, _), t in zip(variants, times):
+            print(f"B {B} T {T} nt {int(mask.sum())} {name}: {sum(t) / len(t):.2f} us per call, rounds {min(t):.2f} .. {max(t):.2f} "
+                  f"({rounds} alternating rounds of {per_round} back-to-back calls, events, output and workspace allocation included)")
+        a, d = variants[0][1](), variants[1][1]()
+        print("no pairs against rnampnn_design_dfa: " + ", ".join(
+            f"{k} equal {bool((x == y).all())}" for k, x, y in zip(("seqs", "seq_nll", "infeasible", "hits", "accepted", "dfa_miss"), a, d)))
+        pa = nest.partner.cpu()
+        for tag, auto, out in (("max_run 3 under the structure", run3, variants[2][1]()), ("require GNRA, max_run 3 under the structure", gnra, variants[3][1]())):
+            q = out[0].cpu()
+            lo = (pa >= 0) & (pa > torch.arange(T)[None])
+            left, right = q[:, lo], torch.gather(q, 2, pa.clamp(min=0).to(torch.int64)[None].expand(q.shape[0], -1, -1))[:, lo]
+            ok = ((left == 0) & (right == 1)) | ((left == 1) & ((right == 0) | (right == 3))) | ((left == 2) & (right == 3)) | ((left == 3) & ((right == 2) | (right == 1)))
+            print(f"{tag}: accepted {int(out[4].sum())} of {8 * B} draws, hits {int(out[3].sum())} (recounted {int(auto.scan(out[0])[0].sum())}), "
+                  f"dfa_miss total {int(out[5].sum())}, nest_miss total {int(out[6].sum())}, compatible pairs {int(ok.sum())} of {ok.numel()}, "
+                  f"mean NLL per nt {float(out[1].sum()) / (8 * int(mask.sum())):.4f}")
+        ws = [int(D._native.lib().rnampnn_design_nested_workspace_bytes(B, T, a.n_live)) for a in (run3, gnra)]
+        print(f"workspace at (B {B}, T {T}): {ws[0]} bytes at {run3.n_live} live states, {ws[1]} bytes at {gnra.n_live}")
     if what == "profile":
         # Seven variants in alternating rounds of one process: the two draw kernels the profiles share their tables with, then the profiles.
         from rnampnn.model import decode as D

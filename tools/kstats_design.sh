@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/design_probe.py under rocprofv3 --kernel-trace --stats, each leg in a run of its own.  usage: tools/kstats_design.sh <outdir> [leg ...]
-# (outdir: a git-ignored place such as build/design_stats; legs: sample_score design tied gc distinct count avoid profile dfa, the first four by default)
+# (outdir: a git-ignored place such as build/design_stats; legs: sample_score design tied gc distinct count avoid profile dfa nested, the first four by default)
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "${1:?usage: tools/kstats_design.sh <outdir> [leg ...]}" && OUT=$(cd "$1" && pwd) || exit 1
 shift
@@ -24,7 +24,7 @@ def launches(match):
     return sorted(((int(r['Start_Timestamp']), int(r['End_Timestamp']) - int(r['Start_Timestamp'])) for r in csv.DictReader(open(t)) if match(r['Kernel_Name'])))
 # the "gc" leg adds, after those of k_design, 55 + 55 + 1 launches of k_design_gc: the window 40..60 % free / with the hairpins
 # the "distinct" leg adds 8 x 55 launches of k_design_distinct (+ 1 after every fourth): S = 8 then 64, sample then best, free then hairpins
-d = launches(lambda n: 'k_design' in n and 'k_design_tied' not in n and 'k_design_gc' not in n and 'k_design_distinct' not in n and 'k_design_count' not in n and 'k_design_avoid' not in n and 'k_design_dfa' not in n)
+d = launches(lambda n: 'k_design' in n and 'k_design_tied' not in n and 'k_design_gc' not in n and 'k_design_distinct' not in n and 'k_design_count' not in n and 'k_design_avoid' not in n and 'k_design_dfa' not in n and 'k_design_nested' not in n)
 g = launches(lambda n: 'k_design_distinct' in n)
 e = launches(lambda n: 'k_design_tied' in n)
 f = launches(lambda n: 'k_design_gc' in n)
@@ -42,6 +42,9 @@ ap = launches(lambda n: 'k_design_avoid_profile' in n)
 # the "dfa" leg: the same rounds - k_design_avoid max_run 3 (1 variant: the yardstick of the same run) and k_design_dfa on the same automaton
 # with every live state accepting / require GGAGG + max_run 3 / require GGAGG and CUUCG + max_run 3 (3 variants of its launches)
 dfa = launches(lambda n: 'k_design_dfa' in n)
+# the "nested" leg: the same rounds - k_design_dfa max_run 3 with every live state accepting (1 variant: the yardstick of the same run) and
+# k_design_nested on the same automaton without pairs / under the hairpin-rich structure / require GNRA + max_run 3 under it (3 variants)
+ns = launches(lambda n: 'k_design_nested' in n)
 def by_round(seq, variants, v):
     body = seq[3 * variants:]
     return [[x[1] / 1e3 for x in body[10 * (variants * r + v):10 * (variants * r + v) + 10]] for r in range(5)]
@@ -51,7 +54,14 @@ def report(table):
         flat = sorted(x for r in rs for x in r)
         print(f"{kernel}, {label}: 5 rounds x 10 launches, mean {sum(flat) / len(flat):.2f} us ({flat[0]:.2f} .. {flat[-1]:.2f}, median {flat[len(flat) // 2]:.2f}); "
               f"round means {' '.join(f'{v:.2f}' for v in means)} (spread {max(means) - min(means):.2f})")
-if dfa:
+if ns:
+    report((("k_design_dfa", "max_run 3, every live state accepting (13 live states), no pairs, S = 8", by_round(dfa, 1, 0)),
+            ("k_design_nested", "max_run 3 (13 live states), no pairs, S = 8", by_round(ns, 3, 0)),
+            ("k_design_nested", "max_run 3 (13 live states), hairpin-rich nested structure, S = 8", by_round(ns, 3, 1)),
+            ("k_design_nested", "require GNRA, max_run 3 (61 states, 53 live), the same structure, S = 8", by_round(ns, 3, 2))))
+    m = [sum(x for r in by_round(s, k, v) for x in r) / 50 for s, k, v in ((dfa, 1, 0), (ns, 3, 0))]
+    print(f"k_design_nested / k_design_dfa on the same automaton without pairs: {m[1] / m[0]:.3f}")
+elif dfa:
     report((("k_design_avoid", "max_run 3 (13 live states), S = 8, no constraints", by_round(av, 1, 0)),
             ("k_design_dfa", "max_run 3, every live state accepting (13 live states), S = 8", by_round(dfa, 3, 0)),
             ("k_design_dfa", "require GGAGG, max_run 3 (38 states, 30 live), S = 8", by_round(dfa, 3, 1)),
