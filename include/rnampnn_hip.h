@@ -315,7 +315,7 @@ int rnampnn_design_tied(const float* logits, int64_t n_rows, const float* mask, 
  * seq_nll is byte for byte rnampnn_score's for the written draw and `infeasible` keeps its meaning, as in rnampnn_design.  One workgroup per
  * (RNA, sample); the levels 1 .. ceil(log2 T) live in dynamic LDS, node (l, i) at min(2 * (its extent within T), T) + 1 doubles (14,328 bytes at
  * T = 128, 73,720 at 512, 159,816 at 1000), + T rounded up to 16 bytes of class ids + 96 bytes: RNAMPNN_ERR_UNSUPPORTED when that exceeds
- * 160 KiB = 163,840 bytes (T <= 1017, which needs 163,800); the message names the byte count and that T.  A tree in global memory for longer RNAs is not built.  No workspace, no
+ * 160 KiB = 163,840 bytes (T <= 1017, which needs 163,800); the message names the byte count and that T.  Longer RNAs: rnampnn_design_count_long with counted = 12 everywhere and count_cap >= T, the tree in global memory.  No workspace, no
  * atomics, no runtime fill / copy node, no host synchronisation: two calls give identical bytes, the call can sit inside a captured graph,
  * and a draw is a pure function of (seed, s, b) and the rows of RNA b - independent of B, T, S and the layout.
  * RNAMPNN_ERR_BAD_ARG, before anything is launched: the cases of rnampnn_design; null gc_lo or gc_hi.  With every output null the call
@@ -366,7 +366,7 @@ int rnampnn_design_gc(const float* logits, int64_t n_rows, const float* mask, co
  * doubles(T, cap) = the sum over the nodes of the levels 1 .. ceil(log2 T) of min(2 * (extent within T), T, cap) + 1: 7,320 bytes at
  * (T = 128, cap 8), 14,552 at (128, 128), 57,176 at (1000, 8).  RNAMPNN_ERR_UNSUPPORTED when that exceeds 160 KiB = 163,840 bytes; the message
  * names the bytes, the limit and the largest T at that cap: T <= 2867 at cap 8 (163,808 bytes), 2236 at cap 16, 1833 at cap 32, 1551 at cap 64,
- * 1017 for cap >= T.  A tree in global memory for longer RNAs is not built.  No workspace, no atomics, no runtime fill / copy node, no host
+ * 1017 for cap >= T.  Longer RNAs: rnampnn_design_count_long, the tree in global memory.  No workspace, no atomics, no runtime fill / copy node, no host
  * synchronisation: two calls give identical bytes, the call can sit inside a captured graph, and a draw is a pure function of (seed, s, b)
  * and the rows of RNA b - independent of B, T, S and the layout.
  * RNAMPNN_ERR_BAD_ARG, before anything is launched: the cases of rnampnn_design; null counted, count_lo or count_hi; count_cap < 0.  With
@@ -376,6 +376,40 @@ int rnampnn_design_count(const float* logits, int64_t n_rows, const float* mask,
                          const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position,
                          const uint8_t* counted, const int32_t* count_lo, const int32_t* count_hi, int32_t count_cap,
                          int8_t* seqs, float* seq_nll, int32_t* infeasible, int32_t* count, int32_t* count_miss, void* stream);
+/* rnampnn_design_count on a count tree in GLOBAL memory (csrc/design_long.hip), for RNAs whose tree does not fit the LDS of a workgroup.
+ * The arguments are those of rnampnn_design_count plus, before the outputs,
+ *   workspace, device, non-null, 8-byte aligned   at least rnampnn_design_count_long_workspace_bytes(B, T, count_cap) bytes; its contents
+ *   workspace_bytes, host                         before the call do not matter, after it they are unspecified
+ * and the outputs are rnampnn_design_count's.  The contract is rnampnn_design_count's, word for word - leaves, tree, window, target, k_min
+ * rule, draw, uniforms, robustness, seq_nll and `infeasible` - and whenever rnampnn_design_count accepts the call every output of this entry
+ * equals its output, byte for byte: each coefficient is one LSE over the same terms in the same order whoever computes it, the total and the
+ * splits of a level with at most four nodes are selected by a wave-wide scan, every other split by one thread, as there.  G+C has no entry of
+ * its own: counted = 12 everywhere and count_cap >= T gives the bytes of rnampnn_design_gc.
+ *   Workspace.  The tree of RNA b - the levels 1 .. ceil(log2 T), [level][node][coefficient], node (l, i) at min(2 * (its extent within T), T,
+ *     cap) + 1 doubles - lies at workspace + 8 b doubles(T, cap) bytes, doubles as in rnampnn_design_count: 172,288 bytes per RNA at T = 1025
+ *     uncapped, 888,608 at T = 4417 uncapped, 247,728 at (4417, cap 8).  It is built ONCE per RNA and read by all S samples; a sample's
+ *     per-node counts live in the LDS of its workgroup, never in the tree.  rnampnn_design_count_long_workspace_bytes returns
+ *     8 B doubles(T, min(count_cap, T)), and 0 when an argument is <= 0; a call with count_cap = 0 (nothing may count) needs the bytes of
+ *     count_cap = 1.
+ *   Launches, all on `stream`, stream order between them: level 1 from the rows, one node per thread; one launch per level l = 2 .. ceil(log2 T)
+ *     dealt flat over (RNA, node, coefficient), so the top levels of one long RNA spread over the device (13 launches at T = 4417); then one
+ *     256-thread workgroup per (RNA, sample) that recomputes `infeasible` and k_min from the leaves, reads the root, walks down reading the
+ *     halves from the workspace and writes the rows.  Dynamic LDS of that workgroup: 2 * (4 * ceil(T / 2) rounded up to 16) + T rounded up to
+ *     16 + 96 bytes - the counts of the level being split and of the level below it, the class ids, the scratch: 41,056 bytes at T = 8192.  It
+ *     does not depend on the cap.  RNAMPNN_ERR_UNSUPPORTED when that exceeds 160 KiB = 163,840 bytes: T <= 32744 (163,824 bytes) at every cap;
+ *     the message names the bytes, the limit and that T.
+ * No atomics, no runtime fill / copy node, no host synchronisation: two calls give identical bytes, the call can sit inside a captured graph,
+ * and a draw is a pure function of (seed, s, b) and the rows of RNA b - independent of B, T, S, the layout and the workspace; the first S' of
+ * S slots are the call with S'.
+ * RNAMPNN_ERR_BAD_ARG, before anything is launched: the cases of rnampnn_design_count; a null, too small or not 8-byte aligned workspace.
+ * With every output null the call returns RNAMPNN_OK without a launch. */
+size_t rnampnn_design_count_long_workspace_bytes(int32_t B, int32_t T, int32_t count_cap);
+int rnampnn_design_count_long(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
+                              float temperature, int32_t S, uint64_t seed, const uint64_t* seed_dev, const uint8_t* allowed,
+                              const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position,
+                              const uint8_t* counted, const int32_t* count_lo, const int32_t* count_hi, int32_t count_cap,
+                              void* workspace, size_t workspace_bytes, int8_t* seqs, float* seq_nll, int32_t* infeasible, int32_t* count,
+                              int32_t* count_miss, void* stream);
 /* Distinct designs in ONE launch (csrc/design_distinct.hip): S pairwise DIFFERENT sequences per RNA under the constraints of rnampnn_design -
  * with noise != 0 an exact sample WITHOUT replacement from the constrained, tempered distribution, in sampling order; with noise == 0 the S
  * most probable admitted sequences, in descending order - each with its log-probability under that distribution.  One algorithm, a beam of
@@ -638,6 +672,22 @@ int rnampnn_design_avoid_profile(const float* logits, int64_t n_rows, const floa
                                  int32_t bias_per_position, const uint8_t* delta, int32_t n_states, uint64_t terminal,
                                  double* marginals, double* log_z, double* log_z_free, double* entropy, int32_t* infeasible,
                                  int32_t* avoid_miss, void* stream);
+/* rnampnn_design_count_profile on trees in GLOBAL memory (csrc/design_long.hip).  The arguments and the outputs are those of
+ * rnampnn_design_count_profile plus, before the outputs, `workspace` and `workspace_bytes` as in rnampnn_design_count_long, sized by
+ * rnampnn_design_count_profile_long_workspace_bytes = twice rnampnn_design_count_long_workspace_bytes: the inside trees of the B RNAs, then
+ * their outside trees, each in rnampnn_design_count_long's layout.  The contract is rnampnn_design_count_profile's, and whenever that entry
+ * accepts the call every output of this one equals its output, byte for byte.  Launches on `stream`: the inside pass of
+ * rnampnn_design_count_long; one workgroup per RNA for the target and the root's outside; the outside pass, one launch per level top down, dealt
+ * flat over (RNA, child node, coefficient); one workgroup per RNA for the leaves, the marginals and the scalars (27 launches at T = 4417).
+ * No dynamic LDS, so T is bound by the 16 levels the argument block addresses alone: T <= 65536, RNAMPNN_ERR_UNSUPPORTED naming it beyond.
+ * No atomics, no runtime fill / copy node, no host synchronisation.  RNAMPNN_ERR_BAD_ARG, before anything is launched: the cases of
+ * rnampnn_design_count_profile; a null, too small or not 8-byte aligned workspace.  With every output null RNAMPNN_OK without a launch. */
+size_t rnampnn_design_count_profile_long_workspace_bytes(int32_t B, int32_t T, int32_t count_cap);
+int rnampnn_design_count_profile_long(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
+                                      float temperature, const uint8_t* allowed, const int32_t* partner, int32_t wobble, const float* bias,
+                                      int32_t bias_per_position, const uint8_t* counted, const int32_t* count_lo, const int32_t* count_hi,
+                                      int32_t count_cap, void* workspace, size_t workspace_bytes, double* marginals, double* log_z,
+                                      double* log_z_free, double* entropy, int32_t* infeasible, int32_t* count_miss, void* stream);
 
 /* -- training ---------------------------------------------------------------------------- */
 /* The training surface of RNAMPNN (rnampnn.py:187-207 + Lightning's loss.backward()):

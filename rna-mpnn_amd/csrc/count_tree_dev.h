@@ -23,6 +23,10 @@
 // writes both ends); when no count of 0 .. min(n, cap) is reachable (SETS only) the walk is skipped and every leaf draws at its own
 // minimum; (C) the rows, the NLL and the counts as k_design writes and reduces them (ds_write_rows, the count as its third sum).
 // No workspace, no atomics, no runtime fill / copy node, no host synchronisation; the draw is a pure function of (seed, s, b) and the rows of the RNA.
+// The tree has a second home, a caller workspace in global memory (design_long.hip: rnampnn_design_count_long, for RNAs whose tree does not
+// fit LDS).  Its kernels build the tree one level per launch and walk it per (RNA, sample) with the per-node counts in LDS; what a leaf, a
+// level-1 node (ct_node1), a coefficient (ct_conv, ct_lse_terms), the target, a selection and a leaf's draw ARE is defined here once, so
+// the two homes return the same bytes.
 #pragma once
 #include "design_dev.h"
 
@@ -198,9 +202,9 @@ __device__ __forceinline__ int ct_select_wave(int i0, int i1, unsigned u24, int 
     return hit != 0x7fffffff ? hit : last >= 0 ? last : i0;
 }
 
-__device__ __forceinline__ int ct_deg(int l, int i, int n, int cap) { return min(min(2 * (min((i + 1) << l, n) - (i << l)), n), cap); }
-__device__ __forceinline__ int ct_stride(int l, int T, int cap) { return min(min(2 << l, T), cap) + 1; }
-__device__ __forceinline__ int ct_nodes(int l, int n) { return (n + (1 << l) - 1) >> l; }
+__host__ __device__ __forceinline__ int ct_deg(int l, int i, int n, int cap) { return min(min(2 * (min((i + 1) << l, n) - (i << l)), n), cap); }
+__host__ __device__ __forceinline__ int ct_stride(int l, int T, int cap) { return min(min(2 << l, T), cap) + 1; }
+__host__ __device__ __forceinline__ int ct_nodes(int l, int n) { return (n + (1 << l) - 1) >> l; }
 
 // LSE over i = i0 .. i1 of term(i), the convolution of the tree: the maximum, then the sum of exp(term - maximum) in index order, -inf
 // when no term is above -inf (unrolled by four: the loads and the exps of four terms overlap).
@@ -212,6 +216,33 @@ __device__ __forceinline__ double ct_lse_terms(int i0, int i1, Term term) {
 #pragma unroll 4
     for (int i = i0; i <= i1; ++i) sum += exp(term(i) - mx);
     return mx > -INFINITY ? mx + log(sum) : -INFINITY;
+}
+
+// The coefficients 0 .. deg of a level-1 node from the polynomials of its two leaves (`two` false: the right leaf is empty and the node is
+// its left leaf), into out.  Whoever builds level 1 - ct_inside into LDS, design_long.hip into the workspace - builds it here.
+__device__ __forceinline__ void ct_node1(const double (&l)[3], const double (&r)[3], bool two, int deg, double* out) {
+#pragma unroll
+    for (int k = 0; k <= 4; ++k) {
+        double mx = -INFINITY, sum = 0.0;
+#pragma unroll
+        for (int c = 0; c <= 2; ++c)
+            if (c <= k && k - c <= 2) mx = fmax(mx, l[c] + r[k - c]);
+#pragma unroll
+        for (int c = 0; c <= 2; ++c)
+            if (c <= k && k - c <= 2) sum += exp(l[c] + r[k - c] - mx);
+        if (k <= deg) out[k] = two ? (mx > -INFINITY ? mx + log(sum) : -INFINITY) : (k <= 2 ? l[k < 2 ? k : 2] : -INFINITY);
+    }
+}
+
+// Coefficient k <= deg of node (l, i), l >= 2, from `below`, the first double of level l - 1 of the same tree (cstride, cnodes: that
+// level's stride and node count): one ct_lse_terms over the halves in index order, or the left half's own when the right half is empty.
+__device__ __forceinline__ double ct_conv(const double* below, int l, int i, int k, int n, int cap, int cstride, int cnodes) {
+    const double* L = below + (size_t)(2 * i) * cstride;
+    const double* R = L + cstride;
+    const int degL = ct_deg(l - 1, 2 * i, n, cap);
+    if (2 * i + 1 >= cnodes) return k <= degL ? L[k] : -INFINITY;
+    const int degR = ct_deg(l - 1, 2 * i + 1, n, cap);
+    return ct_lse_terms(max(0, k - degR), min(k, degL), [&](int c) { return L[c] + R[k - c]; });
 }
 
 // Phase A of every kernel on the tree: the inside tree of RNA b bottom-up into `tree` - level 1 one node per thread straight from the
@@ -237,20 +268,8 @@ __device__ __forceinline__ double ct_inside(const CtArgs& a, double* tree, doubl
         }
         if (SETS) kmin += ct_min_d(l0, l1, l2) + ct_min_d(r0, r1, r2);
         if (n == 1) { s_leaf[0] = l0; s_leaf[1] = l1; s_leaf[2] = l2; break; }
-        double* out = tree + a.base[1] + (size_t)i * ct_stride(1, T, cap);
-        const int deg = ct_deg(1, i, n, cap);
         const double l[3] = {l0, l1, l2}, r[3] = {r0, r1, r2};
-#pragma unroll
-        for (int k = 0; k <= 4; ++k) {
-            double mx = -INFINITY, sum = 0.0;
-#pragma unroll
-            for (int c = 0; c <= 2; ++c)
-                if (c <= k && k - c <= 2) mx = fmax(mx, l[c] + r[k - c]);
-#pragma unroll
-            for (int c = 0; c <= 2; ++c)
-                if (c <= k && k - c <= 2) sum += exp(l[c] + r[k - c] - mx);
-            if (k <= deg) out[k] = t + 1 < n ? (mx > -INFINITY ? mx + log(sum) : -INFINITY) : (k <= 2 ? l[k < 2 ? k : 2] : -INFINITY);
-        }
+        ct_node1(l, r, t + 1 < n, ct_deg(1, i, n, cap), tree + a.base[1] + (size_t)i * ct_stride(1, T, cap));
     }
     if (SETS) {
         kmin = sc_wave_sum(kmin);
@@ -262,17 +281,7 @@ __device__ __forceinline__ double ct_inside(const CtArgs& a, double* tree, doubl
         for (int idx = tid; idx < nodes * stride; idx += SC_THREADS) {
             const int i = idx / stride, k = idx - i * stride;
             if (k > ct_deg(l, i, n, cap)) continue;
-            const double* L = tree + a.base[l - 1] + (size_t)(2 * i) * cstride;
-            const double* R = L + cstride;
-            const int degL = ct_deg(l - 1, 2 * i, n, cap);
-            double v;
-            if (2 * i + 1 < cnodes) {
-                const int degR = ct_deg(l - 1, 2 * i + 1, n, cap);
-                v = ct_lse_terms(max(0, k - degR), min(k, degL), [&](int c) { return L[c] + R[k - c]; });
-            } else {
-                v = k <= degL ? L[k] : -INFINITY;
-            }
-            tree[a.base[l] + idx] = v;
+            tree[a.base[l] + idx] = ct_conv(tree + a.base[l - 1], l, i, k, n, cap, cstride, cnodes);
         }
         __syncthreads();
     }

@@ -1,7 +1,7 @@
 // Pieces shared by the nine design kernels - k_design (design.hip, f32), k_design_tied (design_tied.hip), k_design_gc / k_design_count
 // (count_tree_dev.h), k_design_distinct (design_distinct.hip), k_design_avoid (design_avoid.hip, avoid_chain_dev.h), k_design_dfa
 // (design_dfa.hip: what k_design_avoid uses, with workgroup barriers instead of the fence) and the two profile kernels of
-// design_profile.hip, all fp64 - and by their entries.  Everything that is about "a position
+// design_profile.hip, all fp64 - and the kernels of the count tree in global memory (design_long.hip) - and by their entries.  Everything that is about "a position
 // under the constraints" has its one definition here: the arguments and the entry prologue (ds_prepare), the mask of a position (ds_mask),
 // its row (ds_load<F>), its validated partner (ds_partner), the 16 cells of a pair (ds_pair_mask), the uniform of a position, the DRAW
 // RULE as templates over the scalar type - the weights exp(z - max over the admitted), the selection over an admitted set, the joint cell

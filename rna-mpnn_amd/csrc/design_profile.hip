@@ -5,7 +5,8 @@
 // restates.  One 256-thread workgroup per RNA, no sample axis, no workspace, no atomics, no runtime fill / copy node, no host synchronisation.
 //
 // k_design_count_profile.  The leaves, the tree, the convolution, the window, the target and the k_min rule are count_tree_dev.h's (ct_leaf,
-// ct_inside, ct_lse_terms, ct_target, ct_deg / ct_stride / ct_nodes, ct_min_d).  (A) ct_inside: the inside tree bottom-up into LDS, k_min and
+// ct_inside, ct_lse_terms, ct_target, ct_deg / ct_stride / ct_nodes, ct_min_d); phase B (pf_ct_root), a coefficient of phase C (pf_outside),
+// phase D (pf_ct_leaves) and the final writer are profile_dev.h's, which the same profile on trees in global memory (design_long.hip) shares.  (A) ct_inside: the inside tree bottom-up into LDS, k_min and
 // the free sum on the way.  (B) wave 0: ct_target - the window, the target and count_miss of the draw; K* and log_z; the root's outside
 // O(k) = 0 on K*, -inf elsewhere.
 // (C) the OUTSIDE pass top-down into a second tree of the same layout: O_L(a) = LSE_k O(k) + R(k - a), O_R(b) = LSE_k O(k) + L(k - b), dealt
@@ -29,104 +30,15 @@
 //   160 KiB holds T <= 1168 at L = 13 (no run longer than 3) and T <= 293 at L = 64 (the draw kernel: 1064 and 290).
 // Non-finite rows can make the outputs of THAT RNA NaN; no index depends on a value, so nothing faults and no other RNA changes.
 #include "avoid_chain_dev.h"
-#include "count_tree_dev.h"
+#include "profile_dev.h"
 
 namespace {
-struct PfOut {
-    double* marg;                // (B,T,4) or null
-    double* log_z;               // (B) or null
-    double* log_z_free;          // (B) or null
-    double* entropy;             // (B) or null
-};
-
-// The workgroup's totals of three doubles: wave butterfly, then one LDS hop over the four waves in ascending order - a fixed order, so two
-// calls give the same bytes.  Valid in thread 0 only; every thread calls it (one barrier).  s_d holds 3 x SC_WAVES doubles.
-__device__ __forceinline__ void pf_block_sums(double& x, double& y, double& z, int tid, double (*s_d)[SC_WAVES]) {
-    x = sc_wave_sum(x); y = sc_wave_sum(y); z = sc_wave_sum(z);
-    if ((tid & 63) == 0) { s_d[0][tid >> 6] = x; s_d[1][tid >> 6] = y; s_d[2][tid >> 6] = z; }
-    __syncthreads();
-    if (tid != 0) return;
-    x = 0.0; y = 0.0; z = 0.0;
-#pragma unroll
-    for (int w = 0; w < SC_WAVES; ++w) { x += s_d[0][w]; y += s_d[1][w]; z += s_d[2][w]; }
-}
-// P z for the entropy: a class of probability 0 is skipped (its z may be -inf)
-__device__ __forceinline__ double pf_pz(double p, double z) { return p != 0.0 ? p * z : 0.0; }
-__device__ __forceinline__ void pf_store4(double* marg, size_t row, const double (&p)[4]) {
-    if (!marg) return;
-    double2* out = reinterpret_cast<double2*>(marg + 4 * row);
-    out[0] = make_double2(p[0], p[1]); out[1] = make_double2(p[2], p[3]);
-}
-// what every thread and the final writer share
-__device__ __forceinline__ void pf_finish(const PfOut& o, const DesignArgs& a, int32_t* miss_out, int miss, int b, int n, int tid, int bad, double free_sum,
-                                          double pz_sum, double lz_sum, bool lz_from_sum, double log_z, const DsScratch& sc, double (*s_d)[SC_WAVES]) {
-    const double zero[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int t = n + tid; t < a.T; t += SC_THREADS) pf_store4(o.marg, (size_t)b * a.T + t, zero);
-    float f0 = 0.f, f1 = 0.f;
-    sc_block_sums(bad, f0, f1, tid, sc.s_i, sc.s_f);
-    pf_block_sums(free_sum, pz_sum, lz_sum, tid, s_d);
-    if (tid != 0) return;
-    const double lz = n == 0 ? 0.0 : lz_from_sum ? lz_sum : log_z;
-    if (o.log_z) o.log_z[b] = lz;
-    if (o.log_z_free) o.log_z_free[b] = n == 0 ? 0.0 : free_sum;
-    if (o.entropy) o.entropy[b] = n == 0 ? 0.0 : lz - pz_sum;
-    if (a.infeasible) a.infeasible[b] = bad;
-    if (miss_out) miss_out[b] = miss;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- the count profile
-constexpr size_t PF_CT_SCRATCH = 240;          // DS_SCRATCH 48 | at 48 two flags | at 64 the 1-mer's leaf | at 96 its outside | at 120 log_z | at 128 3 x 4 sums
-static_assert(DS_SCRATCH == 48 && CT_LDS_SCRATCH == 96, "the layout of the count profile's scratch");
-
-struct PfCtArgs : CtArgs { PfOut out; };
-
-// LSE_k over k = k0 .. k1 of O[k] + p(k - k0 .. ) with the sibling LEAF's polynomial (s0, s1, s2): the outside of a leaf below a level-1 node
-__device__ __forceinline__ double pf_leaf_outside(const double* O, int deg, int a, double s0, double s1, double s2) {
-    double v[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) v[d] = a + d <= deg ? O[a + d] + ct_pick(s0, s1, s2, d) : -INFINITY;
-    return ds_lse<3>(v, 7);
-}
-
-// The marginals of leaf t from w(d) = the log of what multiplies exp(z) of a cell that counts d; -> its share of the sum of P z.
-__device__ __forceinline__ double pf_leaf_out(const PfCtArgs& a, const CtLeaf& lf, size_t pad0, int t, double w0, double w1, double w2) {
-    if (lf.kind == 2) return 0.0;                                   // written by the owner of the pair
-    double pz = 0.0;
-    if (lf.kind == 0) {
-        double p[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            p[c] = ((lf.p.m >> c) & 1) ? exp(lf.p.z[c] + ct_pick(w0, w1, w2, (lf.ci >> c) & 1)) : 0.0;
-            pz += pf_pz(p[c], lf.p.z[c]);
-        }
-        pf_store4(a.out.marg, pad0 + t, p);
-        return pz;
-    }
-    double pi[4] = {0.0, 0.0, 0.0, 0.0}, pj[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        const int d = ((lf.ci >> (c >> 2)) & 1) + ((lf.cj >> (c & 3)) & 1);
-        const double pc = ((lf.m16 >> c) & 1) ? exp(lf.p.z[c >> 2] + lf.pj.z[c & 3] + ct_pick(w0, w1, w2, d)) : 0.0;
-        pi[c >> 2] += pc; pj[c & 3] += pc;
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) pz += pf_pz(pi[c], lf.p.z[c]) + pf_pz(pj[c], lf.pj.z[c]);
-    pf_store4(a.out.marg, pad0 + t, pi);
-    pf_store4(a.out.marg, pad0 + lf.j, pj);
-    return pz;
-}
-
 __global__ void __launch_bounds__(SC_THREADS) k_design_count_profile(PfCtArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char pfc_lds[];
     double* tree = reinterpret_cast<double*>(pfc_lds);
     double* outs = reinterpret_cast<double*>(pfc_lds + a.lds_tree);                          // the outside tree, the inside tree's layout
-    unsigned char* scr = pfc_lds + 2 * (size_t)a.lds_tree;
-    const DsScratch sc = ds_scratch(scr);
-    int* s_flag = reinterpret_cast<int*>(scr + 48);                                          // [0]: every leaf at its own minimum; [1]: count_miss
-    double* s_leaf = reinterpret_cast<double*>(scr + 64);                                    // 3 doubles
-    double* o_leaf = reinterpret_cast<double*>(scr + 96);                                    // 3 doubles
-    double* s_logz = reinterpret_cast<double*>(scr + 120);
-    double (*s_d)[SC_WAVES] = reinterpret_cast<double (*)[SC_WAVES]>(scr + 128);
+    const PfCtScratch ps = pf_ct_scratch(pfc_lds + 2 * (size_t)a.lds_tree);
+    const DsScratch sc = ps.sc;
     const int b = blockIdx.x, tid = threadIdx.x, T = a.T, cap = a.cap;
     int n;
     long long row0;
@@ -135,89 +47,28 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_count_profile(PfCtArgs a)
     const int Ln = n > 1 ? 32 - __clz(n - 1) : 0;
     int bad = 0;
     // ---- A: the inside tree
-    double free_sum = ct_inside<true, true>(a, tree, s_leaf, sc.s_i, pad0, row0, n, tid, bad);
+    double free_sum = ct_inside<true, true>(a, tree, ps.s_leaf, sc.s_i, pad0, row0, n, tid, bad);
     // ---- B: the window, the target, K*, log_z and the root's outside
-    if (tid < 64 && n > 0) {
-        const double* root = Ln ? tree + a.base[Ln] : s_leaf;
-        double* oroot = Ln ? outs + a.base[Ln] : o_leaf;
-        const CtTarget g = ct_target<true>(a, root, sc.s_i, b, n, Ln);
-        const int deg = g.deg, lo = g.lo, hi = g.hi, K = g.K;
-        const bool any = g.any;
-        // K*: the finite counts of the window, or the target alone; log_z = LSE over K* of the root, by the wave in a fixed order
-        double mx = -INFINITY, sum = 0.0;
-        for (int k = tid; k <= deg; k += 64) {
-            const bool in = (any ? (k >= lo && k <= hi) : k == K) && ct_finite(root[k]);
-            if (in) mx = fmax(mx, root[k]);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
-        for (int k = tid; k <= deg; k += 64) {
-            const bool in = (any ? (k >= lo && k <= hi) : k == K) && ct_finite(root[k]);
-            if (in) sum += exp(root[k] - mx);
-            oroot[k] = in ? 0.0 : -INFINITY;
-        }
-        sum = sc_wave_sum(sum);
-        if (tid == 0) {
-            s_flag[0] = g.at_min ? 1 : 0; s_flag[1] = g.miss;
-            *s_logz = mx > -INFINITY ? mx + log(sum) : -INFINITY;
-        }
-    }
+    if (tid < 64 && n > 0) pf_ct_root(a, Ln ? tree + a.base[Ln] : ps.s_leaf, Ln ? outs + a.base[Ln] : ps.o_leaf, sc.s_i, b, n, Ln, tid, ps.s_flag, ps.s_logz);
     __syncthreads();
-    const bool at_min = n > 0 && s_flag[0] != 0;                   // the same in every thread
-    const int miss = n > 0 ? s_flag[1] : 0;
-    const double log_z = n > 0 ? *s_logz : 0.0;
+    const bool at_min = n > 0 && ps.s_flag[0] != 0;                // the same in every thread
+    const int miss = n > 0 ? ps.s_flag[1] : 0;
+    const double log_z = n > 0 ? *ps.s_logz : 0.0;
     // ---- C: the outside pass, top down: level l hands its children at level l - 1 their outsides
     for (int l = Ln; l >= 2 && !at_min; --l) {
         const int stride = ct_stride(l, T, cap), cstride = ct_stride(l - 1, T, cap), cnodes = ct_nodes(l - 1, n);
         for (int idx = tid; idx < cnodes * cstride; idx += SC_THREADS) {
             const int j = idx / cstride, c = idx - j * cstride;
             if (c > ct_deg(l - 1, j, n, cap)) continue;
-            const int i = j >> 1, sib = j ^ 1, degP = ct_deg(l, i, n, cap);
-            const double* O = outs + a.base[l] + (size_t)i * stride;
-            double v;
-            if (sib < cnodes) {
-                const double* Sb = tree + a.base[l - 1] + (size_t)sib * cstride;
-                v = ct_lse_terms(c, min(c + ct_deg(l - 1, sib, n, cap), degP), [&](int k) { return O[k] + Sb[k - c]; });
-            } else {
-                v = c <= degP ? O[c] : -INFINITY;                   // an empty right half: the left half is the node
-            }
-            outs[a.base[l - 1] + idx] = v;
+            outs[a.base[l - 1] + idx] = pf_outside(outs + a.base[l], tree + a.base[l - 1], l, j, c, n, cap, stride, cstride, cnodes);
         }
         __syncthreads();
     }
     // ---- D: the leaves of a level-1 node, their outsides and their marginals
     double pz_sum = 0.0, lz_sum = 0.0;
-    int unused_bad = 0;
-    for (int i = tid; 2 * i < n; i += SC_THREADS) {
-        const int t = 2 * i;
-        const bool two = t + 1 < n;
-        double l0, l1, l2, r0 = 0.0, r1 = -INFINITY, r2 = -INFINITY;
-        const CtLeaf ll = ct_leaf<true>(a, pad0, row0, n, t, l0, l1, l2, unused_bad);
-        CtLeaf lr = ll;
-        if (two) lr = ct_leaf<true>(a, pad0, row0, n, t + 1, r0, r1, r2, unused_bad);
-        double wl0, wl1, wl2, wr0 = -INFINITY, wr1 = -INFINITY, wr2 = -INFINITY;
-        if (at_min) {
-            const int dl = ct_min_d(l0, l1, l2), dr = ct_min_d(r0, r1, r2);
-            const double pl = ct_pick(l0, l1, l2, dl), pr = ct_pick(r0, r1, r2, dr);
-            lz_sum += pl + (two ? pr : 0.0);
-            wl0 = dl == 0 ? -pl : -INFINITY; wl1 = dl == 1 ? -pl : -INFINITY; wl2 = dl == 2 ? -pl : -INFINITY;
-            wr0 = dr == 0 ? -pr : -INFINITY; wr1 = dr == 1 ? -pr : -INFINITY; wr2 = dr == 2 ? -pr : -INFINITY;
-        } else {
-            const double* O = n == 1 ? o_leaf : outs + a.base[1] + (size_t)i * ct_stride(1, T, cap);
-            const int deg = n == 1 ? min(1, cap) : ct_deg(1, i, n, cap);
-            if (two) {
-                wl0 = pf_leaf_outside(O, deg, 0, r0, r1, r2) - log_z; wr0 = pf_leaf_outside(O, deg, 0, l0, l1, l2) - log_z;
-                wl1 = pf_leaf_outside(O, deg, 1, r0, r1, r2) - log_z; wr1 = pf_leaf_outside(O, deg, 1, l0, l1, l2) - log_z;
-                wl2 = pf_leaf_outside(O, deg, 2, r0, r1, r2) - log_z; wr2 = pf_leaf_outside(O, deg, 2, l0, l1, l2) - log_z;
-            } else {                                                // an empty right half: the leaf is the node
-                wl0 = O[0] - log_z; wl1 = (1 <= deg ? O[1] : -INFINITY) - log_z; wl2 = (2 <= deg ? O[2] : -INFINITY) - log_z;
-            }
-        }
-        pz_sum += pf_leaf_out(a, ll, pad0, t, wl0, wl1, wl2);
-        if (two) pz_sum += pf_leaf_out(a, lr, pad0, t + 1, wr0, wr1, wr2);
-    }
+    pf_ct_leaves(a, outs + a.base[1], ps.o_leaf, pad0, row0, n, tid, at_min, log_z, pz_sum, lz_sum);
     // ---- E: padding, sums, scalars
-    pf_finish(a.out, a, a.miss, miss, b, n, tid, bad, free_sum, pz_sum, lz_sum, at_min, log_z, sc, s_d);
+    pf_finish(a.out, a, a.miss, miss, b, n, tid, bad, free_sum, pz_sum, lz_sum, at_min, log_z, sc, ps.s_d);
 }
 
 inline size_t pf_ct_lds_bytes(int T, int cap, size_t& tree) {

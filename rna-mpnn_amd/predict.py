@@ -33,7 +33,11 @@ sequence is pair-compatible in all of them.  The designs CSV then has one row pe
 G+C content window (``rnampnn_design_gc``, both families): every draw holds a fraction of C and G between LO and HI of its length - drawn
 exactly from the model's distribution conditioned on that (and on the other constraints), not filtered.  The designs CSV gains the columns
 ``gc`` (the fraction of the draw) and ``gc_miss`` (0, or by how many nucleotides the nearest count the constraints can reach lies outside
-the window; the draws then hold that count).  Not built together with ``--states``.
+the window; the draws then hold that count).  Not built together with ``--states``.  The count tree of the window lives in the LDS of a
+workgroup, which holds structures of up to 1,017 nt (2,867 for ``--max-mutations 8``); ``--tree global`` keeps it in a workspace in global
+memory instead (``rnampnn_design_count_long``, up to 32,744 nt - a ribosomal RNA), ``--tree auto`` does so where LDS refuses.  The draws
+are the same bytes wherever both run.  ``--tree global`` / ``auto`` with a mode that has no count tree is refused before the checkpoint is
+opened.
 
     python rna-mpnn_amd/predict.py --ckpt Final.pt --data DIR --samples 8 --distinct sample [--constraints cons.csv --bias .. --omit .. --no-wobble]
 
@@ -115,6 +119,9 @@ def parse(argv=None):
     ap.add_argument("--no-wobble", action="store_true", help="base pairs of --constraints exclude GU / UG")
     ap.add_argument("--states", default=None, help="CSV design_id,pdb_id,weight: the structures of one design_id share one sequence")
     ap.add_argument("--gc-content", default=None, help="LO:HI: every draw of --samples holds a G+C fraction in this window")
+    ap.add_argument("--tree", default=None, choices=("lds", "global", "auto"),
+                    help="where the count tree of --gc-content / --max-mutations lives: lds (the default, structures of up to 1017 nt under a G+C "
+                         "window), global (a workspace in global memory, up to 32744 nt) or auto (lds where it fits); the draws are the same")
     ap.add_argument("--distinct", default=None, choices=("sample", "best"),
                     help="the draws of --samples are pairwise different: sampled without replacement, or the most probable ones")
     ap.add_argument("--max-mutations", type=int, default=None, help="M: every draw of --samples differs from its reference at no more than M positions")
@@ -153,6 +160,21 @@ def gc_option(args) -> dict:
     if args.samples <= 0 and not args.profile_out:
         raise ValueError("--gc-content needs --samples N > 0")
     return dict(gc_content=parse_gc_content(args.gc_content))
+
+
+def tree_option(args) -> dict:
+    """The ``tree`` keyword of ``predict`` from ``--tree``; empty without the flag.  ``ValueError`` naming the flags for ``global`` / ``auto``
+    with a mode that has no count tree, before the checkpoint is opened."""
+    if args.tree is None:
+        return {}
+    for flag, value in (("--pairs", args.pairs), ("--states", args.states), ("--distinct", args.distinct), ("--require", args.require),
+                        ("--avoid", args.avoid), ("--max-run", args.max_run)):
+        if value is not None and args.tree != "lds":
+            raise ValueError(f"--tree {args.tree} together with {flag} is not built: only the count tree of --gc-content and --max-mutations has "
+                             "a home in global memory")
+    if args.tree != "lds" and args.gc_content is None and args.max_mutations is None and (args.samples > 0 or not args.profile_out):
+        raise ValueError(f"--tree {args.tree} needs --gc-content or --max-mutations: a draw without a count window has no count tree")
+    return dict(tree=args.tree)
 
 
 def distinct_option(args) -> dict:
@@ -275,6 +297,7 @@ def run(args, log=print):
     mutations = mutations_option(args)
     distinct = distinct_option(args)
     gc = gc_option(args)                                           # a bad window fails here, before the model is loaded
+    tree = tree_option(args)                                       # global / auto with a mode that has no count tree fails here
     family = checkpoint_family(args.ckpt)
     if family == "rnampnn":
         from rnampnn.utils.predict import predict
@@ -283,7 +306,7 @@ def run(args, log=print):
         from rdesign.utils.predict import predict
         from rdesign.utils.train import load_checkpoint
     extra = dict(samples=args.samples, temperature=args.temperature, seed=args.seed, designs_csv=args.designs_out, **design_options(args), **gc, **distinct,
-                 **mutations, **avoid, **profile, **require)
+                 **mutations, **avoid, **profile, **require, **tree)
     if args.states:
         if family != "rnampnn":
             raise ValueError("--states designs with rnampnn checkpoints only; for an rdesign checkpoint call RNAModel.design(states=...) "

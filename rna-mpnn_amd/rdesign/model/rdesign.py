@@ -33,7 +33,7 @@ import torch.nn.functional as F
 
 from .. import _native
 from rnampnn.model._base import _prep, _stream
-from rnampnn.model.decode import (check_avoid, check_distinct, check_mutations, check_nested, check_require, check_state_lengths, design_by_mode, design_distinct_from_logits,  # noqa: F401
+from rnampnn.model.decode import (check_avoid, check_distinct, check_mutations, check_nested, check_require, check_state_lengths, check_profile_tree, check_tree, design_by_mode, design_distinct_from_logits,  # noqa: F401
                                   design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits, design_profile_from_logits,
                                   letters_packed,
                                   score_logits)
@@ -431,7 +431,7 @@ class RNAModel(nn.Module):
     @torch.no_grad()
     def design(self, X, mask, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None, lengths=None, states=None,
                state_weights=None, gc_content=None, distinct=None, mutations=None, avoid=None, require=None,
-               pairs=None):
+               pairs=None, tree: str = "lds"):
         """``n_samples`` sequences per RNA drawn from this model's read-out at ``temperature`` and scored, in one ``rnampnn_design`` launch
         on the packed logits -> (seqs int8 (n_samples,B,T), -1 on padding; seq_nll (n_samples,B) f32, the model's own temperature-1 NLL of
         each draw; infeasible (B,) int32).  ``constraints``: a ``rnampnn.utils.constraints.DesignConstraints`` (fixed nucleotides, base
@@ -457,8 +457,12 @@ class RNAModel(nn.Module):
         and / or ``require`` UNDER the base pairs of ``constraints`` (``design_nested_from_logits``): the structure is honoured and the
         draws are exact as long as it is nested -> (seqs, seq_nll, infeasible, hits, accepted, dfa_miss, nest_miss (B,) int32 = 1 for an
         RNA whose pairs cross: it is drawn as plain ``constraints`` draw it); host-side constraints whose structure crosses, another
-        mode, another value, or neither ``avoid`` nor ``require`` are a ``ValueError`` before the forward pass."""
+        mode, another value, or neither ``avoid`` nor ``require`` are a ``ValueError`` before the forward pass.  ``tree`` ("lds", the
+        default: everything above, unchanged; "global"; "auto"): where the count tree of ``gc_content`` and ``mutations`` lives
+        (``check_tree``) - in global memory RNAs of up to 32,744 nt are drawn under a G+C window, with the same bytes wherever both homes
+        run; anything but "lds" with another mode is a ``ValueError`` before the forward pass."""
         mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require, pairs=pairs)
+        check_tree(tree, mode)
         mutations = check_mutations(mutations)
         if mode == "nested":
             require, avoid = check_nested(require, avoid, constraints), None
@@ -470,16 +474,17 @@ class RNAModel(nn.Module):
         logits, cu, T = self._packed_logits(X, mask, lengths)
         return design_by_mode(mode, logits, cu_seqlens=cu, max_len=T, n_samples=n_samples, temperature=temperature, seed=seed,
                               constraints=constraints, states=states, state_weights=state_weights, gc_content=gc_content, distinct=distinct,
-                              mutations=mutations, avoid=avoid, require=require)
+                              mutations=mutations, avoid=avoid, require=require, tree=tree)
 
     @torch.no_grad()
-    def design_profile(self, X, mask, temperature: float = 0.1, constraints=None, lengths=None, gc_content=None, mutations=None, avoid=None):
+    def design_profile(self, X, mask, temperature: float = 0.1, constraints=None, lengths=None, gc_content=None, mutations=None, avoid=None,
+                       tree: str = "lds"):
         """What ``design`` draws FROM under the same arguments, with one eval-mode forward and one launch on the packed logits: the exact
         per-position marginals, log partition sums and entropy of the constrained, tempered distribution (``design_profile_from_logits``)
         -> a ``DesignProfile``.  ``constraints``, ``lengths``, ``gc_content``, ``mutations`` and ``avoid`` as in ``design``; the pairings
         ``design`` refuses are refused here with the same messages, before the forward pass.  No profile is built for ``states`` or
-        ``distinct``."""
-        design_mode(gc_content=gc_content, mutations=mutations, avoid=avoid)
+        ``distinct``.  ``tree`` as in ``design``, for every profile but ``avoid``'s."""
+        check_profile_tree(tree, design_mode(gc_content=gc_content, mutations=mutations, avoid=avoid))
         check_mutations(mutations)
         check_avoid(avoid, constraints)
         was_training = self.training
@@ -489,7 +494,7 @@ class RNAModel(nn.Module):
         finally:
             self.train(was_training)
         return design_profile_from_logits(logits, cu_seqlens=cu, max_len=T, temperature=temperature, constraints=constraints,
-                                          gc_content=gc_content, mutations=mutations, avoid=avoid)
+                                          gc_content=gc_content, mutations=mutations, avoid=avoid, tree=tree)
 
     @torch.no_grad()
     def score_sequences(self, X, mask, seqs, labels=None, lengths=None):

@@ -80,6 +80,12 @@ SYMBOLS = {
                                     _VP, _VP, _VP, _VP]),
     "rnampnn_design_count": (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I32, _F, _I32, C.c_uint64, _VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, _VP, _I32,
                                        _VP, _VP, _VP, _VP, _VP, _VP]),
+    "rnampnn_design_count_long_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
+    "rnampnn_design_count_long": (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I32, _F, _I32, C.c_uint64, _VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, _VP,
+                                            _I32, _VP, _SZ, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "rnampnn_design_count_profile_long_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
+    "rnampnn_design_count_profile_long": (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I32, _F, _VP, _VP, _I32, _VP, _I32, _VP, _VP, _VP, _I32, _VP, _SZ,
+                                                    _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rnampnn_design_distinct": (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I32, _F, _I32, C.c_uint64, _VP, _VP, _VP, _I32, _VP, _I32, _I32, _VP, _VP,
                                           _VP, _VP, _VP, _VP]),
     "rnampnn_design_avoid": (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I32, _F, _I32, C.c_uint64, _VP, _VP, _VP, _I32, _VP, _I32, _VP, _I32, C.c_uint64,

@@ -1,7 +1,7 @@
 """Decoding from logits, as free functions over the C ABI's decode family: argmax + recovery (``rnampnn_argmax_recovery``), free draws
 (``rnampnn_sample``), scores (``rnampnn_score``), constrained and multi-state design (``rnampnn_design``, ``rnampnn_design_tied``), design
 under a G+C content window (``rnampnn_design_gc``), design within a count window / a mutation budget (``rnampnn_design_count``), distinct
-designs (``rnampnn_design_distinct``), design that avoids forbidden motifs (``rnampnn_design_avoid``), design with required motifs (``rnampnn_design_dfa``), motifs under a nested structure (``rnampnn_design_nested``), the distribution those draws come from (``rnampnn_design_count_profile``, ``rnampnn_design_avoid_profile``), the choice between them (``design_mode``, ``design_by_mode``) and the letters of class ids.  Needs the library and ``_base`` only, so both model packages import
+designs (``rnampnn_design_distinct``), design that avoids forbidden motifs (``rnampnn_design_avoid``), design with required motifs (``rnampnn_design_dfa``), motifs under a nested structure (``rnampnn_design_nested``), the distribution those draws come from (``rnampnn_design_count_profile``, ``rnampnn_design_avoid_profile``), the count tree in global memory for long RNAs (``tree=``: ``rnampnn_design_count_long``, ``rnampnn_design_count_profile_long``), the choice between them (``design_mode``, ``design_by_mode``) and the letters of class ids.  Needs the library and ``_base`` only, so both model packages import
 it at module level."""
 from __future__ import annotations
 
@@ -159,6 +159,52 @@ def design_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None
                         entry="rnampnn_design" if states is None else "rnampnn_design_tied")
 
 
+TREES = ("lds", "global", "auto")
+TREE_MODES = ("gc_content", "mutations")
+NO_TREE = {"nested": "pairs"}
+
+
+def check_tree(tree: str, mode: Optional[str] = None) -> str:
+    """``tree`` - where the count tree of a G+C window or a mutation budget lives: "lds" (the default: one launch, the tree in the LDS of
+    the workgroup, ``NotImplementedError`` past what 160 KiB hold), "global" (``rnampnn_design_count_long`` /
+    ``rnampnn_design_count_profile_long``: a workspace in global memory, built once per RNA) or "auto" ("lds" where the library accepts it,
+    "global" otherwise; the two return the same bytes) -> ``tree``.  ``ValueError`` for another value and, with a ``design_mode`` given, for
+    "global" / "auto" together with a mode that has no count tree; touches no device, so a caller refuses before its forward pass."""
+    if tree not in TREES:
+        raise ValueError(f"tree must be one of {list(TREES)}, got {tree!r}")
+    if tree != "lds" and mode is not None and mode not in TREE_MODES:
+        what = "a draw without a count window" if mode == "plain" else NO_TREE.get(mode, mode)
+        raise ValueError(f"tree={tree!r} together with {what} is not built: only the count tree of gc_content and of mutations has a home in "
+                         "global memory")
+    return tree
+
+
+def check_profile_tree(tree: str, mode: str) -> str:
+    """``check_tree`` for ``design_profile_from_logits``, whose "plain" mode is a count profile as well: ``ValueError`` for anything but
+    "lds" together with ``avoid``."""
+    if check_tree(tree) != "lds" and mode == "avoid":
+        raise ValueError(f"tree={tree!r} together with avoid is not built: only the count trees of the plain, gc_content and mutations "
+                         "profiles have a home in global memory")
+    return tree
+
+
+def _by_tree(tree: str, call):
+    """``call(long)`` -> its result, with ``long`` as ``tree`` decides: "lds" False, "global" True, "auto" False first and True when the
+    library refuses the LDS entry (``NotImplementedError``: its size check, which fires before anything is launched)."""
+    if check_tree(tree) != "auto":
+        return call(tree == "global")
+    try:
+        return call(False)
+    except NotImplementedError:
+        return call(True)
+
+
+def _tree_workspace(symbol: str, B: int, T: int, cap: int, device):
+    """The workspace of a long entry: (a ``torch.empty`` of ``symbol``(B, T, max(cap, 1)) bytes, that size as the ABI takes it)."""
+    need = int(getattr(_native.lib(), symbol)(max(B, 0), max(T, 0), max(int(cap), 1)))
+    return torch.empty(max(need, 8), dtype=torch.uint8, device=device), C.c_size_t(need)
+
+
 def gc_fractions(gc_content, B: int) -> torch.Tensor:
     """``gc_content`` - a pair of fractions for every RNA, or a (B,2) tensor - -> (B,2) f64 on its own device.  ``ValueError`` for another
     shape; a host value is also checked for fractions outside [0, 1] and lo > hi (a device tensor is not read here: the kernel clamps)."""
@@ -187,20 +233,27 @@ def gc_counts(fractions: torch.Tensor, lengths: torch.Tensor) -> Tuple[torch.Ten
 
 def design_gc_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
                           max_len: Optional[int] = None, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None,
-                          gc_content=(0.0, 1.0)) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                          gc_content=(0.0, 1.0), tree: str = "lds") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """``rnampnn_design_gc`` (include/rnampnn_hip.h): the draws of ``design_from_logits`` conditioned exactly on the G+C content of every
     RNA lying in a window, in one launch -> (seqs, seq_nll, infeasible, gc_count (S,B) int32 = C or G ids written, gc_miss (B,) int32 = 0
     when the window is reachable under the constraints, else its distance to the nearest reachable count, which the draws then hold).
     Layouts and ``constraints`` as in ``design_from_logits``.  ``gc_content``: a pair of fractions (lo, hi) in [0, 1] for every RNA, or a
     (B,2) tensor of them (float64: a float32 fraction carries its rounding into f * n); the counts are formed on the device from the mask
     or ``cu_seqlens`` (``gc_counts``), without a host synchronisation.  Fractions outside [0, 1] or lo > hi raise ``ValueError`` (a device
-    tensor is not read back for that: the kernel clamps it).  CUDA logits only (there is no CPU fallback)."""
+    tensor is not read back for that: the kernel clamps it).  ``tree`` (``check_tree``): "lds" - this entry, T <= 1017; "global" -
+    ``rnampnn_design_count_long`` with C|G counted everywhere and a cap of T, formed on the device, which returns the same bytes at every
+    length; "auto" - "lds" where it fits.  CUDA logits only (there is no CPU fallback)."""
     def window(B, T, m, cu):
         fr = gc_fractions(gc_content, max(B, 0)).to(logits.device, non_blocking=True)
         lengths = (m.sum(dim=1) + 0.5).floor() if m is not None else (cu[1:] - cu[:-1]).clamp(0, max(T, 0))
         return gc_counts(fr, lengths)
-    return _design_call("rnampnn_design_gc", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints, tail=window,
-                        outputs=((torch.int32, True), (torch.int32, False)))
+
+    def long_window(B, T, m, cu):
+        counted = torch.full((max(B, 0), max(T, 0)), 12, dtype=torch.uint8, device=logits.device)
+        return (counted, *window(B, T, m, cu), T, *_tree_workspace("rnampnn_design_count_long_workspace_bytes", B, T, T, logits.device))
+    return _by_tree(tree, lambda long: _design_call(
+        "rnampnn_design_gc", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints, tail=long_window if long else window,
+        outputs=((torch.int32, True), (torch.int32, False)), entry="rnampnn_design_count_long" if long else None))
 
 
 def mutation_sets(reference: torch.Tensor) -> torch.Tensor:
@@ -240,15 +293,18 @@ def count_window(window, cap: Optional[int], B: int) -> Tuple[torch.Tensor, int]
 def design_count_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
                              max_len: Optional[int] = None, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None,
                              counted: Optional[torch.Tensor] = None, window=(0, 0),
-                             cap: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                             cap: Optional[int] = None,
+                             tree: str = "lds") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """``rnampnn_design_count`` (include/rnampnn_hip.h): the draws of ``design_from_logits`` conditioned exactly on a count lying in a
     window, in one launch -> (seqs, seq_nll, infeasible, count (S,B) int32, count_miss (B,) int32 = 0 when the window is reachable under
     the constraints, else its distance to the count the draws then hold).  ``counted`` (B,T) uint8, padded in both layouts: bits 0..3 mark
     the classes (AUCG) that count 1 at that position (``mutation_sets(reference)``: the count is the number of mutations).  ``window``: a
     pair of ints (lo, hi) for every RNA or a (B,2) int tensor, absolute counts.  ``cap``: no count above it is ever drawn; it sizes the
     tree in LDS (T <= 2867 at cap 8, 1017 without a cap).  It defaults to the largest hi of a host-side window; a device window without
-    ``cap`` or a host hi above ``cap`` is a ``ValueError``.  Layouts and ``constraints`` as in ``design_from_logits``.  CUDA logits only
-    (there is no CPU fallback); no host synchronisation."""
+    ``cap`` or a host hi above ``cap`` is a ``ValueError``.  ``tree`` (``check_tree``): "lds" - this entry and its limits; "global" -
+    ``rnampnn_design_count_long``, the tree in a workspace in global memory (``torch.empty`` here, 8 B doubles(T, cap) bytes, built once per
+    RNA for all samples), T <= 32744 at every cap, the same bytes wherever both run; "auto" - "lds" where it fits.  Layouts and
+    ``constraints`` as in ``design_from_logits``.  CUDA logits only (there is no CPU fallback); no host synchronisation."""
     if counted is None:
         raise ValueError("counted is required: the (B, T) sets of classes that count (mutation_sets(reference) for a mutation budget)")
 
@@ -256,8 +312,14 @@ def design_count_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] 
         w, top = count_window(window, cap, max(B, 0))
         w = w.to(logits.device, non_blocking=True)
         return cs, w[:, 0].contiguous(), w[:, 1].contiguous(), top
-    return _design_call("rnampnn_design_count", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints,
-                        padded=(("counted", counted, torch.uint8),), tail=sets_and_window, outputs=((torch.int32, True), (torch.int32, False)))
+
+    def long_sets_and_window(B, T, m, cu, cs):
+        its = sets_and_window(B, T, m, cu, cs)
+        return (*its, *_tree_workspace("rnampnn_design_count_long_workspace_bytes", B, T, its[3], logits.device))
+    return _by_tree(tree, lambda long: _design_call(
+        "rnampnn_design_count", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints,
+        padded=(("counted", counted, torch.uint8),), tail=long_sets_and_window if long else sets_and_window,
+        outputs=((torch.int32, True), (torch.int32, False)), entry="rnampnn_design_count_long" if long else None))
 
 
 def check_budget(lo: int, hi: int, states=None, gc_content=None, distinct=None) -> Tuple[int, int]:
@@ -284,7 +346,8 @@ def check_mutations(mutations, states=None, gc_content=None, distinct=None):
 
 def design_mutations_from_logits(logits: torch.Tensor, mutations, **kw):
     """``design_count_from_logits`` as a mutation budget: ``mutations`` as ``check_mutations`` returns it -> (seqs, seq_nll, infeasible,
-    n_mut (S,B) int32 = the Hamming distance of each draw to the reference, mut_miss (B,) int32)."""
+    n_mut (S,B) int32 = the Hamming distance of each draw to the reference, mut_miss (B,) int32).  ``kw``: the layout, the draw and
+    ``tree``, as ``design_count_from_logits`` takes them."""
     reference, window = mutations
     return design_count_from_logits(logits, counted=mutation_sets(reference.to(logits.device)), window=window, cap=window[1], **kw)
 
@@ -475,11 +538,13 @@ def design_mode(states=None, gc_content=None, distinct=None, mutations=None, avo
 
 
 def design_by_mode(mode: str, logits: torch.Tensor, states=None, state_weights=None, gc_content=None, distinct=None, mutations=None,
-                   avoid=None, require=None, **kw):
+                   avoid=None, require=None, tree: str = "lds", **kw):
     """The ``*_from_logits`` call of ``mode`` (``design_mode``) -> what that function returns.  ``mutations`` as ``check_mutations``
     returns it, ``avoid`` as ``check_avoid`` does, ``require`` as ``check_require`` does (it holds ``avoid``); ``kw``: the layout and the
     draw (mask / cu_seqlens / max_len, n_samples, temperature, seed, constraints).  "nested": ``require`` as ``check_nested`` returns it
-    (it holds ``avoid``)."""
+    (it holds ``avoid``).  ``tree`` (``check_tree``): the home of the count tree of "gc_content" and "mutations"; anything but "lds" with
+    another mode is a ``ValueError``."""
+    check_tree(tree, mode)
     if mode == "nested":
         return design_nested_from_logits(logits, require=require, **kw)
     if mode == "require":
@@ -487,11 +552,11 @@ def design_by_mode(mode: str, logits: torch.Tensor, states=None, state_weights=N
     if mode == "avoid":
         return design_avoid_from_logits(logits, avoid=avoid, **kw)
     if mode == "mutations":
-        return design_mutations_from_logits(logits, mutations, **kw)
+        return design_mutations_from_logits(logits, mutations, tree=tree, **kw)
     if mode == "distinct":
         return design_distinct_from_logits(logits, mode=distinct, **kw)
     if mode == "gc_content":
-        return design_gc_from_logits(logits, gc_content=gc_content, **kw)
+        return design_gc_from_logits(logits, gc_content=gc_content, tree=tree, **kw)
     return design_from_logits(logits, states=states, state_weights=state_weights, **kw)
 
 
@@ -539,7 +604,7 @@ def profile_mode_args(mode: str, B: int, T: int, device, lengths=None, gc_conten
 
 def design_profile_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
                                max_len: Optional[int] = None, temperature: float = 0.1, constraints=None, gc_content=None, mutations=None,
-                               avoid=None) -> DesignProfile:
+                               avoid=None, tree: str = "lds") -> DesignProfile:
     """``rnampnn_design_count_profile`` / ``rnampnn_design_avoid_profile`` (include/rnampnn_hip.h): the exact distribution that the draws
     of ``design_by_mode`` come from under the same arguments - per-position marginals, log partition sums and entropy, fp64, in one launch ->
     ``DesignProfile``.  The mode is ``design_mode(gc_content=, mutations=, avoid=)``, so the pairings that are not built keep their messages:
@@ -547,9 +612,12 @@ def design_profile_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor
     fractions or (B,2), as in ``design_gc_from_logits``), "mutations" (``(reference, max)`` or ``(reference, min, max)``, as ``design``
     takes it) and "avoid" (a ``MotifAutomaton`` or motif strings; base pairs are the ``ValueError`` of ``check_avoid``).  The trees live in
     LDS: T <= 535 for a G+C window, 1457 for a budget of 8, 1168 for ``max_run=3``; beyond it the library raises ``NotImplementedError``
-    naming the limit.  Layouts and ``constraints`` as in ``design_from_logits``.  CUDA logits only (there is no CPU fallback); no host
-    synchronisation."""
+    naming the limit.  ``tree`` (``check_tree``), for the three count modes: "global" - ``rnampnn_design_count_profile_long``, the inside
+    and the outside tree in a workspace in global memory (``torch.empty`` here), T <= 65536, the same bytes wherever both run; "auto" -
+    "lds" where it fits; anything but "lds" with ``avoid`` is a ``ValueError``.  Layouts and ``constraints`` as in ``design_from_logits``.
+    CUDA logits only (there is no CPU fallback); no host synchronisation."""
     mode = design_mode(gc_content=gc_content, mutations=mutations, avoid=avoid)
+    check_profile_tree(tree, mode)
     mutations = check_mutations(mutations)
     auto = check_avoid(avoid, constraints)
     name = PROFILE_ENTRIES[mode]
@@ -564,8 +632,13 @@ def design_profile_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor
     marg = torch.empty(Bn, Tn, 4, dtype=torch.float64, device=device)
     log_z, free, ent = (torch.empty(Bn, dtype=torch.float64, device=device) for _ in range(3))
     bad, miss = (torch.empty(Bn, dtype=torch.int32, device=device) for _ in range(2))
-    args = [lg, int(lg.numel()) // 4, m, cu, B, T, float(temperature), al, pa, wobble, bi, per_position, *its, marg, log_z, free, ent, bad, miss]
-    _entry_call(name, args, device)
+
+    def call(long):
+        ws = _tree_workspace("rnampnn_design_count_profile_long_workspace_bytes", B, T, its[3], device) if long else ()
+        args = [lg, int(lg.numel()) // 4, m, cu, B, T, float(temperature), al, pa, wobble, bi, per_position, *its, *ws, marg, log_z, free, ent, bad,
+                miss]
+        _entry_call(name + ("_long" if long else ""), args, device)
+    _by_tree(tree, call)
     return DesignProfile(marg, log_z, free, ent, bad, miss, mode)
 
 

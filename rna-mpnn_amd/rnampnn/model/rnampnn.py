@@ -23,7 +23,7 @@ from .. import _native
 from ..config.glob import DEFAULT_SEED, REVERSE_VOCAB
 from ..utils.data import check_prefix_mask
 from ._base import NativeModule, _prep, _ptr, _stream
-from .decode import (SCORE_OUTPUTS, argmax_recovery, check_avoid, check_distinct, check_nested, check_require, check_mutations, check_state_lengths, design_by_mode,  # noqa: F401
+from .decode import (SCORE_OUTPUTS, argmax_recovery, check_avoid, check_distinct, check_nested, check_require, check_mutations, check_state_lengths, check_profile_tree, check_tree, design_by_mode,  # noqa: F401
                      design_distinct_from_logits, design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits,
                      design_profile_from_logits,
                      letters_packed, letters_padded, sample_from_logits, score_logits)
@@ -548,7 +548,7 @@ class RNAMPNN(NativeModule):
     @torch.no_grad()
     def design(self, coords: torch.Tensor, mask: torch.Tensor, n_samples: int = 8, temperature: float = 0.1, seed: int = 0,
                T_norm: int = 0, constraints=None, states=None, state_weights=None, lengths=None, gc_content=None, distinct=None, mutations=None,
-               avoid=None, require=None, pairs=None):
+               avoid=None, require=None, pairs=None, tree: str = "lds"):
         """``sample`` plus the score of every draw against the SAME logits, with one forward: -> (seqs int8 (n_samples,B,T), -1 on
         padding; seq_nll (n_samples,B) f32).  The NLL is the model's own (temperature 1) likelihood, so designs drawn at different
         temperatures rank on one scale.  ``constraints`` (``rnampnn.utils.constraints.DesignConstraints``: fixed nucleotides, base
@@ -580,8 +580,12 @@ class RNAMPNN(NativeModule):
         and / or ``require`` UNDER the base pairs of ``constraints`` (``design_nested_from_logits``): the structure is honoured and the
         draws are exact as long as it is nested -> (seqs, seq_nll, infeasible, hits, accepted, dfa_miss, nest_miss (B,) int32 = 1 for an
         RNA whose pairs cross: it is drawn as plain ``constraints`` draw it); host-side constraints whose structure crosses, another
-        mode, another value, or neither ``avoid`` nor ``require`` are a ``ValueError`` before the forward pass."""
+        mode, another value, or neither ``avoid`` nor ``require`` are a ``ValueError`` before the forward pass.  ``tree`` ("lds", the
+        default: everything above, unchanged; "global"; "auto"): where the count tree of ``gc_content`` and ``mutations`` lives
+        (``check_tree``) - in global memory RNAs of up to 32,744 nt are drawn under a G+C window, with the same bytes wherever both homes
+        run; anything but "lds" with another mode is a ``ValueError`` before the forward pass."""
         mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require, pairs=pairs)
+        check_tree(tree, mode)
         mutations = check_mutations(mutations)
         if mode == "nested":
             require, avoid = check_nested(require, avoid, constraints), None
@@ -594,20 +598,21 @@ class RNAMPNN(NativeModule):
         if mode != "plain" or constraints is not None:
             return design_by_mode(mode, logits, mask=mask, n_samples=n_samples, temperature=temperature, seed=seed, constraints=constraints,
                                   states=states, state_weights=state_weights, gc_content=gc_content, distinct=distinct, mutations=mutations,
-                                  avoid=avoid, require=require)
+                                  avoid=avoid, require=require, tree=tree)
         seqs = sample_from_logits(logits, mask, temperature, n_samples, seed)
         return seqs, score_logits(logits, mask=mask, seqs=seqs, want=("seq_nll",))["seq_nll"]
 
     @torch.no_grad()
     def design_profile(self, coords: torch.Tensor, mask: torch.Tensor, temperature: float = 0.1, T_norm: int = 0, constraints=None,
-                       lengths=None, gc_content=None, mutations=None, avoid=None):
+                       lengths=None, gc_content=None, mutations=None, avoid=None, tree: str = "lds"):
         """What ``design`` draws FROM under the same arguments, with one eval-mode forward and one launch: the exact per-position
         marginals, log partition sums and entropy of the constrained, tempered distribution (``design_profile_from_logits``) -> a
         ``DesignProfile`` (marginals (B,T,4) f64, log_z, log_z_free, entropy (B,) f64, infeasible, miss (B,) int32, mode; ``log_mass`` =
         the log of the share of the model's mass the constraints keep).  ``constraints``, ``gc_content``, ``mutations`` and ``avoid`` as
         in ``design``; the pairings that ``design`` refuses are refused here with the same messages, before the forward pass.  ``lengths``
-        is accepted for symmetry with ``design`` and not read.  No profile is built for ``states`` or ``distinct``."""
-        design_mode(gc_content=gc_content, mutations=mutations, avoid=avoid)
+        is accepted for symmetry with ``design`` and not read.  No profile is built for ``states`` or ``distinct``.  ``tree`` as in
+        ``design``, for every profile but ``avoid``'s."""
+        check_profile_tree(tree, design_mode(gc_content=gc_content, mutations=mutations, avoid=avoid))
         check_mutations(mutations)
         check_avoid(avoid, constraints)
         was_training = self.training
@@ -617,7 +622,7 @@ class RNAMPNN(NativeModule):
         finally:
             self.train(was_training)
         return design_profile_from_logits(logits, mask=mask, temperature=temperature, constraints=constraints, gc_content=gc_content,
-                                          mutations=mutations, avoid=avoid)
+                                          mutations=mutations, avoid=avoid, tree=tree)
 
     @torch.no_grad()
     def test_step(self, batch):

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from ..config.glob import VOCAB
-from ..model.decode import (check_avoid, check_budget, check_nested, check_require, design_by_mode, design_mode, design_profile_from_logits, letters_packed, letters_padded,
+from ..model.decode import (check_avoid, check_budget, check_profile_tree, check_tree, check_nested, check_require, design_by_mode, design_mode, design_profile_from_logits, letters_packed, letters_padded,
                             sample_from_logits, score_logits)
 from .constraints import batch_constraints, crossing_pairs, mutation_references, padded_references, parse_dot_bracket
 from .data import PackedLoader, bucket_batches, fill_nan_deterministic, read_fasta
@@ -184,11 +184,12 @@ def check_nested_run(require, avoid, samples: int, profile_prefix, constraints) 
     return auto
 
 
-def profile_batch(store: dict, idx, lens, logits, cu, max_len: int, temperature: float, cons, gc_content, mutations, avoid) -> None:
-    """The design profile of one packed batch (``design_profile_from_logits``; ``mutations`` as ``design`` takes it) into ``store``:
+def profile_batch(store: dict, idx, lens, logits, cu, max_len: int, temperature: float, cons, gc_content, mutations, avoid,
+                  tree: str = "lds") -> None:
+    """The design profile of one packed batch (``design_profile_from_logits``; ``mutations`` as ``design`` takes it, ``tree`` as it does) into ``store``:
     item index -> (marginals [n][4], log_mass, entropy, infeasible, miss).  One launch, one copy per output."""
     prof = design_profile_from_logits(logits, cu_seqlens=cu, max_len=max_len, temperature=temperature, constraints=cons, gc_content=gc_content,
-                                      mutations=mutations, avoid=avoid)
+                                      mutations=mutations, avoid=avoid, tree=tree)
     marg, mass, ent = prof.marginals.cpu().tolist(), prof.log_mass.cpu().tolist(), prof.entropy.cpu().tolist()
     bad, miss = prof.infeasible.cpu().tolist(), prof.miss.cpu().tolist()
     for r, i in enumerate(idx):
@@ -208,7 +209,7 @@ def write_profile(prefix: str, ids, store: dict) -> None:
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
             wobble: bool = True, states: Optional[dict] = None, gc_content=None, distinct=None, mutations=None,
-            avoid=None, profile_prefix: Optional[str] = None, require=None, pairs=None) -> List[Tuple[str, str]]:
+            avoid=None, profile_prefix: Optional[str] = None, require=None, pairs=None, tree: str = "lds") -> List[Tuple[str, str]]:
     """Design a sequence for every structure under ``data_path`` in length-bucketed var-len batches (``forward_packed``): the tree
     read-out on the packed embedding when one is attached, else the read-out's argmax (``rnampnn_score``'s ``pred``); write ``out_csv``
     with one ``pdb_id,seq`` row per structure in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure
@@ -248,8 +249,12 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     the other modes or a profile.
     ``profile_prefix``: also write the design profile of every structure - the exact distribution the draws of the chosen mode come from
     under ``temperature`` and the constraints (``design_profile_from_logits``) - to ``PREFIX.positions.csv`` and ``PREFIX.rnas.csv``
-    (``write_profile``), with or without ``samples``.  Not built together with ``states`` or ``distinct``."""
+    (``write_profile``), with or without ``samples``.  Not built together with ``states`` or ``distinct``.
+    ``tree`` ("lds", the default: everything above, unchanged; "global"; "auto"): where the count tree of ``gc_content`` and ``mutations``
+    and of their profiles lives (``check_tree``); in global memory structures longer than the 1,017 nt a G+C window fits in LDS are
+    designed.  Anything but "lds" with another mode is a ``ValueError`` before the first forward pass."""
     mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require, pairs=pairs)
+    check_tree(tree, mode) if samples > 0 or not profile_prefix else check_profile_tree(tree, mode)
     check_profile(profile_prefix, states, distinct)
     if mode == "nested":
         require, avoid = check_nested_run(require, avoid, samples, profile_prefix, constraints), None
@@ -305,14 +310,14 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             cons = batch_constraints(constraints, [ids[i] for i in idx], lens, max_len, bias=bias, wobble=wobble, omit=omit).to_device(device)
         if profile_prefix:
             profile_batch(profiles, idx, lens, logits, cu, max_len, temperature, cons, gc_content,
-                          None if mutations is None else (padded_references(refs, idx, max_len), mutations[0], mutations[1]), avoid)
+                          None if mutations is None else (padded_references(refs, idx, max_len), mutations[0], mutations[1]), avoid, tree)
         if samples <= 0:
             continue
         draws, dnll, bad, *extras = draw_batch(
             logits, cu, max_len, samples, temperature, seed + bi, cons, mode, gc_content=gc_content, distinct=distinct, avoid=avoid, require=require,
             mutations=None if mutations is None else (padded_references(refs, idx, max_len), (mutations[0], mutations[1])),
             states=None if gs is None else [len(groups[g][1]) for g in gs],
-            state_weights=None if gs is None else [w for g in gs for w in groups[g][2]])
+            state_weights=None if gs is None else [w for g in gs for w in groups[g][2]], tree=tree)
         if not constrained and gs is None:
             bad = None                                              # the column belongs to the constrained forms
         _, cells, filled = design_columns(mode, extras, lens)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The measurement behind DESIGN.md section 9 "Constrained design", "Multi-state design", "Design under a G+C window", "Distinct designs",
-"Mutation budget", "Forbidden motifs", "Required motifs", "Motifs under a nested structure" and "Design profiles" (profiles/design_nested_kernel_stats.txt, profiles/design_dfa_kernel_stats.txt, profiles/design_profile_kernel_stats.txt, profiles/design_kernel_stats.txt, profiles/design_tied_kernel_stats.txt, profiles/design_gc_kernel_stats.txt,
+"Mutation budget", "Forbidden motifs", "Required motifs", "Motifs under a nested structure", "Design profiles" and "Count tree in global memory" (profiles/design_long_kernel_stats.txt, profiles/design_nested_kernel_stats.txt, profiles/design_dfa_kernel_stats.txt, profiles/design_profile_kernel_stats.txt, profiles/design_kernel_stats.txt, profiles/design_tied_kernel_stats.txt, profiles/design_gc_kernel_stats.txt,
 profiles/design_distinct_kernel_stats.txt, profiles/design_count_kernel_stats.txt, profiles/design_avoid_kernel_stats.txt): the C2 batch (256 RNAs x 100..140 nt), S = 8 sequences per RNA.
 usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + rnampnn_score (seq_nll): the unconstrained pair of launches
        python tools/design_probe.py design [calls=50]         rnampnn_design: free, then with a hairpin's pairs + a fixed GNRA loop per RNA
@@ -35,6 +35,14 @@ usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + r
                                                               yardstick) and rnampnn_design_nested: the same automaton without pairs (the
                                                               same work), the same automaton under a hairpin-rich nested structure on every
                                                               RNA (13 live states), and require GNRA + max_run = 3 under that structure (53)
+       python tools/design_probe.py long                      the count tree in global memory (tree="global": rnampnn_design_count_long,
+                                                              rnampnn_design_count_profile_long), nothing else: (a) the C2 batch in 5
+                                                              alternating rounds of 10 calls - rnampnn_design_gc 40..60 %, rnampnn_design_count
+                                                              (b) and the G+C profile, each through the LDS entry and through the long entry
+                                                              on the same inputs; (b) one RNA of 4,417 nt, S = 8: a G+C window of 45..60 %, a
+                                                              budget of 8 mutations and the G+C profile; (c) a padded batch of the 32 longest
+                                                              lengths of tests/data/c3_train_lengths.npy under the G+C window.  Every chunk of
+                                                              calls is logged in order ("long-calls|name|calls") for tools/kstats_design.sh
 HIP events around each loop of back-to-back calls of the Python wrappers.  Run either under `rocprofv3 --kernel-trace --stats -- python ...`
 (a run of its own) for the kernels' own times.  RNAMPNN_PROBE_ROOT: another checkout (with its library built) to take the package from -
 the `sample_score` leg uses nothing newer than rnampnn_score, so it runs on the parent commit as well."""
@@ -71,7 +79,87 @@ def timed(name, fn):
           f"output allocation included)")
 
 
-if what == "sample_score":
+def long_leg():
+    import numpy as np
+    from rnampnn.model import decode as D
+    rounds, per_round, warm = 5, 10, 3
+
+    def chunk(name, fn, calls):
+        """``calls`` back-to-back calls between two events -> us per call; the chunk is logged in execution order."""
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(calls):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        print(f"long-calls|{name}|{calls}")
+        return e0.elapsed_time(e1) * 1e3 / calls
+
+    def once(name, fn):
+        """One call outside the timing, logged like a chunk so that the order of the log stays the order of the launches."""
+        out = fn()
+        torch.cuda.synchronize()
+        print(f"long-calls|{name} (check)|1")
+        return out
+
+    def report(tag, shape, variants, times):
+        for (name, _), t in zip(variants, times):
+            print(f"{tag} {shape} S {S} {name}: {sum(t) / len(t):.2f} us per call, rounds {min(t):.2f} .. {max(t):.2f} ({len(t)} round(s), events, "
+                  f"output and workspace allocation included)")
+
+    kw = dict(n_samples=S, temperature=0.1, seed=1)
+    ref = torch.randint(0, 4, (B, T), generator=torch.Generator().manual_seed(1)).cuda()
+    sets = D.mutation_sets(ref)
+    a = [(f"{entry}, {tree}", fn) for entry, make in (
+        ("gc 40..60 %", lambda tree: lambda: D.design_gc_from_logits(logits, mask=m, gc_content=(0.4, 0.6), tree=tree, **kw)),
+        ("count (b) 0..8 mutations cap 8", lambda tree: lambda: D.design_count_from_logits(logits, mask=m, counted=sets, window=(0, 8), tree=tree, **kw)),
+        ("profile G+C 40..60 %", lambda tree: lambda: D.design_profile_from_logits(logits, mask=m, temperature=0.1, gc_content=(0.4, 0.6), tree=tree)))
+         for tree, fn in (("lds", make("lds")), ("global", make("global")))]
+    for name, fn in a:
+        chunk(name + " (warm)", fn, warm)
+    times = [[] for _ in a]
+    for _ in range(rounds):
+        for v, (name, fn) in enumerate(a):
+            times[v].append(chunk(name, fn, per_round))
+    report("(a)", f"B {B} T {T} nt {int(mask.sum())}", a, times)
+    for (n0, f0), (n1, f1) in zip(a[0::2], a[1::2]):
+        x, y = once(n0, f0), once(n1, f1)
+        print(f"{n1} against {n0}: " + ", ".join(f"{k} equal {bool((p == q).all())}" for k, p, q in zip(
+            ("seqs / marginals", "seq_nll / log_z", "infeasible / log_z_free", "count / entropy", "miss / infeasible", "- / miss"), x, y)))
+    # (b) one ribosomal-size RNA
+    n1 = 4417
+    lg1 = 3.0 * torch.randn(1, n1, 4, generator=torch.Generator().manual_seed(2)).cuda()
+    m1 = torch.ones(1, n1, device="cuda")
+    ref1 = torch.randint(0, 4, (1, n1), generator=torch.Generator().manual_seed(3)).cuda()
+    b = [("gc 45..60 %, 4417 nt, global", lambda: D.design_gc_from_logits(lg1, mask=m1, gc_content=(0.45, 0.60), tree="global", **kw)),
+         ("mutations 0..8 cap 8, 4417 nt, global", lambda: D.design_mutations_from_logits(lg1, (ref1, (0, 8)), mask=m1, tree="global", **kw)),
+         ("profile G+C 45..60 %, 4417 nt, global", lambda: D.design_profile_from_logits(lg1, mask=m1, temperature=0.1, gc_content=(0.45, 0.60), tree="global"))]
+    for name, fn in b:
+        chunk(name + " (warm)", fn, 2)
+    report("(b)", f"B 1 T {n1}", b, [[chunk(name, fn, 10)] for name, fn in b])
+    out, mut = once(b[0][0], b[0][1]), once(b[1][0], b[1][1])
+    print(f"(b) G+C of the 4,417-nt draws {out[3].min().item() / n1:.4f} .. {out[3].max().item() / n1:.4f}, gc_miss {out[4].tolist()}; "
+          f"mutations {mut[3].tolist()}; workspace {int(D._native.lib().rnampnn_design_count_long_workspace_bytes(1, n1, n1))} / "
+          f"{int(D._native.lib().rnampnn_design_count_long_workspace_bytes(1, n1, 8))} bytes uncapped / cap 8")
+    # (c) the 32 longest RNAs of the training set, one padded batch
+    lens32 = sorted(int(v) for v in np.load(os.path.join(REPO, "tests", "data", "c3_train_lengths.npy")))[-32:]
+    m32 = torch.zeros(32, max(lens32))
+    for r, n in enumerate(lens32):
+        m32[r, :n] = 1
+    m32 = m32.cuda()
+    lg32 = 3.0 * torch.randn(32, max(lens32), 4, generator=torch.Generator().manual_seed(4)).cuda() * m32[..., None]
+    c = [("gc 45..60 %, 32 longest, global", lambda: D.design_gc_from_logits(lg32, mask=m32, gc_content=(0.45, 0.60), tree="global", **kw))]
+    chunk(c[0][0] + " (warm)", c[0][1], 1)
+    report("(c)", f"B 32 T {max(lens32)} nt {sum(lens32)} (lengths {lens32[0]} .. {lens32[-1]})", c, [[chunk(c[0][0], c[0][1], 5)]])
+    out = once(c[0][0], c[0][1])
+    frac = out[3].double() / m32.sum(dim=1).double()
+    print(f"(c) G+C of the draws {float(frac.min()):.4f} .. {float(frac.max()):.4f}, gc_miss total {int(out[4].sum())}, workspace "
+          f"{int(D._native.lib().rnampnn_design_count_long_workspace_bytes(32, max(lens32), max(lens32)))} bytes")
+
+
+if what == "long":
+    long_leg()
+elif what == "sample_score":
     def two_launches():
         seqs = M.sample_from_logits(logits, m, 0.1, S, seed=1)
         return seqs, M.score_logits(logits, mask=m, seqs=seqs, want=("seq_nll",))["seq_nll"]

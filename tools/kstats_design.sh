@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/design_probe.py under rocprofv3 --kernel-trace --stats, each leg in a run of its own.  usage: tools/kstats_design.sh <outdir> [leg ...]
-# (outdir: a git-ignored place such as build/design_stats; legs: sample_score design tied gc distinct count avoid profile dfa nested, the first four by default)
+# (outdir: a git-ignored place such as build/design_stats; legs: sample_score design tied gc distinct count avoid profile dfa nested long, the first four by default)
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "${1:?usage: tools/kstats_design.sh <outdir> [leg ...]}" && OUT=$(cd "$1" && pwd) || exit 1
 shift
@@ -15,7 +15,7 @@ import csv, glob
 f = sorted(glob.glob("$OUT/$name/*/*kernel_stats.csv"))[-1]
 rows = list(csv.DictReader(open(f)))
 print(f"-- $name: {len(rows)} kernel names, {sum(float(r['TotalDurationNs']) for r in rows) / 1e6:.2f} ms of kernel time")
-for r in rows[:8]:
+for r in rows[:16 if "$name" == "long" else 8]:
     print(f"{r['Name'][:72]:72s} n {int(r['Calls']):5d} avg {float(r['AverageNs'])/1e3:8.2f} us min {float(r['MinNs'])/1e3:8.2f} max {float(r['MaxNs'])/1e3:8.2f} {float(r['Percentage']):5.1f}%")
 # k_design by leg of the probe: launches in time order, 55 without constraints, then 55 + 1 with them
 t = sorted(glob.glob("$OUT/$name/*/*kernel_trace.csv"))[-1]
@@ -45,6 +45,49 @@ dfa = launches(lambda n: 'k_design_dfa' in n)
 # the "nested" leg: the same rounds - k_design_dfa max_run 3 with every live state accepting (1 variant: the yardstick of the same run) and
 # k_design_nested on the same automaton without pairs / under the hairpin-rich structure / require GNRA + max_run 3 under it (3 variants)
 ns = launches(lambda n: 'k_design_nested' in n)
+# the "long" leg: every call of a long entry starts with a k_ct_long_leaves launch, so the trace splits into calls; the probe's log names the
+# chunks of calls in order.  Per chunk name: the mean per call of the inside pass (level 1 + the level launches), of the walk
+# (k_design_count_long) or of the outside pass and the leaves (k_pf_long_*), and their number of launches; the LDS entries by name.
+if "$name" == "long":
+    rows_t = sorted(((int(r['Start_Timestamp']), int(r['End_Timestamp']) - int(r['Start_Timestamp']), r['Kernel_Name']) for r in csv.DictReader(open(t))))
+    calls, lds = [], {}
+    for _, dur, kname in rows_t:
+        if 'k_ct_long_leaves' in kname:
+            calls.append(dict(inside=0.0, walk=0.0, outside=0.0, leaves=0.0, n=0))
+        part = ('inside' if 'k_ct_long' in kname else 'walk' if 'k_design_count_long' in kname else 'leaves' if 'k_pf_long_leaves' in kname
+                else 'outside' if 'k_pf_long' in kname else None)
+        if part and calls:
+            calls[-1][part] += dur / 1e3
+            calls[-1]['n'] += 1
+        for short in ('k_design_gc', 'k_design_count_profile', 'k_design_count'):
+            if part is None and short in kname:
+                lds.setdefault(short, []).append(dur / 1e3)
+                break
+    chunks = [line.strip().split('|')[1:] for line in open("$OUT/$name.log") if line.startswith('long-calls|')]
+    at, by_name, order = 0, {}, []
+    for cname, n in chunks:
+        n = int(n)
+        if ', lds' in cname:
+            continue                                                # an LDS entry: one launch, reported by kernel name below
+        if cname not in by_name:
+            by_name[cname] = []
+            order.append(cname)
+        by_name[cname] += calls[at:at + n]
+        at += n
+    print(f"long: {len(calls)} calls of a long entry in the trace, {at} in the probe's log")
+    for cname in order:
+        if '(warm)' in cname or '(check)' in cname:
+            continue
+        cs = by_name[cname]
+        mean = lambda k: sum(c[k] for c in cs) / len(cs)
+        tail = (f"walk {mean('walk'):9.2f} us" if mean('walk') else f"root + outside pass {mean('outside'):9.2f} us, leaves {mean('leaves'):9.2f} us")
+        print(f"long, {cname}: {len(cs)} calls x {cs[0]['n']} launches, inside pass {mean('inside'):9.2f} us, {tail}, kernel time per call "
+              f"{mean('inside') + mean('walk') + mean('outside') + mean('leaves'):9.2f} us")
+    for short, v in lds.items():
+        body = sorted(v[3:])
+        print(f"{short} (the LDS entry of the same run, C2, 3 warm launches dropped): {len(body)} launches, mean {sum(body) / len(body):.2f} us "
+              f"({body[0]:.2f} .. {body[-1]:.2f}, median {body[len(body) // 2]:.2f})")
+    raise SystemExit(0)
 def by_round(seq, variants, v):
     body = seq[3 * variants:]
     return [[x[1] / 1e3 for x in body[10 * (variants * r + v):10 * (variants * r + v) + 10]] for r in range(5)]
