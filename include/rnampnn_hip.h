@@ -560,6 +560,72 @@ int rnampnn_design_dfa(const float* logits, int64_t n_rows, const float* mask, c
                        const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position,
                        const uint8_t* delta, const uint8_t* kind, int32_t n_states, void* workspace, size_t workspace_bytes,
                        int8_t* seqs, float* seq_nll, int32_t* infeasible, int32_t* hits, int32_t* accepted, int32_t* dfa_miss, void* stream);
+/* Design with motifs UNDER A COUNT WINDOW in ONE launch (csrc/design_dfa_count.hip): the draws of rnampnn_design, conditioned EXACTLY on
+ * BOTH the sequence being accepted by the automaton of rnampnn_design_dfa AND the count of rnampnn_design_count lying in its window - no
+ * G-quadruplex run, no restriction site and a primer word with G+C between 45 % and 60 %; at most 6 mutations and no GAAUUC.  The count
+ * joins the automaton's chain as a third index.  The arguments are those of rnampnn_design up to bias_per_position, then
+ *   delta, kind (HOST), n_states                    as rnampnn_design_dfa's
+ *   counted, count_lo, count_hi, count_cap          as rnampnn_design_count's; cap = min(count_cap, T) and K = min(cap, n_b) below
+ *   workspace, workspace_bytes                      device memory, 8-byte aligned, at least 8 B T L (cap + 1) bytes, L the live states.  It
+ *                                                   holds the table l_t(a, k) as [b][t][live column][k], k = 0 .. cap, and nothing else; its
+ *                                                   contents before the call do not matter (every entry that is read was written by the same
+ *                                                   launch before), after it they are unspecified.
+ *                                                   rnampnn_design_dfa_count_workspace_bytes(B, T, L, count_cap) returns that size, and 0 when
+ *                                                   an argument is <= 0; a call with cap 0 (nothing may count) needs the bytes of ONE slab
+ *                                                   per position, 8 B T L, which the size at count_cap = 1 covers.  The table grows with
+ *                                                   the cap: about 33 MB at (B = 256, T = 140, L = 13) with a budget of 8, about 525 MB with
+ *                                                   a G+C window (cap = T) - the price of a draw that is exact in both conditions
+ * and the outputs, each nullable, are those of rnampnn_design plus
+ *   hits, accepted (S,B) i32   as rnampnn_design_dfa's, of what was written
+ *   count (S,B) i32            the sum over the ids written for that draw of bit(counted[b,t], id_t)
+ *   dfa_miss (B) i32           1 when no admitted sequence of RNA b is accepted with a count in 0 .. K, else 0
+ *   count_miss (B) i32         0 when a count of the window is reachable (and when dfa_miss), else the distance from the window to the target
+ *   log_z (B) f64              the log partition sum of what the draws come from: the LSE over the window's counts of root(k), root(target)
+ *                              when a target is used, -inf when dfa_miss
+ * Taken word for word from rnampnn_design_dfa: extent, masks, bias, temperature, `allowed`, seed_dev, "an empty mask is drawn free and counts 1
+ * in `infeasible`", z_t(c) in fp64, the LSE of four terms in class order, the weights and SELECT of a position, u24(seed, s, b, t), live and
+ * dead states (a delta entry >= A is read as dead) and the refusal of a non-null `partner` (RNAMPNN_ERR_UNSUPPORTED, for the same reason).
+ * From rnampnn_design_count: bit(counted[b,t], c), the clamping of lo and hi to [0, K] followed by hi = max(hi, lo), SELECT over counts and
+ * RNAMPNN_DESIGN_GC_SALT.
+ *   Backward.  l_n(a, k) = 0 for a live accepting a and k = 0, -inf otherwise.  For t = n-1 .. 0, a live a and k = 0 .. K:
+ *     l_t(a, k) = LSE over the classes c in class order of z_t(c) + l_{t+1}(delta(a,c), k - d_t(c)), d_t(c) = bit(counted_t, c); a cell is
+ *     admitted iff m_t has c, delta(a,c) is live and k - d_t(c) >= 0.  An entry with k > n - t is -inf (a suffix of n - t positions counts no
+ *     more) and may be written without arithmetic.
+ *   Total.  root(k) = l_0(0, k).  If a count of lo .. hi has a finite root, sample s draws K_s = SELECT(lo .. hi in count order, root,
+ *     u24(seed ^ SALT, s, b, 0)).  Otherwise, if a count of 0 .. K has one, the target is the nearest such count, the lower one on a tie,
+ *     count_miss its distance to the window, and every sample holds the target.  Otherwise dfa_miss = 1, count_miss = 0 and every position
+ *     is drawn as rnampnn_design draws an unpaired position in fp64 with u24(seed, s, b, t), ignoring both conditions.  hits, accepted and
+ *     count always report what was written.  An RNA of length 0 is feasible iff state 0 accepts.
+ *   Walk.  a = 0, r = K_s.  At t the admitted cells are those above (with k = r) that also have l_{t+1}(delta(a,c), r - d_t(c)) > -inf - at
+ *     the last position that value is 0 iff delta(a,c) accepts and r - d_t(c) = 0; c = SELECT over z_t(c) + that value with u24(seed, s, b, t);
+ *     a <- delta(a,c), r <- r - d_t(c).
+ *   Anchors.  With nothing counted (counted = 0 everywhere, at any count_cap, 0 included) and the window (0, 0), seqs, seq_nll, infeasible,
+ *     hits, accepted and dfa_miss are the bytes of rnampnn_design_dfa on the same automaton; count and count_miss are 0.  (A class that
+ *     counts is not admitted at count_cap = 0: that call conditions on "none of them occurs".)  The outputs of an RNA do not
+ *     depend on count_cap as long as its window lies within the cap and a count of the window is reachable.
+ * One 256-thread workgroup per RNA.  The items (live column, k) of step t, L (K + 1) of them, are dealt flat over the threads, each one LSE
+ * over four entries of the slab of t + 1; that slab is read from two slabs in LDS when 16 L (cap + 1) bytes fit beside the rest, otherwise
+ * from the workspace (written by the same workgroup: a barrier orders them) - the same four-term LSE either way, so the two homes give the
+ * same bytes; every entry goes to the workspace, from which 256 samples at a time, one lane each, read the four candidates of their walk.
+ * Dynamic LDS without the slabs:
+ *       bytes(T) = 32 T + 32 ceil(T / 16) + 1024 (ceil(T / 16) | 1) + 4,192
+ *     (the fp64 rows, the masks and the counted sets, 2 bits per position for 256 samples; the automaton and the scratch): 33,856 at
+ *     T = 300.  RNAMPNN_ERR_UNSUPPORTED when that exceeds 160 KiB = 163,840 bytes, for every automaton and every cap alike: T <= 1616
+ *     (162,560 bytes); the message names the bytes, the limit and that T.  LDS bounds neither L x K nor T x L.
+ * No atomics, no runtime fill / copy node, no host synchronisation: two calls give identical bytes, the call can sit inside a captured
+ * graph, and a draw is a pure function of (seed, s, b), the rows of RNA b, the automaton and the RNA's counted, lo and hi - independent of
+ * B, T, S, the layout and the workspace's previous contents; the first S' of S slots are the call with S'.
+ * RNAMPNN_ERR_BAD_ARG, before anything is launched: the cases of rnampnn_design_dfa; null counted, count_lo or count_hi; count_cap < 0; a
+ * null, misaligned or too small workspace (the message names the bytes needed).  Then the partner check, then the LDS check; then, with
+ * every output null, the call returns RNAMPNN_OK without a launch. */
+size_t rnampnn_design_dfa_count_workspace_bytes(int32_t B, int32_t T, int32_t n_live, int32_t count_cap);
+int rnampnn_design_dfa_count(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
+                             float temperature, int32_t S, uint64_t seed, const uint64_t* seed_dev, const uint8_t* allowed,
+                             const int32_t* partner, int32_t wobble, const float* bias, int32_t bias_per_position,
+                             const uint8_t* delta, const uint8_t* kind, int32_t n_states, const uint8_t* counted,
+                             const int32_t* count_lo, const int32_t* count_hi, int32_t count_cap, void* workspace, size_t workspace_bytes,
+                             int8_t* seqs, float* seq_nll, int32_t* infeasible, int32_t* hits, int32_t* accepted, int32_t* count,
+                             int32_t* dfa_miss, int32_t* count_miss, double* log_z, void* stream);
 /* Design with motifs UNDER BASE PAIRS in ONE launch (csrc/design_nested.hip): the draws of rnampnn_design on a NESTED (pseudoknot-free)
  * structure, conditioned EXACTLY on the sequence being accepted by the automaton of rnampnn_design_dfa.  A nested structure is a tree, and
  * on a tree the automaton is carried as a transfer table per enclosed interval (state before its first position -> state after its last):

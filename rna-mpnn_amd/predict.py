@@ -80,6 +80,17 @@ drawn exactly from the model's distribution conditioned on both.  The structures
 its ids, before the checkpoint is opened.  The designs CSV gains the columns ``motif_hits``, ``required_found``, ``require_miss`` and
 ``nest_miss``.  At most 64 live automaton states; not built together with the other modes or ``--profile-out``.
 
+    python rna-mpnn_amd/predict.py --ckpt Final.pt --data DIR --samples 8 --combine chain --avoid GGGG,GAAUUC --max-run 3 --require GNRA --gc-content 0.45:0.60
+    python rna-mpnn_amd/predict.py --ckpt Final.pt --data DIR --samples 8 --combine chain --avoid GAAUUC --max-mutations 6 [--min-mutations 2] [--mutate-from parents.fasta]
+
+Motifs under a count window (``rnampnn_design_dfa_count``, both families): ``--combine chain`` lifts the refusal of ``--avoid`` /
+``--max-run`` / ``--require`` together with ``--gc-content`` or ``--max-mutations``: every draw holds the motif conditions AND its G+C
+content lies in the window (or it differs from its reference within the budget), drawn exactly from the model's distribution conditioned on
+both - an oligo to order, not a filtered sample.  The designs CSV gains the columns ``motif_hits``, ``required_found``, ``require_miss`` and
+then ``gc_count``, ``gc_miss`` (absolute counts) or ``mutations``, ``mut_miss``.  Needs a motif flag and exactly one of the two counts; not
+built together with ``--states``, ``--distinct``, ``--pairs``, ``--tree global`` / ``auto``, ``--profile-out`` or a ``structure`` in
+``--constraints``; all of that is refused before the checkpoint is opened.
+
     python rna-mpnn_amd/predict.py --ckpt Final.pt --data DIR --profile-out PREFIX [--gc-content .. | --max-mutations .. | --avoid ..] [--samples 8]
 
 Design profiles (``rnampnn_design_count_profile`` / ``rnampnn_design_avoid_profile``, both families): what the draws of the chosen mode come
@@ -134,6 +145,8 @@ def parse(argv=None):
                                                     "(AUCG, T = U, IUPAC codes); usable with --avoid / --max-run")
     ap.add_argument("--pairs", default=None, choices=("nested",),
                     help="nested: --avoid / --max-run / --require hold UNDER the structures of --constraints (which must be free of pseudoknots)")
+    ap.add_argument("--combine", default=None, choices=("chain",),
+                    help="chain: --avoid / --max-run / --require hold TOGETHER with --gc-content or --max-mutations, exactly in both")
     ap.add_argument("--profile-out", default=None, help="PREFIX: write the exact distribution the draws come from to PREFIX.positions.csv "
                                                         "(per-position marginals) and PREFIX.rnas.csv (log_mass, entropy)")
     return ap.parse_args(argv)
@@ -268,6 +281,34 @@ def nested_option(args) -> dict:
     return dict(pairs="nested", require=auto)
 
 
+def chain_option(args) -> dict:
+    """The ``combine`` and ``require`` keywords of ``predict`` from ``--combine chain`` with ``--avoid`` / ``--max-run`` / ``--require``:
+    one automaton of all of them, built (and refused) before the model is loaded; empty without ``--combine``.  The count comes from
+    ``--gc-content`` or ``--max-mutations`` through their own options.  ``ValueError`` naming the flags with ``--profile-out``, ``--states``,
+    ``--distinct``, ``--pairs`` or ``--tree global`` / ``auto``, without a motif flag, with both counts or neither, without ``--samples``,
+    and - naming the ids - for a ``--constraints`` table that holds a structure."""
+    if args.combine is None:
+        return {}
+    for flag, value in (("--profile-out", args.profile_out), ("--states", args.states), ("--distinct", args.distinct), ("--pairs", args.pairs),
+                        ("--tree", None if args.tree in (None, "lds") else args.tree)):
+        if value is not None:
+            raise ValueError(f"--combine chain together with {flag} is not built: the chain over (position, automaton state, count) conditions "
+                             "plain single-state designs on the motifs and one count, and no profile is built for it")
+    if args.avoid is None and args.max_run is None and args.require is None:
+        raise ValueError("--combine chain needs --avoid, --max-run or --require: a plain --gc-content or --max-mutations needs no chain")
+    if (args.gc_content is None) == (args.max_mutations is None):
+        raise ValueError("--combine chain needs exactly one of --gc-content and --max-mutations: two counts at once are not built")
+    if args.samples <= 0:
+        raise ValueError("--combine chain needs --samples N > 0")
+    from rnampnn.utils.constraints import read_constraints_csv
+    from rnampnn.utils.motifs import as_nested_automaton
+    from rnampnn.utils.predict import check_chain_run
+    split = lambda text: [m for m in (text or "").split(",") if m.strip()]
+    auto = as_nested_automaton(split(args.require) if args.require is not None else None, split(args.avoid), args.max_run)
+    check_chain_run(auto, None, args.samples, None, read_constraints_csv(args.constraints) if args.constraints else None)
+    return dict(combine="chain", require=auto)
+
+
 def profile_option(args) -> dict:
     """The ``profile_prefix`` keyword of ``predict`` from ``--profile-out``; empty without the flag.  ``ValueError`` naming the flags with
     ``--states`` or ``--distinct``."""
@@ -290,7 +331,8 @@ def checkpoint_family(path: str) -> str:
 
 
 def run(args, log=print):
-    nested = nested_option(args)                                   # --pairs nested takes the motif flags into its own automaton; a pseudoknot fails here
+    nested = chain_option(args)                                    # --combine chain takes the motif flags into its own automaton, beside one count
+    nested = nested or nested_option(args)                         # --pairs nested does the same under base pairs; a pseudoknot fails here
     require = nested or require_option(args)                       # refused with every other mode and --profile-out, before the model is loaded
     profile = profile_option(args)                                 # refused with --states / --distinct here, before the model is loaded
     avoid = {} if nested else avoid_option(args)                   # a combination that is not built fails here, before the model is loaded

@@ -33,7 +33,7 @@ import torch.nn.functional as F
 
 from .. import _native
 from rnampnn.model._base import _prep, _stream
-from rnampnn.model.decode import (check_avoid, check_distinct, check_mutations, check_nested, check_require, check_state_lengths, check_profile_tree, check_tree, design_by_mode, design_distinct_from_logits,  # noqa: F401
+from rnampnn.model.decode import (check_avoid, check_chain, check_distinct, check_mutations, check_nested, check_require, check_state_lengths, check_profile_tree, check_tree, design_by_mode, design_distinct_from_logits,  # noqa: F401
                                   design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits, design_profile_from_logits,
                                   letters_packed,
                                   score_logits)
@@ -431,7 +431,7 @@ class RNAModel(nn.Module):
     @torch.no_grad()
     def design(self, X, mask, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None, lengths=None, states=None,
                state_weights=None, gc_content=None, distinct=None, mutations=None, avoid=None, require=None,
-               pairs=None, tree: str = "lds"):
+               pairs=None, tree: str = "lds", combine=None):
         """``n_samples`` sequences per RNA drawn from this model's read-out at ``temperature`` and scored, in one ``rnampnn_design`` launch
         on the packed logits -> (seqs int8 (n_samples,B,T), -1 on padding; seq_nll (n_samples,B) f32, the model's own temperature-1 NLL of
         each draw; infeasible (B,) int32).  ``constraints``: a ``rnampnn.utils.constraints.DesignConstraints`` (fixed nucleotides, base
@@ -460,11 +460,17 @@ class RNAModel(nn.Module):
         mode, another value, or neither ``avoid`` nor ``require`` are a ``ValueError`` before the forward pass.  ``tree`` ("lds", the
         default: everything above, unchanged; "global"; "auto"): where the count tree of ``gc_content`` and ``mutations`` lives
         (``check_tree``) - in global memory RNAs of up to 32,744 nt are drawn under a G+C window, with the same bytes wherever both homes
-        run; anything but "lds" with another mode is a ``ValueError`` before the forward pass."""
-        mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require, pairs=pairs)
+        run; anything but "lds" with another mode is a ``ValueError`` before the forward pass.  ``combine="chain"`` (``None`` is
+        everything above, unchanged): ``avoid`` and / or ``require`` TOGETHER with ``gc_content`` or ``mutations``
+        (``design_dfa_count_from_logits``), exact in both conditions at once -> (seqs, seq_nll, infeasible, hits, accepted, count
+        (n_samples,B) int32, dfa_miss (B,) int32, count_miss (B,) int32, log_z (B,) f64); the refusals are ``RNAMPNN.design``'s, before
+        the forward pass."""
+        mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require, pairs=pairs, combine=combine, tree=tree)
         check_tree(tree, mode)
         mutations = check_mutations(mutations)
-        if mode == "nested":
+        if mode == "chain":
+            require, avoid = check_chain(constraints, require, avoid), None
+        elif mode == "nested":
             require, avoid = check_nested(require, avoid, constraints), None
         else:
             require = check_require(require, avoid, constraints)

@@ -7,7 +7,7 @@ from typing import List, Optional, Tuple
 from rnampnn.model.decode import check_avoid, check_budget, check_profile_tree, check_tree, design_by_mode, design_mode, letters_padded, score_logits
 from rnampnn.utils.constraints import batch_constraints, mutation_references, padded_references
 from rnampnn.utils.data import bucket_batches
-from rnampnn.utils.predict import check_nested_run, check_profile, check_require_run, design_columns, profile_batch, write_csv, write_profile
+from rnampnn.utils.predict import check_chain_run, check_nested_run, check_profile, check_require_run, design_columns, profile_batch, write_csv, write_profile
 
 from .data import load_rna_dir, padded_loader
 
@@ -15,7 +15,7 @@ from .data import load_rna_dir, padded_loader
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
             wobble: bool = True, gc_content=None, distinct=None, mutations=None, avoid=None,
-            profile_prefix: Optional[str] = None, require=None, pairs=None, tree: str = "lds") -> List[Tuple[str, str]]:
+            profile_prefix: Optional[str] = None, require=None, pairs=None, tree: str = "lds", combine=None) -> List[Tuple[str, str]]:
     """Read ``data_path`` (``coords/<id>.npy`` + ``seqs/<id>.fasta``), design a sequence for every structure in length-bucketed batches
     (``RNAModel.predict_sequences``: the tree read-out when one is attached, else the read-out's argmax) and write ``out_csv`` with one
     ``pdb_id,seq`` row per input in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure at
@@ -40,11 +40,16 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     ``profile_prefix``: also write the design profile of every structure (``design_profile_from_logits``: the exact distribution the
     draws of the chosen mode come from) to ``PREFIX.positions.csv`` and ``PREFIX.rnas.csv``, with or without ``samples``.  Not built
     together with ``distinct``.  ``tree`` ("lds", the default; "global"; "auto"): where the count tree of ``gc_content`` and ``mutations``
-    and of their profiles lives (``check_tree``); anything but "lds" with another mode is a ``ValueError`` before the first forward pass."""
-    mode = design_mode(None, gc_content, distinct, mutations, avoid, require=require, pairs=pairs)
+    and of their profiles lives (``check_tree``); anything but "lds" with another mode is a ``ValueError`` before the first forward pass.
+    ``combine="chain"``: ``avoid`` and / or ``require`` TOGETHER with ``gc_content`` or ``mutations`` (``rnampnn_design_dfa_count``), as in
+    ``rnampnn.utils.predict.predict``: the same columns and the same refusals."""
+    mode = design_mode(None, gc_content, distinct, mutations, avoid, require=require, pairs=pairs, combine=combine, tree=tree)
     check_tree(tree, mode) if samples > 0 or not profile_prefix else check_profile_tree(tree, mode)
     check_profile(profile_prefix, None, distinct)
-    if mode == "nested":
+    count = "gc_content" if gc_content is not None else "mutations"     # (what the chain counts: it names its columns)
+    if mode == "chain":
+        require, avoid = check_chain_run(require, avoid, samples, profile_prefix, constraints), None
+    elif mode == "nested":
         require, avoid = check_nested_run(require, avoid, samples, profile_prefix, constraints), None
     else:
         require = check_require_run(require, avoid, samples, profile_prefix, constraints)
@@ -86,7 +91,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
                 mode, logits, cu_seqlens=cu, max_len=T, n_samples=samples, temperature=temperature, seed=seed + bi,
                 constraints=cons.to_device(device), gc_content=gc_content, distinct=distinct, avoid=avoid, require=require,
                 mutations=None if mutations is None else (padded_references(refs, idx, T), (mutations[0], mutations[1])), tree=tree)
-            _, cells, filled = design_columns(mode, extras, lens)
+            _, cells, filled = design_columns(mode, extras, lens, count)
             match = score_logits(logits, cu_seqlens=cu, labels=S, seqs=draws, want=("seq_match",))["seq_match"].cpu().tolist()
             nll, bad = nll.cpu().tolist(), bad.cpu().tolist()
             for s in range(samples):
@@ -99,6 +104,6 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     if profile_prefix:
         write_profile(profile_prefix, [it[0] for it in items], profiles)
     if samples > 0:
-        write_csv(designs_csv, "pdb_id,sample,seq,nll_per_nt,recovery,infeasible" + design_columns(mode)[0],
+        write_csv(designs_csv, "pdb_id,sample,seq,nll_per_nt,recovery,infeasible" + design_columns(mode, count=count)[0],
                   [(it[0],) + row for i, it in enumerate(items) for row in designs[i]])
     return rows

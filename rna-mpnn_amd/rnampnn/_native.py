@@ -93,6 +93,9 @@ SYMBOLS = {
     "rnampnn_design_dfa_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
     "rnampnn_design_dfa": (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I32, _F, _I32, C.c_uint64, _VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, _I32, _VP, _SZ,
                                      _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "rnampnn_design_dfa_count_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32]),
+    "rnampnn_design_dfa_count": (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I32, _F, _I32, C.c_uint64, _VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, _I32,
+                                           _VP, _VP, _VP, _I32, _VP, _SZ, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rnampnn_design_nested_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
     "rnampnn_design_nested": (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I32, _F, _I32, C.c_uint64, _VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, _I32, _VP,
                                         _SZ, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),

@@ -1,7 +1,7 @@
 """Decoding from logits, as free functions over the C ABI's decode family: argmax + recovery (``rnampnn_argmax_recovery``), free draws
 (``rnampnn_sample``), scores (``rnampnn_score``), constrained and multi-state design (``rnampnn_design``, ``rnampnn_design_tied``), design
 under a G+C content window (``rnampnn_design_gc``), design within a count window / a mutation budget (``rnampnn_design_count``), distinct
-designs (``rnampnn_design_distinct``), design that avoids forbidden motifs (``rnampnn_design_avoid``), design with required motifs (``rnampnn_design_dfa``), motifs under a nested structure (``rnampnn_design_nested``), the distribution those draws come from (``rnampnn_design_count_profile``, ``rnampnn_design_avoid_profile``), the count tree in global memory for long RNAs (``tree=``: ``rnampnn_design_count_long``, ``rnampnn_design_count_profile_long``), the choice between them (``design_mode``, ``design_by_mode``) and the letters of class ids.  Needs the library and ``_base`` only, so both model packages import
+designs (``rnampnn_design_distinct``), design that avoids forbidden motifs (``rnampnn_design_avoid``), design with required motifs (``rnampnn_design_dfa``), motifs under a nested structure (``rnampnn_design_nested``), motifs under a count window (``combine="chain"``: ``rnampnn_design_dfa_count``), the distribution those draws come from (``rnampnn_design_count_profile``, ``rnampnn_design_avoid_profile``), the count tree in global memory for long RNAs (``tree=``: ``rnampnn_design_count_long``, ``rnampnn_design_count_profile_long``), the choice between them (``design_mode``, ``design_by_mode``) and the letters of class ids.  Needs the library and ``_base`` only, so both model packages import
 it at module level."""
 from __future__ import annotations
 
@@ -501,14 +501,103 @@ DESIGN_MODES = (("avoid", ("states", "gc_content", "distinct", "mutations"),
                 ("states", (), ""))
 
 
-def design_mode(states=None, gc_content=None, distinct=None, mutations=None, avoid=None, require=None, pairs=None) -> str:
+def check_chain(constraints=None, require=None, avoid=None, max_run=None):
+    """``design(..., combine="chain", require=..., avoid=..., max_run=...)`` -> the ``DesignAutomaton`` of ``rnampnn_design_dfa_count``
+    (``as_nested_automaton``: ``require`` with ``avoid`` absorbed, or ``avoid`` / ``max_run`` alone with every live state accepting).
+    ``ValueError`` when the constraints carry base pairs - the one ``check_require`` raises with a ``require``, else ``check_avoid``'s -
+    and for what the automaton's constructors refuse.  Touches no device, so a caller refuses before its forward pass."""
+    from ..utils.motifs import as_nested_automaton
+    if require is not None:
+        return check_require(require, avoid, constraints, max_run)
+    if avoid is None and max_run is None:
+        return None
+    check_avoid(avoid if avoid is not None else (), constraints, max_run)
+    return as_nested_automaton(None, avoid, max_run)
+
+
+def design_dfa_count_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
+                                 max_len: Optional[int] = None, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None,
+                                 require=None, avoid=None, max_run=None, gc_content=None, mutations=None):
+    """``rnampnn_design_dfa_count`` (include/rnampnn_hip.h): the draws of ``design_from_logits`` conditioned exactly on BOTH the motifs
+    (every motif of ``require`` occurs, none of ``avoid`` does, no run longer than ``max_run``) AND one count - the G+C window
+    ``gc_content`` (as ``design_gc_from_logits`` takes it) or the budget ``mutations`` (as ``check_mutations`` returns it: (reference,
+    (min, max))) - in one launch -> (seqs, seq_nll, infeasible, hits (S,B) int32, accepted (S,B) int32, count (S,B) int32 = the C or G
+    ids / the mutations of each draw, dfa_miss (B,) int32 = 1 when no admitted sequence holds the motifs at any count the cap allows: the
+    RNA is then drawn as ``design_from_logits`` draws it, count_miss (B,) int32 = 0 when the window is reachable together with the motifs,
+    else its distance to the nearest reachable count, which the draws then hold, log_z (B,) f64 = the log partition sum of what the draws
+    come from).  The automaton is ``check_chain``'s (up to 256 states); the count side is what ``design_gc_from_logits`` /
+    ``design_mutations_from_logits`` pass: C|G counted everywhere with a cap of T, or ``mutation_sets(reference)`` with the budget as
+    window and cap.  Base pairs are a ``ValueError``.  The table lives in a workspace in global memory (``torch.empty`` here,
+    8 B T L (cap + 1) bytes at L live states: it grows with the cap, the price of a draw that is exact in both conditions); T <= 1616 for
+    every automaton and cap, beyond which the library raises ``NotImplementedError`` naming the limit.  Layouts as in
+    ``design_from_logits``.  CUDA logits only (there is no CPU fallback); no host synchronisation."""
+    if (gc_content is None) == (mutations is None):
+        raise ValueError("exactly one of gc_content and mutations conditions the count (two counts at once are not built)")
+    auto = check_chain(constraints, require, avoid, max_run)
+    if auto is None:
+        raise ValueError("require, avoid or max_run is required: a DesignAutomaton or motif strings (require=['GNRA'], avoid=['GGGG'], max_run=3)")
+    device = logits.device
+    padded = () if mutations is None else (("the reference of mutations", mutations[0], torch.int32),)
+
+    def chain(B, T, m, cu, *ref):
+        Bn, Tn = max(B, 0), max(T, 0)
+        if mutations is None:
+            fr = gc_fractions(gc_content, Bn).to(device, non_blocking=True)
+            lengths = (m.sum(dim=1) + 0.5).floor() if m is not None else (cu[1:] - cu[:-1]).clamp(0, Tn)
+            counted, (lo, hi), cap = torch.full((Bn, Tn), 12, dtype=torch.uint8, device=device), gc_counts(fr, lengths), Tn
+        else:
+            w, cap = count_window(mutations[1], mutations[1][1], Bn)
+            w = w.to(device, non_blocking=True)
+            counted, lo, hi = mutation_sets(ref[0]), w[:, 0].contiguous(), w[:, 1].contiguous()
+        need = int(_native.lib().rnampnn_design_dfa_count_workspace_bytes(Bn, Tn, auto.n_live, max(int(cap), 1)))
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+        return auto.delta_on(device), auto.kind, auto.n_states, counted, lo, hi, int(cap), ws, C.c_size_t(need)
+    return _design_call("rnampnn_design_dfa_count", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints,
+                        padded=padded, tail=chain,
+                        outputs=((torch.int32, True), (torch.int32, True), (torch.int32, True), (torch.int32, False), (torch.int32, False),
+                                 (torch.float64, False)))
+
+
+COMBINE = ("chain",)
+
+
+def _chain_mode(given: dict, require, pairs, tree: str) -> str:
+    """``design_mode`` with ``combine="chain"``: "chain", or the ``ValueError`` of a combination that is not built."""
+    if given["avoid"] is None and require is None and given["max_run"] is None:
+        raise ValueError("combine='chain' needs avoid, require or max_run: a plain G+C window or mutation budget needs no chain (drop combine=)")
+    if (given["gc_content"] is None) == (given["mutations"] is None):
+        raise ValueError("combine='chain' conditions on ONE count: pass exactly one of gc_content and mutations (two counts at once are "
+                         "not built)")
+    for name in ("states", "distinct"):
+        if given[name] is not None:
+            raise ValueError(f"combine='chain' together with {name} is not built: the chain over (position, automaton state, count) "
+                             "conditions the draws of rnampnn_design on the motifs and one count alone")
+    if pairs is not None:
+        raise ValueError("combine='chain' together with pairs is not built: base pairs under motifs and a count at once would carry the "
+                         "count through every transfer table of rnampnn_design_nested")
+    if tree != "lds":
+        raise ValueError(f"combine='chain' together with tree={tree!r} is not built: the chain's table lives in its own workspace and has "
+                         "no count tree")
+    return "chain"
+
+
+def design_mode(states=None, gc_content=None, distinct=None, mutations=None, avoid=None, require=None, pairs=None, combine=None,
+                max_run=None, tree: str = "lds") -> str:
     """Which entry ``design(...)`` draws from: "require", "avoid", "mutations", "distinct", "gc_content", "states", or "plain" when none of
     them is given.  ``require`` decides first and absorbs ``avoid`` (one automaton holds both lists).  ``ValueError`` for a combination
     that is not built (``DESIGN_MODES``; ``require`` with anything but ``avoid``) and an unknown ``distinct``; touches no device, so a
     caller refuses before its forward pass.  ``pairs="nested"`` opts in to "nested" (``rnampnn_design_nested``: ``avoid`` and / or
     ``require`` under the base pairs of a nested structure); it is a ``ValueError`` with another value, with a mode the automaton is not
-    built together with, and with neither ``avoid`` nor ``require``.  With ``pairs=None`` nothing differs."""
+    built together with, and with neither ``avoid`` nor ``require``.  With ``pairs=None`` nothing differs.  ``combine="chain"`` opts in
+    to "chain" (``rnampnn_design_dfa_count``: ``avoid`` / ``require`` / ``max_run`` TOGETHER with ``gc_content`` or ``mutations``, exact in
+    both); it is a ``ValueError`` with another value, without a motif argument, with both counts or neither, with ``states``,
+    ``distinct`` or ``pairs``, and with a ``tree`` other than "lds".  With ``combine=None`` nothing differs (``max_run`` and ``tree`` are
+    read by the chain alone)."""
     given = {"states": states, "gc_content": gc_content, "distinct": distinct, "mutations": mutations, "avoid": avoid}
+    if combine is not None:
+        if combine not in COMBINE:
+            raise ValueError(f"combine must be None or 'chain', got {combine!r}")
+        return _chain_mode(dict(given, max_run=max_run), require, pairs, tree)
     if pairs is not None:
         if pairs != "nested":
             raise ValueError(f"pairs must be None or 'nested', got {pairs!r}")
@@ -543,8 +632,11 @@ def design_by_mode(mode: str, logits: torch.Tensor, states=None, state_weights=N
     returns it, ``avoid`` as ``check_avoid`` does, ``require`` as ``check_require`` does (it holds ``avoid``); ``kw``: the layout and the
     draw (mask / cu_seqlens / max_len, n_samples, temperature, seed, constraints).  "nested": ``require`` as ``check_nested`` returns it
     (it holds ``avoid``).  ``tree`` (``check_tree``): the home of the count tree of "gc_content" and "mutations"; anything but "lds" with
-    another mode is a ``ValueError``."""
+    another mode is a ``ValueError``.  "chain": ``require`` as ``check_chain`` returns it (it holds ``avoid``) with ``gc_content`` or
+    ``mutations``."""
     check_tree(tree, mode)
+    if mode == "chain":
+        return design_dfa_count_from_logits(logits, require=require, gc_content=gc_content, mutations=mutations, **kw)
     if mode == "nested":
         return design_nested_from_logits(logits, require=require, **kw)
     if mode == "require":

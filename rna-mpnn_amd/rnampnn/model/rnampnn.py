@@ -23,7 +23,7 @@ from .. import _native
 from ..config.glob import DEFAULT_SEED, REVERSE_VOCAB
 from ..utils.data import check_prefix_mask
 from ._base import NativeModule, _prep, _ptr, _stream
-from .decode import (SCORE_OUTPUTS, argmax_recovery, check_avoid, check_distinct, check_nested, check_require, check_mutations, check_state_lengths, check_profile_tree, check_tree, design_by_mode,  # noqa: F401
+from .decode import (SCORE_OUTPUTS, argmax_recovery, check_avoid, check_chain, check_distinct, check_nested, check_require, check_mutations, check_state_lengths, check_profile_tree, check_tree, design_by_mode,  # noqa: F401
                      design_distinct_from_logits, design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits,
                      design_profile_from_logits,
                      letters_packed, letters_padded, sample_from_logits, score_logits)
@@ -548,7 +548,7 @@ class RNAMPNN(NativeModule):
     @torch.no_grad()
     def design(self, coords: torch.Tensor, mask: torch.Tensor, n_samples: int = 8, temperature: float = 0.1, seed: int = 0,
                T_norm: int = 0, constraints=None, states=None, state_weights=None, lengths=None, gc_content=None, distinct=None, mutations=None,
-               avoid=None, require=None, pairs=None, tree: str = "lds"):
+               avoid=None, require=None, pairs=None, tree: str = "lds", combine=None):
         """``sample`` plus the score of every draw against the SAME logits, with one forward: -> (seqs int8 (n_samples,B,T), -1 on
         padding; seq_nll (n_samples,B) f32).  The NLL is the model's own (temperature 1) likelihood, so designs drawn at different
         temperatures rank on one scale.  ``constraints`` (``rnampnn.utils.constraints.DesignConstraints``: fixed nucleotides, base
@@ -583,11 +583,18 @@ class RNAMPNN(NativeModule):
         mode, another value, or neither ``avoid`` nor ``require`` are a ``ValueError`` before the forward pass.  ``tree`` ("lds", the
         default: everything above, unchanged; "global"; "auto"): where the count tree of ``gc_content`` and ``mutations`` lives
         (``check_tree``) - in global memory RNAs of up to 32,744 nt are drawn under a G+C window, with the same bytes wherever both homes
-        run; anything but "lds" with another mode is a ``ValueError`` before the forward pass."""
-        mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require, pairs=pairs)
+        run; anything but "lds" with another mode is a ``ValueError`` before the forward pass.  ``combine="chain"`` (``None`` is
+        everything above, unchanged): ``avoid`` and / or ``require`` TOGETHER with ``gc_content`` or ``mutations``
+        (``design_dfa_count_from_logits``), exact in both conditions at once -> (seqs, seq_nll, infeasible, hits, accepted, count
+        (n_samples,B) int32 = the C or G ids / the mutations of each draw, dfa_miss (B,) int32, count_miss (B,) int32, log_z (B,) f64);
+        another value, no motif argument, both counts or neither, ``states``, ``distinct``, ``pairs``, a ``tree`` other than "lds" and
+        constraints that carry base pairs are a ``ValueError`` before the forward pass."""
+        mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require, pairs=pairs, combine=combine, tree=tree)
         check_tree(tree, mode)
         mutations = check_mutations(mutations)
-        if mode == "nested":
+        if mode == "chain":
+            require, avoid = check_chain(constraints, require, avoid), None
+        elif mode == "nested":
             require, avoid = check_nested(require, avoid, constraints), None
         else:
             require = check_require(require, avoid, constraints)

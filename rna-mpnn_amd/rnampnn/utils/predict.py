@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from ..config.glob import VOCAB
-from ..model.decode import (check_avoid, check_budget, check_profile_tree, check_tree, check_nested, check_require, design_by_mode, design_mode, design_profile_from_logits, letters_packed, letters_padded,
+from ..model.decode import (check_avoid, check_budget, check_chain, check_profile_tree, check_tree, check_nested, check_require, design_by_mode, design_mode, design_profile_from_logits, letters_packed, letters_padded,
                             sample_from_logits, score_logits)
 from .constraints import batch_constraints, crossing_pairs, mutation_references, padded_references, parse_dot_bracket
 from .data import PackedLoader, bucket_batches, fill_nan_deterministic, read_fasta
@@ -114,10 +114,15 @@ def write_csv(path: str, header: str, rows) -> None:
             f.write(",".join(str(v) for v in row) + "\n")
 
 
-def design_columns(mode: str, extras=(), lens=()):
+def design_columns(mode: str, extras=(), lens=(), count=None):
     """The last columns that ``designs_csv`` gains in a design mode (``design_mode``) -> (their header, cells, filled): ``cells(s, r)``
     the fields of sample s of row r, ``filled`` [B] the slots of a row that hold a sequence, or None for all of them.  ``extras``: the
-    two outputs of the mode's entry past (seqs, seq_nll, infeasible), ``lens`` the rows' lengths; without them only the header counts."""
+    two outputs of the mode's entry past (seqs, seq_nll, infeasible), ``lens`` the rows' lengths; without them only the header counts.
+    ``count``: what the "chain" mode counts, "gc_content" or "mutations" (it names that mode's last two columns)."""
+    if mode == "chain":                                             # six outputs: hits, accepted and count per sample, both misses and log_z per row
+        hits, found, cnt, miss, cmiss, _ = (t.cpu().tolist() for t in extras) if extras else (None,) * 6
+        tail = ",gc_count,gc_miss" if count == "gc_content" else ",mutations,mut_miss"
+        return ",motif_hits,required_found,require_miss" + tail, lambda s, r: (hits[s][r], found[s][r], miss[r], cnt[s][r], cmiss[r]), None
     if mode == "nested":                                            # four outputs: hits and accepted per sample, dfa_miss and nest_miss per row
         hits, found, miss, nest = (t.cpu().tolist() for t in extras) if extras else (None, None, None, None)
         return ",motif_hits,required_found,require_miss,nest_miss", lambda s, r: (hits[s][r], found[s][r], miss[r], nest[r]), None
@@ -158,6 +163,22 @@ def check_require_run(require, avoid, samples: int, profile_prefix, constraints)
     paired = sorted(rid for rid, (_, structure) in (constraints or {}).items() if structure)
     if paired:
         raise ValueError(f"require together with base pairs is not built (an exact draw would carry every open pair in the automaton's "
+                         f"state): drop `structure` from the constraints of {paired[:3]}{' ...' if len(paired) > 3 else ''}")
+    return auto
+
+
+def check_chain_run(require, avoid, samples: int, profile_prefix, constraints) -> object:
+    """``predict(..., combine="chain")`` -> the ``DesignAutomaton`` of ``require`` and / or ``avoid`` (``check_chain``).  ``ValueError``
+    without samples, with a profile (none is built for this mode) and with a structure in ``constraints``; touches no device."""
+    auto = check_chain(None, require, avoid)
+    if profile_prefix:
+        raise ValueError("a design profile together with combine='chain' is not built: the profile entries know a count or forbidden motifs, "
+                         "not both")
+    if samples <= 0:
+        raise ValueError("motifs under a count window need samples > 0")
+    paired = sorted(rid for rid, (_, structure) in (constraints or {}).items() if structure)
+    if paired:
+        raise ValueError(f"combine='chain' together with base pairs is not built (an exact draw would carry every open pair in the automaton's "
                          f"state): drop `structure` from the constraints of {paired[:3]}{' ...' if len(paired) > 3 else ''}")
     return auto
 
@@ -209,7 +230,7 @@ def write_profile(prefix: str, ids, store: dict) -> None:
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
             wobble: bool = True, states: Optional[dict] = None, gc_content=None, distinct=None, mutations=None,
-            avoid=None, profile_prefix: Optional[str] = None, require=None, pairs=None, tree: str = "lds") -> List[Tuple[str, str]]:
+            avoid=None, profile_prefix: Optional[str] = None, require=None, pairs=None, tree: str = "lds", combine=None) -> List[Tuple[str, str]]:
     """Design a sequence for every structure under ``data_path`` in length-bucketed var-len batches (``forward_packed``): the tree
     read-out on the packed embedding when one is attached, else the read-out's argmax (``rnampnn_score``'s ``pred``); write ``out_csv``
     with one ``pdb_id,seq`` row per structure in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure
@@ -252,11 +273,18 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     (``write_profile``), with or without ``samples``.  Not built together with ``states`` or ``distinct``.
     ``tree`` ("lds", the default: everything above, unchanged; "global"; "auto"): where the count tree of ``gc_content`` and ``mutations``
     and of their profiles lives (``check_tree``); in global memory structures longer than the 1,017 nt a G+C window fits in LDS are
-    designed.  Anything but "lds" with another mode is a ``ValueError`` before the first forward pass."""
-    mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require, pairs=pairs)
+    designed.  Anything but "lds" with another mode is a ``ValueError`` before the first forward pass.
+    ``combine="chain"`` (``None`` is everything above, unchanged): ``avoid`` and / or ``require`` TOGETHER with ``gc_content`` or
+    ``mutations`` - the draws come from ``rnampnn_design_dfa_count`` and hold both conditions exactly; ``designs_csv`` gains the last
+    columns ``motif_hits``, ``required_found``, ``require_miss`` and then ``gc_count``, ``gc_miss`` or ``mutations``, ``mut_miss``.  Not
+    built together with ``states``, ``distinct``, ``pairs``, a profile, a ``tree`` other than "lds" or a ``structure`` in ``constraints``."""
+    mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require, pairs=pairs, combine=combine, tree=tree)
     check_tree(tree, mode) if samples > 0 or not profile_prefix else check_profile_tree(tree, mode)
     check_profile(profile_prefix, states, distinct)
-    if mode == "nested":
+    count = "gc_content" if gc_content is not None else "mutations"     # (what the chain counts: it names its columns)
+    if mode == "chain":
+        require, avoid = check_chain_run(require, avoid, samples, profile_prefix, constraints), None
+    elif mode == "nested":
         require, avoid = check_nested_run(require, avoid, samples, profile_prefix, constraints), None
     else:
         require = check_require_run(require, avoid, samples, profile_prefix, constraints)
@@ -320,7 +348,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             state_weights=None if gs is None else [w for g in gs for w in groups[g][2]], tree=tree)
         if not constrained and gs is None:
             bad = None                                              # the column belongs to the constrained forms
-        _, cells, filled = design_columns(mode, extras, lens)
+        _, cells, filled = design_columns(mode, extras, lens, count)
         bad = None if bad is None else bad.cpu().tolist()
         lab, have = padded_labels(items, idx, max_len)
         want = (("seq_nll",) if dnll is None else ()) + (("seq_match",) if lab is not None else ())      # rnampnn_design scores its own draws
@@ -351,6 +379,6 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
         write_csv(designs_csv, "design_id,sample,seq,infeasible,states,nll_per_nt,recovery",
                   [(group[0],) + row for g, group in enumerate(groups) for row in designs[g]])
     elif samples > 0:
-        write_csv(designs_csv, "pdb_id,sample,seq,nll_per_nt,recovery" + (",infeasible" if constrained else "") + design_columns(mode)[0],
+        write_csv(designs_csv, "pdb_id,sample,seq,nll_per_nt,recovery" + (",infeasible" if constrained else "") + design_columns(mode, count=count)[0],
                   [(rid,) + row for i, rid in enumerate(ids) for row in designs[i]])
     return rows

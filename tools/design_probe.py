@@ -35,6 +35,12 @@ usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + r
                                                               yardstick) and rnampnn_design_nested: the same automaton without pairs (the
                                                               same work), the same automaton under a hairpin-rich nested structure on every
                                                               RNA (13 live states), and require GNRA + max_run = 3 under that structure (53)
+       python tools/design_probe.py chain                     rnampnn_design (free, hairpin) and then, in 5 alternating rounds of 10 calls each,
+                                                              the yardsticks of the same run - rnampnn_design_dfa max_run = 3 with every live
+                                                              state accepting, rnampnn_design_count under the G+C window 45..60 % (cap T) and
+                                                              under 0..8 mutations (cap 8), S = 8 - and rnampnn_design_dfa_count on that
+                                                              automaton: nothing counted (the work of rnampnn_design_dfa), under that G+C
+                                                              window, and under that budget (profiles/design_dfa_count_kernel_stats.txt)
        python tools/design_probe.py long                      the count tree in global memory (tree="global": rnampnn_design_count_long,
                                                               rnampnn_design_count_profile_long), nothing else: (a) the C2 batch in 5
                                                               alternating rounds of 10 calls - rnampnn_design_gc 40..60 %, rnampnn_design_count
@@ -329,6 +335,72 @@ else:
             print(f"{tag}: accepted {int(out[4].sum())} of {8 * B} draws, hits {int(out[3].sum())}, dfa_miss total {int(out[5].sum())}, "
                   f"mean NLL per nt {float(out[1].sum()) / (8 * int(mask.sum())):.4f}")
         print(f"filtering yield: {int(word.scan(free)[1].sum())} of the {8 * B} free draws of rnampnn_design at temperature 0.1 contain GGAGG")
+    if what == "chain":
+        # Six variants in alternating rounds of one process, so that k_design_dfa_count is compared with k_design_dfa on the same automaton
+        # and with k_design_count on the same windows of the SAME run.  The automaton is max_run 3 with every live state accepting.
+        from rnampnn.model import decode as D
+        from rnampnn.model.decode import gc_counts, gc_fractions
+        from rnampnn.utils.motifs import DesignAutomaton
+        import ctypes as C
+        rounds, per_round, warm = 5, 10, 3
+        kw = dict(temperature=0.1, seed=1, n_samples=8)
+        run3 = DesignAutomaton.from_avoid([], max_run=3)
+        lo, hi = gc_counts(gc_fractions((0.45, 0.60), B).cuda(), m.sum(dim=1))
+        window = torch.stack([lo, hi], dim=1)
+        cg = torch.full((B, T), 12, dtype=torch.uint8, device="cuda")
+        ref = torch.randint(0, 4, (B, T), generator=torch.Generator().manual_seed(1)).cuda()
+        sets = D.mutation_sets(ref)
+        nothing, zero = torch.zeros(B, T, dtype=torch.uint8, device="cuda"), torch.zeros(B, dtype=torch.int32, device="cuda")
+
+        def nothing_counted():                                      # the entry itself: no Python wrapper passes "nothing counts"
+            def tail(B, T, m, cu):
+                need = int(D._native.lib().rnampnn_design_dfa_count_workspace_bytes(B, T, run3.n_live, 1))
+                return (run3.delta_on("cuda"), run3.kind, run3.n_states, nothing, zero, zero, 0,
+                        torch.empty(need, dtype=torch.uint8, device="cuda"), C.c_size_t(need))
+            return D._design_call("rnampnn_design_dfa_count", logits, m, None, None, 8, 0.1, 1, None, tail=tail,
+                                  outputs=((torch.int32, True),) * 3 + ((torch.int32, False),) * 2 + ((torch.float64, False),))
+        variants = [
+            (f"rnampnn_design_dfa max_run 3, every live state accepting ({run3.n_live} live states), S 8",
+             lambda: D.design_dfa_from_logits(logits, mask=m, require=run3, **kw)),
+            ("rnampnn_design_count C|G counted, cap T, 45..60 %, S 8",
+             lambda: D.design_count_from_logits(logits, mask=m, counted=cg, window=window, cap=T, **kw)),
+            ("rnampnn_design_count random reference, 0..8 mutations, cap 8, S 8",
+             lambda: D.design_count_from_logits(logits, mask=m, counted=sets, window=(0, 8), **kw)),
+            ("rnampnn_design_dfa_count max_run 3, nothing counted, cap 0, S 8", nothing_counted),
+            ("rnampnn_design_dfa_count max_run 3, G+C 45..60 %, cap T, S 8",
+             lambda: D.design_dfa_count_from_logits(logits, mask=m, require=run3, gc_content=(0.45, 0.60), **kw)),
+            ("rnampnn_design_dfa_count max_run 3, 0..8 mutations, cap 8, S 8",
+             lambda: D.design_dfa_count_from_logits(logits, mask=m, require=run3, mutations=(ref, (0, 8)), **kw))]
+        for _, fn in variants:
+            for _ in range(warm):
+                fn()
+        torch.cuda.synchronize()
+        times = [[] for _ in variants]
+        for _ in range(rounds):
+            for v, (_, fn) in enumerate(variants):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(per_round):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                times[v].append(e0.elapsed_time(e1) * 1e3 / per_round)
+        for (name, _), t in zip(variants, times):
+            print(f"B {B} T {T} nt {int(mask.sum())} {name}: {sum(t) / len(t):.2f} us per call, rounds {min(t):.2f} .. {max(t):.2f} "
+                  f"({rounds} alternating rounds of {per_round} back-to-back calls, events, output and workspace allocation included)")
+        a, d = variants[0][1](), variants[3][1]()
+        print("nothing counted against rnampnn_design_dfa: " + ", ".join(
+            f"{k} equal {bool((x == y).all())}" for k, x, y in zip(("seqs", "seq_nll", "infeasible", "hits", "accepted", "dfa_miss"), a, d[:5] + d[6:7])))
+        n = m.sum(dim=1)
+        for tag, out, within in (("G+C 45..60 %", variants[4][1](), lambda c: (c >= lo[None]) & (c <= hi[None])),
+                                 ("0..8 mutations", variants[5][1](), lambda c: c <= 8)):
+            q = out[0]
+            recount = ((q == 2) | (q == 3)).sum(-1) if tag.startswith("G+C") else ((q != ref[None]) & (q >= 0)).sum(-1)
+            print(f"{tag}: accepted {int(out[4].sum())} of {8 * B} draws, hits {int(out[3].sum())} (recounted {int(run3.scan(q)[0].sum())}), "
+                  f"count inside the window {int(within(out[5]).sum())} of {8 * B} (recount equal {bool((recount == out[5]).all())}), dfa_miss total "
+                  f"{int(out[6].sum())}, count_miss total {int(out[7].sum())}, mean NLL per nt {float(out[1].sum()) / (8 * int(mask.sum())):.4f}")
+        ws = [int(D._native.lib().rnampnn_design_dfa_count_workspace_bytes(B, T, run3.n_live, cap)) for cap in (1, 8, T)]
+        print(f"workspace at (B {B}, T {T}, {run3.n_live} live states): {ws[0] // 2} bytes at cap 0, {ws[1]} at cap 8, {ws[2]} at cap T")
     if what == "nested":
         # Four variants in alternating rounds of one process, so that k_design_nested is compared with k_design_dfa of the SAME run.  The
         # structure: three outer pairs around a multiloop of hairpins (a stem of 4 closed by a tetraloop, 2 unpaired between them).

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/design_probe.py under rocprofv3 --kernel-trace --stats, each leg in a run of its own.  usage: tools/kstats_design.sh <outdir> [leg ...]
-# (outdir: a git-ignored place such as build/design_stats; legs: sample_score design tied gc distinct count avoid profile dfa nested long, the first four by default)
+# (outdir: a git-ignored place such as build/design_stats; legs: sample_score design tied gc distinct count avoid profile dfa nested chain long, the first four by default)
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "${1:?usage: tools/kstats_design.sh <outdir> [leg ...]}" && OUT=$(cd "$1" && pwd) || exit 1
 shift
@@ -41,10 +41,14 @@ cp = launches(lambda n: 'k_design_count_profile' in n)
 ap = launches(lambda n: 'k_design_avoid_profile' in n)
 # the "dfa" leg: the same rounds - k_design_avoid max_run 3 (1 variant: the yardstick of the same run) and k_design_dfa on the same automaton
 # with every live state accepting / require GGAGG + max_run 3 / require GGAGG and CUUCG + max_run 3 (3 variants of its launches)
-dfa = launches(lambda n: 'k_design_dfa' in n)
+dfa = launches(lambda n: 'k_design_dfa' in n and 'k_design_dfa_count' not in n)
 # the "nested" leg: the same rounds - k_design_dfa max_run 3 with every live state accepting (1 variant: the yardstick of the same run) and
 # k_design_nested on the same automaton without pairs / under the hairpin-rich structure / require GNRA + max_run 3 under it (3 variants)
 ns = launches(lambda n: 'k_design_nested' in n)
+# the "chain" leg: the same rounds - k_design_dfa max_run 3 with every live state accepting (1 variant) and k_design_count under the G+C
+# window 45..60 % / under 0..8 mutations (2 variants): the yardsticks of the same run; k_design_dfa_count on the same automaton with nothing
+# counted / under that window / under that budget (3 variants of its launches)
+ch = launches(lambda n: 'k_design_dfa_count' in n)
 # the "long" leg: every call of a long entry starts with a k_ct_long_leaves launch, so the trace splits into calls; the probe's log names the
 # chunks of calls in order.  Per chunk name: the mean per call of the inside pass (level 1 + the level launches), of the walk
 # (k_design_count_long) or of the outside pass and the leaves (k_pf_long_*), and their number of launches; the LDS entries by name.
@@ -97,7 +101,17 @@ def report(table):
         flat = sorted(x for r in rs for x in r)
         print(f"{kernel}, {label}: 5 rounds x 10 launches, mean {sum(flat) / len(flat):.2f} us ({flat[0]:.2f} .. {flat[-1]:.2f}, median {flat[len(flat) // 2]:.2f}); "
               f"round means {' '.join(f'{v:.2f}' for v in means)} (spread {max(means) - min(means):.2f})")
-if ns:
+if ch:
+    report((("k_design_dfa", "max_run 3, every live state accepting (13 live states), S = 8", by_round(dfa, 1, 0)),
+            ("k_design_count", "C|G counted, cap T, window 45..60 %, S = 8", by_round(c, 2, 0)),
+            ("k_design_count", "random reference, 0..8 mutations, cap 8, S = 8", by_round(c, 2, 1)),
+            ("k_design_dfa_count", "max_run 3 (13 live states), nothing counted, cap 0, S = 8", by_round(ch, 3, 0)),
+            ("k_design_dfa_count", "max_run 3 (13 live states), G+C window 45..60 %, cap T, S = 8", by_round(ch, 3, 1)),
+            ("k_design_dfa_count", "max_run 3 (13 live states), 0..8 mutations, cap 8, S = 8", by_round(ch, 3, 2))))
+    m = [sum(x for r in by_round(s, k, v) for x in r) / 50 for s, k, v in ((dfa, 1, 0), (ch, 3, 0), (ch, 3, 1), (ch, 3, 2), (c, 2, 0), (c, 2, 1))]
+    print(f"k_design_dfa_count / k_design_dfa, nothing counted: {m[1] / m[0]:.3f}; G+C window: {m[2] / m[0]:.3f} of k_design_dfa, {m[2] / m[4]:.3f} of "
+          f"k_design_count; budget of 8: {m[3] / m[0]:.3f} of k_design_dfa, {m[3] / m[5]:.3f} of k_design_count")
+elif ns:
     report((("k_design_dfa", "max_run 3, every live state accepting (13 live states), no pairs, S = 8", by_round(dfa, 1, 0)),
             ("k_design_nested", "max_run 3 (13 live states), no pairs, S = 8", by_round(ns, 3, 0)),
             ("k_design_nested", "max_run 3 (13 live states), hairpin-rich nested structure, S = 8", by_round(ns, 3, 1)),
