@@ -14,45 +14,13 @@
 // global table - written by this workgroup, so a barrier orders them, not a grid sync - 2 bits per position into LDS words the lane owns,
 // `hits` and `accepted` from the lane's own integers; then per sample the rows and the NLL as k_design writes them (ds_write_rows).
 // No atomics, no fill / copy node, no host synchronisation; every table entry that is read was written by the same launch before.
-#include "design_dev.h"
+// dfa_chain_dev.h holds what this entry shares with rnampnn_design_dfa_count and rnampnn_design_nested: the automaton's constants, helpers
+// and arguments (DfaChainArgs), the host prologue (dfa_prepare), the automaton half of phase A, the candidates and the automaton step of
+// the forward walk (dfa_walk_step<false>, dfa_advance) and the read of a draw (dfa_drawn).  The LDS carve-up, `col` / `cc` and phase B are this file's.
+#include "dfa_chain_dev.h"
 
 namespace {
-constexpr int DFA_MAX_STATES = RNAMPNN_DESIGN_DFA_MAX_STATES;
-static_assert(DFA_MAX_STATES == SC_THREADS, "one thread of the workgroup per state");
-constexpr int DFA_CHUNK = SC_THREADS;          // samples that walk together: one lane each
-constexpr unsigned DFA_DEAD = 0xFFFFu;         // the column of a transition into a dead state or out of the automaton
-constexpr size_t DFA_LDS_SCRATCH = 96;         // the reduction's DS_SCRATCH bytes, padded
-static_assert(DS_SCRATCH <= DFA_LDS_SCRATCH, "the reduction's scratch");
-
-struct DfaArgs : DesignArgs {
-    const uint8_t* delta;        // (A,4), device
-    unsigned long long dead[4];  // bit a set = state a is dead; set for every a >= A
-    unsigned long long acc[4];   // bit a set = state a is live and accepting
-    double* tab;                 // (B,T,live): the caller's workspace
-    int A, live, S, words;       // states, live states, samples, 32-bit words of one sample's draws
-    int32_t* hits;               // (S,B) or null
-    int32_t* accepted;           // (S,B) or null
-    int32_t* miss;               // (B) or null
-};
-
-// the words of one sample's draws: 2 bits per position, an odd count (lanes a word stride apart fall into different banks)
-__host__ __device__ inline int dfa_words(int T) { return ((T + 15) / 16) | 1; }
-
-__device__ __forceinline__ bool dfa_bit(const unsigned long long (&set)[4], unsigned a) {
-    const unsigned long long w = (a >> 6) == 0 ? set[0] : (a >> 6) == 1 ? set[1] : (a >> 6) == 2 ? set[2] : set[3];
-    return (w >> (a & 63u)) & 1ull;
-}
-
-// the live states below a: the table column of a live state a
-__device__ __forceinline__ int dfa_column(const unsigned long long (&dead)[4], unsigned a) {
-    int k = 0;
-#pragma unroll
-    for (unsigned j = 0; j < 4; ++j) {
-        const unsigned long long below = j < (a >> 6) ? ~0ull : j == (a >> 6) ? ((1ull << (a & 63u)) - 1ull) : 0ull;
-        k += __popcll(~dead[j] & below);
-    }
-    return k;
-}
+using DfaArgs = DfaChainArgs<DesignArgs>;      // tab: (B,T,live)
 
 __global__ void __launch_bounds__(SC_THREADS) k_design_dfa(DfaArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dfa_lds[];
@@ -82,25 +50,18 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa(DfaArgs a) {
         zs[4 * t] = p.z[0]; zs[4 * t + 1] = p.z[1]; zs[4 * t + 2] = p.z[2]; zs[4 * t + 3] = p.z[3];
         ms[t] = (unsigned char)p.m;
     }
-    const bool live = tid < A && !dfa_bit(a.dead, tid);
-    const bool accepts = live && dfa_bit(a.acc, tid);
-    own[tid] = live ? (unsigned short)dfa_column(a.dead, tid) : (unsigned short)DFA_DEAD;
-    kd[tid] = (unsigned char)((live ? 0 : 1) | (accepts ? 2 : 0));
+    const DfaState me = dfa_load_state(a, A, tid, DFA_DEAD, own, kd);
+    const bool live = me.live, accepts = me.accepts;
     row[(n & 1) * DFA_MAX_STATES + tid] = accepts ? 0.0 : -INFINITY;               // l_n
     row[((n + 1) & 1) * DFA_MAX_STATES + tid] = -INFINITY;                         // a dead state's entry is never written again
     __syncthreads();
-    unsigned raw = 0, cl[2] = {0, 0};
+    unsigned cl[2] = {0, 0};
     int cc[4], ok = 0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const unsigned nxt = tid < A ? a.delta[4 * tid + c] : 0xFFu;
-        const unsigned k = tid < A && nxt < (unsigned)A ? own[nxt] : DFA_DEAD;
-        raw |= (nxt & 255u) << (8 * c);
+    dfa_load_delta(a, tid, DFA_DEAD, own, nx, [&](int c, unsigned nxt, unsigned k) {
         cl[c >> 1] |= k << (16 * (c & 1));
         ok |= (k != DFA_DEAD ? 1 : 0) << c;
         cc[c] = k != DFA_DEAD ? (int)nxt : 0;                                      // (the LDS rows are indexed by state)
-    }
-    nx[tid] = tid < A ? raw : 0u;
+    });
     col[tid] = make_uint2(cl[0], cl[1]);
     __syncthreads();
     // ---- B: l_t(a), t = n-1 .. 0; thread = state; the row of t + 1 is read, the row of t written, one barrier per step
@@ -122,7 +83,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa(DfaArgs a) {
         }
     }
     const bool miss = !(row[0] > -INFINITY);                        // l_0 of state 0: the loop ends on row 0, and n = 0 starts there
-    if (tid == 0 && a.miss) a.miss[b] = miss ? 1 : 0;
+    if (tid == 0 && a.dfa_miss) a.dfa_miss[b] = miss ? 1 : 0;
     // ---- C: the walks of 256 samples, then their rows
     const int S = (a.seqs || a.seq_nll || a.hits || a.accepted) ? a.S : 1;         // `infeasible` is written with sample 0
     for (int s0 = 0; s0 < S; s0 += DFA_CHUNK) {
@@ -141,32 +102,11 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa(DfaArgs a) {
                 const unsigned step = nx[st];
                 int q = -1;
                 if (!miss) {
-                    const uint2 cl = col[st];
                     const bool last = t + 1 == n;
-                    const double* next = tab + (size_t)(last ? t : t + 1) * AL;    // (the last step reads a row that exists and uses none of it)
-                    double v[4];
-                    int adm = 0;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const unsigned k = ((c < 2 ? cl.x : cl.y) >> (16 * (c & 1))) & 0xFFFFu;
-                        const bool in = ((p.m >> c) & 1) && k != DFA_DEAD;
-                        const double far = next[in ? k : 0];
-                        const double end = (kd[(step >> (8 * c)) & 255u] & 2) ? 0.0 : -INFINITY;
-                        const double l = !in ? -INFINITY : last ? end : far;
-                        v[c] = p.z[c] + l;
-                        adm |= (in && l > -INFINITY ? 1 : 0) << c;
-                    }
-                    if (adm) {
-                        double w[4];
-                        ds_weights(v, adm, w);
-                        q = ds_select(w, adm, u);
-                    }
+                    q = dfa_walk_step<false>(p, u, col[st], step, kd, tab + (size_t)(last ? t : t + 1) * AL, last, 1, 0, 0);
                 }
                 if (q < 0) q = ds_draw_single(p, u);                // no admitted sequence is accepted: rnampnn_design's draw
-                const unsigned nxt = (step >> (8 * q)) & 255u;
-                const bool out = nxt >= (unsigned)A;
-                hit += out || (kd[nxt] & 1) ? 1 : 0;
-                st = out ? 0 : (int)nxt;
+                dfa_advance(step, q, A, kd, st, hit);
                 word |= (unsigned)q << (2 * (t & 15));
                 if ((t & 15) == 15 || t == n - 1) { mine[t >> 4] = word; word = 0; }
             }
@@ -177,7 +117,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa(DfaArgs a) {
         for (int i = 0; i < cn; ++i) {
             const int s = s0 + i;
             const unsigned* drawn = draws + i * W;
-            ds_write_rows(a, s, b, n, row0, tid, s == 0 ? bad : 0, sc, [&](int t) { return (int)((drawn[t >> 4] >> (2 * (t & 15))) & 3u); }, DsNoSum{});
+            ds_write_rows(a, s, b, n, row0, tid, s == 0 ? bad : 0, sc, [&](int t) { return dfa_drawn(drawn, t); }, DsNoSum{});
             __syncthreads();                                        // the scratch is written again by the next sample
         }
     }
@@ -204,45 +144,18 @@ extern "C" int rnampnn_design_dfa(const float* logits, int64_t n_rows, const flo
                                   void* stream) {
     const char* name = "rnampnn_design_dfa";
     DfaArgs a{};
-    const int rc = ds_prepare(name, "RNA", logits, n_rows, mask, cu_seqlens, B, T, temperature, S, seed, seed_dev, allowed, partner, wobble, bias,
-                              bias_per_position, seqs, seq_nll, infeasible, a, [&](int slot) {
-        if (slot == 0 && !delta) return fail(RNAMPNN_ERR_BAD_ARG, "%s: null delta", name);
-        if (slot == 0 && !kind) return fail(RNAMPNN_ERR_BAD_ARG, "%s: null kind (a HOST array of n_states bytes)", name);
-        if (slot == 0 && (n_states < 1 || n_states > DFA_MAX_STATES))
-            return fail(RNAMPNN_ERR_BAD_ARG, "%s: n_states = %d, an automaton has 1 .. %d states", name, (int)n_states, DFA_MAX_STATES);
-        if (slot == 0 && (kind[0] & 1)) return fail(RNAMPNN_ERR_BAD_ARG, "%s: state 0, the start, is marked dead", name);
-        if (slot == 1) {
-            int live = 0;
-            for (int s = 0; s < n_states; ++s) live += (kind[s] & 1) ? 0 : 1;
-            const size_t need = rnampnn_design_dfa_workspace_bytes(B, T, live);
-            if (!workspace || workspace_bytes < need)
-                return fail(RNAMPNN_ERR_BAD_ARG, "%s: the workspace is %s (%zu bytes), the table of partition sums at (B = %d, T = %d, %d live "
-                            "states) needs %zu (rnampnn_design_dfa_workspace_bytes)", name, workspace ? "too small" : "null", workspace_bytes,
-                            (int)B, (int)T, live, need);
-            if (((uintptr_t)workspace & 7) != 0) return fail(RNAMPNN_ERR_BAD_ARG, "%s: the workspace must be 8-byte aligned", name);
-        }
-        return RNAMPNN_OK;
+    const int rc = dfa_prepare(name, logits, n_rows, mask, cu_seqlens, B, T, temperature, S, seed, seed_dev, allowed, partner, wobble, bias,
+                               bias_per_position, seqs, seq_nll, infeasible, delta, kind, n_states, workspace, workspace_bytes, hits, accepted,
+                               dfa_miss, true, a, [] { return RNAMPNN_OK; }, [&](int live, char* what, size_t len) {
+        std::snprintf(what, len, "the table of partition sums at (B = %d, T = %d, %d live states) needs", (int)B, (int)T, live);
+        return rnampnn_design_dfa_workspace_bytes(B, T, live);
     });
     if (rc != RNAMPNN_OK) return rc;
-    if (partner)
-        return fail(RNAMPNN_ERR_UNSUPPORTED, "%s: base pairs (a non-null partner) are not built together with an automaton: a pair couples two "
-                    "distant positions, so an exact chain over (position, automaton state) would carry the class of every open pair in its "
-                    "state, 4^depth states", name);
-    for (int w = 0; w < 4; ++w) a.dead[w] = ~0ull;
-    for (int s = 0; s < n_states; ++s) {
-        if (kind[s] & 1) continue;
-        a.dead[s >> 6] &= ~(1ull << (s & 63));
-        if (kind[s] & 2) a.acc[s >> 6] |= 1ull << (s & 63);
-        ++a.live;
-    }
     const size_t lds = dfa_lds_bytes(T);
     if (lds > DS_LDS_MAX)
         return fail(RNAMPNN_ERR_UNSUPPORTED, "%s: T = %d needs %zu bytes of LDS for the rows and the draws of 256 samples, the limit is %zu "
                     "(T <= %lld; the table of partition sums is in the workspace and does not count)", name, (int)T, lds, DS_LDS_MAX,
                     ds_max_T([](long long t) { return dfa_lds_bytes(t); }));
     if (!seqs && !seq_nll && !infeasible && !hits && !accepted && !dfa_miss) return RNAMPNN_OK;    // nothing asked for
-    a.delta = delta; a.A = n_states; a.S = S; a.words = dfa_words(T);
-    a.tab = reinterpret_cast<double*>(workspace);
-    a.hits = hits; a.accepted = accepted; a.miss = dfa_miss;
     return ds_launch<k_design_dfa>(dim3(B), lds, stream, a);
 }

@@ -1,8 +1,11 @@
 // rnampnn_design_dfa_count: constrained design conditioned EXACTLY on BOTH a finite automaton (motifs that must and must not occur,
 // rnampnn_design_dfa) and a count window (a G+C window or a mutation budget, rnampnn_design_count), in one launch.  The count joins the
 // automaton's chain as a third index: l_t(a, k) = the log of the total weight of the suffixes from t that start in live state a, stay
-// live, end in an accepting state and count exactly k.  Everything about a position, the automaton and its walk is design_dfa.hip's,
-// statement for statement, so with nothing counted the outputs are rnampnn_design_dfa's byte for byte; the counted sets, the window, the
+// live, end in an accepting state and count exactly k.  Everything about a position, the automaton and its walk is design_dfa.hip's -
+// the same functions of dfa_chain_dev.h: the arguments (DfaChainArgs over CtArgs), the prologue (dfa_prepare, with the count side's two
+// checks), the walk's candidates (dfa_walk_step<true>: the count is its optional part), dfa_advance and dfa_drawn; phase A's automaton
+// load is this file's own text, which fills `of` between the stores of `own` and `kd` (through the header's two functions the G+C
+// variant measured 1.5 % slower, docs/experiments.md Round 17) - so with nothing counted the outputs are rnampnn_design_dfa's byte for byte; the counted sets, the window, the
 // target and the selection of the total are count_tree_dev.h's (ct_target, ct_select, the salt).  The contract is the one
 // include/rnampnn_hip.h documents and tests/_design_dfa_count_ref.py restates; all of the draw is fp64.
 // The table l_t(a, k) lives in the caller's WORKSPACE in global memory, [b][t][live column][k], k = 0 .. cap: 8 B T L (cap + 1) bytes.
@@ -17,49 +20,18 @@
 // remaining count), reading the four candidates from the workspace; then per sample the rows and the NLL (ds_write_rows).
 // No atomics, no fill / copy node, no host synchronisation; every table entry that is read was written by the same launch before.
 #include "count_tree_dev.h"
+#include "dfa_chain_dev.h"
 
 #ifndef DFC_SLAB_LDS_MAX
 #define DFC_SLAB_LDS_MAX DS_LDS_MAX            // the LDS a call may take with the two slabs in it; 0 builds the workspace home alone (the A/B of profiles/)
 #endif
 
 namespace {
-constexpr int DFC_MAX_STATES = RNAMPNN_DESIGN_DFA_MAX_STATES;
-static_assert(DFC_MAX_STATES == SC_THREADS, "the automaton is loaded one state per thread");
-constexpr int DFC_CHUNK = SC_THREADS;          // samples that walk together: one lane each
-constexpr unsigned DFC_DEAD = 0xFFFFu;         // the column of a transition into a dead state or out of the automaton
-constexpr size_t DFC_LDS_SCRATCH = 96;         // the reduction's DS_SCRATCH = 48 bytes, then at 48 the six ints of the target
-static_assert(DS_SCRATCH <= 48, "the layout of the scratch");
+static_assert(DS_SCRATCH <= 48, "the layout of the scratch: the reduction's bytes, then at 48 the six ints of the target");
 
-struct DfcArgs : CtArgs {        // counted, lo, hi, count, miss (= count_miss), cap: the count side as CtArgs names it
-    const uint8_t* delta;        // (A,4), device
-    unsigned long long dead[4];  // bit a set = state a is dead; set for every a >= A
-    unsigned long long acc[4];   // bit a set = state a is live and accepting
-    double* tab;                 // (B,T,live,cap+1): the caller's workspace
-    int A, live, S, words;       // states, live states, samples, 32-bit words of one sample's draws
-    int32_t* hits;               // (S,B) or null
-    int32_t* accepted;           // (S,B) or null
-    int32_t* dfa_miss;           // (B) or null
+struct DfcArgs : DfaChainArgs<CtArgs> {   // counted, lo, hi, count, miss (= count_miss), cap: the count side as CtArgs names it; tab: (B,T,live,cap+1)
     double* log_z;               // (B) or null
 };
-
-// the words of one sample's draws: 2 bits per position, an odd count (lanes a word stride apart fall into different banks)
-__host__ __device__ inline int dfc_words(int T) { return ((T + 15) / 16) | 1; }
-
-__device__ __forceinline__ bool dfc_bit(const unsigned long long (&set)[4], unsigned a) {
-    const unsigned long long w = (a >> 6) == 0 ? set[0] : (a >> 6) == 1 ? set[1] : (a >> 6) == 2 ? set[2] : set[3];
-    return (w >> (a & 63u)) & 1ull;
-}
-
-// the live states below a: the table column of a live state a
-__device__ __forceinline__ int dfc_column(const unsigned long long (&dead)[4], unsigned a) {
-    int k = 0;
-#pragma unroll
-    for (unsigned j = 0; j < 4; ++j) {
-        const unsigned long long below = j < (a >> 6) ? ~0ull : j == (a >> 6) ? ((1ull << (a & 63u)) - 1ull) : 0ull;
-        k += __popcll(~dead[j] & below);
-    }
-    return k;
-}
 
 template <bool SLAB>
 __global__ void __launch_bounds__(SC_THREADS) k_design_dfa_count(DfcArgs a) {
@@ -69,15 +41,15 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa_count(DfcArgs a) {
     double* zs = reinterpret_cast<double*>(dfc_lds);                               // [T][4]      z of a position
     double* slab = zs + 4 * (size_t)T;                                             // [2][AL][cap1]  l_{t+1} and l_t (SLAB only)
     unsigned* draws = reinterpret_cast<unsigned*>(slab + 2 * slab_doubles);        // [256][W]    a chunk's draws
-    unsigned* nx = draws + DFC_CHUNK * W;                                          // [256]       delta(a, .), a byte per class
-    uint2* col = reinterpret_cast<uint2*>(nx + DFC_MAX_STATES);                    // [256]       the columns of delta(a, .), 16 bits per class
-    unsigned short* own = reinterpret_cast<unsigned short*>(col + DFC_MAX_STATES); // [256]       the column of state a, or DFC_DEAD
-    unsigned char* of = reinterpret_cast<unsigned char*>(own + DFC_MAX_STATES);    // [256]       the state of a live column
-    unsigned char* red = of + DFC_MAX_STATES;                                      // the reduction's scratch, then the target
+    unsigned* nx = draws + DFA_CHUNK * W;                                          // [256]       delta(a, .), a byte per class
+    uint2* col = reinterpret_cast<uint2*>(nx + DFA_MAX_STATES);                    // [256]       the columns of delta(a, .), 16 bits per class
+    unsigned short* own = reinterpret_cast<unsigned short*>(col + DFA_MAX_STATES); // [256]       the column of state a, or DFA_DEAD
+    unsigned char* of = reinterpret_cast<unsigned char*>(own + DFA_MAX_STATES);    // [256]       the state of a live column
+    unsigned char* red = of + DFA_MAX_STATES;                                      // the reduction's scratch, then the target
     const DsScratch sc = ds_scratch(red);
     int* tg = reinterpret_cast<int*>(red + 48);                                    // lo, hi, K, any, dfa_miss
-    unsigned char* kd = red + DFC_LDS_SCRATCH;                                     // [256]       bit 0 dead, bit 1 accepting
-    unsigned char* ms = kd + DFC_MAX_STATES;                                       // [T]         the mask of a position
+    unsigned char* kd = red + DFA_LDS_SCRATCH;                                     // [256]       bit 0 dead, bit 1 accepting
+    unsigned char* ms = kd + DFA_MAX_STATES;                                       // [T]         the mask of a position
     unsigned char* cn = ms + (((size_t)T + 15) & ~(size_t)15);                     // [T]         its counted set
     const unsigned long long seed = a.seed_dev ? *a.seed_dev : a.seed;
     const size_t step = (size_t)AL * cap1;                                         // the doubles of one slab
@@ -98,9 +70,9 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa_count(DfcArgs a) {
         cn[t] = (unsigned char)ct_counted<true>(a, pad0, t);
     }
     {
-        const bool live = tid < A && !dfc_bit(a.dead, tid);
-        const bool accepts = live && dfc_bit(a.acc, tid);
-        const int mine = live ? dfc_column(a.dead, tid) : (int)DFC_DEAD;
+        const bool live = tid < A && !dfa_bit(a.dead, tid);
+        const bool accepts = live && dfa_bit(a.acc, tid);
+        const int mine = live ? dfa_column(a.dead, tid) : (int)DFA_DEAD;
         own[tid] = (unsigned short)mine;
         if (live) of[mine] = (unsigned char)tid;
         kd[tid] = (unsigned char)((live ? 0 : 1) | (accepts ? 2 : 0));
@@ -111,7 +83,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa_count(DfcArgs a) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const unsigned nxt = tid < A ? a.delta[4 * tid + c] : 0xFFu;
-            const unsigned k = tid < A && nxt < (unsigned)A ? own[nxt] : DFC_DEAD;
+            const unsigned k = tid < A && nxt < (unsigned)A ? own[nxt] : DFA_DEAD;
             raw |= (nxt & 255u) << (8 * c);
             cl[c >> 1] |= k << (16 * (c & 1));
         }
@@ -140,7 +112,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa_count(DfcArgs a) {
                 for (int c = 0; c < 4; ++c) {
                     const unsigned kc = ((c < 2 ? cl.x : cl.y) >> (16 * (c & 1))) & 0xFFFFu;
                     const int kk = k - ((cs >> c) & 1);
-                    const bool in = ((m >> c) & 1) && kc != DFC_DEAD && kk >= 0;
+                    const bool in = ((m >> c) & 1) && kc != DFA_DEAD && kk >= 0;
                     const double far = next[in ? (size_t)kc * cap1 + kk : 0];
                     const double end = (kd[(nxt >> (8 * c)) & 255u] & 2) && kk == 0 ? 0.0 : -INFINITY;
                     v[c] = z[c] + (last ? end : far);
@@ -179,8 +151,8 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa_count(DfcArgs a) {
     const int lo = tg[0], hi = tg[1], target = tg[2];
     const bool any = tg[3] != 0, miss = tg[4] != 0;
     const int S = (a.seqs || a.seq_nll || a.hits || a.accepted || a.count) ? a.S : 1;      // `infeasible` is written with sample 0
-    for (int s0 = 0; s0 < S; s0 += DFC_CHUNK) {
-        const int cnum = min(DFC_CHUNK, S - s0);
+    for (int s0 = 0; s0 < S; s0 += DFA_CHUNK) {
+        const int cnum = min(DFA_CHUNK, S - s0);
         if (tid < cnum) {
             const int s = s0 + tid;
             unsigned* mine = draws + tid * W;
@@ -197,33 +169,11 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa_count(DfcArgs a) {
                 const unsigned nxts = nx[st];
                 int q = -1;
                 if (!miss) {
-                    const uint2 cl = col[st];
                     const bool last = t + 1 == n;
-                    const double* next = tab + (size_t)(last ? t : t + 1) * step;  // (the last step reads a slab that exists and uses none of it)
-                    double v[4];
-                    int adm = 0;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const unsigned kc = ((c < 2 ? cl.x : cl.y) >> (16 * (c & 1))) & 0xFFFFu;
-                        const int kk = r - ((cs >> c) & 1);
-                        const bool in = ((p.m >> c) & 1) && kc != DFC_DEAD && kk >= 0;
-                        const double far = next[in ? (size_t)kc * cap1 + kk : 0];
-                        const double end = (kd[(nxts >> (8 * c)) & 255u] & 2) && kk == 0 ? 0.0 : -INFINITY;
-                        const double l = !in ? -INFINITY : last ? end : far;
-                        v[c] = p.z[c] + l;
-                        adm |= (in && l > -INFINITY ? 1 : 0) << c;
-                    }
-                    if (adm) {
-                        double w[4];
-                        ds_weights(v, adm, w);
-                        q = ds_select(w, adm, u);
-                    }
+                    q = dfa_walk_step<true>(p, u, col[st], nxts, kd, tab + (size_t)(last ? t : t + 1) * step, last, cap1, r, cs);
                 }
                 if (q < 0) q = ds_draw_single(p, u);                // no admitted sequence holds both conditions: rnampnn_design's draw
-                const unsigned nxt = (nxts >> (8 * q)) & 255u;
-                const bool out = nxt >= (unsigned)A;
-                hit += out || (kd[nxt] & 1) ? 1 : 0;
-                st = out ? 0 : (int)nxt;
+                dfa_advance(nxts, q, A, kd, st, hit);
                 cnt += (cs >> q) & 1;
                 r = max(r - ((cs >> q) & 1), 0);
                 word |= (unsigned)q << (2 * (t & 15));
@@ -237,7 +187,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa_count(DfcArgs a) {
         for (int i = 0; i < cnum; ++i) {
             const int s = s0 + i;
             const unsigned* drawn = draws + i * W;
-            ds_write_rows(a, s, b, n, row0, tid, s == 0 ? bad : 0, sc, [&](int t) { return (int)((drawn[t >> 4] >> (2 * (t & 15))) & 3u); }, DsNoSum{});
+            ds_write_rows(a, s, b, n, row0, tid, s == 0 ? bad : 0, sc, [&](int t) { return dfa_drawn(drawn, t); }, DsNoSum{});
             __syncthreads();                                        // the scratch is written again by the next sample
         }
     }
@@ -246,7 +196,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa_count(DfcArgs a) {
 // the bytes of dynamic LDS without the slabs, from T alone, and the bytes of the two slabs: the formulas include/rnampnn_hip.h gives
 size_t dfc_lds_bytes(long long T) {
     const size_t t = (size_t)T;
-    return 32 * t + 2 * 16 * ((t + 15) / 16) + (size_t)DFC_CHUNK * 4 * (size_t)dfc_words((int)T) + (4 + 8 + 2 + 1 + 1) * DFC_MAX_STATES + DFC_LDS_SCRATCH;
+    return 32 * t + 2 * 16 * ((t + 15) / 16) + (size_t)DFA_CHUNK * 4 * (size_t)dfa_words((int)T) + (4 + 8 + 2 + 1 + 1) * DFA_MAX_STATES + DFA_LDS_SCRATCH;
 }
 size_t dfc_slab_bytes(int live, int cap) { return (size_t)16 * (size_t)live * ((size_t)cap + 1); }
 // the table: 8 B T L (cap + 1) bytes, cap already clamped to 0 .. T
@@ -267,49 +217,25 @@ extern "C" int rnampnn_design_dfa_count(const float* logits, int64_t n_rows, con
                                         int32_t* accepted, int32_t* count, int32_t* dfa_miss, int32_t* count_miss, double* log_z, void* stream) {
     const char* name = "rnampnn_design_dfa_count";
     DfcArgs a{};
-    const int rc = ds_prepare(name, "RNA", logits, n_rows, mask, cu_seqlens, B, T, temperature, S, seed, seed_dev, allowed, partner, wobble, bias,
-                              bias_per_position, seqs, seq_nll, infeasible, a, [&](int slot) {
-        if (slot == 0 && !delta) return fail(RNAMPNN_ERR_BAD_ARG, "%s: null delta", name);
-        if (slot == 0 && !kind) return fail(RNAMPNN_ERR_BAD_ARG, "%s: null kind (a HOST array of n_states bytes)", name);
-        if (slot == 0 && (n_states < 1 || n_states > DFC_MAX_STATES))
-            return fail(RNAMPNN_ERR_BAD_ARG, "%s: n_states = %d, an automaton has 1 .. %d states", name, (int)n_states, DFC_MAX_STATES);
-        if (slot == 0 && (kind[0] & 1)) return fail(RNAMPNN_ERR_BAD_ARG, "%s: state 0, the start, is marked dead", name);
-        if (slot == 0 && (!counted || !count_lo || !count_hi)) return fail(RNAMPNN_ERR_BAD_ARG, "%s: null counted, count_lo or count_hi", name);
-        if (slot == 0 && count_cap < 0) return fail(RNAMPNN_ERR_BAD_ARG, "%s: count_cap = %d is negative", name, (int)count_cap);
-        if (slot == 1) {
-            int live = 0;
-            for (int s = 0; s < n_states; ++s) live += (kind[s] & 1) ? 0 : 1;
-            const int cap = std::min<int>(count_cap, T);
-            const size_t need = dfc_table_bytes(B, T, live, cap);
-            if (!workspace || workspace_bytes < need)
-                return fail(RNAMPNN_ERR_BAD_ARG, "%s: the workspace is %s (%zu bytes), the table of partition sums at (B = %d, T = %d, %d live "
-                            "states, counts 0 .. %d) needs %zu (rnampnn_design_dfa_count_workspace_bytes)", name, workspace ? "too small" : "null",
-                            workspace_bytes, (int)B, (int)T, live, cap, need);
-            if (((uintptr_t)workspace & 7) != 0) return fail(RNAMPNN_ERR_BAD_ARG, "%s: the workspace must be 8-byte aligned", name);
-        }
+    const int rc = dfa_prepare(name, logits, n_rows, mask, cu_seqlens, B, T, temperature, S, seed, seed_dev, allowed, partner, wobble, bias,
+                               bias_per_position, seqs, seq_nll, infeasible, delta, kind, n_states, workspace, workspace_bytes, hits, accepted,
+                               dfa_miss, true, a, [&] {
+        if (!counted || !count_lo || !count_hi) return fail(RNAMPNN_ERR_BAD_ARG, "%s: null counted, count_lo or count_hi", name);
+        if (count_cap < 0) return fail(RNAMPNN_ERR_BAD_ARG, "%s: count_cap = %d is negative", name, (int)count_cap);
         return RNAMPNN_OK;
+    }, [&](int live, char* what, size_t len) {
+        const int cap = std::min<int>(count_cap, T);
+        std::snprintf(what, len, "the table of partition sums at (B = %d, T = %d, %d live states, counts 0 .. %d) needs", (int)B, (int)T, live, cap);
+        return dfc_table_bytes(B, T, live, cap);
     });
     if (rc != RNAMPNN_OK) return rc;
-    if (partner)
-        return fail(RNAMPNN_ERR_UNSUPPORTED, "%s: base pairs (a non-null partner) are not built together with an automaton: a pair couples two "
-                    "distant positions, so an exact chain over (position, automaton state) would carry the class of every open pair in its "
-                    "state, 4^depth states", name);
-    for (int w = 0; w < 4; ++w) a.dead[w] = ~0ull;
-    for (int s = 0; s < n_states; ++s) {
-        if (kind[s] & 1) continue;
-        a.dead[s >> 6] &= ~(1ull << (s & 63));
-        if (kind[s] & 2) a.acc[s >> 6] |= 1ull << (s & 63);
-        ++a.live;
-    }
     size_t lds = dfc_lds_bytes(T);
     if (lds > DS_LDS_MAX)
         return fail(RNAMPNN_ERR_UNSUPPORTED, "%s: T = %d needs %zu bytes of LDS for the rows and the draws of 256 samples, the limit is %zu "
                     "(T <= %lld; the table of partition sums is in the workspace and does not count)", name, (int)T, lds, DS_LDS_MAX,
                     ds_max_T([](long long t) { return dfc_lds_bytes(t); }));
     if (!seqs && !seq_nll && !infeasible && !hits && !accepted && !count && !dfa_miss && !count_miss && !log_z) return RNAMPNN_OK;    // nothing asked for
-    a.delta = delta; a.A = n_states; a.S = S; a.words = dfc_words(T);
-    a.tab = reinterpret_cast<double*>(workspace);
-    a.hits = hits; a.accepted = accepted; a.dfa_miss = dfa_miss; a.log_z = log_z;
+    a.log_z = log_z;
     a.counted = counted; a.lo = count_lo; a.hi = count_hi; a.count = count; a.miss = count_miss; a.cap = std::min<int>(count_cap, T);
     const size_t slabs = dfc_slab_bytes(a.live, a.cap);
     if (lds + slabs <= (size_t)DFC_SLAB_LDS_MAX) return ds_launch<k_design_dfa_count<true>>(dim3(B), lds + slabs, stream, a);

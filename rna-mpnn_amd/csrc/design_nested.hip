@@ -16,49 +16,20 @@
 // position in LDS words the lane owns (they lie over the tiles, which phase B is done with); the goals of the open pairs are a stack of
 // bytes per lane in the workspace; then per sample the rows and the NLL as k_design writes them (ds_write_rows).
 // No atomics, no fill / copy node, no host synchronisation; every workspace byte that is read was written by the same launch before.
-#include "design_dev.h"
+// dfa_chain_dev.h holds what this entry shares with rnampnn_design_dfa and rnampnn_design_dfa_count: the automaton's constants, helpers
+// and arguments (DfaChainArgs), the host prologue (dfa_prepare; pairs are not refused here), the automaton half of phase A (columns as
+// bytes, DFA_DEAD8), dfa_advance on a miss and dfa_drawn.  NS_MAX_LIVE, `dl` / `ac`, the structure, phase B and the
+// walk of the tree are this file's.
+#include "dfa_chain_dev.h"
 
 namespace {
-constexpr int NS_MAX_STATES = RNAMPNN_DESIGN_DFA_MAX_STATES;
 constexpr int NS_MAX_LIVE = RNAMPNN_DESIGN_NESTED_MAX_LIVE;
-static_assert(NS_MAX_STATES == SC_THREADS, "one thread of the workgroup per state while the automaton is read");
 static_assert(NS_MAX_LIVE <= 254, "a live column and the dead mark fit a byte");
-constexpr int NS_CHUNK = SC_THREADS;           // samples that walk together: one lane each
-constexpr unsigned NS_DEAD = 0xFFu;            // the column of a transition into a dead state or out of the automaton
-constexpr size_t NS_LDS_SCRATCH = 96;          // the reduction's DS_SCRATCH bytes, padded
-static_assert(DS_SCRATCH <= NS_LDS_SCRATCH, "the reduction's scratch");
 
-struct NestArgs : DesignArgs {
-    const uint8_t* delta;        // (A,4), device
-    unsigned long long dead[4];  // bit a set = state a is dead; set for every a >= A
-    unsigned long long acc[4];   // bit a set = state a is live and accepting
-    double* tab;                 // (B,T,live,live): the tables, in the caller's workspace
-    unsigned char* stack;        // (B,T/2+1,256): the goals of a lane's open pairs, behind the tables
-    int A, live, S, words;       // states, live states, samples, 32-bit words of one sample's draws
-    int32_t* hits;               // (S,B) or null
-    int32_t* accepted;           // (S,B) or null
-    int32_t* miss;               // (B) or null
+struct NestStacks { unsigned char* stack; };   // (B,T/2+1,256): the goals of a lane's open pairs, behind the tables
+struct NestArgs : DfaChainArgs<DesignArgs, NestStacks> {   // tab: (B,T,live,live), the tables
     int32_t* nest;               // (B) or null
 };
-
-// the words of one sample's draws: 2 bits per position, an odd count (lanes a word stride apart fall into different banks)
-__host__ __device__ inline int ns_words(int T) { return ((T + 15) / 16) | 1; }
-
-__device__ __forceinline__ bool ns_bit(const unsigned long long (&set)[4], unsigned a) {
-    const unsigned long long w = (a >> 6) == 0 ? set[0] : (a >> 6) == 1 ? set[1] : (a >> 6) == 2 ? set[2] : set[3];
-    return (w >> (a & 63u)) & 1ull;
-}
-
-// the live states below a: the table column of a live state a
-__device__ __forceinline__ int ns_column(const unsigned long long (&dead)[4], unsigned a) {
-    int k = 0;
-#pragma unroll
-    for (unsigned j = 0; j < 4; ++j) {
-        const unsigned long long below = j < (a >> 6) ? ~0ull : j == (a >> 6) ? ((1ull << (a & 63u)) - 1ull) : 0ull;
-        k += __popcll(~dead[j] & below);
-    }
-    return k;
-}
 
 // A table as the recurrence reads it: one in the workspace (rows of G goals), the identity behind the last element of an inner loop, or
 // the acceptance vector behind position n-1.
@@ -73,24 +44,24 @@ __device__ __forceinline__ double ns_at(const NsTab& t, const unsigned char* ac,
 __global__ void __launch_bounds__(SC_THREADS) k_design_nested(NestArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ns_lds[];
     const int T = a.T, b = blockIdx.x, tid = threadIdx.x, A = a.A, AL = a.live, W = a.words;
-    const size_t area = max((size_t)16 * AL * AL, (size_t)NS_CHUNK * 4 * W);
+    const size_t area = max((size_t)16 * AL * AL, (size_t)DFA_CHUNK * 4 * W);
     double* zs = reinterpret_cast<double*>(ns_lds);                                // [T][4]      z of a position
     double* tile_a = zs + 4 * (size_t)T;                                           // [L][L]      R^in, then the successor's table (phase B)
     double* tile_b = tile_a + AL * AL;                                             // [L][L]      P_t (phase B)
     unsigned* draws = reinterpret_cast<unsigned*>(tile_a);                         // [256][W]    a chunk's draws (phase C, over the tiles)
     unsigned* nx = reinterpret_cast<unsigned*>(ns_lds + 32 * (size_t)T + area);    // [256]       delta(a, .), a byte per class
-    unsigned* dl = nx + NS_MAX_STATES;                                             // [64]        the columns of delta(column k, .), a byte per class
+    unsigned* dl = nx + DFA_MAX_STATES;                                            // [64]        the columns of delta(column k, .), a byte per class
     unsigned char* red = reinterpret_cast<unsigned char*>(dl + NS_MAX_LIVE);       // the reduction's scratch
     const DsScratch sc = ds_scratch(red);
-    short* pr = reinterpret_cast<short*>(red + NS_LDS_SCRATCH);                    // [T]         the partner of a position, -1 for none
-    unsigned char* own = reinterpret_cast<unsigned char*>(pr + T);                 // [256]       the column of state a, or NS_DEAD
-    unsigned char* kd = own + NS_MAX_STATES;                                       // [256]       bit 0 dead, bit 1 accepting
-    unsigned char* ac = kd + NS_MAX_STATES;                                        // [64]        column k accepts
+    short* pr = reinterpret_cast<short*>(red + DFA_LDS_SCRATCH);                   // [T]         the partner of a position, -1 for none
+    unsigned char* own = reinterpret_cast<unsigned char*>(pr + T);                 // [256]       the column of state a, or DFA_DEAD8
+    unsigned char* kd = own + DFA_MAX_STATES;                                      // [256]       bit 0 dead, bit 1 accepting
+    unsigned char* ac = kd + DFA_MAX_STATES;                                       // [64]        column k accepts
     unsigned char* ms = ac + NS_MAX_LIVE;                                          // [T]         the mask of a position
     unsigned char* fl = ms + T;                                                    // [T]         1 = the position lies inside no pair
     const unsigned long long seed = a.seed_dev ? *a.seed_dev : a.seed;
     double* tab = a.tab + (size_t)b * T * AL * AL;                                 // [T][L][G]   R_t
-    unsigned char* stack = a.stack + (size_t)b * (T / 2 + 1) * NS_CHUNK + tid;     // [T/2+1][256]
+    unsigned char* stack = a.more.stack + (size_t)b * (T / 2 + 1) * DFA_CHUNK + tid;    // [T/2+1][256]
     int n;
     long long row0;
     sc_extent(a, b, tid, sc.s_f[0], n, row0);
@@ -104,23 +75,14 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_nested(NestArgs a) {
         zs[4 * t] = p.z[0]; zs[4 * t + 1] = p.z[1]; zs[4 * t + 2] = p.z[2]; zs[4 * t + 3] = p.z[3];
         ms[t] = (unsigned char)p.m;
     }
-    const bool live = tid < A && !ns_bit(a.dead, tid);
-    const bool accepts = live && ns_bit(a.acc, tid);
-    const unsigned mine_col = live ? (unsigned)ns_column(a.dead, tid) : NS_DEAD;
-    own[tid] = (unsigned char)mine_col;
-    kd[tid] = (unsigned char)((live ? 0 : 1) | (accepts ? 2 : 0));
-    if (live) ac[mine_col] = accepts ? 1 : 0;
+    const DfaState me = dfa_load_state(a, A, tid, DFA_DEAD8, own, kd);
+    const bool live = me.live;
+    const unsigned mine_col = me.mine;
+    if (live) ac[mine_col] = me.accepts ? 1 : 0;
     __syncthreads();
     {
-        unsigned raw = 0, cols = 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const unsigned nxt = tid < A ? a.delta[4 * tid + c] : 0xFFu;
-            const unsigned k = tid < A && nxt < (unsigned)A ? own[nxt] : NS_DEAD;
-            raw |= (nxt & 255u) << (8 * c);
-            cols |= k << (8 * c);
-        }
-        nx[tid] = tid < A ? raw : 0u;
+        unsigned cols = 0;
+        dfa_load_delta(a, tid, DFA_DEAD8, own, nx, [&](int c, unsigned, unsigned k) { cols |= k << (8 * c); });
         if (live) dl[mine_col] = cols;
     }
     for (int t = tid; t < n; t += SC_THREADS) {
@@ -176,8 +138,8 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_nested(NestArgs a) {
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         const unsigned k = (d >> (8 * c)) & 255u;
-                        v[c] = z[c] + ns_at(N, ac, k != NS_DEAD ? (int)k : 0, g);
-                        ok |= (k != NS_DEAD ? 1 : 0) << c;
+                        v[c] = z[c] + ns_at(N, ac, k != DFA_DEAD8 ? (int)k : 0, g);
+                        ok |= (k != DFA_DEAD8 ? 1 : 0) << c;
                     }
                     out[e] = ds_lse<4>(v, m & ok);
                 }
@@ -199,7 +161,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_nested(NestArgs a) {
                 for (int pass = 0; pass < 2; ++pass) {
                     for (int cell = 0; cell < 16; ++cell) {
                         const unsigned k = (d >> (8 * (cell >> 2))) & 255u;
-                        if (!((pm >> cell) & 1) || k == NS_DEAD) continue;
+                        if (!((pm >> cell) & 1) || k == DFA_DEAD8) continue;
                         const double zc = zs[4 * t + (cell >> 2)] + zs[4 * j + (cell & 3)];
                         const double* rin = tile_a + k * AL;
                         for (int b2 = 0; b2 < AL; ++b2) {
@@ -237,12 +199,12 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_nested(NestArgs a) {
     __syncthreads();                                                // the tiles are done with: the draws lie over them
     const bool dmiss = !nest && !((n > 0 ? tab[0] : (ac[0] ? 0.0 : -INFINITY)) > -INFINITY);       // R_0(0, accepted)
     const bool miss = nest || dmiss;
-    if (tid == 0 && a.miss) a.miss[b] = dmiss ? 1 : 0;
+    if (tid == 0 && a.dfa_miss) a.dfa_miss[b] = dmiss ? 1 : 0;
     if (tid == 0 && a.nest) a.nest[b] = nest ? 1 : 0;
     // ---- C: the walks of 256 samples, then their rows
     const int S = (a.seqs || a.seq_nll || a.hits || a.accepted) ? a.S : 1;         // `infeasible` is written with sample 0
-    for (int s0 = 0; s0 < S; s0 += NS_CHUNK) {
-        const int cn = min(NS_CHUNK, S - s0);
+    for (int s0 = 0; s0 < S; s0 += DFA_CHUNK) {
+        const int cn = min(DFA_CHUNK, S - s0);
         if (tid < cn) {
             const int s = s0 + tid;
             unsigned* mine = draws + tid * W;
@@ -265,19 +227,16 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_nested(NestArgs a) {
                         if (cell >= 0) q = closer ? (cell & 3) : (cell >> 2);
                     }
                     if (q < 0) q = ds_draw_single(p, ds_u24(seed, s, b, t));
-                    const unsigned nxt = (nx[st] >> (8 * q)) & 255u;
-                    const bool out = nxt >= (unsigned)A;
-                    hit += out || (kd[nxt] & 1) ? 1 : 0;
-                    st = out ? 0 : (int)nxt;
+                    dfa_advance(nx[st], q, A, kd, st, hit);
                     mine[t >> 4] |= (unsigned)q << (2 * (t & 15));
                     continue;
                 }
                 if (closer) {                                       // its class came with the opener's
-                    q = (int)((mine[t >> 4] >> (2 * (t & 15))) & 3u);
+                    q = dfa_drawn(mine, t);
                     const unsigned k = (dl[col] >> (8 * q)) & 255u;
-                    col = k != NS_DEAD ? (int)k : 0;
+                    col = k != DFA_DEAD8 ? (int)k : 0;
                     sp -= sp > 0 ? 1 : 0;
-                    g = stack[(size_t)sp * NS_CHUNK];
+                    g = stack[(size_t)sp * DFA_CHUNK];
                     continue;
                 }
                 const bool top = fl[t] != 0;
@@ -289,7 +248,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_nested(NestArgs a) {
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         const unsigned k = (d >> (8 * c)) & 255u;
-                        const bool in = ((p.m >> c) & 1) && k != NS_DEAD;
+                        const bool in = ((p.m >> c) & 1) && k != DFA_DEAD8;
                         const double l = in ? ns_at(N, ac, (int)k, g) : -INFINITY;
                         v[c] = p.z[c] + l;
                         adm |= (in && l > -INFINITY ? 1 : 0) << c;
@@ -301,7 +260,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_nested(NestArgs a) {
                     }
                     if (q < 0) q = ds_draw_single(p, u);
                     const unsigned k = (d >> (8 * q)) & 255u;
-                    col = k != NS_DEAD ? (int)k : 0;
+                    col = k != DFA_DEAD8 ? (int)k : 0;
                     mine[t >> 4] |= (unsigned)q << (2 * (t & 15));
                     continue;
                 }
@@ -314,11 +273,11 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_nested(NestArgs a) {
                 for (int pass = 0; pass < 3; ++pass) {
                     for (int cell = 0; cell < 16; ++cell) {
                         const unsigned k = (d >> (8 * (cell >> 2))) & 255u;
-                        if (!((pm >> cell) & 1) || k == NS_DEAD) continue;
+                        if (!((pm >> cell) & 1) || k == DFA_DEAD8) continue;
                         const double zc = zs[4 * t + (cell >> 2)] + zs[4 * j + (cell & 3)];
                         for (int b2 = 0; b2 < AL; ++b2) {
                             const unsigned k2 = (dl[b2] >> (8 * (cell & 3))) & 255u;
-                            if (k2 == NS_DEAD) continue;
+                            if (k2 == DFA_DEAD8) continue;
                             const double rin = ns_at(In, ac, (int)k, b2);
                             if (!(rin > -INFINITY)) continue;
                             const double far = ns_at(N, ac, (int)k2, g);
@@ -341,11 +300,11 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_nested(NestArgs a) {
                     o.m = ms[j];
                     cell = max(ds_draw_pair(p, o, a.wobble, u), 0);
                 }
-                stack[(size_t)sp * NS_CHUNK] = (unsigned char)g;
+                stack[(size_t)sp * DFA_CHUNK] = (unsigned char)g;
                 ++sp;
                 g = b2;
                 const unsigned k = (d >> (8 * (cell >> 2))) & 255u;
-                col = k != NS_DEAD ? (int)k : 0;
+                col = k != DFA_DEAD8 ? (int)k : 0;
                 mine[t >> 4] |= (unsigned)(cell >> 2) << (2 * (t & 15));
                 mine[j >> 4] |= (unsigned)(cell & 3) << (2 * (j & 15));
             }
@@ -356,7 +315,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_nested(NestArgs a) {
         for (int i = 0; i < cn; ++i) {
             const int s = s0 + i;
             const unsigned* drawn = draws + i * W;
-            ds_write_rows(a, s, b, n, row0, tid, s == 0 ? bad : 0, sc, [&](int t) { return (int)((drawn[t >> 4] >> (2 * (t & 15))) & 3u); }, DsNoSum{});
+            ds_write_rows(a, s, b, n, row0, tid, s == 0 ? bad : 0, sc, [&](int t) { return dfa_drawn(drawn, t); }, DsNoSum{});
             __syncthreads();                                        // the scratch is written again by the next sample
         }
     }
@@ -364,8 +323,8 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_nested(NestArgs a) {
 
 // the bytes of dynamic LDS, from T and the live states: the formula include/rnampnn_hip.h gives
 size_t ns_lds_bytes(long long T, int live) {
-    const size_t t = (size_t)T, tiles = (size_t)16 * live * live, draws = (size_t)NS_CHUNK * 4 * (size_t)ns_words((int)T);
-    return 32 * t + (tiles > draws ? tiles : draws) + 4 * NS_MAX_STATES + 4 * NS_MAX_LIVE + NS_LDS_SCRATCH + 2 * t + 2 * NS_MAX_STATES + NS_MAX_LIVE +
+    const size_t t = (size_t)T, tiles = (size_t)16 * live * live, draws = (size_t)DFA_CHUNK * 4 * (size_t)dfa_words((int)T);
+    return 32 * t + (tiles > draws ? tiles : draws) + 4 * DFA_MAX_STATES + 4 * NS_MAX_LIVE + DFA_LDS_SCRATCH + 2 * t + 2 * DFA_MAX_STATES + NS_MAX_LIVE +
            2 * t;
 }
 
@@ -374,7 +333,7 @@ size_t ns_table_bytes(int32_t B, int32_t T, int32_t live) { return (size_t)8 * (
 
 extern "C" size_t rnampnn_design_nested_workspace_bytes(int32_t B, int32_t T, int32_t n_live) {
     if (B <= 0 || T <= 0 || n_live <= 0) return 0;
-    return ns_table_bytes(B, T, n_live) + (size_t)NS_CHUNK * (size_t)B * (size_t)(T / 2 + 1);
+    return ns_table_bytes(B, T, n_live) + (size_t)DFA_CHUNK * (size_t)B * (size_t)(T / 2 + 1);
 }
 
 extern "C" int rnampnn_design_nested(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
@@ -385,46 +344,24 @@ extern "C" int rnampnn_design_nested(const float* logits, int64_t n_rows, const 
                                      int32_t* nest_miss, void* stream) {
     const char* name = "rnampnn_design_nested";
     NestArgs a{};
-    int live = 0;
-    const int rc = ds_prepare(name, "RNA", logits, n_rows, mask, cu_seqlens, B, T, temperature, S, seed, seed_dev, allowed, partner, wobble, bias,
-                              bias_per_position, seqs, seq_nll, infeasible, a, [&](int slot) {
-        if (slot == 0 && !delta) return fail(RNAMPNN_ERR_BAD_ARG, "%s: null delta", name);
-        if (slot == 0 && !kind) return fail(RNAMPNN_ERR_BAD_ARG, "%s: null kind (a HOST array of n_states bytes)", name);
-        if (slot == 0 && (n_states < 1 || n_states > NS_MAX_STATES))
-            return fail(RNAMPNN_ERR_BAD_ARG, "%s: n_states = %d, an automaton has 1 .. %d states", name, (int)n_states, NS_MAX_STATES);
-        if (slot == 0 && (kind[0] & 1)) return fail(RNAMPNN_ERR_BAD_ARG, "%s: state 0, the start, is marked dead", name);
-        if (slot == 1) {
-            live = 0;
-            for (int s = 0; s < n_states; ++s) live += (kind[s] & 1) ? 0 : 1;
-            const size_t need = rnampnn_design_nested_workspace_bytes(B, T, live);
-            if (!workspace || workspace_bytes < need)
-                return fail(RNAMPNN_ERR_BAD_ARG, "%s: the workspace is %s (%zu bytes), the tables and the goal stacks at (B = %d, T = %d, %d live "
-                            "states) need %zu (rnampnn_design_nested_workspace_bytes)", name, workspace ? "too small" : "null", workspace_bytes,
-                            (int)B, (int)T, live, need);
-            if (((uintptr_t)workspace & 7) != 0) return fail(RNAMPNN_ERR_BAD_ARG, "%s: the workspace must be 8-byte aligned", name);
-        }
-        return RNAMPNN_OK;
+    const int rc = dfa_prepare(name, logits, n_rows, mask, cu_seqlens, B, T, temperature, S, seed, seed_dev, allowed, partner, wobble, bias,
+                               bias_per_position, seqs, seq_nll, infeasible, delta, kind, n_states, workspace, workspace_bytes, hits, accepted,
+                               dfa_miss, false, a, [] { return RNAMPNN_OK; }, [&](int live, char* what, size_t len) {
+        std::snprintf(what, len, "the tables and the goal stacks at (B = %d, T = %d, %d live states) need", (int)B, (int)T, live);
+        return rnampnn_design_nested_workspace_bytes(B, T, live);
     });
     if (rc != RNAMPNN_OK) return rc;
+    const int live = a.live;
     if (live > NS_MAX_LIVE)
         return fail(RNAMPNN_ERR_UNSUPPORTED, "%s: the automaton has %d live states, the limit is %d (a table per position holds live x live "
                     "entries, and two of them sit in LDS): require or avoid fewer or shorter motifs", name, live, NS_MAX_LIVE);
-    for (int w = 0; w < 4; ++w) a.dead[w] = ~0ull;
-    for (int s = 0; s < n_states; ++s) {
-        if (kind[s] & 1) continue;
-        a.dead[s >> 6] &= ~(1ull << (s & 63));
-        if (kind[s] & 2) a.acc[s >> 6] |= 1ull << (s & 63);
-    }
-    a.live = live;
     const size_t lds = ns_lds_bytes(T, live);
     if (lds > DS_LDS_MAX)
         return fail(RNAMPNN_ERR_UNSUPPORTED, "%s: T = %d needs %zu bytes of LDS for the rows, the structure and the draws of 256 samples, the "
                     "limit is %zu (T <= %lld at %d live states; the tables are in the workspace and do not count)", name, (int)T, lds, DS_LDS_MAX,
                     ds_max_T([&](long long t) { return ns_lds_bytes(t, live); }), live);
     if (!seqs && !seq_nll && !infeasible && !hits && !accepted && !dfa_miss && !nest_miss) return RNAMPNN_OK;    // nothing asked for
-    a.delta = delta; a.A = n_states; a.S = S; a.words = ns_words(T);
-    a.tab = reinterpret_cast<double*>(workspace);
-    a.stack = reinterpret_cast<unsigned char*>(workspace) + ns_table_bytes(B, T, live);
-    a.hits = hits; a.accepted = accepted; a.miss = dfa_miss; a.nest = nest_miss;
+    a.more.stack = reinterpret_cast<unsigned char*>(workspace) + ns_table_bytes(B, T, live);
+    a.nest = nest_miss;
     return ds_launch<k_design_nested>(dim3(B), lds, stream, a);
 }

@@ -34,7 +34,7 @@ import torch.nn.functional as F
 from .. import _native
 from rnampnn.model._base import _prep, _stream
 from rnampnn.model.decode import (check_avoid, check_chain, check_distinct, check_mutations, check_nested, check_require, check_state_lengths, check_profile_tree, check_tree, design_by_mode, design_distinct_from_logits,  # noqa: F401
-                                  design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits, design_profile_from_logits,
+                                  design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits, design_profile_from_logits, resolve_design, resolve_profile,
                                   letters_packed,
                                   score_logits)
 
@@ -432,51 +432,19 @@ class RNAModel(nn.Module):
     def design(self, X, mask, n_samples: int = 8, temperature: float = 0.1, seed: int = 0, constraints=None, lengths=None, states=None,
                state_weights=None, gc_content=None, distinct=None, mutations=None, avoid=None, require=None,
                pairs=None, tree: str = "lds", combine=None):
-        """``n_samples`` sequences per RNA drawn from this model's read-out at ``temperature`` and scored, in one ``rnampnn_design`` launch
-        on the packed logits -> (seqs int8 (n_samples,B,T), -1 on padding; seq_nll (n_samples,B) f32, the model's own temperature-1 NLL of
-        each draw; infeasible (B,) int32).  ``constraints``: a ``rnampnn.utils.constraints.DesignConstraints`` (fixed nucleotides, base
-        pairs, bias) or None for free draws.  ``lengths`` as in ``score_batch``.  ``states`` / ``state_weights``: multi-state design
-        (``rnampnn_design_tied`` through ``design_from_logits``): consecutive rows of a group are states of ONE design and receive the same
-        sequence; with host ``lengths`` a group whose states differ in length is a ``ValueError`` naming the group.  ``gc_content`` (a pair
-        of fractions, or (B,2)): the draws are conditioned exactly on the G+C content of every RNA lying in that window
-        (``design_gc_from_logits``) -> the triple plus gc_count (n_samples,B) int32 and gc_miss (B,) int32; not built together with
-        ``states``.  ``distinct`` ("sample" or "best"; ``None`` is everything above, unchanged): ``n_samples`` pairwise DIFFERENT sequences
-        per RNA (``design_distinct_from_logits``) - an exact sample without replacement, or the most probable admitted sequences in
-        descending order -> (seqs, seq_nll, infeasible, logp (n_samples,B) f32, n_distinct (B,) int32); not built together with ``states``
-        or ``gc_content``.  ``mutations`` (``(reference, max)`` or ``(reference, min, max)``, reference (B,T) class ids, e.g. the native
-        sequence): the draws - under ``constraints`` or free - differ from the reference at between min (default 0) and max positions,
-        drawn exactly from the model's distribution conditioned on that (``design_count_from_logits``) -> (seqs, seq_nll, infeasible,
-        n_mut (n_samples,B) int32, mut_miss (B,) int32 = how far the structure and the fixed positions alone push the count out of the
-        budget, 0 when it is reachable); not built together with ``states``, ``gc_content`` or ``distinct``.  ``avoid`` (a
-        ``rnampnn.utils.motifs.MotifAutomaton`` or motif strings): no draw contains one of the motifs - drawn exactly from the model's
-        distribution conditioned on that (``design_avoid_from_logits``) -> (seqs, seq_nll, infeasible, hits (n_samples,B) int32,
-        avoid_miss (B,) int32); not built together with the other modes, and constraints that carry base pairs are a ``ValueError``
-        before the forward pass.  ``require`` (a ``rnampnn.utils.motifs.DesignAutomaton`` or motif strings): every draw contains EVERY one
-        of the motifs somewhere and none of ``avoid``, which it absorbs (``design_dfa_from_logits``) -> (seqs, seq_nll, infeasible, hits,
-        accepted (n_samples,B) int32, dfa_miss (B,) int32); not built together with the other modes or with base pairs.  ``pairs="nested"`` (``None`` is everything above, unchanged): ``avoid``
-        and / or ``require`` UNDER the base pairs of ``constraints`` (``design_nested_from_logits``): the structure is honoured and the
-        draws are exact as long as it is nested -> (seqs, seq_nll, infeasible, hits, accepted, dfa_miss, nest_miss (B,) int32 = 1 for an
-        RNA whose pairs cross: it is drawn as plain ``constraints`` draw it); host-side constraints whose structure crosses, another
-        mode, another value, or neither ``avoid`` nor ``require`` are a ``ValueError`` before the forward pass.  ``tree`` ("lds", the
-        default: everything above, unchanged; "global"; "auto"): where the count tree of ``gc_content`` and ``mutations`` lives
-        (``check_tree``) - in global memory RNAs of up to 32,744 nt are drawn under a G+C window, with the same bytes wherever both homes
-        run; anything but "lds" with another mode is a ``ValueError`` before the forward pass.  ``combine="chain"`` (``None`` is
-        everything above, unchanged): ``avoid`` and / or ``require`` TOGETHER with ``gc_content`` or ``mutations``
-        (``design_dfa_count_from_logits``), exact in both conditions at once -> (seqs, seq_nll, infeasible, hits, accepted, count
-        (n_samples,B) int32, dfa_miss (B,) int32, count_miss (B,) int32, log_z (B,) f64); the refusals are ``RNAMPNN.design``'s, before
-        the forward pass."""
-        mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require, pairs=pairs, combine=combine, tree=tree)
-        check_tree(tree, mode)
-        mutations = check_mutations(mutations)
-        if mode == "chain":
-            require, avoid = check_chain(constraints, require, avoid), None
-        elif mode == "nested":
-            require, avoid = check_nested(require, avoid, constraints), None
-        else:
-            require = check_require(require, avoid, constraints)
-            avoid = check_avoid(avoid, constraints) if require is None else None
-        if states is not None and lengths is not None:
-            check_state_lengths(states, lengths)
+        """``n_samples`` sequences per RNA drawn from this model's read-out at ``temperature`` and scored, in one launch of the design
+        family on the PACKED logits (``design_by_mode`` with ``cu_seqlens`` built on the device from the mask; ``X``, ``mask`` as
+        ``score_batch`` takes them, ``lengths`` as there).  The return, by mode (S = ``n_samples``):
+        "plain" (``constraints`` or free) and "states" -> (seqs int8 (S,B,T), -1 on padding; seq_nll (S,B) f32, the model's own
+        temperature-1 NLL of each draw; infeasible (B,) int32);
+        and in every other mode that triple plus - "gc_content": gc_count (S,B) int32, gc_miss (B,) int32; "distinct": logp (S,B) f32,
+        n_distinct (B,) int32; "mutations": n_mut (S,B) int32, mut_miss (B,) int32; "avoid": hits (S,B) int32, avoid_miss (B,) int32;
+        "require": hits, accepted (S,B) int32, dfa_miss (B,) int32; ``pairs="nested"``: hits, accepted, dfa_miss, nest_miss (B,) int32;
+        ``combine="chain"``: hits, accepted, count (S,B) int32, dfa_miss, count_miss (B,) int32, log_z (B,) f64.
+        What each argument means, which pairings are built and what is refused - the refusals are ``RNAMPNN.design``'s, each a
+        ``ValueError`` before the forward pass - stands once, on ``rnampnn.model.decode.resolve_design``."""
+        mode, mutations, avoid, require = resolve_design(constraints, states, lengths, gc_content, distinct, mutations, avoid, require, pairs,
+                                                         combine, tree)
         logits, cu, T = self._packed_logits(X, mask, lengths)
         return design_by_mode(mode, logits, cu_seqlens=cu, max_len=T, n_samples=n_samples, temperature=temperature, seed=seed,
                               constraints=constraints, states=states, state_weights=state_weights, gc_content=gc_content, distinct=distinct,
@@ -490,9 +458,7 @@ class RNAModel(nn.Module):
         -> a ``DesignProfile``.  ``constraints``, ``lengths``, ``gc_content``, ``mutations`` and ``avoid`` as in ``design``; the pairings
         ``design`` refuses are refused here with the same messages, before the forward pass.  No profile is built for ``states`` or
         ``distinct``.  ``tree`` as in ``design``, for every profile but ``avoid``'s."""
-        check_profile_tree(tree, design_mode(gc_content=gc_content, mutations=mutations, avoid=avoid))
-        check_mutations(mutations)
-        check_avoid(avoid, constraints)
+        resolve_profile(constraints, gc_content, mutations, avoid, tree)
         was_training = self.training
         self.eval()
         try:

@@ -4,10 +4,10 @@ from __future__ import annotations
 import os
 from typing import List, Optional, Tuple
 
-from rnampnn.model.decode import check_avoid, check_budget, check_profile_tree, check_tree, design_by_mode, design_mode, letters_padded, score_logits
+from rnampnn.model.decode import design_by_mode, letters_padded, score_logits
 from rnampnn.utils.constraints import batch_constraints, mutation_references, padded_references
 from rnampnn.utils.data import bucket_batches
-from rnampnn.utils.predict import check_chain_run, check_nested_run, check_profile, check_require_run, design_columns, profile_batch, write_csv, write_profile
+from rnampnn.utils.predict import design_columns, profile_batch, resolve_run, write_csv, write_profile
 
 from .data import load_rna_dir, padded_loader
 
@@ -43,28 +43,9 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     and of their profiles lives (``check_tree``); anything but "lds" with another mode is a ``ValueError`` before the first forward pass.
     ``combine="chain"``: ``avoid`` and / or ``require`` TOGETHER with ``gc_content`` or ``mutations`` (``rnampnn_design_dfa_count``), as in
     ``rnampnn.utils.predict.predict``: the same columns and the same refusals."""
-    mode = design_mode(None, gc_content, distinct, mutations, avoid, require=require, pairs=pairs, combine=combine, tree=tree)
-    check_tree(tree, mode) if samples > 0 or not profile_prefix else check_profile_tree(tree, mode)
-    check_profile(profile_prefix, None, distinct)
+    mode, avoid, require = resolve_run(samples, profile_prefix, constraints, gc_content=gc_content, distinct=distinct, mutations=mutations,
+                                       avoid=avoid, require=require, pairs=pairs, combine=combine, tree=tree)
     count = "gc_content" if gc_content is not None else "mutations"     # (what the chain counts: it names its columns)
-    if mode == "chain":
-        require, avoid = check_chain_run(require, avoid, samples, profile_prefix, constraints), None
-    elif mode == "nested":
-        require, avoid = check_nested_run(require, avoid, samples, profile_prefix, constraints), None
-    else:
-        require = check_require_run(require, avoid, samples, profile_prefix, constraints)
-        avoid = check_avoid(avoid) if require is None else None
-    if avoid is not None:
-        if samples <= 0 and not profile_prefix:
-            raise ValueError("forbidden motifs need samples > 0")
-        paired = sorted(rid for rid, (_, structure) in (constraints or {}).items() if structure)
-        if paired:
-            raise ValueError(f"avoid together with base pairs is not built (an exact draw would carry every open pair in the automaton's "
-                             f"state): drop `structure` from the constraints of {paired[:3]}{' ...' if len(paired) > 3 else ''}")
-    if mutations is not None:
-        check_budget(mutations[0], mutations[1])
-        if samples <= 0 and not profile_prefix:
-            raise ValueError("a mutation budget needs samples > 0")
     model.eval()
     items = load_rna_dir(data_path)
     if not items:

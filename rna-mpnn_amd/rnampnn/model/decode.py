@@ -199,10 +199,40 @@ def _by_tree(tree: str, call):
         return call(True)
 
 
-def _tree_workspace(symbol: str, B: int, T: int, cap: int, device):
-    """The workspace of a long entry: (a ``torch.empty`` of ``symbol``(B, T, max(cap, 1)) bytes, that size as the ABI takes it)."""
-    need = int(getattr(_native.lib(), symbol)(max(B, 0), max(T, 0), max(int(cap), 1)))
+def _workspace(symbol: str, device, *sizes):
+    """The workspace of an entry: (a ``torch.empty`` of ``symbol``(*sizes) bytes, that size as the ABI takes it)."""
+    need = int(getattr(_native.lib(), symbol)(*sizes))
     return torch.empty(max(need, 8), dtype=torch.uint8, device=device), C.c_size_t(need)
+
+
+def _tree_workspace(symbol: str, B: int, T: int, cap: int, device):
+    """The workspace of a long entry: ``symbol``(B, T, max(cap, 1)) bytes."""
+    return _workspace(symbol, device, max(B, 0), max(T, 0), max(int(cap), 1))
+
+
+def _automaton_tail(symbol: str, auto, device, B: int, T: int, *sizes, own=()):
+    """The own arguments of an entry on a ``DesignAutomaton`` (dfa, nested, chain), between the bias and the outputs: the automaton,
+    ``own`` (the chain's count side) and the workspace of ``symbol``(B, T, live states, *sizes) bytes."""
+    return (auto.delta_on(device), auto.kind, auto.n_states, *own, *_workspace(symbol, device, max(B, 0), max(T, 0), auto.n_live, *sizes))
+
+
+def _lengths(m, cu, T: int) -> torch.Tensor:
+    """(B,) lengths on the device, from the mask's row sums or from ``cu_seqlens``; no host synchronisation."""
+    return (m.sum(dim=1) + 0.5).floor() if m is not None else (cu[1:] - cu[:-1]).clamp(0, max(T, 0))
+
+
+def _count_side(mode: str, B: int, T: int, device, m=None, cu=None, gc_content=None, reference=None, budget=None, lengths=None):
+    """What a count entry counts under ``mode`` -> (counted (B,T) uint8, lo (B,), hi (B,) int32, cap), on ``device``: "gc_content" - C|G
+    count everywhere, the window of ``gc_counts`` over the lengths (``lengths``, or from the mask / ``cu_seqlens``), cap T; "mutations" -
+    ``mutation_sets(reference)``, the budget (lo, hi) as window and hi as cap.  No host synchronisation."""
+    B, T = max(B, 0), max(T, 0)
+    if mode == "gc_content":
+        fr = gc_fractions(gc_content, B).to(device, non_blocking=True)
+        lo, hi = gc_counts(fr, _lengths(m, cu, T) if lengths is None else lengths)
+        return torch.full((B, T), 12, dtype=torch.uint8, device=device), lo, hi, T
+    w, cap = count_window(budget, budget[1], B)
+    w = w.to(device, non_blocking=True)
+    return mutation_sets(reference), w[:, 0].contiguous(), w[:, 1].contiguous(), cap
 
 
 def gc_fractions(gc_content, B: int) -> torch.Tensor:
@@ -243,16 +273,13 @@ def design_gc_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = N
     tensor is not read back for that: the kernel clamps it).  ``tree`` (``check_tree``): "lds" - this entry, T <= 1017; "global" -
     ``rnampnn_design_count_long`` with C|G counted everywhere and a cap of T, formed on the device, which returns the same bytes at every
     length; "auto" - "lds" where it fits.  CUDA logits only (there is no CPU fallback)."""
-    def window(B, T, m, cu):
-        fr = gc_fractions(gc_content, max(B, 0)).to(logits.device, non_blocking=True)
-        lengths = (m.sum(dim=1) + 0.5).floor() if m is not None else (cu[1:] - cu[:-1]).clamp(0, max(T, 0))
-        return gc_counts(fr, lengths)
-
-    def long_window(B, T, m, cu):
-        counted = torch.full((max(B, 0), max(T, 0)), 12, dtype=torch.uint8, device=logits.device)
-        return (counted, *window(B, T, m, cu), T, *_tree_workspace("rnampnn_design_count_long_workspace_bytes", B, T, T, logits.device))
+    def window(long):
+        def tail(B, T, m, cu):
+            side = _count_side("gc_content", B, T, logits.device, m, cu, gc_content=gc_content)
+            return (*side, *_tree_workspace("rnampnn_design_count_long_workspace_bytes", B, T, T, logits.device)) if long else side[1:3]
+        return tail
     return _by_tree(tree, lambda long: _design_call(
-        "rnampnn_design_gc", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints, tail=long_window if long else window,
+        "rnampnn_design_gc", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints, tail=window(long),
         outputs=((torch.int32, True), (torch.int32, False)), entry="rnampnn_design_count_long" if long else None))
 
 
@@ -434,11 +461,8 @@ def design_dfa_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = 
     if auto is None:
         raise ValueError("require is required: a DesignAutomaton or motif strings (DesignAutomaton.from_motifs(['GGAGG'], max_run=3))")
 
-    def automaton(B, T, m, cu):
-        need = int(_native.lib().rnampnn_design_dfa_workspace_bytes(max(B, 0), max(T, 0), auto.n_live))
-        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=logits.device)
-        return auto.delta_on(logits.device), auto.kind, auto.n_states, ws, C.c_size_t(need)
-    return _design_call("rnampnn_design_dfa", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints, tail=automaton,
+    return _design_call("rnampnn_design_dfa", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints,
+                        tail=lambda B, T, m, cu: _automaton_tail("rnampnn_design_dfa_workspace_bytes", auto, logits.device, B, T),
                         outputs=((torch.int32, True), (torch.int32, True), (torch.int32, False)))
 
 
@@ -477,11 +501,8 @@ def design_nested_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor]
     if auto is None:
         raise ValueError("require or avoid is required: a DesignAutomaton or motif strings (require=['GNRA'], avoid=['GGGG'], max_run=3)")
 
-    def automaton(B, T, m, cu):
-        need = int(_native.lib().rnampnn_design_nested_workspace_bytes(max(B, 0), max(T, 0), auto.n_live))
-        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=logits.device)
-        return auto.delta_on(logits.device), auto.kind, auto.n_states, ws, C.c_size_t(need)
-    return _design_call("rnampnn_design_nested", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints, tail=automaton,
+    return _design_call("rnampnn_design_nested", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints,
+                        tail=lambda B, T, m, cu: _automaton_tail("rnampnn_design_nested_workspace_bytes", auto, logits.device, B, T),
                         outputs=((torch.int32, True), (torch.int32, True), (torch.int32, False), (torch.int32, False)))
 
 
@@ -540,18 +561,11 @@ def design_dfa_count_from_logits(logits: torch.Tensor, mask: Optional[torch.Tens
     padded = () if mutations is None else (("the reference of mutations", mutations[0], torch.int32),)
 
     def chain(B, T, m, cu, *ref):
-        Bn, Tn = max(B, 0), max(T, 0)
         if mutations is None:
-            fr = gc_fractions(gc_content, Bn).to(device, non_blocking=True)
-            lengths = (m.sum(dim=1) + 0.5).floor() if m is not None else (cu[1:] - cu[:-1]).clamp(0, Tn)
-            counted, (lo, hi), cap = torch.full((Bn, Tn), 12, dtype=torch.uint8, device=device), gc_counts(fr, lengths), Tn
+            side = _count_side("gc_content", B, T, device, m, cu, gc_content=gc_content)
         else:
-            w, cap = count_window(mutations[1], mutations[1][1], Bn)
-            w = w.to(device, non_blocking=True)
-            counted, lo, hi = mutation_sets(ref[0]), w[:, 0].contiguous(), w[:, 1].contiguous()
-        need = int(_native.lib().rnampnn_design_dfa_count_workspace_bytes(Bn, Tn, auto.n_live, max(int(cap), 1)))
-        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=device)
-        return auto.delta_on(device), auto.kind, auto.n_states, counted, lo, hi, int(cap), ws, C.c_size_t(need)
+            side = _count_side("mutations", B, T, device, reference=ref[0], budget=mutations[1])
+        return _automaton_tail("rnampnn_design_dfa_count_workspace_bytes", auto, device, B, T, max(int(side[3]), 1), own=(*side[:3], int(side[3])))
     return _design_call("rnampnn_design_dfa_count", logits, mask, cu_seqlens, max_len, n_samples, temperature, seed, constraints,
                         padded=padded, tail=chain,
                         outputs=((torch.int32, True), (torch.int32, True), (torch.int32, True), (torch.int32, False), (torch.int32, False),
@@ -626,6 +640,74 @@ def design_mode(states=None, gc_content=None, distinct=None, mutations=None, avo
     return "plain"
 
 
+def resolve_design(constraints=None, states=None, lengths=None, gc_content=None, distinct=None, mutations=None, avoid=None, require=None,
+                   pairs=None, combine=None, tree: str = "lds", run=None):
+    """What every ``design(...)`` - both models' and both command-line ``predict`` - does with its arguments before its forward pass ->
+    (mode, mutations, avoid, require) as ``design_by_mode`` takes them.  Touches no device; what is not built is a ``ValueError`` here, in
+    one order: ``design_mode``, ``check_tree``, ``check_mutations``, the automaton of the mode (``check_chain`` / ``check_nested`` /
+    ``check_require``, else ``check_avoid``), ``check_state_lengths``.  ``run(tree, mode)``: the command line's hook - it makes its own
+    checks of the tree and returns its forms of the four automaton checks, (chain, nested, require)(require, avoid) and avoid(avoid),
+    which know ``samples`` and a constraints TABLE (``rnampnn.utils.predict.resolve_run``); ``mutations`` then passes through unread.
+
+    The arguments, for every caller (the return tuple of each mode stands with ``RNAMPNN.design`` / ``RNAModel.design``):
+    ``constraints`` (``rnampnn.utils.constraints.DesignConstraints``: fixed nucleotides, base pairs of a target structure, bias): the
+    draws come from ``rnampnn_design``, which honours them and scores in the same launch; ``infeasible`` counts the positions whose
+    constraint could not be honoured.  ``states`` / ``state_weights``: multi-state design (``design_from_logits``) - the consecutive rows
+    of a group are states of ONE design and receive the same sequence.  ``lengths``: the loader's host-side lengths; with them a group
+    whose states differ in length is refused naming the group (nothing reads the mask on the host; without them such a group is designed
+    over its common prefix).  ``gc_content`` (a pair of fractions, or (B,2)): the draws, under ``constraints`` or free, are conditioned
+    exactly on the G+C content of every RNA lying in that window (``design_gc_from_logits``); not built together with ``states``.
+    ``distinct`` ("sample" or "best"): ``n_samples`` pairwise DIFFERENT sequences per RNA (``design_distinct_from_logits``), an exact
+    sample without replacement or the most probable admitted sequences in descending order; not built together with ``states`` or
+    ``gc_content``.  ``mutations`` (``(reference, max)`` or ``(reference, min, max)``, reference (B,T) class ids, e.g. the native
+    sequence): the draws differ from the reference at between min (default 0) and max positions, drawn exactly from the model's
+    distribution conditioned on that (``design_count_from_logits``); ``mut_miss`` = how far the structure and the fixed positions alone
+    push the count out of the budget, 0 when it is reachable; not built together with ``states``, ``gc_content`` or ``distinct``.
+    ``avoid`` (a ``rnampnn.utils.motifs.MotifAutomaton`` or motif strings such as ``["GGGG", "GAAUUC"]``): no draw contains one of the
+    motifs, drawn exactly from the model's distribution conditioned on that, under the fixed positions and the bias of ``constraints`` or
+    free (``design_avoid_from_logits``); ``avoid_miss`` = 1 for an RNA whose fixed positions spell a motif; not built together with the
+    modes above or with constraints that carry base pairs.  ``require`` (a ``rnampnn.utils.motifs.DesignAutomaton`` or motif strings such
+    as ``["GGAGG", "GNRA"]``): every draw contains EVERY one of the motifs somewhere and none of ``avoid``, which it absorbs
+    (``design_dfa_from_logits``); ``dfa_miss`` = 1 for an RNA that cannot hold the motifs; not built together with the modes above or with
+    base pairs.  ``pairs="nested"`` (``None``: everything above, unchanged): ``avoid`` and / or ``require`` UNDER the base pairs of
+    ``constraints`` (``design_nested_from_logits``) - the structure is honoured and the draws are exact as long as it is nested;
+    ``nest_miss`` = 1 for an RNA whose pairs cross: it is drawn as plain ``constraints`` draw it; host-side constraints whose structure
+    crosses, another mode, another value, or neither ``avoid`` nor ``require`` are refused.  ``tree`` ("lds", the default: everything
+    above, unchanged; "global"; "auto"): where the count tree of ``gc_content`` and ``mutations`` lives (``check_tree``) - in global
+    memory RNAs of up to 32,744 nt are drawn under a G+C window, with the same bytes wherever both homes run; anything but "lds" with
+    another mode is refused.  ``combine="chain"`` (``None``: everything above, unchanged): ``avoid`` and / or ``require`` TOGETHER with
+    ``gc_content`` or ``mutations`` (``design_dfa_count_from_logits``), exact in both conditions at once; ``count`` = the C or G ids / the
+    mutations of each draw; another value, no motif argument, both counts or neither, ``states``, ``distinct``, ``pairs``, a ``tree``
+    other than "lds" and constraints that carry base pairs are refused."""
+    mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require, pairs=pairs, combine=combine, tree=tree)
+    if run is None:
+        check_tree(tree, mode)
+        mutations = check_mutations(mutations)
+    chain, nested, required, avoided = run(tree, mode) if run is not None else (
+        lambda r, a: check_chain(constraints, r, a), lambda r, a: check_nested(r, a, constraints), lambda r, a: check_require(r, a, constraints),
+        lambda a: check_avoid(a, constraints))
+    if mode == "chain":
+        require, avoid = chain(require, avoid), None
+    elif mode == "nested":
+        require, avoid = nested(require, avoid), None
+    else:
+        require = required(require, avoid)
+        avoid = avoided(avoid) if require is None else None
+    if run is None and states is not None and lengths is not None:
+        check_state_lengths(states, lengths)
+    return mode, mutations, avoid, require
+
+
+def resolve_profile(constraints=None, gc_content=None, mutations=None, avoid=None, tree: str = "lds") -> str:
+    """What both models' ``design_profile`` check before their forward pass -> the mode: the pairings ``design`` refuses, the home of the
+    tree (``check_profile_tree``), the form of ``mutations`` and ``avoid`` together with base pairs.  Touches no device."""
+    mode = design_mode(gc_content=gc_content, mutations=mutations, avoid=avoid)
+    check_profile_tree(tree, mode)
+    check_mutations(mutations)
+    check_avoid(avoid, constraints)
+    return mode
+
+
 def design_by_mode(mode: str, logits: torch.Tensor, states=None, state_weights=None, gc_content=None, distinct=None, mutations=None,
                    avoid=None, require=None, tree: str = "lds", **kw):
     """The ``*_from_logits`` call of ``mode`` (``design_mode``) -> what that function returns.  ``mutations`` as ``check_mutations``
@@ -681,13 +763,8 @@ def profile_mode_args(mode: str, B: int, T: int, device, lengths=None, gc_conten
     (lo, hi) as window and hi as cap; "avoid" - the automaton's tables.  No host synchronisation."""
     if mode == "avoid":
         return auto.delta_on(device), auto.n_states, C.c_uint64(auto.terminal)
-    if mode == "gc_content":
-        lo, hi = gc_counts(gc_fractions(gc_content, B).to(device, non_blocking=True), lengths)
-        return torch.full((B, T), 12, dtype=torch.uint8, device=device), lo, hi, T
-    if mode == "mutations":
-        w, cap = count_window(budget, budget[1], B)
-        w = w.to(device, non_blocking=True)
-        return mutation_sets(reference), w[:, 0].contiguous(), w[:, 1].contiguous(), cap
+    if mode in ("gc_content", "mutations"):
+        return _count_side(mode, B, T, device, gc_content=gc_content, reference=reference, budget=budget, lengths=lengths)
     if mode != "plain":
         raise ValueError(f"no profile is built for the mode {mode!r}")
     zero = torch.zeros(B, dtype=torch.int32, device=device)
@@ -716,9 +793,7 @@ def design_profile_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor
     padded = (("the reference of mutations", mutations[0], torch.int32),) if mode == "mutations" else ()
     lg, m, cu, B, T, own, al, pa, bi, per_position, wobble = _design_inputs(name, logits, mask, cu_seqlens, max_len, constraints, padded)
     device, Bn, Tn = lg.device, max(B, 0), max(T, 0)
-    lengths = None
-    if mode == "gc_content":
-        lengths = (m.sum(dim=1) + 0.5).floor() if m is not None else (cu[1:] - cu[:-1]).clamp(0, Tn)
+    lengths = _lengths(m, cu, Tn) if mode == "gc_content" else None
     its = profile_mode_args(mode, Bn, Tn, device, lengths, gc_content=gc_content, reference=own[0] if own else None,
                             budget=None if mutations is None else mutations[1], auto=auto)
     marg = torch.empty(Bn, Tn, 4, dtype=torch.float64, device=device)

@@ -25,7 +25,7 @@ from ..utils.data import check_prefix_mask
 from ._base import NativeModule, _prep, _ptr, _stream
 from .decode import (SCORE_OUTPUTS, argmax_recovery, check_avoid, check_chain, check_distinct, check_nested, check_require, check_mutations, check_state_lengths, check_profile_tree, check_tree, design_by_mode,  # noqa: F401
                      design_distinct_from_logits, design_from_logits, design_gc_from_logits, design_mode, design_mutations_from_logits,
-                     design_profile_from_logits,
+                     design_profile_from_logits, resolve_design, resolve_profile,
                      letters_packed, letters_padded, sample_from_logits, score_logits)
 from ._schema import DEFAULT_HPARAMS
 
@@ -549,58 +549,20 @@ class RNAMPNN(NativeModule):
     def design(self, coords: torch.Tensor, mask: torch.Tensor, n_samples: int = 8, temperature: float = 0.1, seed: int = 0,
                T_norm: int = 0, constraints=None, states=None, state_weights=None, lengths=None, gc_content=None, distinct=None, mutations=None,
                avoid=None, require=None, pairs=None, tree: str = "lds", combine=None):
-        """``sample`` plus the score of every draw against the SAME logits, with one forward: -> (seqs int8 (n_samples,B,T), -1 on
-        padding; seq_nll (n_samples,B) f32).  The NLL is the model's own (temperature 1) likelihood, so designs drawn at different
-        temperatures rank on one scale.  ``constraints`` (``rnampnn.utils.constraints.DesignConstraints``: fixed nucleotides, base
-        pairs of a target structure, bias): the draws come from ``rnampnn_design`` instead, which honours them and scores in the same
-        launch -> (seqs, seq_nll, infeasible (B,) int32 = positions whose constraint could not be honoured).  ``states`` / ``state_weights``:
-        multi-state design (``design_from_logits``): the rows of a group are states of one design -> the same triple.  ``lengths``: the
-        loader's host-side lengths; with them a group whose states differ in length is a ``ValueError`` naming the group (nothing here reads
-        the mask on the host; without them such a group is designed over its common prefix).  ``gc_content`` (a pair of fractions, or
-        (B,2)): the draws - under ``constraints`` or free - are conditioned exactly on the G+C content of every RNA lying in that window
-        (``design_gc_from_logits``) -> (seqs, seq_nll, infeasible, gc_count (n_samples,B) int32, gc_miss (B,) int32); not built together
-        with ``states``.  ``distinct`` ("sample" or "best"; ``None`` is everything above, unchanged): ``n_samples`` pairwise DIFFERENT
-        sequences per RNA (``design_distinct_from_logits``) - an exact sample without replacement, or the most probable admitted sequences
-        in descending order - under ``constraints`` or free -> (seqs, seq_nll, infeasible, logp (n_samples,B) f32, n_distinct (B,) int32); not
-        built together with ``states`` or ``gc_content``.  ``mutations`` (``(reference, max)`` or ``(reference, min, max)``, reference (B,T)
-        class ids, e.g. the native sequence): the draws - under ``constraints`` or free - differ from the reference at between min
-        (default 0) and max positions, drawn exactly from the model's distribution conditioned on that (``design_count_from_logits``) ->
-        (seqs, seq_nll, infeasible, n_mut (n_samples,B) int32, mut_miss (B,) int32 = how far the structure and the fixed positions alone
-        push the count out of the budget, 0 when it is reachable); not built together with ``states``, ``gc_content`` or ``distinct``.
-        ``avoid`` (a ``rnampnn.utils.motifs.MotifAutomaton`` or motif strings such as ``["GGGG", "GAAUUC"]``): no draw contains one of the
-        motifs - drawn exactly from the model's distribution conditioned on that, under the fixed positions and the bias of
-        ``constraints`` or free (``design_avoid_from_logits``) -> (seqs, seq_nll, infeasible, hits (n_samples,B) int32, avoid_miss (B,)
-        int32 = 1 for an RNA whose fixed positions spell a motif); not built together with the other modes, and constraints that carry
-        base pairs are a ``ValueError`` before the forward pass.
-        ``require`` (a ``rnampnn.utils.motifs.DesignAutomaton`` or motif strings such as ``["GGAGG", "GNRA"]``): every draw contains EVERY
-        one of the motifs somewhere, and none of ``avoid`` (motif strings or a ``MotifAutomaton``), which it absorbs - drawn exactly from
-        the model's distribution conditioned on that (``design_dfa_from_logits``) -> (seqs, seq_nll, infeasible, hits (n_samples,B) int32,
-        accepted (n_samples,B) int32, dfa_miss (B,) int32 = 1 for an RNA that cannot hold the motifs); not built together with the other
-        modes, and constraints that carry base pairs are a ``ValueError`` before the forward pass.  ``pairs="nested"`` (``None`` is everything above, unchanged): ``avoid``
-        and / or ``require`` UNDER the base pairs of ``constraints`` (``design_nested_from_logits``): the structure is honoured and the
-        draws are exact as long as it is nested -> (seqs, seq_nll, infeasible, hits, accepted, dfa_miss, nest_miss (B,) int32 = 1 for an
-        RNA whose pairs cross: it is drawn as plain ``constraints`` draw it); host-side constraints whose structure crosses, another
-        mode, another value, or neither ``avoid`` nor ``require`` are a ``ValueError`` before the forward pass.  ``tree`` ("lds", the
-        default: everything above, unchanged; "global"; "auto"): where the count tree of ``gc_content`` and ``mutations`` lives
-        (``check_tree``) - in global memory RNAs of up to 32,744 nt are drawn under a G+C window, with the same bytes wherever both homes
-        run; anything but "lds" with another mode is a ``ValueError`` before the forward pass.  ``combine="chain"`` (``None`` is
-        everything above, unchanged): ``avoid`` and / or ``require`` TOGETHER with ``gc_content`` or ``mutations``
-        (``design_dfa_count_from_logits``), exact in both conditions at once -> (seqs, seq_nll, infeasible, hits, accepted, count
-        (n_samples,B) int32 = the C or G ids / the mutations of each draw, dfa_miss (B,) int32, count_miss (B,) int32, log_z (B,) f64);
-        another value, no motif argument, both counts or neither, ``states``, ``distinct``, ``pairs``, a ``tree`` other than "lds" and
-        constraints that carry base pairs are a ``ValueError`` before the forward pass."""
-        mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require, pairs=pairs, combine=combine, tree=tree)
-        check_tree(tree, mode)
-        mutations = check_mutations(mutations)
-        if mode == "chain":
-            require, avoid = check_chain(constraints, require, avoid), None
-        elif mode == "nested":
-            require, avoid = check_nested(require, avoid, constraints), None
-        else:
-            require = check_require(require, avoid, constraints)
-            avoid = check_avoid(avoid, constraints) if require is None else None
-        if states is not None and lengths is not None:
-            check_state_lengths(states, lengths)
+        """``sample`` plus the score of every draw against the SAME logits, with one forward on the padded batch (``coords`` (B,T,7,3),
+        ``mask`` (B,T)): -> (seqs int8 (n_samples,B,T), -1 on padding; seq_nll (n_samples,B) f32).  The NLL is the model's own
+        (temperature 1) likelihood, so designs drawn at different temperatures rank on one scale.  That pair is the FREE draw: no
+        ``constraints`` and no mode.  With ``constraints`` or any mode the draws come from the design family (``design_by_mode``) in one
+        launch that scores them too, and the return grows by mode (S = ``n_samples``):
+        "plain" (``constraints``) and "states" -> (seqs, seq_nll, infeasible (B,) int32);
+        and in every other mode that triple plus - "gc_content": gc_count (S,B) int32, gc_miss (B,) int32; "distinct": logp (S,B) f32,
+        n_distinct (B,) int32; "mutations": n_mut (S,B) int32, mut_miss (B,) int32; "avoid": hits (S,B) int32, avoid_miss (B,) int32;
+        "require": hits, accepted (S,B) int32, dfa_miss (B,) int32; ``pairs="nested"``: hits, accepted, dfa_miss, nest_miss (B,) int32;
+        ``combine="chain"``: hits, accepted, count (S,B) int32, dfa_miss, count_miss (B,) int32, log_z (B,) f64.
+        What each argument means, which pairings are built and what is refused - every refusal is a ``ValueError`` before the forward
+        pass - stands once, on ``rnampnn.model.decode.resolve_design``."""
+        mode, mutations, avoid, require = resolve_design(constraints, states, lengths, gc_content, distinct, mutations, avoid, require, pairs,
+                                                         combine, tree)
         logits = self._run(coords, mask, T_norm=T_norm)["logits"]
         if mode != "plain" or constraints is not None:
             return design_by_mode(mode, logits, mask=mask, n_samples=n_samples, temperature=temperature, seed=seed, constraints=constraints,
@@ -619,9 +581,7 @@ class RNAMPNN(NativeModule):
         in ``design``; the pairings that ``design`` refuses are refused here with the same messages, before the forward pass.  ``lengths``
         is accepted for symmetry with ``design`` and not read.  No profile is built for ``states`` or ``distinct``.  ``tree`` as in
         ``design``, for every profile but ``avoid``'s."""
-        check_profile_tree(tree, design_mode(gc_content=gc_content, mutations=mutations, avoid=avoid))
-        check_mutations(mutations)
-        check_avoid(avoid, constraints)
+        resolve_profile(constraints, gc_content, mutations, avoid, tree)
         was_training = self.training
         self.eval()
         try:

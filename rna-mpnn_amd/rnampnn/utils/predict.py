@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from ..config.glob import VOCAB
-from ..model.decode import (check_avoid, check_budget, check_chain, check_profile_tree, check_tree, check_nested, check_require, design_by_mode, design_mode, design_profile_from_logits, letters_packed, letters_padded,
+from ..model.decode import (resolve_design, check_avoid, check_budget, check_chain, check_profile_tree, check_tree, check_nested, check_require, design_by_mode, design_profile_from_logits, letters_packed, letters_padded,
                             sample_from_logits, score_logits)
 from .constraints import batch_constraints, crossing_pairs, mutation_references, padded_references, parse_dot_bracket
 from .data import PackedLoader, bucket_batches, fill_nan_deterministic, read_fasta
@@ -149,6 +149,14 @@ def check_profile(profile_prefix, states=None, distinct=None) -> None:
                          "mutation-budget and motif-avoiding single-state draws")
 
 
+def refuse_structures(what: str, constraints) -> None:
+    """``ValueError`` naming the first ids of a constraints table whose ``structure`` is not empty: ``what`` is not built with base pairs."""
+    paired = sorted(rid for rid, (_, structure) in (constraints or {}).items() if structure)
+    if paired:
+        raise ValueError(f"{what} together with base pairs is not built (an exact draw would carry every open pair in the automaton's "
+                         f"state): drop `structure` from the constraints of {paired[:3]}{' ...' if len(paired) > 3 else ''}")
+
+
 def check_require_run(require, avoid, samples: int, profile_prefix, constraints) -> object:
     """``predict(..., require=...)`` -> the ``DesignAutomaton`` that holds ``require`` and ``avoid``, or None without ``require``.
     ``ValueError`` without samples, with a profile (none is built for this mode) and with a structure in ``constraints``; touches no
@@ -160,10 +168,7 @@ def check_require_run(require, avoid, samples: int, profile_prefix, constraints)
         raise ValueError("a design profile together with require is not built: the profile entries know forbidden motifs only")
     if samples <= 0:
         raise ValueError("required motifs need samples > 0")
-    paired = sorted(rid for rid, (_, structure) in (constraints or {}).items() if structure)
-    if paired:
-        raise ValueError(f"require together with base pairs is not built (an exact draw would carry every open pair in the automaton's "
-                         f"state): drop `structure` from the constraints of {paired[:3]}{' ...' if len(paired) > 3 else ''}")
+    refuse_structures("require", constraints)
     return auto
 
 
@@ -176,10 +181,7 @@ def check_chain_run(require, avoid, samples: int, profile_prefix, constraints) -
                          "not both")
     if samples <= 0:
         raise ValueError("motifs under a count window need samples > 0")
-    paired = sorted(rid for rid, (_, structure) in (constraints or {}).items() if structure)
-    if paired:
-        raise ValueError(f"combine='chain' together with base pairs is not built (an exact draw would carry every open pair in the automaton's "
-                         f"state): drop `structure` from the constraints of {paired[:3]}{' ...' if len(paired) > 3 else ''}")
+    refuse_structures("combine='chain'", constraints)
     return auto
 
 
@@ -203,6 +205,35 @@ def check_nested_run(require, avoid, samples: int, profile_prefix, constraints) 
         raise ValueError(f"pairs='nested': the structure of {knotted[:3]}{' ...' if len(knotted) > 3 else ''} holds a pseudoknot (two of its "
                          "pairs cross); the exact draw under motifs walks a nested structure: drop the crossing pairs")
     return auto
+
+
+def check_avoid_run(avoid, samples: int, profile_prefix, constraints) -> object:
+    """``predict(..., avoid=...)`` without ``require`` -> the ``MotifAutomaton``, or None without ``avoid``.  ``ValueError`` without
+    samples or a profile and with a structure in ``constraints``; touches no device."""
+    auto = check_avoid(avoid)
+    if auto is None:
+        return None
+    if samples <= 0 and not profile_prefix:
+        raise ValueError("forbidden motifs need samples > 0")
+    refuse_structures("avoid", constraints)
+    return auto
+
+
+def resolve_run(samples: int, profile_prefix, constraints, states=None, **given):
+    """``resolve_design`` as both command-line ``predict`` call it, before the first forward pass -> (mode, avoid, require): the checks
+    in their ``*_run`` forms, which know ``samples``, the profile and the constraints TABLE; ``given``: gc_content, distinct, mutations
+    (min, max, references), avoid, require, pairs, combine, tree."""
+    def run(tree, mode):
+        check_tree(tree, mode) if samples > 0 or not profile_prefix else check_profile_tree(tree, mode)
+        check_profile(profile_prefix, states, given.get("distinct"))
+        return [lambda r, a, f=f: f(r, a, samples, profile_prefix, constraints) for f in (check_chain_run, check_nested_run, check_require_run)] + [
+            lambda a: check_avoid_run(a, samples, profile_prefix, constraints)]
+    mode, mutations, avoid, require = resolve_design(states=states, run=run, **given)
+    if mutations is not None:
+        check_budget(mutations[0], mutations[1])
+        if samples <= 0 and not profile_prefix:
+            raise ValueError("a mutation budget needs samples > 0")
+    return mode, avoid, require
 
 
 def profile_batch(store: dict, idx, lens, logits, cu, max_len: int, temperature: float, cons, gc_content, mutations, avoid,
@@ -278,28 +309,9 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     ``mutations`` - the draws come from ``rnampnn_design_dfa_count`` and hold both conditions exactly; ``designs_csv`` gains the last
     columns ``motif_hits``, ``required_found``, ``require_miss`` and then ``gc_count``, ``gc_miss`` or ``mutations``, ``mut_miss``.  Not
     built together with ``states``, ``distinct``, ``pairs``, a profile, a ``tree`` other than "lds" or a ``structure`` in ``constraints``."""
-    mode = design_mode(states, gc_content, distinct, mutations, avoid, require=require, pairs=pairs, combine=combine, tree=tree)
-    check_tree(tree, mode) if samples > 0 or not profile_prefix else check_profile_tree(tree, mode)
-    check_profile(profile_prefix, states, distinct)
+    mode, avoid, require = resolve_run(samples, profile_prefix, constraints, states, gc_content=gc_content, distinct=distinct, mutations=mutations,
+                                       avoid=avoid, require=require, pairs=pairs, combine=combine, tree=tree)
     count = "gc_content" if gc_content is not None else "mutations"     # (what the chain counts: it names its columns)
-    if mode == "chain":
-        require, avoid = check_chain_run(require, avoid, samples, profile_prefix, constraints), None
-    elif mode == "nested":
-        require, avoid = check_nested_run(require, avoid, samples, profile_prefix, constraints), None
-    else:
-        require = check_require_run(require, avoid, samples, profile_prefix, constraints)
-        avoid = check_avoid(avoid) if require is None else None
-    if avoid is not None:
-        if samples <= 0 and not profile_prefix:
-            raise ValueError("forbidden motifs need samples > 0")
-        paired = sorted(rid for rid, (_, structure) in (constraints or {}).items() if structure)
-        if paired:
-            raise ValueError(f"avoid together with base pairs is not built (an exact draw would carry every open pair in the automaton's "
-                             f"state): drop `structure` from the constraints of {paired[:3]}{' ...' if len(paired) > 3 else ''}")
-    if mutations is not None:
-        check_budget(mutations[0], mutations[1])
-        if samples <= 0 and not profile_prefix:
-            raise ValueError("a mutation budget needs samples > 0")
     model.eval()
     device = model._device()
     items = load_structures(data_path, max_len=int(model.hparams["padding_len"]))

@@ -37,7 +37,7 @@ int main() {
     EXPECT(dfc_lds_bytes(72) == 11776 && dfc_lds_bytes(300) == 33856 && dfc_lds_bytes(1616) == 162560 && dfc_lds_bytes(1617) == 164672);
     EXPECT(ds_max_T([](long long t) { return dfc_lds_bytes(t); }) == 1616);
     EXPECT(dfc_slab_bytes(13, 8) == 1872 && dfc_slab_bytes(73, 72) == 85264 && dfc_slab_bytes(256, 72) == 299008);
-    EXPECT(dfc_words(1) == 1 && dfc_words(16) == 1 && dfc_words(17) == 3 && dfc_words(1616) == 101);
+    EXPECT(dfa_words(1) == 1 && dfa_words(16) == 1 && dfa_words(17) == 3 && dfa_words(1616) == 101);
     // ---- the checks; the "device" pointers are host memory that nothing dereferences before the call returns
     const int B = 2, T = 40, A = 5, CAP = 6;
     alignas(16) static float logits[B * T * 4];

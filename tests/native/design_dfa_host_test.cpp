@@ -1,5 +1,6 @@
 // The host side of rnampnn_design_dfa (rna-mpnn_amd/csrc/design_dfa.hip) as a stand-alone program: the size formulas and every check
-// that returns before a launch - the BAD_ARG cases, the workspace, the partner refusal, the LDS ceiling and "nothing asked for".  It
+// that returns before a launch - the BAD_ARG cases, the workspace, the partner refusal, the LDS ceiling and "nothing asked for" - and
+// what dfa_chain_dev.h's dfa_prepare leaves in the automaton's arguments for the three entries that share it (live, dead[], acc[]).  It
 // includes the translation unit itself (compiled for the host only), supplies the library's fail() and never reaches a launch, so it
 // runs on a machine without a GPU; tests/test_design_dfa_host_cpu.py builds it with the address and undefined-behaviour sanitizers.
 #include <cstdarg>
@@ -68,7 +69,9 @@ int main() {
     dead0[0] = 3;
     EXPECT(call(logits, mask, nullptr, B, T, 1.f, 8, delta, dead0.data(), A, ws.data(), need, nullptr, true) == BAD && std::strstr(g_error, "marked dead"));
     EXPECT(call(logits, mask, nullptr, B, T, 1.f, 8, delta, kind.data(), A, nullptr, need, nullptr, true) == BAD && std::strstr(g_error, "is null"));
-    EXPECT(call(logits, mask, nullptr, B, T, 1.f, 8, delta, kind.data(), A, ws.data(), need - 1, nullptr, true) == BAD && std::strstr(g_error, "too small"));
+    EXPECT(call(logits, mask, nullptr, B, T, 1.f, 8, delta, kind.data(), A, ws.data(), need - 1, nullptr, true) == BAD && std::strstr(g_error, "too small") &&
+           std::strstr(g_error, "rnampnn_design_dfa: the workspace is too small (2559 bytes), the table of partition sums at (B = 2, T = 40, 4 live states) "
+                                "needs 2560 (rnampnn_design_dfa_workspace_bytes)"));
     EXPECT(call(logits, mask, nullptr, B, T, 1.f, 8, delta, kind.data(), A, ws.data(), 0, nullptr, true) == BAD);
     EXPECT(call(logits, mask, nullptr, B, T, 1.f, 8, delta, kind.data(), A, (char*)ws.data() + 4, need, nullptr, true) == BAD && std::strstr(g_error, "aligned"));
     EXPECT(call(logits, mask, nullptr, B, T, 1.f, 8, delta, kind.data(), A, ws.data(), need, partner, true) == UNS && std::strstr(g_error, "4^depth"));
@@ -89,6 +92,40 @@ int main() {
     std::vector<double> w2(rnampnn_design_dfa_workspace_bytes(B, T, 256) / 8);
     EXPECT(call(logits, mask, nullptr, B, T, 1.f, 8, delta, full.data(), 256, w2.data(), w2.size() * 8, nullptr, false) == RNAMPNN_OK);
     EXPECT(call(logits, mask, nullptr, B, T, 1.f, 8, delta, full.data(), 256, w2.data(), w2.size() * 8 - 8, nullptr, false) == BAD);
+    // ---- the shared prologue (dfa_prepare): `kind` is read once - the count the workspace check is given is the `live` the kernel gets -
+    // and dead[] / acc[] hold a bit per state in all four 64-bit words: 193 states, dead at 63, 127 and 191, accepting at 5, 64 and 192
+    {
+        const int N = 193;
+        std::vector<uint8_t> wide(N, 0);
+        wide[63] = wide[127] = 1;
+        wide[191] = 3;                                              // dead wins over accepting
+        wide[5] = wide[64] = wide[192] = 2;
+        std::vector<double> w5(rnampnn_design_dfa_workspace_bytes(B, T, N) / 8);
+        DfaArgs a{};
+        int asked = 0, told = -1;
+        g_error[0] = 0;
+        const int rc = dfa_prepare("shared", logits, (int64_t)B * T, mask, nullptr, B, T, 1.f, 8, 1, nullptr, nullptr, nullptr, 1, nullptr, 0, seqs, nullptr,
+                                   nullptr, delta, wide.data(), N, w5.data(), w5.size() * 8, nullptr, nullptr, nullptr, true, a,
+                                   [] { return RNAMPNN_OK; }, [&](int live, char* what, size_t len) {
+            ++asked;
+            told = live;
+            std::snprintf(what, len, "the test's table needs");
+            return rnampnn_design_dfa_workspace_bytes(B, T, live);
+        });
+        EXPECT(rc == RNAMPNN_OK && asked == 1 && told == 190 && a.live == 190 && a.A == N && a.S == 8 && a.words == dfa_words(T));
+        EXPECT(a.dead[0] == 1ull << 63 && a.dead[1] == 1ull << 63 && a.dead[2] == 1ull << 63 && a.dead[3] == ~1ull);
+        EXPECT(a.acc[0] == 1ull << 5 && a.acc[1] == 1ull && a.acc[2] == 0 && a.acc[3] == 1ull);
+        EXPECT(a.delta == delta && a.tab == w5.data() && !a.hits && !a.accepted && !a.dfa_miss && a.seqs == seqs);
+        // one byte short of what `live` states need: the message is built from the entry's words, the count and the name
+        const int rc2 = dfa_prepare("shared", logits, (int64_t)B * T, mask, nullptr, B, T, 1.f, 8, 1, nullptr, nullptr, nullptr, 1, nullptr, 0, seqs,
+                                    nullptr, nullptr, delta, wide.data(), N, w5.data(), (size_t)8 * B * T * 190 - 1, nullptr, nullptr, nullptr, true, a,
+                                    [] { return RNAMPNN_OK; }, [&](int live, char* what, size_t len) {
+            std::snprintf(what, len, "the test's table at %d live states needs", live);
+            return rnampnn_design_dfa_workspace_bytes(B, T, live);
+        });
+        EXPECT(rc2 == BAD && std::strstr(g_error, "shared: the workspace is too small (121599 bytes), the test's table at 190 live states needs 121600 "
+                                                  "(shared_workspace_bytes)"));
+    }
     if (g_bad) return 1;
     std::printf("design_dfa_host_test: ok\n");
     return 0;

@@ -42,7 +42,7 @@ int main() {
     EXPECT(ns_lds_bytes(1000, 64) == 103488 && ns_lds_bytes(1000, 13) == 102464 && ns_lds_bytes(300, 13) == 32208 && ns_lds_bytes(300, 53) == 57696);
     EXPECT(ns_lds_bytes(1616, 64) == 163552 && ns_lds_bytes(1617, 64) == 165636);
     for (int L : {1, 13, 64}) EXPECT(ds_max_T([L](long long t) { return ns_lds_bytes(t, L); }) >= 1000);
-    EXPECT(ns_words(1) == 1 && ns_words(16) == 1 && ns_words(17) == 3 && ns_words(1000) == 63);
+    EXPECT(dfa_words(1) == 1 && dfa_words(16) == 1 && dfa_words(17) == 3 && dfa_words(1000) == 63);
     // ---- the checks; the "device" pointers are host memory that nothing dereferences before the call returns
     const int B = 2, T = 40, A = 5;
     alignas(16) static float logits[B * T * 4];
