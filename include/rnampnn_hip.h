@@ -754,6 +754,46 @@ int rnampnn_design_count_profile_long(const float* logits, int64_t n_rows, const
                                       int32_t bias_per_position, const uint8_t* counted, const int32_t* count_lo, const int32_t* count_hi,
                                       int32_t count_cap, void* workspace, size_t workspace_bytes, double* marginals, double* log_z,
                                       double* log_z_free, double* entropy, int32_t* infeasible, int32_t* count_miss, void* stream);
+/* The profile of REQUIRED motifs in ONE launch (csrc/design_dfa_profile.hip): what rnampnn_design_dfa draws FROM, on its automaton of up to
+ * 256 states, with the backward table in GLOBAL memory.  The arguments are rnampnn_design_avoid_profile's up to bias_per_position; then
+ * delta, kind (HOST) and n_states exactly as rnampnn_design_dfa takes them; then workspace and workspace_bytes as in rnampnn_design_dfa,
+ * sized by rnampnn_design_dfa_profile_workspace_bytes(B, T, L) = 8 B T L bytes at L live states (0 when an argument is <= 0): the table
+ * l_t(a) as [b][t][live column] and nothing else; what it held before the call does not matter, what it holds after is unspecified.  Then
+ * the outputs of the profile family, each nullable: marginals (B,T,4) f64 16-byte aligned, log_z, log_z_free, entropy, infeasible and
+ * dfa_miss (B) i32.  The contract is the profile family's (above, at "Design PROFILES"), applied to the distribution rnampnn_design_dfa
+ * samples:
+ *   Backward.  The table l_t(a) is rnampnn_design_dfa's: l_n(a) = 0 for a live accepting state, -inf otherwise; LSE in class order; a cell
+ *     (a, c) is admitted iff m_t has c and delta(a,c) is live.  log_z = l_0(0).  dfa_miss and infeasible are the draw entry's values, byte
+ *     for byte.
+ *   Forward.  alpha_0(0) = 0, alpha_0(a != 0) = -inf; alpha_{t+1}(a') = LSE over the admitted cells (a, c) with delta(a,c) = a' live of
+ *     alpha_t(a) + z_t(c).  P_t(c) = the sum over a of exp(alpha_t(a) + z_t(c) + l_{t+1}(delta(a,c)) - log_z) over the admitted cells whose
+ *     l_{t+1} is finite.  entropy and log_z_free are the family's; marginals is written as 0 at t >= n_b.  (The kernel walks
+ *     q_t(a) = exp(alpha_t(a) + l_t(a) - log_z), the probability that the draw is in state a before position t, through the draw's own
+ *     conditionals exp(z_t(c) + l_{t+1}(delta(a,c)) - l_t(a)): the same sums in [0, 1]; a state whose posterior is below 1e-308 counts 0.)
+ *   Miss.  With dfa_miss = 1 every position is the softmax over its admitted classes - what the draw entry falls back to - and log_z is
+ *     the sum of the positions' LSEs.  An RNA of length 0 has log_z = log_z_free = entropy = 0 and dfa_miss = !(state 0 accepts).
+ *   Anchor.  With A <= 64 and every live state accepting the outputs agree with rnampnn_design_avoid_profile on (delta, A, terminal = the
+ *     dead states) to the family's tolerances (the two sum in different orders) and the flags byte for byte.
+ * The order of summation is not part of the contract; the family's rule of determinism is: two calls give identical bytes, so do the
+ * padded and the packed layout, an RNA alone and in a batch, and whatever the workspace and the outputs held before.  Non-finite logits or
+ * bias of one RNA may make THAT RNA's outputs NaN; nothing faults, no index leaves its array, no other RNA changes.
+ * One 256-thread workgroup per RNA: thread = state runs rnampnn_design_dfa's backward pass into the workspace, then walks forward with
+ * q_t(a) in its register, reading l_t(a) and l_{t+1}(delta(a, .)) from the workspace (written by the same workgroup: a barrier orders
+ * them).  The marginals of a step are a fixed-order reduction of the 1,024 cells by class; the scatter along delta is a segmented sum
+ * over the cells sorted by target, whose time does not depend on the in-degree of a state.  LDS does not grow with T x L.  Dynamic LDS:
+ *       bytes(T) = 32 T + 16 ceil(T / 16) + 15,392
+ *     (the fp64 rows, the masks; the cells of a step, q_{t+1}, the sorted cells, the automaton and the scratch): 25,296 at T = 300,
+ *     68,720 at T = 1616.  RNAMPNN_ERR_UNSUPPORTED when that exceeds 160 KiB = 163,840 bytes, for every automaton alike: T <= 4498
+ *     (163,840 bytes); the message names the bytes, the limit and that T.
+ * No atomics, no runtime fill / copy node, no host synchronisation; the call can sit inside a captured graph.  RNAMPNN_ERR_BAD_ARG, before
+ * anything is launched: the cases of rnampnn_design_dfa but those about S; marginals not 16-byte aligned.  Then the partner refusal
+ * (RNAMPNN_ERR_UNSUPPORTED, in the draw entry's words); with every output null RNAMPNN_OK without a launch, whatever T is; the LDS check. */
+size_t rnampnn_design_dfa_profile_workspace_bytes(int32_t B, int32_t T, int32_t n_live);
+int rnampnn_design_dfa_profile(const float* logits, int64_t n_rows, const float* mask, const int32_t* cu_seqlens, int32_t B, int32_t T,
+                               float temperature, const uint8_t* allowed, const int32_t* partner, int32_t wobble, const float* bias,
+                               int32_t bias_per_position, const uint8_t* delta, const uint8_t* kind, int32_t n_states, void* workspace,
+                               size_t workspace_bytes, double* marginals, double* log_z, double* log_z_free, double* entropy,
+                               int32_t* infeasible, int32_t* dfa_miss, void* stream);
 
 /* -- training ---------------------------------------------------------------------------- */
 /* The training surface of RNAMPNN (rnampnn.py:187-207 + Lightning's loss.backward()):

@@ -99,7 +99,14 @@ computed, not estimated from samples, with or without ``--samples``.  ``PREFIX.p
 ``pdb_id,position,pA,pU,pC,pG`` (position 1-based; a sequence logo, a bias for another tool); ``PREFIX.rnas.csv`` one row per structure,
 ``pdb_id,length,log_mass,entropy,infeasible,miss``: ``log_mass`` <= 0 is the log of the share of the model's mass the constraints keep,
 ``entropy`` (nats) how diverse the designs can be, ``miss`` the mode's ``gc_miss`` / ``mut_miss`` / ``avoid_miss``.  Not built together with
-``--states`` or ``--distinct``."""
+``--states`` or ``--distinct``.
+
+    python rna-mpnn_amd/predict.py --ckpt Final.pt --data DIR --profile-out PREFIX --table global [--require GGAGG,GNRA] [--avoid ..] [--max-run 3] [--samples 8]
+
+Profiles under required motifs (``rnampnn_design_dfa_profile``, both families): ``--table global`` lifts the refusal of ``--require``
+together with ``--profile-out`` - where the motif will land and whether ``log_mass`` is e^-2 or e^-100, computed on the automaton of up to
+256 states with its table in global memory (structures of up to 4498 nt).  It serves ``--avoid`` / ``--max-run`` alone as well; the files
+keep their columns and ``miss`` holds ``dfa_miss``.  Needs ``--profile-out`` and a motif flag; not built together with another mode."""
 from __future__ import annotations
 
 import argparse
@@ -149,6 +156,9 @@ def parse(argv=None):
                     help="chain: --avoid / --max-run / --require hold TOGETHER with --gc-content or --max-mutations, exactly in both")
     ap.add_argument("--profile-out", default=None, help="PREFIX: write the exact distribution the draws come from to PREFIX.positions.csv "
                                                         "(per-position marginals) and PREFIX.rnas.csv (log_mass, entropy)")
+    ap.add_argument("--table", default=None, choices=("lds", "global"),
+                    help="where the table of the --profile-out of --avoid / --max-run / --require lives: lds (the default: forbidden motifs "
+                         "alone, at most 64 states) or global (a workspace in global memory: required motifs too, up to 256 states, 4498 nt)")
     return ap.parse_args(argv)
 
 
@@ -244,12 +254,13 @@ def require_option(args) -> dict:
     ``--profile-out`` and without ``--samples``."""
     if args.require is None:
         return {}
-    for flag, value in (("--profile-out", args.profile_out), ("--states", args.states), ("--gc-content", args.gc_content),
+    profiled = args.table == "global" and args.profile_out is not None          # --table global: the profile of rnampnn_design_dfa_profile
+    for flag, value in (("--profile-out", None if profiled else args.profile_out), ("--states", args.states), ("--gc-content", args.gc_content),
                         ("--distinct", args.distinct), ("--max-mutations", args.max_mutations)):
         if value is not None:
             raise ValueError(f"--require together with {flag} is not built: the automaton conditions plain single-state designs only, and no "
                              "profile is built for it")
-    if args.samples <= 0:
+    if args.samples <= 0 and not profiled:
         raise ValueError("--require needs --samples N > 0")
     from rnampnn.utils.motifs import DesignAutomaton
     return dict(require=DesignAutomaton.from_motifs([m for m in args.require.split(",") if m.strip()],
@@ -321,6 +332,24 @@ def profile_option(args) -> dict:
     return dict(profile_prefix=args.profile_out)
 
 
+def table_option(args) -> dict:
+    """The ``table`` keyword of ``predict`` from ``--table``; empty without the flag.  ``ValueError`` naming the flags for ``global``
+    without ``--profile-out``, without a motif flag or with a mode that is not motifs alone, before the checkpoint is opened."""
+    if args.table is None:
+        return {}
+    if args.table == "global":
+        if args.profile_out is None:
+            raise ValueError("--table global needs --profile-out PREFIX: it is the home of the profile's table")
+        if args.require is None and args.avoid is None and args.max_run is None:
+            raise ValueError("--table global needs --require, --avoid or --max-run: it is the home of the table of a profile under motifs")
+        for flag, value in (("--states", args.states), ("--gc-content", args.gc_content), ("--distinct", args.distinct),
+                            ("--max-mutations", args.max_mutations), ("--pairs", args.pairs), ("--combine", args.combine),
+                            ("--tree", None if args.tree in (None, "lds") else args.tree)):
+            if value is not None:
+                raise ValueError(f"--table global together with {flag} is not built: the automaton conditions the profile on the motifs alone")
+    return dict(table=args.table)
+
+
 def checkpoint_family(path: str) -> str:
     """The ``model`` key of a checkpoint file; a file without one is an ``rdesign`` checkpoint.  ``weights_only=True``."""
     ck = torch.load(path, map_location="cpu", weights_only=True)
@@ -340,6 +369,7 @@ def run(args, log=print):
     distinct = distinct_option(args)
     gc = gc_option(args)                                           # a bad window fails here, before the model is loaded
     tree = tree_option(args)                                       # global / auto with a mode that has no count tree fails here
+    tree.update(table_option(args))                                # --table global without a profile under motifs fails here
     family = checkpoint_family(args.ckpt)
     if family == "rnampnn":
         from rnampnn.utils.predict import predict

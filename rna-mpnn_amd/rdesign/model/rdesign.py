@@ -452,13 +452,16 @@ class RNAModel(nn.Module):
 
     @torch.no_grad()
     def design_profile(self, X, mask, temperature: float = 0.1, constraints=None, lengths=None, gc_content=None, mutations=None, avoid=None,
-                       tree: str = "lds"):
+                       tree: str = "lds", require=None, max_run=None, table: str = "lds"):
         """What ``design`` draws FROM under the same arguments, with one eval-mode forward and one launch on the packed logits: the exact
         per-position marginals, log partition sums and entropy of the constrained, tempered distribution (``design_profile_from_logits``)
         -> a ``DesignProfile``.  ``constraints``, ``lengths``, ``gc_content``, ``mutations`` and ``avoid`` as in ``design``; the pairings
         ``design`` refuses are refused here with the same messages, before the forward pass.  No profile is built for ``states`` or
-        ``distinct``.  ``tree`` as in ``design``, for every profile but ``avoid``'s."""
-        resolve_profile(constraints, gc_content, mutations, avoid, tree)
+        ``distinct``.  ``tree`` as in ``design``, for every profile but ``avoid``'s.  ``table="global"`` (``check_table``; "lds" is everything above,
+        unchanged): the profile of ``require`` and / or ``avoid`` / ``max_run`` on the 256-state automaton
+        (``rnampnn_design_dfa_profile``), ``miss`` = ``dfa_miss``; ``require`` without it and what it is not built with are refused
+        before the forward pass."""
+        resolve_profile(constraints, gc_content, mutations, avoid, tree, require, table, max_run)
         was_training = self.training
         self.eval()
         try:
@@ -466,7 +469,8 @@ class RNAModel(nn.Module):
         finally:
             self.train(was_training)
         return design_profile_from_logits(logits, cu_seqlens=cu, max_len=T, temperature=temperature, constraints=constraints,
-                                          gc_content=gc_content, mutations=mutations, avoid=avoid, tree=tree)
+                                          gc_content=gc_content, mutations=mutations, avoid=avoid, tree=tree, require=require,
+                                          max_run=max_run, table=table)
 
     @torch.no_grad()
     def score_sequences(self, X, mask, seqs, labels=None, lengths=None):

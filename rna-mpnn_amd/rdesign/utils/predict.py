@@ -15,7 +15,8 @@ from .data import load_rna_dir, padded_loader
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
             wobble: bool = True, gc_content=None, distinct=None, mutations=None, avoid=None,
-            profile_prefix: Optional[str] = None, require=None, pairs=None, tree: str = "lds", combine=None) -> List[Tuple[str, str]]:
+            profile_prefix: Optional[str] = None, require=None, pairs=None, tree: str = "lds", combine=None,
+            table: str = "lds") -> List[Tuple[str, str]]:
     """Read ``data_path`` (``coords/<id>.npy`` + ``seqs/<id>.fasta``), design a sequence for every structure in length-bucketed batches
     (``RNAModel.predict_sequences``: the tree read-out when one is attached, else the read-out's argmax) and write ``out_csv`` with one
     ``pdb_id,seq`` row per input in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure at
@@ -42,9 +43,10 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     together with ``distinct``.  ``tree`` ("lds", the default; "global"; "auto"): where the count tree of ``gc_content`` and ``mutations``
     and of their profiles lives (``check_tree``); anything but "lds" with another mode is a ``ValueError`` before the first forward pass.
     ``combine="chain"``: ``avoid`` and / or ``require`` TOGETHER with ``gc_content`` or ``mutations`` (``rnampnn_design_dfa_count``), as in
-    ``rnampnn.utils.predict.predict``: the same columns and the same refusals."""
+    ``rnampnn.utils.predict.predict``: the same columns and the same refusals.  ``table="global"``: the profile of ``require`` and / or
+    ``avoid`` from ``rnampnn_design_dfa_profile``, as there."""
     mode, avoid, require = resolve_run(samples, profile_prefix, constraints, gc_content=gc_content, distinct=distinct, mutations=mutations,
-                                       avoid=avoid, require=require, pairs=pairs, combine=combine, tree=tree)
+                                       avoid=avoid, require=require, pairs=pairs, combine=combine, tree=tree, table=table)
     count = "gc_content" if gc_content is not None else "mutations"     # (what the chain counts: it names its columns)
     model.eval()
     items = load_rna_dir(data_path)
@@ -66,7 +68,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             cons = batch_constraints(constraints, [items[i][0] for i in idx], lens, T, bias=bias, wobble=wobble, omit=omit)
         if profile_prefix:
             profile_batch(profiles, idx, lens, logits, cu, T, temperature, cons.to_device(device), gc_content,
-                          None if mutations is None else (padded_references(refs, idx, T), mutations[0], mutations[1]), avoid, tree)
+                          None if mutations is None else (padded_references(refs, idx, T), mutations[0], mutations[1]), avoid, tree, require, table)
         if samples > 0:
             draws, nll, bad, *extras = design_by_mode(
                 mode, logits, cu_seqlens=cu, max_len=T, n_samples=samples, temperature=temperature, seed=seed + bi,

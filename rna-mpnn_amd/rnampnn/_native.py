@@ -103,6 +103,9 @@ SYMBOLS = {
                                                _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rnampnn_design_avoid_profile": (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I32, _F, _VP, _VP, _I32, _VP, _I32, _VP, _I32, C.c_uint64,
                                                _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "rnampnn_design_dfa_profile_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
+    "rnampnn_design_dfa_profile": (C.c_int, [_VP, _I64, _VP, _VP, _I32, _I32, _F, _VP, _VP, _I32, _VP, _I32, _VP, _VP, _I32, _VP, _SZ,
+                                             _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rnampnn_train_workspace_bytes": (_SZ, [_VP, _I32, _I32]),
     "rnampnn_grad_numel": (_I64, [_VP]),
     "rnampnn_weight_offset": (C.c_int, [_VP, _I32, C.POINTER(_I64)]),

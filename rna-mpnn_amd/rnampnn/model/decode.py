@@ -698,9 +698,46 @@ def resolve_design(constraints=None, states=None, lengths=None, gc_content=None,
     return mode, mutations, avoid, require
 
 
-def resolve_profile(constraints=None, gc_content=None, mutations=None, avoid=None, tree: str = "lds") -> str:
-    """What both models' ``design_profile`` check before their forward pass -> the mode: the pairings ``design`` refuses, the home of the
-    tree (``check_profile_tree``), the form of ``mutations`` and ``avoid`` together with base pairs.  Touches no device."""
+TABLES = ("lds", "global")
+
+
+def check_table(table: str, constraints=None, gc_content=None, mutations=None, avoid=None, require=None, max_run=None, tree: str = "lds"):
+    """``table`` - where the backward table of a profile under motifs lives: "lds" (the default: ``rnampnn_design_avoid_profile``,
+    forbidden motifs alone, at most 64 states, the table in the LDS of the workgroup) or "global" (``rnampnn_design_dfa_profile``:
+    ``require`` and / or ``avoid`` on the automaton of up to 256 states, the table in a workspace in global memory) -> the
+    ``DesignAutomaton`` of "global" (``check_require``, or ``DesignAutomaton.from_avoid`` for ``avoid`` alone), None for "lds".  There is
+    no "auto": the two homes of the forbidden-motif profile add in different orders and agree to rounding, not to the byte, and that byte
+    equality is what made ``tree="auto"`` invisible.  ``ValueError`` for another value, for ``require`` without "global", and for "global"
+    without ``avoid`` / ``require``, with ``gc_content``, ``mutations``, a ``tree`` other than "lds" or base pairs in the constraints;
+    touches no device, so a caller refuses before its forward pass."""
+    if table not in TABLES:
+        raise ValueError(f"table must be one of {list(TABLES)}, got {table!r}")
+    if table == "lds":
+        if require is not None:
+            raise ValueError("a design profile together with require needs table=\"global\": the profile whose table lives in LDS knows "
+                             "forbidden motifs only (rnampnn_design_dfa_profile keeps the table of the 256-state automaton in global memory)")
+        return None
+    if avoid is None and require is None:
+        raise ValueError("table=\"global\" needs avoid and / or require: it is the home of the table of a profile under motifs (the count "
+                         "profiles have tree=)")
+    for name, value in (("gc_content", gc_content), ("mutations", mutations)):
+        if value is not None:
+            raise ValueError(f"table=\"global\" together with {name} is not built: the automaton conditions the profile on the motifs alone")
+    if tree != "lds":
+        raise ValueError(f"table=\"global\" together with tree={tree!r} is not built: a profile under motifs has no count tree")
+    if require is not None:
+        return check_require(require, avoid, constraints, max_run)
+    from ..utils.motifs import DesignAutomaton
+    return DesignAutomaton.from_avoid(check_avoid(avoid, constraints, max_run))
+
+
+def resolve_profile(constraints=None, gc_content=None, mutations=None, avoid=None, tree: str = "lds", require=None, table: str = "lds",
+                    max_run=None) -> str:
+    """What both models' ``design_profile`` check before their forward pass -> the mode: the home of the table of a profile under motifs
+    (``check_table``: "require" or "avoid" with ``table="global"``), the pairings ``design`` refuses, the home of the tree
+    (``check_profile_tree``), the form of ``mutations`` and ``avoid`` together with base pairs.  Touches no device."""
+    if check_table(table, constraints, gc_content, mutations, avoid, require, max_run, tree) is not None:
+        return "require" if require is not None else "avoid"
     mode = design_mode(gc_content=gc_content, mutations=mutations, avoid=avoid)
     check_profile_tree(tree, mode)
     check_mutations(mutations)
@@ -773,7 +810,7 @@ def profile_mode_args(mode: str, B: int, T: int, device, lengths=None, gc_conten
 
 def design_profile_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
                                max_len: Optional[int] = None, temperature: float = 0.1, constraints=None, gc_content=None, mutations=None,
-                               avoid=None, tree: str = "lds") -> DesignProfile:
+                               avoid=None, tree: str = "lds", require=None, max_run=None, table: str = "lds") -> DesignProfile:
     """``rnampnn_design_count_profile`` / ``rnampnn_design_avoid_profile`` (include/rnampnn_hip.h): the exact distribution that the draws
     of ``design_by_mode`` come from under the same arguments - per-position marginals, log partition sums and entropy, fp64, in one launch ->
     ``DesignProfile``.  The mode is ``design_mode(gc_content=, mutations=, avoid=)``, so the pairings that are not built keep their messages:
@@ -783,12 +820,32 @@ def design_profile_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor
     LDS: T <= 535 for a G+C window, 1457 for a budget of 8, 1168 for ``max_run=3``; beyond it the library raises ``NotImplementedError``
     naming the limit.  ``tree`` (``check_tree``), for the three count modes: "global" - ``rnampnn_design_count_profile_long``, the inside
     and the outside tree in a workspace in global memory (``torch.empty`` here), T <= 65536, the same bytes wherever both run; "auto" -
-    "lds" where it fits; anything but "lds" with ``avoid`` is a ``ValueError``.  Layouts and ``constraints`` as in ``design_from_logits``.
-    CUDA logits only (there is no CPU fallback); no host synchronisation."""
+    "lds" where it fits; anything but "lds" with ``avoid`` is a ``ValueError``.  ``table`` (``check_table``): "lds" - everything above,
+    unchanged; "global" - ``rnampnn_design_dfa_profile``: the profile of what ``design_dfa_from_logits`` draws under ``require`` (a
+    ``DesignAutomaton`` or motif strings, with ``avoid`` and ``max_run`` absorbed), or of ``avoid`` / ``max_run`` alone
+    (``DesignAutomaton.from_avoid``), on automata of up to 256 states with the backward table in a workspace in global memory
+    (``torch.empty`` here, 8 B T L bytes at L live states), T <= 4498 at every automaton; ``mode`` is "require" or "avoid" and ``miss``
+    is ``dfa_miss``.  ``require`` without it, and "global" without ``avoid`` / ``require`` or with ``gc_content``, ``mutations``, another
+    ``tree`` or base pairs, are a ``ValueError`` before any device work.  There is no "auto" table: the two homes of the forbidden-motif
+    profile add in different orders and agree to rounding, not to the byte - and that byte equality is what made ``tree="auto"``
+    invisible.  Layouts and ``constraints`` as in ``design_from_logits``.  CUDA logits only (there is no CPU fallback); no host
+    synchronisation."""
+    dfa = check_table(table, constraints, gc_content, mutations, avoid, require, max_run, tree)
+    if dfa is not None:
+        name = "rnampnn_design_dfa_profile"
+        lg, m, cu, B, T, _, al, pa, bi, per_position, wobble = _design_inputs(name, logits, mask, cu_seqlens, max_len, constraints)
+        device, Bn, Tn = lg.device, max(B, 0), max(T, 0)
+        marg = torch.empty(Bn, Tn, 4, dtype=torch.float64, device=device)
+        log_z, free, ent = (torch.empty(Bn, dtype=torch.float64, device=device) for _ in range(3))
+        bad, miss = (torch.empty(Bn, dtype=torch.int32, device=device) for _ in range(2))
+        _entry_call(name, [lg, int(lg.numel()) // 4, m, cu, B, T, float(temperature), al, pa, wobble, bi, per_position,
+                           *_automaton_tail("rnampnn_design_dfa_profile_workspace_bytes", dfa, device, B, T), marg, log_z, free, ent, bad, miss],
+                    device)
+        return DesignProfile(marg, log_z, free, ent, bad, miss, "require" if require is not None else "avoid")
     mode = design_mode(gc_content=gc_content, mutations=mutations, avoid=avoid)
     check_profile_tree(tree, mode)
     mutations = check_mutations(mutations)
-    auto = check_avoid(avoid, constraints)
+    auto = check_avoid(avoid, constraints, max_run)
     name = PROFILE_ENTRIES[mode]
     padded = (("the reference of mutations", mutations[0], torch.int32),) if mode == "mutations" else ()
     lg, m, cu, B, T, own, al, pa, bi, per_position, wobble = _design_inputs(name, logits, mask, cu_seqlens, max_len, constraints, padded)

@@ -573,15 +573,18 @@ class RNAMPNN(NativeModule):
 
     @torch.no_grad()
     def design_profile(self, coords: torch.Tensor, mask: torch.Tensor, temperature: float = 0.1, T_norm: int = 0, constraints=None,
-                       lengths=None, gc_content=None, mutations=None, avoid=None, tree: str = "lds"):
+                       lengths=None, gc_content=None, mutations=None, avoid=None, tree: str = "lds", require=None, max_run=None,
+                       table: str = "lds"):
         """What ``design`` draws FROM under the same arguments, with one eval-mode forward and one launch: the exact per-position
         marginals, log partition sums and entropy of the constrained, tempered distribution (``design_profile_from_logits``) -> a
         ``DesignProfile`` (marginals (B,T,4) f64, log_z, log_z_free, entropy (B,) f64, infeasible, miss (B,) int32, mode; ``log_mass`` =
         the log of the share of the model's mass the constraints keep).  ``constraints``, ``gc_content``, ``mutations`` and ``avoid`` as
         in ``design``; the pairings that ``design`` refuses are refused here with the same messages, before the forward pass.  ``lengths``
         is accepted for symmetry with ``design`` and not read.  No profile is built for ``states`` or ``distinct``.  ``tree`` as in
-        ``design``, for every profile but ``avoid``'s."""
-        resolve_profile(constraints, gc_content, mutations, avoid, tree)
+        ``design``, for every profile but ``avoid``'s.  ``table="global"`` (``check_table``; "lds" is everything above, unchanged): the
+        profile of ``require`` and / or ``avoid`` / ``max_run`` on the 256-state automaton (``rnampnn_design_dfa_profile``), ``miss`` =
+        ``dfa_miss``; ``require`` without it and what it is not built with are refused before the forward pass."""
+        resolve_profile(constraints, gc_content, mutations, avoid, tree, require, table, max_run)
         was_training = self.training
         self.eval()
         try:
@@ -589,7 +592,7 @@ class RNAMPNN(NativeModule):
         finally:
             self.train(was_training)
         return design_profile_from_logits(logits, mask=mask, temperature=temperature, constraints=constraints, gc_content=gc_content,
-                                          mutations=mutations, avoid=avoid, tree=tree)
+                                          mutations=mutations, avoid=avoid, tree=tree, require=require, max_run=max_run, table=table)
 
     @torch.no_grad()
     def test_step(self, batch):

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from ..config.glob import VOCAB
-from ..model.decode import (resolve_design, check_avoid, check_budget, check_chain, check_profile_tree, check_tree, check_nested, check_require, design_by_mode, design_profile_from_logits, letters_packed, letters_padded,
+from ..model.decode import (resolve_design, check_avoid, check_budget, check_chain, check_profile_tree, check_table, check_tree, check_nested, check_require, design_by_mode, design_profile_from_logits, letters_packed, letters_padded,
                             sample_from_logits, score_logits)
 from .constraints import batch_constraints, crossing_pairs, mutation_references, padded_references, parse_dot_bracket
 from .data import PackedLoader, bucket_batches, fill_nan_deterministic, read_fasta
@@ -157,16 +157,16 @@ def refuse_structures(what: str, constraints) -> None:
                          f"state): drop `structure` from the constraints of {paired[:3]}{' ...' if len(paired) > 3 else ''}")
 
 
-def check_require_run(require, avoid, samples: int, profile_prefix, constraints) -> object:
+def check_require_run(require, avoid, samples: int, profile_prefix, constraints, table: str = "lds") -> object:
     """``predict(..., require=...)`` -> the ``DesignAutomaton`` that holds ``require`` and ``avoid``, or None without ``require``.
-    ``ValueError`` without samples, with a profile (none is built for this mode) and with a structure in ``constraints``; touches no
-    device."""
+    ``ValueError`` without samples, with a profile (none is built for this mode in LDS: ``table="global"`` opts in to
+    ``rnampnn_design_dfa_profile``, with or without samples) and with a structure in ``constraints``; touches no device."""
     auto = check_require(require, avoid)
     if auto is None:
         return None
-    if profile_prefix:
+    if profile_prefix and table != "global":
         raise ValueError("a design profile together with require is not built: the profile entries know forbidden motifs only")
-    if samples <= 0:
+    if samples <= 0 and not (profile_prefix and table == "global"):
         raise ValueError("required motifs need samples > 0")
     refuse_structures("require", constraints)
     return auto
@@ -222,11 +222,21 @@ def check_avoid_run(avoid, samples: int, profile_prefix, constraints) -> object:
 def resolve_run(samples: int, profile_prefix, constraints, states=None, **given):
     """``resolve_design`` as both command-line ``predict`` call it, before the first forward pass -> (mode, avoid, require): the checks
     in their ``*_run`` forms, which know ``samples``, the profile and the constraints TABLE; ``given``: gc_content, distinct, mutations
-    (min, max, references), avoid, require, pairs, combine, tree."""
+    (min, max, references), avoid, require, pairs, combine, tree, and ``table`` ("lds", the default: nothing differs; "global": the
+    profile of ``require`` and / or ``avoid`` comes from ``rnampnn_design_dfa_profile`` - ``check_table``, which needs a profile and a
+    mode of motifs alone)."""
+    table = given.pop("table", "lds")
+
     def run(tree, mode):
         check_tree(tree, mode) if samples > 0 or not profile_prefix else check_profile_tree(tree, mode)
         check_profile(profile_prefix, states, given.get("distinct"))
-        return [lambda r, a, f=f: f(r, a, samples, profile_prefix, constraints) for f in (check_chain_run, check_nested_run, check_require_run)] + [
+        if table != "lds":
+            check_table(table, None, given.get("gc_content"), given.get("mutations"), given.get("avoid"), given.get("require"), None, tree)
+            if not profile_prefix or mode not in ("require", "avoid"):
+                raise ValueError(f"table={table!r} is the home of the table of a design profile under avoid and / or require: it needs "
+                                 "profile_prefix and none of states, distinct, pairs and combine")
+        return [lambda r, a, f=f: f(r, a, samples, profile_prefix, constraints) for f in (check_chain_run, check_nested_run)] + [
+            lambda r, a: check_require_run(r, a, samples, profile_prefix, constraints, table),
             lambda a: check_avoid_run(a, samples, profile_prefix, constraints)]
     mode, mutations, avoid, require = resolve_design(states=states, run=run, **given)
     if mutations is not None:
@@ -237,11 +247,11 @@ def resolve_run(samples: int, profile_prefix, constraints, states=None, **given)
 
 
 def profile_batch(store: dict, idx, lens, logits, cu, max_len: int, temperature: float, cons, gc_content, mutations, avoid,
-                  tree: str = "lds") -> None:
-    """The design profile of one packed batch (``design_profile_from_logits``; ``mutations`` as ``design`` takes it, ``tree`` as it does) into ``store``:
+                  tree: str = "lds", require=None, table: str = "lds") -> None:
+    """The design profile of one packed batch (``design_profile_from_logits``; ``mutations`` as ``design`` takes it, ``tree``, ``require`` and ``table`` as it does) into ``store``:
     item index -> (marginals [n][4], log_mass, entropy, infeasible, miss).  One launch, one copy per output."""
     prof = design_profile_from_logits(logits, cu_seqlens=cu, max_len=max_len, temperature=temperature, constraints=cons, gc_content=gc_content,
-                                      mutations=mutations, avoid=avoid, tree=tree)
+                                      mutations=mutations, avoid=avoid, tree=tree, require=require, table=table)
     marg, mass, ent = prof.marginals.cpu().tolist(), prof.log_mass.cpu().tolist(), prof.entropy.cpu().tolist()
     bad, miss = prof.infeasible.cpu().tolist(), prof.miss.cpu().tolist()
     for r, i in enumerate(idx):
@@ -261,7 +271,7 @@ def write_profile(prefix: str, ids, store: dict) -> None:
 def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows: int = 32768, samples: int = 0, temperature: float = 0.1,
             seed: int = 0, designs_csv: Optional[str] = None, constraints: Optional[dict] = None, bias=None, omit: str = "",
             wobble: bool = True, states: Optional[dict] = None, gc_content=None, distinct=None, mutations=None,
-            avoid=None, profile_prefix: Optional[str] = None, require=None, pairs=None, tree: str = "lds", combine=None) -> List[Tuple[str, str]]:
+            avoid=None, profile_prefix: Optional[str] = None, require=None, pairs=None, tree: str = "lds", combine=None, table: str = "lds") -> List[Tuple[str, str]]:
     """Design a sequence for every structure under ``data_path`` in length-bucketed var-len batches (``forward_packed``): the tree
     read-out on the packed embedding when one is attached, else the read-out's argmax (``rnampnn_score``'s ``pred``); write ``out_csv``
     with one ``pdb_id,seq`` row per structure in id order.  -> the rows.  ``samples > 0``: also draw that many sequences per structure
@@ -308,9 +318,14 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     ``combine="chain"`` (``None`` is everything above, unchanged): ``avoid`` and / or ``require`` TOGETHER with ``gc_content`` or
     ``mutations`` - the draws come from ``rnampnn_design_dfa_count`` and hold both conditions exactly; ``designs_csv`` gains the last
     columns ``motif_hits``, ``required_found``, ``require_miss`` and then ``gc_count``, ``gc_miss`` or ``mutations``, ``mut_miss``.  Not
-    built together with ``states``, ``distinct``, ``pairs``, a profile, a ``tree`` other than "lds" or a ``structure`` in ``constraints``."""
+    built together with ``states``, ``distinct``, ``pairs``, a profile, a ``tree`` other than "lds" or a ``structure`` in ``constraints``.
+    ``table`` ("lds", the default: everything above, unchanged; "global"): with ``profile_prefix`` and ``require`` and / or ``avoid``, the
+    profile comes from ``rnampnn_design_dfa_profile`` - the distribution ``rnampnn_design_dfa`` draws from, on automata of up to 256
+    states, with or without ``samples``; the files keep their columns and ``miss`` holds ``dfa_miss``.  The draws stay
+    ``rnampnn_design_dfa``'s for ``require`` and ``rnampnn_design_avoid``'s for ``avoid`` alone.  Without a profile, or with another mode,
+    it is a ``ValueError`` before the first forward pass."""
     mode, avoid, require = resolve_run(samples, profile_prefix, constraints, states, gc_content=gc_content, distinct=distinct, mutations=mutations,
-                                       avoid=avoid, require=require, pairs=pairs, combine=combine, tree=tree)
+                                       avoid=avoid, require=require, pairs=pairs, combine=combine, tree=tree, table=table)
     count = "gc_content" if gc_content is not None else "mutations"     # (what the chain counts: it names its columns)
     model.eval()
     device = model._device()
@@ -350,7 +365,8 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             cons = batch_constraints(constraints, [ids[i] for i in idx], lens, max_len, bias=bias, wobble=wobble, omit=omit).to_device(device)
         if profile_prefix:
             profile_batch(profiles, idx, lens, logits, cu, max_len, temperature, cons, gc_content,
-                          None if mutations is None else (padded_references(refs, idx, max_len), mutations[0], mutations[1]), avoid, tree)
+                          None if mutations is None else (padded_references(refs, idx, max_len), mutations[0], mutations[1]), avoid, tree,
+                          require, table)
         if samples <= 0:
             continue
         draws, dnll, bad, *extras = draw_batch(

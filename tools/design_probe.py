@@ -41,6 +41,13 @@ usage: python tools/design_probe.py sample_score [calls=50]   rnampnn_sample + r
                                                               under 0..8 mutations (cap 8), S = 8 - and rnampnn_design_dfa_count on that
                                                               automaton: nothing counted (the work of rnampnn_design_dfa), under that G+C
                                                               window, and under that budget (profiles/design_dfa_count_kernel_stats.txt)
+       python tools/design_probe.py dfa_profile               rnampnn_design (free, hairpin) and then, in 5 alternating rounds of 10 calls each,
+                                                              the yardsticks of the same run - rnampnn_design_dfa, S = 8, at max_run = 3 with
+                                                              every live state accepting (13 live states), require GGAGG and CUUCG +
+                                                              max_run = 3 (73) and two long required words (256), and
+                                                              rnampnn_design_avoid_profile max_run = 3 - and rnampnn_design_dfa_profile at the
+                                                              three automata; then one RNA of 4,498 nt, the largest it accepts
+                                                              (profiles/design_dfa_profile_kernel_stats.txt)
        python tools/design_probe.py long                      the count tree in global memory (tree="global": rnampnn_design_count_long,
                                                               rnampnn_design_count_profile_long), nothing else: (a) the C2 batch in 5
                                                               alternating rounds of 10 calls - rnampnn_design_gc 40..60 %, rnampnn_design_count
@@ -501,6 +508,64 @@ else:
             print(f"{name.split(',')[0]}: log_mass {float(p.log_mass.min()):.3f} .. {float(p.log_mass.max()):.3f} nats, entropy "
                   f"{float(p.entropy.min()):.3f} .. {float(p.entropy.max()):.3f} nats, miss total {int(p.miss.sum())}, "
                   f"max |row sum - 1| on valid positions {float(((rows - 1).abs() * m).max()):.2e}")
+    if what == "dfa_profile":
+        # Seven variants in alternating rounds of one process: rnampnn_design_dfa (S = 8) at three automata and rnampnn_design_avoid_profile
+        # at the one it knows - the yardsticks of the same run - then rnampnn_design_dfa_profile at the three; then one RNA at the largest T.
+        from rnampnn.model import decode as D
+        from rnampnn.utils.motifs import DesignAutomaton, MotifAutomaton
+        rounds, per_round, warm = 5, 10, 3
+        long_word = "GGAGGCUUCGAAUUCGCAUGCCAUGGUACCUAGCUAGGAUCCGAUAUCAAGCUUGCGGCCGCUCGAGACGUCUGCAGCCCGGGAGAUCUGUCGACACUAGUUCUAGA"
+        run3 = MotifAutomaton.from_motifs([], max_run=3)
+        autos = [("max_run 3", DesignAutomaton.from_avoid(run3)), ("require GGAGG and CUUCG, max_run 3", DesignAutomaton.from_motifs(["GGAGG", "CUUCG"], max_run=3)),
+                 ("require a 26-mer and a 39-mer", DesignAutomaton.from_motifs([long_word[:26], long_word[50:89]]))]
+        kw = dict(temperature=0.1, seed=1, n_samples=8)
+        pk = dict(mask=m, temperature=0.1)
+        variants = [(f"rnampnn_design_dfa {tag} ({a.n_states} states, {a.n_live} live), S 8",
+                     lambda a=a: D.design_dfa_from_logits(logits, mask=m, require=a, **kw)) for tag, a in autos]
+        variants.append((f"rnampnn_design_avoid_profile max_run 3 ({run3.n_live} live states)", lambda: D.design_profile_from_logits(logits, avoid=run3, **pk)))
+        variants += [(f"rnampnn_design_dfa_profile {tag} ({a.n_states} states, {a.n_live} live)",
+                      lambda a=a: D.design_profile_from_logits(logits, require=a, table="global", **pk)) for tag, a in autos]
+        for _, fn in variants:
+            for _ in range(warm):
+                fn()
+        torch.cuda.synchronize()
+        times = [[] for _ in variants]
+        for _ in range(rounds):
+            for v, (_, fn) in enumerate(variants):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(per_round):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                times[v].append(e0.elapsed_time(e1) * 1e3 / per_round)
+        for (name, _), t in zip(variants, times):
+            print(f"B {B} T {T} nt {int(mask.sum())} {name}: {sum(t) / len(t):.2f} us per call, rounds {min(t):.2f} .. {max(t):.2f} "
+                  f"({rounds} alternating rounds of {per_round} back-to-back calls, events, output allocation included)")
+        t_max = 4498                                                # the largest T the entry accepts (include/rnampnn_hip.h)
+        one = (3.0 * torch.randn(1, t_max, 4, generator=torch.Generator().manual_seed(2))).cuda()
+        ones = torch.ones(1, t_max, device="cuda")
+        big = lambda: D.design_profile_from_logits(one, mask=ones, temperature=0.1, require=autos[0][1], table="global")
+        for _ in range(warm):
+            big()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(per_round):
+            big()
+        e1.record()
+        torch.cuda.synchronize()
+        print(f"B 1 T {t_max} rnampnn_design_dfa_profile max_run 3 ({autos[0][1].n_live} live states): {e0.elapsed_time(e1) * 1e3 / per_round:.2f} us per call "
+              f"({per_round} back-to-back calls, events, output allocation included)")
+        for (name, fn) in variants[3:] + [("rnampnn_design_dfa_profile one RNA of 4498 nt", big)]:
+            p = fn()
+            rows, valid = p.marginals.sum(-1), (m if p.marginals.shape[0] == B else ones)
+            print(f"{name.split('(')[0].strip()}: log_mass {float(p.log_mass.min()):.3f} .. {float(p.log_mass.max()):.3f} nats, entropy "
+                  f"{float(p.entropy.min()):.3f} .. {float(p.entropy.max()):.3f} nats, miss total {int(p.miss.sum())}, "
+                  f"max |row sum - 1| on valid positions {float(((rows - 1).abs() * valid).max()):.2e}")
+        a, p = variants[3][1](), variants[4][1]()
+        print(f"max_run 3, the two homes of the table: max |dP| {float((a.marginals - p.marginals).abs().max()):.2e}, max |d log_z| "
+              f"{float((a.log_z - p.log_z).abs().max()):.2e}, max |d entropy| {float((a.entropy - p.entropy).abs().max()):.2e}")
     if what == "distinct":
         for S in (8, 64):                                           # (timed() prints the global S)
             for mode in ("sample", "best"):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/design_probe.py under rocprofv3 --kernel-trace --stats, each leg in a run of its own.  usage: tools/kstats_design.sh <outdir> [leg ...]
-# (outdir: a git-ignored place such as build/design_stats; legs: sample_score design tied gc distinct count avoid profile dfa nested chain long, the first four by default)
+# (outdir: a git-ignored place such as build/design_stats; legs: sample_score design tied gc distinct count avoid profile dfa dfa_profile nested chain long, the first four by default)
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "${1:?usage: tools/kstats_design.sh <outdir> [leg ...]}" && OUT=$(cd "$1" && pwd) || exit 1
 shift
@@ -41,7 +41,10 @@ cp = launches(lambda n: 'k_design_count_profile' in n)
 ap = launches(lambda n: 'k_design_avoid_profile' in n)
 # the "dfa" leg: the same rounds - k_design_avoid max_run 3 (1 variant: the yardstick of the same run) and k_design_dfa on the same automaton
 # with every live state accepting / require GGAGG + max_run 3 / require GGAGG and CUUCG + max_run 3 (3 variants of its launches)
-dfa = launches(lambda n: 'k_design_dfa' in n and 'k_design_dfa_count' not in n)
+dfa = launches(lambda n: 'k_design_dfa' in n and 'k_design_dfa_count' not in n and 'k_design_dfa_profile' not in n)
+# the "dfa_profile" leg: the same rounds - k_design_dfa at three automata (3 variants) and k_design_avoid_profile max_run 3 (1 variant): the
+# yardsticks of the same run; k_design_dfa_profile at the three automata (3 variants), then 3 + 10 launches on one RNA of 4,498 nt
+dp = launches(lambda n: 'k_design_dfa_profile' in n)
 # the "nested" leg: the same rounds - k_design_dfa max_run 3 with every live state accepting (1 variant: the yardstick of the same run) and
 # k_design_nested on the same automaton without pairs / under the hairpin-rich structure / require GNRA + max_run 3 under it (3 variants)
 ns = launches(lambda n: 'k_design_nested' in n)
@@ -101,7 +104,20 @@ def report(table):
         flat = sorted(x for r in rs for x in r)
         print(f"{kernel}, {label}: 5 rounds x 10 launches, mean {sum(flat) / len(flat):.2f} us ({flat[0]:.2f} .. {flat[-1]:.2f}, median {flat[len(flat) // 2]:.2f}); "
               f"round means {' '.join(f'{v:.2f}' for v in means)} (spread {max(means) - min(means):.2f})")
-if ch:
+if dp:
+    autos = ("max_run 3, every live state accepting (13 live states)", "require GGAGG and CUUCG, max_run 3 (89 states, 73 live)",
+             "require a 26-mer and a 39-mer (256 states, all live)")
+    report(tuple(("k_design_dfa", f"{a}, S = 8", by_round(dfa, 3, v)) for v, a in enumerate(autos)) +
+           (("k_design_avoid_profile", "max_run 3 (13 live states)", by_round(ap, 1, 0)),) +
+           tuple(("k_design_dfa_profile", a, by_round(dp, 3, v)) for v, a in enumerate(autos)))
+    m = [sum(x for r in by_round(s, k, v) for x in r) / 50 for s, k, v in ((dfa, 3, 0), (dfa, 3, 1), (dfa, 3, 2), (ap, 1, 0), (dp, 3, 0), (dp, 3, 1), (dp, 3, 2))]
+    print(f"k_design_dfa_profile / k_design_dfa (S = 8) on the same automaton: {m[4] / m[0]:.3f} at 13 live states, {m[5] / m[1]:.3f} at 73, "
+          f"{m[6] / m[2]:.3f} at 256; k_design_dfa_profile / k_design_avoid_profile at 13 live states: {m[4] / m[3]:.3f}; "
+          f"k_design_dfa_profile / (k_design_dfa + k_design_avoid_profile) at 13 live states: {m[4] / (m[0] + m[3]):.3f}")
+    one = sorted(x[1] / 1e3 for x in dp[3 * 3 + 150 + 3:3 * 3 + 150 + 13])
+    print(f"k_design_dfa_profile, one RNA of 4,498 nt, max_run 3 (13 live states): {len(one)} launches, mean {sum(one) / len(one):.2f} us "
+          f"({one[0]:.2f} .. {one[-1]:.2f}, median {one[len(one) // 2]:.2f})")
+elif ch:
     report((("k_design_dfa", "max_run 3, every live state accepting (13 live states), S = 8", by_round(dfa, 1, 0)),
             ("k_design_count", "C|G counted, cap T, window 45..60 %, S = 8", by_round(c, 2, 0)),
             ("k_design_count", "random reference, 0..8 mutations, cap 8, S = 8", by_round(c, 2, 1)),
