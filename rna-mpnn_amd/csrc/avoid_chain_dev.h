@@ -2,9 +2,10 @@
 // (position x automaton state), as count_tree_dev.h serves the entries on the count tree: the automaton's constants and arguments, the
 // entry's checks of them and the refusal of base pairs (av_prepare), and the bytes of the rows, the table and the masks (av_rows_bytes),
 // to which each kernel's byte formula adds its own part.  Each kernel carves its own LDS (the masks sit in different places) and keeps
-// its own statements for the phases A (rows, masks, automaton into LDS) and B (the backward table l_t(a)): folded into two helpers they
+// its own statements for the automaton half of phase A and for phase B (the backward table l_t(a)): folded into two helpers they
 // compiled to the same loop instructions at another code offset, and every avoid variant measured 1.0 .. 1.5 % slower
 // (docs/experiments.md, Round 15) - so the two texts stay, and tests/test_design_profile_gpu.py holds the profile to the draw's flags.
+// The row loop of phase A alone is design_dev.h's ds_rows_to_lds, within the spread on every avoid variant (Round 18).
 #pragma once
 #include "design_dev.h"
 

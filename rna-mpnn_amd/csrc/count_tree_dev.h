@@ -421,6 +421,17 @@ inline size_t ct_tree_doubles(int T, int cap, unsigned* base) {
     }
     return total;
 }
+// The count side of an entry that reads the counted sets from the call, in slot 0 of its checks: the two refusals, then the fields -
+// the sets, the window, cap = min(count_cap, T) (no node counts more than its positions) and base[] of the tree at that cap, or at
+// max(cap, tree_cap_min) where a tree in global memory keeps one entry per node even at cap 0.  An entry without a tree leaves base unread.
+inline int ct_count_side(const char* name, const uint8_t* counted, const int32_t* count_lo, const int32_t* count_hi, int32_t count_cap, int32_t T,
+                         int tree_cap_min, CtArgs& a) {
+    if (!counted || !count_lo || !count_hi) return fail(RNAMPNN_ERR_BAD_ARG, "%s: null counted, count_lo or count_hi", name);
+    if (count_cap < 0) return fail(RNAMPNN_ERR_BAD_ARG, "%s: count_cap = %d is negative", name, (int)count_cap);
+    a.counted = counted; a.lo = count_lo; a.hi = count_hi; a.cap = std::min<int>(count_cap, T);
+    ct_tree_doubles(T, std::min<int>(std::max<int>(count_cap, tree_cap_min), T), a.base);
+    return RNAMPNN_OK;
+}
 inline size_t ct_lds_bytes(int T, int cap, size_t& tree, size_t& sq) {
     tree = ct_tree_doubles(T, cap, nullptr) * sizeof(double);
     sq = ((size_t)T + 15) & ~(size_t)15;

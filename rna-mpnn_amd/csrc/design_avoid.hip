@@ -49,13 +49,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_avoid(AvArgs a) {
     const size_t pad0 = (size_t)b * T;
     // ---- A: rows, masks and the automaton
     int bad = 0;
-    for (int t = tid; t < n; t += SC_THREADS) {
-        bool empty;
-        const DsPos<double> p = ds_load<double>(a, pad0, row0, t, empty);
-        bad += empty ? 1 : 0;
-        zs[4 * t] = p.z[0]; zs[4 * t + 1] = p.z[1]; zs[4 * t + 2] = p.z[2]; zs[4 * t + 3] = p.z[3];
-        ms[t] = (unsigned char)p.m;
-    }
+    ds_rows_to_lds(a, pad0, row0, n, tid, zs, ms, bad);
     if (tid < AV_MAX_STATES) {
         unsigned raw = 0, cl = 0;
         for (int c = 0; c < 4; ++c) {

@@ -32,22 +32,17 @@ extern "C" int rnampnn_design_count(const float* logits, int64_t n_rows, const f
     CtArgs a{};
     const int rc = ds_prepare("rnampnn_design_count", "RNA", logits, n_rows, mask, cu_seqlens, B, T, temperature, S, seed, seed_dev, allowed,
                               partner, wobble, bias, bias_per_position, seqs, seq_nll, infeasible, a, [&](int slot) {
-        if (slot == 0 && (!counted || !count_lo || !count_hi))
-            return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_count: null counted, count_lo or count_hi");
-        if (slot == 0 && count_cap < 0) return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_count: count_cap = %d is negative", (int)count_cap);
-        return RNAMPNN_OK;
+        return slot == 0 ? ct_count_side("rnampnn_design_count", counted, count_lo, count_hi, count_cap, T, 0, a) : RNAMPNN_OK;
     });
     if (rc != RNAMPNN_OK) return rc;
     if (!seqs && !seq_nll && !infeasible && !count && !count_miss) return RNAMPNN_OK;    // nothing asked for
-    const int cap = std::min<int>(count_cap, T);                   // no node counts more than its positions
     size_t lds_tree = 0, lds_sq = 0;
-    const size_t lds = ct_lds_bytes(T, cap, lds_tree, lds_sq);
+    const size_t lds = ct_lds_bytes(T, a.cap, lds_tree, lds_sq);
     if (lds > DS_LDS_MAX)
         return fail(RNAMPNN_ERR_UNSUPPORTED,
                     "rnampnn_design_count: T = %d at count_cap = %d needs %zu bytes of LDS for the count tree, the limit is %zu (T <= %d at that cap)",
                     (int)T, (int)count_cap, lds, DS_LDS_MAX, ct_max_T(count_cap));
-    a.counted = counted; a.lo = count_lo; a.hi = count_hi; a.count = count; a.miss = count_miss; a.cap = cap;
-    ct_tree_doubles(T, cap, a.base);
+    a.count = count; a.miss = count_miss;
     a.lds_tree = (unsigned)lds_tree; a.lds_sq = (unsigned)lds_sq;
     const int passes = (seqs || seq_nll || count) ? S : 1;      // count_miss and the count of infeasible positions are those of sample 0
     return ds_launch<k_design_count>(dim3(B, passes), lds, stream, a);

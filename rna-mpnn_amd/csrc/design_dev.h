@@ -3,7 +3,7 @@
 // (design_dfa.hip: what k_design_avoid uses, with workgroup barriers instead of the fence) and the two profile kernels of
 // design_profile.hip, all fp64 - and the kernels of the count tree in global memory (design_long.hip) - and by their entries.  Everything that is about "a position
 // under the constraints" has its one definition here: the arguments and the entry prologue (ds_prepare), the mask of a position (ds_mask),
-// its row (ds_load<F>), its validated partner (ds_partner), the 16 cells of a pair (ds_pair_mask), the uniform of a position, the DRAW
+// its row (ds_load<F>), the rows and masks of an RNA into LDS (ds_rows_to_lds), its validated partner (ds_partner), the 16 cells of a pair (ds_pair_mask), the uniform of a position, the DRAW
 // RULE as templates over the scalar type - the weights exp(z - max over the admitted), the selection over an admitted set, the joint cell
 // of a base pair - the logsumexp over an admitted set (ds_lse), the LDS ceiling, the largest T under it and the reduction's scratch
 // (DS_LDS_MAX, ds_max_T, ds_scratch), the fence between lanes of one wave (ds_wave_sync), phase "C" of the kernels that draw into LDS first
@@ -210,11 +210,34 @@ __device__ __forceinline__ double ds_lse(const double (&z)[N], int m) {
     return mx + log(sum);
 }
 
+struct DsNoSum {};
+
+// Phase "A" of the kernels that keep the rows of an RNA in LDS (k_design_avoid, k_design_dfa, k_design_dfa_count, k_design_nested and the
+// two automaton profiles): the fp64 row of position t into zs[4 t ..], its mask into ms[t], t = tid, tid + 256, ..; `bad` counts the
+// positions whose mask admits no class.  `each(t, p)`: what a kernel does with the row in the same turn (the avoid profile's free sum,
+// the counted set of k_design_dfa_count); DsNoSum for nothing.  k_design_dfa keeps the loop as its own text: through this function it
+// compiled to the same instructions on other scalar registers (295 of 2,848 lines) and measured 2.7 - 3.1 % slower at 73 live states in
+// two sessions, +7.40 and +6.96 us where 4.14 and 2.66 were allowed, and within them with the loop back (docs/experiments.md, Round 18).
+template <typename Each>
+__device__ __forceinline__ void ds_rows_to_lds(const DesignArgs& a, size_t pad0, long long row0, int n, int tid, double* zs, unsigned char* ms, int& bad,
+                                               Each each) {
+    for (int t = tid; t < n; t += SC_THREADS) {
+        bool empty;
+        const DsPos<double> p = ds_load<double>(a, pad0, row0, t, empty);
+        bad += empty ? 1 : 0;
+        zs[4 * t] = p.z[0]; zs[4 * t + 1] = p.z[1]; zs[4 * t + 2] = p.z[2]; zs[4 * t + 3] = p.z[3];
+        ms[t] = (unsigned char)p.m;
+        if constexpr (!std::is_same<Each, DsNoSum>::value) each(t, p);
+    }
+}
+__device__ __forceinline__ void ds_rows_to_lds(const DesignArgs& a, size_t pad0, long long row0, int n, int tid, double* zs, unsigned char* ms, int& bad) {
+    ds_rows_to_lds(a, pad0, row0, n, tid, zs, ms, bad, DsNoSum{});
+}
+
 // Phase "C" of a kernel that has drawn into LDS: sample s of RNA b, whose position t holds class cls(t).  Writes the row and its -1
 // padding, sums sc_row_nll and `bad` as k_design walks and reduces them (t = tid, tid + 256, ..; sc_block_sums once, one barrier), and
 // thread 0 writes seq_nll[s, b] and, for s == 0, infeasible[b].  `extra(t, q)`: a third per-position float to sum; DsNoSum for none.
 // -> its total, valid in thread 0.  Every thread calls it.
-struct DsNoSum {};
 template <typename Class, typename Extra>
 __device__ __forceinline__ float ds_write_rows(const DesignArgs& a, int s, int b, int n, long long row0, int tid, int bad, const DsScratch& sc,
                                                Class cls, Extra extra) {

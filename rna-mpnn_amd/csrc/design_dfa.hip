@@ -16,7 +16,8 @@
 // No atomics, no fill / copy node, no host synchronisation; every table entry that is read was written by the same launch before.
 // dfa_chain_dev.h holds what this entry shares with rnampnn_design_dfa_count and rnampnn_design_nested: the automaton's constants, helpers
 // and arguments (DfaChainArgs), the host prologue (dfa_prepare), the automaton half of phase A, the candidates and the automaton step of
-// the forward walk (dfa_walk_step<false>, dfa_advance) and the read of a draw (dfa_drawn).  The LDS carve-up, `col` / `cc` and phase B are this file's.
+// the forward walk (dfa_walk_step<false>, dfa_advance) and the read of a draw (dfa_drawn), and phase B, which the profile shares
+// (dfa_rows_init, dfa_backward).  The LDS carve-up, the row loop of phase A and `col` / `cc` are this file's.
 #include "dfa_chain_dev.h"
 
 namespace {
@@ -41,7 +42,8 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa(DfaArgs a) {
     long long row0;
     sc_extent(a, b, tid, sc.s_f[0], n, row0);
     const size_t pad0 = (size_t)b * T;
-    // ---- A: rows, masks and the automaton
+    // ---- A: rows, masks and the automaton (the row loop is ds_rows_to_lds' text: through the function this kernel measured 2.8 % slower
+    // at 73 live states, docs/experiments.md Round 18)
     int bad = 0;
     for (int t = tid; t < n; t += SC_THREADS) {
         bool empty;
@@ -52,8 +54,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa(DfaArgs a) {
     }
     const DfaState me = dfa_load_state(a, A, tid, DFA_DEAD, own, kd);
     const bool live = me.live, accepts = me.accepts;
-    row[(n & 1) * DFA_MAX_STATES + tid] = accepts ? 0.0 : -INFINITY;               // l_n
-    row[((n + 1) & 1) * DFA_MAX_STATES + tid] = -INFINITY;                         // a dead state's entry is never written again
+    dfa_rows_init(row, n, tid, accepts);
     __syncthreads();
     unsigned cl[2] = {0, 0};
     int cc[4], ok = 0;
@@ -65,24 +66,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa(DfaArgs a) {
     col[tid] = make_uint2(cl[0], cl[1]);
     __syncthreads();
     // ---- B: l_t(a), t = n-1 .. 0; thread = state; the row of t + 1 is read, the row of t written, one barrier per step
-    {
-        const int mine = own[tid];
-        for (int t = n - 1; t >= 0; --t) {
-            if (live) {
-                const double* next = row + ((t + 1) & 1) * DFA_MAX_STATES;
-                double l[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) l[c] = next[cc[c]];
-                const double2 z01 = *reinterpret_cast<const double2*>(zs + 4 * t), z23 = *reinterpret_cast<const double2*>(zs + 4 * t + 2);
-                const double v[4] = {z01.x + l[0], z01.y + l[1], z23.x + l[2], z23.y + l[3]};
-                const double lt = ds_lse<4>(v, (int)ms[t] & ok);
-                row[(t & 1) * DFA_MAX_STATES + tid] = lt;
-                tab[(size_t)t * AL + mine] = lt;
-            }
-            __syncthreads();
-        }
-    }
-    const bool miss = !(row[0] > -INFINITY);                        // l_0 of state 0: the loop ends on row 0, and n = 0 starts there
+    const bool miss = dfa_backward(zs, ms, row, tab, own, n, AL, tid, live, cc, ok);
     if (tid == 0 && a.dfa_miss) a.dfa_miss[b] = miss ? 1 : 0;
     // ---- C: the walks of 256 samples, then their rows
     const int S = (a.seqs || a.seq_nll || a.hits || a.accepted) ? a.S : 1;         // `infeasible` is written with sample 0

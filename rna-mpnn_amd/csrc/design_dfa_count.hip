@@ -61,14 +61,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa_count(DfcArgs a) {
     const int K = min(a.cap, n);
     // ---- A: rows, masks, counted sets and the automaton
     int bad = 0;
-    for (int t = tid; t < n; t += SC_THREADS) {
-        bool empty;
-        const DsPos<double> p = ds_load<double>(a, pad0, row0, t, empty);
-        bad += empty ? 1 : 0;
-        zs[4 * t] = p.z[0]; zs[4 * t + 1] = p.z[1]; zs[4 * t + 2] = p.z[2]; zs[4 * t + 3] = p.z[3];
-        ms[t] = (unsigned char)p.m;
-        cn[t] = (unsigned char)ct_counted<true>(a, pad0, t);
-    }
+    ds_rows_to_lds(a, pad0, row0, n, tid, zs, ms, bad, [&](int t, const DsPos<double>&) { cn[t] = (unsigned char)ct_counted<true>(a, pad0, t); });
     {
         const bool live = tid < A && !dfa_bit(a.dead, tid);
         const bool accepts = live && dfa_bit(a.acc, tid);
@@ -219,11 +212,7 @@ extern "C" int rnampnn_design_dfa_count(const float* logits, int64_t n_rows, con
     DfcArgs a{};
     const int rc = dfa_prepare(name, logits, n_rows, mask, cu_seqlens, B, T, temperature, S, seed, seed_dev, allowed, partner, wobble, bias,
                                bias_per_position, seqs, seq_nll, infeasible, delta, kind, n_states, workspace, workspace_bytes, hits, accepted,
-                               dfa_miss, true, a, [&] {
-        if (!counted || !count_lo || !count_hi) return fail(RNAMPNN_ERR_BAD_ARG, "%s: null counted, count_lo or count_hi", name);
-        if (count_cap < 0) return fail(RNAMPNN_ERR_BAD_ARG, "%s: count_cap = %d is negative", name, (int)count_cap);
-        return RNAMPNN_OK;
-    }, [&](int live, char* what, size_t len) {
+                               dfa_miss, true, a, [&] { return ct_count_side(name, counted, count_lo, count_hi, count_cap, T, 0, a); }, [&](int live, char* what, size_t len) {
         const int cap = std::min<int>(count_cap, T);
         std::snprintf(what, len, "the table of partition sums at (B = %d, T = %d, %d live states, counts 0 .. %d) needs", (int)B, (int)T, live, cap);
         return dfc_table_bytes(B, T, live, cap);
@@ -236,7 +225,7 @@ extern "C" int rnampnn_design_dfa_count(const float* logits, int64_t n_rows, con
                     ds_max_T([](long long t) { return dfc_lds_bytes(t); }));
     if (!seqs && !seq_nll && !infeasible && !hits && !accepted && !count && !dfa_miss && !count_miss && !log_z) return RNAMPNN_OK;    // nothing asked for
     a.log_z = log_z;
-    a.counted = counted; a.lo = count_lo; a.hi = count_hi; a.count = count; a.miss = count_miss; a.cap = std::min<int>(count_cap, T);
+    a.count = count; a.miss = count_miss;
     const size_t slabs = dfc_slab_bytes(a.live, a.cap);
     if (lds + slabs <= (size_t)DFC_SLAB_LDS_MAX) return ds_launch<k_design_dfa_count<true>>(dim3(B), lds + slabs, stream, a);
     return ds_launch<k_design_dfa_count<false>>(dim3(B), lds, stream, a);

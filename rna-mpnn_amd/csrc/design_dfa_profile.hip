@@ -4,7 +4,7 @@
 // on automata of up to 256 states and with the backward table l_t(a) in the caller's WORKSPACE in global memory, [b][t][live column], so
 // LDS grows with T alone.  The contract is the one include/rnampnn_hip.h documents and tests/_design_dfa_profile_ref.py restates.
 // One 256-thread workgroup per RNA, thread = state.  (A) the fp64 rows, the masks and the free sum; the automaton (dfa_chain_dev.h).
-// (B) k_design_dfa's backward pass, statement for statement: l_{t+1} and l_t in two LDS rows, every live l_t(a) to the workspace.
+// (B) k_design_dfa's backward pass (dfa_rows_init, dfa_backward): l_{t+1} and l_t in two LDS rows, every live l_t(a) to the workspace.
 // (C) the forward walk in the POSTERIOR domain.  With q_t(a) = exp(alpha_t(a) + l_t(a) - log_z), the probability that the draw is in
 // state a before position t, the cell (a, c) carries w = q_t(a) exp(z_t(c) + l_{t+1}(delta(a,c)) - l_t(a)) - q times the very
 // conditional the draw entry selects with - and P_t(c) = the sum of w over a, q_{t+1}(a') = the sum of w over the cells that lead to a'.
@@ -21,7 +21,7 @@
 //   were found once, the four wave totals cross in LDS, and the thread that owns the last cell of a segment writes q_{t+1}(target).
 //   Three barriers, six double shuffles and at most seven additions per thread and step WHATEVER the in-degree of a state - the root
 //   of an Aho-Corasick automaton collects several hundred of the cells - and one fixed order of addition, so two calls give the same bytes.
-// With dfa_miss = 1 there is no chain: all threads write the per-position softmax over the admitted classes, as the draw falls back to.
+// With dfa_miss = 1 there is no chain: all threads write the per-position softmax over the admitted classes (pf_softmax_rows).
 //   LDS bytes(T) = 32 T + 16 ceil(T / 16) + 15,392: the fp64 rows and the masks; 8,208 for the cells (the two rows of l lie over them
 //   during (B)), 2,048 for q_{t+1}, 3,088 for the sorted cells and their targets, 1,792 for the automaton, 256 for the sums, the scans
 //   and the reduction's scratch.  160 KiB holds T <= 4,498 at every automaton.
@@ -70,19 +70,12 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa_profile(DfaPfArgs a) 
     const bool live = me.live, accepts = me.accepts;
     int bad = 0;
     double free_sum = 0.0;
-    for (int t = tid; t < n; t += SC_THREADS) {
-        bool empty;
-        const DsPos<double> p = ds_load<double>(a, pad0, row0, t, empty);
-        bad += empty ? 1 : 0;
-        zs[4 * t] = p.z[0]; zs[4 * t + 1] = p.z[1]; zs[4 * t + 2] = p.z[2]; zs[4 * t + 3] = p.z[3];
-        ms[t] = (unsigned char)p.m;
-    }
+    ds_rows_to_lds(a, pad0, row0, n, tid, zs, ms, bad);
     for (int t = tid; t < n; t += SC_THREADS) {                                    // (a loop of its own: the scalar registers of the two do not add up)
         const double z[4] = {zs[4 * t], zs[4 * t + 1], zs[4 * t + 2], zs[4 * t + 3]};
         free_sum += ds_lse<4>(z, 15);
     }
-    row[(n & 1) * DFA_MAX_STATES + tid] = accepts ? 0.0 : -INFINITY;               // l_n
-    row[((n + 1) & 1) * DFA_MAX_STATES + tid] = -INFINITY;                         // a dead state's entry is never written again
+    dfa_rows_init(row, n, tid, accepts);
     __syncthreads();
     int cc[4], ck[4], ok = 0;
     dfa_load_delta(a, tid, DFA_DEAD, own, nx, [&](int c, unsigned nxt, unsigned k) {
@@ -94,41 +87,15 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_dfa_profile(DfaPfArgs a) 
     int accm = 0;                                                                  // the classes that lead into a live accepting state
 #pragma unroll
     for (int c = 0; c < 4; ++c) accm |= (((ok >> c) & 1) && (kd[cc[c]] & 2) ? 1 : 0) << c;
-    // ---- B: l_t(a), t = n-1 .. 0, as k_design_dfa forms it
+    // ---- B: l_t(a), t = n-1 .. 0: k_design_dfa's backward pass (dfa_chain_dev.h)
     const int mine = own[tid];
-    for (int t = n - 1; t >= 0; --t) {
-        if (live) {
-            const double* next = row + ((t + 1) & 1) * DFA_MAX_STATES;
-            double l[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) l[c] = next[cc[c]];
-            const double2 z01 = *reinterpret_cast<const double2*>(zs + 4 * t), z23 = *reinterpret_cast<const double2*>(zs + 4 * t + 2);
-            const double v[4] = {z01.x + l[0], z01.y + l[1], z23.x + l[2], z23.y + l[3]};
-            const double lt = ds_lse<4>(v, (int)ms[t] & ok);
-            row[(t & 1) * DFA_MAX_STATES + tid] = lt;
-            tab[(size_t)t * AL + mine] = lt;
-        }
-        __syncthreads();
-    }
-    const bool miss = !(row[0] > -INFINITY);                        // l_0 of state 0: the loop ends on row 0, and n = 0 starts there
+    const bool miss = dfa_backward(zs, ms, row, tab, own, n, AL, tid, live, cc, ok);
     const double log_z = n > 0 && !miss ? row[0] : 0.0;
     __syncthreads();                                                // the rows of l make way for the cells
     double pz_sum = 0.0, lz_sum = 0.0;
     if (miss) {
         // ---- C': no admitted sequence is accepted: the per-position softmax over the admitted classes, as the draw falls back to
-        for (int t = tid; t < n; t += SC_THREADS) {
-            const double z[4] = {zs[4 * t], zs[4 * t + 1], zs[4 * t + 2], zs[4 * t + 3]};
-            const int m = ms[t];
-            const double l = ds_lse<4>(z, m);
-            double p[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                p[c] = ((m >> c) & 1) ? exp(z[c] - l) : 0.0;
-                pz_sum += pf_pz(p[c], z[c]);
-            }
-            lz_sum += l;
-            pf_store4(a.more.marg, pad0 + t, p);
-        }
+        pf_softmax_rows(a.more.marg, zs, ms, pad0, n, tid, pz_sum, lz_sum);
     } else if (n > 0) {
         // ---- C, once: the live cells sorted by (target, source, class).  Thread = target counts its cells, a workgroup scan of the counts
         // gives its first position, a second pass lists them.
@@ -282,23 +249,21 @@ extern "C" int rnampnn_design_dfa_profile(const float* logits, int64_t n_rows, c
                                           void* workspace, size_t workspace_bytes, double* marginals, double* log_z, double* log_z_free,
                                           double* entropy, int32_t* infeasible, int32_t* dfa_miss, void* stream) {
     const char* name = "rnampnn_design_dfa_profile";
+    const PfAsked asked{name, marginals, log_z, log_z_free, entropy, infeasible, dfa_miss};
     DfaPfArgs a{};
     const int rc = dfa_prepare(name, logits, n_rows, mask, cu_seqlens, B, T, temperature, 1, 0, nullptr, allowed, partner, wobble, bias,
                                bias_per_position, nullptr, nullptr, infeasible, delta, kind, n_states, workspace, workspace_bytes, nullptr, nullptr,
-                               dfa_miss, true, a, [&] {
-        if (marginals && ((uintptr_t)marginals & 15) != 0) return fail(RNAMPNN_ERR_BAD_ARG, "%s: marginals must be 16-byte aligned", name);
-        return RNAMPNN_OK;
-    }, [&](int live, char* what, size_t len) {
+                               dfa_miss, true, a, [&] { return asked.aligned(); }, [&](int live, char* what, size_t len) {
         std::snprintf(what, len, "the table of partition sums at (B = %d, T = %d, %d live states) needs", (int)B, (int)T, live);
         return rnampnn_design_dfa_profile_workspace_bytes(B, T, live);
     });
     if (rc != RNAMPNN_OK) return rc;
-    if (!marginals && !log_z && !log_z_free && !entropy && !infeasible && !dfa_miss) return RNAMPNN_OK;    // nothing asked for
+    if (asked.nothing()) return RNAMPNN_OK;
     const size_t lds = dpf_lds_bytes(T);
     if (lds > DS_LDS_MAX)
         return fail(RNAMPNN_ERR_UNSUPPORTED, "%s: T = %d needs %zu bytes of LDS for the rows and the cells of a step, the limit is %zu "
                     "(T <= %lld; the table of partition sums is in the workspace and does not count)", name, (int)T, lds, DS_LDS_MAX,
                     ds_max_T([](long long t) { return dpf_lds_bytes(t); }));
-    a.more = PfOut{marginals, log_z, log_z_free, entropy};
+    a.more = asked.out();
     return ds_launch<k_design_dfa_profile>(dim3(B), lds, stream, a);
 }

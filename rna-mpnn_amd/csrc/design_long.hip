@@ -301,8 +301,7 @@ extern "C" int rnampnn_design_count_long(const float* logits, int64_t n_rows, co
     CtLongArgs a{};
     const int rc = ds_prepare(name, "RNA", logits, n_rows, mask, cu_seqlens, B, T, temperature, S, seed, seed_dev, allowed, partner, wobble, bias,
                               bias_per_position, seqs, seq_nll, infeasible, a, [&](int slot) {
-        if (slot == 0 && (!counted || !count_lo || !count_hi)) return fail(RNAMPNN_ERR_BAD_ARG, "%s: null counted, count_lo or count_hi", name);
-        if (slot == 0 && count_cap < 0) return fail(RNAMPNN_ERR_BAD_ARG, "%s: count_cap = %d is negative", name, (int)count_cap);
+        if (slot == 0) return ct_count_side(name, counted, count_lo, count_hi, count_cap, T, 1, a);
         if (slot == 1)
             return ctl_check_workspace(name, "the count tree", workspace, workspace_bytes,
                                        rnampnn_design_count_long_workspace_bytes(B, T, std::max<int>(count_cap, 1)), B, T, count_cap);
@@ -316,9 +315,8 @@ extern "C" int rnampnn_design_count_long(const float* logits, int64_t n_rows, co
         return fail(RNAMPNN_ERR_UNSUPPORTED, "%s: T = %d needs %zu bytes of LDS for the counts of two levels and the draw, the limit is %zu "
                     "(T <= %lld; the count tree is in the workspace and does not count)", name, (int)T, lds, DS_LDS_MAX,
                     ds_max_T([](long long t) { size_t c, q; return ctl_lds_bytes(t, c, q); }));
-    a.counted = counted; a.lo = count_lo; a.hi = count_hi; a.count = count; a.miss = count_miss; a.cap = std::min<int>(count_cap, T);
+    a.count = count; a.miss = count_miss;
     a.ws = reinterpret_cast<double*>(workspace); a.per_rna = ctl_doubles(T, count_cap);
-    ct_tree_doubles(T, std::min<int>(std::max<int>(count_cap, 1), T), a.base);
     a.lds_tree = 0; a.lds_sq = (unsigned)lds_sq; a.lds_cnt = (unsigned)lds_cnt;
     if (const int rl = ctl_inside(a, stream)) return rl;
     const int passes = (seqs || seq_nll || count) ? S : 1;      // count_miss and the count of infeasible positions are those of sample 0
@@ -336,26 +334,25 @@ extern "C" int rnampnn_design_count_profile_long(const float* logits, int64_t n_
                                                  double* marginals, double* log_z, double* log_z_free, double* entropy, int32_t* infeasible,
                                                  int32_t* count_miss, void* stream) {
     const char* name = "rnampnn_design_count_profile_long";
+    const PfAsked asked{name, marginals, log_z, log_z_free, entropy, infeasible, count_miss};
     PfLongArgs a{};
     const int rc = ds_prepare(name, "RNA", logits, n_rows, mask, cu_seqlens, B, T, temperature, 1, 0, nullptr, allowed, partner, wobble, bias,
                               bias_per_position, nullptr, nullptr, infeasible, a, [&](int slot) {
-        if (slot == 0 && (!counted || !count_lo || !count_hi)) return fail(RNAMPNN_ERR_BAD_ARG, "%s: null counted, count_lo or count_hi", name);
-        if (slot == 0 && count_cap < 0) return fail(RNAMPNN_ERR_BAD_ARG, "%s: count_cap = %d is negative", name, (int)count_cap);
-        if (slot == 1 && marginals && ((uintptr_t)marginals & 15) != 0) return fail(RNAMPNN_ERR_BAD_ARG, "%s: marginals must be 16-byte aligned", name);
+        if (slot == 0) return ct_count_side(name, counted, count_lo, count_hi, count_cap, T, 1, a);
+        if (const int ra = asked.aligned()) return ra;
         if (slot == 1)
             return ctl_check_workspace(name, "the inside and the outside tree", workspace, workspace_bytes,
                                        rnampnn_design_count_profile_long_workspace_bytes(B, T, std::max<int>(count_cap, 1)), B, T, count_cap);
         return RNAMPNN_OK;
     });
     if (rc != RNAMPNN_OK) return rc;
-    if (!marginals && !log_z && !log_z_free && !entropy && !infeasible && !count_miss) return RNAMPNN_OK;    // nothing asked for
+    if (asked.nothing()) return RNAMPNN_OK;
     if (T > CTL_MAX_T)
         return fail(RNAMPNN_ERR_UNSUPPORTED, "%s: T = %d lies above %d, the largest T whose tree the %d levels of the argument block address",
                     name, (int)T, CTL_MAX_T, CT_MAX_LEVELS);
-    a.counted = counted; a.lo = count_lo; a.hi = count_hi; a.count = nullptr; a.miss = count_miss; a.cap = std::min<int>(count_cap, T);
+    a.count = nullptr; a.miss = count_miss;
     a.ws = reinterpret_cast<double*>(workspace); a.per_rna = ctl_doubles(T, count_cap);
-    ct_tree_doubles(T, std::min<int>(std::max<int>(count_cap, 1), T), a.base);
-    a.out = PfOut{marginals, log_z, log_z_free, entropy};
+    a.out = asked.out();
     CtLongArgs in{};
     static_cast<CtArgs&>(in) = a;
     in.ws = a.ws; in.per_rna = a.per_rna;

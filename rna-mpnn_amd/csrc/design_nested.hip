@@ -68,13 +68,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_nested(NestArgs a) {
     const size_t pad0 = (size_t)b * T;
     // ---- A: rows, masks, the automaton and the structure
     int bad = 0;
-    for (int t = tid; t < n; t += SC_THREADS) {
-        bool empty;
-        const DsPos<double> p = ds_load<double>(a, pad0, row0, t, empty);
-        bad += empty ? 1 : 0;
-        zs[4 * t] = p.z[0]; zs[4 * t + 1] = p.z[1]; zs[4 * t + 2] = p.z[2]; zs[4 * t + 3] = p.z[3];
-        ms[t] = (unsigned char)p.m;
-    }
+    ds_rows_to_lds(a, pad0, row0, n, tid, zs, ms, bad);
     const DfaState me = dfa_load_state(a, A, tid, DFA_DEAD8, own, kd);
     const bool live = me.live;
     const unsigned mine_col = me.mine;

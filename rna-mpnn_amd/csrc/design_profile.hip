@@ -24,7 +24,7 @@
 // exp(alpha + z + l_{t+1}(delta) - log_z), a wave butterfly sums them into P_t(c) (lane 0 writes the row and adds P z), and alpha_{t+1}(a') is
 // gathered by lane a' over its predecessor cells - a list per state built once (counting sort over the 4 A cells, cell order, four cells to a word) - from the
 // candidates alpha + z the lanes parked in LDS: the target takes their maximum, the sources exponentiate their own four candidates
-// against it, the target adds - eight exps per lane and step whatever the fan-in of a state.  With avoid_miss = 1 there is no chain: all threads write the per-position softmax.
+// against it, the target adds - eight exps per lane and step whatever the fan-in of a state.  With avoid_miss = 1 there is no chain: all threads write the per-position softmax (pf_softmax_rows).
 //   LDS bytes(T, L) = (32 + 8 L) T + 16 ceil(T / 16) + 3,680: the fp64 rows, the table of L live states, the masks; 2,560 for the
 //   candidates and the maxima, 512 for the automaton, 448 for the predecessor lists, 160 for the sums and the reduction's scratch.
 //   160 KiB holds T <= 1168 at L = 13 (no run longer than 3) and T <= 293 at L = 64 (the draw kernel: 1064 and 290).
@@ -114,14 +114,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_avoid_profile(PfAvArgs a)
     // ---- A: rows, masks, the free sum and the automaton
     int bad = 0;
     double free_sum = 0.0;
-    for (int t = tid; t < n; t += SC_THREADS) {
-        bool empty;
-        const DsPos<double> p = ds_load<double>(a, pad0, row0, t, empty);
-        bad += empty ? 1 : 0;
-        zs[4 * t] = p.z[0]; zs[4 * t + 1] = p.z[1]; zs[4 * t + 2] = p.z[2]; zs[4 * t + 3] = p.z[3];
-        ms[t] = (unsigned char)p.m;
-        free_sum += ds_lse<4>(p.z, 15);
-    }
+    ds_rows_to_lds(a, pad0, row0, n, tid, zs, ms, bad, [&](int, const DsPos<double>& p) { free_sum += ds_lse<4>(p.z, 15); });
     if (tid < AV_MAX_STATES) {
         unsigned raw = 0, cl = 0;
         for (int c = 0; c < 4; ++c) {
@@ -187,19 +180,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_design_avoid_profile(PfAvArgs a)
     double pz_sum = 0.0, lz_sum = 0.0;
     if (miss) {
         // ---- C': no admitted sequence avoids the motifs: the per-position softmax over the admitted classes, as the draw falls back to
-        for (int t = tid; t < n; t += SC_THREADS) {
-            const double z[4] = {zs[4 * t], zs[4 * t + 1], zs[4 * t + 2], zs[4 * t + 3]};
-            const int m = ms[t];
-            const double l = ds_lse<4>(z, m);
-            double p[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                p[c] = ((m >> c) & 1) ? exp(z[c] - l) : 0.0;
-                pz_sum += pf_pz(p[c], z[c]);
-            }
-            lz_sum += l;
-            pf_store4(a.out.marg, pad0 + t, p);
-        }
+        pf_softmax_rows(a.out.marg, zs, ms, pad0, n, tid, pz_sum, lz_sum);
     } else if (tid < AV_MAX_STATES) {
         // ---- C: the forward walk; alpha_t(a) in the register of lane a.  The LSE of a state's incoming cells is split so that no lane
         // runs more than four exps per step whatever the fan-in of its state: the TARGET takes the maximum over its list, the SOURCES
@@ -267,30 +248,24 @@ extern "C" int rnampnn_design_count_profile(const float* logits, int64_t n_rows,
                                             int32_t bias_per_position, const uint8_t* counted, const int32_t* count_lo, const int32_t* count_hi,
                                             int32_t count_cap, double* marginals, double* log_z, double* log_z_free, double* entropy,
                                             int32_t* infeasible, int32_t* count_miss, void* stream) {
+    const char* name = "rnampnn_design_count_profile";
+    const PfAsked asked{name, marginals, log_z, log_z_free, entropy, infeasible, count_miss};
     PfCtArgs a{};
-    const int rc = ds_prepare("rnampnn_design_count_profile", "RNA", logits, n_rows, mask, cu_seqlens, B, T, temperature, 1, 0, nullptr, allowed,
-                              partner, wobble, bias, bias_per_position, nullptr, nullptr, infeasible, a, [&](int slot) {
-        if (slot == 0 && (!counted || !count_lo || !count_hi))
-            return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_count_profile: null counted, count_lo or count_hi");
-        if (slot == 0 && count_cap < 0)
-            return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_count_profile: count_cap = %d is negative", (int)count_cap);
-        if (slot == 1 && marginals && ((uintptr_t)marginals & 15) != 0)
-            return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_count_profile: marginals must be 16-byte aligned");
-        return RNAMPNN_OK;
+    const int rc = ds_prepare(name, "RNA", logits, n_rows, mask, cu_seqlens, B, T, temperature, 1, 0, nullptr, allowed, partner, wobble, bias,
+                              bias_per_position, nullptr, nullptr, infeasible, a, [&](int slot) {
+        return slot == 0 ? ct_count_side(name, counted, count_lo, count_hi, count_cap, T, 0, a) : asked.aligned();
     });
     if (rc != RNAMPNN_OK) return rc;
-    if (!marginals && !log_z && !log_z_free && !entropy && !infeasible && !count_miss) return RNAMPNN_OK;    // nothing asked for
-    const int cap = std::min<int>(count_cap, T);
+    if (asked.nothing()) return RNAMPNN_OK;
     size_t lds_tree = 0;
-    const size_t lds = pf_ct_lds_bytes(T, cap, lds_tree);
+    const size_t lds = pf_ct_lds_bytes(T, a.cap, lds_tree);
     if (lds > DS_LDS_MAX)
         return fail(RNAMPNN_ERR_UNSUPPORTED,
                     "rnampnn_design_count_profile: T = %d at count_cap = %d needs %zu bytes of LDS for the inside and the outside tree, the limit is "
                     "%zu (T <= %d at that cap)", (int)T, (int)count_cap, lds, DS_LDS_MAX, pf_ct_max_T(count_cap));
-    a.counted = counted; a.lo = count_lo; a.hi = count_hi; a.count = nullptr; a.miss = count_miss; a.cap = cap;
-    ct_tree_doubles(T, cap, a.base);
+    a.count = nullptr; a.miss = count_miss;
     a.lds_tree = (unsigned)lds_tree; a.lds_sq = 0;
-    a.out = PfOut{marginals, log_z, log_z_free, entropy};
+    a.out = asked.out();
     return ds_launch<k_design_count_profile>(dim3(B), lds, stream, a);
 }
 
@@ -299,20 +274,17 @@ extern "C" int rnampnn_design_avoid_profile(const float* logits, int64_t n_rows,
                                             int32_t bias_per_position, const uint8_t* delta, int32_t n_states, uint64_t terminal,
                                             double* marginals, double* log_z, double* log_z_free, double* entropy, int32_t* infeasible,
                                             int32_t* avoid_miss, void* stream) {
+    const PfAsked asked{"rnampnn_design_avoid_profile", marginals, log_z, log_z_free, entropy, infeasible, avoid_miss};
     PfAvArgs a{};
-    const int rc = av_prepare("rnampnn_design_avoid_profile", logits, n_rows, mask, cu_seqlens, B, T, temperature, 1, 0, nullptr, allowed, partner,
-                              wobble, bias, bias_per_position, nullptr, nullptr, infeasible, delta, n_states, terminal, a, [&] {
-        if (marginals && ((uintptr_t)marginals & 15) != 0)
-            return fail(RNAMPNN_ERR_BAD_ARG, "rnampnn_design_avoid_profile: marginals must be 16-byte aligned");
-        return RNAMPNN_OK;
-    });
+    const int rc = av_prepare(asked.name, logits, n_rows, mask, cu_seqlens, B, T, temperature, 1, 0, nullptr, allowed, partner, wobble, bias,
+                              bias_per_position, nullptr, nullptr, infeasible, delta, n_states, terminal, a, [&] { return asked.aligned(); });
     if (rc != RNAMPNN_OK) return rc;
-    if (!marginals && !log_z && !log_z_free && !entropy && !infeasible && !avoid_miss) return RNAMPNN_OK;    // nothing asked for
+    if (asked.nothing()) return RNAMPNN_OK;
     const size_t lds = pf_av_lds_bytes(T, a.live);
     if (lds > DS_LDS_MAX)
         return fail(RNAMPNN_ERR_UNSUPPORTED, "rnampnn_design_avoid_profile: T = %d with %d live states needs %zu bytes of LDS for the table of "
                     "partition sums, the limit is %zu (T <= %lld at this automaton)", (int)T, a.live, lds, DS_LDS_MAX,
                     ds_max_T([&](long long t) { return pf_av_lds_bytes(t, a.live); }));
-    a.miss = avoid_miss; a.out = PfOut{marginals, log_z, log_z_free, entropy};
+    a.miss = avoid_miss; a.out = asked.out();
     return ds_launch<k_design_avoid_profile>(dim3(B), lds, stream, a);
 }

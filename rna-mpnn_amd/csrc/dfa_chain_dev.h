@@ -1,15 +1,16 @@
-// What the three entries on the 256-state automaton share - rnampnn_design_dfa (design_dfa.hip), rnampnn_design_dfa_count
-// (design_dfa_count.hip) and rnampnn_design_nested (design_nested.hip) - as avoid_chain_dev.h serves the two entries on the 64-state chain:
-// the automaton's constants, the pure helpers (dfa_words, dfa_bit, dfa_column), the automaton's arguments as a mixin over the entry's base
+// What the entries on the 256-state automaton share - rnampnn_design_dfa (design_dfa.hip), rnampnn_design_dfa_count
+// (design_dfa_count.hip), rnampnn_design_nested (design_nested.hip) and the profile rnampnn_design_dfa_profile (design_dfa_profile.hip) -
+// as avoid_chain_dev.h serves the two entries on the 64-state chain: the automaton's constants, the pure helpers (dfa_words, dfa_bit, dfa_column), the automaton's arguments as a mixin over the entry's base
 // (DfaChainArgs), the host prologue (dfa_prepare) and the device pieces that are the same statements in every kernel: the automaton half
 // of phase A (dfa_load_state, dfa_load_delta: dfa and nested), one step of the automaton (dfa_advance), the read of a 2-bit draw (dfa_drawn) and the
-// candidates of one step of the forward walk of k_design_dfa and k_design_dfa_count (dfa_walk_step<COUNTED>).  All of them are
+// candidates of one step of the forward walk of k_design_dfa and k_design_dfa_count (dfa_walk_step<COUNTED>), and phase B of k_design_dfa
+// and k_design_dfa_profile (dfa_rows_init, dfa_backward; Round 18).  All of them are
 // __forceinline__ and hold the statements in the order the kernels had them; each fold was held against the compiler's resource report
 // and the kernels' times (docs/experiments.md, Round 17): with these the three kernels use the registers of their own texts, and
 // k_design_nested compiles to its own text's instructions.
 // What stays with each kernel: its LDS carve-up, its own arrays of phase A (`col` as 16-bit columns, `dl` by live column, `of` / `ac`),
-// all of phase B - a thread per state with the transitions in registers, flat dealing over (column, k), transfer tables with tiles: three
-// different loops - the LDS byte formula, the LDS-ceiling message and, in design_nested.hip, NS_MAX_LIVE and the walk of the tree.  And
+// phase B of dfa_count and nested - flat dealing over (column, k), transfer tables with tiles: two other loops than dfa's thread per
+// state - the LDS byte formula, the LDS-ceiling message and, in design_nested.hip, NS_MAX_LIVE and the walk of the tree.  And
 // the CHUNK EPILOGUE, the loop of ds_write_rows over a chunk's samples with its barrier: as one function it cost every kernel 2 - 4 VGPRs
 // and measured k_design_dfa 1.6 % slower at 73 live states and k_design_nested 0.5 - 0.7 % slower (the same round), so the seven lines
 // stand in each kernel, as avoid_chain_dev.h keeps the phases of the avoid kernels.  k_design_dfa_count keeps its own phase-A load for
@@ -64,7 +65,7 @@ __device__ __forceinline__ int dfa_column(const unsigned long long (&dead)[4], u
     return k;
 }
 
-// The prologue of the three entries: ds_prepare with the automaton's four checks and then the entry's `own0` in slot 0 and the workspace
+// The prologue of the four entries: ds_prepare with the automaton's four checks and then the entry's `own0` in slot 0 and the workspace
 // check in slot 1, the refusal of base pairs where the entry has one, then the automaton's fields.  `kind` is read once: the same loop
 // counts `live` for the workspace check and fills dead[] / acc[].  `need(live, what, n)` -> the bytes the workspace must hold, and in
 // `what` the entry's words for it up to the number ("the table of partition sums at (...) needs").  NS_MAX_LIVE, the LDS ceiling and
@@ -137,6 +138,35 @@ __device__ __forceinline__ void dfa_load_delta(const Args& a, int tid, unsigned 
         each(c, nxt, k);
     }
     nx[tid] = tid < a.A ? raw : 0u;
+}
+
+// Phase B of k_design_dfa and k_design_dfa_profile, thread = state.  Two pieces, because the kernels load delta between them under the
+// barrier the rows need anyway.  dfa_rows_init: l_n into row n & 1 of the two LDS rows [2][256] indexed by state, -inf into the other
+// (a dead state's entry is never written again); a barrier follows.  dfa_backward: l_t(a) for t = n-1 .. 0 - the row of t + 1 is read
+// through cc[c] = delta(a, c) (0 for a class `ok` does not admit), the row of t written, every live l_t(a) stored to the workspace at
+// the state's column, one workgroup barrier per step.  -> miss: l_0 of state 0 is -inf (the loop ends on row 0, and n = 0 starts there).
+__device__ __forceinline__ void dfa_rows_init(double* row, int n, int tid, bool accepts) {
+    row[(n & 1) * DFA_MAX_STATES + tid] = accepts ? 0.0 : -INFINITY;               // l_n
+    row[((n + 1) & 1) * DFA_MAX_STATES + tid] = -INFINITY;
+}
+__device__ __forceinline__ bool dfa_backward(const double* zs, const unsigned char* ms, double* row, double* tab, const unsigned short* own, int n, int AL,
+                                             int tid, bool live, const int (&cc)[4], int ok) {
+    const int mine = own[tid];
+    for (int t = n - 1; t >= 0; --t) {
+        if (live) {
+            const double* next = row + ((t + 1) & 1) * DFA_MAX_STATES;
+            double l[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) l[c] = next[cc[c]];
+            const double2 z01 = *reinterpret_cast<const double2*>(zs + 4 * t), z23 = *reinterpret_cast<const double2*>(zs + 4 * t + 2);
+            const double v[4] = {z01.x + l[0], z01.y + l[1], z23.x + l[2], z23.y + l[3]};
+            const double lt = ds_lse<4>(v, (int)ms[t] & ok);
+            row[(t & 1) * DFA_MAX_STATES + tid] = lt;
+            tab[(size_t)t * AL + mine] = lt;
+        }
+        __syncthreads();
+    }
+    return !(row[0] > -INFINITY);
 }
 
 // One step of the automaton by state number: `step` = nx[st], q the class drawn.  A transition out of the automaton or into a dead state

@@ -1,5 +1,7 @@
 // Pieces shared by the profile kernels - k_design_count_profile and k_design_avoid_profile (design_profile.hip), which keep their tables in
-// LDS, and the count profile on a tree in global memory (design_long.hip): the outputs and their final writer (PfOut, pf_finish), the
+// LDS, the count profile on a tree in global memory (design_long.hip) and k_design_dfa_profile (design_dfa_profile.hip) - and by their
+// four entries: the outputs as the caller passed them (PfAsked: the alignment check, "nothing asked for", the kernel's PfOut), the miss
+// fallback of the two automaton profiles (pf_softmax_rows), the outputs and their final writer (PfOut, pf_finish), the
 // fixed-order fp64 workgroup sums, and of the count profile phase B (pf_ct_root: the target, K*, log_z and the root's outside), one
 // coefficient of the outside pass (pf_outside) and phase D (pf_ct_leaves: the leaves' outsides and marginals).  One definition of each, so
 // the two homes of the tree return the same bytes.
@@ -12,6 +14,20 @@ struct PfOut {
     double* log_z;               // (B) or null
     double* log_z_free;          // (B) or null
     double* entropy;             // (B) or null
+};
+
+// The outputs of a profile entry as its caller passed them, and what the four entries do with them on the host: the check of slot 1
+// (before the entry's workspace check, where it has one), "nothing asked for", and the kernel's PfOut.
+struct PfAsked {
+    const char* name;
+    double *marginals, *log_z, *log_z_free, *entropy;
+    int32_t *infeasible, *miss;
+    int aligned() const {
+        if (marginals && ((uintptr_t)marginals & 15) != 0) return fail(RNAMPNN_ERR_BAD_ARG, "%s: marginals must be 16-byte aligned", name);
+        return RNAMPNN_OK;
+    }
+    bool nothing() const { return !marginals && !log_z && !log_z_free && !entropy && !infeasible && !miss; }
+    PfOut out() const { return PfOut{marginals, log_z, log_z_free, entropy}; }
 };
 
 // The workgroup's totals of three doubles: wave butterfly, then one LDS hop over the four waves in ascending order - a fixed order, so two
@@ -31,6 +47,25 @@ __device__ __forceinline__ void pf_store4(double* marg, size_t row, const double
     if (!marg) return;
     double2* out = reinterpret_cast<double2*>(marg + 4 * row);
     out[0] = make_double2(p[0], p[1]); out[1] = make_double2(p[2], p[3]);
+}
+// What the two automaton profiles write on a miss (no admitted sequence passes the automaton), every thread: the per-position softmax
+// over the admitted classes from the rows and masks in LDS, as the draw falls back to.  pz_sum, lz_sum: this thread's shares of the sum
+// of P z and of log_z, which is then the sum of the positions' logsumexps.
+__device__ __forceinline__ void pf_softmax_rows(double* marg, const double* zs, const unsigned char* ms, size_t pad0, int n, int tid, double& pz_sum,
+                                                double& lz_sum) {
+    for (int t = tid; t < n; t += SC_THREADS) {
+        const double z[4] = {zs[4 * t], zs[4 * t + 1], zs[4 * t + 2], zs[4 * t + 3]};
+        const int m = ms[t];
+        const double l = ds_lse<4>(z, m);
+        double p[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            p[c] = ((m >> c) & 1) ? exp(z[c] - l) : 0.0;
+            pz_sum += pf_pz(p[c], z[c]);
+        }
+        lz_sum += l;
+        pf_store4(marg, pad0 + t, p);
+    }
 }
 // what every thread and the final writer share
 __device__ __forceinline__ void pf_finish(const PfOut& o, const DesignArgs& a, int32_t* miss_out, int miss, int b, int n, int tid, int bad, double free_sum,

@@ -461,7 +461,7 @@ class RNAModel(nn.Module):
         unchanged): the profile of ``require`` and / or ``avoid`` / ``max_run`` on the 256-state automaton
         (``rnampnn_design_dfa_profile``), ``miss`` = ``dfa_miss``; ``require`` without it and what it is not built with are refused
         before the forward pass."""
-        resolve_profile(constraints, gc_content, mutations, avoid, tree, require, table, max_run)
+        resolved = resolve_profile(constraints, gc_content, mutations, avoid, tree, require, table, max_run)
         was_training = self.training
         self.eval()
         try:
@@ -469,8 +469,7 @@ class RNAModel(nn.Module):
         finally:
             self.train(was_training)
         return design_profile_from_logits(logits, cu_seqlens=cu, max_len=T, temperature=temperature, constraints=constraints,
-                                          gc_content=gc_content, mutations=mutations, avoid=avoid, tree=tree, require=require,
-                                          max_run=max_run, table=table)
+                                          gc_content=gc_content, tree=tree, resolved=resolved)
 
     @torch.no_grad()
     def score_sequences(self, X, mask, seqs, labels=None, lengths=None):

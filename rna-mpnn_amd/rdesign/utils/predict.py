@@ -7,7 +7,7 @@ from typing import List, Optional, Tuple
 from rnampnn.model.decode import design_by_mode, letters_padded, score_logits
 from rnampnn.utils.constraints import batch_constraints, mutation_references, padded_references
 from rnampnn.utils.data import bucket_batches
-from rnampnn.utils.predict import design_columns, profile_batch, resolve_run, write_csv, write_profile
+from rnampnn.utils.predict import design_columns, profile_automaton, profile_batch, resolve_run, write_csv, write_profile
 
 from .data import load_rna_dir, padded_loader
 
@@ -58,6 +58,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
                                                               [it[2] for it in items])
     batches = bucket_batches([c.shape[0] for _, c, _ in items], batch_size, max_rows, seed=0)
     device = model._device()
+    profiled = profile_automaton(avoid, require, table)
     seqs, designs, profiles = {}, {}, {}
     for bi, (S, X, mask, lengths, idx) in enumerate(padded_loader(items, batches, device=device)):
         for i, s in zip(idx, model.predict_sequences(X, mask, lengths)):
@@ -68,7 +69,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             cons = batch_constraints(constraints, [items[i][0] for i in idx], lens, T, bias=bias, wobble=wobble, omit=omit)
         if profile_prefix:
             profile_batch(profiles, idx, lens, logits, cu, T, temperature, cons.to_device(device), gc_content,
-                          None if mutations is None else (padded_references(refs, idx, T), mutations[0], mutations[1]), avoid, tree, require, table)
+                          None if mutations is None else (padded_references(refs, idx, T), mutations[0], mutations[1]), tree, mode, profiled)
         if samples > 0:
             draws, nll, bad, *extras = design_by_mode(
                 mode, logits, cu_seqlens=cu, max_len=T, n_samples=samples, temperature=temperature, seed=seed + bi,

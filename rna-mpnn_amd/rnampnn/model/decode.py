@@ -732,17 +732,18 @@ def check_table(table: str, constraints=None, gc_content=None, mutations=None, a
 
 
 def resolve_profile(constraints=None, gc_content=None, mutations=None, avoid=None, tree: str = "lds", require=None, table: str = "lds",
-                    max_run=None) -> str:
-    """What both models' ``design_profile`` check before their forward pass -> the mode: the home of the table of a profile under motifs
-    (``check_table``: "require" or "avoid" with ``table="global"``), the pairings ``design`` refuses, the home of the tree
-    (``check_profile_tree``), the form of ``mutations`` and ``avoid`` together with base pairs.  Touches no device."""
-    if check_table(table, constraints, gc_content, mutations, avoid, require, max_run, tree) is not None:
-        return "require" if require is not None else "avoid"
+                    max_run=None) -> tuple:
+    """What both models' ``design_profile`` check before their forward pass, and ``design_profile_from_logits`` when it is called without
+    the result -> (mode, mutations as ``check_mutations`` returns it, the ``MotifAutomaton`` of "avoid" or the ``DesignAutomaton`` of
+    ``table="global"``, or None), as ``design_profile_from_logits`` takes it; the automaton is built once: the home of the table of a profile under motifs (``check_table``), the
+    pairings ``design`` refuses, the home of the tree (``check_profile_tree``), the form of ``mutations`` and ``avoid`` together with
+    base pairs.  Touches no device."""
+    dfa = check_table(table, constraints, gc_content, mutations, avoid, require, max_run, tree)
+    if dfa is not None:
+        return "require" if require is not None else "avoid", None, dfa
     mode = design_mode(gc_content=gc_content, mutations=mutations, avoid=avoid)
     check_profile_tree(tree, mode)
-    check_mutations(mutations)
-    check_avoid(avoid, constraints)
-    return mode
+    return mode, check_mutations(mutations), check_avoid(avoid, constraints, max_run)
 
 
 def design_by_mode(mode: str, logits: torch.Tensor, states=None, state_weights=None, gc_content=None, distinct=None, mutations=None,
@@ -790,14 +791,24 @@ class DesignProfile(NamedTuple):
 
 
 PROFILE_ENTRIES = {"plain": "rnampnn_design_count_profile", "gc_content": "rnampnn_design_count_profile",
-                   "mutations": "rnampnn_design_count_profile", "avoid": "rnampnn_design_avoid_profile"}
+                   "mutations": "rnampnn_design_count_profile", "avoid": "rnampnn_design_avoid_profile",
+                   "require": "rnampnn_design_dfa_profile"}
+
+
+def profile_entry(mode: str, auto=None) -> str:
+    """The profile entry of ``mode`` (None for a mode without one): ``PROFILE_ENTRIES``; "avoid" on a ``DesignAutomaton`` is "require"'s."""
+    from ..utils.motifs import DesignAutomaton
+    return PROFILE_ENTRIES.get("require" if isinstance(auto, DesignAutomaton) else mode)
 
 
 def profile_mode_args(mode: str, B: int, T: int, device, lengths=None, gc_content=None, reference=None, budget=None, auto=None) -> tuple:
-    """The own arguments of the profile entry of ``mode`` (``PROFILE_ENTRIES``), between the bias and the outputs, on ``device``
+    """The own arguments of the profile entry of ``mode`` (``profile_entry``), between the bias and the outputs, on ``device``
     (``lengths`` (B,), read by "gc_content" alone, lives there): "plain" - nothing counts, window (0, 0), cap 0: the tree degenerates and the distribution is ``rnampnn_design``'s;
     "gc_content" - C|G count everywhere, the window of ``gc_counts``, cap T; "mutations" - ``mutation_sets(reference)``, the budget
-    (lo, hi) as window and hi as cap; "avoid" - the automaton's tables.  No host synchronisation."""
+    (lo, hi) as window and hi as cap; "avoid" - the automaton's tables; "require", and "avoid" on a ``DesignAutomaton`` - the automaton and
+    the workspace of its backward table (``_automaton_tail``).  No host synchronisation."""
+    if profile_entry(mode, auto) == PROFILE_ENTRIES["require"]:
+        return _automaton_tail("rnampnn_design_dfa_profile_workspace_bytes", auto, device, B, T)
     if mode == "avoid":
         return auto.delta_on(device), auto.n_states, C.c_uint64(auto.terminal)
     if mode in ("gc_content", "mutations"):
@@ -810,7 +821,8 @@ def profile_mode_args(mode: str, B: int, T: int, device, lengths=None, gc_conten
 
 def design_profile_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, cu_seqlens: Optional[torch.Tensor] = None,
                                max_len: Optional[int] = None, temperature: float = 0.1, constraints=None, gc_content=None, mutations=None,
-                               avoid=None, tree: str = "lds", require=None, max_run=None, table: str = "lds") -> DesignProfile:
+                               avoid=None, tree: str = "lds", require=None, max_run=None, table: str = "lds",
+                               resolved: Optional[tuple] = None) -> DesignProfile:
     """``rnampnn_design_count_profile`` / ``rnampnn_design_avoid_profile`` (include/rnampnn_hip.h): the exact distribution that the draws
     of ``design_by_mode`` come from under the same arguments - per-position marginals, log partition sums and entropy, fp64, in one launch ->
     ``DesignProfile``.  The mode is ``design_mode(gc_content=, mutations=, avoid=)``, so the pairings that are not built keep their messages:
@@ -828,25 +840,12 @@ def design_profile_from_logits(logits: torch.Tensor, mask: Optional[torch.Tensor
     is ``dfa_miss``.  ``require`` without it, and "global" without ``avoid`` / ``require`` or with ``gc_content``, ``mutations``, another
     ``tree`` or base pairs, are a ``ValueError`` before any device work.  There is no "auto" table: the two homes of the forbidden-motif
     profile add in different orders and agree to rounding, not to the byte - and that byte equality is what made ``tree="auto"``
-    invisible.  Layouts and ``constraints`` as in ``design_from_logits``.  CUDA logits only (there is no CPU fallback); no host
-    synchronisation."""
-    dfa = check_table(table, constraints, gc_content, mutations, avoid, require, max_run, tree)
-    if dfa is not None:
-        name = "rnampnn_design_dfa_profile"
-        lg, m, cu, B, T, _, al, pa, bi, per_position, wobble = _design_inputs(name, logits, mask, cu_seqlens, max_len, constraints)
-        device, Bn, Tn = lg.device, max(B, 0), max(T, 0)
-        marg = torch.empty(Bn, Tn, 4, dtype=torch.float64, device=device)
-        log_z, free, ent = (torch.empty(Bn, dtype=torch.float64, device=device) for _ in range(3))
-        bad, miss = (torch.empty(Bn, dtype=torch.int32, device=device) for _ in range(2))
-        _entry_call(name, [lg, int(lg.numel()) // 4, m, cu, B, T, float(temperature), al, pa, wobble, bi, per_position,
-                           *_automaton_tail("rnampnn_design_dfa_profile_workspace_bytes", dfa, device, B, T), marg, log_z, free, ent, bad, miss],
-                    device)
-        return DesignProfile(marg, log_z, free, ent, bad, miss, "require" if require is not None else "avoid")
-    mode = design_mode(gc_content=gc_content, mutations=mutations, avoid=avoid)
-    check_profile_tree(tree, mode)
-    mutations = check_mutations(mutations)
-    auto = check_avoid(avoid, constraints, max_run)
-    name = PROFILE_ENTRIES[mode]
+    invisible.  ``resolved``: ``resolve_profile``'s result from a caller that has run it already; ``mutations``, ``avoid``, ``require``,
+    ``max_run`` and ``table`` are then not read.  Layouts and ``constraints`` as in ``design_from_logits``.  CUDA logits only (there is no CPU fallback); no host synchronisation."""
+    if resolved is None:
+        resolved = resolve_profile(constraints, gc_content, mutations, avoid, tree, require, table, max_run)
+    mode, mutations, auto = resolved
+    name = profile_entry(mode, auto)
     padded = (("the reference of mutations", mutations[0], torch.int32),) if mode == "mutations" else ()
     lg, m, cu, B, T, own, al, pa, bi, per_position, wobble = _design_inputs(name, logits, mask, cu_seqlens, max_len, constraints, padded)
     device, Bn, Tn = lg.device, max(B, 0), max(T, 0)

@@ -584,7 +584,7 @@ class RNAMPNN(NativeModule):
         ``design``, for every profile but ``avoid``'s.  ``table="global"`` (``check_table``; "lds" is everything above, unchanged): the
         profile of ``require`` and / or ``avoid`` / ``max_run`` on the 256-state automaton (``rnampnn_design_dfa_profile``), ``miss`` =
         ``dfa_miss``; ``require`` without it and what it is not built with are refused before the forward pass."""
-        resolve_profile(constraints, gc_content, mutations, avoid, tree, require, table, max_run)
+        resolved = resolve_profile(constraints, gc_content, mutations, avoid, tree, require, table, max_run)
         was_training = self.training
         self.eval()
         try:
@@ -592,7 +592,7 @@ class RNAMPNN(NativeModule):
         finally:
             self.train(was_training)
         return design_profile_from_logits(logits, mask=mask, temperature=temperature, constraints=constraints, gc_content=gc_content,
-                                          mutations=mutations, avoid=avoid, tree=tree, require=require, max_run=max_run, table=table)
+                                          tree=tree, resolved=resolved)
 
     @torch.no_grad()
     def test_step(self, batch):

@@ -11,9 +11,10 @@ import numpy as np
 import torch
 
 from ..config.glob import VOCAB
-from ..model.decode import (resolve_design, check_avoid, check_budget, check_chain, check_profile_tree, check_table, check_tree, check_nested, check_require, design_by_mode, design_profile_from_logits, letters_packed, letters_padded,
+from ..model.decode import (resolve_design, check_avoid, check_budget, check_chain, check_mutations, check_profile_tree, check_table, check_tree, check_nested, check_require, design_by_mode, design_profile_from_logits, letters_packed, letters_padded,
                             sample_from_logits, score_logits)
 from .constraints import batch_constraints, crossing_pairs, mutation_references, padded_references, parse_dot_bracket
+from .motifs import DesignAutomaton
 from .data import PackedLoader, bucket_batches, fill_nan_deterministic, read_fasta
 
 
@@ -246,12 +247,17 @@ def resolve_run(samples: int, profile_prefix, constraints, states=None, **given)
     return mode, avoid, require
 
 
-def profile_batch(store: dict, idx, lens, logits, cu, max_len: int, temperature: float, cons, gc_content, mutations, avoid,
-                  tree: str = "lds", require=None, table: str = "lds") -> None:
-    """The design profile of one packed batch (``design_profile_from_logits``; ``mutations`` as ``design`` takes it, ``tree``, ``require`` and ``table`` as it does) into ``store``:
+def profile_automaton(avoid, require, table: str = "lds"):
+    """The automaton of a run's profiles, once per run, from ``resolve_run``'s result: ``require``, else ``avoid`` (a ``DesignAutomaton`` with ``table="global"``)."""
+    return require if require is not None else DesignAutomaton.from_avoid(avoid) if avoid is not None and table == "global" else avoid
+
+
+def profile_batch(store: dict, idx, lens, logits, cu, max_len: int, temperature: float, cons, gc_content, mutations, tree: str, mode: str,
+                  auto) -> None:
+    """The design profile of one packed batch (``design_profile_from_logits`` on ``resolve_run``'s ``mode`` and ``profile_automaton``'s ``auto``; ``mutations`` as ``design`` takes it) into ``store``:
     item index -> (marginals [n][4], log_mass, entropy, infeasible, miss).  One launch, one copy per output."""
     prof = design_profile_from_logits(logits, cu_seqlens=cu, max_len=max_len, temperature=temperature, constraints=cons, gc_content=gc_content,
-                                      mutations=mutations, avoid=avoid, tree=tree, require=require, table=table)
+                                      tree=tree, resolved=(mode, check_mutations(mutations), auto))
     marg, mass, ent = prof.marginals.cpu().tolist(), prof.log_mass.cpu().tolist(), prof.entropy.cpu().tolist()
     bad, miss = prof.infeasible.cpu().tolist(), prof.miss.cpu().tolist()
     for r, i in enumerate(idx):
@@ -327,6 +333,7 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
     mode, avoid, require = resolve_run(samples, profile_prefix, constraints, states, gc_content=gc_content, distinct=distinct, mutations=mutations,
                                        avoid=avoid, require=require, pairs=pairs, combine=combine, tree=tree, table=table)
     count = "gc_content" if gc_content is not None else "mutations"     # (what the chain counts: it names its columns)
+    profiled = profile_automaton(avoid, require, table)
     model.eval()
     device = model._device()
     items = load_structures(data_path, max_len=int(model.hparams["padding_len"]))
@@ -365,8 +372,8 @@ def predict(model, data_path: str, out_csv: str, batch_size: int = 32, max_rows:
             cons = batch_constraints(constraints, [ids[i] for i in idx], lens, max_len, bias=bias, wobble=wobble, omit=omit).to_device(device)
         if profile_prefix:
             profile_batch(profiles, idx, lens, logits, cu, max_len, temperature, cons, gc_content,
-                          None if mutations is None else (padded_references(refs, idx, max_len), mutations[0], mutations[1]), avoid, tree,
-                          require, table)
+                          None if mutations is None else (padded_references(refs, idx, max_len), mutations[0], mutations[1]), tree, mode,
+                          profiled)
         if samples <= 0:
             continue
         draws, dnll, bad, *extras = draw_batch(

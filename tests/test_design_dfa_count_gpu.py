@@ -9,6 +9,7 @@ left out is printed and capped at 5 %, the cap tests/test_design_dfa_count_cpu.p
 1e-8 max(1, |value|), the profile tests' tolerance for fp64 sums formed in another order."""
 import csv
 import ctypes as C
+import functools
 import itertools
 import os
 import sys
@@ -27,7 +28,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _design_avoid_ref as AV  # noqa: E402
 import _design_dfa_ref as DR  # noqa: E402
 import _design_dfa_count_ref as R  # noqa: E402
-from _design_case import SMALL, design_outputs, raw_design, _bytes, _dev, _write_data, _checkpoint  # noqa: E402
+from _design_case import SMALL, design_outputs, dfa_workspace, raw_design, _bytes, _dev, _write_data, _checkpoint  # noqa: E402
+from _design_case import design_dfa as _case_design_dfa  # noqa: E402
 
 LENGTHS, T, S, SEED = R.CASE_LENGTHS, R.CASE_T, R.CASE_S, R.CASE_SEED
 B = len(LENGTHS)
@@ -36,7 +38,6 @@ DFA_OUTPUTS = ("seqs", "seq_nll", "infeasible", "hits", "accepted", "dfa_miss")
 OUTPUTS = ("seqs", "seq_nll", "infeasible", "hits", "accepted", "count", "dfa_miss", "count_miss", "log_z")
 FURTHER = (("hits", torch.int32, True), ("accepted", torch.int32, True), ("count", torch.int32, True), ("dfa_miss", torch.int32, False),
            ("count_miss", torch.int32, False), ("log_z", torch.float64, False))
-DFA_FURTHER = (("hits", torch.int32, True), ("accepted", torch.int32, True), ("dfa_miss", torch.int32, False))
 
 
 def _automaton(name):
@@ -49,13 +50,8 @@ def _lds_bytes(t):
 
 
 def workspace(Bn, Tn, live, cap, fill=None):
-    from rnampnn import _native
-    need = int(_native.lib().rnampnn_design_dfa_count_workspace_bytes(Bn, Tn, live, max(cap, 1)))
-    assert need == 8 * Bn * Tn * live * (min(max(cap, 1), Tn) + 1)
-    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
-    if fill is not None:
-        ws.fill_(fill)
-    return ws
+    return dfa_workspace("rnampnn_design_dfa_count_workspace_bytes", Bn, Tn, live, max(cap, 1), fill=fill,
+                         need=8 * Bn * Tn * live * (min(max(cap, 1), Tn) + 1))
 
 
 def design_chain(logits, delta, kind, counted, lo, hi, cap, seed=SEED, S=S, ws=None, **kw):
@@ -71,16 +67,7 @@ def design_chain(logits, delta, kind, counted, lo, hi, cap, seed=SEED, S=S, ws=N
     return raw_design("rnampnn_design_dfa_count", own, FURTHER, logits, seed=seed, S=S, **kw)
 
 
-def design_dfa(logits, delta, kind, seed=SEED, S=S, **kw):
-    from rnampnn import _native
-    kind = torch.as_tensor(np.ascontiguousarray(kind), dtype=torch.uint8).contiguous()
-    live = int(((kind & 1) == 0).sum())
-    m, cu = kw.get("mask"), kw.get("cu")
-    Bn = int(m.shape[0]) if m is not None else int(cu.shape[0]) - 1
-    Tp = int(m.shape[1]) if m is not None else int(kw["T"])
-    ws = torch.empty(int(_native.lib().rnampnn_design_dfa_workspace_bytes(Bn, Tp, live)), dtype=torch.uint8, device="cuda")
-    return raw_design("rnampnn_design_dfa", (_dev(delta, torch.uint8), kind, int(kind.numel()), ws, C.c_size_t(ws.numel())), DFA_FURTHER, logits,
-                      seed=seed, S=S, **kw)
+design_dfa = functools.partial(_case_design_dfa, seed=SEED, S=S)
 
 
 @pytest.fixture(scope="module")

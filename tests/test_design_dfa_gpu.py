@@ -7,6 +7,7 @@ draw whose path has a selection within 1e-8 of a cumulative boundary is left out
 capped at 5 %, the cap tests/test_design_dfa_cpu.py holds the restatement alone to."""
 import csv
 import ctypes as C
+import functools
 import itertools
 import os
 import sys
@@ -24,7 +25,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import _design_avoid_ref as AV  # noqa: E402
 import _design_dfa_ref as R  # noqa: E402
-from _design_case import SMALL, design_outputs, raw_design, _bytes, _dev, _write_data, _checkpoint  # noqa: E402
+from _design_case import SMALL, design_outputs, dfa_workspace, raw_design, _bytes, _dev, _write_data, _checkpoint  # noqa: E402
+from _design_case import design_dfa as _case_design_dfa  # noqa: E402
 
 LENGTHS, T, S, SEED = R.CASE_LENGTHS, R.CASE_T, R.CASE_S, R.CASE_SEED
 NEAR = 1e-8
@@ -46,25 +48,10 @@ def _lds_bytes(t):
 
 
 def workspace(B, T, live, fill=None):
-    from rnampnn import _native
-    need = int(_native.lib().rnampnn_design_dfa_workspace_bytes(B, T, live))
-    assert need == 8 * B * T * live
-    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
-    if fill is not None:
-        ws.fill_(fill)
-    return ws
+    return dfa_workspace("rnampnn_design_dfa_workspace_bytes", B, T, live, fill=fill)
 
 
-def design_dfa(logits, delta, kind, seed=SEED, S=S, ws=None, **kw):
-    """The C entry on device tensors (numpy arrays are uploaded; ``kind`` stays on the host) -> dict of its six outputs."""
-    kind = torch.as_tensor(np.ascontiguousarray(kind), dtype=torch.uint8).contiguous()
-    live = int(((kind & 1) == 0).sum())
-    m, cu = kw.get("mask"), kw.get("cu")
-    B = int(m.shape[0]) if m is not None else int(cu.shape[0]) - 1
-    Tp = int(m.shape[1]) if m is not None else int(kw["T"])
-    ws = workspace(B, Tp, live) if ws is None else ws
-    return raw_design("rnampnn_design_dfa", (_dev(delta, torch.uint8), kind, int(kind.numel()), ws, C.c_size_t(ws.numel())), FURTHER, logits,
-                      seed=seed, S=S, **kw)
+design_dfa = functools.partial(_case_design_dfa, seed=SEED, S=S)
 
 
 @pytest.fixture(scope="module")

@@ -153,9 +153,28 @@ def test_table_global_reaches_the_device_check_with_the_automaton_it_documents(m
     auto = D.check_table("global", None, None, None, ["GGGG"], ["GGAGG"], 3)
     assert len(auto.required) == 1 and auto.letters() == ["AAAA", "UUUU", "CCCC", "GGGG"]
     assert D.check_table("lds", None, (0.4, 0.6), None, ["GGGG"]) is None
-    assert D.resolve_profile(None, None, None, ["GGGG"], "lds", ["GGAGG"], "global") == "require"
-    assert D.resolve_profile(None, None, None, ["GGGG"], "lds", None, "global") == "avoid"
+    assert D.resolve_profile(None, None, None, ["GGGG"], "lds", ["GGAGG"], "global")[0] == "require"
+    assert D.resolve_profile(None, None, None, ["GGGG"], "lds", None, "global")[0] == "avoid"
     assert D.TABLES == ("lds", "global")
+
+
+def test_the_resolved_call_path_builds_the_automaton_once(monkeypatch):
+    """``resolve_profile`` returns what ``design_profile_from_logits`` consumes: with its result passed on as ``resolved`` the subset
+    construction runs once per call (twice before the resolver returned it), and the call gets as far as the device check."""
+    built = []
+    for name in ("from_motifs", "from_avoid"):
+        real = getattr(M.DesignAutomaton, name).__func__
+        monkeypatch.setattr(M.DesignAutomaton, name, classmethod(lambda cls, *a, _real=real, _name=name, **k: built.append(_name) or _real(cls, *a, **k)))
+    resolved = D.resolve_profile(require=["GA"], max_run=2, table="global")
+    assert resolved[0] == "require" and isinstance(resolved[2], M.DesignAutomaton) and resolved[1] is None
+    with pytest.raises(RuntimeError, match="rnampnn_design_dfa_profile runs on an MI355X"):
+        D.design_profile_from_logits(torch.zeros(1, 8, 4), mask=torch.ones(1, 8), resolved=resolved)
+    assert built == ["from_motifs"]
+    del built[:]
+    resolved = D.resolve_profile(avoid=["GGGG"], max_run=2, table="global")
+    with pytest.raises(RuntimeError, match="rnampnn_design_dfa_profile runs on an MI355X"):
+        D.design_profile_from_logits(torch.zeros(1, 8, 4), mask=torch.ones(1, 8), resolved=resolved)
+    assert built == ["from_avoid"] and resolved[0] == "avoid" and isinstance(resolved[2], M.DesignAutomaton)
 
 
 def test_without_table_every_refusal_stands_word_for_word():

@@ -11,6 +11,7 @@ Tolerances: the profile family's (include/rnampnn_hip.h) - marginals within 1e-8
 Each test prints the maxima it observed."""
 import csv
 import ctypes as C
+import functools
 import os
 import sys
 
@@ -29,14 +30,13 @@ import _design_avoid_ref as AR  # noqa: E402
 import _design_dfa_profile_ref as PR  # noqa: E402
 import _design_dfa_ref as R  # noqa: E402
 import _design_profile_ref as FR  # noqa: E402
-from _design_case import SMALL, raw_design, _bytes, _dev, _write_data, _checkpoint  # noqa: E402
+from _design_case import (SMALL, PROFILE_OUTPUTS as OUTPUTS, PROFILE_SCALARS as SCALARS, agree_profile, dfa_workspace, one_rna, profile_outputs, raw_design, raw_profile,  # noqa: E402
+                          same_profile, _bytes, _dev, _write_data, _checkpoint)
+from _design_case import design_dfa as _case_design_dfa  # noqa: E402
 
 LENGTHS, T, B = R.CASE_LENGTHS, R.CASE_T, len(R.CASE_LENGTHS)
 TOL = 1e-8
-OUTPUTS = ("marginals", "log_z", "log_z_free", "entropy", "infeasible", "miss")
-SCALARS = ("log_z", "log_z_free", "entropy")
 T_MAX = 4498                                                       # the largest T in 160 KiB of LDS (include/rnampnn_hip.h)
-DFA_FURTHER = (("hits", torch.int32, True), ("accepted", torch.int32, True), ("dfa_miss", torch.int32, False))
 LONG = "GGAGGCUUCGAAUUCGCAUGCCAUGGUACCUAGCUAGGAUCCGAUAUCAAGCUUGCGGCCGCUCGAGACGUCUGCAGCCCGGGAGAUCUGUCGACACUAGUUCUAGA"
 STATES_256 = ((LONG[:26], LONG[50:89]), (), None)                  # two long required words: exactly 256 states, all of them live
 
@@ -50,50 +50,24 @@ def _automaton(spec):
     return DesignAutomaton.from_motifs(*spec)
 
 
-def _outputs(Bn, Tn):
-    out = dict(marginals=torch.empty(Bn, Tn, 4, dtype=torch.float64, device="cuda"))
-    for k in SCALARS:
-        out[k] = torch.empty(Bn, dtype=torch.float64, device="cuda")
-    out["infeasible"], out["miss"] = (torch.empty(Bn, dtype=torch.int32, device="cuda") for _ in range(2))
-    return out
-
-
 def workspace(Bn, Tn, live, fill=None):
     from rnampnn import _native
-    need = int(_native.lib().rnampnn_design_dfa_profile_workspace_bytes(Bn, Tn, live))
-    assert need == 8 * Bn * Tn * live == int(_native.lib().rnampnn_design_dfa_workspace_bytes(Bn, Tn, live))
-    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
-    if fill is not None:
-        ws.fill_(fill)
+    ws = dfa_workspace("rnampnn_design_dfa_profile_workspace_bytes", Bn, Tn, live, fill=fill)
+    assert ws.numel() == int(_native.lib().rnampnn_design_dfa_workspace_bytes(Bn, Tn, live))
     return ws
 
 
-def dfa_profile(logits, delta, kind, mask=None, cu=None, T=None, temperature=1.0, allowed=None, bias=None, ws=None, out=None):
+def dfa_profile(logits, delta, kind, ws=None, **kw):
     """The C entry on device tensors (numpy arrays are uploaded; ``kind`` stays on the host) -> dict of its six outputs."""
-    from rnampnn import _native
-    from rnampnn.model._base import _ptr, _stream
     kind = torch.as_tensor(np.ascontiguousarray(kind), dtype=torch.uint8).contiguous()
-    lg, m, c = _dev(logits, torch.float32), _dev(mask, torch.float32), _dev(cu, torch.int32)
-    Bn = int(m.shape[0]) if m is not None else int(c.numel()) - 1
-    Tn = int(m.shape[1]) if m is not None else int(T)
-    al, bi, dl = _dev(allowed, torch.uint8), _dev(bias, torch.float32), _dev(delta, torch.uint8)
+    m, cu = kw.get("mask"), kw.get("cu")
+    Bn = int(m.shape[0]) if m is not None else int(cu.shape[0]) - 1
+    Tn = int(m.shape[1]) if m is not None else int(kw["T"])
     ws = workspace(Bn, Tn, int(((kind & 1) == 0).sum())) if ws is None else ws
-    out = _outputs(Bn, Tn) if out is None else out
-    _native.check(_native.lib().rnampnn_design_dfa_profile(
-        _ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(c), Bn, Tn, float(temperature), _ptr(al), None, 1, _ptr(bi),
-        int(bi is not None and bi.dim() == 3), _ptr(dl), _ptr(kind), int(kind.numel()), _ptr(ws), C.c_size_t(ws.numel()),
-        *[_ptr(out[k]) for k in OUTPUTS], _stream(lg.device)))
-    return out
+    return raw_profile("rnampnn_design_dfa_profile", (_dev(delta, torch.uint8), kind, int(kind.numel()), ws, C.c_size_t(ws.numel())), logits, **kw)
 
 
-def design_dfa(logits, delta, kind, seed=R.CASE_SEED, S=1, **kw):
-    from rnampnn import _native
-    kind = torch.as_tensor(np.ascontiguousarray(kind), dtype=torch.uint8).contiguous()
-    m = kw["mask"]
-    ws = torch.empty(int(_native.lib().rnampnn_design_dfa_workspace_bytes(int(m.shape[0]), int(m.shape[1]), int(((kind & 1) == 0).sum()))),
-                     dtype=torch.uint8, device="cuda")
-    return raw_design("rnampnn_design_dfa", (_dev(delta, torch.uint8), kind, int(kind.numel()), ws, C.c_size_t(ws.numel())), DFA_FURTHER, logits,
-                      seed=seed, S=S, **kw)
+design_dfa = functools.partial(_case_design_dfa, seed=R.CASE_SEED, S=1)
 
 
 @pytest.fixture(scope="module")
@@ -126,27 +100,13 @@ def _ref(case, name, temperature):
         h["logits"], LENGTHS, temperature, a.delta.numpy(), a.kind.numpy(), h["allowed"], h["bias"]))
 
 
-def _agree(out, ref, what, rows=None, flags=True):
-    """Device outputs within the tolerances of the reference's (a restatement's dict or another entry's outputs); prints the maxima."""
-    ref = {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in ref.items() if k in OUTPUTS}
-    rows = list(range(len(ref["log_z"]))) if rows is None else rows
-    got = {k: out[k].cpu().numpy() for k in OUTPUTS}
-    dm = float(np.abs(got["marginals"][rows] - ref["marginals"][rows]).max())
-    ds = {k: float((np.abs(got[k][rows] - ref[k][rows]) / np.maximum(1.0, np.abs(ref[k][rows]))).max()) for k in SCALARS}
-    print(f"{what}: max |dP| = {dm:.3e}, scalars relative to max(1, |value|): " + ", ".join(f"{k} {v:.3e}" for k, v in ds.items()))
-    assert dm <= TOL, what
-    assert all(v <= TOL for v in ds.values()), (what, ds)
-    if flags:
-        assert got["infeasible"][rows].tolist() == ref["infeasible"][rows].tolist() and got["miss"][rows].tolist() == ref["miss"][rows].tolist()
-
-
 # ---------------------------------------------------------------------------------------------------------------- the restatement
 @pytest.mark.parametrize("name", sorted(R.CASE_AUTOMATA))
 @pytest.mark.parametrize("temperature", [1.0, 0.3])
 def test_the_profile_equals_the_float64_restatement_and_the_draw_entrys_flags(case, name, temperature):
     out = _run(case, name, temperature)
     ref = _ref(case, name, temperature)
-    _agree(out, ref, f"{name}, temperature {temperature}")
+    agree_profile(out, ref, f"{name}, temperature {temperature}", tol=TOL)
     assert ref["miss"].tolist() == R.CASE_MISS and ref["infeasible"].tolist() == R.CASE_INFEASIBLE
     P = out["marginals"].cpu().numpy()
     for b, n in enumerate(LENGTHS):
@@ -174,12 +134,12 @@ def test_an_avoid_only_automaton_agrees_with_rnampnn_design_avoid_profile(name):
     dev = {k: _dev(h[k]) for k in ("logits", "mask", "allowed", "bias")}
     Bn, Tn = h["mask"].shape
     for temperature in (1.0, 0.3):
-        want = _outputs(Bn, Tn)
+        want = profile_outputs(Bn, Tn)
         _native.check(_native.lib().rnampnn_design_avoid_profile(
             _ptr(dev["logits"]), Bn * Tn, _ptr(dev["mask"]), None, Bn, Tn, float(temperature), _ptr(dev["allowed"]), None, 1, _ptr(dev["bias"]), 1,
             _ptr(auto.delta.cuda()), auto.n_states, C.c_uint64(auto.terminal), *[_ptr(want[k]) for k in OUTPUTS], _stream(dev["logits"].device)))
         out = dfa_profile(dev["logits"], auto.delta, kind, mask=dev["mask"], temperature=temperature, allowed=dev["allowed"], bias=dev["bias"])
-        _agree(out, want, f"anchor {name}, temperature {temperature}", flags=False)
+        agree_profile(out, want, f"anchor {name}, temperature {temperature}", flags=False, tol=TOL)
         assert _bytes(out["infeasible"]) == _bytes(want["infeasible"]) and _bytes(out["miss"]) == _bytes(want["miss"])
 
 
@@ -220,23 +180,19 @@ def test_the_frequencies_of_4096_draws_lie_within_six_sigma_of_the_profile(case)
 
 
 # ---------------------------------------------------------------------------------------------------------------- bytes
-def _same(a, b, rows=None):
-    return all(_bytes(a[k] if rows is None else a[k][rows]) == _bytes(b[k] if rows is None else b[k][rows]) for k in OUTPUTS)
-
-
 def test_bytes_do_not_depend_on_the_layout_a_second_call_stale_memory_or_a_graph(case):
     a = case["auto"]["two_run3"]
     delta = a.delta.cuda()                                          # (nothing is uploaded inside the capture)
     kw = dict(mask=case["mask"], temperature=0.3, allowed=case["allowed"], bias=case["bias"])
     padded = _run(case, "two_run3", 0.3)
-    assert _same(padded, _run(case, "two_run3", 0.3, "packed"))
-    assert _same(padded, dfa_profile(case["logits"], delta, a.kind, **kw))
-    out, ws = _outputs(B, T), workspace(B, T, a.n_live)
+    assert same_profile(padded, _run(case, "two_run3", 0.3, "packed"))
+    assert same_profile(padded, dfa_profile(case["logits"], delta, a.kind, **kw))
+    out, ws = profile_outputs(B, T), workspace(B, T, a.n_live)
     for t in list(out.values()) + [ws]:                             # a workspace and outputs of 0xFF bytes (NaN as doubles)
         t.view(torch.uint8).fill_(0xFF)
     dfa_profile(case["logits"], delta, a.kind, ws=ws, out=out, **kw)
-    assert _same(padded, out)
-    assert _same(padded, dfa_profile(case["logits"], delta, a.kind, ws=workspace(B + 1, T, a.n_live, fill=0x7F), **kw))
+    assert same_profile(padded, out)
+    assert same_profile(padded, dfa_profile(case["logits"], delta, a.kind, ws=workspace(B + 1, T, a.n_live, fill=0x7F), **kw))
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
         dfa_profile(case["logits"], delta, a.kind, ws=ws, out=out, **kw)
@@ -244,7 +200,7 @@ def test_bytes_do_not_depend_on_the_layout_a_second_call_stale_memory_or_a_graph
         t.view(torch.uint8).fill_(0xFF)
     graph.replay()
     torch.cuda.synchronize()
-    assert _same(padded, out)
+    assert same_profile(padded, out)
 
 
 def test_an_rna_alone_in_another_batch_and_a_nan_row_leave_the_bytes_unchanged(case):
@@ -270,24 +226,18 @@ def test_an_rna_alone_in_another_batch_and_a_nan_row_leave_the_bytes_unchanged(c
     nan[7, 100, 2] = float("inf")
     out = dfa_profile(nan, a.delta, a.kind, mask=case["mask"], temperature=0.3, allowed=case["allowed"], bias=case["bias"])
     torch.cuda.synchronize()
-    assert _same(out, base, [r for r in range(B) if r != 7])
+    assert same_profile(out, base, [r for r in range(B) if r != 7])
     assert not bool(out["marginals"][7, LENGTHS[7]:].any())         # the padding of the NaN row is still written as 0
 
 
 # ---------------------------------------------------------------------------------------------------------------- extent
-def _one_rna(n, seed):
-    rng = np.random.RandomState(seed)
-    logits = (3.0 * rng.standard_normal((1, n, 4))).astype(np.float32)
-    return logits, np.ones((1, n), dtype=np.float32)
-
-
 def test_an_automaton_of_256_states_runs_and_257_are_refused():
     import __graft_entry__ as g
     g.build()
     auto = _automaton(STATES_256)
     assert auto.n_states == 256 and auto.n_live == 256
     n = 120
-    logits, mask = _one_rna(n, 21)
+    logits, mask = one_rna(n, 21)
     seq = [["AUCG".index(ch) for ch in w] for w in STATES_256[0]]   # both words fixed into the RNA, so that it is feasible
     allowed = np.full((1, n), 15, dtype=np.uint8)
     allowed[0, 5:5 + len(seq[0])] = [1 << c for c in seq[0]]
@@ -295,7 +245,7 @@ def test_an_automaton_of_256_states_runs_and_257_are_refused():
     out = dfa_profile(logits, auto.delta, auto.kind, mask=mask, allowed=allowed)
     ref = PR.design_dfa_profile_ref(logits, [n], 1.0, auto.delta.numpy(), auto.kind.numpy(), allowed)
     assert ref["miss"].tolist() == [0]
-    _agree(out, ref, "256 states, T = 120")
+    agree_profile(out, ref, "256 states, T = 120", tol=TOL)
     kind257 = np.zeros(257, dtype=np.uint8)
     with pytest.raises(ValueError, match="n_states = 257, an automaton has 1 .. 256 states"):
         dfa_profile(logits, np.zeros((257, 4), dtype=np.uint8), kind257, mask=mask, ws=workspace(1, n, 256))
@@ -307,22 +257,22 @@ def test_the_largest_extent_and_one_past_it_and_t_1616_at_73_live_states():
     from rnampnn.utils.motifs import DesignAutomaton
     auto = DesignAutomaton.from_avoid((), 3)                       # 17 states, 13 live
     assert auto.n_live == 13 and _lds_bytes(T_MAX) <= 163840 < _lds_bytes(T_MAX + 1)
-    logits, mask = _one_rna(T_MAX, 14)
+    logits, mask = one_rna(T_MAX, 14)
     logits[0, :, 3] += 6.0
     out = dfa_profile(logits, auto.delta, auto.kind, mask=mask)
     ref = PR.design_dfa_profile_ref(logits, [T_MAX], 1.0, auto.delta.numpy(), auto.kind.numpy())
-    _agree(out, ref, f"T = {T_MAX}, 13 live states")
+    agree_profile(out, ref, f"T = {T_MAX}, 13 live states", tol=TOL)
     n = T_MAX + 1
     with pytest.raises(NotImplementedError, match=rf"rnampnn_design_dfa_profile: T = {n} needs {_lds_bytes(n)} bytes of LDS.*the limit is 163840 "
                                                   rf"\(T <= {T_MAX}; the table of partition sums is in the workspace"):
         dfa_profile(np.zeros((1, n, 4), dtype=np.float32), auto.delta, auto.kind, mask=np.ones((1, n), dtype=np.float32))
     auto = _automaton(R.CASE_AUTOMATA["two_run3"])
-    logits, mask = _one_rna(1616, 15)
+    logits, mask = one_rna(1616, 15)
     logits[0, :, 3] += 6.0
     out = dfa_profile(logits, auto.delta, auto.kind, mask=mask, temperature=0.5)
     ref = PR.design_dfa_profile_ref(logits, [1616], 0.5, auto.delta.numpy(), auto.kind.numpy())
     assert auto.n_live == 73 and ref["miss"].tolist() == [0]
-    _agree(out, ref, "T = 1616, 73 live states")
+    agree_profile(out, ref, "T = 1616, 73 live states", tol=TOL)
 
 
 # ---------------------------------------------------------------------------------------------------------------- refusals
@@ -336,7 +286,7 @@ def test_every_bad_argument_the_partner_and_the_all_null_call_launch_nothing(cas
     dead0[0] = 1
     ws = workspace(B, T, a.n_live)
     partner = torch.full((B, T), -1, dtype=torch.int32, device="cuda")
-    out = _outputs(B, T)
+    out = profile_outputs(B, T)
     BAD, UNSUPPORTED = 1, 2
 
     def ptr(v):
@@ -389,6 +339,33 @@ def test_every_bad_argument_the_partner_and_the_all_null_call_launch_nothing(cas
 
 # ---------------------------------------------------------------------------------------------------------------- the Python surface
 MODEL_LENGTHS = [33, 20, 41]
+RESOLVED_MODES = [dict(require=["GA"], max_run=2, table="global"), dict(avoid=["GAC"], max_run=2, table="lds"),
+                  dict(gc_content=(0.4, 0.6), tree="lds"), dict(gc_content=(0.4, 0.6), tree="global")]
+
+
+@pytest.mark.parametrize("own", RESOLVED_MODES, ids=["require-global", "avoid-lds", "gc-lds", "gc-global"])
+def test_the_resolved_call_path_returns_the_bytes_of_the_raw_arguments(own):
+    """``design_profile_from_logits`` on raw arguments and on ``resolve_profile``'s result (the path both models and the command line
+    take): the same bytes in all six outputs, B = 2, T = 12, lengths (12, 5), temperatures 1.0 and 0.3, both layouts."""
+    import __graft_entry__ as g
+    g.build()
+    from rnampnn.model.decode import design_profile_from_logits, resolve_profile
+    Tn, lengths = 12, (12, 5)
+    rng = np.random.RandomState(5)
+    logits = torch.from_numpy((3.0 * rng.standard_normal((2, Tn, 4))).astype(np.float32)).cuda()
+    mask = torch.tensor([[1.0] * n + [0.0] * (Tn - n) for n in lengths], device="cuda")
+    packed = torch.cat([logits[b, :n] for b, n in enumerate(lengths)])
+    cu = torch.tensor([0, 12, 17], dtype=torch.int32, device="cuda")
+    tree = own.get("tree", "lds")
+    resolved = resolve_profile(None, own.get("gc_content"), None, own.get("avoid"), tree, own.get("require"), own.get("table", "lds"),
+                               own.get("max_run"))
+    for temperature in (1.0, 0.3):
+        for lg, where in ((logits, dict(mask=mask)), (packed, dict(cu_seqlens=cu, max_len=Tn))):
+            raw = design_profile_from_logits(lg, temperature=temperature, **where, **own)
+            got = design_profile_from_logits(lg, temperature=temperature, gc_content=own.get("gc_content"), tree=tree, resolved=resolved, **where)
+            assert got.mode == raw.mode == resolved[0]
+            assert all(_bytes(getattr(got, k)) == _bytes(getattr(raw, k)) for k in OUTPUTS), (own, temperature, sorted(where))
+            assert bool((raw.marginals[1, 5:] == 0).all()) and abs(float(raw.marginals[0].sum()) - Tn) <= TOL * Tn
 
 
 def test_design_profile_from_logits_in_both_layouts_and_both_modes(case):
@@ -414,7 +391,7 @@ def test_design_profile_from_logits_in_both_layouts_and_both_modes(case):
         assert got.mode == "avoid" and all(_bytes(getattr(got, k)) == _bytes(want[k]) for k in OUTPUTS)
     lds = design_profile_from_logits(case["logits"], mask=case["mask"], temperature=0.3, constraints=cons,
                                      avoid=MotifAutomaton.from_motifs(["GGGG", "GAAUUC"], max_run=3))
-    _agree(want, {k: getattr(lds, k) for k in OUTPUTS}, "table=global against table=lds, avoid alone")      # to rounding, not to the byte
+    agree_profile(want, {k: getattr(lds, k) for k in OUTPUTS}, "table=global against table=lds, avoid alone", tol=TOL)      # to rounding, not to the byte
     with pytest.raises(NotImplementedError, match=rf"T = {T_MAX + 1} needs \d+ bytes of LDS.*\(T <= {T_MAX};"):
         design_profile_from_logits(torch.zeros(1, T_MAX + 1, 4, device="cuda"), mask=torch.ones(1, T_MAX + 1, device="cuda"), require=["GGAGG"],
                                    table="global")
@@ -489,7 +466,9 @@ def test_predict_cli_writes_the_profile_of_both_families(family, tmp_path, monke
     assert pos[0] == ["pdb_id", "position", "pA", "pU", "pC", "pG"] and rna[0] == ["pdb_id", "length", "log_mass", "entropy", "infeasible", "miss"]
     order = sorted(ids)
     assert [r[0] for r in rna[1:]] == order and [int(r[1]) for r in rna[1:]] == [lens[ids.index(i)] for i in order]
-    assert len(pos) == 1 + sum(lens) and len(seen) == 2 and all(p.mode == "require" and kw["table"] == "global" for p, kw in seen)
+    assert len(pos) == 1 + sum(lens) and len(seen) == 2 and all(p.mode == "require" and kw["resolved"][0] == "require" for p, kw in seen)
+    from rnampnn.utils.motifs import DesignAutomaton                # the global table's automaton, built once for the run's batches
+    assert isinstance(seen[0][1]["resolved"][2], DesignAutomaton) and seen[0][1]["resolved"][2] is seen[1][1]["resolved"][2]
     rows = {}
     for prof, _ in seen:
         lm, marg = prof.log_mass.cpu().tolist(), prof.marginals.cpu().numpy()

@@ -31,9 +31,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _design_count_ref as R  # noqa: E402
 import _design_gc_ref as G  # noqa: E402
 import _design_long_case as L  # noqa: E402
-import test_design_profile_gpu as TP  # noqa: E402  (its _agree holds the profile tolerances)
+import test_design_profile_gpu as TP  # noqa: E402  (its TOL is the profile tolerance, its count_profile the LDS entry)
 from _design_ref import PAIRS  # noqa: E402
-from _design_case import SMALL, raw_design, _bytes, _dev, _write_data  # noqa: E402
+from _design_case import SMALL, agree_profile, profile_outputs, raw_design, raw_profile, _bytes, _dev, _write_data  # noqa: E402
 
 NEAR = L.NEAR
 FURTHER = (("count", torch.int32, True), ("count_miss", torch.int32, False))
@@ -72,7 +72,7 @@ def profile_long(c, ws=None, layout="padded"):
     ws = _workspace("rnampnn_design_count_profile_long_workspace_bytes", c["B"], c["T"], c["cap"]) if ws is None else ws
     own = (_dev(c["counted"], torch.uint8), _dev(c["lo"], torch.int32), _dev(c["hi"], torch.int32), int(c["cap"]), *ws)
     kw = dict(mask=c["mask"]) if layout == "padded" else dict(cu=c["cu"], T=c["T"])
-    return TP._profile("rnampnn_design_count_profile_long", own, c["logits"] if layout == "padded" else c["packed"], allowed=c["allowed"],
+    return raw_profile("rnampnn_design_count_profile_long", own, c["logits"] if layout == "padded" else c["packed"], allowed=c["allowed"],
                        partner=c["partner"], wobble=c["wobble"], **kw)
 
 
@@ -199,7 +199,7 @@ def test_long_draws_equal_the_float64_restatement(built, name):
 def test_long_profiles_agree_with_the_float64_restatement(built, name):
     c = L.case(name)
     out = profile_long(c)
-    TP._agree(out, L.profile_ref(name), f"long profile {name}")
+    agree_profile(out, L.profile_ref(name), f"long profile {name}", tol=TP.TOL)
     marg = out["marginals"].cpu().numpy()
     for b, n in enumerate(c["lengths"]):
         assert (marg[b, n:] == 0).all() and np.allclose(marg[b, :n].sum(axis=1), 1.0, atol=1e-9)
@@ -270,7 +270,7 @@ def test_both_entries_replay_from_a_captured_graph_with_the_same_bytes(built):
     from _design_case import design_outputs
     c = L.case("mixed")
     base, pbase = _base("mixed"), profile_long(c)
-    out, pout = design_outputs(FURTHER, L.S, c["B"], c["T"]), TP._outputs(c["B"], c["T"])
+    out, pout = design_outputs(FURTHER, L.S, c["B"], c["T"]), profile_outputs(c["B"], c["T"])
     ws = _workspace("rnampnn_design_count_long_workspace_bytes", c["B"], c["T"], c["cap"])
     pws = _workspace("rnampnn_design_count_profile_long_workspace_bytes", c["B"], c["T"], c["cap"])
     dev = {k: _dev(c[k]) for k in ("logits", "mask", "allowed", "partner", "counted", "lo", "hi")}
@@ -278,7 +278,7 @@ def test_both_entries_replay_from_a_captured_graph_with_the_same_bytes(built):
     def both():
         count_long(dev["logits"], dev["counted"], dev["lo"], dev["hi"], c["cap"], ws=ws, mask=dev["mask"], allowed=dev["allowed"],
                    partner=dev["partner"], wobble=c["wobble"], out=out)
-        TP._profile("rnampnn_design_count_profile_long", (dev["counted"], dev["lo"], dev["hi"], int(c["cap"]), *pws), dev["logits"],
+        raw_profile("rnampnn_design_count_profile_long", (dev["counted"], dev["lo"], dev["hi"], int(c["cap"]), *pws), dev["logits"],
                     mask=dev["mask"], allowed=dev["allowed"], partner=dev["partner"], wobble=c["wobble"], out=pout)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())

@@ -8,6 +8,7 @@ draw whose path has a selection within 1e-8 of a cumulative boundary is left out
 capped at 5 %, the cap tests/test_design_nested_cpu.py holds the restatement alone to."""
 import csv
 import ctypes as C
+import functools
 import itertools
 import os
 import sys
@@ -25,14 +26,14 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import _design_dfa_ref as DF  # noqa: E402
 import _design_nested_ref as R  # noqa: E402
-from _design_case import SMALL, design_outputs, raw_design, _bytes, _dev, _write_data, _checkpoint  # noqa: E402
+from _design_case import SMALL, design_outputs, dfa_workspace, raw_design, _bytes, _dev, _write_data, _checkpoint  # noqa: E402
+from _design_case import design_dfa as _case_design_dfa  # noqa: E402
 from _design_ref import PAIRS  # noqa: E402
 
 LENGTHS, T, S, SEED = R.CASE_LENGTHS, R.CASE_T, R.CASE_S, R.CASE_SEED
 NEAR = 1e-8
 OUTPUTS = ("seqs", "seq_nll", "infeasible", "hits", "accepted", "dfa_miss", "nest_miss")
 FURTHER = (("hits", torch.int32, True), ("accepted", torch.int32, True), ("dfa_miss", torch.int32, False), ("nest_miss", torch.int32, False))
-DFA_FURTHER = FURTHER[:3]
 T_EDGE = 1616                                                      # the largest padded extent: 163,552 of 163,840 bytes of LDS
 
 
@@ -47,13 +48,7 @@ def _lds_bytes(t, live):
 
 
 def workspace(B, T, live, fill=None):
-    from rnampnn import _native
-    need = int(_native.lib().rnampnn_design_nested_workspace_bytes(B, T, live))
-    assert need == 8 * B * T * live * live + 256 * B * (T // 2 + 1)
-    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
-    if fill is not None:
-        ws.fill_(fill)
-    return ws
+    return dfa_workspace("rnampnn_design_nested_workspace_bytes", B, T, live, fill=fill, need=8 * B * T * live * live + 256 * B * (T // 2 + 1))
 
 
 def design_nested(logits, delta, kind, seed=SEED, S=S, ws=None, **kw):
@@ -68,15 +63,7 @@ def design_nested(logits, delta, kind, seed=SEED, S=S, ws=None, **kw):
                       seed=seed, S=S, **kw)
 
 
-def design_dfa(logits, delta, kind, seed=SEED, S=S, **kw):
-    from rnampnn import _native
-    kind = torch.as_tensor(np.ascontiguousarray(kind), dtype=torch.uint8).contiguous()
-    live = int(((kind & 1) == 0).sum())
-    m = kw["mask"]
-    need = int(_native.lib().rnampnn_design_dfa_workspace_bytes(int(m.shape[0]), int(m.shape[1]), live))
-    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
-    return raw_design("rnampnn_design_dfa", (_dev(delta, torch.uint8), kind, int(kind.numel()), ws, C.c_size_t(need)), DFA_FURTHER, logits,
-                      seed=seed, S=S, **kw)
+design_dfa = functools.partial(_case_design_dfa, seed=SEED, S=S)
 
 
 @pytest.fixture(scope="module")

@@ -290,7 +290,8 @@ def test_the_mode_mapping():
     auto = MotifAutomaton.from_motifs(["GGGG"])
     delta, n_states, terminal = D.profile_mode_args("avoid", B, T, "cpu", auto=auto)
     assert delta.tolist() == auto.delta.tolist() and n_states == 5 and terminal.value == 1 << 4
-    assert set(D.PROFILE_ENTRIES) == {"plain", "gc_content", "mutations", "avoid"}
+    assert set(D.PROFILE_ENTRIES) == {"plain", "gc_content", "mutations", "avoid", "require"}
+    assert D.PROFILE_ENTRIES["require"] == "rnampnn_design_dfa_profile" and D.profile_entry("avoid", auto) == "rnampnn_design_avoid_profile"
     assert D.PROFILE_ENTRIES["avoid"] == "rnampnn_design_avoid_profile" and D.PROFILE_ENTRIES["gc_content"] == "rnampnn_design_count_profile"
     with pytest.raises(ValueError, match="no profile is built for the mode 'distinct'"):
         D.profile_mode_args("distinct", B, T, "cpu")

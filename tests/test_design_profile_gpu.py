@@ -28,65 +28,27 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _design_avoid_ref as AR  # noqa: E402
 import _design_count_ref as CR  # noqa: E402
 import _design_profile_ref as PR  # noqa: E402
-from _design_case import SMALL, raw_design, _bytes, _dev, _write_data, _checkpoint  # noqa: E402
+from _design_case import (SMALL, PROFILE_OUTPUTS as OUTPUTS, PROFILE_SCALARS as SCALARS, agree_profile, one_rna, profile_outputs, raw_design,  # noqa: E402
+                          raw_profile, same_profile, _bytes, _dev, _write_data, _checkpoint)
 
 LENGTHS, T = CR.CASE_LENGTHS, CR.CASE_T
 TOL = 1e-8
-OUTPUTS = ("marginals", "log_z", "log_z_free", "entropy", "infeasible", "miss")
-SCALARS = ("log_z", "log_z_free", "entropy")
 T_MAX_CAP8, T_MAX_UNCAPPED, T_MAX_RUN3, T_MAX_64 = 1457, 535, 1168, 293      # the largest T in 160 KiB of LDS (include/rnampnn_hip.h)
 
 
-def _outputs(B, T):
-    out = dict(marginals=torch.empty(B, T, 4, dtype=torch.float64, device="cuda"))
-    for k in SCALARS:
-        out[k] = torch.empty(B, dtype=torch.float64, device="cuda")
-    out["infeasible"], out["miss"] = (torch.empty(B, dtype=torch.int32, device="cuda") for _ in range(2))
-    return out
-
-
-def _profile(entry, own, logits, mask=None, cu=None, T=None, temperature=1.0, allowed=None, partner=None, wobble=True, bias=None, out=None):
-    """The C entry ``entry`` on device tensors (numpy arrays are uploaded) -> dict of its six outputs."""
-    from rnampnn import _native
-    from rnampnn.model._base import _ptr, _stream
-    lg, m, c = _dev(logits, torch.float32), _dev(mask, torch.float32), _dev(cu, torch.int32)
-    B = int(m.shape[0]) if m is not None else int(c.numel()) - 1
-    T = int(m.shape[1]) if m is not None else int(T)
-    al, pa, bi = _dev(allowed, torch.uint8), _dev(partner, torch.int32), _dev(bias, torch.float32)
-    out = _outputs(B, T) if out is None else out
-    _native.check(getattr(_native.lib(), entry)(
-        _ptr(lg), int(lg.numel()) // 4, _ptr(m), _ptr(c), B, T, float(temperature), _ptr(al), _ptr(pa), int(wobble), _ptr(bi),
-        int(bi is not None and bi.dim() == 3), *[_ptr(v) if torch.is_tensor(v) else v for v in own], *[_ptr(out[k]) for k in OUTPUTS],
-        _stream(lg.device)))
-    return out
-
-
 def count_profile(logits, counted, lo, hi, cap, wobble=CR.CASE_WOBBLE, **kw):
-    return _profile("rnampnn_design_count_profile", (_dev(counted, torch.uint8), _dev(lo, torch.int32), _dev(hi, torch.int32), int(cap)), logits,
+    return raw_profile("rnampnn_design_count_profile", (_dev(counted, torch.uint8), _dev(lo, torch.int32), _dev(hi, torch.int32), int(cap)), logits,
                     wobble=wobble, **kw)
 
 
 def avoid_profile(logits, delta, n_states, terminal, **kw):
-    return _profile("rnampnn_design_avoid_profile", (_dev(delta, torch.uint8), int(n_states), C.c_uint64(int(terminal))), logits, **kw)
+    return raw_profile("rnampnn_design_avoid_profile", (_dev(delta, torch.uint8), int(n_states), C.c_uint64(int(terminal))), logits, **kw)
 
 
 def _automaton(name):
     from rnampnn.utils.motifs import MotifAutomaton
     motifs, max_run = AR.CASE_AUTOMATA[name]
     return MotifAutomaton.from_motifs(motifs, max_run=max_run)
-
-
-def _agree(out, ref, what, rows=None):
-    """Device outputs within the tolerances of the restatement's; prints and returns the observed maxima."""
-    rows = list(range(len(ref["log_z"]))) if rows is None else rows
-    got = {k: out[k].cpu().numpy() for k in OUTPUTS}
-    dm = float(np.abs(got["marginals"][rows] - ref["marginals"][rows]).max())
-    ds = {k: float((np.abs(got[k][rows] - ref[k][rows]) / np.maximum(1.0, np.abs(ref[k][rows]))).max()) for k in SCALARS}
-    print(f"{what}: max |dP| = {dm:.3e}, scalars relative to max(1, |value|): " + ", ".join(f"{k} {v:.3e}" for k, v in ds.items()))
-    assert dm <= TOL, what
-    assert all(v <= TOL for v in ds.values()), (what, ds)
-    assert got["infeasible"][rows].tolist() == ref["infeasible"][rows].tolist() and got["miss"][rows].tolist() == ref["miss"][rows].tolist()
-    return dm, ds
 
 
 @pytest.fixture(scope="module")
@@ -158,7 +120,7 @@ def _avoid_ref(case, name, temperature):
 def test_count_profile_equals_the_float64_restatement_and_the_draw_entrys_flags(count_case, temperature, cap, variant):
     out = _count_run(count_case, temperature, cap, variant)
     ref = _count_ref(temperature, cap, variant)
-    _agree(out, ref, f"count, temperature {temperature}, cap {cap}, {variant}")
+    agree_profile(out, ref, f"count, temperature {temperature}, cap {cap}, {variant}", tol=TOL)
     P = out["marginals"].cpu().numpy()
     for b, n in enumerate(LENGTHS):
         assert not P[b, n:].any() and (n == 0 or np.abs(P[b, :n].sum(axis=1) - 1.0).max() <= TOL)
@@ -178,7 +140,7 @@ def test_count_profile_equals_the_float64_restatement_and_the_draw_entrys_flags(
 def test_avoid_profile_equals_the_float64_restatement_and_the_draw_entrys_flags(avoid_case, name, temperature):
     out = _avoid_run(avoid_case, name, temperature)
     ref = _avoid_ref(avoid_case, name, temperature)
-    _agree(out, ref, f"avoid, {name}, temperature {temperature}")
+    agree_profile(out, ref, f"avoid, {name}, temperature {temperature}", tol=TOL)
     assert ref["miss"].tolist() == AR.CASE_MISS and ref["infeasible"].tolist() == AR.CASE_INFEASIBLE
     P = out["marginals"].cpu().numpy()
     for b, n in enumerate(LENGTHS):
@@ -204,7 +166,7 @@ def test_the_frequencies_of_4096_draws_lie_within_six_sigma_of_the_profile(built
         from rnampnn.utils.motifs import MotifAutomaton
         a = MotifAutomaton.from_motifs(list(PR.LINK_AVOID[0]), max_run=PR.LINK_AVOID[1])
         own = (a.delta.cuda(), a.n_states, C.c_uint64(a.terminal))
-        prof = _profile("rnampnn_design_avoid_profile", own, h["logits"], **kw)
+        prof = raw_profile("rnampnn_design_avoid_profile", own, h["logits"], **kw)
         draw = raw_design("rnampnn_design_avoid", own, (("hits", torch.int32, True), ("avoid_miss", torch.int32, False)), h["logits"], S=S,
                           seed=PR.LINK_SEED, **kw)
     else:
@@ -215,7 +177,7 @@ def test_the_frequencies_of_4096_draws_lie_within_six_sigma_of_the_profile(built
             own = (_dev(CR.mutation_sets(h["reference"])), _dev(np.full(B, PR.LINK_BUDGET[0], dtype=np.int32)),
                    _dev(np.full(B, PR.LINK_BUDGET[1], dtype=np.int32)), PR.LINK_BUDGET[1])
         kw.update(partner=h["partner"])
-        prof = _profile("rnampnn_design_count_profile", own, h["logits"], **kw)
+        prof = raw_profile("rnampnn_design_count_profile", own, h["logits"], **kw)
         draw = raw_design("rnampnn_design_count", own, (("count", torch.int32, True), ("count_miss", torch.int32, False)), h["logits"], S=S,
                           seed=PR.LINK_SEED, **kw)
     P = prof["marginals"].cpu().numpy()
@@ -228,10 +190,6 @@ def test_the_frequencies_of_4096_draws_lie_within_six_sigma_of_the_profile(built
 
 
 # ---------------------------------------------------------------------------------------------------------------- bytes
-def _same(a, b, rows=None):
-    return all(_bytes(a[k] if rows is None else a[k][rows]) == _bytes(b[k] if rows is None else b[k][rows]) for k in OUTPUTS)
-
-
 def test_bytes_do_not_depend_on_the_layout_the_batch_a_second_call_stale_outputs_or_a_graph(count_case, avoid_case):
     a = avoid_case["auto"]["overlap"]
     delta = a.delta.cuda()                                          # (nothing is uploaded inside the capture)
@@ -243,13 +201,13 @@ def test_bytes_do_not_depend_on_the_layout_the_batch_a_second_call_stale_outputs
                                              allowed=avoid_case["allowed"], bias=avoid_case["bias"], **kw),
          _avoid_run(avoid_case, "overlap", 0.3), _avoid_run(avoid_case, "overlap", 0.3, "packed"))]
     for what, call, padded, packed in runs:
-        assert _same(padded, packed), what                          # the packed layout
-        out = _outputs(len(LENGTHS), T)
+        assert same_profile(padded, packed), what                          # the packed layout
+        out = profile_outputs(len(LENGTHS), T)
         for fill in (-7, 99):                                       # a second call, stale outputs overwritten (padding rows included)
             for t in out.values():
                 t.fill_(fill)
             call(out=out)
-            assert _same(padded, out), (what, fill)
+            assert same_profile(padded, out), (what, fill)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             call(out=out)
@@ -257,7 +215,7 @@ def test_bytes_do_not_depend_on_the_layout_the_batch_a_second_call_stale_outputs
             t.fill_(-7)
         graph.replay()
         torch.cuda.synchronize()
-        assert _same(padded, out), what
+        assert same_profile(padded, out), what
 
 
 def test_an_rna_alone_in_another_batch_and_a_nan_row_leave_the_bytes_unchanged(count_case, avoid_case):
@@ -300,7 +258,7 @@ def test_an_rna_alone_in_another_batch_and_a_nan_row_leave_the_bytes_unchanged(c
         else:
             out = avoid_profile(nan, a.delta, a.n_states, a.terminal, mask=case["mask"], temperature=0.3, allowed=case["allowed"], bias=case["bias"])
         torch.cuda.synchronize()
-        assert _same(out, base, rows), what
+        assert same_profile(out, base, rows), what
         assert not bool(out["marginals"][7, LENGTHS[7]:].any())      # the padding of the NaN row is still written as 0
 
 
@@ -324,20 +282,15 @@ def test_the_plain_mode_equals_the_gc_mode_with_the_window_0_1(built):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the LDS edges
-def _one_rna(n, seed):
-    rng = np.random.RandomState(seed)
-    return (3.0 * rng.standard_normal((1, n, 4))).astype(np.float32), np.ones((1, n), dtype=np.float32)
-
-
 @pytest.mark.parametrize("cap, n", [(8, T_MAX_CAP8), (1 << 20, T_MAX_UNCAPPED)])
 def test_the_largest_extent_of_the_count_profile_and_one_past_it(built, cap, n):
-    logits, mask = _one_rna(n, 12)
+    logits, mask = one_rna(n, 12)
     ref_seq = np.random.RandomState(13).randint(0, 4, size=(1, n))
     counted = CR.mutation_sets(ref_seq) if cap == 8 else np.full((1, n), 12, dtype=np.uint8)
     lo, hi = ([2], [8]) if cap == 8 else ([n // 2 - 5], [n // 2 + 5])
     out = count_profile(logits, counted, np.array(lo, dtype=np.int32), np.array(hi, dtype=np.int32), cap, mask=mask)
     ref = PR.design_count_profile_ref(logits, [n], 1.0, counted, lo, hi, min(cap, n), wobble=CR.CASE_WOBBLE)
-    _agree(out, ref, f"count, T = {n}, cap {cap}")
+    agree_profile(out, ref, f"count, T = {n}, cap {cap}", tol=TOL)
     with pytest.raises(NotImplementedError, match=rf"T = {n + 1} at count_cap = {cap} needs \d+ bytes of LDS.*the limit is 163840 \(T <= {n} at that cap\)"):
         count_profile(np.zeros((1, n + 1, 4), dtype=np.float32), np.zeros((1, n + 1), dtype=np.uint8), [0], [0], cap,
                       mask=np.ones((1, n + 1), dtype=np.float32))
@@ -351,11 +304,11 @@ def test_the_largest_extent_of_the_avoid_profile_and_one_past_it(built, live, n)
     else:                                                          # 64 live states: a counter of the position modulo 64 that also reads the class
         delta = np.array([[(s + 1 + c) % 64 for c in range(4)] for s in range(64)], dtype=np.uint8)
         n_states, terminal = 64, 0
-    logits, mask = _one_rna(n, 14)
+    logits, mask = one_rna(n, 14)
     logits[0, :, 3] += 6.0
     out = avoid_profile(logits, delta, n_states, terminal, mask=mask)
     ref = PR.design_avoid_profile_ref(logits, [n], 1.0, delta, terminal)
-    _agree(out, ref, f"avoid, T = {n}, {live} live states")
+    agree_profile(out, ref, f"avoid, T = {n}, {live} live states", tol=TOL)
     with pytest.raises(NotImplementedError, match=rf"T = {n + 1} with {live} live states needs \d+ bytes of LDS.*the limit is 163840 \(T <= {n} at this automaton\)"):
         avoid_profile(np.zeros((1, n + 1, 4), dtype=np.float32), delta, n_states, terminal, mask=np.ones((1, n + 1), dtype=np.float32))
 
@@ -369,7 +322,7 @@ def test_every_bad_argument_and_the_partner_of_the_avoid_profile_launch_nothing(
     a = avoid_case["auto"]["max_run3"]
     delta = a.delta.cuda()
     partner = torch.full((B, T), -1, dtype=torch.int32, device="cuda")
-    out = _outputs(B, T)
+    out = profile_outputs(B, T)
     BAD, UNSUPPORTED = 1, 2
 
     def ptr(v):

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Every output of the design wrappers on the batches of the GPU tests, as .npy files: the byte comparison of two builds of the library
 (docs/experiments.md, "the design family folded").  Plain dumping - no timing, no profiler, no retry.
-usage: python tools/design_dump.py <outdir>            one child process per family (design tied gc count distinct avoid profile), each under its own
+usage: python tools/design_dump.py <outdir>            one child process per family (design tied gc count distinct avoid profile dfa nested
+                                                       chain dfa_profile), each under its own
                                                        `timeout`, stopping at the first that fails; then the number of dumps, their size
                                                        and one sha256 over all of them
        python tools/design_dump.py <outdir> <family>   that family, in this process
@@ -12,7 +13,10 @@ Per family the `host_case()` / `case_arrays()` batch of its GPU test file, every
 0.3 and 1e-3, the padded and the packed layout, the file's seed (above 2^32); tied: STATES with its weights and one state per group;
 gc: the case's windows as fractions, 40..60 % and the free window; count: caps 8 and T; distinct: S = 8 and 64, "sample" and "best";
 avoid: every automaton of CASE_AUTOMATA under the case's sets and bias, and free; profile: the six outputs of `design_profile_from_logits`
-in the modes plain / gc_content / mutations on the count batch and avoid on the avoid batch.
+in the modes plain / gc_content / mutations on the count batch (the latter two with the tree in LDS and in global memory) and avoid on
+the avoid batch; dfa, nested, chain: every automaton of the file's CASE_AUTOMATA under the case's constraints (nested: the structure
+included; chain: a G+C window and the two mutation budgets of CASE_SIDES); dfa_profile: the six outputs under `table="global"` for every
+automaton of the dfa batch and for the avoid batch's automata.
 With every set of draws the `seq_nll` that `score_logits` gives for it."""
 import hashlib
 import os
@@ -21,7 +25,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.environ.get("RNAMPNN_PROBE_ROOT") or os.path.join(HERE, "..")
-FAMILIES = ("design", "tied", "gc", "count", "distinct", "avoid", "profile")
+FAMILIES = ("design", "tied", "gc", "count", "distinct", "avoid", "profile", "dfa", "nested", "chain", "dfa_profile")
 TEMPERATURES = (1.0, 0.3, 1e-3)
 
 
@@ -128,7 +132,8 @@ def dump_family(outdir: str, family: str) -> None:
         six = ("marginals", "log_z", "log_z_free", "entropy", "infeasible", "miss")
         h, ha = R.case_arrays(), A.case_arrays()
         reference = torch.from_numpy(h["reference"]).cuda()
-        modes = {"plain": dict(), "gc_content": dict(gc_content=(0.4, 0.6)), "mutations": dict(mutations=(reference, 0, 8))}
+        modes = {"plain": dict(), "gc_content": dict(gc_content=(0.4, 0.6)), "mutations": dict(mutations=(reference, 0, 8)),
+                 "gc_content_long": dict(gc_content=(0.4, 0.6), tree="global"), "mutations_long": dict(mutations=(reference, 0, 8), tree="global")}
         variants = {"cons": constraints(h, None, R.CASE_WOBBLE), "wobble": constraints(h, None, True), "free": None}
         for vname, cons in variants.items():
             for mname, mkw in modes.items():
@@ -143,6 +148,40 @@ def dump_family(outdir: str, family: str) -> None:
                     for lname, kw in layouts(ha, A.CASE_T):
                         out = D.design_profile_from_logits(temperature=temperature, constraints=cons, avoid=auto, **kw)
                         save(f"avoid.{vname}.{aname}.t{temperature:g}.{lname}", six, out[:6])
+    elif family in ("dfa", "nested", "chain"):
+        from rnampnn.utils.motifs import DesignAutomaton, as_nested_automaton
+        R = __import__({"dfa": "_design_dfa_ref", "nested": "_design_nested_ref", "chain": "_design_dfa_count_ref"}[family])
+        h = R.case_arrays()
+        partner = torch.from_numpy(h["partner"]) if family == "nested" else None
+        cons = DesignConstraints(torch.from_numpy(h["allowed"]), partner, torch.from_numpy(h["bias"]), True).to_device("cuda")
+        further = {"dfa": ("hits", "accepted", "dfa_miss"), "nested": ("hits", "accepted", "dfa_miss", "nest_miss"),
+                   "chain": ("hits", "accepted", "count", "dfa_miss", "count_miss", "log_z")}[family]
+        sides = {"draw": dict()}
+        if family == "chain":
+            reference = torch.from_numpy(h["reference"]).cuda()
+            sides = {"gc": dict(gc_content=(0.4, 0.6)), "mut4": dict(mutations=(reference, (0, 4))), "mut2_6": dict(mutations=(reference, (2, 6)))}
+        call = {"dfa": D.design_dfa_from_logits, "nested": D.design_nested_from_logits, "chain": D.design_dfa_count_from_logits}[family]
+        for aname, (require, avoid, max_run) in R.CASE_AUTOMATA.items():
+            auto = DesignAutomaton.from_motifs(require, avoid, max_run) if family == "dfa" else as_nested_automaton(require or None, avoid or None, max_run)
+            for temperature in TEMPERATURES:
+                for lname, kw in layouts(h, R.CASE_T):
+                    for sname, skw in sides.items():
+                        out = call(n_samples=R.CASE_S, temperature=temperature, seed=R.CASE_SEED, constraints=cons, require=auto, **skw, **kw)
+                        save(f"{aname}.t{temperature:g}.{lname}.{sname}", triple + further, out, kw)
+    elif family == "dfa_profile":
+        import _design_avoid_ref as A
+        import _design_dfa_ref as R
+        from rnampnn.utils.motifs import DesignAutomaton
+        six = ("marginals", "log_z", "log_z_free", "entropy", "infeasible", "miss")
+        for bname, B, autos in (("require", R, {n: dict(require=DesignAutomaton.from_motifs(*spec)) for n, spec in R.CASE_AUTOMATA.items()}),
+                                ("avoid", A, {n: dict(avoid=a) for n, a in automata(A).items()})):
+            h = B.case_arrays()
+            cons = DesignConstraints(torch.from_numpy(h["allowed"]), None, torch.from_numpy(h["bias"]), True).to_device("cuda")
+            for aname, akw in autos.items():
+                for temperature in TEMPERATURES:
+                    for lname, kw in layouts(h, B.CASE_T):
+                        out = D.design_profile_from_logits(temperature=temperature, constraints=cons, table="global", **akw, **kw)
+                        save(f"{bname}.{aname}.t{temperature:g}.{lname}", six, out[:6])
     else:
         raise SystemExit(f"unknown family {family!r}: choose from {FAMILIES}")
     torch.cuda.synchronize()
